@@ -2,12 +2,13 @@
 """Headline benchmark (BASELINE.json): LR->HR images/s of ESPCN x4 inference (config c2:
 256x256 LR, batch 64 per GPU, fp32) on N MI355X GPUs, printed as ONE JSON line by rank 0.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is one forward pass of the hot path over one synthetic batch that is already resident in
 HBM.  Inference replicas share nothing, so N GPUs = N independent shards of the image stream
-(weak scaling, no data-path collective).  The same JSON line also carries
+(weak scaling, no data-path collective).  A plain run measures the headline alone; --dump-outputs DIR
+writes what the last timed step returned (see dump_outputs).  With --full the same JSON line also carries
   * roofline      — the dominant kernel (conv 64->32, 3x3) timed live with HIP events on the launch
                     stream, against the fp32 MFMA peak, plus the whole-net HBM-roofline fraction
                     the north star quotes (61.11 MB compulsory traffic per image);
@@ -52,12 +53,20 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64, help="LR images per GPU per step (c2: 64)")
     ap.add_argument("--lr-size", type=int, default=256)
-    ap.add_argument("--no-extra", action="store_true", help="skip the c3/c4 training side metrics")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: per-layer roofline, the c2 side figures, the "
+                         "c1/c3/c4/c5 training metrics and the CPU baselines (a plain run prints the headline alone)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the side metrics under `extra`")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--extra-steps", type=int, default=20, help="timed steps of every side metric (after 5 warm-ups)")
     ap.add_argument("--precision", default="mixed", choices=["mixed", "bf16x3", "bf16x6", "fp32"],
                     help="conv arithmetic (ops.set_precision); inference uses bf16x3 unless 'fp32'")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned to DIR/*.npy (float32, at most 64 MB; see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 _JSON_FD = [None]
@@ -129,15 +138,61 @@ def rccl_ranks_seen(dev):
     return int(round(float(one.item())))
 
 
-def time_steps(fn, steps, warmup, world, dev):
+def time_steps(fn, steps, warmup, world, dev, last=None):
+    """Seconds of `steps` calls of fn after `warmup` untimed ones (slowest rank).  `last` (a list) receives what the last
+    timed call returned; every earlier result is dropped as soon as its call returns."""
     for _ in range(warmup):
         fn()
     barrier_sync(world)
     t0 = time.perf_counter()
-    for _ in range(steps):
+    for _ in range(steps - 1):
         fn()
+    y = fn()
     barrier_sync(world)
-    return max_over_ranks(time.perf_counter() - t0, world, dev)
+    sec = max_over_ranks(time.perf_counter() - t0, world, dev)
+    if last is not None:
+        last.append(y)
+    return sec
+
+
+# --dump-outputs: the whole output when it fits in this many bytes, else a fixed, seeded choice of whole images
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, y):
+    """DIR/espcn_x4_hr.npy: the HR images [n, 3, 4(H-8), 4(W-8)] (float32, NCHW) the timed forward returned in its last
+    step.  At the default size the batch (755 MB) is over DUMP_BYTES, so n whole images are written, chosen by a
+    generator seeded with 0 (the same ones in every run with the same --batch and --lr-size).  Rank 0 only."""
+    per_img = y[0].numel() * 4
+    n = min(y.shape[0], DUMP_BYTES // per_img)
+    if n < 1:
+        raise SystemExit("--dump-outputs: one output image is %d bytes, over the %d byte cap" % (per_img, DUMP_BYTES))
+    idx = torch.randperm(y.shape[0], generator=torch.Generator().manual_seed(0))[:n].sort().values
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "espcn_x4_hr.npy"), y[idx.to(y.device)].float().cpu().numpy())
+    sys.stderr.write("bench: wrote %s/espcn_x4_hr.npy = images %s of the last timed batch\n" % (out_dir, idx.tolist()))
+
+
+def measured_copy_gbps(dev):
+    """Measured device-to-device copy bandwidth on this box (read + write bytes / time), beside the vendor peak."""
+    try:
+        a = torch.empty(256 * 1024 * 1024, dtype=torch.float32, device=dev)
+        b = torch.empty_like(a)
+        for _ in range(2):
+            b.copy_(a)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(5):
+            b.copy_(a)
+        e1.record()
+        torch.cuda.synchronize()
+        gbps = round(2 * a.numel() * 4 * 5 / (e0.elapsed_time(e1) * 1e-3) / 1e9, 1)
+        del a, b
+        torch.cuda.empty_cache()
+        return gbps
+    except Exception:  # noqa: BLE001
+        return None
 
 
 def espcn_layer_events(net, x, steps, discard=0):
@@ -800,47 +855,26 @@ def main():
     # The per-layer HIP events (40 forwards, the last 10 averaged) run BEFORE the timed window: behind an idle gap the clock
     # governor takes ~50 steps of this workload to settle (tools/c2_ramp.py: steps 5 - 24 behind 2 s of idle 1.11 ms, steps
     # 50+ 1.01 ms), so W = 5 warm-up steps alone would leave the whole timed window -- and the layer times -- inside that ramp.
-    # Disclosed in the line: extra.c2_cold_window_ms_per_step is the same W + K window behind 2 s of idle,
+    # A plain run needs these forwards for its window too; only --full reports the layer times (`roofline`) and discloses the
+    # ramp: extra.c2_cold_window_ms_per_step is the same W + K window behind 2 s of idle,
     # extra.c2_power_probe.ms_per_step_while_sampling the rate sustained over seconds.
     pkg.trainers.quiesce_gc()   # set-up is done: no full cyclic collection (~80 ms with torch loaded) inside a timed window
     layer_ms, layer_kernels = espcn_layer_events(net, xs, max(3, min(args.steps, 10)), discard=30)
-    sec = time_steps(step, args.steps, args.warmup, world, dev)
+    last = []
+    sec = time_steps(step, args.steps, args.warmup, world, dev, last)
     imgs_per_s = world * args.batch * args.steps / sec
-    ranks_seen = rccl_ranks_seen(dev)
-    local_span = span_over_ranks(rank_local_steps(step, args.steps, 1, dev) / args.steps, world, dev)
-
-    # measured device-to-device copy bandwidth on this box (read + write bytes / time), beside the vendor peak
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last[0])
+    del last[:]
     copy_gbps = None
-    try:
-        a = torch.empty(256 * 1024 * 1024, dtype=torch.float32, device=dev)
-        b = torch.empty_like(a)
-        for _ in range(2):
-            b.copy_(a)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(5):
-            b.copy_(a)
-        e1.record()
-        torch.cuda.synchronize()
-        copy_gbps = round(2 * a.numel() * 4 * 5 / (e0.elapsed_time(e1) * 1e-3) / 1e9, 1)
-        del a, b
-        torch.cuda.empty_cache()
-    except Exception:  # noqa: BLE001
-        pass
+    if args.full:
+        ranks_seen = rccl_ranks_seen(dev)
+        local_span = span_over_ranks(rank_local_steps(step, args.steps, 1, dev) / args.steps, world, dev)
+        copy_gbps = measured_copy_gbps(dev)
 
     result = None
     if rank == 0:
         H = args.lr_size
-        flop_l2 = 2.0 * args.batch * (H - 6) ** 2 * 32 * 64 * 9
-        dom = max(range(3), key=lambda i: layer_ms[i])
-        bf3 = pkg.ops.get_precision() != "fp32"
-        what = ["conv5x5 3->64 + ReLU", "conv3x3 64->32 + ReLU", "conv3x3 32->48 + pixel-shuffle store"]
-        names = ["%s %s" % (k, w) for k, w in zip(layer_kernels, what)]   # kernel ids come from the dispatcher
-        peak = BF16X3_PEAK_TFLOPS if bf3 else FP32_MFMA_PEAK_TFLOPS
-        flops = [2.0 * args.batch * (H - 4) ** 2 * 64 * 3 * 25, flop_l2, 2.0 * args.batch * (H - 8) ** 2 * 48 * 32 * 9]
-        achieved = flops[dom] / (layer_ms[dom] * 1e-3) / 1e12
-        scale = (H / 256.0) ** 2
-        traffic, traffic_source = pmc_traffic(names[dom], args.batch, H)   # (a committed rocprofv3 pass, not this run)
         result = {
             "metric": "ESPCN x4 LR->HR images/sec (infer)", "value": round(imgs_per_s, 1), "unit": "images/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -852,28 +886,40 @@ def main():
                                    % (H, H, args.batch),
                        "timing": "W warm-up + K timed forwards, barrier + synchronize on both sides; 40 forwards of per-layer "
                                  "event timing run in front of the window (the clock governor needs ~50 forwards from idle: "
-                                 "extra.c2_cold_window_* is the same window behind 2 s of idle)",
+                                 "with --full, extra.c2_cold_window_* is the same window behind 2 s of idle)",
                        "untimed_forwards_before_window": 1 + 40 + args.warmup,
                        "input": "3 resident batches in rotation, a new tensor object per forward: the first layer's |x| "
                                 "maximum pass runs inside every timed forward",
                        "parallelism": "replicas x%d (no collective)" % world},
-            "roofline": {"bound": "mfma", "kernel": names[dom], "achieved": round(achieved, 2),
-                         "peak": round(peak, 1), "unit": "TFLOP/s",
-                         "frac": round(achieved / peak, 4),
-                         "traffic": traffic, "traffic_source": traffic_source,
-                         "note": "achieved = algorithmic conv FLOPs / live HIP-event kernel time; peak = dense 16-bit "
-                                 "MFMA peak / 3 (three fp16 / bf16 MFMAs per fp32-equivalent product)" if bf3 else
-                                 "achieved = algorithmic conv FLOPs / live HIP-event kernel time; peak = fp32 MFMA",
-                         "kernel_ms": round(layer_ms[dom], 4),
-                         "layer_ms": [round(m, 4) for m in layer_ms], "layer_kernels": names,
-                         "whole_net_hbm": {
-                             "achieved_GBps": round(ESPCN_BYTES_PER_IMG * scale * imgs_per_s / world / 1e9, 1),
-                             "peak_GBps": HBM_PEAK_GBS, "measured_copy_GBps": copy_gbps,
-                             "frac": round(ESPCN_BYTES_PER_IMG * scale * imgs_per_s / world / 1e9 / HBM_PEAK_GBS, 4),
-                             "note": "61.11 MB/img per-layer compulsory traffic (SURVEY.md 8d); north-star target 0.30"}},
         }
+        if args.full:
+            flop_l2 = 2.0 * args.batch * (H - 6) ** 2 * 32 * 64 * 9
+            dom = max(range(3), key=lambda i: layer_ms[i])
+            bf3 = pkg.ops.get_precision() != "fp32"
+            what = ["conv5x5 3->64 + ReLU", "conv3x3 64->32 + ReLU", "conv3x3 32->48 + pixel-shuffle store"]
+            names = ["%s %s" % (k, w) for k, w in zip(layer_kernels, what)]   # kernel ids come from the dispatcher
+            peak = BF16X3_PEAK_TFLOPS if bf3 else FP32_MFMA_PEAK_TFLOPS
+            flops = [2.0 * args.batch * (H - 4) ** 2 * 64 * 3 * 25, flop_l2, 2.0 * args.batch * (H - 8) ** 2 * 48 * 32 * 9]
+            achieved = flops[dom] / (layer_ms[dom] * 1e-3) / 1e12
+            scale = (H / 256.0) ** 2
+            traffic, traffic_source = pmc_traffic(names[dom], args.batch, H)   # (a committed rocprofv3 pass, not this run)
+            result["roofline"] = {
+                "bound": "mfma", "kernel": names[dom], "achieved": round(achieved, 2),
+                "peak": round(peak, 1), "unit": "TFLOP/s",
+                "frac": round(achieved / peak, 4),
+                "traffic": traffic, "traffic_source": traffic_source,
+                "note": "achieved = algorithmic conv FLOPs / live HIP-event kernel time; peak = dense 16-bit "
+                        "MFMA peak / 3 (three fp16 / bf16 MFMAs per fp32-equivalent product)" if bf3 else
+                        "achieved = algorithmic conv FLOPs / live HIP-event kernel time; peak = fp32 MFMA",
+                "kernel_ms": round(layer_ms[dom], 4),
+                "layer_ms": [round(m, 4) for m in layer_ms], "layer_kernels": names,
+                "whole_net_hbm": {
+                    "achieved_GBps": round(ESPCN_BYTES_PER_IMG * scale * imgs_per_s / world / 1e9, 1),
+                    "peak_GBps": HBM_PEAK_GBS, "measured_copy_GBps": copy_gbps,
+                    "frac": round(ESPCN_BYTES_PER_IMG * scale * imgs_per_s / world / 1e9 / HBM_PEAK_GBS, 4),
+                    "note": "61.11 MB/img per-layer compulsory traffic (SURVEY.md 8d); north-star target 0.30"}}
     extra = {}
-    if torch.distributed.is_initialized():
+    if args.full and torch.distributed.is_initialized():
         # what the collective library saw, so that an N > 1 record explains itself
         extra["rccl_ranks_seen"] = ranks_seen
         extra["dist_backend"] = torch.distributed.get_backend()
@@ -881,7 +927,7 @@ def main():
         extra["c2_images_per_s_per_gpu"] = round(imgs_per_s / world, 1)   # compare with the N = 1 record's `value`
         if ranks_seen != world and rank == 0 and result is not None:
             extra["rccl_error"] = "all-reduce of ones returned %s for WORLD_SIZE %d" % (ranks_seen, world)
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         dog = None
         if torch.distributed.is_initialized():
             torch.distributed.barrier()
@@ -948,7 +994,7 @@ def main():
     if rank == 0:
         if extra:
             result["extra"] = extra
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(lr_size=args.lr_size)
         emit_json(result)
     if torch.distributed.is_initialized():

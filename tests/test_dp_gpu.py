@@ -329,7 +329,7 @@ def test_bench_runs_its_multi_rank_code_path_on_one_gpu(gpu):
                RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", HSA_ENABLE_IPC_MODE_LEGACY="0", SRK_BENCH_EXTRA_TIMEOUT="600")
     env.pop("SRK_ENV_LIVE", None)     # the product configuration: switches read once
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
-                        "--extra-steps", "5", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--extra-steps", "5", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]

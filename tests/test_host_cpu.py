@@ -392,15 +392,15 @@ REFERENCE_DRAWS = [
 
 def test_training_item_draws_follow_the_reference_source_order(pkg, tmp_path, monkeypatch):
     """data.TrainDatasetFromFolder.draw consumes Python's `random` in the order of dataset.py:51-83 -- the table above,
-    checked against the reference's source lines when /root/reference is present (this container) and replayed against
-    draw() for every flag combination: same calls, same arguments, same order."""
-    ref = "/root/reference/dataset.py"
-    if os.path.exists(ref):
-        lines = open(ref).read().splitlines()
-        for lineno, text, _ in REFERENCE_DRAWS:
-            assert text in lines[lineno - 1], (lineno, text, lines[lineno - 1])
-        order = [lineno for lineno, _, _ in REFERENCE_DRAWS]
-        assert order == sorted(order)
+    checked against the reference's source lines (tests/golden/reference_draws.json, make_golden_draws.py) and replayed
+    against draw() for every flag combination: same calls, same arguments, same order."""
+    import json
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_draws.json")) as fh:
+        found = json.load(fh)["lines_containing"]
+    for lineno, text, _ in REFERENCE_DRAWS:
+        assert lineno in found[text], (lineno, text, found[text])
+    order = [lineno for lineno, _, _ in REFERENCE_DRAWS]
+    assert order == sorted(order)
     calls = []
 
     class Recorder(object):

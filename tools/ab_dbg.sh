@@ -3,7 +3,7 @@
 # 4 no MFMA loop, 2 no epilogue) -- results are wrong by construction, only the layer times mean anything
 cd $(dirname $0)/..
 for d in "$@"; do
-  echo "SRK_DBG=$d $(SRK_DBG=$d python bench.py --no-extra --no-cpu-baseline 2>/dev/null | python -c "
+  echo "SRK_DBG=$d $(SRK_DBG=$d python bench.py --full --no-extra --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for ln in sys.stdin:
     if ln.startswith('{'):

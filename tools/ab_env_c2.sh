@@ -3,7 +3,7 @@
 cd $(dirname $0)/..
 VAR=$1; shift
 for round in 1 2 3; do for v in "$@"; do
-  echo "$VAR=$v $(env $VAR=$v python bench.py --no-extra --no-cpu-baseline 2>/dev/null | python -c "
+  echo "$VAR=$v $(env $VAR=$v python bench.py --full --no-extra --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for ln in sys.stdin:
     if ln.startswith('{'):
