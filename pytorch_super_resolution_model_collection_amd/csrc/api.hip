@@ -480,14 +480,13 @@ extern "C" int srk_conv2d_backward_weight(const srk_conv_desc* d, const float* x
   // AUTO / BF16X3: bf16x3 MFMA kernel where it applies (stride-1 convs up to 3x3); MFMA / BF16X6 / DIRECT: the
   // exact fp32 MFMA kernel; GENERIC: the plain kernel
   const int algo = forced_algo(d->algo);
-  const char* wb = env_str("SRK_WGRAD_BF16");  // 0 disables the bf16x3 weight-gradient kernels
-  if ((algo == SRK_ALGO_AUTO || algo == SRK_ALGO_MFMA_BF16X3) && !(wb && atoi(wb) == 0) &&
-      conv_wgrad_tapn_supported(*d, x, mask))  // few-output-channel reconstruction convs
+  const bool bf = algo == SRK_ALGO_AUTO || algo == SRK_ALGO_MFMA_BF16X3;
+  if (bf && conv_wgrad_tapn_supported(*d, x, mask))  // few-output-channel reconstruction convs
     return conv_wgrad_tapn(*d, x, dy, dw, db, beta, workspace, workspace_bytes, (hipStream_t)stream);
-  if ((algo == SRK_ALGO_AUTO || algo == SRK_ALGO_MFMA_BF16X3) && !(wb && atoi(wb) == 0) && conv_wgrad_bf_supported(*d))
+  if (bf && conv_wgrad_bf_supported(*d))
     return conv_wgrad_bf(*d, x, dy, mask, dw, db, beta, workspace, workspace_bytes, (hipStream_t)stream);
   // stride-2 3x3 convs (SRGAN's discriminator): bf16x3 on de-interleaved halo columns
-  if ((algo == SRK_ALGO_AUTO || algo == SRK_ALGO_MFMA_BF16X3) && !(wb && atoi(wb) == 0) && conv_wgrad_s2_supported(*d, x, dy, mask))
+  if (bf && conv_wgrad_s2_supported(*d, x, dy, mask))
     return conv_wgrad_s2(*d, x, dy, dw, db, beta, workspace, workspace_bytes, (hipStream_t)stream);
   if (d->dy_ps_r > 1) {
     set_error("conv2d_backward_weight: pixel-shuffled dy is only supported by the bf16x3 kernel (un-shuffle with "
@@ -501,10 +500,7 @@ extern "C" int srk_conv2d_backward_weight(const srk_conv_desc* d, const float* x
 
 static bool wgrad_group_uses_bf(const srk_conv_desc& d) {
   const int algo = forced_algo(d.algo);
-  const char* wb = env_str("SRK_WGRAD_BF16");
-  const char* gg = env_str("SRK_WGRAD_GROUPED");  // 0: grouped calls run layer by layer (A/B against the per-layer kernels)
-  return (algo == SRK_ALGO_AUTO || algo == SRK_ALGO_MFMA_BF16X3) && !(wb && atoi(wb) == 0) && !(gg && atoi(gg) == 0) &&
-         d.dy_ps_r == 0 && !conv_wgrad_tapn_supported(d, nullptr, nullptr) && conv_wgrad_bf_supported(d);
+  return (algo == SRK_ALGO_AUTO || algo == SRK_ALGO_MFMA_BF16X3) && d.dy_ps_r == 0 && !conv_wgrad_tapn_supported(d, nullptr, nullptr) && conv_wgrad_bf_supported(d);
 }
 
 extern "C" size_t srk_conv2d_backward_weight_grouped_workspace_bytes(const srk_conv_desc* d, int n) {

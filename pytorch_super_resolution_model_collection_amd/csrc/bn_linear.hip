@@ -12,7 +12,7 @@ constexpr int kBnRowSplits = 512;
 // partial[split][2][C] (double): sum(a), sum(a*b') where the second operand depends on MODE:
 //   MODE 0: a = x,  second = x*x                      (forward statistics)
 //   MODE 1: a = dy, second = dy * (x-mean)*rstd       (backward statistics)
-template <int MODE, bool DBL>
+template <int MODE>
 __global__ __launch_bounds__(256) void k_bn_colsum(const float* __restrict__ a, const float* __restrict__ x,
                                                    const float* __restrict__ mean, const float* __restrict__ rstd,
                                                    double* __restrict__ partial, size_t rows, int C,
@@ -49,28 +49,17 @@ __global__ __launch_bounds__(256) void k_bn_colsum(const float* __restrict__ a, 
         va[u] = in ? va[u] : 0.f;
         if (MODE == 1) vx[u] = in ? vx[u] : mu;
       }
-      if (DBL || MODE == 0) {
-        // backward statistics feed a difference that cancels to ~1e-4 of its mass when a BatchNorm follows another
-        // (SRGAN-D at 128x128): products and sums in double, only the inputs are fp32.  Forward: x*x is exact in
-        // double, so mean / var carry no rounding but that of the inputs.
-        double d0 = 0.0, d1 = 0.0;
+      // backward statistics feed a difference that cancels to ~1e-4 of its mass when a BatchNorm follows another
+      // (SRGAN-D at 128x128): products and sums in double, only the inputs are fp32.  Forward: x*x is exact in
+      // double, so mean / var carry no rounding but that of the inputs.
+      double d0 = 0.0, d1 = 0.0;
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-          d0 += (double)va[u];
-          d1 += MODE == 0 ? (double)va[u] * (double)va[u] : (double)va[u] * (((double)vx[u] - (double)mu) * (double)rs);
-        }
-        s0 += d0;
-        s1 += d1;
-      } else {
-        float f0 = 0.f, f1 = 0.f;
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          f0 += va[u];
-          f1 += va[u] * ((vx[u] - mu) * rs);
-        }
-        s0 += f0;
-        s1 += f1;
+      for (int u = 0; u < U; ++u) {
+        d0 += (double)va[u];
+        d1 += MODE == 0 ? (double)va[u] * (double)va[u] : (double)va[u] * (((double)vx[u] - (double)mu) * (double)rs);
       }
+      s0 += d0;
+      s1 += d1;
     }
   }
   sm[0][w][lane] = s0;
@@ -294,7 +283,6 @@ __global__ __launch_bounds__(256) void k_bn_apply(const float* __restrict__ x, f
   }
 }
 
-template <bool DBL>
 __global__ __launch_bounds__(256) void k_bn_bwd_apply(const float* __restrict__ dy, const float* __restrict__ x,
                                                       const float* __restrict__ mean, const float* __restrict__ rstd,
                                                       const float* __restrict__ gamma,
@@ -304,19 +292,12 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const float* __restrict__ 
     const int c = (int)(i % C);
     const float rs = rstd[c];
     const float g = gamma ? gamma[c] : 1.f;
-    if (DBL) {
-      // dy - mean(dy) - xhat*mean(dy*xhat) cancels heavily when this BN's output feeds another BN: evaluate the
-      // difference in double from the fp32 inputs and the double sums, round once
-      const double xhat = ((double)x[i] - (double)mean[c]) * (double)rs;
-      const double m1 = dstats[c] / count;
-      const double m2 = dstats[C + c] / count;
-      dx[i] = (float)((double)g * (double)rs * ((double)dy[i] - m1 - xhat * m2));
-    } else {
-      const float xhat = (x[i] - mean[c]) * rs;
-      const float m1 = (float)(dstats[c] / count);
-      const float m2 = (float)(dstats[C + c] / count);
-      dx[i] = g * rs * (dy[i] - m1 - xhat * m2);
-    }
+    // dy - mean(dy) - xhat*mean(dy*xhat) cancels heavily when this BN's output feeds another BN: evaluate the
+    // difference in double from the fp32 inputs and the double sums, round once
+    const double xhat = ((double)x[i] - (double)mean[c]) * (double)rs;
+    const double m1 = dstats[c] / count;
+    const double m2 = dstats[C + c] / count;
+    dx[i] = (float)((double)g * (double)rs * ((double)dy[i] - m1 - xhat * m2));
   }
 }
 
@@ -344,7 +325,6 @@ __global__ __launch_bounds__(256) void k_bn_apply4(const float* __restrict__ x, 
   if (y_amax) amax_commit_block(y_amax, amax, blockIdx.x, sm_amax, 4, peeked);   // the running maximum the next conv scales by
 }
 
-template <bool DBL>
 __global__ __launch_bounds__(256) void k_bn_bwd_apply4(const float* __restrict__ dy, const float* __restrict__ x,
                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
                                                        const float* __restrict__ gamma,
@@ -358,18 +338,11 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply4(const float* __restrict__
     if (gamma) g = *reinterpret_cast<const bn_f4*>(gamma + c);
     bn_f4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (DBL) {  // (same evaluation as k_bn_bwd_apply<true>)
-        const double xhat = ((double)xv[e] - (double)mu[e]) * (double)rs[e];
-        const double m1 = dstats[c + e] / count;
-        const double m2 = dstats[C + c + e] / count;
-        o[e] = (float)((double)g[e] * (double)rs[e] * ((double)dv[e] - m1 - xhat * m2));
-      } else {
-        const float xhat = (xv[e] - mu[e]) * rs[e];
-        const float m1 = (float)(dstats[c + e] / count);
-        const float m2 = (float)(dstats[C + c + e] / count);
-        o[e] = g[e] * rs[e] * (dv[e] - m1 - xhat * m2);
-      }
+    for (int e = 0; e < 4; ++e) {   // (same evaluation as k_bn_bwd_apply)
+      const double xhat = ((double)xv[e] - (double)mu[e]) * (double)rs[e];
+      const double m1 = dstats[c + e] / count;
+      const double m2 = dstats[C + c + e] / count;
+      o[e] = (float)((double)g[e] * (double)rs[e] * ((double)dv[e] - m1 - xhat * m2));
     }
     *reinterpret_cast<bn_f4*>(dx + i * 4) = o;
   }
@@ -543,7 +516,6 @@ __global__ __launch_bounds__(64 * NW) void k_bn_reduce_act(const double* __restr
   }
 }
 
-template <bool DBL>
 __global__ __launch_bounds__(256) void k_bn_bwd_apply_act4(const float* __restrict__ dy, const float* __restrict__ x,
                                                            const float* __restrict__ mean, const float* __restrict__ rstd,
                                                            BnAct A, const double* __restrict__ dstats, double count,
@@ -560,17 +532,10 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply_act4(const float* __restri
     for (int e = 0; e < 4; ++e) {
       const float z = bn_z(xv[e], mu[e], rs[e], g[e], b[e]);
       const float dz = (A.act == SRK_ACT_NONE || z > 0.f) ? dv[e] : dv[e] * bn_act_slope(A, c + e);
-      if (DBL) {
-        const double xhat = ((double)xv[e] - (double)mu[e]) * (double)rs[e];
-        const double m1 = dstats[c + e] / count;
-        const double m2 = dstats[C + c + e] / count;
-        o[e] = (float)((double)g[e] * (double)rs[e] * ((double)dz - m1 - xhat * m2));
-      } else {
-        const float xhat = (xv[e] - mu[e]) * rs[e];
-        const float m1 = (float)(dstats[c + e] / count);
-        const float m2 = (float)(dstats[C + c + e] / count);
-        o[e] = g[e] * rs[e] * (dz - m1 - xhat * m2);
-      }
+      const double xhat = ((double)xv[e] - (double)mu[e]) * (double)rs[e];
+      const double m1 = dstats[c + e] / count;
+      const double m2 = dstats[C + c + e] / count;
+      o[e] = (float)((double)g[e] * (double)rs[e] * ((double)dz - m1 - xhat * m2));
     }
     *reinterpret_cast<bn_f4*>(dx + i * 4) = o;
   }
@@ -587,11 +552,6 @@ __global__ __launch_bounds__(256) void k_bn_param_grads(const double* __restrict
   if (c >= C) return;
   if (dbeta) dbeta[c] += (float)dstats[c];
   if (dgamma) dgamma[c] += (float)dstats[C + c];
-}
-
-// SRK_BN_F32=1 (debugging / A-B only): the backward arithmetic of round 1 (fp32 per-element terms)
-static bool bn_fp32_backward() {
-  return env_int("SRK_BN_F32", 0) == 1;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -768,7 +728,7 @@ __global__ __launch_bounds__(BNF_THR) void k_bn_fin_apply_act(const double* __re
 // dx = gamma * rstd * (dz - m1 - xhat * m2) with dz = dy * act'(z), z recomputed from x as in the forward
 // NQ sums are reduced per channel; `pq` = planes per split row of `partial` (3 behind k_bn_colsum_act even where the third --
 // PReLU's slope gradient -- is not wanted: NQ = 2 then reads two of the three)
-template <int NQ, bool DBL>
+template <int NQ>
 __global__ __launch_bounds__(BNF_THR) void k_bn_fin_bwd_apply_act(const double* __restrict__ partial, int nsplit, int pq, double count,
                                                                   const float* __restrict__ dy, const float* __restrict__ x,
                                                                   const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -833,13 +793,8 @@ __global__ __launch_bounds__(BNF_THR) void k_bn_fin_bwd_apply_act(const double* 
         const float z = bn_z(xv[e], mu[e], rs[e], g[e], b[e]);
         dz = z > 0.f ? dv[e] : dv[e] * sl[e];
       }
-      if (DBL) {
-        const double xhat = ((double)xv[e] - (double)mu[e]) * (double)rs[e];
-        o[e] = (float)((double)g[e] * (double)rs[e] * ((double)dz - m1[e] - xhat * m2[e]));
-      } else {
-        const float xhat = (xv[e] - mu[e]) * rs[e];
-        o[e] = g[e] * rs[e] * (dz - (float)m1[e] - xhat * (float)m2[e]);
-      }
+      const double xhat = ((double)xv[e] - (double)mu[e]) * (double)rs[e];
+      o[e] = (float)((double)g[e] * (double)rs[e] * ((double)dz - m1[e] - xhat * m2[e]));
     }
     *reinterpret_cast<bn_f4*>(dx + off) = o;
     const size_t rn = r + BNF_THR / 4;
@@ -905,11 +860,9 @@ static int bn_colsum(int mode, const float* a, const float* x, const float* mean
   const size_t rps = (rows + splits - 1) / splits;
   dim3 grid(cdiv(C, 64), splits);
   if (mode == 0)
-    hipLaunchKernelGGL((k_bn_colsum<0, false>), grid, dim3(256), 0, s, a, x, mean, rstd, (double*)ws, rows, C, rps);
-  else if (bn_fp32_backward())
-    hipLaunchKernelGGL((k_bn_colsum<1, false>), grid, dim3(256), 0, s, a, x, mean, rstd, (double*)ws, rows, C, rps);
+    hipLaunchKernelGGL(k_bn_colsum<0>, grid, dim3(256), 0, s, a, x, mean, rstd, (double*)ws, rows, C, rps);
   else
-    hipLaunchKernelGGL((k_bn_colsum<1, true>), grid, dim3(256), 0, s, a, x, mean, rstd, (double*)ws, rows, C, rps);
+    hipLaunchKernelGGL(k_bn_colsum<1>, grid, dim3(256), 0, s, a, x, mean, rstd, (double*)ws, rows, C, rps);
   const bool wide = splits > 64;
   const bool r16 = wide && env_int("SRK_BN_RED16", 1) != 0;
   if (fu.mode == 0 && r16)
@@ -1223,8 +1176,7 @@ __global__ __launch_bounds__(256) void k_linear_dw_wide(const float* __restrict_
 }
 
 static bool linear_wide(const void* a, const void* b, const void* c, int In, int Out) {
-  const bool off = env_int("SRK_LINEAR_WIDE", 1) == 0;
-  if (off || (In & 3) || In < 2048 || Out < 64) return false;
+  if ((In & 3) || In < 2048 || Out < 64) return false;
   return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
 }
 
@@ -1406,18 +1358,11 @@ extern "C" int srk_bn_backward_apply(const float* dy, const float* x, const floa
   size_t nb = (total + 256 * 4 - 1) / (256 * 4);
   if (nb > 4096) nb = 4096;
   const bool v4 = bn_vec4(C, dy, x, mean, rstd, gamma, dx);
-  if (bn_fp32_backward()) {
-    if (v4)
-      hipLaunchKernelGGL(k_bn_bwd_apply4<false>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd,
-                         gamma, dstats, count, dx, total / 4, C);
-    else
-      hipLaunchKernelGGL(k_bn_bwd_apply<false>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd,
-                         gamma, dstats, count, dx, total, C);
-  } else if (v4) {
-    hipLaunchKernelGGL(k_bn_bwd_apply4<true>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd,
+  if (v4) {
+    hipLaunchKernelGGL(k_bn_bwd_apply4, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd,
                        gamma, dstats, count, dx, total / 4, C);
   } else {
-    hipLaunchKernelGGL(k_bn_bwd_apply<true>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd,
+    hipLaunchKernelGGL(k_bn_bwd_apply, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd,
                        gamma, dstats, count, dx, total, C);
   }
   return check_launch("bn_backward_apply");
@@ -1485,17 +1430,13 @@ extern "C" int srk_bn_backward_apply_act(const float* dy, const float* x, const 
   size_t nb = (total + 256 * 4 - 1) / (256 * 4);
   if (nb > 4096) nb = 4096;
   BnAct A{gamma, beta, prelu_weight, act, prelu_n, slope};
-  if (bn_fp32_backward())
-    hipLaunchKernelGGL(k_bn_bwd_apply_act4<false>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd, A,
-                       dstats, count, dx, total / 4, C);
-  else
-    hipLaunchKernelGGL(k_bn_bwd_apply_act4<true>, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd, A,
-                       dstats, count, dx, total / 4, C);
+  hipLaunchKernelGGL(k_bn_bwd_apply_act4, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd, A,
+                     dstats, count, dx, total / 4, C);
   return check_launch("bn_backward_apply_act");
 }
 
 // ---- finalize-in-apply entry points (round 6) ---------------------------------------------------------------------------
-extern "C" int srk_bn_fused_supported(int C) { return C > 0 && C % BNF_CS == 0 && C <= 512 && env_int("SRK_BN_FIN_APPLY", 1) != 0; }
+extern "C" int srk_bn_fused_supported(int C) { return C > 0 && C % BNF_CS == 0 && C <= 512; }
 
 extern "C" int srk_bn_stats_partials(const float* x, size_t rows, int C, void* workspace, int* splits_out, void* stream) {
   SRK_REQUIRE(x && workspace && splits_out && rows > 0 && C > 0, "bn_stats_partials: bad args");
@@ -1503,7 +1444,7 @@ extern "C" int srk_bn_stats_partials(const float* x, size_t rows, int C, void* w
   if (splits > kBnRowSplits) splits = kBnRowSplits;
   if (splits < 1) splits = 1;
   const size_t rps = (rows + splits - 1) / splits;
-  hipLaunchKernelGGL((k_bn_colsum<0, false>), dim3(cdiv(C, 64), splits), dim3(256), 0, (hipStream_t)stream, x, nullptr, nullptr,
+  hipLaunchKernelGGL(k_bn_colsum<0>, dim3(cdiv(C, 64), splits), dim3(256), 0, (hipStream_t)stream, x, nullptr, nullptr,
                      nullptr, (double*)workspace, rows, C, rps);
   *splits_out = splits;
   return check_launch("bn_stats_partials");
@@ -1545,10 +1486,7 @@ extern "C" int srk_bn_backward_partials_act(const float* dy, const float* x, con
     if (splits < 1) splits = 1;
     const size_t rps = (rows + splits - 1) / splits;
     dim3 grid(cdiv(C, 64), splits);
-    if (bn_fp32_backward())
-      hipLaunchKernelGGL((k_bn_colsum<1, false>), grid, dim3(256), 0, s, dy, x, mean, rstd, (double*)workspace, rows, C, rps);
-    else
-      hipLaunchKernelGGL((k_bn_colsum<1, true>), grid, dim3(256), 0, s, dy, x, mean, rstd, (double*)workspace, rows, C, rps);
+    hipLaunchKernelGGL(k_bn_colsum<1>, grid, dim3(256), 0, s, dy, x, mean, rstd, (double*)workspace, rows, C, rps);
     *splits_out = splits;
     return check_launch("bn_backward_partials_act");
   }
@@ -1580,17 +1518,15 @@ extern "C" int srk_bn_backward_finalize_apply_act(const double* partials, int sp
   bnf_grid(rows, C, grid, rpb);
   BnAct A{gamma, beta, prelu_weight, act, prelu_n, slope};
   hipStream_t s = (hipStream_t)stream;
-  const bool f32 = bn_fp32_backward();
   float* dp = act == SRK_ACT_PRELU ? dprelu : nullptr;
   const int pq = act == SRK_ACT_NONE ? 2 : 3;   // planes per split row (srk_bn_backward_partials_act)
-#define SRK_BNF_LAUNCH(NQ, DBL)                                                                                            \
-  hipLaunchKernelGGL((k_bn_fin_bwd_apply_act<NQ, DBL>), grid, dim3(BNF_THR), 0, s, partials, splits, pq, count, dy, x, mean, rstd, A, \
+#define SRK_BNF_LAUNCH(NQ)                                                                                                 \
+  hipLaunchKernelGGL(k_bn_fin_bwd_apply_act<NQ>, grid, dim3(BNF_THR), 0, s, partials, splits, pq, count, dy, x, mean, rstd, A, \
                      dx, rows, C, rpb, dstats, dgamma, dbeta, dp)
-  if (!dp) {    // no PReLU slope gradient wanted: two sums
-    if (f32) SRK_BNF_LAUNCH(2, false); else SRK_BNF_LAUNCH(2, true);
-  } else {
-    if (f32) SRK_BNF_LAUNCH(3, false); else SRK_BNF_LAUNCH(3, true);
-  }
+  if (!dp)    // no PReLU slope gradient wanted: two sums
+    SRK_BNF_LAUNCH(2);
+  else
+    SRK_BNF_LAUNCH(3);
 #undef SRK_BNF_LAUNCH
   return check_launch("bn_backward_finalize_apply_act");
 }

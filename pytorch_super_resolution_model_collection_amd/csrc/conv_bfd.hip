@@ -570,7 +570,6 @@ static void bfd_lds_plan(int TW, int is, int HW, int npx, int npix, int NPW, int
     long best_cost = -1;
     int best_D = 0;
     unsigned best_mask = 0;
-    const bool off = env_int("SRK_BFD_LDS_PLAN", 1) == 0;
     auto cost_of = [&](int D, unsigned mk) {
       long cost = 0;
       for (int t = 0; t < live; ++t) {
@@ -589,7 +588,7 @@ static void bfd_lds_plan(int TW, int is, int HW, int npx, int npix, int NPW, int
       return cost;
     };
     // candidate order: the round-3 layout first (ties keep it), then the rest
-    for (int di = 0; di < (off ? 1 : 16) && best_cost != 2L * live; ++di) {
+    for (int di = 0; di < 16 && best_cost != 2L * live; ++di) {
       const int D = di == 0 ? 0 : (di == 1 ? 8 : (di <= 8 ? di - 1 : di));   // 0, 8, 1 .. 7, 9 .. 15
       // mask: pixels on the lane class A; the first candidate is the identity (pixels {0-3, 12-15}), then every other
       // 8-of-16 subset in increasing order (Gosper's hack: 12870 masks, not 65536 popcount tests)
@@ -603,7 +602,6 @@ static void bfd_lds_plan(int TW, int is, int HW, int npx, int npix, int NPW, int
             if (best_cost == 2L * live) break;   // one clock per set everywhere
           }
         }
-        if (off) break;
         if (first) {
           first = 0;
           mk = 0x00FFu;
@@ -662,13 +660,11 @@ static int bfd_launch(BfdParams B, int budget_bytes, hipStream_t s) {
   if (lds < epi_bytes) lds = epi_bytes;
   dim3 grid((unsigned)((size_t)P.tiles_x * P.tiles_y * P.N), B.OCb);
   if constexpr (NPW == 1) {
-    // small-problem blocks with >= 2 staged chunks: split the chunks over two wave groups (SRK_BFD_KSPLIT=0: off)
-    const int ksplit = env_int("SRK_BFD_KSPLIT", 1);
+    // small-problem blocks with >= 2 staged chunks: split the chunks over two wave groups
     const size_t red_bytes = (size_t)NOW * 4 * NTW * 64 * 16;
     // only while the grid leaves the CUs with one block each: with two resident blocks the other block already hides the
     // latency and the split just adds the reduction (B = 32 EDSR shard: 3.28 -> 3.55 ms with it, B = 16: 2.63 -> 2.37 ms)
-    if (ksplit && B.ICc >= 2 && (B.allc || 2 * lds_chunk <= (size_t)150 * 1024) &&
-        ((long)grid.x * grid.y <= kNumCU + kNumCU / 4 || ksplit > 1)) {
+    if (B.ICc >= 2 && (B.allc || 2 * lds_chunk <= (size_t)150 * 1024) && (long)grid.x * grid.y <= kNumCU + kNumCU / 4) {
       if (!B.allc) {  // many chunks (deep layers of the SRGAN discriminator): two chunks per barrier round, one per group
         B.cpr = 2;
         lds = 2 * lds_chunk;
@@ -749,8 +745,7 @@ static int bfd_launch_small_multi(const MfmaConvParams* phases, int nph, const B
   M.start[nph] = (int)total;
   const int OCb = base.OCb;
   // K split over two wave groups while the whole launch leaves the CUs with about one block each (as bfd_launch)
-  const int ksplit = env_int("SRK_BFD_KSPLIT", 1);
-  bool ks2 = ksplit && base.ICc >= 2 && (total * OCb <= kNumCU + kNumCU / 4 || ksplit > 1);
+  bool ks2 = base.ICc >= 2 && total * OCb <= kNumCU + kNumCU / 4;
   for (int i = 0; i < nph && ks2; ++i) ks2 = M.ph[i].allc || 2 * lds_chunk[i] <= (size_t)150 * 1024;
   size_t lds_max = 0;
   const size_t red_bytes = (size_t)NOW * 4 * NTW * 64 * 16;

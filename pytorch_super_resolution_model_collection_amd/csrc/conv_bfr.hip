@@ -853,7 +853,7 @@ static int conv_bfr_canvas(const BfwParams& B0, hipStream_t s) {
   B.nbuf = (int)nbuf;
   B.perm = 1;
   B.NPIXp = BFR_NPIXP;
-  B.late = env_int("SRK_BFR_PRIO", 2);
+  B.late = 2;
   const size_t lds = wbytes + (size_t)nbuf * slot_bytes + BFR_CNT_BYTES;
   B.ntiles = (int)best_tiles;
 #ifdef BFR_PROF
@@ -909,7 +909,7 @@ int conv_bfr_launch(const BfwParams& B0, hipStream_t s) {
   B.nbuf = (int)nbuf;
   B.perm = 1;
   B.NPIXp = BFR_NPIXP;
-  B.late = env_int("SRK_BFR_PRIO", 2);  // which role issues first on its SIMD (k_conv_bfr: prio)
+  B.late = 2;  // which role issues first on its SIMD (k_conv_bfr: prio)
   const size_t lds = wbytes + (size_t)nbuf * slot_bytes + BFR_CNT_BYTES;
   B.ntiles = (int)ntiles;
 #ifdef BFR_PROF

@@ -647,7 +647,7 @@ int conv_bfw_gather(const GatherConv& g, const float* in, const float* wp, float
     const int perm = SRK_EXP_INT("SRK_BFW_PERM", 1);
     const int w16 = SRK_EXP_INT("SRK_BFW_W16", 0);
     B.perm = perm;
-    B.late = B.ICc == 1 && env_int("SRK_BFW_LATE", 1) != 0;   // (B.ICc is set above)
+    B.late = B.ICc == 1;   // (B.ICc is set above)
     if (T == 9 && P.is == 1) {  // ring of halo buffers instead of the per-stage barrier (conv_bfr.hip) where it applies
       const int rc = conv_bfr_launch(B, s);
       if (rc != -1) return rc;

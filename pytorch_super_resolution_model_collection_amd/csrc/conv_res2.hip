@@ -528,8 +528,8 @@ static int r2_launch(const Res2Params& R, hipStream_t s) {
   const size_t lds = (size_t)2 * NP * (R2_PL1 + R2_PL2) * 16;
   const size_t grid = (size_t)R.N * R.tiles_y * R.tiles_x;
   if constexpr (NP == 2) {
-    // at most one block per CU: the variant that reads the next tap's operands ahead (SRK_RES2_PF=0: off)
-    if (grid <= (size_t)kNumCU && env_int("SRK_RES2_PF", 1) != 0) {
+    // at most one block per CU: the variant that reads the next tap's operands ahead
+    if (grid <= (size_t)kNumCU) {
       static LdsLimit limp;
       limp.ensure(reinterpret_cast<const void*>(&k_res2<NP, BWD, F16, true>), lds);
       note_kernel("k_res2<%d,%d%s,pf>", NP, (int)BWD, F16 ? ",f16" : "");

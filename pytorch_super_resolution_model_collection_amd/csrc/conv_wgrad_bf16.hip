@@ -1052,13 +1052,10 @@ __device__ __forceinline__ void wt_split8(const f32x4& v0, const f32x4& v1, uint
   lo = make_uint4(l[0], l[1], l[2], l[3]);
 }
 
-// NTW = 2: four working waves (2 ci tiles x 2 pairs of co tiles, one per SIMD beside two stager waves; 168 VGPRs).
-// NTW = 1: EIGHT working waves (2 x 4 single co tiles, two per SIMD: one wave's transpose reads are issued while the other's
-// MFMAs run -- a lone working wave pays ~16 clocks of matrix pipe per read, section 12.3 of DESIGN.md; 128 VGPRs).
-template <bool GRP, int NTW>
-__global__ __launch_bounds__(NTW == 2 ? 768 : 1024, NTW == 2 ? 3 : 4) void k_wgrad_tr(WgBfParams P,
-                                                                                       typename WgGroupArg<GRP>::type GR) {
-  constexpr int CIB = 32, COB = 64, NWV = 8 / NTW, WTHR = 64 * NWV, NST = WB_SST, NTHR = WTHR + NST, PIT = 1024 / NST;
+// Four working waves (2 ci tiles x 2 pairs of co tiles, one per SIMD beside two stager waves; 168 VGPRs).
+template <bool GRP>
+__global__ __launch_bounds__(768, 3) void k_wgrad_tr(WgBfParams P, typename WgGroupArg<GRP>::type GR) {
+  constexpr int CIB = 32, COB = 64, NTW = 2, NWV = 8 / NTW, WTHR = 64 * NWV, NST = WB_SST, NTHR = WTHR + NST, PIT = 1024 / NST;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem8[];
   __shared__ unsigned oct_tw[WB_MAXOCT];
   const long long clk_begin = WB_CLK();
@@ -1355,12 +1352,10 @@ __global__ __launch_bounds__(NTW == 2 ? 768 : 1024, NTW == 2 ? 3 : 4) void k_wgr
     const uint2 p0 = tr(a0), p1 = tr(a0 + 512u), q0 = tr(a0 + YPL), q1 = tr(a0 + YPL + 512u);
     bh[0] = make_uint4(p0.x, p0.y, p1.x, p1.y);
     bl[0] = make_uint4(q0.x, q0.y, q1.x, q1.y);
-    if constexpr (NTW == 2) {
-      const unsigned a1 = a0 ^ 32u;   // the wave's second 16-channel tile: lane_y1 = lane_y0 ^ 32
-      const uint2 p2 = tr(a1), p3 = tr(a1 + 512u), q2 = tr(a1 + YPL), q3 = tr(a1 + YPL + 512u);
-      bh[NTW - 1] = make_uint4(p2.x, p2.y, p3.x, p3.y);
-      bl[NTW - 1] = make_uint4(q2.x, q2.y, q3.x, q3.y);
-    }
+    const unsigned a1 = a0 ^ 32u;   // the wave's second 16-channel tile: lane_y1 = lane_y0 ^ 32
+    const uint2 p2 = tr(a1), p3 = tr(a1 + 512u), q2 = tr(a1 + YPL), q3 = tr(a1 + YPL + 512u);
+    bh[NTW - 1] = make_uint4(p2.x, p2.y, p3.x, p3.y);
+    bl[NTW - 1] = make_uint4(q2.x, q2.y, q3.x, q3.y);
   };
   auto rowmm = [&](const XF& f, const uint4 (&bh)[NTW], const uint4 (&bl)[NTW], f32x4 (&a)[3][NTW]) {
     uint4 ah[3], al[3];
@@ -1469,7 +1464,7 @@ __global__ __launch_bounds__(NTW == 2 ? 768 : 1024, NTW == 2 ? 3 : 4) void k_wgr
   auto step = [&](const XF& x0, const uint4 (&yh)[NTW], const uint4 (&yl)[NTW], XF& xn, uint4 (&nh)[NTW], uint4 (&nl)[NTW],
                   const TB& tc, const TB& tn) {
     XF x1 = {}, x2 = {};
-    if (WT_SGB == 3 && NTW == 2) {
+    if (WT_SGB == 3) {
       uint4 ah[3], al[3];
       {
         const unsigned a = nxa;
@@ -1920,8 +1915,6 @@ static WbPlan wb_plan(const srk_conv_desc& d) {
 
 // SPEC stagers prefetch one tile ahead when a tile's pixel pairs fit their register batches (WB_PIT x 512 items per tensor)
 static int wb_prefetch_ok(const WbPlan& pl, const srk_conv_desc& d) {
-  const int env = env_int("SRK_WGRAD_PREFETCH", 1);
-  if (!env) return 0;
   const long x_items = (long)pl.HH * ((pl.TW + d.KW) >> 1) * (pl.CIB / 4);
   const long y_items = (long)pl.TH * (pl.TW >> 1) * (pl.COB / 4);
   // the prefetching stagers load through per-image buffer descriptors with 32-bit byte offsets
@@ -1930,10 +1923,9 @@ static int wb_prefetch_ok(const WbPlan& pl, const srk_conv_desc& d) {
 }
 
 // Ring mode of the wave-specialised kernel (WgBfParams.ring): plane stride of the 2 * HH-row ring and the LDS it needs
-// (ring + two dY buffer sets); 0 when it does not apply.  SRK_WG_RING=0: off.
+// (ring + two dY buffer sets); 0 when it does not apply.
 static size_t wb_ring_setup(const WbPlan& pl, bool spec, int prefetch, int& cs_ring) {
-  const int ring_env = env_int("SRK_WG_RING", 1);
-  if (!ring_env || !spec || !prefetch) return 0;
+  if (!spec || !prefetch) return 0;
   cs_ring = round_8odd(2 * pl.HH * pl.HWp);
   const size_t bytes = ((size_t)2 * pl.CIB * cs_ring + (size_t)2 * 2 * pl.COB * pl.DS) * 2;
   return bytes + 8 * 1024 <= 160 * 1024 ? bytes : 0;
@@ -2051,17 +2043,10 @@ static bool wt_setup(WgBfParams& P, const srk_conv_desc& d, const WbPlan& pl, bo
 }
 template <bool GRP>
 static void wt_launch(const WgBfParams& P, const typename WgGroupArg<GRP>::type& GR, dim3 grid, size_t lds, hipStream_t s) {
-  if (env_int("SRK_WGRAD_TR_W8", 0)) {   // eight working waves (two per SIMD)
-    static LdsLimit lim8;
-    lim8.ensure(reinterpret_cast<const void*>(&k_wgrad_tr<GRP, 1>), lds);
-    note_kernel("k_wgrad_tr<%s,w8>", GRP ? "grouped" : "single");
-    hipLaunchKernelGGL((k_wgrad_tr<GRP, 1>), grid, dim3(1024), lds, s, P, GR);
-    return;
-  }
   static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&k_wgrad_tr<GRP, 2>), lds);
+  lim.ensure(reinterpret_cast<const void*>(&k_wgrad_tr<GRP>), lds);
   note_kernel("k_wgrad_tr<%s>", GRP ? "grouped" : "single");
-  hipLaunchKernelGGL((k_wgrad_tr<GRP, 2>), grid, dim3(768), lds, s, P, GR);
+  hipLaunchKernelGGL(k_wgrad_tr<GRP>, grid, dim3(768), lds, s, P, GR);
 }
 
 bool conv_wgrad_bf_supported(const srk_conv_desc& d) { return wb_plan(d).ok; }
@@ -2072,10 +2057,7 @@ size_t conv_wgrad_bf_ws(const srk_conv_desc& d) {
   return (size_t)pl.G * d.KH * d.KW * d.Cin * d.Cout * sizeof(float) + conv_bias_grad_ws(d);
 }
 
-static bool wb_k33(const WgBfParams& P) {
-  const int env = env_int("SRK_WG_K33", 1);
-  return env && P.KH == 3 && P.KW == 3;
-}
+static bool wb_k33(const WgBfParams& P) { return P.KH == 3 && P.KW == 3; }
 
 template <int CIT, int COW, int NTW>
 static void wb_launch(const WgBfParams& P, dim3 grid, size_t lds, bool spec, hipStream_t s) {
@@ -2217,11 +2199,10 @@ int conv_wgrad_bf(const srk_conv_desc& d, const float* x, const float* dy, const
   P.dy_ps_C = d.dy_ps_r > 1 ? d.Cout / (d.dy_ps_r * d.dy_ps_r) : d.Cout;
   P.prefetch = wb_prefetch_ok(pl, d) && P.vec_x && P.vec_y;  // 16-byte channel groups only
   // wave-specialised variant: one 512-thread block per CU with two LDS buffer sets, when every block has >= 2 tiles
-  // to pipeline (SRK_WGRAD_SPEC=0: never)
-  const int spec_env = env_int("SRK_WGRAD_SPEC", 1);
+  // to pipeline
   int G = pl.G;
   bool spec = false;
-  if (spec_env && 2 * pl.lds + 8 * 1024 <= 160 * 1024) {
+  if (2 * pl.lds + 8 * 1024 <= 160 * 1024) {
     int g1 = kNumCU / (pl.gy * pl.gz);
     if (g1 < 1) g1 = 1;
     if (pl.ntiles >= 2 * g1) {
@@ -2279,13 +2260,12 @@ int conv_wgrad_bf(const srk_conv_desc& d, const float* x, const float* dy, const
 // wave-specialised variant), writes one slab, and 33 layers cost two launches instead of 66.
 // ---------------------------------------------------------------------------------------------
 static int wb_group_G(const WbPlan& pl, int n, bool& spec) {
-  const int spec_env = env_int("SRK_WGRAD_SPEC", 1);
   const int g_env = SRK_EXP_INT("SRK_WG_GROUP_G", 0);  // experiment: slabs per layer
   const int per = n * pl.gy * pl.gz;  // (layer, channel-chunk) pairs
   // one block per CU (wave-specialised, two LDS buffer sets) when every block gets >= 2 tiles; else two per CU
   int g1 = kNumCU / per;
   if (g1 < 1) g1 = 1;
-  spec = spec_env && 2 * pl.lds + 8 * 1024 <= 160 * 1024 && pl.ntiles >= 2 * g1;
+  spec = 2 * pl.lds + 8 * 1024 <= 160 * 1024 && pl.ntiles >= 2 * g1;
   int G = spec ? g1 : (2 * kNumCU) / per;
   if (G < 1) G = 1;
   if (g_env > 0) G = g_env;

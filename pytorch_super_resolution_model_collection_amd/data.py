@@ -396,7 +396,7 @@ class PatchLoader(object):
             seed = 0
         # background: batches are produced by a loader thread up to two ahead of the consumer (its host work -- draws,
         # one call per patch, three batched resizes -- overlaps with the consumer launching / replaying the train step)
-        self.background = bool(background) and os.environ.get("SRK_LOADER_THREAD", "1") != "0"
+        self.background = bool(background)
         self.pool = ThreadPoolExecutor(max_workers=max(1, int(num_threads)))
         self.gen = torch.Generator()
         if seed is not None:

@@ -162,11 +162,10 @@ class DataParallel(object):
         stream is ordered after the last bucket."""
         from . import ops
         if not self.active:
-            ops.join_side_streams()
+            ops.flush_wgrads()
             return
         groups = ops.pending_wgrad_groups(self.trunk_chunk_layers)
-        if not groups:      # nothing deferred (side-stream mode, or a model without conv layers)
-            ops.join_side_streams()
+        if not groups:      # nothing deferred (ops.DEFER_WGRAD off, or a model without conv layers)
             works = []
             self.send([(0, self.flat.grad.numel())], works)
             for w in works:

@@ -35,7 +35,7 @@ CL = torch.channels_last
 #            but convolutions, additions and pixel shuffles between their output and the loss (EDSR: body-end conv,
 #            the two upsampler convs, the reconstruction conv; VDSR: the reconstruction conv), so no mask depends on
 #            their rounding and the ~5e-6 of the backward kernels is what their forward may carry as well (EDSR step
-#            7.11 -> 6.67 ms).  "bf16x6" keeps the fp32-faithful products there too; SRK_LINEAR_TAIL_X3=0 likewise.
+#            7.11 -> 6.67 ms).  "bf16x6" keeps the fp32-faithful products there too; LINEAR_TAIL_X3 = False likewise.
 #   "bf16x3" everything on the 3-term bf16 split (fastest; forward error ~1e-5, gradients subject to
 #            the mask-flip sensitivity above).
 #   "fp32"   everything exact fp32 (summation-order-level agreement with ATen/oneDNN).
@@ -232,12 +232,12 @@ def to_nhwc(x):
 # the tensor: `_srk_premasked = (address of y, version of dx)`.  The upstream backward skips its masks only if the
 # gradient it receives carries the mark for ITS y and is untouched since (autograd's fan-in accumulation adds in place
 # and bumps the version; a fresh sum carries no mark).  ReLU only: its 0/1 mask is idempotent, so a mark that got lost
-# merely costs the second application.  SRK_PREMASK=0 switches the protocol off.
+# merely costs the second application.  PREMASK = False switches the protocol off.
 # The gradient of an INTERMEDIATE activation is not what autograd defines while the protocol runs (it is already
 # multiplied by the ReLU gradient of its producer), so the protocol is active only inside `premasked_gradients()` -- the
 # backward passes of this package's own training steps (trainers._backward), where only parameter gradients are read.
 # A plain loss.backward(), torch.autograd.grad(loss, activation) or tensor.retain_grad() outside it sees standard gradients.
-PREMASK = os.environ.get("SRK_PREMASK", "1") != "0"
+PREMASK = True
 PREMASK_STATS = {"masked_dx": 0, "masks_skipped": 0}   # (tests: how often each half of the protocol ran)
 _PREMASK_DEPTH = [0]
 
@@ -363,7 +363,7 @@ def pack_bias_ps(bias, ps_r):
 # BatchNorm column sums from the producing conv's epilogue (srk_epilogue.bn_partial): a block that runs conv -> BatchNorm
 # in training asks for them around the conv call; a kernel that keeps them (k_c64: the per-tile 64 -> 64 3x3 kernel of
 # SRGAN's generator) tags its output, and _BatchNorm.forward then skips its own pass over the activation.
-BN_PARTIAL = os.environ.get("SRK_BN_PARTIAL", "1") != "0"
+BN_PARTIAL = True
 _BN_REQ = [0]
 
 
@@ -436,42 +436,6 @@ def conv_forward_raw(x, wp, bias_p, weight_shape_src, cfg, prelu_w=None, residua
     return y
 
 
-# Weight gradients on a second HIP stream.  In flat-buffer mode (optim.FlatParams) the weight-gradient kernels
-# accumulate straight into the model's gradient buffer and autograd never looks at their result, so a layer's wgrad
-# (+ slab reduce) can run concurrently with the same layer's data-gradient kernel and with the backward of the layers
-# below it.
-# Measured on MI355X / ROCm 7.2 (tools/edsr_small_batch.py, tools/graph_conc.py): hipGraph replay does not run the
-# forked branch concurrently (a two-branch graph of small kernels replays slower than the same kernels in one chain),
-# so the strong-scaled shard (EDSR x4, 16 patches per GPU) gains only 2 % (2.72 -> 2.65 ms) and the full batch loses
-# 8 % (9.04 -> 9.76 ms, two co-resident kernels fighting over LDS / cache).  OFF by default; SRK_WGRAD_STREAM=1 or
-# ops.WGRAD_SIDE_STREAM = True enables it.  Everything forked is joined by join_side_streams(), which runs at the end
-# of every backward pass (autograd engine callback) and in FlatParams / the optimizers / DataParallel.
-WGRAD_SIDE_STREAM = os.environ.get("SRK_WGRAD_STREAM", "0") == "1"
-_SIDE = {}   # device index -> [stream, tensors kept alive until the join]
-
-
-def _side(device):
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    ent = _SIDE.get(idx)
-    if ent is None:
-        ent = [torch.cuda.Stream(device=idx), []]
-        _SIDE[idx] = ent
-    return ent
-
-
-def join_side_streams():
-    """Every weight gradient of the backward passes so far is enqueued on / ordered before the current stream: launches
-    the deferred grouped weight gradients that are still pending (flush_wgrads) and makes the current stream wait for
-    any forked onto the side stream.  Runs automatically at the end of every backward pass (autograd engine callback),
-    so `loss.backward(); p.grad...` is safe; optimizers, zero_grad, clipping and the gradient exchange call it too."""
-    if _PENDING:
-        flush_wgrads()
-    for idx, ent in _SIDE.items():
-        if ent[1]:
-            torch.cuda.current_stream(idx).wait_stream(ent[0])
-            ent[1] = []
-
-
 # ------------------------------------------------------------------------------------------------
 # Deferred, grouped weight gradients
 # ------------------------------------------------------------------------------------------------
@@ -484,14 +448,13 @@ def join_side_streams():
 # (strong-scaled shard of 16 patches: 0.89 ms -> 0.1x of the step).  The flush happens at the end of the backward pass
 # (autograd engine callback) — `loss.backward(); p.grad` keeps working — or, under data parallelism, group by group
 # from dp.DataParallel.exchange(), which sends each group's bucket off while the next group computes.
-DEFER_WGRAD = os.environ.get("SRK_DEFER_WGRAD", "1") != "0"
-WGRAD_GROUP_MAX = int(os.environ.get("SRK_WGRAD_GROUP_MAX", "0"))   # > 0: split geometry groups into chunks of this many layers
+DEFER_WGRAD = True
 # Deferral trades launches and partial-slab traffic for cache locality: a weight gradient launched right behind its
 # layer's data gradient finds dy (and x) in the 256 MB Infinity Cache, one launched at the end of the pass reads them
 # from HBM.  Records are therefore flushed (grouped) as soon as their x + dy bytes exceed DEFER_MAX_BYTES: a 16-patch
 # EDSR shard (8 MB per layer) defers ~19 layers at a time, a 128-patch batch (67 MB per layer) falls back to
 # one-or-two-layer groups, i.e. the per-layer behaviour.
-DEFER_MAX_BYTES = int(float(os.environ.get("SRK_DEFER_MAX_MB", "160")) * (1 << 20))
+DEFER_MAX_BYTES = 160 << 20
 _PENDING = []                      # [(key, desc, x, dy, y_mask, slope, wacc, bacc)] in backward order
 _DEFER = {"queued": False, "manual": 0, "bytes": 0}
 
@@ -516,7 +479,7 @@ def _auto_flush():
 def pending_wgrad_groups(max_layers=None):
     """The recorded weight gradients as launch groups [[record, ...], ...]: same geometry (and bias / no bias), backward
     order, no two records of a group writing the same dw (shared weights), at most `max_layers` layers per group."""
-    cap = max_layers or WGRAD_GROUP_MAX or 0
+    cap = max_layers or 0
     groups, open_by_key = [], {}
     for rec in _PENDING:
         key, wptr = rec[0], rec[6].data_ptr()
@@ -588,8 +551,8 @@ def drop_pending_wgrads():
     _DEFER["bytes"] = 0
 
 
-MERGE_REDUCES = os.environ.get("SRK_MERGE_REDUCES", "1") != "0"   # 0: every weight-gradient launch group reduces its slabs itself
-FUSE_SKIP_GRAD = os.environ.get("SRK_FUSE_SKIP_GRAD", "1") != "0"  # 0: residual blocks sum their gradient fan-in with srk_axpby
+MERGE_REDUCES = True   # False: every weight-gradient launch group reduces its slabs itself
+FUSE_SKIP_GRAD = True   # False: residual blocks sum their gradient fan-in with srk_axpby
 
 
 class GradBox(object):
@@ -654,8 +617,7 @@ class _Conv2d(torch.autograd.Function):
             # the bf16x3 data- and weight-gradient kernels read the pixel-shuffled dy directly (they un-shuffle while
             # staging their tiles); everything else gets an explicit depth-from-space pass first
             fused_ps = (d.algo in (ALGO_AUTO, _lib.ALGO_MFMA_BF16X3) and not cfg.transposed and cfg.stride == 1
-                        and d.KH <= 3 and d.KW <= 3 and d.Cin >= 8 and (d.Cout // (r * r)) % 8 == 0
-                        and os.environ.get("SRK_FUSE_PS_BWD", "1") != "0")
+                        and d.KH <= 3 and d.KW <= 3 and d.Cin >= 8 and (d.Cout // (r * r)) % 8 == 0)
             ctx_wpb = ctx.wpb
             if fused_ps:
                 d.dy_ps_r = r
@@ -675,11 +637,9 @@ class _Conv2d(torch.autograd.Function):
         bacc = getattr(bref, "_srk_grad", None) if ctx.has_bias else None
         flat_mode = wacc is not None and (not ctx.has_bias or bacc is not None)
         if need_w and flat_mode:
-            # flat-buffer mode: accumulate straight into the (pre-zeroed) gradient views — on the side stream, forked
-            # here (after dy / x are ready, before the data gradient is launched) so the two kernels overlap
-            ws_bytes = 0 if (DEFER_WGRAD and not WGRAD_SIDE_STREAM) else \
-                lib.srk_conv2d_backward_weight_workspace_bytes(ctypes.byref(d))
-            if DEFER_WGRAD and not WGRAD_SIDE_STREAM:
+            # flat-buffer mode: accumulate straight into the (pre-zeroed) gradient views -- recorded for the grouped
+            # deferred launch, or launched here before the data gradient
+            if DEFER_WGRAD:
                 key = (d.N, d.H, d.W, d.Cin, d.OH, d.OW, d.Cout, d.KH, d.KW, d.stride, d.pad, d.transposed, d.out_pad,
                        d.algo, d.dy_ps_r, bacc is not None, str(dy.device))
                 _PENDING.append((key, d, x, dyc, y if mask is not None else None,
@@ -690,18 +650,8 @@ class _Conv2d(torch.autograd.Function):
                 elif not _DEFER["queued"]:   # first record of this backward pass: flush when the engine finishes it
                     _DEFER["queued"] = True
                     torch.autograd.Variable._execution_engine.queue_callback(_auto_flush)
-            elif WGRAD_SIDE_STREAM:
-                side, keep = _side(dy.device)
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=dy.device)
-                    check(lib.srk_conv2d_backward_weight(ctypes.byref(d), ptr(x), ptr(dyc), mref, ptr(wacc), ptr(bacc),
-                                                         1.0, ptr(ws), ws.numel(), stream_ptr()),
-                          "srk_conv2d_backward_weight")
-                if not keep:  # first fork of this backward pass: join when the autograd engine finishes it
-                    torch.autograd.Variable._execution_engine.queue_callback(join_side_streams)
-                keep.append((x, dyc, y, ws))  # the caching allocator must not recycle these before the join
             else:
+                ws_bytes = lib.srk_conv2d_backward_weight_workspace_bytes(ctypes.byref(d))
                 ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=dy.device)
                 check(lib.srk_conv2d_backward_weight(ctypes.byref(d), ptr(x), ptr(dyc), mref, ptr(wacc), ptr(bacc),
                                                      1.0, ptr(ws), ws.numel(), stream_ptr()),
@@ -754,11 +704,11 @@ def conv2d(x, weight, bias=None, residual=None, cfg=None, packed=None, res_box=N
     return _Conv2d.apply(x, weight, bias, residual, cfg, packed, res_box, add_box)
 
 
-LINEAR_TAIL_X3 = os.environ.get("SRK_LINEAR_TAIL_X3", "1") != "0"
+LINEAR_TAIL_X3 = True
 
 
 # ---- residual block with both convolutions in one launch (srk_resblock2_*) ----------------------------------------
-RES2 = os.environ.get("SRK_RES2", "1") != "0"   # 0: residual blocks always run their two convs as separate launches
+RES2 = True   # False: residual blocks always run their two convs as separate launches
 
 
 def _weight_grad(d, x, dyc, weight, bias, need_w):
@@ -770,7 +720,7 @@ def _weight_grad(d, x, dyc, weight, bias, need_w):
     wacc = getattr(weight, "_srk_grad", None)
     bacc = getattr(bias, "_srk_grad", None) if bias is not None else None
     flat_mode = wacc is not None and (bias is None or bacc is not None)
-    if flat_mode and DEFER_WGRAD and not WGRAD_SIDE_STREAM:
+    if flat_mode and DEFER_WGRAD:
         key = (d.N, d.H, d.W, d.Cin, d.OH, d.OW, d.Cout, d.KH, d.KW, d.stride, d.pad, d.transposed, d.out_pad,
                d.algo, d.dy_ps_r, bacc is not None, str(dyc.device))
         _PENDING.append((key, d, x, dyc, None, 0.0, wacc, bacc))
@@ -1189,8 +1139,7 @@ def bce_loss(pred, target):
 # ------------------------------------------------------------------------------------------------
 # BatchNorm2d / Linear (SRGAN)
 # ------------------------------------------------------------------------------------------------
-BN_FIN_APPLY = os.environ.get("SRK_BN_FIN_APPLY", "1") != "0"   # 0: split reductions as launches of their own (rounds 1 - 5)
-BN_FUSE_ACT = os.environ.get("SRK_BN_FUSE_ACT", "1") != "0"   # 0: activations / residual adds after a BatchNorm stay passes of their own
+BN_FIN_APPLY = True   # False: split reductions as launches of their own (rounds 1 - 5)
 
 
 # Collectives inside a captured step (SyncBN's [2C] sums): a capture cannot hold them, so the capturing side
@@ -1388,7 +1337,7 @@ def bn_fusable(x, act, prelu_w=None, bn=None):
     (SyncBN keeps the separate passes)."""
     if bn is not None and getattr(bn, "sync_group", None) is not None:
         return False
-    if not BN_FUSE_ACT or act not in (ACT_NONE, ACT_RELU, ACT_LRELU, ACT_PRELU) or x.dim() < 2 or x.shape[1] % 4:
+    if act not in (ACT_NONE, ACT_RELU, ACT_LRELU, ACT_PRELU) or x.dim() < 2 or x.shape[1] % 4:
         return False
     return act != ACT_PRELU or (prelu_w is not None and prelu_w.numel() in (1, x.shape[1]))
 

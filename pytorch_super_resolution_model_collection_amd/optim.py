@@ -14,7 +14,6 @@ nn.Parameter objects stay in place (their .data / .grad become views), so state_
 reference's checkpoint files keep working.
 """
 import ctypes
-import os
 
 import torch
 
@@ -97,7 +96,7 @@ class FlatParams(object):
     def zero_grad(self):
         """Gradients, the PackPlan's max|w| scratch words and the running-maximum chunk: one fill."""
         from . import ops
-        ops.join_side_streams()  # no weight gradient of the previous step may still be accumulating
+        ops.flush_wgrads()  # no weight gradient of the previous step may still be pending
         self._zero_region.zero_()
 
     def mark_changed(self):
@@ -162,23 +161,22 @@ class PackPlan(object):
         # fast path (k_pack_fast): plain Conv2d filters are packed tile by tile from LDS, (Cout / 8) * ceil(Cin / 32)
         # blocks per layer; everything else (first layers, 64 -> 3 convs, deconvs, 9x9 kernels) takes the generic kernel
         fast = []
-        if os.environ.get("SRK_PACK_FAST", "1") != "0":
-            for i, r in enumerate(rows):
-                cout, cin, kh, kw, tr = r[3], r[4], r[5], r[6], r[7]
-                # (channel counts that leave no padding in either prepared layout: the kernel writes real channels only,
-                #  and the zero groups of a padded contraction axis must exist -- they meet zero activations, 0 x junk)
-                if not tr and kh * kw <= 25 and (cout % 64 == 0 or cout == 32) and (cin % 64 == 0 or cin in (16, 32, 48)) \
-                        and r[1] >= 0 and r[2] >= 0:
-                    r[12] = len(fast)
-                    icc = (cin + 31) // 32
-                    fast += [(i, lb) for lb in range((cout // 8) * icc)]
+        for i, r in enumerate(rows):
+            cout, cin, kh, kw, tr = r[3], r[4], r[5], r[6], r[7]
+            # (channel counts that leave no padding in either prepared layout: the kernel writes real channels only,
+            #  and the zero groups of a padded contraction axis must exist -- they meet zero activations, 0 x junk)
+            if not tr and kh * kw <= 25 and (cout % 64 == 0 or cout == 32) and (cin % 64 == 0 or cin in (16, 32, 48)) \
+                    and r[1] >= 0 and r[2] >= 0:
+                r[12] = len(fast)
+                icc = (cin + 31) // 32
+                fast += [(i, lb) for lb in range((cout // 8) * icc)]
         self.n_fast = len(fast)
         self.fast_blocks = torch.tensor(fast, dtype=torch.int32, device=dev) if fast else None
         self.table = torch.tensor(rows, dtype=torch.int64, device=dev)
         self.epoch = -1
         # grid of the generic kernel: sized by the largest filter it still packs itself
         biggest = max([r[3] * r[4] * r[5] * r[6] for r in rows if r[12] < 0] or [256])
-        self.blocks = max(1, min(int(os.environ.get("SRK_PACK_BLOCKS", "512")), (biggest + 255) // 256))
+        self.blocks = max(1, min(512, (biggest + 255) // 256))
         for m, fo, nf, bo, nb, bp_off, cout, ps_r in self.layers:
             wpf = self.buf[fo:fo + (nf + 3) // 4 * 4].view(torch.float32)
             wpb = self.buf[bo:bo + (nb + 3) // 4 * 4].view(torch.float32)
@@ -251,7 +249,7 @@ class _FlatOptimizer(object):
         norm on the device and stores min(1, max_norm/(norm+1e-6)) where the next step() reads it
         (the flat gradient buffer itself is left unscaled). Returns the device norm tensor."""
         from . import ops
-        ops.join_side_streams()
+        ops.flush_wgrads()
         lib = _lib.load()
         if self._norm_ws is None:
             self._norm_ws = torch.empty(int(lib.srk_grad_norm_workspace_bytes()), dtype=torch.uint8,
@@ -275,7 +273,7 @@ class SGD(_FlatOptimizer):
 
     def step(self):
         from . import ops
-        ops.join_side_streams()  # weight gradients forked onto the side stream
+        ops.flush_wgrads()  # weight gradients still pending from the backward pass
         lib = _lib.load()
         f = self.flat
         check(lib.srk_sgd_step(ptr(f.data), ptr(f.grad), ptr(self.buf), f.numel, 0.0, self.momentum,
@@ -296,7 +294,7 @@ class Adam(_FlatOptimizer):
 
     def step(self):
         from . import ops
-        ops.join_side_streams()  # weight gradients forked onto the side stream
+        ops.flush_wgrads()  # weight gradients still pending from the backward pass
         lib = _lib.load()
         f = self.flat
         check(lib.srk_adam_step(ptr(f.data), ptr(f.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), f.numel, 0.0,

@@ -69,7 +69,7 @@ def _backward(loss, dp):
     else:
         with ops.premasked_gradients():
             ops.backward(loss)   # seeded with the persistent ones tensor: no fill, no scale pass (ops.unit_seed)
-        ops.join_side_streams()  # (also flushes weight gradients recorded outside an engine callback)
+        ops.flush_wgrads()  # (weight gradients recorded outside an engine callback)
 
 
 def _seeded(dp):
@@ -352,7 +352,7 @@ class GraphedSegments(object):
                             ops.launch_wgrad_group(recs)
                         wgraphs.append(wg)
                 else:
-                    ops.join_side_streams()
+                    ops.flush_wgrads()
                 self.plan.append((g, dp, wgraphs, sends, keep))
         self._flats = [dp.flat for _, dp in segments if dp is not None and hasattr(dp.flat, "mark_changed")]
         self._seen = {}

@@ -1057,7 +1057,7 @@ def test_batchnorm_with_folded_activation_and_residual(gpu, act):
 def test_batchnorm_finalize_in_apply(gpu, monkeypatch, shape, act):
     """Round 6: the apply kernels finish the split reduction themselves (srk_bn_finalize_apply_act /
     srk_bn_backward_finalize_apply_act: one launch less per BatchNorm and direction).  Against torch's float64 BatchNorm ->
-    activation -> add, and against the separate-launch path (SRK_BN_FIN_APPLY=0): the forward statistics and outputs of the two
+    activation -> add, and against the separate-launch path (ops.BN_FIN_APPLY = False): the forward statistics and outputs of the two
     paths must be bit-equal (same summation order, same z), the backward equal to fp32 rounding; one and several row ranges per
     slab, 1 .. 32 slabs, ragged last range, 64 .. 512 row splits."""
     import torch.nn.functional as F

@@ -288,28 +288,6 @@ def test_trainer_replays_its_step_as_a_graph(gpu, tmp_path):
         assert abs(d0 - d1) <= 1e-3 * abs(d1) + 1e-6 and abs(g0 - g1) <= 1e-3 * abs(g1) + 1e-6, hist
 
 
-def test_wgrad_side_stream_matches_single_stream(gpu):
-    """ops.WGRAD_SIDE_STREAM (weight gradients forked onto a second stream, joined by the autograd-engine callback):
-    same gradients as the single-stream path, readable right after loss.backward()."""
-    pkg = _pkg()
-    x, t = B((4, 3, 12, 12), 71).to(gpu), B((4, 3, 48, 48), 72).to(gpu)
-    grads = []
-    for side in (False, True):
-        pkg.ops.WGRAD_SIDE_STREAM = side
-        try:
-            net = pkg.EDSRNet(3, 64, 4)
-            fill.fill_module(net, 3, 0.5)
-            net.to(gpu).train()
-            flat = pkg.optim.FlatParams(net)
-            flat.zero_grad()
-            pkg.ops.l1_loss(net(x), t).backward()
-            grads.append(flat.grad.clone())
-        finally:
-            pkg.ops.WGRAD_SIDE_STREAM = False
-    assert float(grads[0].abs().max()) > 0
-    assert torch.equal(grads[0], grads[1])
-
-
 def test_fused_skip_gradient_matches_axpby_fan_in(gpu):
     """ops.GradBox (the residual blocks' skip gradient added by conv1's data-gradient epilogue) against the unfused
     fan-in (ops.fork + srk_axpby): same parameter gradients up to summation order, also when backward runs twice over
