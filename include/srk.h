@@ -323,6 +323,35 @@ int srk_loss_forward_backward(int kind, const float* pred, const float* target, 
                               int N, int C, int H, int W, float eps, float grad_scale, float* loss, float* dpred,
                               void* workspace, void* stream);
 
+/* ---- DRCN recursive-supervision head (drcn.py:38-52, 200-215) ---------------------------------
+ * Y = the D reconstructions stacked along the batch axis ([D*N, C, H, W], Y_d = the d-th block of N*C*H*W
+ * elements); Y, x, target, out and dY share one dense layout (NHWC in this package; any, as long as it is the same).
+ * w = the D combine weights (device).  Sum w is computed on the device: nothing syncs with the host. */
+#define SRK_DRCN_MAX_D 32
+/* out = x + (sum_d w_d * Y_d) * (1 / sum_d w_d)   (the inference forward) */
+int srk_drcn_head_forward(const float* Y, const float* x, const float* w, int D, int N, int C, int H, int W,
+                          float* out, void* stream);
+/* The training head in one pass over (Y, x, target) plus a one-block finalize (deterministic: no float atomics):
+ *   out, *loss = a*mean_d MSE(Y_d, t) + (1-a)*MSE(out, t) + *reg_dev, terms = {mean_d MSE(Y_d, t), MSE(out, t)}
+ *   dY_d = s*(a*2(Y_d - t)/(D*M) + g_out*w_d/sum w),  g_out = (1-a)*2(out - t)/M,  M = N*C*H*W, s = grad_scale
+ *   dw_d = dw_beta*dw_d + s * sum_pixels g_out*(Y_d - (out - x)) / sum w
+ * a = *alpha_dev and the regularisation value *reg_dev (NULL: 0) are read on the device, so a captured hipGraph
+ * stays valid when they change.  terms and dw may be NULL.  `workspace`: srk_drcn_workspace_bytes(D). */
+size_t srk_drcn_workspace_bytes(int D);
+int srk_drcn_head_loss(const float* Y, const float* x, const float* target, const float* w, int D, int N, int C, int H,
+                       int W, const float* alpha_dev, const float* reg_dev, float grad_scale, float* out, float* dY,
+                       float* loss, float* terms, float* dw, float dw_beta, void* workspace, size_t workspace_bytes,
+                       void* stream);
+/* Backward of srk_drcn_head_forward for an upstream gradient `dout` of out (same layout as out):
+ *   dY_d = dout * w_d / sum w,  dw_d = dw_beta*dw_d + sum_pixels dout*(Y_d - c) / sum w,  c = out - x
+ * (c is recomputed from Y and w; dw may be NULL).  `workspace`: srk_drcn_workspace_bytes(D). */
+int srk_drcn_head_backward(const float* Y, const float* w, const float* dout, int D, int N, int C, int H, int W,
+                           float* dY, float* dw, float dw_beta, void* workspace, size_t workspace_bytes, void* stream);
+/* *out = scale * sum_i p_i^2, accumulated in fp64 (drcn.py:212-214: the weight-decay term over a flat parameter
+ * buffer).  `workspace`: srk_sumsq_workspace_bytes(). */
+size_t srk_sumsq_workspace_bytes(void);
+int srk_sumsq(const float* p, size_t n, float scale, float* out, void* workspace, void* stream);
+
 /* ---- optimizers over flat fp32 buffers (srcnn.py:79; fsrcnn.py:105-106; vdsr.py:86-90,149;
  *      espcn.py:79; edsr.py:93; srgan.py:147-149) --------------------------------------------- */
 /* torch.optim.SGD: g += wd*p; buf = mom*buf + g (first step: buf = g); p -= lr*(nesterov ? g+mom*buf : buf).

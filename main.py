@@ -17,7 +17,7 @@ def _names(text):
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="MI355X-native SR collection (reference-compatible CLI)")
     p.add_argument('--model_name', type=str, default='SRGAN',
-                   choices=['SRCNN', 'VDSR', 'ESPCN', 'FSRCNN', 'SRGAN', 'LapSRN', 'EDSR'], help='The type of model')
+                   choices=['SRCNN', 'VDSR', 'ESPCN', 'FSRCNN', 'SRGAN', 'LapSRN', 'EDSR', 'DRCN'], help='The type of model')
     p.add_argument('--data_dir', type=str, default='../Data')
     p.add_argument('--train_dataset', type=_names, default=['DIV2K'], help='The name(s) of the training dataset, comma-separated')
     p.add_argument('--test_dataset', type=_names, default=['Set5', 'Set14', 'Urban100'], help='The name(s) of the test dataset, comma-separated')

@@ -103,6 +103,14 @@ _PROTOTYPES = {
     "srk_loss_workspace_bytes": (c_size, []),
     "srk_loss_forward_backward": (c_int, [c_int, c_f, c_f, ctypes.POINTER(ctypes.c_int64), c_int, c_int, c_int,
                                           c_int, c_float, c_float, c_f, c_f, c_vp, c_vp]),
+    "srk_drcn_head_forward": (c_int, [c_f, c_f, c_f, c_int, c_int, c_int, c_int, c_int, c_f, c_vp]),
+    "srk_drcn_workspace_bytes": (c_size, [c_int]),
+    "srk_drcn_head_loss": (c_int, [c_f, c_f, c_f, c_f, c_int, c_int, c_int, c_int, c_int, c_f, c_f, c_float, c_f, c_f,
+                                   c_f, c_f, c_f, c_float, c_vp, c_size, c_vp]),
+    "srk_drcn_head_backward": (c_int, [c_f, c_f, c_f, c_int, c_int, c_int, c_int, c_int, c_f, c_f, c_float, c_vp, c_size,
+                                       c_vp]),
+    "srk_sumsq_workspace_bytes": (c_size, []),
+    "srk_sumsq": (c_int, [c_f, c_size, c_float, c_f, c_vp, c_vp]),
     "srk_sgd_step": (c_int, [c_f, c_f, c_f, c_size, c_float, c_float, c_float, c_int, c_int, c_f, c_f, c_vp]),
     "srk_adam_step": (c_int, [c_f, c_f, c_f, c_f, c_size, c_float, c_float, c_float, c_float, c_float, c_vp, c_f,
                               c_f, c_vp]),

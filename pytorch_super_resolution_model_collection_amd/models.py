@@ -1,5 +1,5 @@
 """Network topologies of the reference (srcnn.py:13-29, espcn.py:13-29, fsrcnn.py:13-55,
-vdsr.py:13-36, edsr.py:13-45, lapsrn.py:14-85, srgan.py:14-81) built from the MI355X blocks.
+vdsr.py:13-36, edsr.py:13-45, lapsrn.py:14-85, srgan.py:14-81, drcn.py:13-59) built from the MI355X blocks.
 
 Same constructor signatures, attribute names (=> state_dict keys), forward semantics and
 `weight_init` distributions.  Differences are purely about launch count: residual adds are handed
@@ -106,6 +106,62 @@ class VDSRNet(nn.Module):
     def weight_init(self):
         for m in self.modules():
             utils.weights_init_kaming(m)
+
+
+class DRCNNet(nn.Module):
+    """drcn.py:13-59 — embedding (two 3x3 conv + ReLU), ONE conv + ReLU applied `num_recursions` times, ONE two-conv
+    reconstruction applied to every hidden state, and the learnable combine weights `w` (a plain tensor that requires
+    grad: not a parameter, not in the state_dict, moved by .to()).  The recursion runs into one stacked buffer
+    (ops.recursive_conv) and the reconstruction on the stacked batch D*N; forward returns (list of the D y_d views,
+    out = x + sum_d w_d y_d / sum w), both differentiable (to every y_d and to w) when autograd records.  The package's
+    trainer takes `reconstructions` and the fused loss head instead (trainers.drcn_step)."""
+
+    def __init__(self, num_channels, base_filter, num_recursions):
+        super(DRCNNet, self).__init__()
+        self.num_recursions = num_recursions
+        self.embedding_layer = nn.Sequential(
+            ConvBlock(num_channels, base_filter, 3, 1, 1, norm=None),
+            ConvBlock(base_filter, base_filter, 3, 1, 1, norm=None))
+        self.conv_block = ConvBlock(base_filter, base_filter, 3, 1, 1, norm=None)
+        self.reconstruction_layer = nn.Sequential(
+            ConvBlock(base_filter, base_filter, 3, 1, 1, activation=None, norm=None),
+            ConvBlock(base_filter, num_channels, 3, 1, 1, activation=None, norm=None))
+        # only the linear combine and the MSE terms lie between the reconstruction convs and the loss (see VDSRNet)
+        for m in self.reconstruction_layer:
+            m.conv._linear_tail = True
+        self.w = (torch.ones(num_recursions) / num_recursions).requires_grad_(True)
+
+    def _apply(self, fn, *args, **kwargs):
+        # .to() / .cuda() move parameters and buffers; w is neither (drcn.py:35-36), so it is moved here
+        out = super(DRCNNet, self)._apply(fn, *args, **kwargs)
+        with torch.no_grad():
+            w = fn(self.w)
+        if w is not self.w:
+            self.w = w.detach().requires_grad_(True)
+        return out
+
+    def weight_init(self):
+        for m in self.modules():
+            utils.weights_init_kaming(m)
+
+    def reconstructions(self, x):
+        """The D reconstructions stacked along the batch axis: [D*N, C, H, W] (y_d = rows d*N .. (d+1)*N-1)."""
+        from .layers import _plan_views, grad_mode
+        h0 = self.embedding_layer(x)
+        c = self.conv_block.conv
+        cfg = ops.ConvCfg(c._s, c._p)
+        if grad_mode(h0, c.weight, c.bias):
+            packed = _plan_views(c, 0)
+        else:
+            packed = c._cache.get(c.weight, c.bias, False, 0)
+        h = ops.recursive_conv(h0, c.weight, c.bias, self.num_recursions, cfg, packed)
+        return self.reconstruction_layer(h)
+
+    def forward(self, x):
+        y = self.reconstructions(x)
+        n = y.shape[0] // self.num_recursions
+        y_d = [y[d * n:(d + 1) * n] for d in range(self.num_recursions)]
+        return y_d, ops.drcn_head(y, x, self.w)
 
 
 def _trunk_with_skip(head_out, trunk, mid_conv, training):

@@ -384,13 +384,23 @@ class bn_partial_request(object):
         return False
 
 
-def conv_forward_raw(x, wp, bias_p, weight_shape_src, cfg, prelu_w=None, residual=None, role="infer", x_nchw=False):
-    """Launch srk_conv2d_forward on already-packed weights. x must be NHWC-dense (or NCHW with x_nchw)."""
+def conv_forward_raw(x, wp, bias_p, weight_shape_src, cfg, prelu_w=None, residual=None, role="infer", x_nchw=False,
+                     out=None):
+    """Launch srk_conv2d_forward on already-packed weights. x must be NHWC-dense (or NCHW with x_nchw).
+    out: an NHWC-dense tensor of the output's shape to write into (e.g. one slice of a stacked buffer); default: a new
+    one."""
     lib = _lib.load()
     d = _make_desc(x.shape, weight_shape_src, cfg, role)
     d.x_nchw = int(bool(x_nchw))
     r = cfg.ps_r if cfg.ps_r > 1 else 1
-    y = _empty_cl(d.N, d.Cout // (r * r), d.OH * r, d.OW * r, x)
+    if out is None:
+        y = _empty_cl(d.N, d.Cout // (r * r), d.OH * r, d.OW * r, x)
+    else:
+        want = (d.N, d.Cout // (r * r), d.OH * r, d.OW * r)
+        if tuple(out.shape) != want or not _is_nhwc_dense(out) or out.dtype != torch.float32 or out.device != x.device:
+            raise RuntimeError("conv: out= must be a dense NHWC fp32 tensor of shape %s on %s (got %s, strides %s)"
+                               % (want, x.device, tuple(out.shape), out.stride()))
+        y = out
     if residual is not None and tuple(residual.shape) != tuple(y.shape):
         raise RuntimeError("conv: residual shape %s != output shape %s" % (tuple(residual.shape), tuple(y.shape)))
     ep = Epilogue(ptr(bias_p), ptr(prelu_w), ptr(residual), cfg.slope, cfg.act,
@@ -1641,3 +1651,286 @@ def img_interp(imgs, scale_factor, interpolation="bicubic"):
     check(lib.srk_img_interp(ptr(x), ptr(y), n, c, h, w, oh, ow, flt, ptr(ws), ws.numel(), stream_ptr()), "srk_img_interp")
     return y[0] if squeeze else y
 
+
+
+# ------------------------------------------------------------------------------------------------
+# DRCN (drcn.py:13-59): the weight-shared recursion and the recursive-supervision head
+# ------------------------------------------------------------------------------------------------
+# The inference net applies ONE conv + ReLU D times in a row and ONE two-conv reconstruction to each of the D hidden
+# states.  Built from ordinary conv calls that is D + 2D weight-gradient records writing the same three dw tensors, and
+# pending_wgrad_groups() (no two records of a group writing one dw) would turn each into a launch group of its own.
+# Instead the D hidden states live in ONE stacked NHWC buffer H[(D+1)*N] (H[0] = h0): the reconstruction runs as
+# ordinary layers on the batch D*N (two launches and one weight-gradient record per conv), and the recursion's weight
+# gradient is ONE record over the stacked batch (x = H[0:D], dy = the stacked gradient, mask = H[1:D+1]).
+def _copy_amax_tag(src, dst):
+    a = getattr(src, "_srk_amax", None)
+    if a is not None and a[1] == _ver(src) and a[2] == _AMAX_EPOCH[0]:
+        _tag_amax(dst, a[0])
+
+
+def _recursion_forward(h0, weight, bias, D, cfg, packed, role):
+    """H[(D+1)*N, F, H, W] with H[0] = h0 and H[d] = relu(conv(H[d-1])), one conv launch per slice.  Returns (H, the
+    D+1 slice views): the views carry the running maxima the kernels leave, so every application takes the arithmetic
+    a chain of separate conv calls would."""
+    n, f, hh, ww = h0.shape
+    H = _empty_cl((D + 1) * n, f, hh, ww, h0)
+    sl = [H[d * n:(d + 1) * n] for d in range(D + 1)]
+    sl[0].copy_(h0)
+    _copy_amax_tag(h0, sl[0])
+    if packed is not None:
+        wp, bp = packed[0], packed[1]
+    else:
+        wp, bp = pack_weight_fwd(weight, False, 0), bias
+    for d in range(1, D + 1):
+        conv_forward_raw(sl[d - 1], wp, bp, weight, cfg, role=role, out=sl[d])
+    return H, sl
+
+
+class _Recursion(torch.autograd.Function):
+    """H[1:] = the D applications of relu(conv(., weight, bias)) to h0, stacked along the batch axis."""
+
+    @staticmethod
+    def forward(ctx, h0, weight, bias, D, cfg, packed):
+        h0 = to_nhwc(h0)
+        H, sl = _recursion_forward(h0, weight, bias, D, cfg, packed, "train_fwd")
+        ctx.sl, ctx.D, ctx.cfg = sl, D, cfg
+        ctx.H = H
+        ctx.weight_ref, ctx.bias_ref = weight, bias
+        ctx.wpb = packed[2] if packed is not None and len(packed) > 2 else None
+        ctx.save_for_backward(weight)
+        return H[h0.shape[0]:]
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        (weight,) = ctx.saved_tensors
+        D, sl, cfg, H = ctx.D, ctx.sl, ctx.cfg, ctx.H
+        n = sl[0].shape[0]
+        g = to_nhwc(g if (_is_nchw_dense(g) or _is_nhwc_dense(g)) else g.contiguous())
+        gs = [g[d * n:(d + 1) * n] for d in range(D)]        # what the reconstruction sends to h_{d+1}
+        U = _empty_cl(D * n, *g.shape[1:], g)                 # u_{d+1}: the whole gradient reaching h_{d+1}
+        us = [U[d * n:(d + 1) * n] for d in range(D)]
+        us[D - 1].copy_(gs[D - 1])
+        d1 = _make_desc(sl[0].shape, weight, cfg, "bwd")
+        wpb = ctx.wpb if ctx.wpb is not None else pack_weight_bwd(weight, False)
+        # the data-gradient chain: u_{d+1} = conv^T(relu'(h_{d+2}) * u_{d+2}) + g_{d+1}, the add in the kernel's epilogue
+        for i in range(D - 2, -1, -1):
+            mask = BwdMask(ptr(sl[i + 2]), 0.0)
+            check(lib.srk_conv2d_backward_data(ctypes.byref(d1), ptr(us[i + 1]), ptr(wpb), ptr(us[i]), ctypes.byref(mask),
+                                               ptr(gs[i]), stream_ptr()), "srk_conv2d_backward_data")
+        dh0 = None
+        if ctx.needs_input_grad[0]:
+            dh0 = _empty_cl(n, *g.shape[1:], g)
+            mask = BwdMask(ptr(sl[1]), 0.0)
+            check(lib.srk_conv2d_backward_data(ctypes.byref(d1), ptr(us[0]), ptr(wpb), ptr(dh0), ctypes.byref(mask), None,
+                                               stream_ptr()), "srk_conv2d_backward_data")
+        dw = db = None
+        has_bias = ctx.bias_ref is not None
+        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
+            # ONE weight gradient over the stacked batch: x = H[0:D], dy = U, mask = relu'(H[1:D+1])
+            xs, ys = H[:D * n], H[n:]
+            dD = _make_desc(xs.shape, weight, cfg, "bwd")
+            wacc = getattr(ctx.weight_ref, "_srk_grad", None)
+            bacc = getattr(ctx.bias_ref, "_srk_grad", None) if has_bias else None
+            flat_mode = wacc is not None and (not has_bias or bacc is not None)
+            if flat_mode and DEFER_WGRAD:
+                key = (dD.N, dD.H, dD.W, dD.Cin, dD.OH, dD.OW, dD.Cout, dD.KH, dD.KW, dD.stride, dD.pad, dD.transposed,
+                       dD.out_pad, dD.algo, dD.dy_ps_r, bacc is not None, str(U.device))
+                _PENDING.append((key, dD, xs, U, ys, 0.0, wacc, bacc))
+                _DEFER["bytes"] += 4 * (xs.numel() + U.numel())
+                if _DEFER["bytes"] > DEFER_MAX_BYTES:
+                    flush_wgrads()
+                elif not _DEFER["queued"]:
+                    _DEFER["queued"] = True
+                    torch.autograd.Variable._execution_engine.queue_callback(_auto_flush)
+            else:
+                mask = BwdMask(ptr(ys), 0.0)
+                ws = torch.empty(max(int(lib.srk_conv2d_backward_weight_workspace_bytes(ctypes.byref(dD))), 16),
+                                 dtype=torch.uint8, device=U.device)
+                if flat_mode:
+                    dwp, dbp, beta = wacc, bacc, 1.0
+                else:
+                    dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
+                    db = torch.empty(dD.Cout, dtype=torch.float32, device=U.device) if has_bias else None
+                    dwp, dbp, beta = dw, db, 0.0
+                check(lib.srk_conv2d_backward_weight(ctypes.byref(dD), ptr(xs), ptr(U), ctypes.byref(mask), ptr(dwp),
+                                                     ptr(dbp), beta, ptr(ws), ws.numel(), stream_ptr()),
+                      "srk_conv2d_backward_weight")
+        return dh0, dw, db, None, None, None
+
+
+def recursive_conv(h0, weight, bias, D, cfg=None, packed=None):
+    """drcn.py:41-44: h_{d+1} = relu(conv(h_d, weight, bias)) for d = 0..D-1 with ONE shared filter.  Returns the D
+    hidden states h_1..h_D as one [D*N, F, H, W] channels_last tensor (h_d = rows (d-1)*N .. d*N-1).  cfg: the conv's
+    stride / padding (default 1 / 1; the activation is always ReLU).  packed: (wp_fwd, bias[, wp_bwd]) of a PackPlan or
+    a no-grad cache.  Under no_grad nothing is kept for a backward pass."""
+    require_cuda(h0, weight, bias)
+    if D < 1:
+        raise ValueError("recursive_conv: D must be >= 1")
+    cfg = ConvCfg(1 if cfg is None else cfg.stride, 1 if cfg is None else cfg.pad, act=ACT_RELU)
+    cout, cin, _, _ = weight.shape
+    if cout != cin or h0.shape[1] != cin:
+        raise RuntimeError("recursive_conv: a recursion needs an F -> F filter and F-channel input (got %s, %s)"
+                           % (tuple(weight.shape), tuple(h0.shape)))
+    from .layers import grad_mode
+    if grad_mode(h0, weight, bias):
+        return _Recursion.apply(h0, weight, bias, int(D), cfg, packed)
+    with torch.no_grad():
+        H, sl = _recursion_forward(to_nhwc(h0), weight, bias, int(D), cfg, packed, "infer")
+        return H[h0.shape[0]:]
+
+
+class _DRCNHead(torch.autograd.Function):
+    """(loss, out, terms) of srk_drcn_head_loss; the gradients to Y and w come from the forward pass (seeded like
+    _Loss).  out and terms carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, Y, x, w, target, alpha, reg, D, need_grad):
+        lib = _lib.load()
+        n = Y.shape[0] // D
+        c, h, wd = Y.shape[1:]
+        out = _empty_cl(n, c, h, wd, Y)
+        dY = torch.empty_like(Y)
+        loss = torch.empty((), dtype=torch.float32, device=Y.device)
+        terms = torch.empty(2, dtype=torch.float32, device=Y.device)
+        ws = torch.empty(max(int(lib.srk_drcn_workspace_bytes(D)), 16), dtype=torch.uint8, device=Y.device)
+        seed = _LOSS_SEED[0]
+        ctx.seed_ptr, ctx.seed_value = (seed[1].data_ptr(), seed[0]) if seed is not None else (0, 1.0)
+        wacc = getattr(w, "_srk_grad", None) if need_grad else None
+        dw = None
+        if need_grad:
+            dw = wacc if wacc is not None else torch.empty_like(w)
+        check(lib.srk_drcn_head_loss(ptr(Y), ptr(x), ptr(target), ptr(w), D, n, c, h, wd, ptr(alpha), ptr(reg),
+                                     ctx.seed_value, ptr(out), ptr(dY), ptr(loss), ptr(terms), ptr(dw), 0.0, ptr(ws),
+                                     ws.numel(), stream_ptr()), "srk_drcn_head_loss")
+        ctx.dY = dY if need_grad else None
+        ctx.dw, ctx.w_in_place = dw, wacc is not None
+        ctx.mark_non_differentiable(out, terms)
+        return loss, out, terms
+
+    @staticmethod
+    def backward(ctx, g, g_out, g_terms):
+        dY, dw = ctx.dY, ctx.dw
+        if dY is None:
+            return None, None, None, None, None, None, None, None
+        gp = g.data_ptr()
+        if ctx.seed_ptr:
+            if gp == ctx.seed_ptr:
+                return dY, None, (None if ctx.w_in_place else dw), None, None, None, None, None
+            g = g / ctx.seed_value
+        elif gp == unit_seed(dY.device).data_ptr():
+            return dY, None, (None if ctx.w_in_place else dw), None, None, None, None, None
+        lib = _lib.load()
+        g = g.contiguous()
+        out = torch.empty_like(dY)
+        check(lib.srk_scale_dev(ptr(dY), ptr(g), ptr(out), dY.numel(), stream_ptr()), "srk_scale_dev")
+        dws = torch.empty_like(dw)
+        check(lib.srk_scale_dev(ptr(dw), ptr(g), ptr(dws), dw.numel(), stream_ptr()), "srk_scale_dev")
+        if ctx.w_in_place:
+            dw.copy_(dws)
+            return out, None, None, None, None, None, None, None
+        return out, None, dws, None, None, None, None, None
+
+
+def _drcn_combine_raw(Y, x, w, D):
+    lib = _lib.load()
+    n = Y.shape[0] // D
+    c, h, wd = Y.shape[1:]
+    out = _empty_cl(n, c, h, wd, Y)
+    check(lib.srk_drcn_head_forward(ptr(Y), ptr(x), ptr(w), D, n, c, h, wd, ptr(out), stream_ptr()),
+          "srk_drcn_head_forward")
+    return out
+
+
+class _DRCNCombine(torch.autograd.Function):
+    """out = x + sum_d w_d Y_d / sum w with its gradients (srk_drcn_head_backward): the head without a target, for a
+    loss the caller composes itself (the reference's own loop, drcn.py:203-215, differentiates `out` directly)."""
+
+    @staticmethod
+    def forward(ctx, Y, x, w, D):
+        ctx.D = D
+        ctx.save_for_backward(Y, w)
+        return _drcn_combine_raw(Y, x, w, D)
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        Y, w = ctx.saved_tensors
+        D = ctx.D
+        n = Y.shape[0] // D
+        c, h, wd = Y.shape[1:]
+        g = to_nhwc(g if (_is_nchw_dense(g) or _is_nhwc_dense(g)) else g.contiguous())
+        dY = torch.empty_like(Y)
+        dw = torch.empty_like(w) if ctx.needs_input_grad[2] else None
+        ws = torch.empty(max(int(lib.srk_drcn_workspace_bytes(D)), 16), dtype=torch.uint8, device=Y.device)
+        check(lib.srk_drcn_head_backward(ptr(Y), ptr(w), ptr(g), D, n, c, h, wd, ptr(dY), ptr(dw), 0.0, ptr(ws),
+                                         ws.numel(), stream_ptr()), "srk_drcn_head_backward")
+        return (dY if ctx.needs_input_grad[0] else None), (g if ctx.needs_input_grad[1] else None), dw, None
+
+
+def _scalar_dev(t, what, like):
+    if t is None:
+        return
+    if t.numel() != 1 or t.dtype != torch.float32 or t.device != like.device:
+        raise RuntimeError("drcn_head: %s must be a one-element float32 tensor on %s (got %s %s on %s)"
+                           % (what, like.device, tuple(t.shape), t.dtype, t.device))
+
+
+def drcn_head(Y, x, w, target=None, alpha=None, reg=None, parts=False):
+    """drcn.py:46-52 and 203-215.  Y: the D reconstructions stacked along the batch axis ([D*N, C, H, W], as the
+    reconstruction layer produces them from recursive_conv's output); x: the net input; w: the D combine weights.
+      target None: out = x + sum_d w_d Y_d / sum w, differentiable in Y, x and w when autograd records (the
+      inference combine otherwise).
+      else: the scalar loss alpha * mean_d MSE(Y_d, t) + (1 - alpha) * MSE(out, t) + reg, with its gradient to Y and w
+      computed in the same pass.  alpha / reg: 0-dim device tensors (read by the kernel: a captured step stays valid
+      when they change); reg = the weight-decay value beta * R (sumsq), None = 0.  A w with a `_srk_grad` view (the
+      trainer's optimizer) gets its gradient written there directly.  parts=True returns (loss, out, [L1, L2])."""
+    D = int(w.numel())
+    require_cuda(Y, x, w, target, alpha, reg)
+    if Y.dim() != 4 or Y.shape[0] % D:
+        raise RuntimeError("drcn_head: Y must be [D*N, C, H, W] with D = %d (got %s)" % (D, tuple(Y.shape)))
+    n = Y.shape[0] // D
+    if tuple(x.shape) != (n,) + tuple(Y.shape[1:]):
+        raise RuntimeError("drcn_head: x %s does not match one reconstruction %s" % (tuple(x.shape), (n,) + tuple(Y.shape[1:])))
+    if w.dtype != torch.float32 or w.device != Y.device:
+        raise RuntimeError("drcn_head: w must be float32 on %s (got %s on %s)" % (Y.device, w.dtype, w.device))
+    Y, x = to_nhwc(Y), to_nhwc(x)
+    w = w if w.is_contiguous() else w.contiguous()
+    from .layers import grad_mode
+    if target is None:
+        if grad_mode(Y, x, w):
+            return _DRCNCombine.apply(Y, x, w, D)
+        return _drcn_combine_raw(Y, x, w.detach(), D)
+    if tuple(target.shape) != tuple(x.shape):
+        raise RuntimeError("drcn_head: target %s vs output %s" % (tuple(target.shape), tuple(x.shape)))
+    if alpha is None:
+        raise RuntimeError("drcn_head: a target needs alpha (a one-element float32 device tensor)")
+    _scalar_dev(alpha, "alpha", Y)
+    _scalar_dev(reg, "reg", Y)
+    loss, out, terms = _DRCNHead.apply(Y, x.detach(), w, to_nhwc(target).detach(), alpha, reg, D, grad_mode(Y, w))
+    return (loss, out, terms) if parts else loss
+
+
+def sumsq(p, scale=1.0, out=None):
+    """scale * sum(p^2) of a dense fp32 tensor (a FlatParams data buffer: the weight-decay value of drcn.py:212-214) as a
+    0-dim device tensor, accumulated in fp64.  out: a 0-dim tensor to write instead of a new one."""
+    require_cuda(p)
+    p = p.detach()
+    if not p.is_contiguous():
+        raise RuntimeError("sumsq: p must be contiguous")
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty((), dtype=torch.float32, device=p.device)
+    elif out.numel() != 1 or out.dtype != torch.float32 or out.device != p.device:
+        raise RuntimeError("sumsq: out must be a one-element float32 tensor on %s (got %s %s on %s)"
+                           % (p.device, tuple(out.shape), out.dtype, out.device))
+    ws = torch.empty(int(lib.srk_sumsq_workspace_bytes()), dtype=torch.uint8, device=p.device)
+    check(lib.srk_sumsq(ptr(p), p.numel(), float(scale), ptr(out), ptr(ws), stream_ptr()), "srk_sumsq")
+    return out
+
+
+def add_scaled_(a, b, beta):
+    """a += beta * b in place (srk_axpby; flat buffers: DRCN's weight-decay gradient 2 * beta * theta)."""
+    lib = _lib.load()
+    check(lib.srk_axpby(ptr(a), ptr(b), ptr(a), a.numel(), 1.0, float(beta), stream_ptr()), "srk_axpby")
+    return a

@@ -303,6 +303,36 @@ class Adam(_FlatOptimizer):
         f.mark_changed()
 
 
+class TensorAdam(object):
+    """torch.optim.Adam over ONE plain tensor that is not a module parameter (DRCN's combine weights `w`, the second
+    param group of drcn.py:108-111), on srk_adam_step: its own step count (advanced like the model group's), its learning
+    rate a device scalar that `param_groups[0]['lr'] /= 10` reaches.  The gradient lives in a persistent buffer,
+    `t._srk_grad` (= `t.grad`), which the kernel that computes it overwrites every step (ops.drcn_head)."""
+
+    def __init__(self, t, lr, betas=(0.9, 0.999), eps=1e-8):
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+            raise RuntimeError("TensorAdam: a contiguous fp32 GPU tensor is required")
+        self.t = t
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.grad = torch.zeros_like(t)
+        t._srk_grad = self.grad
+        t.grad = self.grad
+        self.exp_avg = torch.zeros_like(t)
+        self.exp_avg_sq = torch.zeros_like(t)
+        self.step_dev = torch.zeros(2, dtype=torch.int32, device=t.device)
+        self.lr_dev = torch.tensor([float(lr)], dtype=torch.float32, device=t.device)
+        self.param_groups = [_Group(self, lr=float(lr))]
+
+    def _set_lr(self, v):
+        self.lr_dev.fill_(float(v))
+
+    def step(self):
+        lib = _lib.load()
+        check(lib.srk_adam_step(ptr(self.t.detach()), ptr(self.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq),
+                                self.t.numel(), 0.0, self.betas[0], self.betas[1], self.eps, 0.0, ptr(self.step_dev),
+                                ptr(self.lr_dev), None, stream_ptr()), "srk_adam_step")
+
+
 def make_optimizer(kind, flat, lr):
     """The reference's per-model optimizer choices."""
     if kind == "srcnn":      # srcnn.py:79
@@ -311,7 +341,7 @@ def make_optimizer(kind, flat, lr):
         return SGD(flat, lr, momentum=0.9)
     if kind == "vdsr":       # vdsr.py:86-90
         return SGD(flat, lr, momentum=0.9, weight_decay=1e-4)
-    if kind in ("espcn", "lapsrn"):   # espcn.py:79, lapsrn.py:135
+    if kind in ("espcn", "lapsrn", "drcn"):   # espcn.py:79, lapsrn.py:135, drcn.py:111 (the model group)
         return Adam(flat, lr)
     if kind in ("edsr", "srgan_g"):   # edsr.py:93, srgan.py:147
         return Adam(flat, lr, betas=(0.9, 0.999), eps=1e-8)

@@ -1,7 +1,7 @@
 """Trainer objects with the reference's surface — MODEL(args).train() / test() / test_single(fn) /
-save_model(epoch) / load_model() — for SRCNN, ESPCN, FSRCNN, VDSR, EDSR, LapSRN and SRGAN
+save_model(epoch) / load_model() — for SRCNN, ESPCN, FSRCNN, VDSR, EDSR, LapSRN, SRGAN and DRCN
 (srcnn.py:32-281, espcn.py:32-281, fsrcnn.py:58-307, vdsr.py:39-301, edsr.py:48-351,
-lapsrn.py:88-349, srgan.py:93-528), on the MI355X hot path.
+lapsrn.py:88-349, srgan.py:93-528, drcn.py:62-355), on the MI355X hot path.
 
 Kept from the reference: per-model hyper-parameters hard-coded in train() (e.g. EDSR base_filter 64 /
 16 residuals, edsr.py:87; VDSR momentum 0.9 / wd 1e-4 / clip 0.4, vdsr.py:86-90,149), the epoch-wise
@@ -42,11 +42,14 @@ def synthetic_loader(kind, args, steps, device, seed=1234):
 #   vdsr.py:127-129  /10 every 20     edsr.py:131-133  /2 every 40     lapsrn.py:173-175  /10 every 100
 #   srgan.py:239-244 /10 every 20 (G and D)            srcnn.py / espcn.py / fsrcnn.py: no decay
 LR_DECAY = {"vdsr": (20, 10.0), "edsr": (40, 2.0), "lapsrn": (100, 10.0), "srgan": (20, 10.0)}
+# drcn.py:164-168 /10 every 20 (both param groups).  Kept apart from LR_DECAY, whose content is the seven-trainer table
+# the host tests pin; apply_lr_decay reads both.
+LR_DECAY_DRCN = {"drcn": (20, 10.0)}
 
 
 def apply_lr_decay(kind, epoch, *optimizers):
     """The reference's `if (epoch+1) % N == 0: param_group['lr'] /= F` (see LR_DECAY).  Returns True if it decayed."""
-    rule = LR_DECAY.get(kind)
+    rule = LR_DECAY.get(kind) or LR_DECAY_DRCN.get(kind)
     if rule is None or (epoch + 1) % rule[0] != 0:
         return False
     for opt in optimizers:
@@ -80,6 +83,14 @@ class _Trainer(object):
     def lr_decay(self, epoch, opt):
         apply_lr_decay(self.kind, epoch, opt)
 
+    def build_step(self):
+        """(flat parameters, optimizer, DataParallel or None, eager step function) of the freshly built model."""
+        return trainers.build(self.kind, self.model, self.lr, use_dp=self.world > 1)
+
+    def begin_epoch(self, epoch):
+        """Top of every epoch, before its first step: the reference's LR decay (and any per-model schedule)."""
+        self.lr_decay(epoch, self.optimizer)
+
     def prepare(self, inp, target):
         """(input, target) of the data loader -> the tensors the train step consumes, on the device:
           SRCNN   y = img_interp(input, r) (bicubic), x = shave(target, 8)               (srcnn.py:116-125)
@@ -88,7 +99,7 @@ class _Trainer(object):
         utils.img_interp is the bit-exact GPU form of the reference's per-image PIL loop."""
         if self.kind == "srcnn":
             return utils.img_interp(inp, self.scale_factor), utils.shave(target, 8).contiguous()
-        if self.kind == "vdsr":
+        if self.kind in ("vdsr", "drcn"):    # drcn.py:183-190 as vdsr.py
             return utils.img_interp(inp, self.scale_factor), target
         if self.kind == "lapsrn":
             return inp, utils.img_interp(target, 1 / self.scale_factor * 2), target
@@ -147,8 +158,7 @@ class _Trainer(object):
         self.model.weight_init()
         self.model.to(self.device).train()
         utils.print_network(self.model) if self.rank == 0 else None
-        self.flat, self.optimizer, self.dp, step = trainers.build(self.kind, self.model, self.lr,
-                                                                  use_dp=self.world > 1)
+        self.flat, self.optimizer, self.dp, step = self.build_step()
         avg_loss = []
         self.data_source = "loader"
         if loader is None:
@@ -157,7 +167,7 @@ class _Trainer(object):
         self._announce_data()
         trainers.quiesce_gc()    # no full cyclic collection (~80 ms) inside a step from here on
         for epoch in range(self.num_epochs):
-            self.lr_decay(epoch, self.optimizer)
+            self.begin_epoch(epoch)
             batches = loader if loader is not None else synthetic_loader(self.kind, self.args, self.steps_per_epoch,
                                                                          self.device, 1234 + epoch * self.world + self.rank)
             total, n = torch.zeros((), device=self.device), 0
@@ -215,7 +225,7 @@ class _Trainer(object):
 
     def _net_input(self, x):
         """SRCNN / VDSR feed the bicubic-upsampled image to the net (srcnn.py:145, vdsr.py:160)."""
-        return utils.img_interp(x, self.scale_factor) if self.kind in ("srcnn", "vdsr") else x
+        return utils.img_interp(x, self.scale_factor) if self.kind in ("srcnn", "vdsr", "drcn") else x
 
     def _infer(self, x):
         self.model.eval()
@@ -453,4 +463,73 @@ class SRGAN(_Trainer):
         return False
 
 
-TRAINERS = {"SRCNN": SRCNN, "VDSR": VDSR, "ESPCN": ESPCN, "FSRCNN": FSRCNN, "SRGAN": SRGAN, "LapSRN": LapSRN, "EDSR": EDSR}
+class DRCN(_Trainer):
+    """drcn.py:62-355: F = 256 and D = 16 hard-coded as in the reference (drcn.py:103-104); Adam over two param groups
+    (the model, w) at the same rate; alpha decays from 1 by 1/25 at the top of every epoch, beta = 1e-3."""
+    kind = "drcn"
+    base_filter, num_recursions = 256, 16
+
+    def __init__(self, args):
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise NotImplementedError("DRCN trains on one GPU: data parallelism is not implemented for it (launch "
+                                      "main.py without torch.distributed.run)")
+        super(DRCN, self).__init__(args)
+        self.loss_alpha = 1.0
+        self.loss_alpha_zero_epoch = 25
+        self.loss_alpha_decay = self.loss_alpha / self.loss_alpha_zero_epoch
+        self.loss_beta = 0.001
+
+    def build_model(self):
+        return models.DRCNNet(self.num_channels, self.base_filter, self.num_recursions)
+
+    def next_alpha(self):
+        """drcn.py:171: the iterated `loss_alpha = max(0, loss_alpha - loss_alpha_decay)` of the top of every epoch."""
+        self.loss_alpha = max(0.0, self.loss_alpha - self.loss_alpha_decay)
+        return self.loss_alpha
+
+    def build_step(self):
+        """Adam over the model's flat buffer and over w (drcn.py:108-111), alpha and the weight-decay value as device
+        scalars the (captured) head reads; the base loop replays the step as a graph (trainers.GraphedFn)."""
+        self.flat = optim.FlatParams(self.model)
+        self.optimizer = optim.make_optimizer("drcn", self.flat, self.lr)
+        self.w_optimizer = optim.TensorAdam(self.model.w, self.lr)
+        self.alpha_dev = torch.ones((), dtype=torch.float32, device=self.device)
+        self.reg_dev = torch.zeros((), dtype=torch.float32, device=self.device)
+        self.loss_alpha = 1.0
+        step = trainers.drcn_step(self.model, self.optimizer, self.w_optimizer, self.alpha_dev, self.loss_beta,
+                                  self.reg_dev)
+        return self.flat, self.optimizer, None, step
+
+    def lr_decay(self, epoch, opt):
+        apply_lr_decay(self.kind, epoch, opt, self.w_optimizer)   # both param groups (drcn.py:164-168)
+
+    def begin_epoch(self, epoch):
+        super(DRCN, self).begin_epoch(epoch)
+        self.alpha_dev.fill_(self.next_alpha())     # drcn.py:171, read by the (captured) head kernel
+
+    def _w_name(self, epoch):
+        model_dir = os.path.join(self.save_dir, 'model')
+        os.makedirs(model_dir, exist_ok=True)
+        if epoch is not None:
+            return model_dir + '/' + self.model_name + '_w_epoch_%d.pkl' % epoch
+        return model_dir + '/' + self.model_name + '_w.pkl'
+
+    def save_model(self, epoch=None):   # drcn.py:327-339
+        super(DRCN, self).save_model(epoch)
+        torch.save(self.model.w.detach().cpu().clone(), self._w_name(epoch))
+
+    def load_model(self):   # drcn.py:341-355: the parameters and w, each if its file exists
+        loaded = super(DRCN, self).load_model()
+        name = self._w_name(None)
+        if os.path.exists(name):
+            w = torch.load(name)
+            with torch.no_grad():
+                self.model.w.copy_(w.reshape(self.model.w.shape))
+            print('Trained weight is loaded.')
+        else:
+            print('No weight exists to load.')
+        return loaded
+
+
+TRAINERS = {"SRCNN": SRCNN, "VDSR": VDSR, "ESPCN": ESPCN, "FSRCNN": FSRCNN, "SRGAN": SRGAN, "LapSRN": LapSRN, "EDSR": EDSR,
+            "DRCN": DRCN}

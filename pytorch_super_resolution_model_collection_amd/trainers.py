@@ -133,6 +133,26 @@ def lapsrn_step(model, opt, dp=None):
     return step
 
 
+def drcn_step(model, opt, w_opt, alpha_dev, beta, reg_dev=None):
+    """drcn.py:196-221: zero_grad -> forward -> loss = alpha * mean_d MSE(y_d, t) + (1 - alpha) * MSE(out, t)
+    + beta * sum_theta sum theta^2 (R of the parameters BEFORE the update; w excluded) -> backward -> Adam on the model's
+    flat buffer and on w.  alpha_dev: the epoch's alpha as a 0-dim device tensor (the trainer rewrites it between epochs,
+    a captured step reads the new value).  The reg term's gradient 2 * beta * theta is added to the flat gradient after
+    the backward pass (one srk_axpby), so `.grad` is what the reference's loss.backward() leaves."""
+    reg_dev = torch.zeros((), dtype=torch.float32, device=alpha_dev.device) if reg_dev is None else reg_dev
+
+    def step(inp, target):
+        opt.zero_grad()
+        ops.sumsq(opt.flat.data, beta, out=reg_dev)
+        loss = ops.drcn_head(model.reconstructions(inp), inp, model.w, target, alpha_dev, reg_dev)
+        _backward(loss, None)
+        ops.add_scaled_(opt.flat.grad, opt.flat.data, 2.0 * beta)
+        opt.step()
+        w_opt.step()
+        return loss
+    return step
+
+
 def srgan_step(G, D, g_opt, d_opt, g_dp=None, d_dp=None, feature_extractor=None, lazy_pack=False, prune_dead_grads=False):
     """srgan.py:249-310 with [B,1] labels.  As in the reference the D step back-propagates through G
     (G is not detached, srgan.py:279) and the G step accumulates into D's gradients, which the
