@@ -82,7 +82,7 @@ __device__ __forceinline__ float exp2i(int k) {  // 2^k for -126 <= k <= 127 (cl
 // Maximum over the 64 lanes, the same value in every lane.  Rotations inside the rows of 16 lanes as DPP operands of
 // v_max (no LDS traffic), then the four row results through v_readlane.  (Until round 4 this was six dependent
 // __shfl_xor = ds_bpermute_b32 round trips, ~400 clocks in front of every running-maximum commit and inside the fused
-// residual block's intermediate scale, tools/res2_prof.py.)
+// residual block's intermediate scale)
 // PRECONDITION: all 64 lanes active (full EXEC) -- v_readlane of an inactive lane returns whatever its register holds.
 // Every caller (amax_commit, amax_commit_block, the fused residual block's intermediate scale) runs convergent; a call under
 // lane divergence or behind a per-lane early return would feed garbage into the running maximum.

@@ -45,7 +45,6 @@ struct BfdParams {
   int NB;            // output channels per block in the prepared layout
   int NPIXp;         // LDS stride of an 8-channel group in 16-byte slots: >= the halo pixels, chosen with `perm` (bfd_lds_plan)
   unsigned long long perm;  // lane column (lane & 15) -> pixel of a 16-pixel M tile, 4 bits each
-  int dbg;
   int allc;          // small problems: every channel chunk of the halo staged up front (one load latency, one barrier)
   int cpr;           // chunks staged per barrier round: ICc (allc), 2 (K-split without allc) or 1
   const float* w_descale;  // F16 kernels: trailer of the fp16 filter section {2^-kw, 2^kw}
@@ -342,7 +341,6 @@ __device__ __forceinline__ void bfd_body(const BfdParams& B, const int bx) {
   // filter fragments of the head position -> registers (past the end the walk re-reads the last chunk: valid
   // memory, never used)
   auto load_b = [&](const Walk& h, uint4 (&dst)[NP][NTW]) {
-    if (SRK_KDBG(B.dbg) & 8) return;
     const int hc = h.cc < B.ICc ? h.cc : B.ICc - 1;
     const size_t slot = (size_t)(h.wt * B.ICc + hc) * B.OCb + ocbi;
     const uint4* w = B.wq + slot * (size_t)(8 * NB) + wlane;
@@ -359,7 +357,7 @@ __device__ __forceinline__ void bfd_body(const BfdParams& B, const int bx) {
   };
   // one tap: A fragments from LDS, 3 or 6 MFMA passes against the given filter fragments
   auto tap_mfma = [&](const uint4* halc, int toff, const uint4 (&bf)[NP][NTW]) {
-    if (wave_live && !(SRK_KDBG(B.dbg) & 4)) {
+    if (wave_live) {
       const uint4* hb = halc + toff;
       uint4 a[NP][4];
 #pragma unroll
@@ -418,7 +416,7 @@ __device__ __forceinline__ void bfd_body(const BfdParams& B, const int bx) {
       const int cfirst = seg * cpr;
       const int cend = cfirst + cpr < B.ICc ? cfirst + cpr : B.ICc;
       if (seg) __syncthreads();  // previous round's halo fully consumed
-      for (int c2 = cfirst; c2 < cend && !(SRK_KDBG(B.dbg) & 1); ++c2) {
+      for (int c2 = cfirst; c2 < cend; ++c2) {
         if (P.mask_y)
           bfd_stage_halo_t<true, NTHR, NP, SIT, F16>(B, hal + (c2 - cfirst) * cstride, n, r0, c0, c2 * 32, sx);
         else
@@ -456,10 +454,6 @@ __device__ __forceinline__ void bfd_body(const BfdParams& B, const int bx) {
             for (int nt = 0; nt < NTW; ++nt) bq[d][p][nt] = bq[d + 1][p][nt];
       }
     }
-  }
-  if (SRK_KDBG(B.dbg) & 2) {
-    if (acc[0][0][0] == 123.456f) P.out[0] = 1.f;  // keep the accumulators live
-    return;
   }
   if (KS > 1) {
     // partial sums of the odd-chunk group -> LDS (the halo is dead) -> added by the even-chunk group, in a fixed order
@@ -673,23 +667,13 @@ static int bfd_launch(BfdParams B, int budget_bytes, hipStream_t s) {
       if (lds < red_bytes) lds = red_bytes;
       static LdsLimit lim2;
       lim2.ensure(reinterpret_cast<const void*>(&k_conv_bfd<NTW, NPW, NOW, NP, PF, 2, F16, OCCX>), lds);
-      if (SRK_KDBG(B.dbg) & 32)
-        fprintf(stderr, "[srk] k_conv_bfd<%d,%d,%d,%d,%d> K-split 2: lds %zu B, grid %u x %u, tile %dx%d halo %dx%d\n", NTW, NPW,
-                NOW, NP, PF, lds, grid.x, grid.y, P.TH, P.TW, P.HH, P.HW);
       note_kernel("k_conv_bfd<%d,%d,%d,%d,%d,2%s>", NTW, NPW, NOW, NP, PF, F16 ? ",f16" : "");
       hipLaunchKernelGGL((k_conv_bfd<NTW, NPW, NOW, NP, PF, 2, F16, OCCX>), grid, dim3(64 * NPW * NOW * 2), lds, s, B);
       return check_launch("conv_bfd");
     }
   }
   static LdsLimit lim;
-  const void* fn = reinterpret_cast<const void*>(&k_conv_bfd<NTW, NPW, NOW, NP, PF, 1, F16, OCCX>);
-  lim.ensure(fn, lds);
-  if (SRK_KDBG(B.dbg) & 32) {
-    int nb = -1;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * NPW * NOW, lds);
-    fprintf(stderr, "[srk] k_conv_bfd<%d,%d,%d,%d,%d>: lds %zu B, grid %u x %u, occupancy %d blocks/CU, tile %dx%d halo %dx%d\n",
-            NTW, NPW, NOW, NP, PF, lds, grid.x, grid.y, nb, P.TH, P.TW, P.HH, P.HW);
-  }
+  lim.ensure(reinterpret_cast<const void*>(&k_conv_bfd<NTW, NPW, NOW, NP, PF, 1, F16, OCCX>), lds);
   note_kernel("k_conv_bfd<%d,%d,%d,%d,%d,1%s%s>", NTW, NPW, NOW, NP, PF, F16 ? ",f16" : "", OCCX == 3 ? ",occ3" : (OCCX == 4 ? ",occ4" : ""));
   hipLaunchKernelGGL((k_conv_bfd<NTW, NPW, NOW, NP, PF, 1, F16, OCCX>), grid, dim3(64 * NPW * NOW), lds, s, B);
   return check_launch("conv_bfd");
@@ -785,10 +769,6 @@ bool conv_bfd_gather_supported(const GatherConv& g, const Epi& ep) {
   return true;
 }
 
-static int bfd_dbg() {
-  return SRK_EXP_INT("SRK_DBG", 0);
-}
-
 // small problem: fewer pixels than two resident 256-pixel tiles per CU -> 64-pixel blocks whose waves
 // split the output channels
 bool conv_bfd_small_problem(const GatherConv& g) {
@@ -810,7 +790,6 @@ static int bfd_launch_phase(MfmaConvParams P, const uint4* wq, const uint4* wq3,
   B.OCb = (P.OC + 63) / 64;
   B.wq = wq;
   B.wq3 = wq3;
-  B.dbg = bfd_dbg();
   B.P = P;
   constexpr int BIG = kLdsBudgetBytes, SMALL = 36 * 1024;
   if (small) {
@@ -833,9 +812,6 @@ static int bfd_launch_phase(MfmaConvParams P, const uint4* wq, const uint4* wq3,
         const int cfg = env_int("SRK_BFD_F16_CFG", 1);
         if (cfg == 1) return bfd_launch<2, 2, 2, NP, 1, true, 3>(B, BIG, s);
         if (cfg == 2) return bfd_launch<2, 2, 2, NP, 1, true, 4>(B, BIG, s);
-      } else if constexpr (NP == 2) {
-        const int cfg3 = SRK_EXP_INT("SRK_BFD_X3_CFG", 0);   // experiment: the same block for bf16x3
-        if (cfg3 == 1) return bfd_launch<2, 2, 2, NP, 1, false, 3>(B, BIG, s);
       }
       return bfd_launch<4, 4, 1, NP, 1, F16>(B, BIG, s);
   }
@@ -879,7 +855,6 @@ int conv_bfd_gather(const GatherConv& g, const float* in, const float* wp, float
       base.OCb = (g.OC + 63) / 64;
       base.wq = wq;
       base.wq3 = wq3;
-      base.dbg = bfd_dbg();
       const int rc = planes == 3 ? bfd_launch_small_multi<4, 3>(phases, nph, base, s) : bfd_launch_small_multi<4, 2>(phases, nph, base, s);
       if (rc != -1) return rc;
     }

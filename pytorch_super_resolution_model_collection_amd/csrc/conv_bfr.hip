@@ -2,8 +2,8 @@
 // filter stays in LDS (c2: ESPCN 64 -> 32 and 32 -> 48 + pixel shuffle).  Same roles and products (f16x3 / bf16x3:
 // x = h + m, w_h x_m + w_m x_h + w_h x_h, fp32 accumulate, chunks in order), two structural changes:
 //
-// 1. Half the LDS bytes per MFMA.  Round 5's constant-ablation builds of the barrier kernel's tap loop (tools/
-//    ring_ablate.sh) on the 64 -> 32 layer: its fragment reads alone run 207 us, its MFMAs alone 261 us, both
+// 1. Half the LDS bytes per MFMA.  Round 5's constant-ablation builds of the barrier kernel's tap loop (DESIGN
+//    11.1) on the 64 -> 32 layer: its fragment reads alone run 207 us, its MFMAs alone 261 us, both
 //    together 303 - 326 us with no global memory traffic at all -- a 32-pixel x 32-channel wave tile reads 8 fragments
 //    per 12 MFMAs (0.67 KB per MFMA: 2/3 of the LDS's peak at full matrix rate, and the LDS reaches ~2/3 of its peak), so
 //    the consumers were LDS-bound before the first byte left HBM.  Here a consumer wave owns 4 ROWS x 16 columns of an
@@ -30,36 +30,15 @@
 
 namespace srk {
 
-// Ablation builds (tools/ring_ablate.sh; release: 0): 1 no global loads, 2 no stores, 4 no MFMAs, 8 no fragment reads,
-// 16 no producer split + LDS commit, 32 no parking arithmetic
-#ifndef BFR_ABL
-#define BFR_ABL 0
-#endif
-#ifndef BFR_NSET
-#define BFR_NSET 3
-#endif
 constexpr int BFR_MAXBUF = 6;
 constexpr int BFR_CNT_BYTES = 128;  // counters behind the ring: full[6], free[6]; fused: scale exponents, staging / compute counts, tile maxima
 constexpr int BFR_PIT = 3;  // producer register batches per set: the 180-pixel halo in 64-pixel batches
-constexpr int BFR_NSET_C = BFR_NSET;  // register sets = stages of loads in flight per producer wave
+constexpr int BFR_NSET = 3;  // register sets = stages of loads in flight per producer wave
 constexpr unsigned BFR_SPIN_CAP = 1u << 18;
 constexpr int BFR_TH = 8, BFR_TW = 16, BFR_HH = 10, BFR_HW = 18, BFR_NPIX = 180;
-constexpr int BFR_NPIXP = 190;  // = bfw_group_stride(180, perm): +-2 (mod 16), conflict-free fragment reads and halo writes
+constexpr int BFR_NPIXP = 190;  // = bfw_group_stride(180): +-2 (mod 16), conflict-free fragment reads and halo writes
 
 __device__ unsigned g_bfr_timeouts = 0;
-
-// Profiling builds (-DBFR_PROF, tools/ring_prof.py): s_memtime sums per role -- 16 int64 per block:
-// [0..5] first producer wave {wait free, wait loads, split + commit, signal, issue, total}, [8..13] consumer wave 0
-// {wait full, steps, signal, park, total, stages}
-// (-DBFR_PROF=2: only the loop totals -- two stamps per wave, the stream itself is the release one)
-#ifdef BFR_PROF
-static long long* g_bfr_prof = nullptr;
-#define BFR_CLK() (BFR_PROF == 2 ? 0ll : clock64())
-#define BFR_CLK_TOTAL() clock64()
-#else
-#define BFR_CLK() 0ll
-#define BFR_CLK_TOTAL() 0ll
-#endif
 
 typedef __attribute__((address_space(3))) unsigned bfr_cnt_t;
 
@@ -73,10 +52,6 @@ __device__ __noinline__ void bfr_fail(int lane) {
   }
   __builtin_trap();
 }
-
-// (ablation builds) a fragment the compiler must treat as written / as read
-__device__ __forceinline__ void bfr_touch(uint4& u) { asm volatile("" : "+v"(u.x), "+v"(u.y), "+v"(u.z), "+v"(u.w)); }
-__device__ __forceinline__ void bfr_use(const uint4& u) { asm volatile("" ::"v"(u.x), "v"(u.y), "v"(u.z), "v"(u.w)); }
 
 __device__ __forceinline__ unsigned bfr_peek(bfr_cnt_t* p) {
   return (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
@@ -97,12 +72,8 @@ __device__ __forceinline__ void bfr_wait(bfr_cnt_t* p, unsigned target, bool& de
 }
 // One count behind every LDS access this wave has issued so far.  No s_waitcnt: the LDS executes the operations of one wave
 // in the order they were issued, so whoever sees the count sees the writes (or finds the reads done) that precede it.
-// (BFR_SIGNAL_WAIT=1 builds drain the wave's LDS queue first.)
-#ifndef BFR_SIGNAL_WAIT
-#define BFR_SIGNAL_WAIT 0
-#endif
 __device__ __forceinline__ void bfr_signal(bfr_cnt_t* p) {
-  if constexpr (BFR_SIGNAL_WAIT != 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); else asm volatile("" ::: "memory");
+  asm volatile("" ::: "memory");
   if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   asm volatile("" ::: "memory");
 }
@@ -130,16 +101,13 @@ __global__ __launch_bounds__(512, 2) void k_conv_bfr(BfwParams B) {
   constexpr int NCW = 4, NGW = 2, NPW = 4;  // consumer waves (two groups of NGW), producer waves
   constexpr int NPS = NPW;                  // producer waves that fill one slot
   constexpr int NTHR = 64 * (NCW + NPW);
-  constexpr int PSTEP = 16 * NPW, PIT = BFR_PIT, NSET = BFR_NSET_C;
+  constexpr int PSTEP = 16 * NPW, PIT = BFR_PIT, NSET = BFR_NSET;
   constexpr int TH = BFR_TH, TW = BFR_TW, HW = BFR_HW, NPIX = BFR_NPIX, NPIXP = BFR_NPIXP;
   constexpr int MR = TH / NGW;          // output rows per consumer wave (4)
   constexpr int WSLOT = 8 * NB;         // uint4 per (tap, chunk): [plane 2][group 4][NB]
   constexpr int HBUF = 8 * NPIXP;       // uint4 per halo slot: [plane 2][group 4][NPIXP]
   constexpr int PLANE_B = 4 * NPIXP, PLANE_A = 4 * NB;
   extern __shared__ __attribute__((aligned(16))) uint4 smem4[];
-#ifdef BFR_PROF
-  const long long cw_entry = wall_clock64();
-#endif
   const MfmaConvParams& P = B.P;
   uint4* wl = smem4;
   uint4* hal0 = smem4 + 9 * ICC * WSLOT;
@@ -156,10 +124,6 @@ __global__ __launch_bounds__(512, 2) void k_conv_bfr(BfwParams B) {
   }
   (void)sx;
 
-#ifdef BFR_PROF
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  const long long cw_p1 = wall_clock64();   // arguments, input maximum, descale read
-#endif
   const int xcd = blockIdx.x & 7;
   int bi = blockIdx.x >> 3, sl = 0;  // (not CV: one slice, the whole filter is resident)
   if constexpr (CV) {
@@ -168,7 +132,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_bfr(BfwParams B) {
   }
   // The filter into LDS: every load of a thread in flight before its first LDS store.  (As a plain loop the compiler waits for
   // each 16-byte load in turn -- global_load; s_waitcnt vmcnt(0); ds_write -- nine L2 round trips in a row, 4.1 - 4.7 us of the
-  // 6.5 - 8.5 us between a block's first instruction and its first tile: tools/ring_prof.py, round 6.  Native vectors: an
+  // 6.5 - 8.5 us between a block's first instruction and its first tile: DESIGN 13.8.  Native vectors: an
   // array of HIP's uint4 structs ends up in scratch memory here.)
   {
     constexpr int FW = 9 * ICC * WSLOT, NLD = (FW + NTHR - 1) / NTHR;
@@ -199,10 +163,6 @@ __global__ __launch_bounds__(512, 2) void k_conv_bfr(BfwParams B) {
     });
   }
   if (tid < 2 * BFR_MAXBUF) cnt[tid] = 0u;
-#ifdef BFR_PROF
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  const long long cw_p2 = wall_clock64();   // filter in LDS
-#endif
   // tiles of this block (XCD-aware contiguous ranges, as in k_conv_bfw): first, first + tstride, ... (count of them)
   const int nblk = gridDim.x;
   int first, count;
@@ -347,20 +307,11 @@ __global__ __launch_bounds__(512, 2) void k_conv_bfr(BfwParams B) {
           ok = it_rel[k] >= 0 && ch_on && (unsigned)(ixb + it_hx[k]) < (unsigned)P.IW;
           o = ok ? (unsigned)(obase + it_rel[k]) : OOB;
         }
-        if constexpr (BFR_ABL & 1) {
-          v[k][0] = v[k][1] = (f32x4){(float)o, 1.f, 2.f, 3.f};
-        } else {
-          v[k][0] = bload(rin, o);
-          v[k][1] = bload(rin, o + 16u);
-        }
+        v[k][0] = bload(rin, o);
+        v[k][1] = bload(rin, o + 16u);
       }
     };
     auto commit = [&](const f32x4 (&v)[PIT][2], uint4* hal) {
-      if constexpr (BFR_ABL & 16) {
-#pragma unroll
-        for (int k = 0; k < PIT; ++k) asm volatile("" ::"v"(v[k][0]), "v"(v[k][1]));
-        return;
-      }
 #pragma unroll
       for (int k = 0; k < PIT; ++k) {
         const int hq = hp0 + PSTEP * k;
@@ -383,42 +334,21 @@ __global__ __launch_bounds__(512, 2) void k_conv_bfr(BfwParams B) {
     __syncthreads();  // filter and counters visible
     int b = 0;
     unsigned k = 0;  // slot and use count of the stage about to be committed
-    long long pt[5] = {0, 0, 0, 0, 0};
-    const long long pt_begin = BFR_CLK_TOTAL();
     for (int s = 0; s < S; s += NSET) {
       srk_static_for<0, NSET>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
-        const long long c0 = BFR_CLK();
         if (s + i < S) {
           bfr_wait(cnt + BFR_MAXBUF + b, NGW * k, dead);
-          const long long c1 = BFR_CLK();
-#ifdef BFR_PROF
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PIT * (NSET - 1)) : "memory");
-#endif
-          const long long c2 = BFR_CLK();
           commit(pv[i], hal0 + (size_t)b * HBUF);
-          const long long c3 = BFR_CLK();
           bfr_signal(cnt + b);
-          const long long c4 = BFR_CLK();
-          pt[0] += c1 - c0; pt[1] += c2 - c1; pt[2] += c3 - c2; pt[3] += c4 - c3;
           if (++b == nbuf) {
             b = 0;
             ++k;
           }
         }
-        const long long c5 = BFR_CLK();
         issue(pv[i]);  // stage s + i + NSET (unconditional: the waits of the next commits stay countable)
-        pt[4] += BFR_CLK() - c5;
       });
     }
-#ifdef BFR_PROF
-    if (B.prof && tid == 64 * NCW) {
-      long long* pr = B.prof + (size_t)blockIdx.x * 16;
-      for (int i = 0; i < 5; ++i) pr[i] = pt[i];
-      pr[5] = BFR_CLK_TOTAL() - pt_begin;
-    }
-#endif
-    (void)pt; (void)pt_begin;
     if (dead) bfr_fail(lane);
     return;
   }
@@ -514,10 +444,6 @@ __global__ __launch_bounds__(512, 2) void k_conv_bfr(BfwParams B) {
     constexpr int q = decltype(qc)::value;
     constexpr int r = q / NTW, nt = q - r * NTW;
     const f32x4 v = pend[nt][r];
-    if constexpr (BFR_ABL & 2) {
-      asm volatile("" ::"v"(v));
-      return;
-    }
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, v), orsrc, (int)(pend_voff[r] + 4u * (unsigned)coff[nt]), 0, 0);
   };
   // accumulators -> pend: v = act(acc * 2^-k + bias).  One packed fma per two values, the activation by kind (ReLU = one
@@ -540,23 +466,21 @@ __global__ __launch_bounds__(512, 2) void k_conv_bfr(BfwParams B) {
 #pragma unroll
       for (int nt = 0; nt < NTW; ++nt) {
         f32x4 v = acc[nt][r];
-        if constexpr (!(BFR_ABL & 32)) {
-          if constexpr (F16) v = __builtin_elementwise_fma(v, (f32x4){dsc_t, dsc_t, dsc_t, dsc_t}, bias4[nt]); else v += bias4[nt];
-          if constexpr (KIND == 1) {
+        if constexpr (F16) v = __builtin_elementwise_fma(v, (f32x4){dsc_t, dsc_t, dsc_t, dsc_t}, bias4[nt]); else v += bias4[nt];
+        if constexpr (KIND == 1) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-          } else if constexpr (KIND == 2) {
+          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+        } else if constexpr (KIND == 2) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(act_slope, fminf(v[e], 0.f), fmaxf(v[e], 0.f));
-          }
-          if constexpr (OMASK) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = om[nt][r][e] > 0.f ? v[e] : 0.f;
-          }
-          if constexpr (RES) v += om[nt][r];
-          rmax = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), rmax);
-          rmax = fmaxf(fmaxf(fabsf(v[2]), fabsf(v[3])), rmax);
+          for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(act_slope, fminf(v[e], 0.f), fmaxf(v[e], 0.f));
         }
+        if constexpr (OMASK) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = om[nt][r][e] > 0.f ? v[e] : 0.f;
+        }
+        if constexpr (RES) v += om[nt][r];
+        rmax = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), rmax);
+        rmax = fmaxf(fmaxf(fabsf(v[2]), fabsf(v[3])), rmax);
         pend[nt][r] = v;
       }
       if (want_amax) amax = pok ? fmaxf(amax, rmax) : amax;
@@ -571,19 +495,11 @@ __global__ __launch_bounds__(512, 2) void k_conv_bfr(BfwParams B) {
 #pragma unroll
   for (int nt = 0; nt < NTW; ++nt) asm volatile("" ::"v"(bias4[nt]));
   asm volatile("" ::"v"(act_slope));
-#ifdef BFR_PROF
-  const long long cw_p3 = wall_clock64();   // consumer set-up (bias, offsets) done, before the barrier
-#endif
   __syncthreads();  // filter and counters visible
 
   // own tiles: list entries grp, grp + 2, ...; stage (entry i, chunk cc) is number (i >> 1) * 2 ICC + cc * ng + (i & 1) of
   // the global order, ng = tiles of the pair
   int o_n = grp ? b_n : a_n, o_y = grp ? b_y : a_y, o_x = grp ? b_x : a_x;
-  long long ct[6] = {0, 0, 0, 0, 0, 0};
-  const long long ct_begin = BFR_CLK_TOTAL();
-#ifdef BFR_PROF
-  const long long cw_begin = wall_clock64();
-#endif
   int b = grp;     // ring slot of the current own stage (nbuf >= 3 > grp)
   unsigned k = 0;  // ... and how often that slot was used before
   uint4 fa[3][2][NTW];  // filter fragments of the current kernel column: [kernel row u][plane][tile]
@@ -594,39 +510,19 @@ __global__ __launch_bounds__(512, 2) void k_conv_bfr(BfwParams B) {
     const uint4* wb = wl + lane_a;
 #pragma unroll
     for (int nt = 0; nt < NTW; ++nt) {
-      if constexpr (BFR_ABL & 8) {
-        bfr_touch(fa[u][0][nt]);
-        bfr_touch(fa[u][1][nt]);
-      } else {
-        fa[u][0][nt] = wb[((u * 3 + v) * ICC + cc) * WSLOT + nt * 16];
-        fa[u][1][nt] = wb[((u * 3 + v) * ICC + cc) * WSLOT + PLANE_A + nt * 16];
-      }
+      fa[u][0][nt] = wb[((u * 3 + v) * ICC + cc) * WSLOT + nt * 16];
+      fa[u][1][nt] = wb[((u * 3 + v) * ICC + cc) * WSLOT + PLANE_A + nt * 16];
     }
   };
   auto ldB = [&](const uint4* base, auto sc) {  // step s = v * 6 + R of the stage whose slot `base` points into
     constexpr int s = decltype(sc)::value, v = s / 6, R = s - 6 * v;
-    if constexpr (BFR_ABL & 8) {
-      bfr_touch(fb[s % 3][0]);
-      bfr_touch(fb[s % 3][1]);
-    } else {
-      fb[s % 3][0] = base[R * HW + v];
-      fb[s % 3][1] = base[R * HW + v + PLANE_B];
-    }
+    fb[s % 3][0] = base[R * HW + v];
+    fb[s % 3][1] = base[R * HW + v + PLANE_B];
   };
   auto mfma3 = [&](auto uc, auto sc) {  // kernel row u against the pixel fragment of step s: output row R - u
     constexpr int u = decltype(uc)::value, s = decltype(sc)::value, R = s % 6, r = R - u;
     const uint4(&a)[2][NTW] = fa[u];
     const uint4(&bb)[2] = fb[s % 3];
-    if constexpr (BFR_ABL & 4) {
-      bfr_use(bb[0]);
-      bfr_use(bb[1]);
-#pragma unroll
-      for (int nt = 0; nt < NTW; ++nt) {
-        bfr_use(a[0][nt]);
-        bfr_use(a[1][nt]);
-      }
-      return;
-    }
 #pragma unroll
     for (int nt = 0; nt < NTW; ++nt) acc[nt][r] = mfma16x<F16>(a[0][nt], bb[1], acc[nt][r]);  // w_h * x_m
 #pragma unroll
@@ -654,7 +550,6 @@ __global__ __launch_bounds__(512, 2) void k_conv_bfr(BfwParams B) {
       for (int r = 0; r < MR; ++r) acc[nt][r] = (f32x4){0.f, 0.f, 0.f, 0.f};
     srk_static_for<0, ICC>([&](auto ccc) {
       constexpr int cc = decltype(ccc)::value, ccn = cc + 1 < ICC ? cc + 1 : 0;
-      const long long k1 = BFR_CLK();
       // the next own stage: its slot, its use count, whether it exists
       const bool has_next = cc + 1 < ICC || ti + 2 < count;
       int nb = b + (cc + 1 < ICC ? ng : 2 * ICC - (ICC - 1) * ng);
@@ -721,36 +616,15 @@ __global__ __launch_bounds__(512, 2) void k_conv_bfr(BfwParams B) {
           }
         });
       });
-      ct[1] += BFR_CLK() - k1; ct[5] += 1;
       b = nb;
       k = nk;
       hb = hbn;
     });
-    const long long k3 = BFR_CLK();
     park(n, r0, c0);
-    ct[3] += BFR_CLK() - k3;
     adv2(o_n, o_y, o_x);
   }
   srk_static_for<0, NST>([&](auto qc) { store_slot(qc); });   // the last tile
-#ifdef BFR_PROF
-  if (B.prof && tid == 0) {
-    long long* pr = B.prof + (size_t)blockIdx.x * 16 + 8;
-    for (int i = 0; i < 4; ++i) pr[i] = ct[i];
-    pr[4] = BFR_CLK_TOTAL() - ct_begin;
-    pr[5] = ct[5];
-    pr[6] = wall_clock64() - cw_begin;   // 100 MHz: the loop in wall time
-    pr[-2] = cw_begin - cw_entry;        // ... from the block's first instruction to the loop (filter copy, set-up, barrier)
-    B.prof[(size_t)(2048 + blockIdx.x) * 16 + 0] = cw_p1 - cw_entry;   // (the prologue split: rows 2048 .. of the buffer)
-    B.prof[(size_t)(2048 + blockIdx.x) * 16 + 1] = cw_p2 - cw_p1;
-    B.prof[(size_t)(2048 + blockIdx.x) * 16 + 2] = cw_p3 - cw_p2;
-    pr[-1] = cw_entry;                   // ... when the block started (absolute)
-  }
-#endif
-  (void)ct; (void)ct_begin;
   if (P.ep.y_amax) amax_commit(P.ep.y_amax, amax, blockIdx.x + wave, amax_peek(P.ep.y_amax, blockIdx.x + wave));
-#ifdef BFR_PROF
-  if (B.prof && tid == 0) B.prof[(size_t)blockIdx.x * 16 + 15] = wall_clock64();   // ... when consumer wave 0 left (absolute)
-#endif
   if (dead) bfr_fail(lane);
 }
 
@@ -851,22 +725,15 @@ static int conv_bfr_canvas(const BfwParams& B0, hipStream_t s) {
   if (nbuf > BFR_MAXBUF) nbuf = BFR_MAXBUF;
   if (nbuf < 3) return -1;
   B.nbuf = (int)nbuf;
-  B.perm = 1;
   B.NPIXp = BFR_NPIXP;
   B.late = 2;
   const size_t lds = wbytes + (size_t)nbuf * slot_bytes + BFR_CNT_BYTES;
   B.ntiles = (int)best_tiles;
-#ifdef BFR_PROF
-  B.prof = g_bfr_prof;
-#endif
   B.out_bytes = (unsigned)out_bytes;
   int grid = kNumCU - kNumCU % (8 * B.nsl);
   const long want = ((best_tiles + 7) / 8) * 8 * B.nsl;
   if (grid == 0) return -1;
   if (want < grid) grid = (int)want;
-  if (B.dbg & 32)
-    fprintf(stderr, "[srk] k_conv_bfr<2,2,canvas>: %d patches across, %d x %d tiles, %d slices, ring %d, grid %d\n", best_kx,
-            P.tiles_y, P.tiles_x, B.nsl, B.nbuf, grid);
   return bfr_launch_cv(B, lds, grid, s);
 }
 
@@ -907,29 +774,18 @@ int conv_bfr_launch(const BfwParams& B0, hipStream_t s) {
   if (nbuf > BFR_MAXBUF) nbuf = BFR_MAXBUF;
   if (nbuf < 3) return -1;
   B.nbuf = (int)nbuf;
-  B.perm = 1;
   B.NPIXp = BFR_NPIXP;
   B.late = 2;  // which role issues first on its SIMD (k_conv_bfr: prio)
   const size_t lds = wbytes + (size_t)nbuf * slot_bytes + BFR_CNT_BYTES;
   B.ntiles = (int)ntiles;
-#ifdef BFR_PROF
-  B.prof = g_bfr_prof;
-#endif
   B.out_bytes = (unsigned)((size_t)P.N * P.OH * P.OW * P.OC * sizeof(float));
   int grid = kNumCU;
   if (grid > ntiles) grid = (int)ntiles;
-  if (B.dbg & 32)
-    fprintf(stderr, "[srk] k_conv_bfr<%d,%d>: lds %zu B (filter %zu), ring %d x %zu B, grid %d of %ld tiles\n", ntw, B.ICc, lds,
-            wbytes, B.nbuf, slot_bytes, grid, ntiles);
   if (ntw == 2) return B.ICc == 1 ? bfr_launch_t<2, 1>(B, lds, grid, s) : bfr_launch_t<2, 2>(B, lds, grid, s);
   return bfr_launch_t<3, 1>(B, lds, grid, s);
 }
 
 }  // namespace srk
-
-#ifdef BFR_PROF
-extern "C" void srk_debug_ring_prof(void* p) { srk::g_bfr_prof = static_cast<long long*>(p); }
-#endif
 
 // Polls of k_conv_bfr and k_espcn_pair (conv_pair.hip) that ran into their iteration cap since the last reset (0 in a correct library; a diagnostic for
 // tests and fuzzers -- synchronises the device).

@@ -26,7 +26,6 @@ struct BfwParams {
   MfmaConvParams P;
   const uint4* wq;  // prepared filter planes (h, m)
   int ICc, NB, NPIXp, ntiles;
-  int perm;  // consumer lanes {0-3, 12-15} hold the even pixels of an M tile, {4-11} the odd ones (bfw_group_stride)
   const float* w_descale;  // F16 kernels: trailer {2^-kw, 2^kw} of the fp16 filter section (wq then points at that section)
   // Output-channel slices: a layer whose whole filter does not fit (64 -> 64: 147 KB) runs as nsl slices of NB = OC / nsl
   // channels; slice sl of tile range i is block 8 * (nsl * i + sl) + xcd -- the nsl blocks that walk the same tiles are
@@ -34,14 +33,11 @@ struct BfwParams {
   int nsl, NBfull, OCb;
   int late;  // consumer waves 4 - 7 park a finished tile at the START of the next stage (see the consumer loop)
   unsigned out_bytes;  // size of the output tensor (buffer descriptor of the consumers' stores)
-  int dbg;  // ablation (SRK_DBG): 1 no global loads, 2 no epilogue, 4 no MFMA loop, 16 no LDS commit, 1024 no deferred stores
   int nbuf;  // k_conv_bfr: halo buffers of the ring (3 .. BFR_MAXBUF)
   int cv_kx;  // k_conv_bfr<.., canvas>: patches side by side on the canvas
   int cv_sep;  // ... 1: every cell ends with a separator row / column; 0: patches of whole tiles (H % 8 == 0, W % 16 == 0) stacked
               // without separators -- a halo pixel outside the tile's own patch is padding
   unsigned cv_mh, cv_mw;  // ... ceil(2^32 / (PH + 1)), ceil(2^32 / (PW + 1))
-  long long* prof;  // experiments build only (srk_debug_bfw_prof): per block 16 int64 -- clock64() sums of the first producer
-                    // wave {commit, issue, barrier wait, stages} and of consumer wave 0 {tap loop, park, barrier wait, stages}
 };
 
 // LDS stride (in 16-byte slots) between the four 8-channel groups of a halo plane, chosen against the lane groups the LDS
@@ -51,27 +47,25 @@ struct BfwParams {
 //   consumers: a lane group reads 8 columns of k-group kq and the OTHER 8 columns of kq + 1.  With the columns
 //     {0-3, 12-15} on the even pixels of the M tile and {4-11} on the odd ones, a stride of +-2 (mod 16) maps a parity
 //     class onto itself                                         -> conflict-free for M tiles of 16 consecutive slots
-// Measured on the c2 layers (rocprofv3 --pmc SQ_LDS_BANK_CONFLICT, tools/pmc_gpad.sh): 54.1 M -> 21.9 M conflict cycles
+// Measured on the c2 layers (rocprofv3 --pmc SQ_LDS_BANK_CONFLICT): 54.1 M -> 21.9 M conflict cycles
 // per launch for 64->32 (0 with 16-wide tiles), 16.2 M -> 0 for 32->48; LDS-busy cycles 139 M -> 107 M.  The layer times
-// do not move (0.472 ms either way): the LDS was not what bounds this kernel.  SRK_BFW_PERM=0 restores the old layout.
-static inline int bfw_group_stride(int npix, bool perm) {
-  if (!perm) return (npix + 15) & ~15;
+// do not move (0.472 ms either way): the LDS was not what bounds this kernel.
+static inline int bfw_group_stride(int npix) {
   const int a = npix + ((2 - npix) & 15), b = npix + ((14 - npix) & 15);
   return a < b ? a : b;
 }
 
-// pick_tile (conv_tile.h) with the padded halo size as the fit test; wmult = 16 restricts the tile width to multiples of
-// 16 (SRK_BFW_W16=1: every M tile is 16 consecutive slots)
-static bool bfw_pick_tile(int maxpix, int PH, int PW, int KHv, int KWv, long cap_px, bool perm, int wmult, TilePick& best) {
+// pick_tile (conv_tile.h) with the padded halo size as the fit test
+static bool bfw_pick_tile(int maxpix, int PH, int PW, int KHv, int KWv, long cap_px, TilePick& best) {
   bool found = false;
   long best_tiles = 0, best_halo = 0;
   const int maxTW = PW < maxpix ? PW : maxpix;
-  for (int TW = wmult; TW <= (maxTW > wmult ? maxTW : wmult); TW += wmult) {
+  for (int TW = 1; TW <= (maxTW > 1 ? maxTW : 1); ++TW) {
     int TH = maxpix / TW;
     if (TH > PH) TH = PH;
     for (; TH >= 1; --TH) {
       const int HH = TH - 1 + KHv, HWd = TW - 1 + KWv;
-      if (bfw_group_stride(HH * HWd, perm) > cap_px) continue;
+      if (bfw_group_stride(HH * HWd) > cap_px) continue;
       const long tiles = (long)cdiv(PH, TH) * cdiv(PW, TW);
       const long halo = (long)HH * HWd * tiles;
       const bool fewer = tiles < best_tiles, same = tiles == best_tiles;

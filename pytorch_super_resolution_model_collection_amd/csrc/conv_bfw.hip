@@ -2,7 +2,7 @@
 // halo-chunk buffers (the ESPCN 64->32 and 32->48 3x3 layers: the c2 benchmark).
 //
 // Why: on those layers every phase of the per-tile kernels is short and the phases do not overlap -- measured on
-// the 64->32 layer (SRK_DBG ablations): halo staging 0.19 ms (= the activation read at HBM speed), MFMAs 0.17 ms,
+// the 64->32 layer (phase ablations): halo staging 0.19 ms (= the activation read at HBM speed), MFMAs 0.17 ms,
 // epilogue 0.08 ms, per-tap filter copies 0.07 ms, loop/barrier skeleton 0.11 ms, total 0.57 ms; co-resident blocks
 // run the same phases in lockstep.  Here the phases run CONCURRENTLY on different waves of one block:
 //
@@ -25,13 +25,6 @@
 #include "conv_bfw.h"
 
 namespace srk {
-
-#ifdef SRK_EXPERIMENTS
-#define BFW_CLK() clock64()
-static long long* g_bfw_prof = nullptr;
-#else
-#define BFW_CLK() 0ll
-#endif
 
 template <int NTW, int TT, int MTW, bool F16 = false, bool MASK = false, bool OMASK = false, int NPW = 4>
 __global__ __launch_bounds__(64 * (16 / MTW + NPW), (16 / MTW + NPW) / 4) void k_conv_bfw(BfwParams B) {
@@ -130,8 +123,8 @@ __global__ __launch_bounds__(64 * (16 / MTW + NPW), (16 / MTW + NPW) / 4) void k
     // producer waves get issue priority over the MFMA waves of the SIMD, so that the next stage's loads leave as soon as
     // the halo buffer is free (64->32 layer of c2: 0.471 -> 0.437 ms; the 48-channel pixel-shuffle layer LOSES 9 % with
     // it -- its consumers also carry the 756 MB store stream -- and priority on the consumers changes nothing).
-    // s_setprio ignores EXEC, so the branch must be provably wave-uniform (readfirstlane).  SRK_DBG & 2048: off.
-    if (NTW <= 2 && __builtin_amdgcn_readfirstlane(tid) >= 64 * NCW && !(SRK_KDBG(B.dbg) & 2048)) __builtin_amdgcn_s_setprio(1);
+    // s_setprio ignores EXEC, so the branch must be provably wave-uniform (readfirstlane).
+    if (NTW <= 2 && __builtin_amdgcn_readfirstlane(tid) >= 64 * NCW) __builtin_amdgcn_s_setprio(1);
     const int ptid = tid - 64 * NCW;
     const int g = ptid & 3, hp0 = ptid >> 2;
     const int hy0 = hp0 / P.HW, hx0 = hp0 - hy0 * P.HW;
@@ -139,7 +132,7 @@ __global__ __launch_bounds__(64 * (16 / MTW + NPW), (16 / MTW + NPW) / 4) void k
     // (Two register sets -- the loads of stage s+2 issued BEFORE stage s+1 is committed, a whole stage to land instead of
     // issue time + barrier wait -- were measured again in round 4 on top of the counted waits: 473 vs 474 us and 356 vs 356
     // us on the two c2 layers.  The producers are not what a stage waits for: after the rewrite of issue() below their wave
-    // spends 35 % of a stage at the barrier, tools/bfw_prof.py.)
+    // spends 35 % of a stage at the barrier)
     f32x4 pv0[PIT], pv1[PIT];
     f32x4 mk0[MASK ? PIT : 1], mk1[MASK ? PIT : 1];  // MASK: y of the forward layer (dx = conv^T(dy * act'(y)))
     // Round 4: everything about the thread's items that does not depend on the stage is computed ONCE -- byte offset
@@ -148,7 +141,7 @@ __global__ __launch_bounds__(64 * (16 / MTW + NPW), (16 / MTW + NPW) / 4) void k
     // left / right of it, a missing item or a channel group beyond IC gets one by a select.  Per stage and item that
     // leaves one add, one compare and one select in front of two loads.  (Before: a 64-bit multiply chain and a
     // divergent branch around every pair of loads -- ~35 VALU instructions per item, 1450 of the producer wave's 6300
-    // clocks per stage by the clock64 stamps of tools/bfw_prof.py, and an s_waitcnt vmcnt(0) in front of the first
+    // clocks per stage by clock64 stamps, and an s_waitcnt vmcnt(0) in front of the first
     // conversion of the commit because loads under a branch cannot be counted.)
     int it_rel[PIT], it_hx[PIT];
     {
@@ -179,7 +172,6 @@ __global__ __launch_bounds__(64 * (16 / MTW + NPW), (16 / MTW + NPW) / 4) void k
     auto issue = [&]() {
       int n, r0, c0, cc;
       decode(n, r0, c0, cc);
-      if (SRK_KDBG(B.dbg) & 1) return;
       constexpr unsigned OOB = 0x80000000u;
       const int iyb = r0 * P.is + P.iy0, ixb = c0 * P.is + P.ix0;
       const bool ch_on = cc * 32 + g * 8 + 7 < P.IC;
@@ -201,7 +193,6 @@ __global__ __launch_bounds__(64 * (16 / MTW + NPW), (16 / MTW + NPW) / 4) void k
       }
     };
     auto commit = [&](uint4* hal) {
-      if (SRK_KDBG(B.dbg) & 16) return;
 #pragma unroll
       for (int k = 0; k < PIT; ++k) {
         const int hq = hp0 + PSTEP * k;
@@ -223,44 +214,28 @@ __global__ __launch_bounds__(64 * (16 / MTW + NPW), (16 / MTW + NPW) / 4) void k
         }
       }
     };
-    long long pt_commit = 0, pt_issue = 0, pt_wait = 0;
     if (S > 0 && T > 0) {
       issue();
       commit(hal0);
       if (S > 1) issue();
     }
     __syncthreads();  // filter, tap table and stage 0 visible
-    const long long pt_begin = BFW_CLK();
     for (int s = 0; s < S; ++s) {
-      const long long c0 = BFW_CLK();
       if (T > 0) {
         if (s + 1 < S) commit(hal0 + (size_t)((s + 1) & 1) * hbuf);
       }
-      const long long c1 = BFW_CLK();
       if (T > 0) {
         if (s + 2 < S) issue();
       }
-      const long long c2 = BFW_CLK();
       __syncthreads();
-      const long long c3 = BFW_CLK();
-      pt_commit += c1 - c0;
-      pt_issue += c2 - c1;
-      pt_wait += c3 - c2;
     }
-#ifdef SRK_EXPERIMENTS
-    if (B.prof && tid == 64 * NCW) {
-      long long* pr = B.prof + (size_t)blockIdx.x * 16;
-      pr[0] = pt_commit; pr[1] = pt_issue; pr[2] = pt_wait; pr[3] = S; pr[4] = BFW_CLK() - pt_begin;
-    }
-#endif
-    (void)pt_commit; (void)pt_issue; (void)pt_wait; (void)pt_begin;
     return;
   }
 
   // -------------------------------------------------------------------- consumers
   const int pw = wave;
   // pixel of the M tile that this lane's MFMA column holds (see bfw_group_stride)
-  const int pj = !B.perm ? j : (j < 4 ? 2 * j : (j < 12 ? 2 * j - 7 : 2 * j - 16));
+  const int pj = j < 4 ? 2 * j : (j < 12 ? 2 * j - 7 : 2 * j - 16);
   int hp[MTW];
 #pragma unroll
   for (int mt = 0; mt < MTW; ++mt) {
@@ -388,10 +363,7 @@ __global__ __launch_bounds__(64 * (16 / MTW + NPW), (16 / MTW + NPW) / 4) void k
   for (int nt = 0; nt < NTW; ++nt) asm volatile("" ::"v"(bias4[nt]));
   asm volatile("" ::"v"(act_slope));
   __syncthreads();  // filter and stage 0 visible
-  long long ct_taps = 0, ct_park = 0, ct_wait = 0;
-  const long long ct_begin = BFW_CLK();
   for (int s = 0; s < S; ++s) {
-    const long long k0 = BFW_CLK();
     int n, r0, c0, cc;
     decode(n, r0, c0, cc);
     if (park_due) {  // (late waves: the previous stage ended a tile; cc == 0 here)
@@ -417,7 +389,7 @@ __global__ __launch_bounds__(64 * (16 / MTW + NPW), (16 / MTW + NPW) / 4) void k
         }
       }
     }
-    if (wave_live && T > 0 && !(SRK_KDBG(B.dbg) & 4)) {
+    if (wave_live && T > 0) {
       const uint4* hal = hal0 + (size_t)(s & 1) * hbuf;
       const uint4* wb = wl + (size_t)cc * wslot;
       const size_t wstep = (size_t)B.ICc * wslot;
@@ -489,33 +461,20 @@ __global__ __launch_bounds__(64 * (16 / MTW + NPW), (16 / MTW + NPW) / 4) void k
         if (t < T) mfmas(fa[0], fb[0]);
       }
     }
-    const long long k1 = BFW_CLK();
-    if (cc == B.ICc - 1 && wave_live && !(SRK_KDBG(B.dbg) & 2)) {
+    if (cc == B.ICc - 1 && wave_live) {
       if (late_wave && s != S - 1) {  // parked at the top of the next stage, while the SIMD's other consumer wave runs its taps
         park_due = true;
         pk_n = n; pk_r0 = r0; pk_c0 = c0;
       } else {
         park(n, r0, c0);
-        if (TT == 0 || s == S - 1 || (SRK_KDBG(B.dbg) & 1024)) {  // no unrolled tap loop to ride under / last tile of this block
+        if (TT == 0 || s == S - 1) {  // no unrolled tap loop to ride under / last tile of this block
           flush_from(std::integral_constant<int, 0>{});
           pend_live = false;
         }
       }
     }
-    const long long k2 = BFW_CLK();
     __syncthreads();
-    const long long k3 = BFW_CLK();
-    ct_taps += k1 - k0;
-    ct_park += k2 - k1;
-    ct_wait += k3 - k2;
   }
-#ifdef SRK_EXPERIMENTS
-  if (B.prof && tid == 0) {
-    long long* pr = B.prof + (size_t)blockIdx.x * 16 + 8;
-    pr[0] = ct_taps; pr[1] = ct_park; pr[2] = ct_wait; pr[3] = S; pr[4] = BFW_CLK() - ct_begin;
-  }
-#endif
-  (void)ct_taps; (void)ct_park; (void)ct_wait; (void)ct_begin;
   if (P.ep.y_amax) amax_commit(P.ep.y_amax, amax, blockIdx.x + wave, amax_peek(P.ep.y_amax, blockIdx.x + wave));  // (persistent: once)
 }
 
@@ -602,15 +561,12 @@ static int bfw_launch(const BfwParams& B, size_t lds, int grid, hipStream_t s) {
   // -1 % / -3.5 % on the c2 64->32 / 32->48 layers vs 4 x 64 pixels) while the kernel fits 168 VGPRs (<= 48 output
   // channels); 64 channels: 4 x 64 pixels.  3x3 kernels get the unrolled tap loop with deferred stores; with 64-pixel
   // consumer waves and > 32 channels that variant spills (256 VGPRs) and the dynamic loop is used.
-  const int mtw_env = SRK_EXP_INT("SRK_BFW_MTW", 0);  // experiment: 2 or 4
-  const bool t9 = B.P.KHv * B.P.KWv == 9;
-  const int mtw = mtw_env ? mtw_env : (NTW <= 3 ? 2 : 4);
-  if (mtw == 2 && NTW <= 3) {
-    if (t9) return bfw_launch_t<NTW, 9, 2>(B, lds, grid, s);
+  if constexpr (NTW <= 3) {
+    if (B.P.KHv * B.P.KWv == 9) return bfw_launch_t<NTW, 9, 2>(B, lds, grid, s);
     return bfw_launch_t<NTW, 0, 2>(B, lds, grid, s);
+  } else {
+    return bfw_launch_t<NTW, 0, 4>(B, lds, grid, s);
   }
-  if (NTW <= 2 && t9) return bfw_launch_t<NTW, 9, 4>(B, lds, grid, s);
-  return bfw_launch_t<NTW, 0, 4>(B, lds, grid, s);
 }
 
 // returns -1 when no tile fits (the caller falls back to the other kernels).  f16: the f16x3 arithmetic (ep.x_amax set)
@@ -621,7 +577,6 @@ int conv_bfw_gather(const GatherConv& g, const float* in, const float* wp, float
   const char* fsec = prepared + f16_section_offset(g.IC, g.OC, g.KH * g.KW);
   const uint4* wq = reinterpret_cast<const uint4*>(f16 ? fsec : prepared);
   const float* w_descale = f16 ? reinterpret_cast<const float*>(fsec + bf3_main_bytes(g.IC, g.OC, g.KH * g.KW)) : nullptr;
-  const int dbg = SRK_EXP_INT("SRK_DBG", 0);
   const int nsl = bfw_slices(g);
   if (nsl == 0) return -1;
   return for_each_phase(g, in, wp, out, ep, mask_y, mask_slope, [&](const MfmaConvParams& P0) {
@@ -635,18 +590,11 @@ int conv_bfw_gather(const GatherConv& g, const float* in, const float* wp, float
     B.OCb = (P.OC + 63) / 64;
     B.NB = P.OC / nsl;
     B.ICc = (P.IC + 31) / 32;
-    B.dbg = dbg;
-#ifdef SRK_EXPERIMENTS
-    B.prof = g_bfw_prof;
-#endif
     const int T = P.KHv * P.KWv;
     const size_t wbytes = (size_t)T * B.ICc * 8 * B.NB * 16;
     const long lds_cap = 160L * 1024 - 512;
     long px_cap = (lds_cap - (long)wbytes) / (2 * 128);  // halo pixels per buffer (128 bytes each)
     if (px_cap > 64 * BFW_IT) px_cap = 64 * BFW_IT;
-    const int perm = SRK_EXP_INT("SRK_BFW_PERM", 1);
-    const int w16 = SRK_EXP_INT("SRK_BFW_W16", 0);
-    B.perm = perm;
     B.late = B.ICc == 1;   // (B.ICc is set above)
     if (T == 9 && P.is == 1) {  // ring of halo buffers instead of the per-stage barrier (conv_bfr.hip) where it applies
       const int rc = conv_bfr_launch(B, s);
@@ -655,9 +603,9 @@ int conv_bfw_gather(const GatherConv& g, const float* in, const float* wp, float
     if (P.ep.residual) return -1;   // (this kernel's epilogue has no residual: the caller's other kernels)
     TilePick best{};
     if (px_cap < 64 || P.is != 1) return -1;
-    if (!bfw_pick_tile(256, P.PH, P.PW, P.KHv, P.KWv, px_cap, perm, w16 ? 16 : 1, best)) return -1;
+    if (!bfw_pick_tile(256, P.PH, P.PW, P.KHv, P.KWv, px_cap, best)) return -1;
     P.TH = best.TH; P.TW = best.TW; P.tiles_y = best.tiles_y; P.tiles_x = best.tiles_x; P.HH = best.HH; P.HW = best.HW;
-    B.NPIXp = bfw_group_stride(best.HH * best.HW, perm);
+    B.NPIXp = bfw_group_stride(best.HH * best.HW);
     const size_t lds = wbytes + (size_t)2 * 8 * B.NPIXp * 16;
     const long ntiles = (long)P.tiles_x * P.tiles_y * P.N;
     if (ntiles >= (1L << 30)) return -1;
@@ -672,9 +620,6 @@ int conv_bfw_gather(const GatherConv& g, const float* in, const float* wp, float
     } else if (grid > ntiles) {
       grid = (int)ntiles;
     }
-    if (dbg & 32)
-      fprintf(stderr, "[srk] k_conv_bfw<%d>: lds %zu B (filter %zu), grid %d of %ld tiles x %d slices, tile %dx%d halo %dx%d\n",
-              B.NB / 16, lds, wbytes, grid, ntiles, nsl, P.TH, P.TW, P.HH, P.HW);
     switch (B.NB / 16) {
       case 1: return bfw_launch<1>(B, lds, grid, s);
       case 2: return bfw_launch<2>(B, lds, grid, s);
@@ -685,8 +630,3 @@ int conv_bfw_gather(const GatherConv& g, const float* in, const float* wp, float
 }
 
 }  // namespace srk
-
-#ifdef SRK_EXPERIMENTS
-// experiments build only: device buffer of 16 int64 per block for the role-time sums of the next k_conv_bfw launches
-extern "C" void srk_debug_bfw_prof(void* p) { srk::g_bfw_prof = static_cast<long long*>(p); }
-#endif

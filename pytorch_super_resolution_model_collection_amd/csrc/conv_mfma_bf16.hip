@@ -40,7 +40,6 @@ struct Bf3Params {
   int OCb;          // 64-channel output blocks
   int NB;           // output channels per block in the prepared layout (NT*16)
   int NPIXp;        // halo pixels rounded up to 16
-  int dbg;          // ablation switches (SRK_DBG env): 1 skip halo loads, 2 skip epilogue, 4 skip MFMAs, 8 skip weight copies
 };
 
 __device__ __forceinline__ void split8(const float (&f)[8], uint4& hi, uint4& lo) {
@@ -249,8 +248,7 @@ constexpr int BF3_EPI_STRIDE = 68; // floats per staged output row (64 + 4: conf
 // loop — is not compiled into the kernel.
 template <int NT, bool VEC_ONLY = false>
 __device__ __forceinline__ void bf3_epilogue(const MfmaConvParams& P, float* smem_f, const f32x4 (&acc)[4][NT], int n,
-                                             int r0, int c0, int ocb, int wave, int lane, int dbg = 0) {
-  if (dbg & 2) return;
+                                             int r0, int c0, int ocb, int wave, int lane) {
   float amax = 0.f;  // running maximum of what this lane stores (ep.y_amax; vector store path only)
   const float peeked = VEC_ONLY ? amax_peek(P.ep.y_amax, blockIdx.x + wave) : 0.f;
   const int j = lane & 15, kq = lane >> 4;
@@ -283,7 +281,7 @@ __device__ __forceinline__ void bf3_epilogue(const MfmaConvParams& P, float* sme
         if (m < npx) {
           const int r = div_small(m, tw_magic), c = m - r * P.TW;
           const int pr = r0 + r, pc = c0 + c;
-          if (pr < P.PH && pc < P.PW && !((dbg & 64) && acc[0][0][0] != 123.456f)) {
+          if (pr < P.PH && pc < P.PW) {
             const epi_f4 v = *reinterpret_cast<const epi_f4*>(st + row * BF3_EPI_STRIDE + q4 * 4);
             if (VEC_ONLY || col.vec) {
               const epi_f4 o = epi_store4_tile(P.ep, col, et, r, c, v, P.out);
@@ -354,7 +352,7 @@ __global__ __launch_bounds__(64 * NW, (NT <= 2 && NW == 4) ? 3 : 2) void k_conv_
       __syncthreads();  // previous chunk fully consumed
       const uint4* wbase = B.wq + ((size_t)cc * B.OCb + ocbi) * (size_t)wslot;
       int wtap = P.wh0 * P.KW_full + P.ww0;  // weight tap of (u, v) = (0, 0)
-      if (!(SRK_KDBG(B.dbg) & 1)) bf3_stage_halo<NTHR>(B, hal, n, r0, c0, cc * 32);
+      bf3_stage_halo<NTHR>(B, hal, n, r0, c0, cc * 32);
       {
         // (loads unconditional from a clamped index, only the LDS writes conditional: load + write under one branch
         //  compiled to load, s_waitcnt vmcnt(0), write -- per copy, one after the other)
@@ -375,13 +373,13 @@ __global__ __launch_bounds__(64 * NW, (NT <= 2 && NW == 4) ? 3 : 2) void k_conv_
         uint4 wr[WCP];
 #pragma unroll
         for (int c = 0; c < WCP; ++c) wr[c] = make_uint4(0, 0, 0, 0);
-        if (t + 1 < T && !(SRK_KDBG(B.dbg) & 8)) {  // prefetch the next tap's slice; lands while the MFMAs below run
+        if (t + 1 < T) {  // prefetch the next tap's slice; lands while the MFMAs below run
           const uint4* src = wbase + (size_t)wnext * wtap_stride;
 #pragma unroll
           for (int c = 0; c < WCP; ++c)
             if (tid + c * NTHR < wslot) wr[c] = src[tid + c * NTHR];
         }
-        if (wave_live && !(SRK_KDBG(B.dbg) & 4)) {
+        if (wave_live) {
           const uint4* wb = wl + (t & 1) * wslot + wlane;
           const uint4* hb = hal + toff;
           uint4 ah[4], al[4];
@@ -426,10 +424,6 @@ __global__ __launch_bounds__(64 * NW, (NT <= 2 && NW == 4) ? 3 : 2) void k_conv_
         __syncthreads();
       }
     }
-  }
-  if (SRK_KDBG(B.dbg) & 2) {
-    if (acc[0][0][0] == 123.456f) P.out[0] = 1.f;  // keep the accumulators live
-    return;
   }
   bf3_epilogue<NT, VEC_ONLY>(P, reinterpret_cast<float*>(smem4), acc, n, r0, c0, ocb, wave, lane);
 }
@@ -766,7 +760,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_bf3_rows(Bf3Params B) {
       if (hp < npix) {
         const int hy = hp / P.HW, hx = hp - hy * P.HW;
         const int iy = iyb + hy, ix = ixb + hx;
-        if (iy >= 0 && iy < P.IH && ix >= 0 && ix < P.IW && !(SRK_KDBG(B.dbg) & 1)) {
+        if (iy >= 0 && iy < P.IH && ix >= 0 && ix < P.IW) {
           const size_t off = (((size_t)n * P.IH + iy) * P.IW + ix) * P.IC;
 #pragma unroll
           for (int e = 0; e < 4; ++e)
@@ -836,7 +830,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_bf3_rows(Bf3Params B) {
         if (w0_ok) wr0 = src[tid];
         if (w1_ok) wr1 = src[tid + 256];
       }
-      if (wave_live && !(SRK_KDBG(B.dbg) & 4)) {
+      if (wave_live) {
         const int toff = u * P.HW + ks * 8;
         const uint4* wb = wl + (q & 1) * wslot + wlane;
         uint4 ah[4], al[4];
@@ -885,7 +879,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_bf3_rows(Bf3Params B) {
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) acc[mt][nt] *= dsc;
   }
-  bf3_epilogue<NT, VEC_ONLY>(P, reinterpret_cast<float*>(smem4), acc, n, r0, c0, ocb, wave, lane, SRK_KDBG(B.dbg));
+  bf3_epilogue<NT, VEC_ONLY>(P, reinterpret_cast<float*>(smem4), acc, n, r0, c0, ocb, wave, lane);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -895,13 +889,6 @@ template <int NT>
 static void bf3_launch_vec(const Bf3Params& B, dim3 grid, size_t lds, hipStream_t s) {
   static LdsLimit lim;
   lim.ensure(reinterpret_cast<const void*>(&k_conv_bf3<NT, 4, true>), lds);
-  if (SRK_KDBG(B.dbg) & 32) {
-    int nb = -1;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&k_conv_bf3<NT, 4, true>), 256,
-                                                       lds);
-    fprintf(stderr, "[srk] k_conv_bf3<%d,4,vec>: lds %zu B, grid %u x %u, occupancy %d blocks/CU, tile %dx%d halo %dx%d\n", NT,
-            lds, grid.x, grid.y, nb, B.P.TH, B.P.TW, B.P.HH, B.P.HW);
-  }
   note_kernel("k_conv_bf3<%d,4,vec>", NT);
   hipLaunchKernelGGL((k_conv_bf3<NT, 4, true>), grid, dim3(256), lds, s, B);
 }
@@ -910,13 +897,6 @@ template <int NT, int NW>
 static void bf3_launch(const Bf3Params& B, dim3 grid, size_t lds, hipStream_t s) {
   static LdsLimit lim;
   lim.ensure(reinterpret_cast<const void*>(&k_conv_bf3<NT, NW>), lds);
-  if (SRK_KDBG(B.dbg) & 32) {
-    int nb = -1;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void*>(&k_conv_bf3<NT, NW>), 64 * NW,
-                                                       lds);
-    fprintf(stderr, "[srk] k_conv_bf3<%d,%d>: lds %zu B, grid %u x %u, occupancy %d blocks/CU, tile %dx%d halo %dx%d\n", NT,
-            NW, lds, grid.x, grid.y, nb, B.P.TH, B.P.TW, B.P.HH, B.P.HW);
-  }
   note_kernel("k_conv_bf3<%d,%d>", NT, NW);
   hipLaunchKernelGGL((k_conv_bf3<NT, NW>), grid, dim3(64 * NW), lds, s, B);
 }
@@ -967,7 +947,6 @@ static int bf3_launch_rows_phase(MfmaConvParams P, const uint4* wq, hipStream_t 
   P.TH = best.TH; P.TW = best.TW; P.tiles_y = best.tiles_y; P.tiles_x = best.tiles_x; P.HH = best.HH; P.HW = best.HW;
   B.NPIXp = (best.HH * best.HW + 16 + 15) & ~15;  // +16: the last row's padded kw slots read past the halo
   B.P = P;
-  B.dbg = SRK_EXP_INT("SRK_ROWS_DBG", 0);   // ablation: 1 no halo loads, 2 no epilogue, 4 no MFMAs, 64 no global stores
   size_t lds = (size_t)B.NPIXp * 16 + wbytes;
   const size_t epi_bytes = (size_t)4 * 32 * BF3_EPI_STRIDE * sizeof(float);
   if (lds < epi_bytes) lds = epi_bytes;
@@ -982,7 +961,7 @@ static int bf3_launch_rows_phase(MfmaConvParams P, const uint4* wq, hipStream_t 
 }
 
 template <int NW>
-static int bf3_launch_phase_nw(MfmaConvParams P, Bf3Params B, int NT, int dbg, hipStream_t s) {
+static int bf3_launch_phase_nw(MfmaConvParams P, Bf3Params B, int NT, hipStream_t s) {
   const int wbytes = 2 * 8 * B.NB * 16;
   const int maxpix = 64 * NW;
   // LDS share that lets `blocks` blocks of this size be co-resident on a CU (160 KiB)
@@ -1007,11 +986,9 @@ static int bf3_launch_phase_nw(MfmaConvParams P, Bf3Params B, int NT, int dbg, h
   P.TH = best.TH; P.TW = best.TW; P.tiles_y = best.tiles_y; P.tiles_x = best.tiles_x; P.HH = best.HH; P.HW = best.HW;
   B.NPIXp = (best.HH * best.HW + 15) & ~15;  // multiple of 16: the kq lane groups of a ds_read_b128 interleave conflict-free
   B.P = P;
-  B.dbg = dbg;
   size_t lds = (size_t)8 * B.NPIXp * 16 + wbytes;
   const size_t epi_bytes = (size_t)NW * 32 * BF3_EPI_STRIDE * sizeof(float);
   if (lds < epi_bytes) lds = epi_bytes;
-  if (dbg & 64) lds = 100 * 1024;  // experiment: force 1 block per CU
   dim3 grid((unsigned)((size_t)P.tiles_x * P.tiles_y * P.N), B.OCb);
   if (NW == 4 && NT >= 2 && P.OC % 16 == 0 && epi_all_vector(P)) {  // full 16-channel tiles, vector stores everywhere
     switch (NT) {
@@ -1038,18 +1015,12 @@ static int bf3_launch_phase(MfmaConvParams P, const uint4* wq, hipStream_t s) {
   B.ICc = (P.IC + 31) / 32;
   B.OCb = (P.OC + 63) / 64;
   B.wq = wq;
-  const int dbg = SRK_EXP_INT("SRK_DBG", 0);
-  const int nw = SRK_EXP_INT("SRK_BF3_WAVES", 0);  // waves per block: 4 (256-px tiles), 2 or 1 -- more, smaller blocks per CU; 0 = automatic
-  int use = nw;
-  if (nw <= 0) {
-    // small problems (strong-scaled shards): fewer pixels than 2 resident 256-pixel tiles per CU ->
-    // smaller blocks so every CU gets work (measured: 256-px tiles win whenever the chip is full)
-    const long px = (long)P.N * P.PH * P.PW * B.OCb;
-    use = px >= 256L * 2 * kNumCU ? 4 : (px >= 128L * 2 * kNumCU ? 2 : 1);
-  }
-  if (use == 1) return bf3_launch_phase_nw<1>(P, B, NT, dbg, s);
-  if (use == 2) return bf3_launch_phase_nw<2>(P, B, NT, dbg, s);
-  return bf3_launch_phase_nw<4>(P, B, NT, dbg, s);
+  // waves per block: 4 (256-px tiles), 2 or 1.  Small problems (strong-scaled shards): fewer pixels than 2 resident
+  // 256-pixel tiles per CU -> smaller blocks so every CU gets work (measured: 256-px tiles win whenever the chip is full)
+  const long px = (long)P.N * P.PH * P.PW * B.OCb;
+  if (px < 128L * 2 * kNumCU) return bf3_launch_phase_nw<1>(P, B, NT, s);
+  if (px < 256L * 2 * kNumCU) return bf3_launch_phase_nw<2>(P, B, NT, s);
+  return bf3_launch_phase_nw<4>(P, B, NT, s);
 }
 
 int conv_bf3_gather(const GatherConv& g, const float* in, const float* wp, float* out, const Epi& ep,

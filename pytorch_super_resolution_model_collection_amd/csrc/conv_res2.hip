@@ -31,7 +31,7 @@ constexpr int R2_H1 = 12;      // input halo width (tile + 2 + 2)
 constexpr int R2_MW = 10;      // mid region width (tile + 1 + 1)
 // Tile = 8 x 8 outputs: 12 x 12 input halo, 10 x 10 intermediate in 7 MFMA pixel tiles, 4 output pixel tiles.
 // (Round 4 experiment, removed: 4-row half tiles so that the 16-patch EDSR shard -- one 8 x 8 tile per CU -- has two
-// resident blocks per CU.  tools/res2_prof.py: forward 16.2 -> 16.5 us, backward 15.2 -> 14.8 us, step 1.199 -> 1.212 ms:
+// resident blocks per CU.  DESIGN 10.1: forward 16.2 -> 16.5 us, backward 15.2 -> 14.8 us, step 1.199 -> 1.212 ms:
 // the two blocks stretch each other's tap phases by what they hide of each other's barriers.)
 constexpr int R2_NPIX1 = R2_H1 * R2_H1;   // 144 input halo pixels
 constexpr int R2_MT1 = 7;                 // 16-pixel tiles of the intermediate (r2_mid_rc)
@@ -88,21 +88,12 @@ struct Res2Params {
   float* mid;          // [N, H, W, 64] centre store of the intermediate
   float* out;
   int N, H, W, tiles_y, tiles_x;
-  int dbg;
   // f16x3 forward (SRK_ALGO_MFMA_F16X3): wq1 / wq2 point at the fp16 planes, wd1 / wd2 at their trailers {2^-kw, 2^kw}
   const float* x_amax;
   float* y_amax;   // optional (any arithmetic): running max of |out|
   const float* wd1;
   const float* wd2;
-  long long* prof;   // experiments build only (srk_debug_res2_prof): 16 clock64() stamps per block, thread 0
 };
-
-#ifdef SRK_EXPERIMENTS
-#define R2_PROF(i) do { if (R.prof && threadIdx.x == 0) R.prof[(size_t)blockIdx.x * 16 + (i)] = clock64(); } while (0)
-static long long* g_res2_prof = nullptr;
-#else
-#define R2_PROF(i) do { } while (0)
-#endif
 
 template <int NP>
 __device__ __forceinline__ void r2_split4(const f32x4& v, uint2 (&pl)[NP]) {
@@ -196,7 +187,6 @@ __global__ __launch_bounds__(512, 2) void k_res2(Res2Params R) {
     dst[1] = w[256];
     if (NP == 3) dst[NP - 1] = ((cv ? R.wq2l : R.wq1l) + slot * 256)[wlane];
   };
-  R2_PROF(0);
   uint4 bq[3][NP];
   load_b(0, bq[0]);
   load_b(1, bq[1]);
@@ -205,25 +195,23 @@ __global__ __launch_bounds__(512, 2) void k_res2(Res2Params R) {
   // [chunk][pixel >> 2] (see lds_goff); every global load is issued before the first conversion
   constexpr int NIT = (R2_NPIX1 * 8 + 511) / 512;
   f32x4 v0[NIT], v1[NIT];
-  if (!(SRK_KDBG(R.dbg) & 1)) {
 #pragma unroll
-    for (int k = 0; k < NIT; ++k) {
-      const int item = tid + k * 512;
-      const int g8 = ((item >> 1) & 2) | ((item >> 3) & 1) | ((item >> 2) & 4), hp = ((item >> 5) << 2) | (item & 3);
-      const int hy = hp / R2_H1, hx = hp - hy * R2_H1;
-      const int iy = r0 - 2 + hy, ix = c0 - 2 + hx;
-      v0[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      v1[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (hp < R2_NPIX1 && (unsigned)iy < (unsigned)R.H && (unsigned)ix < (unsigned)R.W) {
-        const float* p = inb + ((size_t)iy * R.W + ix) * R2_C + g8 * 8;
-        v0[k] = *reinterpret_cast<const f32x4*>(p);
-        v1[k] = *reinterpret_cast<const f32x4*>(p + 4);
-      }
+  for (int k = 0; k < NIT; ++k) {
+    const int item = tid + k * 512;
+    const int g8 = ((item >> 1) & 2) | ((item >> 3) & 1) | ((item >> 2) & 4), hp = ((item >> 5) << 2) | (item & 3);
+    const int hy = hp / R2_H1, hx = hp - hy * R2_H1;
+    const int iy = r0 - 2 + hy, ix = c0 - 2 + hx;
+    v0[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    v1[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (hp < R2_NPIX1 && (unsigned)iy < (unsigned)R.H && (unsigned)ix < (unsigned)R.W) {
+      const float* p = inb + ((size_t)iy * R.W + ix) * R2_C + g8 * 8;
+      v0[k] = *reinterpret_cast<const f32x4*>(p);
+      v1[k] = *reinterpret_cast<const f32x4*>(p + 4);
     }
   }
   // ---- per-lane geometry of the exchange after the first conv (group 0 finishes mid tiles 0-3, group 1 tiles 4-6),
   // computed HERE, behind the halo loads and in front of their first use: after the first conv's taps this index
-  // arithmetic was part of the ~2.3 k clocks the block's first wave then waits at the barrier (tools/res2_prof.py).
+  // arithmetic was part of the ~2.3 k clocks the block's first wave then waits at the barrier.
   // (The gate / bias loads stay behind the taps: 16 + 8 more live registers across them are 132 - 138 VGPRs, one
   //  block per CU.)
   const int ch4 = ow * 16 + kq * 4;
@@ -241,29 +229,25 @@ __global__ __launch_bounds__(512, 2) void k_res2(Res2Params R) {
     moff[q] = inimg ? (int)(((size_t)iy * R.W + ix) * R2_C) + ch4 : -1;
     mcen[q] = inimg && r >= 1 && r <= TH && c >= 1 && c <= R2_TS;
   }
-  if (!(SRK_KDBG(R.dbg) & 1)) {
 #pragma unroll
-    for (int k = 0; k < NIT; ++k) {
-      const int item = tid + k * 512;
-      const int g8 = ((item >> 1) & 2) | ((item >> 3) & 1) | ((item >> 2) & 4), hp = ((item >> 5) << 2) | (item & 3);
-      if (hp < R2_NPIX1) {
-        float f[8];
+  for (int k = 0; k < NIT; ++k) {
+    const int item = tid + k * 512;
+    const int g8 = ((item >> 1) & 2) | ((item >> 3) & 1) | ((item >> 2) & 4), hp = ((item >> 5) << 2) | (item & 3);
+    if (hp < R2_NPIX1) {
+      float f[8];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          f[e] = v0[k][e];
-          f[4 + e] = v1[k][e];
-        }
-        uint4 pl[NP];
-        if constexpr (F16) split8h(f, sx, pl); else split8n<NP>(f, pl);
-        const int chunk = g8 >> 2, g = g8 & 3;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) hal1[(chunk * NP + p) * PL1 + lds_goff(g, S1) + hp] = pl[p];
+      for (int e = 0; e < 4; ++e) {
+        f[e] = v0[k][e];
+        f[4 + e] = v1[k][e];
       }
+      uint4 pl[NP];
+      if constexpr (F16) split8h(f, sx, pl); else split8n<NP>(f, pl);
+      const int chunk = g8 >> 2, g = g8 & 3;
+#pragma unroll
+      for (int p = 0; p < NP; ++p) hal1[(chunk * NP + p) * PL1 + lds_goff(g, S1) + hp] = pl[p];
     }
   }
-  R2_PROF(1);
   __syncthreads();
-  R2_PROF(2);
 
   // ---- first conv on the 10x10 mid region: 7 pixel tiles x this wave's 16 channels x chunk kgrp
   f32x4 acc1[R2_MT1];
@@ -304,20 +288,17 @@ __global__ __launch_bounds__(512, 2) void k_res2(Res2Params R) {
       // (a scheduling fence per tap: without one the unrolled taps' fragment reads are hoisted over each other -- 248 VGPRs,
       //  one block per CU; until round 4 a run-time ablation branch around the tap body had that effect by accident)
       __builtin_amdgcn_sched_barrier(0);
-      if (!(SRK_KDBG(R.dbg) & 4)) {
-        const int toff = (t / 3) * R2_H1 + (t % 3);
-        uint4 a[NP][R2_MT1];
+      const int toff = (t / 3) * R2_H1 + (t % 3);
+      uint4 a[NP][R2_MT1];
 #pragma unroll
-        for (int p = 0; p < NP; ++p)
+      for (int p = 0; p < NP; ++p)
 #pragma unroll
-          for (int mt = 0; mt < R2_MT1; ++mt) a[p][mt] = h1c[p * plane1 + hpA[mt] + toff];
-        SRK_R2_PASSES(acc1, a, bq[t % 3], R2_MT1)
-      }
+        for (int mt = 0; mt < R2_MT1; ++mt) a[p][mt] = h1c[p * plane1 + hpA[mt] + toff];
+      SRK_R2_PASSES(acc1, a, bq[t % 3], R2_MT1)
     }
     }
   }
 
-  R2_PROF(3);
   // ---- the chunk groups swap halves
   f32x4 gt[MT1A];  // backward: forward mid values of this wave's tiles (issued before the barriers)
 #pragma unroll
@@ -333,7 +314,6 @@ __global__ __launch_bounds__(512, 2) void k_res2(Res2Params R) {
   if (!BWD && R.bias1) b1 = *reinterpret_cast<const f32x4*>(R.bias1 + ch4);
   if (!BWD && R.bias2) b2 = *reinterpret_cast<const f32x4*>(R.bias2 + ch4);
   __syncthreads();  // every wave is done with the input halo
-  R2_PROF(10);
   f32x4* red = reinterpret_cast<f32x4*>(smem4) + (size_t)(ow * R2_MT1) * 64 + lane;  // [4 ow][7 tiles][64 lanes]
   if (kgrp == 0) {
 #pragma unroll
@@ -343,7 +323,6 @@ __global__ __launch_bounds__(512, 2) void k_res2(Res2Params R) {
     for (int mt = 0; mt < MT1A; ++mt) red[mt * 64] = acc1[mt];
   }
   __syncthreads();
-  R2_PROF(11);
   float smid = 1.f, dsc2 = 1.f;
   {
     asm volatile("" ::"v"(b1), "v"(b2));
@@ -373,7 +352,6 @@ __global__ __launch_bounds__(512, 2) void k_res2(Res2Params R) {
       vv[q] = v;
       if constexpr (F16) lmax = abs_max4(lmax, v);
     }
-    R2_PROF(12);
     if constexpr (F16) {
       // the intermediate's scale: maximum over the whole 10 x 10 x 64 tile (the second conv mixes all of it)
       lmax = wave_max(lmax);
@@ -386,7 +364,6 @@ __global__ __launch_bounds__(512, 2) void k_res2(Res2Params R) {
       smid = exp2i(km);
       dsc2 = exp2i(-km) * R.wd2[0];
     }
-    R2_PROF(13);
 #pragma unroll
     for (int mt = 0; mt < R2_MT1; ++mt) {
       if ((mt < MT1A) != (kgrp == 0)) continue;
@@ -411,9 +388,7 @@ __global__ __launch_bounds__(512, 2) void k_res2(Res2Params R) {
     ooff[q] = ok ? (int)(((size_t)iy * R.W + ix) * R2_C) + ch4 : -1;
     res[q] = *reinterpret_cast<const f32x4*>(inb + (ok ? ooff[q] : ch4));  // (unconditional: see gt; unused when !ok)
   }
-  R2_PROF(4);
   __syncthreads();  // mid planes complete
-  R2_PROF(5);
 
   // ---- second conv on the TH x 8 centre: MT2 pixel tiles
   f32x4 acc2[MT2];
@@ -451,19 +426,16 @@ __global__ __launch_bounds__(512, 2) void k_res2(Res2Params R) {
     for (int t = 0; t < 9; ++t) {
       if (t + 2 < 9) load_b(9 + t + 2, bq[(t + 2) % 3]);
       __builtin_amdgcn_sched_barrier(0);
-      if (!(SRK_KDBG(R.dbg) & 4)) {
-        const int toff = (t / 3) * R2_MW + (t % 3);
-        uint4 a[NP][MT2];
+      const int toff = (t / 3) * R2_MW + (t % 3);
+      uint4 a[NP][MT2];
 #pragma unroll
-        for (int p = 0; p < NP; ++p)
+      for (int p = 0; p < NP; ++p)
 #pragma unroll
-          for (int mt = 0; mt < MT2; ++mt) a[p][mt] = h2c[p * plane2 + hpB[mt] + toff];
-        SRK_R2_PASSES(acc2, a, bq[t % 3], MT2)
-      }
+        for (int mt = 0; mt < MT2; ++mt) a[p][mt] = h2c[p * plane2 + hpB[mt] + toff];
+      SRK_R2_PASSES(acc2, a, bq[t % 3], MT2)
     }
     }
   }
-  R2_PROF(6);
   // swap halves again (the region of the input halo is free: nothing reads it after the barrier above)
   f32x4* red2 = reinterpret_cast<f32x4*>(smem4) + (size_t)(ow * MT2) * 64 + lane;  // [4 ow][MT2 tiles][64 lanes]
   const float peeked = amax_peek(R.y_amax, blockIdx.x);  // (early: see amax_commit)
@@ -475,7 +447,6 @@ __global__ __launch_bounds__(512, 2) void k_res2(Res2Params R) {
     for (int mt = 0; mt < MT2A; ++mt) red2[mt * 64] = acc2[mt];
   }
   __syncthreads();
-  R2_PROF(7);
 #pragma unroll
   for (int q = 0; q < MT2A; ++q) asm volatile("" ::"v"(res[q]));  // (landed during the second conv: no wait between the stores below)
   float oamax = 0.f;
@@ -496,16 +467,10 @@ __global__ __launch_bounds__(512, 2) void k_res2(Res2Params R) {
       if (R.y_amax) oamax = abs_max4(oamax, v);
     }
   }
-  R2_PROF(8);
   if (R.y_amax) amax_commit_block(R.y_amax, oamax, blockIdx.x, r2_amx, 8, peeked);
-  R2_PROF(9);
 }
 #undef SRK_R2_PASSES
 #undef mfma16
-
-static int r2_dbg() {
-  return SRK_EXP_INT("SRK_DBG", 0);
-}
 
 // Small problems only: the tile does 1.56x the first conv's matrix work, which is free while a CU has a few tiles and
 // mostly waits, and a loss once the separate kernels run many tiles per CU at their matrix rate.  Measured on the EDSR
@@ -567,12 +532,8 @@ int conv_res2(const float* in, const float* wp1, const float* wp2, const float* 
   R.N = N; R.H = H; R.W = W;
   R.tiles_y = (H + R2_TS - 1) / R2_TS;
   R.tiles_x = (W + R2_TS - 1) / R2_TS;
-  R.dbg = r2_dbg();
   R.x_amax = x_amax;
   R.y_amax = y_amax;
-#ifdef SRK_EXPERIMENTS
-  R.prof = g_res2_prof;
-#endif
   if (planes == 4) {
     if (bwd || !x_amax) {
       set_error("conv_res2: f16x3 is a forward arithmetic and needs x_amax");
@@ -590,8 +551,3 @@ int conv_res2(const float* in, const float* wp1, const float* wp2, const float* 
 }
 
 }  // namespace srk
-
-#ifdef SRK_EXPERIMENTS
-// experiments build only: device buffer of 16 int64 per block that the next fused-block launches stamp (R2_PROF); NULL: off
-extern "C" void srk_debug_res2_prof(void* p) { srk::g_res2_prof = static_cast<long long*>(p); }
-#endif

@@ -33,11 +33,6 @@
 
 namespace srk {
 
-// constant-ablation builds (tools/tu_variant.sh RN<bits> conv_rown.hip -DRN_ABL=<bits>; 0 in the release library):
-// 1 no column sums, 2 no matrix phase, 4 no commit (split + LDS stores), 8 no global loads, 16 no z stores
-#ifndef RN_ABL
-#define RN_ABL 0
-#endif
 constexpr int RN_TW = 64;             // output columns per block
 constexpr int RN_ZS = 36;             // z row stride in floats (conflict-free C/D fragment writes, as TAPN_ZS)
 
@@ -184,10 +179,10 @@ __global__ __launch_bounds__(256, 2) void k_conv_rown(MfmaConvParams P) {
   issue(0);
   for (int hh = 0; hh < nrows; ++hh) {
     const bool rok = row_in_image(hh);   // block-uniform
-    if (rok && !(RN_ABL & 4)) commit();
-    if (!(RN_ABL & 8)) issue(hh + 1);    // in flight across the matrix phase and the column sums
+    if (rok) commit();
+    issue(hh + 1);    // in flight across the matrix phase and the column sums
     __syncthreads();
-    if (rok && !(RN_ABL & 2)) {
+    if (rok) {
       // ---- matrix phase: this wave's K pairs over the four 16-pixel tiles of the row
 #pragma unroll 1
       for (int mh = 0; mh < RN_TW / 32; ++mh) {   // two 16-pixel tiles at a time: four independent accumulator chains
@@ -232,22 +227,17 @@ __global__ __launch_bounds__(256, 2) void k_conv_rown(MfmaConvParams P) {
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
           float* zr = zs + (size_t)(wave * RN_TW + (mh * 2 + m) * 16 + kq * 4) * RN_ZS + j;
-          if (!(RN_ABL & 16)) {
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
+          for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-              for (int e = 0; e < 4; ++e) zr[e * RN_ZS + nt * 16] = acc[m][nt][e];
-          } else {
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) asm volatile("" ::"v"(acc[m][nt]));
-          }
+            for (int e = 0; e < 4; ++e) zr[e * RN_ZS + nt * 16] = acc[m][nt][e];
         }
       }
     }
     __syncthreads();
     // ---- column sums: thread (x, oc) keeps the KH running sums of its output column in REGISTERS -- col[u] belongs to
     // output row hh - u; after this row's terms the oldest one (u = KH - 1) is complete, then the window shifts by one row
-    if (cs_on && !(RN_ABL & 1)) {
+    if (cs_on) {
       if (rok) {
         const float* z = zs + (size_t)cs_x * RN_ZS + cs_oc;
         float zv[KW][4];

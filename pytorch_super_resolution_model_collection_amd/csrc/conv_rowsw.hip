@@ -2,7 +2,7 @@
 // of an MFMA step = 8 taps of one kernel row x 4 channels) for problems of benchmark size (the 3 -> 64 5x5 layer of
 // ESPCN on 64 x 256x256: 16384 tiles, 1.04 GB of output).
 //
-// Why: the per-tile kernel's phases do not overlap.  SRK_ROWS_DBG ablations on that layer (320 us): without the halo
+// Why: the per-tile kernel's phases do not overlap.  Phase ablations on that layer (320 us): without the halo
 // loads 232 us (the 19 MB input costs 90 us of pure latency: every block waits for its own few loads), without the
 // epilogue 170, without the MFMAs 243, loop skeleton + per-step filter copies alone 63; a linear fill of the output
 // runs in 180 us on the same box (tools/micro/store_pattern.hip: 64-byte segments per pixel store as fast as whole
@@ -39,19 +39,7 @@ struct RowswParams {
   const float* w_descale;  // F16: trailer {2^-kw, 2^kw} of the fp16 section
   int KS, NBfull, OCb, NPIXp, ntiles, nsl;
   unsigned out_bytes;
-  int dbg;  // ablation (SRK_ROWSW_DBG): 1 no global loads, 2 no stores, 4 no MFMA loop, 16 no LDS commit
-#ifdef SRK_ROWSR_PROF
-  unsigned* prof;  // phase-clock build (tools/rowsr_prof.py): 8 counters per wave
-#endif
 };
-#ifdef SRK_ROWSR_PROF
-static unsigned* g_rowsr_prof = nullptr;
-#define RS_T() ((unsigned)clock64())  /* s_memtime (gfx950 has no SHADER_CYCLES register) */
-#define RS_ACC(i, a, b) pacc[i] += (b) - (a)
-#else
-#define RS_T() 0u
-#define RS_ACC(i, a, b) do { } while (0)
-#endif
 
 // add-and-carry walk over the tiles first, first + step, ... of a block (wave-uniform, scalar registers): a 32-bit
 // division is ~40 VALU instructions = 160 SIMD cycles per wave, and the per-stage decode had three of them
@@ -150,7 +138,6 @@ __global__ __launch_bounds__(512, 2) void k_conv_rowsw(RowswParams B) {
   auto issue = [&]() {
     const int n = wi.n, iyb = wi.y * P.TH + P.iy0, ixb = wi.x * P.TW + P.ix0;
     wi.advance(st_n, st_y, st_x, P.tiles_x, P.tiles_y);
-    if (SRK_KDBG(B.dbg) & 1) return;
     vmask = 0;
     const float* img = P.in + (size_t)n * P.IC * plane;
 #pragma unroll
@@ -168,7 +155,6 @@ __global__ __launch_bounds__(512, 2) void k_conv_rowsw(RowswParams B) {
     }
   };
   auto commit = [&](uint4* hal) {
-    if (SRK_KDBG(B.dbg) & 16) return;
 #pragma unroll
     for (int k = 0; k < RW_IT; ++k) {
       const int hq = tid + NTHR * k;
@@ -332,8 +318,8 @@ __global__ __launch_bounds__(512, 2) void k_conv_rowsw(RowswParams B) {
 #pragma unroll
           for (int mt = 0; mt < MTW; ++mt) acc[nt][mt] = mfma16x<F16>(a[0][nt], b[0][mt], acc[nt][mt]);  // w_h * x_h
       };
-      if (!(SRK_KDBG(B.dbg) & 4)) load_frags(fa[0], fb[0]);
-      if (!(SRK_KDBG(B.dbg) & 4)) rw_static_for<0, QT>([&](auto tc) {
+      load_frags(fa[0], fb[0]);
+      rw_static_for<0, QT>([&](auto tc) {
         constexpr int t = decltype(tc)::value;
         if (t + 1 < QT) load_frags(fa[WREG ? 0 : ((t + 1) & 1)], fb[(t + 1) & 1]);
         __builtin_amdgcn_sched_barrier(0);
@@ -350,7 +336,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_rowsw(RowswParams B) {
 #pragma unroll
       for (int mt = 0; mt < MTW; ++mt) {
         const int r = pix_ok[mt] >> 16, c = pix_ok[mt] & 0xffff;
-        const bool ok = pix_ok[mt] >= 0 && r0 + r < P.PH && c0 + c < P.PW && !(SRK_KDBG(B.dbg) & 2);
+        const bool ok = pix_ok[mt] >= 0 && r0 + r < P.PH && c0 + c < P.PW;
         if (ok) pend_mask |= 1 << mt;
         pend_voff[mt] = ok ? tile_off + 4u * (unsigned)poff[mt] : kDrop;
 #pragma unroll
@@ -375,8 +361,8 @@ __global__ __launch_bounds__(512, 2) void k_conv_rowsw(RowswParams B) {
 // ---------------------------------------------------------------------------------------------------------------------
 // k_conv_rowsr: the same layer with ROW-REUSED pixel fragments and the filter in registers (round 4).
 //
-// k_conv_rowsw on the c2 first layer (3 -> 64, 5x5, 64 x 256x256; builds with the ablation word as a compile-time
-// constant, -DSRK_KDBG_CONST, 310 us): skeleton (staging, parking, barriers) alone 66 us, + the MFMA loop 219 us, + the
+// k_conv_rowsw on the c2 first layer (3 -> 64, 5x5, 64 x 256x256; constant-ablation builds, DESIGN
+// 10.7, 310 us): skeleton (staging, parking, barriers) alone 66 us, + the MFMA loop 219 us, + the
 // stores 310 us, where the layer's 7.9 M MFMAs are 102 us of matrix issue.  Two things: (1) per 32 pixels a wave read the
 // whole filter (40 x ds_read_b128) and 20 pixel fragments for 120 MFMAs -- 480 reads = 1920 LDS cycles per 256-pixel
 // stage and CU beside 3840 clocks of matrix issue per SIMD, every first read of a K step in front of its MFMAs; (2) all
@@ -488,7 +474,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_rowsr(RowswParams B) {
   // k_conv_rowsw, and run TWO stages ahead of the LDS commit in two register sets (tile t in set t & 1): vmcnt retires in
   // order, so the wait for a tile's pixels is also a wait for every store issued before those loads -- with the loads one
   // stage ahead that was the previous stage's eight stores, one stage old, and the write acknowledgements of a chip that
-  // writes 3.5 TB/s take longer than that (constant-ablation builds, tools/build_variant.sh -DSRK_KDBG_CONST: the layer in
+  // writes 3.5 TB/s take longer than that (constant-ablation builds, DESIGN 10.7: the layer in
   // 199 us without the loads, 176 us without the stores, 302 us with both).  Now the wait covers stores two stages old.
   // Everything is issued unconditionally -- tiles past the end of the block's range are dummies (clamped loads, a commit
   // nobody reads, stores dropped) and the stage loop runs in pairs -- so that the compiler can count: a path on which an
@@ -508,7 +494,6 @@ __global__ __launch_bounds__(256, 2) void k_conv_rowsr(RowswParams B) {
     const int n = live ? wi.n : 0, ty = live ? wi.y : 0, tx = live ? wi.x : 0;
     const int iy = ty * TH + P.iy0 + hy0, ix = tx * TW + (BAND ? 0 : P.ix0) + hx0;
     walk(wi);
-    if (SRK_KDBG(B.dbg) & 1) return;
     vok[st] = (BAND ? live : true) && tid < nstage && (unsigned)iy < (unsigned)P.IH && (unsigned)ix < (unsigned)P.IW;
     const int cy = min(max(iy, 0), P.IH - 1), cx = min(max(ix, 0), P.IW - 1);
     const size_t pix = (size_t)cy * P.IW + cx;
@@ -522,7 +507,6 @@ __global__ __launch_bounds__(256, 2) void k_conv_rowsr(RowswParams B) {
   };
   auto commit = [&](uint4* hal, auto setc) {
     constexpr int st = decltype(setc)::value;
-    if (SRK_KDBG(B.dbg) & 16) return;
     uint2 hu, lu;
     if constexpr (F16) {
       typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
@@ -618,14 +602,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_rowsr(RowswParams B) {
     }
   asm volatile("" ::"v"(act_slope));
   __syncthreads();  // tile 0 visible
-#ifdef SRK_ROWSR_PROF
-  unsigned pacc[5] = {0, 0, 0, 0, 0};
-  unsigned pgrp[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // clocks per row group R of the matrix loop (SRK_ROWSR_PROF=2)
-  unsigned pprev = 0;
-#endif
   auto stage = [&](const int s, auto nset) {  // nset: register set of tile s + 1 (= of tile s + 3)
-    const unsigned pt0 = RS_T();
-    unsigned pt1 = 0, pt2 = 0, pt3 = 0;
     const int n = wc.n, r0 = wc.y * TH, c0 = wc.x * TW;
     const int bt = wc.x;
     walk(wc);
@@ -652,8 +629,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_rowsr(RowswParams B) {
         b[1] = make_uint4(p0.z, p0.w, p1.z, p1.w);
         roff += rstep;
       };
-      if (!(SRK_KDBG(B.dbg) & 4)) load_row(fb[0]);
-      if (!(SRK_KDBG(B.dbg) & 4)) rw_static_for<0, NR>([&](auto rc) {
+      load_row(fb[0]);
+      rw_static_for<0, NR>([&](auto rc) {
         constexpr int R = decltype(rc)::value;
         if (R + 1 < NR) load_row(fb[(R + 1) & 1]);
         __builtin_amdgcn_sched_barrier(0);
@@ -683,26 +660,16 @@ __global__ __launch_bounds__(256, 2) void k_conv_rowsr(RowswParams B) {
         __builtin_amdgcn_sched_barrier(0);
         rw_static_for<(R * PER_STEP < NST ? R * PER_STEP : NST), ((R + 1) * PER_STEP < NST ? (R + 1) * PER_STEP : NST)>(
             [&](auto qc) { store_slot(qc); });
-#if defined(SRK_ROWSR_PROF) && SRK_ROWSR_PROF == 2
-        {
-          const unsigned tn = RS_T();
-          pgrp[R & 7] += tn - (R == 0 ? pt0 : pprev);
-          pprev = tn;
-        }
-#endif
       });
-      pt1 = RS_T();
       if constexpr (BAND) commit(hal0 + (size_t)((s + 2) & 3) * BSLOT, nset);  // chunk s + 2 (slot last read in stage s - 1)
       else commit(hal0 + (size_t)((s + 1) & 1) * B.NPIXp, nset);  // tile s + 1 (that buffer was last read in stage s - 1)
-      pt2 = RS_T();
       issue(nset);                                            // tile s + 3 (BAND: chunk s + 4)
-      pt3 = RS_T();
       // tile finished: park it (C/D col = lane & 15 = pixel column, rows kq*4 + reg = 4 consecutive channels)
       const unsigned tile_off = 4u * (unsigned)epi_tile_setup(P, n, r0, c0).off0;
 #pragma unroll
       for (int mt = 0; mt < MTW; ++mt) {
         const int r = rg * MTW + mt;
-        const bool ok = s < S && r0 + r < P.PH && c0 + j < P.PW && !(SRK_KDBG(B.dbg) & 2);
+        const bool ok = s < S && r0 + r < P.PH && c0 + j < P.PW;
         pend_voff[mt] = ok ? tile_off + 4u * (unsigned)(r * e0.RS + j * e0.CS) : kDrop;
 #pragma unroll
         for (int nt = 0; nt < NTW; ++nt) {
@@ -721,11 +688,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_rowsr(RowswParams B) {
         }
       }
     }
-    const unsigned pt4 = RS_T();
     __syncthreads();
-    const unsigned pt5 = RS_T();
-    (void)pt0; (void)pt1; (void)pt2; (void)pt3; (void)pt4; (void)pt5;
-    RS_ACC(0, pt0, pt1); RS_ACC(1, pt1, pt2); RS_ACC(2, pt2, pt3); RS_ACC(3, pt3, pt4); RS_ACC(4, pt4, pt5);
   };
   for (int s0 = 0; s0 < S; s0 += 2) {  // (an odd S ends with one dummy stage)
     if constexpr (BAND) {
@@ -738,17 +701,6 @@ __global__ __launch_bounds__(256, 2) void k_conv_rowsr(RowswParams B) {
   }
   rw_static_for<0, NST>([&](auto qc) { store_slot(qc); });  // the last tile (S = 0: nothing parked, dropped)
   if (P.ep.y_amax) amax_commit(P.ep.y_amax, amax, blockIdx.x + wave, amax_peek(P.ep.y_amax, blockIdx.x + wave));
-#ifdef SRK_ROWSR_PROF
-  if (B.prof && lane == 0) {
-#pragma unroll
-    for (int i = 0; i < 5; ++i) B.prof[((size_t)blockIdx.x * 4 + wave) * 8 + i] = pacc[i];
-    B.prof[((size_t)blockIdx.x * 4 + wave) * 8 + 5] = (unsigned)S;
-#if SRK_ROWSR_PROF == 2
-#pragma unroll
-    for (int i = 0; i < 8; ++i) B.prof[(size_t)gridDim.x * 32 + ((size_t)blockIdx.x * 4 + wave) * 8 + i] = pgrp[i];
-#endif
-  }
-#endif
 }
 
 // the tile (<= 256 pixels) that covers PH x PW with the fewest tiles and a halo of at most cap_px pixels
@@ -859,8 +811,6 @@ int conv_rowsw_gather(const GatherConv& g, const float* in, const float* wp, flo
     // barrier work: measured 366 us against 289 us on the c2 first layer, even with the filter in registers.)
     constexpr int ntw = 4;
     B.nsl = P.OC / (16 * ntw);
-    const int dbg = SRK_EXP_INT("SRK_ROWSW_DBG", 0);
-    B.dbg = dbg;
     // row-reused fragments, filter in registers, two 4-wave blocks per CU (k_conv_rowsr): one K step per kernel row and the
     // fixed 8 x 16 tile's halo on one pixel per thread.  SRK_ROWSR=0: the 8-wave kernel below.
     if (P.is == 1 && B.KS == 1 && (Q == 3 || Q == 5) && (7 + P.KHv) * (15 + P.KWv) <= 256 && env_int("SRK_ROWSR", 1) != 0) {
@@ -887,9 +837,6 @@ int conv_rowsw_gather(const GatherConv& g, const float* in, const float* wp, flo
           B.ntiles = (int)nbands;
           B.out_bytes = (unsigned)((size_t)P.N * P.OH * P.OW * P.OC * sizeof(float));
           const size_t lds = (size_t)5 * (7 + P.KHv) * 16 * 16;
-#ifdef SRK_ROWSR_PROF
-          B.prof = g_rowsr_prof;
-#endif
           return Q == 3 ? rowsr_launch<3, true>(B, lds, grid, s) : rowsr_launch<5, true>(B, lds, grid, s);
         }
       }
@@ -897,9 +844,6 @@ int conv_rowsw_gather(const GatherConv& g, const float* in, const float* wp, flo
         B.ntiles = (int)ntiles;
         B.out_bytes = (unsigned)((size_t)P.N * P.OH * P.OW * P.OC * sizeof(float));
         const size_t lds = (size_t)2 * B.NPIXp * 16;
-#ifdef SRK_ROWSR_PROF
-        B.prof = g_rowsr_prof;
-#endif
         int grid = 2 * kNumCU - (2 * kNumCU) % (8 * B.nsl);
         const long want = ((ntiles + 7) / 8) * 8 * B.nsl;
         if (want < grid) grid = (int)want;
@@ -926,8 +870,3 @@ int conv_rowsw_gather(const GatherConv& g, const float* in, const float* wp, flo
 }
 
 }  // namespace srk
-
-#ifdef SRK_ROWSR_PROF
-// phase-clock build only: device buffer of 8 x uint32 per wave (4 waves per block) that the next k_conv_rowsr launches fill
-extern "C" void srk_debug_rowsr_prof(void* p) { srk::g_rowsr_prof = static_cast<unsigned*>(p); }
-#endif

@@ -59,23 +59,6 @@ __device__ __forceinline__ void wb_item(int tid, int& q, int& pp0) {
     pp0 = tid / QN;
   }
 }
-// WB_PIPE: software-pipelined K loop of the 3x3 kernels (see kloop); 0 = the round-4 loop (tools/build_variant.sh A/B)
-#ifndef WB_PIPE
-#define WB_PIPE 0
-#endif
-#ifndef WB_PRIO
-#define WB_PRIO 0
-#endif
-// ablation bits of k_wgrad_tr's inner loop (16 no fragment reads, 64 no column shifts): compile-time only (-DSRK_KDBG_CONST=..),
-// also in the experiments build -- a run-time test inside the phases changes their schedule (K step 1450 -> 3200 clocks)
-#ifdef SRK_KDBG_CONST
-#define WT_ABL (SRK_KDBG_CONST)
-#else
-#define WT_ABL 0
-#endif
-#ifndef WT_SGB
-#define WT_SGB 1
-#endif
 constexpr int WB_IT = 1;       // pixel pairs per thread loaded together while staging (4 measured: no gain plain, spills in the specialised variant)
 
 struct WgBfParams {
@@ -92,11 +75,9 @@ struct WgBfParams {
   int CS, DS;  // per-channel plane strides (bf16 elements) of the X halo / dY tile
   int ntiles, G, nks;
   int vec_x, vec_y;
-  int dbg;  // ablation (SRK_DBG): 2 skip the staging, 4 skip the K loop
+  int pad_;  // unused: without it the compiler schedules the integer divisions of k_wgrad_bf differently
   int dy_ps_r, dy_ps_C;  // dY handed over pixel-shuffled [N, YH*r, YW*r, Cout/r^2]: un-shuffled while staging
   int prefetch;          // SPEC: a tile's loads fit the stagers' register batch (WB_PIT x 512 items): load one tile ahead
-  long long* prof;       // experiments build only (srk_debug_wgrad_prof): per block 16 int64 -- clock64() sums of the first stager
-                         // wave {commit, issue, barrier wait, tiles} and of worker wave 0 {K loop, barrier wait, tiles, K steps}
   int ring;              // SPEC + prefetch: X halo rows live in a ring of 2 * HH rows shared by vertically adjacent tiles
                          // (a block walks a CONTIGUOUS range of tiles, rows fastest): a tile below its predecessor loads
                          // only its TH new rows instead of all TH + KH - 1 (2-row tiles: the X read halves).  CS is then
@@ -138,22 +119,9 @@ struct WgGroupOut {
   WgOut L[WB_MAXGROUP];
 };
 
-#ifdef SRK_EXPERIMENTS
-#define WB_CLK() clock64()
-static long long* g_wb_prof = nullptr;
-#else
-#define WB_CLK() 0ll
-#endif
-
 __device__ __forceinline__ f32x4 wb_mfma(const uint4& a, const uint4& b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0,
                                                  0);
-}
-
-// ablation helpers: a value the compiler must materialise / may not assume anything about
-__device__ __forceinline__ void wb_keep(const uint4& a) { asm volatile("" ::"v"(a.x), "v"(a.y), "v"(a.z), "v"(a.w)); }
-__device__ __forceinline__ void wb_touch(uint4& a, int dep) {
-  asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w) : "v"(dep));
 }
 
 __device__ __forceinline__ unsigned short wb_bits(__bf16 v) { return __builtin_bit_cast(unsigned short, v); }
@@ -233,9 +201,9 @@ __global__ __launch_bounds__(SPEC ? 64 * CIT * COW + WB_SST : 64 * CIT * COW,
                                  SPEC ? (64 * CIT * COW + WB_SST) / 256 : (CIT * COW == 4 ? 2 : 1)) void k_wgrad_bf(WgBfParams P,
                                                                              typename WgGroupArg<GRP>::type GR) {
   constexpr int CIB = CIT * 16, COB = COW * NTW * 16;
-  // NWV working waves: 4.  (Round 4, tools/wgrad_prof.py: the worker wave's K loop is 97 % of its time and ~2080 clocks per K
+  // NWV working waves: 4.  (Round 4, DESIGN 10.3b: the worker wave's K loop is 97 % of its time and ~2080 clocks per K
   // step for ~920 clocks of MFMA issue, while the stagers wait 30 - 49 % of a tile at the barrier -- the workers pace the kernel.
-  // EIGHT working waves (<2, 4, 1>: two per SIMD taking turns at the matrix pipe, 104 VGPRs, -DSRK_EXPERIMENTS + SRK_WG_W8=1)
+  // EIGHT working waves (<2, 4, 1>: two per SIMD taking turns at the matrix pipe, 104 VGPRs)
   // were measured SLOWER: VDSR layer 0.154 -> 0.184 ms, step 6.00 -> 6.62 ms, EDSR 6.07 -> 6.42 ms.  They read 1.75x the LDS
   // bytes per K step (every X fragment once per output-channel column): the shared LDS pipe -- fragment reads against the
   // stagers' 4-byte transposing writes -- is what the K loop waits for, not latency a second wave could hide.)
@@ -338,7 +306,7 @@ __global__ __launch_bounds__(SPEC ? 64 * CIT * COW + WB_SST : 64 * CIT * COW,
     const int tyi = b % P.tiles_y;
     const int n = b / P.tiles_y;
     const int r0 = tyi * P.TH, c0 = txi * P.TW;
-    if (!(SRK_KDBG(P.dbg) & 2)) {  // X halo: rows [r0-pad, +HH), cols [c0-pad, +TW+KW-1), channels [cib, cib+CIB) -> planes [ci][hy][hx]
+    {  // X halo: rows [r0-pad, +HH), cols [c0-pad, +TW+KW-1), channels [cib, cib+CIB) -> planes [ci][hy][hx]
       // A thread's channel group q is fixed (256 % QN == 0): it walks pixel pairs pp, pp + 256/QN, ...
       constexpr int QN = CIB / 4, PSTEP = NST / QN;
       // only the TW + KW - 1 columns the fragments can touch are loaded (the plane row stride HWp = TW + 8 is for
@@ -385,7 +353,7 @@ __global__ __launch_bounds__(SPEC ? 64 * CIT * COW + WB_SST : 64 * CIT * COW,
         }
       }
     }
-    if (!(SRK_KDBG(P.dbg) & 2)) {  // dY tile: rows [r0, +TH), cols [c0, +TW), channels [cob, cob+COB) -> planes [co][r][c] (masked)
+    {  // dY tile: rows [r0, +TH), cols [c0, +TW), channels [cob, cob+COB) -> planes [co][r][c] (masked)
       constexpr int QN = COB / 4, PSTEP = NST / QN;
       const unsigned tw2_magic = wb_magic20(tw2);
       const int npairs = P.TH * tw2;
@@ -635,148 +603,10 @@ __global__ __launch_bounds__(SPEC ? 64 * CIT * COW + WB_SST : 64 * CIT * COW,
     const unsigned short* xa_l = xa_h + (size_t)CIB * P.CS;
     const unsigned short* yb_h = ys + (size_t)(cow * NTW * 16 + i) * P.DS;
     const unsigned short* yb_l = yb_h + (size_t)COB * P.DS;
-    if constexpr (K33 && WB_PIPE) {
-      // Round 5: the K loop as a software pipeline over (K step, kernel row) phases.  The loop below this one reads a K
-      // step's fragments at the top of that step: its ISA has three exposed LDS round trips per K step (the first
-      // row's reads, and two ds_read_b128 the compiler sinks into the MFMA stream with an s_waitcnt lgkmcnt(0) right
-      // behind each) -- with ONE working wave per SIMD nothing else can use the matrix pipe meanwhile (~2080 clocks per K
-      // step for 864 clocks of MFMA issue, tools/wgrad_prof.py).  Here the X fragments of phase p + 1 (the next kernel
-      // row; at a step's last row the next step's first row and its dY fragments) are requested BEFORE the 9 * NTW MFMAs
-      // of phase p, into a second register set; sched_barriers keep the requests where they are written, the waits the
-      // compiler inserts are then counted ones (lgkmcnt(4..8)) behind a phase's worth of MFMAs.  Two K steps per loop
-      // trip so that the two register sets alternate without copies.  Same products, same order per accumulator:
-      // bit-equal to the loop below.
-      struct XF {
-        uint4 h, l;
-        unsigned eh, el;
-      };
-      // one packed table word per octet (oct_pk: dY offset | halo column << 12 | tile row << 20); ring and plain tiles share
-      // the address form  halo row slot = (base + tile row + u) mod ring rows  (plain: base 0, no wrap)
-      struct TB {
-        int oy, orr, oc;
-      };
-      const int nks_run = (SRK_KDBG(P.dbg) & 4) ? 0 : P.nks;
-      if (nks_run <= 0) return;
-      const int last = nks_run - 1;
-      const int rb = ring ? rbase : 0, rwrap = ring ? R2 : (1 << 20);
-      auto tab = [&](int ks) -> TB {
-        const unsigned w = (unsigned)oct_pk[(ks < last ? ks : last) * 4 + kq];
-        TB t;
-        t.oy = (int)(w & 0xfffu);
-        t.oc = (int)((w >> 12) & 0xffu);
-        t.orr = (int)(w >> 20) + rb;
-        return t;
-      };
-      auto xload = [&](XF& f, const TB& t, int u) {
-        int slot = t.orr + u;
-        slot = slot >= rwrap ? slot - rwrap : slot;
-        const int xo = slot * P.HWp + t.oc;
-        if (SRK_KDBG(P.dbg) & 16) {  // ablation: no fragment reads (the MFMAs run on whatever the registers hold)
-          wb_touch(f.h, xo);
-          wb_touch(f.l, xo);
-          asm volatile("" : "+v"(f.eh), "+v"(f.el) : "v"(xo));
-          return;
-        }
-        f.h = *reinterpret_cast<const uint4*>(xa_h + xo);
-        f.l = *reinterpret_cast<const uint4*>(xa_l + xo);
-        if (SRK_KDBG(P.dbg) & 32) return;   // ablation: no 4-byte tail reads
-        f.eh = *reinterpret_cast<const unsigned*>(xa_h + xo + 8);
-        f.el = *reinterpret_cast<const unsigned*>(xa_l + xo + 8);
-      };
-      auto yload = [&](uint4 (&bh)[NTW], uint4 (&bl)[NTW], int oy) {
-        if (SRK_KDBG(P.dbg) & (16 | 128)) {
-#pragma unroll
-          for (int nt = 0; nt < NTW; ++nt) {
-            wb_touch(bh[nt], oy);
-            wb_touch(bl[nt], oy);
-          }
-          return;
-        }
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) {
-          bh[nt] = *reinterpret_cast<const uint4*>(yb_h + (size_t)nt * 16 * P.DS + oy);
-          bl[nt] = *reinterpret_cast<const uint4*>(yb_l + (size_t)nt * 16 * P.DS + oy);
-        }
-      };
-      auto rowmm = [&](const XF& f, const uint4 (&bh)[NTW], const uint4 (&bl)[NTW], f32x4 (&a)[3][NTW]) {
-        uint4 ah[3], al[3];
-        ah[0] = f.h;
-        al[0] = f.l;
-        ah[1] = make_uint4(__builtin_amdgcn_alignbit(f.h.y, f.h.x, 16), __builtin_amdgcn_alignbit(f.h.z, f.h.y, 16),
-                           __builtin_amdgcn_alignbit(f.h.w, f.h.z, 16), __builtin_amdgcn_alignbit(f.eh, f.h.w, 16));
-        al[1] = make_uint4(__builtin_amdgcn_alignbit(f.l.y, f.l.x, 16), __builtin_amdgcn_alignbit(f.l.z, f.l.y, 16),
-                           __builtin_amdgcn_alignbit(f.l.w, f.l.z, 16), __builtin_amdgcn_alignbit(f.el, f.l.w, 16));
-        ah[2] = make_uint4(f.h.y, f.h.z, f.h.w, f.eh);
-        al[2] = make_uint4(f.l.y, f.l.z, f.l.w, f.el);
-        if (SRK_KDBG(P.dbg) & 64) {  // ablation: no column shifts (every tap column multiplies the unshifted fragment)
-          ah[1] = ah[2] = ah[0];
-          al[1] = al[2] = al[0];
-        }
-        if (SRK_KDBG(P.dbg) & 8) {  // ablation: fragment reads and shifts, no MFMAs
-#pragma unroll
-          for (int v = 0; v < 3; ++v) {
-            wb_keep(ah[v]);
-            wb_keep(al[v]);
-          }
-#pragma unroll
-          for (int nt = 0; nt < NTW; ++nt) {
-            wb_keep(bh[nt]);
-            wb_keep(bl[nt]);
-          }
-          return;
-        }
-#pragma unroll
-        for (int v = 0; v < 3; ++v)
-#pragma unroll
-          for (int nt = 0; nt < NTW; ++nt) a[v][nt] = wb_mfma(al[v], bh[nt], a[v][nt]);
-#pragma unroll
-        for (int v = 0; v < 3; ++v)
-#pragma unroll
-          for (int nt = 0; nt < NTW; ++nt) a[v][nt] = wb_mfma(ah[v], bl[nt], a[v][nt]);
-#pragma unroll
-        for (int v = 0; v < 3; ++v)
-#pragma unroll
-          for (int nt = 0; nt < NTW; ++nt) a[v][nt] = wb_mfma(ah[v], bh[nt], a[v][nt]);
-      };
-      // one K step: rows 0..2 of step `tc` from (x0, yh, yl); leaves row 0 and the dY fragments of step `tn` in (xn, nh, nl)
-      auto step = [&](const XF& x0, const uint4 (&yh)[NTW], const uint4 (&yl)[NTW], XF& xn, uint4 (&nh)[NTW],
-                      uint4 (&nl)[NTW], const TB& tc, const TB& tn) {
-        XF x1 = {}, x2 = {};
-        xload(x1, tc, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        rowmm(x0, yh, yl, acc[0]);
-        __builtin_amdgcn_sched_barrier(0);
-        xload(x2, tc, 2);
-        __builtin_amdgcn_sched_barrier(0);
-        rowmm(x1, yh, yl, acc[1]);
-        __builtin_amdgcn_sched_barrier(0);
-        xload(xn, tn, 0);
-        yload(nh, nl, tn.oy);
-        __builtin_amdgcn_sched_barrier(0);
-        rowmm(x2, yh, yl, acc[2]);
-        __builtin_amdgcn_sched_barrier(0);
-      };
-      TB t0 = tab(0), t1 = tab(1);
-      XF xa = {}, xb = {};
-      uint4 yah[NTW] = {}, yal[NTW] = {}, ybh[NTW] = {}, ybl[NTW] = {};
-      xload(xa, t0, 0);
-      yload(yah, yal, t0.oy);
-      int ks = 0;
-      for (; ks + 1 < nks_run; ks += 2) {
-        const TB t2 = tab(ks + 2);
-        step(xa, yah, yal, xb, ybh, ybl, t0, t1);
-        const TB t3 = tab(ks + 3);
-        step(xb, ybh, ybl, xa, yah, yal, t1, t2);
-        t0 = t2;
-        t1 = t3;
-      }
-      if (ks < nks_run) step(xa, yah, yal, xb, ybh, ybl, t0, t1);
-      return;
-    }
     if constexpr (K33) {
       // (round 4: the octet tables of K step ks + 1 are read while step ks multiplies -- the lookups were a dependent LDS
       //  round trip in front of every K step's fragment reads, with one working wave per SIMD and nothing to hide it)
-      const int nks_run = (SRK_KDBG(P.dbg) & 4) ? 0 : P.nks;
+      const int nks_run = P.nks;
       int ox_n = oct_x[kq], oy_n = oct_y[kq], or_n = ring ? oct_r[kq] : 0, oc_n = ring ? oct_c[kq] : 0;
       for (int ks = 0; ks < nks_run; ++ks) {
         const int ox = ox_n, oy = oy_n;
@@ -814,7 +644,7 @@ __global__ __launch_bounds__(SPEC ? 64 * CIT * COW + WB_SST : 64 * CIT * COW,
         for (int u = 0; u < 3; ++u) {
           // the three column shifts of this row, then pass-major over its 3 * NTW accumulators: two MFMAs on one
           // accumulator are 3 * NTW issues apart (back to back they wait for each other's result)
-          // (Round 4, tools/wgrad_prof.py: the WORKER wave, not the stagers, paces this kernel -- K loop 97 % of its time,
+          // (Round 4, DESIGN 10.3b: the WORKER wave, not the stagers, paces this kernel -- K loop 97 % of its time,
           //  ~2080 clocks per K step for 54 MFMAs, while the first stager wave waits 30 - 49 % of a tile at the barrier.  The
           //  compiler sinks two fragment reads into the MFMA stream and threads the 24 v_perm of the column shifts between the
           //  matrix instructions; scheduling fences that force "all reads, 8 v_perm, 18 MFMAs" per row shift (168 VGPRs) were
@@ -844,7 +674,7 @@ __global__ __launch_bounds__(SPEC ? 64 * CIT * COW + WB_SST : 64 * CIT * COW,
       }
       return;
     }
-    for (int ks = 0; ks < ((SRK_KDBG(P.dbg) & 4) ? 0 : P.nks); ++ks) {
+    for (int ks = 0; ks < P.nks; ++ks) {
       const int ox = oct_x[ks * 4 + kq], oy = oct_y[ks * 4 + kq];
       const int orw = ring ? rbase + oct_r[ks * 4 + kq] : 0, ocl = ring ? oct_c[ks * 4 + kq] : 0;
       uint4 bh[NTW], bl[NTW];
@@ -917,32 +747,18 @@ __global__ __launch_bounds__(SPEC ? 64 * CIT * COW + WB_SST : 64 * CIT * COW,
     // Two loops, one per role, with the same barriers (1 + ntb): the stagers' prefetch registers and the workers'
     // accumulators are never live in the same wave.
     if (stager) {
-      if (P.prefetch && !(SRK_KDBG(P.dbg) & 2)) {
+      if (P.prefetch) {
         if (ntb > 0) {
           issue(first_tile, 0);
           commit(0);
           if (ntb > 1) issue(first_tile + tstep, 1);
         }
         __syncthreads();
-        long long st_commit = 0, st_issue = 0, st_wait = 0;
         for (int it = 0; it < ntb; ++it) {
-          const long long c0 = WB_CLK();
           if (it + 1 < ntb) commit((it + 1) & 1);        // tile it+1: its loads were issued an iteration ago
-          const long long c1 = WB_CLK();
           if (it + 2 < ntb) issue(first_tile + (it + 2) * tstep, it + 2);  // tile it+2: lands under the K loop of tile it+1
-          const long long c2 = WB_CLK();
           __syncthreads();
-          st_commit += c1 - c0;
-          st_issue += c2 - c1;
-          st_wait += WB_CLK() - c2;
         }
-#ifdef SRK_EXPERIMENTS
-        if (P.prof && tid0 == WTHR) {
-          long long* pr = P.prof + ((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 16;
-          pr[0] = st_commit; pr[1] = st_issue; pr[2] = st_wait; pr[3] = ntb;
-        }
-#endif
-        (void)st_commit; (void)st_issue; (void)st_wait;
       } else {
         if (ntb > 0) stage(bx, 0);     // (no ring without the prefetch path: the host never sets both)
         __syncthreads();
@@ -953,25 +769,12 @@ __global__ __launch_bounds__(SPEC ? 64 * CIT * COW + WB_SST : 64 * CIT * COW,
       }
     } else {
       __syncthreads();
-      if (WB_PRIO) __builtin_amdgcn_s_setprio(WB_PRIO);  // (this branch is taken by whole waves: wave >= NWV is wave-uniform)
       int wprev = P.HH;
-      long long wk_loop = 0, wk_wait = 0;
       for (int it = 0; it < ntb; ++it) {
-        const long long k0 = WB_CLK();
         if (ring) wprev = ring_next(wprev, it == 0 || ((first_tile + it) % P.tiles_y) == 0);
         kloop(it & 1, wprev);
-        const long long k1 = WB_CLK();
         __syncthreads();
-        wk_loop += k1 - k0;
-        wk_wait += WB_CLK() - k1;
       }
-#ifdef SRK_EXPERIMENTS
-      if (P.prof && tid0 == 0) {
-        long long* pr = P.prof + ((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 16 + 8;
-        pr[0] = wk_loop; pr[1] = wk_wait; pr[2] = ntb; pr[3] = (long long)ntb * P.nks;
-      }
-#endif
-      (void)wk_loop; (void)wk_wait;
     }
   }
 
@@ -1027,7 +830,7 @@ __global__ __launch_bounds__(SPEC ? 64 * CIT * COW + WB_SST : 64 * CIT * COW,
 //
 // * a staging item is ONE pixel x 8 channels (two 16-byte loads): the bf16 split packs CHANNEL pairs and leaves as one
 //   ds_write_b128 per plane -- 2 LDS stores per item instead of the 8 transposing ds_write_b32 of k_wgrad_bf (the eight
-//   stager waves were bound by their instruction issue: tools/wgrad_variant.sh ablations, stagers alone 133 us of the
+//   stager waves were bound by their instruction issue: DESIGN 12.2, stagers alone 133 us of the
 //   170 us VDSR layer);
 // * a working wave's MFMA fragment (lane = channel, 8 consecutive pixels of a tile row) comes out of two transpose reads:
 //   in a 16-lane group lane r addresses pixel (r >> 2), channels 4 (r & 3) .. + 3 and receives channel r of the
@@ -1058,7 +861,6 @@ __global__ __launch_bounds__(768, 3) void k_wgrad_tr(WgBfParams P, typename WgGr
   constexpr int CIB = 32, COB = 64, NTW = 2, NWV = 8 / NTW, WTHR = 64 * NWV, NST = WB_SST, NTHR = WTHR + NST, PIT = 1024 / NST;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem8[];
   __shared__ unsigned oct_tw[WB_MAXOCT];
-  const long long clk_begin = WB_CLK();
   const int tid0 = threadIdx.x, lane = tid0 & 63, wave = tid0 >> 6;
   const bool worker = wave < NWV;
   const int tid = worker ? tid0 : tid0 - WTHR;
@@ -1249,35 +1051,16 @@ __global__ __launch_bounds__(768, 3) void k_wgrad_tr(WgBfParams P, typename WgGr
         }
       }
     };
-    if (!(SRK_KDBG(P.dbg) & 2)) {
-      if (ntb > 0) {
-        issue(first_tile, 0);
-        commit(0);
-        if (ntb > 1) issue(first_tile + 1, 1);
-      }
+    if (ntb > 0) {
+      issue(first_tile, 0);
+      commit(0);
+      if (ntb > 1) issue(first_tile + 1, 1);
+    }
+    __syncthreads();
+    for (int it = 0; it < ntb; ++it) {
+      if (it + 1 < ntb) commit((it + 1) & 1);              // tile it + 1: its loads were issued an iteration ago
+      if (it + 2 < ntb) issue(first_tile + it + 2, it + 2);  // tile it + 2: lands under the K loop of tile it + 1
       __syncthreads();
-      long long st_commit = 0, st_issue = 0, st_wait = 0;
-      for (int it = 0; it < ntb; ++it) {
-        const long long c0 = WB_CLK();
-        if (it + 1 < ntb) commit((it + 1) & 1);              // tile it + 1: its loads were issued an iteration ago
-        const long long c1 = WB_CLK();
-        if (it + 2 < ntb) issue(first_tile + it + 2, it + 2);  // tile it + 2: lands under the K loop of tile it + 1
-        const long long c2 = WB_CLK();
-        __syncthreads();
-        st_commit += c1 - c0;
-        st_issue += c2 - c1;
-        st_wait += WB_CLK() - c2;
-      }
-#ifdef SRK_EXPERIMENTS
-      if (P.prof && tid0 == WTHR) {
-        long long* pr = P.prof + ((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 16;
-        pr[0] = st_commit; pr[1] = st_issue; pr[2] = st_wait; pr[3] = ntb;
-      }
-#endif
-      (void)st_commit; (void)st_issue; (void)st_wait;
-    } else {
-      __syncthreads();
-      for (int it = 0; it < ntb; ++it) __syncthreads();
     }
     if (want_bias) {   // column sums of dY: the 64 staging threads of one 8-channel group (tid & 7) add up in LDS
       float* bred = reinterpret_cast<float*>(smem8);   // [NST][8 + 1 pad], the X ring is no longer read (barrier above)
@@ -1318,7 +1101,7 @@ __global__ __launch_bounds__(768, 3) void k_wgrad_tr(WgBfParams P, typename WgGr
   const unsigned lane_x = (unsigned)((r16 >> 2) * 64 + (r16 & 3) * 8);
   const int fl = ((r16 >> 3) & 1) | ((kq & 1) << 1);
   const unsigned lane_y0 = (unsigned)((r16 >> 2) * 128 + (r16 & 3) * 8 + (((cow * NTW) ^ fl) << 5));
-  const int nks_run = (SRK_KDBG(P.dbg) & 4) ? 0 : P.nks;
+  const int nks_run = P.nks;
   const int last = nks_run - 1;
   auto tab = [&](int ks) -> TB { return oct_tw[(ks < last ? ks : last) * 4 + kq]; };
   auto tr = [&](unsigned off) -> uint2 {
@@ -1336,7 +1119,6 @@ __global__ __launch_bounds__(768, 3) void k_wgrad_tr(WgBfParams P, typename WgGr
   };
   auto yaddr = [&](const TB& t) -> unsigned { return ysel + ((t & 0xff00u) << 2) + lane_y0; };
   auto xissue = [&](XF& f, unsigned a) {
-    if (WT_ABL & 16) return;   // ablation: no fragment reads (the MFMAs run on whatever the registers hold)
     const unsigned b = (a + 512u) ^ 32u;   // pixels 8 .. 11: the next halo octet (its channel halves are swapped)
     const uint2 h0 = tr(a), h1 = tr(a + 256u), l0 = tr(a + XPL), l1 = tr(a + XPL + 256u);
     const uint2 h2 = tr(b), l2 = tr(b + XPL);
@@ -1348,7 +1130,6 @@ __global__ __launch_bounds__(768, 3) void k_wgrad_tr(WgBfParams P, typename WgGr
     f.xl = l2.y;
   };
   auto yissue = [&](uint4 (&bh)[NTW], uint4 (&bl)[NTW], unsigned a0) {
-    if (WT_ABL & 16) return;
     const uint2 p0 = tr(a0), p1 = tr(a0 + 512u), q0 = tr(a0 + YPL), q1 = tr(a0 + YPL + 512u);
     bh[0] = make_uint4(p0.x, p0.y, p1.x, p1.y);
     bl[0] = make_uint4(q0.x, q0.y, q1.x, q1.y);
@@ -1367,10 +1148,6 @@ __global__ __launch_bounds__(768, 3) void k_wgrad_tr(WgBfParams P, typename WgGr
                        __builtin_amdgcn_alignbit(f.l.w, f.l.z, 16), __builtin_amdgcn_alignbit(f.el, f.l.w, 16));
     ah[2] = make_uint4(f.h.y, f.h.z, f.h.w, f.eh);
     al[2] = make_uint4(f.l.y, f.l.z, f.l.w, f.el);
-    if (WT_ABL & 64) {   // ablation: no column shifts
-      ah[1] = ah[2] = ah[0];
-      al[1] = al[2] = al[0];
-    }
     // (dY is the A operand: the accumulator rows are output channels, a lane's four registers four consecutive co of
     //  one ci -- one 16-byte store per tile into the [tap][ci][co] slab; same products, same order as X-first)
 #pragma unroll
@@ -1391,70 +1168,13 @@ __global__ __launch_bounds__(768, 3) void k_wgrad_tr(WgBfParams P, typename WgGr
   // (addresses computed one phase earlier) and then holds ONLY matrix instructions with the VALU work -- this row's column
   // shifts, the address of the phase after next -- threaded between them: the matrix pipe takes an MFMA every 16 clocks and
   // stands still while its wave issues anything else in front of one.
-  // WT_SGB == 3: the same phase with the order of its matrix instructions and LDS reads written down -- MFMA q, then read q of
-  // the next phase's fragments (sched_barrier(0x6): only VALU / SALU instructions may move across, so the column shifts and
-  // the address arithmetic settle into the gaps the compiler finds for them).  The first reads are the ones the next phase's
-  // first MFMAs need (lo halves, then dY).
-  auto xread1 = [&](XF& f, unsigned a, int k) {
-    if (WT_ABL & 16) return;
-    const unsigned b = (a + 512u) ^ 32u;
-    if (k == 0) { const uint2 t = tr(a + XPL); f.l.x = t.x; f.l.y = t.y; }
-    if (k == 1) { const uint2 t = tr(a + XPL + 256u); f.l.z = t.x; f.l.w = t.y; }
-    if (k == 2) { const uint2 t = tr(a); f.h.x = t.x; f.h.y = t.y; }
-    if (k == 3) { const uint2 t = tr(a + 256u); f.h.z = t.x; f.h.w = t.y; }
-    if (k == 4) { const uint2 t = tr(b + XPL); f.el = t.x; f.xl = t.y; }
-    if (k == 5) { const uint2 t = tr(b); f.eh = t.x; f.xh = t.y; }
-  };
-  auto yread1 = [&](uint4 (&bh)[NTW], uint4 (&bl)[NTW], unsigned a0, int k) {
-    if (WT_ABL & 16) return;
-    const unsigned a = (k & 4) ? (a0 ^ 32u) : a0;
-    const int nt = (k >> 2) < NTW ? (k >> 2) : NTW - 1;
-    if ((k & 3) == 0) { const uint2 t = tr(a); bh[nt].x = t.x; bh[nt].y = t.y; }
-    if ((k & 3) == 1) { const uint2 t = tr(a + 512u); bh[nt].z = t.x; bh[nt].w = t.y; }
-    if ((k & 3) == 2) { const uint2 t = tr(a + YPL); bl[nt].x = t.x; bl[nt].y = t.y; }
-    if ((k & 3) == 3) { const uint2 t = tr(a + YPL + 512u); bl[nt].z = t.x; bl[nt].w = t.y; }
-  };
-  // MFMA q of a row's 18 (pass-major: lo x hi, hi x lo, hi x hi; tap column, then output tile)
-  auto mm1 = [&](const uint4 (&ah)[3], const uint4 (&al)[3], const uint4 (&bh)[NTW], const uint4 (&bl)[NTW], f32x4 (&a)[3][NTW],
-                 int q) {
-    const int pass = q / 6, v = (q % 6) / NTW, nt = q % NTW;
-    a[v][nt] = wb_mfma(pass == 1 ? bl[nt] : bh[nt], pass == 0 ? al[v] : ah[v], a[v][nt]);
-  };
-  auto shifts = [&](const XF& f, uint4 (&ah)[3], uint4 (&al)[3]) {
-    ah[0] = f.h;
-    al[0] = f.l;
-    ah[1] = make_uint4(__builtin_amdgcn_alignbit(f.h.y, f.h.x, 16), __builtin_amdgcn_alignbit(f.h.z, f.h.y, 16),
-                       __builtin_amdgcn_alignbit(f.h.w, f.h.z, 16), __builtin_amdgcn_alignbit(f.eh, f.h.w, 16));
-    al[1] = make_uint4(__builtin_amdgcn_alignbit(f.l.y, f.l.x, 16), __builtin_amdgcn_alignbit(f.l.z, f.l.y, 16),
-                       __builtin_amdgcn_alignbit(f.l.w, f.l.z, 16), __builtin_amdgcn_alignbit(f.el, f.l.w, 16));
-    ah[2] = make_uint4(f.h.y, f.h.z, f.h.w, f.eh);
-    al[2] = make_uint4(f.l.y, f.l.z, f.l.w, f.el);
-    if (WT_ABL & 64) {
-      ah[1] = ah[2] = ah[0];
-      al[1] = al[2] = al[0];
-    }
-  };
-  // (tools/wgrad_variant.sh ablations, workers alone on the VDSR layer: all 92.6 us, no column shifts 87.6, no fragment reads
-  //  65.4 -- a transpose read issued in front of the MFMAs costs the matrix pipe ~16 clocks: with WT_SGB = 2 the NR reads of a
-  //  region are threaded one per MFMA gap as well, oldest first.)
-  auto mm_region = [&](int nreads) {
-    if (WT_SGB == 2) {
+  // (Ablations of the workers alone on the VDSR layer, DESIGN 12.3: all 92.6 us, no column shifts 87.6, no fragment reads
+  //  65.4 -- a transpose read issued in front of the MFMAs costs the matrix pipe ~16 clocks.)
+  auto mm_region = [&]() {
 #pragma unroll
-      for (int q = 0; q < 9 * NTW; ++q) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        if (q < nreads) {
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
-        } else {
-          __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
-        }
-      }
-    } else if (WT_SGB) {
-#pragma unroll
-      for (int q = 0; q < 9 * NTW; ++q) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
-      }
+    for (int q = 0; q < 9 * NTW; ++q) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
     }
     __builtin_amdgcn_sched_barrier(0);
   };
@@ -1464,79 +1184,29 @@ __global__ __launch_bounds__(768, 3) void k_wgrad_tr(WgBfParams P, typename WgGr
   auto step = [&](const XF& x0, const uint4 (&yh)[NTW], const uint4 (&yl)[NTW], XF& xn, uint4 (&nh)[NTW], uint4 (&nl)[NTW],
                   const TB& tc, const TB& tn) {
     XF x1 = {}, x2 = {};
-    if (WT_SGB == 3) {
-      uint4 ah[3], al[3];
-      {
-        const unsigned a = nxa;
-        shifts(x0, ah, al);
-#pragma unroll
-        for (int q = 0; q < 18; ++q) {
-          mm1(ah, al, yh, yl, acc[0], q);
-          if (q < 6) xread1(x1, a, q);
-          __builtin_amdgcn_sched_barrier(0x6);
-        }
-        asm volatile("" ::"v"(x0.xh), "v"(x0.xl));
-        nxa = xaddr(tc, 2);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      {
-        const unsigned a = nxa;
-        shifts(x1, ah, al);
-#pragma unroll
-        for (int q = 0; q < 18; ++q) {
-          mm1(ah, al, yh, yl, acc[1], q);
-          if (q < 6) xread1(x2, a, q);
-          __builtin_amdgcn_sched_barrier(0x6);
-        }
-        asm volatile("" ::"v"(x1.xh), "v"(x1.xl));
-        nxa = xaddr(tn, 0);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      {
-        const unsigned a = nxa, ya = yaddr(tn);
-        shifts(x2, ah, al);
-#pragma unroll
-        for (int q = 0; q < 18; ++q) {
-          mm1(ah, al, yh, yl, acc[2], q);
-          if (q < 2) xread1(xn, a, q);            // lo halves of the next step's first row,
-          else if (q < 10) yread1(nh, nl, ya, q - 2);   // its dY fragments,
-          else if (q < 14) xread1(xn, a, q - 8);  // the rest of the row
-          __builtin_amdgcn_sched_barrier(0x6);
-        }
-        asm volatile("" ::"v"(x2.xh), "v"(x2.xl));
-        nxa = xaddr(tn, 1);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      return;
-    }
     xissue(x1, nxa);
-    if (WT_SGB != 2) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
     rowmm(x0, yh, yl, acc[0]);
     nxa = xaddr(tc, 2);
-    mm_region(6);
+    mm_region();
     xissue(x2, nxa);
-    if (WT_SGB != 2) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
     rowmm(x1, yh, yl, acc[1]);
     nxa = xaddr(tn, 0);
     const unsigned nya = yaddr(tn);
-    mm_region(6);
+    mm_region();
     xissue(xn, nxa);
     yissue(nh, nl, nya);
-    if (WT_SGB != 2) __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_sched_barrier(0);
     rowmm(x2, yh, yl, acc[2]);
     nxa = xaddr(tn, 1);
-    mm_region(14);
+    mm_region();
   };
-  if (WB_PRIO) __builtin_amdgcn_s_setprio(WB_PRIO);
   __syncthreads();   // tile 0 staged
-  const long long clk_first = WB_CLK();   // tile 0 staged: everything before is launch + first-tile latency
-  long long clk_loops = clk_first;
   if (nks_run > 0) {
     const TB tb0 = tab(0), tb1 = tab(1);   // the first two K steps' table words do not depend on the tile
     int wprev = P.HH;
-    long long wk_loop = 0, wk_wait = 0, wk_pro = 0;
     for (int it = 0; it < ntb; ++it) {
-      const long long k0 = WB_CLK();
       wprev = ring_next(wprev, it == 0 || ((first_tile + it) % P.tiles_y) == 0);
       rb = wprev;
       ysel = YSET0 + (unsigned)(it & 1) * YSET;
@@ -1546,7 +1216,6 @@ __global__ __launch_bounds__(768, 3) void k_wgrad_tr(WgBfParams P, typename WgGr
       xissue(xa, xaddr(t0, 0));
       yissue(yah, yal, yaddr(t0));
       nxa = xaddr(t0, 1);
-      const long long k1 = WB_CLK();
       int ks = 0;
       for (; ks + 1 < nks_run; ks += 2) {
         const TB t2 = tab(ks + 2);
@@ -1557,21 +1226,8 @@ __global__ __launch_bounds__(768, 3) void k_wgrad_tr(WgBfParams P, typename WgGr
         t1 = t3;
       }
       if (ks < nks_run) step(xa, yah, yal, xb, ybh, ybl, t0, t1);
-      const long long k2 = WB_CLK();
       __syncthreads();
-      wk_pro += k1 - k0;
-      wk_loop += k2 - k0;
-      wk_wait += WB_CLK() - k2;
     }
-    clk_loops = WB_CLK();
-#ifdef SRK_EXPERIMENTS
-    if (P.prof && tid0 == 0) {
-      long long* pr = P.prof + ((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 16 + 8;
-      pr[0] = wk_loop; pr[1] = wk_wait; pr[2] = ntb; pr[3] = (long long)ntb * P.nks; pr[4] = wk_pro;
-      pr[5] = clk_first - clk_begin;   // launch of the block .. its first tile is staged
-    }
-#endif
-    (void)wk_loop; (void)wk_wait; (void)wk_pro;
   } else {
     for (int it = 0; it < ntb; ++it) __syncthreads();
   }
@@ -1587,15 +1243,6 @@ __global__ __launch_bounds__(768, 3) void k_wgrad_tr(WgBfParams P, typename WgGr
       for (int nt = 0; nt < NTW; ++nt)
         *reinterpret_cast<f32x4*>(slab + (size_t)t * P.Cin * P.Cout + nt * 16) = acc[u][v][nt];
     }
-#ifdef SRK_EXPERIMENTS
-  if (P.prof && tid0 == 0) {
-    __builtin_amdgcn_s_waitcnt(0);   // (vmcnt(0): the slab stores have left)
-    long long* pr = P.prof + ((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 16 + 8;
-    pr[6] = WB_CLK() - clk_loops;   // last tile done .. slab stored
-    pr[7] = WB_CLK() - clk_begin;   // the block's life
-  }
-#endif
-  (void)clk_begin; (void)clk_loops;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1866,17 +1513,10 @@ static WbPlan wb_plan(const srk_conv_desc& d) {
   // pixels per padded K step (e.g. 41-wide VDSR patches: 2 x 48 -> 83 % instead of 4 x 32 -> 60 %); ties -> taller
   // tiles (less halo per pixel).
   double best_eff = -1.0;
-  const char* tile_env = SRK_EXP_STR("SRK_WG_TILE");  // experiment: "TH,TWo" forces the tile shape
-  int force_th = 0, force_two = 0;
-  if (tile_env) sscanf(tile_env, "%d,%d", &force_th, &force_two);
   for (int TWo = 1; TWo <= 6 && (TWo - 1) * 8 < d.OW; ++TWo) {
     const int TW = TWo * 8;
     int TH = 16 / TWo;  // <= 128 pixels per tile
     if (TH > d.OH) TH = d.OH;
-    if (force_two) {
-      if (TWo != force_two) continue;
-      TH = force_th < d.OH ? force_th : d.OH;
-    }
     for (; TH >= 1; --TH) {
       const int HH = TH + d.KH - 1, HWp = TW + 8;
       const int CS = round_8odd(HH * HWp), DS = round_8odd(TH * TW + 8);
@@ -1904,9 +1544,7 @@ static WbPlan wb_plan(const srk_conv_desc& d) {
   pl.ntiles = (int)nt;
   pl.gy = cdiv(d.Cin, pl.CIB);
   pl.gz = cdiv(d.Cout, pl.COB);
-  int blocks_per_cu = SRK_EXP_INT("SRK_WG_BLOCKS", 2);  // experiment: resident blocks per CU (slab count vs overlap)
-  if (blocks_per_cu < 1) blocks_per_cu = 1;
-  int g = (blocks_per_cu * kNumCU) / (pl.gy * pl.gz);
+  int g = (2 * kNumCU) / (pl.gy * pl.gz);  // two resident blocks per CU
   if (g < 1) g = 1;
   pl.G = pl.ntiles < g ? pl.ntiles : g;
   pl.ok = true;
@@ -2222,24 +1860,9 @@ int conv_wgrad_bf(const srk_conv_desc& d, const float* x, const float* dy, const
       lds_half = (ring_bytes + 1) / 2;
     }
   }
-  {
-    const int dbg = SRK_EXP_INT("SRK_DBG", 0);
-    P.dbg = dbg;
-#ifdef SRK_EXPERIMENTS
-    P.prof = g_wb_prof;
-#endif
-    if (dbg & 32)
-      fprintf(stderr, "[srk] k_wgrad_bf cfg %d%s%s: tile %d x %d (%d K steps), %d tiles over %d x %d x %d blocks, lds %zu B\n",
-              pl.cfg, spec ? " (wave-specialised)" : "", P.ring ? " (X ring)" : "", pl.TH, pl.TW, pl.nks, pl.ntiles, G, pl.gy,
-              pl.gz, spec ? 2 * lds_half : pl.lds);
-  }
   size_t tr_lds = 0;
   switch (pl.cfg) {
     case 0:
-#ifdef SRK_EXPERIMENTS
-      // experiment (SRK_WG_W8=1): eight working waves (2 ci tiles x 4 single-tile co columns) -- measured SLOWER: see k_wgrad_bf
-      if (spec && wb_k33(P) && SRK_EXP_INT("SRK_WG_W8", 0)) { wb_launch<2, 4, 1>(P, grid, lds_half, spec, s); break; }
-#endif
       if (wt_setup(P, d, pl, spec, tr_lds)) { wt_launch<false>(P, WgNoGroup{0}, grid, tr_lds, s); break; }
       wb_launch<2, 2, 2>(P, grid, lds_half, spec, s);
       break;
@@ -2260,7 +1883,6 @@ int conv_wgrad_bf(const srk_conv_desc& d, const float* x, const float* dy, const
 // wave-specialised variant), writes one slab, and 33 layers cost two launches instead of 66.
 // ---------------------------------------------------------------------------------------------
 static int wb_group_G(const WbPlan& pl, int n, bool& spec) {
-  const int g_env = SRK_EXP_INT("SRK_WG_GROUP_G", 0);  // experiment: slabs per layer
   const int per = n * pl.gy * pl.gz;  // (layer, channel-chunk) pairs
   // one block per CU (wave-specialised, two LDS buffer sets) when every block gets >= 2 tiles; else two per CU
   int g1 = kNumCU / per;
@@ -2268,7 +1890,6 @@ static int wb_group_G(const WbPlan& pl, int n, bool& spec) {
   spec = 2 * pl.lds + 8 * 1024 <= 160 * 1024 && pl.ntiles >= 2 * g1;
   int G = spec ? g1 : (2 * kNumCU) / per;
   if (G < 1) G = 1;
-  if (g_env > 0) G = g_env;
   if (G > pl.ntiles) G = pl.ntiles;
   if (spec && pl.ntiles < 2 * G) spec = false;
   return G;
@@ -2335,16 +1956,6 @@ int conv_wgrad_bf_grouped(const srk_conv_desc& d, int n, const float* const* xs,
   P.vec_x = vec_x; P.vec_y = vec_y;
   P.dy_ps_r = 0; P.dy_ps_C = d.Cout;
   P.prefetch = wb_prefetch_ok(pl, d) && P.vec_x && P.vec_y;  // 16-byte channel groups only
-  {
-    const int dbg = SRK_EXP_INT("SRK_DBG", 0);
-    P.dbg = dbg;
-#ifdef SRK_EXPERIMENTS
-    P.prof = g_wb_prof;
-#endif
-    if (dbg & 32)
-      fprintf(stderr, "[srk] k_wgrad_bf grouped cfg %d%s: %d layers x %d slabs, tile %d x %d, %d tiles per layer, grid %d x %d x %d\n",
-              pl.cfg, spec ? " (wave-specialised)" : "", n, G, pl.TH, pl.TW, pl.ntiles, n * G, pl.gy, pl.gz);
-  }
   dim3 grid(n * G, pl.gy, pl.gz);
   size_t lds_half = pl.lds;
   {
@@ -2359,9 +1970,6 @@ int conv_wgrad_bf_grouped(const srk_conv_desc& d, int n, const float* const* xs,
   size_t tr_lds = 0;
   switch (pl.cfg) {
     case 0:
-#ifdef SRK_EXPERIMENTS
-      if (spec && wb_k33(P) && SRK_EXP_INT("SRK_WG_W8", 0)) { wb_launch_grouped<2, 4, 1>(P, GR, grid, lds_half, spec, s); break; }
-#endif
       if (wt_setup(P, d, pl, spec, tr_lds)) { wt_launch<true>(P, GR, grid, tr_lds, s); break; }
       wb_launch_grouped<2, 2, 2>(P, GR, grid, lds_half, spec, s);
       break;
@@ -2387,9 +1995,4 @@ int conv_wgrad_bf_grouped(const srk_conv_desc& d, int n, const float* const* xs,
 }
 
 }  // namespace srk
-
-#ifdef SRK_EXPERIMENTS
-// experiments build only: device buffer of 16 int64 per block for the role-time sums of the next k_wgrad_bf launches
-extern "C" void srk_debug_wgrad_prof(void* p) { srk::g_wb_prof = static_cast<long long*>(p); }
-#endif
 

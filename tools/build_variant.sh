@@ -1,7 +1,8 @@
 #!/bin/bash
 # Build a second library from a patched copy of csrc/ for same-box A/B runs:
-#   tools/build_variant.sh <out.so> <patch-script> [extra hipcc flags, e.g. -DSRK_EXPERIMENTS]
-# the patch script is run inside the copy of csrc/ before compiling
+#   tools/build_variant.sh <out.so> <patch-script> [extra hipcc flags]
+# the patch script is run inside the copy of csrc/ before compiling (an ablation or a timing probe is such a patch:
+# DESIGN.md 8); SRK_LIB_PATH=<out.so> and tools/ab*.sh then run it against the release library
 set -e
 ROOT=$(cd $(dirname $0)/.. && pwd)
 OUT=$1; PATCH=$2; shift 2

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """us per layer of c2 (ESPCN x4, 64 x 256x256, default precision), calls queued back to back.
-   python tools/time_c2_layers.py [layer ...]      (SRK_DBG / SRK_ROWSW_DBG / SRK_ROWS_DBG ablations apply)"""
+   python tools/time_c2_layers.py [layer ...]      (SRK_LIB_PATH: a patched library, tools/build_variant.sh)"""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -27,4 +27,4 @@ with torch.no_grad():
             for _ in range(20): l(hs[i])
             e1.record(); torch.cuda.synchronize()
             best = min(best, e0.elapsed_time(e1) / 20)
-        print("layer %d  %8.1f us  %s  SRK_DBG=%s" % (i, best * 1e3, lib.srk_last_kernel_name().decode(), os.environ.get("SRK_DBG", "")))
+        print("layer %d  %8.1f us  %s" % (i, best * 1e3, lib.srk_last_kernel_name().decode()))

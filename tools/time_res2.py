@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time the fused residual-block launches (srk_resblock2_forward / _backward_data) alone: 20 launches in a hipGraph.
-   python tools/time_res2.py [B] [H]     (SRK_DBG: 1 skip the halo staging, 4 skip the matrix work)"""
+   python tools/time_res2.py [B] [H]     (SRK_LIB_PATH: a patched library, tools/build_variant.sh)"""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -55,5 +55,4 @@ for name, fn in (("forward bf16x6", fwd), ("forward f16x3", fwd16), ("backward b
     e1.record(); torch.cuda.synchronize()
     us = e0.elapsed_time(e1) * 10
     flop = 2.0 * B * H * H * 64 * 64 * 9 * 2
-    print("res2 %-16s B=%d %dx%d  %.2f us  %.1f TF (useful)  [SRK_DBG=%s]" % (name, B, H, H, us, flop / us / 1e6,
-                                                                              os.environ.get("SRK_DBG", "0")))
+    print("res2 %-16s B=%d %dx%d  %.2f us  %.1f TF (useful)" % (name, B, H, H, us, flop / us / 1e6))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time single fused-conv launches for the workhorse shapes (HIP events, 20 reps) under the current env
-(SRK_DBG / SRK_BF3_WAVES / SRK_FORCE_ALGO) and print a checksum so variants can be compared for equality.
+(SRK_FORCE_ALGO, SRK_LIB_PATH) and print a checksum so variants can be compared for equality.
 Usage: time_shapes.py [shape ...]"""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,7 +22,7 @@ SHAPES = {  # N, Cin, H, W, Cout, k, pad, act, ps
 }
 names = sys.argv[1:] or ["espcn2", "espcn3", "vdsr", "edsr128", "edsr16", "edsrup16"]
 dev = torch.device("cuda:0")
-tag = " ".join("%s=%s" % (k, os.environ[k]) for k in ("SRK_DBG", "SRK_BF3_WAVES", "SRK_FORCE_ALGO") if k in os.environ)
+tag = " ".join("%s=%s" % (k, os.environ[k]) for k in ("SRK_FORCE_ALGO",) if k in os.environ)
 for name in names:
     N, cin, H, W, cout, k, pad, act, ps = SHAPES[name]
     g = torch.Generator(device="cpu").manual_seed(7)
