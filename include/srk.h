@@ -511,6 +511,31 @@ int srk_patch_from_image_u8(const uint8_t* img_hwc, int C, int H, int W, int sca
                             int crop_w, int crop_h, int rot_k, int fliplr, int fliptb, uint8_t* out_planar,
                             void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the colour tail of test_single / test (edsr.py:276-322, utils.py:116-131), bit-exact with Pillow ----------
+ * Image.convert('YCbCr') / convert('RGB') are integer table look-ups in Pillow (ConvertYCbCr.c, SCALE = 6); the closed
+ * form of the tables is in csrc/color.hip.  The tables are constants of the library, built once by its compiler in IEEE
+ * double; the host helpers and the kernels read the same object.
+ *
+ * srk_rgb_to_ycc_u8: interleaved 8-bit RGB [H][W][3] (row_stride in bytes, >= 3 W) -> any of (NULL = not wanted, at least
+ *   one): y_f32 [H][W] = Y / 255.0f (ToTensor of the Y plane), y_u8 [H][W], cbcr [2][H][W] 8-bit planar (what
+ *   srk_img_resize_u8 reads with plane_stride = H * W).  One pass over the image.
+ * srk_ycc_to_rgb_u8: Image.merge('YCbCr', ...).convert('RGB') -> interleaved 8-bit RGB [H][W][3].  Y is EITHER y_f32 (the
+ *   net's output, addressed through element strides (row, pixel); quantised like srk_float_to_u8_image on the way, the
+ *   8-bit Y never goes to memory) OR y_u8 (dense [H][W]); exactly one of the two is non-NULL.  cb / cr: dense [H][W].
+ * srk_float_to_u8_image: ToPILImage after clamp(0, 1) (edsr.py:305-306): (uint8)(min(max(x, 0), 1) * 255.0f), fp32
+ *   product, truncation, NaN -> 0.  x: fp32 [C][H][W] through element strides (channel, row, pixel) -- a channels-last
+ *   net output is read in place --, C = 1 or 3; out: interleaved [H][W][C]. */
+int srk_rgb_to_ycc_u8(const uint8_t* rgb, int64_t row_stride, int H, int W, float* y_f32, uint8_t* y_u8, uint8_t* cbcr,
+                      void* stream);
+int srk_ycc_to_rgb_u8(const float* y_f32, int64_t y_row_stride, int64_t y_px_stride, const uint8_t* y_u8, const uint8_t* cb,
+                      const uint8_t* cr, uint8_t* rgb, int H, int W, void* stream);
+int srk_float_to_u8_image(const float* x, int64_t c_stride, int64_t row_stride, int64_t px_stride, uint8_t* out, int C,
+                          int H, int W, void* stream);
+/* The same two conversions on the HOST (pure functions, no device involved; n interleaved pixels, 3 bytes each): they
+ * read the very tables the kernels get, so the arithmetic can be pinned against Pillow without a GPU. */
+int srk_rgb_to_ycc_host(const uint8_t* rgb, size_t n, uint8_t* ycc);
+int srk_ycc_to_rgb_host(const uint8_t* ycc, size_t n, uint8_t* rgb);
+
 /* ---- steps either side of the nets ------------------------------------------------
  * utils.PSNR (utils.py:208-216): mse = mean((clamp(pred,0,1) - gt)^2) over all elements, *psnr_out = mse == 0 ? 100 :
  * 10*log10(1/mse), on the device (the reference copies both images to the host per test image).  pred / gt are

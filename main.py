@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Entry point with the reference's command line (main.py:13-36: the same 15 flags and defaults)
 dispatching to the MI355X trainers.  Extra flags: --synthetic (seeded random patches instead of the image
-folders under --data_dir; --steps_per_epoch of them per epoch), --epoch_pretrain and --precision {mixed,bf16x3,fp32}.
+folders under --data_dir; --steps_per_epoch of them per epoch), --epoch_pretrain, --precision {mixed,bf16x3,fp32},
+--test_single PATH (load the checkpoint, super-resolve that picture file into <save_dir>/test_result/SR_result.png, print
+the file name; no training) and --save_test_images (test() also writes every result image and reports the bicubic PSNR).
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N main.py ..."""
 import argparse
 import os
@@ -45,6 +47,11 @@ def parse_args(argv=None):
     p.add_argument('--prune_dead_grads', action='store_true',
                    help='SRGAN: skip the two gradient computations of the reference iteration that nothing reads '
                         '(G gradients of the D step, D parameter gradients of the G step); same parameters after every step')
+    p.add_argument('--test_single', type=str, default=None, metavar='PATH',
+                   help='no training: load the checkpoint, super-resolve this picture file (the Y channel with '
+                        '--num_channels 1, colour restored from the bicubic Cb / Cr) and print the name of the PNG written')
+    p.add_argument('--save_test_images', action='store_true',
+                   help='test(): write every result image to <save_dir>/test_result/<dataset>/ and report the bicubic PSNR')
     return check_args(p.parse_args(argv))
 
 
@@ -68,8 +75,16 @@ def main(argv=None):
     from pytorch_super_resolution_model_collection_amd.sr_trainers import TRAINERS
     pkg.ops.set_precision(args.precision)
     net = TRAINERS[args.model_name](args)   # main.py:70-89
+    if args.test_single:                     # main.py:102: net.test_single(img_fn)
+        print(net.test_single(args.test_single))
+        return net
     net.train()                              # main.py:96
-    net.test()                               # main.py:99
+    if args.save_test_images:
+        net.test(save_images=True)
+        for name, v in net.test_bicubic_psnr.items():
+            print('%s: bicubic PSNR %.4f, %s PSNR %.4f' % (name, v, args.model_name, net.test_psnr.get(name, float('nan'))))
+    else:
+        net.test()                           # main.py:99
     return net
 
 

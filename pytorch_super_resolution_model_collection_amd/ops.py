@@ -1701,6 +1701,111 @@ def img_interp(imgs, scale_factor, interpolation="bicubic"):
 
 
 # ------------------------------------------------------------------------------------------------
+# The colour tail of test_single / test (edsr.py:276-322): 8-bit images on the device, bit-exact with Pillow
+# ------------------------------------------------------------------------------------------------
+def _require_u8(what, *tensors):
+    for t in tensors:
+        if not t.is_cuda:
+            raise RuntimeError("%s runs on GPU tensors (got a %s tensor); there is no CPU fallback" % (what, t.device))
+        if t.device.index is not None and t.device.index != torch.cuda.current_device():
+            raise RuntimeError("%s: tensor on %s but the current device is cuda:%d" % (what, t.device, torch.cuda.current_device()))
+        if t.dtype != torch.uint8:
+            raise RuntimeError("%s expects uint8 tensors (got %s)" % (what, t.dtype))
+
+
+def rgb_to_ycc_planes(img_u8_hwc, y_float=False):
+    """One pass of k_rgb_to_ycc over an interleaved 8-bit RGB image [H,W,3] (a row-strided view is read in place; pixels
+    must be dense): returns (y, cbcr) with cbcr uint8 [2,H,W] planar -- what resize_u8 takes -- and y uint8 [H,W] or,
+    with y_float, the fp32 plane Y / 255 that ToTensor() makes of the Y image."""
+    _require_u8("rgb_to_ycbcr_u8", img_u8_hwc)
+    x = img_u8_hwc
+    if x.dim() != 3 or x.shape[2] != 3:
+        raise RuntimeError("rgb_to_ycbcr_u8 expects an interleaved [H,W,3] image, got shape %s" % (tuple(x.shape),))
+    h, w = int(x.shape[0]), int(x.shape[1])
+    if h == 0 or w == 0:
+        raise RuntimeError("rgb_to_ycbcr_u8: empty image %s" % (tuple(x.shape),))
+    if x.stride(2) != 1 or x.stride(1) != 3 or (h > 1 and x.stride(0) < 3 * w):
+        x = x.contiguous()
+    row_stride = int(x.stride(0)) if h > 1 else 3 * w
+    y = torch.empty((h, w), dtype=torch.float32 if y_float else torch.uint8, device=x.device)
+    cbcr = torch.empty((2, h, w), dtype=torch.uint8, device=x.device)
+    check(_lib.load().srk_rgb_to_ycc_u8(ptr(x), row_stride, h, w, ptr(y) if y_float else None, None if y_float else ptr(y),
+                                        ptr(cbcr), stream_ptr()), "srk_rgb_to_ycc_u8")
+    return y, cbcr
+
+
+def rgb_to_ycbcr_u8(img_u8_hwc, y_float=False):
+    """Image.convert('YCbCr').split() of an interleaved 8-bit RGB image [H,W,3] on the device, bit-exact with Pillow:
+    (y, cb, cr), uint8 [H,W] each; with y_float, y is the fp32 plane Y / 255 instead (see rgb_to_ycc_planes)."""
+    y, cbcr = rgb_to_ycc_planes(img_u8_hwc, y_float)
+    return y, cbcr[0], cbcr[1]
+
+
+def ycbcr_to_rgb_u8(y, cb, cr):
+    """Image.merge('YCbCr', [y, cb, cr]).convert('RGB') on the device (k_ycc_to_rgb), bit-exact with Pillow: interleaved
+    uint8 [H,W,3].  cb / cr: uint8 [H,W].  y: uint8 [H,W], or the fp32 output of a Y-channel net ([H,W], [1,H,W] or
+    [1,1,H,W], any strides), which is quantised like ToPILImage after clamp(0, 1) inside the kernel."""
+    _require_u8("ycbcr_to_rgb_u8", cb, cr)
+    h, w = int(cb.shape[-2]), int(cb.shape[-1])
+    if cb.dim() != 2 or tuple(cr.shape) != (h, w):
+        raise RuntimeError("ycbcr_to_rgb_u8: cb %s / cr %s must be two [H,W] planes of one size" % (tuple(cb.shape), tuple(cr.shape)))
+    if y.numel() != h * w or tuple(y.shape[-2:]) != (h, w):
+        raise RuntimeError("ycbcr_to_rgb_u8: y %s does not match the chroma planes %s" % (tuple(y.shape), (h, w)))
+    cb, cr = cb.contiguous(), cr.contiguous()
+    out = torch.empty((h, w, 3), dtype=torch.uint8, device=cb.device)
+    lib = _lib.load()
+    if y.dtype == torch.uint8:
+        _require_u8("ycbcr_to_rgb_u8", y)
+        y = y.reshape(h, w).contiguous()
+        rc = lib.srk_ycc_to_rgb_u8(None, 0, 0, ptr(y), ptr(cb), ptr(cr), ptr(out), h, w, stream_ptr())
+    else:
+        require_cuda(y)
+        y = y.detach()
+        rc = lib.srk_ycc_to_rgb_u8(ptr(y), int(y.stride(-2)), int(y.stride(-1)), None, ptr(cb), ptr(cr), ptr(out), h, w,
+                                   stream_ptr())
+    check(rc, "srk_ycc_to_rgb_u8")
+    return out
+
+
+def to_u8_image(x):
+    """ToPILImage()(x.clamp(0, 1)) as an array (edsr.py:305-306), on the device (k_to_u8): fp32 [C,H,W] or [1,C,H,W]
+    of any strides (a channels-last net output is read in place), C = 1 or 3 -> interleaved uint8 [H,W,C], each byte
+    (uint8)(clamp(x, 0, 1) * 255) with the fp32 product truncated; NaN gives 0."""
+    require_cuda(x)
+    x = x.detach()
+    if x.dim() == 4 and x.shape[0] == 1:
+        x = x[0]
+    if x.dim() != 3 or x.shape[0] not in (1, 3):
+        raise RuntimeError("to_u8_image expects a [C,H,W] or [1,C,H,W] tensor with C = 1 or 3, got shape %s" % (tuple(x.shape),))
+    c, h, w = (int(v) for v in x.shape)
+    out = torch.empty((h, w, c), dtype=torch.uint8, device=x.device)
+    check(_lib.load().srk_float_to_u8_image(ptr(x), int(x.stride(0)), int(x.stride(1)), int(x.stride(2)), ptr(out), c, h, w,
+                                            stream_ptr()), "srk_float_to_u8_image")
+    return out
+
+
+def resize_u8(planes_u8, oh, ow, interpolation="bicubic", out_float=False):
+    """Image.resize((ow, oh)) of 8-bit planes [P,H,W] (any strides: an interleaved [H,W,C] image is read in place through
+    .permute(2, 0, 1)) on the device: srk_img_resize_u8, bit-exact with Pillow.  Returns uint8 [P,oh,ow], or with
+    out_float the fp32 planes value / 255 (ToTensor); an unchanged size makes that the plain ToTensor of the image."""
+    _require_u8("resize_u8", planes_u8)
+    if planes_u8.dim() != 3:
+        raise RuntimeError("resize_u8 expects [P,H,W] planes, got shape %s" % (tuple(planes_u8.shape),))
+    if interpolation not in ("bicubic", "bilinear"):
+        raise ValueError("resize_u8: interpolation must be 'bicubic' or 'bilinear'")
+    p, h, w = (int(v) for v in planes_u8.shape)
+    lib = _lib.load()
+    flt = _INTERP[interpolation]
+    y = torch.empty((p, oh, ow), dtype=torch.float32 if out_float else torch.uint8, device=planes_u8.device)
+    nbytes = max(int(lib.srk_img_resize_u8_workspace_bytes(p, h, w, oh, ow, flt)), 256)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=planes_u8.device)
+    st = [int(v) for v in planes_u8.stride()]
+    check(lib.srk_img_resize_u8(ptr(planes_u8), st[0], st[1], st[2], ptr(y), int(out_float), p, h, w, oh, ow, flt, ptr(ws), nbytes,
+                                stream_ptr()), "srk_img_resize_u8")
+    return y
+
+
+# ------------------------------------------------------------------------------------------------
 # DRCN (drcn.py:13-59): the weight-shared recursion and the recursive-supervision head
 # ------------------------------------------------------------------------------------------------
 # The inference net applies ONE conv + ReLU D times in a row and ONE two-conv reconstruction to each of the D hidden

@@ -6,8 +6,9 @@ lapsrn.py:88-349, srgan.py:93-528, drcn.py:62-355), on the MI355X hot path.
 Kept from the reference: per-model hyper-parameters hard-coded in train() (e.g. EDSR base_filter 64 /
 16 residuals, edsr.py:87; VDSR momentum 0.9 / wd 1e-4 / clip 0.4, vdsr.py:86-90,149), the epoch-wise
 LR decay rules, the checkpoint file names and that checkpoints are weights-only state_dict pickles.
-Not kept (out of scope): TF1 logging, PNG/plot side effects and the per-iteration host
-sync (`loss.data[0]`).  Training data comes from a `loader` argument (any iterable of tensor tuples in
+Not kept (out of scope): TF1 logging, plot side effects and the per-iteration host
+sync (`loss.data[0]`).  Result pictures are written by test_single(path) and test(save_images=True), with the
+colour tail on the device.  Training data comes from a `loader` argument (any iterable of tensor tuples in
 the reference's (lr, hr, bicubic) order), else from the reference's image folders under `data_dir`
 (data.PatchLoader: decode on host threads, transforms on the GPU) when they exist, else from seeded
 synthetic patches of the configured crop size.
@@ -232,10 +233,14 @@ class _Trainer(object):
         with torch.no_grad():
             return self.model(x.to(self.device))
 
-    def test(self, loader=None):
+    def test(self, loader=None, save_images=False):
         """Evaluation loop (espcn.py:173-215, edsr.py:196-250): forward + PSNR per image (computed on the device), over
         `loader`, else over every folder of `test_dataset` that exists under `data_dir` (data.get_test_set), else over
-        seeded synthetic pairs.  Returns the list of PSNRs; `self.test_psnr` holds the per-dataset averages."""
+        seeded synthetic pairs.  Returns the list of PSNRs; `self.test_psnr` holds the per-dataset averages.
+        save_images: as the reference's test() (edsr.py:215-274), every result also goes through utils.save_img into
+        <save_dir>/test_result/<dataset>/SR_result_<n>.png, and `self.test_bicubic_psnr` holds, per dataset, the
+        average PSNR of the loader's bicubic image (the third item, where the loader yields one) against the target
+        (edsr.py:257-261), computed by the same device kernel."""
         if self.model is None:
             self.model = self.build_model().to(self.device)
             self.load_model()
@@ -250,8 +255,11 @@ class _Trainer(object):
             if not sources:
                 sources.append(("synthetic", synthetic_loader(self.kind, self.args, 2, self.device, 4321)))
         psnrs, self.test_psnr = [], {}
+        if save_images:
+            self.test_bicubic_psnr = {}
         for name, batches in sources:
             mine = []
+            bicubic, img_num = [], 0
             for batch in batches:
                 items = [batch] if torch.is_tensor(batch[0]) else list(zip(*batch))   # ragged test images come as lists
                 for item in items:
@@ -263,20 +271,75 @@ class _Trainer(object):
                         tgt = utils.shave(tgt, 8)
                     if out.shape == tgt.shape:
                         mine.append(utils.PSNR(out, tgt))   # 0-dim device tensors: nothing syncs inside the loop
+                    if save_images:
+                        img_num += 1
+                        utils.save_img(out[0], img_num, save_dir=os.path.join(self.save_dir, 'test_result', str(name)))
+                        if len(item) > 2:
+                            bc_img = self._channels(item[2] if item[2].dim() == 4 else item[2].unsqueeze(0))[0]
+                            if bc_img.shape == hr_img.shape:
+                                bicubic.append(utils.PSNR(bc_img.to(self.device), hr_img.to(self.device)))
             vals = [float(v) for v in torch.stack(mine).cpu()] if mine else []
             if vals:
                 self.test_psnr[name] = sum(vals) / len(vals)
             psnrs += vals
+            if bicubic:
+                bvals = [float(v) for v in torch.stack(bicubic).cpu()]
+                self.test_bicubic_psnr[name] = sum(bvals) / len(bvals)
         return psnrs
 
     def test_single(self, img):
-        """Super-resolve one [C,H,W] (or [1,C,H,W]) tensor (the reference reads an image file with PIL)."""
+        """A tensor: super-resolve one [C,H,W] (or [1,C,H,W]) tensor and return the net's output on the host.
+        A path (str / os.PathLike): the reference's test_single(img_fn) (edsr.py:276-322) -- super-resolve the picture
+        file, write <save_dir>/test_result/SR_result.png and return that file name; see _test_single_file."""
+        if isinstance(img, (str, os.PathLike)):
+            return self._test_single_file(img)
         if self.model is None:
             self.model = self.build_model().to(self.device)
             self.load_model()
         x = img if img.dim() == 4 else img.unsqueeze(0)
         out = self._infer(self._net_input(x.to(self.device)))
         return (out[-1] if isinstance(out, tuple) else out).cpu()
+
+    def _test_single_file(self, img_fn):
+        """edsr.py:276-322 with the picture on the device from the decode to the 8-bit result:
+          num_channels == 1  upload the 8-bit RGB once -> k_rgb_to_ycc (fp32 Y / 255 and planar Cb / Cr in one pass) -> Y
+                             through _net_input and _infer exactly as the tensor form does (bicubic pre-upsampling for
+                             SRCNN / VDSR / DRCN, last element of a tuple output) -> Cb and Cr through the 8-bit bicubic
+                             resizer (one call, two planes) to the height and width the net actually returned (FSRCNN
+                             and ESPCN crop a border) -> k_ycc_to_rgb (quantises Y on the way) -> one device-to-host
+                             copy of the 8-bit image;
+          num_channels == 3  RGB / 255 in, k_to_u8 out.
+        Bit-exact with the reference's Pillow tail for the same net output.  Nothing between the upload and that copy
+        waits for the device.  Every trainer follows the EDSR convention for the net's output, clamp(0, 1): SRCNN's own
+        test_single stretches the output to its min..max instead (srcnn.py:244), which turns any picture grey-scaled to
+        full range; that is not reproduced."""
+        from PIL import Image
+        from . import data
+        if self.model is None:
+            self.model = self.build_model().to(self.device)
+            self.load_model()
+        rgb = torch.tensor(data.load_img(os.fspath(img_fn)), device=self.device)   # [H,W,3] uint8: the one upload
+        h, w = int(rgb.shape[0]), int(rgb.shape[1])
+        if self.num_channels == 1:
+            y, cbcr = ops.rgb_to_ycc_planes(rgb, y_float=True)
+            x = y.view(1, 1, h, w)
+        else:
+            x = ops.resize_u8(rgb.permute(2, 0, 1), h, w, out_float=True).unsqueeze(0)   # ToTensor: planar, / 255
+        out = self._infer(self._net_input(x))
+        out = out[-1] if isinstance(out, tuple) else out
+        if self.num_channels == 1:
+            oh, ow = int(out.shape[-2]), int(out.shape[-1])
+            cbcr = ops.resize_u8(cbcr, oh, ow)   # both chroma planes in one resizer call
+            img8 = ops.ycbcr_to_rgb_u8(out, cbcr[0], cbcr[1])
+        else:
+            img8 = ops.to_u8_image(out)
+        arr = img8.cpu().numpy()   # the one device-to-host copy
+        result_dir = os.path.join(self.save_dir, 'test_result')
+        os.makedirs(result_dir, exist_ok=True)
+        save_fn = result_dir + '/SR_result.png'
+        Image.fromarray(arr).save(save_fn)
+        print('Single test result image is saved.')
+        return save_fn
 
     def _ckpt_name(self, epoch):
         # srcnn.py:260-269 style for the simple trainers, edsr.py:324-337 style (ch/batch/epoch/lr) for EDSR / SRGAN

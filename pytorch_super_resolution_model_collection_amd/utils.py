@@ -1,7 +1,9 @@
 """Tensor-side helpers of the reference's utils.py that sit on the training loop: weight
-initialisers (utils.py:76-113), border crop (`shave`, :197-205), PSNR (:208-216) and the
-mean/std normalisation constants (:219-239).  Plotting / GIF / PNG helpers are out of scope
+initialisers (utils.py:76-113), border crop (`shave`, :197-205), PSNR (:208-216), the
+mean/std normalisation constants (:219-239), and save_img (:116-131).  Plotting / GIF helpers are out of scope
 (SURVEY.md §2 rows 11-12)."""
+import os
+
 import torch
 
 
@@ -46,6 +48,29 @@ def PSNR(pred, gt):
     if not pred.is_cuda:
         pred = pred.to("cuda")
     return ops.psnr(pred.float(), gt.to(pred.device).float())[0]
+
+
+def save_img_name(img_num, save_dir='', is_training=False):
+    """utils.py:126-130: the file a result image goes to."""
+    return save_dir + ('/SR_result_epoch_{:d}' if is_training else '/SR_result_{:d}').format(img_num) + '.png'
+
+
+def save_img(img, img_num, save_dir='', is_training=False):
+    """utils.py:116-131: write the [C,H,W] (or [1,C,H,W]) result image, C = 1 or 3, as an 8-bit PNG under the reference's
+    file name, and return that name.  The image is quantised on the device (ops.to_u8_image: clamp(0, 1) * 255,
+    truncated -- for three channels the bytes of the reference's `(img * 255).clamp(0, 255).astype(uint8)`), copied to
+    the host once and encoded by Pillow (the reference's scipy.misc.imsave no longer exists).  One-channel images are
+    quantised the same way; the reference hands imsave a float array there, which that function stretched to the
+    image's own min..max.  A CPU tensor is moved to the current device first, as in PSNR."""
+    from PIL import Image
+    from . import ops
+    if not img.is_cuda:
+        img = img.to("cuda")
+    arr = ops.to_u8_image(img.float()).cpu().numpy()
+    os.makedirs(save_dir or '.', exist_ok=True)
+    save_fn = save_img_name(img_num, save_dir, is_training)
+    Image.fromarray(arr[:, :, 0] if arr.shape[2] == 1 else arr).save(save_fn)
+    return save_fn
 
 
 VGG_MEAN = (0.485, 0.456, 0.406)
