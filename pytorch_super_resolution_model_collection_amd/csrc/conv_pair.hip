@@ -1,26 +1,33 @@
 // ESPCN's first two layers in one persistent launch: conv5x5 3 -> 64 + ReLU feeding conv3x3 64 -> 32 + ReLU (both
 // "valid", stride 1, f16x3 arithmetic), so the 64-channel map between them never reaches HBM.
 //
-// One 512-thread block per CU walks 8 x 16 output tiles of the second layer.  Its eight waves form two groups of four
-// (one wave per SIMD each) that take alternate tiles of the block's list.  Every wave computes both layers of its group's
-// tiles: the first layer of tile t+1 (its 10 x 18 halo, all 64 channels) into a ring of three 32-channel halo slots
-// while the other group's wave on the same SIMD runs the second layer of tile t out of the ring.  No wave is a pure
-// loader: the 3-channel input tile (14 x 23 px) is loaded, split and staged by the group itself.
+// One 512-thread block per CU walks a contiguous run of 8 x 16 output tiles of the second layer in column-major order
+// (image, tile column, tile row).  Its eight waves form two groups of four (one wave per SIMD each) that take alternate
+// tiles of the run.  Every wave computes both layers of its group's tiles: the first layer of tile t+1 into LDS while the
+// other group's wave on the same SIMD runs the second layer of tile t out of it.  No wave is a pure loader: the
+// 3-channel input tile (14 x 23 px) is loaded, split and staged by the group itself.
+//
+// The second layer of a tile needs a 10 x 18 halo of the intermediate.  Rows 0 .. 1 of it are rows 8 .. 9 of the tile
+// above: a tile whose upper neighbour is the run's previous tile computes only rows 2 .. 9 (144 pixels, nine 16-pixel
+// fragments) and takes rows 0 .. 1 from three rotating buffers of kept rows; the first tile of a run and the top tile of a
+// column compute their rows 0 .. 1 as three more fragments.  Every value of the intermediate is the same number whichever
+// tile computed it (same K order, same scale), so the output does not depend on where runs start.
 //
 // First layer: K packs the 5x5 taps as horizontal tap pairs x 4 channel slots -- 15 pairs of 8 K values, 120 of 128 K
-// used in four 16x16x32 steps -- so a pixel fragment is two 8-byte reads of the staged tile.  Each wave holds the fp16
-// planes of one 16-channel fragment of each 32-channel chunk in registers (64 VGPRs) and computes six of the twelve
-// 16-pixel fragments of the halo for both chunks.  The intermediate's fp16 scale is a BOUND, not a measured maximum:
-// max_c(|b_c| + sum |w_c| max|x|) >= max|relu(conv)|, so no rendezvous per tile; a power-of-two scale above the true
-// maximum gives the same planes unless the residual plane underflows, i.e. it only raises the absolute error floor
-// (ops.declare_absmax).
+// used in four 16x16x32 steps -- so a pixel fragment is two 8-byte reads of the staged tile.  A wave holds the fp16
+// planes of both 16-channel fragments of ONE 32-channel chunk in registers (64 VGPRs), so that a pixel fragment read
+// feeds six MFMAs, and computes four of the nine pixel fragments, every other tile five.  The intermediate's fp16 scale
+// is a BOUND, not a measured maximum: max_c(|b_c| + sum |w_c| max|x|) >= max|relu(conv)|, so no rendezvous per tile; a
+// power-of-two scale above the true maximum gives the same planes unless the residual plane underflows, i.e. it only
+// raises the absolute error floor (ops.declare_absmax).
 // Second layer: the ring kernel's tap loop (conv_bfr.hip) with the filter in LDS; a wave owns 4 rows x 16 columns x 16
 // channels of the tile.  Accumulation order per output: chunk, kernel column, kernel row.
 //
-// Ring: stage (list entry i, chunk c) = 2 i + c lives in slot (2 i + c) % 3; per slot full / free counters in LDS.  A wave
-// waits for free >= 4 k before writing use k of a slot and for full >= 4 (k + 1) before reading it, and signals free
-// right behind its last read of a slot, before it waits for anything else.  Every poll is capped: a slip is counted
-// (srk_ring_timeouts) and the waves run on with wrong numbers instead of faulting the device.
+// Ring: stage (run entry i, chunk c) = 2 i + c holds halo rows 2 .. 7 in slot (2 i + c) % 3; per slot full / free counters
+// in LDS.  A wave waits for free >= 4 k before writing use k of a slot and for full >= 2 (k + 1) (the two waves of the
+// chunk) before reading it, and signals free right behind its last read of a slot.  Halo rows 8 .. 9 go to a kept-row
+// buffer with counters of its own (see the tile loop).  Every poll is capped: a slip is counted (srk_ring_timeouts) and
+// the waves run on with wrong numbers instead of faulting the device.
 #include "srk_common.h"
 #include "conv_problem.h"
 #include "bf16_frag.h"
@@ -30,14 +37,20 @@ namespace srk {
 
 namespace {
 
-constexpr int PR_TH = 8, PR_TW = 16, PR_HW = 18, PR_NPIX = 180, PR_NPIXP = 190;  // (NPIXP: conv_bfr.hip's slot stride)
+constexpr int PR_TH = 8, PR_TW = 16, PR_HW = 18;
+constexpr int PR_NSLOTPIX = 6 * PR_HW, PR_NPIXP = PR_NSLOTPIX + 2;  // halo rows 2 .. 7 live in a ring slot: pixels, stride
+                                                                    // (pixel p of rows 2 .. 9 is halo pixel 36 + p)
+constexpr int PR_NKEEP = 2 * PR_HW, PR_KP = PR_NKEEP + 2;    // halo rows 8 .. 9 = the tile below's rows 0 .. 1: pixels, stride
 constexpr int PR_XR = 14, PR_XC = 23, PR_XP = 24;   // staged input tile: rows, columns, pixel pitch of a row
-constexpr int PR_NSLOT = 3;
+constexpr int PR_NSLOT = 3, PR_NKBUF = 3;
 constexpr int PR_WL2 = 9 * 2 * 256;                 // uint4 of the second layer's filter [tap][chunk][plane][group][32]
-constexpr int PR_HBUF = 8 * PR_NPIXP;               // uint4 per halo slot [plane][group][NPIXP]
+constexpr int PR_HBUF = 4 * PR_NPIXP;               // uint4 per plane of a halo slot [group][NPIXP]
+constexpr int PR_KBUF = 2 * 4 * PR_KP;              // uint4 per plane of a kept-row buffer [chunk][group][KP]
+constexpr int PR_PLANE = PR_NSLOT * PR_HBUF + PR_NKBUF * PR_KBUF;   // the residual planes of all of them lie this far on
 constexpr int PR_XBUF = 2 * PR_XR * PR_XP;          // uint2 per group's input tile [plane][row][pixel]
 constexpr unsigned PR_SPIN_CAP = 1u << 18;
-constexpr size_t PR_LDS = (size_t)PR_WL2 * 16 + (size_t)PR_NSLOT * PR_HBUF * 16 + (size_t)2 * PR_XBUF * 8 + 64;
+constexpr size_t PR_LDS = (size_t)PR_WL2 * 16 + (size_t)2 * PR_PLANE * 16 + (size_t)2 * PR_XBUF * 8 + 64;
+static_assert(PR_LDS <= 160 * 1024, "k_espcn_pair: LDS");
 
 __device__ unsigned g_pair_timeouts = 0;
 
@@ -54,7 +67,7 @@ struct PairParams {
   float* y;                // NHWC [N][H-6][W-6][32]
   const float* x_amax;
   float* y_amax;
-  int N, H, W, OH, OW, tiles_x, img_tiles, ntiles;
+  int N, H, W, OH, OW, tiles_y, img_tiles, ntiles;
   unsigned x_img_bytes, y_bytes;
 };
 
@@ -74,9 +87,9 @@ __device__ __forceinline__ void pr_wait(pr_cnt_t* p, unsigned target, bool& dead
   }
   asm volatile("" ::: "memory");
 }
-__device__ __forceinline__ void pr_signal(pr_cnt_t* p) {
+__device__ __forceinline__ void pr_signal(pr_cnt_t* p, unsigned n = 1u) {
   asm volatile("" ::: "memory");
-  if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(p, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   asm volatile("" ::: "memory");
 }
 
@@ -91,8 +104,9 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
   extern __shared__ __attribute__((aligned(16))) uint4 smem4[];
   uint4* wl2 = smem4;
   uint4* ring = smem4 + PR_WL2;
-  uint2* xin_all = reinterpret_cast<uint2*>(ring + PR_NSLOT * PR_HBUF);
-  pr_cnt_t* cnt = (pr_cnt_t*)(xin_all + 2 * PR_XBUF);  // full[3], free[3], staged[2]
+  uint4* keep = ring + PR_NSLOT * PR_HBUF;
+  uint2* xin_all = reinterpret_cast<uint2*>(ring + 2 * PR_PLANE);
+  pr_cnt_t* cnt = (pr_cnt_t*)(xin_all + 2 * PR_XBUF);  // full[3], free[3], staged[2], kept full[3], kept free[3]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int grp = wave >> 2, gw = wave & 3, lt = tid & 255;
   const int j = lane & 15, kq = lane >> 4;
@@ -119,14 +133,15 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
 
   // ---- second layer's filter into LDS, counters -----------------------------------------------------------------------
   for (int e = tid; e < PR_WL2; e += 512) wl2[e] = B.wq2[e];
-  if (tid < 8) cnt[tid] = 0u;
+  if (tid < 14) cnt[tid] = 0u;
 
-  // ---- first layer's filter fragments: channel cc * 32 + nf1 * 16 + j, K step ks = tap pairs 4 ks + kq ---------------
-  const int nf1 = gw & 1, mh = gw >> 1;
-  uint4 w1f[2][4][2];  // [chunk][K step][plane]
+  // ---- first layer: chunk c1 = channels 32 c1 .. 32 c1 + 31 as two 16-channel fragments, half mh of the pixel fragments -----
+  // filter fragments: channel 32 c1 + 16 nf + j, K step ks = tap pairs 4 ks + kq
+  const int c1 = gw >> 1, mh = gw & 1;
+  uint4 w1f[2][4][2];  // [channel fragment][K step][plane]
 #pragma unroll
-  for (int cc = 0; cc < 2; ++cc) {
-    const int co = cc * 32 + nf1 * 16 + j;
+  for (int nf = 0; nf < 2; ++nf) {
+    const int co = c1 * 32 + nf * 16 + j;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const int q = 4 * ks + kq, dy = q / 3, dx0 = 2 * (q - 3 * (q / 3));
@@ -139,51 +154,57 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
       }
       uint4 pl[2];
       split8h(f, sw1, pl);
-      w1f[cc][ks][0] = pl[0];
-      w1f[cc][ks][1] = pl[1];
+      w1f[nf][ks][0] = pl[0];
+      w1f[nf][ks][1] = pl[1];
     }
   }
-  float b1v[2][4];
-#pragma unroll
-  for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) b1v[cc][e] = B.b1[cc * 32 + nf1 * 16 + 4 * kq + e];
-  // pixel-fragment offsets (in staged pixels): K step -> tap pair (dy, dx); M fragment -> halo pixel (clamped to 179)
-  int koff[4], moff[6], mpix[6];
+  // Rows 2 .. 9 of the halo are nine 16-pixel fragments, pixel 16 f + j of the 144: the wave takes f = 4 mh + m, m < 4, and
+  // every other own tile the ninth as m = 4.  Rows 0 .. 1 (36 pixels) are three fragments: f = 2 mh + m, m < 2.
+  // Offsets in staged pixels: K step -> tap pair (dy, dx); fragment -> pixel (the top ones clamped to pixel 35).
+  int koff[4], mpix[5], moff[5], tpix[2], toff[2];
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) {
     const int q = (4 * ks + kq) < 15 ? 4 * ks + kq : 14;
     koff[ks] = (q / 3) * PR_XP + 2 * (q - 3 * (q / 3));
   }
 #pragma unroll
-  for (int m = 0; m < 6; ++m) {
-    const int p = (6 * mh + m) * 16 + j;
-    mpix[m] = p;
-    const int pc = p < PR_NPIX ? p : PR_NPIX - 1;
-    moff[m] = (pc / PR_HW) * PR_XP + pc % PR_HW;
+  for (int m = 0; m < 5; ++m) {
+    mpix[m] = 16 * (m < 4 ? 4 * mh + m : 8) + j;
+    const int p = PR_NKEEP + mpix[m];
+    moff[m] = (p / PR_HW) * PR_XP + p % PR_HW;
   }
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    tpix[m] = 16 * (2 * mh + m) + j;
+    const int p = tpix[m] < PR_NKEEP ? tpix[m] : PR_NKEEP - 1;
+    toff[m] = (p / PR_HW) * PR_XP + p % PR_HW;
+  }
+  // where this lane's four channels of fragment 0 go: byte offset of pixel 0 inside a slot / inside a buffer of kept rows
+  // (fragment 1: two 8-channel groups on)
+  const int wr_slot = (kq >> 1) * PR_NPIXP * 16 + (kq & 1) * 8, wr_keep = (c1 * 4 + (kq >> 1)) * PR_KP * 16 + (kq & 1) * 8;
 
   // ---- second layer: rows 4 rh .. 4 rh + 3, channels 16 nf2 .. 16 nf2 + 15 -------------------------------------------
+  // Halo row 4 rh + R is slot row 4 rh + R - 2, except halo rows 0 .. 1 (rh == 0: R = 0, 1) and 8 .. 9 (rh == 1: R = 4, 5),
+  // which are kept rows.
   const int rh = gw >> 1, nf2 = gw & 1;
   const int pj = j < 4 ? 2 * j : (j < 12 ? 2 * j - 7 : 2 * j - 16);
-  const int lane_b = (4 * rh) * PR_HW + pj + kq * PR_NPIXP;
+  const int lane_b = (4 * rh - 2) * PR_HW + pj + kq * PR_NPIXP;
+  const int lane_k = pj + kq * PR_KP;
   const int lane_a = kq * 32 + nf2 * 16 + j;
   float b2v[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) b2v[e] = B.b2[nf2 * 16 + 4 * kq + e];
 
-  // ---- tiles of this block: XCD-aware contiguous ranges (as conv_bfr.hip) --------------------------------------------
-  const int nblk = gridDim.x, xcd = blockIdx.x & 7, bi = blockIdx.x >> 3;
+  // ---- tiles of this block: a contiguous run of the column-major order (image, tile column, tile row), runs of equal
+  // length +-1; the blocks of an XCD take neighbouring runs ------------------------------------------------------------
+  const int nblk = gridDim.x, xcd = blockIdx.x & 7;
   int first, count;
   {
-    const int per_x = B.ntiles >> 3, rem_x = B.ntiles & 7;
-    const int nb_x = (nblk + 7 - xcd) >> 3;
-    const int tiles_x = per_x + (xcd < rem_x ? 1 : 0);
-    const int start_x = xcd * per_x + (xcd < rem_x ? xcd : rem_x);
-    first = start_x + bi;
-    count = bi < tiles_x ? (tiles_x - bi + nb_x - 1) / nb_x : 0;
+    const int lb = xcd * (nblk >> 3) + (xcd < (nblk & 7) ? xcd : (nblk & 7)) + (blockIdx.x >> 3);
+    const int per = B.ntiles / nblk, rem = B.ntiles - per * nblk;
+    first = lb * per + (lb < rem ? lb : rem);
+    count = per + (lb < rem ? 1 : 0);
   }
-  const int tstride = (nblk + 7 - xcd) >> 3;
   count = __builtin_amdgcn_readfirstlane(count);
 
   const __amdgpu_buffer_rsrc_t yr = pr_rsrc(B.y, B.y_bytes);
@@ -192,9 +213,9 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
   float xv[2][3];
   auto xload = [&](int i) {
     const bool valid = i < count;
-    const int t = first + (valid ? i : 0) * tstride;
+    const int t = first + (valid ? i : 0);
     const int n = t / B.img_tiles, rem = t - n * B.img_tiles;
-    const int ty = rem / B.tiles_x, tx = rem - ty * B.tiles_x;
+    const int tx = rem / B.tiles_y, ty = rem - tx * B.tiles_y;
     const __amdgpu_buffer_rsrc_t xr = pr_rsrc(B.x + (size_t)n * 3 * HW_, B.x_img_bytes);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -206,13 +227,53 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
         xv[s][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, (int)(o + (ok ? 4u * c * HW_ : 0u)), 0, 0));
     }
   };
+  // NM 16-pixel fragments of the first layer (per output: K step order 0 .. 3, three products per step)
+  auto l1_frags = [&](auto nm, const int* off, f32x4 (*a)[2]) {
+    constexpr int NM = decltype(nm)::value;
+#pragma unroll
+    for (int m = 0; m < NM; ++m) a[m][0] = a[m][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+#pragma unroll
+      for (int m = 0; m < NM; ++m) {
+        const int pa = off[m] + koff[ks];
+        const uint2 h0 = xin[pa], h1 = xin[pa + 1];
+        const uint2 l0 = xin[PR_XR * PR_XP + pa], l1 = xin[PR_XR * PR_XP + pa + 1];
+        const uint4 xh = make_uint4(h0.x, h0.y, h1.x, h1.y), xm = make_uint4(l0.x, l0.y, l1.x, l1.y);
+#pragma unroll
+        for (int nf = 0; nf < 2; ++nf) {
+          a[m][nf] = mfma16h(w1f[nf][ks][0], xm, a[m][nf]);
+          a[m][nf] = mfma16h(w1f[nf][ks][1], xh, a[m][nf]);
+          a[m][nf] = mfma16h(w1f[nf][ks][0], xh, a[m][nf]);
+        }
+      }
+    }
+  };
   bool dead = false;
   float amax = 0.f;
   xload(grp);
   __syncthreads();  // filter and counters visible
 
   unsigned own = 0;  // own tiles done
+  unsigned kseq = 0;
+  int typrev = 0;
   for (int i = grp; i < count; i += 2, ++own) {
+    const int t = first + i;
+    const int n = t / B.img_tiles, rem = t - n * B.img_tiles;
+    const int tx = rem / B.tiles_y, ty = rem - tx * B.tiles_y;
+    // Rows 0 .. 1 of this tile's halo are rows 8 .. 9 of the tile above when that is the run's previous tile; the first
+    // tile of a run and a column's top tile compute them.  Kept rows are numbered along the run: a tile's rows 8 .. 9 are
+    // number kseq, its rows 0 .. 1 number kseq - 1 (the previous tile's kseq, or a number of their own when computed
+    // here); number q lives in buffer q % 3 as its use q / 3.  Every number is written once by the four waves of one
+    // group and released eight times: by the four waves of the tile whose rows 8 .. 9 it is and by those of the tile
+    // below, or twice by the former when no tile takes it over (and twice by the tile that computed its own rows 0 .. 1).
+    // A buffer comes round after three numbers, so in the steady state its readers are two tiles behind the writer.
+    const bool fresh = i == 0 || ty == 0;
+    const bool hand = i + 1 < count && ty + 1 < B.tiles_y;
+    kseq = i == grp ? (grp == 0 ? 1u : 2u + (ty == 0 ? 1u : 0u))
+                    : kseq + 2u + (typrev + 1 == B.tiles_y ? 1u : 0u) + (ty == 0 ? 1u : 0u);
+    typrev = ty;
+    const unsigned kb = kseq % PR_NKBUF, ku = kseq / PR_NKBUF, tb = (kseq - 1u) % PR_NKBUF, tu = (kseq - 1u) / PR_NKBUF;
     // -- stage the input tile (split into fp16 planes at the input's scale), fetch the next own tile's ---------------
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -230,63 +291,75 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
     xload(i + 2);
     pr_wait(cnt + 6 + grp, 4u * (own + 1), dead);
 
-    // -- first layer: six 16-pixel fragments x 16 channels of both chunks ------------------------------------------------
-    f32x4 a1[2][6];
+    float b1v[2][4];  // (read per tile: registers are short where the second layer runs)
 #pragma unroll
-    for (int cc = 0; cc < 2; ++cc)
+    for (int nf = 0; nf < 2; ++nf)
 #pragma unroll
-      for (int m = 0; m < 6; ++m) a1[cc][m] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      for (int e = 0; e < 4; ++e) b1v[nf][e] = B.b1[c1 * 32 + nf * 16 + 4 * kq + e];
+    // bias, ReLU, split at the intermediate's scale; the (high, residual) plane words of the lane's 2 x 4 channels of one
+    // pixel go to pixel cell `pix` of a [group][pitch] block of 16-byte cells and of its residual twin PR_PLANE cells on
+    auto l1_store = [&](const f32x4 (&a)[2], unsigned char* base, int pix, int pitch) {
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
+      for (int nf = 0; nf < 2; ++nf) {
+        float v[4];
 #pragma unroll
-      for (int m = 0; m < 6; ++m) {
-        const int pa = moff[m] + koff[ks];
-        const uint2 h0 = xin[pa], h1 = xin[pa + 1];
-        const uint2 l0 = xin[PR_XR * PR_XP + pa], l1 = xin[PR_XR * PR_XP + pa + 1];
-        const uint4 xh = make_uint4(h0.x, h0.y, h1.x, h1.y), xm = make_uint4(l0.x, l0.y, l1.x, l1.y);
-#pragma unroll
-        for (int cc = 0; cc < 2; ++cc) {
-          a1[cc][m] = mfma16h(w1f[cc][ks][0], xm, a1[cc][m]);
-          a1[cc][m] = mfma16h(w1f[cc][ks][1], xh, a1[cc][m]);
-          a1[cc][m] = mfma16h(w1f[cc][ks][0], xh, a1[cc][m]);
-        }
+        for (int e = 0; e < 4; ++e) v[e] = fmaxf(__builtin_fmaf(a[nf][e], dsc1, b1v[nf][e]), 0.f);
+        unsigned h01, m01, h23, m23;
+        split2h(v[0], v[1], sxm, h01, m01);
+        split2h(v[2], v[3], sxm, h23, m23);
+        *reinterpret_cast<uint2*>(base + ((2 * nf) * pitch + pix) * 16) = make_uint2(h01, h23);
+        *reinterpret_cast<uint2*>(base + (PR_PLANE + (2 * nf) * pitch + pix) * 16) = make_uint2(m01, m23);
       }
-    }
-    // -- ... into the ring: bias, ReLU, split at the intermediate's scale --------------------------------------------------
-#pragma unroll
-    for (int cc = 0; cc < 2; ++cc) {
-      const unsigned st = 2u * (unsigned)i + cc, slot = st % PR_NSLOT, use = st / PR_NSLOT;
+    };
+    // -- first layer: this wave's fragments of rows 2 .. 9, the 32 channels of its chunk, into the ring -----------------
+    auto l1_tile = [&](auto nm) {
+      constexpr int NM = decltype(nm)::value;
+      f32x4 a1[NM][2];
+      l1_frags(nm, moff, a1);
+      const unsigned st = 2u * (unsigned)i + c1, slot = st % PR_NSLOT, use = st / PR_NSLOT;
+      unsigned char* hb = reinterpret_cast<unsigned char*>(ring + slot * PR_HBUF) + wr_slot;
       pr_wait(cnt + 3 + slot, 4u * use, dead);
-      unsigned char* hb = reinterpret_cast<unsigned char*>(ring + slot * PR_HBUF);
-      const int g8 = 2 * nf1 + (kq >> 1), half = kq & 1;
 #pragma unroll
-      for (int m = 0; m < 6; ++m) {
-        if (mpix[m] < PR_NPIX) {
-          float v[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = fmaxf(__builtin_fmaf(a1[cc][m][e], dsc1, b1v[cc][e]), 0.f);
-          unsigned h01, m01, h23, m23;
-          split2h(v[0], v[1], sxm, h01, m01);
-          split2h(v[2], v[3], sxm, h23, m23);
-          *reinterpret_cast<uint2*>(hb + ((size_t)(0 * 4 + g8) * PR_NPIXP + mpix[m]) * 16 + half * 8) = make_uint2(h01, h23);
-          *reinterpret_cast<uint2*>(hb + ((size_t)(1 * 4 + g8) * PR_NPIXP + mpix[m]) * 16 + half * 8) = make_uint2(m01, m23);
-        }
-      }
+      for (int m = 0; m < NM; ++m)
+        if (mpix[m] < PR_NSLOTPIX) l1_store(a1[m], hb, mpix[m], PR_NPIXP);
       pr_signal(cnt + slot);
+      // rows 8 .. 9 = pixels 108 .. 143 (in fragments 6 .. 8, m >= 2 where a wave has them) are kept rows
+      unsigned char* kp = reinterpret_cast<unsigned char*>(keep + kb * PR_KBUF) + wr_keep;
+      pr_wait(cnt + 11 + kb, 8u * ku, dead);
+#pragma unroll
+      for (int m = 2; m < NM; ++m)
+        if (mpix[m] >= PR_NSLOTPIX) l1_store(a1[m], kp, mpix[m] - PR_NSLOTPIX, PR_KP);
+      pr_signal(cnt + 8 + kb);
+    };
+    if (mh == (int)(own & 1))
+      l1_tile(std::integral_constant<int, 5>{});
+    else
+      l1_tile(std::integral_constant<int, 4>{});
+    if (fresh) {  // rows 0 .. 1 computed here
+      f32x4 at[2][2];
+      l1_frags(std::integral_constant<int, 2>{}, toff, at);
+      unsigned char* kp = reinterpret_cast<unsigned char*>(keep + tb * PR_KBUF) + wr_keep;
+      pr_wait(cnt + 11 + tb, 8u * tu, dead);
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+        if (tpix[m] < PR_NKEEP) l1_store(at[m], kp, tpix[m], PR_KP);
+      pr_signal(cnt + 8 + tb);
     }
 
-    // -- second layer out of the ring -----------------------------------------------------------------------------------------
-    const int t = first + i * tstride;
-    const int n = t / B.img_tiles, rem = t - n * B.img_tiles;
-    const int ty = rem / B.tiles_x, tx = rem - ty * B.tiles_x;
+    // -- second layer out of the ring and the kept rows --------------------------------------------------------------
     f32x4 acc[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) acc[r] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    pr_wait(cnt + 8 + (rh == 0 ? tb : kb), 4u * ((rh == 0 ? tu : ku) + 1u), dead);
 #pragma unroll
     for (int cc = 0; cc < 2; ++cc) {
       const unsigned st = 2u * (unsigned)i + cc, slot = st % PR_NSLOT, use = st / PR_NSLOT;
-      pr_wait(cnt + slot, 4u * (use + 1), dead);
+      pr_wait(cnt + slot, 2u * (use + 1), dead);
       const uint4* hb = ring + slot * PR_HBUF + lane_b;
+      // the wave's rows out of kept rows: R = 0, 1 (rh == 0: rows 0 .. 1), R = 4, 5 (rh == 1: rows 8 .. 9)
+      const uint4* kr = keep + (rh == 0 ? tb : kb) * PR_KBUF + cc * 4 * PR_KP + lane_k - (rh == 0 ? 0 : 4 * PR_HW);
+      const uint4* pa = rh == 0 ? kr : hb;
+      const uint4* pc = rh == 0 ? hb : kr;
 #pragma unroll
       for (int v = 0; v < 3; ++v) {
         uint4 fa[3][2];
@@ -297,7 +370,8 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
         }
 #pragma unroll
         for (int R = 0; R < 6; ++R) {
-          const uint4 xh = hb[R * PR_HW + v], xm = hb[R * PR_HW + v + 4 * PR_NPIXP];
+          const uint4* px = R < 2 ? pa : (R < 4 ? hb : pc);
+          const uint4 xh = px[R * PR_HW + v], xm = px[R * PR_HW + v + PR_PLANE];
 #pragma unroll
           for (int u = 0; u < 3; ++u) {
             const int r = R - u;
@@ -311,6 +385,8 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
       }
       pr_signal(cnt + 3 + slot);
     }
+    pr_signal(cnt + 11 + tb, fresh ? 2u : 1u);
+    pr_signal(cnt + 11 + kb, hand ? 1u : 2u);
     // -- epilogue: bias, ReLU, NHWC stores of the pixels inside the output, running maximum -----------------------------
     const int oc = tx * PR_TW + pj;
 #pragma unroll
@@ -352,7 +428,7 @@ int espcn_pair_launch(int N, int H, int W, const float* x, const float* w1, cons
   B.x = x; B.w1 = w1; B.b1 = b1; B.b2 = b2; B.y = y; B.x_amax = x_amax; B.y_amax = y_amax;
   B.wq2 = reinterpret_cast<const uint4*>(fsec);
   B.w2_descale = reinterpret_cast<const float*>(fsec + bf3_main_bytes(64, 32, 9));
-  B.N = N; B.H = H; B.W = W; B.OH = OH; B.OW = OW; B.tiles_x = tiles_x; B.img_tiles = tiles_x * tiles_y;
+  B.N = N; B.H = H; B.W = W; B.OH = OH; B.OW = OW; B.tiles_y = tiles_y; B.img_tiles = tiles_x * tiles_y;
   B.ntiles = (int)ntiles;
   B.x_img_bytes = (unsigned)x_img;
   B.y_bytes = (unsigned)y_bytes;
