@@ -536,6 +536,32 @@ int srk_float_to_u8_image(const float* x, int64_t c_stride, int64_t row_stride, 
 int srk_rgb_to_ycc_host(const uint8_t* rgb, size_t n, uint8_t* ycc);
 int srk_ycc_to_rgb_host(const uint8_t* ycc, size_t n, uint8_t* rgb);
 
+/* ---- tiled super-resolution of one picture (tiling.py; csrc/tile.hip) ------------------------------------------
+ * (Added without a change of srk_version(): new entry points only, nothing existing changed.)
+ * A picture is cut into equal, overlapping tiles that lie inside it, the tiles run through the net as batches, and every
+ * output pixel is taken from the ONE tile that owns it.  The plan is separable; `table` is device memory, int32
+ * [nty + ntx][4], the nty tile rows first, then the ntx tile columns, an entry being {input offset of the tile, first
+ * owned output pixel, end of the owned output pixels, output pixel of the tile's local output pixel 0}.  Tile t =
+ * row * ntx + col; a call handles tiles t0 .. t0 + n.  The kernels skip, and never dereference, a coordinate the table
+ * puts outside a tile or the picture.
+ *
+ * srk_tile_gather: fp32 picture [C][H][W] through element strides (channel, row, pixel), C = 1 or 3 -> dense NHWC tiles
+ *   out [n][th][tw][C].
+ * srk_tile_stitch_f32: tile outputs [n][C][oth][otw] through element strides (tile, channel, row, pixel) -- a
+ *   channels-last net output is read in place -> the owned rectangles of those tiles in the fp32 picture out [C][OH][OW].
+ *   The chunks of a plan together write every pixel of out exactly once.
+ * srk_tile_stitch_u8: the same walk, writing the final interleaved 8-bit picture: cb == cr == NULL: out [OH][OW][C],
+ *   quantised like srk_float_to_u8_image; else C = 1 and cb / cr are dense 8-bit planes [OH][OW]: out [OH][OW][3] RGB,
+ *   Y quantised and converted like srk_ycc_to_rgb_u8.  The fp32 picture is never written. */
+int srk_tile_gather(const float* pic, int64_t c_stride, int64_t row_stride, int64_t px_stride, int C, int H, int W,
+                    const int32_t* table, int nty, int ntx, int th, int tw, int t0, int n, float* out, void* stream);
+int srk_tile_stitch_f32(const float* tiles, int64_t n_stride, int64_t c_stride, int64_t row_stride, int64_t px_stride, int C,
+                        int oth, int otw, const int32_t* table, int nty, int ntx, int t0, int n, float* out, int OH, int OW,
+                        void* stream);
+int srk_tile_stitch_u8(const float* tiles, int64_t n_stride, int64_t c_stride, int64_t row_stride, int64_t px_stride, int C,
+                       int oth, int otw, const int32_t* table, int nty, int ntx, int t0, int n, const uint8_t* cb,
+                       const uint8_t* cr, uint8_t* out, int OH, int OW, void* stream);
+
 /* ---- steps either side of the nets ------------------------------------------------
  * utils.PSNR (utils.py:208-216): mse = mean((clamp(pred,0,1) - gt)^2) over all elements, *psnr_out = mse == 0 ? 100 :
  * 10*log10(1/mse), on the device (the reference copies both images to the host per test image).  pred / gt are

@@ -3,7 +3,8 @@
 dispatching to the MI355X trainers.  Extra flags: --synthetic (seeded random patches instead of the image
 folders under --data_dir; --steps_per_epoch of them per epoch), --epoch_pretrain, --precision {mixed,bf16x3,fp32},
 --test_single PATH (load the checkpoint, super-resolve that picture file into <save_dir>/test_result/SR_result.png, print
-the file name; no training) and --save_test_images (test() also writes every result image and reports the bicubic PSNR).
+the file name; no training) and --save_test_images (test() also writes every result image and reports the bicubic PSNR) and --tile N|auto (--test_single
+and test() cut the picture into overlapping tiles, run them as batches and stitch the exact result).
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N main.py ..."""
 import argparse
 import os
@@ -14,6 +15,16 @@ def _names(text):
     given on the command line into its characters ('DIV2K' -> ['D','I','V','2','K']); here a value is one name or a
     comma-separated list of names."""
     return [n for n in (t.strip() for t in str(text).split(',')) if n]
+
+
+def _tile(text):
+    """--tile: a positive number of net-input pixels, or 'auto'."""
+    if str(text).lower() == 'auto':
+        return 'auto'
+    v = int(text)
+    if v < 1:
+        raise argparse.ArgumentTypeError("--tile takes a positive integer or 'auto'")
+    return v
 
 
 def parse_args(argv=None):
@@ -52,6 +63,10 @@ def parse_args(argv=None):
                         '--num_channels 1, colour restored from the bicubic Cb / Cr) and print the name of the PNG written')
     p.add_argument('--save_test_images', action='store_true',
                    help='test(): write every result image to <save_dir>/test_result/<dataset>/ and report the bicubic PSNR')
+    p.add_argument('--tile', type=_tile, default=None, metavar='N|auto',
+                   help='--test_single and test(): cut the picture into overlapping tiles of N x N net-input pixels, run '
+                        'them as batches and stitch the exact result (auto: only pictures too large for one pass); '
+                        'default: one pass')
     return check_args(p.parse_args(argv))
 
 

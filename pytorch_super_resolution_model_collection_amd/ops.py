@@ -1806,6 +1806,102 @@ def resize_u8(planes_u8, oh, ow, interpolation="bicubic", out_float=False):
 
 
 # ------------------------------------------------------------------------------------------------
+# Tiled super-resolution of one picture (tiling.py, csrc/tile.hip): gather the plan's tiles, stitch their outputs
+# ------------------------------------------------------------------------------------------------
+class TilePlan(object):
+    """A tiling.Plan with its table on the device.  The table goes up once, from pinned memory and without waiting for
+    the copy; the kernels of every chunk read it there."""
+
+    def __init__(self, plan, device):
+        self.plan = plan
+        self.nty, self.ntx = len(plan.rows), len(plan.cols)
+        host = torch.tensor(plan.table(), dtype=torch.int32).pin_memory()
+        self.table = host.to(device, non_blocking=True)
+        self._host = host   # (kept until the plan goes: the copy reads it asynchronously)
+
+
+def _tile_chunk(tp, t0, n):
+    t0 = int(t0)
+    n = tp.plan.ntiles - t0 if n is None else int(n)
+    if t0 < 0 or n < 1 or t0 + n > tp.plan.ntiles:
+        raise RuntimeError("tiles %d .. %d are not in a plan of %d tiles" % (t0, t0 + n, tp.plan.ntiles))
+    return t0, n
+
+
+def tile_gather(pic, tp, t0=0, n=None):
+    """Tiles t0 .. t0 + n of the plan `tp` (a TilePlan) from the fp32 picture `pic` ([C,H,W] or [1,C,H,W], any strides:
+    the planar Y plane of rgb_to_ycc_planes, the planar output of resize_u8 and img_interp's output are read in place),
+    C = 1 or 3, as the batch [n,C,th,tw] in channels-last storage the nets take."""
+    require_cuda(pic)
+    x = pic.detach()
+    if x.dim() == 4 and x.shape[0] == 1:
+        x = x[0]
+    p = tp.plan
+    if x.dim() != 3 or x.shape[0] not in (1, 3) or x.dtype != torch.float32 or tuple(x.shape[1:]) != (p.H, p.W):
+        raise RuntimeError("tile_gather expects an fp32 [C,%d,%d] picture with C = 1 or 3, got %s %s"
+                           % (p.H, p.W, x.dtype, tuple(pic.shape)))
+    t0, n = _tile_chunk(tp, t0, n)
+    c = int(x.shape[0])
+    out = _empty_cl(n, c, p.th, p.tw, x)
+    check(_lib.load().srk_tile_gather(ptr(x), int(x.stride(0)), int(x.stride(1)), int(x.stride(2)), c, p.H, p.W, ptr(tp.table),
+                                      tp.nty, tp.ntx, p.th, p.tw, t0, n, ptr(out), stream_ptr()), "srk_tile_gather")
+    return out
+
+
+def _stitch_source(what, tiles, tp, t0):
+    require_cuda(tiles)
+    y = tiles.detach()
+    p = tp.plan
+    if y.dim() != 4 or y.shape[1] not in (1, 3) or y.dtype != torch.float32 or tuple(y.shape[2:]) != (p.oth, p.otw):
+        raise RuntimeError("%s expects fp32 tile outputs [n,C,%d,%d] with C = 1 or 3, got %s %s"
+                           % (what, p.oth, p.otw, y.dtype, tuple(tiles.shape)))
+    t0, n = _tile_chunk(tp, t0, int(y.shape[0]))
+    return y, t0, n, int(y.shape[1])
+
+
+def tile_stitch(tiles, tp, t0=0, out=None):
+    """The owned rectangles of tile outputs `tiles` ([n,C,oth,otw] fp32 of any strides: a channels-last net output is read
+    in place; tiles t0 .. t0 + n of the plan) into the fp32 picture `out` [C,OH,OW] (allocated when None; the chunks of
+    a plan together write every pixel once).  Returns out."""
+    y, t0, n, c = _stitch_source("tile_stitch", tiles, tp, t0)
+    p = tp.plan
+    if out is None:
+        out = torch.empty((c, p.OH, p.OW), dtype=torch.float32, device=y.device)
+    elif tuple(out.shape) != (c, p.OH, p.OW) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != y.device:
+        raise RuntimeError("tile_stitch: out must be a dense fp32 [%d,%d,%d] tensor on %s" % (c, p.OH, p.OW, y.device))
+    check(_lib.load().srk_tile_stitch_f32(ptr(y), int(y.stride(0)), int(y.stride(1)), int(y.stride(2)), int(y.stride(3)), c,
+                                          p.oth, p.otw, ptr(tp.table), tp.nty, tp.ntx, t0, n, ptr(out), p.OH, p.OW,
+                                          stream_ptr()), "srk_tile_stitch_f32")
+    return out
+
+
+def tile_stitch_u8(tiles, tp, t0=0, out=None, cb=None, cr=None):
+    """tile_stitch writing the final 8-bit picture directly: to_u8_image(tile_stitch(...)) without the fp32 picture
+    (uint8 [OH,OW,C]), or with the chroma planes cb / cr (uint8 [OH,OW]; C = 1) ycbcr_to_rgb_u8(tile_stitch(...), cb, cr)
+    (uint8 [OH,OW,3]); bit-equal to those compositions."""
+    y, t0, n, c = _stitch_source("tile_stitch_u8", tiles, tp, t0)
+    p = tp.plan
+    if (cb is None) != (cr is None):
+        raise RuntimeError("tile_stitch_u8: cb and cr come together")
+    oc = c
+    if cb is not None:
+        _require_u8("tile_stitch_u8", cb, cr)
+        if c != 1 or tuple(cb.shape) != (p.OH, p.OW) or tuple(cr.shape) != (p.OH, p.OW):
+            raise RuntimeError("tile_stitch_u8: chroma planes must be [%d,%d] and go with a one-channel output (got C = %d, "
+                               "cb %s, cr %s)" % (p.OH, p.OW, c, tuple(cb.shape), tuple(cr.shape)))
+        cb, cr, oc = cb.contiguous(), cr.contiguous(), 3
+    if out is None:
+        out = torch.empty((p.OH, p.OW, oc), dtype=torch.uint8, device=y.device)
+    elif tuple(out.shape) != (p.OH, p.OW, oc) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != y.device:
+        raise RuntimeError("tile_stitch_u8: out must be a dense uint8 [%d,%d,%d] tensor on %s" % (p.OH, p.OW, oc, y.device))
+    check(_lib.load().srk_tile_stitch_u8(ptr(y), int(y.stride(0)), int(y.stride(1)), int(y.stride(2)), int(y.stride(3)), c,
+                                         p.oth, p.otw, ptr(tp.table), tp.nty, tp.ntx, t0, n,
+                                         None if cb is None else ptr(cb), None if cr is None else ptr(cr), ptr(out), p.OH, p.OW,
+                                         stream_ptr()), "srk_tile_stitch_u8")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # DRCN (drcn.py:13-59): the weight-shared recursion and the recursive-supervision head
 # ------------------------------------------------------------------------------------------------
 # The inference net applies ONE conv + ReLU D times in a row and ONE two-conv reconstruction to each of the D hidden

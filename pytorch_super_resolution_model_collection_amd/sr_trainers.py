@@ -18,7 +18,7 @@ import os
 import torch
 
 from . import dp as dpmod
-from . import models, ops, optim, trainers, utils
+from . import models, ops, optim, tiling, trainers, utils
 
 
 def synthetic_loader(kind, args, steps, device, seed=1234):
@@ -233,14 +233,64 @@ class _Trainer(object):
         with torch.no_grad():
             return self.model(x.to(self.device))
 
-    def test(self, loader=None, save_images=False):
+    # -- tiled inference (tiling.py, csrc/tile.hip) ------------------------------------------------------------------
+    def _resolve_tile(self, tile, x):
+        """The `tile` option for the net input x -> (tile size or None for one pass, the net's geometry or None).
+        tile=None falls back to args.tile (older args objects have no such field); still None: nothing is computed."""
+        if tile is None:
+            tile = getattr(self.args, 'tile', None)
+        if tile is None:
+            return None, None
+        self.model.eval()
+        geo = tiling.net_geometry(self.model)
+        return tiling.resolve_tile(tile, geo, int(x.shape[-2]), int(x.shape[-1])), geo
+
+    def _infer_tiled(self, x, geo, tile, tile_batch=None, as_u8=False, chroma=None):
+        """The net's output for the net input x [1,C,H,W] (on the device), computed on overlapping tiles: the plan's table
+        goes to the device once, then per chunk of `tile_batch` tiles: k_tile_gather -> _infer on the batch (last element
+        of a tuple output) -> k_tile_stitch of the rectangles those tiles own.  The peak working set is one chunk's
+        activations plus the output picture; nothing waits for the device.  Returns the fp32 picture [1,C,OH,OW], or with
+        as_u8 the final interleaved 8-bit picture (chroma: the picture's 8-bit Cb / Cr planes [2,h,w], resized here to the
+        output size and merged by the stitch), in which case the fp32 picture is never written."""
+        plan = tiling.plan(geo, int(x.shape[-2]), int(x.shape[-1]), tile)
+        tp = ops.TilePlan(plan, self.device)
+        if tile_batch is None:
+            tile_batch = getattr(self.args, 'tile_batch', None) or tiling.DEFAULT_TILE_BATCH
+        tile_batch = plan.ntiles if tile_batch in ('all', 0) else max(1, int(tile_batch))
+        cb = cr = None
+        if chroma is not None:
+            cb, cr = ops.resize_u8(chroma, plan.OH, plan.OW)   # both chroma planes in one resizer call
+        out = None
+        for t0 in range(0, plan.ntiles, tile_batch):
+            y = self._infer(ops.tile_gather(x, tp, t0, min(tile_batch, plan.ntiles - t0)))
+            y = y[-1] if isinstance(y, tuple) else y
+            if tuple(y.shape[-2:]) != (plan.oth, plan.otw):
+                raise RuntimeError("tiled inference: the net returned %s for a tile of %d x %d, the geometry says %d x %d"
+                                   % (tuple(y.shape), plan.th, plan.tw, plan.oth, plan.otw))
+            if as_u8:
+                out = ops.tile_stitch_u8(y, tp, t0, out, cb, cr)
+            else:
+                out = ops.tile_stitch(y, tp, t0, out)
+        return out if as_u8 else out.unsqueeze(0)
+
+    def _forward(self, x, tile=None, tile_batch=None):
+        """_net_input and the net (last element of a tuple output) on the device: one pass, or tiled when `tile` says so."""
+        x = self._net_input(x)
+        size, geo = self._resolve_tile(tile, x)
+        if size is None:
+            out = self._infer(x)
+            return out[-1] if isinstance(out, tuple) else out
+        return self._infer_tiled(x, geo, size, tile_batch)
+
+    def test(self, loader=None, save_images=False, tile=None):
         """Evaluation loop (espcn.py:173-215, edsr.py:196-250): forward + PSNR per image (computed on the device), over
         `loader`, else over every folder of `test_dataset` that exists under `data_dir` (data.get_test_set), else over
         seeded synthetic pairs.  Returns the list of PSNRs; `self.test_psnr` holds the per-dataset averages.
         save_images: as the reference's test() (edsr.py:215-274), every result also goes through utils.save_img into
         <save_dir>/test_result/<dataset>/SR_result_<n>.png, and `self.test_bicubic_psnr` holds, per dataset, the
         average PSNR of the loader's bicubic image (the third item, where the loader yields one) against the target
-        (edsr.py:257-261), computed by the same device kernel."""
+        (edsr.py:257-261), computed by the same device kernel.
+        tile: None (args.tile, else one pass), a tile size in net-input pixels or 'auto': see test_single."""
         if self.model is None:
             self.model = self.build_model().to(self.device)
             self.load_model()
@@ -264,8 +314,7 @@ class _Trainer(object):
                 items = [batch] if torch.is_tensor(batch[0]) else list(zip(*batch))   # ragged test images come as lists
                 for item in items:
                     lr_img, hr_img = self._channels(*[t if t.dim() == 4 else t.unsqueeze(0) for t in item[:2]])
-                    out = self._infer(self._net_input(lr_img.to(self.device)))
-                    out = out[-1] if isinstance(out, tuple) else out
+                    out = self._forward(lr_img.to(self.device), tile)
                     tgt = hr_img.to(self.device)
                     if self.kind == "srcnn":     # srcnn.py:193-199: border pixels excluded
                         tgt = utils.shave(tgt, 8)
@@ -287,20 +336,24 @@ class _Trainer(object):
                 self.test_bicubic_psnr[name] = sum(bvals) / len(bvals)
         return psnrs
 
-    def test_single(self, img):
+    def test_single(self, img, tile=None, tile_batch=None):
         """A tensor: super-resolve one [C,H,W] (or [1,C,H,W]) tensor and return the net's output on the host.
         A path (str / os.PathLike): the reference's test_single(img_fn) (edsr.py:276-322) -- super-resolve the picture
-        file, write <save_dir>/test_result/SR_result.png and return that file name; see _test_single_file."""
+        file, write <save_dir>/test_result/SR_result.png and return that file name; see _test_single_file.
+        tile: None (args.tile, else off) runs the picture in one pass, as a batch of one.  A number cuts the net's input
+        (the bicubic-upsampled picture for SRCNN / VDSR / DRCN) into overlapping tiles of that many pixels a side, runs
+        them in batches of `tile_batch` (tiling.DEFAULT_TILE_BATCH; 'all' = one batch) and stitches every output pixel
+        from the one tile that holds its whole receptive field: the one-pass result, with a working set that does not
+        grow with the picture.  'auto' tiles only pictures whose widest activation exceeds tiling.AUTO_BUDGET_BYTES."""
         if isinstance(img, (str, os.PathLike)):
-            return self._test_single_file(img)
+            return self._test_single_file(img, tile, tile_batch)
         if self.model is None:
             self.model = self.build_model().to(self.device)
             self.load_model()
         x = img if img.dim() == 4 else img.unsqueeze(0)
-        out = self._infer(self._net_input(x.to(self.device)))
-        return (out[-1] if isinstance(out, tuple) else out).cpu()
+        return self._forward(x.to(self.device), tile, tile_batch).cpu()
 
-    def _test_single_file(self, img_fn):
+    def _test_single_file(self, img_fn, tile=None, tile_batch=None):
         """edsr.py:276-322 with the picture on the device from the decode to the 8-bit result:
           num_channels == 1  upload the 8-bit RGB once -> k_rgb_to_ycc (fp32 Y / 255 and planar Cb / Cr in one pass) -> Y
                              through _net_input and _infer exactly as the tensor form does (bicubic pre-upsampling for
@@ -310,10 +363,10 @@ class _Trainer(object):
                              copy of the 8-bit image;
           num_channels == 3  RGB / 255 in, k_to_u8 out.
         Bit-exact with the reference's Pillow tail for the same net output.  Nothing between the upload and that copy
-        waits for the device.  Every trainer follows the EDSR convention for the net's output, clamp(0, 1): SRCNN's own
-        test_single stretches the output to its min..max instead (srcnn.py:244), which turns any picture grey-scaled to
-        full range; that is not reproduced."""
-        from PIL import Image
+        waits for the device.  Tiled (see test_single): the stitch kernel writes the 8-bit result itself (k_tile_stitch
+        quantises, and merges the resized chroma, on the way), so the fp32 HR picture never exists.  Every trainer follows
+        the EDSR convention for the net's output, clamp(0, 1): SRCNN's own test_single stretches the output to its min..max
+        instead (srcnn.py:244), which turns any picture grey-scaled to full range; that is not reproduced."""
         from . import data
         if self.model is None:
             self.model = self.build_model().to(self.device)
@@ -325,7 +378,12 @@ class _Trainer(object):
             x = y.view(1, 1, h, w)
         else:
             x = ops.resize_u8(rgb.permute(2, 0, 1), h, w, out_float=True).unsqueeze(0)   # ToTensor: planar, / 255
-        out = self._infer(self._net_input(x))
+        x = self._net_input(x)
+        size, geo = self._resolve_tile(tile, x)
+        if size is not None:
+            return self._save_single(self._infer_tiled(x, geo, size, tile_batch, as_u8=True,
+                                                       chroma=cbcr if self.num_channels == 1 else None))
+        out = self._infer(x)
         out = out[-1] if isinstance(out, tuple) else out
         if self.num_channels == 1:
             oh, ow = int(out.shape[-2]), int(out.shape[-1])
@@ -333,6 +391,10 @@ class _Trainer(object):
             img8 = ops.ycbcr_to_rgb_u8(out, cbcr[0], cbcr[1])
         else:
             img8 = ops.to_u8_image(out)
+        return self._save_single(img8)
+
+    def _save_single(self, img8):
+        from PIL import Image
         arr = img8.cpu().numpy()   # the one device-to-host copy
         result_dir = os.path.join(self.save_dir, 'test_result')
         os.makedirs(result_dir, exist_ok=True)
