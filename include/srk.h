@@ -569,6 +569,30 @@ int srk_tile_stitch_u8(const float* tiles, int64_t n_stride, int64_t c_stride, i
 size_t srk_psnr_workspace_bytes(void);
 int srk_psnr(const float* pred, const int64_t* pred_strides, const float* gt, const int64_t* gt_strides, int N, int C,
              int H, int W, float* psnr_out, float* mse_out, void* workspace, void* stream);
+/* SSIM (Wang, Bovik, Sheikh, Simoncelli 2004, as ssim_index.m computes it) of pred against gt, on the device.
+ * (Added without a change of srk_version(): new entry points only, nothing existing changed.)
+ * Window 11 x 11, separable, g[i] = exp(-(i - 5)^2 / (2 * 1.5^2)) normalised to sum 1; the five moments at the VALID
+ * positions only ((H' - 10) x (W' - 10) of an H' x W' plane); C1 = (0.01 L)^2, C2 = (0.03 L)^2; the result is the plain
+ * mean over all positions of all planes of all images of the call.  Moments are accumulated in double.
+ * shave >= 0 crops that many pixels from each side of both tensors first (H' = H - 2 shave; no copy).  domain says what
+ * enters the moments, for BOTH tensors, applied while they are read and never written to memory:
+ *   SRK_SSIM_FLOAT  clamp(pred, 0, 1) against gt as it is (what srk_psnr compares; NaN in pred counts as 0), L = 1
+ *   SRK_SSIM_U8     the byte of srk_float_to_u8_image, (uint8)(clamp(v, 0, 1) * 255.0f), L = 255
+ *   SRK_SSIM_Y8     C == 3: those bytes through Pillow's RGB -> Y table (srk_rgb_to_ycc_u8), one plane per image;
+ *                   C == 1: as SRK_SSIM_U8; any other C is refused
+ * *mse_out = mean squared difference of the same pixels (all H' x W' of them) divided by L^2, *psnr_out = mse == 0 ? 100 :
+ * 10 log10(1 / mse); either may be NULL.  pred / gt are addressed through element strides (n,c,h,w); NULL = NHWC-dense.
+ * Per-block sums go to `workspace` (srk_ssim_workspace_bytes() bytes, contents irrelevant) and are added in a fixed
+ * order: two calls on the same inputs return the same bits.  A plane under 11 x 11 after the crop is SRK_ERR_BAD_ARG.
+ * srk_ssim_host: the same definition in plain C++ double on HOST pointers (no device involved), sharing the window, the
+ * domains and the formula with the kernel, so the definition can be pinned without a GPU. */
+enum { SRK_SSIM_FLOAT = 0, SRK_SSIM_U8 = 1, SRK_SSIM_Y8 = 2 };
+size_t srk_ssim_workspace_bytes(void);
+int srk_ssim(const float* pred, const int64_t* pred_strides, const float* gt, const int64_t* gt_strides, int N, int C,
+             int H, int W, int shave, int domain, float* ssim_out, float* psnr_out, float* mse_out, void* workspace,
+             void* stream);
+int srk_ssim_host(const float* pred, const int64_t* pred_strides, const float* gt, const int64_t* gt_strides, int N, int C,
+                  int H, int W, int shave, int domain, double* ssim_out, double* psnr_out, double* mse_out);
 /* utils.norm / utils.denorm (utils.py:219-239; torchvision Normalize = sub_(mean).div_(std)):
  * y[e] = (x[e] - sub[c]) / div[c], c = (e / inner) % C (inner = H*W for NCHW storage, 1 for NHWC), optionally clamped
  * to [0,1] (denorm's non-VGG branch).  sub_host / div_host are HOST arrays of C <= 8 floats. Bit-equal to torch. */

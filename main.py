@@ -4,7 +4,9 @@ dispatching to the MI355X trainers.  Extra flags: --synthetic (seeded random pat
 folders under --data_dir; --steps_per_epoch of them per epoch), --epoch_pretrain, --precision {mixed,bf16x3,fp32},
 --test_single PATH (load the checkpoint, super-resolve that picture file into <save_dir>/test_result/SR_result.png, print
 the file name; no training) and --save_test_images (test() also writes every result image and reports the bicubic PSNR) and --tile N|auto (--test_single
-and test() cut the picture into overlapping tiles, run them as batches and stitch the exact result).
+and test() cut the picture into overlapping tiles, run them as batches and stitch the exact result), --test_only (load
+the checkpoint and run test() on the test sets, no training; one line per dataset with PSNR and SSIM) and --eval_domain
+{float,u8,y8} / --eval_shave N (test() also reports PSNR and SSIM on the 8-bit picture or its luma, with a border left out).
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N main.py ..."""
 import argparse
 import os
@@ -67,6 +69,14 @@ def parse_args(argv=None):
                    help='--test_single and test(): cut the picture into overlapping tiles of N x N net-input pixels, run '
                         'them as batches and stitch the exact result (auto: only pictures too large for one pass); '
                         'default: one pass')
+    p.add_argument('--test_only', action='store_true',
+                   help='no training: load the checkpoint, run test() on the test sets (honours --save_test_images and '
+                        '--tile) and print PSNR and SSIM per dataset')
+    p.add_argument('--eval_domain', type=str, default=None, choices=['float', 'u8', 'y8'],
+                   help='test(): also report PSNR and SSIM in this domain -- float: the tensors as they are; u8: the 8-bit '
+                        'picture that --save_test_images writes; y8: the luma of that picture')
+    p.add_argument('--eval_shave', type=int, default=None, metavar='N',
+                   help='test(): leave a border of N pixels out of the --eval_domain numbers (tables use the scale factor)')
     return check_args(p.parse_args(argv))
 
 
@@ -78,6 +88,23 @@ def check_args(args):   # main.py:39-57
     if args.batch_size < 1:
         print('batch size must be larger than or equal to one')
     return args
+
+
+def report(net, args):
+    """One line per dataset after test(): PSNR and SSIM, the bicubic pair where --save_test_images produced it, and the
+    --eval_domain / --eval_shave numbers where asked for.  Without any of the three new flags nothing more is printed
+    than before them."""
+    if not (args.test_only or args.save_test_images or getattr(net, 'test_eval', None)):
+        return
+    for name, v in net.test_psnr.items():
+        parts = ['%s PSNR %.4f SSIM %.4f' % (args.model_name, v, net.test_ssim.get(name, float('nan')))]
+        if args.save_test_images and name in net.test_bicubic_psnr:
+            parts.insert(0, 'bicubic PSNR %.4f SSIM %.4f' % (net.test_bicubic_psnr[name],
+                                                            net.test_bicubic_ssim.get(name, float('nan'))))
+        ev = getattr(net, 'test_eval', {}).get(name)
+        if ev:
+            parts.append('%s shave %d: PSNR %.4f SSIM %.4f' % (ev['domain'], ev['shave'], ev['psnr'], ev['ssim']))
+        print('%s: %s' % (name, ', '.join(parts)))
 
 
 def main(argv=None):
@@ -93,13 +120,10 @@ def main(argv=None):
     if args.test_single:                     # main.py:102: net.test_single(img_fn)
         print(net.test_single(args.test_single))
         return net
-    net.train()                              # main.py:96
-    if args.save_test_images:
-        net.test(save_images=True)
-        for name, v in net.test_bicubic_psnr.items():
-            print('%s: bicubic PSNR %.4f, %s PSNR %.4f' % (name, v, args.model_name, net.test_psnr.get(name, float('nan'))))
-    else:
-        net.test()                           # main.py:99
+    if not args.test_only:
+        net.train()                          # main.py:96
+    net.test(save_images=True) if args.save_test_images else net.test()   # main.py:99
+    report(net, args)
     return net
 
 

@@ -55,8 +55,8 @@ __host__ __device__ __forceinline__ void ycc_to_rgb_px(const int16_t* inv, int y
 }
 
 // ToPILImage after clamp(0, 1) (edsr.py:305-306): pic.mul(255).byte() -- fp32 product, truncation; NaN -> 0 (fmaxf
-// returns its non-NaN operand)
-__device__ __forceinline__ unsigned quant_u8(float v) {
+// returns its non-NaN operand).  Host too: srk_ssim_host quantises with the very expression.
+__host__ __device__ __forceinline__ unsigned quant_u8(float v) {
   return (unsigned)(fminf(fmaxf(v, 0.f), 1.f) * 255.0f);
 }
 

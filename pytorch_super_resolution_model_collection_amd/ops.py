@@ -1563,6 +1563,39 @@ def psnr(pred, gt):
     return out[0], out[1]
 
 
+def ssim(pred, gt, shave=0, domain='float'):
+    """SSIM (Wang et al. 2004: 11 x 11 Gaussian window, sigma 1.5, valid positions, fp64 moments) of pred against gt on
+    the device, with PSNR and MSE of the same pixels from the same pass: returns (ssim, psnr, mse) as 0-dim device
+    tensors, no host sync.  pred / gt: [N,C,H,W] or [C,H,W] CUDA tensors of any strides, read in place.
+    shave: pixels cropped from each side of both first.  domain: 'float' -- clamp(pred, 0, 1) against gt, what psnr()
+    compares; 'u8' -- both quantised like to_u8_image, the picture save_img writes; 'y8' -- that picture's Pillow luma
+    (three channels), or 'u8' for one channel.  include/srk.h: srk_ssim."""
+    lib = _lib.load()
+    require_cuda(pred, gt)
+    if pred.shape != gt.shape:
+        raise RuntimeError("ssim: pred %s vs gt %s" % (tuple(pred.shape), tuple(gt.shape)))
+    if domain not in _lib.SSIM_DOMAINS:
+        raise RuntimeError("ssim: domain %r is not one of %s" % (domain, sorted(_lib.SSIM_DOMAINS)))
+    p = pred.detach()
+    g = gt.detach()
+    if p.dim() == 3:
+        p, g = p.unsqueeze(0), g.unsqueeze(0)
+    if p.dim() != 4:
+        raise RuntimeError("ssim expects [N,C,H,W] or [C,H,W] tensors, got shape %s" % (tuple(pred.shape),))
+    n, c, h, w = p.shape
+    shave = int(shave)
+    if shave < 0 or min(h, w) - 2 * shave < 11:
+        raise RuntimeError("ssim: planes of %d x %d with shave %d leave %d x %d, under the 11 x 11 window"
+                           % (h, w, shave, h - 2 * shave, w - 2 * shave))
+    if domain == 'y8' and c not in (1, 3):
+        raise RuntimeError("ssim: domain 'y8' takes 1 or 3 channels, got %d" % c)
+    out = torch.empty(3, dtype=torch.float32, device=p.device)
+    ws = torch.empty(int(lib.srk_ssim_workspace_bytes()), dtype=torch.uint8, device=p.device)
+    check(lib.srk_ssim(ptr(p), _strides4(p), ptr(g), _strides4(g), n, c, h, w, shave, _lib.SSIM_DOMAINS[domain],
+                       ptr(out[0:1]), ptr(out[1:2]), ptr(out[2:3]), ptr(ws), stream_ptr()), "srk_ssim")
+    return out[0], out[1], out[2]
+
+
 def _channel_affine_raw(x, sub, div, clamp01=False):
     """y = (x - sub[c]) / div[c] per channel (utils.norm / utils.denorm, utils.py:219-239), same storage layout as x
     ([C,H,W] / [B,C,H,W] NCHW-contiguous or channels_last); bit-equal to torchvision's Normalize."""

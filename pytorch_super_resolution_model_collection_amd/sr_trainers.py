@@ -282,7 +282,7 @@ class _Trainer(object):
             return out[-1] if isinstance(out, tuple) else out
         return self._infer_tiled(x, geo, size, tile_batch)
 
-    def test(self, loader=None, save_images=False, tile=None):
+    def test(self, loader=None, save_images=False, tile=None, eval_domain=None, eval_shave=None):
         """Evaluation loop (espcn.py:173-215, edsr.py:196-250): forward + PSNR per image (computed on the device), over
         `loader`, else over every folder of `test_dataset` that exists under `data_dir` (data.get_test_set), else over
         seeded synthetic pairs.  Returns the list of PSNRs; `self.test_psnr` holds the per-dataset averages.
@@ -290,10 +290,27 @@ class _Trainer(object):
         <save_dir>/test_result/<dataset>/SR_result_<n>.png, and `self.test_bicubic_psnr` holds, per dataset, the
         average PSNR of the loader's bicubic image (the third item, where the loader yields one) against the target
         (edsr.py:257-261), computed by the same device kernel.
-        tile: None (args.tile, else one pass), a tile size in net-input pixels or 'auto': see test_single."""
+        tile: None (args.tile, else one pass), a tile size in net-input pixels or 'auto': see test_single.
+        Beside every PSNR goes the SSIM of the same two tensors (utils.SSIM, on the device): `self.test_ssim` holds the
+        per-dataset averages, with save_images `self.test_bicubic_ssim` the bicubic image's.  A pair smaller than the
+        11 x 11 window is left out of that average.
+        eval_domain / eval_shave (None: args.eval_domain / args.eval_shave where the args object has them): when either
+        is given, `self.test_eval[name] = {'domain', 'shave', 'psnr', 'ssim'}` holds the averages of ops.ssim's fused
+        outputs in that domain ('float', 'u8': the 8-bit picture, 'y8': its luma) with that border left out -- the
+        protocol of published tables.  The returned list and test_psnr do not depend on either."""
         if self.model is None:
             self.model = self.build_model().to(self.device)
             self.load_model()
+        if eval_domain is None:
+            eval_domain = getattr(self.args, 'eval_domain', None)
+        if eval_shave is None:
+            eval_shave = getattr(self.args, 'eval_shave', None)
+        want_eval = eval_domain is not None or eval_shave is not None
+        eval_domain = 'float' if eval_domain is None else eval_domain
+        eval_shave = 0 if eval_shave is None else int(eval_shave)
+
+        def fits(t, border=0):   # the window needs 11 x 11 pixels after the crop
+            return min(int(t.shape[-2]), int(t.shape[-1])) - 2 * border >= 11
         sources = []
         if loader is not None:
             sources.append(("loader", loader))
@@ -304,12 +321,14 @@ class _Trainer(object):
                     sources.append((name, ld))
             if not sources:
                 sources.append(("synthetic", synthetic_loader(self.kind, self.args, 2, self.device, 4321)))
-        psnrs, self.test_psnr = [], {}
+        psnrs, self.test_psnr, self.test_ssim = [], {}, {}
         if save_images:
-            self.test_bicubic_psnr = {}
+            self.test_bicubic_psnr, self.test_bicubic_ssim = {}, {}
+        if want_eval:
+            self.test_eval = {}
         for name, batches in sources:
-            mine = []
-            bicubic, img_num = [], 0
+            mine, mine_ssim, mine_eval = [], [], []
+            bicubic, bicubic_ssim, img_num = [], [], 0
             for batch in batches:
                 items = [batch] if torch.is_tensor(batch[0]) else list(zip(*batch))   # ragged test images come as lists
                 for item in items:
@@ -320,6 +339,10 @@ class _Trainer(object):
                         tgt = utils.shave(tgt, 8)
                     if out.shape == tgt.shape:
                         mine.append(utils.PSNR(out, tgt))   # 0-dim device tensors: nothing syncs inside the loop
+                        if fits(out):
+                            mine_ssim.append(utils.SSIM(out, tgt))
+                        if want_eval and fits(out, eval_shave):
+                            mine_eval.append(torch.stack(ops.ssim(out.float(), tgt.float(), eval_shave, eval_domain)[:2]))
                     if save_images:
                         img_num += 1
                         utils.save_img(out[0], img_num, save_dir=os.path.join(self.save_dir, 'test_result', str(name)))
@@ -327,6 +350,8 @@ class _Trainer(object):
                             bc_img = self._channels(item[2] if item[2].dim() == 4 else item[2].unsqueeze(0))[0]
                             if bc_img.shape == hr_img.shape:
                                 bicubic.append(utils.PSNR(bc_img.to(self.device), hr_img.to(self.device)))
+                                if fits(bc_img):
+                                    bicubic_ssim.append(utils.SSIM(bc_img.to(self.device), hr_img.to(self.device)))
             vals = [float(v) for v in torch.stack(mine).cpu()] if mine else []
             if vals:
                 self.test_psnr[name] = sum(vals) / len(vals)
@@ -334,6 +359,15 @@ class _Trainer(object):
             if bicubic:
                 bvals = [float(v) for v in torch.stack(bicubic).cpu()]
                 self.test_bicubic_psnr[name] = sum(bvals) / len(bvals)
+            for vals_dev, into in ((mine_ssim, self.test_ssim), (bicubic_ssim, getattr(self, 'test_bicubic_ssim', None))):
+                if vals_dev:
+                    svals = [float(v) for v in torch.stack(vals_dev).cpu()]
+                    into[name] = sum(svals) / len(svals)
+            if mine_eval:
+                ev = torch.stack(mine_eval).double().cpu()
+                self.test_eval[name] = {'domain': eval_domain, 'shave': eval_shave,
+                                        'psnr': sum(float(v) for v in ev[:, 1]) / len(ev),
+                                        'ssim': sum(float(v) for v in ev[:, 0]) / len(ev)}
         return psnrs
 
     def test_single(self, img, tile=None, tile_batch=None):

@@ -50,6 +50,16 @@ def PSNR(pred, gt):
     return ops.psnr(pred.float(), gt.to(pred.device).float())[0]
 
 
+def SSIM(pred, gt, shave=0, domain='float'):
+    """Structural similarity of pred against gt (ops.ssim: 11 x 11 Gaussian window, valid positions, mean over planes),
+    computed on the device and returned as a 0-dim DEVICE tensor, like PSNR.  shave crops that many pixels from each
+    side first; domain 'float' compares what PSNR compares, 'u8' the 8-bit picture save_img writes, 'y8' its luma."""
+    from . import ops
+    if not pred.is_cuda:
+        pred = pred.to("cuda")
+    return ops.ssim(pred.float(), gt.to(pred.device).float(), shave, domain)[0]
+
+
 def save_img_name(img_num, save_dir='', is_training=False):
     """utils.py:126-130: the file a result image goes to."""
     return save_dir + ('/SR_result_epoch_{:d}' if is_training else '/SR_result_{:d}').format(img_num) + '.png'
