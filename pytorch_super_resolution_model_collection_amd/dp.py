@@ -107,6 +107,7 @@ class DataParallel(object):
         gradient buffer to send after it.  A parameter is final after the last group that writes it (parameters no
         pending record writes are final already); ranges are maximal runs of final, unsent parameters, held back while
         shorter than `min_elems` unless nothing will follow."""
+        from .ops import WgradRecord
         flat = self.flat
         if min_elems is None:
             min_elems = self.min_bucket_elems
@@ -114,8 +115,8 @@ class DataParallel(object):
         spans = []   # (lo, hi, ready_after_group) per parameter, in buffer order
         ready = {}
         for k, recs in enumerate(groups):
-            for r in recs:
-                for t in (r[6], r[7]):
+            for r in map(WgradRecord._make, recs):   # (a plain 8-tuple in the record's field order is a record too)
+                for t in (r.dw, r.db):
                     if t is None:
                         continue
                     off = (t.data_ptr() - base) // 4

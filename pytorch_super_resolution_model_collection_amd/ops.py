@@ -5,6 +5,7 @@ torch tensors that merely OWN the device memory.  Activations are logically NCHW
 module surface, e.g. edsr.py:146-152) but stored channels_last (= dense NHWC, the kernels'
 layout).  Nothing in this file computes on the CPU and nothing falls back to ATen operators.
 """
+import collections
 import ctypes
 import os
 
@@ -465,7 +466,8 @@ DEFER_WGRAD = True
 # EDSR shard (8 MB per layer) defers ~19 layers at a time, a 128-patch batch (67 MB per layer) falls back to
 # one-or-two-layer groups, i.e. the per-layer behaviour.
 DEFER_MAX_BYTES = 160 << 20
-_PENDING = []                      # [(key, desc, x, dy, y_mask, slope, wacc, bacc)] in backward order
+WgradRecord = collections.namedtuple("WgradRecord", "key desc x dy mask_y slope dw db")
+_PENDING = []                      # WgradRecords in backward order (dw / db: views of the flat gradient buffer)
 _DEFER = {"queued": False, "manual": 0, "bytes": 0}
 
 
@@ -492,7 +494,7 @@ def pending_wgrad_groups(max_layers=None):
     cap = max_layers or 0
     groups, open_by_key = [], {}
     for rec in _PENDING:
-        key, wptr = rec[0], rec[6].data_ptr()
+        key, wptr = rec.key, rec.dw.data_ptr()
         g = open_by_key.get(key)
         if g is None or wptr in g[1] or (cap and len(g[0]) >= cap):
             g = ([], set())
@@ -508,15 +510,15 @@ def launch_wgrad_group(recs):
     gradient views)."""
     lib = _lib.load()
     n = len(recs)
-    d = recs[0][1]
+    d = recs[0].desc
     vp = ctypes.c_void_p
-    xs = (vp * n)(*[r[2].data_ptr() for r in recs])
-    dys = (vp * n)(*[r[3].data_ptr() for r in recs])
-    masks = (BwdMask * n)(*[BwdMask(None if r[4] is None else r[4].data_ptr(), r[5]) for r in recs])
-    dws = (vp * n)(*[r[6].data_ptr() for r in recs])
-    has_bias = recs[0][7] is not None
-    dbs = (vp * n)(*[r[7].data_ptr() for r in recs]) if has_bias else None
-    dev = recs[0][3].device
+    xs = (vp * n)(*[r.x.data_ptr() for r in recs])
+    dys = (vp * n)(*[r.dy.data_ptr() for r in recs])
+    masks = (BwdMask * n)(*[BwdMask(None if r.mask_y is None else r.mask_y.data_ptr(), r.slope) for r in recs])
+    dws = (vp * n)(*[r.dw.data_ptr() for r in recs])
+    has_bias = recs[0].db is not None
+    dbs = (vp * n)(*[r.db.data_ptr() for r in recs]) if has_bias else None
+    dev = recs[0].dy.device
     ws_bytes = int(lib.srk_conv2d_backward_weight_grouped_workspace_bytes(ctypes.byref(d), n))
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
     check(lib.srk_conv2d_backward_weight_grouped(ctypes.byref(d), n, xs, dys, masks, dws, dbs, 1.0, ptr(ws), ws.numel(),
@@ -642,30 +644,11 @@ class _Conv2d(torch.autograd.Function):
         mref = ctypes.byref(mask) if mask is not None else None
         dx = dw = db = None
         need_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
-        wref, bref = ctx.weight_ref, ctx.bias_ref
-        wacc = getattr(wref, "_srk_grad", None)
-        bacc = getattr(bref, "_srk_grad", None) if ctx.has_bias else None
-        flat_mode = wacc is not None and (not ctx.has_bias or bacc is not None)
-        if need_w and flat_mode:
-            # flat-buffer mode: accumulate straight into the (pre-zeroed) gradient views -- recorded for the grouped
-            # deferred launch, or launched here before the data gradient
-            if DEFER_WGRAD:
-                key = (d.N, d.H, d.W, d.Cin, d.OH, d.OW, d.Cout, d.KH, d.KW, d.stride, d.pad, d.transposed, d.out_pad,
-                       d.algo, d.dy_ps_r, bacc is not None, str(dy.device))
-                _PENDING.append((key, d, x, dyc, y if mask is not None else None,
-                                 cfg.slope if cfg.act == ACT_LRELU else 0.0, wacc, bacc))
-                _DEFER["bytes"] += 4 * (x.numel() + dyc.numel())
-                if _DEFER["bytes"] > DEFER_MAX_BYTES:
-                    flush_wgrads()   # (also under manual_wgrad_flush: these gradients are simply final before the exchange)
-                elif not _DEFER["queued"]:   # first record of this backward pass: flush when the engine finishes it
-                    _DEFER["queued"] = True
-                    torch.autograd.Variable._execution_engine.queue_callback(_auto_flush)
-            else:
-                ws_bytes = lib.srk_conv2d_backward_weight_workspace_bytes(ctypes.byref(d))
-                ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=dy.device)
-                check(lib.srk_conv2d_backward_weight(ctypes.byref(d), ptr(x), ptr(dyc), mref, ptr(wacc), ptr(bacc),
-                                                     1.0, ptr(ws), ws.numel(), stream_ptr()),
-                      "srk_conv2d_backward_weight")
+        wref, bref = ctx.weight_ref, (ctx.bias_ref if ctx.has_bias else None)
+        wmask = (y if mask is not None else None, cfg.slope if cfg.act == ACT_LRELU else 0.0)
+        flat_mode = _flat_grads(wref, bref) is not None
+        if flat_mode:   # recorded for the grouped deferred launch, or launched here: before the data gradient
+            _weight_grad(d, x, dyc, wref, bref, need_w, *wmask)
         if ctx.needs_input_grad[0]:
             plan_wpb = ctx.wpb if cfg.ps_r <= 1 else ctx_wpb
             wpb = plan_wpb if plan_wpb is not None else pack_weight_bwd(weight, cfg.transposed, d.dy_ps_r)
@@ -692,14 +675,8 @@ class _Conv2d(torch.autograd.Function):
             else:
                 check(lib.srk_conv2d_backward_data(ctypes.byref(d), ptr(dyc), ptr(wpb), ptr(dx), mref, ptr(add_to),
                                                    stream_ptr()), "srk_conv2d_backward_data")
-        if need_w and not flat_mode:
-            ws_bytes = lib.srk_conv2d_backward_weight_workspace_bytes(ctypes.byref(d))
-            ws = torch.empty(max(int(ws_bytes), 16), dtype=torch.uint8, device=dy.device)
-            dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
-            db = torch.empty(d.Cout, dtype=torch.float32, device=dy.device) if ctx.has_bias else None
-            check(lib.srk_conv2d_backward_weight(ctypes.byref(d), ptr(x), ptr(dyc), mref, ptr(dw), ptr(db), 0.0,
-                                                 ptr(ws), ws.numel(), stream_ptr()),
-                  "srk_conv2d_backward_weight")
+        if not flat_mode:   # gradients autograd owns: after the data gradient
+            dw, db = _weight_grad(d, x, dyc, wref, bref, need_w, *wmask)
         return dx, dw, db, dres, None, None, None, None
 
 
@@ -721,19 +698,29 @@ LINEAR_TAIL_X3 = True
 RES2 = True   # False: residual blocks always run their two convs as separate launches
 
 
-def _weight_grad(d, x, dyc, weight, bias, need_w):
-    """Weight / bias gradient of one conv without an activation mask: recorded for the grouped deferred launch (flat
-    gradient buffers) or computed now.  Returns (dw, db) for autograd (None, None when accumulated in place)."""
+def _flat_grads(weight, bias):
+    """(dw, db) views of the flat gradient buffer (optim.FlatParams) the kernels accumulate into, or None when autograd
+    owns this layer's gradients."""
+    wacc = getattr(weight, "_srk_grad", None)
+    bacc = getattr(bias, "_srk_grad", None) if bias is not None else None
+    return (wacc, bacc) if wacc is not None and (bias is None or bacc is not None) else None
+
+
+def _weight_grad(d, x, dyc, weight, bias, need_w, mask_y=None, slope=0.0):
+    """Weight / bias gradient of one conv -- the one place that records or launches one.  mask_y / slope: the output of
+    a fused (leaky) ReLU whose mask the kernel applies to dyc.  Flat gradient buffers: recorded for the grouped deferred
+    launch (flushed when the pass's records exceed DEFER_MAX_BYTES -- also under manual_wgrad_flush: those gradients are
+    simply final before the exchange -- else by the engine callback the first record of a pass queues), or accumulated
+    now (beta = 1).  Otherwise computed into fresh tensors.  Returns (dw, db) for autograd, (None, None) when
+    accumulated in place."""
     if not need_w:
         return None, None
     lib = _lib.load()
-    wacc = getattr(weight, "_srk_grad", None)
-    bacc = getattr(bias, "_srk_grad", None) if bias is not None else None
-    flat_mode = wacc is not None and (bias is None or bacc is not None)
-    if flat_mode and DEFER_WGRAD:
+    acc = _flat_grads(weight, bias)
+    if acc is not None and DEFER_WGRAD:
         key = (d.N, d.H, d.W, d.Cin, d.OH, d.OW, d.Cout, d.KH, d.KW, d.stride, d.pad, d.transposed, d.out_pad,
-               d.algo, d.dy_ps_r, bacc is not None, str(dyc.device))
-        _PENDING.append((key, d, x, dyc, None, 0.0, wacc, bacc))
+               d.algo, d.dy_ps_r, acc[1] is not None, str(dyc.device))
+        _PENDING.append(WgradRecord(key, d, x, dyc, mask_y, slope, *acc))
         _DEFER["bytes"] += 4 * (x.numel() + dyc.numel())
         if _DEFER["bytes"] > DEFER_MAX_BYTES:
             flush_wgrads()
@@ -743,15 +730,16 @@ def _weight_grad(d, x, dyc, weight, bias, need_w):
         return None, None
     ws = torch.empty(max(int(lib.srk_conv2d_backward_weight_workspace_bytes(ctypes.byref(d))), 16), dtype=torch.uint8,
                      device=dyc.device)
-    if flat_mode:
-        check(lib.srk_conv2d_backward_weight(ctypes.byref(d), ptr(x), ptr(dyc), None, ptr(wacc), ptr(bacc), 1.0,
-                                             ptr(ws), ws.numel(), stream_ptr()), "srk_conv2d_backward_weight")
-        return None, None
-    dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
-    db = torch.empty(d.Cout, dtype=torch.float32, device=dyc.device) if bias is not None else None
-    check(lib.srk_conv2d_backward_weight(ctypes.byref(d), ptr(x), ptr(dyc), None, ptr(dw), ptr(db), 0.0, ptr(ws),
+    if acc is not None:
+        dw, db, beta = acc + (1.0,)
+    else:
+        dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
+        db = torch.empty(d.Cout, dtype=torch.float32, device=dyc.device) if bias is not None else None
+        beta = 0.0
+    mask = ctypes.byref(BwdMask(ptr(mask_y), slope)) if mask_y is not None else None
+    check(lib.srk_conv2d_backward_weight(ctypes.byref(d), ptr(x), ptr(dyc), mask, ptr(dw), ptr(db), beta, ptr(ws),
                                          ws.numel(), stream_ptr()), "srk_conv2d_backward_weight")
-    return dw, db
+    return (None, None) if acc is not None else (dw, db)
 
 
 def resblock2_applicable(x, w1, w2):
@@ -2005,38 +1993,10 @@ class _Recursion(torch.autograd.Function):
             mask = BwdMask(ptr(sl[1]), 0.0)
             check(lib.srk_conv2d_backward_data(ctypes.byref(d1), ptr(us[0]), ptr(wpb), ptr(dh0), ctypes.byref(mask), None,
                                                stream_ptr()), "srk_conv2d_backward_data")
-        dw = db = None
-        has_bias = ctx.bias_ref is not None
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            # ONE weight gradient over the stacked batch: x = H[0:D], dy = U, mask = relu'(H[1:D+1])
-            xs, ys = H[:D * n], H[n:]
-            dD = _make_desc(xs.shape, weight, cfg, "bwd")
-            wacc = getattr(ctx.weight_ref, "_srk_grad", None)
-            bacc = getattr(ctx.bias_ref, "_srk_grad", None) if has_bias else None
-            flat_mode = wacc is not None and (not has_bias or bacc is not None)
-            if flat_mode and DEFER_WGRAD:
-                key = (dD.N, dD.H, dD.W, dD.Cin, dD.OH, dD.OW, dD.Cout, dD.KH, dD.KW, dD.stride, dD.pad, dD.transposed,
-                       dD.out_pad, dD.algo, dD.dy_ps_r, bacc is not None, str(U.device))
-                _PENDING.append((key, dD, xs, U, ys, 0.0, wacc, bacc))
-                _DEFER["bytes"] += 4 * (xs.numel() + U.numel())
-                if _DEFER["bytes"] > DEFER_MAX_BYTES:
-                    flush_wgrads()
-                elif not _DEFER["queued"]:
-                    _DEFER["queued"] = True
-                    torch.autograd.Variable._execution_engine.queue_callback(_auto_flush)
-            else:
-                mask = BwdMask(ptr(ys), 0.0)
-                ws = torch.empty(max(int(lib.srk_conv2d_backward_weight_workspace_bytes(ctypes.byref(dD))), 16),
-                                 dtype=torch.uint8, device=U.device)
-                if flat_mode:
-                    dwp, dbp, beta = wacc, bacc, 1.0
-                else:
-                    dw = torch.empty_like(weight, memory_format=torch.contiguous_format)
-                    db = torch.empty(dD.Cout, dtype=torch.float32, device=U.device) if has_bias else None
-                    dwp, dbp, beta = dw, db, 0.0
-                check(lib.srk_conv2d_backward_weight(ctypes.byref(dD), ptr(xs), ptr(U), ctypes.byref(mask), ptr(dwp),
-                                                     ptr(dbp), beta, ptr(ws), ws.numel(), stream_ptr()),
-                      "srk_conv2d_backward_weight")
+        # ONE weight gradient over the stacked batch: x = H[0:D], dy = U, mask = relu'(H[1:D+1])
+        xs, ys = H[:D * n], H[n:]
+        dw, db = _weight_grad(_make_desc(xs.shape, weight, cfg, "bwd"), xs, U, ctx.weight_ref, ctx.bias_ref,
+                              ctx.needs_input_grad[1] or (ctx.bias_ref is not None and ctx.needs_input_grad[2]), ys, 0.0)
         return dh0, dw, db, None, None, None
 
 

@@ -192,26 +192,17 @@ class _Trainer(object):
     # The reference's loop launches ~110 (EDSR) small kernels per iteration; at its default batch sizes the step is a
     # few hundred microseconds of GPU work behind 1.5+ ms of host launches.  The FIRST batch of a shape runs eagerly (a
     # real training step, and every lazy initialisation happens outside a capture), the next one is captured
-    # (trainers.GraphedStep: zero_grad + filter packing + forward + loss + backward + optimizer as one graph, split at
+    # (trainers.capture_step: zero_grad + filter packing + forward + loss + backward + optimizer as one graph, split at
     # the gradient exchange under data parallelism) and replayed from then on.  A batch of another shape (the ragged
     # last one) runs eagerly; a learning-rate decay needs nothing (the rate is a device scalar).  --eager turns it off.
-    _GRAPH_LOSS = {"edsr": (ops.l1_loss, None), "vdsr": (ops.mse_loss, 0.4), "srcnn": (ops.mse_loss, None),
-                   "fsrcnn": (ops.mse_loss, None), "espcn": (ops.mse_loss, None)}
-
+    # A step without segments (LapSRN's two losses, DRCN) cannot be split: it is captured on one GPU only.
     def _step(self, eager_step, tensors):
         auto = getattr(self, "_auto", None)
         if auto is None or auto.eager is not eager_step:
-            spec = self._GRAPH_LOSS.get(self.kind)
-
             single = self.dp is None or not self.dp.active
-
-            def make(ts):
-                if spec is None:    # steps with their own loss structure (LapSRN's two Charbonnier terms): the eager step
-                    return trainers.GraphedFn(eager_step, ts, warmup=0, flats=[self.flat])   # function itself, one GPU
-                return trainers.GraphedStep(self.model, self.optimizer, spec[0], ts, dp=self.dp, clip=spec[1], warmup=0)
-
-            auto = self._auto = trainers.AutoGraph(eager_step, make,
-                                                   enabled=(spec is not None or single) and not getattr(self.args, "eager", False))
+            auto = self._auto = trainers.AutoGraph(
+                eager_step, lambda ts: trainers.capture_step(eager_step, ts, warmup=0, flats=[self.flat]),
+                enabled=(hasattr(eager_step, "segments") or single) and not getattr(self.args, "eager", False))
         return auto(*tensors)
 
     @property
@@ -548,15 +539,16 @@ class SRGAN(_Trainer):
                 lr_img, hr_img = self._channels(*batch[:2])
                 yield norm(lr_img.to(self.device, non_blocking=True)), norm(hr_img.to(self.device, non_blocking=True))
 
+        def graphed(eager_step, flats):
+            return trainers.AutoGraph(eager_step, lambda ts: trainers.capture_step(eager_step, ts, warmup=0, flats=flats),
+                                      enabled=not bool(getattr(self.args, "eager", False)))
+
         # generator pre-training (srgan.py:179-219): 50 epochs of MSE unless a pre-trained generator checkpoint loads
         self.epoch_pretrain = int(getattr(self.args, "epoch_pretrain", 50)) if pretrain_epochs is None else pretrain_epochs
         if self.load_model(is_pretrain=True):
             g_flat.mark_changed()      # parameters changed behind the optimizer's back: re-pack filters
         else:
-            eager = bool(getattr(self.args, "eager", False))
-            pre_step = trainers.AutoGraph(
-                trainers.mse_step(self.G, g_opt, g_dp),
-                lambda ts: trainers.GraphedStep(self.G, g_opt, ops.mse_loss, ts, dp=g_dp, warmup=0), enabled=not eager)
+            pre_step = graphed(trainers.mse_step(self.G, g_opt, g_dp), [g_flat])
             for epoch in range(self.epoch_pretrain):
                 for y_, x_ in batches(77 + epoch):
                     pre_step(y_, x_)
@@ -564,16 +556,9 @@ class SRGAN(_Trainer):
             if self.rank == 0:
                 self.save_model(is_pretrain=True)
         # the adversarial step (two models, two optimizers) as one hipGraph; data parallel: graphs split at the two exchanges
-        eager_step = trainers.srgan_step(self.G, self.D, g_opt, d_opt, g_dp, d_dp, lazy_pack=True,
-                                         prune_dead_grads=bool(getattr(self.args, "prune_dead_grads", False)))
-
-        def make_graph(ts):
-            if g_dp is not None and g_dp.active:
-                return trainers.GraphedSegments(trainers.srgan_segments(self.G, self.D, g_opt, d_opt, g_dp, d_dp, lazy_pack=True), ts,
-                                                warmup=0)
-            return trainers.GraphedFn(eager_step, ts, warmup=0, flats=[g_flat, d_flat])
-
-        step = trainers.AutoGraph(eager_step, make_graph, enabled=not bool(getattr(self.args, "eager", False)))
+        step = graphed(trainers.srgan_step(self.G, self.D, g_opt, d_opt, g_dp, d_dp, lazy_pack=True,
+                                           prune_dead_grads=bool(getattr(self.args, "prune_dead_grads", False))),
+                       [g_flat, d_flat])
         hist = []
         for epoch in range(self.num_epochs):
             apply_lr_decay("srgan", epoch, g_opt, d_opt)   # srgan.py:239-244: both learning rates /10 every 20 epochs
@@ -648,7 +633,7 @@ class DRCN(_Trainer):
 
     def build_step(self):
         """Adam over the model's flat buffer and over w (drcn.py:108-111), alpha and the weight-decay value as device
-        scalars the (captured) head reads; the base loop replays the step as a graph (trainers.GraphedFn)."""
+        scalars the (captured) head reads; the base loop replays the step as one graph (trainers.capture_step)."""
         self.flat = optim.FlatParams(self.model)
         self.optimizer = optim.make_optimizer("drcn", self.flat, self.lr)
         self.w_optimizer = optim.TensorAdam(self.model.w, self.lr)

@@ -1,11 +1,14 @@
 """Train-step bodies of the reference's trainers on the MI355X path.
 
-Each `*_step` builder returns a closure step(*batch) -> device loss tensor(s) that performs
+A train step is a list of SEGMENTS, [(fn(*batch) -> out, dp or None), ...]: the step
     zero_grad -> forward -> loss -> backward -> [RCCL all-reduce] -> [clip] -> optimizer step
-with the same op order, loss and hyper-parameters as the cited reference lines, and with NO host
-synchronisation (the reference syncs every iteration through loss.data[0], edsr.py:158).
-`GraphedStep` captures the forward+backward and the optimizer parts into hipGraphs so a step is
-two graph launches (+ the all-reduce) instead of ~200 kernel launches from Python.
+cut behind every backward pass whose gradients a DataParallel has to exchange.  `eager_step(segments)` is the closure
+step(*batch) -> device loss tensor(s) that runs them in order (an exchange after each segment with a dp); every `*_step`
+builder returns such a closure, with the same op order, loss and hyper-parameters as the cited reference lines and with
+NO host synchronisation (the reference syncs every iteration through loss.data[0], edsr.py:158).  `GraphedSegments`
+captures the same segments as hipGraphs -- one graph on a single GPU, graphs split at the exchanges under data
+parallelism -- so the eager, the one-graph and the split-graph form of a step are one definition.  `GraphedFn` (any
+function, one graph), `GraphedStep` (a loss step) and `capture_step` (any eager step) are its callers.
 """
 import contextlib
 import gc
@@ -58,14 +61,19 @@ def _static_buffers(example_inputs):
     return out
 
 
+def _active(dp):
+    return dp is not None and dp.active
+
+
 def _backward(loss, dp):
-    """loss.backward() of the reference (edsr.py:154 ...).  Single GPU: the deferred weight gradients are launched
-    (grouped) when the autograd engine finishes the pass.  Data parallel: they stay pending so that dp.exchange() can
-    interleave the grouped launches with the gradient buckets; the backward is seeded with 1/world."""
+    """loss.backward() of the reference (edsr.py:154 ...) for one loss or a list of losses (lapsrn.py:196-197: several
+    backward calls into the same gradients).  Single GPU: the deferred weight gradients are launched (grouped) when the
+    autograd engine finishes the pass.  Data parallel: they stay pending so that dp.exchange() can interleave the grouped
+    launches with the gradient buckets; the backward is seeded with 1/world."""
     # (premasked_gradients: a train step reads parameter gradients only, so activation gradients may travel pre-masked)
-    if dp is not None and dp.active:
+    if _active(dp):
         with ops.manual_wgrad_flush(), ops.premasked_gradients():
-            loss.backward(dp.loss_seed)
+            ops.backward(loss, dp.loss_seed)
     else:
         with ops.premasked_gradients():
             ops.backward(loss)   # seeded with the persistent ones tensor: no fill, no scale pass (ops.unit_seed)
@@ -75,59 +83,70 @@ def _backward(loss, dp):
 def _seeded(dp):
     """Context for computing a loss that `_backward(loss, dp)` will seed: under data parallelism the 1/world seed is
     folded into the loss gradient by the loss kernel itself (ops.loss_seed)."""
-    if dp is not None and dp.active:
+    if _active(dp):
         return ops.loss_seed(1.0 / dp.world, dp.loss_seed)
     return contextlib.nullcontext()
 
 
-def mse_step(model, opt, dp=None, clip=None):
-    """srcnn.py:127-131 / fsrcnn.py:153-157 / vdsr.py:143-150 (clip = 0.4)."""
-    def step(inp, target):
+def eager_step(segments):
+    """The eager form of a step given as segments: every fn in order, dp.exchange() behind a segment that has a dp (the
+    weight gradients its backward left pending and the all-reduce; without an active dp a no-op flush).  Returns what
+    the last fn returned.  `step.segments` keeps the definition, so a captured form is built from the closure alone."""
+    def step(*batch):
+        out = None
+        for fn, dp in segments:
+            out = fn(*batch)
+            if dp is not None:
+                dp.exchange()
+        return out
+    step.segments = segments
+    return step
+
+
+def loss_segments(model, opt, loss_fn, dp=None, clip=None):
+    """The plain loss step, loss_fn(model(input), *targets), cut at its gradient exchange:
+    [(zero_grad + seeded loss + backward, dp), ([clip] + optimizer step, None)]."""
+    out = []
+
+    def fwd_bwd(inp, *targets):
         opt.zero_grad()
         with _seeded(dp):
-            loss = ops.mse_loss(model(inp), target)
+            loss = loss_fn(model(inp), *targets)
         _backward(loss, dp)
-        if dp is not None:
-            dp.allreduce_grads()
+        out.append(loss)
+        return loss
+
+    def update(*batch):
         if clip is not None:
             opt.clip_grad_norm(clip)
         opt.step()
-        return loss
-    return step
+        return out.pop()
+
+    return [(fwd_bwd, dp), (update, None)]
+
+
+def mse_step(model, opt, dp=None, clip=None):
+    """srcnn.py:127-131 / fsrcnn.py:153-157 / vdsr.py:143-150 (clip = 0.4)."""
+    return eager_step(loss_segments(model, opt, ops.mse_loss, dp, clip))
 
 
 def l1_step(model, opt, dp=None):
     """edsr.py:151-155"""
-    def step(inp, target):
-        opt.zero_grad()
-        with _seeded(dp):
-            loss = ops.l1_loss(model(inp), target)
-        _backward(loss, dp)
-        if dp is not None:
-            dp.allreduce_grads()
-        opt.step()
-        return loss
-    return step
+    return eager_step(loss_segments(model, opt, ops.l1_loss, dp))
 
 
 def lapsrn_step(model, opt, dp=None):
-    """lapsrn.py:190-199: two Charbonnier losses, two backward calls into the same gradients."""
+    """lapsrn.py:190-199: two Charbonnier losses, two backward calls into the same gradients.  A plain closure without
+    segments: it cannot be split at its exchange, so under data parallelism it is never captured."""
     def step(inp, target2x, target4x):
         opt.zero_grad()
         hr2, hr4 = model(inp)
         with _seeded(dp):
             l1 = ops.charbonnier_loss(hr2, target2x)
             l2 = ops.charbonnier_loss(hr4, target4x)
-        seed = dp.loss_seed if (dp is not None and dp.active) else None
-        if seed is not None:
-            with ops.manual_wgrad_flush():
-                with ops.premasked_gradients():
-                    torch.autograd.backward([l1, l2], [seed, seed])
-        else:
-            with ops.premasked_gradients():
-                ops.backward([l1, l2])
+        _backward([l1, l2], dp)
         if dp is not None:
-            dp.allreduce_grads()
+            dp.exchange()
         opt.step()
         return l1, l2
     return step
@@ -154,9 +173,16 @@ def drcn_step(model, opt, w_opt, alpha_dev, beta, reg_dev=None):
 
 
 def srgan_step(G, D, g_opt, d_opt, g_dp=None, d_dp=None, feature_extractor=None, lazy_pack=False, prune_dead_grads=False):
-    """srgan.py:249-310 with [B,1] labels.  As in the reference the D step back-propagates through G
-    (G is not detached, srgan.py:279) and the G step accumulates into D's gradients, which the
-    next D step's zero_grad discards.
+    """srgan.py:249-310 with [B,1] labels, as the eager closure of `srgan_segments` (see there for the arguments)."""
+    return eager_step(srgan_segments(G, D, g_opt, d_opt, g_dp, d_dp, lazy_pack, feature_extractor, prune_dead_grads))
+
+
+def srgan_segments(G, D, g_opt, d_opt, g_dp=None, d_dp=None, lazy_pack=False, feature_extractor=None,
+                   prune_dead_grads=False):
+    """The adversarial step, srgan.py:249-310 with [B,1] labels, cut at its two gradient exchanges:
+    [(D forward/backward, d_dp), (D update + G forward/backward, g_dp), (G update, None)] -> (d_loss, g_loss).
+    As in the reference the D step back-propagates through G (G is not detached, srgan.py:279) and the G step accumulates
+    into D's gradients, which the next D step's zero_grad discards.
     `feature_extractor` (models.FeatureExtractor): adds the reference's VGG content term 6e-3 * MSE(vgg(norm(recon.data)),
     vgg(norm(hr)).detach()) to the reported G loss (srgan.py:301-308).  Both operands are detached in the reference,
     so the term changes the logged scalar only — never a gradient; without an extractor the step
@@ -170,9 +196,10 @@ def srgan_step(G, D, g_opt, d_opt, g_dp=None, d_dp=None, feature_extractor=None,
     D_optimizer.zero_grad(), srgan.py:272).  With the flag the D step sees G's output detached and the G step runs D
     with its parameters frozen (data gradients only).  Parameters, optimizer states and BatchNorm statistics after the
     step are the faithful step's (up to the summation order inside the grouped weight-gradient launches, whose split
-    depends on how many layers share a launch); D's `.grad` then holds the D step's gradients only.  Single GPU / eager
-    DP path only (the DP graph segments keep the reference's execution)."""
+    depends on how many layers share a launch); D's `.grad` then holds the D step's gradients only.  The flag is
+    honoured by every form of the step, the split-graph data-parallel one included."""
     from . import utils
+    out = {}
     repack = "stale" if lazy_pack else "always"
     d_params = [p for p in D.parameters()] if prune_dead_grads else []
 
@@ -180,56 +207,15 @@ def srgan_step(G, D, g_opt, d_opt, g_dp=None, d_dp=None, feature_extractor=None,
         for p in d_params:
             p.requires_grad_(not flag)
 
-    def step(lr_img, hr_img):
+    def seg_d(lr_img, hr_img):
         b = lr_img.shape[0]
         real = ops.const_rows(1.0, b, lr_img.device)     # persistent label rows and srk_axpby loss sums: the captured
         fake = ops.const_rows(0.0, b, lr_img.device)     # step holds no ATen arithmetic node
         d_opt.zero_grad(repack=repack)
         recon_d = G(lr_img)      # (in grad mode either way: the same kernels and precision class as the reference path)
-        d_loss = ops.loss_sum(ops.bce_loss(D(hr_img), real),
-                              ops.bce_loss(D(recon_d.detach() if prune_dead_grads else recon_d), fake))
-        del recon_d
-        _backward(d_loss, d_dp)
-        if d_dp is not None:
-            d_dp.allreduce_grads()
-        d_opt.step()
-        g_opt.zero_grad(repack=repack)
-        recon = G(lr_img)
-        if prune_dead_grads:
-            freeze_d(True)
-            try:
-                gan_loss = ops.bce_loss(D(recon), real)
-            finally:
-                freeze_d(False)
-        else:
-            gan_loss = ops.bce_loss(D(recon), real)
-        g_loss = ops.loss_sum(ops.mse_loss(recon, hr_img), gan_loss, 1.0, 1e-3)
-        if feature_extractor is not None:
-            with torch.no_grad():   # srgan.py:301-305 (the inputs are already normalised once, as in the reference)
-                real_feature = feature_extractor(utils.norm(hr_img, vgg=True))
-                fake_feature = feature_extractor(utils.norm(recon.detach(), vgg=True))
-                vgg_loss = ops.mse_loss(fake_feature, real_feature)
-            g_loss = ops.loss_sum(g_loss, vgg_loss, 1.0, 6e-3)
-        _backward(g_loss, g_dp)
-        if g_dp is not None:
-            g_dp.allreduce_grads()
-        g_opt.step()
-        return d_loss, g_loss
-    return step
-
-
-def srgan_segments(G, D, g_opt, d_opt, g_dp=None, d_dp=None, lazy_pack=False):
-    """The adversarial step of `srgan_step` cut at its two gradient exchanges, for GraphedSegments:
-    [(D forward/backward, d_dp), (D update + G forward/backward, g_dp), (G update, None)].  lazy_pack: see srgan_step."""
-    out = {}
-    repack = "stale" if lazy_pack else "always"
-
-    def seg_d(lr_img, hr_img):
-        b = lr_img.shape[0]
-        real = ops.const_rows(1.0, b, lr_img.device)
-        fake = ops.const_rows(0.0, b, lr_img.device)
-        d_opt.zero_grad(repack=repack)
-        out["d"] = ops.loss_sum(ops.bce_loss(D(hr_img), real), ops.bce_loss(D(G(lr_img)), fake))
+        out["d"] = ops.loss_sum(ops.bce_loss(D(hr_img), real),
+                                ops.bce_loss(D(recon_d.detach() if prune_dead_grads else recon_d), fake))
+        del recon_d              # (a local, not in `out`: it dies before the D backward ends)
         _backward(out["d"], d_dp)
         return out["d"]
 
@@ -238,13 +224,25 @@ def srgan_segments(G, D, g_opt, d_opt, g_dp=None, d_dp=None, lazy_pack=False):
         d_opt.step()
         g_opt.zero_grad(repack=repack)
         recon = G(lr_img)
-        out["g"] = ops.loss_sum(ops.mse_loss(recon, hr_img), ops.bce_loss(D(recon), real), 1.0, 1e-3)
-        _backward(out["g"], g_dp)
-        return out["g"]
+        freeze_d(True)
+        try:
+            gan_loss = ops.bce_loss(D(recon), real)
+        finally:
+            freeze_d(False)
+        g_loss = ops.loss_sum(ops.mse_loss(recon, hr_img), gan_loss, 1.0, 1e-3)
+        if feature_extractor is not None:
+            with torch.no_grad():   # srgan.py:301-305 (the inputs are already normalised once, as in the reference)
+                real_feature = feature_extractor(utils.norm(hr_img, vgg=True))
+                fake_feature = feature_extractor(utils.norm(recon.detach(), vgg=True))
+                vgg_loss = ops.mse_loss(fake_feature, real_feature)
+            g_loss = ops.loss_sum(g_loss, vgg_loss, 1.0, 6e-3)
+        _backward(g_loss, g_dp)
+        out["g"] = g_loss
+        return g_loss
 
     def seg_u(lr_img, hr_img):
         g_opt.step()
-        return out["d"], out["g"]
+        return out.pop("d"), out.pop("g")
 
     return [(seg_d, d_dp), (seg_g, g_dp), (seg_u, None)]
 
@@ -329,22 +327,28 @@ def sync_batchnorm(module, group=None):
 
 
 class GraphedSegments(object):
-    """A data-parallel train step as hipGraphs split at the gradient exchanges.
+    """A train step as hipGraphs with static input buffers: THE capture of this package.
 
-    `segments` = [(fn(*inputs), dp or None), ...]: every fn is captured as one graph; a segment with a DataParallel
-    ends in a backward pass whose weight gradients were left pending (ops.manual_wgrad_flush): each pending launch
-    group becomes a small graph of its own, and at replay the groups run one after the other with the RCCL all-reduce
-    of the bucket each one completes issued (eagerly, async) right behind it — the bucket travels while the next
-    group computes.  Call with new batches (copied into the static buffers); returns what the last fn returned."""
+    `segments` = [(fn(*inputs), dp or None), ...] (see the module docstring): `warmup` eager steps on a side stream,
+    then every fn is captured as one graph (cut again at every statistics all-reduce under SyncBN: _Splitter).  A
+    segment with an active DataParallel ends in a backward pass whose weight gradients were left pending
+    (ops.manual_wgrad_flush): each pending launch group becomes a small graph of its own, and at replay the groups run
+    one after the other with the RCCL all-reduce of the bucket each one completes issued (eagerly, async) right behind
+    it — the bucket travels while the next group computes.  `flats`: the FlatParams the step updates, beside those of
+    its dps — their PackPlans and the packed-filter caches of no-grad forwards (layers._PackCache) are invalidated after
+    every replay, which changed the weights without optim.step()'s host bookkeeping, and what somebody else changed
+    between two replays is re-packed in front of the next (_repack_touched).  Call with new batches (copied into the
+    static buffers, `.static`); returns what the last fn returned."""
 
-    def __init__(self, segments, example_inputs, warmup=2, eager_step=None):
+    def __init__(self, segments, example_inputs, warmup=2, flats=()):
         self.static = _static_buffers(example_inputs)
         self.segments = segments
+        eager = eager_step(segments)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(warmup):
-                self._eager()
+                eager(*self.static)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.plan, pool = [], None
@@ -362,7 +366,7 @@ class GraphedSegments(object):
                     pool = g.pool()
                     g = [("graph", g)]
                 wgraphs, sends, keep = [], [], None
-                if dp is not None and dp.active:
+                if _active(dp):
                     keep = ops.pending_wgrad_groups(dp.trunk_chunk_layers)   # holds x / dy / mask tensors of graph `g` alive
                     sends = dp.plan(keep)
                     ops.drop_pending_wgrads()
@@ -374,19 +378,22 @@ class GraphedSegments(object):
                 else:
                     ops.flush_wgrads()
                 self.plan.append((g, dp, wgraphs, sends, keep))
-        self._flats = [dp.flat for _, dp in segments if dp is not None and hasattr(dp.flat, "mark_changed")]
+        self._flats = []
+        for f in list(flats) + [dp.flat for _, dp in segments if dp is not None]:
+            if hasattr(f, "mark_changed") and not any(f is g for g in self._flats):
+                self._flats.append(f)
         self._seen = {}
-        for f in self._flats:   # same host bookkeeping as after a replay
+        self._after_replay()   # same host bookkeeping as after a replay
+
+    def close(self):
+        """Drop the captured graphs now (outside any capture) instead of whenever the garbage collector finds them."""
+        self.plan = []
+
+    def _after_replay(self):
+        bump_weight_epoch()
+        for f in self._flats:
             f.mark_changed()
         _note_epochs(self._flats, self._seen)
-
-    def _eager(self):
-        out = None
-        for fn, dp in self.segments:
-            out = fn(*self.static)
-            if dp is not None:
-                dp.exchange()
-        return out
 
     def __call__(self, *batch):
         for s, b in zip(self.static, batch):
@@ -399,7 +406,7 @@ class GraphedSegments(object):
                     obj.replay()
                 else:
                     obj()
-            if dp is not None and dp.active:
+            if _active(dp):
                 works = []
                 if not wgraphs:
                     dp.send(sends[0] if sends else [(0, dp.flat.grad.numel())], works)
@@ -408,15 +415,52 @@ class GraphedSegments(object):
                     dp.send(ranges, works)
                 for w in works:
                     w.wait()
-        bump_weight_epoch()
-        for f in self._flats:
-            f.mark_changed()
-        _note_epochs(self._flats, self._seen)
+        self._after_replay()
         return self.out
 
 
+def _graph_segments(step):
+    """The segments an eager step is captured as: its own where one of them has an exchange to be cut at, else the whole
+    step as ONE graph (a single-GPU step stays one graph launch; a closure without segments cannot be split)."""
+    segments = getattr(step, "segments", None)
+    if segments and any(_active(dp) for _, dp in segments):
+        return segments
+    return [(step, None)]
+
+
+def capture_step(step, example_inputs, warmup=3, flats=()):
+    """The hipGraph form of an eager step (any closure of this module, or any function of tensors that is stream work
+    only): split at the gradient exchanges where it has segments with an active DataParallel, else one graph."""
+    return GraphedSegments(_graph_segments(step), example_inputs, warmup, flats)
+
+
+class GraphedFn(GraphedSegments):
+    """hipGraph capture of an arbitrary single-GPU step function of tensors (e.g. the two-model, two-optimizer SRGAN
+    step, `srgan_step` without data parallelism) as ONE graph.  Everything the step does must be stream work (no host
+    reads of device values), which holds for all steps of this package."""
+
+    def __init__(self, fn, example_inputs, warmup=3, flats=()):
+        super(GraphedFn, self).__init__([(fn, None)], example_inputs, warmup, flats)
+
+
+class GraphedStep(GraphedSegments):
+    """hipGraph capture of the loss step (`loss_segments`).
+
+    Single GPU: one graph = zero_grad + filter packing + forward + loss + backward (data-gradient chain, then the
+    grouped weight gradients) + [clip] + optimizer.  Data parallel: graph A (through the data-gradient chain), one small
+    graph per weight-gradient group with its gradient bucket's RCCL all-reduce issued behind it, then graph B = [clip] +
+    optimizer."""
+
+    def __init__(self, model, opt, loss_fn, example_inputs, dp=None, clip=None, warmup=3):
+        step = eager_step(loss_segments(model, opt, loss_fn, dp, clip))
+        super(GraphedStep, self).__init__(_graph_segments(step), example_inputs, warmup, [opt.flat])
+
+    seg = property(lambda self: self)   # (the split capture used to be a member of this name: `step.seg.plan` still reads)
+
+
 def build(kind, model, lr, dp_group=None, use_dp=False):
-    """(flat, optimizer, dp, step) for one of 'srcnn' | 'fsrcnn' | 'vdsr' | 'edsr' | 'lapsrn' | 'espcn'."""
+    """(flat, optimizer, dp, step) for one of 'srcnn' | 'fsrcnn' | 'vdsr' | 'edsr' | 'lapsrn' | 'espcn': the one place that
+    names the loss and the clip a kind trains with."""
     from .dp import DataParallel
     flat = FlatParams(model)
     opt = make_optimizer(kind, flat, lr)
@@ -432,77 +476,6 @@ def build(kind, model, lr, dp_group=None, use_dp=False):
     else:
         step = mse_step(model, opt, dp)
     return flat, opt, dp, step
-
-
-class GraphedStep(object):
-    """hipGraph capture of a train step with static input buffers.
-
-    Single GPU: one graph = zero_grad + filter packing + forward + loss + backward (data-gradient chain, then the
-    grouped weight gradients) + [clip] + optimizer.  Data parallel: GraphedSegments — graph A (through the data-gradient
-    chain), one small graph per weight-gradient group with its gradient bucket's RCCL all-reduce issued behind it, then
-    graph B = [clip] + optimizer.  Call with new batches; they are copied into the static buffers.
-    """
-
-    def __init__(self, model, opt, loss_fn, example_inputs, dp=None, clip=None, warmup=3):
-        self.model, self.opt, self.dp, self.clip = model, opt, dp, clip
-        self.loss_fn = loss_fn
-        self.seg = None
-        if dp is not None and dp.active:
-            self.seg = GraphedSegments([(self._fwd_bwd_args, dp), (self._update_args, None)], example_inputs, warmup=warmup)
-            self.static = self.seg.static
-            return
-        self.static = _static_buffers(example_inputs)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                self._fwd_bwd()
-                self._update()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph_a = torch.cuda.CUDAGraph()
-        with _no_gc_during_capture():
-            with _capture(self.graph_a):
-                self.loss = self._fwd_bwd()
-                self._update()
-
-    def close(self):
-        """Drop the captured graphs now (outside any capture) instead of whenever the garbage collector finds them."""
-        self.seg = None
-        self.graph_a = None
-
-    def _fwd_bwd_args(self, *static):
-        self.static = list(static)
-        self.loss = self._fwd_bwd()
-        return self.loss
-
-    def _update_args(self, *static):
-        self._update()
-        return self.loss
-
-    def _fwd_bwd(self):
-        self.opt.zero_grad()
-        with _seeded(self.dp):
-            loss = self.loss_fn(self.model(self.static[0]), *self.static[1:])
-        _backward(loss, self.dp)
-        return loss
-
-    def _update(self):
-        if self.clip is not None:
-            self.opt.clip_grad_norm(self.clip)
-        self.opt.step()
-
-    def __call__(self, *batch):
-        if self.seg is not None:
-            return self.seg(*batch)
-        for s, b in zip(self.static, batch):
-            if b is not s:
-                s.copy_(b, non_blocking=True)
-        self.graph_a.replay()
-        # the replayed optimizer kernel changed the weights without running optim.step()'s host bookkeeping: packed
-        # filters cached by no-grad forwards (layers._PackCache) and the PackPlan must not be reused
-        self.opt.flat.mark_changed()
-        return self.loss
 
 
 def _repack_touched(flats, seen):
@@ -521,50 +494,10 @@ def _note_epochs(flats, seen):
         seen[id(f)] = f.epoch
 
 
-class GraphedFn(object):
-    """hipGraph capture of an arbitrary single-GPU step function of tensors (e.g. the two-model, two-optimizer SRGAN
-    step, `srgan_step` without data parallelism): static input buffers, `warmup` eager calls on a side stream, one
-    graph; call with new batches (copied into the static buffers), returns the captured output tensors.  Everything
-    the step does must be stream work (no host reads of device values), which holds for all steps of this package."""
-
-    def __init__(self, fn, example_inputs, warmup=3, flats=()):
-        self.fn = fn
-        self.flats = list(flats)   # FlatParams the step updates (their PackPlans are invalidated after every replay)
-        self.static = _static_buffers(example_inputs)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):
-                fn(*self.static)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with _no_gc_during_capture():
-            with _capture(self.graph):
-                self.out = fn(*self.static)
-        self._seen = {}
-        for f in self.flats:   # same host bookkeeping as after a replay
-            f.mark_changed()
-        _note_epochs(self.flats, self._seen)
-
-    def __call__(self, *batch):
-        for s, b in zip(self.static, batch):
-            if b is not s:
-                s.copy_(b, non_blocking=True)
-        _repack_touched(self.flats, self._seen)
-        self.graph.replay()
-        # weights changed inside the graph: invalidate the packed-filter caches of no-grad forwards (see GraphedStep)
-        bump_weight_epoch()
-        for f in self.flats:
-            f.mark_changed()
-        _note_epochs(self.flats, self._seen)
-        return self.out
-
-
 class AutoGraph(object):
     """A train step that turns itself into a hipGraph.  The FIRST batch of a shape runs through `eager` (a real step, and
     every lazy initialisation happens outside a capture); the next batch of that shape is captured by
-    `make_graph(tensors)` (a GraphedStep / GraphedFn / GraphedSegments built with warmup=0 on that batch) and replayed
+    `make_graph(tensors)` (capture_step or one of the Graphed* classes, with warmup=0 on that batch) and replayed
     from then on.  Batches of another shape (the ragged last one of an epoch) run eagerly.  Learning rates are device
     scalars the optimizer kernels read (optim._Group: `group['lr'] /= 2` reaches them), so a decay needs no re-capture.
     `enabled=False`: always eager."""

@@ -483,6 +483,55 @@ def test_srgan_step_without_its_dead_gradients(gpu):
             assert torch.equal(a, b), (what, float((a - b).abs().max()), float(b.abs().max()))
 
 
+def test_srgan_step_is_its_segments_run_in_order(gpu):
+    """trainers.srgan_step is the eager closure of trainers.srgan_segments: the closure, and the segments run by hand
+    (in order, dp.exchange() behind every segment that has a dp) from equal starts, are the same code -- parameters,
+    optimizer states, BatchNorm statistics, gradients and losses after two steps must be bit-equal.
+    Shapes: bit equality of two runs needs a step that repeats itself bit for bit.  The gradient of a single-slope PReLU
+    is summed with one float atomicAdd per block of 2048 elements (k_act_bwd4), in whatever order the blocks arrive: up
+    to two blocks the sum does not depend on the order (a + b == b + a), from three on its last bit does -- at 64 filters
+    and four 8x8 patches two runs of the SAME closure differ by 1 ulp in the three PReLU slopes' gradients and Adam
+    moments (measured; nothing else differs).  8 filters and two 4x4 patches keep the largest PReLU output, the second
+    upsampler's [2, 8, 16, 16], at two blocks."""
+    pkg = _pkg()
+    res = {}
+    for mode in ("closure", "segments"):
+        G, D = pkg.SRGANGenerator(3, 8, 1), pkg.SRGANDiscriminator(3, 8, 16)
+        fill.fill_module(G, 31, 0.5)
+        fill.fill_module(D, 32, 0.5)
+        G.to(gpu).train()
+        D.to(gpu).train()
+        gflat, dflat = pkg.optim.FlatParams(G), pkg.optim.FlatParams(D)
+        g_opt = pkg.optim.make_optimizer("srgan_g", gflat, 1e-4)
+        d_opt = pkg.optim.make_optimizer("srgan_d", dflat, 1e-4)
+        g_dp, d_dp = pkg.dp.DataParallel(gflat), pkg.dp.DataParallel(dflat)   # (no process group: inactive, exchange = flush)
+        lr, hr = B((2, 3, 4, 4), 85).to(gpu), B((2, 3, 16, 16), 86).to(gpu)
+        assert hr.shape[0] * 8 * hr.shape[2] * hr.shape[3] <= 2 * 2048   # (the largest PReLU output: two blocks)
+        if mode == "closure":
+            step = pkg.trainers.srgan_step(G, D, g_opt, d_opt, g_dp, d_dp)
+        else:
+            segments = pkg.trainers.srgan_segments(G, D, g_opt, d_opt, g_dp, d_dp)
+            assert [dp for _, dp in segments] == [d_dp, g_dp, None]
+
+            def step(*batch):
+                out = None
+                for fn, dp in segments:
+                    out = fn(*batch)
+                    if dp is not None:
+                        dp.exchange()
+                return out
+        losses = [v.detach().clone() for _ in range(2) for v in step(lr, hr)]
+        torch.cuda.synchronize()
+        bn = [t for net in (G, D) for m in net.modules() if isinstance(m, torch.nn.BatchNorm2d)
+              for t in (m.running_mean.clone(), m.running_var.clone())]
+        states = [getattr(o, k).clone() for o in (g_opt, d_opt) for k in ("buf", "exp_avg", "exp_avg_sq", "step_dev")
+                  if getattr(o, k, None) is not None]
+        res[mode] = losses + [gflat.data.clone(), dflat.data.clone(), gflat.grad.clone(), dflat.grad.clone()] + bn + states
+    assert len(res["closure"]) == len(res["segments"]) > 8
+    for i, (a, b) in enumerate(zip(res["closure"], res["segments"])):
+        assert torch.equal(a, b), i
+
+
 @pytest.mark.parametrize("kind", ["edsr", "lapsrn", "srgan_d"])
 def test_merged_slab_reductions_equal_per_group_reductions(gpu, kind):
     """ops.flush_wgrads runs the slab reductions of all weight-gradient launch groups of a backward pass as ONE launch

@@ -41,8 +41,8 @@ try:
     for i in range(int(os.environ.get("NSTEPS", "4"))):
         torch.distributed.barrier(); t0 = time.perf_counter(); step(x, t); torch.cuda.synchronize()
         print("rank", rank, "step %d: %.2f ms" % (i, (time.perf_counter() - t0) * 1e3), flush=True)
-    if not os.environ.get("EAGER"): print("rank", rank, "sends per group:", [[(lo, hi - lo) for lo, hi in r] for _, _, _, r_all, _ in step.seg.plan for r in (r_all or [])], flush=True)
-    print("rank", rank, "edsr graph-split DP step ok, loss", float(step.loss), flush=True)
+    if not os.environ.get("EAGER"): print("rank", rank, "sends per group:", [[(lo, hi - lo) for lo, hi in r] for _, _, _, r_all, _ in step.plan for r in (r_all or [])], flush=True)
+    print("rank", rank, "edsr graph-split DP step ok, loss", float(step.out), flush=True)
 except Exception:
     traceback.print_exc(); sys.stdout.flush(); sys.stderr.flush(); os._exit(1)
 torch.distributed.barrier(); torch.distributed.destroy_process_group()

@@ -20,4 +20,4 @@ for rep in range(3):
     for _ in range(iters): g(x, t)
     e1.record(); torch.cuda.synchronize()
     best = min(best, e0.elapsed_time(e1) / iters)
-print("edsr x4 train step B=%d: %.3f ms/step (graph), %.1f patches/s, loss %.5f" % (B, best, B / best * 1e3, float(g.loss)))
+print("edsr x4 train step B=%d: %.3f ms/step (graph), %.1f patches/s, loss %.5f" % (B, best, B / best * 1e3, float(g.out)))
