@@ -562,6 +562,26 @@ int srk_tile_stitch_u8(const float* tiles, int64_t n_stride, int64_t c_stride, i
                        int oth, int otw, const int32_t* table, int nty, int ntx, int t0, int n, const uint8_t* cb,
                        const uint8_t* cr, uint8_t* out, int OH, int OW, void* stream);
 
+/* ---- x8 geometric self-ensemble (sr_trainers.py self_ensemble; csrc/dihedral.hip) -------------------------------
+ * (Added without a change of srk_version(): new entry points only, nothing existing changed.)
+ * Variant k = 4 m + r of a picture x is T_k(x) = rot90(flip of the last axis if m, r turns); the ensemble is
+ * E = (((((((y_0 + y_1) + y_2) + y_3) + y_4) + y_5) + y_6) + y_7) * 0.125 in fp32 with y_k = T_k^-1(net(T_k(x))).
+ *
+ * srk_dihedral_variants: fp32 pictures [N][C][H][W] through element strides (image, channel, row, pixel), C = 1 or 3 ->
+ *   out, dense channels-last, 8 N images in one allocation: first 4 N images of H x W, image 4 n + j = T_k(x[n]) with
+ *   k = (0, 2, 4, 6)[j]; then 4 N images of W x H, k = (1, 3, 5, 7)[j].  One launch.
+ * srk_dihedral_merge_f32: the net's outputs for the two groups, even [4N][C][oh][ow] and odd [4N][C][ow][oh], each
+ *   through four element strides (image, channel, row, pixel; NCHW or channels-last) -> E, dense [N][C][oh][ow].
+ * srk_dihedral_merge_u8: N = 1, writing the final interleaved 8-bit picture instead: cb == cr == NULL: out [oh][ow][C],
+ *   quantised like srk_float_to_u8_image; else C = 1 and cb / cr are dense 8-bit planes [oh][ow]: out [oh][ow][3] RGB,
+ *   Y quantised and converted like srk_ycc_to_rgb_u8.  The fp32 mean is never written. */
+int srk_dihedral_variants(const float* x, int64_t n_stride, int64_t c_stride, int64_t row_stride, int64_t px_stride, int N,
+                          int C, int H, int W, float* out, void* stream);
+int srk_dihedral_merge_f32(const float* even, const int64_t* even_strides, const float* odd, const int64_t* odd_strides, int N,
+                           int C, int oh, int ow, float* out, void* stream);
+int srk_dihedral_merge_u8(const float* even, const int64_t* even_strides, const float* odd, const int64_t* odd_strides, int C,
+                          int oh, int ow, const uint8_t* cb, const uint8_t* cr, uint8_t* out, void* stream);
+
 /* ---- steps either side of the nets ------------------------------------------------
  * utils.PSNR (utils.py:208-216): mse = mean((clamp(pred,0,1) - gt)^2) over all elements, *psnr_out = mse == 0 ? 100 :
  * 10*log10(1/mse), on the device (the reference copies both images to the host per test image).  pred / gt are

@@ -6,7 +6,9 @@ folders under --data_dir; --steps_per_epoch of them per epoch), --epoch_pretrain
 the file name; no training) and --save_test_images (test() also writes every result image and reports the bicubic PSNR) and --tile N|auto (--test_single
 and test() cut the picture into overlapping tiles, run them as batches and stitch the exact result), --test_only (load
 the checkpoint and run test() on the test sets, no training; one line per dataset with PSNR and SSIM) and --eval_domain
-{float,u8,y8} / --eval_shave N (test() also reports PSNR and SSIM on the 8-bit picture or its luma, with a border left out).
+{float,u8,y8} / --eval_shave N (test() also reports PSNR and SSIM on the 8-bit picture or its luma, with a border left out)
+and --self_ensemble (--test_single, --test_only and the test() after training run every picture through the x8 geometric
+self-ensemble, "EDSR+": the net on the eight flips / rotations, transformed back and averaged).
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N main.py ..."""
 import argparse
 import os
@@ -77,6 +79,9 @@ def parse_args(argv=None):
                         'picture that --save_test_images writes; y8: the luma of that picture')
     p.add_argument('--eval_shave', type=int, default=None, metavar='N',
                    help='test(): leave a border of N pixels out of the --eval_domain numbers (tables use the scale factor)')
+    p.add_argument('--self_ensemble', action='store_true',
+                   help='--test_single and test(): the x8 geometric self-ensemble ("EDSR+"): the net on the eight flips / '
+                        'rotations of the picture, each result transformed back, the eight averaged; works with --tile')
     return check_args(p.parse_args(argv))
 
 

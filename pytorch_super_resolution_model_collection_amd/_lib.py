@@ -161,6 +161,9 @@ _PROTOTYPES = {
     "srk_tile_gather": (c_int, [c_f, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_vp]),
     "srk_tile_stitch_f32": (c_int, [c_f, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, c_f, c_int, c_int, c_vp]),
     "srk_tile_stitch_u8": (c_int, [c_f, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_vp]),
+    "srk_dihedral_variants": (c_int, [c_f, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_int, c_int, c_int, c_int, c_f, c_vp]),
+    "srk_dihedral_merge_f32": (c_int, [c_f, ctypes.POINTER(ctypes.c_int64), c_f, ctypes.POINTER(ctypes.c_int64), c_int, c_int, c_int, c_int, c_f, c_vp]),
+    "srk_dihedral_merge_u8": (c_int, [c_f, ctypes.POINTER(ctypes.c_int64), c_f, ctypes.POINTER(ctypes.c_int64), c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "srk_rgb_to_ycc_host": (c_int, [c_vp, c_size, c_vp]),
     "srk_ycc_to_rgb_host": (c_int, [c_vp, c_size, c_vp]),
     "srk_psnr_workspace_bytes": (c_size, []),

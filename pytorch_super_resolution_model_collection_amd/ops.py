@@ -1923,6 +1923,95 @@ def tile_stitch_u8(tiles, tp, t0=0, out=None, cb=None, cr=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# x8 geometric self-ensemble (csrc/dihedral.hip): the eight flips / rotations in one launch, their ordered mean in one
+# ------------------------------------------------------------------------------------------------
+class DihedralVariants(tuple):
+    """(even, odd) of dihedral_variants.  `whole` is the one allocation as [8N,C,H,H] when the pictures are square
+    (even then odd, so whole[:4N] is even and whole[4N:] is odd), else None."""
+
+    def __new__(cls, even, odd, whole):
+        self = super(DihedralVariants, cls).__new__(cls, (even, odd))
+        self.even, self.odd, self.whole = even, odd, whole
+        return self
+
+
+def dihedral_variants(x):
+    """The eight variants T_k(x), k = 4 m + r, T_k = rot90(flip of the last axis if m, r) of the fp32 pictures x
+    ([N,C,H,W] or [C,H,W], any strides, C = 1 or 3) in one launch and one allocation, in the channels-last storage the
+    nets take: even [4N,C,H,W] with even[4 n + j] = T_k(x[n]), k = (0, 2, 4, 6)[j], and odd [4N,C,W,H] with
+    k = (1, 3, 5, 7)[j].  Returns a DihedralVariants (even, odd); both are views of the allocation."""
+    require_cuda(x)
+    v = x.detach()
+    if v.dim() == 3:
+        v = v.unsqueeze(0)
+    if v.dim() != 4 or v.shape[1] not in (1, 3) or v.dtype != torch.float32 or v.numel() == 0:
+        raise RuntimeError("dihedral_variants expects fp32 pictures [N,C,H,W] with C = 1 or 3, got %s %s" % (x.dtype, tuple(x.shape)))
+    n, c, h, w = (int(s) for s in v.shape)
+    buf = torch.empty(8 * n * h * w * c, dtype=torch.float32, device=v.device)
+    check(_lib.load().srk_dihedral_variants(ptr(v), int(v.stride(0)), int(v.stride(1)), int(v.stride(2)), int(v.stride(3)),
+                                            n, c, h, w, ptr(buf), stream_ptr()), "srk_dihedral_variants")
+    half = 4 * n * h * w * c
+    even = buf[:half].view(4 * n, h, w, c).permute(0, 3, 1, 2)
+    odd = buf[half:].view(4 * n, w, h, c).permute(0, 3, 1, 2)
+    whole = buf.view(8 * n, h, w, c).permute(0, 3, 1, 2) if h == w else None
+    return DihedralVariants(even, odd, whole)
+
+
+def _merge_sources(what, even, odd):
+    require_cuda(even, odd)
+    e, o = even.detach(), odd.detach()
+    if (e.dim() != 4 or o.dim() != 4 or e.dtype != torch.float32 or o.dtype != torch.float32 or e.shape[1] not in (1, 3)
+            or e.shape[0] % 4 or e.numel() == 0
+            or tuple(o.shape) != (e.shape[0], e.shape[1], e.shape[3], e.shape[2])):
+        raise RuntimeError("%s expects fp32 net outputs even [4N,C,oh,ow] and odd [4N,C,ow,oh] with C = 1 or 3, got %s %s and "
+                           "%s %s" % (what, even.dtype, tuple(even.shape), odd.dtype, tuple(odd.shape)))
+    if o.device != e.device:
+        raise RuntimeError("%s: even is on %s and odd on %s" % (what, e.device, o.device))
+    st = lambda t: (ctypes.c_int64 * 4)(*[int(s) for s in t.stride()])
+    return e, o, st(e), st(o)
+
+
+def dihedral_merge(even, odd, out=None):
+    """The ensemble E = (((((((y_0 + y_1) + y_2) + y_3) + y_4) + y_5) + y_6) + y_7) * 0.125, y_k = T_k^-1 of the net's
+    output for variant k, in fp32 and in that order, in one launch: even [4N,C,oh,ow] (k = 0, 2, 4, 6 per picture) and odd
+    [4N,C,ow,oh] (k = 1, 3, 5, 7) are read in place through their strides (NCHW or channels-last) -> [N,C,oh,ow]."""
+    e, o, se, so = _merge_sources("dihedral_merge", even, odd)
+    n, c, oh, ow = int(e.shape[0]) // 4, int(e.shape[1]), int(e.shape[2]), int(e.shape[3])
+    if out is None:
+        out = torch.empty((n, c, oh, ow), dtype=torch.float32, device=e.device)
+    elif tuple(out.shape) != (n, c, oh, ow) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != e.device:
+        raise RuntimeError("dihedral_merge: out must be a dense fp32 [%d,%d,%d,%d] tensor on %s" % (n, c, oh, ow, e.device))
+    check(_lib.load().srk_dihedral_merge_f32(ptr(e), se, ptr(o), so, n, c, oh, ow, ptr(out), stream_ptr()),
+          "srk_dihedral_merge_f32")
+    return out
+
+
+def dihedral_merge_u8(even, odd, cb=None, cr=None):
+    """dihedral_merge of ONE picture writing the final 8-bit picture directly: to_u8_image(dihedral_merge(...)) without
+    the fp32 mean (uint8 [oh,ow,C]), or with the chroma planes cb / cr (uint8 [oh,ow]; C = 1)
+    ycbcr_to_rgb_u8(dihedral_merge(...), cb, cr) (uint8 [oh,ow,3]); bit-equal to those compositions."""
+    e, o, se, so = _merge_sources("dihedral_merge_u8", even, odd)
+    c, oh, ow = int(e.shape[1]), int(e.shape[2]), int(e.shape[3])
+    if e.shape[0] != 4:
+        raise RuntimeError("dihedral_merge_u8 writes one picture: even must be [4,C,oh,ow], got %s" % (tuple(even.shape),))
+    if (cb is None) != (cr is None):
+        raise RuntimeError("dihedral_merge_u8: cb and cr come together")
+    oc = c
+    if cb is not None:
+        _require_u8("dihedral_merge_u8", cb, cr)
+        if cb.device != e.device or cr.device != e.device:
+            raise RuntimeError("dihedral_merge_u8: the chroma planes are on %s / %s, the net outputs on %s" % (cb.device, cr.device, e.device))
+        if c != 1 or tuple(cb.shape) != (oh, ow) or tuple(cr.shape) != (oh, ow):
+            raise RuntimeError("dihedral_merge_u8: chroma planes must be [%d,%d] and go with a one-channel output (got C = %d, "
+                               "cb %s, cr %s)" % (oh, ow, c, tuple(cb.shape), tuple(cr.shape)))
+        cb, cr, oc = cb.contiguous(), cr.contiguous(), 3
+    out = torch.empty((oh, ow, oc), dtype=torch.uint8, device=e.device)
+    check(_lib.load().srk_dihedral_merge_u8(ptr(e), se, ptr(o), so, c, oh, ow, None if cb is None else ptr(cb),
+                                            None if cr is None else ptr(cr), ptr(out), stream_ptr()), "srk_dihedral_merge_u8")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # DRCN (drcn.py:13-59): the weight-shared recursion and the recursive-supervision head
 # ------------------------------------------------------------------------------------------------
 # The inference net applies ONE conv + ReLU D times in a row and ONE two-conv reconstruction to each of the D hidden

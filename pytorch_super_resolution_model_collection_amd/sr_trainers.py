@@ -225,36 +225,70 @@ class _Trainer(object):
             return self.model(x.to(self.device))
 
     # -- tiled inference (tiling.py, csrc/tile.hip) ------------------------------------------------------------------
-    def _resolve_tile(self, tile, x):
+    def _resolve_tile(self, tile, x, ensemble=False):
         """The `tile` option for the net input x -> (tile size or None for one pass, the net's geometry or None).
-        tile=None falls back to args.tile (older args objects have no such field); still None: nothing is computed."""
+        tile=None falls back to args.tile (older args objects have no such field); still None: nothing is computed.
+        ensemble: the geometry is the union of the net's cone and its mirror image (tiling.ensemble_geometry)."""
         if tile is None:
             tile = getattr(self.args, 'tile', None)
         if tile is None:
             return None, None
         self.model.eval()
         geo = tiling.net_geometry(self.model)
+        if ensemble:
+            geo = tiling.ensemble_geometry(geo)
         return tiling.resolve_tile(tile, geo, int(x.shape[-2]), int(x.shape[-1])), geo
 
-    def _infer_tiled(self, x, geo, tile, tile_batch=None, as_u8=False, chroma=None):
+    # -- x8 geometric self-ensemble (csrc/dihedral.hip) ---------------------------------------------------------------
+    def _self_ensemble(self, flag):
+        """The `self_ensemble` option: None falls back to args.self_ensemble (older args objects have no such field: off)."""
+        return bool(getattr(self.args, 'self_ensemble', False)) if flag is None else bool(flag)
+
+    def _infer_variants(self, x):
+        """The net (last element of a tuple output) on the eight variants T_k, k = 4 m + r, T_k = rot90(flip of the last
+        axis if m, r), of the net inputs x [N,C,H,W]: one launch makes all of them, the net runs on the four of the
+        picture's shape and on the four of the transposed shape (as ONE batch of 8 N when the pictures are square).
+        Returns (even, odd): the outputs for k = 0, 2, 4, 6 and for k = 1, 3, 5, 7, what ops.dihedral_merge takes."""
+        var = ops.dihedral_variants(x)
+        if var.whole is not None:
+            y = self._infer(var.whole)
+            y = y[-1] if isinstance(y, tuple) else y
+            even, odd = y[:y.shape[0] // 2], y[y.shape[0] // 2:]
+        else:
+            even, odd = self._infer(var.even), self._infer(var.odd)
+            even = even[-1] if isinstance(even, tuple) else even
+            odd = odd[-1] if isinstance(odd, tuple) else odd
+        if tuple(odd.shape) != (even.shape[0], even.shape[1], even.shape[3], even.shape[2]):
+            raise RuntimeError("self-ensemble: the net returned %s for the pictures and %s for the transposed ones; it must "
+                               "treat both axes alike" % (tuple(even.shape), tuple(odd.shape)))
+        return even, odd
+
+    def _infer_tiled(self, x, geo, tile, tile_batch=None, as_u8=False, chroma=None, ensemble=False):
         """The net's output for the net input x [1,C,H,W] (on the device), computed on overlapping tiles: the plan's table
         goes to the device once, then per chunk of `tile_batch` tiles: k_tile_gather -> _infer on the batch (last element
         of a tuple output) -> k_tile_stitch of the rectangles those tiles own.  The peak working set is one chunk's
         activations plus the output picture; nothing waits for the device.  Returns the fp32 picture [1,C,OH,OW], or with
         as_u8 the final interleaved 8-bit picture (chroma: the picture's 8-bit Cb / Cr planes [2,h,w], resized here to the
-        output size and merged by the stitch), in which case the fp32 picture is never written."""
+        output size and merged by the stitch), in which case the fp32 picture is never written.
+        ensemble (geo is then tiling.ensemble_geometry of the net's): every chunk goes gather -> the eight variants of its
+        tiles -> net -> k_dihedral_merge to the fp32 tile outputs -> the same stitch; `tile_batch` then counts net inputs,
+        variants included, rounded up to whole tiles (tiling.tiles_per_chunk)."""
         plan = tiling.plan(geo, int(x.shape[-2]), int(x.shape[-1]), tile)
         tp = ops.TilePlan(plan, self.device)
         if tile_batch is None:
             tile_batch = getattr(self.args, 'tile_batch', None) or tiling.DEFAULT_TILE_BATCH
-        tile_batch = plan.ntiles if tile_batch in ('all', 0) else max(1, int(tile_batch))
+        tile_batch = tiling.tiles_per_chunk(tile_batch, plan.ntiles, ensemble)
         cb = cr = None
         if chroma is not None:
             cb, cr = ops.resize_u8(chroma, plan.OH, plan.OW)   # both chroma planes in one resizer call
         out = None
         for t0 in range(0, plan.ntiles, tile_batch):
-            y = self._infer(ops.tile_gather(x, tp, t0, min(tile_batch, plan.ntiles - t0)))
-            y = y[-1] if isinstance(y, tuple) else y
+            tiles = ops.tile_gather(x, tp, t0, min(tile_batch, plan.ntiles - t0))
+            if ensemble:
+                y = ops.dihedral_merge(*self._infer_variants(tiles))
+            else:
+                y = self._infer(tiles)
+                y = y[-1] if isinstance(y, tuple) else y
             if tuple(y.shape[-2:]) != (plan.oth, plan.otw):
                 raise RuntimeError("tiled inference: the net returned %s for a tile of %d x %d, the geometry says %d x %d"
                                    % (tuple(y.shape), plan.th, plan.tw, plan.oth, plan.otw))
@@ -264,16 +298,20 @@ class _Trainer(object):
                 out = ops.tile_stitch(y, tp, t0, out)
         return out if as_u8 else out.unsqueeze(0)
 
-    def _forward(self, x, tile=None, tile_batch=None):
-        """_net_input and the net (last element of a tuple output) on the device: one pass, or tiled when `tile` says so."""
+    def _forward(self, x, tile=None, tile_batch=None, self_ensemble=None):
+        """_net_input and the net (last element of a tuple output) on the device: one pass, or tiled when `tile` says so;
+        with self_ensemble the x8 geometric ensemble of the net (see test_single) in place of the net."""
         x = self._net_input(x)
-        size, geo = self._resolve_tile(tile, x)
+        ens = self._self_ensemble(self_ensemble)
+        size, geo = self._resolve_tile(tile, x, ens)
         if size is None:
+            if ens:
+                return ops.dihedral_merge(*self._infer_variants(x))
             out = self._infer(x)
             return out[-1] if isinstance(out, tuple) else out
-        return self._infer_tiled(x, geo, size, tile_batch)
+        return self._infer_tiled(x, geo, size, tile_batch, ensemble=ens)
 
-    def test(self, loader=None, save_images=False, tile=None, eval_domain=None, eval_shave=None):
+    def test(self, loader=None, save_images=False, tile=None, eval_domain=None, eval_shave=None, self_ensemble=None):
         """Evaluation loop (espcn.py:173-215, edsr.py:196-250): forward + PSNR per image (computed on the device), over
         `loader`, else over every folder of `test_dataset` that exists under `data_dir` (data.get_test_set), else over
         seeded synthetic pairs.  Returns the list of PSNRs; `self.test_psnr` holds the per-dataset averages.
@@ -282,6 +320,7 @@ class _Trainer(object):
         average PSNR of the loader's bicubic image (the third item, where the loader yields one) against the target
         (edsr.py:257-261), computed by the same device kernel.
         tile: None (args.tile, else one pass), a tile size in net-input pixels or 'auto': see test_single.
+        self_ensemble: None (args.self_ensemble, else off) or a bool: every picture through the x8 ensemble, see test_single.
         Beside every PSNR goes the SSIM of the same two tensors (utils.SSIM, on the device): `self.test_ssim` holds the
         per-dataset averages, with save_images `self.test_bicubic_ssim` the bicubic image's.  A pair smaller than the
         11 x 11 window is left out of that average.
@@ -324,7 +363,7 @@ class _Trainer(object):
                 items = [batch] if torch.is_tensor(batch[0]) else list(zip(*batch))   # ragged test images come as lists
                 for item in items:
                     lr_img, hr_img = self._channels(*[t if t.dim() == 4 else t.unsqueeze(0) for t in item[:2]])
-                    out = self._forward(lr_img.to(self.device), tile)
+                    out = self._forward(lr_img.to(self.device), tile, self_ensemble=self_ensemble)
                     tgt = hr_img.to(self.device)
                     if self.kind == "srcnn":     # srcnn.py:193-199: border pixels excluded
                         tgt = utils.shave(tgt, 8)
@@ -361,7 +400,7 @@ class _Trainer(object):
                                         'ssim': sum(float(v) for v in ev[:, 0]) / len(ev)}
         return psnrs
 
-    def test_single(self, img, tile=None, tile_batch=None):
+    def test_single(self, img, tile=None, tile_batch=None, self_ensemble=None):
         """A tensor: super-resolve one [C,H,W] (or [1,C,H,W]) tensor and return the net's output on the host.
         A path (str / os.PathLike): the reference's test_single(img_fn) (edsr.py:276-322) -- super-resolve the picture
         file, write <save_dir>/test_result/SR_result.png and return that file name; see _test_single_file.
@@ -369,16 +408,23 @@ class _Trainer(object):
         (the bicubic-upsampled picture for SRCNN / VDSR / DRCN) into overlapping tiles of that many pixels a side, runs
         them in batches of `tile_batch` (tiling.DEFAULT_TILE_BATCH; 'all' = one batch) and stitches every output pixel
         from the one tile that holds its whole receptive field: the one-pass result, with a working set that does not
-        grow with the picture.  'auto' tiles only pictures whose widest activation exceeds tiling.AUTO_BUDGET_BYTES."""
+        grow with the picture.  'auto' tiles only pictures whose widest activation exceeds tiling.AUTO_BUDGET_BYTES.
+        self_ensemble: None (args.self_ensemble, else off) or a bool.  On: the geometric self-ensemble of the EDSR paper
+        ("EDSR+") in place of the net f: with T_k(x) = rot90(flip of the last axis if m, r turns), k = 4 m + r, the result
+        is (((((((y_0 + y_1) + y_2) + y_3) + y_4) + y_5) + y_6) + y_7) * 0.125 in fp32, y_k = T_k^-1(f(T_k(x))).  It wraps
+        the net, not the pre-processing (the bicubic picture of SRCNN / VDSR / DRCN is made once and transformed), and with
+        num_channels == 1 not the chroma.  The variants and the mean are one kernel launch each (csrc/dihedral.hip); the
+        path form's mean is written as the 8-bit picture.  Tiled, the plan allows for the mirrored net's dependency cone
+        (tiling.ensemble_geometry) and `tile_batch` counts net inputs, variants included."""
         if isinstance(img, (str, os.PathLike)):
-            return self._test_single_file(img, tile, tile_batch)
+            return self._test_single_file(img, tile, tile_batch, self_ensemble)
         if self.model is None:
             self.model = self.build_model().to(self.device)
             self.load_model()
         x = img if img.dim() == 4 else img.unsqueeze(0)
-        return self._forward(x.to(self.device), tile, tile_batch).cpu()
+        return self._forward(x.to(self.device), tile, tile_batch, self_ensemble).cpu()
 
-    def _test_single_file(self, img_fn, tile=None, tile_batch=None):
+    def _test_single_file(self, img_fn, tile=None, tile_batch=None, self_ensemble=None):
         """edsr.py:276-322 with the picture on the device from the decode to the 8-bit result:
           num_channels == 1  upload the 8-bit RGB once -> k_rgb_to_ycc (fp32 Y / 255 and planar Cb / Cr in one pass) -> Y
                              through _net_input and _infer exactly as the tensor form does (bicubic pre-upsampling for
@@ -391,7 +437,9 @@ class _Trainer(object):
         waits for the device.  Tiled (see test_single): the stitch kernel writes the 8-bit result itself (k_tile_stitch
         quantises, and merges the resized chroma, on the way), so the fp32 HR picture never exists.  Every trainer follows
         the EDSR convention for the net's output, clamp(0, 1): SRCNN's own test_single stretches the output to its min..max
-        instead (srcnn.py:244), which turns any picture grey-scaled to full range; that is not reproduced."""
+        instead (srcnn.py:244), which turns any picture grey-scaled to full range; that is not reproduced.
+        self_ensemble (see test_single): k_dihedral_merge writes the 8-bit picture from the eight outputs (it quantises, and
+        merges the resized chroma, on the way); tiled, it writes the fp32 tile outputs the stitch then reads."""
         from . import data
         if self.model is None:
             self.model = self.build_model().to(self.device)
@@ -404,10 +452,17 @@ class _Trainer(object):
         else:
             x = ops.resize_u8(rgb.permute(2, 0, 1), h, w, out_float=True).unsqueeze(0)   # ToTensor: planar, / 255
         x = self._net_input(x)
-        size, geo = self._resolve_tile(tile, x)
+        ens = self._self_ensemble(self_ensemble)
+        size, geo = self._resolve_tile(tile, x, ens)
         if size is not None:
             return self._save_single(self._infer_tiled(x, geo, size, tile_batch, as_u8=True,
-                                                       chroma=cbcr if self.num_channels == 1 else None))
+                                                       chroma=cbcr if self.num_channels == 1 else None, ensemble=ens))
+        if ens:
+            even, odd = self._infer_variants(x)
+            if self.num_channels == 1:
+                cbcr = ops.resize_u8(cbcr, int(even.shape[-2]), int(even.shape[-1]))
+                return self._save_single(ops.dihedral_merge_u8(even, odd, cbcr[0], cbcr[1]))
+            return self._save_single(ops.dihedral_merge_u8(even, odd))
         out = self._infer(x)
         out = out[-1] if isinstance(out, tuple) else out
         if self.num_channels == 1:

@@ -33,6 +33,23 @@ clipped cone of o lies inside [x, x + T): where the unclipped cone leaves the ti
 picture's edge and the net's zero padding there is the one-pass padding.  That is an interval of o per tile; the step
 between tiles is the largest for which consecutive intervals abut, and every output pixel is owned by the FIRST tile
 whose interval holds it.
+
+Self-ensemble.  The x8 ensemble (sr_trainers: self_ensemble) also runs the net on mirrored and rotated pictures and maps
+the results back.  Both axes are alike, so a rotation only swaps which axis a cone applies to; what changes a cone is
+the mirror.  With J the reversal of an axis of n input pixels (i -> n - 1 - i) and J' that of its N = scale n + offset
+output pixels, the mirrored net is x -> J' f(J x), and its output pixel o depends on J(cone of N - 1 - o):
+
+    n - 1 - floor((N - 1 - o + hi) / s) .. n - 1 - floor((N - 1 - o + lo) / s)
+
+and with N = s n + offset and -floor(-a / s) - 1 = floor((a - 1) / s) that is
+
+    floor((o - offset - hi) / s) .. floor((o - offset - lo) / s)
+
+so mirrored(g) = Geometry(scale, offset, -offset - hi, -offset - lo): the extent n has cancelled, hence one geometry
+serves the picture and every tile.  A cone with lo + hi = -offset is its own mirror image (every net here except FSRCNN,
+whose transposed conv makes it lopsided: x4 (-18, 35) against (-19, 34)).  The ensemble of a tile is right at an output
+pixel iff the tile is right there for the net AND for the mirrored net, so the plan of an ensemble run comes from
+ensemble_geometry(g), the union of the two cones.
 """
 from fractions import Fraction
 
@@ -216,6 +233,16 @@ def net_geometry(model):
     raise ValueError("net_geometry: no composition rule for a %s" % type(model).__name__)
 
 
+def mirrored(g):
+    """Geometry of the net wrapped in a reversal of the axis, before and after (the module text has the derivation)."""
+    return Geometry(g.scale, g.offset, -g.offset - g.hi, -g.offset - g.lo, g.floats_per_pixel)
+
+
+def ensemble_geometry(g):
+    """Geometry under which a tile is right for all eight variants of the self-ensemble: the union of both cones."""
+    return _union(g, mirrored(g), "self-ensemble")
+
+
 # ---- the plan ------------------------------------------------------------------------------------------------------------
 class AxisPlan(object):
     """Tiles of one axis: `starts` (input offset of each tile) and `own` ([first, end) output pixels each tile owns)."""
@@ -280,6 +307,16 @@ def plan(geometry, H, W, tile):
     if tile < 1:
         raise ValueError("tile must be a positive number of net-input pixels, got %d" % tile)
     return Plan(geometry, H, W, tile)
+
+
+def tiles_per_chunk(tile_batch, ntiles, ensemble=False):
+    """Tiles per batch of the tiled loop from the `tile_batch` option (None: DEFAULT_TILE_BATCH; 'all' / 0: every tile).
+    With the self-ensemble a tile is eight net inputs and `tile_batch` counts net inputs, rounded up to whole tiles, so a
+    given tile_batch means the same working set with and without it."""
+    if tile_batch in ('all', 0):
+        return max(1, int(ntiles))
+    n = max(1, int(DEFAULT_TILE_BATCH if tile_batch is None else tile_batch))
+    return -(-n // 8) if ensemble else n
 
 
 def activation_bytes(geometry, H, W):
