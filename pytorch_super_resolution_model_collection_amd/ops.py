@@ -927,9 +927,16 @@ def _channels_inner(x):
 
 
 def _dense(x):
+    """x in the layout the streaming kernels read (dense NHWC for 4-D, contiguous otherwise), starting on a 16-byte
+    boundary: a dense view at an odd storage offset (`x[1:]` of a one-channel batch with H * W % 4 != 0) is copied --
+    srk_act_forward / srk_axpby read float4 and refuse such a pointer."""
     if x.dim() == 4:
-        return to_nhwc(x if (_is_nchw_dense(x) or _is_nhwc_dense(x)) else x.contiguous())
-    return x.contiguous()
+        x = to_nhwc(x if (_is_nchw_dense(x) or _is_nhwc_dense(x)) else x.contiguous())
+    else:
+        x = x.contiguous()
+    if x.data_ptr() % 16:
+        x = x.clone(memory_format=torch.preserve_format)
+    return x
 
 
 class _Act(torch.autograd.Function):
@@ -968,6 +975,9 @@ def activation(x, kind, slope=0.0, prelu_w=None):
         kind = ACT_BY_NAME[kind]
     if kind == ACT_NONE:
         return x
+    if kind == ACT_LRELU and float(slope) < 0.0:
+        # the backward decides the side by the sign of the saved OUTPUT, which a negative slope flips
+        raise RuntimeError("activation: LeakyReLU with a negative slope (%g) is not supported" % float(slope))
     return _Act.apply(x, int(kind), float(slope), prelu_w)
 
 
