@@ -294,14 +294,26 @@ int srk_resblock2_backward_data(int N, int H, int W, int C, const float* dy, con
 
 /* ---- ESPCN's first two convs in one launch (conv_pair.hip) ------------------------------------------------------- */
 /* y = relu(conv3x3(relu(conv5x5(x) + b1)) + b2), both "valid", stride 1, f16x3 arithmetic (SRK_ALGO_MFMA_F16X3), inference
- * only; the 64-channel intermediate never leaves the chip.  x: NCHW [N,3,H,W] fp32 (read in place); w1: the plain
- * [64,3,5,5] filter; w2_packed_fwd: srk_pack_weight_fwd of the [32,64,3,3] filter (ps_r = 0); b1 [64], b2 [32];
- * y: NHWC [N,H-6,W-6,32]; x_amax: the SRK_AMAX_FLOATS running-maximum buffer of |x|; y_amax (optional) receives
- * max|y|.  SRK_ERR_UNSUPPORTED when the shape is not worth the fused kernel (tiles too ragged, fewer than four
- * 8 x 16 tiles per CU) -- the caller runs the two convs then; force != 0 skips that efficiency rule. */
-int srk_espcn_pair_forward(int N, int H, int W, const float* x, const float* w1, const float* b1,
-                           const float* w2_packed_fwd, const float* b2, float* y, const float* x_amax, float* y_amax,
-                           int force, void* stream);
+ * only; the 64-channel intermediate never leaves the chip.  x: NCHW [N,3,H,W] fp32 (read in place); w1_prepared: what
+ * srk_espcn_pair_prepare made of the plain [64,3,5,5] filter and its bias (srk_espcn_pair_prepared_bytes() bytes, 16-byte
+ * aligned; once per filter: fragment-ordered fp16 planes, sum |w_c|, |b_c|, max |w|); w2_packed_fwd: srk_pack_weight_fwd of
+ * the [32,64,3,3] filter (ps_r = 0); b1 [64], b2 [32]; y: NHWC [N,H-6,W-6,32]; y_amax (optional) receives max|y|.
+ * x_amax: the SRK_AMAX_FLOATS running-maximum buffer of |x|.  x_amax_compute == 0: it holds the maximum (or a bound) and
+ * is only read.  x_amax_compute != 0: it is ZEROED memory that nothing else uses during the launch; the kernel measures
+ * max|x| itself (every block a slice, one rendezvous behind the prologue) and leaves it in the slots, whose words 1 and 2
+ * it uses as counters and returns to zero, so a captured launch can be replayed on the same buffer (the slots then hold
+ * the running maximum over the replays: never too low).  The output is the same bits as with srk_absmax in front.
+ * SRK_ERR_UNSUPPORTED when the shape is not worth the fused kernel (tiles too ragged, fewer than four 8 x 16 tiles per
+ * CU) -- the caller runs the two convs then.  force: bit 0 skips that efficiency rule; bit 1 (with x_amax_compute) makes
+ * every block take the rendezvous' timeout path, a scan of all of x (tests).
+ * srk_espcn_pair_scans: blocks that took that scan path since the last reset (0 in a product run on an idle device; a
+ * diagnostic like srk_ring_timeouts, which it is not part of).  Synchronises the device. */
+size_t srk_espcn_pair_prepared_bytes(void);
+int srk_espcn_pair_prepare(const float* w1, const float* b1, void* w1_prepared, void* stream);
+int srk_espcn_pair_forward(int N, int H, int W, const float* x, const void* w1_prepared, const float* b1,
+                           const float* w2_packed_fwd, const float* b2, float* y, float* x_amax, int x_amax_compute,
+                           float* y_amax, int force, void* stream);
+int srk_espcn_pair_scans(int reset);
 
 /* ---- pixel shuffle (torch.nn.PixelShuffle: base_networks.py:157,179-181) ----------------- */
 /* x [N,H,W,C*r*r] -> y [N,H*r,W*r,C];  channel c*r*r + i*r + j -> (c, h*r+i, w*r+j). */

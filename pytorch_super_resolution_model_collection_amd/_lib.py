@@ -91,7 +91,10 @@ _PROTOTYPES = {
                                                    ctypes.POINTER(c_vp), ctypes.POINTER(BwdMask), ctypes.POINTER(c_vp),
                                                    ctypes.POINTER(c_vp), c_float, c_vp, c_size, c_vp]),
     "srk_resblock2_supported": (c_int, [c_int, c_int, c_int, c_int]),
-    "srk_espcn_pair_forward": (c_int, [c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_int, c_vp]),
+    "srk_espcn_pair_prepared_bytes": (c_size, []),
+    "srk_espcn_pair_prepare": (c_int, [c_f, c_f, c_vp, c_vp]),
+    "srk_espcn_pair_forward": (c_int, [c_int, c_int, c_int, c_f, c_vp, c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_int, c_vp]),
+    "srk_espcn_pair_scans": (c_int, [c_int]),
     "srk_resblock2_forward": (c_int, [c_int, c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_int, c_f, c_f,
                                       c_vp]),
     "srk_absmax": (c_int, [c_f, c_size, c_f, c_vp]),

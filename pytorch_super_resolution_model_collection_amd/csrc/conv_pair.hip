@@ -28,6 +28,23 @@
 // chunk) before reading it, and signals free right behind its last read of a slot.  Halo rows 8 .. 9 go to a kept-row
 // buffer with counters of its own (see the tile loop).  Every poll is capped: a slip is counted (srk_ring_timeouts) and
 // the waves run on with wrong numbers instead of faulting the device.
+//
+// max|x| (the input's scale, and through the bound the intermediate's) is either handed in (x_amax of a producer, of
+// srk_absmax or declared) or measured inside the launch: block b of G reduces the float4 slice [b n / G, (b + 1) n / G)
+// of x, raises slot b % 16 with one atomic, waits for it to return and arrives on a counter word of the slots buffer; after the rest of its
+// prologue its first wave polls for G arrivals (capped) and reads the slots.  Departures are counted beside the arrivals and
+// the last block to leave zeroes both words, so a captured launch replays.  A block whose poll runs into its cap scans all
+// of x itself (counted in srk_espcn_pair_scans, not in srk_ring_timeouts).  Maximum is order-free and only its exponent is
+// used, so the output is the same bits either way.
+//
+// Everything that depends on the first layer's filter alone -- the fp16 planes of every lane's fragments, sum |w_c|, |b_c|,
+// the filter's maximum -- is prepared once per filter by k_espcn_pair_prep with the same device functions; the kernel
+// loads 16 words per lane.
+//
+// Dead rows: a column's last tile has vr = OH - 8 ty live output rows.  Output row r reads halo rows r .. r + 2, so halo
+// rows >= vr + 2 reach nothing that is stored.  Fragment f of rows 2 .. 9 starts in halo row (36 + 16 f) / 18: the waves of
+// pixel half 1 (f >= 4, first row 5) skip their first layer when vr <= 3, the waves of output rows 4 .. 7 their second layer
+// and stores when vr <= 4.  They still perform every wait and signal.
 #include "srk_common.h"
 #include "conv_problem.h"
 #include "bf16_frag.h"
@@ -49,24 +66,41 @@ constexpr int PR_KBUF = 2 * 4 * PR_KP;              // uint4 per plane of a kept
 constexpr int PR_PLANE = PR_NSLOT * PR_HBUF + PR_NKBUF * PR_KBUF;   // the residual planes of all of them lie this far on
 constexpr int PR_XBUF = 2 * PR_XR * PR_XP;          // uint2 per group's input tile [plane][row][pixel]
 constexpr unsigned PR_SPIN_CAP = 1u << 18;
+constexpr unsigned PR_AMAX_CAP = 1u << 14;          // polls of the max|x| rendezvous (one L2 round trip and a sleep each)
+constexpr int PR_ARRIVE = 1, PR_DEPART = 2;         // counter words of the slots buffer (slot i is word 16 i)
+// Both words MUST stay in one 64-byte line and be touched by one thread of a block (thread 0).  The reset -- the last
+// block to leave zeroes both -- needs every block's arrival, an atomic without a return value, to be performed before
+// that block's own later departure.  Nothing in the memory model orders two relaxed atomics on different words; what
+// does is the hardware path: a wave's vector memory instructions leave the CU in issue order, an address selects its L2
+// channel by line, so both requests queue at the same channel behind each other, and device-scope atomics on ordinary
+// device memory (what the slots are: a torch allocation) are performed there.  Moved to different lines, or issued by different
+// waves, the arrival could land after the zeroing and leave the counter at 1 for the next launch.  The ordering of a
+// block's slot maximum before its arrival does not lean on this: the maximum returns a value the arrival waits for.
+constexpr int PR_XLD = 24;                          // float4 loads a thread keeps in flight over its part of the slice
+constexpr int PR_W1P = 2 * 2 * 4 * 2 * 64;          // uint4 of the prepared first layer [c1][nf][ks][plane][lane]; behind
+constexpr int PR_W1P_FLOATS = 144;                  // them floats: sum |w_c| [64], |b_c| [64], max |w|
+constexpr size_t PR_W1P_BYTES = (size_t)PR_W1P * 16 + PR_W1P_FLOATS * 4;
 constexpr size_t PR_LDS = (size_t)PR_WL2 * 16 + (size_t)2 * PR_PLANE * 16 + (size_t)2 * PR_XBUF * 8 + 64;
 static_assert(PR_LDS <= 160 * 1024, "k_espcn_pair: LDS");
 
 __device__ unsigned g_pair_timeouts = 0;
+__device__ unsigned g_pair_scans = 0;   // blocks that scanned all of x themselves (rendezvous cap, or asked for)
 
 typedef __attribute__((address_space(3))) unsigned pr_cnt_t;
 typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
 
 struct PairParams {
   const float* x;          // NCHW [N][3][H][W]
-  const float* w1;         // [64][3][5][5]
+  const uint4* w1p;        // the first layer as k_espcn_pair_prep leaves it
   const float* b1;         // [64]
   const uint4* wq2;        // fp16 section of the second layer's prepared filter
   const float* w2_descale; // its trailer {2^-kw, 2^kw}
   const float* b2;         // [32]
   float* y;                // NHWC [N][H-6][W-6][32]
-  const float* x_amax;
+  float* x_amax;           // slots of max|x|: read (amax_mode 0) or raised here
   float* y_amax;
+  size_t xn;               // elements of x
+  int amax_mode;           // 0: x_amax holds the maximum; 1: measured in this launch; 2: same, every block scans all of x
   int N, H, W, OH, OW, tiles_y, img_tiles, ntiles;
   unsigned x_img_bytes, y_bytes;
 };
@@ -100,6 +134,74 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t pr_rsrc(const void* base, unsi
   return __builtin_amdgcn_make_buffer_rsrc(p, (short)0, (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
 }
 
+// max |x| over the float4s [lo, hi) (thread t of nt takes lo + t, lo + t + nt, ..: PR_XLD loads in flight) and, with `tail`,
+// over the elements behind the last whole float4
+__device__ __forceinline__ float pr_slice_absmax(const float* __restrict__ x, size_t lo, size_t hi, size_t n, bool tail,
+                                                 int t, int nt) {
+  const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
+  float m = 0.f;
+  for (size_t base = lo; base < hi; base += (size_t)nt * PR_XLD) {
+    f32x4 v[PR_XLD];
+#pragma unroll
+    for (int k = 0; k < PR_XLD; ++k) {
+      const size_t e = base + (size_t)t + (size_t)k * nt;
+      v[k] = x4[e < hi ? e : hi - 1];
+    }
+#pragma unroll
+    for (int k = 0; k < PR_XLD; ++k) m = abs_max4(m, v[k]);
+  }
+  if (tail) {
+    const size_t e = (n & ~(size_t)3) + (size_t)t;
+    if (t < 3 && e < n) m = fmaxf(m, fabsf(x[e]));
+  }
+  return m;
+}
+
+// The first layer's filter as the lanes of k_espcn_pair hold it: wave c1 of two writes, for its 32-channel chunk, lane
+// `lane`'s fp16 planes of channel fragment nf and K step ks (tap pairs 4 ks + kq; K = tap pair x 4 channel slots) at the
+// filter's scale; wave 0 adds sum |w_c|, |b_c| and the filter's maximum.
+__global__ __launch_bounds__(128) void k_espcn_pair_prep(const float* __restrict__ w1, const float* __restrict__ b1,
+                                                         uint4* __restrict__ out) {
+  const int lane = threadIdx.x & 63, c1 = threadIdx.x >> 6;
+  const int j = lane & 15, kq = lane >> 4;
+  float wsum = 0.f, wmax = 0.f;
+  {
+    const float* wc = w1 + lane * 75;
+    for (int i = 0; i < 75; ++i) {
+      const float a = fabsf(wc[i]);
+      wsum += a;
+      wmax = fmaxf(wmax, a);
+    }
+  }
+  const float wm = wave_max(wmax);
+  const float sw1 = exp2i(amax_scale_exp(wm));
+#pragma unroll
+  for (int nf = 0; nf < 2; ++nf) {
+    const int co = c1 * 32 + nf * 16 + j;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const int q = 4 * ks + kq, dy = q / 3, dx0 = 2 * (q - 3 * (q / 3));
+      float f[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int dx = dx0 + (e >> 2), ci = e & 3;
+        const bool on = q < 15 && ci < 3 && dx < 5;   // (the load's index stays inside w1 either way)
+        f[e] = on ? w1[((co * 3 + (on ? ci : 0)) * 5 + (on ? dy : 0)) * 5 + (on ? dx : 0)] : 0.f;
+      }
+      uint4 pl[2];
+      split8h(f, sw1, pl);
+      out[(((c1 * 2 + nf) * 4 + ks) * 2 + 0) * 64 + lane] = pl[0];
+      out[(((c1 * 2 + nf) * 4 + ks) * 2 + 1) * 64 + lane] = pl[1];
+    }
+  }
+  if (c1 == 0) {
+    float* t = reinterpret_cast<float*>(out + PR_W1P);
+    t[lane] = wsum;
+    t[64 + lane] = fabsf(b1[lane]);
+    if (lane == 0) t[128] = wm;
+  }
+}
+
 __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
   extern __shared__ __attribute__((aligned(16))) uint4 smem4[];
   uint4* wl2 = smem4;
@@ -112,52 +214,56 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
   const int j = lane & 15, kq = lane >> 4;
   uint2* xin = xin_all + grp * PR_XBUF;
 
-  // ---- scales: input (measured maximum), first-layer filter (its maximum), intermediate (bound) ----------------------
-  const float xmax = amax_read(B.x_amax);
-  const int kx = amax_scale_exp(xmax);
-  float wsum = 0.f, wmax = 0.f;
-  {
-    const float* wc = B.w1 + lane * 75;
-    for (int i = 0; i < 75; ++i) {
-      const float a = fabsf(wc[i]);
-      wsum += a;
-      wmax = fmaxf(wmax, a);
-    }
-  }
-  const float bnd = wave_max(fabsf(B.b1[lane]) + wsum * xmax);
-  const int kw1 = amax_scale_exp(wave_max(wmax));
-  const int km = amax_scale_exp(bnd);
-  const float sx1 = exp2i(kx), sw1 = exp2i(kw1), sxm = exp2i(km);
-  const float dsc1 = exp2i(-kx) * exp2i(-kw1);
-  const float dsc2 = exp2i(-km) * B.w2_descale[0];
-
-  // ---- second layer's filter into LDS, counters -----------------------------------------------------------------------
-  for (int e = tid; e < PR_WL2; e += 512) wl2[e] = B.wq2[e];
+  // ---- max|x|: handed in, or this block's slice of it on its way to the slots (the other blocks' comes back below) --------
+  const float* w1t = reinterpret_cast<const float*>(B.w1p + PR_W1P);   // sum |w_c| [64], |b_c| [64], max |w|
+  const int nblk = gridDim.x;
+  float xmax = 0.f;
   if (tid < 14) cnt[tid] = 0u;
+  if (B.amax_mode) {
+    float* red = reinterpret_cast<float*>(xin_all);   // (free until the first tile is staged)
+    const size_t n4 = B.xn >> 2;
+    const float m = wave_max(pr_slice_absmax(B.x, (size_t)blockIdx.x * n4 / nblk, (size_t)(blockIdx.x + 1) * n4 / nblk, B.xn,
+                                             blockIdx.x == 0, tid, 512));
+    if (lane == 0) red[wave] = m;
+    __syncthreads();
+    if (tid == 0) {
+      float b = red[0];
+#pragma unroll
+      for (int i = 1; i < 8; ++i) b = fmaxf(b, red[i]);
+      // The arrival is issued once the maximum has RETURNED, i.e. has been performed where agent-scope atomics are (beyond
+      // the XCD's L2); the readers use agent-scope atomic loads.  No fence: at agent scope it writes back and invalidates
+      // the XCD's L2, which cost the rendezvous 10 us.
+      const unsigned was = atomicMax(reinterpret_cast<unsigned*>(B.x_amax + (blockIdx.x & 15) * 16), __float_as_uint(b));
+      asm volatile("s_waitcnt vmcnt(0)" ::"v"(was) : "memory");
+      __hip_atomic_fetch_add(reinterpret_cast<unsigned*>(B.x_amax) + PR_ARRIVE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  } else {
+    xmax = amax_read(B.x_amax);
+  }
+
+  // ---- second layer's filter into LDS: a thread's nine loads in flight before its first LDS store (as a plain loop they are
+  // nine L2 round trips in a row, conv_bfr.hip) -------------------------------------------------------------------------
+  {
+    static_assert(PR_WL2 == 9 * 512, "k_espcn_pair: filter copy");
+    v4u_t wv[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) wv[i] = *reinterpret_cast<const v4u_t*>(B.wq2 + tid + 512 * i);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) *reinterpret_cast<v4u_t*>(wl2 + tid + 512 * i) = wv[i];
+  }
 
   // ---- first layer: chunk c1 = channels 32 c1 .. 32 c1 + 31 as two 16-channel fragments, half mh of the pixel fragments -----
-  // filter fragments: channel 32 c1 + 16 nf + j, K step ks = tap pairs 4 ks + kq
+  // filter fragments: channel 32 c1 + 16 nf + j, K step ks = tap pairs 4 ks + kq (prepared: k_espcn_pair_prep)
   const int c1 = gw >> 1, mh = gw & 1;
+  const int mhu = __builtin_amdgcn_readfirstlane(mh), rhu = __builtin_amdgcn_readfirstlane(gw >> 1);  // (dead-row branches)
   uint4 w1f[2][4][2];  // [channel fragment][K step][plane]
 #pragma unroll
-  for (int nf = 0; nf < 2; ++nf) {
-    const int co = c1 * 32 + nf * 16 + j;
+  for (int nf = 0; nf < 2; ++nf)
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const int q = 4 * ks + kq, dy = q / 3, dx0 = 2 * (q - 3 * (q / 3));
-      float f[8];
+    for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int dx = dx0 + (e >> 2), ci = e & 3;
-        const bool on = q < 15 && ci < 3 && dx < 5;   // (the load's index stays inside w1 either way)
-        f[e] = on ? B.w1[((co * 3 + (on ? ci : 0)) * 5 + (on ? dy : 0)) * 5 + (on ? dx : 0)] : 0.f;
-      }
-      uint4 pl[2];
-      split8h(f, sw1, pl);
-      w1f[nf][ks][0] = pl[0];
-      w1f[nf][ks][1] = pl[1];
-    }
-  }
+      for (int pl = 0; pl < 2; ++pl) w1f[nf][ks][pl] = B.w1p[(((c1 * 2 + nf) * 4 + ks) * 2 + pl) * 64 + lane];
+  const float wsum = w1t[lane], babs = w1t[64 + lane];
   // Rows 2 .. 9 of the halo are nine 16-pixel fragments, pixel 16 f + j of the 144: the wave takes f = 4 mh + m, m < 4, and
   // every other own tile the ninth as m = 4.  Rows 0 .. 1 (36 pixels) are three fragments: f = 2 mh + m, m < 2.
   // Offsets in staged pixels: K step -> tap pair (dy, dx); fragment -> pixel (the top ones clamped to pixel 35).
@@ -197,7 +303,7 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
 
   // ---- tiles of this block: a contiguous run of the column-major order (image, tile column, tile row), runs of equal
   // length +-1; the blocks of an XCD take neighbouring runs ------------------------------------------------------------
-  const int nblk = gridDim.x, xcd = blockIdx.x & 7;
+  const int xcd = blockIdx.x & 7;
   int first, count;
   {
     const int lb = xcd * (nblk >> 3) + (xcd < (nblk & 7) ? xcd : (nblk & 7)) + (blockIdx.x >> 3);
@@ -252,7 +358,61 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
   bool dead = false;
   float amax = 0.f;
   xload(grp);
-  __syncthreads();  // filter and counters visible
+  // ---- max|x| of all blocks: the first wave polls for their arrivals, reads the slots, leaves (the last one to leave
+  // zeroes the two counter words: a captured launch replays) ---------------------------------------------------------------
+  if (B.amax_mode && wave == 0) {
+    unsigned* ctr = reinterpret_cast<unsigned*>(B.x_amax);
+    bool late = B.amax_mode == 2;
+    if (!late) {
+      unsigned spins = 0;
+      while ((int)((unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(ctr + PR_ARRIVE, __ATOMIC_RELAXED,
+                                                                                   __HIP_MEMORY_SCOPE_AGENT)) -
+                   (unsigned)nblk) < 0) {
+        __builtin_amdgcn_s_sleep(16);
+        if (++spins > PR_AMAX_CAP) {
+          late = true;
+          break;
+        }
+      }
+    }
+    asm volatile("" ::: "memory");
+    // agent-scope atomic loads, served where the atomics land (amax_peek); issued behind the poll that saw the last arrival
+    const float sv = wave_max(__hip_atomic_load(B.x_amax + (lane & 15) * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    if (lane == 0) {
+      cnt[14] = __float_as_uint(sv);
+      cnt[15] = late ? 1u : 0u;
+      const unsigned d = __hip_atomic_fetch_add(ctr + PR_DEPART, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (d + 1u == (unsigned)nblk) {   // every block has arrived and finished polling
+        __hip_atomic_store(ctr + PR_ARRIVE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(ctr + PR_DEPART, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+  __syncthreads();  // filter, counters and max|x| visible
+  if (B.amax_mode) {
+    xmax = __uint_as_float(pr_peek(cnt + 14));
+    if (pr_peek(cnt + 15)) {
+      // The slots may lack a block that has not arrived: scan all of x here.  (With the slots, which hold every earlier
+      // launch's maximum, that is the running maximum the other blocks see.)
+      float* red = reinterpret_cast<float*>(xin_all);
+      const float m = wave_max(pr_slice_absmax(B.x, 0, B.xn >> 2, B.xn, true, tid, 512));
+      if (lane == 0) red[wave] = m;
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < 8; ++i) xmax = fmaxf(xmax, red[i]);
+      xmax = __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(xmax)));
+      __syncthreads();  // red is the first staged tile
+      if (tid == 0) atomicAdd(&g_pair_scans, 1u);
+    }
+  }
+  // ---- scales: input (its maximum), first-layer filter (its maximum), intermediate (bound) --------------------------
+  const int kx = amax_scale_exp(xmax);
+  const float bnd = wave_max(fabsf(babs) + wsum * xmax);
+  const int kw1 = amax_scale_exp(w1t[128]);
+  const int km = amax_scale_exp(bnd);
+  const float sx1 = exp2i(kx), sxm = exp2i(km);
+  const float dsc1 = exp2i(-kx) * exp2i(-kw1);
+  const float dsc2 = exp2i(-km) * B.w2_descale[0];
 
   unsigned own = 0;  // own tiles done
   unsigned kseq = 0;
@@ -331,10 +491,20 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
         if (mpix[m] >= PR_NSLOTPIX) l1_store(a1[m], kp, mpix[m] - PR_NSLOTPIX, PR_KP);
       pr_signal(cnt + 8 + kb);
     };
-    if (mh == (int)(own & 1))
+    // Live rows of this tile; halo rows >= vr + 2 reach no stored value (file header).  A wave whose fragments all lie there
+    // -- pixel half 1 starts in halo row 5 -- only keeps the counters going.
+    const int vr = B.OH - ty * PR_TH;
+    if (mhu == 1 && vr <= 3) {
+      const unsigned st = 2u * (unsigned)i + c1, slot = st % PR_NSLOT, use = st / PR_NSLOT;
+      pr_wait(cnt + 3 + slot, 4u * use, dead);
+      pr_signal(cnt + slot);
+      pr_wait(cnt + 11 + kb, 8u * ku, dead);
+      pr_signal(cnt + 8 + kb);
+    } else if (mh == (int)(own & 1)) {
       l1_tile(std::integral_constant<int, 5>{});
-    else
+    } else {
       l1_tile(std::integral_constant<int, 4>{});
+    }
     if (fresh) {  // rows 0 .. 1 computed here
       f32x4 at[2][2];
       l1_frags(std::integral_constant<int, 2>{}, toff, at);
@@ -347,58 +517,69 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
     }
 
     // -- second layer out of the ring and the kept rows --------------------------------------------------------------
-    f32x4 acc[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = (f32x4){0.f, 0.f, 0.f, 0.f};
     pr_wait(cnt + 8 + (rh == 0 ? tb : kb), 4u * ((rh == 0 ? tu : ku) + 1u), dead);
+    if (rhu == 1 && vr <= 4) {  // output rows 4 .. 7 lie below the output: waits and signals only
 #pragma unroll
-    for (int cc = 0; cc < 2; ++cc) {
-      const unsigned st = 2u * (unsigned)i + cc, slot = st % PR_NSLOT, use = st / PR_NSLOT;
-      pr_wait(cnt + slot, 2u * (use + 1), dead);
-      const uint4* hb = ring + slot * PR_HBUF + lane_b;
-      // the wave's rows out of kept rows: R = 0, 1 (rh == 0: rows 0 .. 1), R = 4, 5 (rh == 1: rows 8 .. 9)
-      const uint4* kr = keep + (rh == 0 ? tb : kb) * PR_KBUF + cc * 4 * PR_KP + lane_k - (rh == 0 ? 0 : 4 * PR_HW);
-      const uint4* pa = rh == 0 ? kr : hb;
-      const uint4* pc = rh == 0 ? hb : kr;
+      for (int cc = 0; cc < 2; ++cc) {
+        const unsigned st = 2u * (unsigned)i + cc, slot = st % PR_NSLOT, use = st / PR_NSLOT;
+        pr_wait(cnt + slot, 2u * (use + 1), dead);
+        pr_signal(cnt + 3 + slot);
+      }
+      pr_signal(cnt + 11 + tb, fresh ? 2u : 1u);
+      pr_signal(cnt + 11 + kb, hand ? 1u : 2u);
+    } else {
+      f32x4 acc[4];
 #pragma unroll
-      for (int v = 0; v < 3; ++v) {
-        uint4 fa[3][2];
+      for (int r = 0; r < 4; ++r) acc[r] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int u = 0; u < 3; ++u) {
-          fa[u][0] = wl2[((u * 3 + v) * 2 + cc) * 256 + lane_a];
-          fa[u][1] = wl2[((u * 3 + v) * 2 + cc) * 256 + 128 + lane_a];
-        }
+      for (int cc = 0; cc < 2; ++cc) {
+        const unsigned st = 2u * (unsigned)i + cc, slot = st % PR_NSLOT, use = st / PR_NSLOT;
+        pr_wait(cnt + slot, 2u * (use + 1), dead);
+        const uint4* hb = ring + slot * PR_HBUF + lane_b;
+        // the wave's rows out of kept rows: R = 0, 1 (rh == 0: rows 0 .. 1), R = 4, 5 (rh == 1: rows 8 .. 9)
+        const uint4* kr = keep + (rh == 0 ? tb : kb) * PR_KBUF + cc * 4 * PR_KP + lane_k - (rh == 0 ? 0 : 4 * PR_HW);
+        const uint4* pa = rh == 0 ? kr : hb;
+        const uint4* pc = rh == 0 ? hb : kr;
 #pragma unroll
-        for (int R = 0; R < 6; ++R) {
-          const uint4* px = R < 2 ? pa : (R < 4 ? hb : pc);
-          const uint4 xh = px[R * PR_HW + v], xm = px[R * PR_HW + v + PR_PLANE];
+        for (int v = 0; v < 3; ++v) {
+          uint4 fa[3][2];
 #pragma unroll
           for (int u = 0; u < 3; ++u) {
-            const int r = R - u;
-            if (r >= 0 && r < 4) {
-              acc[r] = mfma16h(fa[u][0], xm, acc[r]);
-              acc[r] = mfma16h(fa[u][1], xh, acc[r]);
-              acc[r] = mfma16h(fa[u][0], xh, acc[r]);
+            fa[u][0] = wl2[((u * 3 + v) * 2 + cc) * 256 + lane_a];
+            fa[u][1] = wl2[((u * 3 + v) * 2 + cc) * 256 + 128 + lane_a];
+          }
+#pragma unroll
+          for (int R = 0; R < 6; ++R) {
+            const uint4* px = R < 2 ? pa : (R < 4 ? hb : pc);
+            const uint4 xh = px[R * PR_HW + v], xm = px[R * PR_HW + v + PR_PLANE];
+#pragma unroll
+            for (int u = 0; u < 3; ++u) {
+              const int r = R - u;
+              if (r >= 0 && r < 4) {
+                acc[r] = mfma16h(fa[u][0], xm, acc[r]);
+                acc[r] = mfma16h(fa[u][1], xh, acc[r]);
+                acc[r] = mfma16h(fa[u][0], xh, acc[r]);
+              }
             }
           }
         }
+        pr_signal(cnt + 3 + slot);
       }
-      pr_signal(cnt + 3 + slot);
-    }
-    pr_signal(cnt + 11 + tb, fresh ? 2u : 1u);
-    pr_signal(cnt + 11 + kb, hand ? 1u : 2u);
-    // -- epilogue: bias, ReLU, NHWC stores of the pixels inside the output, running maximum -----------------------------
-    const int oc = tx * PR_TW + pj;
+      pr_signal(cnt + 11 + tb, fresh ? 2u : 1u);
+      pr_signal(cnt + 11 + kb, hand ? 1u : 2u);
+      // -- epilogue: bias, ReLU, NHWC stores of the pixels inside the output, running maximum -----------------------------
+      const int oc = tx * PR_TW + pj;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int orow = ty * PR_TH + 4 * rh + r;
-      const bool ok = oc < B.OW && orow < B.OH;
-      f32x4 v;
+      for (int r = 0; r < 4; ++r) {
+        const int orow = ty * PR_TH + 4 * rh + r;
+        const bool ok = oc < B.OW && orow < B.OH;
+        f32x4 v;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = fmaxf(__builtin_fmaf(acc[r][e], dsc2, b2v[e]), 0.f);
-      if (ok) amax = fmaxf(amax, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
-      const unsigned o = ok ? 4u * (unsigned)(((n * B.OH + orow) * B.OW + oc) * 32 + nf2 * 16 + 4 * kq) : 0x80000000u;
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_t, v), yr, (int)o, 0, 0);
+        for (int e = 0; e < 4; ++e) v[e] = fmaxf(__builtin_fmaf(acc[r][e], dsc2, b2v[e]), 0.f);
+        if (ok) amax = fmaxf(amax, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+        const unsigned o = ok ? 4u * (unsigned)(((n * B.OH + orow) * B.OW + oc) * 32 + nf2 * 16 + 4 * kq) : 0x80000000u;
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_t, v), yr, (int)o, 0, 0);
+      }
     }
   }
   if (B.y_amax) amax_commit(B.y_amax, amax, blockIdx.x + wave, amax_peek(B.y_amax, blockIdx.x + wave));
@@ -408,8 +589,8 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
 }  // namespace
 
 // -1: not this kernel's problem.  force: skip the efficiency terms of the rule (tests).
-int espcn_pair_launch(int N, int H, int W, const float* x, const float* w1, const float* b1, const void* wp2,
-                      const float* b2, float* y, const float* x_amax, float* y_amax, bool force, hipStream_t s) {
+int espcn_pair_launch(int N, int H, int W, const float* x, const void* w1p, const float* b1, const void* wp2,
+                      const float* b2, float* y, float* x_amax, int amax_mode, float* y_amax, bool force, hipStream_t s) {
   if (N < 1 || H < 7 || W < 7 || !x_amax) return -1;
   const int OH = H - 6, OW = W - 6;
   const int tiles_y = (OH + PR_TH - 1) / PR_TH, tiles_x = (OW + PR_TW - 1) / PR_TW;
@@ -425,7 +606,9 @@ int espcn_pair_launch(int N, int H, int W, const float* x, const float* w1, cons
   const char* prepared = reinterpret_cast<const char*>(wp2) + bf3_prepared_offset(elems);
   const char* fsec = prepared + f16_section_offset(64, 32, 9);
   PairParams B{};
-  B.x = x; B.w1 = w1; B.b1 = b1; B.b2 = b2; B.y = y; B.x_amax = x_amax; B.y_amax = y_amax;
+  B.x = x; B.w1p = reinterpret_cast<const uint4*>(w1p); B.b1 = b1; B.b2 = b2; B.y = y; B.x_amax = x_amax; B.y_amax = y_amax;
+  B.xn = (size_t)N * 3 * H * W;
+  B.amax_mode = amax_mode;
   B.wq2 = reinterpret_cast<const uint4*>(fsec);
   B.w2_descale = reinterpret_cast<const float*>(fsec + bf3_main_bytes(64, 32, 9));
   B.N = N; B.H = H; B.W = W; B.OH = OH; B.OW = OW; B.tiles_y = tiles_y; B.img_tiles = tiles_x * tiles_y;
@@ -455,14 +638,44 @@ int pair_ring_timeouts(int reset) {  // (srk_ring_timeouts, conv_bfr.hip)
   return (int)v;
 }
 
+int pair_scans(int reset) {
+  unsigned v = 0;
+  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_pair_scans), sizeof(v)) != hipSuccess) {
+    (void)hipGetLastError();
+    return -1;
+  }
+  if (reset && v) {
+    const unsigned z = 0;
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_pair_scans), &z, sizeof(z));
+  }
+  return (int)v;
+}
+
+int espcn_pair_prepare(const float* w1, const float* b1, void* out, hipStream_t s) {
+  hipLaunchKernelGGL(k_espcn_pair_prep, dim3(1), dim3(128), 0, s, w1, b1, reinterpret_cast<uint4*>(out));
+  return check_launch("espcn_pair_prepare");
+}
+size_t espcn_pair_prepared_bytes() { return PR_W1P_BYTES; }
+
 }  // namespace srk
 
-extern "C" int srk_espcn_pair_forward(int N, int H, int W, const float* x, const float* w1, const float* b1,
-                                      const float* w2_packed_fwd, const float* b2, float* y, const float* x_amax,
-                                      float* y_amax, int force, void* stream) {
-  if (!x || !w1 || !b1 || !w2_packed_fwd || !b2 || !y || !x_amax) return SRK_ERR_UNSUPPORTED;
-  if (((uintptr_t)x | (uintptr_t)y) % 16 != 0) return SRK_ERR_UNSUPPORTED;
-  const int rc = srk::espcn_pair_launch(N, H, W, x, w1, b1, w2_packed_fwd, b2, y, x_amax, y_amax, force != 0,
-                                        (hipStream_t)stream);
+extern "C" size_t srk_espcn_pair_prepared_bytes(void) { return srk::espcn_pair_prepared_bytes(); }
+
+extern "C" int srk_espcn_pair_prepare(const float* w1, const float* b1, void* w1_prepared, void* stream) {
+  SRK_REQUIRE(w1 && b1 && w1_prepared, "espcn_pair_prepare: null pointer");
+  SRK_REQUIRE((uintptr_t)w1_prepared % 16 == 0, "espcn_pair_prepare: w1_prepared must be 16-byte aligned");
+  return srk::espcn_pair_prepare(w1, b1, w1_prepared, (hipStream_t)stream);
+}
+
+extern "C" int srk_espcn_pair_scans(int reset) { return srk::pair_scans(reset); }
+
+extern "C" int srk_espcn_pair_forward(int N, int H, int W, const float* x, const void* w1_prepared, const float* b1,
+                                      const float* w2_packed_fwd, const float* b2, float* y, float* x_amax,
+                                      int x_amax_compute, float* y_amax, int force, void* stream) {
+  if (!x || !w1_prepared || !b1 || !w2_packed_fwd || !b2 || !y || !x_amax) return SRK_ERR_UNSUPPORTED;
+  if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)w1_prepared) % 16 != 0) return SRK_ERR_UNSUPPORTED;
+  const int mode = x_amax_compute ? ((force & 2) ? 2 : 1) : 0;
+  const int rc = srk::espcn_pair_launch(N, H, W, x, w1_prepared, b1, w2_packed_fwd, b2, y, x_amax, mode, y_amax,
+                                        (force & 1) != 0, (hipStream_t)stream);
   return rc == -1 ? SRK_ERR_UNSUPPORTED : rc;
 }

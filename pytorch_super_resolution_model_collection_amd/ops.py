@@ -843,13 +843,36 @@ def conv2d_infer(x, weight, bias=None, residual=None, cfg=None, prelu_w=None, pa
 
 # ---- ESPCN's first two convs in one launch (srk_espcn_pair_forward, conv_pair.hip) ------------------------------------
 ESPCN_PAIR = True   # False: ESPCNNet.forward always runs its first two convs as separate launches
+# An input without a maximum of its own is measured inside the fused launch up to this many bytes and by one srk_absmax
+# pass in front of it above.  Inside the launch the maximum costs a chain of device-scope atomic round trips (about 8 us)
+# plus the slice read at HBM speed, with nothing to hide behind; the pass costs 4 us plus its read on a busy queue, but a
+# launch of its own where the host is the limit (34 against 37 us at 1.6 MB, the sizes between the library's
+# efficiency rule and this threshold; 49 against 45 at 3 MB, 141 against 139 at 13 MB, 533 against 532 at c2's 50 MB).
+PAIR_AMAX_IN_LAUNCH_BYTES = 2 << 20
 
 
-def espcn_pair(x, block1, block2, force=False):
+def _pair_prepared(conv):
+    """What srk_espcn_pair_prepare makes of the first layer's filter and bias, cached on the module the way its _PackCache
+    keeps the packed filter: keyed by tensor and version."""
+    from . import layers   # (layers imports this module)
+    w, b = conv.weight, conv.bias
+    key = (w.data_ptr(), _ver(w), b.data_ptr(), _ver(b), layers._WEIGHT_EPOCH[0], str(w.device))
+    ent = getattr(conv, "_pair_prep", None)
+    if ent is None or ent[0] != key:
+        lib = _lib.load()
+        buf = torch.empty((lib.srk_espcn_pair_prepared_bytes() + 3) // 4, dtype=torch.float32, device=w.device)
+        check(lib.srk_espcn_pair_prepare(ptr(w.detach().contiguous()), ptr(b.detach().contiguous()), ptr(buf),
+                                         stream_ptr()), "srk_espcn_pair_prepare")
+        ent = conv._pair_prep = (key, buf)
+    return ent[1]
+
+
+def espcn_pair(x, block1, block2, force=False, scan=False):
     """relu(conv3x3(relu(conv5x5(x)))) of ESPCN's first two ConvBlocks as ONE launch (the 64-channel map between them
     stays on chip), or None where that kernel does not apply -- the caller then runs the blocks one by one.  Inference
-    only, f16x3 arithmetic (the fp32-faithful class both layers run in on their own).  force: skip the library's
-    efficiency rule (tests)."""
+    only, f16x3 arithmetic (the fp32-faithful class both layers run in on their own).  An x without a fresh maximum gets
+    it inside the launch (no srk_absmax pass; up to PAIR_AMAX_IN_LAUNCH_BYTES) and is tagged with it afterwards.  force:
+    skip the library's efficiency rule (tests).  scan: every block measures max|x| on the kernel's timeout path (tests)."""
     c1, c2 = block1.conv, block2.conv
     if not F16X3 or x.dim() != 4 or os.environ.get("SRK_FORCE_ALGO"):
         return None
@@ -872,17 +895,28 @@ def espcn_pair(x, block1, block2, force=False):
     if not (x.dtype == torch.float32 and x.is_cuda and _is_nchw_dense(x)) or x.data_ptr() % 16:
         return None
     require_cuda(x, c1.weight, c1.bias, c2.weight, c2.bias)
-    w1 = c1.weight.detach().contiguous()
+    w1p = _pair_prepared(c1)
     b1 = c1.bias.detach().contiguous()
     wp2, bp2 = c2._cache.get(c2.weight, c2.bias, False, 0)
-    xa = amax_of(x)
+    a = getattr(x, "_srk_amax", None)   # a producer's maximum, a declared one, an earlier call's
+    xa = a[0] if a is not None and a[1] == _ver(x) and a[2] == _AMAX_EPOCH[0] else None
+    if xa is None and x.numel() * 4 > PAIR_AMAX_IN_LAUNCH_BYTES:
+        xa = amax_of(x)
+    measure = xa is None
+    if measure:
+        xa = _amax_alloc(x.device)   # zeroed: the kernel raises it
     y = _empty_cl(n, 32, h - 6, w - 6, x)
     ya = _amax_alloc(y.device)
-    rc = _lib.load().srk_espcn_pair_forward(n, h, w, ptr(x), ptr(w1), ptr(b1), ptr(wp2), ptr(bp2), ptr(y), ptr(xa),
-                                            ptr(ya), int(bool(force)), stream_ptr())
+    rc = _lib.load().srk_espcn_pair_forward(n, h, w, ptr(x), ptr(w1p), ptr(b1), ptr(wp2), ptr(bp2), ptr(y), ptr(xa),
+                                            int(measure), ptr(ya), int(bool(force)) | (2 if scan else 0), stream_ptr())
     if rc == _lib.ERR_UNSUPPORTED:
-        return None
+        return None   # (nothing was launched: a buffer taken for the maximum is still zero and simply not used)
     check(rc, "srk_espcn_pair_forward")
+    if measure:
+        try:
+            _tag_amax(x, xa)
+        except Exception:  # noqa: BLE001 -- (a tensor subclass without a __dict__: measured again next time)
+            pass
     _tag_amax(y, ya)
     return y
 
