@@ -302,6 +302,14 @@ extern "C" int srk_conv_out_dim(int in, int k, int stride, int pad, int transpos
   return (in - 1) * stride - 2 * pad + k + out_pad;
 }
 
+// The forward pass as a gather, and dx as a gather over dy: channel roles swapped, the opposite gather kind.
+static GatherConv fwd_gather(const srk_conv_desc* d) {
+  return GatherConv{d->N, d->H, d->W, d->Cin, d->OH, d->OW, d->Cout, d->KH, d->KW, d->stride, d->pad, d->transposed, 0};
+}
+static GatherConv bwd_data_gather(const srk_conv_desc* d) {
+  return GatherConv{d->N, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride, d->pad, !d->transposed, 0, 0};
+}
+
 extern "C" int srk_conv2d_forward(const srk_conv_desc* d, const float* x, const float* w_packed_fwd, float* y,
                                   const srk_epilogue* ep_in, void* stream) {
   note_amax_written(false);
@@ -320,7 +328,7 @@ extern "C" int srk_conv2d_forward(const srk_conv_desc* d, const float* x, const 
     SRK_REQUIRE(ep.act != SRK_ACT_PRELU || ep.prelu_n == 1 || ep.prelu_n == d->Cout,
                 "conv2d_forward: PReLU must have 1 or Cout slopes");
   }
-  GatherConv g{d->N, d->H, d->W, d->Cin, d->OH, d->OW, d->Cout, d->KH, d->KW, d->stride, d->pad, d->transposed, 0};
+  GatherConv g = fwd_gather(d);
   SRK_REQUIRE(d->dy_ps_r == 0, "conv2d_forward: dy_ps_r is a backward-only field");
   if (d->x_nchw) {
     // only the row-packed bf16x3 first-layer kernel reads an NCHW input in place
@@ -354,7 +362,7 @@ extern "C" int srk_conv2d_f16x3_supported(const srk_conv_desc* d, const srk_epil
   Epi ep = make_epi(ep_in);
   static const float dummy = 0.f;
   if (!ep.x_amax) ep.x_amax = &dummy;   // (the question is about the shape; the call itself needs the real slots)
-  GatherConv g{d->N, d->H, d->W, d->Cin, d->OH, d->OW, d->Cout, d->KH, d->KW, d->stride, d->pad, d->transposed, 0};
+  GatherConv g = fwd_gather(d);
   g.in_nchw = d->x_nchw;
   return f16x3_gather_ok(g, ep, reinterpret_cast<const float*>(16), y ? y : reinterpret_cast<const float*>(16)) ? 1 : 0;
 }
@@ -366,8 +374,7 @@ extern "C" int srk_conv2d_backward_data(const srk_conv_desc* d, const float* dy,
   SRK_REQUIRE(d->algo != SRK_ALGO_MFMA_F16X3, "conv2d_backward_data: SRK_ALGO_MFMA_F16X3 is a forward-only arithmetic "
               "(the backward kernels run bf16x3)");
   SRK_REQUIRE(dy && w_packed_bwd && dx, "conv2d_backward_data: null tensor pointer");
-  // dx is a gather over dy with the channel roles swapped and the opposite gather kind.
-  GatherConv g{d->N, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride, d->pad, !d->transposed, 0, 0};
+  GatherConv g = bwd_data_gather(d);
   if (d->dy_ps_r > 1) {
     const int r2 = d->dy_ps_r * d->dy_ps_r;
     SRK_REQUIRE(d->Cout % r2 == 0 && (d->Cout / r2) % 8 == 0, "conv2d_backward_data: dy_ps_r needs Cout/r^2 to be a multiple of 8");
@@ -377,10 +384,6 @@ extern "C" int srk_conv2d_backward_data(const srk_conv_desc* d, const float* dy,
   ep.residual = add_to;
   return run_gather(g, d->algo, dy, w_packed_bwd, dx, ep, mask ? mask->y : nullptr, mask ? mask->slope : 0.f,
                     (hipStream_t)stream, "conv2d_backward_data");
-}
-
-static GatherConv bwd_data_gather(const srk_conv_desc* d) {
-  return GatherConv{d->N, d->OH, d->OW, d->Cout, d->H, d->W, d->Cin, d->KH, d->KW, d->stride, d->pad, !d->transposed, 0, 0};
 }
 
 extern "C" int srk_conv2d_backward_data_relu_supported(const srk_conv_desc* d, const float* dy, const float* dx,

@@ -665,17 +665,13 @@ static int bfd_launch(BfdParams B, int budget_bytes, hipStream_t s) {
         if (lds < epi_bytes) lds = epi_bytes;
       }
       if (lds < red_bytes) lds = red_bytes;
-      static LdsLimit lim2;
-      lim2.ensure(reinterpret_cast<const void*>(&k_conv_bfd<NTW, NPW, NOW, NP, PF, 2, F16, OCCX>), lds);
       note_kernel("k_conv_bfd<%d,%d,%d,%d,%d,2%s>", NTW, NPW, NOW, NP, PF, F16 ? ",f16" : "");
-      hipLaunchKernelGGL((k_conv_bfd<NTW, NPW, NOW, NP, PF, 2, F16, OCCX>), grid, dim3(64 * NPW * NOW * 2), lds, s, B);
+      launch_lds<&k_conv_bfd<NTW, NPW, NOW, NP, PF, 2, F16, OCCX>>(grid, dim3(64 * NPW * NOW * 2), lds, s, B);
       return check_launch("conv_bfd");
     }
   }
-  static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&k_conv_bfd<NTW, NPW, NOW, NP, PF, 1, F16, OCCX>), lds);
   note_kernel("k_conv_bfd<%d,%d,%d,%d,%d,1%s%s>", NTW, NPW, NOW, NP, PF, F16 ? ",f16" : "", OCCX == 3 ? ",occ3" : (OCCX == 4 ? ",occ4" : ""));
-  hipLaunchKernelGGL((k_conv_bfd<NTW, NPW, NOW, NP, PF, 1, F16, OCCX>), grid, dim3(64 * NPW * NOW), lds, s, B);
+  launch_lds<&k_conv_bfd<NTW, NPW, NOW, NP, PF, 1, F16, OCCX>>(grid, dim3(64 * NPW * NOW), lds, s, B);
   return check_launch("conv_bfd");
 }
 
@@ -747,15 +743,11 @@ static int bfd_launch_small_multi(const MfmaConvParams* phases, int nph, const B
   note_amax_written(base.P.ep.y_amax != nullptr);
   dim3 grid((unsigned)total, (unsigned)OCb);
   if (ks2) {
-    static LdsLimit lim2;
-    lim2.ensure(reinterpret_cast<const void*>(&k_conv_bfd_mp<NTW, NPW, NOW, NP, PF, 2>), lds_max);
     note_kernel("k_conv_bfd_mp<%d,%d,%d,%d,%d,2>x%d", NTW, NPW, NOW, NP, PF, nph);
-    hipLaunchKernelGGL((k_conv_bfd_mp<NTW, NPW, NOW, NP, PF, 2>), grid, dim3(64 * NPW * NOW * 2), lds_max, s, M);
+    launch_lds<&k_conv_bfd_mp<NTW, NPW, NOW, NP, PF, 2>>(grid, dim3(64 * NPW * NOW * 2), lds_max, s, M);
   } else {
-    static LdsLimit lim;
-    lim.ensure(reinterpret_cast<const void*>(&k_conv_bfd_mp<NTW, NPW, NOW, NP, PF, 1>), lds_max);
     note_kernel("k_conv_bfd_mp<%d,%d,%d,%d,%d,1>x%d", NTW, NPW, NOW, NP, PF, nph);
-    hipLaunchKernelGGL((k_conv_bfd_mp<NTW, NPW, NOW, NP, PF, 1>), grid, dim3(64 * NPW * NOW), lds_max, s, M);
+    launch_lds<&k_conv_bfd_mp<NTW, NPW, NOW, NP, PF, 1>>(grid, dim3(64 * NPW * NOW), lds_max, s, M);
   }
   return check_launch("conv_bfd_mp");
 }

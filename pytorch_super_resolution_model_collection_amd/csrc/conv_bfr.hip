@@ -34,13 +34,10 @@ constexpr int BFR_MAXBUF = 6;
 constexpr int BFR_CNT_BYTES = 128;  // counters behind the ring: full[6], free[6]; fused: scale exponents, staging / compute counts, tile maxima
 constexpr int BFR_PIT = 3;  // producer register batches per set: the 180-pixel halo in 64-pixel batches
 constexpr int BFR_NSET = 3;  // register sets = stages of loads in flight per producer wave
-constexpr unsigned BFR_SPIN_CAP = 1u << 18;
 constexpr int BFR_TH = 8, BFR_TW = 16, BFR_HH = 10, BFR_HW = 18, BFR_NPIX = 180;
 constexpr int BFR_NPIXP = 190;  // = bfw_group_stride(180): +-2 (mod 16), conflict-free fragment reads and halo writes
 
 __device__ unsigned g_bfr_timeouts = 0;
-
-typedef __attribute__((address_space(3))) unsigned bfr_cnt_t;
 
 // A poll that ran into its cap means the ring protocol slipped (or the wave was starved beyond anything a profiler does):
 // whatever this tile holds is wrong.  Count it (srk_ring_timeouts, diagnostics) and ABORT the dispatch: the stream then
@@ -51,31 +48,6 @@ __device__ __noinline__ void bfr_fail(int lane) {
     __threadfence_system();
   }
   __builtin_trap();
-}
-
-__device__ __forceinline__ unsigned bfr_peek(bfr_cnt_t* p) {
-  return (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-}
-// wait until *p >= target (monotonic counters: the difference stays far below 2^31)
-__device__ __forceinline__ void bfr_wait(bfr_cnt_t* p, unsigned target, bool& dead) {
-  if (!dead) {
-    unsigned spins = 0;
-    while ((int)(bfr_peek(p) - target) < 0) {
-      __builtin_amdgcn_s_sleep(1);
-      if (++spins > BFR_SPIN_CAP) {
-        dead = true;
-        break;
-      }
-    }
-  }
-  asm volatile("" ::: "memory");
-}
-// One count behind every LDS access this wave has issued so far.  No s_waitcnt: the LDS executes the operations of one wave
-// in the order they were issued, so whoever sees the count sees the writes (or finds the reads done) that precede it.
-__device__ __forceinline__ void bfr_signal(bfr_cnt_t* p) {
-  asm volatile("" ::: "memory");
-  if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  asm volatile("" ::: "memory");
 }
 
 // (Round 5 carried a FUSE variant here -- the Cin <= 4 first layer computed by the producers straight into the ring,
@@ -112,7 +84,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_bfr(BfwParams B) {
   uint4* wl = smem4;
   uint4* hal0 = smem4 + 9 * ICC * WSLOT;
   const int nbuf = __builtin_amdgcn_readfirstlane(B.nbuf);
-  bfr_cnt_t* cnt = (bfr_cnt_t*)(hal0 + (size_t)nbuf * HBUF);  // full[BFR_MAXBUF], free[BFR_MAXBUF]
+  lds_cnt_t* cnt = (lds_cnt_t*)(hal0 + (size_t)nbuf * HBUF);  // full[BFR_MAXBUF], free[BFR_MAXBUF]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bool producer = wave >= NCW;
   const int j = lane & 15, kq = lane >> 4;
@@ -338,9 +310,9 @@ __global__ __launch_bounds__(512, 2) void k_conv_bfr(BfwParams B) {
       srk_static_for<0, NSET>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         if (s + i < S) {
-          bfr_wait(cnt + BFR_MAXBUF + b, NGW * k, dead);
+          lds_cnt_wait(cnt + BFR_MAXBUF + b, NGW * k, dead);
           commit(pv[i], hal0 + (size_t)b * HBUF);
-          bfr_signal(cnt + b);
+          lds_cnt_signal(cnt + b);
           if (++b == nbuf) {
             b = 0;
             ++k;
@@ -534,7 +506,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_bfr(BfwParams B) {
   using I1 = std::integral_constant<int, 1>;
   using I2 = std::integral_constant<int, 2>;
   if (grp < count) {  // the first own stage: nothing to overlap the wait and the first fragments with
-    bfr_wait(cnt + b, NPS * (k + 1), dead);
+    lds_cnt_wait(cnt + b, NPS * (k + 1), dead);
     ldA(I0{}, I0{}, I0{});
     ldB(hb, I0{});
     ldA(I1{}, I0{}, I0{});
@@ -582,8 +554,8 @@ __global__ __launch_bounds__(512, 2) void k_conv_bfr(BfwParams B) {
                 unsigned seen = (unsigned)__builtin_amdgcn_readfirstlane((int)peek_v), spins = 0;
                 while ((int)(seen - NPS * (nk + 1)) < 0) {
                   __builtin_amdgcn_s_sleep(1);
-                  seen = bfr_peek(cnt + nb);
-                  if (++spins > BFR_SPIN_CAP) {
+                  seen = lds_cnt_peek(cnt + nb);
+                  if (++spins > kLdsCntSpinCap) {
                     dead = true;
                     break;
                   }
@@ -597,7 +569,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_bfr(BfwParams B) {
             if constexpr (s == 8) peek_v = __hip_atomic_load(cnt + nb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             if constexpr (s == 15) {  // the slot's last fragment (step 17) has just been requested: hand the slot back (the LDS
                                       // executes one wave's operations in order: the count lands behind the reads)
-              bfr_signal(cnt + BFR_MAXBUF + b);
+              lds_cnt_signal(cnt + BFR_MAXBUF + b);
             }
             __builtin_amdgcn_sched_barrier(0);
           }
@@ -635,10 +607,8 @@ static int bfr_launch_cv(const BfwParams& B, size_t lds, int grid, hipStream_t s
   const bool omask = B.P.ep.out_relu != nullptr, res = B.P.ep.residual != nullptr;
   auto go = [&](auto f16c, auto omc, auto resc) {
     constexpr bool F = decltype(f16c)::value, O = decltype(omc)::value, R = decltype(resc)::value;
-    static LdsLimit lim;
-    lim.ensure(reinterpret_cast<const void*>(&k_conv_bfr<2, 2, F, true, O, R>), lds);
     note_kernel("k_conv_bfr<2,2%s,canvas%s%s%s>", F ? ",f16" : "", B.cv_sep ? "" : "0", O ? ",relu" : "", R ? ",res" : "");   // (canvas0: no separators)
-    hipLaunchKernelGGL((k_conv_bfr<2, 2, F, true, O, R>), dim3(grid), blk, lds, s, B);
+    launch_lds<&k_conv_bfr<2, 2, F, true, O, R>>(dim3(grid), blk, lds, s, B);
   };
   if (B.w_descale && res) go(std::true_type{}, std::false_type{}, std::true_type{});
   else if (B.w_descale) go(std::true_type{}, std::false_type{}, std::false_type{});
@@ -653,16 +623,12 @@ static int bfr_launch_t(const BfwParams& B, size_t lds, int grid, hipStream_t s)
   note_amax_written(B.P.ep.y_amax != nullptr);
   const dim3 blk(512);
   if (B.w_descale) {  // f16x3 arithmetic
-    static LdsLimit limh;
-    limh.ensure(reinterpret_cast<const void*>(&k_conv_bfr<NTW, ICC, true>), lds);
     note_kernel("k_conv_bfr<%d,%d,f16>", NTW, ICC);
-    hipLaunchKernelGGL((k_conv_bfr<NTW, ICC, true>), dim3(grid), blk, lds, s, B);
+    launch_lds<&k_conv_bfr<NTW, ICC, true>>(dim3(grid), blk, lds, s, B);
     return check_launch("conv_bfr");
   }
-  static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&k_conv_bfr<NTW, ICC, false>), lds);
   note_kernel("k_conv_bfr<%d,%d>", NTW, ICC);
-  hipLaunchKernelGGL((k_conv_bfr<NTW, ICC, false>), dim3(grid), blk, lds, s, B);
+  launch_lds<&k_conv_bfr<NTW, ICC, false>>(dim3(grid), blk, lds, s, B);
   return check_launch("conv_bfr");
 }
 

@@ -1,5 +1,6 @@
 // Declarations shared by the wave-specialised persistent convolutions: k_conv_bfw (conv_bfw.hip: two halo buffers, one
-// workgroup barrier per stage) and k_conv_bfr (conv_bfr.hip: a ring of halo buffers with full / free counters in LDS).
+// workgroup barrier per stage), k_conv_bfr (conv_bfr.hip: a ring of halo buffers with full / free counters in LDS) and
+// k_espcn_pair (conv_pair.hip: the same counters).
 #pragma once
 #include "srk_common.h"
 #include "conv_problem.h"
@@ -10,13 +11,34 @@
 
 namespace srk {
 
-// compile-time loop: f(std::integral_constant<int, I>{}) for I in [I0, I1)
-template <int I0, int I1, typename F>
-__device__ __forceinline__ void srk_static_for(F&& f) {
-  if constexpr (I0 < I1) {
-    f(std::integral_constant<int, I0>{});
-    srk_static_for<I0 + 1, I1>(f);
+// Counters in LDS that the waves of the ring kernels (k_conv_bfr, k_espcn_pair) hand buffers over with.
+typedef __attribute__((address_space(3))) unsigned lds_cnt_t;
+constexpr unsigned kLdsCntSpinCap = 1u << 18;
+
+__device__ __forceinline__ unsigned lds_cnt_peek(lds_cnt_t* p) {
+  return (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+}
+// wait until *p >= target (monotonic counters: the difference stays far below 2^31).  A poll that runs into its cap sets
+// `dead`; what a kernel does about it is its own business (k_conv_bfr traps, k_espcn_pair counts).
+__device__ __forceinline__ void lds_cnt_wait(lds_cnt_t* p, unsigned target, bool& dead) {
+  if (!dead) {
+    unsigned spins = 0;
+    while ((int)(lds_cnt_peek(p) - target) < 0) {
+      __builtin_amdgcn_s_sleep(1);
+      if (++spins > kLdsCntSpinCap) {
+        dead = true;
+        break;
+      }
+    }
   }
+  asm volatile("" ::: "memory");
+}
+// n counts behind every LDS access this wave has issued so far.  No s_waitcnt: the LDS executes the operations of one wave
+// in the order they were issued, so whoever sees the count sees the writes (or finds the reads done) that precede it.
+__device__ __forceinline__ void lds_cnt_signal(lds_cnt_t* p, unsigned n = 1u) {
+  asm volatile("" ::: "memory");
+  if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(p, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  asm volatile("" ::: "memory");
 }
 
 constexpr int BFW_MAXTAPS = 32;

@@ -520,39 +520,29 @@ static int bfw_launch_t(const BfwParams& B, size_t lds, int grid, hipStream_t s)
   if constexpr (NTW == 2 && TT == 9 && MTW == 2) {  // data gradients (bf16x3): mask on dy and / or ReLU gradient on dx
     const dim3 blk(64 * (16 / MTW + 4));
     if (B.P.mask_y && B.P.ep.out_relu) {
-      static LdsLimit limb;
-      limb.ensure(reinterpret_cast<const void*>(&k_conv_bfw<NTW, TT, MTW, false, true, true>), lds);
       note_kernel("k_conv_bfw<%d,%d,%d,mask,relu>", NTW, TT, MTW);
-      hipLaunchKernelGGL((k_conv_bfw<NTW, TT, MTW, false, true, true>), dim3(grid), blk, lds, s, B);
+      launch_lds<&k_conv_bfw<NTW, TT, MTW, false, true, true>>(dim3(grid), blk, lds, s, B);
       return check_launch("conv_bfw");
     }
     if (B.P.mask_y) {
-      static LdsLimit limm;
-      limm.ensure(reinterpret_cast<const void*>(&k_conv_bfw<NTW, TT, MTW, false, true, false>), lds);
       note_kernel("k_conv_bfw<%d,%d,%d,mask>", NTW, TT, MTW);
-      hipLaunchKernelGGL((k_conv_bfw<NTW, TT, MTW, false, true, false>), dim3(grid), blk, lds, s, B);
+      launch_lds<&k_conv_bfw<NTW, TT, MTW, false, true, false>>(dim3(grid), blk, lds, s, B);
       return check_launch("conv_bfw");
     }
     if (B.P.ep.out_relu) {
-      static LdsLimit limo;
-      limo.ensure(reinterpret_cast<const void*>(&k_conv_bfw<NTW, TT, MTW, false, false, true>), lds);
       note_kernel("k_conv_bfw<%d,%d,%d,relu>", NTW, TT, MTW);
-      hipLaunchKernelGGL((k_conv_bfw<NTW, TT, MTW, false, false, true>), dim3(grid), blk, lds, s, B);
+      launch_lds<&k_conv_bfw<NTW, TT, MTW, false, false, true>>(dim3(grid), blk, lds, s, B);
       return check_launch("conv_bfw");
     }
   }
   if (B.P.mask_y || B.P.ep.out_relu) return -1;
   if (B.w_descale) {  // f16x3 arithmetic
-    static LdsLimit limh;
-    limh.ensure(reinterpret_cast<const void*>(&k_conv_bfw<NTW, TT, MTW, true>), lds);
     note_kernel("k_conv_bfw<%d,%d,%d,f16>", NTW, TT, MTW);
-    hipLaunchKernelGGL((k_conv_bfw<NTW, TT, MTW, true>), dim3(grid), dim3(64 * (16 / MTW + 4)), lds, s, B);
+    launch_lds<&k_conv_bfw<NTW, TT, MTW, true>>(dim3(grid), dim3(64 * (16 / MTW + 4)), lds, s, B);
     return check_launch("conv_bfw");
   }
-  static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&k_conv_bfw<NTW, TT, MTW>), lds);
   note_kernel("k_conv_bfw<%d,%d,%d>", NTW, TT, MTW);
-  hipLaunchKernelGGL((k_conv_bfw<NTW, TT, MTW>), dim3(grid), dim3(64 * (16 / MTW + 4)), lds, s, B);
+  launch_lds<&k_conv_bfw<NTW, TT, MTW>>(dim3(grid), dim3(64 * (16 / MTW + 4)), lds, s, B);
   return check_launch("conv_bfw");
 }
 template <int NTW>

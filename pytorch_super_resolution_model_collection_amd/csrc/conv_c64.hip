@@ -273,11 +273,9 @@ bool conv_c64_applicable(const GatherConv& g, const Epi& ep, const float* in, co
 template <int NP, bool BWD, bool F16>
 static int c64_launch(const C64Params& R, hipStream_t s) {
   const size_t lds = (size_t)2 * NP * C64_PL * 16 + (size_t)4 * 4 * 64 * 16;
-  static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&k_c64<NP, BWD, F16>), lds);
   note_kernel("k_c64<%d,%d%s>", NP, (int)BWD, F16 ? ",f16" : "");
   note_amax_written(R.y_amax != nullptr);
-  hipLaunchKernelGGL((k_c64<NP, BWD, F16>), dim3((unsigned)((size_t)R.N * R.tiles_y * R.tiles_x)), dim3(512), lds, s, R);
+  launch_lds<&k_c64<NP, BWD, F16>>(dim3((unsigned)((size_t)R.N * R.tiles_y * R.tiles_x)), dim3(512), lds, s, R);
   return check_launch("conv_c64");
 }
 

@@ -26,13 +26,6 @@
 
 namespace srk {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 // ---------------------------------------------------------------------------------------------
 // Halo staging: global NHWC -> LDS [pixel][PSA], channels [cb, cb+ck) zero-padded to ckp.
 // ---------------------------------------------------------------------------------------------
@@ -439,21 +432,15 @@ bool conv_mfma_gather_supported(const GatherConv& g, const Epi& ep) {
   return true;
 }
 
-// Raise the dynamic-LDS limit of a kernel once per device (host call, not a stream op): srk_common.h LdsLimit.
-static void ensure_lds(const void* fn, LdsLimit& lim, size_t lds) { lim.ensure(fn, lds); }
-
 template <int NT>
 static void launch_variant(bool tapgroup, const MfmaConvParams& P, dim3 grid, size_t lds, hipStream_t s) {
-  static LdsLimit cur_tg, cur_main;
   note_amax_written(P.ep.y_amax != nullptr && epi_all_vector(P));   // (store_tile: the vector path keeps the maximum)
   if (tapgroup) {
-    ensure_lds(reinterpret_cast<const void*>(&k_conv_mfma_tg<NT>), cur_tg, lds);
     note_kernel("k_conv_mfma_tg<%d>", NT);
-    hipLaunchKernelGGL(k_conv_mfma_tg<NT>, grid, dim3(256), lds, s, P);
+    launch_lds<&k_conv_mfma_tg<NT>>(grid, dim3(256), lds, s, P);
   } else {
-    ensure_lds(reinterpret_cast<const void*>(&k_conv_mfma<NT>), cur_main, lds);
     note_kernel("k_conv_mfma<%d>", NT);
-    hipLaunchKernelGGL(k_conv_mfma<NT>, grid, dim3(256), lds, s, P);
+    launch_lds<&k_conv_mfma<NT>>(grid, dim3(256), lds, s, P);
   }
 }
 
@@ -463,10 +450,8 @@ static void apply_pick(MfmaConvParams& P, const TilePick& t) {
 
 template <int OCT>
 static void launch_direct(const MfmaConvParams& P, dim3 grid, size_t lds, hipStream_t s) {
-  static LdsLimit cur;
-  ensure_lds(reinterpret_cast<const void*>(&k_conv_direct<OCT>), cur, lds);
   note_kernel("k_conv_direct<%d>", OCT);
-  hipLaunchKernelGGL(k_conv_direct<OCT>, grid, dim3(256), lds, s, P);
+  launch_lds<&k_conv_direct<OCT>>(grid, dim3(256), lds, s, P);
 }
 
 // Channel-chunk / tile choice for the variants that stage [pixel][CK+4] halos: try chunks of

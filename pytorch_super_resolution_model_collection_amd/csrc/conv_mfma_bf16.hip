@@ -29,7 +29,6 @@
 
 namespace srk {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct Bf3Params {
@@ -887,18 +886,14 @@ __global__ __launch_bounds__(256, 2) void k_conv_bf3_rows(Bf3Params B) {
 // ---------------------------------------------------------------------------------------------
 template <int NT>
 static void bf3_launch_vec(const Bf3Params& B, dim3 grid, size_t lds, hipStream_t s) {
-  static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&k_conv_bf3<NT, 4, true>), lds);
   note_kernel("k_conv_bf3<%d,4,vec>", NT);
-  hipLaunchKernelGGL((k_conv_bf3<NT, 4, true>), grid, dim3(256), lds, s, B);
+  launch_lds<&k_conv_bf3<NT, 4, true>>(grid, dim3(256), lds, s, B);
 }
 
 template <int NT, int NW>
 static void bf3_launch(const Bf3Params& B, dim3 grid, size_t lds, hipStream_t s) {
-  static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&k_conv_bf3<NT, NW>), lds);
   note_kernel("k_conv_bf3<%d,%d>", NT, NW);
-  hipLaunchKernelGGL((k_conv_bf3<NT, NW>), grid, dim3(64 * NW), lds, s, B);
+  launch_lds<&k_conv_bf3<NT, NW>>(grid, dim3(64 * NW), lds, s, B);
 }
 
 bool conv_bf3_gather_supported(const GatherConv& g, const Epi& ep) {
@@ -913,11 +908,9 @@ bool conv_bf3_gather_supported(const GatherConv& g, const Epi& ep) {
 
 template <int NT, bool VEC_ONLY, bool F16 = false>
 static void bf3_launch_rows_v(const Bf3Params& B, dim3 grid, size_t lds, hipStream_t s) {
-  static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&k_conv_bf3_rows<NT, VEC_ONLY, F16>), lds);
   note_kernel("k_conv_bf3_rows<%d%s%s>", NT, F16 ? ",f16" : "", VEC_ONLY ? "" : ",scalar");
   note_amax_written(VEC_ONLY && B.P.ep.y_amax != nullptr);   // (the scalar-store variant keeps no maximum)
-  hipLaunchKernelGGL((k_conv_bf3_rows<NT, VEC_ONLY, F16>), grid, dim3(256), lds, s, B);
+  launch_lds<&k_conv_bf3_rows<NT, VEC_ONLY, F16>>(grid, dim3(256), lds, s, B);
 }
 template <int NT>
 static void bf3_launch_rows(const Bf3Params& B, dim3 grid, size_t lds, hipStream_t s) {

@@ -45,10 +45,7 @@
 // rows >= vr + 2 reach nothing that is stored.  Fragment f of rows 2 .. 9 starts in halo row (36 + 16 f) / 18: the waves of
 // pixel half 1 (f >= 4, first row 5) skip their first layer when vr <= 3, the waves of output rows 4 .. 7 their second layer
 // and stores when vr <= 4.  They still perform every wait and signal.
-#include "srk_common.h"
-#include "conv_problem.h"
-#include "bf16_frag.h"
-#include <type_traits>
+#include "conv_bfw.h"   // lds_cnt_*; srk_common.h, conv_problem.h, bf16_frag.h
 
 namespace srk {
 
@@ -65,7 +62,6 @@ constexpr int PR_HBUF = 4 * PR_NPIXP;               // uint4 per plane of a halo
 constexpr int PR_KBUF = 2 * 4 * PR_KP;              // uint4 per plane of a kept-row buffer [chunk][group][KP]
 constexpr int PR_PLANE = PR_NSLOT * PR_HBUF + PR_NKBUF * PR_KBUF;   // the residual planes of all of them lie this far on
 constexpr int PR_XBUF = 2 * PR_XR * PR_XP;          // uint2 per group's input tile [plane][row][pixel]
-constexpr unsigned PR_SPIN_CAP = 1u << 18;
 constexpr unsigned PR_AMAX_CAP = 1u << 14;          // polls of the max|x| rendezvous (one L2 round trip and a sleep each)
 constexpr int PR_ARRIVE = 1, PR_DEPART = 2;         // counter words of the slots buffer (slot i is word 16 i)
 // Both words MUST stay in one 64-byte line and be touched by one thread of a block (thread 0).  The reset -- the last
@@ -86,7 +82,6 @@ static_assert(PR_LDS <= 160 * 1024, "k_espcn_pair: LDS");
 __device__ unsigned g_pair_timeouts = 0;
 __device__ unsigned g_pair_scans = 0;   // blocks that scanned all of x themselves (rendezvous cap, or asked for)
 
-typedef __attribute__((address_space(3))) unsigned pr_cnt_t;
 typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
 
 struct PairParams {
@@ -104,35 +99,6 @@ struct PairParams {
   int N, H, W, OH, OW, tiles_y, img_tiles, ntiles;
   unsigned x_img_bytes, y_bytes;
 };
-
-__device__ __forceinline__ unsigned pr_peek(pr_cnt_t* p) {
-  return (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-}
-__device__ __forceinline__ void pr_wait(pr_cnt_t* p, unsigned target, bool& dead) {
-  if (!dead) {
-    unsigned spins = 0;
-    while ((int)(pr_peek(p) - target) < 0) {
-      __builtin_amdgcn_s_sleep(1);
-      if (++spins > PR_SPIN_CAP) {
-        dead = true;
-        break;
-      }
-    }
-  }
-  asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ void pr_signal(pr_cnt_t* p, unsigned n = 1u) {
-  asm volatile("" ::: "memory");
-  if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(p, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t pr_rsrc(const void* base, unsigned bytes) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-  void* p = reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo);
-  return __builtin_amdgcn_make_buffer_rsrc(p, (short)0, (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
 
 // max |x| over the float4s [lo, hi) (thread t of nt takes lo + t, lo + t + nt, ..: PR_XLD loads in flight) and, with `tail`,
 // over the elements behind the last whole float4
@@ -208,7 +174,7 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
   uint4* ring = smem4 + PR_WL2;
   uint4* keep = ring + PR_NSLOT * PR_HBUF;
   uint2* xin_all = reinterpret_cast<uint2*>(ring + 2 * PR_PLANE);
-  pr_cnt_t* cnt = (pr_cnt_t*)(xin_all + 2 * PR_XBUF);  // full[3], free[3], staged[2], kept full[3], kept free[3]
+  lds_cnt_t* cnt = (lds_cnt_t*)(xin_all + 2 * PR_XBUF);  // full[3], free[3], staged[2], kept full[3], kept free[3]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int grp = wave >> 2, gw = wave & 3, lt = tid & 255;
   const int j = lane & 15, kq = lane >> 4;
@@ -313,7 +279,7 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
   }
   count = __builtin_amdgcn_readfirstlane(count);
 
-  const __amdgpu_buffer_rsrc_t yr = pr_rsrc(B.y, B.y_bytes);
+  const __amdgpu_buffer_rsrc_t yr = buffer_rsrc(B.y, B.y_bytes);
   const unsigned HW_ = (unsigned)(B.H * B.W);
   // input staging: pixel q = lt + 256 s of the 14 x 23 tile, 3 channels
   float xv[2][3];
@@ -322,7 +288,7 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
     const int t = first + (valid ? i : 0);
     const int n = t / B.img_tiles, rem = t - n * B.img_tiles;
     const int tx = rem / B.tiles_y, ty = rem - tx * B.tiles_y;
-    const __amdgpu_buffer_rsrc_t xr = pr_rsrc(B.x + (size_t)n * 3 * HW_, B.x_img_bytes);
+    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(B.x + (size_t)n * 3 * HW_, B.x_img_bytes);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const int q = lt + 256 * s, qy = q / PR_XC, qx = q - qy * PR_XC;
@@ -390,8 +356,8 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
   }
   __syncthreads();  // filter, counters and max|x| visible
   if (B.amax_mode) {
-    xmax = __uint_as_float(pr_peek(cnt + 14));
-    if (pr_peek(cnt + 15)) {
+    xmax = __uint_as_float(lds_cnt_peek(cnt + 14));
+    if (lds_cnt_peek(cnt + 15)) {
       // The slots may lack a block that has not arrived: scan all of x here.  (With the slots, which hold every earlier
       // launch's maximum, that is the running maximum the other blocks see.)
       float* red = reinterpret_cast<float*>(xin_all);
@@ -447,9 +413,9 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
         xin[PR_XR * PR_XP + qy * PR_XP + qx] = make_uint2(m01, m2);
       }
     }
-    pr_signal(cnt + 6 + grp);
+    lds_cnt_signal(cnt + 6 + grp);
     xload(i + 2);
-    pr_wait(cnt + 6 + grp, 4u * (own + 1), dead);
+    lds_cnt_wait(cnt + 6 + grp, 4u * (own + 1), dead);
 
     float b1v[2][4];  // (read per tile: registers are short where the second layer runs)
 #pragma unroll
@@ -478,28 +444,28 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
       l1_frags(nm, moff, a1);
       const unsigned st = 2u * (unsigned)i + c1, slot = st % PR_NSLOT, use = st / PR_NSLOT;
       unsigned char* hb = reinterpret_cast<unsigned char*>(ring + slot * PR_HBUF) + wr_slot;
-      pr_wait(cnt + 3 + slot, 4u * use, dead);
+      lds_cnt_wait(cnt + 3 + slot, 4u * use, dead);
 #pragma unroll
       for (int m = 0; m < NM; ++m)
         if (mpix[m] < PR_NSLOTPIX) l1_store(a1[m], hb, mpix[m], PR_NPIXP);
-      pr_signal(cnt + slot);
+      lds_cnt_signal(cnt + slot);
       // rows 8 .. 9 = pixels 108 .. 143 (in fragments 6 .. 8, m >= 2 where a wave has them) are kept rows
       unsigned char* kp = reinterpret_cast<unsigned char*>(keep + kb * PR_KBUF) + wr_keep;
-      pr_wait(cnt + 11 + kb, 8u * ku, dead);
+      lds_cnt_wait(cnt + 11 + kb, 8u * ku, dead);
 #pragma unroll
       for (int m = 2; m < NM; ++m)
         if (mpix[m] >= PR_NSLOTPIX) l1_store(a1[m], kp, mpix[m] - PR_NSLOTPIX, PR_KP);
-      pr_signal(cnt + 8 + kb);
+      lds_cnt_signal(cnt + 8 + kb);
     };
     // Live rows of this tile; halo rows >= vr + 2 reach no stored value (file header).  A wave whose fragments all lie there
     // -- pixel half 1 starts in halo row 5 -- only keeps the counters going.
     const int vr = B.OH - ty * PR_TH;
     if (mhu == 1 && vr <= 3) {
       const unsigned st = 2u * (unsigned)i + c1, slot = st % PR_NSLOT, use = st / PR_NSLOT;
-      pr_wait(cnt + 3 + slot, 4u * use, dead);
-      pr_signal(cnt + slot);
-      pr_wait(cnt + 11 + kb, 8u * ku, dead);
-      pr_signal(cnt + 8 + kb);
+      lds_cnt_wait(cnt + 3 + slot, 4u * use, dead);
+      lds_cnt_signal(cnt + slot);
+      lds_cnt_wait(cnt + 11 + kb, 8u * ku, dead);
+      lds_cnt_signal(cnt + 8 + kb);
     } else if (mh == (int)(own & 1)) {
       l1_tile(std::integral_constant<int, 5>{});
     } else {
@@ -509,24 +475,24 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
       f32x4 at[2][2];
       l1_frags(std::integral_constant<int, 2>{}, toff, at);
       unsigned char* kp = reinterpret_cast<unsigned char*>(keep + tb * PR_KBUF) + wr_keep;
-      pr_wait(cnt + 11 + tb, 8u * tu, dead);
+      lds_cnt_wait(cnt + 11 + tb, 8u * tu, dead);
 #pragma unroll
       for (int m = 0; m < 2; ++m)
         if (tpix[m] < PR_NKEEP) l1_store(at[m], kp, tpix[m], PR_KP);
-      pr_signal(cnt + 8 + tb);
+      lds_cnt_signal(cnt + 8 + tb);
     }
 
     // -- second layer out of the ring and the kept rows --------------------------------------------------------------
-    pr_wait(cnt + 8 + (rh == 0 ? tb : kb), 4u * ((rh == 0 ? tu : ku) + 1u), dead);
+    lds_cnt_wait(cnt + 8 + (rh == 0 ? tb : kb), 4u * ((rh == 0 ? tu : ku) + 1u), dead);
     if (rhu == 1 && vr <= 4) {  // output rows 4 .. 7 lie below the output: waits and signals only
 #pragma unroll
       for (int cc = 0; cc < 2; ++cc) {
         const unsigned st = 2u * (unsigned)i + cc, slot = st % PR_NSLOT, use = st / PR_NSLOT;
-        pr_wait(cnt + slot, 2u * (use + 1), dead);
-        pr_signal(cnt + 3 + slot);
+        lds_cnt_wait(cnt + slot, 2u * (use + 1), dead);
+        lds_cnt_signal(cnt + 3 + slot);
       }
-      pr_signal(cnt + 11 + tb, fresh ? 2u : 1u);
-      pr_signal(cnt + 11 + kb, hand ? 1u : 2u);
+      lds_cnt_signal(cnt + 11 + tb, fresh ? 2u : 1u);
+      lds_cnt_signal(cnt + 11 + kb, hand ? 1u : 2u);
     } else {
       f32x4 acc[4];
 #pragma unroll
@@ -534,7 +500,7 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
 #pragma unroll
       for (int cc = 0; cc < 2; ++cc) {
         const unsigned st = 2u * (unsigned)i + cc, slot = st % PR_NSLOT, use = st / PR_NSLOT;
-        pr_wait(cnt + slot, 2u * (use + 1), dead);
+        lds_cnt_wait(cnt + slot, 2u * (use + 1), dead);
         const uint4* hb = ring + slot * PR_HBUF + lane_b;
         // the wave's rows out of kept rows: R = 0, 1 (rh == 0: rows 0 .. 1), R = 4, 5 (rh == 1: rows 8 .. 9)
         const uint4* kr = keep + (rh == 0 ? tb : kb) * PR_KBUF + cc * 4 * PR_KP + lane_k - (rh == 0 ? 0 : 4 * PR_HW);
@@ -563,10 +529,10 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
             }
           }
         }
-        pr_signal(cnt + 3 + slot);
+        lds_cnt_signal(cnt + 3 + slot);
       }
-      pr_signal(cnt + 11 + tb, fresh ? 2u : 1u);
-      pr_signal(cnt + 11 + kb, hand ? 1u : 2u);
+      lds_cnt_signal(cnt + 11 + tb, fresh ? 2u : 1u);
+      lds_cnt_signal(cnt + 11 + kb, hand ? 1u : 2u);
       // -- epilogue: bias, ReLU, NHWC stores of the pixels inside the output, running maximum -----------------------------
       const int oc = tx * PR_TW + pj;
 #pragma unroll
@@ -618,10 +584,8 @@ int espcn_pair_launch(int N, int H, int W, const float* x, const void* w1p, cons
   int grid = kNumCU;
   if (grid > ntiles) grid = (int)ntiles;
   note_amax_written(y_amax != nullptr);
-  static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&k_espcn_pair), PR_LDS);
   note_kernel("k_espcn_pair");
-  hipLaunchKernelGGL(k_espcn_pair, dim3(grid), dim3(512), PR_LDS, s, B);
+  launch_lds<&k_espcn_pair>(dim3(grid), dim3(512), PR_LDS, s, B);
   return check_launch("espcn_pair");
 }
 

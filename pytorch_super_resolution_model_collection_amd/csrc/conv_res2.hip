@@ -495,17 +495,13 @@ static int r2_launch(const Res2Params& R, hipStream_t s) {
   if constexpr (NP == 2) {
     // at most one block per CU: the variant that reads the next tap's operands ahead
     if (grid <= (size_t)kNumCU) {
-      static LdsLimit limp;
-      limp.ensure(reinterpret_cast<const void*>(&k_res2<NP, BWD, F16, true>), lds);
       note_kernel("k_res2<%d,%d%s,pf>", NP, (int)BWD, F16 ? ",f16" : "");
-      hipLaunchKernelGGL((k_res2<NP, BWD, F16, true>), dim3((unsigned)grid), dim3(512), lds, s, R);
+      launch_lds<&k_res2<NP, BWD, F16, true>>(dim3((unsigned)grid), dim3(512), lds, s, R);
       return check_launch("conv_res2");
     }
   }
-  static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&k_res2<NP, BWD, F16>), lds);
   note_kernel("k_res2<%d,%d%s>", NP, (int)BWD, F16 ? ",f16" : "");
-  hipLaunchKernelGGL((k_res2<NP, BWD, F16>), dim3((unsigned)grid), dim3(512), lds, s, R);
+  launch_lds<&k_res2<NP, BWD, F16>>(dim3((unsigned)grid), dim3(512), lds, s, R);
   return check_launch("conv_res2");
 }
 

@@ -36,14 +36,6 @@ namespace srk {
 constexpr int RN_TW = 64;             // output columns per block
 constexpr int RN_ZS = 36;             // z row stride in floats (conflict-free C/D fragment writes, as TAPN_ZS)
 
-template <int I0, int I1, typename F>
-__device__ __forceinline__ void rn_static_for(F&& f) {
-  if constexpr (I0 < I1) {
-    f(std::integral_constant<int, I0>{});
-    rn_static_for<I0 + 1, I1>(f);
-  }
-}
-
 // KS = IC / 32, OCT = output channels, KW = kernel width (compile time: the filter registers are indexed by it),
 // NP = bf16 planes, NT = 16-column tiles of N (KH * OCT <= 16 * NT)
 template <int KS, int OCT, int KW, int NP, int NT>
@@ -206,7 +198,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_rown(MfmaConvParams P) {
             for (int p = 0; p < NP; ++p) a[buf][m][p] = xs[(p * NG + ks * 4 + kq) * XP + (mh * 2 + m) * 16 + j + v];
         };
         aread(0, 0);
-        rn_static_for<0, QW>([&](auto qic) {
+        srk_static_for<0, QW>([&](auto qic) {
           constexpr int qi = decltype(qic)::value, cur = qi & 1;
           if constexpr (qi + 1 < QW) aread(cur ^ 1, qi + 1);
           // smallest products first (as k_conv_tapn / k_conv_bfd)
@@ -288,11 +280,9 @@ static int rown_launch_t(MfmaConvParams P, hipStream_t s) {
   size_t lds = (size_t)NP * NG * XP * 16 + (size_t)4 * RN_TW * RN_ZS * 4;
   const size_t flt = (size_t)P.KHv * P.KW_full * P.IC * OCT * 4;   // the fp32 filter passes through the same memory first
   if (lds < flt) lds = flt;
-  static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&k_conv_rown<KS, OCT, KW, NP, NT>), lds);
   note_kernel("k_conv_rown<%d,%d,%d,%d,%d>", KS, OCT, KW, NP, NT);
   dim3 grid((unsigned)((size_t)P.tiles_x * P.tiles_y * P.N));
-  hipLaunchKernelGGL((k_conv_rown<KS, OCT, KW, NP, NT>), grid, dim3(256), lds, s, P);
+  launch_lds<&k_conv_rown<KS, OCT, KW, NP, NT>>(grid, dim3(256), lds, s, P);
   return check_launch("conv_rown");
 }
 

@@ -23,14 +23,6 @@
 
 namespace srk {
 
-template <int I0, int I1, typename F>
-__device__ __forceinline__ void rw_static_for(F&& f) {
-  if constexpr (I0 < I1) {
-    f(std::integral_constant<int, I0>{});
-    rw_static_for<I0 + 1, I1>(f);
-  }
-}
-
 constexpr int RW_IT = 2;  // staging register batches: halos of <= 512 * 2 pixels
 
 struct RowswParams {
@@ -319,13 +311,13 @@ __global__ __launch_bounds__(512, 2) void k_conv_rowsw(RowswParams B) {
           for (int mt = 0; mt < MTW; ++mt) acc[nt][mt] = mfma16x<F16>(a[0][nt], b[0][mt], acc[nt][mt]);  // w_h * x_h
       };
       load_frags(fa[0], fb[0]);
-      rw_static_for<0, QT>([&](auto tc) {
+      srk_static_for<0, QT>([&](auto tc) {
         constexpr int t = decltype(tc)::value;
         if (t + 1 < QT) load_frags(fa[WREG ? 0 : ((t + 1) & 1)], fb[(t + 1) & 1]);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (WREG) mfmas(wreg[t], fb[t & 1]); else mfmas(fa[t & 1], fb[t & 1]);
         __builtin_amdgcn_sched_barrier(0);
-        rw_static_for<(t * PER_STEP < NST ? t * PER_STEP : NST), ((t + 1) * PER_STEP < NST ? (t + 1) * PER_STEP : NST)>(
+        srk_static_for<(t * PER_STEP < NST ? t * PER_STEP : NST), ((t + 1) * PER_STEP < NST ? (t + 1) * PER_STEP : NST)>(
             [&](auto qc) { store_slot(qc); });
       });
       if (s + 1 < S) commit(hal0 + (size_t)((s + 1) & 1) * B.NPIXp);  // (that buffer was last read in stage s - 1)
@@ -353,7 +345,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_rowsw(RowswParams B) {
     }
     __syncthreads();
   }
-  rw_static_for<0, NST>([&](auto qc) { store_slot(qc); });  // the last tile (S = 0: nothing parked, dropped)
+  srk_static_for<0, NST>([&](auto qc) { store_slot(qc); });  // the last tile (S = 0: nothing parked, dropped)
   if (P.ep.y_amax) amax_commit(P.ep.y_amax, amax, blockIdx.x + wave, amax_peek(P.ep.y_amax, blockIdx.x + wave));
 }
 
@@ -579,7 +571,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_rowsr(RowswParams B) {
       commit(hal0, Set0{});
       issue(Set0{});
       commit(hal0 + BSLOT, Set1{});
-      rw_static_for<0, NST>([&](auto qc) { store_slot(qc); });  // (dropped: see below)
+      srk_static_for<0, NST>([&](auto qc) { store_slot(qc); });  // (dropped: see below)
       issue(Set1{});
     }
   } else if (S > 0) {
@@ -588,7 +580,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_rowsr(RowswParams B) {
     issue(Set1{});                  // tile 1
     // eight dropped stores (nothing is parked yet): the steady state has a stage's eight stores between the two sets'
     // loads, and the first wait inside the loop is counted for the smaller of the two distances
-    rw_static_for<0, NST>([&](auto qc) { store_slot(qc); });
+    srk_static_for<0, NST>([&](auto qc) { store_slot(qc); });
     issue(Set0{});                  // tile 2
   }
 #pragma unroll
@@ -630,27 +622,27 @@ __global__ __launch_bounds__(256, 2) void k_conv_rowsr(RowswParams B) {
         roff += rstep;
       };
       load_row(fb[0]);
-      rw_static_for<0, NR>([&](auto rc) {
+      srk_static_for<0, NR>([&](auto rc) {
         constexpr int R = decltype(rc)::value;
         if (R + 1 < NR) load_row(fb[(R + 1) & 1]);
         __builtin_amdgcn_sched_barrier(0);
         const uint4(&b)[2] = fb[R & 1];
         // (tile row mt, kernel row ky = R - mt) for every valid pair; pass-major like k_conv_rowsw's K step
-        rw_static_for<0, MTW>([&](auto mc) {
+        srk_static_for<0, MTW>([&](auto mc) {
           constexpr int mt = decltype(mc)::value, ky = R - mt;
           if constexpr (ky >= 0 && ky < KH) {
 #pragma unroll
             for (int nt = 0; nt < NTW; ++nt) acc[nt][mt] = mfma16x<F16>(wreg[ky][0][nt], b[1], acc[nt][mt]);  // w_h * x_l
           }
         });
-        rw_static_for<0, MTW>([&](auto mc) {
+        srk_static_for<0, MTW>([&](auto mc) {
           constexpr int mt = decltype(mc)::value, ky = R - mt;
           if constexpr (ky >= 0 && ky < KH) {
 #pragma unroll
             for (int nt = 0; nt < NTW; ++nt) acc[nt][mt] = mfma16x<F16>(wreg[ky][1][nt], b[0], acc[nt][mt]);  // w_l * x_h
           }
         });
-        rw_static_for<0, MTW>([&](auto mc) {
+        srk_static_for<0, MTW>([&](auto mc) {
           constexpr int mt = decltype(mc)::value, ky = R - mt;
           if constexpr (ky >= 0 && ky < KH) {
 #pragma unroll
@@ -658,7 +650,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_rowsr(RowswParams B) {
           }
         });
         __builtin_amdgcn_sched_barrier(0);
-        rw_static_for<(R * PER_STEP < NST ? R * PER_STEP : NST), ((R + 1) * PER_STEP < NST ? (R + 1) * PER_STEP : NST)>(
+        srk_static_for<(R * PER_STEP < NST ? R * PER_STEP : NST), ((R + 1) * PER_STEP < NST ? (R + 1) * PER_STEP : NST)>(
             [&](auto qc) { store_slot(qc); });
       });
       if constexpr (BAND) commit(hal0 + (size_t)((s + 2) & 3) * BSLOT, nset);  // chunk s + 2 (slot last read in stage s - 1)
@@ -699,7 +691,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_rowsr(RowswParams B) {
       stage(s0 + 1, Set0{});
     }
   }
-  rw_static_for<0, NST>([&](auto qc) { store_slot(qc); });  // the last tile (S = 0: nothing parked, dropped)
+  srk_static_for<0, NST>([&](auto qc) { store_slot(qc); });  // the last tile (S = 0: nothing parked, dropped)
   if (P.ep.y_amax) amax_commit(P.ep.y_amax, amax, blockIdx.x + wave, amax_peek(P.ep.y_amax, blockIdx.x + wave));
 }
 
@@ -754,16 +746,12 @@ template <int NTW, int QT>
 static int rowsw_launch(const RowswParams& B, size_t lds, int grid, hipStream_t s) {
   note_amax_written(B.P.ep.y_amax != nullptr);
   if (B.w_descale) {
-    static LdsLimit limh;
-    limh.ensure(reinterpret_cast<const void*>(&k_conv_rowsw<NTW, QT, true>), lds);
     note_kernel("k_conv_rowsw<%d,%d,f16>", NTW, QT);
-    hipLaunchKernelGGL((k_conv_rowsw<NTW, QT, true>), dim3(grid), dim3(512), lds, s, B);
+    launch_lds<&k_conv_rowsw<NTW, QT, true>>(dim3(grid), dim3(512), lds, s, B);
     return check_launch("conv_rowsw");
   }
-  static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&k_conv_rowsw<NTW, QT, false>), lds);
   note_kernel("k_conv_rowsw<%d,%d>", NTW, QT);
-  hipLaunchKernelGGL((k_conv_rowsw<NTW, QT, false>), dim3(grid), dim3(512), lds, s, B);
+  launch_lds<&k_conv_rowsw<NTW, QT, false>>(dim3(grid), dim3(512), lds, s, B);
   return check_launch("conv_rowsw");
 }
 

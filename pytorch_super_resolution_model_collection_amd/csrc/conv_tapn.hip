@@ -916,13 +916,11 @@ static int tapkm_launch(const MfmaConvParams& P, int gpr, int units, hipStream_t
   size_t lds = (size_t)P.KHv * MTN * 2 * 64 * 16;
   const size_t flt = (size_t)P.KHv * P.KW_full * P.IC * P.OC * 4;
   if (lds < flt) lds = flt;
-  static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&k_conv_tapkm<MTN>), lds);
   long nb = (units + 4 * 2 * 4 - 1) / (4 * 2 * 4);   // >= 4 pairs of pixel groups per wave (the filter prologue is per block)
   if (nb > 2 * kNumCU) nb = 2 * kNumCU;
   if (nb < 1) nb = 1;
   note_kernel("k_conv_tapkm<%d>", MTN);
-  hipLaunchKernelGGL(k_conv_tapkm<MTN>, dim3((unsigned)nb), dim3(256), lds, s, P, gpr, units);
+  launch_lds<&k_conv_tapkm<MTN>>(dim3((unsigned)nb), dim3(256), lds, s, P, gpr, units);
   return check_launch("conv_tapkm");
 }
 

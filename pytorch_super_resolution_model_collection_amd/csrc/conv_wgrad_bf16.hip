@@ -26,7 +26,6 @@
 
 namespace srk {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // conv_wgrad_mfma.hip
@@ -143,14 +142,7 @@ __device__ __forceinline__ void wb_split_pair(const f32x4& p0, const f32x4& p1, 
   }
 }
 
-// Buffer descriptor over [base, base + bytes) built from wave-uniform values (the readfirstlane makes the uniformity
-// provable: no waterfall loop around the loads), and a 16-byte load through it: an offset outside the range reads zero.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wb_rsrc(const float* base, unsigned bytes) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-  void* p = reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo);
-  return __builtin_amdgcn_make_buffer_rsrc(p, (short)0, (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
+// A 16-byte load through a buffer descriptor (buffer_rsrc, srk_common.h): an offset outside its range reads zero.
 __device__ __forceinline__ f32x4 wb_bload(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
   typedef unsigned wb_u32x4 __attribute__((ext_vector_type(4)));
   const wb_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 0);
@@ -516,7 +508,7 @@ __global__ __launch_bounds__(SPEC ? 64 * CIT * COW + WB_SST : 64 * CIT * COW,
       }
       {
         const size_t img = (size_t)P.XH * P.XW * P.Cin;
-        const __amdgpu_buffer_rsrc_t rx = wb_rsrc(Lx + (size_t)n * img, (unsigned)(img * 4));
+        const __amdgpu_buffer_rsrc_t rx = buffer_rsrc(Lx + (size_t)n * img, (unsigned)(img * 4));
         const int by0 = r0 - P.pad, bx0 = c0 - P.pad;
         const int obase = (by0 * P.XW + bx0) * P.Cin * 4;  // may be negative: rows above the image wrap out of range
         const unsigned pstride = (unsigned)P.Cin * 4u;
@@ -531,8 +523,8 @@ __global__ __launch_bounds__(SPEC ? 64 * CIT * COW + WB_SST : 64 * CIT * COW,
       }
       {
         const size_t img = (size_t)P.YH * y_srow;
-        const __amdgpu_buffer_rsrc_t ry = wb_rsrc(Ldy + (size_t)n * img, (unsigned)(img * 4));
-        const __amdgpu_buffer_rsrc_t rm = wb_rsrc(Lmask ? Lmask + (size_t)n * img : Ldy, Lmask ? (unsigned)(img * 4) : 0u);
+        const __amdgpu_buffer_rsrc_t ry = buffer_rsrc(Ldy + (size_t)n * img, (unsigned)(img * 4));
+        const __amdgpu_buffer_rsrc_t rm = buffer_rsrc(Lmask ? Lmask + (size_t)n * img : Ldy, Lmask ? (unsigned)(img * 4) : 0u);
         const unsigned obase = ((unsigned)r0 * y_srow + (unsigned)c0 * y_scol) * 4u;
         const unsigned pstride = y_scol * 4u;
 #pragma unroll
@@ -982,7 +974,7 @@ __global__ __launch_bounds__(768, 3) void k_wgrad_tr(WgBfParams P, typename WgGr
       st_skip[j & 1] = skip_rows;
       {
         const size_t img = (size_t)P.XH * P.XW * P.Cin;
-        const __amdgpu_buffer_rsrc_t rx = wb_rsrc(Lx + (size_t)n * img, (unsigned)(img * 4));
+        const __amdgpu_buffer_rsrc_t rx = buffer_rsrc(Lx + (size_t)n * img, (unsigned)(img * 4));
         const int by0 = r0 - P.pad, bx0 = c0 - P.pad;
         const int obase = (by0 * P.XW + bx0) * P.Cin * 4;  // may be negative: rows above the image wrap out of range
 #pragma unroll
@@ -996,8 +988,8 @@ __global__ __launch_bounds__(768, 3) void k_wgrad_tr(WgBfParams P, typename WgGr
       }
       {
         const size_t img = (size_t)P.YH * y_srow;
-        const __amdgpu_buffer_rsrc_t ry = wb_rsrc(Ldy + (size_t)n * img, (unsigned)(img * 4));
-        const __amdgpu_buffer_rsrc_t rm = wb_rsrc(Lmask ? Lmask + (size_t)n * img : Ldy, Lmask ? (unsigned)(img * 4) : 0u);
+        const __amdgpu_buffer_rsrc_t ry = buffer_rsrc(Ldy + (size_t)n * img, (unsigned)(img * 4));
+        const __amdgpu_buffer_rsrc_t rm = buffer_rsrc(Lmask ? Lmask + (size_t)n * img : Ldy, Lmask ? (unsigned)(img * 4) : 0u);
         const unsigned obase = ((unsigned)r0 * y_srow + (unsigned)c0 * y_scol) * 4u;
 #pragma unroll
         for (int k = 0; k < PIT; ++k) {
@@ -1320,7 +1312,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_s2(WgS2Params P) {
     const int r0 = tyi * P.TH, c0 = txi * P.TW;
     __syncthreads();  // previous tile fully consumed (tables / zero octets visible on the first pass)
     {  // ---- X halo: rows 2 r0 - 1 + hy, columns 2 c0 - 1 + hx; item = (4 adjacent halo pixels, 4 channels)
-      const __amdgpu_buffer_rsrc_t rx = wb_rsrc(P.x + (size_t)n * ximg, (unsigned)(ximg * 4));
+      const __amdgpu_buffer_rsrc_t rx = buffer_rsrc(P.x + (size_t)n * ximg, (unsigned)(ximg * 4));
       const int q = tid & 7, ch = cib + q * 4;
       const int nitems = P.HH * P.nq;
       const int by0 = 2 * r0 - 1, bx0 = 2 * c0 - 1;
@@ -1361,7 +1353,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_s2(WgS2Params P) {
       }
     }
     {  // ---- dY tile: rows [r0, +TH), cols [c0, +TW), channels [cob, +64) -> planes [co][r][c]
-      const __amdgpu_buffer_rsrc_t ry = wb_rsrc(P.dy + (size_t)n * yimg, (unsigned)(yimg * 4));
+      const __amdgpu_buffer_rsrc_t ry = buffer_rsrc(P.dy + (size_t)n * yimg, (unsigned)(yimg * 4));
       const int q = tid & 15, ch = cob + q * 4;
       const int npairs = P.TH * tw2;
       f32x4 p0[WS2_YB], p1[WS2_YB];
@@ -1487,7 +1479,7 @@ struct WbPlan {
   int CIB, COB;
   int TH, TW, TWo, tiles_y, tiles_x, HH, HWp, CS, DS, nks;
   size_t lds;
-  int G, ntiles, gy, gz;
+  int ntiles, gy, gz;
 };
 
 static inline int round_8odd(int v) {  // smallest multiple of 8 >= v whose quotient by 8 is odd
@@ -1544,11 +1536,22 @@ static WbPlan wb_plan(const srk_conv_desc& d) {
   pl.ntiles = (int)nt;
   pl.gy = cdiv(d.Cin, pl.CIB);
   pl.gz = cdiv(d.Cout, pl.COB);
-  int g = (2 * kNumCU) / (pl.gy * pl.gz);  // two resident blocks per CU
-  if (g < 1) g = 1;
-  pl.G = pl.ntiles < g ? pl.ntiles : g;
   pl.ok = true;
   return pl;
+}
+
+// Split-K count G of a launch over n layers of this plan (the per-layer entry: n = 1) and whether the wave-specialised
+// variant runs it: one block per CU with two LDS buffer sets when every block then has >= 2 tiles to pipeline, else two
+// resident blocks per CU.  spec == nullptr: the larger of the two counts, which the workspace is sized for.
+static int wb_split(const WbPlan& pl, int n, bool* spec) {
+  const int per = n * pl.gy * pl.gz;  // (layer, channel-chunk) pairs
+  int g1 = kNumCU / per, g2 = (2 * kNumCU) / per;
+  if (g1 < 1) g1 = 1;
+  if (g2 < 1) g2 = 1;
+  if (g2 > pl.ntiles) g2 = pl.ntiles;
+  if (!spec) return g2;
+  *spec = 2 * pl.lds + 8 * 1024 <= 160 * 1024 && pl.ntiles >= 2 * g1;
+  return *spec ? g1 : g2;
 }
 
 // SPEC stagers prefetch one tile ahead when a tile's pixel pairs fit their register batches (WB_PIT x 512 items per tensor)
@@ -1652,9 +1655,7 @@ int conv_wgrad_s2(const srk_conv_desc& d, const float* x, const float* dy, float
   P.N = d.N; P.Cin = d.Cin; P.Cout = d.Cout; P.XH = d.H; P.XW = d.W; P.YH = d.OH; P.YW = d.OW;
   P.TH = pl.TH; P.TW = pl.TW; P.TWo = pl.TWo; P.tiles_y = pl.tiles_y; P.tiles_x = pl.tiles_x; P.HH = pl.HH; P.TWp = pl.TWp;
   P.CS = pl.CS; P.DS = pl.DS; P.ntiles = pl.ntiles; P.G = pl.G; P.nks = pl.nks; P.nq = pl.nq;
-  static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&k_wgrad_s2), pl.lds);
-  hipLaunchKernelGGL(k_wgrad_s2, dim3(pl.G, pl.gy, pl.gz), dim3(256), pl.lds, s, P);
+  launch_lds<&k_wgrad_s2>(dim3(pl.G, pl.gy, pl.gz), dim3(256), pl.lds, s, P);
   const int rc = check_launch("conv_wgrad_s2");
   if (rc) return rc;
   return conv_wgrad_reduce_launch((const float*)ws, dw, pl.G, d.Cout, d.Cin, 3, 3, 0, beta, db ? bias_ws : nullptr, db, d.Cout,
@@ -1681,10 +1682,8 @@ static bool wt_setup(WgBfParams& P, const srk_conv_desc& d, const WbPlan& pl, bo
 }
 template <bool GRP>
 static void wt_launch(const WgBfParams& P, const typename WgGroupArg<GRP>::type& GR, dim3 grid, size_t lds, hipStream_t s) {
-  static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&k_wgrad_tr<GRP>), lds);
   note_kernel("k_wgrad_tr<%s>", GRP ? "grouped" : "single");
-  hipLaunchKernelGGL(k_wgrad_tr<GRP>, grid, dim3(768), lds, s, P, GR);
+  launch_lds<&k_wgrad_tr<GRP>>(grid, dim3(768), lds, s, P, GR);
 }
 
 bool conv_wgrad_bf_supported(const srk_conv_desc& d) { return wb_plan(d).ok; }
@@ -1692,49 +1691,62 @@ bool conv_wgrad_bf_supported(const srk_conv_desc& d) { return wb_plan(d).ok; }
 size_t conv_wgrad_bf_ws(const srk_conv_desc& d) {
   WbPlan pl = wb_plan(d);
   if (!pl.ok) return 0;
-  return (size_t)pl.G * d.KH * d.KW * d.Cin * d.Cout * sizeof(float) + conv_bias_grad_ws(d);
+  return (size_t)wb_split(pl, 1, nullptr) * d.KH * d.KW * d.Cin * d.Cout * sizeof(float) + conv_bias_grad_ws(d);
 }
 
-static bool wb_k33(const WgBfParams& P) { return P.KH == 3 && P.KW == 3; }
-
-template <int CIT, int COW, int NTW>
-static void wb_launch(const WgBfParams& P, dim3 grid, size_t lds, bool spec, hipStream_t s) {
-  note_kernel("k_wgrad_bf<%d,%d,%d,%s>", CIT, COW, NTW, spec ? "spec" : "tile");
-  if (spec && wb_k33(P)) {
-    static LdsLimit lim3;
-    lim3.ensure(reinterpret_cast<const void*>(&k_wgrad_bf<CIT, COW, NTW, true, false, true>), 2 * lds);
-    hipLaunchKernelGGL((k_wgrad_bf<CIT, COW, NTW, true, false, true>), grid, dim3(64 * CIT * COW + WB_SST), 2 * lds, s, P, WgNoGroup{0});
-    return;
+// What the geometry, the plan and the split decide of WgBfParams, the same for the per-layer and the grouped entry (the
+// tensors are the caller's); the bias partials lie slab_bytes into ws.  lds_half: the LDS of one buffer set (the
+// specialised launch asks for 2 x this), the ring's where that mode applies.
+static WgBfParams wb_params(const srk_conv_desc& d, const WbPlan& pl, int G, bool spec, bool vec_x, bool vec_y, int dy_ps_r,
+                            void* ws, size_t slab_bytes, bool want_bias, size_t& lds_half) {
+  WgBfParams P{};
+  P.ws = (float*)ws;
+  P.bias_partial = want_bias ? reinterpret_cast<float*>(static_cast<char*>(ws) + slab_bytes) : nullptr;
+  P.N = d.N; P.Cin = d.Cin; P.Cout = d.Cout;
+  P.XH = d.H; P.XW = d.W; P.YH = d.OH; P.YW = d.OW;
+  P.KH = d.KH; P.KW = d.KW; P.pad = d.pad;
+  P.TH = pl.TH; P.TW = pl.TW; P.TWo = pl.TWo; P.tiles_y = pl.tiles_y; P.tiles_x = pl.tiles_x;
+  P.HH = pl.HH; P.HWp = pl.HWp; P.CS = pl.CS; P.DS = pl.DS;
+  P.ntiles = pl.ntiles; P.G = G; P.nks = pl.nks;
+  P.vec_x = vec_x; P.vec_y = vec_y;
+  P.dy_ps_r = dy_ps_r;
+  P.dy_ps_C = dy_ps_r ? d.Cout / (dy_ps_r * dy_ps_r) : d.Cout;
+  P.prefetch = wb_prefetch_ok(pl, d) && vec_x && vec_y;  // 16-byte channel groups only
+  lds_half = pl.lds;
+  int cs_ring = 0;
+  if (const size_t ring_bytes = wb_ring_setup(pl, spec, P.prefetch, cs_ring)) {
+    P.ring = 1;
+    P.CS = cs_ring;
+    lds_half = (ring_bytes + 1) / 2;
   }
-  if (spec) {
-    static LdsLimit lim2;
-    lim2.ensure(reinterpret_cast<const void*>(&k_wgrad_bf<CIT, COW, NTW, true, false>), 2 * lds);
-    hipLaunchKernelGGL((k_wgrad_bf<CIT, COW, NTW, true, false>), grid, dim3(64 * CIT * COW + WB_SST), 2 * lds, s, P, WgNoGroup{0});
-    return;
-  }
-  static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&k_wgrad_bf<CIT, COW, NTW, false, false>), lds);
-  hipLaunchKernelGGL((k_wgrad_bf<CIT, COW, NTW, false, false>), grid, dim3(64 * CIT * COW), lds, s, P, WgNoGroup{0});
+  return P;
 }
 
-template <int CIT, int COW, int NTW>
-static void wb_launch_grouped(const WgBfParams& P, const WgGroup& GR, dim3 grid, size_t lds, bool spec, hipStream_t s) {
-  note_kernel("k_wgrad_bf<%d,%d,%d,%s,grouped>", CIT, COW, NTW, spec ? "spec" : "tile");
-  if (spec && wb_k33(P)) {
-    static LdsLimit lim3;
-    lim3.ensure(reinterpret_cast<const void*>(&k_wgrad_bf<CIT, COW, NTW, true, true, true>), 2 * lds);
-    hipLaunchKernelGGL((k_wgrad_bf<CIT, COW, NTW, true, true, true>), grid, dim3(64 * CIT * COW + WB_SST), 2 * lds, s, P, GR);
-    return;
+template <bool GRP, int CIT, int COW, int NTW>
+static void wb_launch_t(const WgBfParams& P, const typename WgGroupArg<GRP>::type& GR, dim3 grid, size_t lds, bool spec,
+                        hipStream_t s) {
+  note_kernel(GRP ? "k_wgrad_bf<%d,%d,%d,%s,grouped>" : "k_wgrad_bf<%d,%d,%d,%s>", CIT, COW, NTW, spec ? "spec" : "tile");
+  if (spec && P.KH == 3 && P.KW == 3)
+    launch_lds<&k_wgrad_bf<CIT, COW, NTW, true, GRP, true>>(grid, dim3(64 * CIT * COW + WB_SST), 2 * lds, s, P, GR);
+  else if (spec)
+    launch_lds<&k_wgrad_bf<CIT, COW, NTW, true, GRP>>(grid, dim3(64 * CIT * COW + WB_SST), 2 * lds, s, P, GR);
+  else
+    launch_lds<&k_wgrad_bf<CIT, COW, NTW, false, GRP>>(grid, dim3(64 * CIT * COW), lds, s, P, GR);
+}
+
+// The kernel of a plan: k_wgrad_tr where it applies, else k_wgrad_bf in the plan's tile configuration.
+template <bool GRP>
+static void wb_launch(WgBfParams& P, const typename WgGroupArg<GRP>::type& GR, const srk_conv_desc& d, const WbPlan& pl,
+                      dim3 grid, size_t lds_half, bool spec, hipStream_t s) {
+  size_t tr_lds = 0;
+  switch (pl.cfg) {
+    case 0:
+      if (wt_setup(P, d, pl, spec, tr_lds)) { wt_launch<GRP>(P, GR, grid, tr_lds, s); break; }
+      wb_launch_t<GRP, 2, 2, 2>(P, GR, grid, lds_half, spec, s);
+      break;
+    case 1: wb_launch_t<GRP, 4, 1, 2>(P, GR, grid, lds_half, spec, s); break;
+    default: wb_launch_t<GRP, 4, 1, 1>(P, GR, grid, lds_half, spec, s); break;
   }
-  if (spec) {
-    static LdsLimit lim2;
-    lim2.ensure(reinterpret_cast<const void*>(&k_wgrad_bf<CIT, COW, NTW, true, true>), 2 * lds);
-    hipLaunchKernelGGL((k_wgrad_bf<CIT, COW, NTW, true, true>), grid, dim3(64 * CIT * COW + WB_SST), 2 * lds, s, P, GR);
-    return;
-  }
-  static LdsLimit lim;
-  lim.ensure(reinterpret_cast<const void*>(&k_wgrad_bf<CIT, COW, NTW, false, true>), lds);
-  hipLaunchKernelGGL((k_wgrad_bf<CIT, COW, NTW, false, true>), grid, dim3(64 * CIT * COW), lds, s, P, GR);
 }
 
 // dw_l (torch layout [co][ci][kh][kw]) = beta*dw_l + sum_g ws[l][g][t][ci][co] and db_l likewise, for every layer of
@@ -1814,65 +1826,25 @@ int conv_wgrad_bf(const srk_conv_desc& d, const float* x, const float* dy, const
     set_error("conv_wgrad_bf: shape not covered");
     return SRK_ERR_UNSUPPORTED;
   }
-  const size_t slab_bytes = (size_t)pl.G * d.KH * d.KW * d.Cin * d.Cout * sizeof(float);
+  const size_t slab_bytes = (size_t)wb_split(pl, 1, nullptr) * d.KH * d.KW * d.Cin * d.Cout * sizeof(float);
   const size_t need = slab_bytes + conv_bias_grad_ws(d);
   if (!ws || ws_bytes < need) {
     set_error("conv_wgrad_bf: workspace %zu < %zu", ws_bytes, need);
     return SRK_ERR_WORKSPACE;
   }
-  WgBfParams P{};
-  P.x = x; P.dy = dy; P.mask_y = mask ? mask->y : nullptr; P.mask_slope = mask ? mask->slope : 0.f;
-  P.ws = (float*)ws;
-  float* bias_ws = reinterpret_cast<float*>(static_cast<char*>(ws) + slab_bytes);
-  P.bias_partial = db ? bias_ws : nullptr;
-  P.N = d.N; P.Cin = d.Cin; P.Cout = d.Cout;
-  P.XH = d.H; P.XW = d.W; P.YH = d.OH; P.YW = d.OW;
-  P.KH = d.KH; P.KW = d.KW; P.pad = d.pad;
-  P.TH = pl.TH; P.TW = pl.TW; P.TWo = pl.TWo; P.tiles_y = pl.tiles_y; P.tiles_x = pl.tiles_x;
-  P.HH = pl.HH; P.HWp = pl.HWp; P.CS = pl.CS; P.DS = pl.DS;
-  P.ntiles = pl.ntiles; P.G = pl.G; P.nks = pl.nks;
-  P.vec_x = (d.Cin % 4 == 0) && ((uintptr_t)x % 16 == 0);
-  P.vec_y = (d.Cout % 4 == 0) && ((uintptr_t)dy % 16 == 0) && (!P.mask_y || (uintptr_t)P.mask_y % 16 == 0);
-  P.dy_ps_r = d.dy_ps_r > 1 ? d.dy_ps_r : 0;
-  P.dy_ps_C = d.dy_ps_r > 1 ? d.Cout / (d.dy_ps_r * d.dy_ps_r) : d.Cout;
-  P.prefetch = wb_prefetch_ok(pl, d) && P.vec_x && P.vec_y;  // 16-byte channel groups only
-  // wave-specialised variant: one 512-thread block per CU with two LDS buffer sets, when every block has >= 2 tiles
-  // to pipeline
-  int G = pl.G;
   bool spec = false;
-  if (2 * pl.lds + 8 * 1024 <= 160 * 1024) {
-    int g1 = kNumCU / (pl.gy * pl.gz);
-    if (g1 < 1) g1 = 1;
-    if (pl.ntiles >= 2 * g1) {
-      spec = true;
-      G = g1;
-    }
-  }
-  P.G = G;
-  dim3 grid(G, pl.gy, pl.gz);
-  size_t lds_half = pl.lds;   // (the specialised launch asks for 2 x this)
-  {
-    int cs_ring = 0;
-    const size_t ring_bytes = wb_ring_setup(pl, spec, P.prefetch, cs_ring);
-    if (ring_bytes) {
-      P.ring = 1;
-      P.CS = cs_ring;
-      lds_half = (ring_bytes + 1) / 2;
-    }
-  }
-  size_t tr_lds = 0;
-  switch (pl.cfg) {
-    case 0:
-      if (wt_setup(P, d, pl, spec, tr_lds)) { wt_launch<false>(P, WgNoGroup{0}, grid, tr_lds, s); break; }
-      wb_launch<2, 2, 2>(P, grid, lds_half, spec, s);
-      break;
-    case 1: wb_launch<4, 1, 2>(P, grid, lds_half, spec, s); break;
-    default: wb_launch<4, 1, 1>(P, grid, lds_half, spec, s); break;
-  }
+  const int G = wb_split(pl, 1, &spec);
+  const float* mask_y = mask ? mask->y : nullptr;
+  const bool vec_x = (d.Cin % 4 == 0) && ((uintptr_t)x % 16 == 0);
+  const bool vec_y = (d.Cout % 4 == 0) && ((uintptr_t)dy % 16 == 0) && (!mask_y || (uintptr_t)mask_y % 16 == 0);
+  size_t lds_half = 0;
+  WgBfParams P = wb_params(d, pl, G, spec, vec_x, vec_y, d.dy_ps_r > 1 ? d.dy_ps_r : 0, ws, slab_bytes, db != nullptr, lds_half);
+  P.x = x; P.dy = dy; P.mask_y = mask_y; P.mask_slope = mask ? mask->slope : 0.f;
+  wb_launch<false>(P, WgNoGroup{0}, d, pl, dim3(G, pl.gy, pl.gz), lds_half, spec, s);
   int rc = check_launch("conv_wgrad_bf");
   if (rc) return rc;
-  return conv_wgrad_reduce_launch((const float*)ws, dw, G, d.Cout, d.Cin, d.KH, d.KW, 0, beta, db ? bias_ws : nullptr,
-                                  db, d.Cout, d.dy_ps_r > 1 ? d.dy_ps_r : 0, s);
+  return conv_wgrad_reduce_launch((const float*)ws, dw, G, d.Cout, d.Cin, d.KH, d.KW, 0, beta, P.bias_partial, db, d.Cout,
+                                  P.dy_ps_r, s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1882,30 +1854,10 @@ int conv_wgrad_bf(const srk_conv_desc& d, const float* x, const float* dy, const
 // work.  With the layer axis in the grid every block walks ~30-40 tiles of ONE layer (double-buffered by the
 // wave-specialised variant), writes one slab, and 33 layers cost two launches instead of 66.
 // ---------------------------------------------------------------------------------------------
-static int wb_group_G(const WbPlan& pl, int n, bool& spec) {
-  const int per = n * pl.gy * pl.gz;  // (layer, channel-chunk) pairs
-  // one block per CU (wave-specialised, two LDS buffer sets) when every block gets >= 2 tiles; else two per CU
-  int g1 = kNumCU / per;
-  if (g1 < 1) g1 = 1;
-  spec = 2 * pl.lds + 8 * 1024 <= 160 * 1024 && pl.ntiles >= 2 * g1;
-  int G = spec ? g1 : (2 * kNumCU) / per;
-  if (G < 1) G = 1;
-  if (G > pl.ntiles) G = pl.ntiles;
-  if (spec && pl.ntiles < 2 * G) spec = false;
-  return G;
-}
-
 size_t conv_wgrad_bf_grouped_ws(const srk_conv_desc& d, int n) {
   WbPlan pl = wb_plan(d);
   if (!pl.ok || n < 1) return 0;
-  bool spec;
-  // workspace for the largest G either variant may pick (2 blocks per CU)
-  int G = (2 * kNumCU) / (n * pl.gy * pl.gz);
-  const int G2 = wb_group_G(pl, n, spec);
-  if (G2 > G) G = G2;
-  if (G < 1) G = 1;
-  if (G > pl.ntiles) G = pl.ntiles;
-  return (size_t)n * G * ((size_t)d.KH * d.KW * d.Cin * d.Cout + d.Cout) * sizeof(float);
+  return (size_t)n * wb_split(pl, n, nullptr) * ((size_t)d.KH * d.KW * d.Cin * d.Cout + d.Cout) * sizeof(float);
 }
 
 int conv_wgrad_bf_grouped(const srk_conv_desc& d, int n, const float* const* xs, const float* const* dys,
@@ -1917,7 +1869,7 @@ int conv_wgrad_bf_grouped(const srk_conv_desc& d, int n, const float* const* xs,
     return SRK_ERR_UNSUPPORTED;
   }
   bool spec = false;
-  const int G = wb_group_G(pl, n, spec);
+  const int G = wb_split(pl, n, &spec);
   const size_t elems = (size_t)d.KH * d.KW * d.Cin * d.Cout;
   const size_t slab_bytes = (size_t)n * G * elems * sizeof(float);
   const size_t need = slab_bytes + (size_t)n * G * d.Cout * sizeof(float);
@@ -1943,45 +1895,16 @@ int conv_wgrad_bf_grouped(const srk_conv_desc& d, int n, const float* const* xs,
     vec_x = vec_x && ((uintptr_t)xs[l] % 16 == 0);
     vec_y = vec_y && ((uintptr_t)dys[l] % 16 == 0) && (!GR.L[l].mask_y || (uintptr_t)GR.L[l].mask_y % 16 == 0);
   }
-  WgBfParams P{};
-  P.ws = (float*)ws;
-  float* bias_ws = reinterpret_cast<float*>(static_cast<char*>(ws) + slab_bytes);
-  P.bias_partial = has_bias ? bias_ws : nullptr;
-  P.N = d.N; P.Cin = d.Cin; P.Cout = d.Cout;
-  P.XH = d.H; P.XW = d.W; P.YH = d.OH; P.YW = d.OW;
-  P.KH = d.KH; P.KW = d.KW; P.pad = d.pad;
-  P.TH = pl.TH; P.TW = pl.TW; P.TWo = pl.TWo; P.tiles_y = pl.tiles_y; P.tiles_x = pl.tiles_x;
-  P.HH = pl.HH; P.HWp = pl.HWp; P.CS = pl.CS; P.DS = pl.DS;
-  P.ntiles = pl.ntiles; P.G = G; P.nks = pl.nks;
-  P.vec_x = vec_x; P.vec_y = vec_y;
-  P.dy_ps_r = 0; P.dy_ps_C = d.Cout;
-  P.prefetch = wb_prefetch_ok(pl, d) && P.vec_x && P.vec_y;  // 16-byte channel groups only
-  dim3 grid(n * G, pl.gy, pl.gz);
-  size_t lds_half = pl.lds;
-  {
-    int cs_ring = 0;
-    const size_t ring_bytes = wb_ring_setup(pl, spec, P.prefetch, cs_ring);
-    if (ring_bytes) {
-      P.ring = 1;
-      P.CS = cs_ring;
-      lds_half = (ring_bytes + 1) / 2;
-    }
-  }
-  size_t tr_lds = 0;
-  switch (pl.cfg) {
-    case 0:
-      if (wt_setup(P, d, pl, spec, tr_lds)) { wt_launch<true>(P, GR, grid, tr_lds, s); break; }
-      wb_launch_grouped<2, 2, 2>(P, GR, grid, lds_half, spec, s);
-      break;
-    case 1: wb_launch_grouped<4, 1, 2>(P, GR, grid, lds_half, spec, s); break;
-    default: wb_launch_grouped<4, 1, 1>(P, GR, grid, lds_half, spec, s); break;
-  }
+  size_t lds_half = 0;
+  WgBfParams P = wb_params(d, pl, G, spec, vec_x, vec_y, 0, ws, slab_bytes, has_bias, lds_half);
+  const float* bias_ws = P.bias_partial;
+  wb_launch<true>(P, GR, d, pl, dim3(n * G, pl.gy, pl.gz), lds_half, spec, s);
   int rc = check_launch("conv_wgrad_bf_grouped");
   if (rc) return rc;
   if (wgrad_reduce_deferring()) {   // queued: one job per layer, summed in this kernel's order by the merged launch
     for (int l = 0; l < n; ++l) {
       rc = wgrad_reduce_submit(false, (const float*)ws + (size_t)l * G * elems, GO.L[l].dw, G, d.Cout, d.Cin, d.KH, d.KW, 0,
-                               beta, has_bias ? (const float*)bias_ws + (size_t)l * G * d.Cout : nullptr, GO.L[l].db, d.Cout,
+                               beta, has_bias ? bias_ws + (size_t)l * G * d.Cout : nullptr, GO.L[l].db, d.Cout,
                                0, s);
       if (rc == -100) break;        // (does not fit a job record: the launch below does the whole group)
       if (rc) return rc;
@@ -1990,7 +1913,7 @@ int conv_wgrad_bf_grouped(const srk_conv_desc& d, int n, const float* const* xs,
   }
   const int nwb = cdiv(elems, 256), bias_blocks = has_bias ? cdiv(d.Cout, 64) : 0;
   hipLaunchKernelGGL(k_wgrad_reduce_grouped, dim3(nwb + bias_blocks, n), dim3(256), 0, s, (const float*)ws, GO, G, d.Cout,
-                     d.Cin, d.KH, d.KW, beta, has_bias ? (const float*)bias_ws : nullptr);
+                     d.Cin, d.KH, d.KW, beta, bias_ws);
   return check_launch("conv_wgrad_reduce_grouped");
 }
 

@@ -23,8 +23,6 @@
 
 namespace srk {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int WG_TP = 64;       // anchor pixels per tile
 constexpr int WG_TP_SC = 192;   // ... of k_wgrad_mfma_smallcin (round 5: a 64-pixel tile was 7 us of barriers and LDS round trips for 16 MFMA quads)
 constexpr int WG_TAPS = 9;      // taps per register pass
@@ -48,10 +46,6 @@ struct WgradParams {
   int xs_floats;       // size of the x region (dy region follows)
   int vec_x, vec_y;
 };
-
-__device__ __forceinline__ f32x4 mfma16w(float a, float b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
 
 // Stage rows [y0,y0+ny) x cols [x0,x0+nx) x channels [cb,cb+cc) of an NHWC tensor into
 // lds[pixel][ps] (channels zero-padded to ccp, OOB pixels zero). `rows_total` >= ny*nx rows are
@@ -186,7 +180,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_mfma(WgradParams P) {
               if (t < tg) {
                 const float a = ap[toff[t]];
 #pragma unroll
-                for (int nt = 0; nt < NTC; ++nt) acc[t][nt] = mfma16w(a, bq[nt], acc[t][nt]);
+                for (int nt = 0; nt < NTC; ++nt) acc[t][nt] = mfma16(a, bq[nt], acc[t][nt]);
               }
             }
           } else {
@@ -196,7 +190,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_mfma(WgradParams P) {
             for (int t = 0; t < WG_TAPS; ++t) {
               if (t < tg) {
 #pragma unroll
-                for (int nt = 0; nt < NTC; ++nt) acc[t][nt] = mfma16w(a, bp[toff[t] + nt * 16], acc[t][nt]);
+                for (int nt = 0; nt < NTC; ++nt) acc[t][nt] = mfma16(a, bp[toff[t] + nt * 16], acc[t][nt]);
               }
             }
           }
@@ -385,7 +379,7 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_mfma_smallcin(WgradParams P) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
           const float a = mval[mt] ? ap[moff[mt]] : 0.f;
-          acc[mt] = mfma16w(a, bv, acc[mt]);
+          acc[mt] = mfma16(a, bv, acc[mt]);
         }
       }
     }
@@ -745,22 +739,13 @@ size_t conv_wgrad_mfma_ws(const srk_conv_desc& d) {
   return need;
 }
 
-template <typename K>
-static void wg_set_lds(K kern, LdsLimit& cur, size_t lds) {
-  cur.ensure(reinterpret_cast<const void*>(kern), lds);
-}
-
 template <int NTC, bool TRANS>
 static void launch_w1(const WgradParams& P, dim3 grid, size_t lds, hipStream_t s) {
-  static LdsLimit cur;
-  wg_set_lds(&k_wgrad_mfma<NTC, TRANS>, cur, lds);
-  hipLaunchKernelGGL((k_wgrad_mfma<NTC, TRANS>), grid, dim3(256), lds, s, P);
+  launch_lds<&k_wgrad_mfma<NTC, TRANS>>(grid, dim3(256), lds, s, P);
 }
 template <int MT>
 static void launch_w2(const WgradParams& P, dim3 grid, size_t lds, hipStream_t s) {
-  static LdsLimit cur;
-  wg_set_lds(&k_wgrad_mfma_smallcin<MT>, cur, lds);
-  hipLaunchKernelGGL((k_wgrad_mfma_smallcin<MT>), grid, dim3(256), lds, s, P);
+  launch_lds<&k_wgrad_mfma_smallcin<MT>>(grid, dim3(256), lds, s, P);
 }
 
 int conv_wgrad_mfma(const srk_conv_desc& d, const float* x, const float* dy, const srk_bwd_mask* mask, float* dw,

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <atomic>
+#include <type_traits>
 #include "../../include/srk.h"
 
 namespace srk {
@@ -48,6 +49,7 @@ inline int check_launch(const char* what) {
   } while (0)
 
 constexpr int kWave = 64;
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 // Compute units of the current device (MI355X: 256), asked once per device: grids of the persistent kernels and the
 // small- / large-problem thresholds follow the part the library runs on instead of a compile-time constant.
 inline int num_cu() {
@@ -66,9 +68,9 @@ inline int num_cu() {
 #define kNumCU (::srk::num_cu())
 constexpr int kMaxDynLds = 160 * 1024;  // gfx950: 160 KB of LDS per CU, all of it usable by one workgroup
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE property of a kernel.  Every launcher that needs more than
-// the 64 KB default owns one `static LdsLimit` and calls ensure() before launching: the limit is raised to the hardware
-// maximum once per (kernel, device).  Thread-safe (relaxed atomics; a race only repeats an idempotent host call), so the
+// hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE property of a kernel.  A kernel that may need more than the
+// 64 KB default is launched through launch_lds (below), which owns one `static LdsLimit` per kernel instantiation and
+// calls ensure() before launching: the limit is raised to the hardware maximum once per (kernel, device).  Thread-safe (relaxed atomics; a race only repeats an idempotent host call), so the
 // main and the autograd threads — or several devices driven from one process — can launch concurrently.
 struct LdsLimit {
   static constexpr int kMaxDevices = 64;
@@ -91,6 +93,15 @@ struct LdsLimit {
   }
 };
 
+// Launches kernel K with `lds` bytes of dynamic LDS, raising K's limit first where needed.  The kernel is named once, so
+// the instantiation whose limit is raised is the one that is launched.
+template <auto K, typename... A>
+inline void launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, A... args) {
+  static LdsLimit lim;  // one per kernel instantiation
+  lim.ensure(reinterpret_cast<const void*>(K), lds);
+  hipLaunchKernelGGL(K, grid, block, lds, s, args...);
+}
+
 inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
 // XCD-aware tile index: hardware deals consecutive block ids round-robin over the 8 XCDs (each with its own L2); this maps
@@ -100,6 +111,29 @@ __device__ __forceinline__ int xcd_tile_index(int bx, int nb) {
   const int per = nb >> 3, rem = nb & 7;
   const int xcd = bx & 7, idx = bx >> 3;
   return xcd < rem ? xcd * (per + 1) + idx : rem * (per + 1) + (xcd - rem) * per + idx;
+}
+
+// compile-time loop: f(std::integral_constant<int, I>{}) for I in [I0, I1)
+template <int I0, int I1, typename F>
+__device__ __forceinline__ void srk_static_for(F&& f) {
+  if constexpr (I0 < I1) {
+    f(std::integral_constant<int, I0>{});
+    srk_static_for<I0 + 1, I1>(f);
+  }
+}
+
+// Buffer descriptor over [base, base + bytes) built from wave-uniform values (the readfirstlane makes the uniformity
+// provable: no waterfall loop around the accesses); an offset outside the range reads zero and stores nothing.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_rsrc(const void* base, unsigned bytes) {
+  const unsigned long long a = reinterpret_cast<unsigned long long>(base);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
+  void* p = reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo);
+  return __builtin_amdgcn_make_buffer_rsrc(p, (short)0, (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+}
+
+// fp32 MFMA, 16 x 16 x 4
+__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
 // Activation forward on a scalar. `a` is the negative-side slope for PReLU / LeakyReLU.

@@ -226,12 +226,10 @@ extern "C" int srk_ssim(const float* pred, const int64_t* pred_strides, const fl
   job.domain = domain;
   const int nb = (int)(job.ntiles < kSsimPartials ? job.ntiles : kSsimPartials);
   const size_t lds = (size_t)job.planes * 2 * kSsimPlane * sizeof(float) + (size_t)5 * kSsimSH * kSsimTW * sizeof(double);
-  static LdsLimit lim;
-  lim.ensure((const void*)k_ssim_partial, lds);
   const double planes_total = (double)N * (luma ? 1 : C);
   const double range = ssim_range(domain);
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(k_ssim_partial, dim3(nb), dim3(256), lds, s, job, (double*)workspace);
+  launch_lds<&k_ssim_partial>(dim3(nb), dim3(256), lds, s, job, (double*)workspace);
   hipLaunchKernelGGL(k_ssim_final, dim3(1), dim3(256), 0, s, (const double*)workspace, nb,
                      1.0 / (planes_total * (job.H - kSsimHalo) * (double)(job.W - kSsimHalo)),
                      1.0 / (planes_total * job.H * (double)job.W * range * range), ssim_out, psnr_out, mse_out);
