@@ -22,7 +22,7 @@
 // its address is 16-byte aligned and the run is complete, else it falls back to scalar accesses (row tails, odd widths,
 // unaligned row strides) -- decided per pointer, so an unaligned source does not cost the stores their width.  The
 // launchers hand a dense image over as ONE row (flatten_rows), so that an odd width does not misalign every other row.
-#include "color_common.h"   // the tables, quant_u8 and the run accessors (shared with tile.hip)
+#include "color_common.h"   // the tables, quant_u8, the run accessors and the run writer (shared with tile.hip)
 
 namespace srk {
 
@@ -76,42 +76,21 @@ __global__ __launch_bounds__(256) void k_rgb_to_ycc(const unsigned char* __restr
   }
 }
 
-// fp32 [C][H][W] through element strides (sc, sh, sw) -> interleaved 8-bit [H][W][C], quantised like ToPILImage after
-// clamp(0, 1).  The nets hand back channels-last tensors (sc = 1, sw = C): for C = 3 a run is then 48 consecutive floats.
+// fp32 [C][H][W] through element strides -> interleaved 8-bit [H][W][C], quantised like ToPILImage after clamp(0, 1).
+// The nets hand back channels-last tensors (sc = 1, sw = C): for C = 3 a run is then 48 consecutive floats.
 template <int C>
-__global__ __launch_bounds__(256) void k_to_u8(const float* __restrict__ x, long long sc, long long sh, long long sw,
-                                               unsigned char* __restrict__ out, int H, int W) {
+__global__ __launch_bounds__(256) void k_to_u8(const float* __restrict__ x, Strides4 s, unsigned char* __restrict__ out, int H,
+                                               int W) {
   const size_t chunks = (size_t)(W + kRun - 1) / kRun;
   const size_t items = chunks * (size_t)H;
+  const PicDst dst{nullptr, out, nullptr, nullptr};
   for (size_t it = (size_t)blockIdx.x * 256 + threadIdx.x; it < items; it += (size_t)gridDim.x * 256) {
     const size_t row = it / chunks;
     const int x0 = (int)(it % chunks) * kRun;
     const int n = W - x0 < kRun ? W - x0 : kRun;
-    const bool full = n == kRun;
-    const float* src = x + (long long)row * sh + (long long)x0 * sw;
-    unsigned w[4 * C];
-#pragma unroll
-    for (int q = 0; q < 4 * C; ++q) w[q] = 0;
-    if (C == 3 && sc == 1 && sw == 3 && full && aligned16(src)) {   // channels-last: the run is dense in memory
-#pragma unroll
-      for (int q = 0; q < 12; ++q) {
-        const float4 f = reinterpret_cast<const float4*>(src)[q];
-        w[q] = quant_u8(f.x) | quant_u8(f.y) << 8 | quant_u8(f.z) << 16 | quant_u8(f.w) << 24;
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        float v[kRun];
-        load_floats(src + c * sc, sw, n, v);
-#pragma unroll
-        for (int p = 0; p < kRun; ++p) {
-          const int k = p * C + c;
-          w[k >> 2] |= quant_u8(v[p]) << ((k & 3) * 8);
-        }
-      }
-    }
-    unsigned char* d = out + (row * (size_t)W + x0) * C;
-    store_bytes<4 * C>(d, full && aligned16(d), n * C, w);
+    float v[C][kRun];
+    load_run<C>(x + (long long)row * s.h + (long long)x0 * s.w, s.c, s.w, n, v);
+    store_run<C, kDstU8>(v, run_mask(n), n, row * (size_t)W + x0, 0, dst, nullptr);
   }
 }
 
@@ -126,37 +105,33 @@ __global__ __launch_bounds__(256) void k_ycc_to_rgb(const float* __restrict__ y_
   stage_tables<kInvTabs>(kColorDev.inv, tab);
   const size_t chunks = (size_t)(W + kRun - 1) / kRun;
   const size_t items = chunks * (size_t)H;
+  const PicDst dst{nullptr, rgb, cb, cr};
   for (size_t it = (size_t)blockIdx.x * 256 + threadIdx.x; it < items; it += (size_t)gridDim.x * 256) {
     const size_t row = it / chunks;
     const int x0 = (int)(it % chunks) * kRun;
     const int n = W - x0 < kRun ? W - x0 : kRun;
-    const bool full = n == kRun;
     const size_t o = row * (size_t)W + x0;
-    unsigned yw[4], bw[4], rw[4];
     if (y_f32) {
-      float v[kRun];
-      load_floats(y_f32 + (long long)row * y_sh + (long long)x0 * y_sw, y_sw, n, v);
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        yw[q] = quant_u8(v[4 * q]) | quant_u8(v[4 * q + 1]) << 8 | quant_u8(v[4 * q + 2]) << 16 | quant_u8(v[4 * q + 3]) << 24;
+      float v[1][kRun];
+      load_floats(y_f32 + (long long)row * y_sh + (long long)x0 * y_sw, y_sw, n, v[0]);
+      store_run<1, kDstYcc>(v, run_mask(n), n, o, 0, dst, tab);
     } else {
+      const bool full = n == kRun;
+      unsigned yw[4], bw[4], rw[4], w[12];
       load_bytes<4>(y_u8 + o, full && aligned16(y_u8 + o), n, yw);
-    }
-    load_bytes<4>(cb + o, full && aligned16(cb + o), n, bw);
-    load_bytes<4>(cr + o, full && aligned16(cr + o), n, rw);
-    unsigned w[12];
+      load_bytes<4>(cb + o, full && aligned16(cb + o), n, bw);
+      load_bytes<4>(cr + o, full && aligned16(cr + o), n, rw);
 #pragma unroll
-    for (int q = 0; q < 12; ++q) w[q] = 0;
+      for (int q = 0; q < 12; ++q) w[q] = 0;
 #pragma unroll
-    for (int p = 0; p < kRun; ++p) {
-      int r, g, b;
-      ycc_to_rgb_px(tab, (int)get_byte(yw, p), (int)get_byte(bw, p), (int)get_byte(rw, p), r, g, b);
-      w[(3 * p) >> 2] |= (unsigned)r << (((3 * p) & 3) * 8);
-      w[(3 * p + 1) >> 2] |= (unsigned)g << (((3 * p + 1) & 3) * 8);
-      w[(3 * p + 2) >> 2] |= (unsigned)b << (((3 * p + 2) & 3) * 8);
+      for (int p = 0; p < kRun; ++p) {
+        int r, g, b;
+        ycc_to_rgb_px(tab, (int)get_byte(yw, p), (int)get_byte(bw, p), (int)get_byte(rw, p), r, g, b);
+        put_rgb(w, p, r, g, b);
+      }
+      unsigned char* d = rgb + o * 3;
+      store_bytes<12>(d, full && aligned16(d), n * 3, w);
     }
-    unsigned char* d = rgb + o * 3;
-    store_bytes<12>(d, full && aligned16(d), n * 3, w);
   }
 }
 
@@ -169,11 +144,7 @@ static void flatten_rows(bool dense, int& H, int& W) {
   H = 1;
 }
 
-static dim3 run_grid(int H, int W) {
-  const size_t items = (size_t)((W + kRun - 1) / kRun) * (size_t)H;
-  const size_t nb = (items + 255) / 256;
-  return dim3((unsigned)(nb > 65535 ? 65535 : nb));
-}
+static dim3 image_grid(int H, int W) { return run_grid((size_t)((W + kRun - 1) / kRun) * (size_t)H); }
 
 }  // namespace srk
 
@@ -207,7 +178,7 @@ extern "C" int srk_rgb_to_ycc_u8(const uint8_t* rgb, int64_t row_stride, int H, 
               (long long)W * 3);
   SRK_REQUIRE(y_f32 || y_u8 || cbcr, "rgb_to_ycc_u8: no output requested");
   flatten_rows(row_stride == (int64_t)W * 3, H, W);
-  hipLaunchKernelGGL(k_rgb_to_ycc, run_grid(H, W), dim3(256), 0, (hipStream_t)stream, rgb, (long long)row_stride, H, W, y_f32,
+  hipLaunchKernelGGL(k_rgb_to_ycc, image_grid(H, W), dim3(256), 0, (hipStream_t)stream, rgb, (long long)row_stride, H, W, y_f32,
                      y_u8, cbcr);
   return check_launch("rgb_to_ycc_u8");
 }
@@ -219,7 +190,7 @@ extern "C" int srk_ycc_to_rgb_u8(const float* y_f32, int64_t y_row_stride, int64
   SRK_REQUIRE(H > 0 && W > 0, "ycc_to_rgb_u8: non-positive dims (%d x %d)", H, W);
   SRK_REQUIRE(!y_f32 || (y_row_stride >= 0 && y_px_stride >= 0), "ycc_to_rgb_u8: negative Y strides");
   flatten_rows(!y_f32 || y_row_stride == (int64_t)W * y_px_stride, H, W);
-  hipLaunchKernelGGL(k_ycc_to_rgb, run_grid(H, W), dim3(256), 0, (hipStream_t)stream, y_f32, (long long)y_row_stride,
+  hipLaunchKernelGGL(k_ycc_to_rgb, image_grid(H, W), dim3(256), 0, (hipStream_t)stream, y_f32, (long long)y_row_stride,
                      (long long)y_px_stride, y_u8, cb, cr, rgb, H, W);
   return check_launch("ycc_to_rgb_u8");
 }
@@ -231,11 +202,9 @@ extern "C" int srk_float_to_u8_image(const float* x, int64_t c_stride, int64_t r
   SRK_REQUIRE(H > 0 && W > 0, "float_to_u8_image: non-positive dims (%d x %d)", H, W);
   SRK_REQUIRE(c_stride >= 0 && row_stride >= 0 && px_stride >= 0, "float_to_u8_image: negative strides");
   flatten_rows(row_stride == (int64_t)W * px_stride, H, W);
-  if (C == 3)
-    hipLaunchKernelGGL(k_to_u8<3>, run_grid(H, W), dim3(256), 0, (hipStream_t)stream, x, (long long)c_stride,
-                       (long long)row_stride, (long long)px_stride, out, H, W);
-  else
-    hipLaunchKernelGGL(k_to_u8<1>, run_grid(H, W), dim3(256), 0, (hipStream_t)stream, x, (long long)c_stride,
-                       (long long)row_stride, (long long)px_stride, out, H, W);
+  launch_pic(C, kDstF32, [&](auto c, auto) {
+    hipLaunchKernelGGL(k_to_u8<c()>, image_grid(H, W), dim3(256), 0, (hipStream_t)stream, x,
+                       Strides4{0, c_stride, row_stride, px_stride}, out, H, W);
+  });
   return check_launch("float_to_u8_image");
 }

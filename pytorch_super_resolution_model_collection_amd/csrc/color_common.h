@@ -1,6 +1,8 @@
-// What the byte-stream kernels of the picture tail share (color.hip: colour conversion and quantisation; tile.hip: the
-// stitch of tiled results, which quantises and converts on the way): Pillow's colour tables, the quantisation expression
-// of ToPILImage, and the 16-pixel-run accessors.  See color.hip for the derivation of the tables and the access pattern.
+// What the kernels of the picture tail share (color.hip: colour conversion and quantisation; tile.hip: the stitch of
+// tiled results; dihedral.hip: the merge of the self-ensemble -- both quantise and convert on the way): Pillow's colour
+// tables, the quantisation expression of ToPILImage, the destination of a picture (PicDst), and for the byte-stream
+// kernels the 16-pixel run: its accessors, its reader (load_run) and its writer (store_run).  See color.hip for the
+// derivation of the tables and the access pattern.
 #ifndef SRK_COLOR_COMMON_H_
 #define SRK_COLOR_COMMON_H_
 #include "srk_common.h"
@@ -108,13 +110,145 @@ __device__ __forceinline__ void load_floats(const float* __restrict__ p, long lo
   }
 }
 
-// copies NT consecutive 256-entry int16 tables from constant memory into LDS (blockDim.x == 256)
-template <int NT>
+// copies NT consecutive 256-entry int16 tables from constant memory into LDS (blockDim.x == THREADS)
+template <int NT, int THREADS = 256>
 __device__ __forceinline__ void stage_tables(const int16_t* __restrict__ src, int16_t* dst) {
   const unsigned* s = reinterpret_cast<const unsigned*>(src);
   unsigned* d = reinterpret_cast<unsigned*>(dst);
-  for (int i = threadIdx.x; i < NT * 128; i += 256) d[i] = s[i];
+  for (int i = threadIdx.x; i < NT * 128; i += THREADS) d[i] = s[i];
   __syncthreads();
+}
+
+// Where a picture goes.  The kernels that end the tail (k_tile_stitch, k_dihedral_merge) are instantiated per kind and
+// take the pointers of all kinds in one PicDst; a launch fills those of its kind.
+enum { kDstF32 = 0,    // fp32 planar [C][H][W]: f32
+       kDstU8 = 1,     // interleaved 8-bit [H][W][C], quantised with quant_u8: u8
+       kDstYcc = 2 };  // C = 1: Y quantised, + 8-bit Cb / Cr planes [H][W] (cb, cr) -> interleaved 8-bit RGB: u8
+struct PicDst {
+  float* f32;
+  unsigned char* u8;
+  const unsigned char* cb;
+  const unsigned char* cr;
+};
+
+// bytes 3 k .. 3 k + 2 of the words w[] = pixel k of an interleaved RGB run
+__device__ __forceinline__ void put_rgb(unsigned* w, int k, int r, int g, int b) {
+  w[(3 * k) >> 2] |= (unsigned)r << (((3 * k) & 3) * 8);
+  w[(3 * k + 1) >> 2] |= (unsigned)g << (((3 * k + 1) & 3) * 8);
+  w[(3 * k + 2) >> 2] |= (unsigned)b << (((3 * k + 2) & 3) * 8);
+}
+
+// `own` of a run whose first n pixels exist
+__device__ __forceinline__ unsigned run_mask(int n) { return n == kRun ? 0xffffu : (1u << n) - 1u; }
+
+// A run of n pixels of one row of a [C][H][W] picture (element strides sc, sw) starting at s -> v[c][k], channel by channel
+template <int C>
+__device__ __forceinline__ void load_planes(const float* __restrict__ s, long long sc, long long sw, int n, float (&v)[C][kRun]) {
+#pragma unroll
+  for (int c = 0; c < C; ++c) load_floats(s + c * sc, sw, n, v[c]);
+}
+// ... taking a complete run of a channels-last RGB picture as what it is in memory, 48 consecutive floats
+template <int C>
+__device__ __forceinline__ void load_run(const float* __restrict__ s, long long sc, long long sw, int n, float (&v)[C][kRun]) {
+  if (C == 3 && sc == 1 && sw == 3 && n == kRun && aligned16(s)) {
+#pragma unroll
+    for (int q = 0; q < 12; ++q) {
+      const float4 f = reinterpret_cast<const float4*>(s)[q];
+      const int e = 4 * q;   // element e of the run's 48 floats is pixel e / C, channel e % C
+      v[e % C][e / C] = f.x, v[(e + 1) % C][(e + 1) / C] = f.y, v[(e + 2) % C][(e + 2) / C] = f.z,
+                   v[(e + 3) % C][(e + 3) / C] = f.w;
+    }
+  } else {
+    load_planes<C>(s, sc, sw, n, v);
+  }
+}
+
+// The run v[c][k] to pixels p0 .. p0 + nrun of a dense picture of `plane` pixels; bit k of `own` says that pixel k is
+// written.  fp32: planar stores.  8-bit: quantised and interleaved, or (kDstYcc; ctab = ColorTables::inv) converted with
+// the run's chroma.  16-byte stores when all 16 pixels are owned and the pointer is aligned, else pixel by pixel.
+template <int C, int DST>
+__device__ __forceinline__ void store_run(const float (&v)[C][kRun], unsigned own, int nrun, size_t p0, size_t plane,
+                                          const PicDst& dst, const int16_t* ctab) {
+  constexpr int OC = DST == kDstYcc ? 3 : C;   // channels of the 8-bit destination
+  const bool all = own == 0xffffu;
+  if (DST == kDstF32) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      float* d = dst.f32 + c * plane + p0;
+      if (all && aligned16(d)) {
+#pragma unroll
+        for (int q = 0; q < kRun / 4; ++q)
+          reinterpret_cast<float4*>(d)[q] = make_float4(v[c][4 * q], v[c][4 * q + 1], v[c][4 * q + 2], v[c][4 * q + 3]);
+      } else {
+#pragma unroll
+        for (int k = 0; k < kRun; ++k)
+          if (own >> k & 1u) d[k] = v[c][k];
+      }
+    }
+  } else {
+    unsigned w[4 * OC];
+#pragma unroll
+    for (int q = 0; q < 4 * OC; ++q) w[q] = 0;
+    if (DST == kDstU8) {
+#pragma unroll
+      for (int c = 0; c < C; ++c)
+#pragma unroll
+        for (int k = 0; k < kRun; ++k) {
+          const int b = k * C + c;
+          w[b >> 2] |= quant_u8(v[c][k]) << ((b & 3) * 8);
+        }
+    } else {
+      unsigned bw[4], rw[4];
+      load_bytes<4>(dst.cb + p0, nrun == kRun && aligned16(dst.cb + p0), nrun, bw);
+      load_bytes<4>(dst.cr + p0, nrun == kRun && aligned16(dst.cr + p0), nrun, rw);
+#pragma unroll
+      for (int k = 0; k < kRun; ++k) {
+        int r, g, b;
+        ycc_to_rgb_px(ctab, (int)quant_u8(v[0][k]), (int)get_byte(bw, k), (int)get_byte(rw, k), r, g, b);
+        put_rgb(w, k, r, g, b);
+      }
+    }
+    unsigned char* d = dst.u8 + p0 * OC;
+    if (all) {
+      store_bytes<4 * OC>(d, aligned16(d), kRun * OC, w);
+    } else {
+#pragma unroll
+      for (int k = 0; k < kRun; ++k)
+        if (own >> k & 1u) {
+#pragma unroll
+          for (int c = 0; c < OC; ++c) d[k * OC + c] = (unsigned char)get_byte(w, k * OC + c);
+        }
+    }
+  }
+}
+
+// ---- host side of the launchers ----
+
+// one thread per run, 256 a block, grid-stride beyond 65535 blocks
+inline dim3 run_grid(size_t runs) {
+  const size_t nb = (runs + 255) / 256;
+  return dim3((unsigned)(nb > 65535 ? 65535 : (nb < 1 ? 1 : nb)));
+}
+
+// f(integral_constant C, integral_constant DST) for the instantiation that (C in {1, 3}, dst) names; a launcher whose
+// kernel has no destination passes kDstF32 and ignores the second argument.  (3, kDstYcc) does not exist: pic_dst_ok.
+template <typename F>
+inline void launch_pic(int C, int dst, F&& f) {
+  typedef std::integral_constant<int, 1> c1;
+  typedef std::integral_constant<int, 3> c3;
+  if (dst == kDstYcc)
+    f(c1{}, std::integral_constant<int, kDstYcc>{});
+  else if (dst == kDstU8)
+    C == 3 ? f(c3{}, std::integral_constant<int, kDstU8>{}) : f(c1{}, std::integral_constant<int, kDstU8>{});
+  else
+    C == 3 ? f(c3{}, std::integral_constant<int, kDstF32>{}) : f(c1{}, std::integral_constant<int, kDstF32>{});
+}
+
+// the chroma planes of an 8-bit destination
+inline int pic_dst_ok(const char* what, int C, const void* cb, const void* cr) {
+  SRK_REQUIRE((cb != nullptr) == (cr != nullptr), "%s: cb and cr come together", what);
+  SRK_REQUIRE(!cb || C == 1, "%s: chroma planes go with a Y output (C = 1), got C = %d", what, C);
+  return SRK_OK;
 }
 
 }  // namespace srk

@@ -127,35 +127,22 @@ __global__ __launch_bounds__(256) void k_dihedral_variants(const float* __restri
   }
 }
 
-// MODE of the merge's destination: the three of k_tile_stitch
-constexpr int kMergeF32 = 0;   // fp32 planar [N][C][oh][ow]
-constexpr int kMergeU8 = 1;    // N = 1: interleaved 8-bit [oh][ow][C], quantised like k_to_u8
-constexpr int kMergeYcc = 2;   // N = 1, C = 1: Y quantised, + 8-bit Cb / Cr planes [oh][ow] -> interleaved RGB like k_ycc_to_rgb
-
-struct Strides4 { long long n, c, h, w; };
-
 // even [4N][C][oh][ow], odd [4N][C][ow][oh] through element strides -> E.  One block per 32 x 32 tile of E: the eight
 // input tiles pass through the LDS tile one after another (k = 0 .. 7, the order of the sum) while every lane keeps the
-// running sums of the destination chunks it owns in registers.
-template <int C, int MODE>
+// running sums of the destination chunks it owns in registers.  DST: kDstF32 is [N][C][oh][ow]; the 8-bit kinds are one
+// picture (N = 1).
+template <int C, int DST>
 __global__ __launch_bounds__(512) void k_dihedral_merge(const float* __restrict__ even, Strides4 se, const float* __restrict__ odd,
-                                                        Strides4 so, int oh, int ow, int tiles_y, int tiles_x,
-                                                        float* __restrict__ out_f32, unsigned char* __restrict__ out_u8,
-                                                        const unsigned char* __restrict__ cb, const unsigned char* __restrict__ cr) {
+                                                        Strides4 so, int oh, int ow, int tiles_y, int tiles_x, PicDst dst) {
   // One-channel 8-bit destinations (U8 with C = 1, YCC) use the lane layout of the fp32 merge, 4 pixels per lane, and four
   // neighbouring lanes (a GROUP: one 16-byte-aligned chunk of 16 pixels) bring their bytes together with cross-lane moves
   // before the 16-byte stores: as many lanes at work as in the fp32 merge, the same conflict-free LDS reads.
-  constexpr bool PACK = MODE != kMergeF32 && C == 1;
-  constexpr int NV = MODE == kMergeF32 || PACK ? 4 : 16;              // values a lane owns per item
-  constexpr int ITEMS = (MODE == kMergeF32 ? C : 1) * kDT / kMergeHalves;   // destination lines per half-wave
+  constexpr bool PACK = DST != kDstF32 && C == 1;
+  constexpr int NV = DST == kDstF32 || PACK ? 4 : 16;              // values a lane owns per item
+  constexpr int ITEMS = (DST == kDstF32 ? C : 1) * kDT / kMergeHalves;   // destination lines per half-wave
   __shared__ float lds[C * kDPlane];
-  __shared__ alignas(16) int16_t ctab[MODE == kMergeYcc ? kInvTabs * 256 : 8];
-  if (MODE == kMergeYcc) {
-    const unsigned* ts = reinterpret_cast<const unsigned*>(kColorDev.inv);
-    unsigned* td = reinterpret_cast<unsigned*>(ctab);
-    for (int i = threadIdx.x; i < kInvTabs * 128; i += blockDim.x) td[i] = ts[i];
-    __syncthreads();
-  }
+  __shared__ alignas(16) int16_t ctab[DST == kDstYcc ? kInvTabs * 256 : 8];
+  if (DST == kDstYcc) stage_tables<kInvTabs, 32 * kMergeHalves>(kColorDev.inv, ctab);
   const int half = threadIdx.x >> 5, lane = threadIdx.x & 31;
   const int tile = blockIdx.x % (tiles_y * tiles_x), n = blockIdx.x / (tiles_y * tiles_x);
   const int a0 = tile / tiles_x * kDT, b0 = tile % tiles_x * kDT;
@@ -167,22 +154,22 @@ __global__ __launch_bounds__(512) void k_dihedral_merge(const float* __restrict_
   auto item_of = [&](int it, int& ch, int& la, int& L, int& lo) -> bool {
     const int line = half + kMergeHalves * it;
     int d;
-    if (MODE == kMergeF32) {
+    if (DST == kDstF32) {
       ch = line / kDT, la = line - ch * kDT;
       L = tw;
-      const float* p = out_f32 + (((size_t)n * C + ch) * oh + a0 + la) * ow + b0;
+      const float* p = dst.f32 + (((size_t)n * C + ch) * oh + a0 + la) * ow + b0;
       d = (int)((reinterpret_cast<uintptr_t>(p) >> 2) & 3);
     } else {
       ch = 0, la = line;
       const size_t px = (size_t)(a0 + la) * ow + b0;
-      if (MODE == kMergeU8) {
+      if (DST == kDstU8) {
         L = tw * C;
-        d = (int)(reinterpret_cast<uintptr_t>(out_u8 + px * C) & 15);
+        d = (int)(reinterpret_cast<uintptr_t>(dst.u8 + px * C) & 15);
       } else {
         L = tw;
         // pixels past the pixel whose 3 bytes start a 16-byte chunk of the picture: 3 (px - d) + out = 0 (mod 16), and
         // 11 is the inverse of 3 mod 16
-        d = (int)((px + 11 * reinterpret_cast<uintptr_t>(out_u8)) & 15);
+        d = (int)((px + 11 * reinterpret_cast<uintptr_t>(dst.u8)) & 15);
       }
     }
     lo = NV * lane - d;
@@ -219,8 +206,8 @@ __global__ __launch_bounds__(512) void k_dihedral_merge(const float* __restrict_
         const int e = lo + u;
         float y = 0.f;
         if (e >= 0 && e < L) {
-          const int lb = MODE == kMergeU8 ? e / C : e;
-          const int c = MODE == kMergeU8 ? e - lb * C : ch;
+          const int lb = DST == kDstU8 ? e / C : e;
+          const int c = DST == kDstU8 ? e - lb * C : ch;
           const int sb = fb ? tw - 1 - lb : lb;
           y = tr ? lds[c * kDPlane + sb * kDLd + sa] : lds[c * kDPlane + sa * kDLd + sb];
         }
@@ -241,15 +228,15 @@ __global__ __launch_bounds__(512) void k_dihedral_merge(const float* __restrict_
       unsigned yq[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) yq[u] = quant_u8(acc[it][u] * 0.125f);
-      if (MODE == kMergeU8) {
+      if (DST == kDstU8) {
         const unsigned w = yq[0] | yq[1] << 8 | yq[2] << 16 | yq[3] << 24;
         const unsigned n1 = __shfl_down(w, 1), n2 = __shfl_down(w, 2), n3 = __shfl_down(w, 3);
         if (whole) {
-          if (sub == 0) *reinterpret_cast<uint4*>(out_u8 + row + g0) = make_uint4(w, n1, n2, n3);
+          if (sub == 0) *reinterpret_cast<uint4*>(dst.u8 + row + g0) = make_uint4(w, n1, n2, n3);
         } else if (ok) {
 #pragma unroll
           for (int u = 0; u < 4; ++u)
-            if (lo + u >= 0 && lo + u < L) out_u8[row + lo + u] = (unsigned char)yq[u];
+            if (lo + u >= 0 && lo + u < L) dst.u8[row + lo + u] = (unsigned char)yq[u];
         }
       } else {
         // this lane's 4 bytes of each chroma plane: its word of the group's 16-byte chunk where that is aligned (the four
@@ -257,7 +244,7 @@ __global__ __launch_bounds__(512) void k_dihedral_merge(const float* __restrict_
         unsigned cw[2] = {0, 0};
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) {
-          const unsigned char* plane = pl ? cr : cb;
+          const unsigned char* plane = pl ? dst.cr : dst.cb;
           if (whole && aligned16(plane + row + g0)) {
             const uint4 q = *reinterpret_cast<const uint4*>(plane + row + g0);
             cw[pl] = sub == 0 ? q.x : (sub == 1 ? q.y : (sub == 2 ? q.z : q.w));
@@ -272,14 +259,12 @@ __global__ __launch_bounds__(512) void k_dihedral_merge(const float* __restrict_
         for (int u = 0; u < 4; ++u) {
           int rr, gg, bb;
           ycc_to_rgb_px(ctab, (int)yq[u], (int)((cw[0] >> (u * 8)) & 255u), (int)((cw[1] >> (u * 8)) & 255u), rr, gg, bb);
-          t[(3 * u) >> 2] |= (unsigned)rr << (((3 * u) & 3) * 8);
-          t[(3 * u + 1) >> 2] |= (unsigned)gg << (((3 * u + 1) & 3) * 8);
-          t[(3 * u + 2) >> 2] |= (unsigned)bb << (((3 * u + 2) & 3) * 8);
+          put_rgb(t, u, rr, gg, bb);
         }
         // the group's 48 bytes are words 3 sub .. 3 sub + 2 of lanes sub = 0 .. 3; lane sub < 3 stores words 4 sub .. 4 sub + 3
         const unsigned n0 = __shfl_down(t[0], 1), n1 = __shfl_down(t[1], 1), n2 = __shfl_down(t[2], 1);
         if (whole) {
-          unsigned char* d = out_u8 + 3 * (row + g0) + 16 * sub;
+          unsigned char* d = dst.u8 + 3 * (row + g0) + 16 * sub;
           if (sub == 0) *reinterpret_cast<uint4*>(d) = make_uint4(t[0], t[1], t[2], n0);
           if (sub == 1) *reinterpret_cast<uint4*>(d) = make_uint4(t[1], t[2], n0, n1);
           if (sub == 2) *reinterpret_cast<uint4*>(d) = make_uint4(t[2], n0, n1, n2);
@@ -288,7 +273,7 @@ __global__ __launch_bounds__(512) void k_dihedral_merge(const float* __restrict_
           for (int u = 0; u < 4; ++u)
             if (lo + u >= 0 && lo + u < L) {
 #pragma unroll
-              for (int c = 0; c < 3; ++c) out_u8[3 * (row + lo + u) + c] = (unsigned char)get_byte(t, 3 * u + c);
+              for (int c = 0; c < 3; ++c) dst.u8[3 * (row + lo + u) + c] = (unsigned char)get_byte(t, 3 * u + c);
             }
         }
       }
@@ -299,8 +284,8 @@ __global__ __launch_bounds__(512) void k_dihedral_merge(const float* __restrict_
       int ch, la, L, lo;
       if (!item_of(it, ch, la, L, lo)) continue;
       const bool whole = lo >= 0 && lo + NV <= L;
-      if (MODE == kMergeF32) {
-        float* d = out_f32 + (((size_t)n * C + ch) * oh + a0 + la) * ow + b0 + lo;
+      if (DST == kDstF32) {
+        float* d = dst.f32 + (((size_t)n * C + ch) * oh + a0 + la) * ow + b0 + lo;
         if (whole) {
           *reinterpret_cast<float4*>(d) = make_float4(acc[it][0] * 0.125f, acc[it][1] * 0.125f, acc[it][2] * 0.125f, acc[it][3] * 0.125f);
         } else {
@@ -309,7 +294,7 @@ __global__ __launch_bounds__(512) void k_dihedral_merge(const float* __restrict_
             if (lo + u >= 0 && lo + u < L) d[u] = acc[it][u] * 0.125f;
         }
       } else {   // interleaved 8-bit RGB: a lane owns one 16-byte chunk
-        unsigned char* d = out_u8 + ((size_t)(a0 + la) * ow + b0) * C + lo;
+        unsigned char* d = dst.u8 + ((size_t)(a0 + la) * ow + b0) * C + lo;
         unsigned w[4] = {0, 0, 0, 0};
 #pragma unroll
         for (int u = 0; u < NV; ++u) w[u >> 2] |= quant_u8(acc[it][u] * 0.125f) << ((u & 3) * 8);
@@ -357,55 +342,39 @@ extern "C" int srk_dihedral_variants(const float* x, int64_t n_stride, int64_t c
   dim3 grid;
   const int rc = dihedral_grid("dihedral_variants", N, H, W, ty, tx, grid);
   if (rc != SRK_OK) return rc;
-  const long long sn = n_stride, sc = c_stride, sh = row_stride, sw = px_stride;
-  if (C == 3)
-    hipLaunchKernelGGL(k_dihedral_variants<3>, grid, dim3(256), 0, (hipStream_t)stream, x, sn, sc, sh, sw, N, H, W, ty, tx, out);
-  else
-    hipLaunchKernelGGL(k_dihedral_variants<1>, grid, dim3(256), 0, (hipStream_t)stream, x, sn, sc, sh, sw, N, H, W, ty, tx, out);
+  launch_pic(C, kDstF32, [&](auto c, auto) {
+    hipLaunchKernelGGL(k_dihedral_variants<c()>, grid, dim3(256), 0, (hipStream_t)stream, x, (long long)n_stride,
+                       (long long)c_stride, (long long)row_stride, (long long)px_stride, N, H, W, ty, tx, out);
+  });
   return check_launch("dihedral_variants");
+}
+
+// checks and launches the merge for one destination
+static int merge(const char* what, const float* even, const int64_t* even_strides, const float* odd, const int64_t* odd_strides,
+                 int N, int C, int oh, int ow, int kind, const PicDst& dst, void* stream) {
+  SRK_REQUIRE(even_strides && odd_strides, "%s: null pointer", what);
+  const Strides4 se = strides4(even_strides), so = strides4(odd_strides);
+  int rc = merge_args_ok(what, even, se, odd, so, N, C, oh, ow, kind == kDstF32 ? (const void*)dst.f32 : dst.u8);
+  if (rc == SRK_OK) rc = pic_dst_ok(what, C, dst.cb, dst.cr);
+  int ty, tx;
+  dim3 grid;
+  if (rc == SRK_OK) rc = dihedral_grid(what, N, oh, ow, ty, tx, grid);
+  if (rc != SRK_OK) return rc;
+  launch_pic(C, kind, [&](auto c, auto d) {
+    hipLaunchKernelGGL((k_dihedral_merge<c(), d()>), grid, dim3(32 * kMergeHalves), 0, (hipStream_t)stream, even, se, odd, so, oh,
+                       ow, ty, tx, dst);
+  });
+  return check_launch(what);
 }
 
 extern "C" int srk_dihedral_merge_f32(const float* even, const int64_t* even_strides, const float* odd, const int64_t* odd_strides,
                                       int N, int C, int oh, int ow, float* out, void* stream) {
-  SRK_REQUIRE(even_strides && odd_strides, "dihedral_merge_f32: null pointer");
-  const Strides4 se{even_strides[0], even_strides[1], even_strides[2], even_strides[3]};
-  const Strides4 so{odd_strides[0], odd_strides[1], odd_strides[2], odd_strides[3]};
-  int rc = merge_args_ok("dihedral_merge_f32", even, se, odd, so, N, C, oh, ow, out);
-  if (rc != SRK_OK) return rc;
-  int ty, tx;
-  dim3 grid;
-  rc = dihedral_grid("dihedral_merge_f32", N, oh, ow, ty, tx, grid);
-  if (rc != SRK_OK) return rc;
-  if (C == 3)
-    hipLaunchKernelGGL((k_dihedral_merge<3, kMergeF32>), grid, dim3(512), 0, (hipStream_t)stream, even, se, odd, so, oh, ow, ty, tx,
-                       out, (unsigned char*)nullptr, (const unsigned char*)nullptr, (const unsigned char*)nullptr);
-  else
-    hipLaunchKernelGGL((k_dihedral_merge<1, kMergeF32>), grid, dim3(512), 0, (hipStream_t)stream, even, se, odd, so, oh, ow, ty, tx,
-                       out, (unsigned char*)nullptr, (const unsigned char*)nullptr, (const unsigned char*)nullptr);
-  return check_launch("dihedral_merge_f32");
+  return merge("dihedral_merge_f32", even, even_strides, odd, odd_strides, N, C, oh, ow, kDstF32, {out, nullptr, nullptr, nullptr},
+               stream);
 }
 
 extern "C" int srk_dihedral_merge_u8(const float* even, const int64_t* even_strides, const float* odd, const int64_t* odd_strides,
                                      int C, int oh, int ow, const uint8_t* cb, const uint8_t* cr, uint8_t* out, void* stream) {
-  SRK_REQUIRE(even_strides && odd_strides, "dihedral_merge_u8: null pointer");
-  const Strides4 se{even_strides[0], even_strides[1], even_strides[2], even_strides[3]};
-  const Strides4 so{odd_strides[0], odd_strides[1], odd_strides[2], odd_strides[3]};
-  int rc = merge_args_ok("dihedral_merge_u8", even, se, odd, so, 1, C, oh, ow, out);
-  if (rc != SRK_OK) return rc;
-  SRK_REQUIRE((cb != nullptr) == (cr != nullptr), "dihedral_merge_u8: cb and cr come together");
-  SRK_REQUIRE(!cb || C == 1, "dihedral_merge_u8: chroma planes go with a Y output (C = 1), got C = %d", C);
-  int ty, tx;
-  dim3 grid;
-  rc = dihedral_grid("dihedral_merge_u8", 1, oh, ow, ty, tx, grid);
-  if (rc != SRK_OK) return rc;
-  if (cb)
-    hipLaunchKernelGGL((k_dihedral_merge<1, kMergeYcc>), grid, dim3(512), 0, (hipStream_t)stream, even, se, odd, so, oh, ow, ty, tx,
-                       (float*)nullptr, out, cb, cr);
-  else if (C == 3)
-    hipLaunchKernelGGL((k_dihedral_merge<3, kMergeU8>), grid, dim3(512), 0, (hipStream_t)stream, even, se, odd, so, oh, ow, ty, tx,
-                       (float*)nullptr, out, (const unsigned char*)nullptr, (const unsigned char*)nullptr);
-  else
-    hipLaunchKernelGGL((k_dihedral_merge<1, kMergeU8>), grid, dim3(512), 0, (hipStream_t)stream, even, se, odd, so, oh, ow, ty, tx,
-                       (float*)nullptr, out, (const unsigned char*)nullptr, (const unsigned char*)nullptr);
-  return check_launch("dihedral_merge_u8");
+  return merge("dihedral_merge_u8", even, even_strides, odd, odd_strides, 1, C, oh, ow, cb ? kDstYcc : kDstU8,
+               {nullptr, out, cb, cr}, stream);
 }

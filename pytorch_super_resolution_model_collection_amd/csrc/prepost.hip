@@ -20,10 +20,6 @@ static inline unsigned pp_grid(size_t items, int per_block) {
 // PSNR: mse = mean((clamp(pred,0,1) - gt)^2); psnr = mse == 0 ? 100 : 10*log10(1/mse).  pred is addressed
 // NHWC-dense or through element strides like the target (a net output is channels_last, a loader's target NCHW).
 // ---------------------------------------------------------------------------------------------
-struct Strides4 {
-  int64_t n, c, h, w;
-};
-
 __global__ __launch_bounds__(256) void k_psnr_partial(const float* __restrict__ pred, Strides4 ps,
                                                       const float* __restrict__ gt, Strides4 gs, int C, int H, int W,
                                                       size_t total, double* __restrict__ partials) {
@@ -165,8 +161,8 @@ extern "C" int srk_psnr(const float* pred, const int64_t* pred_strides, const fl
   SRK_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0, "psnr: bad dims");
   const Strides4 dense = {(int64_t)H * W * C, 1, (int64_t)W * C, C};
   Strides4 ps = dense, gs = dense;
-  if (pred_strides) ps = {pred_strides[0], pred_strides[1], pred_strides[2], pred_strides[3]};
-  if (gt_strides) gs = {gt_strides[0], gt_strides[1], gt_strides[2], gt_strides[3]};
+  if (pred_strides) ps = strides4(pred_strides);
+  if (gt_strides) gs = strides4(gt_strides);
   const size_t total = (size_t)N * C * H * W;
   unsigned nb = pp_grid(total, 256 * 8);
   if (nb > kPsnrPartials) nb = kPsnrPartials;

@@ -104,6 +104,12 @@ inline void launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, A... ar
 
 inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
+// Element strides of a [N][C][H][W] tensor in any layout; passed to kernels by value.
+struct Strides4 {
+  int64_t n, c, h, w;
+};
+inline Strides4 strides4(const int64_t* s) { return {s[0], s[1], s[2], s[3]}; }
+
 // XCD-aware tile index: hardware deals consecutive block ids round-robin over the 8 XCDs (each with its own L2); this maps
 // block `bx` of `nb` to a tile index such that every XCD walks a CONTIGUOUS range of tiles -- neighbouring tiles share
 // their halo in ONE L2 instead of fetching it once per L2.  A bijection on [0, nb) for any nb.

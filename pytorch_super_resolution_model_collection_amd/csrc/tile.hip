@@ -34,9 +34,9 @@ __device__ __forceinline__ int tile_owner(const TileAxis* __restrict__ ax, int n
 // fp32 picture [C][H][W] through element strides -> dense NHWC tiles [n][th][tw][C].  Runs are over the flat destination
 // pixel sequence (tile, y, x): 16 pixels = 16 C consecutive floats.
 template <int C>
-__global__ __launch_bounds__(256) void k_tile_gather(const float* __restrict__ pic, long long sc, long long sh, long long sw,
-                                                     int H, int W, const TileAxis* __restrict__ tab, int nty, int ntx, int th,
-                                                     int tw, int t0, int n, float* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_tile_gather(const float* __restrict__ pic, Strides4 s, int H, int W,
+                                                     const TileAxis* __restrict__ tab, int nty, int ntx, int th, int tw, int t0,
+                                                     int n, float* __restrict__ out) {
   const TileAxis* rows = tab;
   const TileAxis* cols = tab + nty;
   const size_t per_tile = (size_t)th * tw;
@@ -53,14 +53,13 @@ __global__ __launch_bounds__(256) void k_tile_gather(const float* __restrict__ p
       const int t = t0 + tile;
       const int iy = rows[t / ntx].in0 + y, ix = cols[t % ntx].in0 + x;
       const bool ok = iy >= 0 && iy < H && ix >= 0 && ix + nrun <= W;
+      if (ok) {
+        load_planes<C>(pic + (long long)iy * s.h + (long long)ix * s.w, s.c, s.w, nrun, v);
+      } else {
 #pragma unroll
-      for (int c = 0; c < C; ++c) {
-        if (ok) {
-          load_floats(pic + c * sc + (long long)iy * sh + (long long)ix * sw, sw, nrun, v[c]);
-        } else {
+        for (int c = 0; c < C; ++c)
 #pragma unroll
           for (int k = 0; k < kRun; ++k) v[c][k] = 0.f;
-        }
       }
     } else {
 #pragma unroll
@@ -69,7 +68,7 @@ __global__ __launch_bounds__(256) void k_tile_gather(const float* __restrict__ p
         const int iy = rows[t / ntx].in0 + y, ix = cols[t % ntx].in0 + x;
         const bool ok = k < nrun && iy >= 0 && iy < H && ix >= 0 && ix < W;
 #pragma unroll
-        for (int c = 0; c < C; ++c) v[c][k] = ok ? pic[c * sc + (long long)iy * sh + (long long)ix * sw] : 0.f;
+        for (int c = 0; c < C; ++c) v[c][k] = ok ? pic[c * s.c + (long long)iy * s.h + (long long)ix * s.w] : 0.f;
         if (++x == tw) {
           x = 0;
           if (++y == th) y = 0, tile = tile + 1 < n ? tile + 1 : tile;   // (past the last tile only beyond nrun)
@@ -95,22 +94,14 @@ __global__ __launch_bounds__(256) void k_tile_gather(const float* __restrict__ p
   }
 }
 
-// MODE of the stitch's destination
-constexpr int kStitchF32 = 0;   // fp32 planar [C][OH][OW]
-constexpr int kStitchU8 = 1;    // interleaved 8-bit [OH][OW][C], quantised like k_to_u8
-constexpr int kStitchYcc = 2;   // C = 1: Y quantised, + 8-bit Cb / Cr planes [OH][OW] -> interleaved RGB like k_ycc_to_rgb
-
 // tile outputs [n][C][oth][otw] through element strides -> the picture.  Runs are over the flat destination pixel
-// sequence of the rows the chunk's tile rows own.
-template <int C, int MODE>
-__global__ __launch_bounds__(256) void k_tile_stitch(const float* __restrict__ src, long long sn, long long sc, long long sh,
-                                                     long long sw, int oth, int otw, const TileAxis* __restrict__ tab, int nty,
-                                                     int ntx, int t0, int n, float* __restrict__ out_f32,
-                                                     unsigned char* __restrict__ out_u8, const unsigned char* __restrict__ cb,
-                                                     const unsigned char* __restrict__ cr, int OH, int OW) {
-  constexpr int OC = MODE == kStitchYcc ? 3 : C;   // channels of the 8-bit destination
-  __shared__ alignas(16) int16_t ctab[MODE == kStitchYcc ? kInvTabs * 256 : 8];
-  if (MODE == kStitchYcc) stage_tables<kInvTabs>(kColorDev.inv, ctab);
+// sequence of the rows the chunk's tile rows own; DST (kDstF32 / kDstU8 / kDstYcc) is what store_run makes of them.
+template <int C, int DST>
+__global__ __launch_bounds__(256) void k_tile_stitch(const float* __restrict__ src, Strides4 ss, int oth, int otw,
+                                                     const TileAxis* __restrict__ tab, int nty, int ntx, int t0, int n,
+                                                     PicDst dst, int OH, int OW) {
+  __shared__ alignas(16) int16_t ctab[DST == kDstYcc ? kInvTabs * 256 : 8];
+  if (DST == kDstYcc) stage_tables<kInvTabs>(kColorDev.inv, ctab);
   const TileAxis* rows = tab;
   const TileAxis* cols = tab + nty;
   const int ty_first = t0 / ntx, ty_last = (t0 + n - 1) / ntx;
@@ -131,20 +122,8 @@ __global__ __launch_bounds__(256) void k_tile_stitch(const float* __restrict__ s
       const int t = ty * ntx + tx;
       const int ly = Y - rows[ty].out0, lx = X - cols[tx].out0;
       if (t < t0 || t >= t0 + n || ly < 0 || ly >= oth || lx < 0 || lx + nrun > otw) continue;
-      const float* s = src + (long long)(t - t0) * sn + (long long)ly * sh + (long long)lx * sw;
-      if (C == 3 && sc == 1 && sw == 3 && nrun == kRun && aligned16(s)) {   // channels-last: 48 consecutive floats
-#pragma unroll
-        for (int q = 0; q < 12; ++q) {
-          const float4 f = reinterpret_cast<const float4*>(s)[q];
-          const int e = 4 * q;
-          v[e % C][e / C] = f.x, v[(e + 1) % C][(e + 1) / C] = f.y, v[(e + 2) % C][(e + 2) / C] = f.z,
-                       v[(e + 3) % C][(e + 3) / C] = f.w;
-        }
-      } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c) load_floats(s + c * sc, sw, nrun, v[c]);
-      }
-      own = nrun == kRun ? 0xffffu : (1u << nrun) - 1u;
+      load_run<C>(src + (long long)(t - t0) * ss.n + (long long)ly * ss.h + (long long)lx * ss.w, ss.c, ss.w, nrun, v);
+      own = run_mask(nrun);
     } else {
 #pragma unroll
       for (int k = 0; k < kRun; ++k) {
@@ -154,9 +133,9 @@ __global__ __launch_bounds__(256) void k_tile_stitch(const float* __restrict__ s
           const int ly = Y - rows[ty].out0, lx = X - cols[tx].out0;
           ok = t >= t0 && t < t0 + n && ly >= 0 && ly < oth && lx >= 0 && lx < otw;
           if (ok) {
-            const float* s = src + (long long)(t - t0) * sn + (long long)ly * sh + (long long)lx * sw;
+            const float* s = src + (long long)(t - t0) * ss.n + (long long)ly * ss.h + (long long)lx * ss.w;
 #pragma unroll
-            for (int c = 0; c < C; ++c) v[c][k] = s[c * sc];
+            for (int c = 0; c < C; ++c) v[c][k] = s[c * ss.c];
             own |= 1u << k;
           }
         }
@@ -174,74 +153,20 @@ __global__ __launch_bounds__(256) void k_tile_stitch(const float* __restrict__ s
       }
       if (!own) continue;
     }
-    const bool all = own == 0xffffu;
-    if (MODE == kStitchF32) {
-#pragma unroll
-      for (int c = 0; c < C; ++c) {
-        float* d = out_f32 + c * plane + p0;
-        if (all && aligned16(d)) {
-#pragma unroll
-          for (int q = 0; q < kRun / 4; ++q)
-            reinterpret_cast<float4*>(d)[q] = make_float4(v[c][4 * q], v[c][4 * q + 1], v[c][4 * q + 2], v[c][4 * q + 3]);
-        } else {
-#pragma unroll
-          for (int k = 0; k < kRun; ++k)
-            if (own >> k & 1u) d[k] = v[c][k];
-        }
-      }
-    } else {
-      unsigned w[4 * OC];
-#pragma unroll
-      for (int q = 0; q < 4 * OC; ++q) w[q] = 0;
-      if (MODE == kStitchU8) {
-#pragma unroll
-        for (int c = 0; c < C; ++c)
-#pragma unroll
-          for (int k = 0; k < kRun; ++k) {
-            const int b = k * C + c;
-            w[b >> 2] |= quant_u8(v[c][k]) << ((b & 3) * 8);
-          }
-      } else {
-        unsigned bw[4], rw[4];
-        load_bytes<4>(cb + p0, nrun == kRun && aligned16(cb + p0), nrun, bw);
-        load_bytes<4>(cr + p0, nrun == kRun && aligned16(cr + p0), nrun, rw);
-#pragma unroll
-        for (int k = 0; k < kRun; ++k) {
-          int rr, gg, bb;
-          ycc_to_rgb_px(ctab, (int)quant_u8(v[0][k]), (int)get_byte(bw, k), (int)get_byte(rw, k), rr, gg, bb);
-          w[(3 * k) >> 2] |= (unsigned)rr << (((3 * k) & 3) * 8);
-          w[(3 * k + 1) >> 2] |= (unsigned)gg << (((3 * k + 1) & 3) * 8);
-          w[(3 * k + 2) >> 2] |= (unsigned)bb << (((3 * k + 2) & 3) * 8);
-        }
-      }
-      unsigned char* d = out_u8 + p0 * OC;
-      if (all) {
-        store_bytes<4 * OC>(d, aligned16(d), kRun * OC, w);
-      } else {
-#pragma unroll
-        for (int k = 0; k < kRun; ++k)
-          if (own >> k & 1u) {
-#pragma unroll
-            for (int c = 0; c < OC; ++c) d[k * OC + c] = (unsigned char)get_byte(w, k * OC + c);
-          }
-      }
-    }
+    store_run<C, DST>(v, own, nrun, p0, plane, dst, ctab);
   }
 }
 
-static dim3 flat_grid(size_t pixels) {
-  const size_t nb = ((pixels + kRun - 1) / kRun + 255) / 256;
-  return dim3((unsigned)(nb > 65535 ? 65535 : (nb < 1 ? 1 : nb)));
-}
+static dim3 flat_grid(size_t pixels) { return run_grid((pixels + kRun - 1) / kRun); }
 
-static int stitch_args_ok(const char* what, const void* tiles, int64_t sn, int64_t sc, int64_t sh, int64_t sw, int C, int oth,
-                          int otw, const void* table, int nty, int ntx, int t0, int n, const void* out, int OH, int OW) {
+static int stitch_args_ok(const char* what, const void* tiles, const Strides4& s, int C, int oth, int otw, const void* table,
+                          int nty, int ntx, int t0, int n, const void* out, int OH, int OW) {
   SRK_REQUIRE(tiles && table && out, "%s: null pointer", what);
   SRK_REQUIRE(C == 1 || C == 3, "%s: C must be 1 or 3 (got %d)", what, C);
   SRK_REQUIRE(oth > 0 && otw > 0 && OH > 0 && OW > 0, "%s: non-positive dims (tile %d x %d, picture %d x %d)", what, oth, otw,
               OH, OW);
   SRK_REQUIRE(oth <= OH && otw <= OW, "%s: a tile output of %d x %d is larger than the picture %d x %d", what, oth, otw, OH, OW);
-  SRK_REQUIRE(sn >= 0 && sc >= 0 && sh >= 0 && sw >= 0, "%s: negative strides", what);
+  SRK_REQUIRE(s.n >= 0 && s.c >= 0 && s.h >= 0 && s.w >= 0, "%s: negative strides", what);
   SRK_REQUIRE(nty > 0 && ntx > 0 && nty <= 32768 && ntx <= 32768, "%s: bad plan (%d x %d tiles)", what, nty, ntx);
   SRK_REQUIRE(n > 0 && t0 >= 0 && (long long)t0 + n <= (long long)nty * ntx, "%s: tiles %d .. %d are not in a plan of %d x %d", what,
               t0, t0 + n, nty, ntx);
@@ -271,57 +196,38 @@ extern "C" int srk_tile_gather(const float* pic, int64_t c_stride, int64_t row_s
   SRK_REQUIRE(nty > 0 && ntx > 0 && nty <= 32768 && ntx <= 32768, "tile_gather: bad plan (%d x %d tiles)", nty, ntx);
   SRK_REQUIRE(n > 0 && t0 >= 0 && (long long)t0 + n <= (long long)nty * ntx, "tile_gather: tiles %d .. %d are not in a plan of %d x %d",
               t0, t0 + n, nty, ntx);
-  const dim3 grid = flat_grid((size_t)n * th * tw);
-  const TileAxis* tab = reinterpret_cast<const TileAxis*>(table);
-  if (C == 3)
-    hipLaunchKernelGGL(k_tile_gather<3>, grid, dim3(256), 0, (hipStream_t)stream, pic, (long long)c_stride, (long long)row_stride,
-                       (long long)px_stride, H, W, tab, nty, ntx, th, tw, t0, n, out);
-  else
-    hipLaunchKernelGGL(k_tile_gather<1>, grid, dim3(256), 0, (hipStream_t)stream, pic, (long long)c_stride, (long long)row_stride,
-                       (long long)px_stride, H, W, tab, nty, ntx, th, tw, t0, n, out);
+  launch_pic(C, kDstF32, [&](auto c, auto) {
+    hipLaunchKernelGGL(k_tile_gather<c()>, flat_grid((size_t)n * th * tw), dim3(256), 0, (hipStream_t)stream, pic,
+                       Strides4{0, c_stride, row_stride, px_stride}, H, W, reinterpret_cast<const TileAxis*>(table), nty, ntx, th,
+                       tw, t0, n, out);
+  });
   return check_launch("tile_gather");
+}
+
+// checks and launches the stitch for one destination
+static int stitch(const char* what, const float* tiles, const Strides4& s, int C, int oth, int otw, const int32_t* table, int nty,
+                  int ntx, int t0, int n, int kind, const PicDst& dst, int OH, int OW, void* stream) {
+  int rc = stitch_args_ok(what, tiles, s, C, oth, otw, table, nty, ntx, t0, n, kind == kDstF32 ? (const void*)dst.f32 : dst.u8, OH,
+                          OW);
+  if (rc == SRK_OK) rc = pic_dst_ok(what, C, dst.cb, dst.cr);
+  if (rc != SRK_OK) return rc;
+  launch_pic(C, kind, [&](auto c, auto d) {
+    hipLaunchKernelGGL((k_tile_stitch<c(), d()>), stitch_grid(oth, OH, OW, ntx, t0, n), dim3(256), 0, (hipStream_t)stream, tiles, s,
+                       oth, otw, reinterpret_cast<const TileAxis*>(table), nty, ntx, t0, n, dst, OH, OW);
+  });
+  return check_launch(what);
 }
 
 extern "C" int srk_tile_stitch_f32(const float* tiles, int64_t n_stride, int64_t c_stride, int64_t row_stride, int64_t px_stride,
                                    int C, int oth, int otw, const int32_t* table, int nty, int ntx, int t0, int n, float* out,
                                    int OH, int OW, void* stream) {
-  const int rc = stitch_args_ok("tile_stitch_f32", tiles, n_stride, c_stride, row_stride, px_stride, C, oth, otw, table, nty, ntx,
-                                t0, n, out, OH, OW);
-  if (rc != SRK_OK) return rc;
-  const dim3 grid = stitch_grid(oth, OH, OW, ntx, t0, n);
-  const TileAxis* tab = reinterpret_cast<const TileAxis*>(table);
-  if (C == 3)
-    hipLaunchKernelGGL((k_tile_stitch<3, kStitchF32>), grid, dim3(256), 0, (hipStream_t)stream, tiles, (long long)n_stride,
-                       (long long)c_stride, (long long)row_stride, (long long)px_stride, oth, otw, tab, nty, ntx, t0, n, out,
-                       (unsigned char*)nullptr, (const unsigned char*)nullptr, (const unsigned char*)nullptr, OH, OW);
-  else
-    hipLaunchKernelGGL((k_tile_stitch<1, kStitchF32>), grid, dim3(256), 0, (hipStream_t)stream, tiles, (long long)n_stride,
-                       (long long)c_stride, (long long)row_stride, (long long)px_stride, oth, otw, tab, nty, ntx, t0, n, out,
-                       (unsigned char*)nullptr, (const unsigned char*)nullptr, (const unsigned char*)nullptr, OH, OW);
-  return check_launch("tile_stitch_f32");
+  return stitch("tile_stitch_f32", tiles, {n_stride, c_stride, row_stride, px_stride}, C, oth, otw, table, nty, ntx, t0, n, kDstF32,
+                {out, nullptr, nullptr, nullptr}, OH, OW, stream);
 }
 
 extern "C" int srk_tile_stitch_u8(const float* tiles, int64_t n_stride, int64_t c_stride, int64_t row_stride, int64_t px_stride,
                                   int C, int oth, int otw, const int32_t* table, int nty, int ntx, int t0, int n,
                                   const uint8_t* cb, const uint8_t* cr, uint8_t* out, int OH, int OW, void* stream) {
-  const int rc = stitch_args_ok("tile_stitch_u8", tiles, n_stride, c_stride, row_stride, px_stride, C, oth, otw, table, nty, ntx,
-                                t0, n, out, OH, OW);
-  if (rc != SRK_OK) return rc;
-  SRK_REQUIRE((cb != nullptr) == (cr != nullptr), "tile_stitch_u8: cb and cr come together");
-  SRK_REQUIRE(!cb || C == 1, "tile_stitch_u8: chroma planes go with a Y output (C = 1), got C = %d", C);
-  const dim3 grid = stitch_grid(oth, OH, OW, ntx, t0, n);
-  const TileAxis* tab = reinterpret_cast<const TileAxis*>(table);
-  const long long sn = n_stride, sc = c_stride, sh = row_stride, sw = px_stride;
-  if (cb)
-    hipLaunchKernelGGL((k_tile_stitch<1, kStitchYcc>), grid, dim3(256), 0, (hipStream_t)stream, tiles, sn, sc, sh, sw, oth, otw,
-                       tab, nty, ntx, t0, n, (float*)nullptr, out, cb, cr, OH, OW);
-  else if (C == 3)
-    hipLaunchKernelGGL((k_tile_stitch<3, kStitchU8>), grid, dim3(256), 0, (hipStream_t)stream, tiles, sn, sc, sh, sw, oth, otw,
-                       tab, nty, ntx, t0, n, (float*)nullptr, out, (const unsigned char*)nullptr, (const unsigned char*)nullptr,
-                       OH, OW);
-  else
-    hipLaunchKernelGGL((k_tile_stitch<1, kStitchU8>), grid, dim3(256), 0, (hipStream_t)stream, tiles, sn, sc, sh, sw, oth, otw,
-                       tab, nty, ntx, t0, n, (float*)nullptr, out, (const unsigned char*)nullptr, (const unsigned char*)nullptr,
-                       OH, OW);
-  return check_launch("tile_stitch_u8");
+  return stitch("tile_stitch_u8", tiles, {n_stride, c_stride, row_stride, px_stride}, C, oth, otw, table, nty, ntx, t0, n,
+                cb ? kDstYcc : kDstU8, {nullptr, out, cb, cr}, OH, OW, stream);
 }

@@ -1778,6 +1778,48 @@ def _require_u8(what, *tensors):
             raise RuntimeError("%s expects uint8 tensors (got %s)" % (what, t.dtype))
 
 
+def _picture_chw(what, x, hw=None):
+    """The picture x ([C,H,W] or [1,C,H,W], C = 1 or 3; with hw = (H, W): fp32 and of that size) as a detached [C,H,W]
+    view.  `what`: the sentence of the error, up to ', got ...'."""
+    require_cuda(x)
+    v = x.detach()
+    if v.dim() == 4 and v.shape[0] == 1:
+        v = v[0]
+    if v.dim() != 3 or v.shape[0] not in (1, 3) or (hw is not None and (v.dtype != torch.float32 or tuple(v.shape[1:]) != hw)):
+        raise RuntimeError("%s, got %s %s" % (what, x.dtype, tuple(x.shape)))
+    return v
+
+
+def _f32_out(what, shape, device, out):
+    """The fp32 destination of `shape`: `out` checked, or allocated when None."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != device:
+        raise RuntimeError("%s: out must be a dense fp32 [%s] tensor on %s" % (what, ",".join(str(v) for v in shape), device))
+    return out
+
+
+def _u8_out(what, c, h, w, device, cb=None, cr=None, out=None):
+    """The 8-bit destination of a picture of c channels: interleaved uint8 [h,w,c], or with the chroma planes cb / cr
+    (uint8 [h,w], c = 1) [h,w,3].  Returns (cb, cr, out): the planes dense, `out` checked, or allocated when None."""
+    if (cb is None) != (cr is None):
+        raise RuntimeError("%s: cb and cr come together" % what)
+    oc = c
+    if cb is not None:
+        _require_u8(what, cb, cr)
+        if cb.device != device or cr.device != device:
+            raise RuntimeError("%s: the chroma planes are on %s / %s, the net outputs on %s" % (what, cb.device, cr.device, device))
+        if c != 1 or tuple(cb.shape) != (h, w) or tuple(cr.shape) != (h, w):
+            raise RuntimeError("%s: chroma planes must be [%d,%d] and go with a one-channel output (got C = %d, cb %s, cr %s)"
+                               % (what, h, w, c, tuple(cb.shape), tuple(cr.shape)))
+        cb, cr, oc = cb.contiguous(), cr.contiguous(), 3
+    if out is None:
+        out = torch.empty((h, w, oc), dtype=torch.uint8, device=device)
+    elif tuple(out.shape) != (h, w, oc) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != device:
+        raise RuntimeError("%s: out must be a dense uint8 [%d,%d,%d] tensor on %s" % (what, h, w, oc, device))
+    return cb, cr, out
+
+
 def rgb_to_ycc_planes(img_u8_hwc, y_float=False):
     """One pass of k_rgb_to_ycc over an interleaved 8-bit RGB image [H,W,3] (a row-strided view is read in place; pixels
     must be dense): returns (y, cbcr) with cbcr uint8 [2,H,W] planar -- what resize_u8 takes -- and y uint8 [H,W] or,
@@ -1810,14 +1852,10 @@ def ycbcr_to_rgb_u8(y, cb, cr):
     """Image.merge('YCbCr', [y, cb, cr]).convert('RGB') on the device (k_ycc_to_rgb), bit-exact with Pillow: interleaved
     uint8 [H,W,3].  cb / cr: uint8 [H,W].  y: uint8 [H,W], or the fp32 output of a Y-channel net ([H,W], [1,H,W] or
     [1,1,H,W], any strides), which is quantised like ToPILImage after clamp(0, 1) inside the kernel."""
-    _require_u8("ycbcr_to_rgb_u8", cb, cr)
     h, w = int(cb.shape[-2]), int(cb.shape[-1])
-    if cb.dim() != 2 or tuple(cr.shape) != (h, w):
-        raise RuntimeError("ycbcr_to_rgb_u8: cb %s / cr %s must be two [H,W] planes of one size" % (tuple(cb.shape), tuple(cr.shape)))
+    cb, cr, out = _u8_out("ycbcr_to_rgb_u8", 1, h, w, cb.device, cb, cr)
     if y.numel() != h * w or tuple(y.shape[-2:]) != (h, w):
         raise RuntimeError("ycbcr_to_rgb_u8: y %s does not match the chroma planes %s" % (tuple(y.shape), (h, w)))
-    cb, cr = cb.contiguous(), cr.contiguous()
-    out = torch.empty((h, w, 3), dtype=torch.uint8, device=cb.device)
     lib = _lib.load()
     if y.dtype == torch.uint8:
         _require_u8("ycbcr_to_rgb_u8", y)
@@ -1836,14 +1874,9 @@ def to_u8_image(x):
     """ToPILImage()(x.clamp(0, 1)) as an array (edsr.py:305-306), on the device (k_to_u8): fp32 [C,H,W] or [1,C,H,W]
     of any strides (a channels-last net output is read in place), C = 1 or 3 -> interleaved uint8 [H,W,C], each byte
     (uint8)(clamp(x, 0, 1) * 255) with the fp32 product truncated; NaN gives 0."""
-    require_cuda(x)
-    x = x.detach()
-    if x.dim() == 4 and x.shape[0] == 1:
-        x = x[0]
-    if x.dim() != 3 or x.shape[0] not in (1, 3):
-        raise RuntimeError("to_u8_image expects a [C,H,W] or [1,C,H,W] tensor with C = 1 or 3, got shape %s" % (tuple(x.shape),))
+    x = _picture_chw("to_u8_image expects a [C,H,W] or [1,C,H,W] tensor with C = 1 or 3", x)
     c, h, w = (int(v) for v in x.shape)
-    out = torch.empty((h, w, c), dtype=torch.uint8, device=x.device)
+    out = _u8_out("to_u8_image", c, h, w, x.device)[2]
     check(_lib.load().srk_float_to_u8_image(ptr(x), int(x.stride(0)), int(x.stride(1)), int(x.stride(2)), ptr(out), c, h, w,
                                             stream_ptr()), "srk_float_to_u8_image")
     return out
@@ -1897,14 +1930,8 @@ def tile_gather(pic, tp, t0=0, n=None):
     """Tiles t0 .. t0 + n of the plan `tp` (a TilePlan) from the fp32 picture `pic` ([C,H,W] or [1,C,H,W], any strides:
     the planar Y plane of rgb_to_ycc_planes, the planar output of resize_u8 and img_interp's output are read in place),
     C = 1 or 3, as the batch [n,C,th,tw] in channels-last storage the nets take."""
-    require_cuda(pic)
-    x = pic.detach()
-    if x.dim() == 4 and x.shape[0] == 1:
-        x = x[0]
     p = tp.plan
-    if x.dim() != 3 or x.shape[0] not in (1, 3) or x.dtype != torch.float32 or tuple(x.shape[1:]) != (p.H, p.W):
-        raise RuntimeError("tile_gather expects an fp32 [C,%d,%d] picture with C = 1 or 3, got %s %s"
-                           % (p.H, p.W, x.dtype, tuple(pic.shape)))
+    x = _picture_chw("tile_gather expects an fp32 [C,%d,%d] picture with C = 1 or 3" % (p.H, p.W), pic, (p.H, p.W))
     t0, n = _tile_chunk(tp, t0, n)
     c = int(x.shape[0])
     out = _empty_cl(n, c, p.th, p.tw, x)
@@ -1930,10 +1957,7 @@ def tile_stitch(tiles, tp, t0=0, out=None):
     a plan together write every pixel once).  Returns out."""
     y, t0, n, c = _stitch_source("tile_stitch", tiles, tp, t0)
     p = tp.plan
-    if out is None:
-        out = torch.empty((c, p.OH, p.OW), dtype=torch.float32, device=y.device)
-    elif tuple(out.shape) != (c, p.OH, p.OW) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != y.device:
-        raise RuntimeError("tile_stitch: out must be a dense fp32 [%d,%d,%d] tensor on %s" % (c, p.OH, p.OW, y.device))
+    out = _f32_out("tile_stitch", (c, p.OH, p.OW), y.device, out)
     check(_lib.load().srk_tile_stitch_f32(ptr(y), int(y.stride(0)), int(y.stride(1)), int(y.stride(2)), int(y.stride(3)), c,
                                           p.oth, p.otw, ptr(tp.table), tp.nty, tp.ntx, t0, n, ptr(out), p.OH, p.OW,
                                           stream_ptr()), "srk_tile_stitch_f32")
@@ -1946,19 +1970,7 @@ def tile_stitch_u8(tiles, tp, t0=0, out=None, cb=None, cr=None):
     (uint8 [OH,OW,3]); bit-equal to those compositions."""
     y, t0, n, c = _stitch_source("tile_stitch_u8", tiles, tp, t0)
     p = tp.plan
-    if (cb is None) != (cr is None):
-        raise RuntimeError("tile_stitch_u8: cb and cr come together")
-    oc = c
-    if cb is not None:
-        _require_u8("tile_stitch_u8", cb, cr)
-        if c != 1 or tuple(cb.shape) != (p.OH, p.OW) or tuple(cr.shape) != (p.OH, p.OW):
-            raise RuntimeError("tile_stitch_u8: chroma planes must be [%d,%d] and go with a one-channel output (got C = %d, "
-                               "cb %s, cr %s)" % (p.OH, p.OW, c, tuple(cb.shape), tuple(cr.shape)))
-        cb, cr, oc = cb.contiguous(), cr.contiguous(), 3
-    if out is None:
-        out = torch.empty((p.OH, p.OW, oc), dtype=torch.uint8, device=y.device)
-    elif tuple(out.shape) != (p.OH, p.OW, oc) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != y.device:
-        raise RuntimeError("tile_stitch_u8: out must be a dense uint8 [%d,%d,%d] tensor on %s" % (p.OH, p.OW, oc, y.device))
+    cb, cr, out = _u8_out("tile_stitch_u8", c, p.OH, p.OW, y.device, cb, cr, out)
     check(_lib.load().srk_tile_stitch_u8(ptr(y), int(y.stride(0)), int(y.stride(1)), int(y.stride(2)), int(y.stride(3)), c,
                                          p.oth, p.otw, ptr(tp.table), tp.nty, tp.ntx, t0, n,
                                          None if cb is None else ptr(cb), None if cr is None else ptr(cr), ptr(out), p.OH, p.OW,
@@ -2011,8 +2023,7 @@ def _merge_sources(what, even, odd):
                            "%s %s" % (what, even.dtype, tuple(even.shape), odd.dtype, tuple(odd.shape)))
     if o.device != e.device:
         raise RuntimeError("%s: even is on %s and odd on %s" % (what, e.device, o.device))
-    st = lambda t: (ctypes.c_int64 * 4)(*[int(s) for s in t.stride()])
-    return e, o, st(e), st(o)
+    return e, o, _strides4(e), _strides4(o)
 
 
 def dihedral_merge(even, odd, out=None):
@@ -2021,10 +2032,7 @@ def dihedral_merge(even, odd, out=None):
     [4N,C,ow,oh] (k = 1, 3, 5, 7) are read in place through their strides (NCHW or channels-last) -> [N,C,oh,ow]."""
     e, o, se, so = _merge_sources("dihedral_merge", even, odd)
     n, c, oh, ow = int(e.shape[0]) // 4, int(e.shape[1]), int(e.shape[2]), int(e.shape[3])
-    if out is None:
-        out = torch.empty((n, c, oh, ow), dtype=torch.float32, device=e.device)
-    elif tuple(out.shape) != (n, c, oh, ow) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != e.device:
-        raise RuntimeError("dihedral_merge: out must be a dense fp32 [%d,%d,%d,%d] tensor on %s" % (n, c, oh, ow, e.device))
+    out = _f32_out("dihedral_merge", (n, c, oh, ow), e.device, out)
     check(_lib.load().srk_dihedral_merge_f32(ptr(e), se, ptr(o), so, n, c, oh, ow, ptr(out), stream_ptr()),
           "srk_dihedral_merge_f32")
     return out
@@ -2038,18 +2046,7 @@ def dihedral_merge_u8(even, odd, cb=None, cr=None):
     c, oh, ow = int(e.shape[1]), int(e.shape[2]), int(e.shape[3])
     if e.shape[0] != 4:
         raise RuntimeError("dihedral_merge_u8 writes one picture: even must be [4,C,oh,ow], got %s" % (tuple(even.shape),))
-    if (cb is None) != (cr is None):
-        raise RuntimeError("dihedral_merge_u8: cb and cr come together")
-    oc = c
-    if cb is not None:
-        _require_u8("dihedral_merge_u8", cb, cr)
-        if cb.device != e.device or cr.device != e.device:
-            raise RuntimeError("dihedral_merge_u8: the chroma planes are on %s / %s, the net outputs on %s" % (cb.device, cr.device, e.device))
-        if c != 1 or tuple(cb.shape) != (oh, ow) or tuple(cr.shape) != (oh, ow):
-            raise RuntimeError("dihedral_merge_u8: chroma planes must be [%d,%d] and go with a one-channel output (got C = %d, "
-                               "cb %s, cr %s)" % (oh, ow, c, tuple(cb.shape), tuple(cr.shape)))
-        cb, cr, oc = cb.contiguous(), cr.contiguous(), 3
-    out = torch.empty((oh, ow, oc), dtype=torch.uint8, device=e.device)
+    cb, cr, out = _u8_out("dihedral_merge_u8", c, oh, ow, e.device, cb, cr)
     check(_lib.load().srk_dihedral_merge_u8(ptr(e), se, ptr(o), so, c, oh, ow, None if cb is None else ptr(cb),
                                             None if cr is None else ptr(cr), ptr(out), stream_ptr()), "srk_dihedral_merge_u8")
     return out

@@ -224,6 +224,16 @@ class _Trainer(object):
         with torch.no_grad():
             return self.model(x.to(self.device))
 
+    def _net(self, x):
+        """_infer, the last element of a tuple output."""
+        y = self._infer(x)
+        return y[-1] if isinstance(y, tuple) else y
+
+    @staticmethod
+    def _chroma_at(chroma, oh, ow):
+        """(cb, cr): the 8-bit chroma planes [2,h,w] resized to oh x ow, both in one resizer call; (None, None) without."""
+        return (None, None) if chroma is None else tuple(ops.resize_u8(chroma, int(oh), int(ow)))
+
     # -- tiled inference (tiling.py, csrc/tile.hip) ------------------------------------------------------------------
     def _resolve_tile(self, tile, x, ensemble=False):
         """The `tile` option for the net input x -> (tile size or None for one pass, the net's geometry or None).
@@ -251,13 +261,10 @@ class _Trainer(object):
         Returns (even, odd): the outputs for k = 0, 2, 4, 6 and for k = 1, 3, 5, 7, what ops.dihedral_merge takes."""
         var = ops.dihedral_variants(x)
         if var.whole is not None:
-            y = self._infer(var.whole)
-            y = y[-1] if isinstance(y, tuple) else y
+            y = self._net(var.whole)
             even, odd = y[:y.shape[0] // 2], y[y.shape[0] // 2:]
         else:
-            even, odd = self._infer(var.even), self._infer(var.odd)
-            even = even[-1] if isinstance(even, tuple) else even
-            odd = odd[-1] if isinstance(odd, tuple) else odd
+            even, odd = self._net(var.even), self._net(var.odd)
         if tuple(odd.shape) != (even.shape[0], even.shape[1], even.shape[3], even.shape[2]):
             raise RuntimeError("self-ensemble: the net returned %s for the pictures and %s for the transposed ones; it must "
                                "treat both axes alike" % (tuple(even.shape), tuple(odd.shape)))
@@ -278,17 +285,11 @@ class _Trainer(object):
         if tile_batch is None:
             tile_batch = getattr(self.args, 'tile_batch', None) or tiling.DEFAULT_TILE_BATCH
         tile_batch = tiling.tiles_per_chunk(tile_batch, plan.ntiles, ensemble)
-        cb = cr = None
-        if chroma is not None:
-            cb, cr = ops.resize_u8(chroma, plan.OH, plan.OW)   # both chroma planes in one resizer call
+        cb, cr = self._chroma_at(chroma, plan.OH, plan.OW)
         out = None
         for t0 in range(0, plan.ntiles, tile_batch):
             tiles = ops.tile_gather(x, tp, t0, min(tile_batch, plan.ntiles - t0))
-            if ensemble:
-                y = ops.dihedral_merge(*self._infer_variants(tiles))
-            else:
-                y = self._infer(tiles)
-                y = y[-1] if isinstance(y, tuple) else y
+            y = ops.dihedral_merge(*self._infer_variants(tiles)) if ensemble else self._net(tiles)
             if tuple(y.shape[-2:]) != (plan.oth, plan.otw):
                 raise RuntimeError("tiled inference: the net returned %s for a tile of %d x %d, the geometry says %d x %d"
                                    % (tuple(y.shape), plan.th, plan.tw, plan.oth, plan.otw))
@@ -298,18 +299,30 @@ class _Trainer(object):
                 out = ops.tile_stitch(y, tp, t0, out)
         return out if as_u8 else out.unsqueeze(0)
 
+    def _run(self, x, tile, tile_batch, ens, as_u8=False, chroma=None):
+        """The net -- or with `ens` its x8 geometric ensemble (see test_single) -- on the net input x [1,C,H,W]: tiled when
+        `tile` says so, else in one pass.  Returns the fp32 output, or with as_u8 the final interleaved 8-bit picture, written
+        by the last kernel of the path (chroma: the picture's 8-bit Cb / Cr planes [2,h,w] of a Y model, resized to the
+        size the net returned and merged there)."""
+        size, geo = self._resolve_tile(tile, x, ens)
+        if size is not None:
+            return self._infer_tiled(x, geo, size, tile_batch, as_u8, chroma, ens)
+        if ens:
+            even, odd = self._infer_variants(x)
+            if not as_u8:
+                return ops.dihedral_merge(even, odd)
+            return ops.dihedral_merge_u8(even, odd, *self._chroma_at(chroma, even.shape[-2], even.shape[-1]))
+        out = self._net(x)
+        if not as_u8:
+            return out
+        if chroma is None:
+            return ops.to_u8_image(out)
+        return ops.ycbcr_to_rgb_u8(out, *self._chroma_at(chroma, out.shape[-2], out.shape[-1]))
+
     def _forward(self, x, tile=None, tile_batch=None, self_ensemble=None):
         """_net_input and the net (last element of a tuple output) on the device: one pass, or tiled when `tile` says so;
         with self_ensemble the x8 geometric ensemble of the net (see test_single) in place of the net."""
-        x = self._net_input(x)
-        ens = self._self_ensemble(self_ensemble)
-        size, geo = self._resolve_tile(tile, x, ens)
-        if size is None:
-            if ens:
-                return ops.dihedral_merge(*self._infer_variants(x))
-            out = self._infer(x)
-            return out[-1] if isinstance(out, tuple) else out
-        return self._infer_tiled(x, geo, size, tile_batch, ensemble=ens)
+        return self._run(self._net_input(x), tile, tile_batch, self._self_ensemble(self_ensemble))
 
     def test(self, loader=None, save_images=False, tile=None, eval_domain=None, eval_shave=None, self_ensemble=None):
         """Evaluation loop (espcn.py:173-215, edsr.py:196-250): forward + PSNR per image (computed on the device), over
@@ -446,32 +459,14 @@ class _Trainer(object):
             self.load_model()
         rgb = torch.tensor(data.load_img(os.fspath(img_fn)), device=self.device)   # [H,W,3] uint8: the one upload
         h, w = int(rgb.shape[0]), int(rgb.shape[1])
+        chroma = None
         if self.num_channels == 1:
-            y, cbcr = ops.rgb_to_ycc_planes(rgb, y_float=True)
+            y, chroma = ops.rgb_to_ycc_planes(rgb, y_float=True)
             x = y.view(1, 1, h, w)
         else:
             x = ops.resize_u8(rgb.permute(2, 0, 1), h, w, out_float=True).unsqueeze(0)   # ToTensor: planar, / 255
-        x = self._net_input(x)
         ens = self._self_ensemble(self_ensemble)
-        size, geo = self._resolve_tile(tile, x, ens)
-        if size is not None:
-            return self._save_single(self._infer_tiled(x, geo, size, tile_batch, as_u8=True,
-                                                       chroma=cbcr if self.num_channels == 1 else None, ensemble=ens))
-        if ens:
-            even, odd = self._infer_variants(x)
-            if self.num_channels == 1:
-                cbcr = ops.resize_u8(cbcr, int(even.shape[-2]), int(even.shape[-1]))
-                return self._save_single(ops.dihedral_merge_u8(even, odd, cbcr[0], cbcr[1]))
-            return self._save_single(ops.dihedral_merge_u8(even, odd))
-        out = self._infer(x)
-        out = out[-1] if isinstance(out, tuple) else out
-        if self.num_channels == 1:
-            oh, ow = int(out.shape[-2]), int(out.shape[-1])
-            cbcr = ops.resize_u8(cbcr, oh, ow)   # both chroma planes in one resizer call
-            img8 = ops.ycbcr_to_rgb_u8(out, cbcr[0], cbcr[1])
-        else:
-            img8 = ops.to_u8_image(out)
-        return self._save_single(img8)
+        return self._save_single(self._run(self._net_input(x), tile, tile_batch, ens, as_u8=True, chroma=chroma))
 
     def _save_single(self, img8):
         from PIL import Image
