@@ -13,10 +13,14 @@
 // column compute their rows 0 .. 1 as three more fragments.  Every value of the intermediate is the same number whichever
 // tile computed it (same K order, same scale), so the output does not depend on where runs start.
 //
-// First layer: K packs the 5x5 taps as horizontal tap pairs x 4 channel slots -- 15 pairs of 8 K values, 120 of 128 K
-// used in four 16x16x32 steps -- so a pixel fragment is two 8-byte reads of the staged tile.  A wave holds the fp16
-// planes of both 16-channel fragments of ONE 32-channel chunk in registers (64 VGPRs), so that a pixel fragment read
-// feeds six MFMAs, and computes four of the nine pixel fragments, every other tile five.  The intermediate's fp16 scale
+// First layer: every one of the 225 products of the f16x3 sum (75 taps x {w_h x_h, w_h x_m, w_m x_h}) has a K slot of
+// its own: 256 K in eight 16x16x32 steps, one MFMA per step and channel fragment (pr_kgroup below).  A staged pixel is one
+// 16-byte cell of PQ, {h0 h1 h2 m0 m1 m2 h0 h1}, that meets {wh0 wh1 wh2 wh0 wh1 wh2 wm0 wm1} of a tap: 25 K groups, eight
+// of a tap's nine products each; the ninth, wm2 h2, of a kernel row's five taps is one K group against T, which holds h2
+// of four pixels in a row per 8-byte cell.  Steps 0 .. 5 read one aligned 16-byte cell per lane, steps 6 and 7 two aligned
+// 8-byte halves.  A wave holds the filter side of both 16-channel fragments of ONE 32-channel chunk in registers (64
+// VGPRs), so that a pixel fragment read feeds two MFMAs, and computes four of the nine pixel fragments, every other tile
+// five.  The intermediate's fp16 scale
 // is a BOUND, not a measured maximum: max_c(|b_c| + sum |w_c| max|x|) >= max|relu(conv)|, so no rendezvous per tile; a
 // power-of-two scale above the true maximum gives the same planes unless the residual plane underflows, i.e. it only
 // raises the absolute error floor (ops.declare_absmax).
@@ -55,13 +59,16 @@ constexpr int PR_TH = 8, PR_TW = 16, PR_HW = 18;
 constexpr int PR_NSLOTPIX = 6 * PR_HW, PR_NPIXP = PR_NSLOTPIX + 2;  // halo rows 2 .. 7 live in a ring slot: pixels, stride
                                                                     // (pixel p of rows 2 .. 9 is halo pixel 36 + p)
 constexpr int PR_NKEEP = 2 * PR_HW, PR_KP = PR_NKEEP + 2;    // halo rows 8 .. 9 = the tile below's rows 0 .. 1: pixels, stride
-constexpr int PR_XR = 14, PR_XC = 23, PR_XP = 24;   // staged input tile: rows, columns, pixel pitch of a row
+constexpr int PR_XR = 14, PR_XC = 23, PR_XP = 24;   // staged input tile: rows, columns, cell pitch of a row (PQ and T)
 constexpr int PR_NSLOT = 3, PR_NKBUF = 3;
 constexpr int PR_WL2 = 9 * 2 * 256;                 // uint4 of the second layer's filter [tap][chunk][plane][group][32]
 constexpr int PR_HBUF = 4 * PR_NPIXP;               // uint4 per plane of a halo slot [group][NPIXP]
 constexpr int PR_KBUF = 2 * 4 * PR_KP;              // uint4 per plane of a kept-row buffer [chunk][group][KP]
 constexpr int PR_PLANE = PR_NSLOT * PR_HBUF + PR_NKBUF * PR_KBUF;   // the residual planes of all of them lie this far on
-constexpr int PR_XBUF = 2 * PR_XR * PR_XP;          // uint2 per group's input tile [plane][row][pixel]
+constexpr int PR_XPQ = PR_XR * PR_XP * 16;          // bytes of a group's PQ [row][pixel]: 16-byte cells
+constexpr int PR_XT = PR_XPQ + 32;                  // T [row][pixel] of 8-byte cells starts here (cells -3 .. -1 exist: staging)
+constexpr int PR_XBUF = PR_XT + PR_XR * PR_XP * 8;  // bytes of a group's input tile
+constexpr unsigned long long PR_FPIX = 0xfdb9eca875316420ull;   // nibble j: the fragment pixel of lane column j
 constexpr unsigned PR_AMAX_CAP = 1u << 14;          // polls of the max|x| rendezvous (one L2 round trip and a sleep each)
 constexpr int PR_ARRIVE = 1, PR_DEPART = 2;         // counter words of the slots buffer (slot i is word 16 i)
 // Both words MUST stay in one 64-byte line and be touched by one thread of a block (thread 0).  The reset -- the last
@@ -73,10 +80,10 @@ constexpr int PR_ARRIVE = 1, PR_DEPART = 2;         // counter words of the slot
 // waves, the arrival could land after the zeroing and leave the counter at 1 for the next launch.  The ordering of a
 // block's slot maximum before its arrival does not lean on this: the maximum returns a value the arrival waits for.
 constexpr int PR_XLD = 24;                          // float4 loads a thread keeps in flight over its part of the slice
-constexpr int PR_W1P = 2 * 2 * 4 * 2 * 64;          // uint4 of the prepared first layer [c1][nf][ks][plane][lane]; behind
+constexpr int PR_W1P = 2 * 2 * 8 * 64;              // uint4 of the prepared first layer [c1][nf][ks][lane]; behind
 constexpr int PR_W1P_FLOATS = 144;                  // them floats: sum |w_c| [64], |b_c| [64], max |w|
 constexpr size_t PR_W1P_BYTES = (size_t)PR_W1P * 16 + PR_W1P_FLOATS * 4;
-constexpr size_t PR_LDS = (size_t)PR_WL2 * 16 + (size_t)2 * PR_PLANE * 16 + (size_t)2 * PR_XBUF * 8 + 64;
+constexpr size_t PR_LDS = (size_t)PR_WL2 * 16 + (size_t)2 * PR_PLANE * 16 + (size_t)2 * PR_XBUF + 64;
 static_assert(PR_LDS <= 160 * 1024, "k_espcn_pair: LDS");
 
 __device__ unsigned g_pair_timeouts = 0;
@@ -123,9 +130,29 @@ __device__ __forceinline__ float pr_slice_absmax(const float* __restrict__ x, si
   return m;
 }
 
+// The first layer's K: 8 steps of 32, lane quarter kq supplies K values 8 kq .. 8 kq + 7 of step ks -- one K group.
+//   PR_KTAP  tap (dy, dx): pixel side the PQ cell {h0 h1 h2 m0 m1 m2 h0 h1} of pixel (row + dy, col + dx), filter side
+//            {wh0 wh1 wh2 wh0 wh1 wh2 wm0 wm1}: eight of the tap's nine products w_h x_h + w_h x_m + w_m x_h
+//   PR_KROW  kernel row dy: pixel side T(row + dy, col), T(row + dy, col + 4) = h2 of eight pixels in a row, filter side
+//            {wm2 of dx = 0 .. 4, 0, 0, 0}: the ninth product of the row's five taps
+//   PR_KNONE zero weights against any staged cell
+// Steps 0 .. 4: tap (ks, kq).  Step 5: tap (r, 4), r = 0, 2, 1, 3 for kq = 0 .. 3.  Step 6: tap (4, 4), none, rows 0, 2.
+// Step 7: rows 1, 3, 4, none.  A lane's cell of steps 0 .. 4 is its own cell of step 0 plus ks rows: one base and an
+// immediate.  Which groups share a step, and a lane pair (kq, kq + 1) inside it, is chosen for the LDS banks.
+enum { PR_KTAP, PR_KROW, PR_KNONE };
+struct PrKGroup {
+  int kind, dy, dx;
+};
+__device__ __forceinline__ constexpr PrKGroup pr_kgroup(int ks, int kq) {
+  if (ks < 5) return {PR_KTAP, ks, kq};
+  if (ks == 5) return {PR_KTAP, (kq >> 1) + 2 * (kq & 1), 4};
+  if (ks == 6) return kq == 0 ? PrKGroup{PR_KTAP, 4, 4} : (kq == 1 ? PrKGroup{PR_KNONE, 0, 0} : PrKGroup{PR_KROW, 2 * kq - 4, 0});
+  return kq == 3 ? PrKGroup{PR_KNONE, 0, 0} : PrKGroup{PR_KROW, kq == 2 ? 4 : 2 * kq + 1, 0};
+}
+
 // The first layer's filter as the lanes of k_espcn_pair hold it: wave c1 of two writes, for its 32-channel chunk, lane
-// `lane`'s fp16 planes of channel fragment nf and K step ks (tap pairs 4 ks + kq; K = tap pair x 4 channel slots) at the
-// filter's scale; wave 0 adds sum |w_c|, |b_c| and the filter's maximum.
+// `lane`'s filter side of channel fragment nf and K group (ks, kq) at the filter's scale; wave 0 adds sum |w_c|, |b_c| and
+// the filter's maximum.
 __global__ __launch_bounds__(128) void k_espcn_pair_prep(const float* __restrict__ w1, const float* __restrict__ b1,
                                                          uint4* __restrict__ out) {
   const int lane = threadIdx.x & 63, c1 = threadIdx.x >> 6;
@@ -145,19 +172,19 @@ __global__ __launch_bounds__(128) void k_espcn_pair_prep(const float* __restrict
   for (int nf = 0; nf < 2; ++nf) {
     const int co = c1 * 32 + nf * 16 + j;
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const int q = 4 * ks + kq, dy = q / 3, dx0 = 2 * (q - 3 * (q / 3));
+    for (int ks = 0; ks < 8; ++ks) {
+      const PrKGroup g = pr_kgroup(ks, kq);
       float f[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        const int dx = dx0 + (e >> 2), ci = e & 3;
-        const bool on = q < 15 && ci < 3 && dx < 5;   // (the load's index stays inside w1 either way)
-        f[e] = on ? w1[((co * 3 + (on ? ci : 0)) * 5 + (on ? dy : 0)) * 5 + (on ? dx : 0)] : 0.f;
+        const bool tap = g.kind == PR_KTAP;
+        const bool on = tap || (g.kind == PR_KROW && e < 5);   // (the load's index stays inside w1 either way)
+        const int ci = tap ? (e < 6 ? e % 3 : e - 6) : 2, dx = tap ? g.dx : (e < 5 ? e : 0);
+        f[e] = on ? w1[((co * 3 + ci) * 5 + g.dy) * 5 + dx] : 0.f;
       }
       uint4 pl[2];
       split8h(f, sw1, pl);
-      out[(((c1 * 2 + nf) * 4 + ks) * 2 + 0) * 64 + lane] = pl[0];
-      out[(((c1 * 2 + nf) * 4 + ks) * 2 + 1) * 64 + lane] = pl[1];
+      out[((c1 * 2 + nf) * 8 + ks) * 64 + lane] = g.kind == PR_KTAP ? make_uint4(pl[0].x, pl[0].y, pl[0].z, pl[1].w) : pl[1];
     }
   }
   if (c1 == 0) {
@@ -173,12 +200,12 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
   uint4* wl2 = smem4;
   uint4* ring = smem4 + PR_WL2;
   uint4* keep = ring + PR_NSLOT * PR_HBUF;
-  uint2* xin_all = reinterpret_cast<uint2*>(ring + 2 * PR_PLANE);
+  unsigned char* xin_all = reinterpret_cast<unsigned char*>(ring + 2 * PR_PLANE);
   lds_cnt_t* cnt = (lds_cnt_t*)(xin_all + 2 * PR_XBUF);  // full[3], free[3], staged[2], kept full[3], kept free[3]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int grp = wave >> 2, gw = wave & 3, lt = tid & 255;
   const int j = lane & 15, kq = lane >> 4;
-  uint2* xin = xin_all + grp * PR_XBUF;
+  unsigned char* xin = xin_all + grp * PR_XBUF;   // the group's PQ, T PR_XT bytes on
 
   // ---- max|x|: handed in, or this block's slice of it on its way to the slots (the other blocks' comes back below) --------
   const float* w1t = reinterpret_cast<const float*>(B.w1p + PR_W1P);   // sum |w_c| [64], |b_c| [64], max |w|
@@ -219,37 +246,45 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
   }
 
   // ---- first layer: chunk c1 = channels 32 c1 .. 32 c1 + 31 as two 16-channel fragments, half mh of the pixel fragments -----
-  // filter fragments: channel 32 c1 + 16 nf + j, K step ks = tap pairs 4 ks + kq (prepared: k_espcn_pair_prep)
+  // filter fragments: channel 32 c1 + 16 nf + j, K group (ks, kq) (prepared: k_espcn_pair_prep)
   const int c1 = gw >> 1, mh = gw & 1;
   const int mhu = __builtin_amdgcn_readfirstlane(mh), rhu = __builtin_amdgcn_readfirstlane(gw >> 1);  // (dead-row branches)
-  uint4 w1f[2][4][2];  // [channel fragment][K step][plane]
+  uint4 w1f[2][8];  // [channel fragment][K step]
 #pragma unroll
   for (int nf = 0; nf < 2; ++nf)
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-      for (int pl = 0; pl < 2; ++pl) w1f[nf][ks][pl] = B.w1p[(((c1 * 2 + nf) * 4 + ks) * 2 + pl) * 64 + lane];
+    for (int ks = 0; ks < 8; ++ks) w1f[nf][ks] = B.w1p[((c1 * 2 + nf) * 8 + ks) * 64 + lane];
   const float wsum = w1t[lane], babs = w1t[64 + lane];
   // Rows 2 .. 9 of the halo are nine 16-pixel fragments, pixel 16 f + j of the 144: the wave takes f = 4 mh + m, m < 4, and
-  // every other own tile the ninth as m = 4.  Rows 0 .. 1 (36 pixels) are three fragments: f = 2 mh + m, m < 2.
-  // Offsets in staged pixels: K step -> tap pair (dy, dx); fragment -> pixel (the top ones clamped to pixel 35).
-  int koff[4], mpix[5], moff[5], tpix[2], toff[2];
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    const int q = (4 * ks + kq) < 15 ? 4 * ks + kq : 14;
-    koff[ks] = (q / 3) * PR_XP + 2 * (q - 3 * (q / 3));
-  }
+  // every other own tile the ninth as m = 4.  Rows 0 .. 1 (36 pixels) are three fragments: f = 2 mh + m, m < 2.  Lane
+  // column j holds pixel PR_FPIX(j) of its fragment (which pixels share a 16-lane group of ds_read_b128: DESIGN 15.5).
+  // Offsets in staged cells: fragment -> the pixel's cell kq columns on (the top ones clamped to pixel 35).  K steps 0 .. 4
+  // read PQ cell offset + ks PR_XP, step 5 offset + k5; step s of 6 and 7 reads two 8-byte halves, at byte offset * kmul[s]
+  // + kadd[s] and kd[s] on: of the PQ cell of tap (4, 4) or of T's cells of the lane's row.  A lane without a K group reads
+  // what its neighbour reads (the same addresses cost no LDS cycle).
+  const int jp = (int)((PR_FPIX >> (4 * j)) & 15);
+  int mpix[5], moff[5], tpix[2], toff[2];
 #pragma unroll
   for (int m = 0; m < 5; ++m) {
-    mpix[m] = 16 * (m < 4 ? 4 * mh + m : 8) + j;
+    mpix[m] = 16 * (m < 4 ? 4 * mh + m : 8) + jp;
     const int p = PR_NKEEP + mpix[m];
-    moff[m] = (p / PR_HW) * PR_XP + p % PR_HW;
+    moff[m] = (p / PR_HW) * PR_XP + p % PR_HW + kq;
   }
 #pragma unroll
   for (int m = 0; m < 2; ++m) {
-    tpix[m] = 16 * (2 * mh + m) + j;
+    tpix[m] = 16 * (2 * mh + m) + jp;
     const int p = tpix[m] < PR_NKEEP ? tpix[m] : PR_NKEEP - 1;
-    toff[m] = (p / PR_HW) * PR_XP + p % PR_HW;
+    toff[m] = (p / PR_HW) * PR_XP + p % PR_HW + kq;
+  }
+  const int k5 = pr_kgroup(5, kq).dy * PR_XP + 4 - kq;
+  int kmul[2], kadd[2], kd[2];
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const PrKGroup own = pr_kgroup(6 + s, kq), g = own.kind == PR_KNONE ? pr_kgroup(6 + s, kq - 1) : own;
+    kmul[s] = g.kind == PR_KTAP ? 16 : 8;
+    kd[s] = g.kind == PR_KTAP ? 8 : 32;
+    asm volatile("" : "+v"(kd[s]));   // (step 7's is 32 in every lane: as a constant the two reads become one ds_read2_b64)
+    kadd[s] = g.kind == PR_KTAP ? 16 * (g.dy * PR_XP + g.dx - kq) : PR_XT + 8 * (g.dy * PR_XP - kq);
   }
   // where this lane's four channels of fragment 0 go: byte offset of pixel 0 inside a slot / inside a buffer of kept rows
   // (fragment 1: two 8-channel groups on)
@@ -299,25 +334,25 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
         xv[s][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, (int)(o + (ok ? 4u * c * HW_ : 0u)), 0, 0));
     }
   };
-  // NM 16-pixel fragments of the first layer (per output: K step order 0 .. 3, three products per step)
+  // NM 16-pixel fragments of the first layer (per output: K step order 0 .. 7, one product per step)
   auto l1_frags = [&](auto nm, const int* off, f32x4 (*a)[2]) {
     constexpr int NM = decltype(nm)::value;
 #pragma unroll
     for (int m = 0; m < NM; ++m) a[m][0] = a[m][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
+    for (int ks = 0; ks < 8; ++ks) {
 #pragma unroll
       for (int m = 0; m < NM; ++m) {
-        const int pa = off[m] + koff[ks];
-        const uint2 h0 = xin[pa], h1 = xin[pa + 1];
-        const uint2 l0 = xin[PR_XR * PR_XP + pa], l1 = xin[PR_XR * PR_XP + pa + 1];
-        const uint4 xh = make_uint4(h0.x, h0.y, h1.x, h1.y), xm = make_uint4(l0.x, l0.y, l1.x, l1.y);
-#pragma unroll
-        for (int nf = 0; nf < 2; ++nf) {
-          a[m][nf] = mfma16h(w1f[nf][ks][0], xm, a[m][nf]);
-          a[m][nf] = mfma16h(w1f[nf][ks][1], xh, a[m][nf]);
-          a[m][nf] = mfma16h(w1f[nf][ks][0], xh, a[m][nf]);
+        uint4 xc;
+        if (ks < 6) {
+          xc = *reinterpret_cast<const uint4*>(xin + 16 * (off[m] + (ks < 5 ? ks * PR_XP : k5)));
+        } else {
+          const int pa = __mul24(off[m], kmul[ks & 1]) + kadd[ks & 1];
+          const uint2 ca = *reinterpret_cast<const uint2*>(xin + pa), cb = *reinterpret_cast<const uint2*>(xin + pa + kd[ks & 1]);
+          xc = make_uint4(ca.x, ca.y, cb.x, cb.y);
         }
+#pragma unroll
+        for (int nf = 0; nf < 2; ++nf) a[m][nf] = mfma16h(w1f[nf][ks], xc, a[m][nf]);
       }
     }
   };
@@ -367,10 +402,14 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) xmax = fmaxf(xmax, red[i]);
       xmax = __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(xmax)));
-      __syncthreads();  // red is the first staged tile
+      __syncthreads();
       if (tid == 0) atomicAdd(&g_pair_scans, 1u);
     }
   }
+  // The staged tiles start out as zeros (red was in there): T's last slots of a row belong to pixels nobody stages, and the
+  // zero weights they and the empty K groups meet need a finite partner.
+  for (int i = tid; i < 2 * PR_XBUF / 16; i += 512) reinterpret_cast<uint4*>(xin_all)[i] = make_uint4(0u, 0u, 0u, 0u);
+  __syncthreads();
   // ---- scales: input (its maximum), first-layer filter (its maximum), intermediate (bound) --------------------------
   const int kx = amax_scale_exp(xmax);
   const float bnd = wave_max(fabsf(babs) + wsum * xmax);
@@ -408,9 +447,14 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
         const int qy = q / PR_XC, qx = q - qy * PR_XC;
         unsigned h01, m01, h2, m2;
         split2h(xv[s][0], xv[s][1], sx1, h01, m01);
-        split2h(xv[s][2], 0.f, sx1, h2, m2);
-        xin[qy * PR_XP + qx] = make_uint2(h01, h2);
-        xin[PR_XR * PR_XP + qy * PR_XP + qx] = make_uint2(m01, m2);
+        split2h(xv[s][2], 0.f, sx1, h2, m2);   // (high halves: zero)
+        *reinterpret_cast<uint4*>(xin + 16 * (qy * PR_XP + qx)) = make_uint4(h01, h2 | (m01 << 16), (m01 >> 16) | (m2 << 16), h01);
+        // h2 into slot k of T(qy, qx - k): the four cells that start at most three pixels to the left.  Unpredicated: left
+        // of column 0 that is columns 21 .. 23 of the row above, in slots that meet zero weights or nothing (one slot per
+        // such cell, this thread's alone).
+        unsigned short* tq = reinterpret_cast<unsigned short*>(xin + PR_XT) + 4 * (qy * PR_XP + qx);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) tq[-3 * k] = (unsigned short)h2;
       }
     }
     lds_cnt_signal(cnt + 6 + grp);
