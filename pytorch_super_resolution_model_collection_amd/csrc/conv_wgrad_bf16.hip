@@ -1725,7 +1725,10 @@ static WgBfParams wb_params(const srk_conv_desc& d, const WbPlan& pl, int G, boo
 template <bool GRP, int CIT, int COW, int NTW>
 static void wb_launch_t(const WgBfParams& P, const typename WgGroupArg<GRP>::type& GR, dim3 grid, size_t lds, bool spec,
                         hipStream_t s) {
-  note_kernel(GRP ? "k_wgrad_bf<%d,%d,%d,%s,grouped>" : "k_wgrad_bf<%d,%d,%d,%s>", CIT, COW, NTW, spec ? "spec" : "tile");
+  // variant word, then what the shape and the pointers decided: the stagers' mode (spec only), the scalar loads, the group
+  const char* mode = !spec ? "" : P.prefetch && P.ring ? ",pf,ring" : P.prefetch ? ",pf" : "";
+  note_kernel("k_wgrad_bf<%d,%d,%d,%s%s%s%s>", CIT, COW, NTW, spec ? "spec" : "tile", mode,
+              P.vec_x && P.vec_y ? "" : ",scalar", GRP ? ",grouped" : "");
   if (spec && P.KH == 3 && P.KW == 3)
     launch_lds<&k_wgrad_bf<CIT, COW, NTW, true, GRP, true>>(grid, dim3(64 * CIT * COW + WB_SST), 2 * lds, s, P, GR);
   else if (spec)
