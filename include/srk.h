@@ -625,6 +625,29 @@ int srk_ssim(const float* pred, const int64_t* pred_strides, const float* gt, co
              void* stream);
 int srk_ssim_host(const float* pred, const int64_t* pred_strides, const float* gt, const int64_t* gt_strides, int N, int C,
                   int H, int W, int shave, int domain, double* ssim_out, double* psnr_out, double* mse_out);
+/* The SSIM training loss with its gradient, one pass: *loss = 1 - mean SSIM of pred against target, dpred = grad_scale *
+ * d(loss)/d(pred).  (Added without a change of srk_version(): new entry points only.)  Window, constants and the "valid
+ * positions only" rule are srk_ssim's; two things differ: pred is read UNCLAMPED (a clamp would zero the gradient of every
+ * out-of-range pixel; on planes within [0, 1] the loss is 1 - srk_ssim(SRK_SSIM_FLOAT)), and the domain is float, L = 1.
+ * Per plane x (pred), y (target) of H x W, H, W >= 11, with G the 11 x 11 window at the (H-10) x (W-10) valid positions
+ * and G^T its adjoint (a pixel gathers from the up to 11 x 11 positions whose window holds it):
+ *   mx = G x, my = G y, exx = G x^2, eyy = G y^2, exy = G xy;  vx = exx - mx^2, vy = eyy - my^2, cov = exy - mx my
+ *   A1 = 2 mx my + C1, A2 = 2 cov + C2, B1 = mx^2 + my^2 + C1, B2 = vx + vy + C2,  S = A1 A2 / (B1 B2)
+ *   loss = 1 - mean of S over all M = N C (H-10)(W-10) positions (per plane, unweighted across channels)
+ *   Pm = 2 my (A2 - A1)/(B1 B2) - 2 mx S/B1 + 2 mx S/B2,  Pxx = -S / B2,  Pxy = 2 A1 / (B1 B2)
+ *   d loss / d x = -(1/M) (G^T Pm + 2 x G^T Pxx + y G^T Pxy)
+ * All of it in double up to the fp32 stores.  Conventions of srk_loss_forward_backward: pred / dpred NHWC-dense, target
+ * through element strides (n,c,h,w) (NULL = NHWC-dense), dpred may be NULL (loss only), `workspace` of
+ * srk_ssim_loss_workspace_bytes() bytes (contents irrelevant).  No atomics: two calls return the same bits.  A NaN in pred
+ * propagates.  A plane under 11 x 11 is SRK_ERR_BAD_ARG.
+ * srk_ssim_loss_host: the same definition in plain C++ double on HOST pointers, sharing window and formula with the
+ * kernel; *loss and dpred (NHWC-dense, may be NULL) are doubles. */
+size_t srk_ssim_loss_workspace_bytes(void);
+int srk_ssim_loss_forward_backward(const float* pred, const float* target, const int64_t* target_strides, int N, int C,
+                                   int H, int W, float grad_scale, float* loss, float* dpred, void* workspace,
+                                   void* stream);
+int srk_ssim_loss_host(const float* pred, const float* target, const int64_t* target_strides, int N, int C, int H, int W,
+                       double grad_scale, double* loss, double* dpred);
 /* utils.norm / utils.denorm (utils.py:219-239; torchvision Normalize = sub_(mean).div_(std)):
  * y[e] = (x[e] - sub[c]) / div[c], c = (e / inner) % C (inner = H*W for NCHW storage, 1 for NHWC), optionally clamped
  * to [0,1] (denorm's non-VGG branch).  sub_host / div_host are HOST arrays of C <= 8 floats. Bit-equal to torch. */

@@ -8,7 +8,9 @@ and test() cut the picture into overlapping tiles, run them as batches and stitc
 the checkpoint and run test() on the test sets, no training; one line per dataset with PSNR and SSIM) and --eval_domain
 {float,u8,y8} / --eval_shave N (test() also reports PSNR and SSIM on the 8-bit picture or its luma, with a border left out)
 and --self_ensemble (--test_single, --test_only and the test() after training run every picture through the x8 geometric
-self-ensemble, "EDSR+": the net on the eight flips / rotations, transformed back and averaged).
+self-ensemble, "EDSR+": the net on the eight flips / rotations, transformed back and averaged) and --ssim_weight A (train
+on (1 - A) * the model's pixel loss + A * (1 - SSIM), A in [0, 1], default 0; every model but SRGAN and DRCN; the logged
+loss is the mixed one).
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N main.py ..."""
 import argparse
 import os
@@ -28,6 +30,17 @@ def _tile(text):
     v = int(text)
     if v < 1:
         raise argparse.ArgumentTypeError("--tile takes a positive integer or 'auto'")
+    return v
+
+
+def _unit_interval(text):
+    """--ssim_weight: a number in [0, 1] (NaN fails both comparisons)."""
+    try:
+        v = float(text)
+    except ValueError:
+        v = float('nan')
+    if not 0.0 <= v <= 1.0:
+        raise argparse.ArgumentTypeError("--ssim_weight takes a number in [0, 1], got %r" % (text,))
     return v
 
 
@@ -82,7 +95,14 @@ def parse_args(argv=None):
     p.add_argument('--self_ensemble', action='store_true',
                    help='--test_single and test(): the x8 geometric self-ensemble ("EDSR+"): the net on the eight flips / '
                         'rotations of the picture, each result transformed back, the eight averaged; works with --tile')
-    return check_args(p.parse_args(argv))
+    p.add_argument('--ssim_weight', type=_unit_interval, default=0.0, metavar='A',
+                   help='train on (1 - A) * the pixel loss of the model + A * (1 - SSIM) (ops.ssim_loss; LapSRN: both '
+                        'levels); A in [0, 1], default 0: the pixel loss alone, as the reference.  Not for SRGAN and DRCN')
+    args = p.parse_args(argv)
+    if args.ssim_weight > 0 and args.model_name in ('SRGAN', 'DRCN'):
+        p.error('--ssim_weight %g: %s has no SSIM mix (SRGAN trains on an adversarial content term, DRCN through its fused '
+                'recursive-supervision head); use --ssim_weight 0 or another model' % (args.ssim_weight, args.model_name))
+    return check_args(args)
 
 
 def check_args(args):   # main.py:39-57

@@ -19,6 +19,7 @@ ACT_NONE, ACT_RELU, ACT_PRELU, ACT_LRELU, ACT_TANH, ACT_SIGMOID = range(6)
 ALGO_AUTO, ALGO_GENERIC, ALGO_MFMA, ALGO_DIRECT, ALGO_MFMA_BF16X3, ALGO_MFMA_BF16X6, ALGO_MFMA_F16X3 = range(7)
 AMAX_FLOATS = 256   # SRK_AMAX_FLOATS: 16 slots, one per 64-byte line
 LOSS_MSE, LOSS_L1, LOSS_CHARBONNIER, LOSS_BCE = range(4)
+LOSS_SSIM = 4   # no srk_loss kind: ops._Loss routes it to srk_ssim_loss_forward_backward
 SSIM_DOMAINS = {"float": 0, "u8": 1, "y8": 2}   # SRK_SSIM_FLOAT / _U8 / _Y8
 ACT_BY_NAME = {None: ACT_NONE, "relu": ACT_RELU, "prelu": ACT_PRELU, "lrelu": ACT_LRELU, "tanh": ACT_TANH,
                "sigmoid": ACT_SIGMOID}
@@ -178,6 +179,11 @@ _PROTOTYPES = {
     "srk_ssim_host": (c_int, [c_vp, ctypes.POINTER(ctypes.c_int64), c_vp, ctypes.POINTER(ctypes.c_int64), c_int, c_int,
                               c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                               ctypes.POINTER(ctypes.c_double)]),
+    "srk_ssim_loss_workspace_bytes": (c_size, []),
+    "srk_ssim_loss_forward_backward": (c_int, [c_f, c_f, ctypes.POINTER(ctypes.c_int64), c_int, c_int, c_int, c_int,
+                                               c_float, c_f, c_f, c_vp, c_vp]),
+    "srk_ssim_loss_host": (c_int, [c_vp, c_vp, ctypes.POINTER(ctypes.c_int64), c_int, c_int, c_int, c_int,
+                                   ctypes.c_double, ctypes.POINTER(ctypes.c_double), c_vp]),
     "srk_channel_affine": (c_int, [c_f, c_f, c_size, c_int, c_size, ctypes.POINTER(c_float), ctypes.POINTER(c_float),
                                    c_int, c_vp]),
     "srk_upsample_nearest_forward": (c_int, [c_f, c_f, c_int, c_int, c_int, c_int, c_int, c_vp]),

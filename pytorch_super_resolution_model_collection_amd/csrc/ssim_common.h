@@ -45,6 +45,26 @@ __host__ __device__ __forceinline__ double ssim_from_moments(double mx, double m
   return ((2.0 * mxy + c1) * (2.0 * cov + c2)) / ((mxx + myy + c1) * (vx + vy + c2));
 }
 
+// The training loss 1 - mean(SSIM) (ssim_loss.hip; L = 1, pred unclamped): the map value S of one position
+// -- the very expression of ssim_from_moments, so the loss of planes in [0, 1] is 1 - srk_ssim -- and what that
+// position hands back to the pixels of its window through the adjoint G^T of the window:
+//   d(sum S)/dx = G^T pm + 2 x * G^T pxx + y * G^T pxy,   pm = dS/dmx, pxx = dS/dexx, pxy = dS/dexy (include/srk.h).
+// On flat planes the three terms are ~1/C2 = 1e3 times their sum, hence double to the end.
+__host__ __device__ __forceinline__ double ssim_loss_terms(double mx, double my, double exx, double eyy, double exy,
+                                                           double& pm, double& pxx, double& pxy) {
+#pragma clang fp contract(off)
+  const double c1 = 0.01 * 0.01, c2 = 0.03 * 0.03;
+  const double vx = ssim_central(exx, mx, mx), vy = ssim_central(eyy, my, my), cov = ssim_central(exy, mx, my);
+  const double mxy = mx * my, mxx = mx * mx, myy = my * my;
+  const double a1 = 2.0 * mxy + c1, a2 = 2.0 * cov + c2, b1 = mxx + myy + c1, b2 = vx + vy + c2;
+  const double s = (a1 * a2) / (b1 * b2);
+  const double ib1 = 1.0 / b1, ib2 = 1.0 / b2;   // (three divisions a position instead of six: they are half its cost)
+  pm = 2.0 * my * (a2 - a1) * ib1 * ib2 - 2.0 * mx * s * ib1 + 2.0 * mx * s * ib2;
+  pxx = -s * ib2;
+  pxy = 2.0 * a1 * ib1 * ib2;
+  return s;
+}
+
 __host__ __device__ __forceinline__ double psnr_from_mse(double mse) {
   return mse == 0.0 ? 100.0 : 10.0 * log10(1.0 / mse);
 }

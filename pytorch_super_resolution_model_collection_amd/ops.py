@@ -1118,6 +1118,9 @@ class _Loss(torch.autograd.Function):
         require_cuda(pred, target)
         if pred.shape != target.shape:
             raise RuntimeError("loss: pred %s vs target %s" % (tuple(pred.shape), tuple(target.shape)))
+        if kind == _lib.LOSS_SSIM and (pred.dim() != 4 or min(pred.shape[2:]) < 11):
+            raise RuntimeError("ssim_loss: takes [N,C,H,W] with planes of at least the 11 x 11 window, got shape %s"
+                               % (tuple(pred.shape),))
         if pred.dim() == 4:
             pred = _dense(pred)
             n, c, h, w = pred.shape
@@ -1132,11 +1135,16 @@ class _Loss(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=pred.device)
         need_grad = ctx.needs_input_grad[0]
         dpred = torch.empty_like(pred) if need_grad else None
-        ws = torch.empty(int(lib.srk_loss_workspace_bytes()), dtype=torch.uint8, device=pred.device)
+        ws_bytes = lib.srk_ssim_loss_workspace_bytes() if kind == _lib.LOSS_SSIM else lib.srk_loss_workspace_bytes()
+        ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=pred.device)
         seed = _LOSS_SEED[0]
         ctx.seed_ptr, ctx.seed_value = (seed[1].data_ptr(), seed[0]) if seed is not None else (0, 1.0)
-        check(lib.srk_loss_forward_backward(kind, ptr(pred), ptr(target), strides, n, c, h, w, eps, ctx.seed_value, ptr(loss),
-                                            ptr(dpred), ptr(ws), stream_ptr()), "srk_loss_forward_backward")
+        if kind == _lib.LOSS_SSIM:
+            check(lib.srk_ssim_loss_forward_backward(ptr(pred), ptr(target), strides, n, c, h, w, ctx.seed_value, ptr(loss),
+                                                     ptr(dpred), ptr(ws), stream_ptr()), "srk_ssim_loss_forward_backward")
+        else:
+            check(lib.srk_loss_forward_backward(kind, ptr(pred), ptr(target), strides, n, c, h, w, eps, ctx.seed_value,
+                                                ptr(loss), ptr(dpred), ptr(ws), stream_ptr()), "srk_loss_forward_backward")
         ctx.dpred = dpred
         return loss
 
@@ -1205,6 +1213,18 @@ def loss_sum(l1, l2, a=1.0, b=1.0):
     return _LossSum.apply(l1, l2, a, b)
 
 
+def weighted_term(loss_fn, weight, pred, target):
+    """loss_fn(pred, target) as a term that loss_sum will weigh by `weight`.  Where no seed is declared yet (one GPU) the
+    weight is declared as the term's seed, with the very constant that _LossSum.backward hands out under the unit seed:
+    the loss kernel folds it into its gradient and the backward returns that as it is, instead of a srk_scale_dev pass
+    over the whole gradient per term.  Under a declared seed (data parallel), or for a weight of 0 or 1 (which
+    _LossSum answers with its own upstream gradient), the term is computed plainly and takes the general path."""
+    if _LOSS_SEED[0] is None and 0.0 < weight < 1.0:
+        with loss_seed(weight, _const_scalar(weight, pred.device)):
+            return loss_fn(pred, target)
+    return loss_fn(pred, target)
+
+
 def mse_loss(pred, target):
     """nn.MSELoss() (srcnn.py:84-86,129; vdsr.py:145; srgan.py:205,300)."""
     return _Loss.apply(pred, target, _lib.LOSS_MSE, 0.0)
@@ -1223,6 +1243,14 @@ def charbonnier_loss(pred, target, eps=1e-6):
 def bce_loss(pred, target):
     """nn.BCELoss() (srgan.py:157,276-297)."""
     return _Loss.apply(pred, target, _lib.LOSS_BCE, 0.0)
+
+
+def ssim_loss(pred, target):
+    """1 - mean SSIM of pred against target (11 x 11 Gaussian window, valid positions, L = 1, every plane and position
+    weighing the same; pred is read UNCLAMPED so that out-of-range pixels keep their gradient): the loss and its
+    gradient from one launch, with the contract of the pixel losses (loss_seed, unit seed, loss_sum).
+    [N,C,H,W] with H, W >= 11.  include/srk.h: srk_ssim_loss_forward_backward."""
+    return _Loss.apply(pred, target, _lib.LOSS_SSIM, 0.0)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -70,6 +70,8 @@ class _Trainer(object):
             setattr(self, k, getattr(args, k, None))
         self.args = args
         self.steps_per_epoch = getattr(args, "steps_per_epoch", 8)
+        if self.kind in ("srgan", "drcn") and (getattr(args, "ssim_weight", 0.0) or 0.0) > 0:
+            raise ValueError("ssim_weight: %s has no SSIM mix (main.py --ssim_weight)" % self.model_name)
         if not torch.cuda.is_available():
             raise RuntimeError("the MI355X hot path needs a GPU (gpu_mode=False has no CPU fallback; see oracle/)")
         self.rank, self.world, self.local = dpmod.init_from_env()
@@ -86,7 +88,8 @@ class _Trainer(object):
 
     def build_step(self):
         """(flat parameters, optimizer, DataParallel or None, eager step function) of the freshly built model."""
-        return trainers.build(self.kind, self.model, self.lr, use_dp=self.world > 1)
+        return trainers.build(self.kind, self.model, self.lr, use_dp=self.world > 1,
+                              ssim_weight=getattr(self.args, "ssim_weight", 0.0) or 0.0)
 
     def begin_epoch(self, epoch):
         """Top of every epoch, before its first step: the reference's LR decay (and any per-model schedule)."""

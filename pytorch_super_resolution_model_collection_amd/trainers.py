@@ -125,25 +125,45 @@ def loss_segments(model, opt, loss_fn, dp=None, clip=None):
     return [(fwd_bwd, dp), (update, None)]
 
 
-def mse_step(model, opt, dp=None, clip=None):
+def mixed_loss(pixel, ssim_weight=0.0):
+    """The loss a kind trains on: `pixel` itself (the same function object) for weight 0, else the mix of Zhao et al.,
+    (1 - a) * pixel(pred, t) + a * (1 - SSIM(pred, t)), added by srk_axpby (ops.loss_sum); on one GPU each loss kernel
+    folds its weight into its gradient (ops.weighted_term), so the mix adds the SSIM launch, the axpby of the two scalars and the
+    axpby of the two gradients to a step, and no ATen node to a captured one."""
+    a = float(ssim_weight)
+    if not 0.0 <= a <= 1.0:
+        raise ValueError("ssim_weight %r is not in [0, 1]" % (ssim_weight,))
+    if a == 0.0:
+        return pixel
+
+    def loss(pred, target):
+        p1, p2 = ops.fork(pred)   # the two gradients of pred are added by srk_axpby, not by autograd's ATen add
+        return ops.loss_sum(ops.weighted_term(pixel, 1.0 - a, p1, target), ops.weighted_term(ops.ssim_loss, a, p2, target),
+                            1.0 - a, a)
+    return loss
+
+
+def mse_step(model, opt, dp=None, clip=None, ssim_weight=0.0):
     """srcnn.py:127-131 / fsrcnn.py:153-157 / vdsr.py:143-150 (clip = 0.4)."""
-    return eager_step(loss_segments(model, opt, ops.mse_loss, dp, clip))
+    return eager_step(loss_segments(model, opt, mixed_loss(ops.mse_loss, ssim_weight), dp, clip))
 
 
-def l1_step(model, opt, dp=None):
+def l1_step(model, opt, dp=None, ssim_weight=0.0):
     """edsr.py:151-155"""
-    return eager_step(loss_segments(model, opt, ops.l1_loss, dp))
+    return eager_step(loss_segments(model, opt, mixed_loss(ops.l1_loss, ssim_weight), dp))
 
 
-def lapsrn_step(model, opt, dp=None):
+def lapsrn_step(model, opt, dp=None, ssim_weight=0.0):
     """lapsrn.py:190-199: two Charbonnier losses, two backward calls into the same gradients.  A plain closure without
     segments: it cannot be split at its exchange, so under data parallelism it is never captured."""
+    loss_fn = mixed_loss(ops.charbonnier_loss, ssim_weight)   # the same mix at both levels
+
     def step(inp, target2x, target4x):
         opt.zero_grad()
         hr2, hr4 = model(inp)
         with _seeded(dp):
-            l1 = ops.charbonnier_loss(hr2, target2x)
-            l2 = ops.charbonnier_loss(hr4, target4x)
+            l1 = loss_fn(hr2, target2x)
+            l2 = loss_fn(hr4, target4x)
         _backward([l1, l2], dp)
         if dp is not None:
             dp.exchange()
@@ -458,9 +478,10 @@ class GraphedStep(GraphedSegments):
     seg = property(lambda self: self)   # (the split capture used to be a member of this name: `step.seg.plan` still reads)
 
 
-def build(kind, model, lr, dp_group=None, use_dp=False):
+def build(kind, model, lr, dp_group=None, use_dp=False, ssim_weight=0.0):
     """(flat, optimizer, dp, step) for one of 'srcnn' | 'fsrcnn' | 'vdsr' | 'edsr' | 'lapsrn' | 'espcn': the one place that
-    names the loss and the clip a kind trains with."""
+    names the loss and the clip a kind trains with.  ssim_weight a in (0, 1]: (1 - a) * that loss + a * (1 - SSIM)
+    (mixed_loss); 0: the step as it is without the argument."""
     from .dp import DataParallel
     flat = FlatParams(model)
     opt = make_optimizer(kind, flat, lr)
@@ -468,13 +489,13 @@ def build(kind, model, lr, dp_group=None, use_dp=False):
     if dp is not None:
         dp.broadcast_params()
     if kind == "edsr":
-        step = l1_step(model, opt, dp)
+        step = l1_step(model, opt, dp, ssim_weight=ssim_weight)
     elif kind == "lapsrn":
-        step = lapsrn_step(model, opt, dp)
+        step = lapsrn_step(model, opt, dp, ssim_weight=ssim_weight)
     elif kind == "vdsr":
-        step = mse_step(model, opt, dp, clip=0.4)
+        step = mse_step(model, opt, dp, clip=0.4, ssim_weight=ssim_weight)
     else:
-        step = mse_step(model, opt, dp)
+        step = mse_step(model, opt, dp, ssim_weight=ssim_weight)
     return flat, opt, dp, step
 
 

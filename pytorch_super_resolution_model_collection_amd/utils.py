@@ -60,6 +60,15 @@ def SSIM(pred, gt, shave=0, domain='float'):
     return ops.ssim(pred.float(), gt.to(pred.device).float(), shave, domain)[0]
 
 
+class SSIMLoss(torch.nn.Module):
+    """1 - SSIM(pred, target) as a training loss (ops.ssim_loss: the prediction unclamped, float domain, loss and gradient
+    from one kernel launch); [N,C,H,W] CUDA tensors with planes of at least 11 x 11."""
+
+    def forward(self, pred, target):
+        from . import ops
+        return ops.ssim_loss(pred, target.to(pred.device))
+
+
 def save_img_name(img_num, save_dir='', is_training=False):
     """utils.py:126-130: the file a result image goes to."""
     return save_dir + ('/SR_result_epoch_{:d}' if is_training else '/SR_result_{:d}').format(img_num) + '.png'
