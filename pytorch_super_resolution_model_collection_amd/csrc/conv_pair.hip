@@ -25,7 +25,9 @@
 // power-of-two scale above the true maximum gives the same planes unless the residual plane underflows, i.e. it only
 // raises the absolute error floor (ops.declare_absmax).
 // Second layer: the ring kernel's tap loop (conv_bfr.hip) with the filter in LDS; a wave owns 4 rows x 16 columns x 16
-// channels of the tile.  Accumulation order per output: chunk, kernel column, kernel row.
+// channels of the tile.  Accumulation order per output: chunk, kernel column, kernel row.  The second layer's
+// MFMA stream is written out with its LDS reads ahead of use: pixel fragments two steps ahead, across the chunk boundary
+// too, filter fragments replaced behind their last use.
 //
 // Ring: stage (run entry i, chunk c) = 2 i + c holds halo rows 2 .. 7 in slot (2 i + c) % 3; per slot full / free counters
 // in LDS.  A wave waits for free >= 4 k before writing use k of a slot and for full >= 2 (k + 1) (the two waves of the
@@ -541,40 +543,90 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
       f32x4 acc[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) acc[r] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      // The tap loop as a written-out stream (conv_bfr.hip's): 18 steps (kernel column v, halo row R) per chunk, a step's
+      // MFMA groups in ascending kernel row.  Behind a step's first group: the pixel fragment of step s + 2 -- from step 16
+      // of chunk 0 on that of chunk 1, whose counter is peeked at step 8 and checked at step 16, behind the hand-back of
+      // chunk 0's slot at step 15 (a wave never holds a slot while it waits for another) -- and one kernel row of filter
+      // fragments: row 0 follows at R = 4 and row 1 at R = 5 (next column, or chunk 1's first), row 2 at R = 0 of the column
+      // that needs it at R = 2.  Sums and their order are the plain loop's.
+      uint4 fa[3][2], fb[3][2];
+      const uint4 *spa[2], *shb[2], *spc[2];
+      unsigned sslot[2], suse[2];
 #pragma unroll
       for (int cc = 0; cc < 2; ++cc) {
-        const unsigned st = 2u * (unsigned)i + cc, slot = st % PR_NSLOT, use = st / PR_NSLOT;
-        lds_cnt_wait(cnt + slot, 2u * (use + 1), dead);
-        const uint4* hb = ring + slot * PR_HBUF + lane_b;
+        const unsigned st = 2u * (unsigned)i + cc;
+        sslot[cc] = st % PR_NSLOT;
+        suse[cc] = st / PR_NSLOT;
+        shb[cc] = ring + sslot[cc] * PR_HBUF + lane_b;
         // the wave's rows out of kept rows: R = 0, 1 (rh == 0: rows 0 .. 1), R = 4, 5 (rh == 1: rows 8 .. 9)
         const uint4* kr = keep + (rh == 0 ? tb : kb) * PR_KBUF + cc * 4 * PR_KP + lane_k - (rh == 0 ? 0 : 4 * PR_HW);
-        const uint4* pa = rh == 0 ? kr : hb;
-        const uint4* pc = rh == 0 ? hb : kr;
-#pragma unroll
-        for (int v = 0; v < 3; ++v) {
-          uint4 fa[3][2];
-#pragma unroll
-          for (int u = 0; u < 3; ++u) {
-            fa[u][0] = wl2[((u * 3 + v) * 2 + cc) * 256 + lane_a];
-            fa[u][1] = wl2[((u * 3 + v) * 2 + cc) * 256 + 128 + lane_a];
-          }
-#pragma unroll
-          for (int R = 0; R < 6; ++R) {
-            const uint4* px = R < 2 ? pa : (R < 4 ? hb : pc);
-            const uint4 xh = px[R * PR_HW + v], xm = px[R * PR_HW + v + PR_PLANE];
-#pragma unroll
-            for (int u = 0; u < 3; ++u) {
-              const int r = R - u;
-              if (r >= 0 && r < 4) {
-                acc[r] = mfma16h(fa[u][0], xm, acc[r]);
-                acc[r] = mfma16h(fa[u][1], xh, acc[r]);
-                acc[r] = mfma16h(fa[u][0], xh, acc[r]);
+        spa[cc] = rh == 0 ? kr : shb[cc];
+        spc[cc] = rh == 0 ? shb[cc] : kr;
+      }
+      auto ldA = [&](auto uc, auto vc, auto ccc) {
+        constexpr int u = decltype(uc)::value, v = decltype(vc)::value, cc = decltype(ccc)::value;
+        fa[u][0] = wl2[((u * 3 + v) * 2 + cc) * 256 + lane_a];
+        fa[u][1] = wl2[((u * 3 + v) * 2 + cc) * 256 + 128 + lane_a];
+      };
+      auto ldB = [&](auto ccc, auto sc) {
+        constexpr int cc = decltype(ccc)::value, s = decltype(sc)::value, v = s / 6, R = s - 6 * v;
+        const uint4* px = R < 2 ? spa[cc] : (R < 4 ? shb[cc] : spc[cc]);
+        fb[s % 3][0] = px[R * PR_HW + v];
+        fb[s % 3][1] = px[R * PR_HW + v + PR_PLANE];
+      };
+      using I0 = std::integral_constant<int, 0>;
+      using I1 = std::integral_constant<int, 1>;
+      using I2 = std::integral_constant<int, 2>;
+      lds_cnt_wait(cnt + sslot[0], 2u * (suse[0] + 1), dead);
+      ldA(I0{}, I0{}, I0{});
+      ldB(I0{}, I0{});
+      ldA(I1{}, I0{}, I0{});
+      ldB(I0{}, I1{});
+      srk_static_for<0, 2>([&](auto ccc) {
+        constexpr int cc = decltype(ccc)::value;
+        unsigned peek_v = 0;
+        srk_static_for<0, 18>([&](auto sc) {
+          constexpr int s = decltype(sc)::value, v = s / 6, R = s - 6 * v;
+          constexpr int u_lo = R - 3 > 0 ? R - 3 : 0, u_hi = R < 2 ? R : 2;
+          srk_static_for<u_lo, u_hi + 1>([&](auto uc) {
+            constexpr int u = decltype(uc)::value, r = R - u;
+            acc[r] = mfma16h(fa[u][0], fb[s % 3][1], acc[r]);
+            acc[r] = mfma16h(fa[u][1], fb[s % 3][0], acc[r]);
+            acc[r] = mfma16h(fa[u][0], fb[s % 3][0], acc[r]);
+            __builtin_amdgcn_sched_barrier(0);
+            if constexpr (u == u_lo) {
+              if constexpr (cc == 0 && s == 16) {
+                if (!dead) {
+                  unsigned seen = (unsigned)__builtin_amdgcn_readfirstlane((int)peek_v), spins = 0;
+                  while ((int)(seen - 2u * (suse[1] + 1)) < 0) {
+                    __builtin_amdgcn_s_sleep(1);
+                    seen = lds_cnt_peek(cnt + sslot[1]);
+                    if (++spins > kLdsCntSpinCap) {
+                      dead = true;
+                      break;
+                    }
+                  }
+                }
+                asm volatile("" ::: "memory");
+              }
+              if constexpr (s + 2 < 18) ldB(ccc, std::integral_constant<int, s + 2>{});
+              else if constexpr (cc == 0) ldB(I1{}, std::integral_constant<int, s + 2 - 18>{});
+              if constexpr (cc == 0 && s == 8)
+                peek_v = __hip_atomic_load(cnt + sslot[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              if constexpr (s == 15) lds_cnt_signal(cnt + 3 + sslot[cc]);   // behind the slot's last read (step 17's)
+              __builtin_amdgcn_sched_barrier(0);
+              if constexpr (R == 0) {
+                ldA(I2{}, std::integral_constant<int, v>{}, ccc);
+                __builtin_amdgcn_sched_barrier(0);
+              } else if constexpr (R >= 4) {
+                if constexpr (v < 2) ldA(std::integral_constant<int, R - 4>{}, std::integral_constant<int, v + 1>{}, ccc);
+                else if constexpr (cc == 0) ldA(std::integral_constant<int, R - 4>{}, I0{}, I1{});
+                __builtin_amdgcn_sched_barrier(0);
               }
             }
-          }
-        }
-        lds_cnt_signal(cnt + 3 + slot);
-      }
+          });
+        });
+      });
       lds_cnt_signal(cnt + 11 + tb, fresh ? 2u : 1u);
       lds_cnt_signal(cnt + 11 + kb, hand ? 1u : 2u);
       // -- epilogue: bias, ReLU, NHWC stores of the pixels inside the output, running maximum -----------------------------
