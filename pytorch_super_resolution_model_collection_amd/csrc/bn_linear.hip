@@ -1,9 +1,21 @@
 // BatchNorm2d (train / eval) and Linear — the SRGAN-only pieces of the hot path
 // (base_networks.py:7,46,117,161; srgan.py:49-81).  NHWC: a tensor is [rows][C] with
 // rows = N*H*W, so per-channel statistics are column sums with lanes = channels (coalesced rows).
+//
+// BatchNorm, forward and backward alike, is column sums over row splits -> reduce over the splits -> apply, in three shapes
+// that are all live:
+//   separate launches     k_bn_colsum<MODE> / k_bn_colsum_act -> k_bn_reduce | k_bn_reduce_fused | k_bn_reduce16 |
+//                         k_bn_reduce_act [-> k_bn_finalize | k_bn_param_grads] -> k_bn_apply* / k_bn_bwd_apply*
+//                         (SyncBN, eval mode, C % 16 != 0, C > 512, unaligned views, InstanceNorm)
+//   finalize-in-apply     the same column sums -> k_bn_fin_apply_act / k_bn_fin_bwd_apply_act
+// What they share is written once: bn_finish_stats (forward finalize), bn_add_param_grads (dbeta / dgamma / dprelu),
+// bn_dx (the double evaluation of dx), bn_z (the affine the activation mask is taken from), bn_slab_totals (the 16-channel
+// slab reduction); on the host bn_launch_colsum / _colsum_bwd / _reduce and bn_act_args.  The plain forward kernels
+// k_bn_apply / k_bn_apply4 round their affine differently from bn_z and stay what they are.
 #include "srk_common.h"
 #include "bf16_frag.h"
 #include <stdlib.h>
+#include <initializer_list>
 
 namespace srk {
 
@@ -95,9 +107,52 @@ __global__ __launch_bounds__(256) void k_bn_reduce(const double* __restrict__ pa
   if (w == 0 && i < C2) stats[i] = (sm[0][lane] + sm[1][lane]) + (sm[2][lane] + sm[3][lane]);
 }
 
+// What the kernels behind a reduction do with a channel's totals -- each written once.
+// Forward: mean / clamped biased variance / rstd from (s0, s1) = (sum x, sum x^2) over `count` rows, in double, rounded once.
+// `write`: also store them, update the running statistics (unbiased variance; the running mean moves by the ROUNDED mean)
+// and count the batch (nn.BatchNorm's num_batches_tracked, without a launch of its own).
+struct BnMoments {
+  float mean, rstd;
+};
+__device__ __forceinline__ BnMoments bn_finish_stats(double s0, double s1, double count, float eps, float momentum, int c,
+                                                     bool write, float* __restrict__ save_mean, float* __restrict__ save_rstd,
+                                                     float* __restrict__ rm, float* __restrict__ rv, long long* __restrict__ nbt) {
+  const double mean = s0 / count;
+  double var = s1 / count - mean * mean;
+  if (var < 0.0) var = 0.0;
+  const BnMoments m{(float)mean, (float)(1.0 / sqrt(var + (double)eps))};
+  if (write) {
+    if (c == 0 && nbt) *nbt += 1;
+    save_mean[c] = m.mean;
+    save_rstd[c] = m.rstd;
+    if (rm) rm[c] = (1.f - momentum) * rm[c] + momentum * m.mean;
+    if (rv) {
+      const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
+      rv[c] = (1.f - momentum) * rv[c] + momentum * (float)unbiased;
+    }
+  }
+  return m;
+}
+
+// Backward: dbeta += sum dz, dgamma += sum dz * xhat, and with one PReLU slope per channel dprelu += sum_{z<=0} dy * z
+__device__ __forceinline__ void bn_add_param_grads(int c, double s0, double s1, float* __restrict__ dgamma,
+                                                   float* __restrict__ dbeta, float* __restrict__ dprelu_c = nullptr,
+                                                   double s2 = 0.0) {
+  if (dbeta) dbeta[c] += (float)s0;
+  if (dgamma) dgamma[c] += (float)s1;
+  if (dprelu_c) dprelu_c[c] += (float)s2;
+}
+
+// dx = gamma * rstd * (dz - m1 - m2 * xhat), m1 = mean(dz), m2 = mean(dz * xhat).  The difference cancels heavily when this
+// BatchNorm's output feeds another one: evaluated in double from the fp32 inputs and the double sums, rounded once.
+__device__ __forceinline__ float bn_dx(float dz, float x, float mu, float rs, float g, double m1, double m2) {
+  const double xhat = ((double)x - (double)mu) * (double)rs;
+  return (float)((double)g * (double)rs * ((double)dz - m1 - xhat * m2));
+}
+
 // k_bn_reduce fused with what consumes the reduced sums (one launch less per BatchNorm call and direction):
-//   MODE 0 (forward):  + k_bn_finalize  (mean / rstd / running statistics / num_batches_tracked)
-//   MODE 1 (backward): + k_bn_param_grads (dbeta += sum dy, dgamma += sum dy * xhat)
+//   MODE 0 (forward):  + bn_finish_stats  (mean / rstd / running statistics / num_batches_tracked)
+//   MODE 1 (backward): + bn_add_param_grads (o0 = dgamma, o1 = dbeta)
 // 64 channels per block, lane = channel; the NW waves take every NW-th split, combined through LDS in a fixed order.
 // (NW = 16 for more than 64 splits: with 4 waves the 512 splits of a large activation were 8 dependent L2 round trips
 // of ONE block -- the kernel is a latency chain, 8.8 us average on the SRGAN step.)
@@ -146,21 +201,74 @@ __global__ __launch_bounds__(64 * NW) void k_bn_reduce_fused(const double* __res
   }
   stats[c] = s0;
   stats[C + c] = s1;
-  if (MODE == 0) {
-    if (c == 0 && nbt) *nbt += 1;
-    const double mean = s0 / count;
-    double var = s1 / count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    o0[c] = (float)mean;
-    o1[c] = (float)(1.0 / sqrt(var + (double)eps));
-    if (rm) rm[c] = (1.f - momentum) * rm[c] + momentum * (float)mean;
-    if (rv) {
-      const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-      rv[c] = (1.f - momentum) * rv[c] + momentum * (float)unbiased;
+  if (MODE == 0)
+    bn_finish_stats(s0, s1, count, eps, momentum, c, true, o0, o1, rm, rv, nbt);
+  else
+    bn_add_param_grads(c, s0, s1, o0, o1);
+}
+
+// The reduction over the splits for a slab of 16 channels, by a block of 1024 threads (k_bn_reduce16 and the
+// finalize-in-apply kernels below: ONE summation order, so their statistics agree bit for bit).
+constexpr int BNF_CS = 16;      // channels per slab
+constexpr int BNF_THR = 1024;   // 64 phases x 16 channels in the reduction, 256 rows x 4 float4 in the apply loop
+
+// totals of NQ sums for channel c (the thread's t & 15) over partial[k * kstride + q * qstride + c], k < nsplit; every thread
+// of the block returns the totals of ITS channel: 64 phases with 8 splits each in flight and two accumulators, then the
+// phases in two steps of 8 through LDS.
+template <int NQ>
+__device__ __forceinline__ void bn_slab_totals(const double* __restrict__ partial, int nsplit, size_t kstride, size_t qstride,
+                                               int c, double (*sm)[64][BNF_CS], double (&tot)[NQ]) {
+  const int t = threadIdx.x, cl = t & 15, ph = t >> 4;
+  double a0[NQ], a1[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) a0[q] = a1[q] = 0.0;
+  constexpr int U = 8;
+  for (int kb = ph; kb < nsplit; kb += 64 * U) {
+    double v[U][NQ];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int k = kb + 64 * u, kc = k < nsplit ? k : nsplit - 1;   // (clamped unconditional loads + select: see k_bn_colsum)
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) v[u][q] = partial[(size_t)kc * kstride + q * qstride + c];
     }
-  } else {
-    if (o1) o1[c] += (float)s0;  // dbeta
-    if (o0) o0[c] += (float)s1;  // dgamma
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (kb + 64 * u >= nsplit) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) v[u][q] = 0.0;
+      }
+#pragma unroll
+    for (int u = 0; u < U; u += 2)
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) {
+        a0[q] += v[u][q];
+        a1[q] += v[u + 1][q];
+      }
+  }
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) sm[q][ph][cl] = a0[q] + a1[q];
+  __syncthreads();
+  double s[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) s[q] = 0.0;
+  if (ph < 8) {   // phases 8 ph .. 8 ph + 7
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+#pragma unroll
+      for (int q = 0; q < NQ; ++q) s[q] += sm[q][ph * 8 + j][cl];
+  }
+  __syncthreads();
+  if (ph < 8) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) sm[q][ph][cl] = s[q];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    double r = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r += sm[q][j][cl];
+    tot[q] = r;
   }
 }
 
@@ -168,98 +276,33 @@ __global__ __launch_bounds__(64 * NW) void k_bn_reduce_fused(const double* __res
 // of the SRGAN generator is FOUR blocks reading 128 KB of partial sums each -- every split of a thread in flight at once for
 // up to 512 splits -- instead of ONE block reading 512 KB (k_bn_reduce_fused<., 16>: 7.3 us average, ~110 launches per
 // adversarial step; the kernel is the L2 read time of a single CU).  Double sums: the order of the adds is immaterial at
-// the fp32 precision of everything downstream.
+// the fp32 precision of everything downstream.  The lanes past C of the last block (C % 16 != 0) sum channel C - 1 again
+// and write nothing.
 template <int MODE>
-__global__ __launch_bounds__(1024) void k_bn_reduce16(const double* __restrict__ partial, double* __restrict__ stats, int nsplit,
-                                                      int C, double count, float* __restrict__ o0, float* __restrict__ o1,
-                                                      float* __restrict__ rm, float* __restrict__ rv, float momentum, float eps,
-                                                      long long* __restrict__ nbt) {
-  __shared__ double sm[2][64][16];
-  const int t = threadIdx.x, cl = t & 15, ph = t >> 4;
-  const int c = blockIdx.x * 16 + cl;
-  const int cc = c < C ? c : C - 1;
-  double a0 = 0.0, a1 = 0.0, b0 = 0.0, b1 = 0.0;
-  constexpr int U = 8;
-  for (int kb = ph; kb < nsplit; kb += 64 * U) {
-    double va[U], vb[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int k = kb + 64 * u, kc = k < nsplit ? k : nsplit - 1;   // (clamped unconditional loads + select: see k_bn_colsum)
-      va[u] = partial[(size_t)kc * 2 * C + cc];
-      vb[u] = partial[(size_t)kc * 2 * C + C + cc];
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      if (kb + 64 * u >= nsplit) va[u] = vb[u] = 0.0;
-#pragma unroll
-    for (int u = 0; u < U; u += 2) {
-      a0 += va[u];
-      b0 += vb[u];
-      a1 += va[u + 1];
-      b1 += vb[u + 1];
-    }
-  }
-  sm[0][ph][cl] = a0 + a1;
-  sm[1][ph][cl] = b0 + b1;
-  __syncthreads();
-  double s0 = 0.0, s1 = 0.0;
-  if (ph < 8) {   // phases 8 ph .. 8 ph + 7
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      s0 += sm[0][ph * 8 + j][cl];
-      s1 += sm[1][ph * 8 + j][cl];
-    }
-  }
-  __syncthreads();
-  if (ph < 8) {
-    sm[0][ph][cl] = s0;
-    sm[1][ph][cl] = s1;
-  }
-  __syncthreads();
-  if (ph != 0 || c >= C) return;
-  s0 = s1 = 0.0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    s0 += sm[0][j][cl];
-    s1 += sm[1][j][cl];
-  }
-  stats[c] = s0;
-  stats[C + c] = s1;
-  if (MODE == 0) {
-    if (c == 0 && nbt) *nbt += 1;
-    const double mean = s0 / count;
-    double var = s1 / count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    o0[c] = (float)mean;
-    o1[c] = (float)(1.0 / sqrt(var + (double)eps));
-    if (rm) rm[c] = (1.f - momentum) * rm[c] + momentum * (float)mean;
-    if (rv) {
-      const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-      rv[c] = (1.f - momentum) * rv[c] + momentum * (float)unbiased;
-    }
-  } else {
-    if (o1) o1[c] += (float)s0;  // dbeta
-    if (o0) o0[c] += (float)s1;  // dgamma
-  }
+__global__ __launch_bounds__(BNF_THR) void k_bn_reduce16(const double* __restrict__ partial, double* __restrict__ stats, int nsplit,
+                                                         int C, double count, float* __restrict__ o0, float* __restrict__ o1,
+                                                         float* __restrict__ rm, float* __restrict__ rv, float momentum, float eps,
+                                                         long long* __restrict__ nbt) {
+  __shared__ double sm[2][64][BNF_CS];
+  const int c = blockIdx.x * BNF_CS + (threadIdx.x & 15);
+  double tot[2];
+  bn_slab_totals<2>(partial, nsplit, (size_t)2 * C, (size_t)C, c < C ? c : C - 1, sm, tot);
+  if ((threadIdx.x >> 4) != 0 || c >= C) return;
+  stats[c] = tot[0];
+  stats[C + c] = tot[1];
+  if (MODE == 0)
+    bn_finish_stats(tot[0], tot[1], count, eps, momentum, c, true, o0, o1, rm, rv, nbt);
+  else
+    bn_add_param_grads(c, tot[0], tot[1], o0, o1);
 }
 
+// the finalize alone, behind a reduction that something else had to see first (SyncBN's all-reduce, InstanceNorm)
 __global__ __launch_bounds__(256) void k_bn_finalize(const double* __restrict__ stats, double count,
                                                      float* __restrict__ save_mean, float* __restrict__ save_rstd,
                                                      float* __restrict__ rm, float* __restrict__ rv, float momentum,
                                                      float eps, int C, long long* __restrict__ nbt) {
   const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c == 0 && nbt) *nbt += 1;  // nn.BatchNorm's num_batches_tracked bookkeeping, without a launch of its own
-  if (c >= C) return;
-  const double mean = stats[c] / count;
-  double var = stats[C + c] / count - mean * mean;
-  if (var < 0.0) var = 0.0;
-  save_mean[c] = (float)mean;
-  save_rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-  if (rm) rm[c] = (1.f - momentum) * rm[c] + momentum * (float)mean;
-  if (rv) {
-    const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-    rv[c] = (1.f - momentum) * rv[c] + momentum * (float)unbiased;
-  }
+  if (c < C) bn_finish_stats(stats[c], stats[C + c], count, eps, momentum, c, true, save_mean, save_rstd, rm, rv, nbt);
 }
 
 __global__ __launch_bounds__(256) void k_bn_eval_params(const float* __restrict__ rm, const float* __restrict__ rv,
@@ -290,14 +333,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(const float* __restrict__ 
                                                       float* __restrict__ dx, size_t total, int C) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const int c = (int)(i % C);
-    const float rs = rstd[c];
-    const float g = gamma ? gamma[c] : 1.f;
-    // dy - mean(dy) - xhat*mean(dy*xhat) cancels heavily when this BN's output feeds another BN: evaluate the
-    // difference in double from the fp32 inputs and the double sums, round once
-    const double xhat = ((double)x[i] - (double)mean[c]) * (double)rs;
-    const double m1 = dstats[c] / count;
-    const double m2 = dstats[C + c] / count;
-    dx[i] = (float)((double)g * (double)rs * ((double)dy[i] - m1 - xhat * m2));
+    dx[i] = bn_dx(dy[i], x[i], mean[c], rstd[c], gamma ? gamma[c] : 1.f, dstats[c] / count, dstats[C + c] / count);
   }
 }
 
@@ -323,29 +359,6 @@ __global__ __launch_bounds__(256) void k_bn_apply4(const float* __restrict__ x, 
     if (y_amax) amax = abs_max4(amax, v);
   }
   if (y_amax) amax_commit_block(y_amax, amax, blockIdx.x, sm_amax, 4, peeked);   // the running maximum the next conv scales by
-}
-
-__global__ __launch_bounds__(256) void k_bn_bwd_apply4(const float* __restrict__ dy, const float* __restrict__ x,
-                                                       const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                       const float* __restrict__ gamma,
-                                                       const double* __restrict__ dstats, double count,
-                                                       float* __restrict__ dx, size_t total4, int C) {
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (size_t)gridDim.x * 256) {
-    const int c = (int)((i * 4) % (size_t)C);
-    const bn_f4 dv = *reinterpret_cast<const bn_f4*>(dy + i * 4), xv = *reinterpret_cast<const bn_f4*>(x + i * 4);
-    const bn_f4 mu = *reinterpret_cast<const bn_f4*>(mean + c), rs = *reinterpret_cast<const bn_f4*>(rstd + c);
-    bn_f4 g = {1.f, 1.f, 1.f, 1.f};
-    if (gamma) g = *reinterpret_cast<const bn_f4*>(gamma + c);
-    bn_f4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {   // (same evaluation as k_bn_bwd_apply)
-      const double xhat = ((double)xv[e] - (double)mu[e]) * (double)rs[e];
-      const double m1 = dstats[c + e] / count;
-      const double m2 = dstats[C + c + e] / count;
-      o[e] = (float)((double)g[e] * (double)rs[e] * ((double)dv[e] - m1 - xhat * m2));
-    }
-    *reinterpret_cast<bn_f4*>(dx + i * 4) = o;
-  }
 }
 
 // ---- BatchNorm with the activation that follows it (and a residual add) folded in ------------------------------
@@ -459,7 +472,7 @@ __global__ __launch_bounds__(256) void k_bn_colsum_act(const float* __restrict__
   }
 }
 
-// reduce of the above + dbeta += sum dz, dgamma += sum dz * xhat, dprelu += sum_{z<=0} dy * z; stats[2C] as usual
+// reduce of the above + bn_add_param_grads; stats[2C] as usual
 template <int NW>   // waves per block (16 for many splits: see k_bn_reduce_fused)
 __global__ __launch_bounds__(64 * NW) void k_bn_reduce_act(const double* __restrict__ partial, double* __restrict__ stats,
                                                           int nsplit, int C, float* __restrict__ dgamma,
@@ -500,9 +513,7 @@ __global__ __launch_bounds__(64 * NW) void k_bn_reduce_act(const double* __restr
       for (int g = 0; g < NW; g += 4) s[q] += (sm[q][g][lane] + sm[q][g + 1][lane]) + (sm[q][g + 2][lane] + sm[q][g + 3][lane]);
     stats[c] = s[0];
     stats[C + c] = s[1];
-    if (dbeta) dbeta[c] += (float)s[0];
-    if (dgamma) dgamma[c] += (float)s[1];
-    if (dprelu && prelu_n > 1) dprelu[c] += (float)s[2];
+    bn_add_param_grads(c, s[0], s[1], dgamma, dbeta, prelu_n > 1 ? dprelu : nullptr, s[2]);
   }
   if (dprelu && prelu_n == 1) {  // one slope: the block's 64 channels summed in lane order, one atomic per block
     psum[lane] = c < C ? (float)s[2] : 0.f;
@@ -532,26 +543,23 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply_act4(const float* __restri
     for (int e = 0; e < 4; ++e) {
       const float z = bn_z(xv[e], mu[e], rs[e], g[e], b[e]);
       const float dz = (A.act == SRK_ACT_NONE || z > 0.f) ? dv[e] : dv[e] * bn_act_slope(A, c + e);
-      const double xhat = ((double)xv[e] - (double)mu[e]) * (double)rs[e];
-      const double m1 = dstats[c + e] / count;
-      const double m2 = dstats[C + c + e] / count;
-      o[e] = (float)((double)g[e] * (double)rs[e] * ((double)dz - m1 - xhat * m2));
+      o[e] = bn_dx(dz, xv[e], mu[e], rs[e], g[e], dstats[c + e] / count, dstats[C + c + e] / count);
     }
     *reinterpret_cast<bn_f4*>(dx + i * 4) = o;
   }
 }
 
-static bool bn_vec4(int C, const void* a, const void* b, const void* c, const void* d, const void* e, const void* f) {
-  if (C & 3) return false;
-  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e | (uintptr_t)f) & 15) == 0;
+// may the float4 kernels run?  (C % 4 == 0 and every tensor -- null ones aside -- 16-byte aligned)
+static bool bn_vec4(int C, std::initializer_list<const void*> tensors) {
+  uintptr_t bits = (uintptr_t)(C & 3);
+  for (const void* t : tensors) bits |= (uintptr_t)t & 15;
+  return bits == 0;
 }
 
 __global__ __launch_bounds__(256) void k_bn_param_grads(const double* __restrict__ dstats, float* __restrict__ dgamma,
                                                         float* __restrict__ dbeta, int C) {
   const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= C) return;
-  if (dbeta) dbeta[c] += (float)dstats[c];
-  if (dgamma) dgamma[c] += (float)dstats[C + c];
+  if (c < C) bn_add_param_grads(c, dstats[c], dstats[C + c], dgamma, dbeta);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -560,73 +568,11 @@ __global__ __launch_bounds__(256) void k_bn_param_grads(const double* __restrict
 // each at the ~5 us per-node floor of a replayed hipGraph on the 4 MB tensors of the SRGAN step (458 of its 846 nodes).  An
 // in-kernel hand-off does not beat that floor -- but the reduce needs no hand-off at all if every block of the
 // apply kernel sums the partials of ITS OWN channels again: blocks own a slab of 16 channels x a range of rows, start with
-// k_bn_reduce16's summation (64 phases x 16 channels, the same order: forward statistics bit-equal to the two-launch path)
+// k_bn_reduce16's summation (bn_slab_totals, shared with it: forward statistics bit-equal to the two-launch path)
 // over the slab's [nsplit][16] partials -- 32 - 96 KB from L2 per block, no cross-block dependency -- and go straight on to
 // their rows.  The first row-range block of a slab also writes what the reduce kernel wrote (mean / rstd / running
 // statistics / the [2C] sums; dgamma / dbeta / dprelu).  One launch less per BatchNorm and direction.
 // ---------------------------------------------------------------------------------------------------------------------
-constexpr int BNF_CS = 16;      // channels per slab
-constexpr int BNF_THR = 1024;   // 64 phases x 16 channels in the reduction, 256 rows x 4 float4 in the apply loop
-
-// totals of NQ sums for channel c (the thread's t & 15) over partial[k * kstride + q * qstride + c], k < nsplit; every thread
-// of the block returns the totals of ITS channel.  Order of k_bn_reduce16.
-template <int NQ>
-__device__ __forceinline__ void bn_slab_totals(const double* __restrict__ partial, int nsplit, size_t kstride, size_t qstride,
-                                               int c, double (*sm)[64][BNF_CS], double (&tot)[NQ]) {
-  const int t = threadIdx.x, cl = t & 15, ph = t >> 4;
-  double a0[NQ], a1[NQ];
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) a0[q] = a1[q] = 0.0;
-  constexpr int U = 8;
-  for (int kb = ph; kb < nsplit; kb += 64 * U) {
-    double v[U][NQ];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int k = kb + 64 * u, kc = k < nsplit ? k : nsplit - 1;   // (clamped unconditional loads + select: see k_bn_colsum)
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) v[u][q] = partial[(size_t)kc * kstride + q * qstride + c];
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      if (kb + 64 * u >= nsplit) {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) v[u][q] = 0.0;
-      }
-#pragma unroll
-    for (int u = 0; u < U; u += 2)
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) {
-        a0[q] += v[u][q];
-        a1[q] += v[u + 1][q];
-      }
-  }
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) sm[q][ph][cl] = a0[q] + a1[q];
-  __syncthreads();
-  double s[NQ];
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) s[q] = 0.0;
-  if (ph < 8) {   // phases 8 ph .. 8 ph + 7
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-#pragma unroll
-      for (int q = 0; q < NQ; ++q) s[q] += sm[q][ph * 8 + j][cl];
-  }
-  __syncthreads();
-  if (ph < 8) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) sm[q][ph][cl] = s[q];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    double r = 0.0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r += sm[q][j][cl];
-    tot[q] = r;
-  }
-}
-
 // block -> (slab, row range): the slabs of ONE row range sit on consecutive blocks of one XCD (hardware deals block ids
 // round-robin over the 8 XCDs): a 128-byte line of the tensor holds two slabs' 64 bytes, and with slab = blockIdx.x the two
 // readers of a line were on different XCDs -- every line fetched into two L2s
@@ -667,28 +613,17 @@ __global__ __launch_bounds__(BNF_THR) void k_bn_fin_apply_act(const double* __re
   if (residual) res_first = *reinterpret_cast<const bn_f4*>(residual + off_first);
   double tot[2];
   bn_slab_totals<2>(partial, nsplit, (size_t)2 * C, (size_t)C, c, sm, tot);
-  if (ph == 0) {   // (the arithmetic of k_bn_reduce16<0>)
-    const double mean = tot[0] / count;
-    double var = tot[1] / count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float mf = (float)mean, rf = (float)(1.0 / sqrt(var + (double)eps));
-    prm[0][cl] = mf;
-    prm[1][cl] = rf;
-    prm[2][cl] = A.gamma ? A.gamma[c] : 1.f;
-    prm[3][cl] = A.beta ? A.beta[c] : 0.f;
-    prm[4][cl] = A.act == SRK_ACT_NONE ? 1.f : bn_act_slope(A, c);
+  if (ph == 0) {   // every block needs the slab's mean / rstd; the first row range of the slab also writes them
     if (brange == 0) {
       stats[c] = tot[0];
       stats[C + c] = tot[1];
-      if (c == 0 && nbt) *nbt += 1;
-      save_mean[c] = mf;
-      save_rstd[c] = rf;
-      if (rm) rm[c] = (1.f - momentum) * rm[c] + momentum * mf;
-      if (rv) {
-        const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-        rv[c] = (1.f - momentum) * rv[c] + momentum * (float)unbiased;
-      }
     }
+    const BnMoments m = bn_finish_stats(tot[0], tot[1], count, eps, momentum, c, brange == 0, save_mean, save_rstd, rm, rv, nbt);
+    prm[0][cl] = m.mean;
+    prm[1][cl] = m.rstd;
+    prm[2][cl] = A.gamma ? A.gamma[c] : 1.f;
+    prm[3][cl] = A.beta ? A.beta[c] : 0.f;
+    prm[4][cl] = A.act == SRK_ACT_NONE ? 1.f : bn_act_slope(A, c);
   }
   __syncthreads();
   bn_f4 mu, rs, g, b, sl;
@@ -725,7 +660,7 @@ __global__ __launch_bounds__(BNF_THR) void k_bn_fin_apply_act(const double* __re
 }
 
 // backward: (sum dz, sum dz * xhat[, sum_{z<=0} dy * z]) from [nsplit][NQ][C] partials, parameter gradients, and
-// dx = gamma * rstd * (dz - m1 - xhat * m2) with dz = dy * act'(z), z recomputed from x as in the forward
+// dx = gamma * rstd * (dz - m1 - m2 * xhat) with dz = dy * act'(z), z recomputed from x as in the forward
 // NQ sums are reduced per channel; `pq` = planes per split row of `partial` (3 behind k_bn_colsum_act even where the third --
 // PReLU's slope gradient -- is not wanted: NQ = 2 then reads two of the three)
 template <int NQ>
@@ -764,9 +699,7 @@ __global__ __launch_bounds__(BNF_THR) void k_bn_fin_bwd_apply_act(const double* 
     if (brange == 0) {   // (what k_bn_reduce_act / k_bn_reduce16<1> wrote)
       dstats[c] = tot[0];
       dstats[C + c] = tot[1];
-      if (dbeta) dbeta[c] += (float)tot[0];
-      if (dgamma) dgamma[c] += (float)tot[1];
-      if (NQ == 3 && dprelu && A.prelu_n > 1) dprelu[c] += (float)tot[NQ - 1];
+      bn_add_param_grads(c, tot[0], tot[1], dgamma, dbeta, NQ == 3 && A.prelu_n > 1 ? dprelu : nullptr, tot[NQ - 1]);
     }
   }
   __syncthreads();
@@ -793,8 +726,7 @@ __global__ __launch_bounds__(BNF_THR) void k_bn_fin_bwd_apply_act(const double* 
         const float z = bn_z(xv[e], mu[e], rs[e], g[e], b[e]);
         dz = z > 0.f ? dv[e] : dv[e] * sl[e];
       }
-      const double xhat = ((double)xv[e] - (double)mu[e]) * (double)rs[e];
-      o[e] = (float)((double)g[e] * (double)rs[e] * ((double)dz - m1[e] - xhat * m2[e]));
+      o[e] = bn_dx(dz, xv[e], mu[e], rs[e], g[e], m1[e], m2[e]);
     }
     *reinterpret_cast<bn_f4*>(dx + off) = o;
     const size_t rn = r + BNF_THR / 4;
@@ -844,48 +776,76 @@ static void bnf_grid(size_t rows, int C, dim3& grid, size_t& rows_per_block) {
   grid = dim3((unsigned)(slabs * g));
 }
 
-struct BnFused {   // fused tail of bn_colsum: what the reduce kernel also computes
-  int mode = -1;   // -1: plain reduce
-  double count = 0.0;
-  float *o0 = nullptr, *o1 = nullptr, *rm = nullptr, *rv = nullptr;
-  float momentum = 0.f, eps = 0.f;
-  long long* nbt = nullptr;
-};
+// ---- host side: one launcher per kernel family --------------------------------------------------------------------------
+static int bn_splits(size_t rows, size_t rows_per_split, int cap) {
+  const size_t n = (rows + rows_per_split - 1) / rows_per_split;
+  return n > (size_t)cap ? cap : n < 1 ? 1 : (int)n;
+}
 
-static int bn_colsum(int mode, const float* a, const float* x, const float* mean, const float* rstd, double* out,
-                     size_t rows, int C, void* ws, hipStream_t s, const BnFused& fu = BnFused()) {
-  int splits = (int)((rows + 63) / 64);
-  if (splits > kBnRowSplits) splits = kBnRowSplits;
-  if (splits < 1) splits = 1;
-  const size_t rps = (rows + splits - 1) / splits;
-  dim3 grid(cdiv(C, 64), splits);
-  if (mode == 0)
-    hipLaunchKernelGGL(k_bn_colsum<0>, grid, dim3(256), 0, s, a, x, mean, rstd, (double*)ws, rows, C, rps);
+// grid of the grid-stride apply kernels: one float4 (or four scalars) per thread and pass
+static dim3 bn_flat_grid(size_t total) {
+  const size_t nb = (total + 256 * 4 - 1) / (256 * 4);
+  return dim3((unsigned)(nb > 4096 ? 4096 : nb));
+}
+
+// column sums into partial[splits][2][C]; returns the split count
+template <int MODE>
+static int bn_launch_colsum(const float* a, const float* x, const float* mean, const float* rstd, double* partial, size_t rows,
+                            int C, hipStream_t s) {
+  const int splits = bn_splits(rows, 64, kBnRowSplits);
+  hipLaunchKernelGGL(k_bn_colsum<MODE>, dim3(cdiv(C, 64), splits), dim3(256), 0, s, a, x, mean, rstd, partial, rows, C,
+                     (rows + splits - 1) / splits);
+  return splits;
+}
+
+// backward column sums of dz = dy * act'(z): no activation -> the plain sums, [splits][2][C]; otherwise k_bn_colsum_act's
+// [splits][3][C] (which would mask dy by the sign of z whatever A.act says).  Returns the split count.
+static int bn_launch_colsum_bwd(const BnAct& A, const float* dy, const float* x, const float* mean, const float* rstd,
+                                double* partial, size_t rows, int C, hipStream_t s) {
+  if (A.act == SRK_ACT_NONE) return bn_launch_colsum<1>(dy, x, mean, rstd, partial, rows, C, s);
+  const int splits = bn_splits(rows, 128, kBnRowSplits * 2 / 3);   // three sums per split in the same workspace
+  hipLaunchKernelGGL(k_bn_colsum_act, dim3(cdiv(C, 64), splits), dim3(256), 0, s, dy, x, mean, rstd, A, partial, rows, C,
+                     (rows + splits - 1) / splits);
+  return splits;
+}
+
+// [splits][2][C] partials -> stats[2C] and the tail of MODE (k_bn_reduce_fused): up to 64 splits one 4-wave block per 64
+// channels; above, 16-channel slabs (SRK_BN_RED16 = 0: 16-wave blocks of 64 channels, the tests' reference arm)
+template <int MODE>
+static void bn_launch_reduce(const double* partial, int splits, double* stats, int C, double count, float* o0, float* o1,
+                             float* rm, float* rv, float momentum, float eps, long long* nbt, hipStream_t s) {
+  if (splits > 64 && env_int("SRK_BN_RED16", 1) != 0)
+    hipLaunchKernelGGL((k_bn_reduce16<MODE>), dim3(cdiv(C, BNF_CS)), dim3(BNF_THR), 0, s, partial, stats, splits, C, count, o0,
+                       o1, rm, rv, momentum, eps, nbt);
+  else if (splits > 64)
+    hipLaunchKernelGGL((k_bn_reduce_fused<MODE, 16>), dim3(cdiv(C, 64)), dim3(1024), 0, s, partial, stats, splits, C, count, o0,
+                       o1, rm, rv, momentum, eps, nbt);
   else
-    hipLaunchKernelGGL(k_bn_colsum<1>, grid, dim3(256), 0, s, a, x, mean, rstd, (double*)ws, rows, C, rps);
-  const bool wide = splits > 64;
-  const bool r16 = wide && env_int("SRK_BN_RED16", 1) != 0;
-  if (fu.mode == 0 && r16)
-    hipLaunchKernelGGL((k_bn_reduce16<0>), dim3(cdiv(C, 16)), dim3(1024), 0, s, (const double*)ws, out, splits, C, fu.count,
-                       fu.o0, fu.o1, fu.rm, fu.rv, fu.momentum, fu.eps, fu.nbt);
-  else if (fu.mode == 1 && r16)
-    hipLaunchKernelGGL((k_bn_reduce16<1>), dim3(cdiv(C, 16)), dim3(1024), 0, s, (const double*)ws, out, splits, C, 0.0, fu.o0,
-                       fu.o1, nullptr, nullptr, 0.f, 0.f, nullptr);
-  else if (fu.mode == 0 && wide)
-    hipLaunchKernelGGL((k_bn_reduce_fused<0, 16>), dim3(cdiv(C, 64)), dim3(1024), 0, s, (const double*)ws, out, splits, C,
-                       fu.count, fu.o0, fu.o1, fu.rm, fu.rv, fu.momentum, fu.eps, fu.nbt);
-  else if (fu.mode == 0)
-    hipLaunchKernelGGL((k_bn_reduce_fused<0, 4>), dim3(cdiv(C, 64)), dim3(256), 0, s, (const double*)ws, out, splits, C,
-                       fu.count, fu.o0, fu.o1, fu.rm, fu.rv, fu.momentum, fu.eps, fu.nbt);
-  else if (fu.mode == 1 && wide)
-    hipLaunchKernelGGL((k_bn_reduce_fused<1, 16>), dim3(cdiv(C, 64)), dim3(1024), 0, s, (const double*)ws, out, splits, C, 0.0,
-                       fu.o0, fu.o1, nullptr, nullptr, 0.f, 0.f, nullptr);
-  else if (fu.mode == 1)
-    hipLaunchKernelGGL((k_bn_reduce_fused<1, 4>), dim3(cdiv(C, 64)), dim3(256), 0, s, (const double*)ws, out, splits, C, 0.0,
-                       fu.o0, fu.o1, nullptr, nullptr, 0.f, 0.f, nullptr);
-  else
-    hipLaunchKernelGGL(k_bn_reduce, dim3(cdiv(2 * C, 64)), dim3(256), 0, s, (const double*)ws, out, splits, 2 * C);
-  return check_launch("bn_colsum");
+    hipLaunchKernelGGL((k_bn_reduce_fused<MODE, 4>), dim3(cdiv(C, 64)), dim3(256), 0, s, partial, stats, splits, C, count, o0,
+                       o1, rm, rv, momentum, eps, nbt);
+}
+
+// column sums + the plain reduce: stats[2C] alone (SyncBN all-reduces them, InstanceNorm finalizes per sample)
+template <int MODE>
+static int bn_colsum(const float* a, const float* x, const float* mean, const float* rstd, double* stats, size_t rows, int C,
+                     void* ws, hipStream_t s, const char* who) {
+  const int splits = bn_launch_colsum<MODE>(a, x, mean, rstd, (double*)ws, rows, C, s);
+  hipLaunchKernelGGL(k_bn_reduce, dim3(cdiv(2 * C, 64)), dim3(256), 0, s, (const double*)ws, stats, splits, 2 * C);
+  return check_launch(who);
+}
+
+// the activation arguments of an _act entry point, checked, as the kernels' BnAct; `float4_tensors`: what the entry point's
+// float4 kernel reads and writes besides gamma and beta (none: its kernels are scalar)
+static int bn_act_args(BnAct& A, const char* who, int C, const float* gamma, const float* beta, int act, float slope,
+                       const float* prelu_w, int prelu_n, std::initializer_list<const void*> float4_tensors = {}) {
+  SRK_REQUIRE(act == SRK_ACT_NONE || act == SRK_ACT_RELU || act == SRK_ACT_LRELU || act == SRK_ACT_PRELU,
+              "%s: only ReLU / LeakyReLU / PReLU fold into BatchNorm", who);
+  if (act == SRK_ACT_PRELU) SRK_REQUIRE(prelu_w && (prelu_n == 1 || prelu_n == C), "%s: PReLU needs 1 or C slopes", who);
+  if (float4_tensors.size())
+    SRK_REQUIRE(bn_vec4(C, float4_tensors) && bn_vec4(C, {gamma, beta}),
+                "%s: C must be a multiple of 4 and the tensors 16-byte aligned", who);
+  A = BnAct{gamma, beta, prelu_w, act, prelu_n, slope};
+  return SRK_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1197,35 +1157,26 @@ extern "C" size_t srk_bn_workspace_bytes(int C) { return (size_t)kBnRowSplits * 
 
 extern "C" int srk_bn_stats(const float* x, double* stats, size_t rows, int C, void* workspace, void* stream) {
   SRK_REQUIRE(x && stats && workspace && rows > 0 && C > 0, "bn_stats: bad args");
-  return bn_colsum(0, x, nullptr, nullptr, nullptr, stats, rows, C, workspace, (hipStream_t)stream);
+  return bn_colsum<0>(x, nullptr, nullptr, nullptr, stats, rows, C, workspace, (hipStream_t)stream, "bn_stats");
 }
 
 extern "C" int srk_bn_stats_finalize(const float* x, double* stats, size_t rows, int C, float* save_mean, float* save_rstd,
                                      float* running_mean, float* running_var, float momentum, float eps,
                                      int64_t* num_batches_tracked, void* workspace, void* stream) {
   SRK_REQUIRE(x && stats && workspace && save_mean && save_rstd && rows > 0 && C > 0, "bn_stats_finalize: bad args");
-  BnFused fu;
-  fu.mode = 0; fu.count = (double)rows; fu.o0 = save_mean; fu.o1 = save_rstd; fu.rm = running_mean; fu.rv = running_var;
-  fu.momentum = momentum; fu.eps = eps; fu.nbt = (long long*)num_batches_tracked;
-  return bn_colsum(0, x, nullptr, nullptr, nullptr, stats, rows, C, workspace, (hipStream_t)stream, fu);
+  hipStream_t s = (hipStream_t)stream;
+  const int splits = bn_launch_colsum<0>(x, nullptr, nullptr, nullptr, (double*)workspace, rows, C, s);
+  bn_launch_reduce<0>((const double*)workspace, splits, stats, C, (double)rows, save_mean, save_rstd, running_mean, running_var,
+                      momentum, eps, (long long*)num_batches_tracked, s);
+  return check_launch("bn_stats_finalize");
 }
 
 extern "C" int srk_bn_finalize_partials(const double* partials, int splits, double* stats, size_t rows, int C,
                                         float* save_mean, float* save_rstd, float* running_mean, float* running_var,
                                         float momentum, float eps, int64_t* num_batches_tracked, void* stream) {
   SRK_REQUIRE(partials && stats && save_mean && save_rstd && splits > 0 && rows > 0 && C > 0, "bn_finalize_partials: bad args");
-  hipStream_t s = (hipStream_t)stream;
-  if (splits > 64 && env_int("SRK_BN_RED16", 1) != 0)
-    hipLaunchKernelGGL((k_bn_reduce16<0>), dim3(cdiv(C, 16)), dim3(1024), 0, s, partials, stats, splits, C, (double)rows,
-                       save_mean, save_rstd, running_mean, running_var, momentum, eps, (long long*)num_batches_tracked);
-  else if (splits > 64)
-    hipLaunchKernelGGL((k_bn_reduce_fused<0, 16>), dim3(cdiv(C, 64)), dim3(1024), 0, s, partials, stats, splits, C,
-                       (double)rows, save_mean, save_rstd, running_mean, running_var, momentum, eps,
-                       (long long*)num_batches_tracked);
-  else
-    hipLaunchKernelGGL((k_bn_reduce_fused<0, 4>), dim3(cdiv(C, 64)), dim3(256), 0, s, partials, stats, splits, C,
-                       (double)rows, save_mean, save_rstd, running_mean, running_var, momentum, eps,
-                       (long long*)num_batches_tracked);
+  bn_launch_reduce<0>(partials, splits, stats, C, (double)rows, save_mean, save_rstd, running_mean, running_var, momentum, eps,
+                      (long long*)num_batches_tracked, (hipStream_t)stream);
   return check_launch("bn_finalize_partials");
 }
 
@@ -1233,9 +1184,8 @@ extern "C" int srk_bn_backward_stats_grads(const float* dy, const float* x, cons
                                            double* dstats, size_t rows, int C, float* dgamma, float* dbeta, void* workspace,
                                            void* stream) {
   SRK_REQUIRE(dy && x && mean && rstd && dstats && workspace && rows > 0 && C > 0, "bn_backward_stats_grads: bad args");
-  BnFused fu;
-  fu.mode = 1; fu.o0 = dgamma; fu.o1 = dbeta;
-  return bn_colsum(1, dy, x, mean, rstd, dstats, rows, C, workspace, (hipStream_t)stream, fu);
+  return srk_bn_backward_stats_grads_act(dy, x, mean, rstd, nullptr, nullptr, dstats, rows, C, dgamma, dbeta, SRK_ACT_NONE, 0.f,
+                                         nullptr, 0, nullptr, workspace, stream);
 }
 
 extern "C" int srk_bn_finalize(const double* stats, double count, float* save_mean, float* save_rstd,
@@ -1330,16 +1280,14 @@ extern "C" int srk_bn_apply(const float* x, float* y, const float* mean, const f
   SRK_REQUIRE(x && y && mean && rstd && rows > 0 && C > 0, "bn_apply: bad args");
   SRK_REQUIRE(act != SRK_ACT_PRELU, "bn_apply: PReLU is not fused here (use srk_act_forward)");
   const size_t total = rows * (size_t)C;
-  size_t nb = (total + 256 * 4 - 1) / (256 * 4);
-  if (nb > 4096) nb = 4096;
-  if (bn_vec4(C, x, y, mean, rstd, gamma, beta))
-    hipLaunchKernelGGL(k_bn_apply4, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, x, y, mean, rstd, gamma, beta,
+  if (bn_vec4(C, {x, y, mean, rstd, gamma, beta}))
+    hipLaunchKernelGGL(k_bn_apply4, bn_flat_grid(total), dim3(256), 0, (hipStream_t)stream, x, y, mean, rstd, gamma, beta,
                        total / 4, C, act, slope, y_amax);
   else if (y_amax) {
     set_error("bn_apply: y_amax needs the 16-byte path (C %% 4 == 0, aligned tensors)");
     return SRK_ERR_UNSUPPORTED;
   } else
-    hipLaunchKernelGGL(k_bn_apply, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, x, y, mean, rstd, gamma, beta,
+    hipLaunchKernelGGL(k_bn_apply, bn_flat_grid(total), dim3(256), 0, (hipStream_t)stream, x, y, mean, rstd, gamma, beta,
                        total, C, act, slope);
   return check_launch("bn_apply");
 }
@@ -1347,7 +1295,7 @@ extern "C" int srk_bn_apply(const float* x, float* y, const float* mean, const f
 extern "C" int srk_bn_backward_stats(const float* dy, const float* x, const float* mean, const float* rstd,
                                      double* dstats, size_t rows, int C, void* workspace, void* stream) {
   SRK_REQUIRE(dy && x && mean && rstd && dstats && workspace && rows > 0 && C > 0, "bn_backward_stats: bad args");
-  return bn_colsum(1, dy, x, mean, rstd, dstats, rows, C, workspace, (hipStream_t)stream);
+  return bn_colsum<1>(dy, x, mean, rstd, dstats, rows, C, workspace, (hipStream_t)stream, "bn_backward_stats");
 }
 
 extern "C" int srk_bn_backward_apply(const float* dy, const float* x, const float* mean, const float* rstd,
@@ -1355,39 +1303,24 @@ extern "C" int srk_bn_backward_apply(const float* dy, const float* x, const floa
                                      int C, void* stream) {
   SRK_REQUIRE(dy && x && mean && rstd && dstats && dx && rows > 0 && C > 0 && count > 0, "bn_backward_apply: bad args");
   const size_t total = rows * (size_t)C;
-  size_t nb = (total + 256 * 4 - 1) / (256 * 4);
-  if (nb > 4096) nb = 4096;
-  const bool v4 = bn_vec4(C, dy, x, mean, rstd, gamma, dx);
-  if (v4) {
-    hipLaunchKernelGGL(k_bn_bwd_apply4, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd,
-                       gamma, dstats, count, dx, total / 4, C);
-  } else {
-    hipLaunchKernelGGL(k_bn_bwd_apply, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd,
-                       gamma, dstats, count, dx, total, C);
-  }
+  if (bn_vec4(C, {dy, x, mean, rstd, gamma, dx}))   // the float4 kernel without an activation
+    hipLaunchKernelGGL(k_bn_bwd_apply_act4, bn_flat_grid(total), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd,
+                       BnAct{gamma, nullptr, nullptr, SRK_ACT_NONE, 0, 0.f}, dstats, count, dx, total / 4, C);
+  else
+    hipLaunchKernelGGL(k_bn_bwd_apply, bn_flat_grid(total), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd, gamma,
+                       dstats, count, dx, total, C);
   return check_launch("bn_backward_apply");
-}
-
-static int bn_act_check(int act, const float* prelu_w, int prelu_n, int C, const char* who) {
-  SRK_REQUIRE(act == SRK_ACT_NONE || act == SRK_ACT_RELU || act == SRK_ACT_LRELU || act == SRK_ACT_PRELU,
-              "%s: only ReLU / LeakyReLU / PReLU fold into BatchNorm", who);
-  if (act == SRK_ACT_PRELU) SRK_REQUIRE(prelu_w && (prelu_n == 1 || prelu_n == C), "%s: PReLU needs 1 or C slopes", who);
-  return SRK_OK;
 }
 
 extern "C" int srk_bn_apply_act(const float* x, float* y, const float* mean, const float* rstd, const float* gamma,
                                 const float* beta, size_t rows, int C, int act, float slope, const float* prelu_weight,
                                 int prelu_n, const float* residual, float* y_amax, void* stream) {
   SRK_REQUIRE(x && y && mean && rstd && rows > 0 && C > 0, "bn_apply_act: bad args");
-  int rc = bn_act_check(act, prelu_weight, prelu_n, C, "bn_apply_act");
-  if (rc) return rc;
-  SRK_REQUIRE(bn_vec4(C, x, y, mean, rstd, gamma, beta) && ((uintptr_t)residual & 15) == 0,
-              "bn_apply_act: C must be a multiple of 4 and the tensors 16-byte aligned");
+  BnAct A;
+  if (int rc = bn_act_args(A, "bn_apply_act", C, gamma, beta, act, slope, prelu_weight, prelu_n, {x, y, mean, rstd, residual}))
+    return rc;
   const size_t total = rows * (size_t)C;
-  size_t nb = (total + 256 * 4 - 1) / (256 * 4);
-  if (nb > 4096) nb = 4096;
-  BnAct A{gamma, beta, prelu_weight, act, prelu_n, slope};
-  hipLaunchKernelGGL(k_bn_apply_act4, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, x, y, mean, rstd, A, residual,
+  hipLaunchKernelGGL(k_bn_apply_act4, bn_flat_grid(total), dim3(256), 0, (hipStream_t)stream, x, y, mean, rstd, A, residual,
                      total / 4, C, y_amax);
   return check_launch("bn_apply_act");
 }
@@ -1398,17 +1331,13 @@ extern "C" int srk_bn_backward_stats_grads_act(const float* dy, const float* x, 
                                                const float* prelu_weight, int prelu_n, float* dprelu, void* workspace,
                                                void* stream) {
   SRK_REQUIRE(dy && x && mean && rstd && dstats && workspace && rows > 0 && C > 0, "bn_backward_stats_grads_act: bad args");
-  int rc = bn_act_check(act, prelu_weight, prelu_n, C, "bn_backward_stats_grads_act");
-  if (rc) return rc;
-  int splits = (int)((rows + 127) / 128);
-  if (splits > kBnRowSplits * 2 / 3) splits = kBnRowSplits * 2 / 3;  // three sums per split in the same workspace
-  if (splits < 1) splits = 1;
-  const size_t rps = (rows + splits - 1) / splits;
+  BnAct A;
+  if (int rc = bn_act_args(A, "bn_backward_stats_grads_act", C, gamma, beta, act, slope, prelu_weight, prelu_n)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  BnAct A{gamma, beta, prelu_weight, act, prelu_n, slope};
-  hipLaunchKernelGGL(k_bn_colsum_act, dim3(cdiv(C, 64), splits), dim3(256), 0, s, dy, x, mean, rstd, A, (double*)workspace,
-                     rows, C, rps);
-  if (splits > 64)
+  const int splits = bn_launch_colsum_bwd(A, dy, x, mean, rstd, (double*)workspace, rows, C, s);
+  if (act == SRK_ACT_NONE)
+    bn_launch_reduce<1>((const double*)workspace, splits, dstats, C, 0.0, dgamma, dbeta, nullptr, nullptr, 0.f, 0.f, nullptr, s);
+  else if (splits > 64)
     hipLaunchKernelGGL(k_bn_reduce_act<16>, dim3(cdiv(C, 64)), dim3(1024), 0, s, (const double*)workspace, dstats, splits, C,
                        dgamma, dbeta, act == SRK_ACT_PRELU ? dprelu : nullptr, prelu_n);
   else
@@ -1422,16 +1351,14 @@ extern "C" int srk_bn_backward_apply_act(const float* dy, const float* x, const 
                                          float* dx, size_t rows, int C, int act, float slope, const float* prelu_weight,
                                          int prelu_n, void* stream) {
   SRK_REQUIRE(dy && x && mean && rstd && dstats && dx && rows > 0 && C > 0 && count > 0, "bn_backward_apply_act: bad args");
-  int rc = bn_act_check(act, prelu_weight, prelu_n, C, "bn_backward_apply_act");
-  if (rc) return rc;
-  SRK_REQUIRE(bn_vec4(C, dy, x, mean, rstd, gamma, dx) && ((uintptr_t)beta & 15) == 0,
-              "bn_backward_apply_act: C must be a multiple of 4 and the tensors 16-byte aligned");
+  // without an activation this is the plain backward (which has a scalar kernel for what the float4 one cannot take)
+  if (act == SRK_ACT_NONE) return srk_bn_backward_apply(dy, x, mean, rstd, gamma, dstats, count, dx, rows, C, stream);
+  BnAct A;
+  if (int rc = bn_act_args(A, "bn_backward_apply_act", C, gamma, beta, act, slope, prelu_weight, prelu_n, {dy, x, mean, rstd, dx}))
+    return rc;
   const size_t total = rows * (size_t)C;
-  size_t nb = (total + 256 * 4 - 1) / (256 * 4);
-  if (nb > 4096) nb = 4096;
-  BnAct A{gamma, beta, prelu_weight, act, prelu_n, slope};
-  hipLaunchKernelGGL(k_bn_bwd_apply_act4, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd, A,
-                     dstats, count, dx, total / 4, C);
+  hipLaunchKernelGGL(k_bn_bwd_apply_act4, bn_flat_grid(total), dim3(256), 0, (hipStream_t)stream, dy, x, mean, rstd, A, dstats,
+                     count, dx, total / 4, C);
   return check_launch("bn_backward_apply_act");
 }
 
@@ -1440,13 +1367,7 @@ extern "C" int srk_bn_fused_supported(int C) { return C > 0 && C % BNF_CS == 0 &
 
 extern "C" int srk_bn_stats_partials(const float* x, size_t rows, int C, void* workspace, int* splits_out, void* stream) {
   SRK_REQUIRE(x && workspace && splits_out && rows > 0 && C > 0, "bn_stats_partials: bad args");
-  int splits = (int)((rows + 63) / 64);
-  if (splits > kBnRowSplits) splits = kBnRowSplits;
-  if (splits < 1) splits = 1;
-  const size_t rps = (rows + splits - 1) / splits;
-  hipLaunchKernelGGL(k_bn_colsum<0>, dim3(cdiv(C, 64), splits), dim3(256), 0, (hipStream_t)stream, x, nullptr, nullptr,
-                     nullptr, (double*)workspace, rows, C, rps);
-  *splits_out = splits;
+  *splits_out = bn_launch_colsum<0>(x, nullptr, nullptr, nullptr, (double*)workspace, rows, C, (hipStream_t)stream);
   return check_launch("bn_stats_partials");
 }
 
@@ -1457,14 +1378,13 @@ extern "C" int srk_bn_finalize_apply_act(const double* partials, int splits, dou
                                          const float* residual, float* y_amax, void* stream) {
   SRK_REQUIRE(partials && stats && save_mean && save_rstd && x && y && splits > 0 && rows > 0, "bn_finalize_apply_act: bad args");
   SRK_REQUIRE(srk_bn_fused_supported(C), "bn_finalize_apply_act: C must be a multiple of 16, <= 512");
-  int rc = bn_act_check(act, prelu_weight, prelu_n, C, "bn_finalize_apply_act");
-  if (rc) return rc;
-  SRK_REQUIRE(bn_vec4(C, x, y, save_mean, save_rstd, gamma, beta) && ((uintptr_t)residual & 15) == 0,
-              "bn_finalize_apply_act: tensors must be 16-byte aligned");
+  BnAct A;
+  if (int rc = bn_act_args(A, "bn_finalize_apply_act", C, gamma, beta, act, slope, prelu_weight, prelu_n,
+                           {x, y, save_mean, save_rstd, residual}))
+    return rc;
   dim3 grid;
   size_t rpb;
   bnf_grid(rows, C, grid, rpb);
-  BnAct A{gamma, beta, prelu_weight, act, prelu_n, slope};
   hipLaunchKernelGGL(k_bn_fin_apply_act, grid, dim3(BNF_THR), 0, (hipStream_t)stream, partials, splits, (double)rows, x, y, A,
                      residual, rows, C, rpb, save_mean, save_rstd, stats, running_mean, running_var, momentum, eps,
                      (long long*)num_batches_tracked, y_amax);
@@ -1477,27 +1397,9 @@ extern "C" int srk_bn_backward_partials_act(const float* dy, const float* x, con
                                             const float* prelu_weight, int prelu_n, void* workspace, int* splits_out,
                                             void* stream) {
   SRK_REQUIRE(dy && x && mean && rstd && workspace && splits_out && rows > 0 && C > 0, "bn_backward_partials_act: bad args");
-  int rc = bn_act_check(act, prelu_weight, prelu_n, C, "bn_backward_partials_act");
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if (act == SRK_ACT_NONE) {
-    int splits = (int)((rows + 63) / 64);
-    if (splits > kBnRowSplits) splits = kBnRowSplits;
-    if (splits < 1) splits = 1;
-    const size_t rps = (rows + splits - 1) / splits;
-    dim3 grid(cdiv(C, 64), splits);
-    hipLaunchKernelGGL(k_bn_colsum<1>, grid, dim3(256), 0, s, dy, x, mean, rstd, (double*)workspace, rows, C, rps);
-    *splits_out = splits;
-    return check_launch("bn_backward_partials_act");
-  }
-  int splits = (int)((rows + 127) / 128);
-  if (splits > kBnRowSplits * 2 / 3) splits = kBnRowSplits * 2 / 3;  // three sums per split in the same workspace
-  if (splits < 1) splits = 1;
-  const size_t rps = (rows + splits - 1) / splits;
-  BnAct A{gamma, beta, prelu_weight, act, prelu_n, slope};
-  hipLaunchKernelGGL(k_bn_colsum_act, dim3(cdiv(C, 64), splits), dim3(256), 0, s, dy, x, mean, rstd, A, (double*)workspace, rows,
-                     C, rps);
-  *splits_out = splits;
+  BnAct A;
+  if (int rc = bn_act_args(A, "bn_backward_partials_act", C, gamma, beta, act, slope, prelu_weight, prelu_n)) return rc;
+  *splits_out = bn_launch_colsum_bwd(A, dy, x, mean, rstd, (double*)workspace, rows, C, (hipStream_t)stream);
   return check_launch("bn_backward_partials_act");
 }
 
@@ -1509,14 +1411,13 @@ extern "C" int srk_bn_backward_finalize_apply_act(const double* partials, int sp
   SRK_REQUIRE(partials && dstats && dy && x && mean && rstd && dx && splits > 0 && rows > 0 && count > 0,
               "bn_backward_finalize_apply_act: bad args");
   SRK_REQUIRE(srk_bn_fused_supported(C), "bn_backward_finalize_apply_act: C must be a multiple of 16, <= 512");
-  int rc = bn_act_check(act, prelu_weight, prelu_n, C, "bn_backward_finalize_apply_act");
-  if (rc) return rc;
-  SRK_REQUIRE(bn_vec4(C, dy, x, mean, rstd, gamma, dx) && ((uintptr_t)beta & 15) == 0,
-              "bn_backward_finalize_apply_act: tensors must be 16-byte aligned");
+  BnAct A;
+  if (int rc = bn_act_args(A, "bn_backward_finalize_apply_act", C, gamma, beta, act, slope, prelu_weight, prelu_n,
+                           {dy, x, mean, rstd, dx}))
+    return rc;
   dim3 grid;
   size_t rpb;
   bnf_grid(rows, C, grid, rpb);
-  BnAct A{gamma, beta, prelu_weight, act, prelu_n, slope};
   hipStream_t s = (hipStream_t)stream;
   float* dp = act == SRK_ACT_PRELU ? dprelu : nullptr;
   const int pq = act == SRK_ACT_NONE ? 2 : 3;   // planes per split row (srk_bn_backward_partials_act)

@@ -1273,6 +1273,38 @@ def _collective(fn):
         fn()
 
 
+def _bn_train_stats(lib, x, rows, c, mean, rstd, stats, running, momentum, eps, nbt_p, sync_group, fin):
+    """The four ways to a training BatchNorm's statistics.  Returns (count, partials): with `fin` (finalize-in-apply) the
+    column sums are left as partials = (tensor, splits) for srk_bn_finalize_apply_act; otherwise mean / rstd / the running
+    statistics are written here and partials is None."""
+    ws = torch.empty(int(lib.srk_bn_workspace_bytes(c)), dtype=torch.uint8, device=x.device)
+    part = getattr(x, "_srk_bn_partial", None)   # column sums from the producing conv's epilogue (k_c64)
+    if part is not None and (sync_group is not None or part[2] != _ver(x) or part[0].shape[1] != 2 * c):
+        part = None
+    rm, rv = running
+    if fin:
+        if part is not None:
+            return float(rows), (part[0], int(part[1]))
+        sp = ctypes.c_int(0)
+        check(lib.srk_bn_stats_partials(ptr(x), rows, c, ptr(ws), ctypes.byref(sp), stream_ptr()), "srk_bn_stats_partials")
+        return float(rows), (ws, int(sp.value))
+    if part is not None:             # reduce + finalize only
+        check(lib.srk_bn_finalize_partials(ptr(part[0]), part[1], ptr(stats), rows, c, ptr(mean), ptr(rstd), ptr(rm), ptr(rv),
+                                           momentum, eps, nbt_p, stream_ptr()), "srk_bn_finalize_partials")
+        return float(rows), None
+    if sync_group is None:           # column sums, then reduce + mean / rstd / running statistics
+        check(lib.srk_bn_stats_finalize(ptr(x), ptr(stats), rows, c, ptr(mean), ptr(rstd), ptr(rm), ptr(rv), momentum, eps,
+                                        nbt_p, ptr(ws), stream_ptr()), "srk_bn_stats_finalize")
+        return float(rows), None
+    import torch.distributed as dist   # SyncBN: the [2C] sums are all-reduced between the two phases
+    check(lib.srk_bn_stats(ptr(x), ptr(stats), rows, c, ptr(ws), stream_ptr()), "srk_bn_stats")
+    _collective(lambda: dist.all_reduce(stats, group=sync_group))
+    count = float(rows) * dist.get_world_size(sync_group)
+    check(lib.srk_bn_finalize(ptr(stats), count, ptr(mean), ptr(rstd), ptr(rm), ptr(rv), momentum, eps, c, nbt_p,
+                              stream_ptr()), "srk_bn_finalize")
+    return count, None
+
+
 class _BatchNorm(torch.autograd.Function):
     """y = act(bn(x)) [+ residual].  act in {none, relu, lrelu, prelu} and the residual ride in the BatchNorm kernels
     (srk_bn_*_act): the backward recomputes z = gamma * xhat + beta from x, so nothing of the activation is saved."""
@@ -1288,54 +1320,26 @@ class _BatchNorm(torch.autograd.Function):
         rows = x.numel() // c
         mean = torch.empty(c, dtype=torch.float32, device=x.device)
         rstd = torch.empty(c, dtype=torch.float32, device=x.device)
-        count = float(rows)
+        aligned = all(t is None or t.data_ptr() % 16 == 0 for t in (x, gamma, beta, residual))
+        pn = 0 if prelu_w is None else prelu_w.numel()
+        count, part = float(rows), None
         if training:
             stats = torch.empty(2 * c, dtype=torch.float64, device=x.device)
-            ws = torch.empty(int(lib.srk_bn_workspace_bytes(c)), dtype=torch.uint8, device=x.device)
             if nbt is not None and (nbt.dtype != torch.int64 or not nbt.is_cuda):
                 raise RuntimeError("batch_norm: num_batches_tracked must be a CUDA int64 tensor")
             nbt_p = None if nbt is None else ctypes.c_void_p(nbt.data_ptr())
-            part = getattr(x, "_srk_bn_partial", None)
-            if part is not None and (part[2] != _ver(x) or part[0].shape[1] != 2 * c):
-                part = None
             # finalize-in-apply (round 6): the apply kernel finishes the split reduction itself -- one launch less
-            fin = (BN_FIN_APPLY and sync_group is None and lib.srk_bn_fused_supported(c)
-                   and all(t is None or t.data_ptr() % 16 == 0 for t in (x, gamma, beta, residual)))
-            if fin:
-                if part is not None:      # column sums from the producing conv's epilogue (k_c64)
-                    fin_part, fin_splits = part[0], int(part[1])
-                else:
-                    sp = ctypes.c_int(0)
-                    check(lib.srk_bn_stats_partials(ptr(x), rows, c, ptr(ws), ctypes.byref(sp), stream_ptr()),
-                          "srk_bn_stats_partials")
-                    fin_part, fin_splits = ws, int(sp.value)
-            elif sync_group is None and part is not None:
-                # the conv that produced x left its column sums (k_c64's epilogue): reduce + finalize only
-                check(lib.srk_bn_finalize_partials(ptr(part[0]), part[1], ptr(stats), rows, c, ptr(mean), ptr(rstd),
-                                                   ptr(running_mean), ptr(running_var), momentum, eps, nbt_p,
-                                                   stream_ptr()), "srk_bn_finalize_partials")
-            elif sync_group is None:   # statistics + finalize: column sums, then reduce + mean / rstd / running stats
-                check(lib.srk_bn_stats_finalize(ptr(x), ptr(stats), rows, c, ptr(mean), ptr(rstd), ptr(running_mean),
-                                                ptr(running_var), momentum, eps, nbt_p, ptr(ws), stream_ptr()),
-                      "srk_bn_stats_finalize")
-            else:                    # SyncBN: the [2C] sums are all-reduced between the two phases
-                import torch.distributed as dist
-                check(lib.srk_bn_stats(ptr(x), ptr(stats), rows, c, ptr(ws), stream_ptr()), "srk_bn_stats")
-                _collective(lambda: dist.all_reduce(stats, group=sync_group))
-                count *= dist.get_world_size(sync_group)
-                check(lib.srk_bn_finalize(ptr(stats), count, ptr(mean), ptr(rstd), ptr(running_mean), ptr(running_var),
-                                          momentum, eps, c, nbt_p, stream_ptr()), "srk_bn_finalize")
+            fin = bool(BN_FIN_APPLY and sync_group is None and lib.srk_bn_fused_supported(c) and aligned)
+            count, part = _bn_train_stats(lib, x, rows, c, mean, rstd, stats, (running_mean, running_var), momentum, eps,
+                                          nbt_p, sync_group, fin)
         else:
-            fin = False
             check(lib.srk_bn_eval_params(ptr(running_mean), ptr(running_var), eps, ptr(mean), ptr(rstd), c,
                                          stream_ptr()), "srk_bn_eval_params")
         y = torch.empty_like(x)
-        fused = act != ACT_NONE or residual is not None
         # 4-D activations in front of a convolution of the fp32-faithful class: leave the output's running maximum
         # (only on the kernels' 16-byte path -- C % 4 == 0, aligned tensors; an unaligned view takes the scalar kernel,
         # which keeps no maximum: the convolution behind it then stays on the six-MFMA arithmetic)
-        vec_ok = c % 4 == 0 and all(t is None or t.data_ptr() % 16 == 0 for t in (x, gamma, beta, residual))
-        ya = _amax_alloc(x.device) if (F16X3 and x.dim() == 4 and vec_ok
+        ya = _amax_alloc(x.device) if (F16X3 and x.dim() == 4 and c % 4 == 0 and aligned
                                        and (F16X3_ALWAYS or rows * ((c + 63) // 64) >= F16X3_MIN_PIXELS)
                                        and _MODES[_PRECISION["mode"]]["train_fwd" if training else "infer"]
                                        in (_lib.ALGO_MFMA_BF16X6, _lib.ALGO_MFMA_F16X3)) else None
@@ -1343,23 +1347,21 @@ class _BatchNorm(torch.autograd.Function):
             residual = _dense(residual)
             if tuple(residual.shape) != tuple(x.shape) or residual.stride() != x.stride():
                 raise RuntimeError("batch_norm: residual must have the shape and layout of x")
-        if fin:
-            check(lib.srk_bn_finalize_apply_act(ptr(fin_part), fin_splits, ptr(stats), rows, c, ptr(mean), ptr(rstd),
+        if part is not None:
+            check(lib.srk_bn_finalize_apply_act(ptr(part[0]), part[1], ptr(stats), rows, c, ptr(mean), ptr(rstd),
                                                 ptr(running_mean), ptr(running_var), momentum, eps, nbt_p, ptr(x), ptr(y),
-                                                ptr(gamma), ptr(beta), act, slope, ptr(prelu_w),
-                                                0 if prelu_w is None else prelu_w.numel(), ptr(residual), ptr(ya),
+                                                ptr(gamma), ptr(beta), act, slope, ptr(prelu_w), pn, ptr(residual), ptr(ya),
                                                 stream_ptr()), "srk_bn_finalize_apply_act")
-        elif fused:
+        elif act != ACT_NONE or residual is not None:
             check(lib.srk_bn_apply_act(ptr(x), ptr(y), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), rows, c, act, slope,
-                                       ptr(prelu_w), 0 if prelu_w is None else prelu_w.numel(), ptr(residual),
-                                       ptr(ya), stream_ptr()), "srk_bn_apply_act")
-        else:
+                                       ptr(prelu_w), pn, ptr(residual), ptr(ya), stream_ptr()), "srk_bn_apply_act")
+        else:   # (the plain kernels round the affine differently from the _act ones: kept)
             check(lib.srk_bn_apply(ptr(x), ptr(y), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), rows, c, ACT_NONE, 0.0,
                                    ptr(ya), stream_ptr()), "srk_bn_apply")
         if ya is not None:
             _tag_amax(y, ya)    # the convolution behind a BatchNorm scales its fp16 planes by this (F16X3)
         ctx.training, ctx.count, ctx.sync_group = training, count, sync_group
-        ctx.fin = fin
+        ctx.fin = part is not None
         ctx.gamma_ref, ctx.beta_ref, ctx.prelu_ref = gamma, beta, prelu_w
         ctx.act, ctx.slope, ctx.has_res = act, slope, residual is not None
         ctx.save_for_backward(x, gamma, mean, rstd, beta if act != ACT_NONE else None, prelu_w)
@@ -1376,67 +1378,47 @@ class _BatchNorm(torch.autograd.Function):
         ws = torch.empty(int(lib.srk_bn_workspace_bytes(c)), dtype=torch.uint8, device=x.device)
         dgamma = getattr(ctx.gamma_ref, "_srk_grad", None)
         dbeta = getattr(ctx.beta_ref, "_srk_grad", None)
-        ret_g = ret_b = ret_p = None
+        ret_g = ret_b = ret_p = dprelu = None
         if dgamma is None or dbeta is None:
             dgamma = ret_g = torch.zeros(c, dtype=torch.float32, device=x.device)
             dbeta = ret_b = torch.zeros(c, dtype=torch.float32, device=x.device)
+        pn = 0 if prelu_w is None else prelu_w.numel()
+        if ctx.act == ACT_PRELU:
+            dprelu = getattr(ctx.prelu_ref, "_srk_grad", None)
+            if dprelu is None:
+                dprelu = ret_p = torch.zeros_like(prelu_w)
         dres = dy if ctx.has_res else None   # the residual's gradient is dy itself
         if ctx.has_res and ctx.res_box is not None:
             ctx.res_box.g, dres = dy, None   # parked for the block's first conv, which adds it in its data-gradient kernel
-        if ctx.fin and ctx.training and dy.data_ptr() % 16 == 0:
+        dx = torch.empty_like(dy)
+        act_args = (ctx.act, ctx.slope, ptr(prelu_w), pn)
+        if ctx.fin and dy.data_ptr() % 16 == 0:
             # finalize-in-apply: column sums, then ONE kernel that reduces them (per 16-channel slab), adds the parameter
             # gradients and writes dx
-            dprelu = None
-            pn = 0 if prelu_w is None else prelu_w.numel()
-            if ctx.act == ACT_PRELU:
-                dprelu = getattr(ctx.prelu_ref, "_srk_grad", None)
-                if dprelu is None:
-                    dprelu = ret_p = torch.zeros_like(prelu_w)
             sp = ctypes.c_int(0)
             check(lib.srk_bn_backward_partials_act(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), rows, c,
-                                                   ctx.act, ctx.slope, ptr(prelu_w), pn, ptr(ws), ctypes.byref(sp),
-                                                   stream_ptr()), "srk_bn_backward_partials_act")
-            dx = torch.empty_like(dy)
+                                                   *act_args, ptr(ws), ctypes.byref(sp), stream_ptr()),
+                  "srk_bn_backward_partials_act")
             check(lib.srk_bn_backward_finalize_apply_act(ptr(ws), int(sp.value), ptr(dstats), ctx.count, ptr(dy), ptr(x),
                                                          ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(dx), rows, c,
-                                                         ptr(dgamma), ptr(dbeta), ctx.act, ctx.slope, ptr(prelu_w), pn,
-                                                         ptr(dprelu), stream_ptr()), "srk_bn_backward_finalize_apply_act")
-            return dx, ret_g, ret_b, None, None, None, None, None, None, None, None, None, ret_p, dres, None
-        if ctx.act != ACT_NONE:
-            dprelu = None
-            pn = 0 if prelu_w is None else prelu_w.numel()
-            if ctx.act == ACT_PRELU:
-                dprelu = getattr(ctx.prelu_ref, "_srk_grad", None)
-                if dprelu is None:
-                    dprelu = ret_p = torch.zeros_like(prelu_w)
+                                                         ptr(dgamma), ptr(dbeta), *act_args, ptr(dprelu), stream_ptr()),
+                  "srk_bn_backward_finalize_apply_act")
+        else:
+            # statistics of the backward + the parameter gradients (from the LOCAL sums: the DP gradient all-reduce happens
+            # later), then dx; SyncBN all-reduces the sums in between
             check(lib.srk_bn_backward_stats_grads_act(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta),
-                                                      ptr(dstats), rows, c, ptr(dgamma), ptr(dbeta), ctx.act, ctx.slope,
-                                                      ptr(prelu_w), pn, ptr(dprelu), ptr(ws), stream_ptr()),
-                  "srk_bn_backward_stats_grads_act")
+                                                      ptr(dstats), rows, c, ptr(dgamma), ptr(dbeta), *act_args, ptr(dprelu),
+                                                      ptr(ws), stream_ptr()), "srk_bn_backward_stats_grads_act")
             if ctx.training and ctx.sync_group is not None:
                 import torch.distributed as dist
                 grp = ctx.sync_group
                 _collective(lambda: dist.all_reduce(dstats, group=grp))
-            dx = torch.empty_like(dy)
-            use = dstats if ctx.training else torch.zeros_like(dstats)
-            check(lib.srk_bn_backward_apply_act(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(use),
-                                                ctx.count, ptr(dx), rows, c, ctx.act, ctx.slope, ptr(prelu_w), pn,
-                                                stream_ptr()), "srk_bn_backward_apply_act")
-            return dx, ret_g, ret_b, None, None, None, None, None, None, None, None, None, ret_p, dres, None
-        # statistics of the backward + the parameter gradients (from the LOCAL sums: the DP gradient all-reduce happens
-        # later) in two launches
-        check(lib.srk_bn_backward_stats_grads(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(dstats), rows, c, ptr(dgamma),
-                                              ptr(dbeta), ptr(ws), stream_ptr()), "srk_bn_backward_stats_grads")
-        if ctx.training and ctx.sync_group is not None:
-            import torch.distributed as dist
-            grp = ctx.sync_group
-            _collective(lambda: dist.all_reduce(dstats, group=grp))
-        dx = torch.empty_like(dy)
-        # eval-mode BN: statistics are constants -> no mean/projection terms in dx
-        use = dstats if ctx.training else torch.zeros_like(dstats)
-        check(lib.srk_bn_backward_apply(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(use), ctx.count,
-                                        ptr(dx), rows, c, stream_ptr()), "srk_bn_backward_apply")
-        return dx, ret_g, ret_b, None, None, None, None, None, None, None, None, None, None, dres, None
+            if not ctx.training:   # eval-mode BN: statistics are constants -> no mean / projection terms in dx
+                dstats = torch.zeros_like(dstats)
+            check(lib.srk_bn_backward_apply_act(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(dstats),
+                                                ctx.count, ptr(dx), rows, c, *act_args, stream_ptr()),
+                  "srk_bn_backward_apply_act")
+        return dx, ret_g, ret_b, None, None, None, None, None, None, None, None, None, ret_p, dres, None
 
 
 def batch_norm(x, gamma, beta, running_mean, running_var, training, momentum=0.1, eps=1e-5, sync_group=None,
