@@ -257,6 +257,7 @@ int conv_generic_wgrad(const srk_conv_desc& d, const float* x, const float* dy, 
   const int pps = (int)((npix + splits - 1) / splits);
   const float* my = mask ? mask->y : nullptr;
   const float ms = mask ? mask->slope : 0.f;
+  note_kernel("k_wgrad_generic");
   hipLaunchKernelGGL(k_wgrad_generic, dim3(cdiv(elems, 256), splits), dim3(256), 0, s, d, x, dy, my, ms, (float*)ws,
                      pps);
   int rc = check_launch("conv_generic_wgrad");

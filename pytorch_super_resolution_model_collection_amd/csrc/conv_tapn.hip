@@ -225,6 +225,7 @@ static int tapn_launch(MfmaConvParams P, bool x6, hipStream_t s) {
   const size_t lds = (size_t)(((best.HH * best.HW + 15) & ~15)) * TAPN_ZS * sizeof(float);
   dim3 grid((unsigned)((size_t)P.tiles_x * P.tiles_y * P.N));
   if (P.KHv * P.KWv * OCT > 32) {
+    note_kernel("k_conv_tapn<%d,%d,multi,%d>", KS, OCT, x6 ? 3 : 2);
     if (x6)
       hipLaunchKernelGGL((k_conv_tapn<KS, OCT, true, 3>), grid, dim3(256), lds, s, P);
     else

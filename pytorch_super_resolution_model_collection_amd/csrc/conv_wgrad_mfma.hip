@@ -741,10 +741,12 @@ size_t conv_wgrad_mfma_ws(const srk_conv_desc& d) {
 
 template <int NTC, bool TRANS>
 static void launch_w1(const WgradParams& P, dim3 grid, size_t lds, hipStream_t s) {
+  note_kernel("k_wgrad_mfma<%d,%s>", NTC, TRANS ? "trans" : "conv");
   launch_lds<&k_wgrad_mfma<NTC, TRANS>>(grid, dim3(256), lds, s, P);
 }
 template <int MT>
 static void launch_w2(const WgradParams& P, dim3 grid, size_t lds, hipStream_t s) {
+  note_kernel("k_wgrad_mfma_smallcin<%d>", MT);
   launch_lds<&k_wgrad_mfma_smallcin<MT>>(grid, dim3(256), lds, s, P);
 }
 

@@ -280,7 +280,8 @@ FP32_CASES = [c for c in R.CASES if c.ps == 0 and c.n == 1]
 def test_wgrad_fp32_same_shapes(gpu, c):
     """k_wgrad_mfma (algo = mfma_fp32) at the rows' shapes: its blocks walk several tiles here, which no KAT size does"""
     P = _Problem(c, gpu, algo=2)
-    dwA, dbA, _ = P.run(0.0, True, "A")      # (the fp32 kernels report no name)
+    dwA, dbA, name = P.run(0.0, True, "A")
+    assert name.startswith("k_wgrad_mfma<%d,conv>" % min(4, (c.cout + 15) // 16)), (c.row, name)
     _check_against_fp64(c, dwA, dbA, TOL_TIGHT, "fp32", "A")
     dwB, dbB, _ = P.run(0.0, True, "B")
     assert np.array_equal(dwA[0], dwB[0]) and np.array_equal(dbA[0], dbB[0])
