@@ -658,8 +658,17 @@ int srk_channel_affine(const float* x, float* y, size_t n, int C, size_t inner, 
 int srk_upsample_nearest_forward(const float* x, float* y, int N, int H, int W, int C, int r, void* stream);
 int srk_upsample_nearest_backward(const float* dy, float* dx, int N, int H, int W, int C, int r, void* stream);
 /* nn.MaxPool2d(2, 2) of the VGG19 feature extractor (srgan.py:84-90: vgg19.features[:9] holds one), NHWC, floor mode:
- * y [N, H/2, W/2, C].  Forward only — the reference evaluates the VGG loss on detached tensors (srgan.py:302-305). */
+ * y [N, H/2, W/2, C].  The reference evaluates the VGG loss on detached tensors (srgan.py:302-305): forward only there. */
 int srk_maxpool2x2_forward(const float* x, float* y, int N, int H, int W, int C, void* stream);
+/* Its gradient, for a perceptual loss that trains (ops.perceptual_loss): x [N,H,W,C] the pool's input, dy [N,H/2,W/2,C],
+ * dx [N,H,W,C].  The winner of each window is recomputed from x -- ATen's: the first maximum in (row, column) scan order
+ * -- and receives dy; every other element, the trailing row / column of an odd H / W included, is written as zero:
+ * every dx element exactly once, no atomics, nothing to clear before the call.  16-byte accesses when C % 4 == 0 and the
+ * three pointers are 16-byte aligned, else one float at a time.  relu_input != 0: x is the output of a fused conv + ReLU;
+ * windows whose maximum is <= 0 route nothing, so dx is already what that conv's (x > 0) mask would leave.
+ * NaN in x is out of scope (the forward propagates it; the gradient's winner is then unspecified). */
+int srk_maxpool2x2_backward(const float* x, const float* dy, float* dx, int N, int H, int W, int C, int relu_input,
+                            void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,8 @@ the checkpoint and run test() on the test sets, no training; one line per datase
 and --self_ensemble (--test_single, --test_only and the test() after training run every picture through the x8 geometric
 self-ensemble, "EDSR+": the net on the eight flips / rotations, transformed back and averaged) and --ssim_weight A (train
 on (1 - A) * the model's pixel loss + A * (1 - SSIM), A in [0, 1], default 0; every model but SRGAN and DRCN; the logged
-loss is the mixed one).
+loss is the mixed one) and --vgg_weights PATH (SRGAN: a torchvision vgg19 state_dict; the logged G loss gains the reference's
+VGG feature term) with --perceptual (that term trains the generator) and --vgg_loss_weight W (its weight, default 6e-3).
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N main.py ..."""
 import argparse
 import os
@@ -41,6 +42,17 @@ def _unit_interval(text):
         v = float('nan')
     if not 0.0 <= v <= 1.0:
         raise argparse.ArgumentTypeError("--ssim_weight takes a number in [0, 1], got %r" % (text,))
+    return v
+
+
+def _non_negative(text):
+    """--vgg_loss_weight: a finite number >= 0."""
+    try:
+        v = float(text)
+    except ValueError:
+        v = float('nan')
+    if not 0.0 <= v < float('inf'):
+        raise argparse.ArgumentTypeError("--vgg_loss_weight takes a number >= 0, got %r" % (text,))
     return v
 
 
@@ -98,7 +110,23 @@ def parse_args(argv=None):
     p.add_argument('--ssim_weight', type=_unit_interval, default=0.0, metavar='A',
                    help='train on (1 - A) * the pixel loss of the model + A * (1 - SSIM) (ops.ssim_loss; LapSRN: both '
                         'levels); A in [0, 1], default 0: the pixel loss alone, as the reference.  Not for SRGAN and DRCN')
+    p.add_argument('--vgg_weights', type=str, default=None, metavar='PATH',
+                   help='SRGAN: a torchvision vgg19 state_dict file; the G loss then includes the VGG feature term of the '
+                        'reference, 6e-3 * MSE of vgg19.features[:9] -- logged only, as there, unless --perceptual')
+    p.add_argument('--perceptual', action='store_true',
+                   help='SRGAN: the VGG feature term trains the generator (ops.perceptual_loss; the reference detaches it). '
+                        'Needs --vgg_weights and --num_channels 3')
+    p.add_argument('--vgg_loss_weight', type=_non_negative, default=6e-3, metavar='W',
+                   help='SRGAN: weight of the VGG feature term in the G loss (default 6e-3, srgan.py:306); W >= 0')
     args = p.parse_args(argv)
+    if (args.perceptual or args.vgg_weights) and args.model_name != 'SRGAN':
+        p.error('%s: only SRGAN has a VGG feature term, not %s'
+                % ('--perceptual' if args.perceptual else '--vgg_weights', args.model_name))
+    if args.perceptual and not args.vgg_weights:
+        p.error('--perceptual needs --vgg_weights PATH (a torchvision vgg19 state_dict file)')
+    if (args.perceptual or args.vgg_weights) and args.num_channels != 3:
+        p.error('%s: the VGG head reads RGB, use --num_channels 3 (got %d)'
+                % ('--perceptual' if args.perceptual else '--vgg_weights', args.num_channels))
     if args.ssim_weight > 0 and args.model_name in ('SRGAN', 'DRCN'):
         p.error('--ssim_weight %g: %s has no SSIM mix (SRGAN trains on an adversarial content term, DRCN through its fused '
                 'recursive-supervision head); use --ssim_weight 0 or another model' % (args.ssim_weight, args.model_name))

@@ -189,6 +189,7 @@ _PROTOTYPES = {
     "srk_upsample_nearest_forward": (c_int, [c_f, c_f, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "srk_upsample_nearest_backward": (c_int, [c_f, c_f, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "srk_maxpool2x2_forward": (c_int, [c_f, c_f, c_int, c_int, c_int, c_int, c_vp]),
+    "srk_maxpool2x2_backward": (c_int, [c_f, c_f, c_f, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "srk_img_interp_workspace_bytes": (ctypes.c_size_t, [c_int] * 7),
     "srk_img_interp": (c_int, [c_f, c_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, ctypes.c_size_t, c_vp]),
 }

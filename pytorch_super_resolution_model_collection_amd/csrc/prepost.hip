@@ -149,6 +149,97 @@ __global__ __launch_bounds__(256) void k_maxpool2(const float* __restrict__ x, f
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Gradient of that pool.  No index tensor is saved: the winner of a window is recomputed from x, as the conv kernels
+// recompute their masks.  The winner is ATen's: the FIRST maximum in (row, column) scan order, i.e. only a strictly
+// greater value replaces the running one.  NaN inputs are out of scope here (the forward propagates a NaN; a window
+// holding one routes its gradient to whichever element the comparisons above leave).
+// One thread owns one 2x2 window of V channels and writes all four dx elements of it; the grid of windows is
+// ceil(H/2) x ceil(W/2), so with odd H / W the partial windows of the trailing row / column are owned too and get their
+// zeros: every dx element is written exactly once, no memset, no atomics.  The five loads are unconditional, from
+// addresses clamped into the tensors, and the values are selected afterwards (a load under a divergent branch costs a
+// full vmcnt(0) wait at the join).
+// relu_input: x is the output of a fused conv + ReLU whose backward would multiply this dx by (x > 0).  A window whose
+// maximum is <= 0 then routes nothing (its winner is a zero, masked below anyway; a positive winner passes the mask
+// unchanged), so dx leaves pre-masked and the conv below skips its mask read (ops.PREMASK).
+// ---------------------------------------------------------------------------------------------
+template <int V>
+__device__ __forceinline__ void pool_ld(const float* __restrict__ p, float (&v)[V]) {
+  typedef float lf4 __attribute__((ext_vector_type(4)));
+  if (V == 4) {
+    const lf4 t = *reinterpret_cast<const lf4*>(p);
+#pragma unroll
+    for (int i = 0; i < V; ++i) v[i] = t[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < V; ++i) v[i] = p[i];
+  }
+}
+
+template <int V>
+__device__ __forceinline__ void pool_st(float* __restrict__ p, const float (&v)[V]) {
+  typedef float lf4 __attribute__((ext_vector_type(4)));
+  if (V == 4) {
+    lf4 t;
+#pragma unroll
+    for (int i = 0; i < V; ++i) t[i] = v[i];
+    *reinterpret_cast<lf4*>(p) = t;
+  } else {
+#pragma unroll
+    for (int i = 0; i < V; ++i) p[i] = v[i];
+  }
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void k_maxpool2_bwd(const float* __restrict__ x, const float* __restrict__ dy,
+                                                      float* __restrict__ dx, int H, int W, int C, int relu_input,
+                                                      size_t total) {
+  const int OH = H / 2, OW = W / 2, WH = (H + 1) / 2, WW = (W + 1) / 2, CG = C / V;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+    const int cg = (int)(e % CG);
+    size_t t = e / CG;
+    const int wx = (int)(t % WW);
+    t /= WW;
+    const int wy = (int)(t % WH);
+    const size_t n = t / WH;
+    const int y0 = 2 * wy, x0 = 2 * wx;   // always inside the plane
+    const bool has_y1 = y0 + 1 < H, has_x1 = x0 + 1 < W;
+    const bool window = has_y1 && has_x1;   // a whole window: the pool has an output here
+    const int y1 = has_y1 ? y0 + 1 : y0, x1 = has_x1 ? x0 + 1 : x0;   // clamped: loads stay inside x
+    const int py = wy < OH ? wy : OH - 1, px = wx < OW ? wx : OW - 1;   // ... and inside dy
+    const size_t c0 = (size_t)cg * V;
+    const size_t r0 = (n * H + y0) * W, r1 = (n * H + y1) * W;
+    const size_t i00 = (r0 + x0) * C + c0, i01 = (r0 + x1) * C + c0, i10 = (r1 + x0) * C + c0, i11 = (r1 + x1) * C + c0;
+    float a[V], b[V], d[V], f[V], g[V];
+    pool_ld<V>(x + i00, a);
+    pool_ld<V>(x + i01, b);
+    pool_ld<V>(x + i10, d);
+    pool_ld<V>(x + i11, f);
+    pool_ld<V>(dy + ((n * OH + py) * OW + px) * C + c0, g);
+    float o0[V], o1[V], o2[V], o3[V];
+#pragma unroll
+    for (int i = 0; i < V; ++i) {
+      float m = a[i];
+      int k = 0;
+      if (b[i] > m) m = b[i], k = 1;
+      if (d[i] > m) m = d[i], k = 2;
+      if (f[i] > m) m = f[i], k = 3;
+      const bool route = window && !(relu_input && m <= 0.f);
+      const float gi = route ? g[i] : 0.f;
+      o0[i] = k == 0 ? gi : 0.f;
+      o1[i] = k == 1 ? gi : 0.f;
+      o2[i] = k == 2 ? gi : 0.f;
+      o3[i] = k == 3 ? gi : 0.f;
+    }
+    pool_st<V>(dx + i00, o0);
+    if (has_x1) pool_st<V>(dx + i01, o1);
+    if (has_y1) {
+      pool_st<V>(dx + i10, o2);
+      if (has_x1) pool_st<V>(dx + i11, o3);
+    }
+  }
+}
+
 }  // namespace srk
 
 using namespace srk;
@@ -217,4 +308,23 @@ extern "C" int srk_maxpool2x2_forward(const float* x, float* y, int N, int H, in
   const size_t total = (size_t)N * (H / 2) * (W / 2) * C;
   hipLaunchKernelGGL(k_maxpool2, dim3(pp_grid(total, 256 * 4)), dim3(256), 0, (hipStream_t)stream, x, y, H, W, C, total);
   return check_launch("maxpool2x2_forward");
+}
+
+extern "C" int srk_maxpool2x2_backward(const float* x, const float* dy, float* dx, int N, int H, int W, int C,
+                                       int relu_input, void* stream) {
+  SRK_REQUIRE(x && dy && dx, "maxpool2x2_backward: null pointer");
+  SRK_REQUIRE(N > 0 && H >= 2 && W >= 2 && C > 0, "maxpool2x2_backward: bad dims");
+  const size_t windows = (size_t)N * ((H + 1) / 2) * ((W + 1) / 2);
+  hipStream_t s = (hipStream_t)stream;
+  const bool wide = C % 4 == 0 && (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0;
+  if (wide) {
+    const size_t total = windows * (C / 4);
+    hipLaunchKernelGGL(k_maxpool2_bwd<4>, dim3(pp_grid(total, 256)), dim3(256), 0, s, x, dy, dx, H, W, C,
+                       relu_input != 0, total);
+  } else {
+    const size_t total = windows * C;
+    hipLaunchKernelGGL(k_maxpool2_bwd<1>, dim3(pp_grid(total, 256 * 2)), dim3(256), 0, s, x, dy, dx, H, W, C,
+                       relu_input != 0, total);
+  }
+  return check_launch("maxpool2x2_backward");
 }

@@ -33,20 +33,36 @@ def grad_mode(*tensors):
 
 
 class _PackCache(object):
-    """Packed-weight cache for no-grad execution, invalidated when the parameters change."""
+    """Packed-weight cache for no-grad execution, invalidated when the parameters change.
+    get(..., bwd=True) adds the data-gradient pack, (wp_fwd, bias, wp_bwd) as ops.conv2d's `packed` takes it: for a
+    frozen layer that is differentiated through (the VGG head of ops.perceptual_loss), packed on first use and dropped
+    with the forward pack.
+    frozen: the layer belongs to no optimizer (models.FeatureExtractor), so the epoch that optim.step() bumps says
+    nothing about it: address, version counter and device of the parameters remain the key (load_state_dict, .to())
+    and `drop()` (load_vgg19), and a train step that runs optimizer steps packs nothing for the layer."""
 
     def __init__(self):
         self.key = None
         self.val = None
+        self.bwd = None
+        self.frozen = False
 
-    def get(self, weight, bias, transposed, ps_r):
+    def drop(self):
+        self.key = self.val = self.bwd = None
+
+    def get(self, weight, bias, transposed, ps_r, bwd=False):
         key = (weight.data_ptr(), ops._ver(weight), None if bias is None else (bias.data_ptr(), ops._ver(bias)),
-               transposed, ps_r, _WEIGHT_EPOCH[0], str(weight.device))
+               transposed, ps_r, None if self.frozen else _WEIGHT_EPOCH[0], str(weight.device))
         if key != self.key:
             self.val = (ops.pack_weight_fwd(weight.detach(), transposed, ps_r),
                         ops.pack_bias_ps(None if bias is None else bias.detach(), ps_r))
+            self.bwd = None
             self.key = key
-        return self.val
+        if not bwd:
+            return self.val
+        if self.bwd is None:
+            self.bwd = ops.pack_weight_bwd(weight.detach(), transposed, ps_r)
+        return self.val + (self.bwd,)
 
 
 def _plan_views(m, ps_r):

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import ops, utils
-from ._lib import ACT_RELU
+from ._lib import ACT_NONE, ACT_RELU
 from .base_networks import ConvBlock, DeconvBlock, DenseBlock, PSBlock, ResnetBlock, Upsample2xBlock
 from .layers import Conv2d, ConvTranspose2d, PReLU, grad_mode
 
@@ -334,8 +334,9 @@ class FeatureExtractor(nn.Module):
     feature_layer = 8 that is conv3-64, ReLU, conv64-64, ReLU, MaxPool 2x2, conv64-128, ReLU, conv128-128, ReLU, kept
     under the same indices so a torchvision `vgg19` checkpoint's `features.{0,2,5,7}.{weight,bias}` load directly
     (`load_vgg19`).  The reference downloads pretrained weights (srgan.py:144); without network access the weights
-    are whatever the caller loads (kaiming-normal until then, like torchvision's own init).  The module is evaluated
-    without gradients only (srgan.py:302-305): conv + ReLU run as one fused kernel each."""
+    are whatever the caller loads (kaiming-normal until then, like torchvision's own init).  forward() evaluates the
+    module without gradients, as the reference does (srgan.py:302-305); extract(x, grad=True) is the same walk
+    differentiable in x, for a perceptual loss that trains (ops.perceptual_loss).  conv + ReLU run as one fused kernel each."""
 
     # torchvision.models.vgg19 `features` layout up to index 36: numbers = conv3x3 output channels, 'M' = MaxPool2d(2,2)
     VGG19_CFG = (64, 64, 'M', 128, 128, 'M', 256, 256, 256, 256, 'M', 512, 512, 512, 512, 'M', 512, 512, 512, 512, 'M')
@@ -357,6 +358,9 @@ class FeatureExtractor(nn.Module):
                 m.bias.data.zero_()
         for p in self.parameters():
             p.requires_grad_(False)
+        for m in self.features:
+            if isinstance(m, nn.Conv2d):   # in no optimizer: the packs outlive optimizer steps (layers._PackCache)
+                m._cache.frozen = True
         if netVGG is not None:
             self.load_vgg19(netVGG.state_dict() if hasattr(netVGG, "state_dict") else netVGG)
 
@@ -373,19 +377,44 @@ class FeatureExtractor(nn.Module):
         self.load_state_dict(picked)
         from .layers import bump_weight_epoch
         bump_weight_epoch()
+        for m in self.features:
+            if isinstance(m, nn.Conv2d):
+                m._cache.drop()
         return self
 
     def forward(self, x):
-        with torch.no_grad():
-            out = x.detach()
-            mods = list(self.features)
-            i = 0
-            while i < len(mods):
-                m = mods[i]
-                if isinstance(m, nn.Conv2d) and i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU):
-                    out = m.run(out, ACT_RELU)   # conv + bias + ReLU in one kernel
-                    i += 2
+        return self.extract(x, grad=False)
+
+    def extract(self, x, grad=False):
+        """The walk through the head: conv + ReLU as one fused kernel each, the pools in between.
+        grad=False: on the detached input, without a graph, on the inference kernels -- the reference's use.
+        grad=True: differentiable with respect to x (ops.perceptual_loss): the convs run ops.conv2d (the training forward,
+        in grad mode or not: both operands of the loss then see the same kernels), the pools ops.max_pool2x2_train.  The
+        parameters stay frozen, so a backward pass runs data gradients only, and both filter packs of every layer come
+        from the layer's cache: a train step launches no pack for the head."""
+        if not grad:
+            with torch.no_grad():
+                return self._walk(x.detach(), False)
+        return self._walk(x, True)
+
+    def _walk(self, out, grad):
+        mods = list(self.features)
+        i = 0
+        while i < len(mods):
+            m = mods[i]
+            if isinstance(m, nn.Conv2d):
+                fused = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+                act = ACT_RELU if fused else ACT_NONE
+                if grad:
+                    out = ops.conv2d(out, m.weight, m.bias, None, ops.ConvCfg(m._s, m._p, False, 0, act),
+                                     m._cache.get(m.weight, m.bias, False, 0, bwd=True))
                 else:
-                    out = m(out)
-                    i += 1
-            return out
+                    out = m.run(out, act)   # conv + bias + ReLU in one kernel
+                i += 2 if fused else 1
+            elif isinstance(m, _MaxPool2x2) and grad:
+                out = ops.max_pool2x2_train(out)
+                i += 1
+            else:
+                out = m(out)
+                i += 1
+        return out

@@ -1575,6 +1575,68 @@ def max_pool2x2(x):
     return y
 
 
+class _MaxPool2x2(torch.autograd.Function):
+    """MaxPool2d(2, 2) with its gradient (srk_maxpool2x2_backward).  Only x is saved: the backward kernel recomputes
+    each window's winner.  When x is the output of a fused conv + ReLU and the backward runs inside
+    premasked_gradients(), dx leaves already multiplied by that ReLU's mask and carries the mark (see PREMASK)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        lib = _lib.load()
+        require_cuda(x)
+        x = to_nhwc(x)
+        n, c, h, w = x.shape
+        if h < 2 or w < 2:
+            raise RuntimeError("max_pool2x2_train: input %s too small" % (tuple(x.shape),))
+        y = _empty_cl(n, c, h // 2, w // 2, x)
+        check(lib.srk_maxpool2x2_forward(ptr(x), ptr(y), n, h, w, c, stream_ptr()), "srk_maxpool2x2_forward")
+        ctx.x_relu_out = _is_relu_output(x)
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, = ctx.saved_tensors
+        dy = to_nhwc(dy if (_is_nchw_dense(dy) or _is_nhwc_dense(dy)) else dy.contiguous())
+        n, c, h, w = x.shape
+        dx = _empty_cl(n, c, h, w, dy)
+        premask = ctx.x_relu_out and _premask_on() and not x.retains_grad
+        check(lib.srk_maxpool2x2_backward(ptr(x), ptr(dy), ptr(dx), n, h, w, c, int(premask), stream_ptr()),
+              "srk_maxpool2x2_backward")
+        if premask:
+            dx._srk_premasked = (x.data_ptr(), _ver(dx))
+            PREMASK_STATS["masked_dx"] += 1
+        return dx
+
+
+def max_pool2x2_train(x):
+    """nn.MaxPool2d(2, 2) with a backward: the pool of a VGG head whose loss trains (perceptual_loss).  max_pool2x2 stays
+    the no-grad form."""
+    return _MaxPool2x2.apply(x)
+
+
+def perceptual_loss(pred, target, extractor, normalize=True):
+    """The VGG feature loss of SRGAN (srgan.py:301-305) as a term that trains: MSE(extractor.extract(norm(pred)),
+    extractor.extract(norm(target))), norm = utils.norm(vgg=True) when `normalize`; a 0-dim fp32 device tensor with the
+    contract of the other losses (it IS ops.mse_loss on the two feature maps: loss_seed, unit seed, weighted_term,
+    loss_sum).  The gradient flows to pred only.  Both operands run the same kernels -- the training forward of the
+    head, the target's without a graph -- so equal inputs give a loss of exactly 0 and a zero gradient.
+    pred / target: [N, 3, H, W]; extractor: models.FeatureExtractor."""
+    from . import utils
+    for name, t in (("pred", pred), ("target", target)):
+        if t.dim() != 4 or t.shape[1] != 3:
+            raise ValueError("perceptual_loss: %s must be [N, 3, H, W] (the VGG head reads RGB), got shape %s"
+                             % (name, tuple(t.shape)))
+    if pred.shape != target.shape:
+        raise ValueError("perceptual_loss: pred %s vs target %s" % (tuple(pred.shape), tuple(target.shape)))
+    with torch.no_grad():
+        t = target.detach()
+        real = extractor.extract(utils.norm(t, vgg=True) if normalize else t, grad=True)
+    fake = extractor.extract(utils.norm(pred, vgg=True) if normalize else pred, grad=True)
+    return mse_loss(fake, real)
+
+
 def grad_enabled_for(*tensors):
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 

@@ -59,6 +59,24 @@ def apply_lr_decay(kind, epoch, *optimizers):
     return True
 
 
+def check_perceptual_args(args, kind):
+    """--vgg_weights / --perceptual / --vgg_loss_weight of main.py: the VGG feature term belongs to the SRGAN step, reads
+    RGB, and trains only with weights to extract features with.  Raises ValueError naming the flag."""
+    perceptual = bool(getattr(args, "perceptual", False))
+    vgg_weights = getattr(args, "vgg_weights", None)
+    weight = getattr(args, "vgg_loss_weight", None)
+    if weight is not None and not float(weight) >= 0.0:
+        raise ValueError("vgg_loss_weight %r must be >= 0 (main.py --vgg_loss_weight)" % (weight,))
+    if (perceptual or vgg_weights) and kind != "srgan":
+        raise ValueError("%s: only SRGAN has a VGG feature term (main.py --model_name SRGAN)"
+                         % ("perceptual" if perceptual else "vgg_weights"))
+    if perceptual and not vgg_weights:
+        raise ValueError("perceptual: needs the VGG19 weights to extract features with (main.py --vgg_weights PATH)")
+    if (perceptual or vgg_weights) and getattr(args, "num_channels", 3) != 3:
+        raise ValueError("%s: the VGG head reads RGB (main.py --num_channels 3)"
+                         % ("perceptual" if perceptual else "vgg_weights"))
+
+
 class _Trainer(object):
     kind = None
 
@@ -72,6 +90,7 @@ class _Trainer(object):
         self.steps_per_epoch = getattr(args, "steps_per_epoch", 8)
         if self.kind in ("srgan", "drcn") and (getattr(args, "ssim_weight", 0.0) or 0.0) > 0:
             raise ValueError("ssim_weight: %s has no SSIM mix (main.py --ssim_weight)" % self.model_name)
+        check_perceptual_args(args, self.kind)
         if not torch.cuda.is_available():
             raise RuntimeError("the MI355X hot path needs a GPU (gpu_mode=False has no CPU fallback; see oracle/)")
         self.rank, self.world, self.local = dpmod.init_from_env()
@@ -609,8 +628,15 @@ class SRGAN(_Trainer):
             if self.rank == 0:
                 self.save_model(is_pretrain=True)
         # the adversarial step (two models, two optimizers) as one hipGraph; data parallel: graphs split at the two exchanges
-        step = graphed(trainers.srgan_step(self.G, self.D, g_opt, d_opt, g_dp, d_dp, lazy_pack=True,
-                                           prune_dead_grads=bool(getattr(self.args, "prune_dead_grads", False))),
+        # --vgg_weights: the reference's VGG content term in the logged G loss; --perceptual: the term trains G
+        fe = None
+        if getattr(self.args, "vgg_weights", None):
+            fe = models.FeatureExtractor().load_vgg19(self.args.vgg_weights).to(self.device)
+        vgg_w = getattr(self.args, "vgg_loss_weight", None)
+        step = graphed(trainers.srgan_step(self.G, self.D, g_opt, d_opt, g_dp, d_dp, feature_extractor=fe, lazy_pack=True,
+                                           prune_dead_grads=bool(getattr(self.args, "prune_dead_grads", False)),
+                                           perceptual=bool(getattr(self.args, "perceptual", False)),
+                                           vgg_weight=6e-3 if vgg_w is None else float(vgg_w)),
                        [g_flat, d_flat])
         hist = []
         for epoch in range(self.num_epochs):

@@ -192,13 +192,15 @@ def drcn_step(model, opt, w_opt, alpha_dev, beta, reg_dev=None):
     return step
 
 
-def srgan_step(G, D, g_opt, d_opt, g_dp=None, d_dp=None, feature_extractor=None, lazy_pack=False, prune_dead_grads=False):
+def srgan_step(G, D, g_opt, d_opt, g_dp=None, d_dp=None, feature_extractor=None, lazy_pack=False, prune_dead_grads=False,
+               perceptual=False, vgg_weight=6e-3):
     """srgan.py:249-310 with [B,1] labels, as the eager closure of `srgan_segments` (see there for the arguments)."""
-    return eager_step(srgan_segments(G, D, g_opt, d_opt, g_dp, d_dp, lazy_pack, feature_extractor, prune_dead_grads))
+    return eager_step(srgan_segments(G, D, g_opt, d_opt, g_dp, d_dp, lazy_pack, feature_extractor, prune_dead_grads,
+                                     perceptual, vgg_weight))
 
 
 def srgan_segments(G, D, g_opt, d_opt, g_dp=None, d_dp=None, lazy_pack=False, feature_extractor=None,
-                   prune_dead_grads=False):
+                   prune_dead_grads=False, perceptual=False, vgg_weight=6e-3):
     """The adversarial step, srgan.py:249-310 with [B,1] labels, cut at its two gradient exchanges:
     [(D forward/backward, d_dp), (D update + G forward/backward, g_dp), (G update, None)] -> (d_loss, g_loss).
     As in the reference the D step back-propagates through G (G is not detached, srgan.py:279) and the G step accumulates
@@ -206,7 +208,12 @@ def srgan_segments(G, D, g_opt, d_opt, g_dp=None, d_dp=None, lazy_pack=False, fe
     `feature_extractor` (models.FeatureExtractor): adds the reference's VGG content term 6e-3 * MSE(vgg(norm(recon.data)),
     vgg(norm(hr)).detach()) to the reported G loss (srgan.py:301-308).  Both operands are detached in the reference,
     so the term changes the logged scalar only — never a gradient; without an extractor the step
-    returns mse + 1e-3 * GAN, which has the same gradients.
+    returns mse + 1e-3 * GAN, which has the same gradients.  `vgg_weight` replaces the 6e-3.
+    perceptual (NOT the reference's execution, off by default): the term stays attached to G's output,
+    g_loss = mse + 1e-3 * GAN + vgg_weight * ops.perceptual_loss(recon, hr, feature_extractor), and trains the generator
+    -- the loss the SRGAN paper is about.  It needs an extractor.  The extractor's parameters are frozen (data gradients
+    only; nothing joins a flat buffer or an exchange); the three gradients of recon are added by srk_axpby (ops.fork).
+    As in the logged term the batch arrives normalised and the term normalises it again (srgan.py:193-194,302-303).
     lazy_pack: the two zero_grad() calls skip the filter pack of a model whose plan is current (optim.zero_grad,
     repack="stale": 2 instead of 4 whole-model packs per step) -- for steps replayed by a graph that knows both
     FlatParams (GraphedFn(flats=[...]) / GraphedSegments).
@@ -219,6 +226,11 @@ def srgan_segments(G, D, g_opt, d_opt, g_dp=None, d_dp=None, lazy_pack=False, fe
     depends on how many layers share a launch); D's `.grad` then holds the D step's gradients only.  The flag is
     honoured by every form of the step, the split-graph data-parallel one included."""
     from . import utils
+    vgg_weight = float(vgg_weight)
+    if perceptual and feature_extractor is None:
+        raise ValueError("srgan step: perceptual=True needs a feature_extractor (models.FeatureExtractor)")
+    if not vgg_weight >= 0.0:
+        raise ValueError("srgan step: vgg_weight %r is negative" % (vgg_weight,))
     out = {}
     repack = "stale" if lazy_pack else "always"
     d_params = [p for p in D.parameters()] if prune_dead_grads else []
@@ -244,18 +256,27 @@ def srgan_segments(G, D, g_opt, d_opt, g_dp=None, d_dp=None, lazy_pack=False, fe
         d_opt.step()
         g_opt.zero_grad(repack=repack)
         recon = G(lr_img)
+        if perceptual:   # three consumers: their gradients are added by srk_axpby, not by autograd's ATen add
+            recon, rest = ops.fork(recon)
+            rest, recon_vgg = ops.fork(rest)
+        else:
+            rest = recon
         freeze_d(True)
         try:
             gan_loss = ops.bce_loss(D(recon), real)
         finally:
             freeze_d(False)
-        g_loss = ops.loss_sum(ops.mse_loss(recon, hr_img), gan_loss, 1.0, 1e-3)
-        if feature_extractor is not None:
+        g_loss = ops.loss_sum(ops.mse_loss(rest, hr_img), gan_loss, 1.0, 1e-3)
+        if perceptual:
+            vgg_loss = ops.weighted_term(lambda p, t: ops.perceptual_loss(p, t, feature_extractor), vgg_weight,
+                                         recon_vgg, hr_img)
+            g_loss = ops.loss_sum(g_loss, vgg_loss, 1.0, vgg_weight)
+        elif feature_extractor is not None:
             with torch.no_grad():   # srgan.py:301-305 (the inputs are already normalised once, as in the reference)
                 real_feature = feature_extractor(utils.norm(hr_img, vgg=True))
                 fake_feature = feature_extractor(utils.norm(recon.detach(), vgg=True))
                 vgg_loss = ops.mse_loss(fake_feature, real_feature)
-            g_loss = ops.loss_sum(g_loss, vgg_loss, 1.0, 6e-3)
+            g_loss = ops.loss_sum(g_loss, vgg_loss, 1.0, vgg_weight)
         _backward(g_loss, g_dp)
         out["g"] = g_loss
         return g_loss

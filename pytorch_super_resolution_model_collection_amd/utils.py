@@ -69,6 +69,21 @@ class SSIMLoss(torch.nn.Module):
         return ops.ssim_loss(pred, target.to(pred.device))
 
 
+class PerceptualLoss(torch.nn.Module):
+    """The VGG feature loss as a training loss (ops.perceptual_loss): MSE of `extractor`'s features of pred and target,
+    each normalised with the VGG constants first when `normalize`; the gradient reaches pred only.  [N,3,H,W] CUDA
+    tensors; extractor: models.FeatureExtractor (held as a sub-module, its parameters stay frozen)."""
+
+    def __init__(self, extractor, normalize=True):
+        super(PerceptualLoss, self).__init__()
+        self.extractor = extractor
+        self.normalize = bool(normalize)
+
+    def forward(self, pred, target):
+        from . import ops
+        return ops.perceptual_loss(pred, target.to(pred.device), self.extractor, self.normalize)
+
+
 def save_img_name(img_num, save_dir='', is_training=False):
     """utils.py:126-130: the file a result image goes to."""
     return save_dir + ('/SR_result_epoch_{:d}' if is_training else '/SR_result_{:d}').format(img_num) + '.png'
