@@ -10,26 +10,6 @@
 namespace srk {
 
 constexpr int kDrcnMaxBlocks = 1024;
-typedef float drcn_f4 __attribute__((ext_vector_type(4)));
-
-template <int V>
-struct Vec;
-template <>
-struct Vec<4> {
-  typedef drcn_f4 T;
-  static __device__ __forceinline__ T load(const float* p, size_t i) { return reinterpret_cast<const T*>(p)[i]; }
-  static __device__ __forceinline__ void store(float* p, size_t i, const T& v) { reinterpret_cast<T*>(p)[i] = v; }
-  static __device__ __forceinline__ float at(const T& v, int k) { return v[k]; }
-  static __device__ __forceinline__ void set(T& v, int k, float x) { v[k] = x; }
-};
-template <>
-struct Vec<1> {
-  typedef float T;
-  static __device__ __forceinline__ T load(const float* p, size_t i) { return p[i]; }
-  static __device__ __forceinline__ void store(float* p, size_t i, const T& v) { p[i] = v; }
-  static __device__ __forceinline__ float at(const T& v, int) { return v; }
-  static __device__ __forceinline__ void set(T& v, int, float x) { v = x; }
-};
 
 // sum_d w_d in the reference's order (the same value in every thread: w is read through the scalar cache)
 __device__ __forceinline__ float drcn_wsum(const float* __restrict__ w, int D) {
@@ -202,9 +182,7 @@ __global__ __launch_bounds__(256) void k_drcn_final(const double* __restrict__ p
   __shared__ double s01[2];
   const float S = drcn_wsum(w, D);
   for (int q = 0; q < D + 2; ++q) {
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += 256) acc += partials[(size_t)q * nparts + i];
-    const double tot = block_sum_256_d(acc, sm);
+    const double tot = sum_partials_256_d(partials + (size_t)q * nparts, nparts, sm);
     if (threadIdx.x == 0) {
       if (q < 2) {
         s01[q] = tot;
@@ -238,27 +216,15 @@ __global__ __launch_bounds__(256) void k_sumsq_partial(const float* __restrict__
 #pragma unroll
     for (int k = 0; k < V; ++k) acc += (double)Q::at(v, k) * (double)Q::at(v, k);
   }
-  const double tot = block_sum_256_d(acc, sm);
-  if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+  store_block_sum_256_d(acc, sm, partials + blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) void k_sumsq_final(const double* __restrict__ partials, int nparts, float scale,
                                                      float* __restrict__ out) {
   __shared__ double sm[4];
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += 256) acc += partials[i];
-  const double tot = block_sum_256_d(acc, sm);
+  const double tot = sum_partials_256_d(partials, nparts, sm);
   if (threadIdx.x == 0) *out = (float)((double)scale * tot);
 }
-
-static inline unsigned drcn_grid(size_t groups) {
-  size_t b = (groups + 255) / 256;
-  if (b < 1) b = 1;
-  if (b > (size_t)kDrcnMaxBlocks) b = kDrcnMaxBlocks;
-  return (unsigned)b;
-}
-
-static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace srk
 
@@ -275,11 +241,10 @@ extern "C" int srk_drcn_head_forward(const float* Y, const float* x, const float
   SRK_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0, "drcn_head_forward: bad dims");
   const size_t M = (size_t)N * C * H * W;
   hipStream_t s = (hipStream_t)stream;
-  if (M % 4 == 0 && aligned16(Y) && aligned16(x) && aligned16(out)) {
-    hipLaunchKernelGGL(k_drcn_combine<4>, dim3(drcn_grid(M / 4)), dim3(256), 0, s, Y, x, w, D, M, M / 4, out);
-  } else {
-    hipLaunchKernelGGL(k_drcn_combine<1>, dim3(drcn_grid(M)), dim3(256), 0, s, Y, x, w, D, M, M, out);
-  }
+  const bool vec = M % 4 == 0 && aligned16(Y, x, out);
+  const size_t groups = vec ? M / 4 : M;
+  hipLaunchKernelGGL(vec ? k_drcn_combine<4> : k_drcn_combine<1>, dim3(grid_for(groups, 256, kDrcnMaxBlocks)),
+                     dim3(256), 0, s, Y, x, w, D, M, groups, out);
   return check_launch("drcn_head_forward");
 }
 
@@ -295,9 +260,9 @@ extern "C" int srk_drcn_head_loss(const float* Y, const float* x, const float* t
   const size_t M = (size_t)N * C * H * W;
   hipStream_t s = (hipStream_t)stream;
   double* part = (double*)workspace;
-  const bool vec = M % 4 == 0 && aligned16(Y) && aligned16(x) && aligned16(target) && aligned16(out) && aligned16(dY);
+  const bool vec = M % 4 == 0 && aligned16(Y, x, target, out, dY);
   const size_t groups = vec ? M / 4 : M;
-  const unsigned nb = drcn_grid(groups);
+  const unsigned nb = grid_for(groups, 256, kDrcnMaxBlocks);
 #define SRK_DRCN_LOSS(DM, V)                                                                                          \
   hipLaunchKernelGGL((k_drcn_loss<DM, V>), dim3(nb), dim3(256), 0, s, Y, x, target, w, D, M, groups, alpha_dev,      \
                      grad_scale, out, dY, part)
@@ -327,9 +292,9 @@ extern "C" int srk_drcn_head_backward(const float* Y, const float* w, const floa
   const size_t M = (size_t)N * C * H * W;
   hipStream_t s = (hipStream_t)stream;
   double* part = (double*)workspace;
-  const bool vec = M % 4 == 0 && aligned16(Y) && aligned16(dout) && aligned16(dY);
+  const bool vec = M % 4 == 0 && aligned16(Y, dout, dY);
   const size_t groups = vec ? M / 4 : M;
-  const unsigned nb = drcn_grid(groups);
+  const unsigned nb = grid_for(groups, 256, kDrcnMaxBlocks);
 #define SRK_DRCN_BWD(DM, V)                                                                                           \
   hipLaunchKernelGGL((k_drcn_combine_bwd<DM, V>), dim3(nb), dim3(256), 0, s, Y, dout, w, D, M, groups, dY, part)
   if (vec) {
@@ -353,14 +318,11 @@ extern "C" size_t srk_sumsq_workspace_bytes(void) { return kDrcnMaxBlocks * size
 extern "C" int srk_sumsq(const float* p, size_t n, float scale, float* out, void* workspace, void* stream) {
   SRK_REQUIRE(p && out && workspace && n > 0, "sumsq: null pointer or empty");
   hipStream_t s = (hipStream_t)stream;
-  unsigned nb;
-  if (n % 4 == 0 && aligned16(p)) {
-    nb = drcn_grid(n / 4);
-    hipLaunchKernelGGL(k_sumsq_partial<4>, dim3(nb), dim3(256), 0, s, p, n / 4, (double*)workspace);
-  } else {
-    nb = drcn_grid(n);
-    hipLaunchKernelGGL(k_sumsq_partial<1>, dim3(nb), dim3(256), 0, s, p, n, (double*)workspace);
-  }
+  const bool vec = n % 4 == 0 && aligned16(p);
+  const size_t groups = vec ? n / 4 : n;
+  const unsigned nb = grid_for(groups, 256, kDrcnMaxBlocks);
+  hipLaunchKernelGGL(vec ? k_sumsq_partial<4> : k_sumsq_partial<1>, dim3(nb), dim3(256), 0, s, p, groups,
+                     (double*)workspace);
   hipLaunchKernelGGL(k_sumsq_final, dim3(1), dim3(256), 0, s, (const double*)workspace, (int)nb, scale, out);
   return check_launch("sumsq");
 }

@@ -5,12 +5,7 @@
 
 namespace srk {
 
-static inline unsigned ew_grid(size_t work_items, int per_block) {
-  size_t b = (work_items + per_block - 1) / per_block;
-  if (b < 1) b = 1;
-  if (b > 256 * 16) b = 256 * 16;
-  return (unsigned)b;
-}
+constexpr int kEwMaxBlocks = 256 * 16;   // grid cap of every kernel here but k_absmax
 
 // ---------------------------------------------------------------------------------------------
 // NCHW <-> NHWC: per image a [C][HW] <-> [HW][C] transpose through a padded LDS tile.
@@ -112,7 +107,6 @@ __global__ __launch_bounds__(256) void k_pixel_shuffle_tile(const float* __restr
   constexpr int RR = R * R, CIN = C * RR, RC = R * C;
   constexpr bool VX = CIN % 4 == 0;   // x-side runs start on 16-byte boundaries
   constexpr bool VY = RC % 4 == 0;    // y-side runs do
-  typedef float ps_f4 __attribute__((ext_vector_type(4)));
   extern __shared__ __attribute__((aligned(16))) float ps_sm[];
   int b = blockIdx.x;
   const int wt = b % nwt;
@@ -133,7 +127,7 @@ __global__ __launch_bounds__(256) void k_pixel_shuffle_tile(const float* __restr
   if (FWD) {
     if (VX) {
       for (int q = tid; q < nx / 4; q += 256)
-        reinterpret_cast<ps_f4*>(ps_sm)[q] = reinterpret_cast<const ps_f4*>(src + x_off)[q];
+        reinterpret_cast<f32x4*>(ps_sm)[q] = reinterpret_cast<const f32x4*>(src + x_off)[q];
     } else {
       for (int q = tid; q < nx; q += 256) ps_sm[q] = src[x_off + q];
     }
@@ -143,10 +137,10 @@ __global__ __launch_bounds__(256) void k_pixel_shuffle_tile(const float* __restr
       float* row = dst + y_row0 + (size_t)i * W * RC;
       if (VY) {
         for (int q = tid; q < ny / 4; q += 256) {
-          ps_f4 v;
+          f32x4 v;
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = ps_sm[word(i, 4 * q + e)];
-          reinterpret_cast<ps_f4*>(row)[q] = v;
+          reinterpret_cast<f32x4*>(row)[q] = v;
         }
       } else {
         for (int q = tid; q < ny; q += 256) row[q] = ps_sm[word(i, q)];
@@ -158,7 +152,7 @@ __global__ __launch_bounds__(256) void k_pixel_shuffle_tile(const float* __restr
       const float* row = src + y_row0 + (size_t)i * W * RC;
       if (VY) {
         for (int q = tid; q < ny / 4; q += 256) {
-          const ps_f4 v = reinterpret_cast<const ps_f4*>(row)[q];
+          const f32x4 v = reinterpret_cast<const f32x4*>(row)[q];
 #pragma unroll
           for (int e = 0; e < 4; ++e) ps_sm[word(i, 4 * q + e)] = v[e];
         }
@@ -169,7 +163,7 @@ __global__ __launch_bounds__(256) void k_pixel_shuffle_tile(const float* __restr
     __syncthreads();
     if (VX) {
       for (int q = tid; q < nx / 4; q += 256)
-        reinterpret_cast<ps_f4*>(dst + x_off)[q] = reinterpret_cast<const ps_f4*>(ps_sm)[q];
+        reinterpret_cast<f32x4*>(dst + x_off)[q] = reinterpret_cast<const f32x4*>(ps_sm)[q];
     } else {
       for (int q = tid; q < nx; q += 256) dst[x_off + q] = ps_sm[q];
     }
@@ -197,7 +191,7 @@ static bool ps_tile_launch(const float* src, float* dst, int N, int H, int W, bo
 
 // true: the tiled kernel took the call
 static bool ps_tile(const float* src, float* dst, int N, int H, int W, int C, int r, bool fwd, hipStream_t s) {
-  if ((((uintptr_t)src | (uintptr_t)dst) & 15) != 0 || env_int("SRK_PS_TILE", 1) == 0) return false;
+  if (!aligned16(src, dst) || env_int("SRK_PS_TILE", 1) == 0) return false;
   // (a side is vectorised only when its pixel size is a multiple of 16 bytes -- then every run start is aligned)
   if ((long)W * C * r * r >= (1L << 30)) return false;
 #define SRK_PS_CASE(RV, CV) if (r == RV && C == CV) return ps_tile_launch<RV, CV>(src, dst, N, H, W, fwd, s);
@@ -221,17 +215,11 @@ __global__ __launch_bounds__(256) void k_act_fwd(const float* __restrict__ x, fl
   const bool vec_ok = (channels % 4 == 0) || !per_ch;
   if (vec_ok) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-      float4 v = reinterpret_cast<const float4*>(x)[i];
-      float a0 = a, a1 = a, a2 = a, a3 = a;
-      if (per_ch) {
-        const int c = (int)((i * 4) % channels);
-        a0 = pw[c]; a1 = pw[c + 1]; a2 = pw[c + 2]; a3 = pw[c + 3];
-      }
-      v.x = act_apply(v.x, act, a0);
-      v.y = act_apply(v.y, act, a1);
-      v.z = act_apply(v.z, act, a2);
-      v.w = act_apply(v.w, act, a3);
-      reinterpret_cast<float4*>(y)[i] = v;
+      f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
+      const int c = per_ch ? (int)((i * 4) % channels) : 0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v[e] = act_apply(v[e], act, per_ch ? pw[c + e] : a);
+      reinterpret_cast<f32x4*>(y)[i] = v;
     }
     for (size_t i = n4 * 4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
       y[i] = act_apply(x[i], act, per_ch ? pw[i % channels] : a);
@@ -241,66 +229,60 @@ __global__ __launch_bounds__(256) void k_act_fwd(const float* __restrict__ x, fl
   }
 }
 
-// dx = dy * act'(.) ; PReLU slope gradient reduced per block then atomically added.
-__global__ __launch_bounds__(256) void k_act_bwd(const float* __restrict__ dy, const float* __restrict__ saved,
-                                                 float* __restrict__ dx, size_t n, int channels, int act, float slope,
-                                                 const float* __restrict__ pw, int pn, float* __restrict__ dpw) {
-  __shared__ float sm[4];
-  const bool per_ch = (act == SRK_ACT_PRELU && pn > 1);
-  float a = slope;
-  if (act == SRK_ACT_PRELU && !per_ch) a = pw[0];
-  float dslope = 0.f;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-    const float g = dy[i], s = saved[i];
-    float d;
-    switch (act) {
-      case SRK_ACT_RELU: d = s > 0.f ? g : 0.f; break;
-      case SRK_ACT_LRELU: d = s > 0.f ? g : g * slope; break;
-      case SRK_ACT_PRELU: {
-        const float ai = per_ch ? pw[i % channels] : a;
-        d = s > 0.f ? g : g * ai;
-        const float ds = s > 0.f ? 0.f : g * s;
-        if (per_ch) {
-          if (ds != 0.f) atomicAdd(&dpw[i % channels], ds);
-        } else {
-          dslope += ds;
-        }
-        break;
-      }
-      case SRK_ACT_TANH: d = g * (1.f - s * s); break;
-      case SRK_ACT_SIGMOID: d = g * s * (1.f - s); break;
-      default: d = g;
-    }
-    dx[i] = d;
-  }
-  if (act == SRK_ACT_PRELU && !per_ch && dpw) {
-    const float tot = block_sum_256(dslope, sm);
-    if (threadIdx.x == 0 && tot != 0.f) atomicAdd(dpw, tot);
+// One element of the backward: returns d = dy * act'(.), `ds` = its contribution to a PReLU slope's gradient.
+// `a`: the negative-side slope.  RELU_FAMILY (ReLU / LeakyReLU / PReLU alone, known at compile time) is the one
+// expression s > 0 ? g : g * a with a = 0 for ReLU; its zeros there carry g's sign, the general form's are +0.
+template <bool RELU_FAMILY>
+__device__ __forceinline__ float act_grad(int act, float g, float s, float a, float& ds) {
+  ds = act == SRK_ACT_PRELU ? (s > 0.f ? 0.f : g * s) : 0.f;
+  if (RELU_FAMILY) return s > 0.f ? g : g * a;
+  switch (act) {
+    case SRK_ACT_RELU: return s > 0.f ? g : 0.f;
+    case SRK_ACT_LRELU:
+    case SRK_ACT_PRELU: return s > 0.f ? g : g * a;
+    case SRK_ACT_TANH: return g * (1.f - s * s);
+    case SRK_ACT_SIGMOID: return g * s * (1.f - s);
+    default: return g;
   }
 }
 
-// 16-byte version of k_act_bwd for the activations the nets use in training (ReLU / LeakyReLU / single-slope PReLU):
-// one float4 per thread and pass.  The scalar kernel walks 8 elements per thread one dependent 4-byte load pair at a
-// time (13 us for the 1 M-element tensors of the SRGAN generator; 65 calls per adversarial step).
-__global__ __launch_bounds__(256) void k_act_bwd4(const float* __restrict__ dy, const float* __restrict__ saved,
-                                                  float* __restrict__ dx, size_t n4, int act, float slope,
-                                                  const float* __restrict__ pw, float* __restrict__ dpw) {
-  typedef float af4 __attribute__((ext_vector_type(4)));
+// dx = dy * act'(.) ; the PReLU slope gradient is reduced per block then atomically added (one slope), or added per
+// element (one slope per channel).  V = 1 takes every activation; V = 4 is the form for the activations the nets train
+// with (ReLU / LeakyReLU / single-slope PReLU on n % 4 == 0 aligned elements): one 16-byte access per thread and pass,
+// where the 4-byte form walks 8 elements per thread one dependent load pair at a time (13 us for the 1 M-element
+// tensors of the SRGAN generator; 65 calls per adversarial step).
+template <int V>
+__global__ __launch_bounds__(256) void k_act_bwd(const float* __restrict__ dy, const float* __restrict__ saved,
+                                                 float* __restrict__ dx, size_t groups, int channels, int act,
+                                                 float slope, const float* __restrict__ pw, int pn,
+                                                 float* __restrict__ dpw) {
+  typedef Vec<V> Q;
+  constexpr bool RELU_FAMILY = V == 4;   // (srk_act_backward launches the 16-byte form for nothing else)
   __shared__ float sm[4];
-  float a = act == SRK_ACT_RELU ? 0.f : slope;
-  if (act == SRK_ACT_PRELU) a = pw[0];
+  const bool per_ch = !RELU_FAMILY && act == SRK_ACT_PRELU && pn > 1;
+  float a = RELU_FAMILY && act == SRK_ACT_RELU ? 0.f : slope;
+  if (act == SRK_ACT_PRELU && !per_ch) a = pw[0];
   float dslope = 0.f;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    const af4 g = reinterpret_cast<const af4*>(dy)[i], s = reinterpret_cast<const af4*>(saved)[i];
-    af4 d;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < groups; i += (size_t)gridDim.x * 256) {
+    const typename Q::T g = Q::load(dy, i), s = Q::load(saved, i);
+    typename Q::T d;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      d[e] = s[e] > 0.f ? g[e] : g[e] * a;
-      if (act == SRK_ACT_PRELU) dslope += s[e] > 0.f ? 0.f : g[e] * s[e];
+    for (int e = 0; e < V; ++e) {
+      float ae = a, ds;
+      int c = 0;
+      if constexpr (V == 1) {
+        if (per_ch) c = (int)(i % channels), ae = pw[c];
+      }
+      Q::set(d, e, act_grad<RELU_FAMILY>(act, Q::at(g, e), Q::at(s, e), ae, ds));
+      if (per_ch) {
+        if (ds != 0.f) atomicAdd(&dpw[c], ds);
+      } else if (act == SRK_ACT_PRELU) {
+        dslope += ds;
+      }
     }
-    reinterpret_cast<af4*>(dx)[i] = d;
+    Q::store(dx, i, d);
   }
-  if (act == SRK_ACT_PRELU && dpw) {
+  if (act == SRK_ACT_PRELU && !per_ch && dpw) {
     const float tot = block_sum_256(dslope, sm);
     if (threadIdx.x == 0 && tot != 0.f) atomicAdd(dpw, tot);
   }
@@ -310,14 +292,8 @@ __global__ __launch_bounds__(256) void k_axpby(const float* __restrict__ a, cons
                                                float* __restrict__ out, size_t n, float alpha, float beta) {
   const size_t n4 = n / 4;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    const float4 u = reinterpret_cast<const float4*>(a)[i];
-    const float4 v = reinterpret_cast<const float4*>(b)[i];
-    float4 o;
-    o.x = alpha * u.x + beta * v.x;
-    o.y = alpha * u.y + beta * v.y;
-    o.z = alpha * u.z + beta * v.z;
-    o.w = alpha * u.w + beta * v.w;
-    reinterpret_cast<float4*>(out)[i] = o;
+    const f32x4 u = reinterpret_cast<const f32x4*>(a)[i], v = reinterpret_cast<const f32x4*>(b)[i];
+    reinterpret_cast<f32x4*>(out)[i] = alpha * u + beta * v;
   }
   for (size_t i = n4 * 4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
     out[i] = alpha * a[i] + beta * b[i];
@@ -337,10 +313,9 @@ namespace srk {
 __global__ __launch_bounds__(256) void k_absmax(const float* __restrict__ x, size_t n, float* __restrict__ slots) {
   float a = 0.f;
   const size_t n4 = n / 4;
-  typedef float am_f4 __attribute__((ext_vector_type(4)));
-  if (((uintptr_t)x & 15) == 0) {
+  if (aligned16(x)) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-      const am_f4 v = reinterpret_cast<const am_f4*>(x)[i];
+      const f32x4 v = reinterpret_cast<const f32x4*>(x)[i];
       a = fmaxf(fmaxf(a, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
     }
     for (size_t i = n4 * 4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) a = fmaxf(a, fabsf(x[i]));
@@ -364,7 +339,8 @@ using namespace srk;
 
 extern "C" int srk_scale_dev(const float* x, const float* alpha_dev, float* out, size_t n, void* stream) {
   SRK_REQUIRE(x && alpha_dev && out && n > 0, "scale_dev: null pointer or empty");
-  hipLaunchKernelGGL(k_scale_dev, dim3(ew_grid(n, 256 * 4)), dim3(256), 0, (hipStream_t)stream, x, alpha_dev, out, n);
+  hipLaunchKernelGGL(k_scale_dev, dim3(grid_for(n, 256 * 4, kEwMaxBlocks)), dim3(256), 0, (hipStream_t)stream, x,
+                     alpha_dev, out, n);
   return check_launch("scale_dev");
 }
 
@@ -380,8 +356,8 @@ extern "C" int srk_pixel_shuffle_forward(const float* x, float* y, int N, int H,
   SRK_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && r >= 1, "pixel_shuffle_forward: bad dims");
   const size_t total = (size_t)N * H * W * C * r * r;
   if (ps_tile(x, y, N, H, W, C, r, true, (hipStream_t)stream)) return check_launch("pixel_shuffle_forward");
-  hipLaunchKernelGGL(k_pixel_shuffle<true>, dim3(ew_grid(total, 256 * 4)), dim3(256), 0, (hipStream_t)stream, x, y, H,
-                     W, C, r, total);
+  hipLaunchKernelGGL(k_pixel_shuffle<true>, dim3(grid_for(total, 256 * 4, kEwMaxBlocks)), dim3(256), 0,
+                     (hipStream_t)stream, x, y, H, W, C, r, total);
   return check_launch("pixel_shuffle_forward");
 }
 extern "C" int srk_pixel_shuffle_backward(const float* dy, float* dx, int N, int H, int W, int C, int r,
@@ -390,8 +366,8 @@ extern "C" int srk_pixel_shuffle_backward(const float* dy, float* dx, int N, int
   SRK_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && r >= 1, "pixel_shuffle_backward: bad dims");
   const size_t total = (size_t)N * H * W * C * r * r;
   if (ps_tile(dy, dx, N, H, W, C, r, false, (hipStream_t)stream)) return check_launch("pixel_shuffle_backward");
-  hipLaunchKernelGGL(k_pixel_shuffle<false>, dim3(ew_grid(total, 256 * 4)), dim3(256), 0, (hipStream_t)stream, dy, dx,
-                     H, W, C, r, total);
+  hipLaunchKernelGGL(k_pixel_shuffle<false>, dim3(grid_for(total, 256 * 4, kEwMaxBlocks)), dim3(256), 0,
+                     (hipStream_t)stream, dy, dx, H, W, C, r, total);
   return check_launch("pixel_shuffle_backward");
 }
 
@@ -403,9 +379,9 @@ extern "C" int srk_act_forward(const float* x, float* y, size_t n, int channels,
     SRK_REQUIRE(prelu_weight && prelu_n >= 1, "act_forward: PReLU needs its weight");
     SRK_REQUIRE(prelu_n == 1 || prelu_n == channels, "act_forward: prelu_n %d != channels %d", prelu_n, channels);
   }
-  SRK_REQUIRE(((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0), "act_forward: pointers must be 16-byte aligned");
-  hipLaunchKernelGGL(k_act_fwd, dim3(ew_grid(n, 256 * 8)), dim3(256), 0, (hipStream_t)stream, x, y, n, channels, act,
-                     slope, prelu_weight, prelu_n);
+  SRK_REQUIRE(aligned16(x, y), "act_forward: pointers must be 16-byte aligned");
+  hipLaunchKernelGGL(k_act_fwd, dim3(grid_for(n, 256 * 8, kEwMaxBlocks)), dim3(256), 0, (hipStream_t)stream, x, y, n,
+                     channels, act, slope, prelu_weight, prelu_n);
   return check_launch("act_forward");
 }
 
@@ -418,28 +394,24 @@ extern "C" int srk_act_backward(const float* dy, const float* saved, float* dx, 
     SRK_REQUIRE(prelu_n == 1 || prelu_n == channels, "act_backward: prelu_n %d != channels %d", prelu_n, channels);
   }
   const bool relu_family = act == SRK_ACT_RELU || act == SRK_ACT_LRELU || (act == SRK_ACT_PRELU && prelu_n == 1);
-  if (relu_family && (n & 3) == 0 && (((uintptr_t)dy | (uintptr_t)saved | (uintptr_t)dx) & 15) == 0) {
-    hipLaunchKernelGGL(k_act_bwd4, dim3(ew_grid(n / 4, 256 * 2)), dim3(256), 0, (hipStream_t)stream, dy, saved, dx, n / 4,
-                       act, slope, prelu_weight, dprelu);
-    return check_launch("act_backward");
-  }
-  hipLaunchKernelGGL(k_act_bwd, dim3(ew_grid(n, 256 * 8)), dim3(256), 0, (hipStream_t)stream, dy, saved, dx, n,
-                     channels, act, slope, prelu_weight, prelu_n, dprelu);
+  const bool vec = relu_family && (n & 3) == 0 && aligned16(dy, saved, dx);
+  const size_t groups = vec ? n / 4 : n;
+  const unsigned nb = vec ? grid_for(groups, 256 * 2, kEwMaxBlocks) : grid_for(groups, 256 * 8, kEwMaxBlocks);
+  hipLaunchKernelGGL(vec ? k_act_bwd<4> : k_act_bwd<1>, dim3(nb), dim3(256), 0, (hipStream_t)stream, dy, saved, dx,
+                     groups, channels, act, slope, prelu_weight, prelu_n, dprelu);
   return check_launch("act_backward");
 }
 
 extern "C" int srk_axpby(const float* a, const float* b, float* out, size_t n, float alpha, float beta, void* stream) {
   SRK_REQUIRE(a && b && out && n > 0, "axpby: null pointer or empty");
-  SRK_REQUIRE(((uintptr_t)a % 16 == 0) && ((uintptr_t)b % 16 == 0) && ((uintptr_t)out % 16 == 0),
-              "axpby: pointers must be 16-byte aligned");
-  hipLaunchKernelGGL(k_axpby, dim3(ew_grid(n, 256 * 8)), dim3(256), 0, (hipStream_t)stream, a, b, out, n, alpha, beta);
+  SRK_REQUIRE(aligned16(a, b, out), "axpby: pointers must be 16-byte aligned");
+  hipLaunchKernelGGL(k_axpby, dim3(grid_for(n, 256 * 8, kEwMaxBlocks)), dim3(256), 0, (hipStream_t)stream, a, b, out, n,
+                     alpha, beta);
   return check_launch("axpby");
 }
 
 extern "C" int srk_absmax(const float* x, size_t n, float* amax_slots, void* stream) {
   SRK_REQUIRE(x && amax_slots && n > 0, "absmax: null pointer or empty");
-  size_t b = (n + 256 * 16 - 1) / (256 * 16);
-  if (b > 1024) b = 1024;
-  hipLaunchKernelGGL(k_absmax, dim3((unsigned)b), dim3(256), 0, (hipStream_t)stream, x, n, amax_slots);
+  hipLaunchKernelGGL(k_absmax, dim3(grid_for(n, 256 * 16, 1024)), dim3(256), 0, (hipStream_t)stream, x, n, amax_slots);
   return check_launch("absmax");
 }

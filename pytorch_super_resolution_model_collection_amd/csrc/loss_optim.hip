@@ -11,6 +11,15 @@ constexpr int kMaxPartials = 1024;  // doubles
 //   pred/dpred : NHWC dense, element e = ((n*H+h)*W+w)*C + c
 //   target     : element strides (sn, sc, sh, sw); `contig` = target is NHWC dense too.
 // ---------------------------------------------------------------------------------------------
+// a * b + c in two roundings whatever the context.  Left to the compiler's contraction, whether an expression becomes an fma
+// depends on what else the optimizer finds next to it (a packed multiply takes the product away), so the 4-byte and the
+// 16-byte form of one source line could round differently; the operations below are pinned to what both forms have
+// always computed.
+__device__ __forceinline__ float mul_then_add(float a, float b, float c) {
+#pragma clang fp contract(off)
+  return a * b + c;
+}
+
 __device__ __forceinline__ void loss_term(int kind, float p, float t, float eps, float& val, float& grad) {
   const float d = p - t;
   switch (kind) {
@@ -23,7 +32,7 @@ __device__ __forceinline__ void loss_term(int kind, float p, float t, float eps,
       grad = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
       break;
     case SRK_LOSS_CHARBONNIER: {
-      const float e = sqrtf(d * d + eps);  // lapsrn.py:81-85
+      const float e = sqrtf(__builtin_fmaf(d, d, eps));  // lapsrn.py:81-85 (the fma spelled out: see mul_then_add)
       val = e;
       grad = d / e;
       break;
@@ -37,200 +46,149 @@ __device__ __forceinline__ void loss_term(int kind, float p, float t, float eps,
   }
 }
 
+// One float (V = 1) or four (V = 4: dense, aligned tensors, pred, target and dpred in one layout) per thread and pass.  Each
+// form keeps its own summation order: a thread adds its elements in lane order into one float, so the 16-byte form's
+// partials are those of 4-element groups.  Only the 4-byte form walks a strided target.
+template <int V>
 __global__ __launch_bounds__(256) void k_loss_partial(int kind, const float* __restrict__ pred,
                                                       const float* __restrict__ target, int64_t sn, int64_t sc,
                                                       int64_t sh, int64_t sw, int contig, int C, int H, int W,
-                                                      size_t total, float eps, float gscale,
+                                                      size_t groups, float eps, float gscale,
                                                       float* __restrict__ dpred, double* __restrict__ partials) {
+  typedef Vec<V> Q;
   __shared__ double sm[4];
   float acc = 0.f;
-  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < groups; e += (size_t)gridDim.x * 256) {
     size_t ti = e;
-    if (!contig) {
-      const int c = (int)(e % C);
-      size_t t = e / C;
-      const int w = (int)(t % W);
-      t /= W;
-      const int h = (int)(t % H);
-      const size_t n = t / H;
-      ti = n * sn + c * sc + h * sh + w * sw;
+    if constexpr (V == 1) {
+      if (!contig) {
+        const int c = (int)(e % C);
+        size_t t = e / C;
+        const int w = (int)(t % W);
+        t /= W;
+        const int h = (int)(t % H);
+        const size_t n = t / H;
+        ti = n * sn + c * sc + h * sh + w * sw;
+      }
     }
-    float v, g;
-    loss_term(kind, pred[e], target[ti], eps, v, g);
-    acc += v;
-    if (dpred) dpred[e] = g * gscale;
-  }
-  const double tot = block_sum_256_d((double)acc, sm);
-  if (threadIdx.x == 0) partials[blockIdx.x] = tot;
-}
-
-// 16-byte form for dense, aligned tensors (pred, target and dpred in one layout): four elements per thread and pass
-typedef float loss_f4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void k_loss_partial4(int kind, const float* __restrict__ pred,
-                                                       const float* __restrict__ target, size_t total4, float eps,
-                                                       float gscale, float* __restrict__ dpred,
-                                                       double* __restrict__ partials) {
-  __shared__ double sm[4];
-  float acc = 0.f;
-  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total4; e += (size_t)gridDim.x * 256) {
-    const loss_f4 p = reinterpret_cast<const loss_f4*>(pred)[e], t = reinterpret_cast<const loss_f4*>(target)[e];
-    loss_f4 g;
+    const typename Q::T p = Q::load(pred, e), t = Q::load(target, ti);
+    typename Q::T g;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < V; ++k) {
       float v, gg;
-      loss_term(kind, p[k], t[k], eps, v, gg);
+      loss_term(kind, Q::at(p, k), Q::at(t, k), eps, v, gg);
       acc += v;
-      g[k] = gg * gscale;
+      Q::set(g, k, gg * gscale);
     }
-    if (dpred) reinterpret_cast<loss_f4*>(dpred)[e] = g;
+    if (dpred) Q::store(dpred, e, g);
   }
-  const double tot = block_sum_256_d((double)acc, sm);
-  if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+  store_block_sum_256_d((double)acc, sm, partials + blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) void k_loss_final(const double* __restrict__ partials, int nparts, double inv_count,
                                                     float* __restrict__ loss) {
   __shared__ double sm[4];
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += 256) acc += partials[i];
-  const double tot = block_sum_256_d(acc, sm);
+  const double tot = sum_partials_256_d(partials, nparts, sm);
   if (threadIdx.x == 0) *loss = (float)(tot * inv_count);
 }
 
 // ---------------------------------------------------------------------------------------------
-// Optimizers
+// Optimizers.  V = 4 (n % 4 == 0, aligned buffers): the same operations per element, four elements per thread and pass
+// (SRGAN-D's 23 M parameters under SGD: 184 -> ~100 us; the 4-byte loop moved 2.5 TB/s).
 // ---------------------------------------------------------------------------------------------
+template <int V>
 __global__ __launch_bounds__(256) void k_sgd(float* __restrict__ p, const float* __restrict__ g,
-                                             float* __restrict__ buf, size_t n, float lr, float mom, float wd,
+                                             float* __restrict__ buf, size_t groups, float lr, float mom, float wd,
                                              int nesterov, int first, const float* __restrict__ lr_dev,
                                              const float* __restrict__ gs_dev) {
+  typedef Vec<V> Q;
   if (lr_dev) lr = *lr_dev;
   const float gs = gs_dev ? *gs_dev : 1.f;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-    float pi = p[i];
-    float d = g[i] * gs;
-    if (wd != 0.f) d += wd * pi;
-    if (mom != 0.f) {
-      float b = first ? d : buf[i] * mom + d;
-      buf[i] = b;
-      d = nesterov ? d + mom * b : b;
-    }
-    p[i] = pi - lr * d;
-  }
-}
-
-// 16-byte form of k_sgd (n % 4 == 0, aligned buffers): the same operations per element, four elements per thread and pass
-// (SRGAN-D's 23 M parameters: 184 -> ~100 us; the scalar loop moved 2.5 TB/s)
-typedef float sgd_f4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void k_sgd4(float* __restrict__ p, const float* __restrict__ g,
-                                              float* __restrict__ buf, size_t n4, float lr, float mom, float wd,
-                                              int nesterov, int first, const float* __restrict__ lr_dev,
-                                              const float* __restrict__ gs_dev) {
-  if (lr_dev) lr = *lr_dev;
-  const float gs = gs_dev ? *gs_dev : 1.f;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    sgd_f4 pi = reinterpret_cast<const sgd_f4*>(p)[i];
-    const sgd_f4 gi = reinterpret_cast<const sgd_f4*>(g)[i];
-    sgd_f4 bi = {0.f, 0.f, 0.f, 0.f};
-    if (mom != 0.f && !first) bi = reinterpret_cast<const sgd_f4*>(buf)[i];
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < groups; i += (size_t)gridDim.x * 256) {
+    typename Q::T pi = Q::load(p, i);
+    const typename Q::T gi = Q::load(g, i);
+    typename Q::T bi = {};
+    if (mom != 0.f && !first) bi = Q::load(buf, i);   // (the first step must not read the buffer)
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float d = gi[e] * gs;
-      if (wd != 0.f) d += wd * pi[e];
+    for (int e = 0; e < V; ++e) {
+      float d = Q::at(gi, e) * gs;
+      if (wd != 0.f) d = mul_then_add(wd, Q::at(pi, e), d);   // (torch: grad.add(param, alpha = wd), a multiply and an add)
       if (mom != 0.f) {
-        const float b = first ? d : bi[e] * mom + d;
-        bi[e] = b;
+        const float b = first ? d : Q::at(bi, e) * mom + d;
+        Q::set(bi, e, b);
         d = nesterov ? d + mom * b : b;
       }
-      pi[e] = pi[e] - lr * d;
+      Q::set(pi, e, Q::at(pi, e) - lr * d);
     }
-    if (mom != 0.f) reinterpret_cast<sgd_f4*>(buf)[i] = bi;
-    reinterpret_cast<sgd_f4*>(p)[i] = pi;
+    if (mom != 0.f) Q::store(buf, i, bi);
+    Q::store(p, i, pi);
   }
 }
 
-// The step counter is advanced by the kernel itself (it used to be a one-thread launch of its own in front, ~5 us of a
-// 1.2 ms train step): every block reads the count of the PREVIOUS steps before anything else and works with count + 1;
-// the block that finishes last -- a ticket in step_dev[1]: it has seen every other block's arrival, so every block has
-// read the old count -- stores count + 1 and clears the ticket.  The count is consumed by the next launch only.
-__global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float* __restrict__ g,
-                                              float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
-                                              float b1, float b2, float eps, float wd,
-                                              int32_t* __restrict__ step_dev, const float* __restrict__ lr_dev,
-                                              const float* __restrict__ gs_dev) {
-  if (lr_dev) lr = *lr_dev;
-  const float gs = gs_dev ? *gs_dev : 1.f;
-  const int32_t t_i = __hip_atomic_load(step_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
-  const float t = (float)t_i;
+// Adam's step counter is advanced by the kernel itself (it used to be a one-thread launch of its own in front, ~5 us of a
+// 1.2 ms train step): every block reads the count of the PREVIOUS steps before anything else (adam_begin) and works with
+// count + 1; the block that finishes last -- a ticket in step_dev[1]: it has seen every other block's arrival, so every
+// block has read the old count -- stores count + 1 and clears the ticket (adam_arrive).  The count is consumed by the
+// next launch only.
+struct AdamStep {
+  int32_t count;            // this step's number, 1-based
+  float step_size, bc2_sqrt;
+};
+__device__ __forceinline__ AdamStep adam_begin(const int32_t* __restrict__ step_dev, float lr, float b1, float b2) {
+  AdamStep a;
+  a.count = __hip_atomic_load(step_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+  const float t = (float)a.count;
   // torch/optim/adam.py (_single_tensor_adam): bias corrections, step_size, denom
   const float bc1 = 1.f - powf(b1, t);
   const float bc2 = 1.f - powf(b2, t);
-  const float step_size = lr / bc1;
-  const float bc2_sqrt = sqrtf(bc2);
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-    float pi = p[i];
-    float gi = g[i] * gs;
-    if (wd != 0.f) gi += wd * pi;
-    float mi = m[i];
-    mi = mi + (1.f - b1) * (gi - mi);  // exp_avg.lerp_(grad, 1 - beta1)
-    float vi = v[i] * b2 + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = pi - step_size * (mi / denom);
-  }
+  a.step_size = lr / bc1;
+  a.bc2_sqrt = sqrtf(bc2);
+  return a;
+}
+__device__ __forceinline__ void adam_arrive(int32_t* __restrict__ step_dev, int32_t count) {
   __syncthreads();   // (the whole block has read the old count)
   if (threadIdx.x == 0) {
     const int32_t arrived = atomicAdd(step_dev + 1, 1);
     if (arrived == (int32_t)gridDim.x - 1) {
-      __hip_atomic_store(step_dev, t_i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(step_dev, count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(step_dev + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
 }
 
-// 16-byte form of k_adam (n % 4 == 0, aligned buffers): the same operations per element, four elements per thread and
-// pass, and at most two blocks per CU -- the arrival ticket is one atomic per block on one word, and ~740 of them in the
-// scalar kernel's grid made the folded step counter cost what the separate launch had (EDSR: 19.4 vs 14.5 + 2.8 us).
-typedef float adam_f4 __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void k_adam4(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                               float* __restrict__ v, size_t n4, float lr, float b1, float b2, float eps,
-                                               float wd, int32_t* __restrict__ step_dev, const float* __restrict__ lr_dev,
-                                               const float* __restrict__ gs_dev) {
+// The 16-byte form runs at most two blocks per CU (srk_adam_step): the arrival ticket is one atomic per block on one
+// word, and ~740 of them in the 4-byte form's grid made the folded step counter cost what the separate launch had
+// (EDSR: 19.4 vs 14.5 + 2.8 us).
+template <int V>
+__global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float* __restrict__ g,
+                                              float* __restrict__ m, float* __restrict__ v, size_t groups, float lr,
+                                              float b1, float b2, float eps, float wd,
+                                              int32_t* __restrict__ step_dev, const float* __restrict__ lr_dev,
+                                              const float* __restrict__ gs_dev) {
+  typedef Vec<V> Q;
   if (lr_dev) lr = *lr_dev;
   const float gs = gs_dev ? *gs_dev : 1.f;
-  const int32_t t_i = __hip_atomic_load(step_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
-  const float t = (float)t_i;
-  const float bc1 = 1.f - powf(b1, t);
-  const float bc2 = 1.f - powf(b2, t);
-  const float step_size = lr / bc1;
-  const float bc2_sqrt = sqrtf(bc2);
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    adam_f4 pi = reinterpret_cast<const adam_f4*>(p)[i];
-    const adam_f4 gi4 = reinterpret_cast<const adam_f4*>(g)[i];
-    adam_f4 mi = reinterpret_cast<const adam_f4*>(m)[i];
-    adam_f4 vi = reinterpret_cast<const adam_f4*>(v)[i];
+  const AdamStep st = adam_begin(step_dev, lr, b1, b2);
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < groups; i += (size_t)gridDim.x * 256) {
+    typename Q::T pi = Q::load(p, i);
+    const typename Q::T gv = Q::load(g, i);
+    typename Q::T mi = Q::load(m, i), vi = Q::load(v, i);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float gi = gi4[e] * gs;
-      if (wd != 0.f) gi += wd * pi[e];
-      mi[e] = mi[e] + (1.f - b1) * (gi - mi[e]);
-      vi[e] = vi[e] * b2 + (1.f - b2) * gi * gi;
-      const float denom = sqrtf(vi[e]) / bc2_sqrt + eps;
-      pi[e] = pi[e] - step_size * (mi[e] / denom);
+    for (int e = 0; e < V; ++e) {
+      float gi = Q::at(gv, e) * gs;
+      if (wd != 0.f) gi += wd * Q::at(pi, e);
+      const float me = Q::at(mi, e) + (1.f - b1) * (gi - Q::at(mi, e));   // exp_avg.lerp_(grad, 1 - beta1)
+      const float ve = Q::at(vi, e) * b2 + (1.f - b2) * gi * gi;
+      Q::set(mi, e, me);
+      Q::set(vi, e, ve);
+      const float denom = sqrtf(ve) / st.bc2_sqrt + eps;
+      Q::set(pi, e, Q::at(pi, e) - st.step_size * (me / denom));
     }
-    reinterpret_cast<adam_f4*>(m)[i] = mi;
-    reinterpret_cast<adam_f4*>(v)[i] = vi;
-    reinterpret_cast<adam_f4*>(p)[i] = pi;
+    Q::store(m, i, mi);
+    Q::store(v, i, vi);
+    Q::store(p, i, pi);
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int32_t arrived = atomicAdd(step_dev + 1, 1);
-    if (arrived == (int32_t)gridDim.x - 1) {
-      __hip_atomic_store(step_dev, t_i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(step_dev + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  adam_arrive(step_dev, st.count);
 }
 
 __global__ __launch_bounds__(256) void k_sqsum_partial(const float* __restrict__ g, size_t n,
@@ -241,16 +199,13 @@ __global__ __launch_bounds__(256) void k_sqsum_partial(const float* __restrict__
     const float x = g[i];
     acc += x * x;
   }
-  const double tot = block_sum_256_d((double)acc, sm);
-  if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+  store_block_sum_256_d((double)acc, sm, partials + blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) void k_norm_final(const double* __restrict__ partials, int nparts, float max_norm,
                                                     float* __restrict__ norm_out, float* __restrict__ scale_out) {
   __shared__ double sm[4];
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += 256) acc += partials[i];
-  const double tot = block_sum_256_d(acc, sm);
+  const double tot = sum_partials_256_d(partials, nparts, sm);
   if (threadIdx.x == 0) {
     const float nrm = (float)sqrt(tot);
     if (norm_out) *norm_out = nrm;
@@ -259,13 +214,6 @@ __global__ __launch_bounds__(256) void k_norm_final(const double* __restrict__ p
       *scale_out = c < 1.f ? c : 1.f;
     }
   }
-}
-
-static inline unsigned red_grid(size_t n) {
-  size_t b = (n + 256 * 8 - 1) / (256 * 8);
-  if (b < 1) b = 1;
-  if (b > kMaxPartials) b = kMaxPartials;
-  return (unsigned)b;
 }
 
 }  // namespace srk
@@ -289,17 +237,12 @@ extern "C" int srk_loss_forward_backward(int kind, const float* pred, const floa
              (target_strides[2] == sh || H == 1) && (target_strides[3] == sw || W == 1);
     sn = target_strides[0]; sc = target_strides[1]; sh = target_strides[2]; sw = target_strides[3];
   }
-  unsigned nb = red_grid(total);
   hipStream_t s = (hipStream_t)stream;
-  const bool vec = contig && (total & 3) == 0 && (((uintptr_t)pred | (uintptr_t)target | (uintptr_t)dpred) & 15) == 0;
-  if (vec) {   // (the summation order differs from the scalar kernel's: partials of 4-element groups)
-    size_t b = (total / 4 + 255) / 256;
-    nb = (unsigned)(b > kMaxPartials ? kMaxPartials : (b < 1 ? 1 : b));
-    hipLaunchKernelGGL(k_loss_partial4, dim3(nb), dim3(256), 0, s, kind, pred, target, total / 4, eps,
-                       grad_scale / (float)total, dpred, (double*)workspace);
-  } else
-  hipLaunchKernelGGL(k_loss_partial, dim3(nb), dim3(256), 0, s, kind, pred, target, sn, sc, sh, sw, contig, C, H, W,
-                     total, eps, grad_scale / (float)total, dpred, (double*)workspace);
+  const bool vec = contig && (total & 3) == 0 && aligned16(pred, target, dpred);
+  const size_t groups = vec ? total / 4 : total;
+  const unsigned nb = vec ? grid_for(groups, 256, kMaxPartials) : grid_for(groups, 256 * 8, kMaxPartials);
+  hipLaunchKernelGGL(vec ? k_loss_partial<4> : k_loss_partial<1>, dim3(nb), dim3(256), 0, s, kind, pred, target, sn, sc,
+                     sh, sw, contig, C, H, W, groups, eps, grad_scale / (float)total, dpred, (double*)workspace);
   hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(256), 0, s, (const double*)workspace, (int)nb, 1.0 / (double)total,
                      loss);
   return check_launch("loss_forward_backward");
@@ -310,16 +253,11 @@ extern "C" int srk_sgd_step(float* p, const float* g, float* momentum_buf, size_
                             const float* grad_scale_dev, void* stream) {
   SRK_REQUIRE(p && g && n > 0, "sgd_step: null pointer or empty");
   SRK_REQUIRE(momentum == 0.f || momentum_buf, "sgd_step: momentum needs a buffer");
-  const bool vec = (n & 3) == 0 && (((uintptr_t)p | (uintptr_t)g | (uintptr_t)momentum_buf) & 15) == 0;
-  if (vec) {
-    size_t b = (n / 4 + 256 * 2 - 1) / (256 * 2);   // two float4 per thread
-    if (b > 65535) b = 65535;
-    hipLaunchKernelGGL(k_sgd4, dim3((unsigned)b), dim3(256), 0, (hipStream_t)stream, p, g, momentum_buf, n / 4, lr, momentum,
-                       weight_decay, nesterov, first_step, lr_dev, grad_scale_dev);
-    return check_launch("sgd_step");
-  }
-  hipLaunchKernelGGL(k_sgd, dim3(red_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, momentum_buf, n, lr, momentum,
-                     weight_decay, nesterov, first_step, lr_dev, grad_scale_dev);
+  const bool vec = (n & 3) == 0 && aligned16(p, g, momentum_buf);
+  const size_t groups = vec ? n / 4 : n;
+  const unsigned nb = vec ? grid_for(groups, 256 * 2, 65535) : grid_for(groups, 256 * 8, kMaxPartials);   // two float4 / eight floats per thread
+  hipLaunchKernelGGL(vec ? k_sgd<4> : k_sgd<1>, dim3(nb), dim3(256), 0, (hipStream_t)stream, p, g, momentum_buf, groups,
+                     lr, momentum, weight_decay, nesterov, first_step, lr_dev, grad_scale_dev);
   return check_launch("sgd_step");
 }
 
@@ -328,23 +266,18 @@ extern "C" int srk_adam_step(float* p, const float* g, float* exp_avg, float* ex
                              const float* lr_dev, const float* grad_scale_dev, void* stream) {
   SRK_REQUIRE(p && g && exp_avg && exp_avg_sq && step_dev && n > 0, "adam_step: null pointer or empty");
   hipStream_t s = (hipStream_t)stream;
-  if (n % 4 == 0 && (((uintptr_t)p | (uintptr_t)g | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0) {
-    size_t nb = (n / 4 + 256 * 2 - 1) / (256 * 2);
-    const size_t cap = (size_t)2 * kNumCU;
-    if (nb > cap) nb = cap;
-    hipLaunchKernelGGL(k_adam4, dim3((unsigned)nb), dim3(256), 0, s, p, g, exp_avg, exp_avg_sq, n / 4, lr, beta1, beta2, eps,
-                       weight_decay, step_dev, lr_dev, grad_scale_dev);
-    return check_launch("adam_step");
-  }
-  hipLaunchKernelGGL(k_adam, dim3(red_grid(n)), dim3(256), 0, s, p, g, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps,
-                     weight_decay, step_dev, lr_dev, grad_scale_dev);
+  const bool vec = n % 4 == 0 && aligned16(p, g, exp_avg, exp_avg_sq);
+  const size_t groups = vec ? n / 4 : n;
+  const unsigned nb = vec ? grid_for(groups, 256 * 2, (size_t)2 * kNumCU) : grid_for(groups, 256 * 8, kMaxPartials);
+  hipLaunchKernelGGL(vec ? k_adam<4> : k_adam<1>, dim3(nb), dim3(256), 0, s, p, g, exp_avg, exp_avg_sq, groups, lr,
+                     beta1, beta2, eps, weight_decay, step_dev, lr_dev, grad_scale_dev);
   return check_launch("adam_step");
 }
 
 extern "C" int srk_grad_norm_clip(const float* g, size_t n, float max_norm, float* norm_out, float* scale_out,
                                   void* workspace, void* stream) {
   SRK_REQUIRE(g && workspace && n > 0, "grad_norm_clip: null pointer or empty");
-  const unsigned nb = red_grid(n);
+  const unsigned nb = grid_for(n, 256 * 8, kMaxPartials);
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_sqsum_partial, dim3(nb), dim3(256), 0, s, g, n, (double*)workspace);
   hipLaunchKernelGGL(k_norm_final, dim3(1), dim3(256), 0, s, (const double*)workspace, (int)nb, max_norm, norm_out,

@@ -9,12 +9,7 @@ namespace srk {
 
 constexpr int kPsnrPartials = 1024;
 
-static inline unsigned pp_grid(size_t items, int per_block) {
-  size_t b = (items + per_block - 1) / per_block;
-  if (b < 1) b = 1;
-  if (b > 4096) b = 4096;
-  return (unsigned)b;
-}
+constexpr int kPpMaxBlocks = 4096;   // grid cap of every kernel here
 
 // ---------------------------------------------------------------------------------------------
 // PSNR: mse = mean((clamp(pred,0,1) - gt)^2); psnr = mse == 0 ? 100 : 10*log10(1/mse).  pred is addressed
@@ -38,16 +33,13 @@ __global__ __launch_bounds__(256) void k_psnr_partial(const float* __restrict__ 
     const float d = p - gt[n * gs.n + c * gs.c + h * gs.h + w * gs.w];  // fp32 difference, as the reference
     acc += (double)d * (double)d;
   }
-  const double tot = block_sum_256_d(acc, sm);
-  if (threadIdx.x == 0) partials[blockIdx.x] = tot;
+  store_block_sum_256_d(acc, sm, partials + blockIdx.x);
 }
 
 __global__ __launch_bounds__(256) void k_psnr_final(const double* __restrict__ partials, int nparts, double inv_count,
                                                     float* __restrict__ psnr, float* __restrict__ mse_out) {
   __shared__ double sm[4];
-  double acc = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += 256) acc += partials[i];
-  const double tot = block_sum_256_d(acc, sm);
+  const double tot = sum_partials_256_d(partials, nparts, sm);
   if (threadIdx.x == 0) {
     const double mse = tot * inv_count;
     if (mse_out) *mse_out = (float)mse;
@@ -78,33 +70,20 @@ __global__ __launch_bounds__(256) void k_channel_affine(const float* __restrict_
 // Nearest-neighbour integer up-sampling, NHWC: y[n, oy, ox, c] = x[n, oy / r, ox / r, c]
 // (torch.nn.Upsample(scale_factor=r, mode='nearest')); backward sums each r x r block.
 // ---------------------------------------------------------------------------------------------
+// V = 4 (C % 4 == 0): one 16-byte group of channels per thread and pass; CG = C / V.
+template <int V>
 __global__ __launch_bounds__(256) void k_upsample_nearest_fwd(const float* __restrict__ x, float* __restrict__ y, int H,
-                                                              int W, int C4, int r, size_t total4) {
-  typedef float lf4 __attribute__((ext_vector_type(4)));
+                                                              int W, int CG, int r, size_t groups) {
+  typedef Vec<V> Q;
   const int OW = W * r, OH = H * r;
-  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total4; e += (size_t)gridDim.x * 256) {
-    const int c = (int)(e % C4);
-    size_t t = e / C4;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < groups; e += (size_t)gridDim.x * 256) {
+    const int c = (int)(e % CG);
+    size_t t = e / CG;
     const int ox = (int)(t % OW);
     t /= OW;
     const int oy = (int)(t % OH);
     const size_t n = t / OH;
-    const size_t src = ((n * H + oy / r) * W + ox / r) * C4 + c;
-    reinterpret_cast<lf4*>(y)[e] = reinterpret_cast<const lf4*>(x)[src];
-  }
-}
-
-__global__ __launch_bounds__(256) void k_upsample_nearest_fwd1(const float* __restrict__ x, float* __restrict__ y, int H,
-                                                               int W, int C, int r, size_t total) {
-  const int OW = W * r, OH = H * r;
-  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-    const int c = (int)(e % C);
-    size_t t = e / C;
-    const int ox = (int)(t % OW);
-    t /= OW;
-    const int oy = (int)(t % OH);
-    const size_t n = t / OH;
-    y[e] = x[((n * H + oy / r) * W + ox / r) * C + c];
+    Q::store(y, e, Q::load(x, ((n * H + oy / r) * W + ox / r) * CG + c));
   }
 }
 
@@ -164,36 +143,10 @@ __global__ __launch_bounds__(256) void k_maxpool2(const float* __restrict__ x, f
 // unchanged), so dx leaves pre-masked and the conv below skips its mask read (ops.PREMASK).
 // ---------------------------------------------------------------------------------------------
 template <int V>
-__device__ __forceinline__ void pool_ld(const float* __restrict__ p, float (&v)[V]) {
-  typedef float lf4 __attribute__((ext_vector_type(4)));
-  if (V == 4) {
-    const lf4 t = *reinterpret_cast<const lf4*>(p);
-#pragma unroll
-    for (int i = 0; i < V; ++i) v[i] = t[i];
-  } else {
-#pragma unroll
-    for (int i = 0; i < V; ++i) v[i] = p[i];
-  }
-}
-
-template <int V>
-__device__ __forceinline__ void pool_st(float* __restrict__ p, const float (&v)[V]) {
-  typedef float lf4 __attribute__((ext_vector_type(4)));
-  if (V == 4) {
-    lf4 t;
-#pragma unroll
-    for (int i = 0; i < V; ++i) t[i] = v[i];
-    *reinterpret_cast<lf4*>(p) = t;
-  } else {
-#pragma unroll
-    for (int i = 0; i < V; ++i) p[i] = v[i];
-  }
-}
-
-template <int V>
 __global__ __launch_bounds__(256) void k_maxpool2_bwd(const float* __restrict__ x, const float* __restrict__ dy,
                                                       float* __restrict__ dx, int H, int W, int C, int relu_input,
                                                       size_t total) {
+  typedef Vec<V> Q;
   const int OH = H / 2, OW = W / 2, WH = (H + 1) / 2, WW = (W + 1) / 2, CG = C / V;
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
     const int cg = (int)(e % CG);
@@ -210,32 +163,29 @@ __global__ __launch_bounds__(256) void k_maxpool2_bwd(const float* __restrict__ 
     const size_t c0 = (size_t)cg * V;
     const size_t r0 = (n * H + y0) * W, r1 = (n * H + y1) * W;
     const size_t i00 = (r0 + x0) * C + c0, i01 = (r0 + x1) * C + c0, i10 = (r1 + x0) * C + c0, i11 = (r1 + x1) * C + c0;
-    float a[V], b[V], d[V], f[V], g[V];
-    pool_ld<V>(x + i00, a);
-    pool_ld<V>(x + i01, b);
-    pool_ld<V>(x + i10, d);
-    pool_ld<V>(x + i11, f);
-    pool_ld<V>(dy + ((n * OH + py) * OW + px) * C + c0, g);
-    float o0[V], o1[V], o2[V], o3[V];
+    // (every index below is a multiple of V floats: C % V == 0)
+    const typename Q::T a = Q::load(x + i00, 0), b = Q::load(x + i01, 0), d = Q::load(x + i10, 0), f = Q::load(x + i11, 0);
+    const typename Q::T g = Q::load(dy + ((n * OH + py) * OW + px) * C + c0, 0);
+    typename Q::T o0, o1, o2, o3;
 #pragma unroll
     for (int i = 0; i < V; ++i) {
-      float m = a[i];
+      float m = Q::at(a, i);
       int k = 0;
-      if (b[i] > m) m = b[i], k = 1;
-      if (d[i] > m) m = d[i], k = 2;
-      if (f[i] > m) m = f[i], k = 3;
+      if (Q::at(b, i) > m) m = Q::at(b, i), k = 1;
+      if (Q::at(d, i) > m) m = Q::at(d, i), k = 2;
+      if (Q::at(f, i) > m) m = Q::at(f, i), k = 3;
       const bool route = window && !(relu_input && m <= 0.f);
-      const float gi = route ? g[i] : 0.f;
-      o0[i] = k == 0 ? gi : 0.f;
-      o1[i] = k == 1 ? gi : 0.f;
-      o2[i] = k == 2 ? gi : 0.f;
-      o3[i] = k == 3 ? gi : 0.f;
+      const float gi = route ? Q::at(g, i) : 0.f;
+      Q::set(o0, i, k == 0 ? gi : 0.f);
+      Q::set(o1, i, k == 1 ? gi : 0.f);
+      Q::set(o2, i, k == 2 ? gi : 0.f);
+      Q::set(o3, i, k == 3 ? gi : 0.f);
     }
-    pool_st<V>(dx + i00, o0);
-    if (has_x1) pool_st<V>(dx + i01, o1);
+    Q::store(dx + i00, 0, o0);
+    if (has_x1) Q::store(dx + i01, 0, o1);
     if (has_y1) {
-      pool_st<V>(dx + i10, o2);
-      if (has_x1) pool_st<V>(dx + i11, o3);
+      Q::store(dx + i10, 0, o2);
+      if (has_x1) Q::store(dx + i11, 0, o3);
     }
   }
 }
@@ -255,7 +205,7 @@ extern "C" int srk_psnr(const float* pred, const int64_t* pred_strides, const fl
   if (pred_strides) ps = strides4(pred_strides);
   if (gt_strides) gs = strides4(gt_strides);
   const size_t total = (size_t)N * C * H * W;
-  unsigned nb = pp_grid(total, 256 * 8);
+  unsigned nb = grid_for(total, 256 * 8, kPpMaxBlocks);
   if (nb > kPsnrPartials) nb = kPsnrPartials;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_psnr_partial, dim3(nb), dim3(256), 0, s, pred, ps, gt, gs, C, H, W, total, (double*)workspace);
@@ -274,8 +224,8 @@ extern "C" int srk_channel_affine(const float* x, float* y, size_t n, int C, siz
     k.div[c] = c < C ? div_host[c] : 1.f;
     SRK_REQUIRE(k.div[c] != 0.f, "channel_affine: zero divisor for channel %d", c);
   }
-  hipLaunchKernelGGL(k_channel_affine, dim3(pp_grid(n, 256 * 4)), dim3(256), 0, (hipStream_t)stream, x, y, n, C, inner, k,
-                     clamp01);
+  hipLaunchKernelGGL(k_channel_affine, dim3(grid_for(n, 256 * 4, kPpMaxBlocks)), dim3(256), 0, (hipStream_t)stream, x,
+                     y, n, C, inner, k, clamp01);
   return check_launch("channel_affine");
 }
 
@@ -285,10 +235,11 @@ extern "C" int srk_upsample_nearest_forward(const float* x, float* y, int N, int
   const size_t total = (size_t)N * H * r * W * r * C;
   hipStream_t s = (hipStream_t)stream;
   if (C % 4 == 0)
-    hipLaunchKernelGGL(k_upsample_nearest_fwd, dim3(pp_grid(total / 4, 256 * 2)), dim3(256), 0, s, x, y, H, W, C / 4, r,
-                       total / 4);
+    hipLaunchKernelGGL(k_upsample_nearest_fwd<4>, dim3(grid_for(total / 4, 256 * 2, kPpMaxBlocks)), dim3(256), 0, s, x,
+                       y, H, W, C / 4, r, total / 4);
   else
-    hipLaunchKernelGGL(k_upsample_nearest_fwd1, dim3(pp_grid(total, 256 * 4)), dim3(256), 0, s, x, y, H, W, C, r, total);
+    hipLaunchKernelGGL(k_upsample_nearest_fwd<1>, dim3(grid_for(total, 256 * 4, kPpMaxBlocks)), dim3(256), 0, s, x, y,
+                       H, W, C, r, total);
   return check_launch("upsample_nearest_forward");
 }
 
@@ -297,8 +248,8 @@ extern "C" int srk_upsample_nearest_backward(const float* dy, float* dx, int N, 
   SRK_REQUIRE(dy && dx, "upsample_nearest_backward: null pointer");
   SRK_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && r >= 1, "upsample_nearest_backward: bad dims");
   const size_t total = (size_t)N * H * W * C;
-  hipLaunchKernelGGL(k_upsample_nearest_bwd, dim3(pp_grid(total, 256 * 2)), dim3(256), 0, (hipStream_t)stream, dy, dx, H,
-                     W, C, r, total);
+  hipLaunchKernelGGL(k_upsample_nearest_bwd, dim3(grid_for(total, 256 * 2, kPpMaxBlocks)), dim3(256), 0,
+                     (hipStream_t)stream, dy, dx, H, W, C, r, total);
   return check_launch("upsample_nearest_backward");
 }
 
@@ -306,7 +257,8 @@ extern "C" int srk_maxpool2x2_forward(const float* x, float* y, int N, int H, in
   SRK_REQUIRE(x && y, "maxpool2x2: null pointer");
   SRK_REQUIRE(N > 0 && H >= 2 && W >= 2 && C > 0, "maxpool2x2: bad dims");
   const size_t total = (size_t)N * (H / 2) * (W / 2) * C;
-  hipLaunchKernelGGL(k_maxpool2, dim3(pp_grid(total, 256 * 4)), dim3(256), 0, (hipStream_t)stream, x, y, H, W, C, total);
+  hipLaunchKernelGGL(k_maxpool2, dim3(grid_for(total, 256 * 4, kPpMaxBlocks)), dim3(256), 0, (hipStream_t)stream, x, y,
+                     H, W, C, total);
   return check_launch("maxpool2x2_forward");
 }
 
@@ -316,15 +268,10 @@ extern "C" int srk_maxpool2x2_backward(const float* x, const float* dy, float* d
   SRK_REQUIRE(N > 0 && H >= 2 && W >= 2 && C > 0, "maxpool2x2_backward: bad dims");
   const size_t windows = (size_t)N * ((H + 1) / 2) * ((W + 1) / 2);
   hipStream_t s = (hipStream_t)stream;
-  const bool wide = C % 4 == 0 && (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0;
-  if (wide) {
-    const size_t total = windows * (C / 4);
-    hipLaunchKernelGGL(k_maxpool2_bwd<4>, dim3(pp_grid(total, 256)), dim3(256), 0, s, x, dy, dx, H, W, C,
-                       relu_input != 0, total);
-  } else {
-    const size_t total = windows * C;
-    hipLaunchKernelGGL(k_maxpool2_bwd<1>, dim3(pp_grid(total, 256 * 2)), dim3(256), 0, s, x, dy, dx, H, W, C,
-                       relu_input != 0, total);
-  }
+  const bool vec = C % 4 == 0 && aligned16(x, dy, dx);
+  const size_t total = vec ? windows * (C / 4) : windows * C;
+  const unsigned nb = vec ? grid_for(total, 256, kPpMaxBlocks) : grid_for(total, 256 * 2, kPpMaxBlocks);
+  hipLaunchKernelGGL(vec ? k_maxpool2_bwd<4> : k_maxpool2_bwd<1>, dim3(nb), dim3(256), 0, s, x, dy, dx, H, W, C,
+                     relu_input != 0, total);
   return check_launch("maxpool2x2_backward");
 }

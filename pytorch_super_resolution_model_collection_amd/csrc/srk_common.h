@@ -104,6 +104,39 @@ inline void launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t s, A... ar
 
 inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
 
+// Blocks of a grid-stride streaming kernel: one per `per_block` items, at least 1, at most `cap`.
+inline unsigned grid_for(size_t items, size_t per_block, size_t cap) {
+  const size_t b = (items + per_block - 1) / per_block;
+  return (unsigned)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
+// Every pointer on a 16-byte boundary (NULL counts as aligned): the condition of a kernel's 16-byte form.
+template <typename... P>
+__host__ __device__ __forceinline__ bool aligned16(const P*... p) {
+  return ((... | reinterpret_cast<uintptr_t>(p)) & 15) == 0;
+}
+
+// V consecutive floats as one access: the 4-byte and the 16-byte form of a streaming kernel are one template over V.
+// load / store index in units of V floats.
+template <int V>
+struct Vec;
+template <>
+struct Vec<4> {
+  typedef f32x4 T;
+  static __device__ __forceinline__ T load(const float* p, size_t i) { return reinterpret_cast<const T*>(p)[i]; }
+  static __device__ __forceinline__ void store(float* p, size_t i, const T& v) { reinterpret_cast<T*>(p)[i] = v; }
+  static __device__ __forceinline__ float at(const T& v, int k) { return v[k]; }
+  static __device__ __forceinline__ void set(T& v, int k, float x) { v[k] = x; }
+};
+template <>
+struct Vec<1> {
+  typedef float T;
+  static __device__ __forceinline__ T load(const float* p, size_t i) { return p[i]; }
+  static __device__ __forceinline__ void store(float* p, size_t i, const T& v) { p[i] = v; }
+  static __device__ __forceinline__ float at(const T& v, int) { return v; }
+  static __device__ __forceinline__ void set(T& v, int, float x) { v = x; }
+};
+
 // Element strides of a [N][C][H][W] tensor in any layout; passed to kernels by value.
 struct Strides4 {
   int64_t n, c, h, w;
@@ -182,6 +215,21 @@ __device__ __forceinline__ double block_sum_256_d(double v, double* sm) {
   if ((threadIdx.x & 63) == 0) sm[w] = v;
   __syncthreads();
   return sm[0] + sm[1] + sm[2] + sm[3];
+}
+
+// The two halves of a reduction through per-block partials (blocks of 256 threads, `sm` = 4 doubles).
+// Tail of a partial kernel: the block's sum of v, stored to *slot by thread 0.
+__device__ __forceinline__ void store_block_sum_256_d(double v, double* sm, double* __restrict__ slot) {
+  const double tot = block_sum_256_d(v, sm);
+  if (threadIdx.x == 0) *slot = tot;
+}
+// One-block final: the sum of partials[i * stride], i < nparts, in a fixed order (thread t adds i = t, t + 256, ...; then
+// the block sum).  All threads get the total.
+__device__ __forceinline__ double sum_partials_256_d(const double* __restrict__ partials, int nparts, double* sm,
+                                                     int stride = 1) {
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < nparts; i += 256) acc += partials[(size_t)i * stride];
+  return block_sum_256_d(acc, sm);
 }
 
 }  // namespace srk

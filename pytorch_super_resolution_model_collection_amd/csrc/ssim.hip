@@ -167,10 +167,8 @@ __global__ __launch_bounds__(256) void k_ssim_final(const double* __restrict__ p
                                                     double inv_pixels_range2, float* __restrict__ ssim_out,
                                                     float* __restrict__ psnr_out, float* __restrict__ mse_out) {
   __shared__ double sm[4];
-  double s = 0.0, q = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += 256) s += partials[2 * i], q += partials[2 * i + 1];
-  const double s_tot = block_sum_256_d(s, sm);
-  const double q_tot = block_sum_256_d(q, sm);
+  const double s_tot = sum_partials_256_d(partials, nparts, sm, 2);       // [block][0]: sum of the SSIM map
+  const double q_tot = sum_partials_256_d(partials + 1, nparts, sm, 2);   // [block][1]: sum of squared differences
   if (threadIdx.x == 0) {
     const double mse = q_tot * inv_pixels_range2;
     *ssim_out = (float)(s_tot * inv_positions);

@@ -211,9 +211,7 @@ __global__ __launch_bounds__(256) void k_ssim_loss(SsimLossJob job, double* __re
 __global__ __launch_bounds__(256) void k_ssim_loss_final(const double* __restrict__ partials, int nparts, double positions,
                                                          float* __restrict__ loss) {
   __shared__ double sm[4];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += 256) s += partials[i];
-  const double s_tot = block_sum_256_d(s, sm);
+  const double s_tot = sum_partials_256_d(partials, nparts, sm);
   if (threadIdx.x == 0) *loss = (float)(1.0 - s_tot / positions);
 }
 

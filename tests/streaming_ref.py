@@ -188,14 +188,14 @@ def _blocks(items, per_block, cap):
 
 
 SMALL = (1, 2, 3, 4, 5, 7, 8, 1020, 1023, 1024, 1025, 1028, 4096, 4099, 6145)
-CAP_EW = 4096 * 2048          # ew_grid(n, 256 * 8): act forward / scalar backward / axpby; backward4: ew_grid(n / 4, 512)
-CAP_RED = 1024 * 2048         # red_grid: scalar loss / sgd / adam / grad norm; psnr (pp_grid then kPsnrPartials)
-CAP_LOSS4 = 4 * 1024 * 256    # k_loss_partial4: one float4 per thread and pass, kMaxPartials blocks
-CAP_ADAM4 = 4 * 512 * 512     # k_adam4: two float4 per thread, 2 * CUs blocks (256 CUs)
+CAP_EW = 4096 * 2048          # grid_for(n, 256 * 8, 4096): act forward / scalar backward / axpby; k_act_bwd<4>: (n / 4, 512, 4096)
+CAP_RED = 1024 * 2048         # grid_for(n, 256 * 8, 1024): scalar loss / sgd / adam / grad norm; psnr (4096, then kPsnrPartials)
+CAP_LOSS4 = 4 * 1024 * 256    # k_loss_partial<4>: one float4 per thread and pass, kMaxPartials blocks
+CAP_ADAM4 = 4 * 512 * 512     # k_adam<4>: two float4 per thread, 2 * CUs blocks (256 CUs)
 CAP_ABSMAX = 1024 * 4096
-CAP_PP = 4096 * 1024          # pp_grid(n, 256 * 4): channel_affine, maxpool, scalar up-sample
-CAP_UP4 = 4 * 4096 * 512      # float4 up-sample: pp_grid(total / 4, 256 * 2)
-# (k_sgd4's cap of 65535 blocks of 512 float4 needs > 500 MB per buffer: not swept)
+CAP_PP = 4096 * 1024          # grid_for(n, 256 * 4, 4096): channel_affine, maxpool, scalar up-sample
+CAP_UP4 = 4 * 4096 * 512      # float4 up-sample: grid_for(total / 4, 256 * 2, 4096)
+# (k_sgd<4>'s cap of 65535 blocks of 512 float4 needs > 500 MB per buffer: not swept)
 
 
 def sizes(cap, cap2=None):

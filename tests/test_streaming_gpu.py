@@ -10,29 +10,29 @@ gradient (float atomics); tests/test_streaming_cpu.py shows fp32 arithmetic with
 Write side: an output of a direct C-ABI call lives inside a larger tensor, NaN-filled, between two guards of 64 sentinel
 floats; afterwards no NaN is left and the guards are untouched.  Every extent is checked on the host before a launch.
 Read side of the reductions: mass planted at the structural positions (streaming_ref.positions).
-k_sgd4's 65535-block cap needs > 500 MB per buffer and is not swept.
+k_sgd<4>'s 65535-block cap needs > 500 MB per buffer and is not swept.
 
 Which test runs which kernel / branch
   k_act_fwd        float4 body, scalar tail, > 1 block, grid cap      test_act_forward_backward_sizes
                    per-channel float4 branch (C = 8, 64)              test_prelu_per_channel, test_activation_op[(3,8,4,4) / (5,12)]
                    !vec_ok scalar branch (C = 3, 6)                   test_prelu_per_channel, test_activation_op[(2,6,5,7)]
-  k_act_bwd4       ReLU family, n % 4 == 0, aligned, grid cap         test_act_forward_backward_sizes (off = 0)
-  k_act_bwd        n % 4 != 0; dx off a 16-byte boundary; tanh /      test_act_forward_backward_sizes (off = 1),
+  k_act_bwd<4>     ReLU family, n % 4 == 0, aligned, grid cap         test_act_forward_backward_sizes (off = 0)
+  k_act_bwd<1>     n % 4 != 0; dx off a 16-byte boundary; tanh /      test_act_forward_backward_sizes (off = 1),
                    sigmoid; per-channel slope gradient                test_prelu_per_channel
   k_axpby          body, tail, cap                                    test_axpby_sizes
   k_scale_dev      foreign upstream gradient of a loss                test_loss_seeds_and_foreign_gradients
-  k_loss_partial4  dense aligned n % 4 == 0, 1 .. 1024 blocks, cap    test_loss_sizes, test_loss_op_layouts[(2,4,6,5)]
-  k_loss_partial   contiguous branch, cap                             test_loss_sizes, test_loss_scalar_kernel_at_multiples_of_4
+  k_loss_partial<4> dense aligned n % 4 == 0, 1 .. 1024 blocks, cap   test_loss_sizes, test_loss_op_layouts[(2,4,6,5)]
+  k_loss_partial<1> contiguous branch, cap                            test_loss_sizes, test_loss_scalar_kernel_at_multiples_of_4
                    strided branch (NCHW, crop, expand, stride 2)      test_loss_op_layouts, test_loss_scalar_kernel_at_multiples_of_4
-  k_sgd4 / k_sgd   first_step, lr_dev / lr, grad_scale_dev / NULL     test_sgd_sizes, test_sgd_scalar_kernel_at_multiples_of_4,
+  k_sgd<4> / <1>   first_step, lr_dev / lr, grad_scale_dev / NULL     test_sgd_sizes, test_sgd_scalar_kernel_at_multiples_of_4,
                                                                       test_clip_scale_reaches_the_scalar_sgd
-  k_adam4 / k_adam 1, 2 - 3, capped blocks; the arrival ticket        test_adam_sizes, test_adam_scalar_kernel_at_multiples_of_4,
+  k_adam<4> / <1>  1, 2 - 3, capped blocks; the arrival ticket        test_adam_sizes, test_adam_scalar_kernel_at_multiples_of_4,
                                                                       test_tensor_adam_17
   k_sqsum_partial / k_norm_final                                      test_grad_norm_clip_sizes
   k_absmax         float4 branch, tail, unaligned branch, cap         test_absmax
   k_psnr_partial   cap, strided pred / gt                             test_psnr_sizes, test_psnr_op_layouts
   k_channel_affine cap, NHWC / NCHW channel index                     test_channel_affine_sizes, test_channel_affine_op
-  k_upsample_nearest_fwd / _fwd1 / _bwd, caps                         test_upsample_op, test_upsample_above_the_caps
+  k_upsample_nearest_fwd<4> / <1> / _bwd, caps                        test_upsample_op, test_upsample_above_the_caps
   k_maxpool2       odd H / W, cap                                     test_maxpool_op, test_maxpool_above_the_cap"""
 import ctypes
 
@@ -149,8 +149,8 @@ ACT_SIZES = R.sizes(R.CAP_EW)
 
 @pytest.mark.parametrize("n", ACT_SIZES)
 def test_act_forward_backward_sizes(gpu, n):
-    """k_act_fwd: float4 body + scalar tail (n % 4 != 0), one block .. the 4096-block cap.  Backward: k_act_bwd4 for the ReLU
-    family at n % 4 == 0, the scalar k_act_bwd otherwise (and for tanh / sigmoid); with dx one float off a 16-byte boundary
+    """k_act_fwd: float4 body + scalar tail (n % 4 != 0), one block .. the 4096-block cap.  Backward: k_act_bwd<4> for the ReLU
+    family at n % 4 == 0, the scalar k_act_bwd<1> otherwise (and for tanh / sigmoid); with dx one float off a 16-byte boundary
     the scalar kernel at n % 4 == 0 too.  The slope gradient accumulates into a buffer that holds 0.75."""
     big = n > 10000
     x, dy = R.gen_act(n)
@@ -318,7 +318,7 @@ def _check_loss(kind, p, t, where, val, g, scale=1.0, what=""):
 @pytest.mark.parametrize("kind", R.LOSSES)
 @pytest.mark.parametrize("n", LOSS_SIZES)
 def test_loss_sizes(gpu, kind, n):
-    """n % 4 == 0, aligned, dense: k_loss_partial4 (capped at 1024 blocks above 4 * 1024 * 256); otherwise k_loss_partial
+    """n % 4 == 0, aligned, dense: k_loss_partial<4> (capped at 1024 blocks above 4 * 1024 * 256); otherwise k_loss_partial<1>
     (capped above 1024 * 2048).  |pred - target| is 1000 x larger at the last element, the end of the float4 body, the
     start of the second grid-stride pass and in the last block.  Without dpred the value is the same."""
     vec = n % 4 == 0
@@ -479,15 +479,15 @@ def _sgd_run(gpu, n, variant, off):
 @pytest.mark.parametrize("variant", sorted(R.SGD_VARIANTS))
 @pytest.mark.parametrize("n", OPT_SIZES)
 def test_sgd_sizes(gpu, variant, n):
-    """Three chained steps, the first with first_step = 1 over a NaN-filled momentum buffer.  n % 4 == 0: k_sgd4; otherwise
-    k_sgd (capped at 1024 blocks above 1024 * 2048)."""
+    """Three chained steps, the first with first_step = 1 over a NaN-filled momentum buffer.  n % 4 == 0: k_sgd<4>; otherwise
+    k_sgd<1> (capped at 1024 blocks above 1024 * 2048)."""
     _sgd_run(gpu, n, variant, 0)
 
 
 @pytest.mark.parametrize("variant", sorted(R.SGD_VARIANTS))
 @pytest.mark.parametrize("n", [8, 4096])
 def test_sgd_scalar_kernel_at_multiples_of_4(gpu, variant, n):
-    """buffers one float off a 16-byte boundary: k_sgd at n % 4 == 0"""
+    """buffers one float off a 16-byte boundary: k_sgd<1> at n % 4 == 0"""
     _sgd_run(gpu, n, variant, 1)
 
 
@@ -521,8 +521,8 @@ def _adam_run(gpu, n, wd, off):
 @pytest.mark.parametrize("wd", [0.0, f32(1e-4)])
 @pytest.mark.parametrize("n", R.sizes(R.CAP_ADAM4, R.CAP_RED))
 def test_adam_sizes(gpu, wd, n):
-    """Three steps launched back to back; afterwards {count, ticket} = [3, 0].  n % 4 == 0: k_adam4 (1, 2 - 3 and, above
-    4 * 512 * 512, the capped 2 * CUs blocks); otherwise k_adam (capped above 1024 * 2048).  lr 0.05: the three steps move p
+    """Three steps launched back to back; afterwards {count, ticket} = [3, 0].  n % 4 == 0: k_adam<4> (1, 2 - 3 and, above
+    4 * 512 * 512, the capped 2 * CUs blocks); otherwise k_adam<1> (capped above 1024 * 2048).  lr 0.05: the three steps move p
     by 0.1 - 0.3 of |p|, so an error of the step is not hidden by p's own rounding."""
     _adam_run(gpu, n, wd, 0)
 
@@ -533,7 +533,7 @@ def test_adam_scalar_kernel_at_multiples_of_4(gpu, n):
 
 
 def test_tensor_adam_17(gpu):
-    """optim.TensorAdam on 17 elements (DRCN's combine weights): the scalar k_adam, one block, lr on the device."""
+    """optim.TensorAdam on 17 elements (DRCN's combine weights): the scalar k_adam<1>, one block, lr on the device."""
     pkg = _pkg()
     p0, grads = R.gen_opt(17)
     t = _dev(p0, gpu)
@@ -681,7 +681,7 @@ SUB, DIV = (0.4, 0.5, 0.6, 0.1, 0.2, 0.3, 0.7, 0.8), (0.2, 0.25, 0.3, 0.9, 1.1, 
 
 @pytest.mark.parametrize("n", R.sizes(R.CAP_PP))
 def test_channel_affine_sizes(gpu, n):
-    """k_channel_affine up to pp_grid's 4096-block cap, flat: channel = (e / inner) % C for NHWC (inner 1) and NCHW-like
+    """k_channel_affine up to its 4096-block cap, flat: channel = (e / inner) % C for NHWC (inner 1) and NCHW-like
     (inner 5) storage; bit-equal to fp32 (x - sub) / div."""
     lib = _lib()
     x = R._rs(3).standard_normal(n).astype(np.float32)

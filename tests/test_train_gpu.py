@@ -488,7 +488,7 @@ def test_srgan_step_is_its_segments_run_in_order(gpu):
     (in order, dp.exchange() behind every segment that has a dp) from equal starts, are the same code -- parameters,
     optimizer states, BatchNorm statistics, gradients and losses after two steps must be bit-equal.
     Shapes: bit equality of two runs needs a step that repeats itself bit for bit.  The gradient of a single-slope PReLU
-    is summed with one float atomicAdd per block of 2048 elements (k_act_bwd4), in whatever order the blocks arrive: up
+    is summed with one float atomicAdd per block of 2048 elements (k_act_bwd<4>), in whatever order the blocks arrive: up
     to two blocks the sum does not depend on the order (a + b == b + a), from three on its last bit does -- at 64 filters
     and four 8x8 patches two runs of the SAME closure differ by 1 ulp in the three PReLU slopes' gradients and Adam
     moments (measured; nothing else differs).  8 filters and two 4x4 patches keep the largest PReLU output, the second
