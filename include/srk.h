@@ -170,6 +170,55 @@ int srk_ring_timeouts(int reset);
 /* Output spatial size of a conv / transposed conv along one axis (torch semantics). */
 int srk_conv_out_dim(int in, int k, int stride, int pad, int transposed, int out_pad);
 
+/* ---- host planners, as diagnostics ------------------------------------------------------- */
+/* What the library's host planners decide, for tests and measurements: no device, no stream, no allocation, nothing is
+ * launched.  Every out-struct is a HOST struct sized by the caller through a leading struct_size, as srk_conv_result is.
+ * (Added without a change of srk_version(): new entry points only, nothing existing changed.) */
+enum { SRK_WGRAD_KERNEL_BF = 0, SRK_WGRAD_KERNEL_TR = 1 }; /* k_wgrad_bf | k_wgrad_tr */
+/* The launch the stride-1 bf16x3 weight gradient makes of a problem, when srk_conv2d_backward_weight[_grouped] hands it one
+ * (SRK_ALGO_AUTO / _MFMA_BF16X3, not a few-output-channel layer). */
+typedef struct srk_wgrad_plan {
+  uint32_t struct_size;
+  int32_t ok;                    /* 0: these kernels do not cover the problem (every other field is 0) */
+  int32_t kernel;                /* SRK_WGRAD_KERNEL_* */
+  int32_t cfg, CIB, COB;         /* tile configuration 0..2: input x output channels of a block */
+  int32_t spec, k33;             /* wave-specialised variant (else one tile per block step); its 3x3 K loop */
+  int32_t prefetch, ring;        /* spec: the stagers load one tile ahead; X halo rows live in a ring */
+  int32_t vec_x, vec_y, scalar;  /* 16-byte loads of x / of dy and the mask (channels a multiple of 4, pointers on 16-byte
+                                    boundaries); scalar = not both: what the name says, and no prefetch */
+  int32_t grouped, n;            /* the grouped entry, its layers (per-layer entry: 0, 1) */
+  int32_t G;                     /* split-K partial slabs per layer */
+  int32_t grid_x, grid_y, grid_z, block, lds_bytes; /* the launch: blocks, threads, dynamic LDS */
+  int32_t TH, TW, TWo, HH, HWp, CS, DS, nks;        /* tile rows / pixels / octets per row, halo rows / padded width, plane strides, K steps */
+  int32_t tiles_y, tiles_x, ntiles, gy, gz;         /* tiles per image and in all; input / output channel chunks */
+  int32_t lds_set, ring_bytes;   /* LDS of one buffer set; of the ring layout (0 without it) */
+  int32_t XP, XPL, YPL;          /* k_wgrad_tr: pixels per ring row, bytes per X / dY plane */
+  uint64_t slab_bytes, ws_bytes; /* workspace: the partial slabs in front of the bias partials; all of it */
+  char name[64];                 /* what srk_last_kernel_name() reports after the launch */
+} srk_wgrad_plan;
+/* n_layers = 1: srk_conv2d_backward_weight; > 1: one grouped launch of that many layers.  x_aligned / dy_aligned: x / dy
+ * and the mask are on 16-byte boundaries.  num_cu: compute units to plan for, 0 = the current device's.  out->struct_size
+ * must be set.  SRK_OK also when the plan says ok = 0. */
+int srk_conv2d_backward_weight_plan(const srk_conv_desc* d, int n_layers, int x_aligned, int dy_aligned, int num_cu,
+                                    srk_wgrad_plan* out);
+/* The stride-1 problems a strided TRANS gather (ConvTranspose2d forward, data gradient of a strided Conv2d) is split into,
+ * one per output phase.  One axis: the phase writes outputs o0 + r * stride, r < P; its virtual tap u reads input
+ * r + i0 + u and weight tap w0 + wd * u, u < Kv (Kv = 0: no tap reaches the phase, i0 = w0 = wd = 0). */
+typedef struct srk_phase_axis {
+  uint32_t struct_size;
+  int32_t o0, P, Kv, i0, w0, wd;
+} srk_phase_axis;
+/* Both axes; a phase without taps on either axis has none at all (KHv = KWv = 0 and zero tap fields). */
+typedef struct srk_phase {
+  uint32_t struct_size;
+  int32_t oy0, ox0, PH, PW, KHv, KWv, iy0, ix0, wh0, wdh, ww0, wdw;
+} srk_phase;
+/* Fill out[0 .. count) with the phases that run (a phase whose first output lies outside O does not), in launch order,
+ * and return count.  out[0].struct_size must be set: it is the size and stride of the caller's elements.  Negative
+ * srk_status on bad arguments or when max is too small. */
+int srk_trans_phase_axis(int K, int stride, int pad, int O, srk_phase_axis* out, int max);
+int srk_trans_phases(int KH, int KW, int stride, int pad, int OH, int OW, srk_phase* out, int max);
+
 /* ---- layout ---------------------------------------------------------------------------- */
 /* NCHW <-> NHWC copies at the module boundary (the reference feeds NCHW tensors:
  * edsr.py:146-152). */

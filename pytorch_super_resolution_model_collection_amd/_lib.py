@@ -58,6 +58,34 @@ class BwdMask(ctypes.Structure):
     _fields_ = [("y", c_vp), ("slope", c_float)]
 
 
+class _Sized(ctypes.Structure):
+    """a host out-struct the caller sizes through its leading struct_size"""
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = ctypes.sizeof(type(self))
+
+
+class WgradPlan(_Sized):
+    """struct srk_wgrad_plan (srk_conv2d_backward_weight_plan)"""
+    _fields_ = ([("struct_size", ctypes.c_uint32)] + [(n, ctypes.c_int32) for n in
+                ("ok", "kernel", "cfg", "CIB", "COB", "spec", "k33", "prefetch", "ring", "vec_x", "vec_y", "scalar",
+                 "grouped", "n", "G", "grid_x", "grid_y", "grid_z", "block", "lds_bytes", "TH", "TW", "TWo", "HH", "HWp",
+                 "CS", "DS", "nks", "tiles_y", "tiles_x", "ntiles", "gy", "gz", "lds_set", "ring_bytes", "XP", "XPL", "YPL")]
+                + [("slab_bytes", ctypes.c_uint64), ("ws_bytes", ctypes.c_uint64), ("name", ctypes.c_char * 64)])
+
+
+class PhaseAxis(_Sized):
+    """struct srk_phase_axis (srk_trans_phase_axis)"""
+    _fields_ = [("struct_size", ctypes.c_uint32)] + [(n, ctypes.c_int32) for n in ("o0", "P", "Kv", "i0", "w0", "wd")]
+
+
+class Phase(_Sized):
+    """struct srk_phase (srk_trans_phases)"""
+    _fields_ = [("struct_size", ctypes.c_uint32)] + [(n, ctypes.c_int32) for n in
+                ("oy0", "ox0", "PH", "PW", "KHv", "KWv", "iy0", "ix0", "wh0", "wdh", "ww0", "wdw")]
+
+
 _PROTOTYPES = {
     "srk_version": (c_int, []),
     "srk_status_string": (ctypes.c_char_p, [c_int]),
@@ -67,6 +95,10 @@ _PROTOTYPES = {
     "srk_last_conv_bn_partial_rows": (c_int, []),
     "srk_ring_timeouts": (c_int, [c_int]),
     "srk_conv_out_dim": (c_int, [c_int] * 6),
+    "srk_conv2d_backward_weight_plan": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_int, c_int, c_int,
+                                                ctypes.POINTER(WgradPlan)]),
+    "srk_trans_phase_axis": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(PhaseAxis), c_int]),
+    "srk_trans_phases": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(Phase), c_int]),
     "srk_nchw_to_nhwc": (c_int, [c_f, c_f, c_int, c_int, c_int, c_int, c_vp]),
     "srk_nhwc_to_nchw": (c_int, [c_f, c_f, c_int, c_int, c_int, c_int, c_vp]),
     "srk_pack_weight_fwd": (c_int, [c_f, c_f, c_int, c_int, c_int, c_int, c_int, c_int, c_vp]),

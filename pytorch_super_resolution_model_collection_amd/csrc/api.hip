@@ -3,6 +3,8 @@
 // the MFMA, direct or generic kernels.
 #include "srk_common.h"
 #include "conv_problem.h"
+#include "conv_tile.h"
+#include "conv_wgrad_plan.h"
 #include <stddef.h>
 #include <string.h>
 #include <stdlib.h>
@@ -132,7 +134,8 @@ size_t conv_wgrad_bf_grouped_ws(const srk_conv_desc& d, int n);
 int conv_wgrad_bf_grouped(const srk_conv_desc& d, int n, const float* const* xs, const float* const* dys,
                           const srk_bwd_mask* masks, float* const* dws, float* const* dbs, float beta, void* ws,
                           size_t ws_bytes, hipStream_t s);
-constexpr int kMaxWgradGroup = 40;  // = WB_MAXGROUP of conv_wgrad_bf16.hip
+srk_wgrad_plan conv_wgrad_bf_plan(const srk_conv_desc& d, int n, bool grouped, bool x_aligned, bool y_aligned, int num_cu);
+constexpr int kMaxWgradGroup = WB_MAXGROUP;
 
 // conv_mfma_bf16.hip
 int pack_weights_batched(const float* params, void* packed, const long long* table, int n_layers, int blocks,
@@ -463,7 +466,7 @@ extern "C" size_t srk_conv2d_backward_weight_workspace_bytes(const srk_conv_desc
   if (!d) return 0;
   size_t a = conv_generic_wgrad_ws(*d);
   size_t b = conv_wgrad_mfma_supported(*d) ? conv_wgrad_mfma_ws(*d) : 0;
-  size_t c = conv_wgrad_bf_supported(*d) ? conv_wgrad_bf_ws(*d) : 0;
+  size_t c = conv_wgrad_bf_ws(*d);   // (0 when the stride-1 bf16x3 kernels do not cover the layer)
   if (b > a) a = b;
   if (c > a) a = c;
   const size_t t = conv_wgrad_tapn_supported(*d, nullptr, nullptr) ? conv_wgrad_tapn_ws(*d) : 0;
@@ -557,6 +560,57 @@ extern "C" int srk_conv2d_backward_weight_grouped(const srk_conv_desc* d, int n,
     if (l + 1 < n && wgrad_reduce_deferring() && (rc = wgrad_reduce_flush((hipStream_t)stream))) return rc;
   }
   return SRK_OK;
+}
+
+// ---- host planners as diagnostics: no device work.  Caller-sized out-structs: only the leading struct_size bytes are written.
+extern "C" int srk_conv2d_backward_weight_plan(const srk_conv_desc* d, int n_layers, int x_aligned, int dy_aligned, int num_cu,
+                                               srk_wgrad_plan* out) {
+  const int rc = validate_desc(d, "conv2d_backward_weight_plan");
+  if (rc) return rc;
+  SRK_REQUIRE(n_layers >= 1 && num_cu >= 0, "conv2d_backward_weight_plan: bad layer or CU count");
+  SRK_REQUIRE(out && out->struct_size >= sizeof(uint32_t), "conv2d_backward_weight_plan: out->struct_size not set");
+  srk_wgrad_plan L = conv_wgrad_bf_plan(*d, n_layers, n_layers > 1, x_aligned != 0, dy_aligned != 0, num_cu);
+  const size_t size = out->struct_size < sizeof(L) ? out->struct_size : sizeof(L);
+  L.struct_size = (uint32_t)size;
+  memcpy(out, &L, size);
+  return SRK_OK;
+}
+
+// One record into a caller-sized array element (its size and stride: out[0].struct_size)
+template <typename T>
+static int put_phase(T* out, uint32_t size, int i, int max, T v) {
+  if (i >= max) return SRK_ERR_BAD_ARG;
+  v.struct_size = size;
+  memcpy(reinterpret_cast<char*>(out) + (size_t)i * size, &v, size < sizeof(T) ? size : sizeof(T));
+  return SRK_OK;
+}
+
+extern "C" int srk_trans_phase_axis(int K, int stride, int pad, int O, srk_phase_axis* out, int max) {
+  SRK_REQUIRE(K > 0 && stride > 0 && pad >= 0 && O > 0, "trans_phase_axis: bad geometry");
+  SRK_REQUIRE(out && max > 0 && out->struct_size >= sizeof(uint32_t), "trans_phase_axis: out[0].struct_size not set");
+  const uint32_t size = out->struct_size;
+  int n = 0;
+  srk_phase_axis a;
+  for (int p = 0; p < stride; ++p)
+    if (phase_axis(K, stride, pad, O, p, a)) {
+      SRK_REQUIRE(put_phase(out, size, n, max, a) == SRK_OK, "trans_phase_axis: more than max = %d phases", max);
+      ++n;
+    }
+  return n;
+}
+
+extern "C" int srk_trans_phases(int KH, int KW, int stride, int pad, int OH, int OW, srk_phase* out, int max) {
+  SRK_REQUIRE(KH > 0 && KW > 0 && stride > 0 && pad >= 0 && OH > 0 && OW > 0, "trans_phases: bad geometry");
+  SRK_REQUIRE(out && max > 0 && out->struct_size >= sizeof(uint32_t), "trans_phases: out[0].struct_size not set");
+  const uint32_t size = out->struct_size;
+  int n = 0;
+  const int rc = for_each_trans_phase(KH, KW, stride, pad, OH, OW, [&](const srk_phase& q) {
+    const int e = put_phase(out, size, n, max, q);
+    if (e == SRK_OK) ++n;
+    return e;
+  });
+  SRK_REQUIRE(rc == SRK_OK, "trans_phases: more than max = %d phases", max);
+  return n;
 }
 
 extern "C" int srk_pack_weights_batched(const float* params_base, void* packed_base, const int64_t* table, int n_layers,

@@ -619,9 +619,15 @@ static void bfd_lds_plan(int TW, int is, int HW, int npx, int npix, int NPW, int
   perm = v.perm;
 }
 
-template <int NTW, int NPW, int NOW, int NP, int PF, bool F16 = false, int OCCX = 0>
-static int bfd_launch(BfdParams B, int budget_bytes, hipStream_t s) {
-  note_amax_written(B.P.ep.y_amax != nullptr);   // both epilogues keep the running maximum of what they store
+// What one phase (one stride-1 gather) takes of a block of 64 * NPW pixels: the tile, with one block per CU where the
+// budget's tiles are too ragged; the LDS plan of the operand reads; whether all input-channel chunks are staged at once;
+// the LDS of one chunk and of the block.  Written into B; false: no tile fits LDS.
+struct BfdPhasePlan {
+  size_t lds_chunk, lds, epi_bytes;
+  // the split of the staged chunks over two wave groups needs both groups' chunks in LDS
+  bool can_split(const BfdParams& B) const { return B.allc || 2 * lds_chunk <= (size_t)150 * 1024; }
+};
+static bool bfd_plan_phase(BfdParams& B, int NPW, int NP, int budget_bytes, BfdPhasePlan& pp) {
   MfmaConvParams& P = B.P;
   const int maxpix = 64 * NPW;
   TilePick best{};
@@ -635,49 +641,63 @@ static int bfd_launch(BfdParams B, int budget_bytes, hipStream_t s) {
       ok = true;
     }
   }
-  if (!ok) {
+  if (!ok) return false;
+  P.TH = best.TH; P.TW = best.TW; P.tiles_y = best.tiles_y; P.tiles_x = best.tiles_x; P.HH = best.HH; P.HW = best.HW;
+  bfd_lds_plan(P.TW, P.is, P.HW, P.TH * P.TW, P.HH * P.HW, NPW, B.NPIXp, B.perm);
+  pp.lds_chunk = pp.lds = (size_t)NP * (4 * B.NPIXp + 4) * 16;
+  B.allc = 0;
+  B.cpr = 1;
+  if (NPW == 1 && B.ICc > 1 && pp.lds * B.ICc <= 64 * 1024) {  // small-problem blocks: stage all chunks at once
+    B.allc = 1;
+    B.cpr = B.ICc;
+    pp.lds *= B.ICc;
+  }
+  pp.epi_bytes = (size_t)NPW * 32 * BFD_EPI_STRIDE * sizeof(float);
+  if (pp.lds < pp.epi_bytes) pp.lds = pp.epi_bytes;
+  return true;
+}
+// ... and what changes when the launch takes that split (small-problem blocks, NPW = 1, NTW = 1)
+static void bfd_plan_split(BfdParams& B, int NOW, BfdPhasePlan& pp) {
+  if (!B.allc) {  // many chunks (deep layers of the SRGAN discriminator): two chunks per barrier round, one per group
+    B.cpr = 2;
+    pp.lds = 2 * pp.lds_chunk;
+    if (pp.lds < pp.epi_bytes) pp.lds = pp.epi_bytes;
+  }
+  const size_t red_bytes = (size_t)NOW * 4 * 64 * 16;
+  if (pp.lds < red_bytes) pp.lds = red_bytes;
+}
+// small-problem blocks with >= 2 staged chunks split them over two wave groups, but only while the grid leaves the CUs
+// with one block each: with two resident blocks the other block already hides the latency and the split just adds the
+// reduction (B = 32 EDSR shard: 3.28 -> 3.55 ms with it, B = 16: 2.63 -> 2.37 ms)
+static bool bfd_grid_wants_split(int ICc, long blocks) { return ICc >= 2 && blocks <= kNumCU + kNumCU / 4; }
+
+template <int NTW, int NPW, int NOW, int NP, int PF, bool F16 = false, int OCCX = 0>
+static int bfd_launch(BfdParams B, int budget_bytes, hipStream_t s) {
+  note_amax_written(B.P.ep.y_amax != nullptr);   // both epilogues keep the running maximum of what they store
+  BfdPhasePlan pp{};
+  if (!bfd_plan_phase(B, NPW, NP, budget_bytes, pp)) {
     set_error("conv_bfd: no tile fits LDS");
     return SRK_ERR_UNSUPPORTED;
   }
-  P.TH = best.TH; P.TW = best.TW; P.tiles_y = best.tiles_y; P.tiles_x = best.tiles_x; P.HH = best.HH; P.HW = best.HW;
-  bfd_lds_plan(P.TW, P.is, P.HW, P.TH * P.TW, P.HH * P.HW, NPW, B.NPIXp, B.perm);
-  size_t lds = (size_t)NP * (4 * B.NPIXp + 4) * 16;
-  B.allc = 0;
-  B.cpr = 1;
-  const size_t lds_chunk = lds;
-  if (NPW == 1 && B.ICc > 1 && lds * B.ICc <= 64 * 1024) {  // small-problem blocks: stage all chunks at once
-    B.allc = 1;
-    B.cpr = B.ICc;
-    lds *= B.ICc;
-  }
-  const size_t epi_bytes = (size_t)NPW * 32 * BFD_EPI_STRIDE * sizeof(float);
-  if (lds < epi_bytes) lds = epi_bytes;
+  const MfmaConvParams& P = B.P;
   dim3 grid((unsigned)((size_t)P.tiles_x * P.tiles_y * P.N), B.OCb);
   if constexpr (NPW == 1) {
-    // small-problem blocks with >= 2 staged chunks: split the chunks over two wave groups
-    const size_t red_bytes = (size_t)NOW * 4 * NTW * 64 * 16;
-    // only while the grid leaves the CUs with one block each: with two resident blocks the other block already hides the
-    // latency and the split just adds the reduction (B = 32 EDSR shard: 3.28 -> 3.55 ms with it, B = 16: 2.63 -> 2.37 ms)
-    if (B.ICc >= 2 && (B.allc || 2 * lds_chunk <= (size_t)150 * 1024) && (long)grid.x * grid.y <= kNumCU + kNumCU / 4) {
-      if (!B.allc) {  // many chunks (deep layers of the SRGAN discriminator): two chunks per barrier round, one per group
-        B.cpr = 2;
-        lds = 2 * lds_chunk;
-        if (lds < epi_bytes) lds = epi_bytes;
-      }
-      if (lds < red_bytes) lds = red_bytes;
+    static_assert(NTW == 1, "bfd_plan_split sizes the reduction for one M tile per wave");
+    if (pp.can_split(B) && bfd_grid_wants_split(B.ICc, (long)grid.x * grid.y)) {
+      bfd_plan_split(B, NOW, pp);
       note_kernel("k_conv_bfd<%d,%d,%d,%d,%d,2%s>", NTW, NPW, NOW, NP, PF, F16 ? ",f16" : "");
-      launch_lds<&k_conv_bfd<NTW, NPW, NOW, NP, PF, 2, F16, OCCX>>(grid, dim3(64 * NPW * NOW * 2), lds, s, B);
+      launch_lds<&k_conv_bfd<NTW, NPW, NOW, NP, PF, 2, F16, OCCX>>(grid, dim3(64 * NPW * NOW * 2), pp.lds, s, B);
       return check_launch("conv_bfd");
     }
   }
   note_kernel("k_conv_bfd<%d,%d,%d,%d,%d,1%s%s>", NTW, NPW, NOW, NP, PF, F16 ? ",f16" : "", OCCX == 3 ? ",occ3" : (OCCX == 4 ? ",occ4" : ""));
-  launch_lds<&k_conv_bfd<NTW, NPW, NOW, NP, PF, 1, F16, OCCX>>(grid, dim3(64 * NPW * NOW), lds, s, B);
+  launch_lds<&k_conv_bfd<NTW, NPW, NOW, NP, PF, 1, F16, OCCX>>(grid, dim3(64 * NPW * NOW), pp.lds, s, B);
   return check_launch("conv_bfd");
 }
 
 // The phases of a stride-2 TRANS gather as one launch of the small-problem block (64 pixels x NOW channel-waves): every
-// phase keeps the tile, LDS plan and staging mode bfd_launch would give it; the K-split decision is taken on the blocks of
-// the WHOLE launch.  -1: not taken (the caller launches the phases one by one).
+// phase gets bfd_plan_phase's plan, as in bfd_launch; the K-split decision is taken on the blocks of the WHOLE launch.
+// -1: not taken (the caller launches the phases one by one).
 template <int NOW, int NP>
 static int bfd_launch_small_multi(const MfmaConvParams* phases, int nph, const BfdParams& base, hipStream_t s) {
   constexpr int NTW = 1, NPW = 1, PF = 2;
@@ -685,60 +705,26 @@ static int bfd_launch_small_multi(const MfmaConvParams* phases, int nph, const B
   if (nph < 2 || nph > BFD_MAXPH) return -1;
   BfdMulti M{};
   M.nph = nph;
-  size_t lds_chunk[BFD_MAXPH], lds[BFD_MAXPH];
+  BfdPhasePlan pp[BFD_MAXPH];
   long total = 0;
-  const size_t epi_bytes = (size_t)NPW * 32 * BFD_EPI_STRIDE * sizeof(float);
+  bool ks2 = true;
   for (int i = 0; i < nph; ++i) {
-    BfdParams B = base;
+    BfdParams& B = M.ph[i];
+    B = base;
     B.P = phases[i];
-    MfmaConvParams& P = B.P;
-    TilePick best{};
-    const int kh = P.KHv > 0 ? P.KHv : 1, kw = P.KWv > 0 ? P.KWv : 1;
-    bool ok = pick_tile(64 * NPW, P.PH, P.PW, P.is, kh, kw, NP * 16, SMALL / 4 - 16 * NP * 16, best);
-    if (!ok || best.eff < 0.6) {
-      TilePick big{};
-      if (pick_tile(64 * NPW, P.PH, P.PW, P.is, kh, kw, NP * 16, (156 * 1024) / 4 - 16 * NP * 16, big) &&
-          (!ok || big.eff > best.eff * 1.2)) {
-        best = big;
-        ok = true;
-      }
-    }
-    if (!ok) return -1;
-    P.TH = best.TH; P.TW = best.TW; P.tiles_y = best.tiles_y; P.tiles_x = best.tiles_x; P.HH = best.HH; P.HW = best.HW;
-    bfd_lds_plan(P.TW, P.is, P.HW, P.TH * P.TW, P.HH * P.HW, NPW, B.NPIXp, B.perm);
-    size_t l = (size_t)NP * (4 * B.NPIXp + 4) * 16;
-    B.allc = 0;
-    B.cpr = 1;
-    lds_chunk[i] = l;
-    if (B.ICc > 1 && l * B.ICc <= 64 * 1024) {
-      B.allc = 1;
-      B.cpr = B.ICc;
-      l *= B.ICc;
-    }
-    if (l < epi_bytes) l = epi_bytes;
-    lds[i] = l;
-    M.ph[i] = B;
+    if (!bfd_plan_phase(B, NPW, NP, SMALL, pp[i])) return -1;
+    ks2 = ks2 && pp[i].can_split(B);
     M.start[i] = (int)total;
-    total += (long)P.tiles_x * P.tiles_y * P.N;
+    total += (long)B.P.tiles_x * B.P.tiles_y * B.P.N;
     if (total >= (1L << 30)) return -1;
   }
   M.start[nph] = (int)total;
   const int OCb = base.OCb;
-  // K split over two wave groups while the whole launch leaves the CUs with about one block each (as bfd_launch)
-  bool ks2 = base.ICc >= 2 && total * OCb <= kNumCU + kNumCU / 4;
-  for (int i = 0; i < nph && ks2; ++i) ks2 = M.ph[i].allc || 2 * lds_chunk[i] <= (size_t)150 * 1024;
+  ks2 = ks2 && bfd_grid_wants_split(base.ICc, total * OCb);
   size_t lds_max = 0;
-  const size_t red_bytes = (size_t)NOW * 4 * NTW * 64 * 16;
   for (int i = 0; i < nph; ++i) {
-    if (ks2) {
-      if (!M.ph[i].allc) {
-        M.ph[i].cpr = 2;
-        lds[i] = 2 * lds_chunk[i];
-        if (lds[i] < epi_bytes) lds[i] = epi_bytes;
-      }
-      if (lds[i] < red_bytes) lds[i] = red_bytes;
-    }
-    if (lds[i] > lds_max) lds_max = lds[i];
+    if (ks2) bfd_plan_split(M.ph[i], NOW, pp[i]);
+    if (pp[i].lds > lds_max) lds_max = pp[i].lds;
   }
   note_amax_written(base.P.ep.y_amax != nullptr);
   dim3 grid((unsigned)total, (unsigned)OCb);

@@ -101,6 +101,44 @@ static inline bool pick_tile(int maxpix, int PH, int PW, int is, int KHv, int KW
 }
 
 
+// TRANS gather along one axis: i = (o + pad - k) / st where the division is exact.  Output phase p = (o + pad) % st is a
+// stride-1 problem of its own over the taps k = p (mod st); false when its first output o0 lies outside O (srk.h:
+// srk_phase_axis; plain host arithmetic, also answered by srk_trans_phase_axis).
+inline bool phase_axis(int K, int st, int pad, int O, int p, srk_phase_axis& a) {
+  a = srk_phase_axis{};
+  a.o0 = (((p - pad) % st) + st) % st;
+  if (a.o0 >= O) return false;
+  a.P = (O - a.o0 + st - 1) / st;
+  a.Kv = p < K ? (K - p + st - 1) / st : 0;
+  if (a.Kv) {
+    a.i0 = (a.o0 + pad - p) / st - (a.Kv - 1);
+    a.w0 = p + st * (a.Kv - 1);
+    a.wd = -st;
+  }
+  return true;
+}
+
+// The phases of a 2-D TRANS gather, rows outermost: f(phase) for each one that runs, until f returns non-zero.
+template <typename F>
+inline int for_each_trans_phase(int KH, int KW, int st, int pad, int OH, int OW, F f) {
+  srk_phase_axis y, x;
+  for (int py = 0; py < st; ++py) {
+    if (!phase_axis(KH, st, pad, OH, py, y)) continue;
+    for (int px = 0; px < st; ++px) {
+      if (!phase_axis(KW, st, pad, OW, px, x)) continue;
+      srk_phase q{};
+      q.oy0 = y.o0; q.ox0 = x.o0; q.PH = y.P; q.PW = x.P;
+      if (y.Kv && x.Kv) {  // (no tap on one axis: no tap at all)
+        q.KHv = y.Kv; q.iy0 = y.i0; q.wh0 = y.w0; q.wdh = y.wd;
+        q.KWv = x.Kv; q.ix0 = x.i0; q.ww0 = x.w0; q.wdw = x.wd;
+      }
+      const int rc = f(q);
+      if (rc) return rc;
+    }
+  }
+  return 0;
+}
+
 // Fills the geometry of `P` from the gather problem and calls launch(P) once (CONV gather, TRANS
 // gather with stride 1) or once per output phase (TRANS gather with stride s: s*s launches).
 template <typename Launch>
@@ -122,34 +160,13 @@ static inline int for_each_phase(const GatherConv& g, const float* in, const flo
     return launch(P);
   }
   // TRANS gather: iy = (oy + p - kh)/s.  One launch per output phase (py,px) = ((oy+p)%s, (ox+p)%s).
-  const int st = g.stride;
-  for (int py = 0; py < st; ++py) {
-    const int oy0 = (((py - g.pad) % st) + st) % st;
-    if (oy0 >= g.OH) continue;
-    const int KHv = py < g.KH ? (g.KH - py + st - 1) / st : 0;
-    const int by = (oy0 + g.pad - py) / st;
-    for (int px = 0; px < st; ++px) {
-      const int ox0 = (((px - g.pad) % st) + st) % st;
-      if (ox0 >= g.OW) continue;
-      const int KWv = px < g.KW ? (g.KW - px + st - 1) / st : 0;
-      const int bx = (ox0 + g.pad - px) / st;
-      MfmaConvParams Q = P;
-      Q.PH = (g.OH - oy0 + st - 1) / st;
-      Q.PW = (g.OW - ox0 + st - 1) / st;
-      Q.oy0 = oy0; Q.ox0 = ox0; Q.os = st; Q.is = 1;
-      if (KHv == 0 || KWv == 0) {
-        Q.KHv = 0; Q.KWv = 0; Q.iy0 = 0; Q.ix0 = 0; Q.wh0 = 0; Q.wdh = 0; Q.ww0 = 0; Q.wdw = 0;
-      } else {
-        Q.KHv = KHv; Q.KWv = KWv;
-        Q.iy0 = by - (KHv - 1); Q.ix0 = bx - (KWv - 1);
-        Q.wh0 = py + st * (KHv - 1); Q.wdh = -st;
-        Q.ww0 = px + st * (KWv - 1); Q.wdw = -st;
-      }
-      const int rc = launch(Q);
-      if (rc) return rc;
-    }
-  }
-  return SRK_OK;
+  return for_each_trans_phase(g.KH, g.KW, g.stride, g.pad, g.OH, g.OW, [&](const srk_phase& q) {
+    MfmaConvParams Q = P;
+    Q.PH = q.PH; Q.PW = q.PW; Q.oy0 = q.oy0; Q.ox0 = q.ox0; Q.os = g.stride; Q.is = 1;
+    Q.KHv = q.KHv; Q.KWv = q.KWv; Q.iy0 = q.iy0; Q.ix0 = q.ix0;
+    Q.wh0 = q.wh0; Q.wdh = q.wdh; Q.ww0 = q.ww0; Q.wdw = q.wdw;
+    return launch(Q);
+  });
 }
 
 

@@ -22,6 +22,7 @@
 // kernels of conv_wgrad_mfma.hip.
 #include "srk_common.h"
 #include "conv_problem.h"
+#include "conv_wgrad_plan.h"
 #include <stdlib.h>
 
 namespace srk {
@@ -36,9 +37,7 @@ bool wgrad_reduce_deferring();
 int wgrad_reduce_submit(bool wide, const float* ws, float* dw, int G, int Cout, int Cin, int KH, int KW, int transposed,
                         float beta, const float* bias_partial, float* db, int bias_cout, int out_ps_r, hipStream_t s);
 
-constexpr int WB_MAXOCT = 64;  // octets per tile (<= 512 pixels)
-constexpr int WB_SST = 512;    // SPEC: staging threads (8 waves next to the 4 working waves; 4 stager waves: 0.157 -> 0.20 ms on the VDSR layer)
-constexpr int WB_PIT = 1024 / WB_SST;  // SPEC stagers: register batches per tensor and tile when prefetching one tile ahead
+// (WB_MAXOCT, WB_SST, WB_PIT, WB_MAXGROUP: conv_wgrad_plan.h, with the planner that sizes tiles and groups by them)
 // Staging-thread -> (channel group q, first pixel pair) map.  A wave covers 4 channel groups x 16 consecutive pixel pairs:
 // its transposing 4-byte LDS stores then fall on 4 x 16 distinct banks (channel-group stride = 16 * odd dwords, pixel pairs =
 // consecutive dwords).  The round-1 map (q fastest: 16 groups x 4 pairs per wave for a 64-channel tensor) put 4 lanes on
@@ -88,7 +87,6 @@ struct WgBfParams {
 // of EDSR, edsr.py:37-45; the 18 of VDSR, vdsr.py:17-24) in one launch.  Only the tensors differ per layer; their
 // pointers travel by value in the kernel arguments (no device-side table, so the call is hipGraph-capturable as is).
 // Block x = layer * G + g: layer `layer` has G split-K partial slabs, slab / bias-partial index = blockIdx.x.
-constexpr int WB_MAXGROUP = 40;
 struct WgLayer {
   const float* x;
   const float* dy;
@@ -1471,105 +1469,11 @@ __global__ __launch_bounds__(256, 2) void k_wgrad_s2(WgS2Params P) {
 // ---------------------------------------------------------------------------------------------
 // Host
 // ---------------------------------------------------------------------------------------------
-static constexpr int kWbLdsBudget = 74 * 1024;  // + ~4.6 KB static (tables, bias reduction): 2 blocks per CU
-
-struct WbPlan {
-  bool ok;
-  int cfg;  // 0: 32 ci x 64 co (CIT 2, COW 2, NTW 2); 1: 64 ci x 32 co (4,1,2); 2: 64 ci x 16 co (4,1,1)
-  int CIB, COB;
-  int TH, TW, TWo, tiles_y, tiles_x, HH, HWp, CS, DS, nks;
-  size_t lds;
-  int ntiles, gy, gz;
-};
-
-static inline int round_8odd(int v) {  // smallest multiple of 8 >= v whose quotient by 8 is odd
-  int q = (v + 7) / 8;
-  if ((q & 1) == 0) ++q;
-  return q * 8;
-}
-
-static WbPlan wb_plan(const srk_conv_desc& d) {
-  WbPlan pl{};
-  pl.ok = false;
-  if (d.transposed || d.stride != 1 || d.KH > 3 || d.KW > 3 || d.Cin < 8 || d.Cout < 1) return pl;
-  if ((long)d.H * d.W * d.Cin >= (1L << 30) || (long)d.OH * d.OW * d.Cout >= (1L << 30)) return pl;  // 32-bit in-image offsets
-  if (d.dy_ps_r > 1 && (d.Cout % (d.dy_ps_r * d.dy_ps_r) != 0 || (d.Cout / (d.dy_ps_r * d.dy_ps_r)) % 4 != 0)) return pl;
-  if (d.Cout > 32) {
-    pl.cfg = 0; pl.CIB = 32; pl.COB = 64;
-  } else if (d.Cout > 16) {
-    pl.cfg = 1; pl.CIB = 64; pl.COB = 32;
-  } else {
-    pl.cfg = 2; pl.CIB = 64; pl.COB = 16;
-  }
-  // tile = TH rows x TWo octets (8 pixels each).  Search the shapes that fit LDS for the one with the most useful
-  // pixels per padded K step (e.g. 41-wide VDSR patches: 2 x 48 -> 83 % instead of 4 x 32 -> 60 %); ties -> taller
-  // tiles (less halo per pixel).
-  double best_eff = -1.0;
-  for (int TWo = 1; TWo <= 6 && (TWo - 1) * 8 < d.OW; ++TWo) {
-    const int TW = TWo * 8;
-    int TH = 16 / TWo;  // <= 128 pixels per tile
-    if (TH > d.OH) TH = d.OH;
-    for (; TH >= 1; --TH) {
-      const int HH = TH + d.KH - 1, HWp = TW + 8;
-      const int CS = round_8odd(HH * HWp), DS = round_8odd(TH * TW + 8);
-      const size_t lds = ((size_t)2 * pl.CIB * CS + (size_t)2 * pl.COB * DS) * 2;
-      if (lds > (size_t)kWbLdsBudget || TH * TWo > WB_MAXOCT) continue;
-      const int nks = cdiv(TH * TWo, 4);
-      const double tiles = (double)cdiv(d.OH, TH) * cdiv(d.OW, TW);
-      // cost per tile: nks K steps + staging, calibrated on the VDSR / EDSR body layers (ablation: staging one
-      // channel-pixel costs 1/3136 of a K step; only TW + KW - 1 halo columns are loaded)
-      const double cost = tiles * (nks + ((double)HH * (TW + d.KW - 1) * pl.CIB + (double)TH * TW * pl.COB) / 3136.0);
-      const double eff = (double)d.OH * d.OW / cost;
-      if (eff > best_eff * 1.02 || (eff > best_eff * 0.98 && eff > 0 && TH > pl.TH)) {
-        if (eff > best_eff) best_eff = eff;
-        pl.TWo = TWo; pl.TW = TW; pl.TH = TH; pl.HH = HH; pl.HWp = HWp; pl.CS = CS; pl.DS = DS; pl.lds = lds;
-      }
-      break;  // smaller TH only gets worse for this width
-    }
-  }
-  if (best_eff < 0) return pl;
-  pl.tiles_x = cdiv(d.OW, pl.TW);
-  pl.tiles_y = cdiv(d.OH, pl.TH);
-  pl.nks = cdiv(pl.TH * pl.TWo, 4);
-  const long nt = (long)d.N * pl.tiles_y * pl.tiles_x;
-  if (nt > (1L << 30)) return pl;
-  pl.ntiles = (int)nt;
-  pl.gy = cdiv(d.Cin, pl.CIB);
-  pl.gz = cdiv(d.Cout, pl.COB);
-  pl.ok = true;
-  return pl;
-}
-
-// Split-K count G of a launch over n layers of this plan (the per-layer entry: n = 1) and whether the wave-specialised
-// variant runs it: one block per CU with two LDS buffer sets when every block then has >= 2 tiles to pipeline, else two
-// resident blocks per CU.  spec == nullptr: the larger of the two counts, which the workspace is sized for.
-static int wb_split(const WbPlan& pl, int n, bool* spec) {
-  const int per = n * pl.gy * pl.gz;  // (layer, channel-chunk) pairs
-  int g1 = kNumCU / per, g2 = (2 * kNumCU) / per;
-  if (g1 < 1) g1 = 1;
-  if (g2 < 1) g2 = 1;
-  if (g2 > pl.ntiles) g2 = pl.ntiles;
-  if (!spec) return g2;
-  *spec = 2 * pl.lds + 8 * 1024 <= 160 * 1024 && pl.ntiles >= 2 * g1;
-  return *spec ? g1 : g2;
-}
-
-// SPEC stagers prefetch one tile ahead when a tile's pixel pairs fit their register batches (WB_PIT x 512 items per tensor)
-static int wb_prefetch_ok(const WbPlan& pl, const srk_conv_desc& d) {
-  const long x_items = (long)pl.HH * ((pl.TW + d.KW) >> 1) * (pl.CIB / 4);
-  const long y_items = (long)pl.TH * (pl.TW >> 1) * (pl.COB / 4);
-  // the prefetching stagers load through per-image buffer descriptors with 32-bit byte offsets
-  const long ximg = (long)d.H * d.W * d.Cin * 4, yimg = (long)d.OH * d.OW * d.Cout * 4;
-  return x_items <= (long)WB_PIT * WB_SST && y_items <= (long)WB_PIT * WB_SST && ximg < (1L << 31) && yimg < (1L << 31);
-}
-
-// Ring mode of the wave-specialised kernel (WgBfParams.ring): plane stride of the 2 * HH-row ring and the LDS it needs
-// (ring + two dY buffer sets); 0 when it does not apply.
-static size_t wb_ring_setup(const WbPlan& pl, bool spec, int prefetch, int& cs_ring) {
-  if (!spec || !prefetch) return 0;
-  cs_ring = round_8odd(2 * pl.HH * pl.HWp);
-  const size_t bytes = ((size_t)2 * pl.CIB * cs_ring + (size_t)2 * 2 * pl.COB * pl.DS) * 2;
-  return bytes + 8 * 1024 <= 160 * 1024 ? bytes : 0;
+// The stride-1 planner is conv_wgrad_plan.h: wb_launch_plan() decides kernel, variant, grid, LDS, workspace and name.  This
+// is the one place that hands it the device and the switch (num_cu = 0: the current device's; the launchers' case).
+srk_wgrad_plan conv_wgrad_bf_plan(const srk_conv_desc& d, int n, bool grouped, bool x_aligned, bool y_aligned, int num_cu) {
+  return wb_launch_plan(d, n, grouped, x_aligned, y_aligned, num_cu > 0 ? num_cu : kNumCU, env_int("SRK_WGRAD_TR", 1) != 0,
+                        conv_bias_grad_ws(d));
 }
 
 // ---- stride-2 plan (k_wgrad_s2) ----
@@ -1662,93 +1566,52 @@ int conv_wgrad_s2(const srk_conv_desc& d, const float* x, const float* dy, float
                                   0, s);
 }
 
-// ---- k_wgrad_tr (pixel-major LDS image + transpose reads): eligibility, LDS layout, launch.  SRK_WGRAD_TR=0: never.
-static bool wt_setup(WgBfParams& P, const srk_conv_desc& d, const WbPlan& pl, bool spec, size_t& lds_bytes) {
-  if (!spec || pl.cfg != 0 || !env_int("SRK_WGRAD_TR", 1)) return false;
-  if (d.KH != 3 || d.KW != 3 || d.Cin % 32 != 0 || d.Cout % 64 != 0 || !P.vec_x || !P.vec_y) return false;
-  if (d.dy_ps_r > 1 && (d.Cout / (d.dy_ps_r * d.dy_ps_r)) % 64 != 0) return false;
-  const long ximg = (long)d.H * d.W * d.Cin * 4, yimg = (long)d.OH * d.OW * d.Cout * 4;
-  if (ximg >= (1L << 31) || yimg >= (1L << 31)) return false;   // per-image buffer descriptors, 32-bit byte offsets
-  if ((long)pl.HH * (pl.TW + 2) * 4 > 1024 || (long)pl.TH * pl.TW * 8 > 1024) return false;  // two items per stager and tensor
-  const int XP = pl.TW + 4;   // halo columns 0 .. TW + 1 are staged; the third transpose read of a row touches TW + 3
-  const size_t XPL = (size_t)2 * pl.HH * XP * 64, YPL = (size_t)(pl.TH * pl.TW + 8) * 128;
-  const size_t bytes = 2 * XPL + 4 * YPL;
-  if (bytes + 1024 > 160 * 1024 || 2 * XPL < (size_t)WB_SST * 9 * 4 || XPL + 512 >= 65536 || YPL + 1024 >= 65536) return false;
-  P.XP = XP;
-  P.XPL = (int)XPL;
-  P.YPL = (int)YPL;
-  lds_bytes = bytes;
-  return true;
-}
-template <bool GRP>
-static void wt_launch(const WgBfParams& P, const typename WgGroupArg<GRP>::type& GR, dim3 grid, size_t lds, hipStream_t s) {
-  note_kernel("k_wgrad_tr<%s>", GRP ? "grouped" : "single");
-  launch_lds<&k_wgrad_tr<GRP>>(grid, dim3(768), lds, s, P, GR);
-}
+bool conv_wgrad_bf_supported(const srk_conv_desc& d) { return conv_wgrad_bf_plan(d, 1, false, true, true, 0).ok; }
 
-bool conv_wgrad_bf_supported(const srk_conv_desc& d) { return wb_plan(d).ok; }
+size_t conv_wgrad_bf_ws(const srk_conv_desc& d) { return conv_wgrad_bf_plan(d, 1, false, true, true, 0).ws_bytes; }
 
-size_t conv_wgrad_bf_ws(const srk_conv_desc& d) {
-  WbPlan pl = wb_plan(d);
-  if (!pl.ok) return 0;
-  return (size_t)wb_split(pl, 1, nullptr) * d.KH * d.KW * d.Cin * d.Cout * sizeof(float) + conv_bias_grad_ws(d);
-}
-
-// What the geometry, the plan and the split decide of WgBfParams, the same for the per-layer and the grouped entry (the
-// tensors are the caller's); the bias partials lie slab_bytes into ws.  lds_half: the LDS of one buffer set (the
-// specialised launch asks for 2 x this), the ring's where that mode applies.
-static WgBfParams wb_params(const srk_conv_desc& d, const WbPlan& pl, int G, bool spec, bool vec_x, bool vec_y, int dy_ps_r,
-                            void* ws, size_t slab_bytes, bool want_bias, size_t& lds_half) {
+// The kernel parameters of a plan, the same for the per-layer and the grouped entry (the tensors are the caller's); the
+// bias partials lie L.slab_bytes into ws.
+static WgBfParams wb_params(const srk_conv_desc& d, const srk_wgrad_plan& L, void* ws, bool want_bias) {
   WgBfParams P{};
   P.ws = (float*)ws;
-  P.bias_partial = want_bias ? reinterpret_cast<float*>(static_cast<char*>(ws) + slab_bytes) : nullptr;
+  P.bias_partial = want_bias ? reinterpret_cast<float*>(static_cast<char*>(ws) + L.slab_bytes) : nullptr;
   P.N = d.N; P.Cin = d.Cin; P.Cout = d.Cout;
   P.XH = d.H; P.XW = d.W; P.YH = d.OH; P.YW = d.OW;
   P.KH = d.KH; P.KW = d.KW; P.pad = d.pad;
-  P.TH = pl.TH; P.TW = pl.TW; P.TWo = pl.TWo; P.tiles_y = pl.tiles_y; P.tiles_x = pl.tiles_x;
-  P.HH = pl.HH; P.HWp = pl.HWp; P.CS = pl.CS; P.DS = pl.DS;
-  P.ntiles = pl.ntiles; P.G = G; P.nks = pl.nks;
-  P.vec_x = vec_x; P.vec_y = vec_y;
-  P.dy_ps_r = dy_ps_r;
-  P.dy_ps_C = dy_ps_r ? d.Cout / (dy_ps_r * dy_ps_r) : d.Cout;
-  P.prefetch = wb_prefetch_ok(pl, d) && vec_x && vec_y;  // 16-byte channel groups only
-  lds_half = pl.lds;
-  int cs_ring = 0;
-  if (const size_t ring_bytes = wb_ring_setup(pl, spec, P.prefetch, cs_ring)) {
-    P.ring = 1;
-    P.CS = cs_ring;
-    lds_half = (ring_bytes + 1) / 2;
-  }
+  P.TH = L.TH; P.TW = L.TW; P.TWo = L.TWo; P.tiles_y = L.tiles_y; P.tiles_x = L.tiles_x;
+  P.HH = L.HH; P.HWp = L.HWp; P.CS = L.CS; P.DS = L.DS;
+  P.ntiles = L.ntiles; P.G = L.G; P.nks = L.nks;
+  P.vec_x = L.vec_x; P.vec_y = L.vec_y;
+  P.dy_ps_r = d.dy_ps_r > 1 ? d.dy_ps_r : 0;
+  P.dy_ps_C = P.dy_ps_r ? d.Cout / (P.dy_ps_r * P.dy_ps_r) : d.Cout;
+  P.prefetch = L.prefetch;
+  P.ring = L.ring;
+  P.XP = L.XP; P.XPL = L.XPL; P.YPL = L.YPL;
   return P;
 }
 
 template <bool GRP, int CIT, int COW, int NTW>
-static void wb_launch_t(const WgBfParams& P, const typename WgGroupArg<GRP>::type& GR, dim3 grid, size_t lds, bool spec,
+static void wb_launch_t(const srk_wgrad_plan& L, const WgBfParams& P, const typename WgGroupArg<GRP>::type& GR, dim3 grid,
                         hipStream_t s) {
-  // variant word, then what the shape and the pointers decided: the stagers' mode (spec only), the scalar loads, the group
-  const char* mode = !spec ? "" : P.prefetch && P.ring ? ",pf,ring" : P.prefetch ? ",pf" : "";
-  note_kernel("k_wgrad_bf<%d,%d,%d,%s%s%s%s>", CIT, COW, NTW, spec ? "spec" : "tile", mode,
-              P.vec_x && P.vec_y ? "" : ",scalar", GRP ? ",grouped" : "");
-  if (spec && P.KH == 3 && P.KW == 3)
-    launch_lds<&k_wgrad_bf<CIT, COW, NTW, true, GRP, true>>(grid, dim3(64 * CIT * COW + WB_SST), 2 * lds, s, P, GR);
-  else if (spec)
-    launch_lds<&k_wgrad_bf<CIT, COW, NTW, true, GRP>>(grid, dim3(64 * CIT * COW + WB_SST), 2 * lds, s, P, GR);
+  if (L.k33)
+    launch_lds<&k_wgrad_bf<CIT, COW, NTW, true, GRP, true>>(grid, dim3(L.block), L.lds_bytes, s, P, GR);
+  else if (L.spec)
+    launch_lds<&k_wgrad_bf<CIT, COW, NTW, true, GRP>>(grid, dim3(L.block), L.lds_bytes, s, P, GR);
   else
-    launch_lds<&k_wgrad_bf<CIT, COW, NTW, false, GRP>>(grid, dim3(64 * CIT * COW), lds, s, P, GR);
+    launch_lds<&k_wgrad_bf<CIT, COW, NTW, false, GRP>>(grid, dim3(L.block), L.lds_bytes, s, P, GR);
 }
 
-// The kernel of a plan: k_wgrad_tr where it applies, else k_wgrad_bf in the plan's tile configuration.
+// Launches the kernel the plan names.
 template <bool GRP>
-static void wb_launch(WgBfParams& P, const typename WgGroupArg<GRP>::type& GR, const srk_conv_desc& d, const WbPlan& pl,
-                      dim3 grid, size_t lds_half, bool spec, hipStream_t s) {
-  size_t tr_lds = 0;
-  switch (pl.cfg) {
-    case 0:
-      if (wt_setup(P, d, pl, spec, tr_lds)) { wt_launch<GRP>(P, GR, grid, tr_lds, s); break; }
-      wb_launch_t<GRP, 2, 2, 2>(P, GR, grid, lds_half, spec, s);
-      break;
-    case 1: wb_launch_t<GRP, 4, 1, 2>(P, GR, grid, lds_half, spec, s); break;
-    default: wb_launch_t<GRP, 4, 1, 1>(P, GR, grid, lds_half, spec, s); break;
+static void wb_launch(const srk_wgrad_plan& L, const WgBfParams& P, const typename WgGroupArg<GRP>::type& GR, hipStream_t s) {
+  note_kernel("%s", L.name);
+  const dim3 grid(L.grid_x, L.grid_y, L.grid_z);
+  if (L.kernel == SRK_WGRAD_KERNEL_TR) return launch_lds<&k_wgrad_tr<GRP>>(grid, dim3(L.block), L.lds_bytes, s, P, GR);
+  switch (L.cfg) {
+    case 0: return wb_launch_t<GRP, 2, 2, 2>(L, P, GR, grid, s);
+    case 1: return wb_launch_t<GRP, 4, 1, 2>(L, P, GR, grid, s);
+    default: return wb_launch_t<GRP, 4, 1, 1>(L, P, GR, grid, s);
   }
 }
 
@@ -1824,29 +1687,22 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce_grouped(const float* __res
 
 int conv_wgrad_bf(const srk_conv_desc& d, const float* x, const float* dy, const srk_bwd_mask* mask, float* dw,
                   float* db, float beta, void* ws, size_t ws_bytes, hipStream_t s) {
-  WbPlan pl = wb_plan(d);
-  if (!pl.ok) {
+  const float* mask_y = mask ? mask->y : nullptr;
+  const srk_wgrad_plan L = conv_wgrad_bf_plan(d, 1, false, aligned16(x), aligned16(dy, mask_y), 0);
+  if (!L.ok) {
     set_error("conv_wgrad_bf: shape not covered");
     return SRK_ERR_UNSUPPORTED;
   }
-  const size_t slab_bytes = (size_t)wb_split(pl, 1, nullptr) * d.KH * d.KW * d.Cin * d.Cout * sizeof(float);
-  const size_t need = slab_bytes + conv_bias_grad_ws(d);
-  if (!ws || ws_bytes < need) {
-    set_error("conv_wgrad_bf: workspace %zu < %zu", ws_bytes, need);
+  if (!ws || ws_bytes < L.ws_bytes) {
+    set_error("conv_wgrad_bf: workspace %zu < %zu", ws_bytes, (size_t)L.ws_bytes);
     return SRK_ERR_WORKSPACE;
   }
-  bool spec = false;
-  const int G = wb_split(pl, 1, &spec);
-  const float* mask_y = mask ? mask->y : nullptr;
-  const bool vec_x = (d.Cin % 4 == 0) && ((uintptr_t)x % 16 == 0);
-  const bool vec_y = (d.Cout % 4 == 0) && ((uintptr_t)dy % 16 == 0) && (!mask_y || (uintptr_t)mask_y % 16 == 0);
-  size_t lds_half = 0;
-  WgBfParams P = wb_params(d, pl, G, spec, vec_x, vec_y, d.dy_ps_r > 1 ? d.dy_ps_r : 0, ws, slab_bytes, db != nullptr, lds_half);
+  WgBfParams P = wb_params(d, L, ws, db != nullptr);
   P.x = x; P.dy = dy; P.mask_y = mask_y; P.mask_slope = mask ? mask->slope : 0.f;
-  wb_launch<false>(P, WgNoGroup{0}, d, pl, dim3(G, pl.gy, pl.gz), lds_half, spec, s);
+  wb_launch<false>(L, P, WgNoGroup{0}, s);
   int rc = check_launch("conv_wgrad_bf");
   if (rc) return rc;
-  return conv_wgrad_reduce_launch((const float*)ws, dw, G, d.Cout, d.Cin, d.KH, d.KW, 0, beta, P.bias_partial, db, d.Cout,
+  return conv_wgrad_reduce_launch((const float*)ws, dw, L.G, d.Cout, d.Cin, d.KH, d.KW, 0, beta, P.bias_partial, db, d.Cout,
                                   P.dy_ps_r, s);
 }
 
@@ -1857,34 +1713,16 @@ int conv_wgrad_bf(const srk_conv_desc& d, const float* x, const float* dy, const
 // work.  With the layer axis in the grid every block walks ~30-40 tiles of ONE layer (double-buffered by the
 // wave-specialised variant), writes one slab, and 33 layers cost two launches instead of 66.
 // ---------------------------------------------------------------------------------------------
-size_t conv_wgrad_bf_grouped_ws(const srk_conv_desc& d, int n) {
-  WbPlan pl = wb_plan(d);
-  if (!pl.ok || n < 1) return 0;
-  return (size_t)n * wb_split(pl, n, nullptr) * ((size_t)d.KH * d.KW * d.Cin * d.Cout + d.Cout) * sizeof(float);
-}
+size_t conv_wgrad_bf_grouped_ws(const srk_conv_desc& d, int n) { return conv_wgrad_bf_plan(d, n, true, true, true, 0).ws_bytes; }
 
 int conv_wgrad_bf_grouped(const srk_conv_desc& d, int n, const float* const* xs, const float* const* dys,
                           const srk_bwd_mask* masks, float* const* dws, float* const* dbs, float beta, void* ws,
                           size_t ws_bytes, hipStream_t s) {
-  WbPlan pl = wb_plan(d);
-  if (!pl.ok || n < 1 || n > WB_MAXGROUP || d.dy_ps_r > 1) {
-    set_error("conv_wgrad_bf_grouped: shape / group size not covered");
-    return SRK_ERR_UNSUPPORTED;
-  }
-  bool spec = false;
-  const int G = wb_split(pl, n, &spec);
-  const size_t elems = (size_t)d.KH * d.KW * d.Cin * d.Cout;
-  const size_t slab_bytes = (size_t)n * G * elems * sizeof(float);
-  const size_t need = slab_bytes + (size_t)n * G * d.Cout * sizeof(float);
-  if (!ws || ws_bytes < need) {
-    set_error("conv_wgrad_bf_grouped: workspace %zu < %zu", ws_bytes, need);
-    return SRK_ERR_WORKSPACE;
-  }
-  const bool has_bias = dbs && dbs[0];
+  const bool has_bias = n >= 1 && dbs && dbs[0];
   WgGroup GR{};
   WgGroupOut GO{};
-  bool vec_x = d.Cin % 4 == 0, vec_y = d.Cout % 4 == 0;
-  for (int l = 0; l < n; ++l) {
+  bool x_aligned = true, y_aligned = true;
+  for (int l = 0; l < n && l < WB_MAXGROUP; ++l) {
     if (!xs[l] || !dys[l] || !dws[l] || (has_bias != (dbs && dbs[l] != nullptr))) {
       set_error("conv_wgrad_bf_grouped: null tensor or mixed bias / bias-free layers in one group (layer %d)", l);
       return SRK_ERR_BAD_ARG;
@@ -1895,13 +1733,24 @@ int conv_wgrad_bf_grouped(const srk_conv_desc& d, int n, const float* const* xs,
     GR.L[l].mask_slope = masks ? masks[l].slope : 0.f;
     GO.L[l].dw = dws[l];
     GO.L[l].db = has_bias ? dbs[l] : nullptr;
-    vec_x = vec_x && ((uintptr_t)xs[l] % 16 == 0);
-    vec_y = vec_y && ((uintptr_t)dys[l] % 16 == 0) && (!GR.L[l].mask_y || (uintptr_t)GR.L[l].mask_y % 16 == 0);
+    x_aligned = x_aligned && aligned16(xs[l]);
+    y_aligned = y_aligned && aligned16(dys[l], GR.L[l].mask_y);
   }
-  size_t lds_half = 0;
-  WgBfParams P = wb_params(d, pl, G, spec, vec_x, vec_y, 0, ws, slab_bytes, has_bias, lds_half);
+  const srk_wgrad_plan L = conv_wgrad_bf_plan(d, n, true, x_aligned, y_aligned, 0);
+  if (!L.ok) {
+    set_error("conv_wgrad_bf_grouped: shape / group size not covered");
+    return SRK_ERR_UNSUPPORTED;
+  }
+  const int G = L.G;
+  const size_t elems = (size_t)d.KH * d.KW * d.Cin * d.Cout;
+  const size_t need = L.slab_bytes + (size_t)n * G * d.Cout * sizeof(float);
+  if (!ws || ws_bytes < need) {
+    set_error("conv_wgrad_bf_grouped: workspace %zu < %zu", ws_bytes, need);
+    return SRK_ERR_WORKSPACE;
+  }
+  const WgBfParams P = wb_params(d, L, ws, has_bias);
   const float* bias_ws = P.bias_partial;
-  wb_launch<true>(P, GR, d, pl, dim3(n * G, pl.gy, pl.gz), lds_half, spec, s);
+  wb_launch<true>(L, P, GR, s);
   int rc = check_launch("conv_wgrad_bf_grouped");
   if (rc) return rc;
   if (wgrad_reduce_deferring()) {   // queued: one job per layer, summed in this kernel's order by the merged launch

@@ -1,16 +1,16 @@
-"""TEST INFRASTRUCTURE: the phase decomposition of strided TRANS gathers (csrc/conv_tile.h, for_each_phase) in plain
-Python, and the case table of the strided / transposed convolution tests.
+"""TEST INFRASTRUCTURE: the library's phase decomposition of strided TRANS gathers (csrc/conv_tile.h: phase_axis,
+for_each_trans_phase, which for_each_phase launches from), and the case table of the strided / transposed convolution tests.
 
 A ConvTranspose2d forward and the data gradient of a strided Conv2d are "TRANS gathers": out[oy] = sum over kh of
-in[(oy + p - kh) / s] * w[kh] where the division is exact.  for_each_phase splits one into s x s stride-1 problems, one
-per output phase; `phases()` is that function transcribed line by line (host integer arithmetic only, it never calls the
-library), `phases_1d()` the same lines for one axis.  tests/test_strided_phase_cpu.py runs a transposed convolution
-phase by phase through them against torch in float64, and checks every declared property of the table below against them;
-tests/test_strided_gpu.py runs the table on the device.
+in[(oy + p - kh) / s] * w[kh] where the division is exact.  The library splits one into s x s stride-1 problems, one per
+output phase; `phases()` and `phases_1d()` ask it for them through srk_trans_phases / srk_trans_phase_axis, host-only calls
+that need no GPU.  tests/test_strided_phase_cpu.py runs a transposed convolution phase by phase through them against torch
+in float64, and checks every declared property of the table below against them; tests/test_strided_gpu.py runs the table
+on the device.
 
 CASES: one row per (kernel family, block configuration, arithmetic, epilogue, phase geometry).  A row's `props` are the
-edges it is in the table for -- the CPU test recomputes them from the mirror, so a row can neither claim an edge it does
-not have nor have one it does not claim:
+edges it is in the table for -- the CPU test recomputes them from the library's phases, so a row can neither claim an edge
+it does not have nor have one it does not claim:
   zero_tap     a phase with no tap at all (kernel smaller than the stride): its outputs are the epilogue of zero
   skipped      fewer than s x s phases run (oy0 >= OH or ox0 >= OW)
   uneven_taps  the phases that have taps differ in their tap counts
@@ -20,58 +20,40 @@ Shapes: spatial sizes 1 .. 40, N 1 .. 3, the smallest at which the row's kernel 
 import collections
 
 
+def _lib():
+    from pytorch_super_resolution_model_collection_amd import _lib as L
+    return L
+
+
 def out_dim(n, k, stride, pad, transposed, out_pad):
     """srk_conv_out_dim"""
-    if n <= 0 or k <= 0 or stride <= 0 or pad < 0:
-        return -1
-    if not transposed:
-        return (n + 2 * pad - k) // stride + 1
-    return (n - 1) * stride - 2 * pad + k + out_pad
+    return _lib().load().srk_conv_out_dim(n, k, stride, pad, int(transposed), out_pad)
 
 
 Phase = collections.namedtuple("Phase", "oy0 ox0 PH PW KHv KWv iy0 ix0 wh0 wdh ww0 wdw")
 
 
+def _query(fn, record, args, most):
+    out = (record * most)()
+    out[0].struct_size = record().struct_size
+    n = fn(*(args + (out, most)))
+    assert 0 <= n <= most, (n, _lib().load().srk_last_error_string())
+    return out[:n]
+
+
 def phases(KH, KW, stride, pad, OH, OW):
-    """for_each_phase's TRANS branch: this launch produces outputs (oy0 + r*st, ox0 + c*st), r < PH, c < PW; virtual tap
-    (u, v) reads input (r + iy0 + u, c + ix0 + v) and weight tap (wh0 + wdh*u, ww0 + wdw*v)."""
-    out = []
-    st = stride
-    for py in range(st):
-        oy0 = (((py - pad) % st) + st) % st
-        if oy0 >= OH:
-            continue
-        KHv = (KH - py + st - 1) // st if py < KH else 0
-        by = (oy0 + pad - py) // st
-        for px in range(st):
-            ox0 = (((px - pad) % st) + st) % st
-            if ox0 >= OW:
-                continue
-            KWv = (KW - px + st - 1) // st if px < KW else 0
-            bx = (ox0 + pad - px) // st
-            PH = (OH - oy0 + st - 1) // st
-            PW = (OW - ox0 + st - 1) // st
-            if KHv == 0 or KWv == 0:
-                out.append(Phase(oy0, ox0, PH, PW, 0, 0, 0, 0, 0, 0, 0, 0))
-            else:
-                out.append(Phase(oy0, ox0, PH, PW, KHv, KWv, by - (KHv - 1), bx - (KWv - 1),
-                                 py + st * (KHv - 1), -st, px + st * (KWv - 1), -st))
-    return out
+    """srk_trans_phases: this launch produces outputs (oy0 + r*st, ox0 + c*st), r < PH, c < PW; virtual tap (u, v) reads
+    input (r + iy0 + u, c + ix0 + v) and weight tap (wh0 + wdh*u, ww0 + wdw*v)."""
+    L = _lib()
+    return [Phase(*(getattr(q, f) for f in Phase._fields))
+            for q in _query(L.load().srk_trans_phases, L.Phase, (KH, KW, stride, pad, OH, OW), stride * stride)]
 
 
 def phases_1d(K, stride, pad, O):
-    """one axis of phases(): (o0, P, Kv, i0, w0, wd) per phase that runs"""
-    out = []
-    st = stride
-    for py in range(st):
-        o0 = (((py - pad) % st) + st) % st
-        if o0 >= O:
-            continue
-        Kv = (K - py + st - 1) // st if py < K else 0
-        b = (o0 + pad - py) // st
-        P = (O - o0 + st - 1) // st
-        out.append((o0, P, 0, 0, 0, 0) if Kv == 0 else (o0, P, Kv, b - (Kv - 1), py + st * (Kv - 1), -st))
-    return out
+    """srk_trans_phase_axis, one axis of phases(): (o0, P, Kv, i0, w0, wd) per phase that runs"""
+    L = _lib()
+    return [(a.o0, a.P, a.Kv, a.i0, a.w0, a.wd)
+            for a in _query(L.load().srk_trans_phase_axis, L.PhaseAxis, (K, stride, pad, O), stride)]
 
 
 # ---- the GPU table ---------------------------------------------------------------------------------------------------
@@ -295,7 +277,7 @@ def axis_reached(K, stride, pad, O, I):
 
 
 def properties(c):
-    """the row's edges, recomputed from the mirror"""
+    """the row's edges, recomputed from the library's phases"""
     props = set()
     if c.kind == "wgrad":
         return props

@@ -4,7 +4,7 @@ srk_conv2d_backward_data, srk_conv2d_backward_weight).
 A ConvTranspose2d forward and the data gradient of a strided Conv2d are TRANS gathers that csrc/conv_tile.h for_each_phase
 splits into s x s output phases, each with its own tap count, output origin, extent, input origin and reversed weight
 walk; every conv family consumes those parameters.  The rows are the table of tests/strided_phase_ref.py (CASES; its
-docstring names the edges, tests/test_strided_phase_cpu.py checks each row's against a Python mirror of for_each_phase):
+docstring names the edges, tests/test_strided_phase_cpu.py checks each row's against the library's own phase decomposition):
 zero-tap phases, skipped phases, phases of several ragged tiles, unequal tap counts, dx rows no dy reaches, the phased
 store under bias / LeakyReLU / per-channel PReLU / residual, unaligned tensors -- on k_conv_bfd_mp, k_conv_bfd (small
 block with 1 .. 4 channel waves, the large blocks, bf16x3 / bf16x6 / f16x3), k_conv_bf3, k_conv_tapn (one tap group and

@@ -1,7 +1,8 @@
-"""The phase decomposition of strided TRANS gathers (csrc/conv_tile.h for_each_phase, mirrored by
-tests/strided_phase_ref.py) without a GPU: a transposed convolution computed phase by phase in float64 numpy -- every
-output element written exactly once into a NaN-filled tensor -- against torch.nn.functional.conv_transpose{1,2}d, over
-every geometry of a small grid; and the declared edges of the GPU table against the mirror.
+"""The phase decomposition of strided TRANS gathers (csrc/conv_tile.h: what for_each_phase launches from, asked of the
+library through tests/strided_phase_ref.py) without a GPU: a transposed convolution computed phase by phase in float64
+numpy -- every output element written exactly once into a NaN-filled tensor -- against
+torch.nn.functional.conv_transpose{1,2}d, over every geometry of a small grid; and the declared edges of the GPU table
+against the library's phases.
 
 The sweeps' sizes are asserted, so they cannot shrink without notice:
   1-D  stride 1..4, kernel 1..9, padding 0..k-1, output padding 0..s-1, input 1..7:  2871 problems with a non-empty
@@ -14,7 +15,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import __graft_entry__
 import strided_phase_ref as R
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _built():
+    __graft_entry__.build()
 
 
 def _deconv_1d_by_phase(x, w, s, p, O):
@@ -141,7 +148,7 @@ def test_table_covers_what_it_is_for():
     assert {c.prefix[:len("k_conv_bfd<1,1,1")] for c in fwd if c.prefix.startswith("k_conv_bfd<1,1,")} == \
         {"k_conv_bfd<1,1,%d" % now for now in (1, 2, 3, 4)}
     assert sum(c.algo == "f16x3" for c in fwd) == 2 and sum(c.algo == "bf16x6" and "SRK_BFD_SMALL" in dict(c.env) for c in fwd) == 2
-    # the phase count in k_conv_bfd_mp's name is the mirror's
+    # the phase count in k_conv_bfd_mp's name is the library's
     for c in R.CASES:
         if c.prefix.startswith("k_conv_bfd_mp<") and c.prefix.endswith("x4"):
             assert len(R.case_phases(c)) == 4, c.id

@@ -3,8 +3,8 @@ configurations, per-tile and wave-specialised, both K loops, both staging modes,
 pixel-shuffled dY, single and grouped launches) against torch's float64 gradient, through the C ABI
 (srk_conv2d_backward_weight[_grouped]) so that pointer alignment and db == NULL are the test's choice.  The shapes are
 the table of tests/wgrad_plan_ref.py (CASES): the smallest batch at which the planner picks the row's variant on 256 CUs;
-tests/test_wgrad_plan_cpu.py checks the table against a Python mirror of the planner, this module checks it against
-srk_last_kernel_name().  Then the exact-fp32 kernels (k_wgrad_mfma, algo = mfma_fp32) at the same shapes, where their
+tests/test_wgrad_plan_cpu.py checks the table against the library's planner (srk_conv2d_backward_weight_plan), this module
+checks table and planner against srk_last_kernel_name().  Then the exact-fp32 kernels (k_wgrad_mfma, algo = mfma_fp32) at the same shapes, where their
 blocks walk more than one tile (ntiles ~ 500 .. 3000 against <= 512 slabs).
 
 Inputs: oracle.fill.randn, the outermost two rows and columns of x, dY and the mask source times 4 (border and halo terms
@@ -41,7 +41,8 @@ Which row runs which kernel / branch (k_wgrad_bf<CIT,COW,NTW,...>; "plain" = sta
                 scalar: 1-channel tails / x / mask off a boundary     17 c9_33, 18 x_unaligned, 20 mask_unaligned
   <.,tile>      swizzled grid / scalar tail / unaligned / ps dY       33 tile_swizzle, 34 tile_scalar, 35 tile_unaligned,
                                                                       36 tile_ps_C16
-(`prefetch` without `ring` cannot be planned: test_wgrad_plan_cpu.py::test_no_plannable_tile_prefetches_without_the_ring.)
+(`prefetch` without `ring` cannot be planned: the static_assert of csrc/conv_wgrad_plan.h, and
+test_wgrad_plan_cpu.py::test_no_plannable_tile_prefetches_without_the_ring.)
 
 Measured on an MI355X (profiles/wgrad_bf_parity.txt has every row), worst error / bar:
   bf16x3  dw  0.087 (row 25) .. 0.211 (row 34) of the 1e-4 bar (a CPU emulation of the 3-term split: 0.12 .. 0.14)

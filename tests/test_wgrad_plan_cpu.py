@@ -1,17 +1,20 @@
-"""The case table of tests/test_wgrad_bf_gpu.py against the Python mirror of the weight-gradient planner
-(tests/wgrad_plan_ref.py), for the 256 CUs of an MI355X.  Runs anywhere: host arithmetic only.
+"""The case table of tests/test_wgrad_bf_gpu.py against the library's weight-gradient planner (csrc/conv_wgrad_plan.h,
+asked through srk_conv2d_backward_weight_plan), for the 256 CUs of an MI355X.  Runs anywhere: the query is host arithmetic.
 
 The GPU test asserts srk_last_kernel_name() per row, so a row that drifted off its branch fails there too -- but only
 on a GPU.  Here the drift shows on every machine, together with which variants the table as a whole still reaches."""
-import os
-import re
+import itertools
 
 import pytest
 
+import __graft_entry__
 import wgrad_plan_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "pytorch_super_resolution_model_collection_amd", "csrc", "conv_wgrad_bf16.hip")
+
+@pytest.fixture(scope="module", autouse=True)
+def _built():
+    __graft_entry__.build()
+
 
 # every k_wgrad_bf variant the table must reach (what srk_last_kernel_name() reports, "k_wgrad_bf<...>")
 REQUIRED = {
@@ -65,26 +68,18 @@ def test_table_reaches_every_required_variant():
 
 
 def test_no_plannable_tile_prefetches_without_the_ring():
-    """For every tile shape wb_plan can choose (any configuration, kernel height, width and height inside the LDS
-    budget) the ring fits, and so do two buffer sets: `prefetch && !ring` is unreachable, and wb_split's LDS clause
-    never decides."""
-    shapes = 0
-    for cfg in R.CFG:
-        for KH in (1, 2, 3):
-            for OH in range(1, 18):
-                for TWo, TH, lds in R.tile_candidates(cfg, KH, OH, 6 * 8):
-                    shapes += 1
-                    assert R.ring_bytes(cfg, TH, TWo * 8, KH) > 0, (cfg, KH, TWo, TH)
-                    assert 2 * lds + 8 * 1024 <= 160 * 1024, (cfg, KH, TWo, TH)
-            # and every tile inside the budget, whether the search would stop at it or not
-            for TWo in range(1, 7):
-                for TH in range(1, 16 // TWo + 1):
-                    HH, HWp, TW = TH + KH - 1, TWo * 8 + 8, TWo * 8
-                    CIB, COB, _ = R.CFG[cfg]
-                    lds = (2 * CIB * R.round_8odd(HH * HWp) + 2 * COB * R.round_8odd(TH * TW + 8)) * 2
-                    if lds <= R.LDS_BUDGET and TH * TWo <= R.MAXOCT:
-                        assert R.ring_bytes(cfg, TH, TW, KH) > 0 and 2 * lds + 8 * 1024 <= 160 * 1024, (cfg, KH, TWo, TH)
-    assert shapes > 100
+    """conv_wgrad_plan.h asserts at compile time that every tile inside the LDS budget has room for the ring and for two
+    buffer sets; here the planner is asked over a grid of problems that reaches every tile height and width it can
+    choose: no plan has `prefetch && !ring`, and wb_split's LDS clause never decides."""
+    plans = 0
+    widths = (1, 8, 9, 16, 17, 24, 25, 32, 33, 40, 41, 48)
+    for cout, k, OH, OW in itertools.product((64, 32, 16), (1, 2, 3), range(1, 18), widths):
+        p = R.plan(64, OH + k - 1, OW + k - 1, 64, cout, k, k, 0)
+        assert p is not None, (cout, k, OH, OW)
+        plans += 1
+        assert not (p.prefetch and not p.ring), (cout, k, OH, OW, p)
+        assert 2 * p.lds + 8 * 1024 <= 160 * 1024, (cout, k, OH, OW, p)
+    assert plans == 1836
 
 
 def test_idle_ring_blocks_formula():
@@ -93,22 +88,3 @@ def test_idle_ring_blocks_formula():
     assert (p.ntiles, p.G, p.idle_blocks) == (515, 256, 84)
     per = R.cdiv(p.ntiles, p.G)
     assert per == 3 and sum(1 for b in range(p.G) if b * per < p.ntiles) == p.G - p.idle_blocks
-
-
-def test_mirror_constants_are_the_sources():
-    """The mirror does not call the library; its constants are read off the planner's source here, so that a change
-    there fails this test instead of silently moving the table off its branches."""
-    with open(SRC) as f:
-        src = f.read()
-
-    def const(pattern):
-        m = re.search(pattern, src)
-        assert m, pattern
-        return int(m.group(1))
-    assert const(r"kWbLdsBudget = (\d+) \* 1024") * 1024 == R.LDS_BUDGET
-    assert const(r"constexpr int WB_MAXOCT = (\d+);") == R.MAXOCT
-    assert const(r"constexpr int WB_SST = (\d+);") == R.SST
-    assert const(r"constexpr int WB_MAXGROUP = (\d+);") == R.MAXGROUP
-    assert "WB_PIT = 1024 / WB_SST" in src and "/ 3136.0" in src
-    assert "2 * pl.lds + 8 * 1024 <= 160 * 1024 && pl.ntiles >= 2 * g1" in src
-    assert "bytes + 8 * 1024 <= 160 * 1024 ? bytes : 0" in src
