@@ -438,6 +438,18 @@ int srk_sgd_step(float* p, const float* g, float* momentum_buf, size_t n, float 
 int srk_adam_step(float* p, const float* g, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1,
                   float beta2, float eps, float weight_decay, int32_t* step_dev, const float* lr_dev,
                   const float* grad_scale_dev, void* stream);
+/* srk_sgd_step / srk_adam_step that also keep an exponential moving average of the parameters (new entry points only:
+ * the two above and srk_version() are unchanged).  `ema` is a buffer laid out like `p`; after the parameter update, from
+ * the new value in registers (p is not read again): ema = ema + (1 - ema_decay) * (p_new - ema), a subtraction, a
+ * multiply and an add in fp32.  p, the optimizer's buffers and step_dev come out bit-equal to the plain entry point's.
+ * The 16-byte form needs `ema` on a 16-byte boundary like the other buffers.  SRK_REQUIRE errors: ema == NULL,
+ * ema_decay outside [0, 1) (NaN included). */
+int srk_sgd_step_ema(float* p, const float* g, float* momentum_buf, size_t n, float lr, float momentum,
+                     float weight_decay, int nesterov, int first_step, const float* lr_dev,
+                     const float* grad_scale_dev, float* ema, float ema_decay, void* stream);
+int srk_adam_step_ema(float* p, const float* g, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1,
+                      float beta2, float eps, float weight_decay, int32_t* step_dev, const float* lr_dev,
+                      const float* grad_scale_dev, float* ema, float ema_decay, void* stream);
 /* torch.nn.utils.clip_grad_norm (vdsr.py:149): *norm_out = ||g||_2; *scale_out = min(1, max_norm/(norm+1e-6)). */
 size_t srk_grad_norm_workspace_bytes(void);
 int srk_grad_norm_clip(const float* g, size_t n, float max_norm, float* norm_out, float* scale_out, void* workspace,

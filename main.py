@@ -11,7 +11,11 @@ and --self_ensemble (--test_single, --test_only and the test() after training ru
 self-ensemble, "EDSR+": the net on the eight flips / rotations, transformed back and averaged) and --ssim_weight A (train
 on (1 - A) * the model's pixel loss + A * (1 - SSIM), A in [0, 1], default 0; every model but SRGAN and DRCN; the logged
 loss is the mixed one) and --vgg_weights PATH (SRGAN: a torchvision vgg19 state_dict; the logged G loss gains the reference's
-VGG feature term) with --perceptual (that term trains the generator) and --vgg_loss_weight W (its weight, default 6e-3).
+VGG feature term) with --perceptual (that term trains the generator) and --vgg_loss_weight W (its weight, default 6e-3)
+and --resume [PATH] (continue training from the training-state file a run writes beside its checkpoints at every
+--save_epochs boundary and at its end; without PATH this run's own <save_dir>/model/<model_name>_train_state.pkl) and
+--ema_decay D (the optimizer kernel also keeps an exponential moving average of the weights, saved beside every
+checkpoint as ..._ema.pkl; D in [0, 1), default 0: none; not DRCN) with --use_ema (--test_only / --test_single load it).
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N main.py ..."""
 import argparse
 import os
@@ -53,6 +57,17 @@ def _non_negative(text):
         v = float('nan')
     if not 0.0 <= v < float('inf'):
         raise argparse.ArgumentTypeError("--vgg_loss_weight takes a number >= 0, got %r" % (text,))
+    return v
+
+
+def _ema_decay(text):
+    """--ema_decay: a number in [0, 1) (NaN fails both comparisons)."""
+    try:
+        v = float(text)
+    except ValueError:
+        v = float('nan')
+    if not 0.0 <= v < 1.0:
+        raise argparse.ArgumentTypeError("--ema_decay takes a number in [0, 1), got %r" % (text,))
     return v
 
 
@@ -118,7 +133,22 @@ def parse_args(argv=None):
                         'Needs --vgg_weights and --num_channels 3')
     p.add_argument('--vgg_loss_weight', type=_non_negative, default=6e-3, metavar='W',
                    help='SRGAN: weight of the VGG feature term in the G loss (default 6e-3, srgan.py:306); W >= 0')
+    p.add_argument('--resume', type=str, nargs='?', const='auto', default=None, metavar='PATH',
+                   help='continue training from a training-state file (weights, optimizer state, learning rates, epoch, '
+                        'loss history, random generators): PATH, or without one the file this run writes, '
+                        '<save_dir>/model/<model_name>_train_state.pkl.  Runs continue at epoch boundaries only')
+    p.add_argument('--ema_decay', type=_ema_decay, default=0.0, metavar='D',
+                   help='keep an exponential moving average of the weights, ema += (1 - D) * (w - ema) after every step, '
+                        'inside the optimizer kernel; written beside every checkpoint as ..._ema.pkl.  D in [0, 1), '
+                        'default 0: none.  Not for DRCN')
+    p.add_argument('--use_ema', action='store_true',
+                   help='--test_only / --test_single: load the EMA weights (..._ema.pkl) instead of the plain checkpoint')
     args = p.parse_args(argv)
+    if args.ema_decay > 0 and args.model_name == 'DRCN':
+        p.error('--ema_decay %g: DRCN keeps no EMA of its weights (its combine weights w train outside the flat '
+                'parameter buffer); use --ema_decay 0 or another model' % args.ema_decay)
+    if args.resume and args.test_only:
+        p.error('--resume continues a training run; --test_only does not train')
     if (args.perceptual or args.vgg_weights) and args.model_name != 'SRGAN':
         p.error('%s: only SRGAN has a VGG feature term, not %s'
                 % ('--perceptual' if args.perceptual else '--vgg_weights', args.model_name))

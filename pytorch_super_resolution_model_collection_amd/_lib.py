@@ -152,6 +152,10 @@ _PROTOTYPES = {
     "srk_sgd_step": (c_int, [c_f, c_f, c_f, c_size, c_float, c_float, c_float, c_int, c_int, c_f, c_f, c_vp]),
     "srk_adam_step": (c_int, [c_f, c_f, c_f, c_f, c_size, c_float, c_float, c_float, c_float, c_float, c_vp, c_f,
                               c_f, c_vp]),
+    "srk_sgd_step_ema": (c_int, [c_f, c_f, c_f, c_size, c_float, c_float, c_float, c_int, c_int, c_f, c_f, c_f, c_float,
+                                 c_vp]),
+    "srk_adam_step_ema": (c_int, [c_f, c_f, c_f, c_f, c_size, c_float, c_float, c_float, c_float, c_float, c_vp, c_f,
+                                  c_f, c_f, c_float, c_vp]),
     "srk_grad_norm_workspace_bytes": (c_size, []),
     "srk_grad_norm_clip": (c_int, [c_f, c_size, c_float, c_f, c_f, c_vp, c_vp]),
     "srk_bn_stats": (c_int, [c_f, c_vp, c_size, c_int, c_vp, c_vp]),

@@ -20,6 +20,23 @@ __device__ __forceinline__ float mul_then_add(float a, float b, float c) {
   return a * b + c;
 }
 
+// Exponential moving average of a parameter, from the value the optimizer has just computed (still in a register):
+// ema + (1 - d) * (p - ema), a subtraction, a multiply and an add in fp32, three roundings whatever the context (see
+// mul_then_add).
+__device__ __forceinline__ float ema_update(float ema, float p_new, float one_minus_d) {
+#pragma clang fp contract(off)
+  const float diff = p_new - ema;
+  return ema + one_minus_d * diff;
+}
+// The optional last argument of k_sgd / k_adam.  The kernels take it as a parameter pack: without it the kernel has the
+// argument block, and the machine code, it had before there was an EMA (profiles/ema_asm.txt).
+struct EmaArg {
+  float* ema;
+  float one_minus_d;   // 1.f - ema_decay, rounded once on the host
+};
+__host__ __device__ __forceinline__ EmaArg ema_of() { return {nullptr, 0.f}; }
+__host__ __device__ __forceinline__ EmaArg ema_of(EmaArg a) { return a; }
+
 __device__ __forceinline__ void loss_term(int kind, float p, float t, float eps, float& val, float& grad) {
   const float d = p - t;
   switch (kind) {
@@ -95,13 +112,18 @@ __global__ __launch_bounds__(256) void k_loss_final(const double* __restrict__ p
 // ---------------------------------------------------------------------------------------------
 // Optimizers.  V = 4 (n % 4 == 0, aligned buffers): the same operations per element, four elements per thread and pass
 // (SRGAN-D's 23 M parameters under SGD: 184 -> ~100 us; the 4-byte loop moved 2.5 TB/s).
+// EMA (srk_sgd_step_ema / srk_adam_step_ema): the shadow weights `ema` are updated from the new parameter value in the
+// same pass, 8 more bytes per parameter and no launch of their own.  A compile-time switch (EMA, on when the kernel is
+// instantiated with an EmaArg): off, the kernel is the one srk_sgd_step / srk_adam_step have always launched.
 // ---------------------------------------------------------------------------------------------
-template <int V>
+template <int V, typename... Ema>
 __global__ __launch_bounds__(256) void k_sgd(float* __restrict__ p, const float* __restrict__ g,
                                              float* __restrict__ buf, size_t groups, float lr, float mom, float wd,
                                              int nesterov, int first, const float* __restrict__ lr_dev,
-                                             const float* __restrict__ gs_dev) {
+                                             const float* __restrict__ gs_dev, Ema... ema_arg) {
   typedef Vec<V> Q;
+  constexpr bool EMA = sizeof...(Ema) != 0;
+  const EmaArg ea = ema_of(ema_arg...);
   if (lr_dev) lr = *lr_dev;
   const float gs = gs_dev ? *gs_dev : 1.f;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < groups; i += (size_t)gridDim.x * 256) {
@@ -109,6 +131,8 @@ __global__ __launch_bounds__(256) void k_sgd(float* __restrict__ p, const float*
     const typename Q::T gi = Q::load(g, i);
     typename Q::T bi = {};
     if (mom != 0.f && !first) bi = Q::load(buf, i);   // (the first step must not read the buffer)
+    typename Q::T ei = {};
+    if constexpr (EMA) ei = Q::load(ea.ema, i);
 #pragma unroll
     for (int e = 0; e < V; ++e) {
       float d = Q::at(gi, e) * gs;
@@ -119,9 +143,11 @@ __global__ __launch_bounds__(256) void k_sgd(float* __restrict__ p, const float*
         d = nesterov ? d + mom * b : b;
       }
       Q::set(pi, e, Q::at(pi, e) - lr * d);
+      if constexpr (EMA) Q::set(ei, e, ema_update(Q::at(ei, e), Q::at(pi, e), ea.one_minus_d));
     }
     if (mom != 0.f) Q::store(buf, i, bi);
     Q::store(p, i, pi);
+    if constexpr (EMA) Q::store(ea.ema, i, ei);
   }
 }
 
@@ -159,13 +185,15 @@ __device__ __forceinline__ void adam_arrive(int32_t* __restrict__ step_dev, int3
 // The 16-byte form runs at most two blocks per CU (srk_adam_step): the arrival ticket is one atomic per block on one
 // word, and ~740 of them in the 4-byte form's grid made the folded step counter cost what the separate launch had
 // (EDSR: 19.4 vs 14.5 + 2.8 us).
-template <int V>
+template <int V, typename... Ema>
 __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float* __restrict__ g,
                                               float* __restrict__ m, float* __restrict__ v, size_t groups, float lr,
                                               float b1, float b2, float eps, float wd,
                                               int32_t* __restrict__ step_dev, const float* __restrict__ lr_dev,
-                                              const float* __restrict__ gs_dev) {
+                                              const float* __restrict__ gs_dev, Ema... ema_arg) {
   typedef Vec<V> Q;
+  constexpr bool EMA = sizeof...(Ema) != 0;
+  const EmaArg ea = ema_of(ema_arg...);
   if (lr_dev) lr = *lr_dev;
   const float gs = gs_dev ? *gs_dev : 1.f;
   const AdamStep st = adam_begin(step_dev, lr, b1, b2);
@@ -173,6 +201,8 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float
     typename Q::T pi = Q::load(p, i);
     const typename Q::T gv = Q::load(g, i);
     typename Q::T mi = Q::load(m, i), vi = Q::load(v, i);
+    typename Q::T ei = {};
+    if constexpr (EMA) ei = Q::load(ea.ema, i);
 #pragma unroll
     for (int e = 0; e < V; ++e) {
       float gi = Q::at(gv, e) * gs;
@@ -183,10 +213,12 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ p, const float
       Q::set(vi, e, ve);
       const float denom = sqrtf(ve) / st.bc2_sqrt + eps;
       Q::set(pi, e, Q::at(pi, e) - st.step_size * (me / denom));
+      if constexpr (EMA) Q::set(ei, e, ema_update(Q::at(ei, e), Q::at(pi, e), ea.one_minus_d));
     }
     Q::store(m, i, mi);
     Q::store(v, i, vi);
     Q::store(p, i, pi);
+    if constexpr (EMA) Q::store(ea.ema, i, ei);
   }
   adam_arrive(step_dev, st.count);
 }
@@ -248,30 +280,76 @@ extern "C" int srk_loss_forward_backward(int kind, const float* pred, const floa
   return check_launch("loss_forward_backward");
 }
 
+// One launcher per optimizer for the plain and the EMA entry point: the same form rule and the same grid.
+template <bool EMA>
+static int sgd_launch(float* p, const float* g, float* momentum_buf, size_t n, float lr, float momentum,
+                      float weight_decay, int nesterov, int first_step, const float* lr_dev,
+                      const float* grad_scale_dev, float* ema, float ema_decay, void* stream) {
+  SRK_REQUIRE(p && g && n > 0, "sgd_step: null pointer or empty");
+  SRK_REQUIRE(momentum == 0.f || momentum_buf, "sgd_step: momentum needs a buffer");
+  const bool vec = (n & 3) == 0 && aligned16(p, g, momentum_buf, ema);
+  const size_t groups = vec ? n / 4 : n;
+  const unsigned nb = vec ? grid_for(groups, 256 * 2, 65535) : grid_for(groups, 256 * 8, kMaxPartials);   // two float4 / eight floats per thread
+  if constexpr (EMA)
+    hipLaunchKernelGGL((vec ? k_sgd<4, EmaArg> : k_sgd<1, EmaArg>), dim3(nb), dim3(256), 0, (hipStream_t)stream, p, g,
+                       momentum_buf, groups, lr, momentum, weight_decay, nesterov, first_step, lr_dev, grad_scale_dev,
+                       EmaArg{ema, 1.f - ema_decay});
+  else
+    hipLaunchKernelGGL(vec ? k_sgd<4> : k_sgd<1>, dim3(nb), dim3(256), 0, (hipStream_t)stream, p, g, momentum_buf,
+                       groups, lr, momentum, weight_decay, nesterov, first_step, lr_dev, grad_scale_dev);
+  return check_launch("sgd_step");
+}
+
+template <bool EMA>
+static int adam_launch(float* p, const float* g, float* exp_avg, float* exp_avg_sq, size_t n, float lr, float beta1,
+                       float beta2, float eps, float weight_decay, int32_t* step_dev, const float* lr_dev,
+                       const float* grad_scale_dev, float* ema, float ema_decay, void* stream) {
+  SRK_REQUIRE(p && g && exp_avg && exp_avg_sq && step_dev && n > 0, "adam_step: null pointer or empty");
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = n % 4 == 0 && aligned16(p, g, exp_avg, exp_avg_sq, ema);
+  const size_t groups = vec ? n / 4 : n;
+  const unsigned nb = vec ? grid_for(groups, 256 * 2, (size_t)2 * kNumCU) : grid_for(groups, 256 * 8, kMaxPartials);
+  if constexpr (EMA)
+    hipLaunchKernelGGL((vec ? k_adam<4, EmaArg> : k_adam<1, EmaArg>), dim3(nb), dim3(256), 0, s, p, g, exp_avg,
+                       exp_avg_sq, groups, lr, beta1, beta2, eps, weight_decay, step_dev, lr_dev, grad_scale_dev,
+                       EmaArg{ema, 1.f - ema_decay});
+  else
+    hipLaunchKernelGGL(vec ? k_adam<4> : k_adam<1>, dim3(nb), dim3(256), 0, s, p, g, exp_avg, exp_avg_sq, groups, lr,
+                       beta1, beta2, eps, weight_decay, step_dev, lr_dev, grad_scale_dev);
+  return check_launch("adam_step");
+}
+
 extern "C" int srk_sgd_step(float* p, const float* g, float* momentum_buf, size_t n, float lr, float momentum,
                             float weight_decay, int nesterov, int first_step, const float* lr_dev,
                             const float* grad_scale_dev, void* stream) {
-  SRK_REQUIRE(p && g && n > 0, "sgd_step: null pointer or empty");
-  SRK_REQUIRE(momentum == 0.f || momentum_buf, "sgd_step: momentum needs a buffer");
-  const bool vec = (n & 3) == 0 && aligned16(p, g, momentum_buf);
-  const size_t groups = vec ? n / 4 : n;
-  const unsigned nb = vec ? grid_for(groups, 256 * 2, 65535) : grid_for(groups, 256 * 8, kMaxPartials);   // two float4 / eight floats per thread
-  hipLaunchKernelGGL(vec ? k_sgd<4> : k_sgd<1>, dim3(nb), dim3(256), 0, (hipStream_t)stream, p, g, momentum_buf, groups,
-                     lr, momentum, weight_decay, nesterov, first_step, lr_dev, grad_scale_dev);
-  return check_launch("sgd_step");
+  return sgd_launch<false>(p, g, momentum_buf, n, lr, momentum, weight_decay, nesterov, first_step, lr_dev,
+                           grad_scale_dev, nullptr, 0.f, stream);
+}
+
+extern "C" int srk_sgd_step_ema(float* p, const float* g, float* momentum_buf, size_t n, float lr, float momentum,
+                                float weight_decay, int nesterov, int first_step, const float* lr_dev,
+                                const float* grad_scale_dev, float* ema, float ema_decay, void* stream) {
+  SRK_REQUIRE(ema, "sgd_step_ema: null ema buffer");
+  SRK_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, "sgd_step_ema: ema_decay %g outside [0, 1)", (double)ema_decay);
+  return sgd_launch<true>(p, g, momentum_buf, n, lr, momentum, weight_decay, nesterov, first_step, lr_dev,
+                          grad_scale_dev, ema, ema_decay, stream);
 }
 
 extern "C" int srk_adam_step(float* p, const float* g, float* exp_avg, float* exp_avg_sq, size_t n, float lr,
                              float beta1, float beta2, float eps, float weight_decay, int32_t* step_dev,
                              const float* lr_dev, const float* grad_scale_dev, void* stream) {
-  SRK_REQUIRE(p && g && exp_avg && exp_avg_sq && step_dev && n > 0, "adam_step: null pointer or empty");
-  hipStream_t s = (hipStream_t)stream;
-  const bool vec = n % 4 == 0 && aligned16(p, g, exp_avg, exp_avg_sq);
-  const size_t groups = vec ? n / 4 : n;
-  const unsigned nb = vec ? grid_for(groups, 256 * 2, (size_t)2 * kNumCU) : grid_for(groups, 256 * 8, kMaxPartials);
-  hipLaunchKernelGGL(vec ? k_adam<4> : k_adam<1>, dim3(nb), dim3(256), 0, s, p, g, exp_avg, exp_avg_sq, groups, lr,
-                     beta1, beta2, eps, weight_decay, step_dev, lr_dev, grad_scale_dev);
-  return check_launch("adam_step");
+  return adam_launch<false>(p, g, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step_dev, lr_dev,
+                            grad_scale_dev, nullptr, 0.f, stream);
+}
+
+extern "C" int srk_adam_step_ema(float* p, const float* g, float* exp_avg, float* exp_avg_sq, size_t n, float lr,
+                                 float beta1, float beta2, float eps, float weight_decay, int32_t* step_dev,
+                                 const float* lr_dev, const float* grad_scale_dev, float* ema, float ema_decay,
+                                 void* stream) {
+  SRK_REQUIRE(ema, "adam_step_ema: null ema buffer");
+  SRK_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, "adam_step_ema: ema_decay %g outside [0, 1)", (double)ema_decay);
+  return adam_launch<true>(p, g, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step_dev, lr_dev,
+                           grad_scale_dev, ema, ema_decay, stream);
 }
 
 extern "C" int srk_grad_norm_clip(const float* g, size_t n, float max_norm, float* norm_out, float* scale_out,

@@ -402,6 +402,14 @@ class PatchLoader(object):
         if seed is not None:
             self.gen.manual_seed(int(seed))
 
+    def state_dict(self):
+        """What an epoch boundary leaves of the loader: the shuffle generator (the crops and flips draw from Python's
+        global `random`, which whoever saves a training state saves with it).  Needs no GPU."""
+        return {"gen": self.gen.get_state().clone()}
+
+    def load_state_dict(self, sd):
+        self.gen.set_state(sd["gen"])
+
     def _shard_len(self):
         return -(-len(self.ds) // self.world)      # ceil: short ranks wrap around (torch's DistributedSampler rule)
 

@@ -216,12 +216,55 @@ class _Group(dict):
             self._owner._set_lr(v)
 
 
+def _check_ema_decay(d):
+    d = float(d or 0.0)
+    if not 0.0 <= d < 1.0:
+        raise ValueError("ema_decay %r must be in [0, 1) (main.py --ema_decay)" % (d,))
+    return d
+
+
+def _cpu(t):
+    return t.detach().to("cpu", copy=True)
+
+
+def _check_state(sd, kind, names=None, shapes=None):
+    """The checks every load_state_dict starts with: the optimizer kind, then (flat optimizers) the name set and the
+    shape of every per-parameter tensor.  ValueError names the first offender."""
+    if not isinstance(sd, dict) or sd.get("kind") != kind:
+        raise ValueError("optimizer state of kind %r cannot be loaded into %s"
+                         % (sd.get("kind") if isinstance(sd, dict) else type(sd).__name__, kind))
+    if names is None:
+        return
+    groups = [("state", sd.get("state") or {})]
+    if sd.get("ema") is not None:
+        groups.append(("ema", sd["ema"].get("params") or {}))
+    for what, per_name in groups:
+        for n in names:
+            if n not in per_name:
+                raise ValueError("optimizer state (%s) has no entry for parameter %r" % (what, n))
+        for n in per_name:
+            if n not in shapes:
+                raise ValueError("optimizer state (%s) names %r, which is not a parameter of this model" % (what, n))
+        for n in names:
+            ts = per_name[n].values() if isinstance(per_name[n], dict) else [per_name[n]]
+            for t in ts:
+                if tuple(t.shape) != shapes[n]:
+                    raise ValueError("optimizer state (%s) of parameter %r has shape %s, the parameter %s"
+                                     % (what, n, tuple(t.shape), shapes[n]))
+
+
 class _FlatOptimizer(object):
-    def __init__(self, params, lr):
+    kind = None
+    _state_buffers = ()    # names of the per-parameter flat buffers, which are also their keys in state_dict()
+
+    def __init__(self, params, lr, ema_decay=0.0):
         if not isinstance(params, FlatParams):
             params = FlatParams(params)
         self.flat = params
         dev = params.data.device
+        self.ema_decay = _check_ema_decay(ema_decay)
+        # the shadow weights: allocated once (captured graphs hold the pointer), a copy of the parameters to begin with
+        self.ema = params.data.clone() if self.ema_decay > 0 else None
         self.lr_dev = torch.tensor([float(lr)], dtype=torch.float32, device=dev)
         self.scale_dev = torch.ones(1, dtype=torch.float32, device=dev)   # gradient scale (clip / DP average)
         self.norm_dev = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -261,12 +304,83 @@ class _FlatOptimizer(object):
     def reset_grad_scale(self):
         self.scale_dev.fill_(1.0)
 
+    # -- exponential moving average of the weights (updated inside the step kernel) --------------------------------------
+    def ema_reset(self):
+        """The shadow becomes a copy of the current parameters, in place: after the parameters were replaced behind the
+        optimizer (a loaded checkpoint)."""
+        if self.ema is not None:
+            self.ema.copy_(self.flat.data)
+
+    def _views(self, buf):
+        """{parameter name: view of the flat buffer `buf` in the parameter's shape} -- the padding between is nobody's."""
+        f = self.flat
+        return {n: buf[o:o + p.numel()].view(p.shape) for n, p, o in zip(f.names, f.params, f.offsets)}
+
+    def ema_state_dict(self, module=None):
+        """module.state_dict() with every parameter replaced by its shadow value (buffers, BatchNorm's running statistics,
+        are the live ones).  Same keys and shapes; a key that is a second name of a shared parameter is found by the
+        parameter's identity, not by its name."""
+        if self.ema is None:
+            raise RuntimeError("ema_state_dict: this optimizer keeps no EMA (ema_decay == 0)")
+        module = self.flat.module if module is None else module
+        shadow = dict((id(p), v) for p, v in zip(self.flat.params, self._views(self.ema).values()))
+        by_key = {}
+        for prefix, m in module.named_modules(remove_duplicate=False):
+            for n, p in m._parameters.items():
+                if p is not None:
+                    by_key[(prefix + "." if prefix else "") + n] = p
+        out = module.state_dict()
+        for k in out:
+            if k in by_key:
+                if id(by_key[k]) not in shadow:
+                    raise ValueError("ema_state_dict: %r is not a parameter this optimizer updates" % (k,))
+                out[k] = shadow[id(by_key[k])].detach().clone()
+        return out
+
+    # -- the whole state, for a training-state file ---------------------------------------------------------------------
+    def _hyper(self):
+        raise NotImplementedError
+
+    def state_dict(self):
+        """Plain containers and CPU tensors only (loads with torch.load(weights_only=True)).  Per-parameter state is keyed
+        by FlatParams.names, each tensor in its parameter's shape: the file does not depend on the flat layout."""
+        bufs = [(b, self._views(getattr(self, b))) for b in self._state_buffers if getattr(self, b) is not None]
+        sd = {"kind": self.kind, "hyper": self._hyper(), "lr": float(self.param_groups[0]["lr"]),
+              "state": {n: {b: _cpu(v[n]) for b, v in bufs} for n in self.flat.names}}
+        if self.ema is not None:
+            sd["ema"] = {"decay": self.ema_decay, "params": {n: _cpu(v) for n, v in self._views(self.ema).items()}}
+        return sd
+
+    def load_state_dict(self, sd):
+        """In place: no buffer is replaced, so a captured graph of the step stays valid.  Not inside a capture."""
+        f = self.flat
+        _check_state(sd, self.kind, f.names, {n: tuple(p.shape) for n, p in zip(f.names, f.params)})
+        have = [b for b in self._state_buffers if getattr(self, b) is not None]
+        for n in f.names:
+            if sorted(sd["state"][n]) != sorted(have):
+                raise ValueError("optimizer state of parameter %r holds %s, this optimizer keeps %s"
+                                 % (n, sorted(sd["state"][n]), sorted(have)))
+        for b in have:
+            for n, v in self._views(getattr(self, b)).items():
+                v.copy_(sd["state"][n][b])
+        self.param_groups[0]["lr"] = float(sd["lr"])    # (reaches the device scalar)
+        if sd.get("ema") is not None and self.ema is not None:
+            for n, v in self._views(self.ema).items():
+                v.copy_(sd["ema"]["params"][n])
+        elif sd.get("ema") is not None:
+            print("optimizer state: the stored EMA weights are ignored (this run keeps none: --ema_decay 0)")
+        else:
+            self.ema_reset()
+
 
 class SGD(_FlatOptimizer):
     """torch.optim.SGD(lr, momentum, weight_decay, nesterov) — dampening 0 as in every reference call."""
 
-    def __init__(self, params, lr, momentum=0.0, weight_decay=0.0, nesterov=False):
-        super(SGD, self).__init__(params, lr)
+    kind = "sgd"
+    _state_buffers = ("momentum_buffer",)
+
+    def __init__(self, params, lr, momentum=0.0, weight_decay=0.0, nesterov=False, ema_decay=0.0):
+        super(SGD, self).__init__(params, lr, ema_decay)
         self.momentum, self.weight_decay, self.nesterov = float(momentum), float(weight_decay), bool(nesterov)
         # zero-initialised buffer: mom*0 + g == g, i.e. torch's "buf = clone(grad)" first step
         self.buf = torch.zeros_like(self.flat.data) if momentum != 0.0 else None
@@ -276,17 +390,32 @@ class SGD(_FlatOptimizer):
         ops.flush_wgrads()  # weight gradients still pending from the backward pass
         lib = _lib.load()
         f = self.flat
-        check(lib.srk_sgd_step(ptr(f.data), ptr(f.grad), ptr(self.buf), f.numel, 0.0, self.momentum,
-                               self.weight_decay, int(self.nesterov), 0, ptr(self.lr_dev), ptr(self.scale_dev),
-                               stream_ptr()), "srk_sgd_step")
+        if self.ema is None:
+            check(lib.srk_sgd_step(ptr(f.data), ptr(f.grad), ptr(self.buf), f.numel, 0.0, self.momentum,
+                                   self.weight_decay, int(self.nesterov), 0, ptr(self.lr_dev), ptr(self.scale_dev),
+                                   stream_ptr()), "srk_sgd_step")
+        else:
+            check(lib.srk_sgd_step_ema(ptr(f.data), ptr(f.grad), ptr(self.buf), f.numel, 0.0, self.momentum,
+                                       self.weight_decay, int(self.nesterov), 0, ptr(self.lr_dev), ptr(self.scale_dev),
+                                       ptr(self.ema), self.ema_decay, stream_ptr()), "srk_sgd_step_ema")
         f.mark_changed()
+
+    @property
+    def momentum_buffer(self):
+        return self.buf
+
+    def _hyper(self):
+        return {"momentum": self.momentum, "weight_decay": self.weight_decay, "nesterov": self.nesterov}
 
 
 class Adam(_FlatOptimizer):
     """torch.optim.Adam(lr, betas, eps, weight_decay) without amsgrad."""
 
-    def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
-        super(Adam, self).__init__(params, lr)
+    kind = "adam"
+    _state_buffers = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, ema_decay=0.0):
+        super(Adam, self).__init__(params, lr, ema_decay)
         self.betas, self.eps, self.weight_decay = (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
         self.exp_avg = torch.zeros_like(self.flat.data)
         self.exp_avg_sq = torch.zeros_like(self.flat.data)
@@ -297,10 +426,33 @@ class Adam(_FlatOptimizer):
         ops.flush_wgrads()  # weight gradients still pending from the backward pass
         lib = _lib.load()
         f = self.flat
-        check(lib.srk_adam_step(ptr(f.data), ptr(f.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), f.numel, 0.0,
-                                self.betas[0], self.betas[1], self.eps, self.weight_decay, ptr(self.step_dev),
-                                ptr(self.lr_dev), ptr(self.scale_dev), stream_ptr()), "srk_adam_step")
+        if self.ema is None:
+            check(lib.srk_adam_step(ptr(f.data), ptr(f.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), f.numel, 0.0,
+                                    self.betas[0], self.betas[1], self.eps, self.weight_decay, ptr(self.step_dev),
+                                    ptr(self.lr_dev), ptr(self.scale_dev), stream_ptr()), "srk_adam_step")
+        else:
+            check(lib.srk_adam_step_ema(ptr(f.data), ptr(f.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), f.numel, 0.0,
+                                        self.betas[0], self.betas[1], self.eps, self.weight_decay, ptr(self.step_dev),
+                                        ptr(self.lr_dev), ptr(self.scale_dev), ptr(self.ema), self.ema_decay,
+                                        stream_ptr()), "srk_adam_step_ema")
         f.mark_changed()
+
+    def _hyper(self):
+        return {"betas": [self.betas[0], self.betas[1]], "eps": self.eps, "weight_decay": self.weight_decay}
+
+    def state_dict(self):
+        sd = super(Adam, self).state_dict()
+        sd["step"] = int(self.step_dev[0])    # the one host sync, at save time only
+        return sd
+
+    def load_state_dict(self, sd):
+        super(Adam, self).load_state_dict(sd)
+        _set_step(self.step_dev, sd["step"])
+
+
+def _set_step(step_dev, step):
+    """{step count, the kernel's arrival ticket (0 between launches)}, in place."""
+    step_dev.copy_(torch.tensor([int(step), 0], dtype=torch.int32))
 
 
 class TensorAdam(object):
@@ -308,6 +460,8 @@ class TensorAdam(object):
     param group of drcn.py:108-111), on srk_adam_step: its own step count (advanced like the model group's), its learning
     rate a device scalar that `param_groups[0]['lr'] /= 10` reaches.  The gradient lives in a persistent buffer,
     `t._srk_grad` (= `t.grad`), which the kernel that computes it overwrites every step (ops.drcn_head)."""
+
+    kind = "tensor_adam"
 
     def __init__(self, t, lr, betas=(0.9, 0.999), eps=1e-8):
         if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
@@ -332,19 +486,39 @@ class TensorAdam(object):
                                 self.t.numel(), 0.0, self.betas[0], self.betas[1], self.eps, 0.0, ptr(self.step_dev),
                                 ptr(self.lr_dev), None, stream_ptr()), "srk_adam_step")
 
+    def state_dict(self):
+        """As the flat optimizers' (plain containers, CPU tensors); the one tensor's state is in its own shape."""
+        return {"kind": self.kind, "hyper": {"betas": [self.betas[0], self.betas[1]], "eps": self.eps},
+                "lr": float(self.param_groups[0]["lr"]), "step": int(self.step_dev[0]),
+                "state": {"exp_avg": _cpu(self.exp_avg), "exp_avg_sq": _cpu(self.exp_avg_sq)}}
 
-def make_optimizer(kind, flat, lr):
-    """The reference's per-model optimizer choices."""
+    def load_state_dict(self, sd):
+        """In place (see _FlatOptimizer.load_state_dict)."""
+        _check_state(sd, self.kind)
+        for b in ("exp_avg", "exp_avg_sq"):
+            t = (sd.get("state") or {}).get(b)
+            if t is None or tuple(t.shape) != tuple(self.t.shape):
+                raise ValueError("optimizer state %r has shape %s, the tensor %s"
+                                 % (b, None if t is None else tuple(t.shape), tuple(self.t.shape)))
+        self.exp_avg.copy_(sd["state"]["exp_avg"])
+        self.exp_avg_sq.copy_(sd["state"]["exp_avg_sq"])
+        self.param_groups[0]["lr"] = float(sd["lr"])
+        _set_step(self.step_dev, sd["step"])
+
+
+def make_optimizer(kind, flat, lr, ema_decay=0.0):
+    """The reference's per-model optimizer choices.  ema_decay > 0: the optimizer also keeps the
+    exponential moving average of the weights (`opt.ema`), updated by its step kernel."""
     if kind == "srcnn":      # srcnn.py:79
-        return SGD(flat, lr)
+        return SGD(flat, lr, ema_decay=ema_decay)
     if kind == "fsrcnn":     # fsrcnn.py:105-106
-        return SGD(flat, lr, momentum=0.9)
+        return SGD(flat, lr, momentum=0.9, ema_decay=ema_decay)
     if kind == "vdsr":       # vdsr.py:86-90
-        return SGD(flat, lr, momentum=0.9, weight_decay=1e-4)
+        return SGD(flat, lr, momentum=0.9, weight_decay=1e-4, ema_decay=ema_decay)
     if kind in ("espcn", "lapsrn", "drcn"):   # espcn.py:79, lapsrn.py:135, drcn.py:111 (the model group)
-        return Adam(flat, lr)
+        return Adam(flat, lr, ema_decay=ema_decay)
     if kind in ("edsr", "srgan_g"):   # edsr.py:93, srgan.py:147
-        return Adam(flat, lr, betas=(0.9, 0.999), eps=1e-8)
+        return Adam(flat, lr, betas=(0.9, 0.999), eps=1e-8, ema_decay=ema_decay)
     if kind == "srgan_d":    # srgan.py:149
-        return SGD(flat, lr / 100, momentum=0.9, nesterov=True)
+        return SGD(flat, lr / 100, momentum=0.9, nesterov=True, ema_decay=ema_decay)
     raise ValueError("unknown optimizer kind %r" % (kind,))

@@ -14,6 +14,7 @@ the reference's (lr, hr, bicubic) order), else from the reference's image folder
 synthetic patches of the configured crop size.
 """
 import os
+import random
 
 import torch
 
@@ -77,6 +78,33 @@ def check_perceptual_args(args, kind):
                          % ("perceptual" if perceptual else "vgg_weights"))
 
 
+# -- the training-state file (<save_dir>/model/<model_name>_train_state.pkl) ---------------------------------------------
+# Everything a run needs to continue at an epoch boundary as if it had not stopped; plain containers, numbers, strings
+# and CPU tensors only, so it loads with torch.load(weights_only=True).  The weights-only checkpoint files beside it are
+# the reference's and do not change.
+STATE_VERSION = 1
+
+
+def check_resume_state(state, model_name, num_channels, scale_factor):
+    """A state file continues only the kind of run that wrote it.  ValueError names the field that differs."""
+    if not isinstance(state, dict) or state.get("version") != STATE_VERSION:
+        raise ValueError("version: not a training-state file of format %d (%r)"
+                         % (STATE_VERSION, state.get("version") if isinstance(state, dict) else type(state).__name__))
+    for field, mine in (("model_name", model_name), ("num_channels", num_channels), ("scale_factor", scale_factor)):
+        if state.get(field) != mine:
+            raise ValueError("%s: the training state was written for %r, this run has %r (main.py --%s)"
+                             % (field, state.get(field), mine, field))
+
+
+def _cpu_state(module):
+    return {k: v.detach().cpu().clone() for k, v in module.state_dict().items()}
+
+
+def _ema_name(name):
+    """The EMA weights' file beside a checkpoint file: `_ema` in front of `.pkl`."""
+    return name[:-len('.pkl')] + '_ema.pkl'
+
+
 class _Trainer(object):
     kind = None
 
@@ -91,6 +119,11 @@ class _Trainer(object):
         if self.kind in ("srgan", "drcn") and (getattr(args, "ssim_weight", 0.0) or 0.0) > 0:
             raise ValueError("ssim_weight: %s has no SSIM mix (main.py --ssim_weight)" % self.model_name)
         check_perceptual_args(args, self.kind)
+        self.ema_decay = optim._check_ema_decay(getattr(args, "ema_decay", 0.0))
+        if self.kind == "drcn" and self.ema_decay > 0:
+            raise ValueError("ema_decay: %s keeps no EMA of its weights (main.py --ema_decay)" % self.model_name)
+        self.resume = getattr(args, "resume", None)
+        self.use_ema = bool(getattr(args, "use_ema", False))
         if not torch.cuda.is_available():
             raise RuntimeError("the MI355X hot path needs a GPU (gpu_mode=False has no CPU fallback; see oracle/)")
         self.rank, self.world, self.local = dpmod.init_from_env()
@@ -108,7 +141,78 @@ class _Trainer(object):
     def build_step(self):
         """(flat parameters, optimizer, DataParallel or None, eager step function) of the freshly built model."""
         return trainers.build(self.kind, self.model, self.lr, use_dp=self.world > 1,
-                              ssim_weight=getattr(self.args, "ssim_weight", 0.0) or 0.0)
+                              ssim_weight=getattr(self.args, "ssim_weight", 0.0) or 0.0, ema_decay=self.ema_decay)
+
+    # -- training state: save at epoch boundaries, continue with --resume --------------------------------------------
+    def _state_name(self):
+        model_dir = os.path.join(self.save_dir, 'model')
+        os.makedirs(model_dir, exist_ok=True)
+        return model_dir + '/' + self.model_name + '_train_state.pkl'
+
+    def _optimizers(self):
+        """{name in the state file: optimizer}."""
+        return {"optimizer": self.optimizer}
+
+    def _modules(self):
+        """{name in the state file: module}."""
+        return {"model": self.model}
+
+    def training_state(self, done, history, loader=None, **extra):
+        """The state after `done` completed epochs (see STATE_VERSION)."""
+        rnd = random.getstate()
+        state = {"version": STATE_VERSION, "model_name": self.model_name, "num_channels": self.num_channels,
+                 "scale_factor": self.scale_factor, "epochs_done": int(done),
+                 "batch_size": self.batch_size, "lr": self.lr, "world": self.world,
+                 "history": [list(h) if isinstance(h, tuple) else h for h in history],
+                 "modules": {k: _cpu_state(m) for k, m in self._modules().items()},
+                 "optimizers": {k: o.state_dict() for k, o in self._optimizers().items()},
+                 "python_random": [rnd[0], list(rnd[1]), rnd[2]],
+                 "torch_rng": torch.get_rng_state().clone()}
+        if hasattr(loader, "state_dict") and hasattr(loader, "load_state_dict"):
+            state["loader"] = loader.state_dict()
+        state.update(extra)
+        return state
+
+    def _write_state(self, state):
+        """Atomically: a run killed while it writes leaves the previous file."""
+        name = self._state_name()
+        torch.save(state, name + '.tmp')
+        os.replace(name + '.tmp', name)
+
+    def save_state(self, done, history, loader=None, **extra):
+        if self.rank == 0:
+            self._write_state(self.training_state(done, history, loader, **extra))
+
+    def read_resume_state(self):
+        """None without `resume`; else the checked state of the file it names ('auto': this run's own)."""
+        if not self.resume:
+            return None
+        name = self._state_name() if self.resume == 'auto' else os.fspath(self.resume)
+        if not os.path.exists(name):
+            raise FileNotFoundError("--resume: no training state at %r" % (name,))
+        state = torch.load(name, map_location="cpu", weights_only=True)
+        check_resume_state(state, self.model_name, self.num_channels, self.scale_factor)
+        return state
+
+    def load_training_state(self, state, loader=None):
+        """Into the freshly built model and optimizers, in place (under data parallelism after the broadcast: every rank
+        reads the same file).  Returns (completed epochs, history so far)."""
+        for k, m in self._modules().items():
+            m.load_state_dict(state["modules"][k])     # (FlatParams' post-hook marks the flat buffer changed)
+        for k, o in self._optimizers().items():
+            o.load_state_dict(state["optimizers"][k])
+        rnd = state["python_random"]
+        random.setstate((rnd[0], tuple(rnd[1]), rnd[2]))
+        torch.set_rng_state(state["torch_rng"])
+        if "loader" in state and hasattr(loader, "load_state_dict"):
+            loader.load_state_dict(state["loader"])
+        changed = ["%s %r -> %r" % (f, state.get(f), mine) for f, mine in
+                   (("batch_size", self.batch_size), ("lr", self.lr), ("world", self.world)) if state.get(f) != mine]
+        if self.rank == 0:
+            stored = next(iter(self._optimizers().values())).param_groups[0]["lr"]
+            print("Resumed after epoch %d%s" % (state["epochs_done"], "" if not changed else
+                  " (%s; the stored learning rate %g is used)" % (", ".join(changed), stored)))
+        return int(state["epochs_done"]), list(state["history"])
 
     def begin_epoch(self, epoch):
         """Top of every epoch, before its first step: the reference's LR decay (and any per-model schedule)."""
@@ -177,6 +281,7 @@ class _Trainer(object):
 
     # -- reference surface ------------------------------------------------------------------------
     def train(self, loader=None, log_every=0):
+        state = self.read_resume_state()
         self.model = self.build_model()
         self.model.weight_init()
         self.model.to(self.device).train()
@@ -188,8 +293,11 @@ class _Trainer(object):
             loader = self.load_dataset(self.train_dataset, is_train=True)
             self.data_source = "folder" if loader is not None else "synthetic"
         self._announce_data()
+        done = 0
+        if state is not None:
+            done, avg_loss = self.load_training_state(state, loader)
         trainers.quiesce_gc()    # no full cyclic collection (~80 ms) inside a step from here on
-        for epoch in range(self.num_epochs):
+        for epoch in range(done, self.num_epochs):
             self.begin_epoch(epoch)
             batches = loader if loader is not None else synthetic_loader(self.kind, self.args, self.steps_per_epoch,
                                                                          self.device, 1234 + epoch * self.world + self.rank)
@@ -205,9 +313,11 @@ class _Trainer(object):
                 print('Epoch: [%2d] avg loss: %.8f' % (epoch + 1, avg_loss[-1]))
                 if (epoch + 1) % self.save_epochs == 0:
                     self.save_model(epoch + 1)
+                    self.save_state(epoch + 1, avg_loss, loader)
         self._close_graph()
         if self.rank == 0:
             self.save_model(epoch=None)
+            self.save_state(max(done, self.num_epochs), avg_loss, loader)
         return avg_loss
 
     # -- the train step as a hipGraph ------------------------------------------------------------------------------
@@ -514,10 +624,21 @@ class _Trainer(object):
     def save_model(self, epoch=None):
         sd = {k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()}
         torch.save(sd, self._ckpt_name(epoch))
+        if self.ema_decay > 0:   # the EMA weights beside it: the same keys and shapes, a file load_model() reads alike
+            self._save_ema(self.optimizer, self.model, self._ckpt_name(epoch))
         print('Trained model is saved.')
+
+    @staticmethod
+    def _save_ema(opt, module, name):
+        torch.save({k: v.detach().cpu().clone() for k, v in opt.ema_state_dict(module).items()}, _ema_name(name))
 
     def load_model(self):
         name = self._ckpt_name(None)
+        if self.use_ema:
+            name = _ema_name(name)
+            if not os.path.exists(name):
+                print('No EMA model exists to load (%s).' % os.path.basename(name))
+                return False
         if os.path.exists(name):
             self.model.load_state_dict(torch.load(name))
             print('Trained model is loaded.')
@@ -580,20 +701,28 @@ class SRGAN(_Trainer):
         self.D = models.SRGANDiscriminator(self.num_channels, 64, self.crop_size)  # srgan.py:137
         return self.G
 
+    def _optimizers(self):
+        return {"g_opt": self.g_opt, "d_opt": self.d_opt}
+
+    def _modules(self):
+        return {"G": self.G, "D": self.D}
+
     def train(self, loader=None, pretrain_epochs=None, log_every=0):
+        state = self.read_resume_state()
         self.model = self.build_model()
         self.G.weight_init(mean=0.0, std=0.02)
         self.D.weight_init(mean=0.0, std=0.02)
         self.G.to(self.device).train()
         self.D.to(self.device).train()
         g_flat, d_flat = optim.FlatParams(self.G), optim.FlatParams(self.D)
-        g_opt = optim.make_optimizer("srgan_g", g_flat, self.lr)
-        d_opt = optim.make_optimizer("srgan_d", d_flat, self.lr)
+        g_opt = self.g_opt = optim.make_optimizer("srgan_g", g_flat, self.lr, ema_decay=self.ema_decay)   # (the EMA is G's)
+        d_opt = self.d_opt = optim.make_optimizer("srgan_d", d_flat, self.lr)
         g_dp = d_dp = None
         if self.world > 1:
             g_dp, d_dp = dpmod.DataParallel(g_flat), dpmod.DataParallel(d_flat)
             g_dp.broadcast_params()
             d_dp.broadcast_params()
+            g_opt.ema_reset()
             if getattr(self.args, "sync_bn", False):   # statistics of the global batch (SURVEY.md 8e caveat)
                 trainers.sync_batchnorm(self.G)
                 trainers.sync_batchnorm(self.D)
@@ -617,16 +746,34 @@ class SRGAN(_Trainer):
 
         # generator pre-training (srgan.py:179-219): 50 epochs of MSE unless a pre-trained generator checkpoint loads
         self.epoch_pretrain = int(getattr(self.args, "epoch_pretrain", 50)) if pretrain_epochs is None else pretrain_epochs
-        if self.load_model(is_pretrain=True):
+        # a resumed run continues in the phase it stopped in: inside pre-training after `pre_done` of its epochs, or in the
+        # adversarial loop after `done` epochs with the history so far
+        self.phase, pre_done, done, hist = "pretrain", 0, 0, []
+        if state is not None:
+            self.phase = state["phase"]
+            n, h = self.load_training_state(state, loader)
+            if self.phase == "pretrain":
+                pre_done = n
+            else:
+                done, hist = n, [tuple(v) for v in h]
+        if self.phase == "adversarial":
+            pass
+        elif state is None and self.load_model(is_pretrain=True):
             g_flat.mark_changed()      # parameters changed behind the optimizer's back: re-pack filters
+            g_opt.ema_reset()          # ... and the shadow weights start from them
         else:
             pre_step = graphed(trainers.mse_step(self.G, g_opt, g_dp), [g_flat])
-            for epoch in range(self.epoch_pretrain):
+            for epoch in range(pre_done, self.epoch_pretrain):
                 for y_, x_ in batches(77 + epoch):
                     pre_step(y_, x_)
+                if (epoch + 1) % self.save_epochs == 0 and epoch + 1 < self.epoch_pretrain:
+                    self.save_state(epoch + 1, [], loader, phase="pretrain")
             pre_step.close()
             if self.rank == 0:
                 self.save_model(is_pretrain=True)
+        if self.phase == "pretrain":
+            self.phase = "adversarial"
+            self.save_state(0, [], loader, phase=self.phase)
         # the adversarial step (two models, two optimizers) as one hipGraph; data parallel: graphs split at the two exchanges
         # --vgg_weights: the reference's VGG content term in the logged G loss; --perceptual: the term trains G
         fe = None
@@ -638,8 +785,7 @@ class SRGAN(_Trainer):
                                            perceptual=bool(getattr(self.args, "perceptual", False)),
                                            vgg_weight=6e-3 if vgg_w is None else float(vgg_w)),
                        [g_flat, d_flat])
-        hist = []
-        for epoch in range(self.num_epochs):
+        for epoch in range(done, self.num_epochs):
             apply_lr_decay("srgan", epoch, g_opt, d_opt)   # srgan.py:239-244: both learning rates /10 every 20 epochs
             d_tot, g_tot, n = torch.zeros((), device=self.device), torch.zeros((), device=self.device), 0
             for y_, x_ in batches(1234 + epoch):
@@ -652,9 +798,11 @@ class SRGAN(_Trainer):
                 print('Epoch: [%2d] D_loss: %.8f G_loss: %.8f' % ((epoch + 1,) + hist[-1]))
                 if (epoch + 1) % self.save_epochs == 0:
                     self.save_model(epoch + 1)
+                    self.save_state(epoch + 1, hist, loader, phase=self.phase)
         step.close()
         if self.rank == 0:
             self.save_model(epoch=None)
+            self.save_state(max(done, self.num_epochs), hist, loader, phase=self.phase)
         return hist
 
     def _names(self, epoch):
@@ -670,15 +818,24 @@ class SRGAN(_Trainer):
         cpu = lambda m: {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}
         if is_pretrain:
             torch.save(cpu(self.G), pre)
+            if self.ema_decay > 0:
+                self._save_ema(self.g_opt, self.G, pre)
             print('Pre-trained generator model is saved.')
         else:
             torch.save(cpu(self.G), g_name)
             torch.save(cpu(self.D), d_name)
+            if self.ema_decay > 0:   # (the generator's only)
+                self._save_ema(self.g_opt, self.G, g_name)
             print('Trained models are saved.')
 
     def load_model(self, is_pretrain=False):   # srgan.py:508-526
         g_name, _, pre = self._names(None)
         name = pre if is_pretrain else g_name
+        if self.use_ema and not is_pretrain:   # (what test() / test_single() evaluate; train() starts from the plain file)
+            name = _ema_name(name)
+            if not os.path.exists(name):
+                print('No EMA generator model exists to load (%s).' % os.path.basename(name))
+                return False
         if os.path.exists(name):
             self.G.load_state_dict(torch.load(name))
             print('Trained generator model is loaded.')
@@ -725,6 +882,20 @@ class DRCN(_Trainer):
 
     def lr_decay(self, epoch, opt):
         apply_lr_decay(self.kind, epoch, opt, self.w_optimizer)   # both param groups (drcn.py:164-168)
+
+    def _optimizers(self):
+        return {"optimizer": self.optimizer, "w_optimizer": self.w_optimizer}
+
+    def training_state(self, done, history, loader=None, **extra):
+        return super(DRCN, self).training_state(done, history, loader, w=self.model.w.detach().cpu().clone(),
+                                                loss_alpha=float(self.loss_alpha), **extra)
+
+    def load_training_state(self, state, loader=None):
+        out = super(DRCN, self).load_training_state(state, loader)
+        with torch.no_grad():
+            self.model.w.copy_(state["w"].reshape(self.model.w.shape))
+        self.loss_alpha = float(state["loss_alpha"])   # (begin_epoch takes the next value from here)
+        return out
 
     def begin_epoch(self, epoch):
         super(DRCN, self).begin_epoch(epoch)
