@@ -44,6 +44,7 @@ extern "C" {
 typedef enum srk_status {
   SRK_OK = 0,
   SRK_ERR_BAD_ARG = -1,     /* null pointer, non-positive dim, inconsistent shapes        */
+  SRK_ERR_INVALID = SRK_ERR_BAD_ARG, /* the same status under the name the degradation entry points document */
   SRK_ERR_UNSUPPORTED = -2, /* legal request that no kernel in this build covers          */
   SRK_ERR_LAUNCH = -3,      /* hipGetLastError() != hipSuccess after a launch             */
   SRK_ERR_WORKSPACE = -4    /* caller-provided workspace smaller than srk_*_workspace_bytes */
@@ -730,6 +731,39 @@ int srk_maxpool2x2_forward(const float* x, float* y, int N, int H, int W, int C,
  * NaN in x is out of scope (the forward propagates it; the gradient's winner is then unspecified). */
 int srk_maxpool2x2_backward(const float* x, const float* dy, float* dx, int N, int H, int W, int C, int relu_input,
                             void* stream);
+
+/* ---- training degradations on the loader's 8-bit patches (data.Degradation; csrc/degrade.hip) -------------------
+ * (Added without a change of srk_version(): new entry points only, nothing existing changed.)
+ * The classical degradation model LR = (HR * k) shrunk + n, defined to the bit so that a numpy restatement gives the
+ * same bytes.
+ *
+ * srk_blur_u8: x, y dense 8-bit [B][planes_per_patch][H][W]; w fp64 [B][K][K], one table per patch, row-major (i, j).
+ *   y = floor(clamp(sum_{i,j} w[b][i][j] * x[b][c][yy + i - r][xx + j - r], 0, 255) + 0.5), r = K / 2, borders mirrored
+ *   without repeating the edge pixel (reflect-101).  The sum is fp64, taps added in row-major (i, j) order; a table
+ *   narrower than K sits centred among zeros (0.0 * p leaves the sum unchanged), and the delta table returns x bit for bit.
+ *   SRK_ERR_INVALID before anything is launched: null pointer, K even or outside [3, 21], H or W <= K / 2.
+ * srk_noise_u8: x 8-bit, y float, both dense [B][elems_per_patch]; sigma fp64 [B] on the device, in 8-bit levels.
+ *   y[e] = float(clamp(floor(x[e] + sigma[b] * z[e] + 0.5), 0, 255)) / 255.0f (the division srk_img_resize_u8 makes with
+ *   out_float = 1; sigma = 0 gives x / 255 exactly).  z[e] is lane e & 3 of the four normals of group q = e >> 2, e the
+ *   linear index over the whole call: Philox4x32-10 under key (seed & 0xffffffff, seed >> 32) on counter
+ *   (q & 0xffffffff, q >> 32, 0, 0) gives words x0..x3; with u(x) = (x + 0.5) * 2^-32 and rad(x) = sqrt(-2 ln u(x)):
+ *   n0 = rad(x0) cos(2 pi u(x1)), n1 = rad(x0) sin(2 pi u(x1)), n2 = rad(x2) cos(2 pi u(x3)), n3 = rad(x2) sin(2 pi u(x3)),
+ *   all in fp64.
+ * Host-only twins, pure functions that need no device:
+ * srk_blur_weights_host: w[i][j] = exp(-0.5 * (u^2 / s1^2 + v^2 / s2^2)), u = cos(theta) x + sin(theta) y,
+ *   v = -sin(theta) x + cos(theta) y, x = j - K / 2, y = i - K / 2, divided by the table's sum (row-major, fp64).
+ *   K odd in [1, 21], s1, s2 > 0.
+ * srk_noise_normals_host: z[k] = the normal of element first_elem + k under `seed`, from the very Philox and Box-Muller
+ *   body the kernel compiles (csrc/degrade_common.h); the two sides differ by what their libm's do, an ulp.
+ * srk_philox4x32_10_host: that body's generator alone, out[0..3] = Philox4x32-10 of counter[0..3] under key[0..1], so
+ *   the published known-answer vectors (any counter, any key) can be checked against the code the kernel runs. */
+int srk_blur_u8(const uint8_t* x, uint8_t* y, const double* w, int planes_per_patch, int B, int H, int W, int K,
+                void* stream);
+int srk_noise_u8(const uint8_t* x, float* y, const double* sigma, uint64_t seed, int B, int64_t elems_per_patch,
+                 void* stream);
+int srk_blur_weights_host(double s1, double s2, double theta, int K, double* w);
+int srk_noise_normals_host(uint64_t seed, int64_t first_elem, int64_t n, double* z);
+int srk_philox4x32_10_host(const uint32_t* counter, const uint32_t* key, uint32_t* out);
 
 #ifdef __cplusplus
 }

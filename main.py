@@ -15,7 +15,10 @@ VGG feature term) with --perceptual (that term trains the generator) and --vgg_l
 and --resume [PATH] (continue training from the training-state file a run writes beside its checkpoints at every
 --save_epochs boundary and at its end; without PATH this run's own <save_dir>/model/<model_name>_train_state.pkl) and
 --ema_decay D (the optimizer kernel also keeps an exponential moving average of the weights, saved beside every
-checkpoint as ..._ema.pkl; D in [0, 1), default 0: none; not DRCN) with --use_ema (--test_only / --test_single load it).
+checkpoint as ..._ema.pkl; D in [0, 1), default 0: none; not DRCN) with --use_ema (--test_only / --test_single load it)
+and --degrade (train on LR = (HR * k) shrunk + n instead of the clean bicubic shrink: a random anisotropic Gaussian blur and
+Gaussian noise on the device, data.Degradation) with --blur_sigma LO,HI, --blur_prob P and --noise_sigma LO,HI, and
+--degrade_test S1,S2,THETA_DEG,NOISE (the test sets under one fixed degradation); image folders only, not --synthetic.
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N main.py ..."""
 import argparse
 import os
@@ -69,6 +72,52 @@ def _ema_decay(text):
     if not 0.0 <= v < 1.0:
         raise argparse.ArgumentTypeError("--ema_decay takes a number in [0, 1), got %r" % (text,))
     return v
+
+
+def _floats(text, n, flag):
+    try:
+        v = tuple(float(s) for s in str(text).split(','))
+    except ValueError:
+        v = ()
+    if len(v) != n or not all(x == x and abs(x) != float('inf') for x in v):
+        raise argparse.ArgumentTypeError("%s takes %d comma-separated numbers, got %r" % (flag, n, text))
+    return v
+
+
+def _blur_sigma(text):
+    """--blur_sigma LO,HI: 0 < LO <= HI, in pixels."""
+    lo, hi = _floats(text, 2, '--blur_sigma')
+    if not 0.0 < lo <= hi:
+        raise argparse.ArgumentTypeError("--blur_sigma takes LO,HI with 0 < LO <= HI, got %r" % (text,))
+    return lo, hi
+
+
+def _noise_sigma(text):
+    """--noise_sigma LO,HI: 0 <= LO <= HI, in 8-bit levels."""
+    lo, hi = _floats(text, 2, '--noise_sigma')
+    if not 0.0 <= lo <= hi:
+        raise argparse.ArgumentTypeError("--noise_sigma takes LO,HI with 0 <= LO <= HI, got %r" % (text,))
+    return lo, hi
+
+
+def _blur_prob(text):
+    """--blur_prob: a number in [0, 1] (NaN fails both comparisons)."""
+    try:
+        v = float(text)
+    except ValueError:
+        v = float('nan')
+    if not 0.0 <= v <= 1.0:
+        raise argparse.ArgumentTypeError("--blur_prob takes a number in [0, 1], got %r" % (text,))
+    return v
+
+
+def _degrade_test(text):
+    """--degrade_test S1,S2,THETA_DEG,NOISE: S1, S2 > 0 pixels, the angle in degrees, NOISE >= 0 8-bit levels."""
+    s1, s2, th, ns = _floats(text, 4, '--degrade_test')
+    if not (s1 > 0 and s2 > 0 and ns >= 0):
+        raise argparse.ArgumentTypeError("--degrade_test takes S1,S2,THETA_DEG,NOISE with S1, S2 > 0 and NOISE >= 0, got %r"
+                                         % (text,))
+    return s1, s2, th, ns
 
 
 def parse_args(argv=None):
@@ -143,7 +192,23 @@ def parse_args(argv=None):
                         'default 0: none.  Not for DRCN')
     p.add_argument('--use_ema', action='store_true',
                    help='--test_only / --test_single: load the EMA weights (..._ema.pkl) instead of the plain checkpoint')
+    p.add_argument('--degrade', action='store_true',
+                   help='train on the degradation model LR = (HR * k) shrunk + n instead of the clean bicubic shrink: per '
+                        'patch a random anisotropic Gaussian blur in front of the shrink and Gaussian noise behind it, on '
+                        'the device (data.Degradation).  Image folders only')
+    p.add_argument('--blur_sigma', type=_blur_sigma, default=(0.2, 4.0), metavar='LO,HI',
+                   help='--degrade: range of the blur\'s two standard deviations in HR pixels (default 0.2,4.0)')
+    p.add_argument('--blur_prob', type=_blur_prob, default=1.0, metavar='P',
+                   help='--degrade: probability that a patch is blurred at all (default 1)')
+    p.add_argument('--noise_sigma', type=_noise_sigma, default=(0.0, 10.0), metavar='LO,HI',
+                   help='--degrade: range of the noise\'s standard deviation in 8-bit levels (default 0,10; 0,0: none)')
+    p.add_argument('--degrade_test', type=_degrade_test, default=None, metavar='S1,S2,THETA_DEG,NOISE',
+                   help='test(): every test image under this one degradation (blur standard deviations, angle in degrees, '
+                        'noise standard deviation; the noise seeded by the image\'s index).  Image folders only')
     args = p.parse_args(argv)
+    for flag in ('degrade', 'degrade_test'):
+        if getattr(args, flag) and args.synthetic:
+            p.error('--%s: synthetic patches are not degraded; train and test on image folders (drop --synthetic)' % flag)
     if args.ema_decay > 0 and args.model_name == 'DRCN':
         p.error('--ema_decay %g: DRCN keeps no EMA of its weights (its combine weights w train outside the flat '
                 'parameter buffer); use --ema_decay 0 or another model' % args.ema_decay)

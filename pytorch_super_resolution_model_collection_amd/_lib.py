@@ -228,6 +228,12 @@ _PROTOTYPES = {
     "srk_maxpool2x2_backward": (c_int, [c_f, c_f, c_f, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "srk_img_interp_workspace_bytes": (ctypes.c_size_t, [c_int] * 7),
     "srk_img_interp": (c_int, [c_f, c_f, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, ctypes.c_size_t, c_vp]),
+    "srk_blur_u8": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
+    "srk_noise_u8": (c_int, [c_vp, c_f, c_vp, ctypes.c_uint64, c_int, ctypes.c_int64, c_vp]),
+    "srk_blur_weights_host": (c_int, [ctypes.c_double, ctypes.c_double, ctypes.c_double, c_int,
+                                      ctypes.POINTER(ctypes.c_double)]),
+    "srk_noise_normals_host": (c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_double)]),
+    "srk_philox4x32_10_host": (c_int, [ctypes.POINTER(ctypes.c_uint32)] * 3),
 }
 
 _lib = None

@@ -15,8 +15,12 @@ Reference quirk kept: with random_scale the whole image is 
 "random crop" is then a no-op.  `is_gray` (convert('YCbCr'), dataset.py:85-86) is done by Pillow on the host on the
 augmented 8-bit patch (one small D2H/H2D per patch, gray mode only): its integer colour matrix is Pillow's own.
 Not provided: the BSDS300 HTTP download of data.py:9-30 (no network code in this package).
+Beyond the reference: `Degradation` -- with `degrade=` set, the LR image is no longer the clean bicubic
+shrink of the HR patch but LR = (HR * k) shrunk + n: a random anisotropic Gaussian blur in front of the shrink and Gaussian
+noise behind it, both HIP kernels on the loader stream (csrc/degrade.hip).  Without it nothing changes, draws included.
 """
 import ctypes
+import math
 import os
 import random
 from concurrent.futures import ThreadPoolExecutor
@@ -192,6 +196,26 @@ class _Device(object):
                                      self._sp), "srk_img_interp")
         return y
 
+    def upload_f64(self, values):
+        """Host fp64 numpy array -> device fp64 tensor, through the pinned ring like an image."""
+        values = np.ascontiguousarray(values, dtype=np.float64)
+        return self.upload(values.reshape(-1).view(np.uint8)).view(torch.float64).view(values.shape)
+
+    def blur(self, x, weights, planes_per_patch, b, h, w):
+        """srk_blur_u8: dense 8-bit [b, planes_per_patch, h, w] under the fp64 tables weights [b, K, K] (device)."""
+        with self._on_stream():
+            y = torch.empty((b, planes_per_patch, h, w), dtype=torch.uint8, device=self.device)
+            check(self.lib.srk_blur_u8(ptr(x), ptr(y), ptr(weights), planes_per_patch, b, h, w, int(weights.shape[-1]),
+                                       self._sp), "srk_blur_u8")
+        return y
+
+    def noise(self, x, sigma, seed, b):
+        """srk_noise_u8: dense 8-bit [b, ...] -> fp32 (x + sigma[b] * z) / 255 of the same shape; sigma fp64 [b] (device)."""
+        with self._on_stream():
+            y = torch.empty(x.shape, dtype=torch.float32, device=self.device)
+            check(self.lib.srk_noise_u8(ptr(x), ptr(y), ptr(sigma), int(seed), b, x.numel() // b, self._sp), "srk_noise_u8")
+        return y
+
     def hand_over(self, *tensors):
         """Make the consumer's current stream wait for the loader stream; tensors become usable there."""
         cur = torch.cuda.current_stream(self.device)
@@ -205,12 +229,100 @@ _HWC = lambda h, w, c: (1, w * c, c)       # element strides (plane, row, pixel)
 _CHW = lambda h, w: (h * w, w, 1)
 
 
+BLUR_MAX_K = 21   # kBlurMaxK (csrc/degrade_common.h)
+
+
+def blur_kernel_size(s1, s2):
+    """Taps of the table of a blur with standard deviations s1, s2: 3 sigma to each side, capped at BLUR_MAX_K."""
+    return min(BLUR_MAX_K, 2 * int(math.ceil(3 * max(s1, s2))) + 1)
+
+
+def blur_weights(s1, s2, theta, K=None):
+    """srk_blur_weights_host: the normalised K x K anisotropic Gaussian table (fp64 numpy); needs no GPU."""
+    K = blur_kernel_size(s1, s2) if K is None else int(K)
+    buf = (ctypes.c_double * (K * K))()      # (a ctypes array: numpy's .ctypes.data_as costs as much as the table itself)
+    check(_lib.load().srk_blur_weights_host(float(s1), float(s2), float(theta), K, buf), "srk_blur_weights_host")
+    w = np.frombuffer(buf, np.float64).reshape(K, K)
+    return w
+
+
+def _centred(tables, K):
+    """The square tables (None = not blurred: the delta) centred among zeros in [B, K, K]."""
+    out = np.zeros((len(tables), K, K), np.float64)
+    for b, w in enumerate(tables):
+        if w is None:
+            out[b, K // 2, K // 2] = 1.0
+        else:
+            o = (K - w.shape[0]) // 2
+            out[b, o:o + w.shape[0], o:o + w.shape[0]] = w
+    return out
+
+
+def _degrade_u8(dev, planes, weights, sigma, seed, oh, ow):
+    """blur -> Pillow-exact bicubic shrink -> noise of dense 8-bit planes [B, C, H, W] on the loader stream.  weights
+    [B, K, K] and sigma [B] are host fp64 arrays; they cross in one copy.  A batch without a blurred patch skips the blur
+    (the delta table returns its input) and one without noise takes the shrink's own / 255: the same bits, fewer launches."""
+    b, c, h, w = (int(v) for v in planes.shape)
+    K = weights.shape[-1]
+    blurred = bool((weights[:, K // 2, K // 2] != 1.0).any())
+    noisy = bool((sigma != 0.0).any())
+    if blurred or noisy:
+        params = dev.upload_f64(np.concatenate([weights.reshape(-1), sigma.reshape(-1)]))
+    q = dev.blur(planes, params[:weights.size].view(b, K, K), c, b, h, w) if blurred else planes
+    lr = dev.resize(q, _CHW(h, w), b * c, h, w, oh, ow, out_float=not noisy).view(b, c, oh, ow)
+    return dev.noise(lr, params[weights.size:], seed, b) if noisy else lr
+
+
+class Degradation(object):
+    """The classical degradation model of blind super-resolution, LR = (HR * k) shrunk + n: per patch,
+    with probability `blur_prob`, an anisotropic Gaussian blur with standard deviations drawn from `blur_sigma` = (lo, hi)
+    pixels and a uniform angle; then the loader's own bicubic shrink; then Gaussian noise of a standard deviation drawn
+    from `noise_sigma` = (lo, hi) 8-bit levels (hi = 0: no noise, and no draw for it).  Draws come from Python's global
+    `random`, after the batch's patch draws."""
+
+    def __init__(self, blur_prob=1.0, blur_sigma=(0.2, 4.0), noise_sigma=(0.0, 10.0)):
+        self.blur_prob = float(blur_prob)
+        self.blur_sigma = (float(blur_sigma[0]), float(blur_sigma[1]))
+        self.noise_sigma = (float(noise_sigma[0]), float(noise_sigma[1]))
+        if not 0.0 <= self.blur_prob <= 1.0:
+            raise ValueError("blur_prob must lie in [0, 1] (got %r)" % (blur_prob,))
+        if not 0.0 < self.blur_sigma[0] <= self.blur_sigma[1] < float('inf'):
+            raise ValueError("blur_sigma must be 0 < lo <= hi (got %r)" % (blur_sigma,))
+        if not 0.0 <= self.noise_sigma[0] <= self.noise_sigma[1] < float('inf'):
+            raise ValueError("noise_sigma must be 0 <= lo <= hi (got %r)" % (noise_sigma,))
+
+    def draw(self, batch):
+        """(weights [B, K, K], sigma [B], seed) of one batch as host arrays.  Per patch: random() < blur_prob -> s1, s2,
+        theta, else the delta; then sigma, only if noise is on; after the loop the 64-bit noise seed, only if noise is on.
+        K is the batch's widest table (3 when no patch is blurred), narrower ones centred among zeros."""
+        lo, hi = self.blur_sigma
+        nlo, nhi = self.noise_sigma
+        tables, sigma = [], np.zeros(batch, np.float64)
+        for j in range(batch):
+            if random.random() < self.blur_prob:
+                s1, s2 = random.uniform(lo, hi), random.uniform(lo, hi)
+                tables.append(blur_weights(s1, s2, random.uniform(0, math.pi)))
+            else:
+                tables.append(None)
+            if nhi > 0:
+                sigma[j] = random.uniform(nlo, nhi)
+        seed = random.getrandbits(64) if nhi > 0 else 0
+        K = max([w.shape[0] for w in tables if w is not None] + [3])
+        return _centred(tables, K), sigma, seed
+
+    def apply(self, dev, patches, lr_sz):
+        """Dense 8-bit patches [B, C, crop, crop] on the device -> the degraded fp32 lr [B, C, lr_sz, lr_sz]."""
+        weights, sigma, seed = self.draw(int(patches.shape[0]))
+        return _degrade_u8(dev, patches, weights, sigma, seed, lr_sz, lr_sz)
+
+
 class TrainDatasetFromFolder(object):
     """dataset.py:22-104 with device-side transforms.  `__getitem__` returns (lr_img, hr_img, bc_img) CUDA tensors."""
 
     def __init__(self, image_dirs, is_gray=False, random_scale=True, crop_size=128, rotate=True, fliplr=True,
-                 fliptb=True, scale_factor=4, device="cuda"):
+                 fliptb=True, scale_factor=4, device="cuda", degrade=None):
         self.image_filenames = []
+        self.degrade = degrade    # a Degradation, or None: the clean bicubic shrink of the reference
         for image_dir in image_dirs:
             self.image_filenames.extend(join(image_dir, x) for x in sorted(listdir(image_dir)) if is_image_file(x))
         self.is_gray, self.random_scale, self.crop_size = is_gray, random_scale, crop_size
@@ -306,7 +418,10 @@ class TrainDatasetFromFolder(object):
         lr_sz = crop // sf
         st = _CHW(crop, crop)
         hr = dev.resize(patches, st, b * c, crop, crop, crop, crop, out_float=True).view(b, c, crop, crop)
-        lr = dev.resize(patches, st, b * c, crop, crop, lr_sz, lr_sz, out_float=True).view(b, c, lr_sz, lr_sz)
+        if self.degrade is not None:
+            lr = self.degrade.apply(dev, patches.contiguous(), lr_sz)
+        else:
+            lr = dev.resize(patches, st, b * c, crop, crop, lr_sz, lr_sz, out_float=True).view(b, c, lr_sz, lr_sz)
         bc = dev.bicubic_of_lr(lr, crop, crop)
         return lr, hr, bc
 
@@ -323,9 +438,15 @@ class TrainDatasetFromFolder(object):
 class TestDatasetFromFolder(object):
     """dataset.py:106-149 with device-side resizes."""
 
-    def __init__(self, image_dir, is_gray=False, scale_factor=4, device="cuda"):
+    def __init__(self, image_dir, is_gray=False, scale_factor=4, device="cuda", degrade=None):
         self.image_filenames = [join(image_dir, x) for x in sorted(listdir(image_dir)) if is_image_file(x)]
         self.is_gray, self.scale_factor = is_gray, scale_factor
+        # degrade: None, or one FIXED degradation (s1, s2, theta in radians, noise sigma in 8-bit levels) for every image,
+        # the noise seeded with the image's index: an item is the same on every read
+        self.degrade = None if degrade is None else tuple(float(v) for v in degrade)
+        if self.degrade is not None and not (len(self.degrade) == 4 and self.degrade[0] > 0 and self.degrade[1] > 0
+                                             and self.degrade[3] >= 0):
+            raise ValueError("degrade must be (s1 > 0, s2 > 0, theta, noise_sigma >= 0), got %r" % (degrade,))
         self._device, self._dev = device, None
 
     @property
@@ -350,12 +471,19 @@ class TestDatasetFromFolder(object):
         img = dev.upload(hwc)
         st = _HWC(h, w, c)
         hr = dev.resize(img, st, c, h, w, hr_h, hr_w, out_float=True)
-        lr = dev.resize(img, st, c, h, w, lr_h, lr_w, out_float=True)
+        if self.degrade is not None:
+            s1, s2, theta, noise_sigma = self.degrade
+            with torch.cuda.stream(dev.stream):
+                planes = img.permute(2, 0, 1).contiguous().unsqueeze(0)   # (the blur reads dense planes)
+            lr = _degrade_u8(dev, planes, blur_weights(s1, s2, theta)[None], np.array([noise_sigma], np.float64),
+                             index, lr_h, lr_w)[0]
+        else:
+            lr = dev.resize(img, st, c, h, w, lr_h, lr_w, out_float=True)
         bc = dev.bicubic_of_lr(lr.unsqueeze(0), hr_h, hr_w)[0]
         return dev.hand_over(lr, hr, bc)
 
 
-def get_training_set(data_dir, datasets, crop_size, scale_factor, is_gray=False, device="cuda"):
+def get_training_set(data_dir, datasets, crop_size, scale_factor, is_gray=False, device="cuda", degrade=None):
     """data.py:33-51 (directory layout and augmentation switches; 'bsds300' must already be on disk)."""
     train_dir = []
     for dataset in datasets:
@@ -366,10 +494,10 @@ def get_training_set(data_dir, datasets, crop_size, scale_factor, is_gray=False,
         else:
             train_dir.append(join(data_dir, dataset))
     return TrainDatasetFromFolder(train_dir, is_gray=is_gray, random_scale=True, crop_size=crop_size, rotate=True,
-                                  fliplr=True, fliptb=True, scale_factor=scale_factor, device=device)
+                                  fliplr=True, fliptb=True, scale_factor=scale_factor, device=device, degrade=degrade)
 
 
-def get_test_set(data_dir, dataset, scale_factor, is_gray=False, device="cuda"):
+def get_test_set(data_dir, dataset, scale_factor, is_gray=False, device="cuda", degrade=None):
     """data.py:54-65"""
     if dataset == 'bsds300':
         test_dir = join(data_dir, "BSDS300/images", "test")
@@ -377,7 +505,7 @@ def get_test_set(data_dir, dataset, scale_factor, is_gray=False, device="cuda"):
         test_dir = join(data_dir, dataset, 'DIV2K_test_LR_bicubic/X4')
     else:
         test_dir = join(data_dir, dataset)
-    return TestDatasetFromFolder(test_dir, is_gray=is_gray, scale_factor=scale_factor, device=device)
+    return TestDatasetFromFolder(test_dir, is_gray=is_gray, scale_factor=scale_factor, device=device, degrade=degrade)
 
 
 class PatchLoader(object):

@@ -1975,6 +1975,48 @@ def resize_u8(planes_u8, oh, ow, interpolation="bicubic", out_float=False):
     return y
 
 
+def _require_f64(what, name, t, shape):
+    if not t.is_cuda:
+        raise RuntimeError("%s runs on GPU tensors (got %s on %s); there is no CPU fallback" % (what, name, t.device))
+    if t.dtype != torch.float64 or tuple(t.shape) != tuple(shape):
+        raise RuntimeError("%s: %s must be an fp64 %s tensor, got %s %s" % (what, name, list(shape), t.dtype, tuple(t.shape)))
+    return t.contiguous()
+
+
+def blur_u8(x, weights):
+    """Per-patch blur of 8-bit patches x [B,C,H,W] under the fp64 tables weights [B,K,K] (K odd, 3 <= K <= 21, H, W >
+    K // 2) on the device: srk_blur_u8.  Each output byte is floor(clamp(sum, 0, 255) + 0.5) of the fp64 sum of its K x K
+    taps in row-major order, borders mirrored without repeating the edge pixel; the delta table returns x."""
+    _require_u8("blur_u8", x)
+    if x.dim() != 4 or weights.dim() != 3:
+        raise RuntimeError("blur_u8 expects x [B,C,H,W] and weights [B,K,K], got %s and %s" % (tuple(x.shape), tuple(weights.shape)))
+    b, c, h, w = (int(v) for v in x.shape)
+    k = int(weights.shape[-1])
+    weights = _require_f64("blur_u8", "weights", weights, (b, k, k))
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    check(_lib.load().srk_blur_u8(ptr(x), ptr(y), ptr(weights), c, b, h, w, k, stream_ptr()), "srk_blur_u8")
+    return y
+
+
+def noise_u8(x, sigma, seed):
+    """Additive Gaussian noise on 8-bit patches x [B,...] with one standard deviation per patch (sigma fp64 [B], in 8-bit
+    levels) on the device: srk_noise_u8.  Returns fp32 floor(x + sigma * z + 0.5) clamped to [0, 255] and divided by 255;
+    z from Philox4x32-10 under the 64-bit `seed` on the element's index, Box-Muller in fp64.  sigma 0 gives x / 255."""
+    _require_u8("noise_u8", x)
+    if x.dim() < 1 or x.numel() == 0:
+        raise RuntimeError("noise_u8 expects a non-empty [B,...] tensor, got shape %s" % (tuple(x.shape),))
+    b = int(x.shape[0])
+    sigma = _require_f64("noise_u8", "sigma", sigma, (b,))
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("noise_u8: seed must fit 64 bits (got %d)" % seed)
+    x = x.contiguous()
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    check(_lib.load().srk_noise_u8(ptr(x), ptr(y), ptr(sigma), seed, b, x.numel() // b, stream_ptr()), "srk_noise_u8")
+    return y
+
+
 # ------------------------------------------------------------------------------------------------
 # Tiled super-resolution of one picture (tiling.py, csrc/tile.hip): gather the plan's tiles, stitch their outputs
 # ------------------------------------------------------------------------------------------------

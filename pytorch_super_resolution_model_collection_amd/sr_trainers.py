@@ -13,6 +13,7 @@ the reference's (lr, hr, bicubic) order), else from the reference's image folder
 (data.PatchLoader: decode on host threads, transforms on the GPU) when they exist, else from seeded
 synthetic patches of the configured crop size.
 """
+import math
 import os
 import random
 
@@ -119,6 +120,10 @@ class _Trainer(object):
         if self.kind in ("srgan", "drcn") and (getattr(args, "ssim_weight", 0.0) or 0.0) > 0:
             raise ValueError("ssim_weight: %s has no SSIM mix (main.py --ssim_weight)" % self.model_name)
         check_perceptual_args(args, self.kind)
+        for flag in ("degrade", "degrade_test"):
+            if getattr(args, flag, None) and getattr(args, "synthetic", False):
+                raise ValueError("%s: synthetic patches are not degraded, train and test on image folders (main.py "
+                                 "--%s without --synthetic)" % (flag, flag))
         self.ema_decay = optim._check_ema_decay(getattr(args, "ema_decay", 0.0))
         if self.kind == "drcn" and self.ema_decay > 0:
             raise ValueError("ema_decay: %s keeps no EMA of its weights (main.py --ema_decay)" % self.model_name)
@@ -245,13 +250,23 @@ class _Trainer(object):
         synthetic = bool(getattr(self.args, "synthetic", False))
         if synthetic:
             return None
+        args = self.args
         try:
             if is_train:
+                degrade = None
+                if getattr(args, "degrade", False):   # main.py --degrade: LR = (HR * k) shrunk + n (data.Degradation)
+                    degrade = data.Degradation(blur_prob=getattr(args, "blur_prob", 1.0),
+                                               blur_sigma=getattr(args, "blur_sigma", (0.2, 4.0)),
+                                               noise_sigma=getattr(args, "noise_sigma", (0.0, 10.0)))
                 ds = data.get_training_set(self.data_dir, dataset, self.crop_size, self.scale_factor, is_gray=is_gray,
-                                           device=self.device)
+                                           device=self.device, degrade=degrade)
                 bs, shuffle = self.batch_size, True
             else:
-                ds = data.get_test_set(self.data_dir, dataset, self.scale_factor, is_gray=is_gray, device=self.device)
+                fixed = getattr(args, "degrade_test", None)   # (s1, s2, theta in degrees, noise sigma)
+                if fixed:
+                    fixed = (fixed[0], fixed[1], math.radians(fixed[2]), fixed[3])
+                ds = data.get_test_set(self.data_dir, dataset, self.scale_factor, is_gray=is_gray, device=self.device,
+                                       degrade=fixed or None)
                 bs, shuffle = self.test_batch_size or 1, False
         except (OSError, TypeError) as e:
             if not is_train:
