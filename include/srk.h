@@ -765,6 +765,42 @@ int srk_blur_weights_host(double s1, double s2, double theta, int K, double* w);
 int srk_noise_normals_host(uint64_t seed, int64_t first_elem, int64_t n, double* z);
 int srk_philox4x32_10_host(const uint32_t* counter, const uint32_t* key, uint32_t* out);
 
+/* ---- JPEG artefacts on the loader's 8-bit patches (data.Degradation's last stage; csrc/jpeg.hip) -------------------
+ * (Additive again: new entry points only, srk_version() and everything existing unchanged.)
+ * y = decode(encode(x, Q)): libjpeg's baseline round trip at quality Q without its lossless entropy coder, a pure function
+ * from bytes to bytes in int32 arithmetic (>> arithmetic, DESCALE(v, n) = (v + (1 << (n - 1))) >> n); DESIGN.md 24 and
+ * csrc/jpeg_common.h spell out every step.  In short, per picture of C dense 8-bit planes [H][W]:
+ *   tables    Annex K (luminance, chrominance), t = clamp((base * s + 50) / 100, 1, 255), s = 5000 / Q below 50, else
+ *             200 - 2 Q, Q clamped to 1..100;
+ *   colour    color = 1 (C = 3, planes R, G, B): libjpeg's 16-bit fixed-point RGB -> YCbCr; color = 0: the planes are
+ *             Y, Cb, Cr as they stand; C = 1: a grey picture, luminance table only;
+ *   shrink    subsampling = 1 (4:2:0): 2 x 2 means with bias 1 / 2 on even / odd columns; source columns replicated to a
+ *             multiple of 16, an odd height's last row once more, then the SHRUNK plane's last row replicated to a
+ *             multiple of 8.  subsampling = 0 (4:4:4), and luma always: last row / column replicated to a multiple of 8;
+ *   DCT       jfdctint on sample - 128 (rows, then columns), q = sign(c) * ((|c| + (d >> 1)) / d) with d = t << 3, the
+ *             coefficient q * t, jidctint (columns, then rows), + 128, clamped to 0..255 (libjpeg's range-limit table
+ *             wraps far outside its range; the one deliberate departure);
+ *   expand    4:2:0: libjpeg's "fancy" triangle filter over the ceil(H/2) x ceil(W/2) real chroma samples, neighbours
+ *             clamped to them; chroma planes of at most two columns (W <= 4) are replicated instead, as libjpeg does;
+ *   colour    color = 1: libjpeg's fixed-point YCbCr -> RGB, clamped.
+ *   Q = 0 means "not compressed": the patch comes out bit for bit.
+ * srk_jpeg_u8: x dense 8-bit [B][C][H][W]; quality fp64 [B] on the device, whole numbers (they ride in the loader's one
+ *   fp64 parameter copy), one per patch; y 8-bit of x's shape, or with out_float fp32 byte / 255.0f -- the division
+ *   srk_img_resize_u8 and srk_noise_u8 make.  SRK_ERR_INVALID before anything is launched: null pointer, C not 1 or 3,
+ *   color = 1 with C = 1, subsampling outside {0, 1}, a size <= 0.  With C = 1 subsampling has nothing to act on.
+ * srk_noise_u8_bytes: srk_noise_u8 with the clamped 8-bit level itself as the result (the same kernel body), so that
+ *   bytes / 255.0f are srk_noise_u8's bits and the JPEG stage can follow the noise.
+ * Host-only twins, pure functions that need no device:
+ * srk_jpeg_quant_table_host: out[0..63] = the table (chroma 0 / 1) of `quality` in natural order.
+ * srk_jpeg_u8_host: the whole round trip as a loop over the very bodies the kernel compiles; quality int [B] on the host. */
+int srk_jpeg_u8(const uint8_t* x, void* y, const double* quality, int C, int B, int H, int W, int subsampling, int color,
+                int out_float, void* stream);
+int srk_noise_u8_bytes(const uint8_t* x, uint8_t* y, const double* sigma, uint64_t seed, int B, int64_t elems_per_patch,
+                       void* stream);
+int srk_jpeg_quant_table_host(int quality, int chroma, int* out);
+int srk_jpeg_u8_host(const uint8_t* x, uint8_t* y, const int* quality, int C, int B, int H, int W, int subsampling,
+                     int color);
+
 #ifdef __cplusplus
 }
 #endif

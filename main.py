@@ -18,7 +18,10 @@ and --resume [PATH] (continue training from the training-state file a run writes
 checkpoint as ..._ema.pkl; D in [0, 1), default 0: none; not DRCN) with --use_ema (--test_only / --test_single load it)
 and --degrade (train on LR = (HR * k) shrunk + n instead of the clean bicubic shrink: a random anisotropic Gaussian blur and
 Gaussian noise on the device, data.Degradation) with --blur_sigma LO,HI, --blur_prob P and --noise_sigma LO,HI, and
---degrade_test S1,S2,THETA_DEG,NOISE (the test sets under one fixed degradation); image folders only, not --synthetic.
+--degrade_test S1,S2,THETA_DEG,NOISE (the test sets under one fixed degradation); image folders only, not --synthetic;
+and --jpeg_quality LO,HI (with --degrade: the degraded LR patch is also JPEG-compressed at a quality drawn from LO..HI and
+decoded again, on the device, byte for byte as Pillow would) with --jpeg_prob P and --jpeg_subsampling {420,444}, and
+--jpeg_test Q (every test image's LR input compressed at quality Q, behind --degrade_test where that is given).
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N main.py ..."""
 import argparse
 import os
@@ -120,6 +123,43 @@ def _degrade_test(text):
     return s1, s2, th, ns
 
 
+def _jpeg_int(text, flag):
+    try:
+        v = int(str(text).strip())
+    except ValueError:
+        v = 0
+    if not 1 <= v <= 100:
+        raise argparse.ArgumentTypeError("%s takes whole numbers in 1..100, got %r" % (flag, text))
+    return v
+
+
+def _jpeg_quality(text):
+    """--jpeg_quality LO,HI: whole numbers, 1 <= LO <= HI <= 100."""
+    parts = str(text).split(',')
+    if len(parts) != 2:
+        raise argparse.ArgumentTypeError("--jpeg_quality takes LO,HI, got %r" % (text,))
+    lo, hi = (_jpeg_int(t, '--jpeg_quality') for t in parts)
+    if lo > hi:
+        raise argparse.ArgumentTypeError("--jpeg_quality takes LO,HI with LO <= HI, got %r" % (text,))
+    return lo, hi
+
+
+def _jpeg_test(text):
+    """--jpeg_test Q: a whole number in 1..100."""
+    return _jpeg_int(text, '--jpeg_test')
+
+
+def _jpeg_prob(text):
+    """--jpeg_prob: a number in [0, 1] (NaN fails both comparisons)."""
+    try:
+        v = float(text)
+    except ValueError:
+        v = float('nan')
+    if not 0.0 <= v <= 1.0:
+        raise argparse.ArgumentTypeError("--jpeg_prob takes a number in [0, 1], got %r" % (text,))
+    return v
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="MI355X-native SR collection (reference-compatible CLI)")
     p.add_argument('--model_name', type=str, default='SRGAN',
@@ -205,10 +245,23 @@ def parse_args(argv=None):
     p.add_argument('--degrade_test', type=_degrade_test, default=None, metavar='S1,S2,THETA_DEG,NOISE',
                    help='test(): every test image under this one degradation (blur standard deviations, angle in degrees, '
                         'noise standard deviation; the noise seeded by the image\'s index).  Image folders only')
+    p.add_argument('--jpeg_quality', type=_jpeg_quality, default=None, metavar='LO,HI',
+                   help='--degrade: also JPEG-compress the degraded LR patch at a quality drawn from LO..HI (whole numbers '
+                        'in 1..100) and decode it again, on the device (default: no JPEG stage)')
+    p.add_argument('--jpeg_prob', type=_jpeg_prob, default=1.0, metavar='P',
+                   help='--jpeg_quality: probability that a patch is compressed at all (default 1)')
+    p.add_argument('--jpeg_subsampling', type=str, default='420', choices=['420', '444'],
+                   help='--jpeg_quality / --jpeg_test: chroma subsampling, 4:2:0 (Pillow\'s default) or 4:4:4')
+    p.add_argument('--jpeg_test', type=_jpeg_test, default=None, metavar='Q',
+                   help='test(): every test image\'s LR input JPEG-compressed at quality Q and decoded again, behind '
+                        '--degrade_test where that is given.  Image folders only')
     args = p.parse_args(argv)
-    for flag in ('degrade', 'degrade_test'):
+    for flag in ('degrade', 'degrade_test', 'jpeg_quality', 'jpeg_test'):
         if getattr(args, flag) and args.synthetic:
             p.error('--%s: synthetic patches are not degraded; train and test on image folders (drop --synthetic)' % flag)
+    if args.jpeg_quality and not args.degrade:
+        p.error('--jpeg_quality is a stage of the training degradation: pass --degrade too (--blur_prob 0 --noise_sigma 0,0 '
+                'leaves JPEG alone)')
     if args.ema_decay > 0 and args.model_name == 'DRCN':
         p.error('--ema_decay %g: DRCN keeps no EMA of its weights (its combine weights w train outside the flat '
                 'parameter buffer); use --ema_decay 0 or another model' % args.ema_decay)

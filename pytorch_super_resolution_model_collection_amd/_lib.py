@@ -234,6 +234,10 @@ _PROTOTYPES = {
                                       ctypes.POINTER(ctypes.c_double)]),
     "srk_noise_normals_host": (c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_double)]),
     "srk_philox4x32_10_host": (c_int, [ctypes.POINTER(ctypes.c_uint32)] * 3),
+    "srk_jpeg_u8": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp]),
+    "srk_noise_u8_bytes": (c_int, [c_vp, c_vp, c_vp, ctypes.c_uint64, c_int, ctypes.c_int64, c_vp]),
+    "srk_jpeg_quant_table_host": (c_int, [c_int, c_int, ctypes.POINTER(c_int)]),
+    "srk_jpeg_u8_host": (c_int, [c_vp, c_vp, ctypes.POINTER(c_int), c_int, c_int, c_int, c_int, c_int, c_int]),
 }
 
 _lib = None

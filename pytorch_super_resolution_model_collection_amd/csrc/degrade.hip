@@ -91,12 +91,15 @@ static void launch_blur(const uint8_t* x, uint8_t* y, const double* w, int plane
   hipLaunchKernelGGL(k_blur_u8<K>, dim3(blocks), dim3(256), 0, s, x, y, w, planes_per_patch, H, W, tiles_x, tiles_per_plane);
 }
 
-// y[e] = float(clamp(round_half_up(x[e] + sigma[patch of e] * z[e]), 0, 255)) / 255.0f over `total` elements.
-__global__ __launch_bounds__(256) void k_noise_u8(const uint8_t* __restrict__ x, float* __restrict__ y,
+// y[e] = float(clamp(round_half_up(x[e] + sigma[patch of e] * z[e]), 0, 255)) / 255.0f over `total` elements; with
+// OutT = uint8_t the clamped level itself (srk_noise_u8_bytes: what the JPEG stage takes).
+template <typename OutT>
+__global__ __launch_bounds__(256) void k_noise_u8(const uint8_t* __restrict__ x, OutT* __restrict__ y,
                                                   const double* __restrict__ sigma, uint64_t seed, int64_t elems_per_patch,
                                                   int64_t total) {
   const int64_t groups = (total + 3) >> 2;
-  const bool vec = aligned16(y) && (reinterpret_cast<uintptr_t>(x) & 3) == 0;
+  constexpr bool kBytes = std::is_same<OutT, uint8_t>::value;
+  const bool vec = (kBytes ? (reinterpret_cast<uintptr_t>(y) & 3) == 0 : aligned16(y)) && (reinterpret_cast<uintptr_t>(x) & 3) == 0;
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < groups; q += (int64_t)gridDim.x * 256) {
     const int64_t e0 = q << 2;
     const int n = total - e0 < 4 ? (int)(total - e0) : 4;
@@ -115,15 +118,21 @@ __global__ __launch_bounds__(256) void k_noise_u8(const uint8_t* __restrict__ x,
     }
     double z[4] = {0.0, 0.0, 0.0, 0.0};
     if (any) noise_normals4(seed, (uint64_t)q, z);   // (a group whose sigmas are all zero adds 0 * z: skip the generator)
-    float out[4];
+    OutT out[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const double r = floor((double)in[k] + sg[k] * z[k] + 0.5);
-      out[k] = (float)fmin(fmax(r, 0.0), 255.0) / 255.f;
+      if constexpr (kBytes) out[k] = (uint8_t)(int)fmin(fmax(r, 0.0), 255.0);
+      else out[k] = (float)fmin(fmax(r, 0.0), 255.0) / 255.f;
     }
     if (vec && n == 4) {
-      f32x4 o = {out[0], out[1], out[2], out[3]};
-      *reinterpret_cast<f32x4*>(y + e0) = o;
+      if constexpr (kBytes) {
+        *reinterpret_cast<uint32_t*>(y + e0) =
+            (uint32_t)out[0] | ((uint32_t)out[1] << 8) | ((uint32_t)out[2] << 16) | ((uint32_t)out[3] << 24);
+      } else {
+        f32x4 o = {out[0], out[1], out[2], out[3]};
+        *reinterpret_cast<f32x4*>(y + e0) = o;
+      }
     } else {
       for (int k = 0; k < n; ++k) y[e0 + k] = out[k];
     }
@@ -157,15 +166,26 @@ extern "C" int srk_blur_u8(const uint8_t* x, uint8_t* y, const double* w, int pl
   return check_launch("blur_u8");
 }
 
-extern "C" int srk_noise_u8(const uint8_t* x, float* y, const double* sigma, uint64_t seed, int B, int64_t elems_per_patch,
-                            void* stream) {
-  SRK_REQUIRE(x && y && sigma, "noise_u8: null pointer");
-  SRK_REQUIRE(B > 0 && elems_per_patch > 0, "noise_u8: bad dims (B %d, %lld elements per patch)", B,
+template <typename OutT>
+static int launch_noise(const char* what, const uint8_t* x, OutT* y, const double* sigma, uint64_t seed, int B,
+                        int64_t elems_per_patch, void* stream) {
+  SRK_REQUIRE(x && y && sigma, "%s: null pointer", what);
+  SRK_REQUIRE(B > 0 && elems_per_patch > 0, "%s: bad dims (B %d, %lld elements per patch)", what, B,
               (long long)elems_per_patch);
   const int64_t total = (int64_t)B * elems_per_patch;
-  hipLaunchKernelGGL(k_noise_u8, dim3(grid_for((size_t)((total + 3) >> 2), 256, (size_t)kNumCU * 8)), dim3(256), 0,
+  hipLaunchKernelGGL(k_noise_u8<OutT>, dim3(grid_for((size_t)((total + 3) >> 2), 256, (size_t)kNumCU * 8)), dim3(256), 0,
                      (hipStream_t)stream, x, y, sigma, seed, elems_per_patch, total);
-  return check_launch("noise_u8");
+  return check_launch(what);
+}
+
+extern "C" int srk_noise_u8(const uint8_t* x, float* y, const double* sigma, uint64_t seed, int B, int64_t elems_per_patch,
+                            void* stream) {
+  return launch_noise("noise_u8", x, y, sigma, seed, B, elems_per_patch, stream);
+}
+
+extern "C" int srk_noise_u8_bytes(const uint8_t* x, uint8_t* y, const double* sigma, uint64_t seed, int B,
+                                  int64_t elems_per_patch, void* stream) {
+  return launch_noise("noise_u8_bytes", x, y, sigma, seed, B, elems_per_patch, stream);
 }
 
 extern "C" int srk_blur_weights_host(double s1, double s2, double theta, int K, double* w) {

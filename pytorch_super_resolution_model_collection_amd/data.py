@@ -17,7 +17,8 @@ augmented 8-bit patch (one small D2H/H2D per patch, gray mode only): its integer
 Not provided: the BSDS300 HTTP download of data.py:9-30 (no network code in this package).
 Beyond the reference: `Degradation` -- with `degrade=` set, the LR image is no longer the clean bicubic
 shrink of the HR patch but LR = (HR * k) shrunk + n: a random anisotropic Gaussian blur in front of the shrink and Gaussian
-noise behind it, both HIP kernels on the loader stream (csrc/degrade.hip).  Without it nothing changes, draws included.
+noise behind it, both HIP kernels on the loader stream (csrc/degrade.hip), and with `jpeg_quality` JPEG compression of the
+result (csrc/jpeg.hip).  Without it nothing changes, draws included.
 """
 import ctypes
 import math
@@ -32,6 +33,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
+from .ops import jpeg_subsampling as jpeg_subsampling_code
 
 BICUBIC = 3  # PIL.Image.BICUBIC / srk_interp
 
@@ -216,6 +218,24 @@ class _Device(object):
             check(self.lib.srk_noise_u8(ptr(x), ptr(y), ptr(sigma), int(seed), b, x.numel() // b, self._sp), "srk_noise_u8")
         return y
 
+    def noise_bytes(self, x, sigma, seed, b):
+        """srk_noise_u8_bytes: noise() with the 8-bit level itself as the result, for the JPEG stage to follow."""
+        with self._on_stream():
+            y = torch.empty(x.shape, dtype=torch.uint8, device=self.device)
+            check(self.lib.srk_noise_u8_bytes(ptr(x), ptr(y), ptr(sigma), int(seed), b, x.numel() // b, self._sp),
+                  "srk_noise_u8_bytes")
+        return y
+
+    def jpeg(self, x, quality, subsampling, color):
+        """srk_jpeg_u8: dense 8-bit [b, c, h, w] -> fp32 bytes / 255 of each patch compressed at quality[b] (fp64 on the
+        device, 0 = left as it is) and decoded again."""
+        b, c, h, w = (int(v) for v in x.shape)
+        with self._on_stream():
+            y = torch.empty(x.shape, dtype=torch.float32, device=self.device)
+            check(self.lib.srk_jpeg_u8(ptr(x), ptr(y), ptr(quality), c, b, h, w, int(subsampling), int(bool(color)), 1,
+                                       self._sp), "srk_jpeg_u8")
+        return y
+
     def hand_over(self, *tensors):
         """Make the consumer's current stream wait for the loader stream; tensors become usable there."""
         cur = torch.cuda.current_stream(self.device)
@@ -258,29 +278,42 @@ def _centred(tables, K):
     return out
 
 
-def _degrade_u8(dev, planes, weights, sigma, seed, oh, ow):
-    """blur -> Pillow-exact bicubic shrink -> noise of dense 8-bit planes [B, C, H, W] on the loader stream.  weights
-    [B, K, K] and sigma [B] are host fp64 arrays; they cross in one copy.  A batch without a blurred patch skips the blur
-    (the delta table returns its input) and one without noise takes the shrink's own / 255: the same bits, fewer launches."""
+def _degrade_u8(dev, planes, weights, sigma, seed, oh, ow, quality=None, subsampling=1, color=True):
+    """blur -> Pillow-exact bicubic shrink -> noise -> JPEG of dense 8-bit planes [B, C, H, W] on the loader stream.
+    weights [B, K, K], sigma [B] and quality [B] (or None: no JPEG stage) are host fp64 arrays; they cross in one copy.  A
+    batch without a blurred patch skips the blur (the delta table returns its input), one without noise takes the shrink's
+    own bytes and one without a compressed patch (quality 0) the / 255 of the stage before: the same bits, fewer launches."""
     b, c, h, w = (int(v) for v in planes.shape)
     K = weights.shape[-1]
     blurred = bool((weights[:, K // 2, K // 2] != 1.0).any())
     noisy = bool((sigma != 0.0).any())
-    if blurred or noisy:
-        params = dev.upload_f64(np.concatenate([weights.reshape(-1), sigma.reshape(-1)]))
+    jpeg = quality is not None and bool((quality != 0.0).any())
+    if blurred or noisy or jpeg:
+        params = dev.upload_f64(np.concatenate([weights.reshape(-1), sigma.reshape(-1)] + ([quality.reshape(-1)] if jpeg else [])))
     q = dev.blur(planes, params[:weights.size].view(b, K, K), c, b, h, w) if blurred else planes
-    lr = dev.resize(q, _CHW(h, w), b * c, h, w, oh, ow, out_float=not noisy).view(b, c, oh, ow)
-    return dev.noise(lr, params[weights.size:], seed, b) if noisy else lr
+    lr = dev.resize(q, _CHW(h, w), b * c, h, w, oh, ow, out_float=not (noisy or jpeg)).view(b, c, oh, ow)
+    if noisy:
+        lr = (dev.noise_bytes if jpeg else dev.noise)(lr, params[weights.size:weights.size + b], seed, b)
+    return dev.jpeg(lr, params[weights.size + b:], subsampling, color) if jpeg else lr
+
+
+def _check_jpeg_quality(q, what):
+    if int(q) != q or not 1 <= int(q) <= 100:
+        raise ValueError("%s must be a whole number in 1..100 (got %r)" % (what, q))
+    return int(q)
 
 
 class Degradation(object):
     """The classical degradation model of blind super-resolution, LR = (HR * k) shrunk + n: per patch,
     with probability `blur_prob`, an anisotropic Gaussian blur with standard deviations drawn from `blur_sigma` = (lo, hi)
     pixels and a uniform angle; then the loader's own bicubic shrink; then Gaussian noise of a standard deviation drawn
-    from `noise_sigma` = (lo, hi) 8-bit levels (hi = 0: no noise, and no draw for it).  Draws come from Python's global
-    `random`, after the batch's patch draws."""
+    from `noise_sigma` = (lo, hi) 8-bit levels (hi = 0: no noise, and no draw for it); then, with `jpeg_quality` = (lo, hi)
+    set and with probability `jpeg_prob`, JPEG compression at a quality drawn from it and decoding again (DESIGN.md 24;
+    `jpeg_subsampling` '4:2:0' as Pillow's default, or '4:4:4').  Draws come from Python's global `random`, after the
+    batch's patch draws; those of the JPEG stage (draw_jpeg) after all others, and only when it is on."""
 
-    def __init__(self, blur_prob=1.0, blur_sigma=(0.2, 4.0), noise_sigma=(0.0, 10.0)):
+    def __init__(self, blur_prob=1.0, blur_sigma=(0.2, 4.0), noise_sigma=(0.0, 10.0), jpeg_quality=None, jpeg_prob=1.0,
+                 jpeg_subsampling='4:2:0'):
         self.blur_prob = float(blur_prob)
         self.blur_sigma = (float(blur_sigma[0]), float(blur_sigma[1]))
         self.noise_sigma = (float(noise_sigma[0]), float(noise_sigma[1]))
@@ -290,6 +323,16 @@ class Degradation(object):
             raise ValueError("blur_sigma must be 0 < lo <= hi (got %r)" % (blur_sigma,))
         if not 0.0 <= self.noise_sigma[0] <= self.noise_sigma[1] < float('inf'):
             raise ValueError("noise_sigma must be 0 <= lo <= hi (got %r)" % (noise_sigma,))
+        self.jpeg_quality, self.jpeg_prob = None, float(jpeg_prob)
+        if jpeg_quality is not None:
+            if len(jpeg_quality) != 2:
+                raise ValueError("jpeg_quality must be (lo, hi) or None (got %r)" % (jpeg_quality,))
+            self.jpeg_quality = tuple(_check_jpeg_quality(q, "jpeg_quality's bounds") for q in jpeg_quality)
+            if self.jpeg_quality[0] > self.jpeg_quality[1]:
+                raise ValueError("jpeg_quality must be lo <= hi (got %r)" % (jpeg_quality,))
+        if not 0.0 <= self.jpeg_prob <= 1.0:
+            raise ValueError("jpeg_prob must lie in [0, 1] (got %r)" % (jpeg_prob,))
+        self.jpeg_subsampling = jpeg_subsampling_code(jpeg_subsampling)       # 1: 4:2:0, 0: 4:4:4
 
     def draw(self, batch):
         """(weights [B, K, K], sigma [B], seed) of one batch as host arrays.  Per patch: random() < blur_prob -> s1, s2,
@@ -310,10 +353,26 @@ class Degradation(object):
         K = max([w.shape[0] for w in tables if w is not None] + [3])
         return _centred(tables, K), sigma, seed
 
-    def apply(self, dev, patches, lr_sz):
-        """Dense 8-bit patches [B, C, crop, crop] on the device -> the degraded fp32 lr [B, C, lr_sz, lr_sz]."""
+    def draw_jpeg(self, batch):
+        """quality [B] of one batch as a host fp64 array (0: the patch is not compressed), or None when the JPEG stage is
+        off -- then nothing is drawn.  Runs after draw().  Per patch: random() < jpeg_prob -> randint(lo, hi)."""
+        if self.jpeg_quality is None:
+            return None
+        lo, hi = self.jpeg_quality
+        quality = np.zeros(batch, np.float64)
+        for j in range(batch):
+            if random.random() < self.jpeg_prob:
+                quality[j] = random.randint(lo, hi)
+        return quality
+
+    def apply(self, dev, patches, lr_sz, color=True):
+        """Dense 8-bit patches [B, C, crop, crop] on the device -> the degraded fp32 lr [B, C, lr_sz, lr_sz].  color: the
+        planes are R, G, B (else Y, Cb, Cr); only the JPEG stage asks."""
         weights, sigma, seed = self.draw(int(patches.shape[0]))
-        return _degrade_u8(dev, patches, weights, sigma, seed, lr_sz, lr_sz)
+        quality = self.draw_jpeg(int(patches.shape[0]))
+        if quality is None:
+            return _degrade_u8(dev, patches, weights, sigma, seed, lr_sz, lr_sz)
+        return _degrade_u8(dev, patches, weights, sigma, seed, lr_sz, lr_sz, quality, self.jpeg_subsampling, color)
 
 
 class TrainDatasetFromFolder(object):
@@ -419,7 +478,7 @@ class TrainDatasetFromFolder(object):
         st = _CHW(crop, crop)
         hr = dev.resize(patches, st, b * c, crop, crop, crop, crop, out_float=True).view(b, c, crop, crop)
         if self.degrade is not None:
-            lr = self.degrade.apply(dev, patches.contiguous(), lr_sz)
+            lr = self.degrade.apply(dev, patches.contiguous(), lr_sz, color=not self.is_gray)
         else:
             lr = dev.resize(patches, st, b * c, crop, crop, lr_sz, lr_sz, out_float=True).view(b, c, lr_sz, lr_sz)
         bc = dev.bicubic_of_lr(lr, crop, crop)
@@ -438,8 +497,13 @@ class TrainDatasetFromFolder(object):
 class TestDatasetFromFolder(object):
     """dataset.py:106-149 with device-side resizes."""
 
-    def __init__(self, image_dir, is_gray=False, scale_factor=4, device="cuda", degrade=None):
+    def __init__(self, image_dir, is_gray=False, scale_factor=4, device="cuda", degrade=None, jpeg=None,
+                 jpeg_subsampling='4:2:0'):
         self.image_filenames = [join(image_dir, x) for x in sorted(listdir(image_dir)) if is_image_file(x)]
+        # jpeg: None, or one FIXED quality 1..100 at which every low-resolution image is compressed and decoded again,
+        # behind the degradation where there is one
+        self.jpeg = None if jpeg is None else _check_jpeg_quality(jpeg, "jpeg")
+        self.jpeg_subsampling = jpeg_subsampling_code(jpeg_subsampling)
         self.is_gray, self.scale_factor = is_gray, scale_factor
         # degrade: None, or one FIXED degradation (s1, s2, theta in radians, noise sigma in 8-bit levels) for every image,
         # the noise seeded with the image's index: an item is the same on every read
@@ -471,12 +535,16 @@ class TestDatasetFromFolder(object):
         img = dev.upload(hwc)
         st = _HWC(h, w, c)
         hr = dev.resize(img, st, c, h, w, hr_h, hr_w, out_float=True)
-        if self.degrade is not None:
-            s1, s2, theta, noise_sigma = self.degrade
+        if self.degrade is not None or self.jpeg is not None:
             with torch.cuda.stream(dev.stream):
                 planes = img.permute(2, 0, 1).contiguous().unsqueeze(0)   # (the blur reads dense planes)
-            lr = _degrade_u8(dev, planes, blur_weights(s1, s2, theta)[None], np.array([noise_sigma], np.float64),
-                             index, lr_h, lr_w)[0]
+            if self.degrade is not None:
+                s1, s2, theta, noise_sigma = self.degrade
+                table = blur_weights(s1, s2, theta)[None]
+            else:                                                         # a clean shrink, then JPEG
+                noise_sigma, table = 0.0, _centred([None], 3)
+            jpeg = () if self.jpeg is None else (np.array([self.jpeg], np.float64), self.jpeg_subsampling, not self.is_gray)
+            lr = _degrade_u8(dev, planes, table, np.array([noise_sigma], np.float64), index, lr_h, lr_w, *jpeg)[0]
         else:
             lr = dev.resize(img, st, c, h, w, lr_h, lr_w, out_float=True)
         bc = dev.bicubic_of_lr(lr.unsqueeze(0), hr_h, hr_w)[0]
@@ -497,7 +565,8 @@ def get_training_set(data_dir, datasets, crop_size, scale_factor, is_gray=False,
                                   fliplr=True, fliptb=True, scale_factor=scale_factor, device=device, degrade=degrade)
 
 
-def get_test_set(data_dir, dataset, scale_factor, is_gray=False, device="cuda", degrade=None):
+def get_test_set(data_dir, dataset, scale_factor, is_gray=False, device="cuda", degrade=None, jpeg=None,
+                 jpeg_subsampling='4:2:0'):
     """data.py:54-65"""
     if dataset == 'bsds300':
         test_dir = join(data_dir, "BSDS300/images", "test")
@@ -505,7 +574,8 @@ def get_test_set(data_dir, dataset, scale_factor, is_gray=False, device="cuda", 
         test_dir = join(data_dir, dataset, 'DIV2K_test_LR_bicubic/X4')
     else:
         test_dir = join(data_dir, dataset)
-    return TestDatasetFromFolder(test_dir, is_gray=is_gray, scale_factor=scale_factor, device=device, degrade=degrade)
+    return TestDatasetFromFolder(test_dir, is_gray=is_gray, scale_factor=scale_factor, device=device, degrade=degrade,
+                                 jpeg=jpeg, jpeg_subsampling=jpeg_subsampling)
 
 
 class PatchLoader(object):

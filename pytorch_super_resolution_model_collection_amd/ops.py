@@ -2017,6 +2017,61 @@ def noise_u8(x, sigma, seed):
     return y
 
 
+JPEG_SUBSAMPLING = {"4:2:0": 1, "420": 1, 420: 1, "4:4:4": 0, "444": 0, 444: 0}
+
+
+def jpeg_subsampling(value):
+    """'4:2:0' / '420' / 420 -> 1, '4:4:4' / '444' / 444 -> 0 (srk_jpeg_u8's subsampling); anything else is a ValueError."""
+    try:
+        return JPEG_SUBSAMPLING[value]
+    except (KeyError, TypeError):
+        raise ValueError("jpeg subsampling must be '4:2:0' or '4:4:4' (got %r)" % (value,))
+
+
+def jpeg_u8(x, quality, subsampling='4:2:0', color=True, out_float=False):
+    """JPEG artefacts on 8-bit patches x [B,C,H,W] (C 1 or 3) on the device: srk_jpeg_u8, every patch compressed at its
+    quality and decoded again, byte for byte what Pillow's save(quality=q, subsampling=...) and open give (libjpeg's integer
+    baseline path).  quality: an integer tensor [B] (or a Python int for all patches), 1..100, and 0 = leave
+    the patch as it is; a tensor's values beyond that range act as libjpeg clamps them, below 1 as 1 and above 100 as 100.  color: the planes are R, G, B (needs C = 3); else they are Y, Cb, Cr, or with C = 1 a grey
+    picture.  Returns uint8, or with out_float the fp32 bytes / 255."""
+    _require_u8("jpeg_u8", x)
+    if x.dim() != 4 or x.numel() == 0:
+        raise RuntimeError("jpeg_u8 expects a non-empty x [B,C,H,W], got shape %s" % (tuple(x.shape),))
+    b, c, h, w = (int(v) for v in x.shape)
+    sub = jpeg_subsampling(subsampling)
+    if isinstance(quality, torch.Tensor):
+        if quality.is_floating_point() or quality.dtype == torch.bool or tuple(quality.shape) != (b,):
+            raise RuntimeError("jpeg_u8: quality must be an integer tensor [%d] or an int, got %s %s"
+                               % (b, quality.dtype, tuple(quality.shape)))
+        q = quality.to(device=x.device, dtype=torch.float64)      # (not inspected: a look would wait for the device)
+    else:
+        if int(quality) != quality or not 0 <= quality <= 100:
+            raise ValueError("jpeg_u8: quality must be a whole number in 0..100, 0: not compressed (got %r)" % (quality,))
+        q = torch.full((b,), float(int(quality)), dtype=torch.float64, device=x.device)
+    x = x.contiguous()
+    y = torch.empty(x.shape, dtype=torch.float32 if out_float else torch.uint8, device=x.device)
+    check(_lib.load().srk_jpeg_u8(ptr(x), ptr(y), ptr(q), c, b, h, w, sub, int(bool(color)), int(bool(out_float)),
+                                  stream_ptr()), "srk_jpeg_u8")
+    return y
+
+
+def noise_u8_bytes(x, sigma, seed):
+    """noise_u8 with the clamped 8-bit level itself as the result (srk_noise_u8_bytes): bytes / 255 are noise_u8's bits."""
+    _require_u8("noise_u8_bytes", x)
+    if x.dim() < 1 or x.numel() == 0:
+        raise RuntimeError("noise_u8_bytes expects a non-empty [B,...] tensor, got shape %s" % (tuple(x.shape),))
+    b = int(x.shape[0])
+    sigma = _require_f64("noise_u8_bytes", "sigma", sigma, (b,))
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("noise_u8_bytes: seed must fit 64 bits (got %d)" % seed)
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    check(_lib.load().srk_noise_u8_bytes(ptr(x), ptr(y), ptr(sigma), seed, b, x.numel() // b, stream_ptr()),
+          "srk_noise_u8_bytes")
+    return y
+
+
 # ------------------------------------------------------------------------------------------------
 # Tiled super-resolution of one picture (tiling.py, csrc/tile.hip): gather the plan's tiles, stitch their outputs
 # ------------------------------------------------------------------------------------------------

@@ -120,10 +120,12 @@ class _Trainer(object):
         if self.kind in ("srgan", "drcn") and (getattr(args, "ssim_weight", 0.0) or 0.0) > 0:
             raise ValueError("ssim_weight: %s has no SSIM mix (main.py --ssim_weight)" % self.model_name)
         check_perceptual_args(args, self.kind)
-        for flag in ("degrade", "degrade_test"):
+        for flag in ("degrade", "degrade_test", "jpeg_quality", "jpeg_test"):
             if getattr(args, flag, None) and getattr(args, "synthetic", False):
                 raise ValueError("%s: synthetic patches are not degraded, train and test on image folders (main.py "
                                  "--%s without --synthetic)" % (flag, flag))
+        if getattr(args, "jpeg_quality", None) and not getattr(args, "degrade", False):
+            raise ValueError("jpeg_quality is a stage of the training degradation (main.py --jpeg_quality with --degrade)")
         self.ema_decay = optim._check_ema_decay(getattr(args, "ema_decay", 0.0))
         if self.kind == "drcn" and self.ema_decay > 0:
             raise ValueError("ema_decay: %s keeps no EMA of its weights (main.py --ema_decay)" % self.model_name)
@@ -257,7 +259,10 @@ class _Trainer(object):
                 if getattr(args, "degrade", False):   # main.py --degrade: LR = (HR * k) shrunk + n (data.Degradation)
                     degrade = data.Degradation(blur_prob=getattr(args, "blur_prob", 1.0),
                                                blur_sigma=getattr(args, "blur_sigma", (0.2, 4.0)),
-                                               noise_sigma=getattr(args, "noise_sigma", (0.0, 10.0)))
+                                               noise_sigma=getattr(args, "noise_sigma", (0.0, 10.0)),
+                                               jpeg_quality=getattr(args, "jpeg_quality", None),
+                                               jpeg_prob=getattr(args, "jpeg_prob", 1.0),
+                                               jpeg_subsampling=getattr(args, "jpeg_subsampling", "420"))
                 ds = data.get_training_set(self.data_dir, dataset, self.crop_size, self.scale_factor, is_gray=is_gray,
                                            device=self.device, degrade=degrade)
                 bs, shuffle = self.batch_size, True
@@ -266,7 +271,8 @@ class _Trainer(object):
                 if fixed:
                     fixed = (fixed[0], fixed[1], math.radians(fixed[2]), fixed[3])
                 ds = data.get_test_set(self.data_dir, dataset, self.scale_factor, is_gray=is_gray, device=self.device,
-                                       degrade=fixed or None)
+                                       degrade=fixed or None, jpeg=getattr(args, "jpeg_test", None),
+                                       jpeg_subsampling=getattr(args, "jpeg_subsampling", "420"))
                 bs, shuffle = self.test_batch_size or 1, False
         except (OSError, TypeError) as e:
             if not is_train:
