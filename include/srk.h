@@ -801,6 +801,44 @@ int srk_jpeg_quant_table_host(int quality, int chroma, int* out);
 int srk_jpeg_u8_host(const uint8_t* x, uint8_t* y, const int* quality, int C, int B, int H, int W, int subsampling,
                      int color);
 
+/* ---- Channel attention: the gate of RCAN's residual channel attention block (csrc/ca.hip, csrc/ca_common.h) ---------
+ * (Additive again: new entry points only, srk_version() and everything existing unchanged.)
+ * t, x, y, g, dt dense NHWC [N][H][W][C]; W1 [Cr][C], b1 [Cr], W2 [C][Cr], b2 [C] (1x1 conv filters, [out][in]).
+ *   m[n][c] = (1 / HW) sum_hw t[n][h][w][c]       h[n] = relu(W1 m[n] + b1)       s[n] = sigmoid(W2 h[n] + b2)
+ *   y = t * s[n][c] (+ x)                          x == NULL: no skip
+ * and from g = dL/dy (dL/dx is g itself: the caller hands it on, no kernel and no argument here)
+ *   ds[n][c] = sum_hw g * t      da = ds * s * (1 - s)      dh = (W2^T da) where h > 0      dm = W1^T dh
+ *   dt = g * s[n][c] + dm[n][c] / HW
+ *   dW2 = sum_n da_n h_n^T   db2 = sum_n da_n   dW1 = sum_n dh_n m_n^T   db1 = sum_n dh_n
+ * Both sums over HW are fp64 sums of exact products through srk_channel_attention_splits() per-block partials a sample,
+ * added up in index order; the MLP and its backward are fp64; the sums over n run in index order.  No atomics: two calls
+ * on the same inputs give the same bits.  Only y = fma(t, s, x) and dt = fma(g, s, dm / HW) are fp32.
+ * Supported: C <= SRK_CA_MAX_C, Cr <= SRK_CA_MAX_CR (SRK_ERR_UNSUPPORTED beyond, the message names the limit); 16-byte
+ * accesses where C % 4 == 0 and the tensors are 16-byte aligned, else a 4-byte path.  SRK_ERR_BAD_ARG: a null pointer, a
+ * size <= 0, Cr > C.  SRK_ERR_WORKSPACE: fewer than srk_channel_attention_workspace() bytes.
+ * srk_channel_attention_splits: the partial blocks per sample the planner chooses (a negative status for bad sizes).
+ * srk_channel_attention_workspace: bytes either direction needs (0 for bad sizes); 8-byte aligned, contents undefined.
+ * srk_channel_attention_forward: two launches.  m [N][C], h [N][Cr], s [N][C] are what the backward reads; all three
+ *   NULL when no backward follows.
+ * srk_channel_attention_backward: three launches (two when dw1, db1, dw2 and db2 are all NULL; each may be NULL alone).
+ *   out = beta * out + gradient for the four parameter gradients; beta == 0 never reads out.
+ * srk_channel_attention_host: forward (and, with g != NULL, backward) on host pointers with everything after the fp32
+ *   inputs in double, from the very MLP bodies the kernels compile. */
+#define SRK_CA_MAX_C 256
+#define SRK_CA_MAX_CR 64
+int srk_channel_attention_splits(int N, int H, int W, int C);
+size_t srk_channel_attention_workspace(int N, int H, int W, int C);
+int srk_channel_attention_forward(const float* t, const float* x, const float* w1, const float* b1, const float* w2,
+                                  const float* b2, int N, int H, int W, int C, int Cr, float* y, float* m, float* h, float* s,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+int srk_channel_attention_backward(const float* g, const float* t, const float* w1, const float* w2, const float* m,
+                                   const float* h, const float* s, int N, int H, int W, int C, int Cr, float* dt, float* dw1,
+                                   float* db1, float* dw2, float* db2, float beta, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+int srk_channel_attention_host(const float* t, const float* x, const float* w1, const float* b1, const float* w2,
+                               const float* b2, const float* g, int N, int H, int W, int C, int Cr, double* y, double* dt,
+                               double* dw1, double* db1, double* dw2, double* db2);
+
 #ifdef __cplusplus
 }
 #endif

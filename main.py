@@ -22,6 +22,8 @@ Gaussian noise on the device, data.Degradation) with --blur_sigma LO,HI, --blur_
 and --jpeg_quality LO,HI (with --degrade: the degraded LR patch is also JPEG-compressed at a quality drawn from LO..HI and
 decoded again, on the device, byte for byte as Pillow would) with --jpeg_prob P and --jpeg_subsampling {420,444}, and
 --jpeg_test Q (every test image's LR input compressed at quality Q, behind --degrade_test where that is given).
+--model_name RCAN (not in the reference: EDSR's trunk with channel attention, models.RCANNet) with --rcan_groups G,
+--rcan_blocks B and --rcan_reduction R (defaults 10, 20, 16); every flag of the common trainer works with it but --tile.
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N main.py ..."""
 import argparse
 import os
@@ -41,6 +43,17 @@ def _tile(text):
     v = int(text)
     if v < 1:
         raise argparse.ArgumentTypeError("--tile takes a positive integer or 'auto'")
+    return v
+
+
+def _positive(text):
+    """--rcan_groups / --rcan_blocks / --rcan_reduction: a whole number >= 1."""
+    try:
+        v = int(text)
+    except ValueError:
+        v = 0
+    if v < 1:
+        raise argparse.ArgumentTypeError("a whole number >= 1 is expected, got %r" % (text,))
     return v
 
 
@@ -163,7 +176,8 @@ def _jpeg_prob(text):
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="MI355X-native SR collection (reference-compatible CLI)")
     p.add_argument('--model_name', type=str, default='SRGAN',
-                   choices=['SRCNN', 'VDSR', 'ESPCN', 'FSRCNN', 'SRGAN', 'LapSRN', 'EDSR', 'DRCN'], help='The type of model')
+                   choices=['SRCNN', 'VDSR', 'ESPCN', 'FSRCNN', 'SRGAN', 'LapSRN', 'EDSR', 'DRCN', 'RCAN'],
+                   help='The type of model')
     p.add_argument('--data_dir', type=str, default='../Data')
     p.add_argument('--train_dataset', type=_names, default=['DIV2K'], help='The name(s) of the training dataset, comma-separated')
     p.add_argument('--test_dataset', type=_names, default=['Set5', 'Set14', 'Urban100'], help='The name(s) of the test dataset, comma-separated')
@@ -255,7 +269,18 @@ def parse_args(argv=None):
     p.add_argument('--jpeg_test', type=_jpeg_test, default=None, metavar='Q',
                    help='test(): every test image\'s LR input JPEG-compressed at quality Q and decoded again, behind '
                         '--degrade_test where that is given.  Image folders only')
+    p.add_argument('--rcan_groups', type=_positive, default=10, metavar='G', help='RCAN: residual groups (default 10)')
+    p.add_argument('--rcan_blocks', type=_positive, default=20, metavar='B',
+                   help='RCAN: residual channel attention blocks per group (default 20)')
+    p.add_argument('--rcan_reduction', type=_positive, default=16, metavar='R',
+                   help='RCAN: channel reduction of the attention gate, a divisor of 64 (default 16)')
     args = p.parse_args(argv)
+    if args.model_name == 'RCAN' and args.tile is not None:
+        p.error('--tile: RCAN\'s channel attention depends on the whole image, its pictures run in one pass (drop --tile)')
+    if args.model_name == 'RCAN' and 64 % args.rcan_reduction:
+        p.error('--rcan_reduction %d does not divide RCAN\'s 64 channels' % args.rcan_reduction)
+    if args.model_name == 'RCAN' and args.scale_factor not in (2, 4, 8):
+        p.error('--scale_factor %d: RCAN upsamples by 2, 4 or 8' % args.scale_factor)
     for flag in ('degrade', 'degrade_test', 'jpeg_quality', 'jpeg_test'):
         if getattr(args, flag) and args.synthetic:
             p.error('--%s: synthetic patches are not degraded; train and test on image folders (drop --synthetic)' % flag)

@@ -238,6 +238,11 @@ _PROTOTYPES = {
     "srk_noise_u8_bytes": (c_int, [c_vp, c_vp, c_vp, ctypes.c_uint64, c_int, ctypes.c_int64, c_vp]),
     "srk_jpeg_quant_table_host": (c_int, [c_int, c_int, ctypes.POINTER(c_int)]),
     "srk_jpeg_u8_host": (c_int, [c_vp, c_vp, ctypes.POINTER(c_int), c_int, c_int, c_int, c_int, c_int, c_int]),
+    "srk_channel_attention_splits": (c_int, [c_int] * 4),
+    "srk_channel_attention_workspace": (c_size, [c_int] * 4),
+    "srk_channel_attention_forward": (c_int, [c_f] * 6 + [c_int] * 5 + [c_f] * 4 + [c_vp, c_size, c_vp]),
+    "srk_channel_attention_backward": (c_int, [c_f] * 7 + [c_int] * 5 + [c_f] * 5 + [c_float, c_vp, c_size, c_vp]),
+    "srk_channel_attention_host": (c_int, [c_vp] * 7 + [c_int] * 5 + [c_vp] * 6),
 }
 
 _lib = None

@@ -7,6 +7,7 @@ to as few kernel launches as the arithmetic allows:
     ConvBlock / DeconvBlock   conv + bias + activation                     -> 1 launch
     ResnetBlock (no norm)     conv+act, conv + residual add                -> 2 launches
     PSBlock (no norm)         conv + bias + pixel-shuffle store (+ act)    -> 1 launch (+1 in training w/ PReLU)
+    RCAB (RCAN; not in the reference)  conv+act, conv, channel-attention gate + residual add -> 4 launches
 
 With autograd enabled only ReLU / LeakyReLU are fused into the conv (their gradient mask can be
 recovered from the saved output); PReLU / tanh / sigmoid then run as a separate pointwise kernel
@@ -15,8 +16,8 @@ that saves what its backward needs.
 import torch
 
 from . import ops
-from .layers import (ACT_LRELU, ACT_NONE, ACT_PRELU, ACT_RELU, BatchNorm2d, Conv2d, ConvTranspose2d, Linear,
-                     PixelShuffle, _plan_views, grad_mode, make_activation, make_norm1d, make_norm2d)
+from .layers import (ACT_LRELU, ACT_NONE, ACT_PRELU, ACT_RELU, BatchNorm2d, Conv2d, ConvTranspose2d, GateConv2d, Linear,
+                     PixelShuffle, ReLU, Sigmoid, _plan_views, grad_mode, make_activation, make_norm1d, make_norm2d)
 
 _FUSABLE_IN_TRAINING = (ACT_NONE, ACT_RELU, ACT_LRELU)
 
@@ -178,6 +179,61 @@ class ResnetBlock(_Block):
             out = self.act(out)
         out = self.bn(self.conv2.run(out))
         return ops.add(out, residual)
+
+
+class ChannelAttention(torch.nn.Module):
+    """The gate of RCAN (Zhang et al. 2018, eq. 4-5): y = t * sigmoid(W_U relu(W_D mean_hw(t))) [+ residual], with the
+    official module's parameter names: conv_du.0 = W_D [C/r, C, 1, 1], conv_du.2 = W_U [C, C/r, 1, 1].  One fused op
+    (ops.channel_attention), the skip add of the surrounding block included."""
+
+    def __init__(self, num_filter, reduction=16):
+        super(ChannelAttention, self).__init__()
+        if reduction < 1 or num_filter % reduction != 0:
+            raise ValueError("ChannelAttention: %d channels are not divisible by reduction %d" % (num_filter, reduction))
+        self.conv_du = torch.nn.Sequential(GateConv2d(num_filter, num_filter // reduction), ReLU(True),
+                                           GateConv2d(num_filter // reduction, num_filter), Sigmoid())
+
+    def forward(self, t, residual=None, res_box=None):
+        down, up = self.conv_du[0], self.conv_du[2]
+        return ops.channel_attention(t, residual, down.weight, down.bias, up.weight, up.bias, res_box)
+
+
+class RCAB(torch.nn.Module):
+    """Residual channel attention block: x + CA(conv2(relu(conv1(x)))) in three ops -- conv1 with its ReLU fused, conv2,
+    and the gate with the skip add fused.  In training the skip's gradient (= the block output gradient, which the gate's
+    backward hands over untouched) is added by conv1's data-gradient kernel (ops.GradBox), as in ResnetBlock's no-norm
+    path; where the input itself needs no gradient there is no fan-in and the tensor is simply used twice (ops.fork)."""
+
+    def __init__(self, num_filter, reduction=16):
+        super(RCAB, self).__init__()
+        self.conv1 = Conv2d(num_filter, num_filter, 3, 1, 1)
+        self.conv2 = Conv2d(num_filter, num_filter, 3, 1, 1)
+        self.ca = ChannelAttention(num_filter, reduction)
+
+    def forward(self, x):
+        training = grad_mode(x, *self.parameters())
+        box = ops.GradBox() if (training and x.requires_grad and ops.FUSE_SKIP_GRAD) else None
+        residual = x
+        if training and box is None:
+            x, residual = ops.fork(x)
+        out = self.conv1.run(x, ACT_RELU, add_box=box)
+        return self.ca(self.conv2.run(out), residual, res_box=box)
+
+
+class ResidualGroup(torch.nn.Module):
+    """RCAN's residual group: `num_blocks` RCABs, one 3x3 conv, and the group's skip fused into that conv's store."""
+
+    def __init__(self, num_filter, num_blocks, reduction=16):
+        super(ResidualGroup, self).__init__()
+        self.blocks = torch.nn.Sequential(*[RCAB(num_filter, reduction) for _ in range(num_blocks)])
+        self.conv = ConvBlock(num_filter, num_filter, 3, 1, 1, activation=None, norm=None)
+
+    def forward(self, x):
+        if grad_mode(x, *self.parameters()):
+            x, skip = ops.fork(x)   # gradient fan-in summed by srk_axpby
+        else:
+            skip = x
+        return self.conv(self.blocks(x), residual=skip)
 
 
 class PSBlock(_Block):

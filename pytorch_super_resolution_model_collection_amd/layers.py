@@ -106,6 +106,20 @@ class Conv2d(torch.nn.Conv2d):
         return self.run(x)
 
 
+class GateConv2d(torch.nn.Conv2d):
+    """The 1x1 Conv2d of a channel-attention gate (base_networks.ChannelAttention.conv_du): torch's parameter names, shapes
+    and initialisation on a 1x1 map of one value per channel.  Its arithmetic is part of ops.channel_attention, which reads
+    the parameters directly, so it is not a layers.Conv2d: no filter is packed for it (optim.PackPlan), and calling it is
+    an error rather than an ATen convolution."""
+
+    def __init__(self, in_channels, out_channels):
+        super(GateConv2d, self).__init__(in_channels, out_channels, 1, 1, 0, bias=True)
+
+    def forward(self, x):
+        raise RuntimeError("GateConv2d holds the parameters of a channel-attention gate; the gate runs as "
+                           "ops.channel_attention (base_networks.ChannelAttention.forward)")
+
+
 class ConvTranspose2d(torch.nn.ConvTranspose2d):
     """torch.nn.ConvTranspose2d surface (base_networks.py:77; fsrcnn.py:33)."""
 

@@ -14,7 +14,8 @@ import torch.nn as nn
 
 from . import ops, utils
 from ._lib import ACT_NONE, ACT_RELU
-from .base_networks import ConvBlock, DeconvBlock, DenseBlock, PSBlock, ResnetBlock, Upsample2xBlock
+from .base_networks import (ConvBlock, DeconvBlock, DenseBlock, PSBlock, ResidualGroup, ResnetBlock,
+                            Upsample2xBlock)
 from .layers import Conv2d, ConvTranspose2d, PReLU, grad_mode
 
 
@@ -204,6 +205,37 @@ class EDSRNet(nn.Module):
     def forward(self, x):
         out = _trunk_with_skip(self.input_conv(x), self.residual_layers, self.mid_conv, _training_graph(self, x))
         return self.output_conv(self.upscale4x(out))
+
+
+class RCANNet(nn.Module):
+    """RCAN (Zhang et al., ECCV 2018; not in the reference collection): EDSR's BN-free trunk with a channel-attention gate in
+    every block, residual in residual -- `num_groups` groups of `num_blocks` RCABs and a conv under a group skip, a conv
+    under the long skip, log2(scale) 2x pixel-shuffle upsamplers.  No mean shift, as in this package's EDSR."""
+
+    def __init__(self, num_channels, base_filter=64, num_groups=10, num_blocks=20, reduction=16, scale_factor=4):
+        super(RCANNet, self).__init__()
+        if scale_factor not in (2, 4, 8):
+            raise ValueError("RCANNet: scale_factor %r is not 2, 4 or 8" % (scale_factor,))
+        if num_groups < 1 or num_blocks < 1:
+            raise ValueError("RCANNet: num_groups %r and num_blocks %r must be at least 1" % (num_groups, num_blocks))
+        self.input_conv = ConvBlock(num_channels, base_filter, 3, 1, 1, activation=None, norm=None)
+        self.residual_groups = nn.Sequential(*[ResidualGroup(base_filter, num_blocks, reduction)
+                                               for _ in range(num_groups)])
+        self.mid_conv = ConvBlock(base_filter, base_filter, 3, 1, 1, activation=None, norm=None)
+        self.upscale = nn.Sequential(*[Upsample2xBlock(base_filter, base_filter, upsample='ps', activation=None, norm=None)
+                                       for _ in range(int(math.log2(scale_factor)))])
+        self.output_conv = ConvBlock(base_filter, num_channels, 3, 1, 1, activation=None, norm=None)
+        # as in EDSRNet: only convolutions, additions and pixel shuffles lie between these layers and the loss
+        for m in [self.mid_conv.conv, self.output_conv.conv] + [u.upsample.conv for u in self.upscale]:
+            m._linear_tail = True
+
+    def weight_init(self, mean=0.0, std=0.02):
+        for m in self.modules():
+            utils.weights_init_normal(m, mean=mean, std=std)
+
+    def forward(self, x):
+        out = _trunk_with_skip(self.input_conv(x), self.residual_groups, self.mid_conv, _training_graph(self, x))
+        return self.output_conv(self.upscale(out))
 
 
 def get_upsample_filter(size):

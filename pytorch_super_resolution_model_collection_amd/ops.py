@@ -2474,3 +2474,87 @@ def add_scaled_(a, b, beta):
     lib = _lib.load()
     check(lib.srk_axpby(ptr(a), ptr(b), ptr(a), a.numel(), 1.0, float(beta), stream_ptr()), "srk_axpby")
     return a
+
+
+# ------------------------------------------------------------------------------------------------
+# Channel attention (RCAN's gate; csrc/ca.hip)
+# ------------------------------------------------------------------------------------------------
+def _ca_workspace(lib, t):
+    n, c, h, w = t.shape
+    nbytes = int(lib.srk_channel_attention_workspace(n, h, w, c))
+    return torch.empty(max(nbytes, 8), dtype=torch.uint8, device=t.device), nbytes   # torch's allocator: a graph owns it
+
+
+class _ChannelAttention(torch.autograd.Function):
+    """y = t * sigmoid(W2 relu(W1 mean_hw(t) + b1) + b2) (+ x): two launches forward, three backward; saves t, m, h, s."""
+
+    @staticmethod
+    def forward(ctx, t, x, w1, b1, w2, b2, res_box=None):
+        lib = _lib.load()
+        require_cuda(t, x, w1, b1, w2, b2)
+        if t.dim() != 4:
+            raise RuntimeError("channel_attention: expected a 4-D NCHW tensor, got shape %s" % (tuple(t.shape),))
+        n, c, hh, ww = t.shape
+        cr = w1.shape[0]
+        if tuple(w1.shape[:2]) != (cr, c) or w1.numel() != cr * c or tuple(w2.shape[:2]) != (c, cr) \
+                or w2.numel() != c * cr or b1.numel() != cr or b2.numel() != c:
+            raise RuntimeError("channel_attention: weights %s, %s and biases %s, %s do not fit C = %d"
+                               % (tuple(w1.shape), tuple(w2.shape), tuple(b1.shape), tuple(b2.shape), c))
+        if x is not None and x.shape != t.shape:
+            raise RuntimeError("channel_attention: skip %s vs input %s" % (tuple(x.shape), tuple(t.shape)))
+        t = _dense(t)
+        x = _dense(x) if x is not None else None
+        w1c, b1c, w2c, b2c = (p.detach().contiguous() for p in (w1, b1, w2, b2))
+        need_grad = any(ctx.needs_input_grad)
+        y = torch.empty_like(t)
+        m = h = s = None
+        if need_grad:
+            m = torch.empty((n, c), dtype=torch.float32, device=t.device)
+            h = torch.empty((n, cr), dtype=torch.float32, device=t.device)
+            s = torch.empty((n, c), dtype=torch.float32, device=t.device)
+        ws, nbytes = _ca_workspace(lib, t)
+        check(lib.srk_channel_attention_forward(ptr(t), ptr(x), ptr(w1c), ptr(b1c), ptr(w2c), ptr(b2c), n, hh, ww, c, cr,
+                                                ptr(y), ptr(m), ptr(h), ptr(s), ptr(ws), nbytes, stream_ptr()),
+              "srk_channel_attention_forward")
+        ctx.has_skip, ctx.res_box = x is not None, res_box
+        ctx.params = (w1, b1, w2, b2)
+        if need_grad:
+            ctx.save_for_backward(t, m, h, s, w1c, w2c)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        t, m, h, s, w1c, w2c = ctx.saved_tensors
+        w1, b1, w2, b2 = ctx.params
+        n, c, hh, ww = t.shape
+        cr = h.shape[1]
+        g = _dense(g)
+        dt = torch.empty_like(t)
+        need = ctx.needs_input_grad[2:6]
+        acc = [getattr(p, "_srk_grad", None) for p in (w1, b1, w2, b2)]
+        flat = all(a is not None for a in acc)     # optim.FlatParams: accumulate into the flat gradient buffer
+        if flat:
+            outs, beta = [a if nd else None for a, nd in zip(acc, need)], 1.0
+        else:
+            outs, beta = [torch.empty(p.shape, dtype=torch.float32, device=t.device) if nd else None
+                          for p, nd in zip((w1, b1, w2, b2), need)], 0.0
+        ws, nbytes = _ca_workspace(lib, t)
+        check(lib.srk_channel_attention_backward(ptr(g), ptr(t), ptr(w1c), ptr(w2c), ptr(m), ptr(h), ptr(s), n, hh, ww, c,
+                                                 cr, ptr(dt), ptr(outs[0]), ptr(outs[1]), ptr(outs[2]), ptr(outs[3]), beta,
+                                                 ptr(ws), nbytes, stream_ptr()), "srk_channel_attention_backward")
+        dx = g if ctx.has_skip else None      # the skip's gradient is g itself: no kernel
+        if dx is not None and ctx.res_box is not None:
+            ctx.res_box.g, dx = dx, None      # consumed by the block's first conv (GradBox)
+        if flat:
+            outs = [None] * 4
+        return (dt if ctx.needs_input_grad[0] else None, dx) + tuple(outs) + (None,)
+
+
+def channel_attention(t, x, w1, b1, w2, b2, res_box=None):
+    """Channel attention with the skip add fused: y = t * s (+ x), s = sigmoid(W2 relu(W1 m + b1) + b2), m the mean of t
+    over each sample's pixels.  t, x: [N,C,H,W], NCHW-contiguous or channels_last (x may be None); w1 [Cr,C] or
+    [Cr,C,1,1], w2 [C,Cr] or [C,Cr,1,1] (1x1 conv filters), b1 [Cr], b2 [C].  The gradient of x is the gradient of y
+    itself; res_box: the ops.GradBox that takes it instead (base_networks.RCAB).  include/srk.h:
+    srk_channel_attention_forward / _backward."""
+    return _ChannelAttention.apply(t, x, w1, b1, w2, b2, res_box)

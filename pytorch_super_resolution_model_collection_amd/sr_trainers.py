@@ -946,5 +946,26 @@ class DRCN(_Trainer):
         return loaded
 
 
+class RCAN(_Trainer):
+    """RCAN (models.RCANNet; not in the reference collection) behind the common trainer: L1 and Adam as EDSR, EDSR's
+    learning-rate decay, `--rcan_groups` x `--rcan_blocks` RCABs with `--rcan_reduction`.  Its channel attention reads the
+    whole picture, so tiling is refused here (args.tile) and by tiling.net_geometry (test_single(img, tile=...))."""
+    kind = "rcan"
+
+    def __init__(self, args):
+        if getattr(args, "tile", None) is not None:
+            raise ValueError("tile: RCAN's channel attention depends on the whole image and cannot be tiled (main.py --tile)")
+        super(RCAN, self).__init__(args)
+        self.groups = int(getattr(args, "rcan_groups", None) or 10)
+        self.blocks = int(getattr(args, "rcan_blocks", None) or 20)
+        self.reduction = int(getattr(args, "rcan_reduction", None) or 16)
+
+    def build_model(self):
+        return models.RCANNet(self.num_channels, 64, self.groups, self.blocks, self.reduction, self.scale_factor)
+
+    def lr_decay(self, epoch, opt):
+        apply_lr_decay("edsr", epoch, opt)
+
+
 TRAINERS = {"SRCNN": SRCNN, "VDSR": VDSR, "ESPCN": ESPCN, "FSRCNN": FSRCNN, "SRGAN": SRGAN, "LapSRN": LapSRN, "EDSR": EDSR,
-            "DRCN": DRCN}
+            "DRCN": DRCN, "RCAN": RCAN}

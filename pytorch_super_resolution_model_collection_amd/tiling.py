@@ -3,8 +3,9 @@
 Host only, exact integer arithmetic, importable without a GPU.  The device side is csrc/tile.hip (ops.tile_gather /
 tile_stitch / tile_stitch_u8); the trainers drive both from sr_trainers._Trainer._infer_tiled.
 
-All eight nets are convolutional with a bounded receptive field and treat both axes alike, so everything here is
-one-dimensional and applied to rows and columns independently.
+The reference's eight nets are convolutional with a bounded receptive field and treat both axes alike, so everything
+here is one-dimensional and applied to rows and columns independently.  The ninth, RCAN, is not: its channel attention
+pools over the whole picture, the walk says so (as it does for instance norm) and the picture runs in one pass.
 
 Geometry.  Along one axis, a feature map of a net is described against the net's INPUT by three integers (scale, lo, hi):
 map pixel o depends on the input pixels
@@ -175,6 +176,13 @@ def _walk(g, m, path):
         return _union(out, g, path)
     if isinstance(m, B.Upsample2xBlock):
         return _walk(g, m.upsample, path + ".upsample")
+    if isinstance(m, B.ChannelAttention):   # its gate is a function of every pixel of the picture
+        raise ValueError("%s: ChannelAttention depends on the whole image and cannot be tiled" % path)
+    if isinstance(m, B.RCAB):   # x + ca(conv2(relu(conv1(x))))
+        out = _conv(_conv(g, m.conv1, path + ".conv1"), m.conv2, path + ".conv2")
+        return _union(_walk(out, m.ca, path + ".ca"), g, path)
+    if isinstance(m, B.ResidualGroup):
+        return _union(_walk(_walk(g, m.blocks, path + ".blocks"), m.conv, path + ".conv"), g, path)
     if isinstance(m, torch.nn.ConvTranspose2d):
         return _deconv(g, m, path)
     if isinstance(m, torch.nn.Conv2d):
@@ -218,6 +226,11 @@ def net_geometry(model):
         out = _walk(_walk(head, model.residual_layers, "residual_layers"), model.mid_conv, "mid_conv")
         out = _union(out, head, "mid_conv")
         return _walk(_walk(out, model.upscale4x, "upscale4x"), model.output_conv, "output_conv")
+    if isinstance(model, M.RCANNet):   # raises at the first channel attention; the composition is the forward's all the same
+        head = _walk(g, model.input_conv, "input_conv")
+        out = _walk(_walk(head, model.residual_groups, "residual_groups"), model.mid_conv, "mid_conv")
+        out = _union(out, head, "mid_conv")
+        return _walk(_walk(out, model.upscale, "upscale"), model.output_conv, "output_conv")
     if isinstance(model, M.LapSRNNet):
         f1 = _walk(_walk(g, model.input_conv, "input_conv"), model.convt_F1, "convt_F1")
         coarse = _union(_walk(f1, model.convt_R1, "convt_R1"), _walk(g, model.convt_I1, "convt_I1"), "convt_R1")

@@ -500,7 +500,7 @@ class GraphedStep(GraphedSegments):
 
 
 def build(kind, model, lr, dp_group=None, use_dp=False, ssim_weight=0.0, ema_decay=0.0):
-    """(flat, optimizer, dp, step) for one of 'srcnn' | 'fsrcnn' | 'vdsr' | 'edsr' | 'lapsrn' | 'espcn': the one place that
+    """(flat, optimizer, dp, step) for one of 'srcnn' | 'fsrcnn' | 'vdsr' | 'edsr' | 'lapsrn' | 'espcn' | 'rcan': the one place that
     names the loss and the clip a kind trains with.  ssim_weight a in (0, 1]: (1 - a) * that loss + a * (1 - SSIM)
     (mixed_loss); 0: the step as it is without the argument.  ema_decay d in (0, 1): the optimizer keeps the moving average
     of the weights (`opt.ema`); it is updated inside opt.step()'s kernel, so eager steps, segments and graphs all carry it
@@ -512,7 +512,7 @@ def build(kind, model, lr, dp_group=None, use_dp=False, ssim_weight=0.0, ema_dec
     if dp is not None:
         dp.broadcast_params()
         opt.ema_reset()      # (the shadow starts as a copy of the parameters every rank now has)
-    if kind == "edsr":
+    if kind in ("edsr", "rcan"):
         step = l1_step(model, opt, dp, ssim_weight=ssim_weight)
     elif kind == "lapsrn":
         step = lapsrn_step(model, opt, dp, ssim_weight=ssim_weight)
