@@ -710,6 +710,36 @@ int srk_ssim_loss_forward_backward(const float* pred, const float* target, const
                                    void* stream);
 int srk_ssim_loss_host(const float* pred, const float* target, const int64_t* target_strides, int N, int C, int H, int W,
                        double grad_scale, double* loss, double* dpred);
+/* The frequency-domain training loss with its gradient: an L1 on the full 2-D Fourier spectrum of d = pred - target, per
+ * plane (BasicSR's FFTLoss: L1Loss(view_as_real(fft2(pred)), view_as_real(fft2(target)))).  (Added without a change of
+ * srk_version(): new entry points only.)  pred, target [N,C,H,W] fp32, 1 <= H, W <= SRK_FFT_LOSS_MAX_DIM, M = N*C*H*W,
+ * d formed in double from the fp32 values:
+ *   F[n,c,u,v] = s * sum_{y,x} d[n,c,y,x] * exp(-2 pi i (u y / H + v x / W))     s = `scale`: 1 ("backward") or
+ *   loss       = (1 / (2 M)) * sum_{n,c,u,v} (|Re F| + |Im F|)                       1 / sqrt(H W) ("ortho")
+ *   G          = sign(Re F) + i sign(Im F),  sign(0) = 0
+ *   dpred[n,c,y,x] = grad_scale * (s / (2 M)) * Re sum_{u,v} G[n,c,u,v] * exp(+2 pi i (u y / H + v x / W))
+ * No gradient goes to target; a NaN in pred propagates (to the loss and to its own plane's gradient).  The DFT is dense
+ * and fp64 up to the fp32 stores of dpred and *loss.  Its twiddles are DATA from one host function:
+ * srk_dft_table_host(n, cos_sin) fills cos_sin[2k] = cos(2 pi k / n), cos_sin[2k+1] = sin(2 pi k / n), k = 0 .. n-1;
+ * wherever 4k is a multiple of n the entries are exactly 0 and +-1, and entry n - k is the conjugate of entry k to the
+ * bit.  Kernels, host twin and tests all address these values by (u * y) mod n, so for a real d Im F is an exact zero
+ * at the self-conjugate bins (2u = 0 mod H and 2v = 0 mod W) and the sign there is 0.
+ * `tables` (device): the table of H followed by the table of W, 2 * (H + W) doubles.  Conventions of
+ * srk_ssim_loss_forward_backward: pred / dpred NHWC-dense, target through element strides (n,c,h,w) (NULL = NHWC-dense),
+ * dpred may be NULL (loss only), `workspace` of srk_fft_loss_workspace_bytes(N, C, H, W) bytes (contents irrelevant; 0
+ * for dims the call refuses).  No atomics: two calls return the same bits.  H or W beyond SRK_FFT_LOSS_MAX_DIM is
+ * SRK_ERR_UNSUPPORTED; null pointers, non-positive dims and a scale that is not positive and finite are SRK_ERR_BAD_ARG,
+ * all before anything is launched.
+ * srk_fft_loss_host: the same definition in plain C++ double on HOST pointers (full spectrum, no mirror), sharing table
+ * and arithmetic (csrc/fft_loss_common.h) with the kernels; *loss and dpred (NHWC-dense, may be NULL) are doubles. */
+#define SRK_FFT_LOSS_MAX_DIM 256
+int srk_dft_table_host(int n, double* cos_sin);
+size_t srk_fft_loss_workspace_bytes(int N, int C, int H, int W);
+int srk_fft_loss_forward_backward(const float* pred, const float* target, const int64_t* target_strides, int N, int C,
+                                  int H, int W, const double* tables, double scale, float grad_scale, float* loss,
+                                  float* dpred, void* workspace, void* stream);
+int srk_fft_loss_host(const float* pred, const float* target, const int64_t* target_strides, int N, int C, int H, int W,
+                      double scale, double grad_scale, double* loss, double* dpred);
 /* utils.norm / utils.denorm (utils.py:219-239; torchvision Normalize = sub_(mean).div_(std)):
  * y[e] = (x[e] - sub[c]) / div[c], c = (e / inner) % C (inner = H*W for NCHW storage, 1 for NHWC), optionally clamped
  * to [0,1] (denorm's non-VGG branch).  sub_host / div_host are HOST arrays of C <= 8 floats. Bit-equal to torch. */

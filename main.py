@@ -10,7 +10,8 @@ the checkpoint and run test() on the test sets, no training; one line per datase
 and --self_ensemble (--test_single, --test_only and the test() after training run every picture through the x8 geometric
 self-ensemble, "EDSR+": the net on the eight flips / rotations, transformed back and averaged) and --ssim_weight A (train
 on (1 - A) * the model's pixel loss + A * (1 - SSIM), A in [0, 1], default 0; every model but SRGAN and DRCN; the logged
-loss is the mixed one) and --vgg_weights PATH (SRGAN: a torchvision vgg19 state_dict; the logged G loss gains the reference's
+loss is the mixed one) and --fft_weight W (add W * the L1 on the 2-D Fourier spectrum of prediction - target, ops.fft_loss, to that
+loss; W >= 0, default 0; --fft_norm {backward,ortho}; HR patches of at most 256 on a side; not SRGAN and DRCN) and --vgg_weights PATH (SRGAN: a torchvision vgg19 state_dict; the logged G loss gains the reference's
 VGG feature term) with --perceptual (that term trains the generator) and --vgg_loss_weight W (its weight, default 6e-3)
 and --resume [PATH] (continue training from the training-state file a run writes beside its checkpoints at every
 --save_epochs boundary and at its end; without PATH this run's own <save_dir>/model/<model_name>_train_state.pkl) and
@@ -76,6 +77,17 @@ def _non_negative(text):
         v = float('nan')
     if not 0.0 <= v < float('inf'):
         raise argparse.ArgumentTypeError("--vgg_loss_weight takes a number >= 0, got %r" % (text,))
+    return v
+
+
+def _fft_weight(text):
+    """--fft_weight: a finite number >= 0."""
+    try:
+        v = float(text)
+    except ValueError:
+        v = float('nan')
+    if not 0.0 <= v < float('inf'):
+        raise argparse.ArgumentTypeError("--fft_weight takes a number >= 0, got %r" % (text,))
     return v
 
 
@@ -228,6 +240,13 @@ def parse_args(argv=None):
     p.add_argument('--ssim_weight', type=_unit_interval, default=0.0, metavar='A',
                    help='train on (1 - A) * the pixel loss of the model + A * (1 - SSIM) (ops.ssim_loss; LapSRN: both '
                         'levels); A in [0, 1], default 0: the pixel loss alone, as the reference.  Not for SRGAN and DRCN')
+    p.add_argument('--fft_weight', type=_fft_weight, default=0.0, metavar='W',
+                   help='add W * the L1 on the full 2-D Fourier spectrum of prediction - target (ops.fft_loss, BasicSR\'s '
+                        'FFTLoss; LapSRN: both levels) to the training loss; W >= 0, default 0: none.  HR patches of at '
+                        'most 256 on a side.  Not for SRGAN and DRCN')
+    p.add_argument('--fft_norm', choices=('backward', 'ortho'), default='backward',
+                   help='--fft_weight: the transform unscaled ("backward", torch.fft.fft2\'s default) or divided by '
+                        'sqrt(H W) ("ortho")')
     p.add_argument('--vgg_weights', type=str, default=None, metavar='PATH',
                    help='SRGAN: a torchvision vgg19 state_dict file; the G loss then includes the VGG feature term of the '
                         'reference, 6e-3 * MSE of vgg19.features[:9] -- logged only, as there, unless --perceptual')
@@ -303,6 +322,12 @@ def parse_args(argv=None):
     if args.ssim_weight > 0 and args.model_name in ('SRGAN', 'DRCN'):
         p.error('--ssim_weight %g: %s has no SSIM mix (SRGAN trains on an adversarial content term, DRCN through its fused '
                 'recursive-supervision head); use --ssim_weight 0 or another model' % (args.ssim_weight, args.model_name))
+    if args.fft_weight > 0 and args.model_name in ('SRGAN', 'DRCN'):
+        p.error('--fft_weight %g: %s has no frequency-domain term (SRGAN trains on an adversarial content term, DRCN through '
+                'its fused recursive-supervision head); use --fft_weight 0 or another model' % (args.fft_weight, args.model_name))
+    if args.fft_weight > 0 and args.crop_size > 256:
+        p.error('--fft_weight %g: the dense DFT takes HR patches of at most 256 on a side, --crop_size is %d'
+                % (args.fft_weight, args.crop_size))
     return check_args(args)
 
 

@@ -20,6 +20,8 @@ ALGO_AUTO, ALGO_GENERIC, ALGO_MFMA, ALGO_DIRECT, ALGO_MFMA_BF16X3, ALGO_MFMA_BF1
 AMAX_FLOATS = 256   # SRK_AMAX_FLOATS: 16 slots, one per 64-byte line
 LOSS_MSE, LOSS_L1, LOSS_CHARBONNIER, LOSS_BCE = range(4)
 LOSS_SSIM = 4   # no srk_loss kind: ops._Loss routes it to srk_ssim_loss_forward_backward
+LOSS_FFT = 5    # no srk_loss kind either: ops._Loss routes it to srk_fft_loss_forward_backward
+FFT_LOSS_MAX_DIM = 256   # SRK_FFT_LOSS_MAX_DIM
 SSIM_DOMAINS = {"float": 0, "u8": 1, "y8": 2}   # SRK_SSIM_FLOAT / _U8 / _Y8
 ACT_BY_NAME = {None: ACT_NONE, "relu": ACT_RELU, "prelu": ACT_PRELU, "lrelu": ACT_LRELU, "tanh": ACT_TANH,
                "sigmoid": ACT_SIGMOID}
@@ -220,6 +222,12 @@ _PROTOTYPES = {
                                                c_float, c_f, c_f, c_vp, c_vp]),
     "srk_ssim_loss_host": (c_int, [c_vp, c_vp, ctypes.POINTER(ctypes.c_int64), c_int, c_int, c_int, c_int,
                                    ctypes.c_double, ctypes.POINTER(ctypes.c_double), c_vp]),
+    "srk_dft_table_host": (c_int, [c_int, ctypes.POINTER(ctypes.c_double)]),
+    "srk_fft_loss_workspace_bytes": (c_size, [c_int, c_int, c_int, c_int]),
+    "srk_fft_loss_forward_backward": (c_int, [c_f, c_f, ctypes.POINTER(ctypes.c_int64), c_int, c_int, c_int, c_int, c_vp,
+                                              ctypes.c_double, c_float, c_f, c_f, c_vp, c_vp]),
+    "srk_fft_loss_host": (c_int, [c_vp, c_vp, ctypes.POINTER(ctypes.c_int64), c_int, c_int, c_int, c_int, ctypes.c_double,
+                                  ctypes.c_double, ctypes.POINTER(ctypes.c_double), c_vp]),
     "srk_channel_affine": (c_int, [c_f, c_f, c_size, c_int, c_size, ctypes.POINTER(c_float), ctypes.POINTER(c_float),
                                    c_int, c_vp]),
     "srk_upsample_nearest_forward": (c_int, [c_f, c_f, c_int, c_int, c_int, c_int, c_int, c_vp]),

@@ -7,6 +7,7 @@ layout).  Nothing in this file computes on the CPU and nothing falls back to ATe
 """
 import collections
 import ctypes
+import math
 import os
 
 import torch
@@ -1121,6 +1122,12 @@ class _Loss(torch.autograd.Function):
         if kind == _lib.LOSS_SSIM and (pred.dim() != 4 or min(pred.shape[2:]) < 11):
             raise RuntimeError("ssim_loss: takes [N,C,H,W] with planes of at least the 11 x 11 window, got shape %s"
                                % (tuple(pred.shape),))
+        if kind == _lib.LOSS_FFT:
+            if pred.dim() != 4 or min(pred.shape) < 1:
+                raise RuntimeError("fft_loss: takes non-empty [N,C,H,W], got shape %s" % (tuple(pred.shape),))
+            if max(pred.shape[2:]) > _lib.FFT_LOSS_MAX_DIM:
+                raise RuntimeError("fft_loss: planes of %d x %d, the dense DFT takes at most %d on a side"
+                                   % (pred.shape[2], pred.shape[3], _lib.FFT_LOSS_MAX_DIM))
         if pred.dim() == 4:
             pred = _dense(pred)
             n, c, h, w = pred.shape
@@ -1135,13 +1142,22 @@ class _Loss(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=pred.device)
         need_grad = ctx.needs_input_grad[0]
         dpred = torch.empty_like(pred) if need_grad else None
-        ws_bytes = lib.srk_ssim_loss_workspace_bytes() if kind == _lib.LOSS_SSIM else lib.srk_loss_workspace_bytes()
+        if kind == _lib.LOSS_FFT:
+            ws_bytes = lib.srk_fft_loss_workspace_bytes(n, c, h, w)
+            tables = _dft_tables(h, w, pred.device)
+        else:
+            ws_bytes = lib.srk_ssim_loss_workspace_bytes() if kind == _lib.LOSS_SSIM else lib.srk_loss_workspace_bytes()
         ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=pred.device)
         seed = _LOSS_SEED[0]
         ctx.seed_ptr, ctx.seed_value = (seed[1].data_ptr(), seed[0]) if seed is not None else (0, 1.0)
         if kind == _lib.LOSS_SSIM:
             check(lib.srk_ssim_loss_forward_backward(ptr(pred), ptr(target), strides, n, c, h, w, ctx.seed_value, ptr(loss),
                                                      ptr(dpred), ptr(ws), stream_ptr()), "srk_ssim_loss_forward_backward")
+        elif kind == _lib.LOSS_FFT:   # eps carries the norm: 1 = "ortho", 0 = "backward"
+            scale = 1.0 / math.sqrt(float(h) * float(w)) if eps else 1.0
+            check(lib.srk_fft_loss_forward_backward(ptr(pred), ptr(target), strides, n, c, h, w, ptr(tables), scale,
+                                                    ctx.seed_value, ptr(loss), ptr(dpred), ptr(ws), stream_ptr()),
+                  "srk_fft_loss_forward_backward")
         else:
             check(lib.srk_loss_forward_backward(kind, ptr(pred), ptr(target), strides, n, c, h, w, eps, ctx.seed_value,
                                                 ptr(loss), ptr(dpred), ptr(ws), stream_ptr()), "srk_loss_forward_backward")
@@ -1251,6 +1267,42 @@ def ssim_loss(pred, target):
     gradient from one launch, with the contract of the pixel losses (loss_seed, unit seed, loss_sum).
     [N,C,H,W] with H, W >= 11.  include/srk.h: srk_ssim_loss_forward_backward."""
     return _Loss.apply(pred, target, _lib.LOSS_SSIM, 0.0)
+
+
+_DFT_TABLES = {}
+FFT_NORMS = ("backward", "ortho")
+
+
+def _dft_tables(h, w, device):
+    """The twiddle tables of srk_dft_table_host for H then W as one fp64 device tensor, uploaded once per (H, W, device):
+    the device computes no cos / sin of its own.  The first use of a size must come before a graph capture (a warm-up
+    step does it): the upload is a host-to-device copy."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    key = (int(h), int(w), idx)
+    t = _DFT_TABLES.get(key)
+    if t is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("fft_loss: the twiddle tables of %d x %d are not on the device yet; run one step before "
+                               "capturing" % (h, w))
+        lib = _lib.load()
+        host = torch.empty(2 * (int(h) + int(w)), dtype=torch.float64)
+        base = ctypes.cast(host.data_ptr(), ctypes.POINTER(ctypes.c_double))
+        check(lib.srk_dft_table_host(int(h), base), "srk_dft_table_host")
+        check(lib.srk_dft_table_host(int(w), ctypes.cast(host.data_ptr() + 16 * int(h), ctypes.POINTER(ctypes.c_double))),
+              "srk_dft_table_host")
+        t = _DFT_TABLES[key] = host.to(torch.device("cuda", idx))
+    return t
+
+
+def fft_loss(pred, target, norm="backward"):
+    """The frequency-domain loss of BasicSR's FFTLoss, nn.L1Loss()(view_as_real(fft2(pred)), view_as_real(fft2(target)))
+    with fft2's `norm` ("backward": unscaled, "ortho": 1 / sqrt(H W)), over the full spectrum of every plane: a dense
+    fp64 DFT on tables from the host, so the bits do not depend on a library's plan and Im F is an exact zero at the
+    self-conjugate bins.  Loss and gradient from one call, with the contract of the pixel losses (loss_seed, unit seed,
+    loss_sum).  [N,C,H,W] with H, W <= 256.  include/srk.h: srk_fft_loss_forward_backward."""
+    if norm not in FFT_NORMS:
+        raise ValueError("fft_loss: norm %r is not one of %s" % (norm, FFT_NORMS))
+    return _Loss.apply(pred, target, _lib.LOSS_FFT, 1.0 if norm == "ortho" else 0.0)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -119,6 +119,8 @@ class _Trainer(object):
         self.steps_per_epoch = getattr(args, "steps_per_epoch", 8)
         if self.kind in ("srgan", "drcn") and (getattr(args, "ssim_weight", 0.0) or 0.0) > 0:
             raise ValueError("ssim_weight: %s has no SSIM mix (main.py --ssim_weight)" % self.model_name)
+        if self.kind in ("srgan", "drcn") and (getattr(args, "fft_weight", 0.0) or 0.0) > 0:
+            raise ValueError("fft_weight: %s has no frequency-domain term (main.py --fft_weight)" % self.model_name)
         check_perceptual_args(args, self.kind)
         for flag in ("degrade", "degrade_test", "jpeg_quality", "jpeg_test"):
             if getattr(args, flag, None) and getattr(args, "synthetic", False):
@@ -148,7 +150,9 @@ class _Trainer(object):
     def build_step(self):
         """(flat parameters, optimizer, DataParallel or None, eager step function) of the freshly built model."""
         return trainers.build(self.kind, self.model, self.lr, use_dp=self.world > 1,
-                              ssim_weight=getattr(self.args, "ssim_weight", 0.0) or 0.0, ema_decay=self.ema_decay)
+                              ssim_weight=getattr(self.args, "ssim_weight", 0.0) or 0.0, ema_decay=self.ema_decay,
+                              fft_weight=getattr(self.args, "fft_weight", 0.0) or 0.0,
+                              fft_norm=getattr(self.args, "fft_norm", None) or "backward")
 
     # -- training state: save at epoch boundaries, continue with --resume --------------------------------------------
     def _state_name(self):

@@ -125,38 +125,54 @@ def loss_segments(model, opt, loss_fn, dp=None, clip=None):
     return [(fwd_bwd, dp), (update, None)]
 
 
-def mixed_loss(pixel, ssim_weight=0.0):
-    """The loss a kind trains on: `pixel` itself (the same function object) for weight 0, else the mix of Zhao et al.,
-    (1 - a) * pixel(pred, t) + a * (1 - SSIM(pred, t)), added by srk_axpby (ops.loss_sum); on one GPU each loss kernel
-    folds its weight into its gradient (ops.weighted_term), so the mix adds the SSIM launch, the axpby of the two scalars and the
-    axpby of the two gradients to a step, and no ATen node to a captured one."""
-    a = float(ssim_weight)
+def mixed_loss(pixel, ssim_weight=0.0, fft_weight=0.0, fft_norm="backward"):
+    """The loss a kind trains on: `pixel` itself (the same function object) for both weights 0, else
+    [(1 - a) * pixel(pred, t) + a * (1 - SSIM(pred, t))] + w * FFT(pred, t): the mix of Zhao et al. (a = ssim_weight) plus
+    the frequency-domain L1 of ops.fft_loss (w = fft_weight >= 0), added by srk_axpby (ops.loss_sum); on one GPU each loss
+    kernel folds its weight into its gradient (ops.weighted_term), so each extra term adds its loss launches, the axpby of
+    two scalars and the axpby of two gradients to a step, and no ATen node to a captured one.  With w == 0 the result is
+    what it was before the argument existed."""
+    a, w = float(ssim_weight), float(fft_weight)
     if not 0.0 <= a <= 1.0:
         raise ValueError("ssim_weight %r is not in [0, 1]" % (ssim_weight,))
+    if not 0.0 <= w < float("inf"):
+        raise ValueError("fft_weight %r is not a non-negative finite number" % (fft_weight,))
+    if fft_norm not in ops.FFT_NORMS:
+        raise ValueError("fft_norm %r is not one of %s" % (fft_norm, ops.FFT_NORMS))
     if a == 0.0:
-        return pixel
+        base = pixel
+    else:
+        def base(pred, target):
+            p1, p2 = ops.fork(pred)   # the two gradients of pred are added by srk_axpby, not by autograd's ATen add
+            return ops.loss_sum(ops.weighted_term(pixel, 1.0 - a, p1, target), ops.weighted_term(ops.ssim_loss, a, p2, target),
+                                1.0 - a, a)
+    if w == 0.0:
+        return base
+
+    def fft(pred, target):
+        return ops.fft_loss(pred, target, fft_norm)
 
     def loss(pred, target):
-        p1, p2 = ops.fork(pred)   # the two gradients of pred are added by srk_axpby, not by autograd's ATen add
-        return ops.loss_sum(ops.weighted_term(pixel, 1.0 - a, p1, target), ops.weighted_term(ops.ssim_loss, a, p2, target),
-                            1.0 - a, a)
+        p1, p2 = ops.fork(pred)
+        # (base carries weight 1: its terms take their own weights, or the general path, exactly as without the third term)
+        return ops.loss_sum(base(p1, target), ops.weighted_term(fft, w, p2, target), 1.0, w)
     return loss
 
 
-def mse_step(model, opt, dp=None, clip=None, ssim_weight=0.0):
+def mse_step(model, opt, dp=None, clip=None, ssim_weight=0.0, fft_weight=0.0, fft_norm="backward"):
     """srcnn.py:127-131 / fsrcnn.py:153-157 / vdsr.py:143-150 (clip = 0.4)."""
-    return eager_step(loss_segments(model, opt, mixed_loss(ops.mse_loss, ssim_weight), dp, clip))
+    return eager_step(loss_segments(model, opt, mixed_loss(ops.mse_loss, ssim_weight, fft_weight, fft_norm), dp, clip))
 
 
-def l1_step(model, opt, dp=None, ssim_weight=0.0):
+def l1_step(model, opt, dp=None, ssim_weight=0.0, fft_weight=0.0, fft_norm="backward"):
     """edsr.py:151-155"""
-    return eager_step(loss_segments(model, opt, mixed_loss(ops.l1_loss, ssim_weight), dp))
+    return eager_step(loss_segments(model, opt, mixed_loss(ops.l1_loss, ssim_weight, fft_weight, fft_norm), dp))
 
 
-def lapsrn_step(model, opt, dp=None, ssim_weight=0.0):
+def lapsrn_step(model, opt, dp=None, ssim_weight=0.0, fft_weight=0.0, fft_norm="backward"):
     """lapsrn.py:190-199: two Charbonnier losses, two backward calls into the same gradients.  A plain closure without
     segments: it cannot be split at its exchange, so under data parallelism it is never captured."""
-    loss_fn = mixed_loss(ops.charbonnier_loss, ssim_weight)   # the same mix at both levels
+    loss_fn = mixed_loss(ops.charbonnier_loss, ssim_weight, fft_weight, fft_norm)   # the same mix at both levels
 
     def step(inp, target2x, target4x):
         opt.zero_grad()
@@ -499,10 +515,11 @@ class GraphedStep(GraphedSegments):
     seg = property(lambda self: self)   # (the split capture used to be a member of this name: `step.seg.plan` still reads)
 
 
-def build(kind, model, lr, dp_group=None, use_dp=False, ssim_weight=0.0, ema_decay=0.0):
+def build(kind, model, lr, dp_group=None, use_dp=False, ssim_weight=0.0, ema_decay=0.0, fft_weight=0.0, fft_norm="backward"):
     """(flat, optimizer, dp, step) for one of 'srcnn' | 'fsrcnn' | 'vdsr' | 'edsr' | 'lapsrn' | 'espcn' | 'rcan': the one place that
     names the loss and the clip a kind trains with.  ssim_weight a in (0, 1]: (1 - a) * that loss + a * (1 - SSIM)
-    (mixed_loss); 0: the step as it is without the argument.  ema_decay d in (0, 1): the optimizer keeps the moving average
+    (mixed_loss); 0: the step as it is without the argument.  fft_weight w > 0 adds w * ops.fft_loss(pred, target, fft_norm)
+    to that (mixed_loss); 0: the step as it is without the argument.  ema_decay d in (0, 1): the optimizer keeps the moving average
     of the weights (`opt.ema`); it is updated inside opt.step()'s kernel, so eager steps, segments and graphs all carry it
     without a node of its own, and under data parallelism every rank's shadow is the same (same parameters, same kernel)."""
     from .dp import DataParallel
@@ -512,14 +529,15 @@ def build(kind, model, lr, dp_group=None, use_dp=False, ssim_weight=0.0, ema_dec
     if dp is not None:
         dp.broadcast_params()
         opt.ema_reset()      # (the shadow starts as a copy of the parameters every rank now has)
+    fft = dict(fft_weight=fft_weight, fft_norm=fft_norm)
     if kind in ("edsr", "rcan"):
-        step = l1_step(model, opt, dp, ssim_weight=ssim_weight)
+        step = l1_step(model, opt, dp, ssim_weight=ssim_weight, **fft)
     elif kind == "lapsrn":
-        step = lapsrn_step(model, opt, dp, ssim_weight=ssim_weight)
+        step = lapsrn_step(model, opt, dp, ssim_weight=ssim_weight, **fft)
     elif kind == "vdsr":
-        step = mse_step(model, opt, dp, clip=0.4, ssim_weight=ssim_weight)
+        step = mse_step(model, opt, dp, clip=0.4, ssim_weight=ssim_weight, **fft)
     else:
-        step = mse_step(model, opt, dp, ssim_weight=ssim_weight)
+        step = mse_step(model, opt, dp, ssim_weight=ssim_weight, **fft)
     return flat, opt, dp, step
 
 

@@ -69,6 +69,22 @@ class SSIMLoss(torch.nn.Module):
         return ops.ssim_loss(pred, target.to(pred.device))
 
 
+class FFTLoss(torch.nn.Module):
+    """The L1 on the 2-D Fourier spectrum of pred - target as a training loss (ops.fft_loss: BasicSR's FFTLoss on a dense
+    fp64 DFT, loss and gradient from one call); norm "backward" or "ortho" as torch.fft.fft2 names them.  [N,C,H,W] CUDA
+    tensors with planes of at most 256 x 256."""
+
+    def __init__(self, norm="backward"):
+        super(FFTLoss, self).__init__()
+        if norm not in ("backward", "ortho"):
+            raise ValueError("FFTLoss: norm %r is not 'backward' or 'ortho'" % (norm,))
+        self.norm = norm
+
+    def forward(self, pred, target):
+        from . import ops
+        return ops.fft_loss(pred, target.to(pred.device), self.norm)
+
+
 class PerceptualLoss(torch.nn.Module):
     """The VGG feature loss as a training loss (ops.perceptual_loss): MSE of `extractor`'s features of pred and target,
     each normalised with the VGG constants first when `normalize`; the gradient reaches pred only.  [N,3,H,W] CUDA
