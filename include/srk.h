@@ -869,6 +869,43 @@ int srk_channel_attention_host(const float* t, const float* x, const float* w1, 
                                const float* b2, const float* g, int N, int H, int W, int C, int Cr, double* y, double* dt,
                                double* dw1, double* db1, double* dw2, double* db2);
 
+/* ---- LPIPS (Zhang et al. 2018, the VGG variant): the distance of one tapped layer (csrc/lpips.hip, lpips_common.h) ----
+ * (Additive again: new entry points only, srk_version() and everything existing unchanged.)
+ * f0 (the prediction's features), f1 (the target's) and df0 dense NHWC [N][H][W][C]; w [C] the layer's 1 x 1 weights.
+ * Per pixel, the norms over its channels:
+ *   a = ||f0||_2 + 1e-10      b = ||f1||_2 + 1e-10      q[c] = f0[c] / a - f1[c] / b      d = sum_c w[c] q[c]^2
+ * value[n] = the mean of d over the sample's HW pixels; LPIPS[n] = the sum of the L layers' values; the scalar their mean
+ * over n.  The normalised values are subtracted (not the expanded quadratic form): f0 == f1 gives exactly 0 and a zero
+ * gradient.  The gradient goes to f0 only, with r = ||f0||_2:
+ *   dd/df0[k] = 2 w[k] q[k] / a - f0[k] / (a^2 r) * sum_c 2 w[c] q[c] f0[c]      the second term is 0 where r == 0
+ * (its limit, and the subgradient of a vector norm at the origin; a ReLU map has such pixels).
+ * Every feature element is read once (the lanes that share a pixel hold its channels in registers) unless a lane would
+ * hold more than 8 channel groups (C > 2048, or C > 512 on the 4-byte path), when the pixel is read twice.  The per-pixel
+ * sums and the sum over pixels are fp64 in a fixed order, through per-block partials; no atomics: two calls on the same
+ * inputs give the same bits.  Any C, H, W >= 1; 16-byte accesses where C % 4 == 0 and f0, f1, w (and df0) are 16-byte
+ * aligned, else a 4-byte path.  SRK_ERR_BAD_ARG before anything is read: a null pointer, a size <= 0, a row outside the
+ * table.  SRK_ERR_WORKSPACE: fewer than srk_lpips_layer_workspace() bytes.
+ * srk_lpips_layer_workspace: bytes the forward needs (0 for bad sizes); 8-byte aligned, contents undefined.
+ * srk_lpips_layer_blocks: the partial blocks per sample of the 16-byte (vec = 1) or the 4-byte path (a negative status for
+ *   bad sizes).
+ * srk_lpips_layer_forward: two launches; writes row `row` of the fp64 table [L][N]: table[row][n] = value[n].
+ * srk_lpips_finish: one launch; the L rows added in order: values[n] (fp32) and mean, their mean over n (either may be
+ *   NULL), and gvec[n] = seed / N (may be NULL), the per-sample upstream gradients of the scalar with the loss weight
+ *   `seed` folded in -- what the layer backwards take.
+ * srk_lpips_layer_backward: one launch, no workspace; recomputes the norms from f0 and f1 and writes every element of
+ *   df0 = gout[n] / HW * dd/df0 once.  gout fp64 [N] on the device.
+ * srk_lpips_layer_host: the same on host pointers in double throughout, from the very per-pixel bodies the kernels
+ *   compile; value [N]; gout and df0 both NULL: forward only. */
+size_t srk_lpips_layer_workspace(int N, int H, int W, int C);
+int srk_lpips_layer_blocks(int N, int H, int W, int C, int vec);
+int srk_lpips_layer_forward(const float* f0, const float* f1, const float* w, int N, int H, int W, int C, int row, int L,
+                            double* table, void* workspace, size_t workspace_bytes, void* stream);
+int srk_lpips_finish(const double* table, int L, int N, double seed, float* values, float* mean, double* gvec, void* stream);
+int srk_lpips_layer_backward(const float* f0, const float* f1, const float* w, const double* gout, int N, int H, int W, int C,
+                             float* df0, void* stream);
+int srk_lpips_layer_host(const float* f0, const float* f1, const float* w, const double* gout, int N, int H, int W, int C,
+                         double* value, double* df0);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,9 @@ decoded again, on the device, byte for byte as Pillow would) with --jpeg_prob P 
 --jpeg_test Q (every test image's LR input compressed at quality Q, behind --degrade_test where that is given).
 --model_name RCAN (not in the reference: EDSR's trunk with channel attention, models.RCANNet) with --rcan_groups G,
 --rcan_blocks B and --rcan_reduction R (defaults 10, 20, 16); every flag of the common trainer works with it but --tile.
+--lpips_vgg PATH --lpips_lin PATH (a torchvision vgg16 state_dict and the `lpips` package's vgg.pth; both or neither):
+test() also reports LPIPS (ops.lpips, on the device) beside PSNR and SSIM; with them --lpips_weight W adds W * LPIPS to the
+training loss of every model but SRGAN and DRCN.  RGB only (--num_channels 3).
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N main.py ..."""
 import argparse
 import os
@@ -88,6 +91,17 @@ def _fft_weight(text):
         v = float('nan')
     if not 0.0 <= v < float('inf'):
         raise argparse.ArgumentTypeError("--fft_weight takes a number >= 0, got %r" % (text,))
+    return v
+
+
+def _lpips_weight(text):
+    """--lpips_weight: a finite number >= 0."""
+    try:
+        v = float(text)
+    except ValueError:
+        v = float('nan')
+    if not 0.0 <= v < float('inf'):
+        raise argparse.ArgumentTypeError("--lpips_weight takes a number >= 0, got %r" % (text,))
     return v
 
 
@@ -293,7 +307,28 @@ def parse_args(argv=None):
                    help='RCAN: residual channel attention blocks per group (default 20)')
     p.add_argument('--rcan_reduction', type=_positive, default=16, metavar='R',
                    help='RCAN: channel reduction of the attention gate, a divisor of 64 (default 16)')
+    p.add_argument('--lpips_vgg', type=str, default=None, metavar='PATH',
+                   help='a torchvision vgg16 state_dict file; with --lpips_lin, test() also reports LPIPS (Zhang et al. '
+                        '2018, the VGG variant; ops.lpips) beside PSNR and SSIM.  Needs --num_channels 3')
+    p.add_argument('--lpips_lin', type=str, default=None, metavar='PATH',
+                   help='the linear layers of LPIPS: the `lpips` package\'s vgg.pth (lin{l}.model.1.weight); goes with '
+                        '--lpips_vgg')
+    p.add_argument('--lpips_weight', type=_lpips_weight, default=0.0, metavar='W',
+                   help='add W * LPIPS(prediction, target) to the training loss (LapSRN: both levels); W >= 0, default 0: '
+                        'none.  Needs --lpips_vgg and --lpips_lin; HR patches of at least 16 on a side (LapSRN: 32).  Not '
+                        'for SRGAN and DRCN')
     args = p.parse_args(argv)
+    if bool(args.lpips_vgg) != bool(args.lpips_lin):
+        p.error('--lpips_vgg and --lpips_lin come together: LPIPS needs the vgg16 weights and its linear layers')
+    if args.lpips_weight > 0 and not args.lpips_vgg:
+        p.error('--lpips_weight %g needs --lpips_vgg PATH and --lpips_lin PATH' % args.lpips_weight)
+    if args.lpips_vgg and args.num_channels != 3:
+        p.error('--lpips_vgg: LPIPS reads RGB, use --num_channels 3 (got %d; scoring the restored-colour picture of a Y '
+                'model is not supported)' % args.num_channels)
+    if args.lpips_weight > 0 and args.model_name in ('SRGAN', 'DRCN'):
+        p.error('--lpips_weight %g: %s has no LPIPS term (SRGAN trains on an adversarial content term, DRCN through its '
+                'fused recursive-supervision head); use --lpips_weight 0 or another model'
+                % (args.lpips_weight, args.model_name))
     if args.model_name == 'RCAN' and args.tile is not None:
         p.error('--tile: RCAN\'s channel attention depends on the whole image, its pictures run in one pass (drop --tile)')
     if args.model_name == 'RCAN' and 64 % args.rcan_reduction:
@@ -349,9 +384,14 @@ def report(net, args):
         return
     for name, v in net.test_psnr.items():
         parts = ['%s PSNR %.4f SSIM %.4f' % (args.model_name, v, net.test_ssim.get(name, float('nan')))]
+        lp = getattr(net, 'test_lpips', None) if getattr(args, 'lpips_vgg', None) else None
+        if lp is not None:
+            parts[0] += ' LPIPS %.4f' % lp.get(name, float('nan'))
         if args.save_test_images and name in net.test_bicubic_psnr:
             parts.insert(0, 'bicubic PSNR %.4f SSIM %.4f' % (net.test_bicubic_psnr[name],
                                                             net.test_bicubic_ssim.get(name, float('nan'))))
+            if lp is not None:
+                parts[0] += ' LPIPS %.4f' % getattr(net, 'test_bicubic_lpips', {}).get(name, float('nan'))
         ev = getattr(net, 'test_eval', {}).get(name)
         if ev:
             parts.append('%s shave %d: PSNR %.4f SSIM %.4f' % (ev['domain'], ev['shave'], ev['psnr'], ev['ssim']))

@@ -3,7 +3,7 @@ LapSRN / SRGAN / DRCN / RCAN on the shared base_networks blocks), drop-in for th
 togheppi/pytorch-super-resolution-model-collection.  See DESIGN.md."""
 from . import _lib, ops, layers, base_networks, utils, models, optim, dp, trainers, data  # noqa: F401
 from .models import (SRCNNNet, ESPCNNet, FSRCNNNet, VDSRNet, EDSRNet, LapSRNNet, SRGANGenerator,  # noqa: F401
-                     SRGANDiscriminator, FeatureExtractor, DRCNNet, RCANNet)
+                     SRGANDiscriminator, FeatureExtractor, DRCNNet, RCANNet, LPIPS)
 
 __all__ = ["ops", "layers", "base_networks", "utils", "models", "SRCNNNet", "ESPCNNet", "FSRCNNNet", "VDSRNet",
-           "EDSRNet", "LapSRNNet", "SRGANGenerator", "SRGANDiscriminator", "FeatureExtractor", "DRCNNet", "RCANNet"]
+           "EDSRNet", "LapSRNNet", "SRGANGenerator", "SRGANDiscriminator", "FeatureExtractor", "DRCNNet", "RCANNet", "LPIPS"]

@@ -251,6 +251,12 @@ _PROTOTYPES = {
     "srk_channel_attention_forward": (c_int, [c_f] * 6 + [c_int] * 5 + [c_f] * 4 + [c_vp, c_size, c_vp]),
     "srk_channel_attention_backward": (c_int, [c_f] * 7 + [c_int] * 5 + [c_f] * 5 + [c_float, c_vp, c_size, c_vp]),
     "srk_channel_attention_host": (c_int, [c_vp] * 7 + [c_int] * 5 + [c_vp] * 6),
+    "srk_lpips_layer_workspace": (c_size, [c_int] * 4),
+    "srk_lpips_layer_blocks": (c_int, [c_int] * 5),
+    "srk_lpips_layer_forward": (c_int, [c_f] * 3 + [c_int] * 6 + [c_vp, c_vp, c_size, c_vp]),
+    "srk_lpips_finish": (c_int, [c_vp, c_int, c_int, ctypes.c_double, c_f, c_f, c_vp, c_vp]),
+    "srk_lpips_layer_backward": (c_int, [c_f] * 3 + [c_vp] + [c_int] * 4 + [c_f, c_vp]),
+    "srk_lpips_layer_host": (c_int, [c_vp] * 4 + [c_int] * 4 + [c_vp] * 2),
 }
 
 _lib = None

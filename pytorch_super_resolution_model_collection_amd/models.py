@@ -430,23 +430,141 @@ class FeatureExtractor(nn.Module):
         return self._walk(x, True)
 
     def _walk(self, out, grad):
-        mods = list(self.features)
-        i = 0
-        while i < len(mods):
-            m = mods[i]
-            if isinstance(m, nn.Conv2d):
-                fused = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
-                act = ACT_RELU if fused else ACT_NONE
-                if grad:
-                    out = ops.conv2d(out, m.weight, m.bias, None, ops.ConvCfg(m._s, m._p, False, 0, act),
-                                     m._cache.get(m.weight, m.bias, False, 0, bwd=True))
-                else:
-                    out = m.run(out, act)   # conv + bias + ReLU in one kernel
-                i += 2 if fused else 1
-            elif isinstance(m, _MaxPool2x2) and grad:
-                out = ops.max_pool2x2_train(out)
-                i += 1
+        return _vgg_walk(list(self.features), out, grad)
+
+
+def _vgg_modules(cfg):
+    """torchvision's `features` of a VGG configuration (numbers = conv3x3 output channels, 'M' = MaxPool2d(2,2)) as this
+    package's modules, under torchvision's indices, with torchvision's initialisation."""
+    from .layers import Conv2d, ReLU
+    mods, cin = [], 3
+    for v in cfg:
+        if v == 'M':
+            mods.append(_MaxPool2x2())
+        else:
+            conv = Conv2d(cin, v, 3, 1, 1)
+            nn.init.kaiming_normal_(conv.weight, mode='fan_out', nonlinearity='relu')
+            conv.bias.data.zero_()
+            mods += [conv, ReLU(True)]
+            cin = v
+    return mods
+
+
+def _freeze_vgg(module):
+    """No parameter of a VGG head trains, and its convs are in no optimizer: their packs outlive optimizer steps
+    (layers._PackCache)."""
+    for p in module.parameters():
+        p.requires_grad_(False)
+    for m in module.features:
+        if isinstance(m, nn.Conv2d):
+            m._cache.frozen = True
+
+
+def _load_vgg_features(module, state_dict, what):
+    """Copy `features.N.weight/bias` of a torchvision VGG state_dict (or a path to its .pth file) for the layers `module`
+    keeps; every other entry is ignored, a missing one is a KeyError."""
+    if isinstance(state_dict, str):
+        state_dict = torch.load(state_dict, map_location="cpu")
+    own = [k for k in module.state_dict() if k.startswith("features.")]
+    missing = [k for k in own if k not in state_dict]
+    if missing:
+        raise KeyError("%s state_dict lacks %s" % (what, missing))
+    module.load_state_dict({k: state_dict[k] for k in own}, strict=False)
+    from .layers import bump_weight_epoch
+    bump_weight_epoch()
+    for m in module.features:
+        if isinstance(m, nn.Conv2d):
+            m._cache.drop()
+    return module
+
+
+def _vgg_walk(mods, out, grad, taps=None):
+    """The walk through a VGG head given as its module list: conv + ReLU as one fused kernel each, the pools in between
+    (FeatureExtractor.extract says what `grad` chooses).  taps=None: returns the last map.  taps = module indices:
+    returns the list of the maps that leave those modules (a fused ReLU's index for a conv + ReLU pair); where autograd
+    records, a tapped map that the walk goes on from is forked (ops.fork: it feeds its consumer here and the next layer
+    there, and the two gradients are added by srk_axpby)."""
+    got = []
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        if isinstance(m, nn.Conv2d):
+            fused = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+            act = ACT_RELU if fused else ACT_NONE
+            if grad:
+                out = ops.conv2d(out, m.weight, m.bias, None, ops.ConvCfg(m._s, m._p, False, 0, act),
+                                 m._cache.get(m.weight, m.bias, False, 0, bwd=True))
             else:
-                out = m(out)
-                i += 1
-        return out
+                out = m.run(out, act)   # conv + bias + ReLU in one kernel
+            i += 2 if fused else 1
+        elif isinstance(m, _MaxPool2x2) and grad:
+            out = ops.max_pool2x2_train(out)
+            i += 1
+        else:
+            out = m(out)
+            i += 1
+        if taps is not None and i - 1 in taps:
+            if i < len(mods) and ops.grad_enabled_for(out):
+                keep, out = ops.fork(out)
+            else:
+                keep = out
+            got.append(keep)
+    return out if taps is None else got
+
+
+class LPIPS(nn.Module):
+    """The net of LPIPS (Zhang et al. 2018), VGG variant: torchvision's vgg16.features up to index 29 (the fifth pool is
+    not run), tapped behind ReLU 1_2, 2_2, 3_3, 4_3 and 5_3 (indices 3, 8, 15, 22, 29; 64, 128, 256, 512, 512 channels),
+    and the five non-negative 1 x 1 weight vectors `lins`.  `features` keeps torchvision's indices, so a vgg16
+    checkpoint's `features.N.weight/bias` load directly (`load_vgg16`); `load_lins` takes the `lpips` package's vgg.pth
+    (`lin{l}.model.1.weight`, each [1, C_l, 1, 1]).  Until loaded: torchvision's initialisation and lins of 1 / C_l.
+    Every parameter is frozen.  forward(x) / extract(x): the five maps of an already scaled input; ops.lpips(pred,
+    target, net) is the metric and the loss."""
+
+    VGG16_CFG = (64, 64, 'M', 128, 128, 'M', 256, 256, 256, 'M', 512, 512, 512, 'M', 512, 512, 512)
+    TAPS = (3, 8, 15, 22, 29)
+    WIDTHS = (64, 128, 256, 512, 512)
+
+    def __init__(self, vgg16=None, lins=None):
+        super(LPIPS, self).__init__()
+        self.features = nn.Sequential(*_vgg_modules(self.VGG16_CFG))
+        self.lins = nn.ParameterList([nn.Parameter(torch.full((c,), 1.0 / c)) for c in self.WIDTHS])
+        _freeze_vgg(self)
+        if vgg16 is not None:
+            self.load_vgg16(vgg16.state_dict() if hasattr(vgg16, "state_dict") else vgg16)
+        if lins is not None:
+            self.load_lins(lins)
+
+    def load_vgg16(self, state_dict):
+        """Copy `features.N.weight/bias` of a torchvision vgg16 state_dict (or a path to its .pth file); classifier
+        entries are ignored, a missing layer is a KeyError."""
+        return _load_vgg_features(self, state_dict, "vgg16")
+
+    def load_lins(self, state_dict):
+        """Copy the five weight vectors from the `lpips` package's vgg.pth state_dict (or a path to it): exactly the keys
+        `lin{l}.model.1.weight`, l = 0..4, each with C_l elements; a missing one is a KeyError."""
+        if isinstance(state_dict, str):
+            state_dict = torch.load(state_dict, map_location="cpu")
+        keys = ["lin%d.model.1.weight" % l for l in range(len(self.WIDTHS))]
+        missing = [k for k in keys if k not in state_dict]
+        if missing:
+            raise KeyError("lpips state_dict lacks %s" % missing)
+        for k, c, p in zip(keys, self.WIDTHS, self.lins):
+            v = state_dict[k]
+            if v.numel() != c:
+                raise ValueError("lpips state_dict: %s has %d elements, the tap has %d channels" % (k, v.numel(), c))
+            p.data.copy_(v.detach().reshape(-1).to(p.dtype))
+        return self
+
+    def forward(self, x):
+        return self.extract(x, grad=False)
+
+    def extract(self, x, grad=False):
+        """The five tapped maps of x (already shifted and scaled: ops.lpips_input_affine), as FeatureExtractor.extract:
+        grad=False on the detached input, without a graph, on the inference kernels; grad=True the training forward,
+        differentiable in x where autograd records."""
+        mods = list(self.features)
+        if not grad:
+            with torch.no_grad():
+                return _vgg_walk(mods, x.detach(), False, self.TAPS)
+        return _vgg_walk(mods, x, True, self.TAPS)

@@ -2610,3 +2610,137 @@ def channel_attention(t, x, w1, b1, w2, b2, res_box=None):
     itself; res_box: the ops.GradBox that takes it instead (base_networks.RCAB).  include/srk.h:
     srk_channel_attention_forward / _backward."""
     return _ChannelAttention.apply(t, x, w1, b1, w2, b2, res_box)
+
+
+# ------------------------------------------------------------------------------------------------
+# LPIPS (Zhang et al. 2018, the VGG variant; csrc/lpips.hip, DESIGN.md 27)
+# ------------------------------------------------------------------------------------------------
+def _nhwc(x):
+    return to_nhwc(x if (_is_nchw_dense(x) or _is_nhwc_dense(x)) else x.contiguous())
+
+
+class _LpipsLayer(torch.autograd.Function):
+    """One tapped layer's distance: writes table[row][n] = mean_hw sum_c w[c] (f0[c] / a - f1[c] / b)^2 (two launches)
+    and returns that row; the backward (one launch) recomputes the norms from the two saved maps.  Gradient: f_pred only."""
+
+    @staticmethod
+    def forward(ctx, f_pred, f_target, w, row, table):
+        lib = _lib.load()
+        require_cuda(f_pred, f_target, w)
+        if f_pred.dim() != 4 or f_pred.shape != f_target.shape:
+            raise RuntimeError("lpips_layer: feature maps %s and %s must be equal 4-D NCHW shapes"
+                               % (tuple(f_pred.shape), tuple(f_target.shape)))
+        n, c, h, ww = f_pred.shape
+        if w.numel() != c:
+            raise RuntimeError("lpips_layer: %d weights for %d channels" % (w.numel(), c))
+        if (table.dtype != torch.float64 or not table.is_cuda or table.dim() != 2 or table.shape[1] != n
+                or not table.is_contiguous()):
+            raise RuntimeError("lpips_layer: table must be a contiguous float64 [L, %d] device tensor, got %s %s"
+                               % (n, table.dtype, tuple(table.shape)))
+        row = int(row)
+        if not 0 <= row < table.shape[0]:
+            raise RuntimeError("lpips_layer: row %d of a table of %d rows" % (row, table.shape[0]))
+        f0 = _nhwc(f_pred)
+        f1 = f0 if f_target is f_pred else _nhwc(f_target.detach())
+        wc = w.detach().reshape(-1).contiguous()
+        nbytes = int(lib.srk_lpips_layer_workspace(n, h, ww, c))
+        ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=f0.device)   # torch's allocator: a graph owns it
+        check(lib.srk_lpips_layer_forward(ptr(f0), ptr(f1), ptr(wc), n, h, ww, c, row, table.shape[0], ptr(table), ptr(ws),
+                                          nbytes, stream_ptr()), "srk_lpips_layer_forward")
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(f0, f1, wc)
+        return table[row]
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        f0, f1, wc = ctx.saved_tensors
+        n, c, h, ww = f0.shape
+        g = g.to(torch.float64).contiguous()   # (what _LpipsFinish hands out already is both)
+        df0 = _empty_cl(n, c, h, ww, f0)
+        check(lib.srk_lpips_layer_backward(ptr(f0), ptr(f1), ptr(wc), ptr(g), n, h, ww, c, ptr(df0), stream_ptr()),
+              "srk_lpips_layer_backward")
+        return df0, None, None, None, None
+
+
+def lpips_layer(f_pred, f_target, w, row, table):
+    """The LPIPS distance of one tapped layer, fused: per pixel both maps are normalised over their channels, subtracted,
+    squared and weighed by w [C], and the mean over the sample's pixels goes to table[row] (`table`: float64 [L, N] on the
+    device, written in place by the kernels; the returned [N] tensor is that row, a view -- nothing else may write the
+    table in place before the backward has run).  f_pred, f_target: [N,C,H,W], NCHW-contiguous or
+    channels_last.  The gradient goes to f_pred only: d(row[n]) / d f_pred times the [N] float64 gradient of the row.
+    include/srk.h: srk_lpips_layer_forward / _backward."""
+    return _LpipsLayer.apply(f_pred, f_target, w, row, table)
+
+
+class _LpipsFinish(torch.autograd.Function):
+    """The L rows of the table added in order (one launch): the per-sample values [N], or their mean under the contract of
+    the losses (loss_seed, unit seed, weighted_term, loss_sum) -- the same launch writes seed / N for every sample, the
+    gradient of each row, so a backward seeded as declared runs no arithmetic of its own.  `rows`: what lpips_layer
+    returned, one per row (they tie the layers into the graph)."""
+
+    @staticmethod
+    def forward(ctx, table, reduce, *rows):
+        lib = _lib.load()
+        nl, n = table.shape
+        need = any(ctx.needs_input_grad[2:])
+        seed = _LOSS_SEED[0] if reduce else None
+        ctx.seed_ptr, ctx.seed_value = (seed[1].data_ptr(), seed[0]) if seed is not None else (0, 1.0)
+        out = torch.empty(n if not reduce else (), dtype=torch.float32, device=table.device)
+        gvec = torch.empty(n, dtype=torch.float64, device=table.device) if (need and reduce) else None
+        check(lib.srk_lpips_finish(ptr(table), nl, n, ctx.seed_value, None if reduce else ptr(out), ptr(out) if reduce else None,
+                                   ptr(gvec), stream_ptr()), "srk_lpips_finish")
+        ctx.reduce, ctx.gvec, ctx.k, ctx.need = reduce, gvec, len(rows), need
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.need:
+            return (None,) * (2 + ctx.k)
+        if not ctx.reduce:
+            gv = g.to(torch.float64).contiguous()       # the per-sample gradients as they come
+        else:
+            gp = g.data_ptr()
+            declared = ctx.seed_ptr if ctx.seed_ptr else unit_seed(g.device).data_ptr()
+            if gp == declared:                           # the seed this loss was computed for: already in gvec
+                gv = ctx.gvec
+            else:                                        # some other upstream gradient: gvec = seed / N
+                gv = ctx.gvec * (g.to(torch.float64) / ctx.seed_value)
+        return (None, None) + (gv,) * ctx.k
+
+
+LPIPS_SHIFT, LPIPS_SCALE = (-.030, -.088, -.188), (.458, .448, .450)
+
+
+def lpips_input_affine(normalize=True):
+    """(sub, div) of the one channel_affine call in front of the LPIPS net: (x - shift) / scale on inputs in [-1, 1], or
+    with `normalize` ((2 x - 1) - shift) / scale = (x - (1 + shift) / 2) / (scale / 2) on inputs in [0, 1]."""
+    if normalize:
+        return tuple((1.0 + s) / 2.0 for s in LPIPS_SHIFT), tuple(s / 2.0 for s in LPIPS_SCALE)
+    return LPIPS_SHIFT, LPIPS_SCALE
+
+
+def lpips(pred, target, net, normalize=True, reduce=True):
+    """LPIPS (Zhang et al. 2018, the VGG variant) of pred against target: the five tapped VGG16 maps of both, each pair
+    through lpips_layer, the five values added.  reduce=True: the mean over the batch as a 0-dim fp32 device tensor with
+    the contract of the other losses (loss_seed, unit seed, weighted_term, loss_sum); reduce=False: the per-sample
+    values [N].  normalize: the inputs are in [0, 1] (True) or already in [-1, 1] (False).  The gradient flows to pred
+    only; both operands run the same kernels (the target's without a graph), so equal inputs give exactly 0 and a zero
+    gradient.  pred / target: [N, 3, H, W] on the device with H, W >= 16; net: models.LPIPS."""
+    for name, t in (("pred", pred), ("target", target)):
+        if not torch.is_tensor(t) or t.dim() != 4 or t.shape[1] != 3:
+            raise ValueError("lpips: %s must be [N, 3, H, W] (LPIPS reads RGB), got shape %s"
+                             % (name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+    if pred.shape != target.shape:
+        raise ValueError("lpips: pred %s vs target %s" % (tuple(pred.shape), tuple(target.shape)))
+    if min(pred.shape[2:]) < 16:
+        raise ValueError("lpips: pictures of %d x %d, the five taps need at least 16 on a side" % tuple(pred.shape[2:]))
+    if not (pred.is_cuda and target.is_cuda):
+        raise ValueError("lpips: pred (%s) and target (%s) must be on the device" % (pred.device, target.device))
+    sub, div = lpips_input_affine(normalize)
+    with torch.no_grad():
+        real = net.extract(channel_affine(target.detach(), sub, div), grad=True)
+    fake = net.extract(channel_affine(pred, sub, div), grad=True)
+    table = torch.empty((len(fake), pred.shape[0]), dtype=torch.float64, device=pred.device)
+    rows = [lpips_layer(a, b, w, l, table) for l, (a, b, w) in enumerate(zip(fake, real, net.lins))]
+    return _LpipsFinish.apply(table, bool(reduce), *rows)

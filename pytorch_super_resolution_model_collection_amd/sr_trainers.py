@@ -79,6 +79,24 @@ def check_perceptual_args(args, kind):
                          % ("perceptual" if perceptual else "vgg_weights"))
 
 
+def check_lpips_args(args, kind):
+    """--lpips_vgg / --lpips_lin / --lpips_weight of main.py: the two weight files come together, LPIPS reads RGB, and the
+    training term belongs to the kinds trainers.mixed_loss serves.  Raises ValueError naming the flag."""
+    vgg, lin = getattr(args, "lpips_vgg", None), getattr(args, "lpips_lin", None)
+    weight = getattr(args, "lpips_weight", None) or 0.0
+    if not 0.0 <= float(weight) < float("inf"):
+        raise ValueError("lpips_weight %r must be a finite number >= 0 (main.py --lpips_weight)" % (weight,))
+    if bool(vgg) != bool(lin):
+        raise ValueError("%s: LPIPS needs both weight files (main.py --lpips_vgg PATH --lpips_lin PATH)"
+                         % ("lpips_lin" if vgg else "lpips_vgg"))
+    if weight > 0 and not vgg:
+        raise ValueError("lpips_weight: needs the weights of the LPIPS net (main.py --lpips_vgg PATH --lpips_lin PATH)")
+    if weight > 0 and kind in ("srgan", "drcn"):
+        raise ValueError("lpips_weight: %s has no LPIPS term (main.py --lpips_weight)" % kind.upper())
+    if vgg and getattr(args, "num_channels", 3) != 3:
+        raise ValueError("lpips_vgg: LPIPS reads RGB (main.py --num_channels 3)")
+
+
 # -- the training-state file (<save_dir>/model/<model_name>_train_state.pkl) ---------------------------------------------
 # Everything a run needs to continue at an epoch boundary as if it had not stopped; plain containers, numbers, strings
 # and CPU tensors only, so it loads with torch.load(weights_only=True).  The weights-only checkpoint files beside it are
@@ -122,6 +140,7 @@ class _Trainer(object):
         if self.kind in ("srgan", "drcn") and (getattr(args, "fft_weight", 0.0) or 0.0) > 0:
             raise ValueError("fft_weight: %s has no frequency-domain term (main.py --fft_weight)" % self.model_name)
         check_perceptual_args(args, self.kind)
+        check_lpips_args(args, self.kind)
         for flag in ("degrade", "degrade_test", "jpeg_quality", "jpeg_test"):
             if getattr(args, flag, None) and getattr(args, "synthetic", False):
                 raise ValueError("%s: synthetic patches are not degraded, train and test on image folders (main.py "
@@ -152,7 +171,16 @@ class _Trainer(object):
         return trainers.build(self.kind, self.model, self.lr, use_dp=self.world > 1,
                               ssim_weight=getattr(self.args, "ssim_weight", 0.0) or 0.0, ema_decay=self.ema_decay,
                               fft_weight=getattr(self.args, "fft_weight", 0.0) or 0.0,
-                              fft_norm=getattr(self.args, "fft_norm", None) or "backward")
+                              fft_norm=getattr(self.args, "fft_norm", None) or "backward",
+                              lpips_weight=getattr(self.args, "lpips_weight", 0.0) or 0.0, lpips_net=self.lpips_net())
+
+    def lpips_net(self):
+        """models.LPIPS with the weights of --lpips_vgg / --lpips_lin on this trainer's device, built once; None without
+        the two files."""
+        if getattr(self, "_lpips", None) is None and getattr(self.args, "lpips_vgg", None):
+            net = models.LPIPS().load_vgg16(self.args.lpips_vgg).load_lins(self.args.lpips_lin)
+            self._lpips = net.to(self.device).eval()
+        return getattr(self, "_lpips", None)
 
     # -- training state: save at epoch boundaries, continue with --resume --------------------------------------------
     def _state_name(self):
@@ -497,7 +525,10 @@ class _Trainer(object):
         eval_domain / eval_shave (None: args.eval_domain / args.eval_shave where the args object has them): when either
         is given, `self.test_eval[name] = {'domain', 'shave', 'psnr', 'ssim'}` holds the averages of ops.ssim's fused
         outputs in that domain ('float', 'u8': the 8-bit picture, 'y8': its luma) with that border left out -- the
-        protocol of published tables.  The returned list and test_psnr do not depend on either."""
+        protocol of published tables.  The returned list and test_psnr do not depend on either.
+        With the LPIPS weights (args.lpips_vgg / args.lpips_lin) `self.test_lpips` holds the per-dataset averages of
+        ops.lpips of the same two float tensors PSNR sees (unshaved, unclamped; a pair under 16 on a side is left out), and
+        with save_images `self.test_bicubic_lpips` the bicubic image's."""
         if self.model is None:
             self.model = self.build_model().to(self.device)
             self.load_model()
@@ -522,13 +553,25 @@ class _Trainer(object):
             if not sources:
                 sources.append(("synthetic", synthetic_loader(self.kind, self.args, 2, self.device, 4321)))
         psnrs, self.test_psnr, self.test_ssim = [], {}, {}
+        lpips_net = self.lpips_net()
+        if lpips_net is not None:
+            self.test_lpips = {}
+
+        def lpips_of(a, b):   # 0-dim device tensor, or None for a pair the five taps do not fit
+            if lpips_net is None or min(int(a.shape[-2]), int(a.shape[-1])) < 16:
+                return None
+            with torch.no_grad():
+                return ops.lpips(a.float(), b.float(), lpips_net, normalize=True, reduce=True)
         if save_images:
             self.test_bicubic_psnr, self.test_bicubic_ssim = {}, {}
+            if lpips_net is not None:
+                self.test_bicubic_lpips = {}
         if want_eval:
             self.test_eval = {}
         for name, batches in sources:
             mine, mine_ssim, mine_eval = [], [], []
             bicubic, bicubic_ssim, img_num = [], [], 0
+            mine_lpips, bicubic_lpips = [], []
             for batch in batches:
                 items = [batch] if torch.is_tensor(batch[0]) else list(zip(*batch))   # ragged test images come as lists
                 for item in items:
@@ -541,6 +584,7 @@ class _Trainer(object):
                         mine.append(utils.PSNR(out, tgt))   # 0-dim device tensors: nothing syncs inside the loop
                         if fits(out):
                             mine_ssim.append(utils.SSIM(out, tgt))
+                        mine_lpips.append(lpips_of(out, tgt))
                         if want_eval and fits(out, eval_shave):
                             mine_eval.append(torch.stack(ops.ssim(out.float(), tgt.float(), eval_shave, eval_domain)[:2]))
                     if save_images:
@@ -552,6 +596,7 @@ class _Trainer(object):
                                 bicubic.append(utils.PSNR(bc_img.to(self.device), hr_img.to(self.device)))
                                 if fits(bc_img):
                                     bicubic_ssim.append(utils.SSIM(bc_img.to(self.device), hr_img.to(self.device)))
+                                bicubic_lpips.append(lpips_of(bc_img.to(self.device), hr_img.to(self.device)))
             vals = [float(v) for v in torch.stack(mine).cpu()] if mine else []
             if vals:
                 self.test_psnr[name] = sum(vals) / len(vals)
@@ -559,7 +604,10 @@ class _Trainer(object):
             if bicubic:
                 bvals = [float(v) for v in torch.stack(bicubic).cpu()]
                 self.test_bicubic_psnr[name] = sum(bvals) / len(bvals)
-            for vals_dev, into in ((mine_ssim, self.test_ssim), (bicubic_ssim, getattr(self, 'test_bicubic_ssim', None))):
+            mine_lpips, bicubic_lpips = ([v for v in vals if v is not None] for vals in (mine_lpips, bicubic_lpips))
+            for vals_dev, into in ((mine_ssim, self.test_ssim), (bicubic_ssim, getattr(self, 'test_bicubic_ssim', None)),
+                                   (mine_lpips, getattr(self, 'test_lpips', None)),
+                                   (bicubic_lpips, getattr(self, 'test_bicubic_lpips', None))):
                 if vals_dev:
                     svals = [float(v) for v in torch.stack(vals_dev).cpu()]
                     into[name] = sum(svals) / len(svals)

@@ -125,14 +125,31 @@ def loss_segments(model, opt, loss_fn, dp=None, clip=None):
     return [(fwd_bwd, dp), (update, None)]
 
 
-def mixed_loss(pixel, ssim_weight=0.0, fft_weight=0.0, fft_norm="backward"):
+def mixed_loss(pixel, ssim_weight=0.0, fft_weight=0.0, fft_norm="backward", lpips_weight=0.0, lpips_net=None):
     """The loss a kind trains on: `pixel` itself (the same function object) for both weights 0, else
     [(1 - a) * pixel(pred, t) + a * (1 - SSIM(pred, t))] + w * FFT(pred, t): the mix of Zhao et al. (a = ssim_weight) plus
     the frequency-domain L1 of ops.fft_loss (w = fft_weight >= 0), added by srk_axpby (ops.loss_sum); on one GPU each loss
     kernel folds its weight into its gradient (ops.weighted_term), so each extra term adds its loss launches, the axpby of
     two scalars and the axpby of two gradients to a step, and no ATen node to a captured one.  With w == 0 the result is
-    what it was before the argument existed."""
-    a, w = float(ssim_weight), float(fft_weight)
+    what it was before the argument existed.  lpips_weight v > 0 adds v * ops.lpips(pred, t, lpips_net) (models.LPIPS; the
+    batches of every kind are in [0, 1], so normalize=True) as one more such stage; with v == 0 the result is the object
+    it was before that argument existed."""
+    a, w, v = float(ssim_weight), float(fft_weight), float(lpips_weight)
+    if not 0.0 <= v < float("inf"):
+        raise ValueError("lpips_weight %r is not a non-negative finite number" % (lpips_weight,))
+    if v > 0.0 and lpips_net is None:
+        raise ValueError("lpips_weight %r needs an lpips_net (models.LPIPS with its weights loaded)" % (lpips_weight,))
+    if v > 0.0:
+        inner = mixed_loss(pixel, ssim_weight, fft_weight, fft_norm)
+
+        def perceptual(pred, target):
+            return ops.lpips(pred, target, lpips_net, normalize=True)
+
+        def with_lpips(pred, target):
+            p1, p2 = ops.fork(pred)
+            # (inner carries weight 1: its terms take their own weights, exactly as without this term)
+            return ops.loss_sum(inner(p1, target), ops.weighted_term(perceptual, v, p2, target), 1.0, v)
+        return with_lpips
     if not 0.0 <= a <= 1.0:
         raise ValueError("ssim_weight %r is not in [0, 1]" % (ssim_weight,))
     if not 0.0 <= w < float("inf"):
@@ -159,20 +176,25 @@ def mixed_loss(pixel, ssim_weight=0.0, fft_weight=0.0, fft_norm="backward"):
     return loss
 
 
-def mse_step(model, opt, dp=None, clip=None, ssim_weight=0.0, fft_weight=0.0, fft_norm="backward"):
+def mse_step(model, opt, dp=None, clip=None, ssim_weight=0.0, fft_weight=0.0, fft_norm="backward", lpips_weight=0.0,
+             lpips_net=None):
     """srcnn.py:127-131 / fsrcnn.py:153-157 / vdsr.py:143-150 (clip = 0.4)."""
-    return eager_step(loss_segments(model, opt, mixed_loss(ops.mse_loss, ssim_weight, fft_weight, fft_norm), dp, clip))
+    return eager_step(loss_segments(model, opt, mixed_loss(ops.mse_loss, ssim_weight, fft_weight, fft_norm, lpips_weight,
+                                                      lpips_net), dp, clip))
 
 
-def l1_step(model, opt, dp=None, ssim_weight=0.0, fft_weight=0.0, fft_norm="backward"):
+def l1_step(model, opt, dp=None, ssim_weight=0.0, fft_weight=0.0, fft_norm="backward", lpips_weight=0.0,
+            lpips_net=None):
     """edsr.py:151-155"""
-    return eager_step(loss_segments(model, opt, mixed_loss(ops.l1_loss, ssim_weight, fft_weight, fft_norm), dp))
+    return eager_step(loss_segments(model, opt, mixed_loss(ops.l1_loss, ssim_weight, fft_weight, fft_norm, lpips_weight,
+                                                      lpips_net), dp))
 
 
-def lapsrn_step(model, opt, dp=None, ssim_weight=0.0, fft_weight=0.0, fft_norm="backward"):
+def lapsrn_step(model, opt, dp=None, ssim_weight=0.0, fft_weight=0.0, fft_norm="backward", lpips_weight=0.0,
+                lpips_net=None):
     """lapsrn.py:190-199: two Charbonnier losses, two backward calls into the same gradients.  A plain closure without
     segments: it cannot be split at its exchange, so under data parallelism it is never captured."""
-    loss_fn = mixed_loss(ops.charbonnier_loss, ssim_weight, fft_weight, fft_norm)   # the same mix at both levels
+    loss_fn = mixed_loss(ops.charbonnier_loss, ssim_weight, fft_weight, fft_norm, lpips_weight, lpips_net)   # both levels
 
     def step(inp, target2x, target4x):
         opt.zero_grad()
@@ -515,21 +537,27 @@ class GraphedStep(GraphedSegments):
     seg = property(lambda self: self)   # (the split capture used to be a member of this name: `step.seg.plan` still reads)
 
 
-def build(kind, model, lr, dp_group=None, use_dp=False, ssim_weight=0.0, ema_decay=0.0, fft_weight=0.0, fft_norm="backward"):
+def build(kind, model, lr, dp_group=None, use_dp=False, ssim_weight=0.0, ema_decay=0.0, fft_weight=0.0, fft_norm="backward",
+          lpips_weight=0.0, lpips_net=None):
     """(flat, optimizer, dp, step) for one of 'srcnn' | 'fsrcnn' | 'vdsr' | 'edsr' | 'lapsrn' | 'espcn' | 'rcan': the one place that
     names the loss and the clip a kind trains with.  ssim_weight a in (0, 1]: (1 - a) * that loss + a * (1 - SSIM)
     (mixed_loss); 0: the step as it is without the argument.  fft_weight w > 0 adds w * ops.fft_loss(pred, target, fft_norm)
-    to that (mixed_loss); 0: the step as it is without the argument.  ema_decay d in (0, 1): the optimizer keeps the moving average
+    to that (mixed_loss); 0: the step as it is without the argument.  lpips_weight v > 0 adds v * ops.lpips(pred, target,
+    lpips_net) (mixed_loss; RGB models only, refused for 'srgan' and 'drcn'); 0: the step as it is without the argument.
+    ema_decay d in (0, 1): the optimizer keeps the moving average
     of the weights (`opt.ema`); it is updated inside opt.step()'s kernel, so eager steps, segments and graphs all carry it
     without a node of its own, and under data parallelism every rank's shadow is the same (same parameters, same kernel)."""
     from .dp import DataParallel
+    if float(lpips_weight) > 0.0 and kind in ("srgan", "drcn"):
+        raise ValueError("lpips_weight %r: %s has no LPIPS term (SRGAN trains on an adversarial content term, DRCN through "
+                         "its fused recursive-supervision head)" % (lpips_weight, kind))
     flat = FlatParams(model)
     opt = make_optimizer(kind, flat, lr, ema_decay=ema_decay)
     dp = DataParallel(flat, dp_group) if use_dp else None
     if dp is not None:
         dp.broadcast_params()
         opt.ema_reset()      # (the shadow starts as a copy of the parameters every rank now has)
-    fft = dict(fft_weight=fft_weight, fft_norm=fft_norm)
+    fft = dict(fft_weight=fft_weight, fft_norm=fft_norm, lpips_weight=lpips_weight, lpips_net=lpips_net)
     if kind in ("edsr", "rcan"):
         step = l1_step(model, opt, dp, ssim_weight=ssim_weight, **fft)
     elif kind == "lapsrn":

@@ -85,6 +85,36 @@ class FFTLoss(torch.nn.Module):
         return ops.fft_loss(pred, target.to(pred.device), self.norm)
 
 
+class LPIPS(torch.nn.Module):
+    """LPIPS (ops.lpips: Zhang et al. 2018, the VGG variant) as a metric: forward(pred, target) returns the per-sample
+    values [N] on the device, without a graph.  [N,3,H,W] tensors with H, W >= 16, in [0, 1] when `normalize`, else in
+    [-1, 1]; net: models.LPIPS (held as a sub-module, its parameters stay frozen)."""
+
+    def __init__(self, net, normalize=True):
+        super(LPIPS, self).__init__()
+        self.net = net
+        self.normalize = bool(normalize)
+
+    def forward(self, pred, target):
+        from . import ops
+        with torch.no_grad():
+            return ops.lpips(pred.detach(), target.to(pred.device), self.net, self.normalize, reduce=False)
+
+
+class LPIPSLoss(torch.nn.Module):
+    """LPIPS as a training loss (ops.lpips, reduce=True): the mean over the batch, a 0-dim device tensor with the contract
+    of the other losses; the gradient reaches pred only.  Arguments as utils.LPIPS."""
+
+    def __init__(self, net, normalize=True):
+        super(LPIPSLoss, self).__init__()
+        self.net = net
+        self.normalize = bool(normalize)
+
+    def forward(self, pred, target):
+        from . import ops
+        return ops.lpips(pred, target.to(pred.device), self.net, self.normalize, reduce=True)
+
+
 class PerceptualLoss(torch.nn.Module):
     """The VGG feature loss as a training loss (ops.perceptual_loss): MSE of `extractor`'s features of pred and target,
     each normalised with the VGG constants first when `normalize`; the gradient reaches pred only.  [N,3,H,W] CUDA
