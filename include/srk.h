@@ -906,6 +906,70 @@ int srk_lpips_layer_backward(const float* f0, const float* f1, const float* w, c
 int srk_lpips_layer_host(const float* f0, const float* f1, const float* w, const double* gout, int N, int H, int W, int C,
                          double* value, double* df0);
 
+/* ---- Convolution over channel slices: dense connectivity without a concatenation (csrc/dense.hip, dense_common.h) ----
+ * (Additive again: new entry points and one new struct, srk_version() and everything existing unchanged.)
+ * A stride-1 "same" convolution, K in {1, 3}, pad (K - 1) / 2, NHWC fp32, whose input channels are the concatenation
+ * [A | B] of up to two SLICES and whose Cout results go to a slice.  A slice is a pointer to its first channel of pixel 0
+ * plus the pixel stride `ld` of the buffer it lives in, in floats (ld >= its channels): pixel p = (n * H + h) * W + w of the
+ * slice starts at ptr + p * ld.  CB == 0: one source (B and ldB are ignored).  W is [Cout][CA + CB][K][K] in torch's order,
+ * its input channels in the order of torch.cat((A, B), 1); it is read as it is, there is no packed form.
+ *   forward          y = act(conv([A | B]; W) + bias) (+ residual)       act: SRK_ACT_NONE / _RELU / _LRELU (slope)
+ *   backward_data    g = dy * act'(y_saved);  dA = betaA * dA + (conv^T(g))[:CA] (+ add);  dB = betaB * dB + (conv^T(g))[CA:]
+ *   backward_weight  dW = beta * dW + sum_p [A | B]^T g;  db = beta * db + sum_p g
+ * y / y_saved share ldY, dy has ldDy, residual ldR, dA / dB ldDA / ldDB, add ldAdd.  y_saved is read only where act is not
+ * SRK_ACT_NONE (it may be NULL otherwise).  dA or dB may be NULL: that part is not computed.  Each beta is 0 (the
+ * destination may hold anything, NaN included: it is not read) or 1.  Slices of one buffer may be read and written by
+ * the same call as long as their channels are disjoint (dy and dB are both slices of the growth-gradient buffer).
+ * Only the slices' own channels are ever read or written.
+ * Arithmetic: v_mfma_f32_16x16x32_bf16 on the exact operand splits of bf16_frag.h, fp32 accumulation; terms = 3 (x = h + m,
+ * products hh + hm + mh: the SRK_ALGO_MFMA_BF16X3 class, ~5e-6) or 6 (x = h + m + l, six products: the fp32-faithful
+ * SRK_ALGO_MFMA_BF16X6 class).  The weight gradient's sum over N * H * W is split into srk_dense_plan.splits pixel ranges
+ * whose partials a second launch adds in index order: no atomics, two calls give the same bits.
+ * Supported: CA, CB, Cout multiples of SRK_DENSE_CHANNEL_MULTIPLE, Cout <= SRK_DENSE_MAX_COUT, every ld a multiple of 4 and
+ * every pointer 16-byte aligned; anything else is SRK_ERR_UNSUPPORTED and the message names the number.  SRK_ERR_BAD_ARG:
+ * a null pointer, a size <= 0, terms not 3 or 6, another activation, a beta that is not 0 or 1.
+ * srk_dense_conv_supported: 1 / 0 for the descriptor alone (strides and sizes; pointers are checked by the calls).
+ * srk_dense_conv_plan: what the planner decided (a negative status for a refused descriptor).
+ * srk_dense_conv_workspace_bytes: bytes backward_weight needs (0 for a refused descriptor); contents undefined.
+ * srk_dense_conv_forward / _backward_data: one launch.  srk_dense_conv_backward_weight: two.
+ * srk_dense_conv_host: the same three directions (direction 0 / 1 / 2) as plain loops on host pointers with fp64
+ *   accumulation, through the same addressing and the same betas; the arguments a direction does not use may be NULL. */
+#define SRK_DENSE_CHANNEL_MULTIPLE 16
+#define SRK_DENSE_MAX_COUT 64
+typedef struct srk_dense_desc {
+  int32_t N, H, W;
+  int32_t K;                 /* 1 or 3 */
+  int32_t CA, CB, Cout;
+  int32_t ldA, ldB, ldY;     /* pixel strides, in floats: sources, and the destination slice (= the saved output's) */
+  int32_t ldR;               /* residual (forward) */
+  int32_t ldDy, ldDA, ldDB;  /* output gradient, and the two source gradients */
+  int32_t ldAdd;             /* the slice added into dA */
+  int32_t act;               /* SRK_ACT_NONE / SRK_ACT_RELU / SRK_ACT_LRELU */
+  float slope;               /* SRK_ACT_LRELU */
+  int32_t terms;             /* 3 or 6 */
+} srk_dense_desc;
+typedef struct srk_dense_plan {
+  uint32_t struct_size;      /* sizeof(srk_dense_plan) of the caller */
+  int32_t pix_tiles;         /* 16-pixel tiles a wave of the forward / data-gradient kernel owns */
+  int32_t splits;            /* pixel ranges of the weight gradient */
+  int64_t split_pixels;      /* pixels per range */
+  uint64_t ws_bytes;         /* = srk_dense_conv_workspace_bytes */
+  uint64_t partial_floats;   /* floats one range's partials take: Cout * (CA + CB) * K * K + Cout */
+} srk_dense_plan;
+int srk_dense_conv_supported(const srk_dense_desc* d);
+int srk_dense_conv_plan(const srk_dense_desc* d, srk_dense_plan* plan);
+size_t srk_dense_conv_workspace_bytes(const srk_dense_desc* d);
+int srk_dense_conv_forward(const srk_dense_desc* d, const float* A, const float* B, const float* W, const float* bias,
+                           const float* residual, float* y, void* stream);
+int srk_dense_conv_backward_data(const srk_dense_desc* d, const float* dy, const float* y_saved, const float* W, float* dA,
+                                 float betaA, float* dB, float betaB, const float* add, void* stream);
+int srk_dense_conv_backward_weight(const srk_dense_desc* d, const float* A, const float* B, const float* dy,
+                                   const float* y_saved, float* dW, float* db, float beta, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+int srk_dense_conv_host(const srk_dense_desc* d, int direction, const float* A, const float* B, const float* W,
+                        const float* bias, const float* residual, float* y, const float* dy, const float* add, float* dA,
+                        float betaA, float* dB, float betaB, float* dW, float* db, float beta);
+
 #ifdef __cplusplus
 }
 #endif

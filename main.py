@@ -28,6 +28,9 @@ decoded again, on the device, byte for byte as Pillow would) with --jpeg_prob P 
 --lpips_vgg PATH --lpips_lin PATH (a torchvision vgg16 state_dict and the `lpips` package's vgg.pth; both or neither):
 test() also reports LPIPS (ops.lpips, on the device) beside PSNR and SSIM; with them --lpips_weight W adds W * LPIPS to the
 training loss of every model but SRGAN and DRCN.  RGB only (--num_channels 3).
+--model_name RDN (not in the reference: residual dense blocks on concat-free slice convolutions, models.RDNNet) with
+--rdn_blocks D, --rdn_layers C and --rdn_growth G (defaults 16, 8, 64: the paper's net); every flag of the common trainer
+works with it, --tile included.
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N main.py ..."""
 import argparse
 import os
@@ -202,7 +205,7 @@ def _jpeg_prob(text):
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="MI355X-native SR collection (reference-compatible CLI)")
     p.add_argument('--model_name', type=str, default='SRGAN',
-                   choices=['SRCNN', 'VDSR', 'ESPCN', 'FSRCNN', 'SRGAN', 'LapSRN', 'EDSR', 'DRCN', 'RCAN'],
+                   choices=['SRCNN', 'VDSR', 'ESPCN', 'FSRCNN', 'SRGAN', 'LapSRN', 'EDSR', 'DRCN', 'RCAN', 'RDN'],
                    help='The type of model')
     p.add_argument('--data_dir', type=str, default='../Data')
     p.add_argument('--train_dataset', type=_names, default=['DIV2K'], help='The name(s) of the training dataset, comma-separated')
@@ -317,7 +320,16 @@ def parse_args(argv=None):
                    help='add W * LPIPS(prediction, target) to the training loss (LapSRN: both levels); W >= 0, default 0: '
                         'none.  Needs --lpips_vgg and --lpips_lin; HR patches of at least 16 on a side (LapSRN: 32).  Not '
                         'for SRGAN and DRCN')
+    p.add_argument('--rdn_blocks', type=_positive, default=16, metavar='D', help='RDN: residual dense blocks (default 16)')
+    p.add_argument('--rdn_layers', type=_positive, default=8, metavar='C',
+                   help='RDN: convolutions per residual dense block (default 8)')
+    p.add_argument('--rdn_growth', type=_positive, default=64, metavar='G',
+                   help='RDN: growth rate, channels every layer adds: 16, 32, 48 or 64 (default 64)')
     args = p.parse_args(argv)
+    if args.model_name == 'RDN' and (args.rdn_growth % 16 or args.rdn_growth > 64):
+        p.error('--rdn_growth %d: RDN\'s slice convolutions write 16, 32, 48 or 64 channels' % args.rdn_growth)
+    if args.model_name == 'RDN' and args.scale_factor not in (2, 3, 4):
+        p.error('--scale_factor %d: RDN upsamples by 2, 3 or 4' % args.scale_factor)
     if bool(args.lpips_vgg) != bool(args.lpips_lin):
         p.error('--lpips_vgg and --lpips_lin come together: LPIPS needs the vgg16 weights and its linear layers')
     if args.lpips_weight > 0 and not args.lpips_vgg:

@@ -77,6 +77,19 @@ class WgradPlan(_Sized):
                 + [("slab_bytes", ctypes.c_uint64), ("ws_bytes", ctypes.c_uint64), ("name", ctypes.c_char * 64)])
 
 
+class DenseDesc(ctypes.Structure):
+    """struct srk_dense_desc: a convolution over channel slices (csrc/dense.hip)"""
+    _fields_ = ([(n, ctypes.c_int32) for n in ("N", "H", "W", "K", "CA", "CB", "Cout", "ldA", "ldB", "ldY", "ldR", "ldDy",
+                                               "ldDA", "ldDB", "ldAdd", "act")]
+                + [("slope", c_float), ("terms", ctypes.c_int32)])
+
+
+class DensePlan(_Sized):
+    """struct srk_dense_plan (srk_dense_conv_plan)"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("pix_tiles", ctypes.c_int32), ("splits", ctypes.c_int32),
+                ("split_pixels", ctypes.c_int64), ("ws_bytes", ctypes.c_uint64), ("partial_floats", ctypes.c_uint64)]
+
+
 class PhaseAxis(_Sized):
     """struct srk_phase_axis (srk_trans_phase_axis)"""
     _fields_ = [("struct_size", ctypes.c_uint32)] + [(n, ctypes.c_int32) for n in ("o0", "P", "Kv", "i0", "w0", "wd")]
@@ -257,6 +270,14 @@ _PROTOTYPES = {
     "srk_lpips_finish": (c_int, [c_vp, c_int, c_int, ctypes.c_double, c_f, c_f, c_vp, c_vp]),
     "srk_lpips_layer_backward": (c_int, [c_f] * 3 + [c_vp] + [c_int] * 4 + [c_f, c_vp]),
     "srk_lpips_layer_host": (c_int, [c_vp] * 4 + [c_int] * 4 + [c_vp] * 2),
+    "srk_dense_conv_supported": (c_int, [ctypes.POINTER(DenseDesc)]),
+    "srk_dense_conv_plan": (c_int, [ctypes.POINTER(DenseDesc), ctypes.POINTER(DensePlan)]),
+    "srk_dense_conv_workspace_bytes": (c_size, [ctypes.POINTER(DenseDesc)]),
+    "srk_dense_conv_forward": (c_int, [ctypes.POINTER(DenseDesc)] + [c_f] * 6 + [c_vp]),
+    "srk_dense_conv_backward_data": (c_int, [ctypes.POINTER(DenseDesc)] + [c_f] * 4 + [c_float, c_f, c_float, c_f, c_vp]),
+    "srk_dense_conv_backward_weight": (c_int, [ctypes.POINTER(DenseDesc)] + [c_f] * 6 + [c_float, c_vp, c_size, c_vp]),
+    "srk_dense_conv_host": (c_int, [ctypes.POINTER(DenseDesc), c_int] + [c_vp] * 9 + [c_float, c_vp, c_float, c_vp, c_vp,
+                                                                                     c_float]),
 }
 
 _lib = None

@@ -8,6 +8,7 @@ to as few kernel launches as the arithmetic allows:
     ResnetBlock (no norm)     conv+act, conv + residual add                -> 2 launches
     PSBlock (no norm)         conv + bias + pixel-shuffle store (+ act)    -> 1 launch (+1 in training w/ PReLU)
     RCAB (RCAN; not in the reference)  conv+act, conv, channel-attention gate + residual add -> 4 launches
+    RDB (RDN; not in the reference)    C convs + ReLU on channel slices, 1x1 fusion + skip    -> C + 1 launches, no cat
 
 With autograd enabled only ReLU / LeakyReLU are fused into the conv (their gradient mask can be
 recovered from the saved output); PReLU / tanh / sigmoid then run as a separate pointwise kernel
@@ -17,7 +18,7 @@ import torch
 
 from . import ops
 from .layers import (ACT_LRELU, ACT_NONE, ACT_PRELU, ACT_RELU, BatchNorm2d, Conv2d, ConvTranspose2d, GateConv2d, Linear,
-                     PixelShuffle, ReLU, Sigmoid, _plan_views, grad_mode, make_activation, make_norm1d, make_norm2d)
+                     PixelShuffle, ReLU, Sigmoid, SliceConv2d, _plan_views, grad_mode, make_activation, make_norm1d, make_norm2d)
 
 _FUSABLE_IN_TRAINING = (ACT_NONE, ACT_RELU, ACT_LRELU)
 
@@ -234,6 +235,49 @@ class ResidualGroup(torch.nn.Module):
         else:
             skip = x
         return self.conv(self.blocks(x), residual=skip)
+
+
+class RDB(torch.nn.Module):
+    """Residual dense block of RDN (Zhang et al., CVPR 2018): C 3x3 convs with ReLU, layer c reading the concatenation of
+    the block input and the c - 1 outputs before it, a 1x1 local fusion over all of them, and the block's skip.  (The name
+    DenseBlock is the reference's Linear block.)  Parameter names as in the official net: convs.{c}.conv.0.{weight,bias},
+    LFF.{weight,bias}.  Nothing is concatenated: ops.residual_dense_blocks runs every conv on channel slices of one
+    growth buffer (C + 1 launches); models.RDNNet hands all its blocks to one call, this forward runs a block alone."""
+
+    def __init__(self, G0, G, C):
+        super(RDB, self).__init__()
+        for name, v in (("G0", G0), ("G", G)):
+            if v < 16 or v % 16:
+                raise ValueError("RDB: %s = %r is not a positive multiple of 16 (the slice convolutions' channel tile)"
+                                 % (name, v))
+        if G > 64 or G0 > 64:
+            raise ValueError("RDB: G = %r, G0 = %r: a slice convolution writes at most 64 channels" % (G, G0))
+        if C < 1:
+            raise ValueError("RDB: C = %r layers, at least 1" % (C,))
+        self.G0, self.G, self.C = G0, G, C
+        self.convs = torch.nn.Sequential(*[_RDBConv(G0 + c * G, G) for c in range(C)])
+        self.LFF = SliceConv2d(G0 + C * G, G0, 1)
+
+    def block_params(self):
+        """(w_1, b_1, ..., w_C, b_C, w_lff, b_lff) as ops.residual_dense_blocks takes a block."""
+        out = []
+        for m in self.convs:
+            out += [m.conv[0].weight, m.conv[0].bias]
+        return tuple(out) + (self.LFF.weight, self.LFF.bias)
+
+    def forward(self, x):
+        return ops.residual_dense_blocks(x, [self.block_params()])
+
+
+class _RDBConv(torch.nn.Module):
+    """One growth layer of an RDB; `conv` = Sequential(conv 3x3, ReLU) as in the official net, hence the key conv.0."""
+
+    def __init__(self, in_channels, G):
+        super(_RDBConv, self).__init__()
+        self.conv = torch.nn.Sequential(SliceConv2d(in_channels, G, 3), ReLU())
+
+    def forward(self, x):
+        raise RuntimeError("an RDB layer runs inside ops.residual_dense_blocks (base_networks.RDB.forward)")
 
 
 class PSBlock(_Block):

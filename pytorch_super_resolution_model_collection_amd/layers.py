@@ -120,6 +120,20 @@ class GateConv2d(torch.nn.Conv2d):
                            "ops.channel_attention (base_networks.ChannelAttention.forward)")
 
 
+class SliceConv2d(torch.nn.Conv2d):
+    """A convolution of a residual dense block (base_networks.RDB): torch's parameter names, shapes and initialisation.  It
+    reads and writes channel slices of the block's buffers inside ops.residual_dense_blocks, which takes the parameters
+    directly and in torch's order, so -- like GateConv2d -- it is not a layers.Conv2d: nothing is packed for it
+    (optim.PackPlan), and calling it is an error rather than an ATen convolution on a concatenation."""
+
+    def __init__(self, in_channels, out_channels, kernel_size):
+        super(SliceConv2d, self).__init__(in_channels, out_channels, kernel_size, 1, (kernel_size - 1) // 2, bias=True)
+
+    def forward(self, x):
+        raise RuntimeError("SliceConv2d holds the parameters of a residual dense block; the block runs as "
+                           "ops.residual_dense_blocks (base_networks.RDB.forward)")
+
+
 class ConvTranspose2d(torch.nn.ConvTranspose2d):
     """torch.nn.ConvTranspose2d surface (base_networks.py:77; fsrcnn.py:33)."""
 

@@ -14,9 +14,9 @@ import torch.nn as nn
 
 from . import ops, utils
 from ._lib import ACT_NONE, ACT_RELU
-from .base_networks import (ConvBlock, DeconvBlock, DenseBlock, PSBlock, ResidualGroup, ResnetBlock,
+from .base_networks import (RDB, ConvBlock, DeconvBlock, DenseBlock, PSBlock, ResidualGroup, ResnetBlock,
                             Upsample2xBlock)
-from .layers import Conv2d, ConvTranspose2d, PReLU, grad_mode
+from .layers import Conv2d, ConvTranspose2d, PixelShuffle, PReLU, grad_mode
 
 
 def _training_graph(module, x):
@@ -236,6 +236,55 @@ class RCANNet(nn.Module):
     def forward(self, x):
         out = _trunk_with_skip(self.input_conv(x), self.residual_groups, self.mid_conv, _training_graph(self, x))
         return self.output_conv(self.upscale(out))
+
+
+class RDNNet(nn.Module):
+    """RDN (Zhang et al., CVPR 2018; not in the reference collection): two shallow-feature convs, D residual dense blocks
+    whose outputs are all fused by a 1x1 and a 3x3 conv (GFF) under the SFENet1 skip, a pixel-shuffle upsampler.  Module
+    names as in the official net (SFENet1, SFENet2, RDBs, GFF, UPNet).  The D blocks run as ONE op on channel slices
+    (ops.residual_dense_blocks): its result is the buffer GFF reads, no concatenation exists anywhere in the net."""
+
+    def __init__(self, num_channels, G0=64, D=16, C=8, G=64, scale_factor=4):
+        super(RDNNet, self).__init__()
+        if scale_factor not in (2, 3, 4):
+            raise ValueError("RDNNet: scale_factor %r is not 2, 3 or 4" % (scale_factor,))
+        if D < 1:
+            raise ValueError("RDNNet: D = %r blocks, at least 1" % (D,))
+        self.scale_factor = scale_factor
+        self.SFENet1 = Conv2d(num_channels, G0, 3, 1, 1)
+        self.SFENet2 = Conv2d(G0, G0, 3, 1, 1)
+        self.RDBs = nn.ModuleList([RDB(G0, G, C) for _ in range(D)])    # (RDB raises for the G0, G and C it refuses)
+        self.GFF = nn.Sequential(Conv2d(D * G0, G0, 1, 1, 0), Conv2d(G0, G0, 3, 1, 1))
+        if scale_factor == 4:
+            up = [Conv2d(G0, G * 4, 3, 1, 1), PixelShuffle(2), Conv2d(G, G * 4, 3, 1, 1), PixelShuffle(2)]
+        else:
+            r = scale_factor
+            up = [Conv2d(G0, G * r * r, 3, 1, 1), PixelShuffle(r)]
+        self.UPNet = nn.Sequential(*(up + [Conv2d(G, num_channels, 3, 1, 1)]))
+        for conv, nxt in zip(self.UPNet, list(self.UPNet)[1:] + [None]):
+            if isinstance(nxt, PixelShuffle):
+                conv._ps_r = int(nxt.upscale_factor)      # the shuffle is fused into this conv's store (optim.PackPlan packs for it)
+        # only convolutions, additions and pixel shuffles lie between these layers and the loss (as in EDSRNet)
+        for m in list(self.GFF) + [m for m in self.UPNet if isinstance(m, Conv2d)]:
+            m._linear_tail = True
+
+    def weight_init(self, mean=0.0, std=0.02):
+        for m in self.modules():
+            utils.weights_init_normal(m, mean=mean, std=std)
+
+    def forward(self, x):
+        training = _training_graph(self, x)
+        f1 = self.SFENet1(x)
+        if training:
+            f1, skip = ops.fork(f1)   # gradient fan-in summed by srk_axpby
+        else:
+            skip = f1
+        fusion = ops.residual_dense_blocks(self.SFENet2(f1), [b.block_params() for b in self.RDBs])
+        out = self.GFF[1].run(self.GFF[0](fusion), residual=skip)
+        for m in self.UPNet:
+            if isinstance(m, Conv2d):
+                out = m.run(out, ps_r=getattr(m, "_ps_r", 0))
+        return out
 
 
 def get_upsample_filter(size):

@@ -1100,7 +1100,8 @@ def backward(losses, seed=None):
 
 class loss_seed(object):
     """Context: losses computed inside store their gradient already multiplied by `value`; a backward pass seeded with
-    `tensor` (which must hold `value`) then uses it as is."""
+    `tensor` (which must hold `value`) then uses it as is.  The seed is recognised by its address; every loss node
+    computed inside keeps `tensor` alive until its graph is freed, so no other gradient can come to live at that address."""
 
     def __init__(self, value, tensor):
         self.seed = (float(value), tensor)
@@ -1150,6 +1151,9 @@ class _Loss(torch.autograd.Function):
         ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=pred.device)
         seed = _LOSS_SEED[0]
         ctx.seed_ptr, ctx.seed_value = (seed[1].data_ptr(), seed[0]) if seed is not None else (0, 1.0)
+        # the declared seed is recognised by its address, so the node keeps the tensor alive: freed, its block could
+        # be handed to another upstream gradient, which would then pass for the declared one
+        ctx.seed_keep = seed[1] if seed is not None else None
         if kind == _lib.LOSS_SSIM:
             check(lib.srk_ssim_loss_forward_backward(ptr(pred), ptr(target), strides, n, c, h, w, ctx.seed_value, ptr(loss),
                                                      ptr(dpred), ptr(ws), stream_ptr()), "srk_ssim_loss_forward_backward")
@@ -2388,6 +2392,9 @@ class _DRCNHead(torch.autograd.Function):
         ws = torch.empty(max(int(lib.srk_drcn_workspace_bytes(D)), 16), dtype=torch.uint8, device=Y.device)
         seed = _LOSS_SEED[0]
         ctx.seed_ptr, ctx.seed_value = (seed[1].data_ptr(), seed[0]) if seed is not None else (0, 1.0)
+        # the declared seed is recognised by its address, so the node keeps the tensor alive: freed, its block could
+        # be handed to another upstream gradient, which would then pass for the declared one
+        ctx.seed_keep = seed[1] if seed is not None else None
         wacc = getattr(w, "_srk_grad", None) if need_grad else None
         dw = None
         if need_grad:
@@ -2686,6 +2693,9 @@ class _LpipsFinish(torch.autograd.Function):
         need = any(ctx.needs_input_grad[2:])
         seed = _LOSS_SEED[0] if reduce else None
         ctx.seed_ptr, ctx.seed_value = (seed[1].data_ptr(), seed[0]) if seed is not None else (0, 1.0)
+        # the declared seed is recognised by its address, so the node keeps the tensor alive: freed, its block could
+        # be handed to another upstream gradient, which would then pass for the declared one
+        ctx.seed_keep = seed[1] if seed is not None else None
         out = torch.empty(n if not reduce else (), dtype=torch.float32, device=table.device)
         gvec = torch.empty(n, dtype=torch.float64, device=table.device) if (need and reduce) else None
         check(lib.srk_lpips_finish(ptr(table), nl, n, ctx.seed_value, None if reduce else ptr(out), ptr(out) if reduce else None,
@@ -2744,3 +2754,262 @@ def lpips(pred, target, net, normalize=True, reduce=True):
     table = torch.empty((len(fake), pred.shape[0]), dtype=torch.float64, device=pred.device)
     rows = [lpips_layer(a, b, w, l, table) for l, (a, b, w) in enumerate(zip(fake, real, net.lins))]
     return _LpipsFinish.apply(table, bool(reduce), *rows)
+
+
+# ------------------------------------------------------------------------------------------------
+# Convolution over channel slices and the residual-dense trunk of RDN (csrc/dense.hip)
+# ------------------------------------------------------------------------------------------------
+def dense_terms(role):
+    """MFMA products per multiplication of the slice convolutions in the current precision mode: 3 where _MODES asks for
+    ALGO_AUTO (the bf16x3 class), 6 for the fp32-faithful class -- and for 'fp32', whose exact-fp32 MFMA kernel the
+    six-term split is tighter than (see _MODES).  role: 'infer' | 'train_fwd' | 'bwd'."""
+    return 3 if _MODES[_PRECISION["mode"]][role] in (ALGO_AUTO, _lib.ALGO_MFMA_BF16X3) else 6
+
+
+def _dense_check(rc, what):
+    """check(), but a request no kernel covers is the caller's ValueError (the message names the number): there is no
+    concatenating fallback."""
+    if rc == _lib.ERR_UNSUPPORTED:
+        raise ValueError("%s: %s" % (what, _lib.load().srk_last_error_string().decode()))
+    check(rc, what)
+
+
+class _Slice(object):
+    """`channels` channels of a dense NHWC buffer, from channel `off`: pointer and pixel stride for the kernels."""
+    __slots__ = ("t", "off", "channels", "ld", "p")
+
+    def __init__(self, what, t, off, channels, like=None):
+        if not torch.is_tensor(t) or t.dim() != 4 or not t.is_cuda or t.dtype != torch.float32 or not _is_nhwc_dense(t):
+            raise RuntimeError("%s: a channels_last fp32 [N, C, H, W] tensor on the device is expected, got %s"
+                               % (what, (tuple(t.shape), t.stride(), t.dtype, t.device) if torch.is_tensor(t) else type(t)))
+        off, channels = int(off), int(channels)
+        if off < 0 or channels < 0 or off + channels > t.shape[1]:
+            raise ValueError("%s: channels [%d, %d) do not lie in the buffer's %d" % (what, off, off + channels, t.shape[1]))
+        if like is not None and (t.shape[0], t.shape[2], t.shape[3]) != (like.t.shape[0], like.t.shape[2], like.t.shape[3]):
+            raise ValueError("%s: %s vs %s: batch and picture sizes differ" % (what, tuple(t.shape), tuple(like.t.shape)))
+        self.t, self.off, self.channels, self.ld = t, off, channels, int(t.shape[1])
+        self.p = ctypes.c_void_p(t.data_ptr() + 4 * off)
+
+
+def _dense_desc(a, b, cout, k, act, slope, terms):
+    d = _lib.DenseDesc()
+    d.N, d.H, d.W = int(a.t.shape[0]), int(a.t.shape[2]), int(a.t.shape[3])
+    d.K, d.CA, d.CB, d.Cout = int(k), a.channels, (b.channels if b is not None else 0), int(cout)
+    d.ldA, d.ldB = a.ld, (b.ld if b is not None else 0)
+    d.act, d.slope, d.terms = int(act), float(slope), int(terms)
+    return d
+
+
+def _dense_weight(what, weight, d):
+    if tuple(weight.shape) != (d.Cout, d.CA + d.CB, d.K, d.K) or not weight.is_contiguous():
+        raise ValueError("%s: a contiguous weight [%d, %d, %d, %d] is expected, got %s"
+                         % (what, d.Cout, d.CA + d.CB, d.K, d.K, tuple(weight.shape)))
+
+
+def dense_conv(a, weight, bias=None, b=None, out=None, ca=None, a_off=0, cb=None, b_off=0, out_off=0, act=ACT_NONE,
+               slope=0.0, residual=None, res_off=0, terms=3):
+    """out[:, out_off : out_off + Cout] = act(conv(cat(a[:, a_off : a_off + ca], b[:, b_off : b_off + cb]), weight) + bias)
+    (+ residual[:, res_off : res_off + Cout]) without the cat: stride 1, 'same', K in {1, 3}.  a, b, out, residual:
+    channels_last buffers of any width; no other channel of `out` is touched.  out=None: a new [N, Cout, H, W] tensor.
+    No autograd (ops.residual_dense_blocks is the differentiable user).  ValueError for what no kernel covers."""
+    lib = _lib.load()
+    what = "dense_conv"
+    cout, k = int(weight.shape[0]), int(weight.shape[2])
+    sa = _Slice(what + ": a", a, a_off, a.shape[1] - a_off if ca is None else ca)
+    sb = None
+    if b is not None and (cb is None or cb > 0):
+        sb = _Slice(what + ": b", b, b_off, b.shape[1] - b_off if cb is None else cb, sa)
+    if out is None:
+        out = _empty_cl(a.shape[0], cout, a.shape[2], a.shape[3], a)
+    so = _Slice(what + ": out", out, out_off, cout, sa)
+    d = _dense_desc(sa, sb, cout, k, act, slope, terms)
+    _dense_weight(what, weight, d)
+    d.ldY = so.ld
+    sr = None
+    if residual is not None:
+        sr = _Slice(what + ": residual", residual, res_off, cout, sa)
+        d.ldR = sr.ld
+    _dense_check(lib.srk_dense_conv_forward(ctypes.byref(d), sa.p, sb.p if sb else None, ptr(weight.detach()),
+                                            ptr(bias.detach()) if bias is not None else None, sr.p if sr else None, so.p,
+                                            stream_ptr()), "srk_dense_conv_forward")
+    return out
+
+
+def dense_conv_backward_data(dy, weight, ca, cb=0, y_saved=None, da=None, db=None, add=None, dy_off=0, y_off=0, da_off=0,
+                             db_off=0, add_off=0, beta_a=0.0, beta_b=0.0, act=ACT_NONE, slope=0.0, terms=3):
+    """The data gradient of dense_conv into the slices da[:, da_off : da_off + ca] and db[:, db_off : db_off + cb]
+    (either may be None): slice = beta * slice + conv^T(dy * act'(y_saved)) (+ add into da), beta 0 or 1."""
+    lib = _lib.load()
+    what = "dense_conv_backward_data"
+    cout, k = int(weight.shape[0]), int(weight.shape[2])
+    sdy = _Slice(what + ": dy", dy, dy_off, cout)
+    d = _lib.DenseDesc()
+    d.N, d.H, d.W = int(dy.shape[0]), int(dy.shape[2]), int(dy.shape[3])
+    d.K, d.CA, d.CB, d.Cout = k, int(ca), int(cb), cout
+    d.act, d.slope, d.terms = int(act), float(slope), int(terms)
+    _dense_weight(what, weight, d)
+    d.ldDy = sdy.ld
+    sy = sda = sdb = sadd = None
+    if y_saved is not None:
+        sy = _Slice(what + ": y_saved", y_saved, y_off, cout, sdy)
+        d.ldY = sy.ld
+    if da is not None:
+        sda = _Slice(what + ": da", da, da_off, ca, sdy)
+        d.ldDA = sda.ld
+    if db is not None and cb > 0:
+        sdb = _Slice(what + ": db", db, db_off, cb, sdy)
+        d.ldDB = sdb.ld
+    if add is not None:
+        sadd = _Slice(what + ": add", add, add_off, ca, sdy)
+        d.ldAdd = sadd.ld
+    _dense_check(lib.srk_dense_conv_backward_data(ctypes.byref(d), sdy.p, sy.p if sy else None, ptr(weight.detach()),
+                                                  sda.p if sda else None, float(beta_a), sdb.p if sdb else None,
+                                                  float(beta_b), sadd.p if sadd else None, stream_ptr()),
+                 "srk_dense_conv_backward_data")
+    return da, db
+
+
+def dense_conv_backward_weight(a, dy, dw, dbias=None, b=None, y_saved=None, ca=None, a_off=0, cb=None, b_off=0, dy_off=0,
+                               y_off=0, beta=0.0, act=ACT_NONE, slope=0.0, terms=3):
+    """dw = beta * dw + sum over pixels of cat(a, b)^T (dy * act'(y_saved)), dbias likewise (beta 0 or 1); dw is a
+    contiguous [Cout, ca + cb, K, K] tensor or view (a parameter's slice of the flat gradient buffer).  Two launches, the
+    pixel ranges added in a fixed order: two calls give the same bits."""
+    lib = _lib.load()
+    what = "dense_conv_backward_weight"
+    cout, k = int(dw.shape[0]), int(dw.shape[2])
+    sa = _Slice(what + ": a", a, a_off, a.shape[1] - a_off if ca is None else ca)
+    sb = None
+    if b is not None and (cb is None or cb > 0):
+        sb = _Slice(what + ": b", b, b_off, b.shape[1] - b_off if cb is None else cb, sa)
+    sdy = _Slice(what + ": dy", dy, dy_off, cout, sa)
+    d = _dense_desc(sa, sb, cout, k, act, slope, terms)
+    _dense_weight(what, dw, d)
+    d.ldDy = sdy.ld
+    sy = None
+    if y_saved is not None:
+        sy = _Slice(what + ": y_saved", y_saved, y_off, cout, sa)
+        d.ldY = sy.ld
+    if lib.srk_dense_conv_plan(ctypes.byref(d), ctypes.byref(_lib.DensePlan())) == _lib.ERR_UNSUPPORTED:
+        raise ValueError("%s: %s" % (what, lib.srk_last_error_string().decode()))
+    nbytes = int(lib.srk_dense_conv_workspace_bytes(ctypes.byref(d)))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=a.device)   # torch's allocator: a captured graph owns it
+    _dense_check(lib.srk_dense_conv_backward_weight(ctypes.byref(d), sa.p, sb.p if sb else None, sdy.p,
+                                                    sy.p if sy else None, ptr(dw), ptr(dbias), float(beta), ptr(ws), nbytes,
+                                                    stream_ptr()), "srk_dense_conv_backward_weight")
+    return dw, dbias
+
+
+def _growth_buffer(n, c, h, w, like):
+    """A block's growth buffer (its own name, so that a test can count them: one per call without a backward)."""
+    return _empty_cl(n, c, h, w, like)
+
+
+class _ResidualDenseBlocks(torch.autograd.Function):
+    """D residual dense blocks on slice convolutions; see residual_dense_blocks."""
+
+    @staticmethod
+    def forward(ctx, x, D, C, need_grad, *params):
+        require_cuda(x, *params)
+        x = to_nhwc(x)
+        n, g0, hh, ww = x.shape
+        per = 2 * (C + 1)
+        g = int(params[0].shape[0])
+        # need_grad: decided by the caller, where the grad mode is still visible (needs_input_grad mirrors requires_grad
+        # under torch.no_grad() too, and test() runs the training model there)
+        terms = dense_terms("train_fwd" if need_grad else "infer")
+        fusion = _empty_cl(n, D * g0, hh, ww, x)
+        growths, growth = [], None
+        for blk in range(D):
+            p = params[blk * per:(blk + 1) * per]
+            if need_grad or growth is None:     # a backward reads every block's growth buffer: they are its ReLU masks
+                growth = _growth_buffer(n, C * g, hh, ww, x)
+            growths.append(growth)
+            a, a_off = (x, 0) if blk == 0 else (fusion, (blk - 1) * g0)
+            for c in range(C):
+                dense_conv(a, p[2 * c], p[2 * c + 1], growth if c else None, growth, g0, a_off, c * g, 0, c * g, ACT_RELU,
+                           0.0, None, 0, terms)
+            dense_conv(a, p[2 * C], p[2 * C + 1], growth, fusion, g0, a_off, C * g, 0, blk * g0, ACT_NONE, 0.0, a, a_off,
+                       terms)
+        ctx.dims = (D, C, g0, g)
+        ctx.params = params
+        if need_grad:
+            ctx.save_for_backward(x, fusion, *growths)
+        return fusion
+
+    @staticmethod
+    def backward(ctx, gout):
+        D, C, g0, g = ctx.dims
+        params = ctx.params
+        saved = ctx.saved_tensors
+        x, fusion, growths = saved[0], saved[1], saved[2:]
+        n, _, hh, ww = x.shape
+        per = 2 * (C + 1)
+        terms = dense_terms("bwd")
+        gf = _dense(gout)                  # the fan-in accumulator: one copy, because autograd owns gout
+        if gf is gout:                     # (a layout conversion already made one)
+            gf = gout.clone(memory_format=torch.preserve_format)
+        gg = _empty_cl(n, C * g, hh, ww, x)
+        dx = _empty_cl(n, g0, hh, ww, x) if ctx.needs_input_grad[0] else None
+        grads = [None] * len(params)
+
+        def wgrad(i, a, a_off, b, cb, dy, dy_off, ys, y_off, act):
+            w, bias = params[i], params[i + 1]
+            if not (ctx.needs_input_grad[4 + i] or ctx.needs_input_grad[5 + i]):
+                return
+            acc = _flat_grads(w, bias)
+            if acc is not None:    # optim.FlatParams: accumulated in the flat gradient buffer
+                dw, dbias, beta = acc[0], acc[1], 1.0
+            else:
+                dw = torch.empty_like(w, memory_format=torch.contiguous_format)
+                dbias, beta = torch.empty_like(bias), 0.0
+                grads[i], grads[i + 1] = dw, dbias
+            dense_conv_backward_weight(a, dy, dw, dbias, b if cb else None, ys, g0, a_off, cb, 0, dy_off, y_off, beta, act,
+                                       0.0, terms)
+
+        for blk in reversed(range(D)):
+            i0 = blk * per
+            growth = growths[blk]
+            a, a_off = (x, 0) if blk == 0 else (fusion, (blk - 1) * g0)
+            da, da_off = (dx, 0) if blk == 0 else (gf, (blk - 1) * g0)
+            # the local fusion: its data gradient starts the growth gradient (beta 0) and adds the skip's gradient, the
+            # block's output gradient itself, into the input's slice in the same epilogue
+            wgrad(i0 + 2 * C, a, a_off, growth, C * g, gf, blk * g0, None, 0, ACT_NONE)
+            dense_conv_backward_data(gf, params[i0 + 2 * C], g0, C * g, None, da, gg, gf if da is not None else None,
+                                     blk * g0, 0, da_off, 0, blk * g0, 0.0 if blk == 0 else 1.0, 0.0, ACT_NONE, 0.0, terms)
+            for c in reversed(range(C)):
+                wgrad(i0 + 2 * c, a, a_off, growth, c * g, gg, c * g, growth, c * g, ACT_RELU)
+                if da is None and c == 0:
+                    continue
+                dense_conv_backward_data(gg, params[i0 + 2 * c], g0, c * g, growth, da, gg if c else None, None, c * g,
+                                         c * g, da_off, 0, 0, 1.0, 1.0, ACT_RELU, 0.0, terms)
+        return (dx, None, None, None) + tuple(grads)
+
+
+def residual_dense_blocks(x, blocks):
+    """The trunk of RDN: D residual dense blocks without a concatenation.  x: [N, G0, H, W]; blocks: D sequences
+    (w_1, b_1, ..., w_C, b_C, w_lff, b_lff) with w_c [G, G0 + (c - 1) G, 3, 3] and w_lff [G0, G0 + C G, 1, 1].  Returns the
+    global-fusion buffer [N, D * G0, H, W] (channels_last) = cat(RDB_1 .. RDB_D outputs): block d writes channels
+    [d G0, (d + 1) G0) and block d + 1 reads them in place.  C + 1 launches a block forward; the backward accumulates
+    every gradient fan-in inside the data-gradient kernels (base_networks.RDB, models.RDNNet)."""
+    blocks = [tuple(b) for b in blocks]
+    if not blocks or len(set(len(b) for b in blocks)) != 1 or len(blocks[0]) < 4 or len(blocks[0]) % 2:
+        raise ValueError("residual_dense_blocks: every block is (w_1, b_1, ..., w_C, b_C, w_lff, b_lff) with the same C >= 1")
+    if x.dim() != 4:
+        raise ValueError("residual_dense_blocks: x must be [N, G0, H, W], got shape %s" % (tuple(x.shape),))
+    C = len(blocks[0]) // 2 - 1
+    g0, g = int(x.shape[1]), int(blocks[0][0].shape[0])
+    for b in blocks:
+        for c in range(C):
+            if tuple(b[2 * c].shape) != (g, g0 + c * g, 3, 3) or tuple(b[2 * c + 1].shape) != (g,):
+                raise ValueError("residual_dense_blocks: layer %d holds %s / %s, expected [%d, %d, 3, 3] / [%d]"
+                                 % (c + 1, tuple(b[2 * c].shape), tuple(b[2 * c + 1].shape), g, g0 + c * g, g))
+        if tuple(b[2 * C].shape) != (g0, g0 + C * g, 1, 1) or tuple(b[2 * C + 1].shape) != (g0,):
+            raise ValueError("residual_dense_blocks: the local fusion holds %s / %s, expected [%d, %d, 1, 1] / [%d]"
+                             % (tuple(b[2 * C].shape), tuple(b[2 * C + 1].shape), g0, g0 + C * g, g0))
+    for name, v in (("G0", g0), ("G", g)):
+        if v % 16:
+            raise ValueError("residual_dense_blocks: %s = %d is not a multiple of 16" % (name, v))
+    if g > 64 or g0 > 64:
+        raise ValueError("residual_dense_blocks: G = %d, G0 = %d: at most 64 output channels a convolution" % (g, g0))
+    params = [t for b in blocks for t in b]
+    return _ResidualDenseBlocks.apply(x, len(blocks), C, grad_enabled_for(x, *params), *params)

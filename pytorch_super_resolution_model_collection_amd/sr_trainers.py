@@ -1019,5 +1019,24 @@ class RCAN(_Trainer):
         apply_lr_decay("edsr", epoch, opt)
 
 
+class RDN(_Trainer):
+    """RDN (models.RDNNet; not in the reference collection) behind the common trainer: L1 and Adam as EDSR, EDSR's
+    learning-rate decay, `--rdn_blocks` residual dense blocks of `--rdn_layers` layers with growth `--rdn_growth`, 64
+    shallow features.  Purely convolutional: `--tile` works (tiling.net_geometry)."""
+    kind = "rdn"
+
+    def __init__(self, args):
+        super(RDN, self).__init__(args)
+        self.blocks = int(getattr(args, "rdn_blocks", None) or 16)
+        self.layers = int(getattr(args, "rdn_layers", None) or 8)
+        self.growth = int(getattr(args, "rdn_growth", None) or 64)
+
+    def build_model(self):
+        return models.RDNNet(self.num_channels, 64, self.blocks, self.layers, self.growth, self.scale_factor)
+
+    def lr_decay(self, epoch, opt):
+        apply_lr_decay("edsr", epoch, opt)
+
+
 TRAINERS = {"SRCNN": SRCNN, "VDSR": VDSR, "ESPCN": ESPCN, "FSRCNN": FSRCNN, "SRGAN": SRGAN, "LapSRN": LapSRN, "EDSR": EDSR,
-            "DRCN": DRCN, "RCAN": RCAN}
+            "DRCN": DRCN, "RCAN": RCAN, "RDN": RDN}

@@ -5,7 +5,8 @@ tile_stitch / tile_stitch_u8); the trainers drive both from sr_trainers._Trainer
 
 The reference's eight nets are convolutional with a bounded receptive field and treat both axes alike, so everything
 here is one-dimensional and applied to rows and columns independently.  The ninth, RCAN, is not: its channel attention
-pools over the whole picture, the walk says so (as it does for instance norm) and the picture runs in one pass.
+pools over the whole picture, the walk says so (as it does for instance norm) and the picture runs in one pass.  The
+tenth, RDN, is convolutional again: a residual dense block is the cone of its C chained 3x3 convs.
 
 Geometry.  Along one axis, a feature map of a net is described against the net's INPUT by three integers (scale, lo, hi):
 map pixel o depends on the input pixels
@@ -183,6 +184,14 @@ def _walk(g, m, path):
         return _union(_walk(out, m.ca, path + ".ca"), g, path)
     if isinstance(m, B.ResidualGroup):
         return _union(_walk(_walk(g, m.blocks, path + ".blocks"), m.conv, path + ".conv"), g, path)
+    if isinstance(m, B.RDB):   # x + LFF(cat(x, y_1 .. y_C)), y_c = relu(conv_c(cat(x, y_1 .. y_c-1))): the deepest cone is
+        out = g                # the chain of all C 3x3 convs, the 1x1 fusion adds nothing, the skip is the input itself
+        for name, layer in m.convs.named_children():
+            out = _union(_conv(out, layer.conv[0], "%s.convs.%s.conv.0" % (path, name)), g, path)
+        out = _union(_conv(out, m.LFF, path + ".LFF"), g, path)
+        # live while the block runs: its input, the growth buffer and its output
+        live = (2 * m.G0 + m.C * m.G) * g.scale ** 2
+        return Geometry(out.scale, out.offset, out.lo, out.hi, max(out.floats_per_pixel, live))
     if isinstance(m, torch.nn.ConvTranspose2d):
         return _deconv(g, m, path)
     if isinstance(m, torch.nn.Conv2d):
@@ -231,6 +240,19 @@ def net_geometry(model):
         out = _walk(_walk(head, model.residual_groups, "residual_groups"), model.mid_conv, "mid_conv")
         out = _union(out, head, "mid_conv")
         return _walk(_walk(out, model.upscale, "upscale"), model.output_conv, "output_conv")
+    if isinstance(model, M.RDNNet):
+        head = _walk(g, model.SFENet1, "SFENet1")
+        out = _walk(head, model.SFENet2, "SFENet2")
+        fused = None   # the fusion buffer: every block's output, block d + 1 reading block d's
+        for name, block in model.RDBs.named_children():
+            out = _walk(out, block, "RDBs.%s" % name)
+            fused = out if fused is None else _union(fused, out, "RDBs.%s" % name)
+        rdb = model.RDBs[0]
+        # live through the trunk: the SFENet1 skip, the trunk's input, the whole fusion buffer and one growth buffer
+        live = (2 * rdb.G0 + len(model.RDBs) * rdb.G0 + rdb.C * rdb.G) * fused.scale ** 2
+        fused = Geometry(fused.scale, fused.offset, fused.lo, fused.hi, max(fused.floats_per_pixel, live))
+        out = _union(_walk(fused, model.GFF, "GFF"), head, "GFF")
+        return _walk(out, model.UPNet, "UPNet")
     if isinstance(model, M.LapSRNNet):
         f1 = _walk(_walk(g, model.input_conv, "input_conv"), model.convt_F1, "convt_F1")
         coarse = _union(_walk(f1, model.convt_R1, "convt_R1"), _walk(g, model.convt_I1, "convt_I1"), "convt_R1")
