@@ -970,6 +970,62 @@ int srk_dense_conv_host(const srk_dense_desc* d, int direction, const float* A, 
                         const float* bias, const float* residual, float* y, const float* dy, const float* add, float* dA,
                         float betaA, float* dB, float betaB, float* dW, float* db, float beta);
 
+/* ---- Shifted-window self-attention: SwinIR's attention operator (csrc/wattn.hip, csrc/wattn_common.h) ----------------
+ * (Additive again: new entry points only, srk_version() and everything existing unchanged.)
+ * qkv dense NHWC [N][H][W][3C], the qkv projection with its bias applied, channels q | k | v, each split heads x d
+ * (d = C / heads); table [(2 window - 1)^2][heads]; out, dout [N][H][W][C]; dqkv as qkv.
+ * The map is rolled by -shift along both axes and cut into window x window windows of T = window^2 tokens.  Per window
+ * and head, with i, j tokens in row-major order:
+ *   S = d^-0.5 Q K^T + table[rel(i, j)][head] + mask(i, j)      P = softmax_j S      O = P V
+ *   rel(i, j) = (y_i - y_j + window - 1) (2 window - 1) + (x_i - x_j + window - 1)
+ *   mask(i, j) = -100 where shift > 0 and the tokens' region ids differ; a token at shifted (r, c) has id
+ *   3 band(r, H) + band(c, W), band(r, H) = 0 if r < H - window, 1 if r < H - shift, else 2
+ * and O is written where the token was read (the roll back).  Neither mask nor index exists in memory.  From dout:
+ *   dV = P^T dO   dP = dO V^T   dS = P (dP - rowsum(P dP))   dQ = d^-0.5 dS K   dK = d^-0.5 dS^T Q
+ *   dtable[r][head] = sum over N, windows and pairs with rel(i, j) = r of dS
+ * fp32 FMAs; one wave a (window, head), one lane a token.  dtable goes through per-block bins added up in a fixed order;
+ * the grid is a function of the shape.  No atomics: two calls on the same inputs give the same bits.
+ * Supported (SRK_ERR_BAD_ARG otherwise, the message names the number): 2 <= window <= 8, 0 <= shift < window, H and W
+ * multiples of window, heads dividing C, d <= SRK_WATTN_MAX_HEAD_DIM.
+ * srk_window_attention_forward: lse [N * (H / window) * (W / window)][heads][64], the row log-sum-exp the backward
+ *   reads, or NULL when no backward follows.
+ * srk_window_attention_backward: reads the forward's out and lse.  dtable == NULL: no table gradient (and no workspace);
+ *   else dtable = beta * dtable + gradient (beta == 0 never reads it) through srk_window_attention_workspace() bytes.
+ * srk_window_attention_host: the definition in double on host pointers, from the loop of wattn_common.h.  dout == NULL:
+ *   forward only.  srk_window_attention_region / _rel_index / _token_pixel: the header's index functions (-1 for
+ *   arguments out of range); region takes SHIFTED coordinates, token_pixel returns y * W + x of the unshifted map. */
+#define SRK_WATTN_MAX_HEAD_DIM 32
+size_t srk_window_attention_workspace(int N, int H, int W, int C, int heads, int window);
+int srk_window_attention_forward(const float* qkv, const float* table, int N, int H, int W, int C, int heads, int window,
+                                 int shift, float* out, float* lse, void* stream);
+int srk_window_attention_backward(const float* dout, const float* qkv, const float* table, const float* out,
+                                  const float* lse, int N, int H, int W, int C, int heads, int window, int shift,
+                                  float* dqkv, float* dtable, float beta, void* workspace, size_t workspace_bytes,
+                                  void* stream);
+int srk_window_attention_host(const float* qkv, const float* table, const float* dout, int N, int H, int W, int C,
+                              int heads, int window, int shift, double* out, double* dqkv, double* dtable);
+int srk_window_attention_region(int H, int W, int window, int shift, int r, int c);
+int srk_window_attention_rel_index(int window, int ti, int tj);
+int64_t srk_window_attention_token_pixel(int H, int W, int window, int shift, int wy, int wx, int t);
+
+/* ---- LayerNorm over the last axis with an affine, and the exact GELU (csrc/swin_pointwise.hip) ----------------------
+ * x, y, dy, dx [rows][C] dense; gamma, beta [C]; mean, rstd [rows] (biased variance, rstd = 1 / sqrt(var + eps)).
+ *   y = (x - mean) rstd gamma + beta        dx = rstd (g dy - mean_c(g dy) - xhat mean_c(g dy xhat)), xhat = (x - mean) rstd
+ *   dgamma = sum_rows dy xhat               dbeta = sum_rows dy
+ * Any C >= 1.  mean and rstd: both or neither (NULL: inference).  The parameter gradients go through
+ * srk_layer_norm_workspace() bytes of per-range partials added up in index order; out = acc * out + gradient
+ * (acc == 0 never reads out); either may be NULL, dx may be NULL.  No atomics.
+ * GELU: y = x Phi(x) with erf; dx = dy (Phi(x) + x phi(x)) from the saved input.  16-byte accesses with a scalar tail
+ * where every pointer is 16-byte aligned, else 4-byte accesses. */
+size_t srk_layer_norm_workspace(int64_t rows, int C);
+int srk_layer_norm_forward(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd,
+                           int64_t rows, int C, float eps, void* stream);
+int srk_layer_norm_backward(const float* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+                            float* dx, float* dgamma, float* dbeta, float acc, int64_t rows, int C, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int srk_gelu_forward(const float* x, float* y, size_t n, void* stream);
+int srk_gelu_backward(const float* dy, const float* x, float* dx, size_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

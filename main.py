@@ -31,6 +31,9 @@ training loss of every model but SRGAN and DRCN.  RGB only (--num_channels 3).
 --model_name RDN (not in the reference: residual dense blocks on concat-free slice convolutions, models.RDNNet) with
 --rdn_blocks D, --rdn_layers C and --rdn_growth G (defaults 16, 8, 64: the paper's net); every flag of the common trainer
 works with it, --tile included.
+--model_name SwinIR (not in the reference: shifted-window attention, models.SwinIRNet) with --swinir_dim, --swinir_depths,
+--swinir_heads, --swinir_window, --swinir_mlp_ratio and --swinir_upsampler {pixelshuffle,pixelshuffledirect} (defaults: the
+classical net, 180 channels, 6 x 6 layers, 6 heads, window 8, ratio 2); every flag of the common trainer but --tile.
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N main.py ..."""
 import argparse
 import os
@@ -61,6 +64,28 @@ def _positive(text):
         v = 0
     if v < 1:
         raise argparse.ArgumentTypeError("a whole number >= 1 is expected, got %r" % (text,))
+    return v
+
+
+def _depths(text):
+    """--swinir_depths: layers per RSTB, whole numbers >= 1, comma-separated."""
+    try:
+        v = tuple(int(t) for t in text.split(','))
+    except ValueError:
+        v = ()
+    if not v or min(v) < 1:
+        raise argparse.ArgumentTypeError("whole numbers >= 1, comma-separated, are expected, got %r" % (text,))
+    return v
+
+
+def _mlp_ratio(text):
+    """--swinir_mlp_ratio: a number > 0."""
+    try:
+        v = float(text)
+    except ValueError:
+        v = 0.0
+    if not v > 0:
+        raise argparse.ArgumentTypeError("a number > 0 is expected, got %r" % (text,))
     return v
 
 
@@ -205,7 +230,7 @@ def _jpeg_prob(text):
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="MI355X-native SR collection (reference-compatible CLI)")
     p.add_argument('--model_name', type=str, default='SRGAN',
-                   choices=['SRCNN', 'VDSR', 'ESPCN', 'FSRCNN', 'SRGAN', 'LapSRN', 'EDSR', 'DRCN', 'RCAN', 'RDN'],
+                   choices=['SRCNN', 'VDSR', 'ESPCN', 'FSRCNN', 'SRGAN', 'LapSRN', 'EDSR', 'DRCN', 'RCAN', 'RDN', 'SwinIR'],
                    help='The type of model')
     p.add_argument('--data_dir', type=str, default='../Data')
     p.add_argument('--train_dataset', type=_names, default=['DIV2K'], help='The name(s) of the training dataset, comma-separated')
@@ -325,7 +350,32 @@ def parse_args(argv=None):
                    help='RDN: convolutions per residual dense block (default 8)')
     p.add_argument('--rdn_growth', type=_positive, default=64, metavar='G',
                    help='RDN: growth rate, channels every layer adds: 16, 32, 48 or 64 (default 64)')
+    p.add_argument('--swinir_dim', type=_positive, default=180, metavar='C', help='SwinIR: embedding channels (default 180)')
+    p.add_argument('--swinir_depths', type=_depths, default=(6, 6, 6, 6, 6, 6), metavar='D1,D2,...',
+                   help='SwinIR: layers of every residual Swin Transformer block (default 6,6,6,6,6,6)')
+    p.add_argument('--swinir_heads', type=_positive, default=6, metavar='H', help='SwinIR: attention heads (default 6)')
+    p.add_argument('--swinir_window', type=_positive, default=8, metavar='W', help='SwinIR: window size, 2 .. 8 (default 8)')
+    p.add_argument('--swinir_mlp_ratio', type=_mlp_ratio, default=2.0, metavar='R',
+                   help='SwinIR: hidden channels of the MLP over the embedding channels (default 2)')
+    p.add_argument('--swinir_upsampler', type=str, default='pixelshuffle', choices=['pixelshuffle', 'pixelshuffledirect'],
+                   help='SwinIR: the classical (pixelshuffle) or the lightweight (pixelshuffledirect) reconstruction')
     args = p.parse_args(argv)
+    if args.model_name == 'SwinIR':
+        if args.tile is not None:
+            p.error('--tile: SwinIR\'s WindowAttention partitions the whole image into windows, its pictures run in one '
+                    'pass (drop --tile)')
+        if args.swinir_dim % args.swinir_heads:
+            p.error('--swinir_heads %d does not divide --swinir_dim %d' % (args.swinir_heads, args.swinir_dim))
+        if args.swinir_dim // args.swinir_heads > 32:
+            p.error('--swinir_dim %d / --swinir_heads %d: a head dimension of %d exceeds 32'
+                    % (args.swinir_dim, args.swinir_heads, args.swinir_dim // args.swinir_heads))
+        if not 2 <= args.swinir_window <= 8:
+            p.error('--swinir_window %d is not in 2 .. 8' % args.swinir_window)
+        if args.swinir_upsampler == 'pixelshuffle' and args.scale_factor not in (2, 3, 4, 8):
+            p.error('--scale_factor %d: SwinIR\'s pixelshuffle upsampler works by 2, 3, 4 or 8' % args.scale_factor)
+        if args.crop_size % args.scale_factor or (args.crop_size // args.scale_factor) % args.swinir_window:
+            p.error('--crop_size %d / --scale_factor %d is not a multiple of --swinir_window %d'
+                    % (args.crop_size, args.scale_factor, args.swinir_window))
     if args.model_name == 'RDN' and (args.rdn_growth % 16 or args.rdn_growth > 64):
         p.error('--rdn_growth %d: RDN\'s slice convolutions write 16, 32, 48 or 64 channels' % args.rdn_growth)
     if args.model_name == 'RDN' and args.scale_factor not in (2, 3, 4):

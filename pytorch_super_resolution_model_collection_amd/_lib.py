@@ -278,6 +278,18 @@ _PROTOTYPES = {
     "srk_dense_conv_backward_weight": (c_int, [ctypes.POINTER(DenseDesc)] + [c_f] * 6 + [c_float, c_vp, c_size, c_vp]),
     "srk_dense_conv_host": (c_int, [ctypes.POINTER(DenseDesc), c_int] + [c_vp] * 9 + [c_float, c_vp, c_float, c_vp, c_vp,
                                                                                      c_float]),
+    "srk_window_attention_workspace": (c_size, [c_int] * 6),
+    "srk_window_attention_forward": (c_int, [c_f, c_f] + [c_int] * 7 + [c_f, c_f, c_vp]),
+    "srk_window_attention_backward": (c_int, [c_f] * 5 + [c_int] * 7 + [c_f, c_f, c_float, c_vp, c_size, c_vp]),
+    "srk_window_attention_host": (c_int, [c_vp] * 3 + [c_int] * 7 + [c_vp] * 3),
+    "srk_window_attention_region": (c_int, [c_int] * 6),
+    "srk_window_attention_rel_index": (c_int, [c_int] * 3),
+    "srk_window_attention_token_pixel": (ctypes.c_int64, [c_int] * 7),
+    "srk_layer_norm_workspace": (c_size, [ctypes.c_int64, c_int]),
+    "srk_layer_norm_forward": (c_int, [c_f] * 6 + [ctypes.c_int64, c_int, c_float, c_vp]),
+    "srk_layer_norm_backward": (c_int, [c_f] * 8 + [c_float, ctypes.c_int64, c_int, c_vp, c_size, c_vp]),
+    "srk_gelu_forward": (c_int, [c_f, c_f, c_size, c_vp]),
+    "srk_gelu_backward": (c_int, [c_f, c_f, c_f, c_size, c_vp]),
 }
 
 _lib = None

@@ -8,6 +8,8 @@ to as few kernel launches as the arithmetic allows:
     ResnetBlock (no norm)     conv+act, conv + residual add                -> 2 launches
     PSBlock (no norm)         conv + bias + pixel-shuffle store (+ act)    -> 1 launch (+1 in training w/ PReLU)
     RCAB (RCAN; not in the reference)  conv+act, conv, channel-attention gate + residual add -> 4 launches
+    SwinTransformerLayer (SwinIR; not in the reference)  norm, qkv, attention, proj + skip, norm, fc1, GELU, fc2 + skip
+                                                                                  -> 8 launches
     RDB (RDN; not in the reference)    C convs + ReLU on channel slices, 1x1 fusion + skip    -> C + 1 launches, no cat
 
 With autograd enabled only ReLU / LeakyReLU are fused into the conv (their gradient mask can be
@@ -17,8 +19,9 @@ that saves what its backward needs.
 import torch
 
 from . import ops
-from .layers import (ACT_LRELU, ACT_NONE, ACT_PRELU, ACT_RELU, BatchNorm2d, Conv2d, ConvTranspose2d, GateConv2d, Linear,
-                     PixelShuffle, ReLU, Sigmoid, SliceConv2d, _plan_views, grad_mode, make_activation, make_norm1d, make_norm2d)
+from .layers import (ACT_LRELU, ACT_NONE, ACT_PRELU, ACT_RELU, GELU, BatchNorm2d, Conv2d, ConvTranspose2d, GateConv2d,
+                     LayerNorm, Linear, PixelShuffle, ReLU, Sigmoid, SliceConv2d, TokenLinear, _plan_views, grad_mode,
+                     make_activation, make_norm1d, make_norm2d)
 
 _FUSABLE_IN_TRAINING = (ACT_NONE, ACT_RELU, ACT_LRELU)
 
@@ -278,6 +281,98 @@ class _RDBConv(torch.nn.Module):
 
     def forward(self, x):
         raise RuntimeError("an RDB layer runs inside ops.residual_dense_blocks (base_networks.RDB.forward)")
+
+
+class WindowAttention(torch.nn.Module):
+    """Window multi-head self-attention with a relative position bias (Swin's W-MSA / SW-MSA), upstream's parameter names:
+    `relative_position_bias_table` [(2w - 1)^2, heads], `qkv` and `proj` with nn.Linear's [out, in] weights.  The two
+    projections are 1x1 convolutions of the NHWC map (layers.TokenLinear); everything between them -- shift, partition,
+    head split, bias gather, mask, softmax and the way back -- is ops.window_attention.  Upstream's
+    `relative_position_index` buffer does not exist here: the kernel computes the index."""
+
+    def __init__(self, dim, window_size, num_heads):
+        super(WindowAttention, self).__init__()
+        ops.window_attention_check(dim, num_heads, window_size, 0, who="WindowAttention")
+        self.dim, self.window_size, self.num_heads = dim, int(window_size), int(num_heads)
+        self.relative_position_bias_table = torch.nn.Parameter(torch.zeros((2 * self.window_size - 1) ** 2, num_heads))
+        torch.nn.init.trunc_normal_(self.relative_position_bias_table, std=.02)
+        self.qkv = TokenLinear(dim, dim * 3)
+        self.proj = TokenLinear(dim, dim)
+
+    def forward(self, x, shift=0, residual=None):
+        """x: logical [N, C, H, W] channels_last; `residual` is added in proj's epilogue."""
+        qkv = ops.to_nhwc(self.qkv.run(x)).permute(0, 2, 3, 1)          # [N, H, W, 3C], the storage as it is
+        out = ops.window_attention(qkv, self.relative_position_bias_table, self.num_heads, self.window_size, shift)
+        return self.proj.run(out.permute(0, 3, 1, 2), residual=residual)
+
+
+class Mlp(torch.nn.Module):
+    """fc1, exact GELU, fc2 per token (upstream's names); `residual` is added in fc2's epilogue."""
+
+    def __init__(self, in_features, hidden_features):
+        super(Mlp, self).__init__()
+        self.fc1 = TokenLinear(in_features, hidden_features)
+        self.act = GELU()
+        self.fc2 = TokenLinear(hidden_features, in_features)
+
+    def forward(self, x, residual=None):
+        return self.fc2.run(self.act(self.fc1.run(x)), residual=residual)
+
+
+class SwinTransformerLayer(torch.nn.Module):
+    """x + attn(norm1(x)), then x + mlp(norm2(x)) (upstream's SwinTransformerBlock without stochastic depth): eight
+    launches, both skips in the epilogues of proj and fc2.  In training each skip's gradient fan-in is one srk_axpby
+    (ops.fork)."""
+
+    def __init__(self, dim, num_heads, window_size=8, shift_size=0, mlp_ratio=2.):
+        super(SwinTransformerLayer, self).__init__()
+        ops.window_attention_check(dim, num_heads, window_size, shift_size, who="SwinTransformerLayer")
+        self.shift_size = int(shift_size)
+        self.norm1 = LayerNorm(dim)
+        self.attn = WindowAttention(dim, window_size, num_heads)
+        self.norm2 = LayerNorm(dim)
+        self.mlp = Mlp(dim, int(dim * mlp_ratio))
+
+    def forward(self, x):
+        training = grad_mode(x, *self.parameters())
+        x, skip = ops.fork(x) if training else (x, x)
+        x = self.attn(self.norm1(x), self.shift_size, residual=skip)
+        x, skip = ops.fork(x) if training else (x, x)
+        return self.mlp(self.norm2(x), residual=skip)
+
+
+class _SwinLayers(torch.nn.Module):
+    """The `residual_group` of an RSTB (upstream's BasicLayer): `blocks`, even ones unshifted, odd ones shifted by half a
+    window."""
+
+    def __init__(self, dim, depth, num_heads, window_size, mlp_ratio):
+        super(_SwinLayers, self).__init__()
+        self.blocks = torch.nn.ModuleList([
+            SwinTransformerLayer(dim, num_heads, window_size, 0 if j % 2 == 0 else window_size // 2, mlp_ratio)
+            for j in range(depth)])
+
+    def forward(self, x):
+        for blk in self.blocks:
+            x = blk(x)
+        return x
+
+
+class RSTB(torch.nn.Module):
+    """Residual Swin Transformer block: `depth` layers, a 3x3 conv, the skip (fused into that conv's store)."""
+
+    def __init__(self, dim, depth, num_heads, window_size=8, mlp_ratio=2.):
+        super(RSTB, self).__init__()
+        if depth < 1:
+            raise ValueError("RSTB: depth %r, at least 1 layer" % (depth,))
+        self.residual_group = _SwinLayers(dim, depth, num_heads, window_size, mlp_ratio)
+        self.conv = Conv2d(dim, dim, 3, 1, 1)
+
+    def forward(self, x):
+        if grad_mode(x, *self.parameters()):
+            x, skip = ops.fork(x)   # gradient fan-in summed by srk_axpby
+        else:
+            skip = x
+        return self.conv.run(self.residual_group(x), residual=skip)
 
 
 class PSBlock(_Block):

@@ -134,6 +134,62 @@ class SliceConv2d(torch.nn.Conv2d):
                            "ops.residual_dense_blocks (base_networks.RDB.forward)")
 
 
+class TokenLinear(torch.nn.Linear):
+    """An nn.Linear over the channels of every pixel (SwinIR's qkv, proj, fc1 and fc2: a token is an NHWC pixel): torch's
+    parameter names, [out, in] weight and initialisation, run as a 1x1 convolution through ops.conv2d on the
+    [out, in, 1, 1] view of that weight -- the existing kernels, the existing precision modes, no permutes.  It is not a
+    layers.Conv2d, so optim.PackPlan packs nothing for it; its filter is packed per call.  Under optim.FlatParams the
+    view carries the parameter's slice of the flat gradient buffer, so the weight-gradient kernels accumulate there."""
+
+    def __init__(self, in_features, out_features):
+        super(TokenLinear, self).__init__(in_features, out_features, bias=True)
+        self._cache = _PackCache()
+
+    def _filter(self):
+        w4 = self.weight.view(self.out_features, self.in_features, 1, 1)
+        acc = getattr(self.weight, "_srk_grad", None)
+        if acc is not None:
+            w4._srk_grad = acc.view(self.out_features, self.in_features, 1, 1)
+        return w4
+
+    def run(self, x, act=ACT_NONE, slope=0.0, residual=None):
+        """x, residual: logical [N, C, H, W], channels_last."""
+        cfg = ops.ConvCfg(1, 0, False, 0, act, slope, 0)
+        w4 = self._filter()
+        if grad_mode(x, self.weight, self.bias, residual):
+            return ops.conv2d(x, w4, self.bias, residual, cfg)
+        packed = self._cache.get(w4, self.bias, False, 0)
+        return ops.conv2d_infer(x, w4, self.bias, residual, cfg, None, packed)
+
+    def forward(self, x):
+        return self.run(x)
+
+
+class LayerNorm(torch.nn.LayerNorm):
+    """nn.LayerNorm(C) surface over the channels of a logical [N, C, H, W] channels_last map (= the last axis of its NHWC
+    storage) or the last axis of a [rows, C] tensor, on ops.layer_norm."""
+
+    def __init__(self, num_features, eps=1e-5):
+        super(LayerNorm, self).__init__(num_features, eps=eps)
+
+    def forward(self, x):
+        if x.dim() == 4:
+            y = ops.layer_norm(ops.to_nhwc(x).permute(0, 2, 3, 1), self.weight, self.bias, self.eps)
+            return y.permute(0, 3, 1, 2)
+        return ops.layer_norm(x, self.weight, self.bias, self.eps)
+
+
+class GELU(torch.nn.GELU):
+    """nn.GELU() (the exact erf form) on ops.gelu; a 4-D map is read in its NHWC storage order."""
+
+    def forward(self, x):
+        if self.approximate != "none":
+            raise NotImplementedError("GELU: only the exact erf form is implemented")
+        if x.dim() == 4:
+            return ops.gelu(ops.to_nhwc(x).permute(0, 2, 3, 1)).permute(0, 3, 1, 2)
+        return ops.gelu(x)
+
+
 class ConvTranspose2d(torch.nn.ConvTranspose2d):
     """torch.nn.ConvTranspose2d surface (base_networks.py:77; fsrcnn.py:33)."""
 

@@ -14,9 +14,10 @@ import torch.nn as nn
 
 from . import ops, utils
 from ._lib import ACT_NONE, ACT_RELU
-from .base_networks import (RDB, ConvBlock, DeconvBlock, DenseBlock, PSBlock, ResidualGroup, ResnetBlock,
+from .base_networks import (RDB, RSTB, ConvBlock, DeconvBlock, DenseBlock, PSBlock, ResidualGroup, ResnetBlock,
                             Upsample2xBlock)
-from .layers import Conv2d, ConvTranspose2d, PixelShuffle, PReLU, grad_mode
+from .layers import Conv2d, ConvTranspose2d, LayerNorm, LeakyReLU, PixelShuffle, PReLU, grad_mode
+from ._lib import ACT_LRELU
 
 
 def _training_graph(module, x):
@@ -284,6 +285,122 @@ class RDNNet(nn.Module):
         for m in self.UPNet:
             if isinstance(m, Conv2d):
                 out = m.run(out, ps_r=getattr(m, "_ps_r", 0))
+        return out
+
+
+class _PatchEmbed(nn.Module):
+    """Upstream's `patch_embed` at patch size 1: only its LayerNorm has parameters (`patch_embed.norm.*`)."""
+
+    def __init__(self, dim):
+        super(_PatchEmbed, self).__init__()
+        self.norm = LayerNorm(dim)
+
+    def forward(self, x):
+        return self.norm(x)
+
+
+SWINIR_RGB_MEAN = (0.4488, 0.4371, 0.4040)
+SWINIR_UPSAMPLERS = ("pixelshuffle", "pixelshuffledirect")
+
+
+class SwinIRNet(nn.Module):
+    """SwinIR (Liang et al., ICCVW 2021; not in the reference collection), the classical (`pixelshuffle`) and lightweight
+    (`pixelshuffledirect`) image-SR nets: mean shift for 3 channels, conv_first, patch_embed.norm, `len(depths)` RSTBs
+    (layers.{i}.residual_group.blocks.{j}.*, layers.{i}.conv), norm, conv_after_body under the long skip, the upsampler.
+    Module names follow upstream's network_swinir.py as remembered; they could not be checked against it.  Upstream's
+    `relative_position_index` and `attn_mask` buffers do not exist (the attention kernel computes both), so an upstream
+    checkpoint loads with strict=False.  Not built: stochastic depth (upstream's class default drop_path_rate = 0.1),
+    the absolute position embedding, resi_connection = '3conv', the real-SR 'nearest+conv' upsampler.
+    A token is an NHWC pixel: the map never leaves its layout, the projections are 1x1 convolutions."""
+
+    def __init__(self, num_channels, embed_dim=180, depths=(6, 6, 6, 6, 6, 6), num_heads=6, window_size=8, mlp_ratio=2,
+                 scale_factor=4, upsampler="pixelshuffle"):
+        super(SwinIRNet, self).__init__()
+        if upsampler not in SWINIR_UPSAMPLERS:
+            raise ValueError("SwinIRNet: upsampler %r is not one of %s" % (upsampler, SWINIR_UPSAMPLERS))
+        if upsampler == "pixelshuffle" and scale_factor not in (2, 3, 4, 8):
+            raise ValueError("SwinIRNet: scale_factor %r is not 2, 3, 4 or 8 (pixelshuffle)" % (scale_factor,))
+        if int(scale_factor) < 1:
+            raise ValueError("SwinIRNet: scale_factor %r" % (scale_factor,))
+        depths = tuple(int(d) for d in depths)
+        if not depths or min(depths) < 1:
+            raise ValueError("SwinIRNet: depths %r, at least one RSTB of at least one layer" % (depths,))
+        ops.window_attention_check(embed_dim, num_heads, window_size, window_size // 2, who="SwinIRNet")
+        self.window_size, self.scale_factor, self.upsampler = int(window_size), int(scale_factor), upsampler
+        self.mean = SWINIR_RGB_MEAN if num_channels == 3 else None
+        self.conv_first = Conv2d(num_channels, embed_dim, 3, 1, 1)
+        self.patch_embed = _PatchEmbed(embed_dim)
+        self.layers = nn.ModuleList([RSTB(embed_dim, d, num_heads, window_size, mlp_ratio) for d in depths])
+        self.norm = LayerNorm(embed_dim)
+        self.conv_after_body = Conv2d(embed_dim, embed_dim, 3, 1, 1)
+        if upsampler == "pixelshuffle":
+            num_feat = 64
+            self.conv_before_upsample = nn.Sequential(Conv2d(embed_dim, num_feat, 3, 1, 1), LeakyReLU(inplace=True))
+            up = []
+            if scale_factor == 3:
+                up = [Conv2d(num_feat, 9 * num_feat, 3, 1, 1), PixelShuffle(3)]
+            else:
+                for _ in range(int(math.log2(scale_factor))):
+                    up += [Conv2d(num_feat, 4 * num_feat, 3, 1, 1), PixelShuffle(2)]
+            self.upsample = nn.Sequential(*up)
+            self.conv_last = Conv2d(num_feat, num_channels, 3, 1, 1)
+        else:
+            self.upsample = nn.Sequential(Conv2d(embed_dim, scale_factor ** 2 * num_channels, 3, 1, 1),
+                                          PixelShuffle(scale_factor))
+        for conv, nxt in zip(self.upsample, list(self.upsample)[1:] + [None]):
+            if isinstance(nxt, PixelShuffle):
+                conv._ps_r = int(nxt.upscale_factor)      # the shuffle is fused into this conv's store (optim.PackPlan)
+
+    def weight_init(self, mean=0.0, std=0.02):
+        for m in self.modules():
+            utils.weights_init_normal(m, mean=mean, std=std)
+
+    def check_image_size(self, x):
+        """Training: the LR size must be a multiple of the window.  eval(): reflect padding at the bottom and the right up
+        to the next multiple (plain torch indexing: not the hot path)."""
+        h, w = x.shape[2], x.shape[3]
+        ph, pw = (-h) % self.window_size, (-w) % self.window_size
+        if not (ph or pw):
+            return x
+        if self.training:
+            raise ValueError("SwinIRNet: a %d x %d input is not a multiple of the window %d (training); eval() pads"
+                             % (h, w, self.window_size))
+        if ph >= h or pw >= w:
+            raise ValueError("SwinIRNet: a %d x %d input cannot be reflect-padded to a multiple of the window %d"
+                             % (h, w, self.window_size))
+        if ph:
+            x = torch.cat([x, x[:, :, h - 1 - ph:h - 1].flip(2)], 2)
+        if pw:
+            x = torch.cat([x, x[:, :, :, w - 1 - pw:w - 1].flip(3)], 3)
+        return x
+
+    def forward(self, x):
+        h, w = x.shape[2], x.shape[3]
+        x = self.check_image_size(x)
+        if self.mean is not None:
+            x = ops.channel_affine(x, self.mean, (1.0, 1.0, 1.0))
+        first = self.conv_first(x)
+        training = _training_graph(self, x)
+        if training:
+            first, skip = ops.fork(first)   # gradient fan-in summed by srk_axpby
+        else:
+            skip = first
+        t = self.patch_embed(first)
+        for layer in self.layers:
+            t = layer(t)
+        out = self.conv_after_body.run(self.norm(t), residual=skip)
+        if self.upsampler == "pixelshuffle":
+            out = self.conv_before_upsample[0].run(out, ACT_LRELU, self.conv_before_upsample[1].slope)
+            for m in self.upsample:
+                if isinstance(m, Conv2d):
+                    out = m.run(out, ps_r=m._ps_r)
+            out = self.conv_last(out)
+        else:
+            out = self.upsample[0].run(out, ps_r=self.upsample[0]._ps_r)
+        if self.mean is not None:
+            out = ops.channel_affine(out, tuple(-v for v in self.mean), (1.0, 1.0, 1.0))
+        if out.shape[2] != h * self.scale_factor or out.shape[3] != w * self.scale_factor:
+            out = out[:, :, :h * self.scale_factor, :w * self.scale_factor]
         return out
 
 

@@ -3013,3 +3013,197 @@ def residual_dense_blocks(x, blocks):
         raise ValueError("residual_dense_blocks: G = %d, G0 = %d: at most 64 output channels a convolution" % (g, g0))
     params = [t for b in blocks for t in b]
     return _ResidualDenseBlocks.apply(x, len(blocks), C, grad_enabled_for(x, *params), *params)
+
+
+# ------------------------------------------------------------------------------------------------
+# SwinIR's operators: shifted-window attention, LayerNorm, GELU (csrc/wattn.hip, csrc/swin_pointwise.hip)
+# ------------------------------------------------------------------------------------------------
+WATTN_MAX_HEAD_DIM = 32
+
+
+def window_attention_check(c, heads, window, shift, h=None, w=None, who="window_attention"):
+    """The shapes the kernel covers; anything else is a ValueError that names the number."""
+    if not 2 <= int(window) <= 8:
+        raise ValueError("%s: window %r is not in 2 .. 8 (one lane per token, window^2 <= 64)" % (who, window))
+    if not 0 <= int(shift) < int(window):
+        raise ValueError("%s: shift %r is not in 0 .. window - 1 = %d" % (who, shift, window - 1))
+    if heads < 1 or c % heads:
+        raise ValueError("%s: %r heads do not divide %d channels" % (who, heads, c))
+    if c // heads > WATTN_MAX_HEAD_DIM:
+        raise ValueError("%s: head dimension %d = %d / %d exceeds %d" % (who, c // heads, c, heads, WATTN_MAX_HEAD_DIM))
+    if h is not None and (h % window or w % window):
+        raise ValueError("%s: a %d x %d map is not a multiple of the window %d" % (who, h, w, window))
+
+
+class _WindowAttention(torch.autograd.Function):
+    """softmax(d^-0.5 Q K^T + bias + mask) V per shifted window and head on an NHWC map: one launch forward, two
+    backward; saves qkv, the output and the row log-sum-exp."""
+
+    @staticmethod
+    def forward(ctx, qkv, table, heads, window, shift):
+        lib = _lib.load()
+        require_cuda(qkv, table)
+        n, h, w, c3 = qkv.shape
+        c = c3 // 3
+        qkv = qkv.contiguous()
+        tb = table.detach().contiguous()
+        need_grad = any(ctx.needs_input_grad)
+        out = torch.empty((n, h, w, c), dtype=torch.float32, device=qkv.device)
+        lse = None
+        if need_grad:
+            lse = torch.empty((n * (h // window) * (w // window), heads, 64), dtype=torch.float32, device=qkv.device)
+        check(lib.srk_window_attention_forward(ptr(qkv), ptr(tb), n, h, w, c, heads, window, shift, ptr(out), ptr(lse),
+                                               stream_ptr()), "srk_window_attention_forward")
+        ctx.cfg = (heads, window, shift)
+        ctx.table_ref = table
+        if need_grad:
+            ctx.save_for_backward(qkv, tb, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        qkv, tb, out, lse = ctx.saved_tensors
+        heads, window, shift = ctx.cfg
+        n, h, w, c3 = qkv.shape
+        c = c3 // 3
+        dout = dout.contiguous()      # a strided gradient is copied, never read with the wrong strides
+        dqkv = torch.empty_like(qkv)
+        dtable = ret = ws = None
+        beta, nbytes = 0.0, 0
+        if ctx.needs_input_grad[1]:
+            dtable = getattr(ctx.table_ref, "_srk_grad", None)   # optim.FlatParams: accumulate into the flat buffer
+            if dtable is not None:
+                beta = 1.0
+            else:
+                dtable = ret = torch.empty(tb.shape, dtype=torch.float32, device=qkv.device)
+            nbytes = int(lib.srk_window_attention_workspace(n, h, w, c, heads, window))
+            ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=qkv.device)
+        check(lib.srk_window_attention_backward(ptr(dout), ptr(qkv), ptr(tb), ptr(out), ptr(lse), n, h, w, c, heads, window,
+                                                shift, ptr(dqkv), ptr(dtable), beta, ptr(ws), nbytes, stream_ptr()),
+              "srk_window_attention_backward")
+        return dqkv if ctx.needs_input_grad[0] else None, ret, None, None, None
+
+
+def window_attention(qkv, table, heads, window, shift=0):
+    """Shifted-window self-attention (Swin / SwinIR) on an NHWC map.  qkv [N, H, W, 3C]: the qkv projection with its bias,
+    channels q | k | v, each heads x d; table [(2 window - 1)^2, heads]: the relative position bias.  Returns
+    [N, H, W, C].  The roll by -shift, the window partition, the bias gather, the -100 mask of the shifted windows, the
+    softmax and all their inverses are one kernel; nothing but the result is written.  include/srk.h:
+    srk_window_attention_forward / _backward."""
+    if qkv.dim() != 4 or qkv.shape[3] % 3:
+        raise ValueError("window_attention: qkv must be [N, H, W, 3C], got shape %s" % (tuple(qkv.shape),))
+    heads, window, shift = int(heads), int(window), int(shift)
+    n, h, w, c3 = qkv.shape
+    window_attention_check(c3 // 3, heads, window, shift, h, w)
+    if tuple(table.shape) != ((2 * window - 1) ** 2, heads):
+        raise ValueError("window_attention: table %s, expected (%d, %d) for window %d and %d heads"
+                         % (tuple(table.shape), (2 * window - 1) ** 2, heads, window, heads))
+    return _WindowAttention.apply(qkv, table, heads, window, shift)
+
+
+def _ln_workspace(lib, rows, c, device):
+    nbytes = int(lib.srk_layer_norm_workspace(rows, c))
+    return torch.empty(max(nbytes, 8), dtype=torch.uint8, device=device), nbytes
+
+
+class _LayerNorm(torch.autograd.Function):
+    """LayerNorm over the last axis with gamma and beta; saves x, mean and rstd per row."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps):
+        lib = _lib.load()
+        require_cuda(x, gamma, beta)
+        x = x.contiguous()
+        c = x.shape[-1]
+        rows = x.numel() // c
+        gc, bc = gamma.detach().contiguous(), beta.detach().contiguous()
+        need_grad = any(ctx.needs_input_grad)
+        y = torch.empty_like(x)
+        mean = rstd = None
+        if need_grad:
+            mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+            rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+        check(lib.srk_layer_norm_forward(ptr(x), ptr(gc), ptr(bc), ptr(y), ptr(mean), ptr(rstd), rows, c, eps, stream_ptr()),
+              "srk_layer_norm_forward")
+        ctx.params = (gamma, beta)
+        if need_grad:
+            ctx.save_for_backward(x, gc, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, gc, mean, rstd = ctx.saved_tensors
+        gamma, beta = ctx.params
+        c = x.shape[-1]
+        rows = x.numel() // c
+        dy = dy.contiguous()
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        need = ctx.needs_input_grad[1:3]
+        acc = [getattr(p, "_srk_grad", None) for p in (gamma, beta)]
+        flat = all(a is not None for a in acc)     # optim.FlatParams: accumulate into the flat gradient buffer
+        if flat:
+            outs, a = [g if nd else None for g, nd in zip(acc, need)], 1.0
+        else:
+            outs, a = [torch.empty(c, dtype=torch.float32, device=x.device) if nd else None for nd in need], 0.0
+        ws, nbytes = _ln_workspace(lib, rows, c, x.device) if any(need) else (None, 0)
+        check(lib.srk_layer_norm_backward(ptr(dy), ptr(x), ptr(gc), ptr(mean), ptr(rstd), ptr(dx), ptr(outs[0]),
+                                          ptr(outs[1]), a, rows, c, ptr(ws), nbytes, stream_ptr()),
+              "srk_layer_norm_backward")
+        if flat:
+            outs = [None, None]
+        return dx, outs[0], outs[1], None
+
+
+def layer_norm(x, gamma, beta, eps=1e-5):
+    """nn.LayerNorm(C) over the last axis of a dense [..., C] tensor (an NHWC map or [rows, C]), any C >= 1."""
+    if x.dim() < 1 or gamma.numel() != x.shape[-1] or beta.numel() != x.shape[-1]:
+        raise ValueError("layer_norm: gamma %s and beta %s do not fit the last axis of %s"
+                         % (tuple(gamma.shape), tuple(beta.shape), tuple(x.shape)))
+    return _LayerNorm.apply(x, gamma, beta, float(eps))
+
+
+def layer_norm_stats(x, gamma, beta, eps=1e-5):
+    """(y, mean, rstd) of the forward kernel, without a graph: what the backward is given."""
+    lib = _lib.load()
+    require_cuda(x, gamma, beta)
+    x = x.contiguous()
+    c = x.shape[-1]
+    rows = x.numel() // c
+    y = torch.empty_like(x)
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+    check(lib.srk_layer_norm_forward(ptr(x), ptr(gamma.detach().contiguous()), ptr(beta.detach().contiguous()), ptr(y),
+                                     ptr(mean), ptr(rstd), rows, c, float(eps), stream_ptr()), "srk_layer_norm_forward")
+    return y, mean, rstd
+
+
+class _Gelu(torch.autograd.Function):
+    """x Phi(x), the exact erf form; the backward reads the saved input."""
+
+    @staticmethod
+    def forward(ctx, x):
+        lib = _lib.load()
+        require_cuda(x)
+        x = x.contiguous()      # (a view at an odd offset stays a view: the kernels have a 4-byte form)
+        y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        check(lib.srk_gelu_forward(ptr(x), ptr(y), x.numel(), stream_ptr()), "srk_gelu_forward")
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        x, = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        check(lib.srk_gelu_backward(ptr(dy), ptr(x), ptr(dx), x.numel(), stream_ptr()), "srk_gelu_backward")
+        return dx
+
+
+def gelu(x):
+    """nn.GELU() (approximate='none') on a dense tensor of any shape."""
+    if x.numel() == 0:
+        raise ValueError("gelu: empty tensor")
+    return _Gelu.apply(x)

@@ -1038,5 +1038,33 @@ class RDN(_Trainer):
         apply_lr_decay("edsr", epoch, opt)
 
 
+class SwinIR(_Trainer):
+    """SwinIR (models.SwinIRNet; not in the reference collection) behind the common trainer: L1 and Adam as EDSR, EDSR's
+    learning-rate decay; `--swinir_dim`, `--swinir_depths`, `--swinir_heads`, `--swinir_window`, `--swinir_mlp_ratio`,
+    `--swinir_upsampler`.  The window grid and the border mask of its WindowAttention belong to the whole picture, so
+    tiling is refused here (args.tile) and by tiling.net_geometry (test_single(img, tile=...))."""
+    kind = "swinir"
+
+    def __init__(self, args):
+        if getattr(args, "tile", None) is not None:
+            raise ValueError("tile: SwinIR's WindowAttention partitions the whole image into windows and cannot be tiled "
+                             "(main.py --tile)")
+        super(SwinIR, self).__init__(args)
+        self.dim = int(getattr(args, "swinir_dim", None) or 180)
+        depths = getattr(args, "swinir_depths", None) or (6, 6, 6, 6, 6, 6)
+        self.depths = tuple(int(d) for d in (depths.split(",") if isinstance(depths, str) else depths))
+        self.heads = int(getattr(args, "swinir_heads", None) or 6)
+        self.window = int(getattr(args, "swinir_window", None) or 8)
+        self.mlp_ratio = float(getattr(args, "swinir_mlp_ratio", None) or 2)
+        self.upsampler = getattr(args, "swinir_upsampler", None) or "pixelshuffle"
+
+    def build_model(self):
+        return models.SwinIRNet(self.num_channels, self.dim, self.depths, self.heads, self.window, self.mlp_ratio,
+                                self.scale_factor, self.upsampler)
+
+    def lr_decay(self, epoch, opt):
+        apply_lr_decay("edsr", epoch, opt)
+
+
 TRAINERS = {"SRCNN": SRCNN, "VDSR": VDSR, "ESPCN": ESPCN, "FSRCNN": FSRCNN, "SRGAN": SRGAN, "LapSRN": LapSRN, "EDSR": EDSR,
-            "DRCN": DRCN, "RCAN": RCAN, "RDN": RDN}
+            "DRCN": DRCN, "RCAN": RCAN, "RDN": RDN, "SwinIR": SwinIR}

@@ -6,7 +6,8 @@ tile_stitch / tile_stitch_u8); the trainers drive both from sr_trainers._Trainer
 The reference's eight nets are convolutional with a bounded receptive field and treat both axes alike, so everything
 here is one-dimensional and applied to rows and columns independently.  The ninth, RCAN, is not: its channel attention
 pools over the whole picture, the walk says so (as it does for instance norm) and the picture runs in one pass.  The
-tenth, RDN, is convolutional again: a residual dense block is the cone of its C chained 3x3 convs.
+tenth, RDN, is convolutional again: a residual dense block is the cone of its C chained 3x3 convs.  The eleventh, SwinIR,
+cuts the whole picture into windows and masks by its borders: refused like RCAN.
 
 Geometry.  Along one axis, a feature map of a net is described against the net's INPUT by three integers (scale, lo, hi):
 map pixel o depends on the input pixels
@@ -179,6 +180,15 @@ def _walk(g, m, path):
         return _walk(g, m.upsample, path + ".upsample")
     if isinstance(m, B.ChannelAttention):   # its gate is a function of every pixel of the picture
         raise ValueError("%s: ChannelAttention depends on the whole image and cannot be tiled" % path)
+    if isinstance(m, B.WindowAttention):   # the window grid and the border mask belong to the whole picture
+        raise ValueError("%s: WindowAttention partitions the whole image into windows and cannot be tiled" % path)
+    if isinstance(m, B.SwinTransformerLayer):
+        return _union(_walk(g, m.attn, path + ".attn"), g, path)
+    if isinstance(m, B.RSTB):
+        out = g
+        for name, blk in m.residual_group.blocks.named_children():
+            out = _walk(out, blk, "%s.residual_group.blocks.%s" % (path, name))
+        return _union(_walk(out, m.conv, path + ".conv"), g, path)
     if isinstance(m, B.RCAB):   # x + ca(conv2(relu(conv1(x))))
         out = _conv(_conv(g, m.conv1, path + ".conv1"), m.conv2, path + ".conv2")
         return _union(_walk(out, m.ca, path + ".ca"), g, path)
@@ -240,6 +250,12 @@ def net_geometry(model):
         out = _walk(_walk(head, model.residual_groups, "residual_groups"), model.mid_conv, "mid_conv")
         out = _union(out, head, "mid_conv")
         return _walk(_walk(out, model.upscale, "upscale"), model.output_conv, "output_conv")
+    if isinstance(model, M.SwinIRNet):   # raises at the first window attention
+        head = _walk(g, model.conv_first, "conv_first")
+        out = head
+        for name, layer in model.layers.named_children():
+            out = _walk(out, layer, "layers.%s" % name)
+        return out
     if isinstance(model, M.RDNNet):
         head = _walk(g, model.SFENet1, "SFENet1")
         out = _walk(head, model.SFENet2, "SFENet2")

@@ -539,7 +539,7 @@ class GraphedStep(GraphedSegments):
 
 def build(kind, model, lr, dp_group=None, use_dp=False, ssim_weight=0.0, ema_decay=0.0, fft_weight=0.0, fft_norm="backward",
           lpips_weight=0.0, lpips_net=None):
-    """(flat, optimizer, dp, step) for one of 'srcnn' | 'fsrcnn' | 'vdsr' | 'edsr' | 'lapsrn' | 'espcn' | 'rcan' | 'rdn': the one place that
+    """(flat, optimizer, dp, step) for one of 'srcnn' | 'fsrcnn' | 'vdsr' | 'edsr' | 'lapsrn' | 'espcn' | 'rcan' | 'rdn' | 'swinir': the one place that
     names the loss and the clip a kind trains with.  ssim_weight a in (0, 1]: (1 - a) * that loss + a * (1 - SSIM)
     (mixed_loss); 0: the step as it is without the argument.  fft_weight w > 0 adds w * ops.fft_loss(pred, target, fft_norm)
     to that (mixed_loss); 0: the step as it is without the argument.  lpips_weight v > 0 adds v * ops.lpips(pred, target,
@@ -558,7 +558,7 @@ def build(kind, model, lr, dp_group=None, use_dp=False, ssim_weight=0.0, ema_dec
         dp.broadcast_params()
         opt.ema_reset()      # (the shadow starts as a copy of the parameters every rank now has)
     fft = dict(fft_weight=fft_weight, fft_norm=fft_norm, lpips_weight=lpips_weight, lpips_net=lpips_net)
-    if kind in ("edsr", "rcan", "rdn"):
+    if kind in ("edsr", "rcan", "rdn", "swinir"):
         step = l1_step(model, opt, dp, ssim_weight=ssim_weight, **fft)
     elif kind == "lapsrn":
         step = lapsrn_step(model, opt, dp, ssim_weight=ssim_weight, **fft)
