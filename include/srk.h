@@ -970,6 +970,56 @@ int srk_dense_conv_host(const srk_dense_desc* d, int direction, const float* A, 
                         const float* bias, const float* residual, float* y, const float* dy, const float* add, float* dA,
                         float betaA, float* dB, float betaB, float* dW, float* db, float beta);
 
+/* ---- Slice convolution with a scaled output and two scaled skips: the RRDB epilogues (csrc/dense.hip) ----
+ * (Additive again: new entry points and one new struct, srk_version(), srk_dense_desc and every srk_dense_* above unchanged.)
+ * The convolution of srk_dense_desc with a caller-sized srk_dense_epilogue `e` (NULL: s = r1 = a1 = 1, no R2):
+ *   forward          y = s * act(conv([A | B]; W) + bias) + r1 * R1 + r2 * R2
+ *   backward_data    g = s * dy * act'(y_saved);  dA = betaA * dA + (conv^T(g))[:CA] + a1 * add;  dB as srk_dense_conv_backward_data
+ *   backward_weight  the same g: dW = beta * dW + sum_p [A | B]^T g;  db = beta * db + sum_p g
+ * R1 (pixel stride desc.ldR) and R2 (pixel stride e->ldR2) are optional slices of Cout channels; either may be NULL.
+ * With an activation, y_saved must carry the sign of the activation's own output: s > 0 and no skip (the RRDB's scaled
+ * convolutions have no activation).  s = r1 = 1 with R2 = NULL gives the bits of srk_dense_conv_forward; s = a1 = 1 those of
+ * srk_dense_conv_backward_data / _backward_weight.  One launch each (backward_weight: two), the launch geometry, the
+ * workspace and the planner of the plain entry points; 16-byte accesses in every epilogue; no atomics.
+ * SRK_ERR_BAD_ARG: e->struct_size smaller than the struct, a scale that is not finite.
+ * srk_dense_conv_host_ex: srk_dense_conv_host plus R2 and the epilogue, fp64 accumulation, the same addressing. */
+typedef struct srk_dense_epilogue {
+  uint32_t struct_size;      /* sizeof(srk_dense_epilogue) of the caller */
+  float s;                   /* forward: scale of act(conv + bias); both gradients: scale of dy */
+  float r1, r2;              /* forward: scales of R1 and R2 */
+  int32_t ldR2;              /* forward: pixel stride of R2, in floats */
+  float a1;                  /* backward_data: scale of `add` */
+} srk_dense_epilogue;
+int srk_dense_conv_forward_ex(const srk_dense_desc* d, const float* A, const float* B, const float* W, const float* bias,
+                              const float* R1, const float* R2, const srk_dense_epilogue* e, float* y, void* stream);
+int srk_dense_conv_backward_data_ex(const srk_dense_desc* d, const float* dy, const float* y_saved, const float* W, float* dA,
+                                    float betaA, float* dB, float betaB, const float* add, const srk_dense_epilogue* e,
+                                    void* stream);
+int srk_dense_conv_backward_weight_ex(const srk_dense_desc* d, const float* A, const float* B, const float* dy,
+                                      const float* y_saved, float* dW, float* db, float beta, const srk_dense_epilogue* e,
+                                      void* workspace, size_t workspace_bytes, void* stream);
+int srk_dense_conv_host_ex(const srk_dense_desc* d, int direction, const float* A, const float* B, const float* W,
+                           const float* bias, const float* R1, const float* R2, const srk_dense_epilogue* e, float* y,
+                           const float* dy, const float* add, float* dA, float betaA, float* dB, float betaB, float* dW,
+                           float* db, float beta);
+
+/* ---- Relativistic average GAN loss: ESRGAN's adversarial term (csrc/ragan.hip, csrc/ragan_common.h) -------------------
+ * (Additive again: new entry points only, srk_version() and everything existing unchanged.)
+ * real, fake: B discriminator LOGITS each ([B] or [B, 1], dense).  mr = mean(real), mf = mean(fake), a_i = real_i - mf,
+ * b_i = fake_i - mr, sp(x) = max(x, 0) + log1p(exp(-|x|)):
+ *   discriminator (for_generator == 0)   L = 1/(2B) sum_i [sp(-a_i) + sp(b_i)]
+ *   generator     (for_generator != 0)   L = 1/(2B) sum_i [sp(a_i) + sp(-b_i)]
+ * The gradient is the full derivative, the two means included: with A_i = dL/da_i and Bv_i = dL/db_i,
+ *   d_real_i = grad_scale (A_i - mean(Bv))      d_fake_i = grad_scale (Bv_i - mean(A)).
+ * Everything in double up to the fp32 stores; sums in a fixed order; one launch of one block; no atomics; any B >= 1.
+ * d_real or d_fake may be NULL (the generator's step detaches the real logits).  `workspace` is not used and may be NULL
+ * (the argument keeps the calling convention of the other loss kernels).
+ * srk_ragan_loss_host: the same formulas (ragan_common.h) on host pointers, results in double; d_real / d_fake may be NULL. */
+int srk_ragan_loss_forward_backward(const float* real, const float* fake, int B, int for_generator, float grad_scale,
+                                    float* loss, float* d_real, float* d_fake, void* workspace, void* stream);
+int srk_ragan_loss_host(const float* real, const float* fake, int B, int for_generator, double grad_scale, double* loss,
+                        double* d_real, double* d_fake);
+
 /* ---- Shifted-window self-attention: SwinIR's attention operator (csrc/wattn.hip, csrc/wattn_common.h) ----------------
  * (Additive again: new entry points only, srk_version() and everything existing unchanged.)
  * qkv dense NHWC [N][H][W][3C], the qkv projection with its bias applied, channels q | k | v, each split heads x d

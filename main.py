@@ -34,6 +34,12 @@ works with it, --tile included.
 --model_name SwinIR (not in the reference: shifted-window attention, models.SwinIRNet) with --swinir_dim, --swinir_depths,
 --swinir_heads, --swinir_window, --swinir_mlp_ratio and --swinir_upsampler {pixelshuffle,pixelshuffledirect} (defaults: the
 classical net, 180 channels, 6 x 6 layers, 6 heads, window 8, ratio 2); every flag of the common trainer but --tile.
+--model_name ESRGAN (not in the reference: the RRDB generator, models.RRDBNet, on SRGAN's two-phase trainer) with
+--rrdb_blocks NB and --rrdb_growth GC (defaults 23, 32), --pixel_weight, --vgg_loss_weight (default 1.0 for this model) and
+--gan_weight (defaults 1e-2, 5e-3): --epoch_pretrain epochs of L1, then the adversarial phase on the relativistic average
+GAN loss, which needs --vgg_weights PATH (conv5_4 features before the ReLU).  x4, RGB, one GPU; no --tile, --ssim_weight,
+--fft_weight or --lpips_weight.  --net_interp A (with --test_only / --test_single) evaluates the blend
+(1 - A) * pre-trained + A * adversarial generator, 0 <= A <= 1.
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N main.py ..."""
 import argparse
 import os
@@ -130,6 +136,28 @@ def _lpips_weight(text):
         v = float('nan')
     if not 0.0 <= v < float('inf'):
         raise argparse.ArgumentTypeError("--lpips_weight takes a number >= 0, got %r" % (text,))
+    return v
+
+
+def _net_interp(text):
+    """--net_interp: a number in [0, 1] (NaN fails both comparisons)."""
+    try:
+        v = float(text)
+    except ValueError:
+        v = float('nan')
+    if not 0.0 <= v <= 1.0:
+        raise argparse.ArgumentTypeError("--net_interp takes a number in [0, 1], got %r" % (text,))
+    return v
+
+
+def _loss_weight(text):
+    """--gan_weight / --pixel_weight: a finite number >= 0."""
+    try:
+        v = float(text)
+    except ValueError:
+        v = float('nan')
+    if not 0.0 <= v < float('inf'):
+        raise argparse.ArgumentTypeError("a number >= 0 is expected, got %r" % (text,))
     return v
 
 
@@ -230,7 +258,8 @@ def _jpeg_prob(text):
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="MI355X-native SR collection (reference-compatible CLI)")
     p.add_argument('--model_name', type=str, default='SRGAN',
-                   choices=['SRCNN', 'VDSR', 'ESPCN', 'FSRCNN', 'SRGAN', 'LapSRN', 'EDSR', 'DRCN', 'RCAN', 'RDN', 'SwinIR'],
+                   choices=['SRCNN', 'VDSR', 'ESPCN', 'FSRCNN', 'SRGAN', 'LapSRN', 'EDSR', 'DRCN', 'RCAN', 'RDN', 'SwinIR',
+                            'ESRGAN'],
                    help='The type of model')
     p.add_argument('--data_dir', type=str, default='../Data')
     p.add_argument('--train_dataset', type=_names, default=['DIV2K'], help='The name(s) of the training dataset, comma-separated')
@@ -295,8 +324,9 @@ def parse_args(argv=None):
     p.add_argument('--perceptual', action='store_true',
                    help='SRGAN: the VGG feature term trains the generator (ops.perceptual_loss; the reference detaches it). '
                         'Needs --vgg_weights and --num_channels 3')
-    p.add_argument('--vgg_loss_weight', type=_non_negative, default=6e-3, metavar='W',
-                   help='SRGAN: weight of the VGG feature term in the G loss (default 6e-3, srgan.py:306); W >= 0')
+    p.add_argument('--vgg_loss_weight', type=_non_negative, default=None, metavar='W',
+                   help='SRGAN: weight of the VGG feature term in the G loss (default 6e-3, srgan.py:306); W >= 0.  '
+                        'ESRGAN: default 1.0')
     p.add_argument('--resume', type=str, nargs='?', const='auto', default=None, metavar='PATH',
                    help='continue training from a training-state file (weights, optimizer state, learning rates, epoch, '
                         'loss history, random generators): PATH, or without one the file this run writes, '
@@ -359,7 +389,47 @@ def parse_args(argv=None):
                    help='SwinIR: hidden channels of the MLP over the embedding channels (default 2)')
     p.add_argument('--swinir_upsampler', type=str, default='pixelshuffle', choices=['pixelshuffle', 'pixelshuffledirect'],
                    help='SwinIR: the classical (pixelshuffle) or the lightweight (pixelshuffledirect) reconstruction')
+    p.add_argument('--rrdb_blocks', type=_positive, default=23, metavar='NB',
+                   help='ESRGAN: residual-in-residual dense blocks of the generator (default 23)')
+    p.add_argument('--rrdb_growth', type=_positive, default=32, metavar='GC',
+                   help='ESRGAN: growth channels of the dense blocks: 16, 32, 48 or 64 (default 32)')
+    p.add_argument('--gan_weight', type=_loss_weight, default=5e-3, metavar='W',
+                   help='ESRGAN: weight of the relativistic average GAN term in the G loss (default 5e-3)')
+    p.add_argument('--pixel_weight', type=_loss_weight, default=1e-2, metavar='W',
+                   help='ESRGAN: weight of the L1 pixel term in the G loss of the adversarial phase (default 1e-2)')
+    p.add_argument('--net_interp', type=_net_interp, default=None, metavar='A',
+                   help='ESRGAN, with --test_only / --test_single: evaluate (1 - A) * the pre-trained generator + A * the '
+                        'adversarially trained one (network interpolation of the ESRGAN paper); A in [0, 1]')
     args = p.parse_args(argv)
+    esrgan = args.model_name == 'ESRGAN'
+    if args.vgg_loss_weight is None:
+        args.vgg_loss_weight = 1.0 if esrgan else 6e-3
+    if esrgan:
+        if args.scale_factor != 4:
+            p.error('--scale_factor %d: RRDBNet upsamples by 4 only' % args.scale_factor)
+        if args.tile is not None:
+            p.error('--tile: the RRDB trunk reaches about 350 LR pixels to each side (23 blocks), a tile would be mostly '
+                    'halo; ESRGAN\'s pictures run in one pass (drop --tile)')
+        if args.rrdb_growth % 16 or args.rrdb_growth > 64:
+            p.error('--rrdb_growth %d: the slice convolutions write 16, 32, 48 or 64 channels' % args.rrdb_growth)
+        if args.num_channels != 3:
+            p.error('--num_channels %d: ESRGAN\'s VGG feature term reads RGB, use --num_channels 3' % args.num_channels)
+        if args.perceptual:
+            p.error('--perceptual: ESRGAN\'s feature term always trains the generator (drop --perceptual)')
+        if not args.vgg_weights and not (args.test_only or args.test_single):
+            p.error('--vgg_weights PATH is required: ESRGAN\'s adversarial phase trains on VGG19 conv5_4 features (a '
+                    'torchvision vgg19 state_dict file)')
+        for flag in ('ssim_weight', 'fft_weight', 'lpips_weight'):
+            if getattr(args, flag) > 0:
+                p.error('--%s %g: ESRGAN\'s adversarial phase has its own three terms (--pixel_weight, --vgg_loss_weight, '
+                        '--gan_weight); use --%s 0' % (flag, getattr(args, flag), flag))
+        if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+            p.error('ESRGAN trains on one GPU (a world size of %s): launch main.py without torch.distributed.run'
+                    % os.environ['WORLD_SIZE'])
+    if args.net_interp is not None and not esrgan:
+        p.error('--net_interp: only ESRGAN has a pre-trained and an adversarial generator to blend, not %s' % args.model_name)
+    if args.net_interp is not None and not (args.test_only or args.test_single):
+        p.error('--net_interp blends two finished checkpoints: it goes with --test_only or --test_single')
     if args.model_name == 'SwinIR':
         if args.tile is not None:
             p.error('--tile: SwinIR\'s WindowAttention partitions the whole image into windows, its pictures run in one '
@@ -408,7 +478,7 @@ def parse_args(argv=None):
                 'parameter buffer); use --ema_decay 0 or another model' % args.ema_decay)
     if args.resume and args.test_only:
         p.error('--resume continues a training run; --test_only does not train')
-    if (args.perceptual or args.vgg_weights) and args.model_name != 'SRGAN':
+    if (args.perceptual or args.vgg_weights) and args.model_name not in ('SRGAN', 'ESRGAN'):
         p.error('%s: only SRGAN has a VGG feature term, not %s'
                 % ('--perceptual' if args.perceptual else '--vgg_weights', args.model_name))
     if args.perceptual and not args.vgg_weights:

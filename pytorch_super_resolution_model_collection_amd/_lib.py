@@ -84,6 +84,16 @@ class DenseDesc(ctypes.Structure):
                 + [("slope", c_float), ("terms", ctypes.c_int32)])
 
 
+class DenseEpilogue(_Sized):
+    """struct srk_dense_epilogue: the scaled output and the scaled skips of the srk_dense_conv_*_ex entry points"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("s", c_float), ("r1", c_float), ("r2", c_float), ("ldR2", ctypes.c_int32),
+                ("a1", c_float)]
+
+    def __init__(self, s=1.0, r1=1.0, r2=0.0, ldR2=0, a1=1.0):
+        super().__init__()
+        self.s, self.r1, self.r2, self.ldR2, self.a1 = float(s), float(r1), float(r2), int(ldR2), float(a1)
+
+
 class DensePlan(_Sized):
     """struct srk_dense_plan (srk_dense_conv_plan)"""
     _fields_ = [("struct_size", ctypes.c_uint32), ("pix_tiles", ctypes.c_int32), ("splits", ctypes.c_int32),
@@ -278,6 +288,15 @@ _PROTOTYPES = {
     "srk_dense_conv_backward_weight": (c_int, [ctypes.POINTER(DenseDesc)] + [c_f] * 6 + [c_float, c_vp, c_size, c_vp]),
     "srk_dense_conv_host": (c_int, [ctypes.POINTER(DenseDesc), c_int] + [c_vp] * 9 + [c_float, c_vp, c_float, c_vp, c_vp,
                                                                                      c_float]),
+    "srk_dense_conv_forward_ex": (c_int, [ctypes.POINTER(DenseDesc)] + [c_f] * 6 + [ctypes.POINTER(DenseEpilogue), c_f, c_vp]),
+    "srk_dense_conv_backward_data_ex": (c_int, [ctypes.POINTER(DenseDesc)] + [c_f] * 4 + [c_float, c_f, c_float, c_f,
+                                                                                         ctypes.POINTER(DenseEpilogue), c_vp]),
+    "srk_dense_conv_backward_weight_ex": (c_int, [ctypes.POINTER(DenseDesc)] + [c_f] * 6 + [c_float, ctypes.POINTER(DenseEpilogue),
+                                                                                           c_vp, c_size, c_vp]),
+    "srk_dense_conv_host_ex": (c_int, [ctypes.POINTER(DenseDesc), c_int] + [c_vp] * 6 + [ctypes.POINTER(DenseEpilogue)]
+                               + [c_vp] * 4 + [c_float, c_vp, c_float, c_vp, c_vp, c_float]),
+    "srk_ragan_loss_forward_backward": (c_int, [c_f, c_f, c_int, c_int, c_float, c_f, c_f, c_f, c_vp, c_vp]),
+    "srk_ragan_loss_host": (c_int, [c_vp, c_vp, c_int, c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_double), c_vp, c_vp]),
     "srk_window_attention_workspace": (c_size, [c_int] * 6),
     "srk_window_attention_forward": (c_int, [c_f, c_f] + [c_int] * 7 + [c_f, c_f, c_vp]),
     "srk_window_attention_backward": (c_int, [c_f] * 5 + [c_int] * 7 + [c_f, c_f, c_float, c_vp, c_size, c_vp]),

@@ -272,6 +272,55 @@ class RDB(torch.nn.Module):
         return ops.residual_dense_blocks(x, [self.block_params()])
 
 
+class _ResidualDenseBlock5(torch.nn.Module):
+    """One of the three dense blocks of an RRDB: conv1..conv4 (growth, LeakyReLU 0.2) and conv5 (back to the trunk width),
+    all 3x3.  Parameter holder only -- the arithmetic is ops.rrdb_trunk."""
+
+    def __init__(self, nf, gc):
+        super(_ResidualDenseBlock5, self).__init__()
+        for c in range(4):
+            setattr(self, "conv%d" % (c + 1), SliceConv2d(nf + c * gc, gc, 3))
+        self.conv5 = SliceConv2d(nf + 4 * gc, nf, 3)
+
+    def block_params(self):
+        out = []
+        for c in range(5):
+            m = getattr(self, "conv%d" % (c + 1))
+            out += [m.weight, m.bias]
+        return tuple(out)
+
+    def forward(self, x):
+        raise RuntimeError("a dense block of an RRDB runs inside ops.rrdb_trunk (base_networks.RRDB.forward)")
+
+
+class RRDB(torch.nn.Module):
+    """Residual-in-residual dense block of ESRGAN (Wang et al., ECCV-W 2018): three dense blocks of five 3x3 convs, each
+    v = res_scale * conv5(dense(u)) + u, and the outer out = res_scale * v3 + x.  Parameter names as in BasicSR's
+    RRDBNet: rdb{1,2,3}.conv{1..5}.{weight,bias}.  Nothing is concatenated and no scaling or addition is a launch of its
+    own: ops.rrdb_trunk runs the 15 convs on channel slices with the scales and both skips in the conv5 epilogues;
+    models.RRDBNet hands all its blocks to one call, this forward runs a block alone."""
+
+    def __init__(self, nf, gc=32, res_scale=0.2):
+        super(RRDB, self).__init__()
+        for name, v in (("nf", nf), ("gc", gc)):
+            if v < 16 or v % 16:
+                raise ValueError("RRDB: %s = %r is not a positive multiple of 16 (the slice convolutions' channel tile)"
+                                 % (name, v))
+            if v > 64:
+                raise ValueError("RRDB: %s = %r: a slice convolution writes at most 64 channels" % (name, v))
+        self.nf, self.gc, self.res_scale = nf, gc, float(res_scale)
+        self.rdb1 = _ResidualDenseBlock5(nf, gc)
+        self.rdb2 = _ResidualDenseBlock5(nf, gc)
+        self.rdb3 = _ResidualDenseBlock5(nf, gc)
+
+    def block_params(self):
+        """The three dense blocks' (w1, b1, ..., w5, b5), as ops.rrdb_trunk takes an RRDB."""
+        return (self.rdb1.block_params(), self.rdb2.block_params(), self.rdb3.block_params())
+
+    def forward(self, x):
+        return ops.rrdb_trunk(x, [self.block_params()], self.res_scale)
+
+
 class _RDBConv(torch.nn.Module):
     """One growth layer of an RDB; `conv` = Sequential(conv 3x3, ReLU) as in the official net, hence the key conv.0."""
 

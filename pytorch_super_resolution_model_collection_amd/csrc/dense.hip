@@ -6,6 +6,8 @@
 //   data gradient    k_dense_dgrad<NP, PT>   one block = 64 input channels (grid.y walks [A | B]) x 4 waves of PT pixel tiles
 //   weight gradient  k_dense_wgrad<NP>       one wave = 16 input channels x one tap x one pixel range -> partials
 //                    k_dense_wreduce         the ranges added in index order, beta applied: dW and db
+//   k_dense_fwd_ex / k_dense_dgrad_ex / k_dense_wgrad_ex: the same three bodies (dense_*_body<.., EX = true>) with the scaled
+//                    output and the two scaled skips of srk_dense_epilogue -- the RRDB epilogues of ESRGAN, DESIGN.md 30
 // All three products are v_mfma_f32_16x16x32_bf16 on split8n<NP> planes (bf16_frag.h): NP = 2 planes and three products
 // (terms = 3), or NP = 3 planes and six (terms = 6), smallest products first as in k_conv_bfd.  Operand maps: A[row = lane &
 // 15][k = 8 (lane >> 4) + j], B[k][col = lane & 15], D[row = 4 (lane >> 4) + reg][col = lane & 15].  The forward and the data
@@ -22,6 +24,13 @@
 #include "srk_common.h"
 
 namespace srk {
+
+// srk_dense_epilogue as the _ex kernels take it
+struct DenseEpi {
+  float s = 1.f, r1 = 1.f, r2 = 0.f, a1 = 1.f;
+  const float* R2 = nullptr;
+  int ldR2 = 0;
+};
 
 template <int NP>
 __device__ __forceinline__ f32x4 dense_mma(const uint4 (&a)[NP], const uint4 (&b)[NP], f32x4 c) {
@@ -65,10 +74,11 @@ constexpr int kDenseDgPitch = 64 * 9 + 1;           // floats of one output chan
 
 // One block = ONE tile of 16 output channels x four pixel groups, one a wave, of PT tiles of 16 pixels.  Per chunk of 32
 // input channels the block stages W[16 oc][32 ic][K K] once; every wave then walks the taps.
-template <int NP, int PT>
-__global__ __launch_bounds__(256) void k_dense_fwd(srk_dense_desc d, const float* A, const float* B, const float* Wt,
-                                                   const float* bias, const float* res, float* y, int P) {
-  __shared__ float sw[16 * kDenseFwdPitch];
+// The body is shared by k_dense_fwd and k_dense_fwd_ex (EX: the scaled output and the two scaled skips of DenseEpi).
+template <int NP, int PT, bool EX>
+__device__ __forceinline__ void dense_fwd_body(const srk_dense_desc& d, const float* A, const float* B, const float* Wt,
+                                               const float* bias, const float* res, float* y, int P, const DenseEpi& e,
+                                               float* sw) {
   const int lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
   const int OT = d.Cout >> 4;
   const int o = blockIdx.x % OT;
@@ -131,19 +141,40 @@ __global__ __launch_bounds__(256) void k_dense_fwd(srk_dense_desc d, const float
     f32x4 v = acc[t] + bv;
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = act_apply(v[e], d.act, d.slope);
-    if (res) v += *reinterpret_cast<const f32x4*>(res + (size_t)p * d.ldR + oc);
+    if constexpr (EX) {
+      v *= e.s;
+      if (res) v += e.r1 * *reinterpret_cast<const f32x4*>(res + (size_t)p * d.ldR + oc);
+      if (e.R2) v += e.r2 * *reinterpret_cast<const f32x4*>(e.R2 + (size_t)p * e.ldR2 + oc);
+    } else {
+      if (res) v += *reinterpret_cast<const f32x4*>(res + (size_t)p * d.ldR + oc);
+    }
     *reinterpret_cast<f32x4*>(y + (size_t)p * d.ldY + oc) = v;
   }
+}
+
+template <int NP, int PT>
+__global__ __launch_bounds__(256) void k_dense_fwd(srk_dense_desc d, const float* A, const float* B, const float* Wt,
+                                                   const float* bias, const float* res, float* y, int P) {
+  __shared__ float sw[16 * kDenseFwdPitch];
+  dense_fwd_body<NP, PT, false>(d, A, B, Wt, bias, res, y, P, DenseEpi{}, sw);
+}
+
+template <int NP, int PT>
+__global__ __launch_bounds__(256) void k_dense_fwd_ex(srk_dense_desc d, const float* A, const float* B, const float* Wt,
+                                                      const float* bias, const float* res, float* y, int P, DenseEpi e) {
+  __shared__ float sw[16 * kDenseFwdPitch];
+  dense_fwd_body<NP, PT, true>(d, A, B, Wt, bias, res, y, P, e, sw);
 }
 
 // dX[p][ic] = sum over taps, oc of g[p - (tap - pad)][oc] * W[oc][ic][tap].  One block = up to four tiles of 16 input
 // channels (blockIdx.y: which 64 channels of [A | B]) x four pixel groups, one a wave, so a g fragment -- two slices read
 // and a mask -- serves four products.  Per chunk of 32 output channels the block stages W[32 oc][64 ic][K K] (dynamic LDS,
 // 32 rows of kDenseDgPitch floats) once; every wave then walks the taps.
-template <int NP, int PT>
-__global__ __launch_bounds__(256) void k_dense_dgrad(srk_dense_desc d, const float* dy, const float* ys, const float* Wt,
-                                                     float* dA, float betaA, float* dB, float betaB, const float* add, int P) {
-  extern __shared__ float sdw[];
+// EX (k_dense_dgrad_ex): g is scaled by e.s where it is read and `add` by e.a1.
+template <int NP, int PT, bool EX>
+__device__ __forceinline__ void dense_dgrad_body(const srk_dense_desc& d, const float* dy, const float* ys, const float* Wt,
+                                                 float* dA, float betaA, float* dB, float betaB, const float* add, int P,
+                                                 const DenseEpi& e, float* sdw) {
   const int lane = threadIdx.x & 63, col = lane & 15, q = lane >> 4;
   const int64_t p64 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * (PT * kDensePixTile);
   const bool alive = p64 < P;
@@ -201,6 +232,10 @@ __global__ __launch_bounds__(256) void k_dense_dgrad(srk_dense_desc d, const flo
 #pragma unroll
             for (int j = 0; j < 8; ++j) f[j] = dense_mask(d.act, d.slope, f[j], m[j]);
           }
+          if constexpr (EX) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f[j] *= e.s;
+          }
         }
         split8n<NP>(f, gb[t]);
       }
@@ -227,7 +262,10 @@ __global__ __launch_bounds__(256) void k_dense_dgrad(srk_dense_desc d, const flo
         const int p = p0 + t * kDensePixTile + col;
         if (p >= P) continue;
         f32x4 v = acc[o][t];
-        if (inA && add) v += *reinterpret_cast<const f32x4*>(add + (size_t)p * d.ldAdd + ic);
+        if (inA && add) {
+          const f32x4 av = *reinterpret_cast<const f32x4*>(add + (size_t)p * d.ldAdd + ic);
+          if constexpr (EX) v += e.a1 * av; else v += av;
+        }
         f32x4* out = reinterpret_cast<f32x4*>(dst + (size_t)p * ld + off);
         if (beta != 0.f) v += *out;   // (beta == 0: the destination may hold anything)
         *out = v;
@@ -235,13 +273,29 @@ __global__ __launch_bounds__(256) void k_dense_dgrad(srk_dense_desc d, const flo
     }
 }
 
+template <int NP, int PT>
+__global__ __launch_bounds__(256) void k_dense_dgrad(srk_dense_desc d, const float* dy, const float* ys, const float* Wt,
+                                                     float* dA, float betaA, float* dB, float betaB, const float* add, int P) {
+  extern __shared__ float sdw[];
+  dense_dgrad_body<NP, PT, false>(d, dy, ys, Wt, dA, betaA, dB, betaB, add, P, DenseEpi{}, sdw);
+}
+
+template <int NP, int PT>
+__global__ __launch_bounds__(256) void k_dense_dgrad_ex(srk_dense_desc d, const float* dy, const float* ys, const float* Wt,
+                                                        float* dA, float betaA, float* dB, float betaB, const float* add,
+                                                        int P, DenseEpi e) {
+  extern __shared__ float sdw[];
+  dense_dgrad_body<NP, PT, true>(d, dy, ys, Wt, dA, betaA, dB, betaB, add, P, e, sdw);
+}
+
 // partial[split][oc][ic][tap] = sum over the range's pixels of g[p][oc] * X[p + tap - pad][ic]; the (tile 0, tap 0) wave of
 // a range also leaves sum_p g[p][oc] (a product with a plane of ones) behind the range's dW partials.
 // blockIdx.x = (input-channel tile) * K * K + tap, blockIdx.y = range.  The next 32 pixels' raw operands are requested
 // before this chunk's MFMAs.
-template <int NP>
-__global__ __launch_bounds__(64) void k_dense_wgrad(srk_dense_desc d, const float* A, const float* B, const float* dy,
-                                                    const float* ys, float* ws, int P, int split_pixels) {
+// EX (k_dense_wgrad_ex): g is scaled by gs where it is read.
+template <int NP, bool EX>
+__device__ __forceinline__ void dense_wgrad_body(const srk_dense_desc& d, const float* A, const float* B, const float* dy,
+                                                 const float* ys, float* ws, int P, int split_pixels, float gs) {
   const int lane = threadIdx.x, col = lane & 15, q = lane >> 4;
   const int Ctot = d.CA + d.CB, KK = d.K * d.K, pad = d.K >> 1, OT = d.Cout >> 4;
   const int it = blockIdx.x / KK, tap = blockIdx.x - it * KK;
@@ -293,7 +347,10 @@ __global__ __launch_bounds__(64) void k_dense_wgrad(srk_dense_desc d, const floa
       if (o < OT) {
         float f[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] = dense_mask(d.act, d.slope, gf[o][j], mf[o][j]);
+        for (int j = 0; j < 8; ++j) {
+          f[j] = dense_mask(d.act, d.slope, gf[o][j], mf[o][j]);
+          if constexpr (EX) f[j] *= gs;
+        }
         split8n<NP>(f, ga[o]);
       }
     if (pc + kDenseWgChunk < pend) load(pc + kDenseWgChunk);
@@ -318,6 +375,18 @@ __global__ __launch_bounds__(64) void k_dense_wgrad(srk_dense_desc d, const floa
         if (do_bias && col == 0) part[(size_t)d.Cout * Ctot * KK + oc] = accb[o][r];
       }
     }
+}
+
+template <int NP>
+__global__ __launch_bounds__(64) void k_dense_wgrad(srk_dense_desc d, const float* A, const float* B, const float* dy,
+                                                    const float* ys, float* ws, int P, int split_pixels) {
+  dense_wgrad_body<NP, false>(d, A, B, dy, ys, ws, P, split_pixels, 1.f);
+}
+
+template <int NP>
+__global__ __launch_bounds__(64) void k_dense_wgrad_ex(srk_dense_desc d, const float* A, const float* B, const float* dy,
+                                                       const float* ys, float* ws, int P, int split_pixels, float gs) {
+  dense_wgrad_body<NP, true>(d, A, B, dy, ys, ws, P, split_pixels, gs);
 }
 
 __global__ __launch_bounds__(256) void k_dense_wreduce(const float* __restrict__ ws, int splits, size_t partial_floats,
@@ -371,6 +440,23 @@ static int dense_check_beta(const char* who, float beta) {
   return SRK_OK;
 }
 
+// the caller's epilogue (NULL: the plain operator) as the kernels take it
+static int dense_epilogue(const char* who, const srk_dense_epilogue* e, const float* R2, DenseEpi* out) {
+  *out = DenseEpi{};
+  if (!e) {
+    SRK_REQUIRE(!R2, "%s: R2 needs an epilogue (its scale and pixel stride)", who);
+    return SRK_OK;
+  }
+  SRK_REQUIRE(e->struct_size >= sizeof(srk_dense_epilogue), "%s: the epilogue's struct_size = %u is too small", who,
+              (unsigned)e->struct_size);
+  SRK_REQUIRE(isfinite(e->s) && isfinite(e->r1) && isfinite(e->r2) && isfinite(e->a1),
+              "%s: an epilogue scale is not finite (s = %g, r1 = %g, r2 = %g, a1 = %g)", who, (double)e->s, (double)e->r1,
+              (double)e->r2, (double)e->a1);
+  out->s = e->s, out->r1 = e->r1, out->r2 = e->r2, out->a1 = e->a1;
+  out->R2 = R2, out->ldR2 = e->ldR2;
+  return SRK_OK;
+}
+
 }  // namespace srk
 
 using namespace srk;
@@ -401,10 +487,15 @@ extern "C" size_t srk_dense_conv_workspace_bytes(const srk_dense_desc* d) {
   return dense_plan(*d).ws_bytes;
 }
 
-extern "C" int srk_dense_conv_forward(const srk_dense_desc* d, const float* A, const float* B, const float* W,
-                                      const float* bias, const float* residual, float* y, void* stream) {
-  const char* who = "dense_conv_forward";
+// ex: the _ex entry point (its kernels, whatever the scales); else the kernels RDN has always run
+static int dense_forward(const char* who, bool ex, const srk_dense_desc* d, const float* A, const float* B, const float* W,
+                         const float* bias, const float* residual, const float* R2, const srk_dense_epilogue* epi, float* y,
+                         void* stream) {
   if (int rc = dense_check(d, who)) return rc;
+  DenseEpi e;
+  if (int rc = dense_epilogue(who, epi, R2, &e)) return rc;
+  if (R2)
+    if (int rc = dense_check_ld(who, "ldR2", e.ldR2, d->Cout)) return rc;
   SRK_REQUIRE(A && W && y && (B || d->CB == 0), "%s: null pointer", who);
   if (int rc = dense_check_ld(who, "ldA", d->ldA, d->CA)) return rc;
   if (d->CB)
@@ -412,28 +503,44 @@ extern "C" int srk_dense_conv_forward(const srk_dense_desc* d, const float* A, c
   if (int rc = dense_check_ld(who, "ldY", d->ldY, d->Cout)) return rc;
   if (residual)
     if (int rc = dense_check_ld(who, "ldR", d->ldR, d->Cout)) return rc;
-  if (int rc = dense_check_align(who, A, d->CB ? B : nullptr, bias, residual, (const float*)y)) return rc;
+  if (int rc = dense_check_align(who, A, d->CB ? B : nullptr, bias, residual, R2, (const float*)y)) return rc;
   const DensePlan pl = dense_plan(*d);
   const int P = (int)dense_pixels(*d);
   const dim3 grid(cdiv(cdiv((size_t)P, (size_t)pl.pix_tiles * kDensePixTile), 4) * (unsigned)(d->Cout / kDenseChan)), blk(256);
   hipStream_t st = (hipStream_t)stream;
   if (d->CB == 0) B = A;   // never read
-#define SRK_DENSE_FWD(NP, PT) \
-  hipLaunchKernelGGL((k_dense_fwd<NP, PT>), grid, blk, 0, st, *d, A, B, W, bias, residual, y, P)
+#define SRK_DENSE_FWD(NP, PT)                                                                              \
+  do {                                                                                                     \
+    if (ex) hipLaunchKernelGGL((k_dense_fwd_ex<NP, PT>), grid, blk, 0, st, *d, A, B, W, bias, residual, y, P, e); \
+    else hipLaunchKernelGGL((k_dense_fwd<NP, PT>), grid, blk, 0, st, *d, A, B, W, bias, residual, y, P);   \
+  } while (0)
   if (d->terms == 6) {
     if (pl.pix_tiles == 4) SRK_DENSE_FWD(3, 4); else if (pl.pix_tiles == 2) SRK_DENSE_FWD(3, 2); else SRK_DENSE_FWD(3, 1);
   } else {
     if (pl.pix_tiles == 4) SRK_DENSE_FWD(2, 4); else if (pl.pix_tiles == 2) SRK_DENSE_FWD(2, 2); else SRK_DENSE_FWD(2, 1);
   }
 #undef SRK_DENSE_FWD
-  note_kernel("k_dense_fwd<%d,%d>", d->terms == 6 ? 3 : 2, pl.pix_tiles);
+  note_kernel(ex ? "k_dense_fwd_ex<%d,%d>" : "k_dense_fwd<%d,%d>", d->terms == 6 ? 3 : 2, pl.pix_tiles);
   return check_launch(who);
 }
 
-extern "C" int srk_dense_conv_backward_data(const srk_dense_desc* d, const float* dy, const float* y_saved, const float* W,
-                                            float* dA, float betaA, float* dB, float betaB, const float* add, void* stream) {
-  const char* who = "dense_conv_backward_data";
+extern "C" int srk_dense_conv_forward(const srk_dense_desc* d, const float* A, const float* B, const float* W,
+                                      const float* bias, const float* residual, float* y, void* stream) {
+  return dense_forward("dense_conv_forward", false, d, A, B, W, bias, residual, nullptr, nullptr, y, stream);
+}
+
+extern "C" int srk_dense_conv_forward_ex(const srk_dense_desc* d, const float* A, const float* B, const float* W,
+                                         const float* bias, const float* R1, const float* R2, const srk_dense_epilogue* e,
+                                         float* y, void* stream) {
+  return dense_forward("dense_conv_forward_ex", true, d, A, B, W, bias, R1, R2, e, y, stream);
+}
+
+static int dense_backward_data(const char* who, bool ex, const srk_dense_desc* d, const float* dy, const float* y_saved,
+                               const float* W, float* dA, float betaA, float* dB, float betaB, const float* add,
+                               const srk_dense_epilogue* epi, void* stream) {
   if (int rc = dense_check(d, who)) return rc;
+  DenseEpi e;
+  if (int rc = dense_epilogue(who, epi, nullptr, &e)) return rc;
   SRK_REQUIRE(dy && W && (dA || dB), "%s: null pointer", who);
   SRK_REQUIRE(y_saved || d->act == SRK_ACT_NONE, "%s: an activation needs the saved output", who);
   SRK_REQUIRE(!add || dA, "%s: add goes into dA, which is null", who);
@@ -455,23 +562,38 @@ extern "C" int srk_dense_conv_backward_data(const srk_dense_desc* d, const float
   const int P = (int)dense_pixels(*d);
   const dim3 grid(cdiv(cdiv((size_t)P, (size_t)pl.pix_tiles * kDensePixTile), 4), cdiv((size_t)dense_ctot(*d), 64)), blk(256);
   hipStream_t st = (hipStream_t)stream;
-#define SRK_DENSE_DG(NP, PT) \
-  launch_lds<k_dense_dgrad<NP, PT>>(grid, blk, (size_t)32 * kDenseDgPitch * sizeof(float), st, *d, dy, y_saved, W, dA, betaA, dB, betaB, add, P)
+#define SRK_DENSE_DG(NP, PT)                                                                                          \
+  do {                                                                                                                \
+    if (ex) launch_lds<k_dense_dgrad_ex<NP, PT>>(grid, blk, (size_t)32 * kDenseDgPitch * sizeof(float), st, *d, dy, y_saved, W, dA, betaA, dB, betaB, add, P, e); \
+    else launch_lds<k_dense_dgrad<NP, PT>>(grid, blk, (size_t)32 * kDenseDgPitch * sizeof(float), st, *d, dy, y_saved, W, dA, betaA, dB, betaB, add, P); \
+  } while (0)
   if (d->terms == 6) {
     if (pl.pix_tiles == 4) SRK_DENSE_DG(3, 4); else if (pl.pix_tiles == 2) SRK_DENSE_DG(3, 2); else SRK_DENSE_DG(3, 1);
   } else {
     if (pl.pix_tiles == 4) SRK_DENSE_DG(2, 4); else if (pl.pix_tiles == 2) SRK_DENSE_DG(2, 2); else SRK_DENSE_DG(2, 1);
   }
 #undef SRK_DENSE_DG
-  note_kernel("k_dense_dgrad<%d,%d>", d->terms == 6 ? 3 : 2, pl.pix_tiles);
+  note_kernel(ex ? "k_dense_dgrad_ex<%d,%d>" : "k_dense_dgrad<%d,%d>", d->terms == 6 ? 3 : 2, pl.pix_tiles);
   return check_launch(who);
 }
 
-extern "C" int srk_dense_conv_backward_weight(const srk_dense_desc* d, const float* A, const float* B, const float* dy,
-                                              const float* y_saved, float* dW, float* db, float beta, void* workspace,
-                                              size_t workspace_bytes, void* stream) {
-  const char* who = "dense_conv_backward_weight";
+extern "C" int srk_dense_conv_backward_data(const srk_dense_desc* d, const float* dy, const float* y_saved, const float* W,
+                                            float* dA, float betaA, float* dB, float betaB, const float* add, void* stream) {
+  return dense_backward_data("dense_conv_backward_data", false, d, dy, y_saved, W, dA, betaA, dB, betaB, add, nullptr, stream);
+}
+
+extern "C" int srk_dense_conv_backward_data_ex(const srk_dense_desc* d, const float* dy, const float* y_saved, const float* W,
+                                               float* dA, float betaA, float* dB, float betaB, const float* add,
+                                               const srk_dense_epilogue* e, void* stream) {
+  return dense_backward_data("dense_conv_backward_data_ex", true, d, dy, y_saved, W, dA, betaA, dB, betaB, add, e, stream);
+}
+
+static int dense_backward_weight(const char* who, bool ex, const srk_dense_desc* d, const float* A, const float* B,
+                                 const float* dy, const float* y_saved, float* dW, float* db, float beta,
+                                 const srk_dense_epilogue* epi, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = dense_check(d, who)) return rc;
+  DenseEpi e;
+  if (int rc = dense_epilogue(who, epi, nullptr, &e)) return rc;
   SRK_REQUIRE(A && dy && (dW || db) && workspace && (B || d->CB == 0), "%s: null pointer", who);
   SRK_REQUIRE(y_saved || d->act == SRK_ACT_NONE, "%s: an activation needs the saved output", who);
   if (int rc = dense_check_beta(who, beta)) return rc;
@@ -492,24 +614,46 @@ extern "C" int srk_dense_conv_backward_weight(const srk_dense_desc* d, const flo
   hipStream_t st = (hipStream_t)stream;
   float* ws = (float*)workspace;
   if (d->CB == 0) B = A;   // never read
-  if (d->terms == 6)
+  if (ex) {
+    if (d->terms == 6)
+      hipLaunchKernelGGL(k_dense_wgrad_ex<3>, grid, blk, 0, st, *d, A, B, dy, y_saved, ws, P, (int)pl.split_pixels, e.s);
+    else
+      hipLaunchKernelGGL(k_dense_wgrad_ex<2>, grid, blk, 0, st, *d, A, B, dy, y_saved, ws, P, (int)pl.split_pixels, e.s);
+  } else if (d->terms == 6)
     hipLaunchKernelGGL(k_dense_wgrad<3>, grid, blk, 0, st, *d, A, B, dy, y_saved, ws, P, (int)pl.split_pixels);
   else
     hipLaunchKernelGGL(k_dense_wgrad<2>, grid, blk, 0, st, *d, A, B, dy, y_saved, ws, P, (int)pl.split_pixels);
   const size_t pf = dense_partial_floats(*d);
   hipLaunchKernelGGL(k_dense_wreduce, dim3(cdiv(pf, 256)), dim3(256), 0, st, (const float*)ws, pl.splits, pf,
                      pf - (size_t)d->Cout, dW, db, beta);
-  note_kernel("k_dense_wgrad<%d> x%d", d->terms == 6 ? 3 : 2, pl.splits);
+  note_kernel(ex ? "k_dense_wgrad_ex<%d> x%d" : "k_dense_wgrad<%d> x%d", d->terms == 6 ? 3 : 2, pl.splits);
   return check_launch(who);
 }
 
+extern "C" int srk_dense_conv_backward_weight(const srk_dense_desc* d, const float* A, const float* B, const float* dy,
+                                              const float* y_saved, float* dW, float* db, float beta, void* workspace,
+                                              size_t workspace_bytes, void* stream) {
+  return dense_backward_weight("dense_conv_backward_weight", false, d, A, B, dy, y_saved, dW, db, beta, nullptr, workspace,
+                               workspace_bytes, stream);
+}
+
+extern "C" int srk_dense_conv_backward_weight_ex(const srk_dense_desc* d, const float* A, const float* B, const float* dy,
+                                                 const float* y_saved, float* dW, float* db, float beta,
+                                                 const srk_dense_epilogue* e, void* workspace, size_t workspace_bytes,
+                                                 void* stream) {
+  return dense_backward_weight("dense_conv_backward_weight_ex", true, d, A, B, dy, y_saved, dW, db, beta, e, workspace,
+                               workspace_bytes, stream);
+}
+
 // The same three directions as plain loops over host pointers, fp64 accumulation, one rounding to fp32 at the store.
-extern "C" int srk_dense_conv_host(const srk_dense_desc* dp, int direction, const float* A, const float* B, const float* W,
-                                   const float* bias, const float* residual, float* y, const float* dy, const float* add,
-                                   float* dA, float betaA, float* dB, float betaB, float* dW, float* db, float beta) {
-  const char* who = "dense_conv_host";
+static int dense_host(const char* who, const srk_dense_desc* dp, int direction, const float* A, const float* B, const float* W,
+                      const float* bias, const float* residual, const float* R2, const srk_dense_epilogue* epi, float* y,
+                      const float* dy, const float* add, float* dA, float betaA, float* dB, float betaB, float* dW, float* db,
+                      float beta) {
   if (int rc = dense_check(dp, who)) return rc;
   const srk_dense_desc& d = *dp;
+  DenseEpi e;
+  if (int rc = dense_epilogue(who, epi, R2, &e)) return rc;
   SRK_REQUIRE(direction >= 0 && direction <= 2, "%s: direction %d is not 0 (forward), 1 (data) or 2 (weight)", who, direction);
   const int Ctot = dense_ctot(d), K = d.K, KK = K * K, pad = K >> 1;
   const int64_t P = dense_pixels(d);
@@ -522,10 +666,10 @@ extern "C" int srk_dense_conv_host(const srk_dense_desc* dp, int direction, cons
     const int hh = h + dh, ww = w + dw;
     return (hh >= 0 && hh < d.H && ww >= 0 && ww < d.W) ? ((int64_t)n * d.H + hh) * d.W + ww : -1;
   };
-  auto grad = [&](int64_t p, int oc) -> double {   // g = dy * act'(y_saved)
-    const float g = dy[(size_t)p * d.ldDy + oc];
-    if (d.act == SRK_ACT_NONE) return (double)g;
-    return (double)g * (double)dense_act_grad(d.act, d.slope, y[(size_t)p * d.ldY + oc]);
+  auto grad = [&](int64_t p, int oc) -> double {   // g = s * dy * act'(y_saved)
+    const double g = (double)e.s * (double)dy[(size_t)p * d.ldDy + oc];
+    if (d.act == SRK_ACT_NONE) return g;
+    return g * (double)dense_act_grad(d.act, d.slope, y[(size_t)p * d.ldY + oc]);
   };
   if (direction == 0) {
     SRK_REQUIRE(A && W && y && (B || d.CB == 0), "%s: null pointer", who);
@@ -535,6 +679,8 @@ extern "C" int srk_dense_conv_host(const srk_dense_desc* dp, int direction, cons
     if (int rc = dense_check_ld(who, "ldY", d.ldY, d.Cout)) return rc;
     if (residual)
       if (int rc = dense_check_ld(who, "ldR", d.ldR, d.Cout)) return rc;
+    if (R2)
+      if (int rc = dense_check_ld(who, "ldR2", e.ldR2, d.Cout)) return rc;
     for (int64_t p = 0; p < P; ++p)
       for (int oc = 0; oc < d.Cout; ++oc) {
         double a = bias ? (double)bias[oc] : 0.0;
@@ -545,7 +691,9 @@ extern "C" int srk_dense_conv_host(const srk_dense_desc* dp, int direction, cons
         }
         if (d.act == SRK_ACT_RELU) a = a > 0.0 ? a : 0.0;
         if (d.act == SRK_ACT_LRELU) a = a > 0.0 ? a : (double)d.slope * a;
-        if (residual) a += (double)residual[(size_t)p * d.ldR + oc];
+        a *= (double)e.s;
+        if (residual) a += (double)e.r1 * (double)residual[(size_t)p * d.ldR + oc];
+        if (R2) a += (double)e.r2 * (double)R2[(size_t)p * e.ldR2 + oc];
         y[(size_t)p * d.ldY + oc] = (float)a;
       }
     return SRK_OK;
@@ -581,7 +729,7 @@ extern "C" int srk_dense_conv_host(const srk_dense_desc* dp, int direction, cons
         for (int tap = 0; tap < KK; ++tap)
           for (int oc = 0; oc < d.Cout; ++oc)
             a += g[(size_t)tap * d.Cout + oc] * (double)W[((size_t)oc * Ctot + c) * KK + tap];
-        if (inA && add) a += (double)add[(size_t)p * d.ldAdd + c];
+        if (inA && add) a += (double)e.a1 * (double)add[(size_t)p * d.ldAdd + c];
         if ((inA ? betaA : betaB) != 0.f) a += (double)*out;
         *out = (float)a;
       }
@@ -608,4 +756,19 @@ extern "C" int srk_dense_conv_host(const srk_dense_desc* dp, int direction, cons
   for (size_t i = 0; i < aw.size(); ++i) dW[i] = (float)(beta != 0.f ? (double)dW[i] + aw[i] : aw[i]);
   for (size_t i = 0; i < ab.size(); ++i) db[i] = (float)(beta != 0.f ? (double)db[i] + ab[i] : ab[i]);
   return SRK_OK;
+}
+
+extern "C" int srk_dense_conv_host(const srk_dense_desc* d, int direction, const float* A, const float* B, const float* W,
+                                   const float* bias, const float* residual, float* y, const float* dy, const float* add,
+                                   float* dA, float betaA, float* dB, float betaB, float* dW, float* db, float beta) {
+  return dense_host("dense_conv_host", d, direction, A, B, W, bias, residual, nullptr, nullptr, y, dy, add, dA, betaA, dB,
+                    betaB, dW, db, beta);
+}
+
+extern "C" int srk_dense_conv_host_ex(const srk_dense_desc* d, int direction, const float* A, const float* B, const float* W,
+                                      const float* bias, const float* R1, const float* R2, const srk_dense_epilogue* e, float* y,
+                                      const float* dy, const float* add, float* dA, float betaA, float* dB, float betaB,
+                                      float* dW, float* db, float beta) {
+  return dense_host("dense_conv_host_ex", d, direction, A, B, W, bias, R1, R2, e, y, dy, add, dA, betaA, dB, betaB, dW, db,
+                    beta);
 }

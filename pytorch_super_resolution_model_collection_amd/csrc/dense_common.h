@@ -1,5 +1,5 @@
 // What the channel-slice convolution kernels (dense.hip) and their host twin (srk_dense_conv_host) share: the supported
-// range, the slice addressing and the planner.  DESIGN.md 28.
+// range, the slice addressing and the planner.  DESIGN.md 28 (and 30: the _ex entry points share all of it).
 //
 // A "slice" is `C` channels of a wider NHWC buffer: a pointer to the slice's first channel of pixel 0 and the buffer's
 // pixel stride `ld` in floats (ld >= C).  Pixel p = (n * H + h) * W + w of a slice starts at ptr + p * ld.  The input

@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from . import ops, utils
 from ._lib import ACT_NONE, ACT_RELU
-from .base_networks import (RDB, RSTB, ConvBlock, DeconvBlock, DenseBlock, PSBlock, ResidualGroup, ResnetBlock,
+from .base_networks import (RDB, RRDB, RSTB, ConvBlock, DeconvBlock, DenseBlock, PSBlock, ResidualGroup, ResnetBlock,
                             Upsample2xBlock)
 from .layers import Conv2d, ConvTranspose2d, LayerNorm, LeakyReLU, PixelShuffle, PReLU, grad_mode
 from ._lib import ACT_LRELU
@@ -288,6 +288,47 @@ class RDNNet(nn.Module):
         return out
 
 
+class RRDBNet(nn.Module):
+    """ESRGAN's generator (Wang et al., ECCV-W 2018; not in the reference collection): conv_first, nb residual-in-residual
+    dense blocks, conv_body under the conv_first skip, two nearest-neighbour x2 upsamplings each followed by a conv with
+    LeakyReLU(0.2), conv_hr with LeakyReLU and conv_last.  Parameter names as in BasicSR's RRDBNet (conv_first,
+    body.{i}.rdb{1,2,3}.conv{1..5}, conv_body, conv_up1, conv_up2, conv_hr, conv_last).  The nb blocks run as ONE op on
+    channel slices (ops.rrdb_trunk).  Scale 4 only: BasicSR's x2 goes through a pixel-unshuffle, which is not built."""
+
+    def __init__(self, num_channels, nf=64, nb=23, gc=32, scale_factor=4):
+        super(RRDBNet, self).__init__()
+        if scale_factor != 4:
+            raise ValueError("RRDBNet: scale_factor %r is not 4 (the only scale this net is built for)" % (scale_factor,))
+        if nb < 1:
+            raise ValueError("RRDBNet: nb = %r blocks, at least 1" % (nb,))
+        self.scale_factor = scale_factor
+        self.conv_first = Conv2d(num_channels, nf, 3, 1, 1)
+        self.body = nn.ModuleList([RRDB(nf, gc) for _ in range(nb)])     # (RRDB raises for the nf and gc it refuses)
+        self.conv_body = Conv2d(nf, nf, 3, 1, 1)
+        self.conv_up1 = Conv2d(nf, nf, 3, 1, 1)
+        self.conv_up2 = Conv2d(nf, nf, 3, 1, 1)
+        self.conv_hr = Conv2d(nf, nf, 3, 1, 1)
+        self.conv_last = Conv2d(nf, num_channels, 3, 1, 1)
+        self.conv_last._linear_tail = True
+
+    def weight_init(self, mean=0.0, std=0.02):
+        for m in self.modules():
+            utils.weights_init_normal(m, mean=mean, std=std)
+
+    def forward(self, x):
+        training = _training_graph(self, x)
+        feat = self.conv_first(x)
+        if training:
+            feat, skip = ops.fork(feat)   # gradient fan-in summed by srk_axpby
+        else:
+            skip = feat
+        trunk = ops.rrdb_trunk(feat, [b.block_params() for b in self.body], self.body[0].res_scale)
+        out = self.conv_body.run(trunk, residual=skip)
+        out = self.conv_up1.run(ops.upsample_nearest(out, 2), ACT_LRELU, 0.2)
+        out = self.conv_up2.run(ops.upsample_nearest(out, 2), ACT_LRELU, 0.2)
+        return self.conv_last.run(self.conv_hr.run(out, ACT_LRELU, 0.2))
+
+
 class _PatchEmbed(nn.Module):
     """Upstream's `patch_embed` at patch size 1: only its LayerNorm has parameters (`patch_embed.norm.*`)."""
 
@@ -515,6 +556,18 @@ class SRGANDiscriminator(nn.Module):
     def weight_init(self, mean=0.0, std=0.02):
         for m in self.modules():
             utils.weights_init_normal(m, mean=mean, std=std)
+
+
+class ESRGANDiscriminator(SRGANDiscriminator):
+    """SRGANDiscriminator's body ending in a LOGIT: the last dense layer has no sigmoid, as the relativistic average loss
+    (ops.ragan_loss) takes it.  (BasicSR's 4x4 stride-2 VGG-style discriminator is not built.)"""
+
+    def __init__(self, num_channels, base_filter, image_size):
+        super(ESRGANDiscriminator, self).__init__(num_channels, base_filter, image_size)
+        self.dense_layers = nn.Sequential(
+            DenseBlock(base_filter * 8 * image_size // 16 * image_size // 16, base_filter * 16, activation='lrelu',
+                       norm=None),
+            DenseBlock(base_filter * 16, 1, activation=None, norm=None))
 
 
 class _MaxPool2x2(nn.MaxPool2d):

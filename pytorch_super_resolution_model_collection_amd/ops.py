@@ -1672,14 +1672,17 @@ def max_pool2x2_train(x):
     return _MaxPool2x2.apply(x)
 
 
-def perceptual_loss(pred, target, extractor, normalize=True):
+def perceptual_loss(pred, target, extractor, normalize=True, criterion='mse'):
     """The VGG feature loss of SRGAN (srgan.py:301-305) as a term that trains: MSE(extractor.extract(norm(pred)),
     extractor.extract(norm(target))), norm = utils.norm(vgg=True) when `normalize`; a 0-dim fp32 device tensor with the
     contract of the other losses (it IS ops.mse_loss on the two feature maps: loss_seed, unit seed, weighted_term,
     loss_sum).  The gradient flows to pred only.  Both operands run the same kernels -- the training forward of the
     head, the target's without a graph -- so equal inputs give a loss of exactly 0 and a zero gradient.
-    pred / target: [N, 3, H, W]; extractor: models.FeatureExtractor."""
+    pred / target: [N, 3, H, W]; extractor: models.FeatureExtractor.  criterion: 'mse' (SRGAN) or 'l1' (ESRGAN: ops.l1_loss
+    on the two feature maps, the same contract)."""
     from . import utils
+    if criterion not in ('mse', 'l1'):
+        raise ValueError("perceptual_loss: criterion = %r is neither 'mse' nor 'l1'" % (criterion,))
     for name, t in (("pred", pred), ("target", target)):
         if t.dim() != 4 or t.shape[1] != 3:
             raise ValueError("perceptual_loss: %s must be [N, 3, H, W] (the VGG head reads RGB), got shape %s"
@@ -1690,7 +1693,7 @@ def perceptual_loss(pred, target, extractor, normalize=True):
         t = target.detach()
         real = extractor.extract(utils.norm(t, vgg=True) if normalize else t, grad=True)
     fake = extractor.extract(utils.norm(pred, vgg=True) if normalize else pred, grad=True)
-    return mse_loss(fake, real)
+    return mse_loss(fake, real) if criterion == 'mse' else l1_loss(fake, real)
 
 
 def grad_enabled_for(*tensors):
@@ -2807,11 +2810,13 @@ def _dense_weight(what, weight, d):
 
 
 def dense_conv(a, weight, bias=None, b=None, out=None, ca=None, a_off=0, cb=None, b_off=0, out_off=0, act=ACT_NONE,
-               slope=0.0, residual=None, res_off=0, terms=3):
+               slope=0.0, residual=None, res_off=0, terms=3, s=None, r1=1.0, residual2=None, res2_off=0, r2=1.0):
     """out[:, out_off : out_off + Cout] = act(conv(cat(a[:, a_off : a_off + ca], b[:, b_off : b_off + cb]), weight) + bias)
     (+ residual[:, res_off : res_off + Cout]) without the cat: stride 1, 'same', K in {1, 3}.  a, b, out, residual:
     channels_last buffers of any width; no other channel of `out` is touched.  out=None: a new [N, Cout, H, W] tensor.
-    No autograd (ops.residual_dense_blocks is the differentiable user).  ValueError for what no kernel covers."""
+    No autograd (ops.residual_dense_blocks is the differentiable user).  ValueError for what no kernel covers.
+    With `s` (or residual2) the call is srk_dense_conv_forward_ex:
+    out = s * act(conv + bias) + r1 * residual + r2 * residual2[:, res2_off : res2_off + Cout] (s=None: 1)."""
     lib = _lib.load()
     what = "dense_conv"
     cout, k = int(weight.shape[0]), int(weight.shape[2])
@@ -2829,6 +2834,14 @@ def dense_conv(a, weight, bias=None, b=None, out=None, ca=None, a_off=0, cb=None
     if residual is not None:
         sr = _Slice(what + ": residual", residual, res_off, cout, sa)
         d.ldR = sr.ld
+    if s is not None or residual2 is not None:
+        sr2 = _Slice(what + ": residual2", residual2, res2_off, cout, sa) if residual2 is not None else None
+        e = _lib.DenseEpilogue(1.0 if s is None else s, r1, r2, sr2.ld if sr2 else 0)
+        _dense_check(lib.srk_dense_conv_forward_ex(ctypes.byref(d), sa.p, sb.p if sb else None, ptr(weight.detach()),
+                                                   ptr(bias.detach()) if bias is not None else None, sr.p if sr else None,
+                                                   sr2.p if sr2 else None, ctypes.byref(e), so.p, stream_ptr()),
+                     "srk_dense_conv_forward_ex")
+        return out
     _dense_check(lib.srk_dense_conv_forward(ctypes.byref(d), sa.p, sb.p if sb else None, ptr(weight.detach()),
                                             ptr(bias.detach()) if bias is not None else None, sr.p if sr else None, so.p,
                                             stream_ptr()), "srk_dense_conv_forward")
@@ -2836,9 +2849,10 @@ def dense_conv(a, weight, bias=None, b=None, out=None, ca=None, a_off=0, cb=None
 
 
 def dense_conv_backward_data(dy, weight, ca, cb=0, y_saved=None, da=None, db=None, add=None, dy_off=0, y_off=0, da_off=0,
-                             db_off=0, add_off=0, beta_a=0.0, beta_b=0.0, act=ACT_NONE, slope=0.0, terms=3):
+                             db_off=0, add_off=0, beta_a=0.0, beta_b=0.0, act=ACT_NONE, slope=0.0, terms=3, s=None, a1=1.0):
     """The data gradient of dense_conv into the slices da[:, da_off : da_off + ca] and db[:, db_off : db_off + cb]
-    (either may be None): slice = beta * slice + conv^T(dy * act'(y_saved)) (+ add into da), beta 0 or 1."""
+    (either may be None): slice = beta * slice + conv^T(dy * act'(y_saved)) (+ add into da), beta 0 or 1.  With `s` the
+    call is srk_dense_conv_backward_data_ex: dy is scaled by s and add by a1."""
     lib = _lib.load()
     what = "dense_conv_backward_data"
     cout, k = int(weight.shape[0]), int(weight.shape[2])
@@ -2862,6 +2876,13 @@ def dense_conv_backward_data(dy, weight, ca, cb=0, y_saved=None, da=None, db=Non
     if add is not None:
         sadd = _Slice(what + ": add", add, add_off, ca, sdy)
         d.ldAdd = sadd.ld
+    if s is not None:
+        e = _lib.DenseEpilogue(s, a1=a1)
+        _dense_check(lib.srk_dense_conv_backward_data_ex(ctypes.byref(d), sdy.p, sy.p if sy else None, ptr(weight.detach()),
+                                                         sda.p if sda else None, float(beta_a), sdb.p if sdb else None,
+                                                         float(beta_b), sadd.p if sadd else None, ctypes.byref(e),
+                                                         stream_ptr()), "srk_dense_conv_backward_data_ex")
+        return da, db
     _dense_check(lib.srk_dense_conv_backward_data(ctypes.byref(d), sdy.p, sy.p if sy else None, ptr(weight.detach()),
                                                   sda.p if sda else None, float(beta_a), sdb.p if sdb else None,
                                                   float(beta_b), sadd.p if sadd else None, stream_ptr()),
@@ -2870,10 +2891,11 @@ def dense_conv_backward_data(dy, weight, ca, cb=0, y_saved=None, da=None, db=Non
 
 
 def dense_conv_backward_weight(a, dy, dw, dbias=None, b=None, y_saved=None, ca=None, a_off=0, cb=None, b_off=0, dy_off=0,
-                               y_off=0, beta=0.0, act=ACT_NONE, slope=0.0, terms=3):
+                               y_off=0, beta=0.0, act=ACT_NONE, slope=0.0, terms=3, s=None):
     """dw = beta * dw + sum over pixels of cat(a, b)^T (dy * act'(y_saved)), dbias likewise (beta 0 or 1); dw is a
     contiguous [Cout, ca + cb, K, K] tensor or view (a parameter's slice of the flat gradient buffer).  Two launches, the
-    pixel ranges added in a fixed order: two calls give the same bits."""
+    pixel ranges added in a fixed order: two calls give the same bits.  With `s` the call is
+    srk_dense_conv_backward_weight_ex: dy is scaled by s where the kernel reads it (no further launch)."""
     lib = _lib.load()
     what = "dense_conv_backward_weight"
     cout, k = int(dw.shape[0]), int(dw.shape[2])
@@ -2893,6 +2915,13 @@ def dense_conv_backward_weight(a, dy, dw, dbias=None, b=None, y_saved=None, ca=N
         raise ValueError("%s: %s" % (what, lib.srk_last_error_string().decode()))
     nbytes = int(lib.srk_dense_conv_workspace_bytes(ctypes.byref(d)))
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=a.device)   # torch's allocator: a captured graph owns it
+    if s is not None:
+        e = _lib.DenseEpilogue(s)
+        _dense_check(lib.srk_dense_conv_backward_weight_ex(ctypes.byref(d), sa.p, sb.p if sb else None, sdy.p,
+                                                           sy.p if sy else None, ptr(dw), ptr(dbias), float(beta),
+                                                           ctypes.byref(e), ptr(ws), nbytes, stream_ptr()),
+                     "srk_dense_conv_backward_weight_ex")
+        return dw, dbias
     _dense_check(lib.srk_dense_conv_backward_weight(ctypes.byref(d), sa.p, sb.p if sb else None, sdy.p,
                                                     sy.p if sy else None, ptr(dw), ptr(dbias), float(beta), ptr(ws), nbytes,
                                                     stream_ptr()), "srk_dense_conv_backward_weight")
@@ -3013,6 +3042,209 @@ def residual_dense_blocks(x, blocks):
         raise ValueError("residual_dense_blocks: G = %d, G0 = %d: at most 64 output channels a convolution" % (g, g0))
     params = [t for b in blocks for t in b]
     return _ResidualDenseBlocks.apply(x, len(blocks), C, grad_enabled_for(x, *params), *params)
+
+
+# ------------------------------------------------------------------------------------------------
+# The residual-in-residual dense trunk of ESRGAN (csrc/dense.hip: the _ex entry points)
+# ------------------------------------------------------------------------------------------------
+_RRDB_SLOPE = 0.2
+
+
+def _trunk_buffer(n, c, h, w, like):
+    """An RDB's output map (its own name, so that a test can count them)."""
+    return _empty_cl(n, c, h, w, like)
+
+
+class _RRDBTrunk(torch.autograd.Function):
+    """nb residual-in-residual dense blocks on slice convolutions; see rrdb_trunk."""
+
+    @staticmethod
+    def forward(ctx, x, nb, rs, need_grad, *params):
+        require_cuda(x, *params)
+        x = to_nhwc(x)
+        n, f, hh, ww = x.shape
+        g = int(params[0].shape[0])
+        terms = dense_terms("train_fwd" if need_grad else "infer")
+        free, growth = [], None
+        ins, growths = [], []
+
+        def take():
+            return free.pop() if free else _trunk_buffer(n, f, hh, ww, x)
+
+        u1 = x
+        for i in range(nb):
+            u = u1
+            for k in range(3):
+                p = params[30 * i + 10 * k:30 * i + 10 * k + 10]
+                if need_grad or growth is None:     # a backward reads every growth buffer: the LeakyReLU masks, the wgrad inputs
+                    growth = _growth_buffer(n, 4 * g, hh, ww, x)
+                for c in range(4):
+                    dense_conv(u, p[2 * c], p[2 * c + 1], growth if c else None, growth, f, 0, c * g, 0, c * g, ACT_LRELU,
+                               _RRDB_SLOPE, None, 0, terms)
+                v = _trunk_buffer(n, f, hh, ww, x) if need_grad else take()
+                if k < 2:      # v = rs conv5 + u
+                    dense_conv(u, p[8], p[9], growth, v, f, 0, 4 * g, 0, 0, ACT_NONE, 0.0, u, 0, terms, s=rs, r1=1.0)
+                else:          # out = rs (rs conv5 + u3) + u1: the outer skip rides in the same epilogue
+                    dense_conv(u, p[8], p[9], growth, v, f, 0, 4 * g, 0, 0, ACT_NONE, 0.0, u, 0, terms, s=rs * rs, r1=rs,
+                               residual2=u1, res2_off=0, r2=1.0)
+                if need_grad:
+                    ins.append(u)
+                    growths.append(growth)
+                elif k > 0:
+                    free.append(u)                  # u2 / u3: read for the last time
+                u = v
+            if not need_grad and i > 0:
+                free.append(u1)
+            u1 = u
+        ctx.dims = (nb, f, g, float(rs))
+        ctx.params = params
+        if need_grad:
+            ctx.save_for_backward(*(ins + growths))
+        return u1
+
+    @staticmethod
+    def backward(ctx, gout):
+        nb, f, g, rs = ctx.dims
+        params = ctx.params
+        saved = ctx.saved_tensors
+        ins, growths = saved[:3 * nb], saved[3 * nb:]
+        n, _, hh, ww = ins[0].shape
+        terms = dense_terms("bwd")
+        like = ins[0]
+        gnext = _dense(gout)               # read only: every accumulator below is this op's own
+        gg = _empty_cl(n, 4 * g, hh, ww, like)
+        grads = [None] * len(params)
+
+        def wgrad(i, a, b, cb, dy, dy_off, ys, y_off, act, s):
+            w, bias = params[i], params[i + 1]
+            if not (ctx.needs_input_grad[4 + i] or ctx.needs_input_grad[5 + i]):
+                return
+            acc = _flat_grads(w, bias)
+            if acc is not None:    # optim.FlatParams: accumulated in the flat gradient buffer
+                dw, dbias, beta = acc[0], acc[1], 1.0
+            else:
+                dw = torch.empty_like(w, memory_format=torch.contiguous_format)
+                dbias, beta = torch.empty_like(bias), 0.0
+                grads[i], grads[i + 1] = dw, dbias
+            dense_conv_backward_weight(a, dy, dw, dbias, b if cb else None, ys, f, 0, cb, 0, dy_off, y_off, beta, act,
+                                       _RRDB_SLOPE if act == ACT_LRELU else 0.0, terms, s=s)
+
+        def rdb(j, dy, s, da, a1, extra):
+            """The backward of RDB j (its output = s conv5 + a1 u + ...): da = the whole gradient of its input u -- conv5's
+            data gradient starts it (beta 0) with a1 * dy, the RDB skip, in the epilogue; the four growth convolutions add
+            theirs; `extra` (the RRDB's outer skip) rides in the epilogue of the fourth."""
+            i0, u, growth = 10 * j, ins[j], growths[j]
+            wgrad(i0 + 8, u, growth, 4 * g, dy, 0, None, 0, ACT_NONE, s)
+            dense_conv_backward_data(dy, params[i0 + 8], f, 4 * g, None, da, gg, dy if da is not None else None, 0, 0, 0, 0, 0,
+                                     0.0, 0.0, ACT_NONE, 0.0, terms, s=s, a1=a1)
+            for c in reversed(range(4)):
+                wgrad(i0 + 2 * c, u, growth, c * g, gg, c * g, growth, c * g, ACT_LRELU, None)
+                if da is None and c == 0:
+                    continue
+                dense_conv_backward_data(gg, params[i0 + 2 * c], f, c * g, growth, da, gg if c else None,
+                                         extra if (c == 3 and da is not None) else None, c * g, c * g, 0, 0, 0, 1.0, 1.0,
+                                         ACT_LRELU, _RRDB_SLOPE, terms)
+
+        for i in reversed(range(nb)):
+            gu3 = _empty_cl(n, f, hh, ww, like)
+            rdb(3 * i + 2, gnext, rs * rs, gu3, rs, None)       # out = rs^2 conv5 + rs u3 + u1
+            gu2 = _empty_cl(n, f, hh, ww, like)
+            rdb(3 * i + 1, gu3, rs, gu2, 1.0, None)             # u3 = rs conv5 + u2
+            gu1 = _empty_cl(n, f, hh, ww, like) if (i > 0 or ctx.needs_input_grad[0]) else None
+            rdb(3 * i, gu2, rs, gu1, 1.0, gnext)                # u2 = rs conv5 + u1, and u1's own way to the output
+            gnext = gu1
+        return (gnext, None, None, None) + tuple(grads)
+
+
+def rrdb_trunk(x, blocks, res_scale=0.2):
+    """The trunk of ESRGAN's RRDBNet: residual-in-residual dense blocks without a concatenation or an elementwise launch.
+    x: [N, F, H, W]; blocks: a list of RRDBs, each 3 RDBs, each (w1, b1, ..., w5, b5) with w_c [G, F + (c - 1) G, 3, 3] for
+    c = 1..4 and w5 [F, F + 4 G, 3, 3].  Per RDB: four slice convolutions with LeakyReLU(0.2) into one growth buffer, then
+    u' = res_scale * conv5([u | growth]) + u; an RRDB's third conv5 also folds the outer skip into its epilogue:
+    out = res_scale^2 * conv5 + res_scale * u3 + u1.  15 launches an RRDB forward; the backward (15 data-gradient and 15
+    two-launch weight-gradient calls an RRDB) accumulates every fan-in inside the data-gradient epilogues.
+    F and G: multiples of 16, at most 64 (ValueError otherwise).  (base_networks.RRDB, models.RRDBNet)"""
+    blocks = [tuple(tuple(r) for r in b) for b in blocks]
+    if x.dim() != 4:
+        raise ValueError("rrdb_trunk: x must be [N, F, H, W], got shape %s" % (tuple(x.shape),))
+    if not blocks or any(len(b) != 3 or any(len(r) != 10 for r in b) for b in blocks):
+        raise ValueError("rrdb_trunk: every RRDB is 3 RDBs of (w1, b1, ..., w5, b5)")
+    f, g = int(x.shape[1]), int(blocks[0][0][0].shape[0])
+    for name, v in (("F", f), ("G", g)):
+        if v % 16:
+            raise ValueError("rrdb_trunk: %s = %d is not a multiple of 16" % (name, v))
+        if v > 64:
+            raise ValueError("rrdb_trunk: %s = %d: at most 64 output channels a convolution" % (name, v))
+    if not 0.0 < float(res_scale) < float("inf"):
+        raise ValueError("rrdb_trunk: res_scale = %r is not a positive number" % (res_scale,))
+    for b in blocks:
+        for r in b:
+            for c in range(5):
+                want = (g, f + c * g, 3, 3) if c < 4 else (f, f + 4 * g, 3, 3)
+                if tuple(r[2 * c].shape) != want or tuple(r[2 * c + 1].shape) != want[:1]:
+                    raise ValueError("rrdb_trunk: conv%d holds %s / %s, expected [%d, %d, 3, 3] / [%d]"
+                                     % (c + 1, tuple(r[2 * c].shape), tuple(r[2 * c + 1].shape), want[0], want[1], want[0]))
+    params = [t for b in blocks for r in b for t in r]
+    return _RRDBTrunk.apply(x, len(blocks), float(res_scale), grad_enabled_for(x, *params), *params)
+
+
+class _RaganLoss(torch.autograd.Function):
+    """srk_ragan_loss_forward_backward: the loss and both gradient rows from one launch, with the seed contract of _Loss."""
+
+    @staticmethod
+    def forward(ctx, real, fake, for_generator):
+        lib = _lib.load()
+        require_cuda(real, fake)
+        for name, t in (("real_logits", real), ("fake_logits", fake)):
+            if not (t.dim() == 1 or (t.dim() == 2 and t.shape[1] == 1)) or t.shape[0] < 1:
+                raise ValueError("ragan_loss: %s must be [B] or [B, 1] with B >= 1, got shape %s" % (name, tuple(t.shape)))
+        if real.shape[0] != fake.shape[0]:
+            raise ValueError("ragan_loss: %d real logits vs %d fake" % (real.shape[0], fake.shape[0]))
+        real, fake = real.contiguous(), fake.contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=real.device)
+        d_real = torch.empty_like(real) if ctx.needs_input_grad[0] else None
+        d_fake = torch.empty_like(fake) if ctx.needs_input_grad[1] else None
+        seed = _LOSS_SEED[0]
+        ctx.seed_ptr, ctx.seed_value = (seed[1].data_ptr(), seed[0]) if seed is not None else (0, 1.0)
+        ctx.seed_keep = seed[1] if seed is not None else None      # (see _Loss.forward)
+        check(lib.srk_ragan_loss_forward_backward(ptr(real), ptr(fake), int(real.shape[0]), 1 if for_generator else 0,
+                                                  ctx.seed_value, ptr(loss), ptr(d_real), ptr(d_fake), None, stream_ptr()),
+              "srk_ragan_loss_forward_backward")
+        ctx.grads = (d_real, d_fake)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        grads = ctx.grads
+        if grads[0] is None and grads[1] is None:
+            return None, None, None
+        dev = (grads[0] if grads[0] is not None else grads[1]).device
+        gp = g.data_ptr()
+        if ctx.seed_ptr:
+            if gp == ctx.seed_ptr:
+                return grads[0], grads[1], None
+            g = g / ctx.seed_value
+        elif gp == unit_seed(dev).data_ptr():
+            return grads[0], grads[1], None
+        lib = _lib.load()
+        outs = []
+        for d in grads:
+            if d is None:
+                outs.append(None)
+                continue
+            out = torch.empty_like(d)
+            check(lib.srk_scale_dev(ptr(d), ptr(g.contiguous()), ptr(out), d.numel(), stream_ptr()), "srk_scale_dev")
+            outs.append(out)
+        return outs[0], outs[1], None
+
+
+def ragan_loss(real_logits, fake_logits, for_generator):
+    """The relativistic average GAN loss of ESRGAN on discriminator LOGITS ([B] or [B, 1]): with a = real - mean(fake) and
+    b = fake - mean(real), the discriminator's mean of softplus(-a) and softplus(b) or, for_generator, of softplus(a) and
+    softplus(-b); the gradient is the full derivative, the means included.  A 0-dim fp32 device tensor with the contract
+    of the other losses (loss_seed, unit seed, weighted_term, loss_sum); a detached operand gets no gradient row.
+    include/srk.h: srk_ragan_loss_forward_backward."""
+    return _RaganLoss.apply(real_logits, fake_logits, bool(for_generator))
 
 
 # ------------------------------------------------------------------------------------------------

@@ -69,7 +69,7 @@ def check_perceptual_args(args, kind):
     weight = getattr(args, "vgg_loss_weight", None)
     if weight is not None and not float(weight) >= 0.0:
         raise ValueError("vgg_loss_weight %r must be >= 0 (main.py --vgg_loss_weight)" % (weight,))
-    if (perceptual or vgg_weights) and kind != "srgan":
+    if (perceptual or vgg_weights) and kind not in ("srgan", "esrgan"):
         raise ValueError("%s: only SRGAN has a VGG feature term (main.py --model_name SRGAN)"
                          % ("perceptual" if perceptual else "vgg_weights"))
     if perceptual and not vgg_weights:
@@ -91,7 +91,7 @@ def check_lpips_args(args, kind):
                          % ("lpips_lin" if vgg else "lpips_vgg"))
     if weight > 0 and not vgg:
         raise ValueError("lpips_weight: needs the weights of the LPIPS net (main.py --lpips_vgg PATH --lpips_lin PATH)")
-    if weight > 0 and kind in ("srgan", "drcn"):
+    if weight > 0 and kind in ("srgan", "drcn", "esrgan"):
         raise ValueError("lpips_weight: %s has no LPIPS term (main.py --lpips_weight)" % kind.upper())
     if vgg and getattr(args, "num_channels", 3) != 3:
         raise ValueError("lpips_vgg: LPIPS reads RGB (main.py --num_channels 3)")
@@ -135,9 +135,9 @@ class _Trainer(object):
             setattr(self, k, getattr(args, k, None))
         self.args = args
         self.steps_per_epoch = getattr(args, "steps_per_epoch", 8)
-        if self.kind in ("srgan", "drcn") and (getattr(args, "ssim_weight", 0.0) or 0.0) > 0:
+        if self.kind in ("srgan", "drcn", "esrgan") and (getattr(args, "ssim_weight", 0.0) or 0.0) > 0:
             raise ValueError("ssim_weight: %s has no SSIM mix (main.py --ssim_weight)" % self.model_name)
-        if self.kind in ("srgan", "drcn") and (getattr(args, "fft_weight", 0.0) or 0.0) > 0:
+        if self.kind in ("srgan", "drcn", "esrgan") and (getattr(args, "fft_weight", 0.0) or 0.0) > 0:
             raise ValueError("fft_weight: %s has no frequency-domain term (main.py --fft_weight)" % self.model_name)
         check_perceptual_args(args, self.kind)
         check_lpips_args(args, self.kind)
@@ -768,6 +768,28 @@ class LapSRN(_Trainer):
 class SRGAN(_Trainer):
     """srgan.py:93-528: generator pre-training with MSE, then the adversarial loop."""
     kind = "srgan"
+    opt_kinds = ("srgan_g", "srgan_d")
+    decay_kind = "srgan"
+
+    def _normalise(self, t):
+        """What the loader's batches go through on their way to both phases (srgan.py:193-194,257-258)."""
+        return utils.norm(t, vgg=True)
+
+    def _pretrain_step(self, g_opt, g_dp):
+        """The generator's pre-training step (srgan.py:179-219: MSE)."""
+        return trainers.mse_step(self.G, g_opt, g_dp)
+
+    def _adversarial_step(self, g_opt, d_opt, g_dp, d_dp):
+        """The adversarial step (two models, two optimizers); data parallel: cut at the two exchanges.
+        --vgg_weights: the reference's VGG content term in the logged G loss; --perceptual: the term trains G."""
+        fe = None
+        if getattr(self.args, "vgg_weights", None):
+            fe = models.FeatureExtractor().load_vgg19(self.args.vgg_weights).to(self.device)
+        vgg_w = getattr(self.args, "vgg_loss_weight", None)
+        return trainers.srgan_step(self.G, self.D, g_opt, d_opt, g_dp, d_dp, feature_extractor=fe, lazy_pack=True,
+                                   prune_dead_grads=bool(getattr(self.args, "prune_dead_grads", False)),
+                                   perceptual=bool(getattr(self.args, "perceptual", False)),
+                                   vgg_weight=6e-3 if vgg_w is None else float(vgg_w))
 
     def build_model(self):
         self.G = models.SRGANGenerator(self.num_channels, 64, 16)                 # srgan.py:136
@@ -788,8 +810,8 @@ class SRGAN(_Trainer):
         self.G.to(self.device).train()
         self.D.to(self.device).train()
         g_flat, d_flat = optim.FlatParams(self.G), optim.FlatParams(self.D)
-        g_opt = self.g_opt = optim.make_optimizer("srgan_g", g_flat, self.lr, ema_decay=self.ema_decay)   # (the EMA is G's)
-        d_opt = self.d_opt = optim.make_optimizer("srgan_d", d_flat, self.lr)
+        g_opt = self.g_opt = optim.make_optimizer(self.opt_kinds[0], g_flat, self.lr, ema_decay=self.ema_decay)   # (the EMA is G's)
+        d_opt = self.d_opt = optim.make_optimizer(self.opt_kinds[1], d_flat, self.lr)
         g_dp = d_dp = None
         if self.world > 1:
             g_dp, d_dp = dpmod.DataParallel(g_flat), dpmod.DataParallel(d_flat)
@@ -799,7 +821,7 @@ class SRGAN(_Trainer):
             if getattr(self.args, "sync_bn", False):   # statistics of the global batch (SURVEY.md 8e caveat)
                 trainers.sync_batchnorm(self.G)
                 trainers.sync_batchnorm(self.D)
-        norm = lambda t: utils.norm(t, vgg=True)   # srgan.py:193-194,257-258
+        norm = self._normalise
 
         self.data_source = "loader"
         if loader is None:
@@ -835,7 +857,7 @@ class SRGAN(_Trainer):
             g_flat.mark_changed()      # parameters changed behind the optimizer's back: re-pack filters
             g_opt.ema_reset()          # ... and the shadow weights start from them
         else:
-            pre_step = graphed(trainers.mse_step(self.G, g_opt, g_dp), [g_flat])
+            pre_step = graphed(self._pretrain_step(g_opt, g_dp), [g_flat])
             for epoch in range(pre_done, self.epoch_pretrain):
                 for y_, x_ in batches(77 + epoch):
                     pre_step(y_, x_)
@@ -848,18 +870,9 @@ class SRGAN(_Trainer):
             self.phase = "adversarial"
             self.save_state(0, [], loader, phase=self.phase)
         # the adversarial step (two models, two optimizers) as one hipGraph; data parallel: graphs split at the two exchanges
-        # --vgg_weights: the reference's VGG content term in the logged G loss; --perceptual: the term trains G
-        fe = None
-        if getattr(self.args, "vgg_weights", None):
-            fe = models.FeatureExtractor().load_vgg19(self.args.vgg_weights).to(self.device)
-        vgg_w = getattr(self.args, "vgg_loss_weight", None)
-        step = graphed(trainers.srgan_step(self.G, self.D, g_opt, d_opt, g_dp, d_dp, feature_extractor=fe, lazy_pack=True,
-                                           prune_dead_grads=bool(getattr(self.args, "prune_dead_grads", False)),
-                                           perceptual=bool(getattr(self.args, "perceptual", False)),
-                                           vgg_weight=6e-3 if vgg_w is None else float(vgg_w)),
-                       [g_flat, d_flat])
+        step = graphed(self._adversarial_step(g_opt, d_opt, g_dp, d_dp), [g_flat, d_flat])
         for epoch in range(done, self.num_epochs):
-            apply_lr_decay("srgan", epoch, g_opt, d_opt)   # srgan.py:239-244: both learning rates /10 every 20 epochs
+            apply_lr_decay(self.decay_kind, epoch, g_opt, d_opt)   # srgan.py:239-244: both learning rates /10 every 20 epochs
             d_tot, g_tot, n = torch.zeros((), device=self.device), torch.zeros((), device=self.device), 0
             for y_, x_ in batches(1234 + epoch):
                 d_loss, g_loss = step(y_, x_)
@@ -914,6 +927,86 @@ class SRGAN(_Trainer):
             print('Trained generator model is loaded.')
             return True
         return False
+
+
+class ESRGAN(SRGAN):
+    """ESRGAN (Wang et al., ECCV-W 2018; not in the reference collection) on SRGAN's two-phase trainer: models.RRDBNet
+    (`--rrdb_blocks` blocks of growth `--rrdb_growth`, 64 trunk channels) pre-trained with L1 for `--epoch_pretrain` epochs
+    into the same `_G_param_pretrain.pkl`, then trainers.esrgan_step against models.ESRGANDiscriminator with
+    `--pixel_weight` * L1 + `--vgg_loss_weight` * the conv5_4 feature L1 + `--gan_weight` * the relativistic average loss;
+    both optimizers Adam at --lr, no learning-rate decay rule of its own.  Batches stay in [0, 1] (the feature term
+    normalises once).  x4 only; one GPU; `--tile` is refused (the exact halo of 23 blocks is about 350 LR pixels: the
+    tiles would be mostly halo); `--net_interp A` evaluates (1 - A) * the pre-trained + A * the adversarial generator."""
+    kind = "esrgan"
+    opt_kinds = ("esrgan_g", "esrgan_d")
+    decay_kind = None
+
+    def __init__(self, args):
+        if getattr(args, "tile", None) is not None:
+            raise ValueError("tile: the RRDB trunk's receptive field (about 350 LR pixels for 23 blocks) leaves a tile mostly "
+                             "halo; ESRGAN's pictures run in one pass (main.py --tile)")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise NotImplementedError("ESRGAN trains on one GPU: data parallelism is not implemented for it (launch "
+                                      "main.py without torch.distributed.run)")
+        if getattr(args, "scale_factor", 4) != 4:
+            raise ValueError("scale_factor %r: RRDBNet upsamples by 4 only (main.py --scale_factor 4)" % (args.scale_factor,))
+        if getattr(args, "perceptual", False):
+            raise ValueError("perceptual: ESRGAN's feature term always trains the generator (drop main.py --perceptual)")
+        interp = getattr(args, "net_interp", None)
+        if interp is not None and not 0.0 <= float(interp) <= 1.0:
+            raise ValueError("net_interp %r is not in [0, 1] (main.py --net_interp)" % (interp,))
+        super(ESRGAN, self).__init__(args)
+        self.blocks = int(getattr(args, "rrdb_blocks", None) or 23)
+        self.growth = int(getattr(args, "rrdb_growth", None) or 32)
+        w = lambda name, default: default if getattr(args, name, None) is None else float(getattr(args, name))
+        self.gan_weight, self.pixel_weight = w("gan_weight", 5e-3), w("pixel_weight", 1e-2)
+        self.vgg_weight = w("vgg_loss_weight", 1.0)
+        self.net_interp = None if interp is None else float(interp)
+
+    def build_model(self):
+        self.G = models.RRDBNet(self.num_channels, 64, self.blocks, self.growth, self.scale_factor)
+        self.D = models.ESRGANDiscriminator(self.num_channels, 64, self.crop_size)
+        return self.G
+
+    def _normalise(self, t):
+        return t
+
+    def _pretrain_step(self, g_opt, g_dp):
+        return trainers.l1_step(self.G, g_opt, g_dp)
+
+    def _adversarial_step(self, g_opt, d_opt, g_dp, d_dp):
+        fe = models.FeatureExtractor(feature_layer=34).load_vgg19(self.args.vgg_weights).to(self.device)
+        return trainers.esrgan_step(self.G, self.D, g_opt, d_opt, fe, self.pixel_weight, self.vgg_weight, self.gan_weight)
+
+    def train(self, loader=None, pretrain_epochs=None, log_every=0):
+        if not getattr(self.args, "vgg_weights", None):
+            raise ValueError("vgg_weights: ESRGAN's adversarial phase trains on VGG19 conv5_4 features and needs the "
+                             "weights to extract them with (main.py --vgg_weights PATH, a torchvision vgg19 state_dict)")
+        if self.num_channels != 3:
+            raise ValueError("num_channels %r: ESRGAN's feature term reads RGB (main.py --num_channels 3)" % (self.num_channels,))
+        return super(ESRGAN, self).train(loader, pretrain_epochs, log_every)
+
+    def load_model(self, is_pretrain=False):
+        """The generator's checkpoint; with net_interp A (evaluation only) the blend (1 - A) * pre-trained + A * adversarial
+        of the two files, made on the device by srk_axpby.  A missing file is an error that names it."""
+        if is_pretrain or self.net_interp is None:
+            return super(ESRGAN, self).load_model(is_pretrain)
+        g_name, _, pre = self._names(None)
+        if self.use_ema:
+            g_name = _ema_name(g_name)
+        for name in (pre, g_name):
+            if not os.path.exists(name):
+                raise FileNotFoundError("--net_interp: no generator checkpoint at %r" % (name,))
+        a = self.net_interp
+        theta_pre = torch.load(pre, map_location="cpu")
+        theta_gan = torch.load(g_name, map_location="cpu")
+        blend = {}
+        for k, v in self.G.state_dict().items():
+            p, q = theta_pre[k].to(self.device).contiguous(), theta_gan[k].to(self.device).contiguous()
+            blend[k] = ops._axpby(p, q, 1.0 - a, a) if v.is_floating_point() else q
+        self.G.load_state_dict(blend)
+        print('Interpolated generator model is loaded (%g of the adversarial one).' % a)
+        return True
 
 
 class DRCN(_Trainer):
@@ -1067,4 +1160,4 @@ class SwinIR(_Trainer):
 
 
 TRAINERS = {"SRCNN": SRCNN, "VDSR": VDSR, "ESPCN": ESPCN, "FSRCNN": FSRCNN, "SRGAN": SRGAN, "LapSRN": LapSRN, "EDSR": EDSR,
-            "DRCN": DRCN, "RCAN": RCAN, "RDN": RDN, "SwinIR": SwinIR}
+            "DRCN": DRCN, "RCAN": RCAN, "RDN": RDN, "SwinIR": SwinIR, "ESRGAN": ESRGAN}

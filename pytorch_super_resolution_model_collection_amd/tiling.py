@@ -202,6 +202,9 @@ def _walk(g, m, path):
         # live while the block runs: its input, the growth buffer and its output
         live = (2 * m.G0 + m.C * m.G) * g.scale ** 2
         return Geometry(out.scale, out.offset, out.lo, out.hi, max(out.floats_per_pixel, live))
+    if isinstance(m, B.RRDB):   # 15 chained 3x3 convs a block: 23 blocks reach about 350 input pixels to each side
+        raise ValueError("%s: RRDB: the trunk's dependency cone (15 pixels a block to each side) leaves a tile mostly halo; "
+                         "ESRGAN's pictures run in one pass" % path)
     if isinstance(m, torch.nn.ConvTranspose2d):
         return _deconv(g, m, path)
     if isinstance(m, torch.nn.Conv2d):
@@ -269,6 +272,8 @@ def net_geometry(model):
         fused = Geometry(fused.scale, fused.offset, fused.lo, fused.hi, max(fused.floats_per_pixel, live))
         out = _union(_walk(fused, model.GFF, "GFF"), head, "GFF")
         return _walk(out, model.UPNet, "UPNet")
+    if isinstance(model, M.RRDBNet):   # raises at the first RRDB
+        return _walk(_walk(g, model.conv_first, "conv_first"), model.body[0], "body.0")
     if isinstance(model, M.LapSRNNet):
         f1 = _walk(_walk(g, model.input_conv, "input_conv"), model.convt_F1, "convt_F1")
         coarse = _union(_walk(f1, model.convt_R1, "convt_R1"), _walk(g, model.convt_I1, "convt_I1"), "convt_R1")

@@ -326,6 +326,73 @@ def srgan_segments(G, D, g_opt, d_opt, g_dp=None, d_dp=None, lazy_pack=False, fe
     return [(seg_d, d_dp), (seg_g, g_dp), (seg_u, None)]
 
 
+def esrgan_step(G, D, g_opt, d_opt, feature_extractor, pixel_weight=1e-2, vgg_weight=1.0, gan_weight=5e-3):
+    """The adversarial step of ESRGAN as the eager closure of `esrgan_segments` (see there)."""
+    return eager_step(esrgan_segments(G, D, g_opt, d_opt, feature_extractor, pixel_weight, vgg_weight, gan_weight))
+
+
+def esrgan_segments(G, D, g_opt, d_opt, feature_extractor, pixel_weight=1e-2, vgg_weight=1.0, gan_weight=5e-3):
+    """ESRGAN's adversarial step (Wang et al., ECCV-W 2018) in the order BasicSR's model runs it, for batches in [0, 1]:
+      G step, D's parameters frozen:   fake = G(lr)
+          g_loss = pixel_weight * L1(fake, hr) + vgg_weight * L1(vgg(norm(fake)), vgg(norm(hr)))
+                   + gan_weight * ragan(D(hr).detach(), D(fake), for the generator)          backward, g_opt.step()
+      D step:   d_loss = ragan(D(hr), D(fake.detach()), for the discriminator)              backward, d_opt.step()
+    -> (d_loss, g_loss), the order srgan_segments returns them in.  ragan = ops.ragan_loss, the relativistic average loss on
+    D's logits (models.ESRGANDiscriminator) with the gradient through both batch means -- the paper's and the original
+    code's D step, not BasicSR's later split one.  feature_extractor: models.FeatureExtractor(feature_layer=34), conv5_4
+    before its ReLU; its term is ops.perceptual_loss(criterion='l1') and normalises the batch once.  D runs in training
+    mode throughout (its BatchNorm statistics move in both steps, as there).  The three gradients of `fake` are added by
+    srk_axpby (ops.fork) and the loss terms by ops.loss_sum with each weight folded into its loss kernel
+    (ops.weighted_term): no ATen arithmetic node in a captured step.  One GPU: two segments without an exchange."""
+    pixel_weight, vgg_weight, gan_weight = float(pixel_weight), float(vgg_weight), float(gan_weight)
+    if feature_extractor is None:
+        raise ValueError("esrgan step: needs a feature_extractor (models.FeatureExtractor(feature_layer=34) with its weights)")
+    for name, v in (("pixel_weight", pixel_weight), ("vgg_weight", vgg_weight), ("gan_weight", gan_weight)):
+        if not 0.0 <= v < float("inf"):
+            raise ValueError("esrgan step: %s %r is not a non-negative finite number" % (name, v))
+    out = {}
+    d_params = [p for p in D.parameters()]
+
+    def freeze_d(flag):
+        for p in d_params:
+            p.requires_grad_(not flag)
+
+    def percep(pred, target):
+        return ops.perceptual_loss(pred, target, feature_extractor, normalize=True, criterion='l1')
+
+    def gan_g(fake_logits, real_logits):
+        return ops.ragan_loss(real_logits, fake_logits, True)
+
+    def seg_g(lr_img, hr_img):
+        g_opt.zero_grad()
+        fake = G(lr_img)
+        f_gan, rest = ops.fork(fake)       # three consumers: their gradients are added by srk_axpby
+        f_pix, f_vgg = ops.fork(rest)
+        out["fake"] = fake.detach()
+        freeze_d(True)
+        try:
+            real_logits = D(hr_img).detach()
+            l_gan = ops.weighted_term(gan_g, gan_weight, D(f_gan), real_logits)
+        finally:
+            freeze_d(False)
+        l_pix = ops.weighted_term(ops.l1_loss, pixel_weight, f_pix, hr_img)
+        l_vgg = ops.weighted_term(percep, vgg_weight, f_vgg, hr_img)
+        g_loss = ops.loss_sum(ops.loss_sum(l_pix, l_vgg, pixel_weight, vgg_weight), l_gan, 1.0, gan_weight)
+        _backward(g_loss, None)
+        g_opt.step()
+        out["g"] = g_loss
+        return g_loss
+
+    def seg_d(lr_img, hr_img):
+        d_opt.zero_grad()
+        d_loss = ops.ragan_loss(D(hr_img), D(out.pop("fake")), False)
+        _backward(d_loss, None)
+        d_opt.step()
+        return d_loss, out.pop("g")
+
+    return [(seg_g, None), (seg_d, None)]
+
+
 def _capture(graph, pool=None):
     """torch.cuda.graph with capture_error_mode="thread_local": ProcessGroupNCCL's watchdog thread polls the events of
     earlier collectives (hipEventQuery) at its own pace, and under the default "global" mode a query that lands while
