@@ -1076,6 +1076,68 @@ int srk_layer_norm_backward(const float* dy, const float* x, const float* gamma,
 int srk_gelu_forward(const float* x, float* y, size_t n, void* stream);
 int srk_gelu_backward(const float* dy, const float* x, float* dx, size_t n, void* stream);
 
+/* ---- Spectral normalisation of filters: Real-ESRGAN's U-Net discriminator (csrc/spectral_norm.hip) -------------------
+ * (Additive again: new entry points only, srk_version() and everything existing unchanged.)
+ * torch.nn.utils.spectral_norm(conv, n_power_iterations=1, eps, dim=0).  W is the dense [R][K] view of a filter, R = out
+ * channels, K = in * kh * kw; u [R] and v [K] are the fp32 buffers of the power iteration.
+ *   training:  v <- W^T u / max(||W^T u||, eps)   u <- W v / max(||W v||, eps)   (both written back in place)
+ *   then       sigma = u . (W v)                  w_sn = W / sigma
+ *   eval:      no update; sigma from the stored u and v.
+ *   backward:  u, v constants; with G = dL/dw_sn:  dW = (G - <G, w_sn> u v^T) / sigma.
+ * `saved` (R + K + 1 floats, or NULL): the u, v and sigma of THIS forward, for its backward: two forwards between two
+ * optimizer steps have different ones.  Every dot product and norm is a double sum in an order that is a function of the
+ * shape alone, through per-block partials; no atomics; u, v and w_sn are stored fp32 and used as stored.
+ * srk_spectral_norm_forward: n <= SRK_SPECTRAL_MAX_LAYERS layers in three launches (two in eval mode); K <= 16384;
+ *   workspace of srk_spectral_norm_workspace(layers, n) bytes, 8-byte aligned.
+ * srk_spectral_norm_backward: one layer in two launches; dW = beta * dW + gradient (beta == 0 never reads dW); workspace of
+ *   srk_spectral_norm_backward_workspace(R, K) bytes, 8-byte aligned.
+ * 16-byte accesses along K where K % 4 == 0 and the pointers are 16-byte aligned, else 4-byte accesses.
+ * srk_spectral_norm_host: one layer on host pointers from the same formulas (spectral_norm_common.h), u / v / results in
+ *   double; u and v are updated in place in training mode; G and dW come together or are both NULL. */
+#define SRK_SPECTRAL_MAX_LAYERS 16
+typedef struct srk_spectral_layer {
+  const float* W;            /* [R][K] */
+  float* u;                  /* [R] */
+  float* v;                  /* [K] */
+  float* w_sn;               /* [R][K] out */
+  float* saved;              /* [R + K + 1] out: u, v, sigma of this forward; or NULL */
+  int32_t R, K;
+} srk_spectral_layer;
+size_t srk_spectral_norm_workspace(const srk_spectral_layer* layers, int n);
+int srk_spectral_norm_forward(const srk_spectral_layer* layers, int n, int training, double eps, void* workspace,
+                              size_t workspace_bytes, void* stream);
+size_t srk_spectral_norm_backward_workspace(int R, int K);
+int srk_spectral_norm_backward(const float* G, const float* w_sn, const float* saved, int R, int K, float* dW, float beta,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int srk_spectral_norm_host(const float* W, int R, int K, int training, double eps, double* u, double* v, double* w_sn,
+                           double* sigma, const double* G, double* dW);
+
+/* ---- Bilinear x2 upsampling with a fused skip addition (csrc/bilinear.hip, csrc/bilinear_common.h) -------------------
+ * y = F.interpolate(x + add, scale_factor=2, mode='bilinear', align_corners=False) on dense NHWC: x, add [N][H][W][C]
+ * (add may be NULL), y [N][2H][2W][C].  Per axis of n inputs: output 2k reads (k - 1, k) with weights (0.25, 0.75), index 0
+ * alone for k = 0; output 2k + 1 reads (k, min(k + 1, n - 1)) with (0.75, 0.25).
+ * backward: dx = the adjoint applied to dy, in gather form: every dx element is written once and adds its at most 4 x 4
+ * outputs in index order; no atomics.  dx is the gradient of x and of add alike.
+ * 16-byte accesses along C where C % 4 == 0 and the pointers are 16-byte aligned, else 4-byte accesses.
+ * srk_upsample_bilinear2x_host: both halves in double on host pointers; x and y, dy and dx come in pairs, a NULL pair is skipped. */
+int srk_upsample_bilinear2x_forward(const float* x, const float* add, float* y, int N, int H, int W, int C, void* stream);
+int srk_upsample_bilinear2x_backward(const float* dy, float* dx, int N, int H, int W, int C, void* stream);
+int srk_upsample_bilinear2x_host(const float* x, const float* add, const float* dy, int N, int H, int W, int C, double* y,
+                                 double* dx);
+
+/* ---- Vanilla GAN loss on logits (csrc/gan_logit.hip, csrc/ragan_common.h) --------------------------------------------
+ * n >= 1 logits of any shape, dense.  sp(x) = max(x, 0) + log1p(exp(-|x|)):
+ *   target_is_real != 0   L = mean sp(-x)      d_logits = grad_scale * -sigmoid(-x) / n
+ *   target_is_real == 0   L = mean sp(x)       d_logits = grad_scale * sigmoid(x) / n
+ * One pass writes the gradient and per-block double partials (the grid is a function of n), one block finishes them in a
+ * fixed order; no atomics.  d_logits may be NULL.  workspace: srk_gan_logit_loss_workspace_bytes() bytes, 8-byte aligned.
+ * srk_gan_logit_loss_host: the same formulas on host pointers, results in double. */
+size_t srk_gan_logit_loss_workspace_bytes(void);
+int srk_gan_logit_loss_forward_backward(const float* logits, size_t n, int target_is_real, float grad_scale, float* loss,
+                                        float* d_logits, void* workspace, void* stream);
+int srk_gan_logit_loss_host(const float* logits, size_t n, int target_is_real, double grad_scale, double* loss,
+                            double* d_logits);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,10 @@ classical net, 180 channels, 6 x 6 layers, 6 heads, window 8, ratio 2); every fl
 GAN loss, which needs --vgg_weights PATH (conv5_4 features before the ReLU).  x4, RGB, one GPU; no --tile, --ssim_weight,
 --fft_weight or --lpips_weight.  --net_interp A (with --test_only / --test_single) evaluates the blend
 (1 - A) * pre-trained + A * adversarial generator, 0 <= A <= 1.
+--discriminator {vgg,unet} (ESRGAN; default vgg): unet trains against Real-ESRGAN's U-Net discriminator with spectral
+normalisation (models.UNetDiscriminatorSN, --unet_feat F channels, default 64; one logit a pixel, so any --crop_size that is
+a multiple of 8) on --gan_type vanilla (ops.gan_logit_loss; the default with unet, where ragan is refused; ragan stays the
+default with vgg).  Real-ESRGAN's degradation model, its multi-layer VGG term and data parallelism are not part of it.
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N main.py ..."""
 import argparse
 import os
@@ -400,8 +404,33 @@ def parse_args(argv=None):
     p.add_argument('--net_interp', type=_net_interp, default=None, metavar='A',
                    help='ESRGAN, with --test_only / --test_single: evaluate (1 - A) * the pre-trained generator + A * the '
                         'adversarially trained one (network interpolation of the ESRGAN paper); A in [0, 1]')
+    p.add_argument('--discriminator', type=str, default=None, choices=['vgg', 'unet'],
+                   help='ESRGAN: the discriminator of the adversarial phase: vgg (default; SRGAN\'s body ending in a logit) '
+                        'or unet (Real-ESRGAN\'s U-Net with spectral normalisation, one logit a pixel, any --crop_size that '
+                        'is a multiple of 8)')
+    p.add_argument('--gan_type', type=str, default=None, choices=['ragan', 'vanilla'],
+                   help='ESRGAN: the GAN loss on the discriminator\'s logits: ragan (relativistic average; default with '
+                        '--discriminator vgg) or vanilla (default with, and the only one for, --discriminator unet)')
+    p.add_argument('--unet_feat', type=_positive, default=None, metavar='F',
+                   help='ESRGAN with --discriminator unet: channels of the U-Net\'s first layer (default 64)')
     args = p.parse_args(argv)
     esrgan = args.model_name == 'ESRGAN'
+    for flag in ('discriminator', 'gan_type', 'unet_feat'):
+        if getattr(args, flag) is not None and not esrgan:
+            p.error('--%s: only ESRGAN chooses its discriminator and GAN loss, not %s' % (flag, args.model_name))
+    if esrgan:
+        if args.unet_feat is not None and args.discriminator != 'unet':
+            p.error('--unet_feat: only the U-Net discriminator has a feature count to set (pass --discriminator unet)')
+        if args.discriminator == 'unet' and args.gan_type == 'ragan':
+            p.error('--gan_type ragan: the relativistic average loss takes one logit a sample, the U-Net discriminator '
+                    'gives one a pixel (use --gan_type vanilla with --discriminator unet)')
+        if args.discriminator == 'unet' and args.crop_size % 8:
+            p.error('--crop_size %d is not a multiple of 8, which the three stride-2 stages of --discriminator unet need'
+                    % args.crop_size)
+        args.discriminator = args.discriminator or 'vgg'
+        args.gan_type = args.gan_type or ('vanilla' if args.discriminator == 'unet' else 'ragan')
+        if args.discriminator == 'unet' and args.unet_feat is None:
+            args.unet_feat = 64
     if args.vgg_loss_weight is None:
         args.vgg_loss_weight = 1.0 if esrgan else 6e-3
     if esrgan:

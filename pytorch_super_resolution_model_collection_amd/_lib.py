@@ -100,6 +100,15 @@ class DensePlan(_Sized):
                 ("split_pixels", ctypes.c_int64), ("ws_bytes", ctypes.c_uint64), ("partial_floats", ctypes.c_uint64)]
 
 
+SPECTRAL_MAX_LAYERS = 16   # SRK_SPECTRAL_MAX_LAYERS
+
+
+class SpectralLayer(ctypes.Structure):
+    """struct srk_spectral_layer (srk_spectral_norm_forward)"""
+    _fields_ = [("W", c_vp), ("u", c_vp), ("v", c_vp), ("w_sn", c_vp), ("saved", c_vp), ("R", ctypes.c_int32),
+                ("K", ctypes.c_int32)]
+
+
 class PhaseAxis(_Sized):
     """struct srk_phase_axis (srk_trans_phase_axis)"""
     _fields_ = [("struct_size", ctypes.c_uint32)] + [(n, ctypes.c_int32) for n in ("o0", "P", "Kv", "i0", "w0", "wd")]
@@ -309,6 +318,18 @@ _PROTOTYPES = {
     "srk_layer_norm_backward": (c_int, [c_f] * 8 + [c_float, ctypes.c_int64, c_int, c_vp, c_size, c_vp]),
     "srk_gelu_forward": (c_int, [c_f, c_f, c_size, c_vp]),
     "srk_gelu_backward": (c_int, [c_f, c_f, c_f, c_size, c_vp]),
+    "srk_spectral_norm_workspace": (c_size, [ctypes.POINTER(SpectralLayer), c_int]),
+    "srk_spectral_norm_forward": (c_int, [ctypes.POINTER(SpectralLayer), c_int, c_int, ctypes.c_double, c_vp, c_size, c_vp]),
+    "srk_spectral_norm_backward_workspace": (c_size, [c_int, c_int]),
+    "srk_spectral_norm_backward": (c_int, [c_f, c_f, c_f, c_int, c_int, c_f, c_float, c_vp, c_size, c_vp]),
+    "srk_spectral_norm_host": (c_int, [c_vp, c_int, c_int, c_int, ctypes.c_double, c_vp, c_vp, c_vp,
+                                       ctypes.POINTER(ctypes.c_double), c_vp, c_vp]),
+    "srk_upsample_bilinear2x_forward": (c_int, [c_f, c_f, c_f, c_int, c_int, c_int, c_int, c_vp]),
+    "srk_upsample_bilinear2x_backward": (c_int, [c_f, c_f, c_int, c_int, c_int, c_int, c_vp]),
+    "srk_upsample_bilinear2x_host": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "srk_gan_logit_loss_workspace_bytes": (c_size, []),
+    "srk_gan_logit_loss_forward_backward": (c_int, [c_f, c_size, c_int, c_float, c_f, c_f, c_vp, c_vp]),
+    "srk_gan_logit_loss_host": (c_int, [c_vp, c_size, c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_double), c_vp]),
 }
 
 _lib = None

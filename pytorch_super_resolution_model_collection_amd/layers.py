@@ -165,6 +165,42 @@ class TokenLinear(torch.nn.Linear):
         return self.run(x)
 
 
+class SpectralNormConv2d(torch.nn.Module):
+    """A bias-free convolution under torch.nn.utils.spectral_norm (the legacy hook form, one power iteration, eps 1e-12,
+    dim 0) with the names that form gives a state_dict: parameter `weight_orig` [out, in, kh, kw], buffers `weight_u` [out]
+    and `weight_v` [in * kh * kw], both initialised as torch does (normalised standard normals).  The normalised filter is
+    computed by ops.spectral_norm -- by the owning model for all its layers in one call (models.UNetDiscriminatorSN), or
+    by this layer alone -- and handed to `run`, which is an ordinary ops.conv2d on it; it is not a layers.Conv2d, so
+    optim.PackPlan packs nothing for it and its filter is packed per call, as TokenLinear's."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0):
+        super(SpectralNormConv2d, self).__init__()
+        k = int(kernel_size)
+        self.in_channels, self.out_channels, self.kernel_size = int(in_channels), int(out_channels), (k, k)
+        self._s, self._p = int(stride), int(padding)
+        self.weight_orig = torch.nn.Parameter(torch.empty(self.out_channels, self.in_channels, k, k))
+        torch.nn.init.kaiming_uniform_(self.weight_orig, a=5 ** 0.5)        # nn.Conv2d.reset_parameters
+        norm = lambda t: t / t.norm().clamp_min(ops.SPECTRAL_EPS)
+        self.register_buffer("weight_u", norm(torch.randn(self.out_channels)))
+        self.register_buffer("weight_v", norm(torch.randn(self.in_channels * k * k)))
+
+    def spectral_layer(self):
+        """(weight_orig, u, v) as ops.spectral_norm takes it."""
+        return (self.weight_orig, self.weight_u, self.weight_v)
+
+    def run(self, x, w_sn=None, act=ACT_NONE, slope=0.0):
+        """conv(x, w_sn) with a fused activation; w_sn: this layer's filter from ops.spectral_norm (None: computed here)."""
+        if w_sn is None:
+            w_sn = ops.spectral_norm([self.spectral_layer()], self.training)[0]
+        cfg = ops.ConvCfg(self._s, self._p, False, 0, act, slope, 0)
+        if grad_mode(x, w_sn):
+            return ops.conv2d(x, w_sn, None, None, cfg)
+        return ops.conv2d_infer(x, w_sn.detach(), None, None, cfg)
+
+    def forward(self, x):
+        return self.run(x)
+
+
 class LayerNorm(torch.nn.LayerNorm):
     """nn.LayerNorm(C) surface over the channels of a logical [N, C, H, W] channels_last map (= the last axis of its NHWC
     storage) or the last axis of a [rows, C] tensor, on ops.layer_norm."""

@@ -570,6 +570,62 @@ class ESRGANDiscriminator(SRGANDiscriminator):
             DenseBlock(base_filter * 16, 1, activation=None, norm=None))
 
 
+class UNetDiscriminatorSN(nn.Module):
+    """Real-ESRGAN's U-Net discriminator with spectral normalisation (Wang et al., ICCVW 2021; not in the reference
+    collection), under the names its checkpoints carry: conv0 (3x3, bias), conv1..3 (4x4 stride 2), conv4..6 (3x3 behind a
+    bilinear x2), conv7, conv8 (3x3), all bias-free under spectral norm (`weight_orig`, `weight_u`, `weight_v`), conv9
+    (3x3 to one channel, bias).  Leaky ReLU 0.2 in every conv's epilogue but the last; skips x4 += x2, x5 += x1, x6 += x0.
+    Fully convolutional: [B, C, H, W] -> [B, 1, H, W] logits for H and W multiples of 8; no BatchNorm.
+    All eight normalised filters come from ONE ops.spectral_norm call at the top of forward (three launches); two skip
+    additions ride in the next upsample's read (ops.upsample_bilinear2x(add=)), the third is ops.add."""
+
+    SN_LAYERS = ("conv1", "conv2", "conv3", "conv4", "conv5", "conv6", "conv7", "conv8")
+
+    def __init__(self, num_in_ch=3, num_feat=64, skip_connection=True):
+        super(UNetDiscriminatorSN, self).__init__()
+        from .layers import SpectralNormConv2d as SN
+        f = int(num_feat)
+        self.num_in_ch, self.num_feat, self.skip_connection = int(num_in_ch), f, bool(skip_connection)
+        self.conv0 = Conv2d(num_in_ch, f, 3, 1, 1)
+        self.conv1 = SN(f, 2 * f, 4, 2, 1)
+        self.conv2 = SN(2 * f, 4 * f, 4, 2, 1)
+        self.conv3 = SN(4 * f, 8 * f, 4, 2, 1)
+        self.conv4 = SN(8 * f, 4 * f, 3, 1, 1)
+        self.conv5 = SN(4 * f, 2 * f, 3, 1, 1)
+        self.conv6 = SN(2 * f, f, 3, 1, 1)
+        self.conv7 = SN(f, f, 3, 1, 1)
+        self.conv8 = SN(f, f, 3, 1, 1)
+        self.conv9 = Conv2d(f, 1, 3, 1, 1)
+
+    def weight_init(self, mean=0.0, std=0.02):
+        """Real-ESRGAN trains this net from torch's default initialisation, which the constructors have already drawn."""
+        return None
+
+    def forward(self, x):
+        if x.dim() != 4 or x.shape[1] != self.num_in_ch:
+            raise ValueError("UNetDiscriminatorSN: takes [B, %d, H, W], got shape %s" % (self.num_in_ch, tuple(x.shape)))
+        for name, v in (("H", x.shape[2]), ("W", x.shape[3])):
+            if v % 8 or v < 8:
+                raise ValueError("UNetDiscriminatorSN: %s = %d is not a multiple of 8 (three stride-2 stages)" % (name, v))
+        lrelu = dict(act=ACT_LRELU, slope=0.2)
+        training = _training_graph(self, x)
+        w = ops.spectral_norm([getattr(self, n).spectral_layer() for n in self.SN_LAYERS], self.training)
+        split = ops.fork if (training and self.skip_connection) else (lambda t: (t, t))
+        x0, s0 = split(self.conv0.run(x, **lrelu))
+        x1, s1 = split(self.conv1.run(x0, w[0], **lrelu))
+        x2, s2 = split(self.conv2.run(x1, w[1], **lrelu))
+        x3 = self.conv3.run(x2, w[2], **lrelu)
+        skip = self.skip_connection
+        x4 = self.conv4.run(ops.upsample_bilinear2x(x3), w[3], **lrelu)
+        x5 = self.conv5.run(ops.upsample_bilinear2x(x4, s2 if skip else None), w[4], **lrelu)
+        x6 = self.conv6.run(ops.upsample_bilinear2x(x5, s1 if skip else None), w[5], **lrelu)
+        if skip:
+            x6 = ops.add(x6, s0)
+        out = self.conv7.run(x6, w[6], **lrelu)
+        out = self.conv8.run(out, w[7], **lrelu)
+        return self.conv9.run(out)
+
+
 class _MaxPool2x2(nn.MaxPool2d):
     """nn.MaxPool2d(kernel_size=2, stride=2) surface (vgg19.features[4]) on srk_maxpool2x2_forward."""
 

@@ -3248,6 +3248,172 @@ def ragan_loss(real_logits, fake_logits, for_generator):
 
 
 # ------------------------------------------------------------------------------------------------
+# The operators of Real-ESRGAN's U-Net discriminator: spectral normalisation, bilinear x2, the vanilla GAN loss on logits
+# (csrc/spectral_norm.hip, csrc/bilinear.hip, csrc/gan_logit.hip)
+# ------------------------------------------------------------------------------------------------
+SPECTRAL_EPS = 1e-12
+
+
+class _SpectralForward(object):
+    """What one layer's backward reads of the forward it belongs to: its own w_sn and its own copy of (u, v, sigma)."""
+    __slots__ = ("w_sn", "saved", "R", "K")
+
+
+def _spectral_forward_raw(layers, training):
+    """One srk_spectral_norm_forward call for all `layers` = [(weight_orig, u, v), ...] -> [_SpectralForward, ...]."""
+    lib = _lib.load()
+    if not 1 <= len(layers) <= _lib.SPECTRAL_MAX_LAYERS:
+        raise ValueError("spectral_norm: %d layers, 1 .. %d go into one call" % (len(layers), _lib.SPECTRAL_MAX_LAYERS))
+    table = (_lib.SpectralLayer * len(layers))()
+    outs = []
+    for i, (w, u, v) in enumerate(layers):
+        require_cuda(w, u, v)
+        if w.dim() < 2 or not w.is_contiguous():
+            raise ValueError("spectral_norm: layer %d: the weight must be dense with at least two axes, got shape %s"
+                             % (i, tuple(w.shape)))
+        R, K = int(w.shape[0]), int(w.numel() // w.shape[0])
+        if tuple(u.shape) != (R,) or tuple(v.shape) != (K,) or not u.is_contiguous() or not v.is_contiguous():
+            raise ValueError("spectral_norm: layer %d: u %s / v %s do not match the [%d, %d] view of the weight"
+                             % (i, tuple(u.shape), tuple(v.shape), R, K))
+        f = _SpectralForward()
+        f.R, f.K = R, K
+        f.w_sn = torch.empty(w.shape, dtype=torch.float32, device=w.device)
+        f.saved = torch.empty(R + K + 1, dtype=torch.float32, device=w.device)
+        table[i] = _lib.SpectralLayer(w.data_ptr(), u.data_ptr(), v.data_ptr(), f.w_sn.data_ptr(), f.saved.data_ptr(), R, K)
+        outs.append(f)
+    nbytes = int(lib.srk_spectral_norm_workspace(table, len(layers)))
+    if nbytes == 0:
+        raise RuntimeError("spectral_norm: %s" % lib.srk_last_error_string().decode())
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=layers[0][0].device)
+    check(lib.srk_spectral_norm_forward(table, len(layers), 1 if training else 0, SPECTRAL_EPS, ptr(ws), ws.numel(),
+                                        stream_ptr()), "srk_spectral_norm_forward")
+    return outs
+
+
+class _SpectralNormNode(torch.autograd.Function):
+    """The autograd node of ONE layer of a multi-layer spectral_norm call: forward hands out the w_sn the call computed,
+    backward turns G = dL/dw_sn into dW with the u, v, sigma of that forward (srk_spectral_norm_backward, two launches).
+    With a flat gradient buffer (optim.FlatParams) dW is accumulated into the parameter's slice, beta = 1."""
+
+    @staticmethod
+    def forward(ctx, weight_orig, fwd):
+        ctx.fwd, ctx.weight_ref = fwd, weight_orig
+        return fwd.w_sn
+
+    @staticmethod
+    def backward(ctx, G):
+        lib = _lib.load()
+        f, w = ctx.fwd, ctx.weight_ref
+        G = G.contiguous()
+        acc = getattr(w, "_srk_grad", None)
+        dW, beta = (acc, 1.0) if acc is not None else (torch.empty_like(f.w_sn), 0.0)
+        ws = torch.empty(max(int(lib.srk_spectral_norm_backward_workspace(f.R, f.K)), 8), dtype=torch.uint8, device=G.device)
+        check(lib.srk_spectral_norm_backward(ptr(G), ptr(f.w_sn), ptr(f.saved), f.R, f.K, ptr(dW), beta, ptr(ws), ws.numel(),
+                                             stream_ptr()), "srk_spectral_norm_backward")
+        return (None if acc is not None else dW), None
+
+
+def spectral_norm(layers, training=True):
+    """torch.nn.utils.spectral_norm(n_power_iterations=1, eps=1e-12, dim=0) for a list of layers [(weight_orig, u, v), ...]
+    in ONE call of three launches (two in eval mode): training mode runs one power iteration and writes u and v back in
+    place; then sigma = u . (W v) and w_sn = W / sigma.  Returns the list of w_sn, ordinary non-leaf tensors to hand to
+    ops.conv2d: each has its own backward node (u, v constants, as in torch), which keeps the u, v, sigma of this call.  A
+    weight_orig that does not require a gradient (a frozen discriminator) gets a plain tensor and no node.
+    include/srk.h: srk_spectral_norm_forward / _backward."""
+    outs = _spectral_forward_raw([(w.detach(), u, v) for w, u, v in layers], training)
+    res = []
+    for (w, _, _), f in zip(layers, outs):
+        if torch.is_grad_enabled() and w.requires_grad:
+            res.append(_SpectralNormNode.apply(w, f))
+        else:
+            res.append(f.w_sn)
+    return res
+
+
+class _UpsampleBilinear2x(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, add):
+        lib = _lib.load()
+        require_cuda(x, add)
+        if x.dim() != 4:
+            raise ValueError("upsample_bilinear2x: takes [N, C, H, W], got shape %s" % (tuple(x.shape),))
+        if add is not None and add.shape != x.shape:
+            raise ValueError("upsample_bilinear2x: add %s does not match x %s" % (tuple(add.shape), tuple(x.shape)))
+        x = to_nhwc(x)
+        add = to_nhwc(add) if add is not None else None
+        n, c, h, w = x.shape
+        y = _empty_cl(n, c, 2 * h, 2 * w, x)
+        check(lib.srk_upsample_bilinear2x_forward(ptr(x), ptr(add), ptr(y), n, h, w, c, stream_ptr()),
+              "srk_upsample_bilinear2x_forward")
+        ctx.has_add = add is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        dy = _dense(dy)
+        n, c, hr, wr = dy.shape
+        dx = _empty_cl(n, c, hr // 2, wr // 2, dy)
+        check(lib.srk_upsample_bilinear2x_backward(ptr(dy), ptr(dx), n, hr // 2, wr // 2, c, stream_ptr()),
+              "srk_upsample_bilinear2x_backward")
+        return (dx if ctx.needs_input_grad[0] else None), (dx if ctx.has_add and ctx.needs_input_grad[1] else None)
+
+
+def upsample_bilinear2x(x, add=None):
+    """F.interpolate(x + add, scale_factor=2, mode='bilinear', align_corners=False) in one launch; `add` (a U-Net skip) is
+    summed while x is read.  The backward is the adjoint in gather form, one launch; its result is the gradient of x and
+    of add alike (the same tensor).  include/srk.h: srk_upsample_bilinear2x_forward / _backward."""
+    return _UpsampleBilinear2x.apply(x, add)
+
+
+class _GanLogitLoss(torch.autograd.Function):
+    """srk_gan_logit_loss_forward_backward: the loss and its gradient from one pass and a finish, with _Loss's seed contract."""
+
+    @staticmethod
+    def forward(ctx, logits, target_is_real):
+        lib = _lib.load()
+        require_cuda(logits)
+        if logits.numel() < 1:
+            raise ValueError("gan_logit_loss: no logits (shape %s)" % (tuple(logits.shape),))
+        x = logits if (logits.is_contiguous() or (logits.dim() == 4 and _is_nhwc_dense(logits))) else logits.contiguous()
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None     # (preserve_format: the storage order of x)
+        ws = torch.empty(int(lib.srk_gan_logit_loss_workspace_bytes()), dtype=torch.uint8, device=x.device)
+        seed = _LOSS_SEED[0]
+        ctx.seed_ptr, ctx.seed_value = (seed[1].data_ptr(), seed[0]) if seed is not None else (0, 1.0)
+        ctx.seed_keep = seed[1] if seed is not None else None      # (see _Loss.forward)
+        check(lib.srk_gan_logit_loss_forward_backward(ptr(x), x.numel(), 1 if target_is_real else 0, ctx.seed_value, ptr(loss),
+                                                      ptr(dx), ptr(ws), stream_ptr()), "srk_gan_logit_loss_forward_backward")
+        ctx.dx = dx
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        dx = ctx.dx
+        if dx is None:
+            return None, None
+        gp = g.data_ptr()
+        if ctx.seed_ptr:
+            if gp == ctx.seed_ptr:
+                return dx, None
+            g = g / ctx.seed_value
+        elif gp == unit_seed(dx.device).data_ptr():
+            return dx, None
+        lib = _lib.load()
+        out = torch.empty_like(dx)
+        check(lib.srk_scale_dev(ptr(dx), ptr(g.contiguous()), ptr(out), dx.numel(), stream_ptr()), "srk_scale_dev")
+        return out, None
+
+
+def gan_logit_loss(logits, target_is_real):
+    """The vanilla GAN loss on discriminator LOGITS of any shape (a U-Net discriminator's [B, 1, H, W] map, or [B, 1]):
+    mean softplus(-x) for a real target, mean softplus(x) for a fake one (BCEWithLogits against ones / zeros).  A 0-dim
+    fp32 device tensor with the contract of the other losses (loss_seed, unit seed, weighted_term, loss_sum).
+    include/srk.h: srk_gan_logit_loss_forward_backward."""
+    return _GanLogitLoss.apply(logits, bool(target_is_real))
+
+
+# ------------------------------------------------------------------------------------------------
 # SwinIR's operators: shifted-window attention, LayerNorm, GELU (csrc/wattn.hip, csrc/swin_pointwise.hip, DESIGN.md 29)
 # ------------------------------------------------------------------------------------------------
 WATTN_MAX_HEAD_DIM = 32

@@ -97,6 +97,44 @@ def check_lpips_args(args, kind):
         raise ValueError("lpips_vgg: LPIPS reads RGB (main.py --num_channels 3)")
 
 
+DISCRIMINATORS = ("vgg", "unet")
+
+
+def check_discriminator_args(args, kind):
+    """--discriminator / --gan_type / --unet_feat of main.py belong to ESRGAN's adversarial phase; the relativistic loss
+    takes one logit a sample, so it does not go with the U-Net's logit map, whose three stride-2 stages need a crop size
+    that is a multiple of 8.  Raises ValueError naming the flag.  -> (discriminator, gan_type, unet_feat) for ESRGAN."""
+    disc, gan, feat = (getattr(args, n, None) for n in ("discriminator", "gan_type", "unet_feat"))
+    if kind != "esrgan":
+        for flag, v in (("discriminator", disc), ("gan_type", gan), ("unet_feat", feat)):
+            if v is not None:
+                raise ValueError("%s: only ESRGAN chooses its discriminator and GAN loss (main.py --model_name ESRGAN)" % flag)
+        return None
+    disc = disc or "vgg"
+    if disc not in DISCRIMINATORS:
+        raise ValueError("discriminator %r is not one of %s (main.py --discriminator)" % (disc, ", ".join(DISCRIMINATORS)))
+    gan = gan or ("vanilla" if disc == "unet" else "ragan")
+    if gan not in trainers.GAN_TYPES:
+        raise ValueError("gan_type %r is not one of %s (main.py --gan_type)" % (gan, ", ".join(trainers.GAN_TYPES)))
+    if disc == "unet" and gan == "ragan":
+        raise ValueError("gan_type 'ragan': the relativistic average loss takes one logit a sample, the U-Net discriminator "
+                         "gives one a pixel (main.py --gan_type vanilla with --discriminator unet)")
+    if feat is not None and disc != "unet":
+        raise ValueError("unet_feat: only the U-Net discriminator has a feature count to set (main.py --discriminator unet)")
+    if feat is not None and int(feat) < 1:
+        raise ValueError("unet_feat %r must be a whole number >= 1 (main.py --unet_feat)" % (feat,))
+    crop = getattr(args, "crop_size", None)
+    if disc == "unet" and crop is not None and int(crop) % 8:
+        raise ValueError("crop_size %d is not a multiple of 8, which the U-Net discriminator's three stride-2 stages need "
+                         "(main.py --crop_size)" % int(crop))
+    return disc, gan, 64 if feat is None else int(feat)
+
+
+def discriminator_kind(state_dict):
+    """'unet' or 'vgg' from the keys of a discriminator's state_dict."""
+    return "unet" if any(k.endswith("weight_orig") for k in state_dict) else "vgg"
+
+
 # -- the training-state file (<save_dir>/model/<model_name>_train_state.pkl) ---------------------------------------------
 # Everything a run needs to continue at an epoch boundary as if it had not stopped; plain containers, numbers, strings
 # and CPU tensors only, so it loads with torch.load(weights_only=True).  The weights-only checkpoint files beside it are
@@ -141,6 +179,7 @@ class _Trainer(object):
             raise ValueError("fft_weight: %s has no frequency-domain term (main.py --fft_weight)" % self.model_name)
         check_perceptual_args(args, self.kind)
         check_lpips_args(args, self.kind)
+        self.disc_args = check_discriminator_args(args, self.kind)
         for flag in ("degrade", "degrade_test", "jpeg_quality", "jpeg_test"):
             if getattr(args, flag, None) and getattr(args, "synthetic", False):
                 raise ValueError("%s: synthetic patches are not degraded, train and test on image folders (main.py "
@@ -962,11 +1001,26 @@ class ESRGAN(SRGAN):
         self.gan_weight, self.pixel_weight = w("gan_weight", 5e-3), w("pixel_weight", 1e-2)
         self.vgg_weight = w("vgg_loss_weight", 1.0)
         self.net_interp = None if interp is None else float(interp)
+        self.discriminator, self.gan_type, self.unet_feat = self.disc_args
+
+    def build_discriminator(self):
+        """--discriminator vgg (default): SRGAN's body ending in a logit; unet: Real-ESRGAN's UNetDiscriminatorSN."""
+        if self.discriminator == "unet":
+            return models.UNetDiscriminatorSN(self.num_channels, self.unet_feat)
+        return models.ESRGANDiscriminator(self.num_channels, 64, self.crop_size)
 
     def build_model(self):
         self.G = models.RRDBNet(self.num_channels, 64, self.blocks, self.growth, self.scale_factor)
-        self.D = models.ESRGANDiscriminator(self.num_channels, 64, self.crop_size)
+        self.D = self.build_discriminator()
         return self.G
+
+    def load_training_state(self, state, loader=None):
+        stored = discriminator_kind(state["modules"]["D"])
+        mine = discriminator_kind(self.D.state_dict())
+        if stored != mine:
+            raise ValueError("discriminator: the training state holds a %r discriminator, this run builds a %r one "
+                             "(main.py --discriminator %s)" % (stored, mine, stored))
+        return super(ESRGAN, self).load_training_state(state, loader)
 
     def _normalise(self, t):
         return t
@@ -976,7 +1030,8 @@ class ESRGAN(SRGAN):
 
     def _adversarial_step(self, g_opt, d_opt, g_dp, d_dp):
         fe = models.FeatureExtractor(feature_layer=34).load_vgg19(self.args.vgg_weights).to(self.device)
-        return trainers.esrgan_step(self.G, self.D, g_opt, d_opt, fe, self.pixel_weight, self.vgg_weight, self.gan_weight)
+        return trainers.esrgan_step(self.G, self.D, g_opt, d_opt, fe, self.pixel_weight, self.vgg_weight, self.gan_weight,
+                                    self.gan_type)
 
     def train(self, loader=None, pretrain_epochs=None, log_every=0):
         if not getattr(self.args, "vgg_weights", None):

@@ -326,12 +326,18 @@ def srgan_segments(G, D, g_opt, d_opt, g_dp=None, d_dp=None, lazy_pack=False, fe
     return [(seg_d, d_dp), (seg_g, g_dp), (seg_u, None)]
 
 
-def esrgan_step(G, D, g_opt, d_opt, feature_extractor, pixel_weight=1e-2, vgg_weight=1.0, gan_weight=5e-3):
+def esrgan_step(G, D, g_opt, d_opt, feature_extractor, pixel_weight=1e-2, vgg_weight=1.0, gan_weight=5e-3,
+                gan_type='ragan'):
     """The adversarial step of ESRGAN as the eager closure of `esrgan_segments` (see there)."""
-    return eager_step(esrgan_segments(G, D, g_opt, d_opt, feature_extractor, pixel_weight, vgg_weight, gan_weight))
+    return eager_step(esrgan_segments(G, D, g_opt, d_opt, feature_extractor, pixel_weight, vgg_weight, gan_weight,
+                                      gan_type))
 
 
-def esrgan_segments(G, D, g_opt, d_opt, feature_extractor, pixel_weight=1e-2, vgg_weight=1.0, gan_weight=5e-3):
+GAN_TYPES = ("ragan", "vanilla")
+
+
+def esrgan_segments(G, D, g_opt, d_opt, feature_extractor, pixel_weight=1e-2, vgg_weight=1.0, gan_weight=5e-3,
+                    gan_type='ragan'):
     """ESRGAN's adversarial step (Wang et al., ECCV-W 2018) in the order BasicSR's model runs it, for batches in [0, 1]:
       G step, D's parameters frozen:   fake = G(lr)
           g_loss = pixel_weight * L1(fake, hr) + vgg_weight * L1(vgg(norm(fake)), vgg(norm(hr)))
@@ -343,7 +349,19 @@ def esrgan_segments(G, D, g_opt, d_opt, feature_extractor, pixel_weight=1e-2, vg
     before its ReLU; its term is ops.perceptual_loss(criterion='l1') and normalises the batch once.  D runs in training
     mode throughout (its BatchNorm statistics move in both steps, as there).  The three gradients of `fake` are added by
     srk_axpby (ops.fork) and the loss terms by ops.loss_sum with each weight folded into its loss kernel
-    (ops.weighted_term): no ATen arithmetic node in a captured step.  One GPU: two segments without an exchange."""
+    (ops.weighted_term): no ATen arithmetic node in a captured step.  One GPU: two segments without an exchange.
+    gan_type 'vanilla' (BasicSR's SRGAN order, what Real-ESRGAN trains models.UNetDiscriminatorSN with): the term is
+    ops.gan_logit_loss on D's logits of any shape,
+      G step, D frozen:   gan_weight * gan(D(fake), real)            (D(hr) is not evaluated)
+      D step:             d_loss = gan(D(hr), real) + gan(D(fake.detach()), fake), the sum and not the half.
+    A U-Net discriminator's logit map is refused with 'ragan' (gan_type: the relativistic loss takes one logit a sample)."""
+    from . import models
+    if gan_type not in GAN_TYPES:
+        raise ValueError("esrgan step: gan_type %r is not one of %s" % (gan_type, ", ".join(GAN_TYPES)))
+    if gan_type == "ragan" and isinstance(D, models.UNetDiscriminatorSN):
+        raise ValueError("esrgan step: gan_type 'ragan' with a U-Net discriminator: the relativistic average loss takes one "
+                         "logit a sample, not a logit map (use gan_type='vanilla', main.py --gan_type vanilla)")
+    vanilla = gan_type == "vanilla"
     pixel_weight, vgg_weight, gan_weight = float(pixel_weight), float(vgg_weight), float(gan_weight)
     if feature_extractor is None:
         raise ValueError("esrgan step: needs a feature_extractor (models.FeatureExtractor(feature_layer=34) with its weights)")
@@ -371,8 +389,11 @@ def esrgan_segments(G, D, g_opt, d_opt, feature_extractor, pixel_weight=1e-2, vg
         out["fake"] = fake.detach()
         freeze_d(True)
         try:
-            real_logits = D(hr_img).detach()
-            l_gan = ops.weighted_term(gan_g, gan_weight, D(f_gan), real_logits)
+            if vanilla:
+                l_gan = ops.weighted_term(lambda p, t: ops.gan_logit_loss(p, True), gan_weight, D(f_gan), None)
+            else:
+                real_logits = D(hr_img).detach()
+                l_gan = ops.weighted_term(gan_g, gan_weight, D(f_gan), real_logits)
         finally:
             freeze_d(False)
         l_pix = ops.weighted_term(ops.l1_loss, pixel_weight, f_pix, hr_img)
@@ -385,7 +406,10 @@ def esrgan_segments(G, D, g_opt, d_opt, feature_extractor, pixel_weight=1e-2, vg
 
     def seg_d(lr_img, hr_img):
         d_opt.zero_grad()
-        d_loss = ops.ragan_loss(D(hr_img), D(out.pop("fake")), False)
+        if vanilla:
+            d_loss = ops.loss_sum(ops.gan_logit_loss(D(hr_img), True), ops.gan_logit_loss(D(out.pop("fake")), False))
+        else:
+            d_loss = ops.ragan_loss(D(hr_img), D(out.pop("fake")), False)
         _backward(d_loss, None)
         d_opt.step()
         return d_loss, out.pop("g")
