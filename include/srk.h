@@ -558,13 +558,18 @@ int srk_linear_backward(const float* x, const float* w, const float* dy, float* 
  * x, y: dense NCHW fp32 (the reference's FloatTensor layout); values are quantised to uint8 by truncation of x*255
  * (saturating outside [0,1]), resampled with Pillow's 8-bit two-pass algorithm and returned as uint8/255.
  * SRCNN / VDSR / LapSRN call it every iteration (srcnn.py:119, vdsr.py:137, lapsrn.py:183). */
-typedef enum srk_interp { SRK_INTERP_NEAREST = 0, SRK_INTERP_BILINEAR = 2, SRK_INTERP_BICUBIC = 3 } srk_interp; /* PIL codes */
+typedef enum srk_interp {
+  SRK_INTERP_NEAREST = 0,
+  SRK_INTERP_BILINEAR = 2,
+  SRK_INTERP_BICUBIC = 3,
+  SRK_INTERP_BOX = 4 /* Image.BOX: support 0.5, weight 1 on (-0.5, 0.5]; srk_img_resize_u8 only */
+} srk_interp; /* PIL codes */
 size_t srk_img_interp_workspace_bytes(int N, int C, int H, int W, int OH, int OW, int filter);
 int srk_img_interp(const float* x_nchw, float* y_nchw, int N, int C, int H, int W, int OH, int OW, int filter,
                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- training-set pipeline on 8-bit images (dataset.py:51-99; torchvision's Scale / RandomCrop / flips around Pillow) ----
- * Image.resize((OW, OH), BICUBIC | BILINEAR) on 8-bit planes, bit-exact with Pillow (same two-pass resampler as
+ * Image.resize((OW, OH), BICUBIC | BILINEAR | BOX) on 8-bit planes, bit-exact with Pillow (same two-pass resampler as
  * srk_img_interp; a pass is skipped when that axis keeps its size, as Pillow does).  x is addressed through element
  * strides (plane, row, pixel): an interleaved HWC decode buffer is read in place with (1, W*C, C).  y: planar
  * [planes][OH][OW], uint8 (out_float = 0) or float = value / 255 (out_float = 1: ToTensor). */
@@ -830,6 +835,59 @@ int srk_noise_u8_bytes(const uint8_t* x, uint8_t* y, const double* sigma, uint64
 int srk_jpeg_quant_table_host(int quality, int chroma, int* out);
 int srk_jpeg_u8_host(const uint8_t* x, uint8_t* y, const int* quality, int C, int B, int H, int W, int subsampling,
                      int color);
+
+/* ---- Real-ESRGAN's second-order degradation and USM targets (data.Degradation2) ----------------------
+ * (Additive: new entry points and SRK_INTERP_BOX only, srk_version() and everything existing unchanged.)
+ * Every stage is 8 bits in, 8 bits out and defined to the byte; tests/degrade2_ref.py restates each in numpy.
+ *
+ * srk_blur_table_host: the normalised K x K fp64 table (row-major (i, j), x = j - K / 2, y = i - K / 2) of one kind, K odd
+ *   in [7, 21], for srk_blur_u8 to take unchanged.  With u = cos(theta) x + sin(theta) y, v = -sin(theta) x + cos(theta) y
+ *   and q = u^2 / s1^2 + v^2 / s2^2:  GAUSS exp(-0.5 q);  GGAUSS exp(-0.5 q^beta);  PLATEAU 1 / (1 + q^beta);  SINC the
+ *   circular low-pass cutoff * J1(cutoff r) / (2 pi r), r = sqrt(x^2 + y^2), cutoff^2 / (4 pi) at r = 0 (J1 is libm's j1;
+ *   the table has negative entries, which srk_blur_u8's clamp covers).  Each table is divided by its compensated sum;
+ *   the centre tap then takes up what the rounded entries' sum still lacks from 1, so a table sums to 1 within an ulp.
+ *   Arguments a kind does not use are ignored.  SRK_ERR_INVALID: null pointer, K even or outside [7, 21], a sigma, beta or
+ *   cutoff that its kind needs and that is not positive.
+ * srk_poisson_cdf_host: cdf[256][KT] fp64, cdf[L][k] = P(Pois(L * peak / 255) <= k) from the running product
+ *   pmf(k) = pmf(k - 1) * lambda / k (pmf(0) = exp(-lambda)) under a compensated sum, clamped to 1, made non-decreasing,
+ *   the last column forced to 1.0.  The chain uses peak 256, KT = SRK_POISSON_KT = 448.
+ * srk_noise2_u8: x, y dense 8-bit [B][C][H][W], C 1 or 3; mode, gray, amount fp64 [B] and cdf fp64 [256][448] on the
+ *   device.  Words and normals are srk_noise_u8's (Philox4x32-10, Box-Muller in fp64) with `stage` (0, 1 or 2) in counter
+ *   word 2; stage 0 is srk_noise_u8's own stream.  An element's generator index is its linear index e over the call
+ *   (colour noise) or its pixel's index b * H * W + y * W + x (gray[b] != 0: one draw per pixel, shared by the planes); it
+ *   takes lane (index & 3) of group (index >> 2).  Per patch:
+ *     mode 0 (SRK_NOISE2_OFF)      y = x;
+ *     mode 1 (SRK_NOISE2_GAUSS)    y = clamp(floor(x + amount * z + 0.5), 0, 255), z the index's normal;
+ *     mode 2 (SRK_NOISE2_POISSON)  k = the smallest column with u(word) <= cdf[L][k] (binary search), L the byte itself,
+ *                                  or with gray noise the pixel's gray level: floor((R + G + B) / 3 + 0.5) with
+ *                                  color != 0, plane 0 (the Y of Y, Cb, Cr planes) with color = 0, the byte with C = 1; y = clamp(floor(x + amount * (k * 255 / 256 - L) + 0.5), 0, 255).
+ *   All arithmetic is fp64, products and sums uncontracted; the device evaluates no transcendental for Poisson.
+ *   SRK_ERR_INVALID before anything is launched: null pointer, C not 1 or 3, a size <= 0, stage outside 0..2.
+ * srk_noise2_u8_host: the same body (csrc/degrade_common.h) looped on the host, all pointers host memory.
+ * srk_usm_table_host: g[i] = exp(-(i - K / 2)^2 / (2 sigma^2)) normalised as srk_blur_table_host's, K odd in [1, 51];
+ *   sigma <= 0 means cv2's 0.3 * ((K - 1) * 0.5 - 1) + 0.8 (8.0 at K = 51).
+ * srk_usm_u8: Real-ESRGAN's USMSharp on dense 8-bit planes x [B][C][H][W] -> y; g fp64 [K] on the device.  With blur(A)
+ *   the separable pass of g over rows then columns (fp64 intermediate unrounded, taps added in index order from 0, borders
+ *   reflect-101):  Bl = blur(x);  R = x - Bl;  M = |R| > threshold;  S = blur(M);  sharp = clamp(x + weight * R, 0, 255);
+ *   y = floor(clamp(S * sharp + (1 - S) * x, 0, 255) + 0.5).  fp64 throughout, uncontracted; no atomics; the workspace
+ *   (srk_usm_u8_workspace_bytes) holds R and M between the two launches.  SRK_ERR_INVALID before anything is launched:
+ *   null pointer, K even or outside [1, 51], C not 1 or 3, H or W <= K / 2; SRK_ERR_WORKSPACE: workspace too small.
+ * srk_usm_u8_host: the same bodies (csrc/usm_common.h) looped on the host. */
+enum { SRK_BLUR_GAUSS = 0, SRK_BLUR_GGAUSS = 1, SRK_BLUR_PLATEAU = 2, SRK_BLUR_SINC = 3 };
+enum { SRK_NOISE2_OFF = 0, SRK_NOISE2_GAUSS = 1, SRK_NOISE2_POISSON = 2 };
+enum { SRK_POISSON_KT = 448, SRK_USM_MAX_K = 51 };
+int srk_blur_table_host(int kind, int K, double s1, double s2, double theta, double beta, double cutoff, double* w);
+int srk_poisson_cdf_host(double peak, int KT, double* cdf);
+int srk_noise2_u8(const uint8_t* x, uint8_t* y, const double* mode, const double* gray, const double* amount,
+                  const double* cdf, uint64_t seed, int stage, int B, int C, int H, int W, int color, void* stream);
+int srk_noise2_u8_host(const uint8_t* x, uint8_t* y, const double* mode, const double* gray, const double* amount,
+                       const double* cdf, uint64_t seed, int stage, int B, int C, int H, int W, int color);
+int srk_usm_table_host(int K, double sigma, double* g);
+size_t srk_usm_u8_workspace_bytes(int B, int C, int H, int W);
+int srk_usm_u8(const uint8_t* x, uint8_t* y, const double* g, int K, double weight, double threshold, int B, int C, int H,
+               int W, void* workspace, size_t workspace_bytes, void* stream);
+int srk_usm_u8_host(const uint8_t* x, uint8_t* y, const double* g, int K, double weight, double threshold, int B, int C,
+                    int H, int W);
 
 /* ---- Channel attention: the gate of RCAN's residual channel attention block (csrc/ca.hip, csrc/ca_common.h) ---------
  * (Additive again: new entry points only, srk_version() and everything existing unchanged.)

@@ -43,10 +43,22 @@ GAN loss, which needs --vgg_weights PATH (conv5_4 features before the ReLU).  x4
 --discriminator {vgg,unet} (ESRGAN; default vgg): unet trains against Real-ESRGAN's U-Net discriminator with spectral
 normalisation (models.UNetDiscriminatorSN, --unet_feat F channels, default 64; one logit a pixel, so any --crop_size that is
 a multiple of 8) on --gan_type vanilla (ops.gan_logit_loss; the default with unet, where ragan is refused; ragan stays the
-default with vgg).  Real-ESRGAN's degradation model, its multi-layer VGG term and data parallelism are not part of it.
+default with vgg).  Real-ESRGAN's multi-layer VGG term and data parallelism are not part of it.
+--degrade2 [SETTINGS.json] (train on Real-ESRGAN's second-order degradation, data.Degradation2: blur, resize, Gaussian or
+Poisson noise and JPEG, twice, then a sinc filter, every stage a kernel on 8-bit patches; the file holds only overrides of
+Degradation2's keywords), --usm (the training target and the degradation's input are the patches sharpened by
+Real-ESRGAN's USMSharp; also with --degrade or alone) and --degrade2_test SEED (every test image under its own seeded chain);
+image folders only; not with --degrade or --jpeg_quality.
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N main.py ..."""
 import argparse
 import os
+
+# data.Degradation2's keywords (tests hold the two lists together): what --degrade2's SETTINGS.json may override
+DEGRADE2_KEYS = ('kernel_sizes', 'kernel_sizes2', 'kernel_prob', 'kernel_prob2', 'sinc_prob', 'sinc_prob2', 'blur_sigma',
+                 'blur_sigma2', 'betag_range', 'betag_range2', 'betap_range', 'betap_range2', 'second_blur_prob',
+                 'resize_prob', 'resize_prob2', 'resize_range', 'resize_range2', 'gaussian_noise_prob',
+                 'gaussian_noise_prob2', 'noise_range', 'noise_range2', 'poisson_scale_range', 'poisson_scale_range2',
+                 'gray_noise_prob', 'gray_noise_prob2', 'jpeg_range', 'jpeg_range2', 'final_sinc_prob', 'jpeg_subsampling')
 
 
 def _names(text):
@@ -222,6 +234,23 @@ def _degrade_test(text):
     return s1, s2, th, ns
 
 
+def _degrade2_settings(path):
+    """--degrade2 SETTINGS.json: a JSON object of data.Degradation2 keyword overrides; unknown keys are named."""
+    import json
+    try:
+        with open(path) as f:
+            settings = json.load(f)
+    except (OSError, ValueError) as e:
+        raise argparse.ArgumentTypeError("--degrade2: cannot read %r (%s)" % (path, e))
+    if not isinstance(settings, dict):
+        raise argparse.ArgumentTypeError("--degrade2: %r must hold a JSON object of Degradation2 settings" % (path,))
+    unknown = sorted(set(settings) - set(DEGRADE2_KEYS))
+    if unknown:
+        raise argparse.ArgumentTypeError("--degrade2: %r holds unknown key%s %s (known: %s)"
+                                         % (path, "s" if len(unknown) > 1 else "", ", ".join(unknown), ", ".join(DEGRADE2_KEYS)))
+    return settings
+
+
 def _jpeg_int(text, flag):
     try:
         v = int(str(text).strip())
@@ -354,6 +383,16 @@ def parse_args(argv=None):
     p.add_argument('--degrade_test', type=_degrade_test, default=None, metavar='S1,S2,THETA_DEG,NOISE',
                    help='test(): every test image under this one degradation (blur standard deviations, angle in degrees, '
                         'noise standard deviation; the noise seeded by the image\'s index).  Image folders only')
+    p.add_argument('--degrade2', type=_degrade2_settings, nargs='?', const={}, default=None, metavar='SETTINGS.json',
+                   help='train on Real-ESRGAN\'s second-order degradation (blur, resize, noise, JPEG, twice, then a sinc '
+                        'filter), on the device; SETTINGS.json holds only overrides of data.Degradation2\'s keywords.  Image '
+                        'folders only')
+    p.add_argument('--usm', action='store_true',
+                   help='sharpen the 8-bit training patches with Real-ESRGAN\'s USMSharp first: the target and the input of '
+                        'the shrink or the degradation are the sharpened patches.  Image folders only')
+    p.add_argument('--degrade2_test', type=int, default=None, metavar='SEED',
+                   help='degrade every test image by its own chain of --degrade2\'s settings, drawn from a private generator '
+                        'seeded by (SEED, index): an item is the same on every read.  Image folders only')
     p.add_argument('--jpeg_quality', type=_jpeg_quality, default=None, metavar='LO,HI',
                    help='--degrade: also JPEG-compress the degraded LR patch at a quality drawn from LO..HI (whole numbers '
                         'in 1..100) and decode it again, on the device (default: no JPEG stage)')
@@ -499,6 +538,16 @@ def parse_args(argv=None):
     for flag in ('degrade', 'degrade_test', 'jpeg_quality', 'jpeg_test'):
         if getattr(args, flag) and args.synthetic:
             p.error('--%s: synthetic patches are not degraded; train and test on image folders (drop --synthetic)' % flag)
+    for flag, on in (('degrade2', args.degrade2 is not None), ('usm', args.usm), ('degrade2_test', args.degrade2_test is not None)):
+        if on and args.synthetic:
+            p.error('--%s: synthetic patches are not degraded; train and test on image folders (drop --synthetic)' % flag)
+    if args.degrade2 is not None and args.degrade:
+        p.error('--degrade2 and --degrade are two degradation models: give one')
+    if args.degrade2 is not None and args.jpeg_quality:
+        p.error('--jpeg_quality belongs to --degrade; --degrade2\'s chain has JPEG stages of its own (jpeg_range, jpeg_range2 '
+                'in its settings file)')
+    if args.degrade2_test is not None and (args.degrade_test or args.jpeg_test):
+        p.error('--degrade2_test brings its own blur, noise and JPEG: give neither --degrade_test nor --jpeg_test with it')
     if args.jpeg_quality and not args.degrade:
         p.error('--jpeg_quality is a stage of the training degradation: pass --degrade too (--blur_prob 0 --noise_sigma 0,0 '
                 'leaves JPEG alone)')

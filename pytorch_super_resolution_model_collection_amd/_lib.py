@@ -330,6 +330,14 @@ _PROTOTYPES = {
     "srk_gan_logit_loss_workspace_bytes": (c_size, []),
     "srk_gan_logit_loss_forward_backward": (c_int, [c_f, c_size, c_int, c_float, c_f, c_f, c_vp, c_vp]),
     "srk_gan_logit_loss_host": (c_int, [c_vp, c_size, c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_double), c_vp]),
+    "srk_blur_table_host": (c_int, [c_int, c_int] + [ctypes.c_double] * 5 + [ctypes.POINTER(ctypes.c_double)]),
+    "srk_poisson_cdf_host": (c_int, [ctypes.c_double, c_int, c_vp]),
+    "srk_noise2_u8": (c_int, [c_vp] * 6 + [ctypes.c_uint64] + [c_int] * 6 + [c_vp]),
+    "srk_noise2_u8_host": (c_int, [c_vp] * 6 + [ctypes.c_uint64] + [c_int] * 6),
+    "srk_usm_table_host": (c_int, [c_int, ctypes.c_double, ctypes.POINTER(ctypes.c_double)]),
+    "srk_usm_u8_workspace_bytes": (c_size, [c_int] * 4),
+    "srk_usm_u8": (c_int, [c_vp] * 3 + [c_int, ctypes.c_double, ctypes.c_double] + [c_int] * 4 + [c_vp, c_size, c_vp]),
+    "srk_usm_u8_host": (c_int, [c_vp] * 3 + [c_int, ctypes.c_double, ctypes.c_double] + [c_int] * 4),
 }
 
 _lib = None

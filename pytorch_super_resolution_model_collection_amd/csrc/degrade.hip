@@ -139,6 +139,19 @@ __global__ __launch_bounds__(256) void k_noise_u8(const uint8_t* __restrict__ x,
   }
 }
 
+// srk_noise2_u8: a thread makes up to four consecutive elements through noise2_group (degrade_common.h), the body the host
+// twin loops over.  Bytes are read and written one by one: the per-patch mode decides what an element needs.
+__global__ __launch_bounds__(256) void k_noise2_u8(const uint8_t* __restrict__ x, uint8_t* __restrict__ y,
+                                                   const double* __restrict__ mode, const double* __restrict__ gray,
+                                                   const double* __restrict__ amount, const double* __restrict__ cdf,
+                                                   uint64_t seed, uint32_t stage, int C, int64_t HW, int color, int64_t total) {
+  const int64_t groups = (total + 3) >> 2;
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < groups; q += (int64_t)gridDim.x * 256) {
+    const int64_t e0 = q << 2;
+    noise2_group(x, y, mode, gray, amount, cdf, seed, stage, C, HW, color, e0, total - e0 < 4 ? (int)(total - e0) : 4);
+  }
+}
+
 }  // namespace srk
 
 using namespace srk;
@@ -238,5 +251,110 @@ extern "C" int srk_noise_normals_host(uint64_t seed, int64_t first_elem, int64_t
     }
     z[k] = g[e & 3];
   }
+  return SRK_OK;
+}
+
+// ---- the second-order chain (data.Degradation2) ----------------------------------------------------------
+static int noise2_check(const char* what, const void* x, const void* y, const double* mode, const double* gray,
+                        const double* amount, const double* cdf, int stage, int B, int C, int H, int W) {
+  SRK_REQUIRE(x && y && mode && gray && amount && cdf, "%s: null pointer", what);
+  SRK_REQUIRE(B > 0 && H > 0 && W > 0, "%s: bad dims (B %d, %d x %d)", what, B, H, W);
+  SRK_REQUIRE(C == 1 || C == 3, "%s: C must be 1 or 3 (got %d)", what, C);
+  SRK_REQUIRE(stage >= 0 && stage <= 2, "%s: stage must be 0, 1 or 2 (got %d)", what, stage);
+  return SRK_OK;
+}
+
+extern "C" int srk_noise2_u8(const uint8_t* x, uint8_t* y, const double* mode, const double* gray, const double* amount,
+                             const double* cdf, uint64_t seed, int stage, int B, int C, int H, int W, int color,
+                             void* stream) {
+  if (int rc = noise2_check("noise2_u8", x, y, mode, gray, amount, cdf, stage, B, C, H, W)) return rc;
+  const int64_t HW = (int64_t)H * W, total = HW * C * B;
+  hipLaunchKernelGGL(k_noise2_u8, dim3(grid_for((size_t)((total + 3) >> 2), 256, (size_t)kNumCU * 8)), dim3(256), 0,
+                     (hipStream_t)stream, x, y, mode, gray, amount, cdf, seed, (uint32_t)stage, C, HW, color ? 1 : 0, total);
+  return check_launch("noise2_u8");
+}
+
+extern "C" int srk_noise2_u8_host(const uint8_t* x, uint8_t* y, const double* mode, const double* gray,
+                                  const double* amount, const double* cdf, uint64_t seed, int stage, int B, int C, int H,
+                                  int W, int color) {
+  if (int rc = noise2_check("noise2_u8_host", x, y, mode, gray, amount, cdf, stage, B, C, H, W)) return rc;
+  const int64_t HW = (int64_t)H * W, total = HW * C * B;
+  for (int64_t e0 = 0; e0 < total; e0 += 4)
+    noise2_group(x, y, mode, gray, amount, cdf, seed, (uint32_t)stage, C, HW, color ? 1 : 0, e0,
+                 total - e0 < 4 ? (int)(total - e0) : 4);
+  return SRK_OK;
+}
+
+// Neumaier's compensated sum, one term at a time (srk_blur_weights_host's, as a value that can be read after every term).
+namespace {
+struct CompSum {
+  double sum = 0.0, comp = 0.0;
+  void add(double e) {
+    const double t = sum + e;
+    comp += fabs(sum) >= fabs(e) ? (sum - t) + e : (e - t) + sum;
+    sum = t;
+  }
+  double value() const { return sum + comp; }
+};
+}  // namespace
+
+extern "C" int srk_poisson_cdf_host(double peak, int KT, double* cdf) {
+#pragma clang fp contract(off)
+  SRK_REQUIRE(cdf, "poisson_cdf_host: null pointer");
+  SRK_REQUIRE(KT >= 2, "poisson_cdf_host: KT must be at least 2 (got %d)", KT);
+  SRK_REQUIRE(peak > 0.0 && peak <= 700.0, "poisson_cdf_host: peak must lie in (0, 700] (got %g)", peak);
+  for (int L = 0; L < 256; ++L) {
+    const double lambda = (double)L * peak / 255.0;
+    double* row = cdf + (size_t)L * KT;
+    double pmf = exp(-lambda), prev = 0.0;   // the running product pmf(k) = pmf(k - 1) * lambda / k
+    CompSum s;
+    for (int k = 0; k < KT; ++k) {
+      if (k > 0) pmf = pmf * lambda / (double)k;
+      s.add(pmf);
+      double v = s.value();
+      v = v > 1.0 ? 1.0 : v;
+      v = v < prev ? prev : v;               // (a compensated sum of non-negative terms may still step back an ulp)
+      row[k] = prev = v;
+    }
+    row[KT - 1] = 1.0;
+  }
+  return SRK_OK;
+}
+
+extern "C" int srk_blur_table_host(int kind, int K, double s1, double s2, double theta, double beta, double cutoff,
+                                   double* w) {
+#pragma clang fp contract(off)
+  SRK_REQUIRE(w, "blur_table_host: null pointer");
+  SRK_REQUIRE(kind >= SRK_BLUR_GAUSS && kind <= SRK_BLUR_SINC, "blur_table_host: unknown kind %d", kind);
+  SRK_REQUIRE(K >= 7 && K <= kBlurMaxK && (K & 1), "blur_table_host: K must be odd and in [7, %d] (got %d)", kBlurMaxK, K);
+  if (kind == SRK_BLUR_SINC) {
+    SRK_REQUIRE(cutoff > 0.0, "blur_table_host: the sinc cutoff must be positive (got %g)", cutoff);
+  } else {
+    SRK_REQUIRE(s1 > 0.0 && s2 > 0.0, "blur_table_host: sigmas must be positive (got %g, %g)", s1, s2);
+    SRK_REQUIRE(kind == SRK_BLUR_GAUSS || beta > 0.0, "blur_table_host: beta must be positive (got %g)", beta);
+  }
+  const int r = K / 2, n = K * K;
+  const double c = cos(theta), s = sin(theta);
+  for (int idx = 0; idx < n; ++idx) {
+    const double xx = (double)(idx % K - r), yy = (double)(idx / K - r);
+    if (kind == SRK_BLUR_SINC) {
+      const double rr = sqrt(xx * xx + yy * yy);
+      w[idx] = rr == 0.0 ? cutoff * cutoff / (4.0 * 3.141592653589793)
+                         : cutoff * j1(cutoff * rr) / (2.0 * 3.141592653589793 * rr);
+      continue;
+    }
+    const double u = c * xx + s * yy, v = -s * xx + c * yy;
+    const double q = u * u / (s1 * s1) + v * v / (s2 * s2);
+    w[idx] = kind == SRK_BLUR_GAUSS ? exp(-0.5 * q) : kind == SRK_BLUR_GGAUSS ? exp(-0.5 * pow(q, beta)) : 1.0 / (1.0 + pow(q, beta));
+  }
+  CompSum sum;
+  for (int idx = 0; idx < n; ++idx) sum.add(w[idx]);
+  const double total = sum.value();
+  for (int idx = 0; idx < n; ++idx) w[idx] /= total;
+  // `total` is itself rounded, so the divided table's sum can miss 1 by an ulp.  The centre tap (the largest of every
+  // kind) takes up what is missing: (sum - 1) is exact so close to 1, the compensation carries the rest.
+  CompSum again;
+  for (int idx = 0; idx < n; ++idx) again.add(w[idx]);
+  w[n / 2] -= (again.sum - 1.0) + again.comp;
   return SRK_OK;
 }

@@ -16,7 +16,8 @@
 // The coefficient tables are produced on the device by k_resize_tables in IEEE double with
 // contraction off — the same operations in the same order as the C source — so they are identical
 // to Pillow's; everything after that is integer.  Result: bit-equal to the reference (tested against
-// Pillow itself).  Filters: bicubic (a = -0.5), bilinear; nearest uses Pillow's affine/nearest rule.
+// Pillow itself).  Filters: bicubic (a = -0.5), bilinear, box (srk_img_resize_u8 only: the second-order degradation's
+// "area"); nearest uses Pillow's affine/nearest rule.
 #include "srk_common.h"
 #include <math.h>
 
@@ -26,6 +27,7 @@ constexpr int kPrecisionBits = 32 - 8 - 2;
 
 __device__ __forceinline__ double pil_filter(int filter, double x) {
 #pragma clang fp contract(off)
+  if (filter == SRK_INTERP_BOX) return x > -0.5 && x <= 0.5 ? 1.0 : 0.0;   // Resample.c box_filter: the half-open cell
   if (x < 0.0) x = -x;
   if (filter == SRK_INTERP_BILINEAR) return x < 1.0 ? 1.0 - x : 0.0;
   const double a = -0.5;
@@ -40,7 +42,7 @@ __global__ void k_resize_tables(int inSize, int outSize, int filter, int ksize, 
 #pragma clang fp contract(off)
   const int xx = blockIdx.x * blockDim.x + threadIdx.x;
   if (xx >= outSize) return;
-  const double fsupport = filter == SRK_INTERP_BILINEAR ? 1.0 : 2.0;
+  const double fsupport = filter == SRK_INTERP_BILINEAR ? 1.0 : (filter == SRK_INTERP_BOX ? 0.5 : 2.0);
   const double scale = (double)((float)inSize - 0.0f) / outSize;
   double filterscale = scale;
   if (filterscale < 1.0) filterscale = 1.0;
@@ -231,7 +233,7 @@ __global__ __launch_bounds__(256) void k_resize_nearest(const float* __restrict_
 }
 
 static int resize_ksize(int inSize, int outSize, int filter) {
-  const double fsupport = filter == SRK_INTERP_BILINEAR ? 1.0 : 2.0;
+  const double fsupport = filter == SRK_INTERP_BILINEAR ? 1.0 : (filter == SRK_INTERP_BOX ? 0.5 : 2.0);
   double filterscale = (double)((float)inSize) / outSize;
   if (filterscale < 1.0) filterscale = 1.0;
   return (int)ceil(fsupport * filterscale) * 2 + 1;
@@ -306,7 +308,8 @@ extern "C" int srk_img_resize_u8(const uint8_t* x, int64_t plane_stride, int64_t
                                  size_t workspace_bytes, void* stream) {
   SRK_REQUIRE(x && y, "img_resize_u8: null pointer");
   SRK_REQUIRE(planes > 0 && H > 0 && W > 0 && OH > 0 && OW > 0, "img_resize_u8: non-positive dims");
-  SRK_REQUIRE(filter == SRK_INTERP_BILINEAR || filter == SRK_INTERP_BICUBIC, "img_resize_u8: filter must be bilinear or bicubic");
+  SRK_REQUIRE(filter == SRK_INTERP_BILINEAR || filter == SRK_INTERP_BICUBIC || filter == SRK_INTERP_BOX,
+              "img_resize_u8: filter must be bilinear, bicubic or box");
   const size_t need = srk_img_resize_u8_workspace_bytes(planes, H, W, OH, OW, filter);
   SRK_REQUIRE(workspace && workspace_bytes >= need, "img_resize_u8: workspace %zu < %zu", workspace_bytes, need);
   hipStream_t s = (hipStream_t)stream;

@@ -18,7 +18,9 @@ Not provided: the BSDS300 HTTP download of data.py:9-30 (no network code in this
 Beyond the reference: `Degradation` -- with `degrade=` set, the LR image is no longer the clean bicubic
 shrink of the HR patch but LR = (HR * k) shrunk + n: a random anisotropic Gaussian blur in front of the shrink and Gaussian
 noise behind it, both HIP kernels on the loader stream (csrc/degrade.hip), and with `jpeg_quality` JPEG compression of the
-result (csrc/jpeg.hip).  Without it nothing changes, draws included.
+result (csrc/jpeg.hip).  Without it nothing changes, draws included.  `Degradation2` is
+Real-ESRGAN's second-order chain in its place -- blur, resize, Gaussian or Poisson noise and JPEG, twice, then a sinc filter,
+every stage a kernel from 8 bits to 8 bits -- and `usm=True` sharpens the 8-bit patches first (csrc/usm.hip).
 """
 import ctypes
 import math
@@ -31,7 +33,7 @@ from os.path import join
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import check, ptr
 from .ops import jpeg_subsampling as jpeg_subsampling_code
 
@@ -143,20 +145,21 @@ class _Device(object):
         self._ring_ev[i] = ev
         return d
 
-    def resize(self, x, strides, planes, h, w, oh, ow, out_float):
-        """Image.resize((ow, oh), BICUBIC) of `planes` 8-bit planes addressed by element strides (plane, row, pixel)."""
+    def resize(self, x, strides, planes, h, w, oh, ow, out_float, filt=BICUBIC):
+        """Image.resize((ow, oh), BICUBIC) of `planes` 8-bit planes addressed by element strides (plane, row, pixel); filt:
+        another of Pillow's filters (BILINEAR, BOX: the second-order chain draws it)."""
         lib = self.lib
         with self._on_stream():
             y = torch.empty((planes, oh, ow), dtype=torch.float32 if out_float else torch.uint8, device=self.device)
-            key = (planes, h, w, oh, ow)
+            key = (planes, h, w, oh, ow) if filt == BICUBIC else (planes, h, w, oh, ow, filt)
             nbytes = self._ws_bytes.get(key)
             if nbytes is None:
-                nbytes = self._ws_bytes[key] = max(int(lib.srk_img_resize_u8_workspace_bytes(planes, h, w, oh, ow, BICUBIC)), 256)
+                nbytes = self._ws_bytes[key] = max(int(lib.srk_img_resize_u8_workspace_bytes(planes, h, w, oh, ow, filt)), 256)
             # one workspace per call (the calls of a batch are in flight together on the loader stream), drawn from a
             # slab that is re-used batch after batch
             ws = self._slab(nbytes)
             check(lib.srk_img_resize_u8(ptr(x), strides[0], strides[1], strides[2], ptr(y), int(out_float), planes, h, w,
-                                        oh, ow, BICUBIC, ptr(ws), nbytes, self._sp), "srk_img_resize_u8")
+                                        oh, ow, filt, ptr(ws), nbytes, self._sp), "srk_img_resize_u8")
         return y
 
     def augment(self, x, strides, c, h, w, crop, rot, fliplr, fliptb, out=None):
@@ -226,15 +229,48 @@ class _Device(object):
                   "srk_noise_u8_bytes")
         return y
 
-    def jpeg(self, x, quality, subsampling, color):
+    def jpeg(self, x, quality, subsampling, color, out_float=True):
         """srk_jpeg_u8: dense 8-bit [b, c, h, w] -> fp32 bytes / 255 of each patch compressed at quality[b] (fp64 on the
-        device, 0 = left as it is) and decoded again."""
+        device, 0 = left as it is) and decoded again; out_float False: the bytes themselves, for a stage to follow."""
         b, c, h, w = (int(v) for v in x.shape)
         with self._on_stream():
-            y = torch.empty(x.shape, dtype=torch.float32, device=self.device)
-            check(self.lib.srk_jpeg_u8(ptr(x), ptr(y), ptr(quality), c, b, h, w, int(subsampling), int(bool(color)), 1,
-                                       self._sp), "srk_jpeg_u8")
+            y = torch.empty(x.shape, dtype=torch.float32 if out_float else torch.uint8, device=self.device)
+            check(self.lib.srk_jpeg_u8(ptr(x), ptr(y), ptr(quality), c, b, h, w, int(subsampling), int(bool(color)),
+                                       int(bool(out_float)), self._sp), "srk_jpeg_u8")
         return y
+
+    def noise2(self, x, mode, gray, amount, cdf, seed, stage, color):
+        """srk_noise2_u8: dense 8-bit [b, c, h, w] -> 8 bits under the per-patch fp64 mode, gray and amount [b] and the
+        Poisson table cdf [256, 448], all on the device."""
+        b, c, h, w = (int(v) for v in x.shape)
+        with self._on_stream():
+            y = torch.empty(x.shape, dtype=torch.uint8, device=self.device)
+            check(self.lib.srk_noise2_u8(ptr(x), ptr(y), ptr(mode), ptr(gray), ptr(amount), ptr(cdf), int(seed), int(stage),
+                                         b, c, h, w, int(bool(color)), self._sp), "srk_noise2_u8")
+        return y
+
+    def usm(self, x, g, weight, threshold):
+        """srk_usm_u8: dense 8-bit [b, c, h, w] -> the unsharp-masked 8 bits; g fp64 [K] on the device."""
+        b, c, h, w = (int(v) for v in x.shape)
+        with self._on_stream():
+            y = torch.empty(x.shape, dtype=torch.uint8, device=self.device)
+            key = ("usm", b, c, h, w)
+            nbytes = self._ws_bytes.get(key)
+            if nbytes is None:
+                nbytes = self._ws_bytes[key] = max(int(self.lib.srk_usm_u8_workspace_bytes(b, c, h, w)), 256)
+            ws = self._slab(nbytes)
+            check(self.lib.srk_usm_u8(ptr(x), ptr(y), ptr(g), int(g.numel()), float(weight), float(threshold), b, c, h, w,
+                                      ptr(ws), nbytes, self._sp), "srk_usm_u8")
+        return y
+
+    def resident_f64(self, key, make):
+        """A host-made fp64 table that goes up once and stays on the device (the Poisson table, the USM Gaussian)."""
+        if not hasattr(self, "_tables"):
+            self._tables = {}
+        t = self._tables.get(key)
+        if t is None:
+            t = self._tables[key] = self.upload_f64(make())
+        return t
 
     def hand_over(self, *tensors):
         """Make the consumer's current stream wait for the loader stream; tensors become usable there."""
@@ -375,13 +411,247 @@ class Degradation(object):
         return _degrade_u8(dev, patches, weights, sigma, seed, lr_sz, lr_sz, quality, self.jpeg_subsampling, color)
 
 
+BOX, BILINEAR = 4, 2     # PIL.Image.BOX / BILINEAR / srk_interp
+USM_K, USM_WEIGHT, USM_THRESHOLD = 51, 0.5, 10.0   # Real-ESRGAN's USMSharp: radius 50 -> 51 taps, sigma 0 -> 8.0
+
+
+def _usm(dev, patches):
+    """USMSharp of dense 8-bit patches on the loader stream (srk_usm_u8); the Gaussian goes up once."""
+    g = dev.resident_f64(("usm", USM_K), lambda: ops.usm_table(USM_K, 0.0))
+    return dev.usm(patches, g, USM_WEIGHT, USM_THRESHOLD)
+
+
+class Degradation2(object):
+    """Real-ESRGAN's second-order degradation model on 8-bit stage boundaries.  Keywords carry
+    Real-ESRGAN's names and defaults.  Per batch, [b] marking what is drawn per patch:
+
+        stage 1: blur[b] -> resize to int(side * s1), filter of {BOX, BILINEAR, BICUBIC} -> noise[b] -> jpeg[b]
+        stage 2: blur[b] (prob second_blur_prob) -> resize to int(lr side * s2) -> noise[b]
+        final:   with prob 0.5  resize to the lr size -> sinc blur[b] (prob final_sinc_prob) -> jpeg[b]
+                 else           jpeg[b] -> resize to the lr size -> sinc blur[b]
+        lr = bytes / 255.0f
+
+    Draws come from Python's global `random` (or the `rng` given to apply), after the batch's patch draws, in this order:
+      1. stage-1 kernel of every patch (kernel(): below);
+      2. stage-1 resize: random() against resize_prob -> up: uniform(1, hi) | down: uniform(lo, 1) | keep: no draw; then
+         choice of the filter;
+      3. stage-1 noise: random() < gaussian_noise_prob (Gaussian, else Poisson; once a batch); per patch uniform(amount
+         range) then random() < gray_noise_prob; then getrandbits(64), the stage's seed;
+      4. stage-1 JPEG quality of every patch: randint(lo, hi);
+      5. per patch random() < second_blur_prob -> kernel(), else the delta;
+      6. stage-2 resize as 2 (resize_prob2, resize_range2);  7. stage-2 noise as 3 (noise_range2, poisson_scale_range2);
+      8. random() < 0.5: the final order;  9. choice of the final resize's filter;
+      10. per patch random() < final_sinc_prob -> choice of K, uniform cutoff -> sinc table, else the delta;
+      11. final JPEG quality of every patch: randint(lo, hi).
+    kernel(): choice of K among kernel_sizes; random() < sinc_prob -> uniform cutoff ((pi / 3, pi) for K < 13, else
+    (pi / 5, pi)); else random() against kernel_prob (iso, aniso, generalized iso, generalized aniso, plateau iso, plateau
+    aniso) -> uniform s1; aniso: uniform s2, uniform(-pi, pi) theta; generalized: uniform beta of betag_range; plateau:
+    of betap_range.  Nothing else is kept between batches, so a restored `random` state reproduces them."""
+
+    DEFAULTS = dict(kernel_sizes=tuple(range(7, 22, 2)), kernel_sizes2=tuple(range(7, 22, 2)),
+                    kernel_prob=(.45, .25, .12, .03, .12, .03), kernel_prob2=(.45, .25, .12, .03, .12, .03),
+                    sinc_prob=.1, sinc_prob2=.1, blur_sigma=(0.2, 3.0), blur_sigma2=(0.2, 1.5),
+                    betag_range=(0.5, 4.0), betag_range2=(0.5, 4.0), betap_range=(1.0, 2.0), betap_range2=(1.0, 2.0),
+                    second_blur_prob=0.8, resize_prob=(.2, .7, .1), resize_prob2=(.3, .4, .3),
+                    resize_range=(0.15, 1.5), resize_range2=(0.3, 1.2), gaussian_noise_prob=.5, gaussian_noise_prob2=.5,
+                    noise_range=(1.0, 30.0), noise_range2=(1.0, 25.0), poisson_scale_range=(0.05, 3.0),
+                    poisson_scale_range2=(0.05, 2.5), gray_noise_prob=.4, gray_noise_prob2=.4, jpeg_range=(30, 95),
+                    jpeg_range2=(30, 95), final_sinc_prob=0.8, jpeg_subsampling='4:2:0')
+    KINDS = (("gauss", False), ("gauss", True), ("ggauss", False), ("ggauss", True), ("plateau", False), ("plateau", True))
+    FILTERS = (BOX, BILINEAR, BICUBIC)
+
+    def __init__(self, **kw):
+        unknown = sorted(set(kw) - set(self.DEFAULTS))
+        if unknown:
+            raise ValueError("Degradation2: unknown setting%s %s (known: %s)"
+                             % ("s" if len(unknown) > 1 else "", ", ".join(unknown), ", ".join(sorted(self.DEFAULTS))))
+        for name, dflt in self.DEFAULTS.items():
+            v = kw.get(name, dflt)
+            if name == 'jpeg_subsampling':
+                self.jpeg_subsampling = jpeg_subsampling_code(v)
+                continue
+            if name.startswith('kernel_sizes'):
+                v = tuple(int(k) for k in v)
+                if not v or any(k % 2 == 0 or not 7 <= k <= BLUR_MAX_K for k in v):
+                    raise ValueError("%s must be odd sizes in 7..%d (got %r)" % (name, BLUR_MAX_K, kw.get(name)))
+            elif name.startswith('kernel_prob') or name.startswith('resize_prob'):
+                v = tuple(float(x) for x in v)
+                if len(v) != len(dflt) or min(v) < 0 or abs(sum(v) - 1.0) > 1e-9:
+                    raise ValueError("%s must be %d probabilities that sum to 1 (got %r)" % (name, len(dflt), kw.get(name)))
+            elif name.startswith('jpeg_range'):
+                if len(v) != 2:
+                    raise ValueError("%s must be (lo, hi) (got %r)" % (name, v))
+                v = tuple(_check_jpeg_quality(q, "%s's bounds" % name) for q in v)
+                if v[0] > v[1]:
+                    raise ValueError("%s must be lo <= hi (got %r)" % (name, kw.get(name)))
+            elif isinstance(dflt, tuple):
+                v = tuple(float(x) for x in v)
+                if len(v) != 2 or not 0.0 < v[0] <= v[1] < float('inf'):
+                    raise ValueError("%s must be 0 < lo <= hi (got %r)" % (name, kw.get(name)))
+            else:
+                v = float(v)
+                if not 0.0 <= v <= 1.0:
+                    raise ValueError("%s must lie in [0, 1] (got %r)" % (name, kw.get(name)))
+            setattr(self, name, v)
+        for name in ('resize_range', 'resize_range2'):
+            lo, hi = getattr(self, name)
+            if not lo <= 1.0 <= hi:
+                raise ValueError("%s must be lo <= 1 <= hi (got %r)" % (name, getattr(self, name)))
+
+    def check(self, crop, sf):
+        """Refuse a crop / scale at which a blurred side could not mirror the widest table's halo (reflect-101 with K = 21
+        needs sides > 10): the stage-2 blur runs at int(crop * s1), the final one at crop // sf."""
+        if min(int(crop * self.resize_range[0]), crop // sf) <= BLUR_MAX_K // 2:
+            raise ValueError("resize_range %r with crop_size %d and scale_factor %d: the chain blurs sides of "
+                             "int(crop_size * resize_range[0]) = %d and crop_size // scale_factor = %d, and both must exceed "
+                             "%d (raise crop_size or resize_range's lower bound)"
+                             % (self.resize_range, crop, sf, int(crop * self.resize_range[0]), crop // sf, BLUR_MAX_K // 2))
+
+    # -- draws ------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _cutoff(rng, K):
+        return rng.uniform(math.pi / 3 if K < 13 else math.pi / 5, math.pi)
+
+    def _kernel(self, rng, stage2):
+        sfx = '2' if stage2 else ''
+        K = rng.choice(getattr(self, 'kernel_sizes' + sfx))
+        if rng.random() < getattr(self, 'sinc_prob' + sfx):
+            return ops.blur_table("sinc", K, cutoff=self._cutoff(rng, K))
+        r, acc, kind = rng.random(), 0.0, len(self.KINDS) - 1
+        for i, pk in enumerate(getattr(self, 'kernel_prob' + sfx)):
+            acc += pk
+            if r < acc:
+                kind = i
+                break
+        name, aniso = self.KINDS[kind]
+        lo, hi = getattr(self, 'blur_sigma' + sfx)
+        s1 = rng.uniform(lo, hi)
+        s2, theta = (rng.uniform(lo, hi), rng.uniform(-math.pi, math.pi)) if aniso else (s1, 0.0)
+        beta = 1.0
+        if name == "ggauss":
+            beta = rng.uniform(*getattr(self, 'betag_range' + sfx))
+        elif name == "plateau":
+            beta = rng.uniform(*getattr(self, 'betap_range' + sfx))
+        return ops.blur_table(name, K, s1, s2, theta, beta)
+
+    def _resize(self, rng, stage2):
+        sfx = '2' if stage2 else ''
+        up, down, _ = getattr(self, 'resize_prob' + sfx)
+        lo, hi = getattr(self, 'resize_range' + sfx)
+        r = rng.random()
+        s = rng.uniform(1.0, hi) if r < up else (rng.uniform(lo, 1.0) if r < up + down else 1.0)
+        return s, rng.choice(self.FILTERS)
+
+    def _noise(self, rng, batch, stage2):
+        sfx = '2' if stage2 else ''
+        gauss = rng.random() < getattr(self, 'gaussian_noise_prob' + sfx)
+        lo, hi = getattr(self, ('noise_range' if gauss else 'poisson_scale_range') + sfx)
+        amount, gray = np.zeros(batch, np.float64), np.zeros(batch, np.float64)
+        for j in range(batch):
+            amount[j] = rng.uniform(lo, hi)
+            gray[j] = float(rng.random() < getattr(self, 'gray_noise_prob' + sfx))
+        mode = np.full(batch, float(ops.NOISE2_GAUSS if gauss else ops.NOISE2_POISSON), np.float64)
+        return dict(mode=mode, gray=gray, amount=amount, seed=rng.getrandbits(64))
+
+    def draw(self, batch, rng=random):
+        """One batch's parameters as host values, in the order the class docstring fixes: a dict with the tables
+        k1, k2, k3 [B, K, K] (narrower ones and the delta centred among zeros), the scales and filters s1, f1, s2, f2, f3,
+        the noise dicts n1, n2 (mode, gray, amount [B], seed), the qualities q1, q2 [B] and `resize_first`."""
+        p = {}
+        t1 = [self._kernel(rng, False) for _ in range(batch)]
+        p['s1'], p['f1'] = self._resize(rng, False)
+        p['n1'] = self._noise(rng, batch, False)
+        p['q1'] = np.array([rng.randint(*self.jpeg_range) for _ in range(batch)], np.float64)
+        t2 = [self._kernel(rng, True) if rng.random() < self.second_blur_prob else None for _ in range(batch)]
+        p['s2'], p['f2'] = self._resize(rng, True)
+        p['n2'] = self._noise(rng, batch, True)
+        p['resize_first'] = rng.random() < 0.5
+        p['f3'] = rng.choice(self.FILTERS)
+        t3 = []
+        for _ in range(batch):
+            if rng.random() < self.final_sinc_prob:
+                K = rng.choice(self.kernel_sizes2)
+                t3.append(ops.blur_table("sinc", K, cutoff=self._cutoff(rng, K)))
+            else:
+                t3.append(None)
+        p['q2'] = np.array([rng.randint(*self.jpeg_range2) for _ in range(batch)], np.float64)
+        for name, tables in (('k1', t1), ('k2', t2), ('k3', t3)):
+            p[name] = _centred(tables, max([w.shape[0] for w in tables if w is not None] + [7]))
+        return p
+
+    def apply(self, dev, patches, lr_sz, color=True, rng=random):
+        """Dense 8-bit patches [B, C, H, W] on the device -> the degraded fp32 lr [B, C, lr_sz, lr_sz] (lr_sz: a side, or
+        (h, w)).  color: the planes are R, G, B (else Y, Cb, Cr): the JPEG stages and gray noise ask.  Every per-patch
+        parameter and table crosses in one copy; a stage that is the identity for the whole batch (all-delta tables, an
+        unchanged size, noise off, quality 0) is not launched."""
+        b, c, h, w = (int(v) for v in patches.shape)
+        lh, lw = (int(lr_sz), int(lr_sz)) if np.ndim(lr_sz) == 0 else (int(lr_sz[0]), int(lr_sz[1]))
+        p = self.draw(b, rng)
+        parts = [p['k1'], p['k2'], p['k3'], p['q1'], p['q2']] + [p[n][f] for n in ('n1', 'n2') for f in ('mode', 'gray', 'amount')]
+        flat = dev.upload_f64(np.concatenate([a.reshape(-1) for a in parts]))
+        on_dev, off = [], 0
+        for a in parts:
+            on_dev.append(flat[off:off + a.size].view(a.shape))
+            off += a.size
+        k1, k2, k3, q1, q2, m1, g1, a1, m2, g2, a2 = on_dev
+        cdf = dev.resident_f64(("poisson", ops.POISSON_PEAK), ops.poisson_cdf)
+        st = {'x': patches, 'h': h, 'w': w}
+
+        def blur(host, table):
+            K = host.shape[-1]
+            if bool((host[:, K // 2, K // 2] != 1.0).any()):
+                st['x'] = dev.blur(st['x'], table, c, b, st['h'], st['w'])
+
+        def resize(oh, ow, filt, out_float=False):
+            oh, ow = max(1, oh), max(1, ow)
+            if (oh, ow) != (st['h'], st['w']) or out_float:
+                st['x'] = dev.resize(st['x'], _CHW(st['h'], st['w']), b * c, st['h'], st['w'], oh, ow, out_float,
+                                     filt=filt).view(b, c, oh, ow)
+                st['h'], st['w'] = oh, ow
+
+        def noise(n, mode, gray, amount, stage):
+            if bool((n['mode'] != 0.0).any()):
+                st['x'] = dev.noise2(st['x'], mode, gray, amount, cdf, n['seed'], stage, color)
+
+        def jpeg(host, quality, out_float=False):
+            if bool((host != 0.0).any()) or out_float:
+                st['x'] = dev.jpeg(st['x'], quality, self.jpeg_subsampling, color, out_float=out_float)
+
+        blur(p['k1'], k1)
+        resize(int(h * p['s1']), int(w * p['s1']), p['f1'])
+        noise(p['n1'], m1, g1, a1, 1)
+        jpeg(p['q1'], q1)
+        blur(p['k2'], k2)
+        resize(int(lh * p['s2']), int(lw * p['s2']), p['f2'])
+        noise(p['n2'], m2, g2, a2, 2)
+        if p['resize_first']:
+            resize(lh, lw, p['f3'])
+            blur(p['k3'], k3)
+            jpeg(p['q2'], q2, out_float=True)
+        else:
+            jpeg(p['q2'], q2)
+            K = p['k3'].shape[-1]
+            sinc = bool((p['k3'][:, K // 2, K // 2] != 1.0).any())
+            resize(lh, lw, p['f3'], out_float=not sinc)
+            if sinc:
+                blur(p['k3'], k3)
+                resize(lh, lw, p['f3'], out_float=True)      # (an unchanged size: the bytes / 255 and nothing else)
+        return st['x']
+
+
 class TrainDatasetFromFolder(object):
     """dataset.py:22-104 with device-side transforms.  `__getitem__` returns (lr_img, hr_img, bc_img) CUDA tensors."""
 
     def __init__(self, image_dirs, is_gray=False, random_scale=True, crop_size=128, rotate=True, fliplr=True,
-                 fliptb=True, scale_factor=4, device="cuda", degrade=None):
+                 fliptb=True, scale_factor=4, device="cuda", degrade=None, usm=False):
         self.image_filenames = []
-        self.degrade = degrade    # a Degradation, or None: the clean bicubic shrink of the reference
+        self.degrade = degrade    # a Degradation or a Degradation2, or None: the clean bicubic shrink of the reference
+        self.usm = bool(usm)      # Real-ESRGAN's USMSharp on the 8-bit patches: hr and the shrink's input are the sharpened bytes
+        if isinstance(degrade, Degradation2):
+            degrade.check(calculate_valid_crop_size(crop_size, scale_factor), scale_factor)
+        if self.usm and calculate_valid_crop_size(crop_size, scale_factor) <= USM_K // 2:
+            raise ValueError("usm: crop_size %d must exceed %d, the radius of USMSharp's %d-tap Gaussian"
+                             % (crop_size, USM_K // 2, USM_K))
         for image_dir in image_dirs:
             self.image_filenames.extend(join(image_dir, x) for x in sorted(listdir(image_dir)) if is_image_file(x))
         self.is_gray, self.random_scale, self.crop_size = is_gray, random_scale, crop_size
@@ -476,6 +746,8 @@ class TrainDatasetFromFolder(object):
         b, c = patches.shape[0], patches.shape[1]
         lr_sz = crop // sf
         st = _CHW(crop, crop)
+        if self.usm:
+            patches = _usm(dev, patches.contiguous())
         hr = dev.resize(patches, st, b * c, crop, crop, crop, crop, out_float=True).view(b, c, crop, crop)
         if self.degrade is not None:
             lr = self.degrade.apply(dev, patches.contiguous(), lr_sz, color=not self.is_gray)
@@ -498,8 +770,17 @@ class TestDatasetFromFolder(object):
     """dataset.py:106-149 with device-side resizes."""
 
     def __init__(self, image_dir, is_gray=False, scale_factor=4, device="cuda", degrade=None, jpeg=None,
-                 jpeg_subsampling='4:2:0'):
+                 jpeg_subsampling='4:2:0', degrade2=None):
         self.image_filenames = [join(image_dir, x) for x in sorted(listdir(image_dir)) if is_image_file(x)]
+        # degrade2: None, or (Degradation2, seed): item i's whole chain is drawn from a private random.Random seeded by
+        # (seed, i), so an item is the same on every read and the global `random` is left alone
+        self.degrade2 = None
+        if degrade2 is not None:
+            if degrade is not None or jpeg is not None:
+                raise ValueError("degrade2 brings its own blur, noise and JPEG stages: give neither degrade nor jpeg with it")
+            if not (len(degrade2) == 2 and isinstance(degrade2[0], Degradation2)):
+                raise ValueError("degrade2 must be (Degradation2, seed), got %r" % (degrade2,))
+            self.degrade2 = (degrade2[0], int(degrade2[1]))
         # jpeg: None, or one FIXED quality 1..100 at which every low-resolution image is compressed and decoded again,
         # behind the degradation where there is one
         self.jpeg = None if jpeg is None else _check_jpeg_quality(jpeg, "jpeg")
@@ -535,7 +816,15 @@ class TestDatasetFromFolder(object):
         img = dev.upload(hwc)
         st = _HWC(h, w, c)
         hr = dev.resize(img, st, c, h, w, hr_h, hr_w, out_float=True)
-        if self.degrade is not None or self.jpeg is not None:
+        if self.degrade2 is not None:
+            d, seed = self.degrade2
+            if min(int(h * d.resize_range[0]), int(w * d.resize_range[0]), lr_h, lr_w) <= BLUR_MAX_K // 2:
+                raise ValueError("degrade2: image %dx%d is too small for resize_range %r at scale_factor %d (every blurred "
+                                 "side must exceed %d)" % (w, h, d.resize_range, sf, BLUR_MAX_K // 2))
+            with torch.cuda.stream(dev.stream):
+                planes = img.permute(2, 0, 1).contiguous().unsqueeze(0)
+            lr = d.apply(dev, planes, (lr_h, lr_w), color=not self.is_gray, rng=test_item_rng(seed, index))[0]
+        elif self.degrade is not None or self.jpeg is not None:
             with torch.cuda.stream(dev.stream):
                 planes = img.permute(2, 0, 1).contiguous().unsqueeze(0)   # (the blur reads dense planes)
             if self.degrade is not None:
@@ -551,7 +840,12 @@ class TestDatasetFromFolder(object):
         return dev.hand_over(lr, hr, bc)
 
 
-def get_training_set(data_dir, datasets, crop_size, scale_factor, is_gray=False, device="cuda", degrade=None):
+def test_item_rng(seed, index):
+    """The private generator of test item `index` under degrade2's `seed`."""
+    return random.Random("degrade2:%d:%d" % (int(seed), int(index)))
+
+
+def get_training_set(data_dir, datasets, crop_size, scale_factor, is_gray=False, device="cuda", degrade=None, usm=False):
     """data.py:33-51 (directory layout and augmentation switches; 'bsds300' must already be on disk)."""
     train_dir = []
     for dataset in datasets:
@@ -562,11 +856,12 @@ def get_training_set(data_dir, datasets, crop_size, scale_factor, is_gray=False,
         else:
             train_dir.append(join(data_dir, dataset))
     return TrainDatasetFromFolder(train_dir, is_gray=is_gray, random_scale=True, crop_size=crop_size, rotate=True,
-                                  fliplr=True, fliptb=True, scale_factor=scale_factor, device=device, degrade=degrade)
+                                  fliplr=True, fliptb=True, scale_factor=scale_factor, device=device, degrade=degrade,
+                                  usm=usm)
 
 
 def get_test_set(data_dir, dataset, scale_factor, is_gray=False, device="cuda", degrade=None, jpeg=None,
-                 jpeg_subsampling='4:2:0'):
+                 jpeg_subsampling='4:2:0', degrade2=None):
     """data.py:54-65"""
     if dataset == 'bsds300':
         test_dir = join(data_dir, "BSDS300/images", "test")
@@ -575,7 +870,7 @@ def get_test_set(data_dir, dataset, scale_factor, is_gray=False, device="cuda", 
     else:
         test_dir = join(data_dir, dataset)
     return TestDatasetFromFolder(test_dir, is_gray=is_gray, scale_factor=scale_factor, device=device, degrade=degrade,
-                                 jpeg=jpeg, jpeg_subsampling=jpeg_subsampling)
+                                 jpeg=jpeg, jpeg_subsampling=jpeg_subsampling, degrade2=degrade2)
 
 
 class PatchLoader(object):

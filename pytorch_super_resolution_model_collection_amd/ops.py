@@ -10,6 +10,7 @@ import ctypes
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -2020,11 +2021,11 @@ def resize_u8(planes_u8, oh, ow, interpolation="bicubic", out_float=False):
     _require_u8("resize_u8", planes_u8)
     if planes_u8.dim() != 3:
         raise RuntimeError("resize_u8 expects [P,H,W] planes, got shape %s" % (tuple(planes_u8.shape),))
-    if interpolation not in ("bicubic", "bilinear"):
-        raise ValueError("resize_u8: interpolation must be 'bicubic' or 'bilinear'")
+    if interpolation not in ("bicubic", "bilinear", "box"):
+        raise ValueError("resize_u8: interpolation must be 'bicubic', 'bilinear' or 'box'")
     p, h, w = (int(v) for v in planes_u8.shape)
     lib = _lib.load()
-    flt = _INTERP[interpolation]
+    flt = INTERP_BOX if interpolation == "box" else _INTERP[interpolation]
     y = torch.empty((p, oh, ow), dtype=torch.float32 if out_float else torch.uint8, device=planes_u8.device)
     nbytes = max(int(lib.srk_img_resize_u8_workspace_bytes(p, h, w, oh, ow, flt)), 256)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=planes_u8.device)
@@ -2128,6 +2129,87 @@ def noise_u8_bytes(x, sigma, seed):
     y = torch.empty_like(x)
     check(_lib.load().srk_noise_u8_bytes(ptr(x), ptr(y), ptr(sigma), seed, b, x.numel() // b, stream_ptr()),
           "srk_noise_u8_bytes")
+    return y
+
+
+# ---- Real-ESRGAN's second-order degradation (data.Degradation2) ------------------------------------
+INTERP_BOX = 4                                                          # SRK_INTERP_BOX
+BLUR_KINDS = {"gauss": 0, "ggauss": 1, "plateau": 2, "sinc": 3}         # SRK_BLUR_*
+NOISE2_OFF, NOISE2_GAUSS, NOISE2_POISSON = 0, 1, 2                      # SRK_NOISE2_*
+POISSON_KT, POISSON_PEAK = 448, 256.0                                   # SRK_POISSON_KT; the chain's fixed peak
+USM_MAX_K = 51                                                          # SRK_USM_MAX_K
+
+
+def blur_table(kind, K, s1=1.0, s2=1.0, theta=0.0, beta=1.0, cutoff=1.0):
+    """srk_blur_table_host: the normalised K x K fp64 table (numpy) of kind 'gauss', 'ggauss', 'plateau' or 'sinc', K odd
+    in 7..21, for blur_u8 to take as it is.  Made on the host; needs no GPU."""
+    if kind not in BLUR_KINDS:
+        raise ValueError("blur_table: kind must be one of %s (got %r)" % (sorted(BLUR_KINDS), kind))
+    K = int(K)
+    buf = (ctypes.c_double * (K * K if K > 0 else 1))()
+    check(_lib.load().srk_blur_table_host(BLUR_KINDS[kind], K, float(s1), float(s2), float(theta), float(beta),
+                                          float(cutoff), buf), "srk_blur_table_host")
+    return np.frombuffer(buf, np.float64).reshape(K, K)
+
+
+def poisson_cdf(peak=POISSON_PEAK, KT=POISSON_KT):
+    """srk_poisson_cdf_host: the inversion table cdf[256][KT] (fp64 numpy) that noise2_u8 reads, cdf[L][k] = P(Pois(L * peak
+    / 255) <= k), last column 1.0.  Made on the host; needs no GPU."""
+    out = np.empty((256, int(KT)), np.float64)
+    check(_lib.load().srk_poisson_cdf_host(float(peak), int(KT), ctypes.c_void_p(out.ctypes.data)), "srk_poisson_cdf_host")
+    return out
+
+
+def usm_table(K=USM_MAX_K, sigma=0.0):
+    """srk_usm_table_host: the normalised K-tap Gaussian (fp64 numpy) of usm_u8; sigma 0 means cv2's rule (8.0 at K = 51)."""
+    K = int(K)
+    buf = (ctypes.c_double * max(K, 1))()
+    check(_lib.load().srk_usm_table_host(K, float(sigma), buf), "srk_usm_table_host")
+    return np.frombuffer(buf, np.float64)[:K].copy()
+
+
+def noise2_u8(x, mode, gray, amount, cdf, seed, stage=0, color=True):
+    """The second-order chain's noise on 8-bit patches x [B,C,H,W] (C 1 or 3) on the device: srk_noise2_u8.  mode, gray and
+    amount are fp64 [B] per patch: mode 0 leaves the patch, 1 adds Gaussian noise of standard deviation `amount` levels, 2
+    Poisson noise scaled by `amount` (k by inversion from `cdf` [256, 448], see poisson_cdf()); gray != 0 draws once per
+    pixel for all planes, from the mean of R, G, B (color) or from plane 0 (the Y of Y, Cb, Cr).  `stage` (0, 1, 2) goes into the generator's counter; stage 0 with colour Gaussian noise gives
+    noise_u8_bytes' bytes.  Returns uint8 of x's shape; the same inputs give the same bytes."""
+    _require_u8("noise2_u8", x)
+    if x.dim() != 4 or x.numel() == 0:
+        raise RuntimeError("noise2_u8 expects a non-empty x [B,C,H,W], got shape %s" % (tuple(x.shape),))
+    b, c, h, w = (int(v) for v in x.shape)
+    mode = _require_f64("noise2_u8", "mode", mode, (b,))
+    gray = _require_f64("noise2_u8", "gray", gray, (b,))
+    amount = _require_f64("noise2_u8", "amount", amount, (b,))
+    cdf = _require_f64("noise2_u8", "cdf", cdf, (256, POISSON_KT))
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("noise2_u8: seed must fit 64 bits (got %d)" % seed)
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    check(_lib.load().srk_noise2_u8(ptr(x), ptr(y), ptr(mode), ptr(gray), ptr(amount), ptr(cdf), seed, int(stage), b, c, h, w,
+                                    int(bool(color)), stream_ptr()), "srk_noise2_u8")
+    return y
+
+
+def usm_u8(x, g=None, weight=0.5, threshold=10.0):
+    """Real-ESRGAN's USMSharp on 8-bit patches x [B,C,H,W] (C 1 or 3, sides > K // 2) on the device: srk_usm_u8.  g: the
+    fp64 [K] Gaussian on the device (None: usm_table(), K = 51, sigma 8).  Returns uint8 of x's shape."""
+    _require_u8("usm_u8", x)
+    if x.dim() != 4 or x.numel() == 0:
+        raise RuntimeError("usm_u8 expects a non-empty x [B,C,H,W], got shape %s" % (tuple(x.shape),))
+    b, c, h, w = (int(v) for v in x.shape)
+    if g is None:
+        g = torch.from_numpy(usm_table()).to(x.device)
+    k = int(g.numel())
+    g = _require_f64("usm_u8", "g", g, (k,))
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    lib = _lib.load()
+    nbytes = max(int(lib.srk_usm_u8_workspace_bytes(b, c, h, w)), 256)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    check(lib.srk_usm_u8(ptr(x), ptr(y), ptr(g), k, float(weight), float(threshold), b, c, h, w, ptr(ws), nbytes,
+                         stream_ptr()), "srk_usm_u8")
     return y
 
 

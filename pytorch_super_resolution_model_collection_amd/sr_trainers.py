@@ -61,6 +61,29 @@ def apply_lr_decay(kind, epoch, *optimizers):
     return True
 
 
+def check_data_flags(args):
+    """The loader's degradation flags against each other and against --synthetic, as main.py refuses them."""
+    degrade2 = getattr(args, "degrade2", None) is not None      # ({}: --degrade2 with its defaults)
+    degrade2_test = getattr(args, "degrade2_test", None) is not None
+    for flag in ("degrade", "degrade_test", "jpeg_quality", "jpeg_test"):
+        if getattr(args, flag, None) and getattr(args, "synthetic", False):
+            raise ValueError("%s: synthetic patches are not degraded, train and test on image folders (main.py "
+                             "--%s without --synthetic)" % (flag, flag))
+    for flag, on in (("degrade2", degrade2), ("usm", bool(getattr(args, "usm", False))), ("degrade2_test", degrade2_test)):
+        if on and getattr(args, "synthetic", False):
+            raise ValueError("%s: synthetic patches are not degraded, train and test on image folders (main.py "
+                             "--%s without --synthetic)" % (flag, flag))
+    if degrade2 and getattr(args, "degrade", False):
+        raise ValueError("degrade2 and degrade are two degradation models: give one (main.py --degrade2 or --degrade)")
+    if degrade2 and getattr(args, "jpeg_quality", None):
+        raise ValueError("jpeg_quality belongs to --degrade; degrade2's chain has JPEG stages of its own (jpeg_range, "
+                         "jpeg_range2 in its settings)")
+    if degrade2_test and (getattr(args, "degrade_test", None) or getattr(args, "jpeg_test", None)):
+        raise ValueError("degrade2_test brings its own blur, noise and JPEG: give neither degrade_test nor jpeg_test with it")
+    if getattr(args, "jpeg_quality", None) and not getattr(args, "degrade", False):
+        raise ValueError("jpeg_quality is a stage of the training degradation (main.py --jpeg_quality with --degrade)")
+
+
 def check_perceptual_args(args, kind):
     """--vgg_weights / --perceptual / --vgg_loss_weight of main.py: the VGG feature term belongs to the SRGAN step, reads
     RGB, and trains only with weights to extract features with.  Raises ValueError naming the flag."""
@@ -180,12 +203,7 @@ class _Trainer(object):
         check_perceptual_args(args, self.kind)
         check_lpips_args(args, self.kind)
         self.disc_args = check_discriminator_args(args, self.kind)
-        for flag in ("degrade", "degrade_test", "jpeg_quality", "jpeg_test"):
-            if getattr(args, flag, None) and getattr(args, "synthetic", False):
-                raise ValueError("%s: synthetic patches are not degraded, train and test on image folders (main.py "
-                                 "--%s without --synthetic)" % (flag, flag))
-        if getattr(args, "jpeg_quality", None) and not getattr(args, "degrade", False):
-            raise ValueError("jpeg_quality is a stage of the training degradation (main.py --jpeg_quality with --degrade)")
+        check_data_flags(args)
         self.ema_decay = optim._check_ema_decay(getattr(args, "ema_decay", 0.0))
         if self.kind == "drcn" and self.ema_decay > 0:
             raise ValueError("ema_decay: %s keeps no EMA of its weights (main.py --ema_decay)" % self.model_name)
@@ -334,16 +352,22 @@ class _Trainer(object):
                                                jpeg_quality=getattr(args, "jpeg_quality", None),
                                                jpeg_prob=getattr(args, "jpeg_prob", 1.0),
                                                jpeg_subsampling=getattr(args, "jpeg_subsampling", "420"))
+                if getattr(args, "degrade2", None) is not None:   # main.py --degrade2: the second-order chain
+                    degrade = data.Degradation2(**dict(args.degrade2))
                 ds = data.get_training_set(self.data_dir, dataset, self.crop_size, self.scale_factor, is_gray=is_gray,
-                                           device=self.device, degrade=degrade)
+                                           device=self.device, degrade=degrade, usm=bool(getattr(args, "usm", False)))
                 bs, shuffle = self.batch_size, True
             else:
                 fixed = getattr(args, "degrade_test", None)   # (s1, s2, theta in degrees, noise sigma)
                 if fixed:
                     fixed = (fixed[0], fixed[1], math.radians(fixed[2]), fixed[3])
+                seed2 = getattr(args, "degrade2_test", None)   # every test item under its own seeded chain
+                if seed2 is not None:
+                    settings = getattr(args, "degrade2", None) or {}
+                    seed2 = (data.Degradation2(**dict(settings)), int(seed2))
                 ds = data.get_test_set(self.data_dir, dataset, self.scale_factor, is_gray=is_gray, device=self.device,
                                        degrade=fixed or None, jpeg=getattr(args, "jpeg_test", None),
-                                       jpeg_subsampling=getattr(args, "jpeg_subsampling", "420"))
+                                       jpeg_subsampling=getattr(args, "jpeg_subsampling", "420"), degrade2=seed2)
                 bs, shuffle = self.test_batch_size or 1, False
         except (OSError, TypeError) as e:
             if not is_train:
