@@ -2859,6 +2859,16 @@ def _dense_check(rc, what):
     check(rc, what)
 
 
+def _dense_launch(name, args, e=None, at=None):
+    """srk_dense_conv_<name>(*args), or with a DenseEpilogue `e` its _ex twin, which takes `e` as argument number `at`:
+    the one place that chooses between the two (they are different kernel instantiations)."""
+    symbol = "srk_dense_conv_" + name
+    if e is not None:
+        symbol += "_ex"
+        args.insert(at, ctypes.byref(e))
+    _dense_check(getattr(_lib.load(), symbol)(*args), symbol)
+
+
 class _Slice(object):
     """`channels` channels of a dense NHWC buffer, from channel `off`: pointer and pixel stride for the kernels."""
     __slots__ = ("t", "off", "channels", "ld", "p")
@@ -2876,19 +2886,29 @@ class _Slice(object):
         self.p = ctypes.c_void_p(t.data_ptr() + 4 * off)
 
 
-def _dense_desc(a, b, cout, k, act, slope, terms):
+_NO_SLICE = _Slice.__new__(_Slice)      # an operand the call does not have: a null pointer, no channels, stride 0
+_NO_SLICE.t, _NO_SLICE.off, _NO_SLICE.channels, _NO_SLICE.ld, _NO_SLICE.p = None, 0, 0, 0, None
+
+
+def _dense_inputs(what, a, a_off, ca, b, b_off, cb):
+    """The slices (a, b) a convolution or its weight gradient reads; no b without a buffer or with cb = 0."""
+    sa = _Slice(what + ": a", a, a_off, a.shape[1] - a_off if ca is None else ca)
+    if b is not None and (cb is None or cb > 0):
+        return sa, _Slice(what + ": b", b, b_off, b.shape[1] - b_off if cb is None else cb, sa)
+    return sa, _NO_SLICE
+
+
+def _dense_desc(what, like, weight, ca, cb, act, slope, terms):
+    """The descriptor of a convolution with `weight` (or its gradient) [Cout, ca + cb, K, K] over pictures the size of the
+    slice `like`'s, every stride still 0: the caller fills in those of the operands it has."""
     d = _lib.DenseDesc()
-    d.N, d.H, d.W = int(a.t.shape[0]), int(a.t.shape[2]), int(a.t.shape[3])
-    d.K, d.CA, d.CB, d.Cout = int(k), a.channels, (b.channels if b is not None else 0), int(cout)
-    d.ldA, d.ldB = a.ld, (b.ld if b is not None else 0)
+    d.N, d.H, d.W = int(like.t.shape[0]), int(like.t.shape[2]), int(like.t.shape[3])
+    d.K, d.CA, d.CB, d.Cout = int(weight.shape[2]), int(ca), int(cb), int(weight.shape[0])
     d.act, d.slope, d.terms = int(act), float(slope), int(terms)
-    return d
-
-
-def _dense_weight(what, weight, d):
     if tuple(weight.shape) != (d.Cout, d.CA + d.CB, d.K, d.K) or not weight.is_contiguous():
         raise ValueError("%s: a contiguous weight [%d, %d, %d, %d] is expected, got %s"
                          % (what, d.Cout, d.CA + d.CB, d.K, d.K, tuple(weight.shape)))
+    return d
 
 
 def dense_conv(a, weight, bias=None, b=None, out=None, ca=None, a_off=0, cb=None, b_off=0, out_off=0, act=ACT_NONE,
@@ -2899,34 +2919,22 @@ def dense_conv(a, weight, bias=None, b=None, out=None, ca=None, a_off=0, cb=None
     No autograd (ops.residual_dense_blocks is the differentiable user).  ValueError for what no kernel covers.
     With `s` (or residual2) the call is srk_dense_conv_forward_ex:
     out = s * act(conv + bias) + r1 * residual + r2 * residual2[:, res2_off : res2_off + Cout] (s=None: 1)."""
-    lib = _lib.load()
     what = "dense_conv"
-    cout, k = int(weight.shape[0]), int(weight.shape[2])
-    sa = _Slice(what + ": a", a, a_off, a.shape[1] - a_off if ca is None else ca)
-    sb = None
-    if b is not None and (cb is None or cb > 0):
-        sb = _Slice(what + ": b", b, b_off, b.shape[1] - b_off if cb is None else cb, sa)
+    cout = int(weight.shape[0])
+    sa, sb = _dense_inputs(what, a, a_off, ca, b, b_off, cb)
     if out is None:
         out = _empty_cl(a.shape[0], cout, a.shape[2], a.shape[3], a)
     so = _Slice(what + ": out", out, out_off, cout, sa)
-    d = _dense_desc(sa, sb, cout, k, act, slope, terms)
-    _dense_weight(what, weight, d)
-    d.ldY = so.ld
-    sr = None
-    if residual is not None:
-        sr = _Slice(what + ": residual", residual, res_off, cout, sa)
-        d.ldR = sr.ld
+    d = _dense_desc(what, sa, weight, sa.channels, sb.channels, act, slope, terms)
+    sr = _Slice(what + ": residual", residual, res_off, cout, sa) if residual is not None else _NO_SLICE
+    d.ldA, d.ldB, d.ldY, d.ldR = sa.ld, sb.ld, so.ld, sr.ld
+    args = [ctypes.byref(d), sa.p, sb.p, ptr(weight), ptr(bias), sr.p, so.p, stream_ptr()]   # (an address needs no detach)
+    e = None
     if s is not None or residual2 is not None:
-        sr2 = _Slice(what + ": residual2", residual2, res2_off, cout, sa) if residual2 is not None else None
-        e = _lib.DenseEpilogue(1.0 if s is None else s, r1, r2, sr2.ld if sr2 else 0)
-        _dense_check(lib.srk_dense_conv_forward_ex(ctypes.byref(d), sa.p, sb.p if sb else None, ptr(weight.detach()),
-                                                   ptr(bias.detach()) if bias is not None else None, sr.p if sr else None,
-                                                   sr2.p if sr2 else None, ctypes.byref(e), so.p, stream_ptr()),
-                     "srk_dense_conv_forward_ex")
-        return out
-    _dense_check(lib.srk_dense_conv_forward(ctypes.byref(d), sa.p, sb.p if sb else None, ptr(weight.detach()),
-                                            ptr(bias.detach()) if bias is not None else None, sr.p if sr else None, so.p,
-                                            stream_ptr()), "srk_dense_conv_forward")
+        sr2 = _Slice(what + ": residual2", residual2, res2_off, cout, sa) if residual2 is not None else _NO_SLICE
+        e = _lib.DenseEpilogue(1.0 if s is None else s, r1, r2, sr2.ld)
+        args.insert(6, sr2.p)       # the _ex twin takes R2 behind R1, in front of its epilogue
+    _dense_launch("forward", args, e, 7)
     return out
 
 
@@ -2935,40 +2943,17 @@ def dense_conv_backward_data(dy, weight, ca, cb=0, y_saved=None, da=None, db=Non
     """The data gradient of dense_conv into the slices da[:, da_off : da_off + ca] and db[:, db_off : db_off + cb]
     (either may be None): slice = beta * slice + conv^T(dy * act'(y_saved)) (+ add into da), beta 0 or 1.  With `s` the
     call is srk_dense_conv_backward_data_ex: dy is scaled by s and add by a1."""
-    lib = _lib.load()
     what = "dense_conv_backward_data"
-    cout, k = int(weight.shape[0]), int(weight.shape[2])
+    cout = int(weight.shape[0])
     sdy = _Slice(what + ": dy", dy, dy_off, cout)
-    d = _lib.DenseDesc()
-    d.N, d.H, d.W = int(dy.shape[0]), int(dy.shape[2]), int(dy.shape[3])
-    d.K, d.CA, d.CB, d.Cout = k, int(ca), int(cb), cout
-    d.act, d.slope, d.terms = int(act), float(slope), int(terms)
-    _dense_weight(what, weight, d)
-    d.ldDy = sdy.ld
-    sy = sda = sdb = sadd = None
-    if y_saved is not None:
-        sy = _Slice(what + ": y_saved", y_saved, y_off, cout, sdy)
-        d.ldY = sy.ld
-    if da is not None:
-        sda = _Slice(what + ": da", da, da_off, ca, sdy)
-        d.ldDA = sda.ld
-    if db is not None and cb > 0:
-        sdb = _Slice(what + ": db", db, db_off, cb, sdy)
-        d.ldDB = sdb.ld
-    if add is not None:
-        sadd = _Slice(what + ": add", add, add_off, ca, sdy)
-        d.ldAdd = sadd.ld
-    if s is not None:
-        e = _lib.DenseEpilogue(s, a1=a1)
-        _dense_check(lib.srk_dense_conv_backward_data_ex(ctypes.byref(d), sdy.p, sy.p if sy else None, ptr(weight.detach()),
-                                                         sda.p if sda else None, float(beta_a), sdb.p if sdb else None,
-                                                         float(beta_b), sadd.p if sadd else None, ctypes.byref(e),
-                                                         stream_ptr()), "srk_dense_conv_backward_data_ex")
-        return da, db
-    _dense_check(lib.srk_dense_conv_backward_data(ctypes.byref(d), sdy.p, sy.p if sy else None, ptr(weight.detach()),
-                                                  sda.p if sda else None, float(beta_a), sdb.p if sdb else None,
-                                                  float(beta_b), sadd.p if sadd else None, stream_ptr()),
-                 "srk_dense_conv_backward_data")
+    d = _dense_desc(what, sdy, weight, ca, cb, act, slope, terms)
+    sy = _Slice(what + ": y_saved", y_saved, y_off, cout, sdy) if y_saved is not None else _NO_SLICE
+    sda = _Slice(what + ": da", da, da_off, ca, sdy) if da is not None else _NO_SLICE
+    sdb = _Slice(what + ": db", db, db_off, cb, sdy) if db is not None and cb > 0 else _NO_SLICE
+    sadd = _Slice(what + ": add", add, add_off, ca, sdy) if add is not None else _NO_SLICE
+    d.ldDy, d.ldY, d.ldDA, d.ldDB, d.ldAdd = sdy.ld, sy.ld, sda.ld, sdb.ld, sadd.ld
+    _dense_launch("backward_data", [ctypes.byref(d), sdy.p, sy.p, ptr(weight), sda.p, float(beta_a), sdb.p, float(beta_b),
+                                    sadd.p, stream_ptr()], None if s is None else _lib.DenseEpilogue(s, a1=a1), 9)
     return da, db
 
 
@@ -2980,39 +2965,79 @@ def dense_conv_backward_weight(a, dy, dw, dbias=None, b=None, y_saved=None, ca=N
     srk_dense_conv_backward_weight_ex: dy is scaled by s where the kernel reads it (no further launch)."""
     lib = _lib.load()
     what = "dense_conv_backward_weight"
-    cout, k = int(dw.shape[0]), int(dw.shape[2])
-    sa = _Slice(what + ": a", a, a_off, a.shape[1] - a_off if ca is None else ca)
-    sb = None
-    if b is not None and (cb is None or cb > 0):
-        sb = _Slice(what + ": b", b, b_off, b.shape[1] - b_off if cb is None else cb, sa)
+    cout = int(dw.shape[0])
+    sa, sb = _dense_inputs(what, a, a_off, ca, b, b_off, cb)
     sdy = _Slice(what + ": dy", dy, dy_off, cout, sa)
-    d = _dense_desc(sa, sb, cout, k, act, slope, terms)
-    _dense_weight(what, dw, d)
-    d.ldDy = sdy.ld
-    sy = None
-    if y_saved is not None:
-        sy = _Slice(what + ": y_saved", y_saved, y_off, cout, sa)
-        d.ldY = sy.ld
+    d = _dense_desc(what, sa, dw, sa.channels, sb.channels, act, slope, terms)
+    sy = _Slice(what + ": y_saved", y_saved, y_off, cout, sa) if y_saved is not None else _NO_SLICE
+    d.ldA, d.ldB, d.ldDy, d.ldY = sa.ld, sb.ld, sdy.ld, sy.ld
     if lib.srk_dense_conv_plan(ctypes.byref(d), ctypes.byref(_lib.DensePlan())) == _lib.ERR_UNSUPPORTED:
         raise ValueError("%s: %s" % (what, lib.srk_last_error_string().decode()))
     nbytes = int(lib.srk_dense_conv_workspace_bytes(ctypes.byref(d)))
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=a.device)   # torch's allocator: a captured graph owns it
-    if s is not None:
-        e = _lib.DenseEpilogue(s)
-        _dense_check(lib.srk_dense_conv_backward_weight_ex(ctypes.byref(d), sa.p, sb.p if sb else None, sdy.p,
-                                                           sy.p if sy else None, ptr(dw), ptr(dbias), float(beta),
-                                                           ctypes.byref(e), ptr(ws), nbytes, stream_ptr()),
-                     "srk_dense_conv_backward_weight_ex")
-        return dw, dbias
-    _dense_check(lib.srk_dense_conv_backward_weight(ctypes.byref(d), sa.p, sb.p if sb else None, sdy.p,
-                                                    sy.p if sy else None, ptr(dw), ptr(dbias), float(beta), ptr(ws), nbytes,
-                                                    stream_ptr()), "srk_dense_conv_backward_weight")
+    _dense_launch("backward_weight", [ctypes.byref(d), sa.p, sb.p, sdy.p, sy.p, ptr(dw), ptr(dbias), float(beta), ptr(ws),
+                                      nbytes, stream_ptr()], None if s is None else _lib.DenseEpilogue(s), 8)
     return dw, dbias
 
 
 def _growth_buffer(n, c, h, w, like):
     """A block's growth buffer (its own name, so that a test can count them: one per call without a backward)."""
     return _empty_cl(n, c, h, w, like)
+
+
+# One block core, two buffer policies: both trunks below (RDN here, ESRGAN in DESIGN.md 30) call it, and keep only where
+# a block's input, output and gradients live and which skips its fusion convolution carries.
+def _dense_block_forward(*, a, a_off, ca, layers, growth, out, out_off, act, slope, terms, s=None, r1=1.0, residual2=None,
+                         r2=1.0):
+    """layers = (w_1, b_1, .., w_C, b_C, w_fusion, b_fusion).  Growth convolution c reads the input a[:, a_off : a_off + ca]
+    and growth[:, : (c - 1) G], and writes act(.) into growth[:, (c - 1) G : c G]; the fusion convolution reads
+    [input | growth] and writes out[:, out_off : out_off + Cout] with the skip in its epilogue: conv + input, or with `s`
+    (the _ex kernel) s * conv + r1 * input + r2 * residual2.  C + 1 launches."""
+    C = len(layers) // 2 - 1
+    g = int(layers[0].shape[0])
+    for c in range(C):
+        dense_conv(a, layers[2 * c], layers[2 * c + 1], b=growth if c else None, out=growth, ca=ca, a_off=a_off, cb=c * g,
+                   out_off=c * g, act=act, slope=slope, terms=terms)
+    dense_conv(a, layers[2 * C], layers[2 * C + 1], b=growth, out=out, ca=ca, a_off=a_off, cb=C * g, out_off=out_off,
+               act=ACT_NONE, slope=0.0, residual=a, res_off=a_off, terms=terms, s=s, r1=r1, residual2=residual2, r2=r2)
+
+
+def _dense_wgrad(layers, need, grads, i, a, dy, **conv):
+    """dense_conv_backward_weight(a, dy, .., **conv) for layers[i], layers[i + 1] unless neither needs a gradient: added
+    (beta 1) to their flat gradient buffer (optim.FlatParams), else written (beta 0) to a new dw, dbias kept in `grads`."""
+    if not (need[i] or need[i + 1]):
+        return
+    acc = _flat_grads(layers[i], layers[i + 1])
+    if acc is not None:
+        dw, dbias, beta = acc[0], acc[1], 1.0
+    else:
+        dw = torch.empty_like(layers[i], memory_format=torch.contiguous_format)
+        dbias, beta = torch.empty_like(layers[i + 1]), 0.0
+        grads[i], grads[i + 1] = dw, dbias
+    dense_conv_backward_weight(a, dy, dw, dbias=dbias, beta=beta, **conv)
+
+
+def _dense_block_backward(*, a, a_off, ca, layers, need, growth, gg, dy, dy_off, da, da_off, beta_a, act, slope, terms,
+                          s=None, a1=1.0, extra=None):
+    """The backward of _dense_block_forward for the output gradient dy[:, dy_off : dy_off + Cout]; gg: room for the growth
+    gradient.  The fusion convolution's data gradient starts gg (beta 0) and leaves beta_a * da + its share + the skip's
+    gradient (dy itself; a1 * dy with `s`) in da[:, da_off : da_off + ca] in one epilogue; the growth convolutions C .. 1
+    add theirs (beta 1), `extra`, one more gradient of the input, riding in the epilogue of the C-th.  da = None: nobody
+    needs the input's gradient, one launch fewer.  Returns the parameter gradients autograd is to have (see _dense_wgrad)."""
+    C = len(layers) // 2 - 1
+    g = int(layers[0].shape[0])
+    grads = [None] * len(layers)
+    conv = dict(ca=ca, cb=C * g, dy_off=dy_off, terms=terms, s=s)
+    _dense_wgrad(layers, need, grads, 2 * C, a, dy, b=growth, a_off=a_off, **conv)
+    dense_conv_backward_data(dy, layers[2 * C], da=da, db=gg, add=dy if da is not None else None, da_off=da_off,
+                             add_off=dy_off, beta_a=beta_a, beta_b=0.0, a1=a1, **conv)
+    for c in reversed(range(C)):
+        conv = dict(ca=ca, cb=c * g, y_saved=growth, dy_off=c * g, y_off=c * g, act=act, slope=slope, terms=terms)
+        _dense_wgrad(layers, need, grads, 2 * c, a, gg, b=growth if c else None, a_off=a_off, **conv)
+        if da is not None or c:
+            dense_conv_backward_data(gg, layers[2 * c], da=da, db=gg if c else None, da_off=da_off, beta_a=1.0, beta_b=1.0,
+                                     add=extra if (c == C - 1 and da is not None) else None, **conv)
+    return grads
 
 
 class _ResidualDenseBlocks(torch.autograd.Function):
@@ -3031,16 +3056,13 @@ class _ResidualDenseBlocks(torch.autograd.Function):
         fusion = _empty_cl(n, D * g0, hh, ww, x)
         growths, growth = [], None
         for blk in range(D):
-            p = params[blk * per:(blk + 1) * per]
             if need_grad or growth is None:     # a backward reads every block's growth buffer: they are its ReLU masks
                 growth = _growth_buffer(n, C * g, hh, ww, x)
             growths.append(growth)
             a, a_off = (x, 0) if blk == 0 else (fusion, (blk - 1) * g0)
-            for c in range(C):
-                dense_conv(a, p[2 * c], p[2 * c + 1], growth if c else None, growth, g0, a_off, c * g, 0, c * g, ACT_RELU,
-                           0.0, None, 0, terms)
-            dense_conv(a, p[2 * C], p[2 * C + 1], growth, fusion, g0, a_off, C * g, 0, blk * g0, ACT_NONE, 0.0, a, a_off,
-                       terms)
+            # the 1x1 local fusion adds the block's input and writes slice blk of the fusion buffer, the next block's input
+            _dense_block_forward(a=a, a_off=a_off, ca=g0, layers=params[blk * per:(blk + 1) * per], growth=growth, out=fusion,
+                                 out_off=blk * g0, act=ACT_RELU, slope=0.0, terms=terms)
         ctx.dims = (D, C, g0, g)
         ctx.params = params
         if need_grad:
@@ -3061,38 +3083,16 @@ class _ResidualDenseBlocks(torch.autograd.Function):
             gf = gout.clone(memory_format=torch.preserve_format)
         gg = _empty_cl(n, C * g, hh, ww, x)
         dx = _empty_cl(n, g0, hh, ww, x) if ctx.needs_input_grad[0] else None
-        grads = [None] * len(params)
-
-        def wgrad(i, a, a_off, b, cb, dy, dy_off, ys, y_off, act):
-            w, bias = params[i], params[i + 1]
-            if not (ctx.needs_input_grad[4 + i] or ctx.needs_input_grad[5 + i]):
-                return
-            acc = _flat_grads(w, bias)
-            if acc is not None:    # optim.FlatParams: accumulated in the flat gradient buffer
-                dw, dbias, beta = acc[0], acc[1], 1.0
-            else:
-                dw = torch.empty_like(w, memory_format=torch.contiguous_format)
-                dbias, beta = torch.empty_like(bias), 0.0
-                grads[i], grads[i + 1] = dw, dbias
-            dense_conv_backward_weight(a, dy, dw, dbias, b if cb else None, ys, g0, a_off, cb, 0, dy_off, y_off, beta, act,
-                                       0.0, terms)
-
+        need, grads = ctx.needs_input_grad[4:], []
         for blk in reversed(range(D)):
             i0 = blk * per
-            growth = growths[blk]
             a, a_off = (x, 0) if blk == 0 else (fusion, (blk - 1) * g0)
+            # block blk's output gradient is slice blk of gf; its input's gradient is accumulated (beta 1) into slice
+            # blk - 1, where the blocks behind have already left theirs, and block 0 writes the dense dx (beta 0)
             da, da_off = (dx, 0) if blk == 0 else (gf, (blk - 1) * g0)
-            # the local fusion: its data gradient starts the growth gradient (beta 0) and adds the skip's gradient, the
-            # block's output gradient itself, into the input's slice in the same epilogue
-            wgrad(i0 + 2 * C, a, a_off, growth, C * g, gf, blk * g0, None, 0, ACT_NONE)
-            dense_conv_backward_data(gf, params[i0 + 2 * C], g0, C * g, None, da, gg, gf if da is not None else None,
-                                     blk * g0, 0, da_off, 0, blk * g0, 0.0 if blk == 0 else 1.0, 0.0, ACT_NONE, 0.0, terms)
-            for c in reversed(range(C)):
-                wgrad(i0 + 2 * c, a, a_off, growth, c * g, gg, c * g, growth, c * g, ACT_RELU)
-                if da is None and c == 0:
-                    continue
-                dense_conv_backward_data(gg, params[i0 + 2 * c], g0, c * g, growth, da, gg if c else None, None, c * g,
-                                         c * g, da_off, 0, 0, 1.0, 1.0, ACT_RELU, 0.0, terms)
+            grads = _dense_block_backward(a=a, a_off=a_off, ca=g0, layers=params[i0:i0 + per], need=need[i0:i0 + per],
+                                          growth=growths[blk], gg=gg, dy=gf, dy_off=blk * g0, da=da, da_off=da_off,
+                                          beta_a=0.0 if blk == 0 else 1.0, act=ACT_RELU, slope=0.0, terms=terms) + grads
         return (dx, None, None, None) + tuple(grads)
 
 
@@ -3128,6 +3128,7 @@ def residual_dense_blocks(x, blocks):
 
 # ------------------------------------------------------------------------------------------------
 # The residual-in-residual dense trunk of ESRGAN (csrc/dense.hip: the _ex entry points)
+# The second buffer policy on the block core above: ping-pong trunk maps, scaled skips in the fusion epilogue.
 # ------------------------------------------------------------------------------------------------
 _RRDB_SLOPE = 0.2
 
@@ -3160,15 +3161,13 @@ class _RRDBTrunk(torch.autograd.Function):
                 p = params[30 * i + 10 * k:30 * i + 10 * k + 10]
                 if need_grad or growth is None:     # a backward reads every growth buffer: the LeakyReLU masks, the wgrad inputs
                     growth = _growth_buffer(n, 4 * g, hh, ww, x)
-                for c in range(4):
-                    dense_conv(u, p[2 * c], p[2 * c + 1], growth if c else None, growth, f, 0, c * g, 0, c * g, ACT_LRELU,
-                               _RRDB_SLOPE, None, 0, terms)
                 v = _trunk_buffer(n, f, hh, ww, x) if need_grad else take()
                 if k < 2:      # v = rs conv5 + u
-                    dense_conv(u, p[8], p[9], growth, v, f, 0, 4 * g, 0, 0, ACT_NONE, 0.0, u, 0, terms, s=rs, r1=1.0)
+                    skips = dict(s=rs, r1=1.0)
                 else:          # out = rs (rs conv5 + u3) + u1: the outer skip rides in the same epilogue
-                    dense_conv(u, p[8], p[9], growth, v, f, 0, 4 * g, 0, 0, ACT_NONE, 0.0, u, 0, terms, s=rs * rs, r1=rs,
-                               residual2=u1, res2_off=0, r2=1.0)
+                    skips = dict(s=rs * rs, r1=rs, residual2=u1, r2=1.0)
+                _dense_block_forward(a=u, a_off=0, ca=f, layers=p, growth=growth, out=v, out_off=0, act=ACT_LRELU,
+                                     slope=_RRDB_SLOPE, terms=terms, **skips)
                 if need_grad:
                     ins.append(u)
                     growths.append(growth)
@@ -3195,45 +3194,23 @@ class _RRDBTrunk(torch.autograd.Function):
         like = ins[0]
         gnext = _dense(gout)               # read only: every accumulator below is this op's own
         gg = _empty_cl(n, 4 * g, hh, ww, like)
-        grads = [None] * len(params)
+        need, grads = ctx.needs_input_grad[4:], [None] * len(params)
 
-        def wgrad(i, a, b, cb, dy, dy_off, ys, y_off, act, s):
-            w, bias = params[i], params[i + 1]
-            if not (ctx.needs_input_grad[4 + i] or ctx.needs_input_grad[5 + i]):
-                return
-            acc = _flat_grads(w, bias)
-            if acc is not None:    # optim.FlatParams: accumulated in the flat gradient buffer
-                dw, dbias, beta = acc[0], acc[1], 1.0
-            else:
-                dw = torch.empty_like(w, memory_format=torch.contiguous_format)
-                dbias, beta = torch.empty_like(bias), 0.0
-                grads[i], grads[i + 1] = dw, dbias
-            dense_conv_backward_weight(a, dy, dw, dbias, b if cb else None, ys, f, 0, cb, 0, dy_off, y_off, beta, act,
-                                       _RRDB_SLOPE if act == ACT_LRELU else 0.0, terms, s=s)
-
-        def rdb(j, dy, s, da, a1, extra):
-            """The backward of RDB j (its output = s conv5 + a1 u + ...): da = the whole gradient of its input u -- conv5's
-            data gradient starts it (beta 0) with a1 * dy, the RDB skip, in the epilogue; the four growth convolutions add
-            theirs; `extra` (the RRDB's outer skip) rides in the epilogue of the fourth."""
-            i0, u, growth = 10 * j, ins[j], growths[j]
-            wgrad(i0 + 8, u, growth, 4 * g, dy, 0, None, 0, ACT_NONE, s)
-            dense_conv_backward_data(dy, params[i0 + 8], f, 4 * g, None, da, gg, dy if da is not None else None, 0, 0, 0, 0, 0,
-                                     0.0, 0.0, ACT_NONE, 0.0, terms, s=s, a1=a1)
-            for c in reversed(range(4)):
-                wgrad(i0 + 2 * c, u, growth, c * g, gg, c * g, growth, c * g, ACT_LRELU, None)
-                if da is None and c == 0:
-                    continue
-                dense_conv_backward_data(gg, params[i0 + 2 * c], f, c * g, growth, da, gg if c else None,
-                                         extra if (c == 3 and da is not None) else None, c * g, c * g, 0, 0, 0, 1.0, 1.0,
-                                         ACT_LRELU, _RRDB_SLOPE, terms)
+        def rdb(j, dy, da, s, a1, extra=None):
+            """The backward of RDB j (its output = s conv5 + a1 u + ...): da = the whole gradient of its input u, written
+            (beta 0); `extra`: the RRDB's outer skip."""
+            grads[10 * j:10 * j + 10] = _dense_block_backward(
+                a=ins[j], a_off=0, ca=f, layers=params[10 * j:10 * j + 10], need=need[10 * j:10 * j + 10], growth=growths[j],
+                gg=gg, dy=dy, dy_off=0, da=da, da_off=0, beta_a=0.0, act=ACT_LRELU, slope=_RRDB_SLOPE, terms=terms, s=s,
+                a1=a1, extra=extra)
 
         for i in reversed(range(nb)):
             gu3 = _empty_cl(n, f, hh, ww, like)
-            rdb(3 * i + 2, gnext, rs * rs, gu3, rs, None)       # out = rs^2 conv5 + rs u3 + u1
+            rdb(3 * i + 2, gnext, gu3, s=rs * rs, a1=rs)            # out = rs^2 conv5 + rs u3 + u1
             gu2 = _empty_cl(n, f, hh, ww, like)
-            rdb(3 * i + 1, gu3, rs, gu2, 1.0, None)             # u3 = rs conv5 + u2
+            rdb(3 * i + 1, gu3, gu2, s=rs, a1=1.0)                  # u3 = rs conv5 + u2
             gu1 = _empty_cl(n, f, hh, ww, like) if (i > 0 or ctx.needs_input_grad[0]) else None
-            rdb(3 * i, gu2, rs, gu1, 1.0, gnext)                # u2 = rs conv5 + u1, and u1's own way to the output
+            rdb(3 * i, gu2, gu1, s=rs, a1=1.0, extra=gnext)         # u2 = rs conv5 + u1, and u1's own way to the output
             gnext = gu1
         return (gnext, None, None, None) + tuple(grads)
 
