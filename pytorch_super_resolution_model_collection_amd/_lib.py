@@ -19,8 +19,6 @@ ACT_NONE, ACT_RELU, ACT_PRELU, ACT_LRELU, ACT_TANH, ACT_SIGMOID = range(6)
 ALGO_AUTO, ALGO_GENERIC, ALGO_MFMA, ALGO_DIRECT, ALGO_MFMA_BF16X3, ALGO_MFMA_BF16X6, ALGO_MFMA_F16X3 = range(7)
 AMAX_FLOATS = 256   # SRK_AMAX_FLOATS: 16 slots, one per 64-byte line
 LOSS_MSE, LOSS_L1, LOSS_CHARBONNIER, LOSS_BCE = range(4)
-LOSS_SSIM = 4   # no srk_loss kind: ops._Loss routes it to srk_ssim_loss_forward_backward
-LOSS_FFT = 5    # no srk_loss kind either: ops._Loss routes it to srk_fft_loss_forward_backward
 FFT_LOSS_MAX_DIM = 256   # SRK_FFT_LOSS_MAX_DIM
 SSIM_DOMAINS = {"float": 0, "u8": 1, "y8": 2}   # SRK_SSIM_FLOAT / _U8 / _Y8
 ACT_BY_NAME = {None: ACT_NONE, "relu": ACT_RELU, "prelu": ACT_PRELU, "lrelu": ACT_LRELU, "tanh": ACT_TANH,

@@ -1075,17 +1075,23 @@ def fork(x):
 # Seeds of a backward pass.  `loss.backward()` makes autograd fill a ones tensor (one ATen launch) and the loss backward
 # multiply its stored gradient by it (srk_scale_dev, a second launch); a data-parallel step seeds with 1/world instead.
 # The train steps of this package know their seed when they compute the loss:
-#   * backward(loss) seeds with a persistent per-device ones tensor, which _Loss.backward recognises (by address) and
+#   * backward(loss) seeds with a persistent per-device ones tensor, which the loss backward recognises (by address) and
 #     answers with the gradient the forward already wrote -- no fill, no scale;
 #   * inside `with loss_seed(value, tensor):` the loss forward folds `value` into that gradient, and a backward seeded with
 #     `tensor` (dp.loss_seed) skips the multiply as well.
 # Any other upstream gradient (a weighted sum of losses, user code) takes the general path.
+# This is the seed contract of every scalar loss here (the pixel, SSIM and FFT losses, drcn_head, lpips, ragan_loss,
+# gan_logit_loss), and three functions hold it: _declare_seed in the forward, _is_own_seed and _seed_scaled in the backward.
 _UNIT = {}
 _LOSS_SEED = [None]
 
 
+def _device_index(device):
+    return device.index if device.index is not None else torch.cuda.current_device()
+
+
 def unit_seed(device):
-    idx = device.index if device.index is not None else torch.cuda.current_device()
+    idx = _device_index(device)
     t = _UNIT.get(idx)
     if t is None:
         t = _UNIT[idx] = torch.ones((), dtype=torch.float32, device=torch.device("cuda", idx))
@@ -1114,79 +1120,123 @@ class loss_seed(object):
         _LOSS_SEED[0] = self.prev
 
 
-class _Loss(torch.autograd.Function):
+def _declare_seed(ctx, declare=True):
+    """Forward of a loss node: records the seed declared by loss_seed (none where `declare` is false) on the ctx and
+    returns the value the kernel folds into the gradient it stores, 1.0 when none is declared."""
+    seed = _LOSS_SEED[0] if declare else None
+    ctx.seed_ptr, ctx.seed_value = (seed[1].data_ptr(), seed[0]) if seed is not None else (0, 1.0)
+    # the declared seed is recognised by its address, so the node keeps the tensor alive: freed, its block could
+    # be handed to another upstream gradient, which would then pass for the declared one
+    ctx.seed_keep = seed[1] if seed is not None else None
+    return ctx.seed_value
+
+
+def _is_own_seed(ctx, g, device):
+    """Backward of a loss node: whether the upstream gradient g is the seed the stored gradient was computed for -- the
+    declared seed or, with none declared, the unit seed of the device (under a declared seed the unit seed is as foreign
+    as any other gradient).  A foreign g is a factor on the stored gradient, after g / ctx.seed_value has undone a
+    folded seed: _seed_scaled applies it in fp32, _LpipsFinish to its fp64 row."""
+    return g.data_ptr() == (ctx.seed_ptr if ctx.seed_ptr else unit_seed(device).data_ptr())
+
+
+def _seed_scaled(ctx, g, grads):
+    """The stored fp32 gradients `grads` (a tuple, None where an operand takes none) as the backward hands them out: as
+    they are under the node's own seed, else each times the foreign g (srk_scale_dev into a fresh tensor, one launch per
+    gradient).  They stay on the ctx, not in save_for_backward: a second backward over a retained graph sees them, and
+    they are freed with the graph."""
+    live = [d for d in grads if d is not None]
+    if not live or _is_own_seed(ctx, g, live[0].device):
+        return grads
+    lib = _lib.load()
+    g = (g / ctx.seed_value if ctx.seed_ptr else g).contiguous()
+    outs = tuple(None if d is None else torch.empty_like(d) for d in grads)
+    for d, out in zip(grads, outs):
+        if d is not None:
+            check(lib.srk_scale_dev(ptr(d), ptr(g), ptr(out), d.numel(), stream_ptr()), "srk_scale_dev")
+    return outs
+
+
+def _loss_inputs(ctx, pred, target, ws_bytes):
+    """What the pixel, SSIM and FFT losses do before their launch: pred dense as [N,C,H,W] (or [B, F] as N = B, C = F,
+    H = W = 1: BCE on the discriminator output), the target's strides, and the loss, gradient (None where pred takes
+    none) and workspace (ws_bytes(n, c, h, w) bytes) to write."""
+    require_cuda(pred, target)
+    if pred.shape != target.shape:
+        raise RuntimeError("loss: pred %s vs target %s" % (tuple(pred.shape), tuple(target.shape)))
+    if pred.dim() == 4:
+        pred = _dense(pred)
+        n, c, h, w = pred.shape
+        ts = target.stride()
+    else:
+        pred = pred.contiguous()
+        n, c = pred.shape[0], pred.numel() // pred.shape[0]
+        h = w = 1
+        target = target.contiguous()
+        ts = (c, 1, 1, 1)
+    strides = (ctypes.c_int64 * 4)(*[int(s) for s in ts])
+    loss = torch.empty((), dtype=torch.float32, device=pred.device)
+    dpred = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
+    ws = torch.empty(int(ws_bytes(n, c, h, w)), dtype=torch.uint8, device=pred.device)
+    return pred, target, strides, (n, c, h, w), loss, dpred, ws
+
+
+class _PixelLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, target, kind, eps):
         lib = _lib.load()
-        require_cuda(pred, target)
-        if pred.shape != target.shape:
-            raise RuntimeError("loss: pred %s vs target %s" % (tuple(pred.shape), tuple(target.shape)))
-        if kind == _lib.LOSS_SSIM and (pred.dim() != 4 or min(pred.shape[2:]) < 11):
-            raise RuntimeError("ssim_loss: takes [N,C,H,W] with planes of at least the 11 x 11 window, got shape %s"
-                               % (tuple(pred.shape),))
-        if kind == _lib.LOSS_FFT:
-            if pred.dim() != 4 or min(pred.shape) < 1:
-                raise RuntimeError("fft_loss: takes non-empty [N,C,H,W], got shape %s" % (tuple(pred.shape),))
-            if max(pred.shape[2:]) > _lib.FFT_LOSS_MAX_DIM:
-                raise RuntimeError("fft_loss: planes of %d x %d, the dense DFT takes at most %d on a side"
-                                   % (pred.shape[2], pred.shape[3], _lib.FFT_LOSS_MAX_DIM))
-        if pred.dim() == 4:
-            pred = _dense(pred)
-            n, c, h, w = pred.shape
-            ts = target.stride()
-        else:  # [B, F] (BCE on the discriminator output): treat as N=B, C=F, H=W=1
-            pred = pred.contiguous()
-            n, c = pred.shape[0], pred.numel() // pred.shape[0]
-            h = w = 1
-            target = target.contiguous()
-            ts = (c, 1, 1, 1)
-        strides = (ctypes.c_int64 * 4)(*[int(s) for s in ts])
-        loss = torch.empty((), dtype=torch.float32, device=pred.device)
-        need_grad = ctx.needs_input_grad[0]
-        dpred = torch.empty_like(pred) if need_grad else None
-        if kind == _lib.LOSS_FFT:
-            ws_bytes = lib.srk_fft_loss_workspace_bytes(n, c, h, w)
-            tables = _dft_tables(h, w, pred.device)
-        else:
-            ws_bytes = lib.srk_ssim_loss_workspace_bytes() if kind == _lib.LOSS_SSIM else lib.srk_loss_workspace_bytes()
-        ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=pred.device)
-        seed = _LOSS_SEED[0]
-        ctx.seed_ptr, ctx.seed_value = (seed[1].data_ptr(), seed[0]) if seed is not None else (0, 1.0)
-        # the declared seed is recognised by its address, so the node keeps the tensor alive: freed, its block could
-        # be handed to another upstream gradient, which would then pass for the declared one
-        ctx.seed_keep = seed[1] if seed is not None else None
-        if kind == _lib.LOSS_SSIM:
-            check(lib.srk_ssim_loss_forward_backward(ptr(pred), ptr(target), strides, n, c, h, w, ctx.seed_value, ptr(loss),
-                                                     ptr(dpred), ptr(ws), stream_ptr()), "srk_ssim_loss_forward_backward")
-        elif kind == _lib.LOSS_FFT:   # eps carries the norm: 1 = "ortho", 0 = "backward"
-            scale = 1.0 / math.sqrt(float(h) * float(w)) if eps else 1.0
-            check(lib.srk_fft_loss_forward_backward(ptr(pred), ptr(target), strides, n, c, h, w, ptr(tables), scale,
-                                                    ctx.seed_value, ptr(loss), ptr(dpred), ptr(ws), stream_ptr()),
-                  "srk_fft_loss_forward_backward")
-        else:
-            check(lib.srk_loss_forward_backward(kind, ptr(pred), ptr(target), strides, n, c, h, w, eps, ctx.seed_value,
-                                                ptr(loss), ptr(dpred), ptr(ws), stream_ptr()), "srk_loss_forward_backward")
-        ctx.dpred = dpred
+        ws_bytes = lambda *dims: lib.srk_loss_workspace_bytes()
+        pred, target, strides, dims, loss, dpred, ws = _loss_inputs(ctx, pred, target, ws_bytes)
+        check(lib.srk_loss_forward_backward(kind, ptr(pred), ptr(target), strides, *dims, eps, _declare_seed(ctx),
+                                            ptr(loss), ptr(dpred), ptr(ws), stream_ptr()), "srk_loss_forward_backward")
+        ctx.grads = (dpred,)
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        dpred = ctx.dpred  # (kept on the ctx: a second backward over a retained graph must see it; freed with the graph)
-        if dpred is None:
-            return None, None, None, None
-        gp = g.data_ptr()
-        if ctx.seed_ptr:
-            if gp == ctx.seed_ptr:      # the seed this loss was computed for: already folded into dpred
-                return dpred, None, None, None
-            # some other upstream gradient: undo the folded seed (dpred = seed * dL/dpred)
-            g = g / ctx.seed_value
-        elif gp == unit_seed(dpred.device).data_ptr():
-            return dpred, None, None, None
+        return _seed_scaled(ctx, g, ctx.grads) + (None, None, None)
+
+
+class _SSIMLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target):
         lib = _lib.load()
-        out = torch.empty_like(dpred)
-        check(lib.srk_scale_dev(ptr(dpred), ptr(g.contiguous()), ptr(out), dpred.numel(), stream_ptr()),
-              "srk_scale_dev")
-        return out, None, None, None
+        if pred.dim() != 4 or min(pred.shape[2:]) < 11:
+            raise RuntimeError("ssim_loss: takes [N,C,H,W] with planes of at least the 11 x 11 window, got shape %s"
+                               % (tuple(pred.shape),))
+        ws_bytes = lambda *dims: lib.srk_ssim_loss_workspace_bytes()
+        pred, target, strides, dims, loss, dpred, ws = _loss_inputs(ctx, pred, target, ws_bytes)
+        check(lib.srk_ssim_loss_forward_backward(ptr(pred), ptr(target), strides, *dims, _declare_seed(ctx), ptr(loss),
+                                                 ptr(dpred), ptr(ws), stream_ptr()), "srk_ssim_loss_forward_backward")
+        ctx.grads = (dpred,)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        return _seed_scaled(ctx, g, ctx.grads) + (None,)
+
+
+class _FFTLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, ortho):
+        lib = _lib.load()
+        if pred.dim() != 4 or min(pred.shape) < 1:
+            raise RuntimeError("fft_loss: takes non-empty [N,C,H,W], got shape %s" % (tuple(pred.shape),))
+        if max(pred.shape[2:]) > _lib.FFT_LOSS_MAX_DIM:
+            raise RuntimeError("fft_loss: planes of %d x %d, the dense DFT takes at most %d on a side"
+                               % (pred.shape[2], pred.shape[3], _lib.FFT_LOSS_MAX_DIM))
+        pred, target, strides, dims, loss, dpred, ws = _loss_inputs(ctx, pred, target, lib.srk_fft_loss_workspace_bytes)
+        h, w = dims[2:]
+        scale = 1.0 / math.sqrt(float(h) * float(w)) if ortho else 1.0
+        tables = _dft_tables(h, w, pred.device)
+        check(lib.srk_fft_loss_forward_backward(ptr(pred), ptr(target), strides, *dims, ptr(tables), scale,
+                                                _declare_seed(ctx), ptr(loss), ptr(dpred), ptr(ws), stream_ptr()),
+              "srk_fft_loss_forward_backward")
+        ctx.grads = (dpred,)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        return _seed_scaled(ctx, g, ctx.grads) + (None, None)
 
 
 _CONSTS = {}
@@ -1194,7 +1244,7 @@ _CONSTS = {}
 
 def _const_scalar(value, device):
     """A persistent 0-dim device tensor holding `value` (loss weights, label rows): no fill launch per step."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
+    idx = _device_index(device)
     key = (float(value), idx)
     t = _CONSTS.get(key)
     if t is None:
@@ -1204,7 +1254,7 @@ def _const_scalar(value, device):
 
 def const_rows(value, rows, device):
     """Persistent [rows, 1] label tensor (torch.ones(B, 1) / zeros(B, 1) of srgan.py:264-265 without a fill per step)."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
+    idx = _device_index(device)
     key = (float(value), int(rows), idx)
     t = _CONSTS.get(key)
     if t is None:
@@ -1248,30 +1298,30 @@ def weighted_term(loss_fn, weight, pred, target):
 
 def mse_loss(pred, target):
     """nn.MSELoss() (srcnn.py:84-86,129; vdsr.py:145; srgan.py:205,300)."""
-    return _Loss.apply(pred, target, _lib.LOSS_MSE, 0.0)
+    return _PixelLoss.apply(pred, target, _lib.LOSS_MSE, 0.0)
 
 
 def l1_loss(pred, target):
     """nn.L1Loss() (edsr.py:98-100,153)."""
-    return _Loss.apply(pred, target, _lib.LOSS_L1, 0.0)
+    return _PixelLoss.apply(pred, target, _lib.LOSS_L1, 0.0)
 
 
 def charbonnier_loss(pred, target, eps=1e-6):
     """L1_Charbonnier_loss (lapsrn.py:75-85)."""
-    return _Loss.apply(pred, target, _lib.LOSS_CHARBONNIER, float(eps))
+    return _PixelLoss.apply(pred, target, _lib.LOSS_CHARBONNIER, float(eps))
 
 
 def bce_loss(pred, target):
     """nn.BCELoss() (srgan.py:157,276-297)."""
-    return _Loss.apply(pred, target, _lib.LOSS_BCE, 0.0)
+    return _PixelLoss.apply(pred, target, _lib.LOSS_BCE, 0.0)
 
 
 def ssim_loss(pred, target):
     """1 - mean SSIM of pred against target (11 x 11 Gaussian window, valid positions, L = 1, every plane and position
     weighing the same; pred is read UNCLAMPED so that out-of-range pixels keep their gradient): the loss and its
-    gradient from one launch, with the contract of the pixel losses (loss_seed, unit seed, loss_sum).
+    gradient from one launch, under the seed contract of the losses (_declare_seed).
     [N,C,H,W] with H, W >= 11.  include/srk.h: srk_ssim_loss_forward_backward."""
-    return _Loss.apply(pred, target, _lib.LOSS_SSIM, 0.0)
+    return _SSIMLoss.apply(pred, target)
 
 
 _DFT_TABLES = {}
@@ -1282,7 +1332,7 @@ def _dft_tables(h, w, device):
     """The twiddle tables of srk_dft_table_host for H then W as one fp64 device tensor, uploaded once per (H, W, device):
     the device computes no cos / sin of its own.  The first use of a size must come before a graph capture (a warm-up
     step does it): the upload is a host-to-device copy."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
+    idx = _device_index(device)
     key = (int(h), int(w), idx)
     t = _DFT_TABLES.get(key)
     if t is None:
@@ -1303,11 +1353,11 @@ def fft_loss(pred, target, norm="backward"):
     """The frequency-domain loss of BasicSR's FFTLoss, nn.L1Loss()(view_as_real(fft2(pred)), view_as_real(fft2(target)))
     with fft2's `norm` ("backward": unscaled, "ortho": 1 / sqrt(H W)), over the full spectrum of every plane: a dense
     fp64 DFT on tables from the host, so the bits do not depend on a library's plan and Im F is an exact zero at the
-    self-conjugate bins.  Loss and gradient from one call, with the contract of the pixel losses (loss_seed, unit seed,
-    loss_sum).  [N,C,H,W] with H, W <= 256.  include/srk.h: srk_fft_loss_forward_backward."""
+    self-conjugate bins.  Loss and gradient from one call, under the seed contract of the losses
+    (_declare_seed).  [N,C,H,W] with H, W <= 256.  include/srk.h: srk_fft_loss_forward_backward."""
     if norm not in FFT_NORMS:
         raise ValueError("fft_loss: norm %r is not one of %s" % (norm, FFT_NORMS))
-    return _Loss.apply(pred, target, _lib.LOSS_FFT, 1.0 if norm == "ortho" else 0.0)
+    return _FFTLoss.apply(pred, target, norm == "ortho")
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1676,9 +1726,9 @@ def max_pool2x2_train(x):
 def perceptual_loss(pred, target, extractor, normalize=True, criterion='mse'):
     """The VGG feature loss of SRGAN (srgan.py:301-305) as a term that trains: MSE(extractor.extract(norm(pred)),
     extractor.extract(norm(target))), norm = utils.norm(vgg=True) when `normalize`; a 0-dim fp32 device tensor with the
-    contract of the other losses (it IS ops.mse_loss on the two feature maps: loss_seed, unit seed, weighted_term,
-    loss_sum).  The gradient flows to pred only.  Both operands run the same kernels -- the training forward of the
-    head, the target's without a graph -- so equal inputs give a loss of exactly 0 and a zero gradient.
+    seed contract of the losses, _declare_seed (it IS ops.mse_loss on the two feature maps).  The gradient flows to pred
+    only.  Both operands run the same kernels -- the training forward of the head, the target's without a graph -- so
+    equal inputs give a loss of exactly 0 and a zero gradient.
     pred / target: [N, 3, H, W]; extractor: models.FeatureExtractor.  criterion: 'mse' (SRGAN) or 'l1' (ESRGAN: ops.l1_loss
     on the two feature maps, the same contract)."""
     from . import utils
@@ -2462,8 +2512,8 @@ def recursive_conv(h0, weight, bias, D, cfg=None, packed=None):
 
 
 class _DRCNHead(torch.autograd.Function):
-    """(loss, out, terms) of srk_drcn_head_loss; the gradients to Y and w come from the forward pass (seeded like
-    _Loss).  out and terms carry no gradient."""
+    """(loss, out, terms) of srk_drcn_head_loss; the gradients to Y and w come from the forward pass (the seed contract
+    of the losses, _declare_seed).  out and terms carry no gradient."""
 
     @staticmethod
     def forward(ctx, Y, x, w, target, alpha, reg, D, need_grad):
@@ -2475,45 +2525,26 @@ class _DRCNHead(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=Y.device)
         terms = torch.empty(2, dtype=torch.float32, device=Y.device)
         ws = torch.empty(max(int(lib.srk_drcn_workspace_bytes(D)), 16), dtype=torch.uint8, device=Y.device)
-        seed = _LOSS_SEED[0]
-        ctx.seed_ptr, ctx.seed_value = (seed[1].data_ptr(), seed[0]) if seed is not None else (0, 1.0)
-        # the declared seed is recognised by its address, so the node keeps the tensor alive: freed, its block could
-        # be handed to another upstream gradient, which would then pass for the declared one
-        ctx.seed_keep = seed[1] if seed is not None else None
         wacc = getattr(w, "_srk_grad", None) if need_grad else None
         dw = None
         if need_grad:
             dw = wacc if wacc is not None else torch.empty_like(w)
         check(lib.srk_drcn_head_loss(ptr(Y), ptr(x), ptr(target), ptr(w), D, n, c, h, wd, ptr(alpha), ptr(reg),
-                                     ctx.seed_value, ptr(out), ptr(dY), ptr(loss), ptr(terms), ptr(dw), 0.0, ptr(ws),
+                                     _declare_seed(ctx), ptr(out), ptr(dY), ptr(loss), ptr(terms), ptr(dw), 0.0, ptr(ws),
                                      ws.numel(), stream_ptr()), "srk_drcn_head_loss")
-        ctx.dY = dY if need_grad else None
-        ctx.dw, ctx.w_in_place = dw, wacc is not None
+        ctx.grads = (dY, dw) if need_grad else (None, None)
+        ctx.w_in_place = wacc is not None
         ctx.mark_non_differentiable(out, terms)
         return loss, out, terms
 
     @staticmethod
     def backward(ctx, g, g_out, g_terms):
-        dY, dw = ctx.dY, ctx.dw
-        if dY is None:
-            return None, None, None, None, None, None, None, None
-        gp = g.data_ptr()
-        if ctx.seed_ptr:
-            if gp == ctx.seed_ptr:
-                return dY, None, (None if ctx.w_in_place else dw), None, None, None, None, None
-            g = g / ctx.seed_value
-        elif gp == unit_seed(dY.device).data_ptr():
-            return dY, None, (None if ctx.w_in_place else dw), None, None, None, None, None
-        lib = _lib.load()
-        g = g.contiguous()
-        out = torch.empty_like(dY)
-        check(lib.srk_scale_dev(ptr(dY), ptr(g), ptr(out), dY.numel(), stream_ptr()), "srk_scale_dev")
-        dws = torch.empty_like(dw)
-        check(lib.srk_scale_dev(ptr(dw), ptr(g), ptr(dws), dw.numel(), stream_ptr()), "srk_scale_dev")
-        if ctx.w_in_place:
-            dw.copy_(dws)
-            return out, None, None, None, None, None, None, None
-        return out, None, dws, None, None, None, None, None
+        dY, dw = _seed_scaled(ctx, g, ctx.grads)
+        if ctx.w_in_place:      # w's gradient lives in its _srk_grad view: a scaled one goes back there, none is returned
+            if dw is not ctx.grads[1]:
+                ctx.grads[1].copy_(dw)
+            dw = None
+        return dY, None, dw, None, None, None, None, None
 
 
 def _drcn_combine_raw(Y, x, w, D):
@@ -2766,8 +2797,8 @@ def lpips_layer(f_pred, f_target, w, row, table):
 
 
 class _LpipsFinish(torch.autograd.Function):
-    """The L rows of the table added in order (one launch): the per-sample values [N], or their mean under the contract of
-    the losses (loss_seed, unit seed, weighted_term, loss_sum) -- the same launch writes seed / N for every sample, the
+    """The L rows of the table added in order (one launch): the per-sample values [N], or their mean under the seed contract
+    of the losses (_declare_seed) -- the same launch writes seed / N for every sample, the
     gradient of each row, so a backward seeded as declared runs no arithmetic of its own.  `rows`: what lpips_layer
     returned, one per row (they tie the layers into the graph)."""
 
@@ -2776,15 +2807,10 @@ class _LpipsFinish(torch.autograd.Function):
         lib = _lib.load()
         nl, n = table.shape
         need = any(ctx.needs_input_grad[2:])
-        seed = _LOSS_SEED[0] if reduce else None
-        ctx.seed_ptr, ctx.seed_value = (seed[1].data_ptr(), seed[0]) if seed is not None else (0, 1.0)
-        # the declared seed is recognised by its address, so the node keeps the tensor alive: freed, its block could
-        # be handed to another upstream gradient, which would then pass for the declared one
-        ctx.seed_keep = seed[1] if seed is not None else None
         out = torch.empty(n if not reduce else (), dtype=torch.float32, device=table.device)
         gvec = torch.empty(n, dtype=torch.float64, device=table.device) if (need and reduce) else None
-        check(lib.srk_lpips_finish(ptr(table), nl, n, ctx.seed_value, None if reduce else ptr(out), ptr(out) if reduce else None,
-                                   ptr(gvec), stream_ptr()), "srk_lpips_finish")
+        check(lib.srk_lpips_finish(ptr(table), nl, n, _declare_seed(ctx, reduce), None if reduce else ptr(out),
+                                   ptr(out) if reduce else None, ptr(gvec), stream_ptr()), "srk_lpips_finish")
         ctx.reduce, ctx.gvec, ctx.k, ctx.need = reduce, gvec, len(rows), need
         return out
 
@@ -2794,13 +2820,10 @@ class _LpipsFinish(torch.autograd.Function):
             return (None,) * (2 + ctx.k)
         if not ctx.reduce:
             gv = g.to(torch.float64).contiguous()       # the per-sample gradients as they come
-        else:
-            gp = g.data_ptr()
-            declared = ctx.seed_ptr if ctx.seed_ptr else unit_seed(g.device).data_ptr()
-            if gp == declared:                           # the seed this loss was computed for: already in gvec
-                gv = ctx.gvec
-            else:                                        # some other upstream gradient: gvec = seed / N
-                gv = ctx.gvec * (g.to(torch.float64) / ctx.seed_value)
+        elif _is_own_seed(ctx, g, g.device):            # the seed this loss was computed for: already in gvec
+            gv = ctx.gvec
+        else:                                           # some other upstream gradient: gvec = seed / N, a fp64 row
+            gv = ctx.gvec * (g.to(torch.float64) / ctx.seed_value)
         return (None, None) + (gv,) * ctx.k
 
 
@@ -2818,7 +2841,7 @@ def lpips_input_affine(normalize=True):
 def lpips(pred, target, net, normalize=True, reduce=True):
     """LPIPS (Zhang et al. 2018, the VGG variant) of pred against target: the five tapped VGG16 maps of both, each pair
     through lpips_layer, the five values added.  reduce=True: the mean over the batch as a 0-dim fp32 device tensor with
-    the contract of the other losses (loss_seed, unit seed, weighted_term, loss_sum); reduce=False: the per-sample
+    the seed contract of the losses (_declare_seed); reduce=False: the per-sample
     values [N].  normalize: the inputs are in [0, 1] (True) or already in [-1, 1] (False).  The gradient flows to pred
     only; both operands run the same kernels (the target's without a graph), so equal inputs give exactly 0 and a zero
     gradient.  pred / target: [N, 3, H, W] on the device with H, W >= 16; net: models.LPIPS."""
@@ -3248,7 +3271,7 @@ def rrdb_trunk(x, blocks, res_scale=0.2):
 
 
 class _RaganLoss(torch.autograd.Function):
-    """srk_ragan_loss_forward_backward: the loss and both gradient rows from one launch, with the seed contract of _Loss."""
+    """srk_ragan_loss_forward_backward: the loss and both gradient rows from one launch, under the losses' seed contract."""
 
     @staticmethod
     def forward(ctx, real, fake, for_generator):
@@ -3263,45 +3286,22 @@ class _RaganLoss(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=real.device)
         d_real = torch.empty_like(real) if ctx.needs_input_grad[0] else None
         d_fake = torch.empty_like(fake) if ctx.needs_input_grad[1] else None
-        seed = _LOSS_SEED[0]
-        ctx.seed_ptr, ctx.seed_value = (seed[1].data_ptr(), seed[0]) if seed is not None else (0, 1.0)
-        ctx.seed_keep = seed[1] if seed is not None else None      # (see _Loss.forward)
         check(lib.srk_ragan_loss_forward_backward(ptr(real), ptr(fake), int(real.shape[0]), 1 if for_generator else 0,
-                                                  ctx.seed_value, ptr(loss), ptr(d_real), ptr(d_fake), None, stream_ptr()),
+                                                  _declare_seed(ctx), ptr(loss), ptr(d_real), ptr(d_fake), None, stream_ptr()),
               "srk_ragan_loss_forward_backward")
         ctx.grads = (d_real, d_fake)
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        grads = ctx.grads
-        if grads[0] is None and grads[1] is None:
-            return None, None, None
-        dev = (grads[0] if grads[0] is not None else grads[1]).device
-        gp = g.data_ptr()
-        if ctx.seed_ptr:
-            if gp == ctx.seed_ptr:
-                return grads[0], grads[1], None
-            g = g / ctx.seed_value
-        elif gp == unit_seed(dev).data_ptr():
-            return grads[0], grads[1], None
-        lib = _lib.load()
-        outs = []
-        for d in grads:
-            if d is None:
-                outs.append(None)
-                continue
-            out = torch.empty_like(d)
-            check(lib.srk_scale_dev(ptr(d), ptr(g.contiguous()), ptr(out), d.numel(), stream_ptr()), "srk_scale_dev")
-            outs.append(out)
-        return outs[0], outs[1], None
+        return _seed_scaled(ctx, g, ctx.grads) + (None,)
 
 
 def ragan_loss(real_logits, fake_logits, for_generator):
     """The relativistic average GAN loss of ESRGAN on discriminator LOGITS ([B] or [B, 1]): with a = real - mean(fake) and
     b = fake - mean(real), the discriminator's mean of softplus(-a) and softplus(b) or, for_generator, of softplus(a) and
-    softplus(-b); the gradient is the full derivative, the means included.  A 0-dim fp32 device tensor with the contract
-    of the other losses (loss_seed, unit seed, weighted_term, loss_sum); a detached operand gets no gradient row.
+    softplus(-b); the gradient is the full derivative, the means included.  A 0-dim fp32 device tensor under the seed
+    contract of the losses (_declare_seed); a detached operand gets no gradient row.
     include/srk.h: srk_ragan_loss_forward_backward."""
     return _RaganLoss.apply(real_logits, fake_logits, bool(for_generator))
 
@@ -3426,7 +3426,7 @@ def upsample_bilinear2x(x, add=None):
 
 
 class _GanLogitLoss(torch.autograd.Function):
-    """srk_gan_logit_loss_forward_backward: the loss and its gradient from one pass and a finish, with _Loss's seed contract."""
+    """srk_gan_logit_loss_forward_backward: loss and gradient from one pass and a finish, under the losses' seed contract."""
 
     @staticmethod
     def forward(ctx, logits, target_is_real):
@@ -3438,36 +3438,21 @@ class _GanLogitLoss(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=x.device)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None     # (preserve_format: the storage order of x)
         ws = torch.empty(int(lib.srk_gan_logit_loss_workspace_bytes()), dtype=torch.uint8, device=x.device)
-        seed = _LOSS_SEED[0]
-        ctx.seed_ptr, ctx.seed_value = (seed[1].data_ptr(), seed[0]) if seed is not None else (0, 1.0)
-        ctx.seed_keep = seed[1] if seed is not None else None      # (see _Loss.forward)
-        check(lib.srk_gan_logit_loss_forward_backward(ptr(x), x.numel(), 1 if target_is_real else 0, ctx.seed_value, ptr(loss),
-                                                      ptr(dx), ptr(ws), stream_ptr()), "srk_gan_logit_loss_forward_backward")
-        ctx.dx = dx
+        check(lib.srk_gan_logit_loss_forward_backward(ptr(x), x.numel(), 1 if target_is_real else 0, _declare_seed(ctx),
+                                                      ptr(loss), ptr(dx), ptr(ws), stream_ptr()),
+              "srk_gan_logit_loss_forward_backward")
+        ctx.grads = (dx,)
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        dx = ctx.dx
-        if dx is None:
-            return None, None
-        gp = g.data_ptr()
-        if ctx.seed_ptr:
-            if gp == ctx.seed_ptr:
-                return dx, None
-            g = g / ctx.seed_value
-        elif gp == unit_seed(dx.device).data_ptr():
-            return dx, None
-        lib = _lib.load()
-        out = torch.empty_like(dx)
-        check(lib.srk_scale_dev(ptr(dx), ptr(g.contiguous()), ptr(out), dx.numel(), stream_ptr()), "srk_scale_dev")
-        return out, None
+        return _seed_scaled(ctx, g, ctx.grads) + (None,)
 
 
 def gan_logit_loss(logits, target_is_real):
     """The vanilla GAN loss on discriminator LOGITS of any shape (a U-Net discriminator's [B, 1, H, W] map, or [B, 1]):
     mean softplus(-x) for a real target, mean softplus(x) for a fake one (BCEWithLogits against ones / zeros).  A 0-dim
-    fp32 device tensor with the contract of the other losses (loss_seed, unit seed, weighted_term, loss_sum).
+    fp32 device tensor under the seed contract of the losses (_declare_seed).
     include/srk.h: srk_gan_logit_loss_forward_backward."""
     return _GanLogitLoss.apply(logits, bool(target_is_real))
 

@@ -1,10 +1,12 @@
 """A loss computed under ops.loss_seed recognises its declared seed by the tensor's address.  If the seed tensor dies before
 the backward, torch's allocator may hand its block to the next small tensor -- another upstream gradient, which must not
-pass for the declared seed.  The loss node keeps the seed alive, so the address cannot be reused while the graph lives."""
+pass for the declared seed.  The loss node keeps the seed alive, so the address cannot be reused while the graph lives.
+One function declares the seed for every loss (ops._declare_seed), so this is one property: it is held for every operator
+of tests/test_loss_seed_contract_gpu.py."""
 import pytest
 import torch
 
-from oracle import fill
+from test_loss_seed_contract_gpu import BUILDERS, case_of
 
 pytestmark = pytest.mark.gpu
 
@@ -14,21 +16,23 @@ def _pkg():
     return pkg
 
 
-def test_a_dead_seeds_address_is_not_mistaken_for_the_seed(gpu):
+@pytest.mark.parametrize("name", sorted(BUILDERS))
+def test_a_dead_seeds_address_is_not_mistaken_for_the_seed(gpu, name):
     ops = _pkg().ops
-    pred, target = fill.rand((2, 3, 8, 8), 1).to(gpu), fill.rand((2, 3, 8, 8), 2).to(gpu)
-    p0 = pred.clone().requires_grad_(True)
-    ops.backward(ops.l1_loss(p0, target))
-    base = p0.grad.detach()
+    case = case_of(name, gpu)
+    leaves = case.on(gpu)
+    ops.backward(case.fn(ops, *leaves))
+    base = [t.grad.detach() for t in leaves]
     for _ in range(4):                       # (several rounds: each leaves the allocator's free list in another state)
-        p = pred.clone().requires_grad_(True)
+        leaves = case.on(gpu)
         seed = torch.full((), 0.25, device=gpu)
         addr = seed.data_ptr()
         with ops.loss_seed(0.25, seed):
-            loss = ops.l1_loss(p, target)
+            loss = case.fn(ops, *leaves)
         del seed                             # the caller's last reference: only the loss node may still hold the tensor
         others = [torch.ones((), device=gpu) for _ in range(8)]     # small tensors: candidates for the freed block
         assert all(o.data_ptr() != addr for o in others)            # the block is still the seed's
         loss.backward(others[0])             # not the declared seed: the folded 0.25 is undone
-        assert torch.allclose(p.grad, base, rtol=1e-6, atol=0.0)
+        for t, b in zip(leaves, base):
+            assert torch.allclose(t.grad, b, rtol=1e-6, atol=0.0)
         del loss, others
