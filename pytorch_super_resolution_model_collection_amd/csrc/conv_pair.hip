@@ -11,16 +11,19 @@
 // above: a tile whose upper neighbour is the run's previous tile computes only rows 2 .. 9 (144 pixels, nine 16-pixel
 // fragments) and takes rows 0 .. 1 from three rotating buffers of kept rows; the first tile of a run and the top tile of a
 // column compute their rows 0 .. 1 as three more fragments.  Every value of the intermediate is the same number whichever
-// tile computed it (same K order, same scale), so the output does not depend on where runs start.
+// tile computed it (same K order, same scale), so the output does not depend on where runs start.  The coordinates (image,
+// tile column, tile row) of a group's tile are split once in front of the tile loop and then advanced by two list steps
+// with add and carry; nothing inside the loop divides by a run-time value.
 //
 // First layer: every one of the 225 products of the f16x3 sum (75 taps x {w_h x_h, w_h x_m, w_m x_h}) has a K slot of
-// its own: 256 K in eight 16x16x32 steps, one MFMA per step and channel fragment (pr_kgroup below).  A staged pixel is one
-// 16-byte cell of PQ, {h0 h1 h2 m0 m1 m2 h0 h1}, that meets {wh0 wh1 wh2 wh0 wh1 wh2 wm0 wm1} of a tap: 25 K groups, eight
+// its own: 256 K in eight 16x16x32 steps, one MFMA per step and channel fragment (pr_kgroup, conv_pair_layout.h).  A
+// staged pixel is one 16-byte cell of PQ, {h0 h1 h2 m0 m1 m2 h0 h1}, that meets {wh0 wh1 wh2 wh0 wh1 wh2 wm0 wm1} of a tap: 25 K groups, eight
 // of a tap's nine products each; the ninth, wm2 h2, of a kernel row's five taps is one K group against T, which holds h2
 // of four pixels in a row per 8-byte cell.  Steps 0 .. 5 read one aligned 16-byte cell per lane, steps 6 and 7 two aligned
 // 8-byte halves.  A wave holds the filter side of both 16-channel fragments of ONE 32-channel chunk in registers (64
 // VGPRs), so that a pixel fragment read feeds two MFMAs, and computes four of the nine pixel fragments, every other tile
-// five.  The intermediate's fp16 scale
+// five.  A cell is requested a K step ahead of its two MFMAs, through five rotating registers of four (l1_frags; DESIGN
+// 15.7).  The intermediate's fp16 scale
 // is a BOUND, not a measured maximum: max_c(|b_c| + sum |w_c| max|x|) >= max|relu(conv)|, so no rendezvous per tile; a
 // power-of-two scale above the true maximum gives the same planes unless the residual plane underflows, i.e. it only
 // raises the absolute error floor (ops.declare_absmax).
@@ -52,25 +55,21 @@
 // pixel half 1 (f >= 4, first row 5) skip their first layer when vr <= 3, the waves of output rows 4 .. 7 their second layer
 // and stores when vr <= 4.  They still perform every wait and signal.
 #include "conv_bfw.h"   // lds_cnt_*; srk_common.h, conv_problem.h, bf16_frag.h
+#include "conv_pair_layout.h"   // the staged tile, pr_kgroup, the fragment addresses (shared with tools/pair_lds_host_check.cpp)
 
 namespace srk {
 
 namespace {
 
-constexpr int PR_TH = 8, PR_TW = 16, PR_HW = 18;
+constexpr int PR_TH = 8, PR_TW = 16;
 constexpr int PR_NSLOTPIX = 6 * PR_HW, PR_NPIXP = PR_NSLOTPIX + 2;  // halo rows 2 .. 7 live in a ring slot: pixels, stride
                                                                     // (pixel p of rows 2 .. 9 is halo pixel 36 + p)
-constexpr int PR_NKEEP = 2 * PR_HW, PR_KP = PR_NKEEP + 2;    // halo rows 8 .. 9 = the tile below's rows 0 .. 1: pixels, stride
-constexpr int PR_XR = 14, PR_XC = 23, PR_XP = 24;   // staged input tile: rows, columns, cell pitch of a row (PQ and T)
+constexpr int PR_KP = PR_NKEEP + 2;                 // halo rows 8 .. 9 = the tile below's rows 0 .. 1 (PR_NKEEP pixels): stride
 constexpr int PR_NSLOT = 3, PR_NKBUF = 3;
 constexpr int PR_WL2 = 9 * 2 * 256;                 // uint4 of the second layer's filter [tap][chunk][plane][group][32]
 constexpr int PR_HBUF = 4 * PR_NPIXP;               // uint4 per plane of a halo slot [group][NPIXP]
 constexpr int PR_KBUF = 2 * 4 * PR_KP;              // uint4 per plane of a kept-row buffer [chunk][group][KP]
 constexpr int PR_PLANE = PR_NSLOT * PR_HBUF + PR_NKBUF * PR_KBUF;   // the residual planes of all of them lie this far on
-constexpr int PR_XPQ = PR_XR * PR_XP * 16;          // bytes of a group's PQ [row][pixel]: 16-byte cells
-constexpr int PR_XT = PR_XPQ + 32;                  // T [row][pixel] of 8-byte cells starts here (cells -3 .. -1 exist: staging)
-constexpr int PR_XBUF = PR_XT + PR_XR * PR_XP * 8;  // bytes of a group's input tile
-constexpr unsigned long long PR_FPIX = 0xfdb9eca875316420ull;   // nibble j: the fragment pixel of lane column j
 constexpr unsigned PR_AMAX_CAP = 1u << 14;          // polls of the max|x| rendezvous (one L2 round trip and a sleep each)
 constexpr int PR_ARRIVE = 1, PR_DEPART = 2;         // counter words of the slots buffer (slot i is word 16 i)
 // Both words MUST stay in one 64-byte line and be touched by one thread of a block (thread 0).  The reset -- the last
@@ -81,6 +80,9 @@ constexpr int PR_ARRIVE = 1, PR_DEPART = 2;         // counter words of the slot
 // device memory (what the slots are: a torch allocation) are performed there.  Moved to different lines, or issued by different
 // waves, the arrival could land after the zeroing and leave the counter at 1 for the next launch.  The ordering of a
 // block's slot maximum before its arrival does not lean on this: the maximum returns a value the arrival waits for.
+// l1_frags requests the cell of group g + D in front of the MFMAs of group g: a K step ahead in the two- and the four-
+// fragment form; the five-fragment form, where the kernel's register maximum lies, keeps the same five cell registers
+#define PR_L1_AHEAD(NM) ((NM) == 2 ? 2 : 4)
 constexpr int PR_XLD = 24;                          // float4 loads a thread keeps in flight over its part of the slice
 constexpr int PR_W1P = 2 * 2 * 8 * 64;              // uint4 of the prepared first layer [c1][nf][ks][lane]; behind
 constexpr int PR_W1P_FLOATS = 144;                  // them floats: sum |w_c| [64], |b_c| [64], max |w|
@@ -105,7 +107,7 @@ struct PairParams {
   float* y_amax;
   size_t xn;               // elements of x
   int amax_mode;           // 0: x_amax holds the maximum; 1: measured in this launch; 2: same, every block scans all of x
-  int N, H, W, OH, OW, tiles_y, img_tiles, ntiles;
+  int N, H, W, OH, OW, tiles_x, tiles_y, img_tiles, ntiles;
   unsigned x_img_bytes, y_bytes;
 };
 
@@ -130,26 +132,6 @@ __device__ __forceinline__ float pr_slice_absmax(const float* __restrict__ x, si
     if (t < 3 && e < n) m = fmaxf(m, fabsf(x[e]));
   }
   return m;
-}
-
-// The first layer's K: 8 steps of 32, lane quarter kq supplies K values 8 kq .. 8 kq + 7 of step ks -- one K group.
-//   PR_KTAP  tap (dy, dx): pixel side the PQ cell {h0 h1 h2 m0 m1 m2 h0 h1} of pixel (row + dy, col + dx), filter side
-//            {wh0 wh1 wh2 wh0 wh1 wh2 wm0 wm1}: eight of the tap's nine products w_h x_h + w_h x_m + w_m x_h
-//   PR_KROW  kernel row dy: pixel side T(row + dy, col), T(row + dy, col + 4) = h2 of eight pixels in a row, filter side
-//            {wm2 of dx = 0 .. 4, 0, 0, 0}: the ninth product of the row's five taps
-//   PR_KNONE zero weights against any staged cell
-// Steps 0 .. 4: tap (ks, kq).  Step 5: tap (r, 4), r = 0, 2, 1, 3 for kq = 0 .. 3.  Step 6: tap (4, 4), none, rows 0, 2.
-// Step 7: rows 1, 3, 4, none.  A lane's cell of steps 0 .. 4 is its own cell of step 0 plus ks rows: one base and an
-// immediate.  Which groups share a step, and a lane pair (kq, kq + 1) inside it, is chosen for the LDS banks.
-enum { PR_KTAP, PR_KROW, PR_KNONE };
-struct PrKGroup {
-  int kind, dy, dx;
-};
-__device__ __forceinline__ constexpr PrKGroup pr_kgroup(int ks, int kq) {
-  if (ks < 5) return {PR_KTAP, ks, kq};
-  if (ks == 5) return {PR_KTAP, (kq >> 1) + 2 * (kq & 1), 4};
-  if (ks == 6) return kq == 0 ? PrKGroup{PR_KTAP, 4, 4} : (kq == 1 ? PrKGroup{PR_KNONE, 0, 0} : PrKGroup{PR_KROW, 2 * kq - 4, 0});
-  return kq == 3 ? PrKGroup{PR_KNONE, 0, 0} : PrKGroup{PR_KROW, kq == 2 ? 4 : 2 * kq + 1, 0};
 }
 
 // The first layer's filter as the lanes of k_espcn_pair hold it: wave c1 of two writes, for its 32-channel chunk, lane
@@ -264,29 +246,27 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
   // read PQ cell offset + ks PR_XP, step 5 offset + k5; step s of 6 and 7 reads two 8-byte halves, at byte offset * kmul[s]
   // + kadd[s] and kd[s] on: of the PQ cell of tap (4, 4) or of T's cells of the lane's row.  A lane without a K group reads
   // what its neighbour reads (the same addresses cost no LDS cycle).
-  const int jp = (int)((PR_FPIX >> (4 * j)) & 15);
+  // (conv_pair_layout.h holds these expressions: pr_body_pix, pr_top_pix, pr_cell_off, pr_k5, pr_k67)
   int mpix[5], moff[5], tpix[2], toff[2];
 #pragma unroll
   for (int m = 0; m < 5; ++m) {
-    mpix[m] = 16 * (m < 4 ? 4 * mh + m : 8) + jp;
-    const int p = PR_NKEEP + mpix[m];
-    moff[m] = (p / PR_HW) * PR_XP + p % PR_HW + kq;
+    mpix[m] = pr_body_pix(mh, m, j) - PR_NKEEP;
+    moff[m] = pr_cell_off(pr_body_pix(mh, m, j), kq);
   }
 #pragma unroll
   for (int m = 0; m < 2; ++m) {
-    tpix[m] = 16 * (2 * mh + m) + jp;
-    const int p = tpix[m] < PR_NKEEP ? tpix[m] : PR_NKEEP - 1;
-    toff[m] = (p / PR_HW) * PR_XP + p % PR_HW + kq;
+    tpix[m] = 16 * (2 * mh + m) + pr_fpix(j);
+    toff[m] = pr_cell_off(pr_top_pix(mh, m, j), kq);
   }
-  const int k5 = pr_kgroup(5, kq).dy * PR_XP + 4 - kq;
+  const int k5 = pr_k5(kq);
   int kmul[2], kadd[2], kd[2];
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    const PrKGroup own = pr_kgroup(6 + s, kq), g = own.kind == PR_KNONE ? pr_kgroup(6 + s, kq - 1) : own;
-    kmul[s] = g.kind == PR_KTAP ? 16 : 8;
-    kd[s] = g.kind == PR_KTAP ? 8 : 32;
+    const PrK67 k = pr_k67(s, kq);
+    kmul[s] = k.kmul;
+    kd[s] = k.kd;
     asm volatile("" : "+v"(kd[s]));   // (step 7's is 32 in every lane: as a constant the two reads become one ds_read2_b64)
-    kadd[s] = g.kind == PR_KTAP ? 16 * (g.dy * PR_XP + g.dx - kq) : PR_XT + 8 * (g.dy * PR_XP - kq);
+    kadd[s] = k.kadd;
   }
   // where this lane's four channels of fragment 0 go: byte offset of pixel 0 inside a slot / inside a buffer of kept rows
   // (fragment 1: two 8-channel groups on)
@@ -315,17 +295,38 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
     count = per + (lb < rem ? 1 : 0);
   }
   count = __builtin_amdgcn_readfirstlane(count);
+  // Tile coordinates (image, tile column, tile row) of the group's current tile, the same in every lane of a wave, split
+  // once here (the only divisions by run-time values) and advanced by two list steps with add and carry (conv_bfr.hip's
+  // adv2; as two single steps, so that no step vector is held): the tile two on is the group's next, whose input xload
+  // fetches.  Held in VGPRs: as SGPRs they turn the tile loop's tests into scalar branches and cost six SGPR spills.
+  int cn, cx, cy;
+  {
+    const int t = first + grp;
+    const int n = t / B.img_tiles, rem = t - n * B.img_tiles, x = rem / B.tiles_y;
+    cn = n;
+    cx = x;
+    cy = rem - x * B.tiles_y;
+  }
+  auto adv2 = [&](int& n, int& x, int& y) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      if (++y == B.tiles_y) {
+        y = 0;
+        if (++x == B.tiles_x) {
+          x = 0;
+          ++n;
+        }
+      }
+    }
+  };
 
   const __amdgpu_buffer_rsrc_t yr = buffer_rsrc(B.y, B.y_bytes);
   const unsigned HW_ = (unsigned)(B.H * B.W);
   // input staging: pixel q = lt + 256 s of the 14 x 23 tile, 3 channels
   float xv[2][3];
-  auto xload = [&](int i) {
+  auto xload = [&](int i, int n, int tx, int ty) {   // run entry i = tile (n, tx, ty); nothing is read past the run's end
     const bool valid = i < count;
-    const int t = first + (valid ? i : 0);
-    const int n = t / B.img_tiles, rem = t - n * B.img_tiles;
-    const int tx = rem / B.tiles_y, ty = rem - tx * B.tiles_y;
-    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(B.x + (size_t)n * 3 * HW_, B.x_img_bytes);
+    const __amdgpu_buffer_rsrc_t xr = buffer_rsrc(B.x + (size_t)(valid ? n : 0) * 3 * HW_, B.x_img_bytes);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const int q = lt + 256 * s, qy = q / PR_XC, qx = q - qy * PR_XC;
@@ -336,31 +337,38 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
         xv[s][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xr, (int)(o + (ok ? 4u * c * HW_ : 0u)), 0, 0));
     }
   };
-  // NM 16-pixel fragments of the first layer (per output: K step order 0 .. 7, one product per step)
+  // NM 16-pixel fragments of the first layer (per output: K step order 0 .. 7, one product per step).  A group is one cell
+  // and its two MFMAs, groups run in the order (K step, fragment); the cell of group g + D is requested in front of the
+  // MFMAs of group g, through D + 1 rotating registers of four: a K step ahead where the registers allow it.
   auto l1_frags = [&](auto nm, const int* off, f32x4 (*a)[2]) {
-    constexpr int NM = decltype(nm)::value;
+    constexpr int NM = decltype(nm)::value, G = 8 * NM, D = PR_L1_AHEAD(NM);
+    uint4 xc[D + 1];
+    auto rd = [&](auto gc) {
+      constexpr int g = decltype(gc)::value, ks = g / NM, m = g % NM;
+      if constexpr (ks < 6) {
+        xc[g % (D + 1)] = *reinterpret_cast<const uint4*>(xin + 16 * (off[m] + (ks < 5 ? ks * PR_XP : k5)));
+      } else {
+        const int pa = __mul24(off[m], kmul[ks & 1]) + kadd[ks & 1];
+        const uint2 ca = *reinterpret_cast<const uint2*>(xin + pa), cb = *reinterpret_cast<const uint2*>(xin + pa + kd[ks & 1]);
+        xc[g % (D + 1)] = make_uint4(ca.x, ca.y, cb.x, cb.y);
+      }
+    };
 #pragma unroll
     for (int m = 0; m < NM; ++m) a[m][0] = a[m][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    srk_static_for<0, D>([&](auto gc) { rd(gc); });
+    __builtin_amdgcn_sched_barrier(0);
+    srk_static_for<0, G>([&](auto gc) {
+      constexpr int g = decltype(gc)::value, ks = g / NM, m = g % NM;
+      if constexpr (g + D < G) rd(std::integral_constant<int, g + D>{});
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-#pragma unroll
-      for (int m = 0; m < NM; ++m) {
-        uint4 xc;
-        if (ks < 6) {
-          xc = *reinterpret_cast<const uint4*>(xin + 16 * (off[m] + (ks < 5 ? ks * PR_XP : k5)));
-        } else {
-          const int pa = __mul24(off[m], kmul[ks & 1]) + kadd[ks & 1];
-          const uint2 ca = *reinterpret_cast<const uint2*>(xin + pa), cb = *reinterpret_cast<const uint2*>(xin + pa + kd[ks & 1]);
-          xc = make_uint4(ca.x, ca.y, cb.x, cb.y);
-        }
-#pragma unroll
-        for (int nf = 0; nf < 2; ++nf) a[m][nf] = mfma16h(w1f[nf][ks], xc, a[m][nf]);
-      }
-    }
+      for (int nf = 0; nf < 2; ++nf) a[m][nf] = mfma16h(w1f[nf][ks], xc[g % (D + 1)], a[m][nf]);
+      __builtin_amdgcn_sched_barrier(0);
+    });
   };
   bool dead = false;
   float amax = 0.f;
-  xload(grp);
+  xload(grp, cn, cx, cy);
   // ---- max|x| of all blocks: the first wave polls for their arrivals, reads the slots, leaves (the last one to leave
   // zeroes the two counter words: a captured launch replays) ---------------------------------------------------------------
   if (B.amax_mode && wave == 0) {
@@ -425,9 +433,8 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
   unsigned kseq = 0;
   int typrev = 0;
   for (int i = grp; i < count; i += 2, ++own) {
-    const int t = first + i;
-    const int n = t / B.img_tiles, rem = t - n * B.img_tiles;
-    const int tx = rem / B.tiles_y, ty = rem - tx * B.tiles_y;
+    const int n = cn, tx = cx, ty = cy;
+    adv2(cn, cx, cy);   // (the next own tile's)
     // Rows 0 .. 1 of this tile's halo are rows 8 .. 9 of the tile above when that is the run's previous tile; the first
     // tile of a run and a column's top tile compute them.  Kept rows are numbered along the run: a tile's rows 8 .. 9 are
     // number kseq, its rows 0 .. 1 number kseq - 1 (the previous tile's kseq, or a number of their own when computed
@@ -460,7 +467,7 @@ __global__ __launch_bounds__(512, 1) void k_espcn_pair(PairParams B) {
       }
     }
     lds_cnt_signal(cnt + 6 + grp);
-    xload(i + 2);
+    xload(i + 2, cn, cx, cy);
     lds_cnt_wait(cnt + 6 + grp, 4u * (own + 1), dead);
 
     float b1v[2][4];  // (read per tile: registers are short where the second layer runs)
@@ -673,7 +680,7 @@ int espcn_pair_launch(int N, int H, int W, const float* x, const void* w1p, cons
   B.amax_mode = amax_mode;
   B.wq2 = reinterpret_cast<const uint4*>(fsec);
   B.w2_descale = reinterpret_cast<const float*>(fsec + bf3_main_bytes(64, 32, 9));
-  B.N = N; B.H = H; B.W = W; B.OH = OH; B.OW = OW; B.tiles_y = tiles_y; B.img_tiles = tiles_x * tiles_y;
+  B.N = N; B.H = H; B.W = W; B.OH = OH; B.OW = OW; B.tiles_x = tiles_x; B.tiles_y = tiles_y; B.img_tiles = tiles_x * tiles_y;
   B.ntiles = (int)ntiles;
   B.x_img_bytes = (unsigned)x_img;
   B.y_bytes = (unsigned)y_bytes;
