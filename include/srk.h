@@ -1196,6 +1196,45 @@ int srk_gan_logit_loss_forward_backward(const float* logits, size_t n, int targe
 int srk_gan_logit_loss_host(const float* logits, size_t n, int target_is_real, double grad_scale, double* loss,
                             double* d_logits);
 
+/* ---- The multi-layer VGG feature loss: one tapped layer, fused (csrc/vgg_tap.hip, csrc/vgg_tap_common.h) ---------------
+ * (Additive again: new entry points and one enum, srk_version() and everything existing unchanged.)
+ * a (the prediction's map, takes the gradient) and b (the target's) are the PRE-activation maps of one VGG layer, dense
+ * NHWC [N][H][W][C] fp32; weight >= 0.  The tap's term is weight * mean |a - b| over all N*H*W*C elements; `mode` says
+ * what the head runs behind the tap, and the tap runs it:
+ *   SRK_VGG_TAP_POOL   ReLU, MaxPool 2 x 2     forward writes ya = pool(relu(a)), yb = pool(relu(b))  [N][H/2][W/2][C]
+ *                                              backward  da = c * sign(a - b) + route(g)       g: the gradient of ya
+ *   SRK_VGG_TAP_RELU   ReLU, then a conv       forward writes ya = relu(a), yb = relu(b)       [N][H][W][C]
+ *                                              backward  da = c * sign(a - b) + (a > 0 ? g : 0)
+ *   SRK_VGG_TAP_LAST   nothing                 forward writes no map (ya, yb, g are ignored)   da = c * sign(a - b)
+ * sign(0) = 0.  route(g): the winner of a window is the first strictly greater value in (row, column) order, and a
+ * window whose maximum is <= 0 routes nothing -- srk_maxpool2x2_backward with relu_input = 1.  The windows are
+ * ceil(H/2) x ceil(W/2): with odd H or W the trailing row / column counts in the term and gets its da, and has no pooled
+ * output (floor mode).  POOL needs H, W >= 2.
+ * One launch each way.  Every element of ya, yb and da is written exactly once: nothing is cleared, no atomics.
+ * 16-byte accesses where C % 4 == 0 and every pointer is 16-byte aligned, else 4-byte accesses.
+ * The term's sum: |a - b| with the difference in fp64, per-block fp64 partials in a fixed order.  The forward writes row
+ * `row` of the workspace, srk_vgg_tap_workspace_bytes(rows) bytes, 8-byte aligned, all rows of which must be written by
+ * taps before srk_vgg_tap_finish (one launch) adds them in index order into *loss (fp32) = sum_k weight_k * mean_k.  Two
+ * runs on the same inputs give the same bits.
+ * srk_vgg_tap_backward: c = weight * seed / (N*H*W*C) on the host; factor: NULL, or one fp32 on the device that multiplies
+ *   c (an upstream gradient that is not the node's own seed).
+ * srk_vgg_tap_plan: the blocks of either launch of that mode on the 16-byte (vec = 1) or 4-byte path and, in *items, the
+ *   items its grid-stride loop walks (256 per block and pass); a negative status for bad sizes.
+ * srk_vgg_tap_forward_host / _backward_host: the same window bodies on host pointers, in double up to the fp32 stores;
+ *   *loss = weight * mean |a - b| in double; c as above (with any factor folded in). */
+typedef enum srk_vgg_tap_mode { SRK_VGG_TAP_POOL = 0, SRK_VGG_TAP_RELU = 1, SRK_VGG_TAP_LAST = 2 } srk_vgg_tap_mode;
+size_t srk_vgg_tap_workspace_bytes(int rows);
+int srk_vgg_tap_plan(int N, int H, int W, int C, int mode, int vec, long long* items);
+int srk_vgg_tap_forward(const float* a, const float* b, int N, int H, int W, int C, int mode, double weight, int row,
+                        int rows, void* workspace, float* ya, float* yb, void* stream);
+int srk_vgg_tap_finish(const void* workspace, int rows, float* loss, void* stream);
+int srk_vgg_tap_backward(const float* a, const float* b, const float* g, int N, int H, int W, int C, int mode, double c,
+                         const float* factor, float* da, void* stream);
+int srk_vgg_tap_forward_host(const float* a, const float* b, int N, int H, int W, int C, int mode, double weight,
+                             double* loss, float* ya, float* yb);
+int srk_vgg_tap_backward_host(const float* a, const float* b, const float* g, int N, int H, int W, int C, int mode, double c,
+                              float* da);
+
 #ifdef __cplusplus
 }
 #endif

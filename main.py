@@ -43,7 +43,10 @@ GAN loss, which needs --vgg_weights PATH (conv5_4 features before the ReLU).  x4
 --discriminator {vgg,unet} (ESRGAN; default vgg): unet trains against Real-ESRGAN's U-Net discriminator with spectral
 normalisation (models.UNetDiscriminatorSN, --unet_feat F channels, default 64; one logit a pixel, so any --crop_size that is
 a multiple of 8) on --gan_type vanilla (ops.gan_logit_loss; the default with unet, where ragan is refused; ragan stays the
-default with vgg).  Real-ESRGAN's multi-layer VGG term and data parallelism are not part of it.
+default with vgg).  Data parallelism is not part of it.
+--vgg_layers SPEC (ESRGAN, with --vgg_weights): Real-ESRGAN's multi-layer VGG feature term in place of the conv5_4 one, an
+L1 on VGG19 maps taken before their ReLUs: SPEC is name:weight,... (conv1_1 .. conv5_4) or `realesrgan`
+(conv1_2:0.1,conv2_2:0.1,conv3_4:1,conv4_4:1,conv5_4:1); each tapped layer is one fused kernel (ops.vgg_feature_loss).
 --degrade2 [SETTINGS.json] (train on Real-ESRGAN's second-order degradation, data.Degradation2: blur, resize, Gaussian or
 Poisson noise and JPEG, twice, then a sinc filter, every stage a kernel on 8-bit patches; the file holds only overrides of
 Degradation2's keywords), --usm (the training target and the degradation's input are the patches sharpened by
@@ -452,8 +455,23 @@ def parse_args(argv=None):
                         '--discriminator vgg) or vanilla (default with, and the only one for, --discriminator unet)')
     p.add_argument('--unet_feat', type=_positive, default=None, metavar='F',
                    help='ESRGAN with --discriminator unet: channels of the U-Net\'s first layer (default 64)')
+    p.add_argument('--vgg_layers', type=str, default=None, metavar='SPEC',
+                   help='ESRGAN: train on Real-ESRGAN\'s multi-layer VGG feature term instead of the single conv5_4 one: '
+                        'name:weight,... over VGG19 conv layers taken before their ReLUs (conv1_1 .. conv5_4), or the word '
+                        'realesrgan = conv1_2:0.1,conv2_2:0.1,conv3_4:1,conv4_4:1,conv5_4:1.  Needs --vgg_weights; the whole '
+                        'term is weighed by --vgg_loss_weight')
     args = p.parse_args(argv)
     esrgan = args.model_name == 'ESRGAN'
+    if args.vgg_layers is not None:
+        if not esrgan:
+            p.error('--vgg_layers: only ESRGAN has the multi-layer VGG feature term, not %s' % args.model_name)
+        if not args.vgg_weights:
+            p.error('--vgg_layers needs --vgg_weights PATH (a torchvision vgg19 state_dict file)')
+        from pytorch_super_resolution_model_collection_amd.sr_trainers import parse_vgg_layers
+        try:
+            parse_vgg_layers(args.vgg_layers)
+        except ValueError as e:
+            p.error('--vgg_layers %s: %s' % (args.vgg_layers, e))
     for flag in ('discriminator', 'gan_type', 'unet_feat'):
         if getattr(args, flag) is not None and not esrgan:
             p.error('--%s: only ESRGAN chooses its discriminator and GAN loss, not %s' % (flag, args.model_name))

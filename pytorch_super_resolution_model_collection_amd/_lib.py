@@ -20,6 +20,7 @@ ALGO_AUTO, ALGO_GENERIC, ALGO_MFMA, ALGO_DIRECT, ALGO_MFMA_BF16X3, ALGO_MFMA_BF1
 AMAX_FLOATS = 256   # SRK_AMAX_FLOATS: 16 slots, one per 64-byte line
 LOSS_MSE, LOSS_L1, LOSS_CHARBONNIER, LOSS_BCE = range(4)
 FFT_LOSS_MAX_DIM = 256   # SRK_FFT_LOSS_MAX_DIM
+VGG_TAP_POOL, VGG_TAP_RELU, VGG_TAP_LAST = range(3)   # srk_vgg_tap_mode
 SSIM_DOMAINS = {"float": 0, "u8": 1, "y8": 2}   # SRK_SSIM_FLOAT / _U8 / _Y8
 ACT_BY_NAME = {None: ACT_NONE, "relu": ACT_RELU, "prelu": ACT_PRELU, "lrelu": ACT_LRELU, "tanh": ACT_TANH,
                "sigmoid": ACT_SIGMOID}
@@ -336,6 +337,14 @@ _PROTOTYPES = {
     "srk_usm_u8_workspace_bytes": (c_size, [c_int] * 4),
     "srk_usm_u8": (c_int, [c_vp] * 3 + [c_int, ctypes.c_double, ctypes.c_double] + [c_int] * 4 + [c_vp, c_size, c_vp]),
     "srk_usm_u8_host": (c_int, [c_vp] * 3 + [c_int, ctypes.c_double, ctypes.c_double] + [c_int] * 4),
+    "srk_vgg_tap_workspace_bytes": (c_size, [c_int]),
+    "srk_vgg_tap_plan": (c_int, [c_int] * 6 + [ctypes.POINTER(ctypes.c_longlong)]),
+    "srk_vgg_tap_forward": (c_int, [c_f, c_f] + [c_int] * 5 + [ctypes.c_double, c_int, c_int, c_vp, c_f, c_f, c_vp]),
+    "srk_vgg_tap_finish": (c_int, [c_vp, c_int, c_f, c_vp]),
+    "srk_vgg_tap_backward": (c_int, [c_f] * 3 + [c_int] * 5 + [ctypes.c_double, c_f, c_f, c_vp]),
+    "srk_vgg_tap_forward_host": (c_int, [c_vp, c_vp] + [c_int] * 5 + [ctypes.c_double, ctypes.POINTER(ctypes.c_double),
+                                         c_vp, c_vp]),
+    "srk_vgg_tap_backward_host": (c_int, [c_vp] * 3 + [c_int] * 5 + [ctypes.c_double, c_vp]),
 }
 
 _lib = None

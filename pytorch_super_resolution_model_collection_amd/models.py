@@ -12,7 +12,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops, utils
+from . import _lib, ops, utils
 from ._lib import ACT_NONE, ACT_RELU
 from .base_networks import (RDB, RRDB, RSTB, ConvBlock, DeconvBlock, DenseBlock, PSBlock, ResidualGroup, ResnetBlock,
                             Upsample2xBlock)
@@ -707,6 +707,10 @@ class FeatureExtractor(nn.Module):
     def _walk(self, out, grad):
         return _vgg_walk(list(self.features), out, grad)
 
+    def tap_walk(self, a, b, taps):
+        """The multi-layer feature term of ops.vgg_feature_loss on already normalised operands: see _vgg_pair_walk."""
+        return _vgg_pair_walk(list(self.features), a, b, taps)
+
 
 def _vgg_modules(cfg):
     """torchvision's `features` of a VGG configuration (numbers = conv3x3 output channels, 'M' = MaxPool2d(2,2)) as this
@@ -785,6 +789,52 @@ def _vgg_walk(mods, out, grad, taps=None):
                 keep = out
             got.append(keep)
     return out if taps is None else got
+
+
+def _vgg_pair_walk(mods, a, b, taps):
+    """Prediction `a` and target `b` through a VGG head in lockstep, up to the deepest tap; taps = [(conv index, weight)]
+    in the order of the head.  Returns sum_k weight_k * L1 of the two maps that leave conv k BEFORE its ReLU
+    (ops.vgg_feature_loss).  Untapped layers run as _vgg_walk(grad=True) runs them, `b` without a graph on the same
+    kernels.  A tapped conv runs without its ReLU, both packs from the layer's cache, and ops.vgg_tap then does in one
+    launch what the head runs behind it: the ReLU and the pool, the ReLU alone, or nothing at the deepest tap -- no fork,
+    no separate ReLU or pool launch."""
+    want = dict(taps)
+    last = max(want)
+    ws = torch.empty(int(_lib.load().srk_vgg_tap_workspace_bytes(len(want))), dtype=torch.uint8, device=a.device)
+    tokens = []
+    i = 0
+    while i <= last:
+        m = mods[i]
+        if isinstance(m, nn.Conv2d):
+            fused = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+            tapped = i in want
+            cfg = ops.ConvCfg(m._s, m._p, False, 0, ACT_RELU if (fused and not tapped) else ACT_NONE)
+            packs = m._cache.get(m.weight, m.bias, False, 0, bwd=True)
+            a = ops.conv2d(a, m.weight, m.bias, None, cfg, packs)
+            with torch.no_grad():
+                b = ops.conv2d(b, m.weight, m.bias, None, cfg, packs)
+            step = 2 if fused else 1
+            if tapped:
+                if i == last:
+                    mode = _lib.VGG_TAP_LAST
+                elif fused and i + 2 < len(mods) and isinstance(mods[i + 2], _MaxPool2x2):
+                    mode, step = _lib.VGG_TAP_POOL, 3
+                elif fused:
+                    mode = _lib.VGG_TAP_RELU
+                else:
+                    raise ValueError("vgg tap: layer %d is followed by neither a ReLU nor the end of the walk" % i)
+                token, a, b = ops.vgg_tap(a, b, mode, want[i], len(tokens), len(want), ws)
+                tokens.append(token)
+            i += step
+        elif isinstance(m, _MaxPool2x2):
+            a = ops.max_pool2x2_train(a)
+            with torch.no_grad():
+                b = ops.max_pool2x2_train(b)
+            i += 1
+        else:
+            a, b = m(a), m(b)
+            i += 1
+    return ops.vgg_tap_finish(ws, len(want), tokens)
 
 
 class LPIPS(nn.Module):

@@ -1747,6 +1747,159 @@ def perceptual_loss(pred, target, extractor, normalize=True, criterion='mse'):
     return mse_loss(fake, real) if criterion == 'mse' else l1_loss(fake, real)
 
 
+# ---- the multi-layer VGG feature loss (Real-ESRGAN's; csrc/vgg_tap.hip) -------------------------------
+REALESRGAN_VGG_LAYERS = (('conv1_2', 0.1), ('conv2_2', 0.1), ('conv3_4', 1.0), ('conv4_4', 1.0), ('conv5_4', 1.0))
+
+
+def vgg_conv_names(cfg):
+    """{'conv{k}_{j}': torchvision index} of a VGG configuration (numbers = conv3x3 channels, each followed by its ReLU;
+    'M' = the pool that ends block k): for vgg19, conv1_2 -> 2, conv2_2 -> 7, conv3_4 -> 16, conv4_4 -> 25, conv5_4 -> 34."""
+    names, idx, k, j = {}, 0, 1, 0
+    for v in cfg:
+        if v == 'M':
+            idx, k, j = idx + 1, k + 1, 0
+        else:
+            j += 1
+            names['conv%d_%d' % (k, j)] = idx
+            idx += 2
+    return names
+
+
+def vgg_layer_plan(layer_weights, cfg):
+    """The taps of a layer_weights mapping (or a sequence of (name, weight) pairs), checked: [(name, index, weight)] in the
+    order of the head, weight-0 layers dropped.  ValueError, naming the culprit: a name that is no conv of `cfg`, a
+    duplicate, a negative or non-finite weight, nothing left."""
+    names = vgg_conv_names(cfg)
+    pairs = list(layer_weights.items()) if hasattr(layer_weights, "items") else [tuple(p) for p in layer_weights]
+    seen, plan = set(), []
+    for name, weight in pairs:
+        if name not in names:
+            raise ValueError("vgg_layers: %r is not a VGG19 conv layer (conv1_1 .. conv5_4; relu* and pool* taps are not "
+                             "built)" % (name,))
+        if name in seen:
+            raise ValueError("vgg_layers: %r is named twice" % (name,))
+        seen.add(name)
+        try:
+            weight = float(weight)
+        except (TypeError, ValueError):
+            raise ValueError("vgg_layers: the weight %r of %r is not a number" % (weight, name))
+        if not 0.0 <= weight < float("inf"):
+            raise ValueError("vgg_layers: the weight %r of %r is not a non-negative finite number" % (weight, name))
+        if weight > 0.0:
+            plan.append((name, names[name], weight))
+    if not plan:
+        raise ValueError("vgg_layers: no layer with a positive weight")
+    return sorted(plan, key=lambda p: p[1])
+
+
+class _VggTap(torch.autograd.Function):
+    """One tapped layer (srk_vgg_tap_forward / _backward, one launch each): a, b the pre-activation maps of prediction and
+    target; writes row `row` of the term's workspace and returns (token, ya, yb) -- the token ties the row into
+    _VggTapFinish, ya / yb are what the head runs behind the tap (None for VGG_TAP_LAST).  a and b are what the backward
+    keeps.  The gradient goes to a only; the seed contract of the losses holds per tap (_declare_seed)."""
+
+    @staticmethod
+    def forward(ctx, a, b, mode, weight, row, rows, ws):
+        lib = _lib.load()
+        require_cuda(a, b)
+        if a.dim() != 4 or a.shape != b.shape:
+            raise RuntimeError("vgg_tap: maps %s and %s must be equal 4-D NCHW shapes" % (tuple(a.shape), tuple(b.shape)))
+        a, b = _nhwc(a), _nhwc(b.detach())
+        n, c, h, w = a.shape
+        ya = yb = None
+        if mode == _lib.VGG_TAP_POOL:
+            if h < 2 or w < 2:
+                raise RuntimeError("vgg_tap: a %d x %d map has no 2 x 2 window to pool" % (h, w))
+            ya, yb = _empty_cl(n, c, h // 2, w // 2, a), _empty_cl(n, c, h // 2, w // 2, a)
+        elif mode == _lib.VGG_TAP_RELU:
+            ya, yb = _empty_cl(n, c, h, w, a), _empty_cl(n, c, h, w, a)
+        check(lib.srk_vgg_tap_forward(ptr(a), ptr(b), n, h, w, c, mode, float(weight), int(row), int(rows), ptr(ws), ptr(ya),
+                                      ptr(yb), stream_ptr()), "srk_vgg_tap_forward")
+        ctx.mode, ctx.scale = mode, float(weight) / float(a.numel())
+        _declare_seed(ctx)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(a, b)
+        token = torch.empty((), dtype=torch.float32, device=a.device)   # (never read: it carries the graph edge)
+        if yb is not None:
+            ctx.mark_non_differentiable(yb)
+        return token, ya, yb
+
+    @staticmethod
+    def backward(ctx, g_token, g_ya, g_yb):
+        lib = _lib.load()
+        a, b = ctx.saved_tensors
+        n, c, h, w = a.shape
+        mode = ctx.mode if g_ya is not None else _lib.VGG_TAP_LAST   # nothing behind the tap was used
+        g_ya = _nhwc(g_ya) if mode != _lib.VGG_TAP_LAST else None
+        factor = None
+        if g_token is None:
+            coeff = 0.0
+        elif _is_own_seed(ctx, g_token, a.device):     # c is known on the host: the seed is folded in here
+            coeff = ctx.scale * ctx.seed_value
+        else:                                          # a foreign gradient multiplies the unseeded c on the device
+            coeff, factor = ctx.scale, g_token.to(torch.float32).contiguous()
+        da = _empty_cl(n, c, h, w, a)
+        check(lib.srk_vgg_tap_backward(ptr(a), ptr(b), ptr(g_ya), n, h, w, c, mode, coeff, ptr(factor), ptr(da),
+                                       stream_ptr()), "srk_vgg_tap_backward")
+        return da, None, None, None, None, None, None
+
+
+def vgg_tap(a, b, mode, weight, row, rows, ws):
+    """One tap of the multi-layer VGG feature loss: see _VggTap.  mode: _lib.VGG_TAP_POOL / _RELU / _LAST; ws: the uint8
+    workspace of srk_vgg_tap_workspace_bytes(rows) bytes that the term's taps share."""
+    return _VggTap.apply(a, b, int(mode), float(weight), int(row), int(rows), ws)
+
+
+class _VggTapFinish(torch.autograd.Function):
+    """The rows of the term's workspace added in order (one launch): sum_k w_k * mean_k as a 0-dim fp32 tensor.  The
+    backward hands its upstream gradient to every tap as it came, so each tap recognises its own seed."""
+
+    @staticmethod
+    def forward(ctx, ws, rows, *tokens):
+        lib = _lib.load()
+        loss = torch.empty((), dtype=torch.float32, device=ws.device)
+        check(lib.srk_vgg_tap_finish(ptr(ws), int(rows), ptr(loss), stream_ptr()), "srk_vgg_tap_finish")
+        ctx.k = len(tokens)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        return (None, None) + (g,) * ctx.k
+
+
+def vgg_tap_finish(ws, rows, tokens):
+    return _VggTapFinish.apply(ws, int(rows), *tokens)
+
+
+def vgg_feature_loss(pred, target, extractor, layer_weights, normalize=True, criterion='l1'):
+    """Real-ESRGAN's feature term: sum_k w_k * L1(f_k(norm(pred)), f_k(norm(target))), f_k the VGG19 map of layer k BEFORE
+    its ReLU, as a 0-dim fp32 device tensor with the seed contract of the losses (_declare_seed); ops.weighted_term and
+    ops.loss_sum take it like any other.  layer_weights: an ordered mapping {'conv1_2': 0.1, ...} of conv names of
+    extractor.VGG19_CFG (vgg_layer_plan says what is refused; a weight of 0 drops the layer).  Prediction and target walk
+    the head in lockstep (extractor.tap_walk), the target without a graph on the same kernels, so equal inputs give exactly
+    0.0 and a zero gradient; each tapped layer is one fused launch each way (vgg_tap) and one more launch adds the rows.
+    The gradient flows to pred only.  Only the L1 criterion is built.  pred / target: [N, 3, H, W]; extractor:
+    models.FeatureExtractor reaching the deepest named layer."""
+    from . import utils
+    if criterion != 'l1':
+        raise ValueError("vgg_feature_loss: criterion = %r is not built, only 'l1' is" % (criterion,))
+    plan = vgg_layer_plan(layer_weights, extractor.VGG19_CFG)
+    for name, t in (("pred", pred), ("target", target)):
+        if not torch.is_tensor(t) or t.dim() != 4 or t.shape[1] != 3:
+            raise ValueError("vgg_feature_loss: %s must be [N, 3, H, W] (the VGG head reads RGB), got %s"
+                             % (name, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+    if pred.shape != target.shape:
+        raise ValueError("vgg_feature_loss: pred %s vs target %s" % (tuple(pred.shape), tuple(target.shape)))
+    if plan[-1][1] >= len(extractor.features):
+        raise ValueError("vgg_feature_loss: %r is layer %d of the head, the extractor keeps %d (FeatureExtractor("
+                         "feature_layer=%d))" % (plan[-1][0], plan[-1][1], len(extractor.features), plan[-1][1]))
+    with torch.no_grad():
+        t = target.detach()
+        b = utils.norm(t, vgg=True) if normalize else t
+    a = utils.norm(pred, vgg=True) if normalize else pred
+    return extractor.tap_walk(a, b, [(idx, weight) for _, idx, weight in plan])
+
+
 def grad_enabled_for(*tensors):
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 

@@ -120,6 +120,41 @@ def check_lpips_args(args, kind):
         raise ValueError("lpips_vgg: LPIPS reads RGB (main.py --num_channels 3)")
 
 
+def parse_vgg_layers(spec):
+    """--vgg_layers of main.py: `name:weight,...` or the word `realesrgan` (Real-ESRGAN's five taps, ops.
+    REALESRGAN_VGG_LAYERS), or a mapping / pair sequence given in code.  -> ops.vgg_layer_plan's [(name, index, weight)],
+    None for no spec.  ValueError naming the culprit."""
+    if spec is None:
+        return None
+    if isinstance(spec, str):
+        if spec.strip().lower() == "realesrgan":
+            pairs = list(ops.REALESRGAN_VGG_LAYERS)
+        else:
+            pairs = []
+            for item in spec.split(","):
+                name, sep, weight = item.strip().partition(":")
+                if not sep or not name.strip() or not weight.strip():
+                    raise ValueError("vgg_layers: %r is not name:weight (main.py --vgg_layers conv1_2:0.1,... or "
+                                     "realesrgan)" % (item,))
+                pairs.append((name.strip(), weight.strip()))
+    else:
+        pairs = spec
+    return ops.vgg_layer_plan(pairs, models.FeatureExtractor.VGG19_CFG)
+
+
+def check_vgg_layers_args(args, kind):
+    """--vgg_layers belongs to ESRGAN's adversarial phase and needs the VGG19 weights.  Raises ValueError naming the
+    flag.  -> the parsed plan, None without the flag."""
+    spec = getattr(args, "vgg_layers", None)
+    if spec is None:
+        return None
+    if kind != "esrgan":
+        raise ValueError("vgg_layers: only ESRGAN has the multi-layer VGG feature term (main.py --model_name ESRGAN)")
+    if not getattr(args, "vgg_weights", None):
+        raise ValueError("vgg_layers: needs the VGG19 weights to extract features with (main.py --vgg_weights PATH)")
+    return parse_vgg_layers(spec)
+
+
 DISCRIMINATORS = ("vgg", "unet")
 
 
@@ -202,6 +237,7 @@ class _Trainer(object):
             raise ValueError("fft_weight: %s has no frequency-domain term (main.py --fft_weight)" % self.model_name)
         check_perceptual_args(args, self.kind)
         check_lpips_args(args, self.kind)
+        self.vgg_layers = check_vgg_layers_args(args, self.kind)
         self.disc_args = check_discriminator_args(args, self.kind)
         check_data_flags(args)
         self.ema_decay = optim._check_ema_decay(getattr(args, "ema_decay", 0.0))
@@ -1053,9 +1089,11 @@ class ESRGAN(SRGAN):
         return trainers.l1_step(self.G, g_opt, g_dp)
 
     def _adversarial_step(self, g_opt, d_opt, g_dp, d_dp):
-        fe = models.FeatureExtractor(feature_layer=34).load_vgg19(self.args.vgg_weights).to(self.device)
+        layers = self.vgg_layers
+        deepest = 34 if layers is None else max(idx for _, idx, _ in layers)
+        fe = models.FeatureExtractor(feature_layer=deepest).load_vgg19(self.args.vgg_weights).to(self.device)
         return trainers.esrgan_step(self.G, self.D, g_opt, d_opt, fe, self.pixel_weight, self.vgg_weight, self.gan_weight,
-                                    self.gan_type)
+                                    self.gan_type, None if layers is None else [(name, w) for name, _, w in layers])
 
     def train(self, loader=None, pretrain_epochs=None, log_every=0):
         if not getattr(self.args, "vgg_weights", None):

@@ -327,17 +327,17 @@ def srgan_segments(G, D, g_opt, d_opt, g_dp=None, d_dp=None, lazy_pack=False, fe
 
 
 def esrgan_step(G, D, g_opt, d_opt, feature_extractor, pixel_weight=1e-2, vgg_weight=1.0, gan_weight=5e-3,
-                gan_type='ragan'):
+                gan_type='ragan', vgg_layers=None):
     """The adversarial step of ESRGAN as the eager closure of `esrgan_segments` (see there)."""
     return eager_step(esrgan_segments(G, D, g_opt, d_opt, feature_extractor, pixel_weight, vgg_weight, gan_weight,
-                                      gan_type))
+                                      gan_type, vgg_layers))
 
 
 GAN_TYPES = ("ragan", "vanilla")
 
 
 def esrgan_segments(G, D, g_opt, d_opt, feature_extractor, pixel_weight=1e-2, vgg_weight=1.0, gan_weight=5e-3,
-                    gan_type='ragan'):
+                    gan_type='ragan', vgg_layers=None):
     """ESRGAN's adversarial step (Wang et al., ECCV-W 2018) in the order BasicSR's model runs it, for batches in [0, 1]:
       G step, D's parameters frozen:   fake = G(lr)
           g_loss = pixel_weight * L1(fake, hr) + vgg_weight * L1(vgg(norm(fake)), vgg(norm(hr)))
@@ -354,7 +354,10 @@ def esrgan_segments(G, D, g_opt, d_opt, feature_extractor, pixel_weight=1e-2, vg
     ops.gan_logit_loss on D's logits of any shape,
       G step, D frozen:   gan_weight * gan(D(fake), real)            (D(hr) is not evaluated)
       D step:             d_loss = gan(D(hr), real) + gan(D(fake.detach()), fake), the sum and not the half.
-    A U-Net discriminator's logit map is refused with 'ragan' (gan_type: the relativistic loss takes one logit a sample)."""
+    A U-Net discriminator's logit map is refused with 'ragan' (gan_type: the relativistic loss takes one logit a sample).
+    vgg_layers (None: the single conv5_4 term above): an ordered mapping {'conv1_2': 0.1, ...}; the feature term is then
+    Real-ESRGAN's, vgg_weight * ops.vgg_feature_loss(fake, hr, feature_extractor, vgg_layers), and the extractor must reach
+    the deepest named layer."""
     from . import models
     if gan_type not in GAN_TYPES:
         raise ValueError("esrgan step: gan_type %r is not one of %s" % (gan_type, ", ".join(GAN_TYPES)))
@@ -375,7 +378,12 @@ def esrgan_segments(G, D, g_opt, d_opt, feature_extractor, pixel_weight=1e-2, vg
         for p in d_params:
             p.requires_grad_(not flag)
 
+    if vgg_layers is not None:
+        vgg_layers = dict((name, w) for name, _, w in ops.vgg_layer_plan(vgg_layers, feature_extractor.VGG19_CFG))
+
     def percep(pred, target):
+        if vgg_layers is not None:
+            return ops.vgg_feature_loss(pred, target, feature_extractor, vgg_layers, normalize=True)
         return ops.perceptual_loss(pred, target, feature_extractor, normalize=True, criterion='l1')
 
     def gan_g(fake_logits, real_logits):

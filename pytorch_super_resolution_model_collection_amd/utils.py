@@ -130,6 +130,25 @@ class PerceptualLoss(torch.nn.Module):
         return ops.perceptual_loss(pred, target.to(pred.device), self.extractor, self.normalize)
 
 
+class VGGFeatureLoss(torch.nn.Module):
+    """Real-ESRGAN's multi-layer VGG feature loss as a training loss (ops.vgg_feature_loss): sum_k w_k * L1 of the VGG19
+    maps of layer k before its ReLU.  layer_weights: an ordered mapping {'conv1_2': 0.1, ...}, checked here;
+    extractor: models.FeatureExtractor reaching the deepest named layer (held as a sub-module, its parameters stay
+    frozen).  [N,3,H,W] CUDA tensors; the gradient reaches pred only."""
+
+    def __init__(self, layer_weights, extractor, normalize=True):
+        super(VGGFeatureLoss, self).__init__()
+        from . import ops
+        plan = ops.vgg_layer_plan(layer_weights, extractor.VGG19_CFG)
+        self.layer_weights = dict((name, weight) for name, _, weight in plan)
+        self.extractor = extractor
+        self.normalize = bool(normalize)
+
+    def forward(self, pred, target):
+        from . import ops
+        return ops.vgg_feature_loss(pred, target.to(pred.device), self.extractor, self.layer_weights, self.normalize)
+
+
 def save_img_name(img_num, save_dir='', is_training=False):
     """utils.py:126-130: the file a result image goes to."""
     return save_dir + ('/SR_result_epoch_{:d}' if is_training else '/SR_result_{:d}').format(img_num) + '.png'
