@@ -1235,6 +1235,53 @@ int srk_vgg_tap_forward_host(const float* a, const float* b, int N, int H, int W
 int srk_vgg_tap_backward_host(const float* a, const float* b, const float* g, int N, int H, int W, int C, int mode, double c,
                               float* da);
 
+/* ---- NIQE features on the device (csrc/niqe.hip, csrc/niqe_common.h) ---------------------------------------
+ * (Additive again: new entry points only, srk_version() and everything existing unchanged.)
+ * NIQE (Mittal, Soundararajan, Bovik 2013) as BasicSR's calculate_niqe states it -- written down from memory of that code,
+ * not checked against it; the yardstick is the numpy / scipy restatement in tests/niqe_ref.py.  The entry points make the
+ * [blocks, 36] natural-scene-statistics features of one picture; the 36 x 36 finish is the caller's (ops.niqe_finish).
+ * img: one picture [C, H, W], C in {1, 3}, read through element strides (c, h, w).  is_u8 == 0: fp32, each value quantised
+ *   by the byte rule of srk_float_to_u8_image, (uint8)(clamp(v, 0, 1) * 255.0f); is_u8 != 0: bytes, taken as they are.
+ * shave >= 0, block even in 8 .. 96.
+ * 1. Luma.  C == 3: Y = rint(16 + (65.481 R + 128.553 G + 24.966 B) / 255) on the bytes, in double, ties to even (BT.601
+ *    studio range; NOT the Pillow luma of SRK_SSIM_Y8).  C == 1: the byte.
+ * 2. Crop.  shave pixels off each side, then the top-left nh*block x nw*block pixels, nh = (H - 2 shave) / block, nw
+ *    likewise.  Nothing outside the crop is read again; every border rule below acts at the crop's edges.  nh * nw < 2 is
+ *    SRK_ERR_BAD_ARG.
+ * 3. Two scales s = 1, 2, block side b_s = block / s, on the plane P_s (P_1 = Y).  Window g[i] = exp(-(i - 3)^2 /
+ *    (2 (7/6)^2)), i = 0 .. 6, normalised to sum 1, separable, plane borders replicated.  mu = G P, sigma = sqrt(|G P^2 -
+ *    mu^2|), n = (P - mu) / (sigma + 1).
+ * 4. Per block B (b_s x b_s of n) five maps: m_0 = B, m_k = B * roll(B, shift_k), shifts (0,1), (1,0), (1,1), (1,-1) over
+ *    (rows, columns), circular INSIDE the block (numpy's roll).
+ * 5. Per map over its M = b_s^2 values: c_neg, q_neg = count and sum of squares of the values < 0; c_pos, q_pos of the
+ *    values > 0 (zeros belong to neither); a = sum |m|; q = sum m^2.
+ * 6. AGGD fit per map: ls = sqrt(q_neg / c_neg), rs = sqrt(q_pos / c_pos), gh = ls / rs, rhat = (a / M)^2 / (q / M),
+ *    rn = rhat (gh^3 + 1)(gh + 1) / (gh^2 + 1)^2, alpha = gam[argmin_j (r_gam[j] - rn)^2] (first index on a tie),
+ *    gam[j] = 0.2 + 0.001 j, j < SRK_NIQE_TABLE, r_gam = Gamma(2/gam)^2 / (Gamma(1/gam) Gamma(3/gam)),
+ *    beta_l = ls sqrt(Gamma(1/alpha) / Gamma(3/alpha)), beta_r likewise from rs.  c_neg == 0, c_pos == 0 or q == 0 makes
+ *    every feature of that map NaN.
+ * 7. 18 features per scale: [alpha_0, (beta_l0 + beta_r0) / 2], then per product map [alpha_k, (beta_rk - beta_lk)
+ *    Gamma(2/alpha_k) / Gamma(1/alpha_k), beta_lk, beta_rk].  features[blk][0..17] scale 1, [18..35] scale 2 of the block
+ *    at the same grid position, blk = by * nw + bx.
+ * 8. P_2 = shrink(P_1): MATLAB's antialiased bicubic at exactly 1/2, in double: output i reads inputs 2i - 3 .. 2i + 4
+ *    with the weights [-3, -9, 29, 111, 111, 29, -9, -3] / 256; out-of-range indices reflect with the edge sample
+ *    repeated (-1 -> 0, -2 -> 1, n -> n - 1).  Bytes times these weights add exactly in double, so P_2 does not depend on
+ *    the order of the two passes.  P_2 is not rounded.
+ * 9. sharpness (may be NULL): [blocks], the mean of scale 1's sigma over the block.
+ * tables: 3 * SRK_NIQE_TABLE doubles (srk_niqe_tables_host): r_gam, sqrt(Gamma(1/g) / Gamma(3/g)), Gamma(2/g) / Gamma(1/g);
+ *   on the device for srk_niqe_features, on the host for srk_niqe_features_host.
+ * workspace: srk_niqe_workspace_bytes(H, W, block) bytes, 8-byte aligned (holds P_2, fp64; 0 for bad sizes).
+ * Two launches a picture; all arithmetic fp64; sums in a fixed order through per-thread, per-wave and per-block
+ * partials, no atomics: two calls on the same inputs return the same bits.
+ * srk_niqe_features_host: the same definition in plain C++ double on HOST pointers. */
+enum { SRK_NIQE_TABLE = 9801, SRK_NIQE_FEATURES = 36 };
+int srk_niqe_tables_host(double* out);
+size_t srk_niqe_workspace_bytes(int H, int W, int block);
+int srk_niqe_features(const void* img, int is_u8, const int64_t* strides, int C, int H, int W, int shave, int block,
+                      const double* tables, double* features, double* sharpness, void* workspace, void* stream);
+int srk_niqe_features_host(const void* img, int is_u8, const int64_t* strides, int C, int H, int W, int shave, int block,
+                           const double* tables, double* features, double* sharpness);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,9 @@ Poisson noise and JPEG, twice, then a sinc filter, every stage a kernel on 8-bit
 Degradation2's keywords), --usm (the training target and the degradation's input are the patches sharpened by
 Real-ESRGAN's USMSharp; also with --degrade or alone) and --degrade2_test SEED (every test image under its own seeded chain);
 image folders only; not with --degrade or --jpeg_quality.
+--niqe_params PATH (an .npz with mu_pris_param and cov_pris_param): test() also reports NIQE (ops.niqe, on the device; no
+ground truth) of the net's 8-bit output -- ' NIQE %.4f' on the --test_only line, a second line after --test_single.
+--niqe_fit DIR --niqe_params OUT fits such a file from the pictures of DIR and exits.
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N main.py ..."""
 import argparse
 import os
@@ -460,7 +463,29 @@ def parse_args(argv=None):
                         'name:weight,... over VGG19 conv layers taken before their ReLUs (conv1_1 .. conv5_4), or the word '
                         'realesrgan = conv1_2:0.1,conv2_2:0.1,conv3_4:1,conv4_4:1,conv5_4:1.  Needs --vgg_weights; the whole '
                         'term is weighed by --vgg_loss_weight')
+    p.add_argument('--niqe_params', type=str, default=None, metavar='PATH',
+                   help='NIQE\'s pristine model, an .npz with mu_pris_param [36] and cov_pris_param [36, 36] (BasicSR\'s '
+                        'niqe_pris_params.npz, or one written by --niqe_fit): test() also reports NIQE (Mittal et al. 2013; '
+                        'ops.niqe, on the device, no ground truth needed) of the net\'s 8-bit output, --eval_shave pixels off '
+                        'each side; --test_only appends it to its line, --test_single prints it on a second line.  With '
+                        '--niqe_fit: the file to write')
+    p.add_argument('--niqe_fit', type=str, default=None, metavar='DIR',
+                   help='fit NIQE\'s pristine model from the image files of DIR (blocks of 96 x 96 sharper than 0.75 of '
+                        'each picture\'s sharpest), write it to --niqe_params OUT (which must not exist), print the number '
+                        'of blocks used and exit.  Goes with no other mode flag')
     args = p.parse_args(argv)
+    if args.niqe_fit is not None:
+        if not args.niqe_params:
+            p.error('--niqe_fit DIR needs --niqe_params OUT, the .npz file to write')
+        for flag in ('test_only', 'test_single', 'resume', 'save_test_images'):
+            if getattr(args, flag):
+                p.error('--niqe_fit fits a parameter file and exits: it does not go with --%s' % flag)
+        if not os.path.isdir(args.niqe_fit):
+            p.error('--niqe_fit %s: no such directory' % args.niqe_fit)
+        if os.path.exists(args.niqe_params):
+            p.error('--niqe_params %s exists: --niqe_fit does not overwrite a parameter file' % args.niqe_params)
+    elif args.niqe_params is not None and not os.path.isfile(args.niqe_params):
+        p.error('--niqe_params %s: no such file' % args.niqe_params)
     esrgan = args.model_name == 'ESRGAN'
     if args.vgg_layers is not None:
         if not esrgan:
@@ -615,15 +640,33 @@ def report(net, args):
         lp = getattr(net, 'test_lpips', None) if getattr(args, 'lpips_vgg', None) else None
         if lp is not None:
             parts[0] += ' LPIPS %.4f' % lp.get(name, float('nan'))
+        nq = getattr(net, 'test_niqe', None) if getattr(args, 'niqe_params', None) else None
+        if nq is not None:
+            parts[0] += ' NIQE %.4f' % nq.get(name, float('nan'))
         if args.save_test_images and name in net.test_bicubic_psnr:
             parts.insert(0, 'bicubic PSNR %.4f SSIM %.4f' % (net.test_bicubic_psnr[name],
                                                             net.test_bicubic_ssim.get(name, float('nan'))))
             if lp is not None:
                 parts[0] += ' LPIPS %.4f' % getattr(net, 'test_bicubic_lpips', {}).get(name, float('nan'))
+            if nq is not None:
+                parts[0] += ' NIQE %.4f' % getattr(net, 'test_bicubic_niqe', {}).get(name, float('nan'))
         ev = getattr(net, 'test_eval', {}).get(name)
         if ev:
             parts.append('%s shave %d: PSNR %.4f SSIM %.4f' % (ev['domain'], ev['shave'], ev['psnr'], ev['ssim']))
         print('%s: %s' % (name, ', '.join(parts)))
+
+
+def niqe_fit(args):
+    """--niqe_fit DIR --niqe_params OUT: NIQE's own fit (utils.fit_niqe_params) over the image files of DIR."""
+    import torch
+    from pytorch_super_resolution_model_collection_amd import data, utils
+    names = sorted(f for f in os.listdir(args.niqe_fit) if data.is_image_file(f))
+    if not names:
+        raise SystemExit('--niqe_fit %s: no image files' % args.niqe_fit)
+    pictures = (torch.tensor(data.load_img(os.path.join(args.niqe_fit, f))).permute(2, 0, 1) for f in names)
+    mu_p, cov_p, rows = utils.fit_niqe_params(pictures)
+    utils.save_niqe_params(args.niqe_params, mu_p, cov_p)
+    print('NIQE parameters fitted from %d blocks of %d pictures: %s' % (rows, len(names), args.niqe_params))
 
 
 def main(argv=None):
@@ -633,11 +676,15 @@ def main(argv=None):
     import __graft_entry__
     __graft_entry__.build()
     import pytorch_super_resolution_model_collection_amd as pkg
+    if args.niqe_fit is not None:
+        return niqe_fit(args)
     from pytorch_super_resolution_model_collection_amd.sr_trainers import TRAINERS
     pkg.ops.set_precision(args.precision)
     net = TRAINERS[args.model_name](args)   # main.py:70-89
     if args.test_single:                     # main.py:102: net.test_single(img_fn)
         print(net.test_single(args.test_single))
+        if args.niqe_params:
+            print('NIQE %.4f' % net.test_single_niqe)
         return net
     if not args.test_only:
         net.train()                          # main.py:96

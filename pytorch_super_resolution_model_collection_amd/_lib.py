@@ -22,6 +22,7 @@ LOSS_MSE, LOSS_L1, LOSS_CHARBONNIER, LOSS_BCE = range(4)
 FFT_LOSS_MAX_DIM = 256   # SRK_FFT_LOSS_MAX_DIM
 VGG_TAP_POOL, VGG_TAP_RELU, VGG_TAP_LAST = range(3)   # srk_vgg_tap_mode
 SSIM_DOMAINS = {"float": 0, "u8": 1, "y8": 2}   # SRK_SSIM_FLOAT / _U8 / _Y8
+NIQE_TABLE, NIQE_FEATURES = 9801, 36   # SRK_NIQE_TABLE / SRK_NIQE_FEATURES
 ACT_BY_NAME = {None: ACT_NONE, "relu": ACT_RELU, "prelu": ACT_PRELU, "lrelu": ACT_LRELU, "tanh": ACT_TANH,
                "sigmoid": ACT_SIGMOID}
 
@@ -345,6 +346,10 @@ _PROTOTYPES = {
     "srk_vgg_tap_forward_host": (c_int, [c_vp, c_vp] + [c_int] * 5 + [ctypes.c_double, ctypes.POINTER(ctypes.c_double),
                                          c_vp, c_vp]),
     "srk_vgg_tap_backward_host": (c_int, [c_vp] * 3 + [c_int] * 5 + [ctypes.c_double, c_vp]),
+    "srk_niqe_tables_host": (c_int, [ctypes.POINTER(ctypes.c_double)]),
+    "srk_niqe_workspace_bytes": (c_size, [c_int] * 3),
+    "srk_niqe_features": (c_int, [c_vp, c_int, ctypes.POINTER(ctypes.c_int64)] + [c_int] * 5 + [c_vp] * 5),
+    "srk_niqe_features_host": (c_int, [c_vp, c_int, ctypes.POINTER(ctypes.c_int64)] + [c_int] * 5 + [c_vp] * 3),
 }
 
 _lib = None

@@ -3802,3 +3802,133 @@ def gelu(x):
     if x.numel() == 0:
         raise ValueError("gelu: empty tensor")
     return _Gelu.apply(x)
+
+
+# -------------------------------------------------------------------------------------------------------------------------
+# NIQE (Mittal, Soundararajan, Bovik 2013, as BasicSR's calculate_niqe states it; csrc/niqe.hip)
+# -------------------------------------------------------------------------------------------------------------------------
+_NIQE_TABLES = {}
+
+
+def niqe_tables_host():
+    """The three host-made tables of the AGGD fit as a float64 numpy array [3, 9801] over gam = 0.2 + 0.001 j: r_gam,
+    sqrt(Gamma(1/g) / Gamma(3/g)), Gamma(2/g) / Gamma(1/g).  include/srk.h: srk_niqe_tables_host."""
+    if "host" not in _NIQE_TABLES:
+        out = np.empty((3, _lib.NIQE_TABLE), dtype=np.float64)
+        check(_lib.load().srk_niqe_tables_host(out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))), "srk_niqe_tables_host")
+        _NIQE_TABLES["host"] = out
+    return _NIQE_TABLES["host"]
+
+
+def niqe_tables(device=None):
+    """niqe_tables_host() on the device, uploaded once per device."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if dev not in _NIQE_TABLES:
+        _NIQE_TABLES[dev] = torch.from_numpy(niqe_tables_host()).to(dev)
+    return _NIQE_TABLES[dev]
+
+
+def _niqe_picture(img, who):
+    """[C,H,W] (or [1,C,H,W]) float32 or uint8 of any strides -> (tensor [C,H,W], is_u8, (c, h, w) strides, C, H, W)."""
+    if img.dim() == 4 and img.shape[0] == 1:
+        img = img[0]
+    if img.dim() != 3 or img.shape[0] not in (1, 3):
+        raise ValueError("%s: takes one picture [C, H, W] with C in {1, 3}, got shape %s" % (who, tuple(img.shape)))
+    if img.dtype not in (torch.float32, torch.uint8):
+        raise ValueError("%s: takes a float32 or a uint8 picture, got %s" % (who, img.dtype))
+    img = img.detach()
+    strides = (ctypes.c_int64 * 3)(*[int(v) for v in img.stride()])
+    return img, int(img.dtype == torch.uint8), strides, int(img.shape[0]), int(img.shape[1]), int(img.shape[2])
+
+
+def niqe_blocks(h, w, shave=0, block=96):
+    """(nh, nw): the grid of block x block blocks NIQE reads of an h x w picture with `shave` pixels off each side."""
+    return max(int(h) - 2 * int(shave), 0) // int(block), max(int(w) - 2 * int(shave), 0) // int(block)
+
+
+def _niqe_check(h, w, shave, block, who):
+    shave, block = int(shave), int(block)
+    if shave < 0:
+        raise ValueError("%s: negative shave (%d)" % (who, shave))
+    if block % 2 or not 8 <= block <= 96:
+        raise ValueError("%s: block must be even and in 8 .. 96 (got %d)" % (who, block))
+    nh, nw = niqe_blocks(h, w, shave, block)
+    if nh * nw < 2:
+        raise ValueError("%s: a picture of %d x %d with %d pixels shaved from each side holds %d x %d blocks of %d x %d, "
+                         "fewer than 2" % (who, h, w, shave, nh, nw, block, block))
+    return shave, block, nh * nw
+
+
+def niqe_features(img, shave=0, block=96, sharpness=False):
+    """NIQE's natural-scene-statistics features of one picture on the device: a float64 device tensor [blocks, 36] (18
+    per scale; a block without both signs in a map holds NaNs there), and with sharpness=True also [blocks], the mean
+    local sigma of each block at scale 1.  img: [C, H, W], C in {1, 3}, on the device, read in place through its strides
+    -- float32 (quantised like to_u8_image on the way) or uint8.  Luma, crop, both scales and the AGGD fit run in two
+    launches; nothing syncs.  include/srk.h: srk_niqe_features."""
+    lib = _lib.load()
+    img, is_u8, strides, c, h, w = _niqe_picture(img, "niqe_features")
+    if not img.is_cuda:
+        raise RuntimeError("niqe_features: the picture must be on the device (got %s); niqe_features_host is the "
+                           "definition on host memory" % img.device)
+    if img.device.index != torch.cuda.current_device():
+        raise RuntimeError("niqe_features: tensor on %s but the current device is cuda:%d"
+                           % (img.device, torch.cuda.current_device()))
+    shave, block, blocks = _niqe_check(h, w, shave, block, "niqe_features")
+    tables = niqe_tables(img.device)
+    feats = torch.empty((blocks, _lib.NIQE_FEATURES), dtype=torch.float64, device=img.device)
+    sharp = torch.empty(blocks, dtype=torch.float64, device=img.device) if sharpness else None
+    ws = torch.empty(int(lib.srk_niqe_workspace_bytes(h, w, block)) // 8, dtype=torch.float64, device=img.device)
+    check(lib.srk_niqe_features(ptr(img), is_u8, strides, c, h, w, shave, block, ptr(tables), ptr(feats), ptr(sharp),
+                                ptr(ws), stream_ptr()), "srk_niqe_features")
+    return (feats, sharp) if sharpness else feats
+
+
+def niqe_features_host(img, shave=0, block=96, sharpness=False):
+    """niqe_features in plain C++ double on host memory (srk_niqe_features_host): img is a CPU tensor or a numpy array
+    [C, H, W], float32 or uint8, of any strides; returns numpy float64 arrays.  No device involved."""
+    lib = _lib.load()
+    if isinstance(img, np.ndarray):
+        img = torch.from_numpy(img)
+    img, is_u8, strides, c, h, w = _niqe_picture(img, "niqe_features_host")
+    if img.is_cuda:
+        raise RuntimeError("niqe_features_host: takes host memory, got a tensor on %s" % img.device)
+    shave, block, blocks = _niqe_check(h, w, shave, block, "niqe_features_host")
+    tables = niqe_tables_host()
+    feats = np.empty((blocks, _lib.NIQE_FEATURES), dtype=np.float64)
+    sharp = np.empty(blocks, dtype=np.float64) if sharpness else None
+    check(lib.srk_niqe_features_host(ctypes.c_void_p(img.data_ptr()), is_u8, strides, c, h, w, shave, block,
+                                     tables.ctypes.data_as(ctypes.c_void_p), feats.ctypes.data_as(ctypes.c_void_p),
+                                     sharp.ctypes.data_as(ctypes.c_void_p) if sharpness else None),
+          "srk_niqe_features_host")
+    return (feats, sharp) if sharpness else feats
+
+
+def niqe_finish(features, mu_p, cov_p):
+    """NIQE's score from the features of one picture and the pristine model (host, numpy, double): with mu = nanmean of
+    the rows and cov = np.cov of the rows without a NaN, sqrt((mu_p - mu) pinv((cov_p + cov) / 2) (mu_p - mu)^T).
+    features: [blocks, 36], a tensor (copied to the host here: the one sync) or an array."""
+    f = features.detach().cpu().numpy() if torch.is_tensor(features) else np.asarray(features)
+    f = np.asarray(f, dtype=np.float64)
+    mu_p = np.asarray(mu_p, dtype=np.float64).reshape(-1)
+    cov_p = np.asarray(cov_p, dtype=np.float64)
+    nf = _lib.NIQE_FEATURES
+    if f.ndim != 2 or f.shape[1] != nf or mu_p.shape != (nf,) or cov_p.shape != (nf, nf):
+        raise ValueError("niqe_finish: features %s, mu_p %s, cov_p %s are not [blocks, %d], [%d], [%d, %d]"
+                         % (f.shape, mu_p.shape, cov_p.shape, nf, nf, nf, nf))
+    good = f[~np.isnan(f).any(axis=1)]
+    if good.shape[0] < 2:
+        raise ValueError("niqe_finish: %d of %d blocks have features without a NaN, the covariance needs 2"
+                         % (good.shape[0], f.shape[0]))
+    mu = np.nanmean(f, axis=0)
+    cov = np.cov(good, rowvar=False)
+    d = mu_p - mu
+    return float(np.sqrt(d @ np.linalg.pinv((cov_p + cov) / 2.0) @ d))
+
+
+def niqe(img, params, shave=0, block=96):
+    """NIQE of one picture (lower is better): niqe_finish(niqe_features(img, shave, block), *params).  params: (mu_p,
+    cov_p), what utils.load_niqe_params / utils.fit_niqe_params return.  Syncs (the finish is host arithmetic)."""
+    mu_p, cov_p = params
+    return niqe_finish(niqe_features(img, shave, block), mu_p, cov_p)

@@ -275,6 +275,39 @@ class _Trainer(object):
             self._lpips = net.to(self.device).eval()
         return getattr(self, "_lpips", None)
 
+    def niqe_params(self):
+        """(mu_p, cov_p) of --niqe_params (utils.load_niqe_params), read once; None without the flag."""
+        if getattr(self, "_niqe", None) is None and getattr(self.args, "niqe_params", None):
+            self._niqe = utils.load_niqe_params(self.args.niqe_params)
+        return getattr(self, "_niqe", None)
+
+    @staticmethod
+    def _niqe_features(img, shave):
+        """ops.niqe_features of one picture ([1,C,H,W] / [C,H,W] float, or [H,W,3] / [H,W] uint8 as the picture tail
+        writes it) as a device tensor, or None where NIQE does not apply: fewer than two 96 x 96 blocks, or channels
+        other than 1 or 3."""
+        if img.dtype == torch.uint8:
+            img = img.unsqueeze(0) if img.dim() == 2 else img.permute(2, 0, 1)
+        else:
+            img = (img[0] if img.dim() == 4 else img).float()
+        nh, nw = ops.niqe_blocks(img.shape[1], img.shape[2], shave)
+        if img.shape[0] not in (1, 3) or nh * nw < 2:
+            return None
+        return ops.niqe_features(img, shave)
+
+    @staticmethod
+    def _niqe_mean(feats, params):
+        """Mean NIQE over the pictures whose features are given (None entries and pictures with fewer than two NaN-free
+        blocks are left out); None when none is left."""
+        vals = []
+        for f in feats:
+            if f is not None:
+                try:
+                    vals.append(ops.niqe_finish(f, *params))
+                except ValueError:
+                    pass
+        return sum(vals) / len(vals) if vals else None
+
     # -- training state: save at epoch boundaries, continue with --resume --------------------------------------------
     def _state_name(self):
         model_dir = os.path.join(self.save_dir, 'model')
@@ -627,7 +660,12 @@ class _Trainer(object):
         protocol of published tables.  The returned list and test_psnr do not depend on either.
         With the LPIPS weights (args.lpips_vgg / args.lpips_lin) `self.test_lpips` holds the per-dataset averages of
         ops.lpips of the same two float tensors PSNR sees (unshaved, unclamped; a pair under 16 on a side is left out), and
-        with save_images `self.test_bicubic_lpips` the bicubic image's."""
+        with save_images `self.test_bicubic_lpips` the bicubic image's.
+        With args.niqe_params (a parameter file, utils.load_niqe_params) `self.test_niqe` holds the per-dataset mean of
+        the NIQE of the net's outputs (ops.niqe_features on the 8-bit picture of each output, eval_shave pixels off each
+        side, else 0; no target involved, so a pair of unequal shapes counts too; a picture with fewer than two 96 x 96
+        blocks, or fewer than two blocks without a NaN, is left out), and with save_images `self.test_bicubic_niqe` the
+        bicubic image's.  The features stay on the device inside the loop; the 36 x 36 finish runs after it."""
         if self.model is None:
             self.model = self.build_model().to(self.device)
             self.load_model()
@@ -661,6 +699,11 @@ class _Trainer(object):
                 return None
             with torch.no_grad():
                 return ops.lpips(a.float(), b.float(), lpips_net, normalize=True, reduce=True)
+        niqe_params = self.niqe_params()
+        if niqe_params is not None:
+            self.test_niqe = {}
+            if save_images:
+                self.test_bicubic_niqe = {}
         if save_images:
             self.test_bicubic_psnr, self.test_bicubic_ssim = {}, {}
             if lpips_net is not None:
@@ -671,12 +714,15 @@ class _Trainer(object):
             mine, mine_ssim, mine_eval = [], [], []
             bicubic, bicubic_ssim, img_num = [], [], 0
             mine_lpips, bicubic_lpips = [], []
+            mine_niqe, bicubic_niqe = [], []
             for batch in batches:
                 items = [batch] if torch.is_tensor(batch[0]) else list(zip(*batch))   # ragged test images come as lists
                 for item in items:
                     lr_img, hr_img = self._channels(*[t if t.dim() == 4 else t.unsqueeze(0) for t in item[:2]])
                     out = self._forward(lr_img.to(self.device), tile, self_ensemble=self_ensemble)
                     tgt = hr_img.to(self.device)
+                    if niqe_params is not None:
+                        mine_niqe.append(self._niqe_features(out, eval_shave))
                     if self.kind == "srcnn":     # srcnn.py:193-199: border pixels excluded
                         tgt = utils.shave(tgt, 8)
                     if out.shape == tgt.shape:
@@ -691,6 +737,8 @@ class _Trainer(object):
                         utils.save_img(out[0], img_num, save_dir=os.path.join(self.save_dir, 'test_result', str(name)))
                         if len(item) > 2:
                             bc_img = self._channels(item[2] if item[2].dim() == 4 else item[2].unsqueeze(0))[0]
+                            if niqe_params is not None:
+                                bicubic_niqe.append(self._niqe_features(bc_img.to(self.device), eval_shave))
                             if bc_img.shape == hr_img.shape:
                                 bicubic.append(utils.PSNR(bc_img.to(self.device), hr_img.to(self.device)))
                                 if fits(bc_img):
@@ -710,6 +758,11 @@ class _Trainer(object):
                 if vals_dev:
                     svals = [float(v) for v in torch.stack(vals_dev).cpu()]
                     into[name] = sum(svals) / len(svals)
+            if niqe_params is not None:
+                for feats, into in ((mine_niqe, self.test_niqe), (bicubic_niqe, getattr(self, 'test_bicubic_niqe', None))):
+                    mean = self._niqe_mean(feats, niqe_params)
+                    if mean is not None:
+                        into[name] = mean
             if mine_eval:
                 ev = torch.stack(mine_eval).double().cpu()
                 self.test_eval[name] = {'domain': eval_domain, 'shave': eval_shave,
@@ -770,7 +823,13 @@ class _Trainer(object):
         else:
             x = ops.resize_u8(rgb.permute(2, 0, 1), h, w, out_float=True).unsqueeze(0)   # ToTensor: planar, / 255
         ens = self._self_ensemble(self_ensemble)
-        return self._save_single(self._run(self._net_input(x), tile, tile_batch, ens, as_u8=True, chroma=chroma))
+        img8 = self._run(self._net_input(x), tile, tile_batch, ens, as_u8=True, chroma=chroma)
+        niqe_params = self.niqe_params()
+        if niqe_params is not None:   # of the very bytes the file gets (the colour-restored picture of a Y model)
+            shave = getattr(self.args, 'eval_shave', None) or 0
+            mean = self._niqe_mean([self._niqe_features(img8, int(shave))], niqe_params)
+            self.test_single_niqe = float('nan') if mean is None else mean
+        return self._save_single(img8)
 
     def _save_single(self, img8):
         from PIL import Image

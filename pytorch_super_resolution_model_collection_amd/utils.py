@@ -60,6 +60,80 @@ def SSIM(pred, gt, shave=0, domain='float'):
     return ops.ssim(pred.float(), gt.to(pred.device).float(), shave, domain)[0]
 
 
+def load_niqe_params(path):
+    """The pristine model of NIQE from an .npz file: (mu_p [36], cov_p [36, 36]) as float64 arrays.  Keys: `mu_pris_param`
+    ([36] or [1, 36]) and `cov_pris_param` -- the names BasicSR's niqe_pris_params.npz uses as remembered, not checked
+    against that file; a `gaussian_window` key is ignored (the window is the kernel's own).  A missing key is named."""
+    import numpy as np
+    with np.load(os.fspath(path), allow_pickle=False) as f:
+        missing = [k for k in ('mu_pris_param', 'cov_pris_param') if k not in f.files]
+        if missing:
+            raise KeyError("%s: no key %s (a NIQE parameter file holds mu_pris_param and cov_pris_param; it has %s)"
+                           % (path, ' and '.join(repr(k) for k in missing), sorted(f.files)))
+        mu, cov = np.asarray(f['mu_pris_param'], dtype=np.float64), np.asarray(f['cov_pris_param'], dtype=np.float64)
+    if mu.size != 36 or cov.shape != (36, 36):
+        raise ValueError("%s: mu_pris_param %s and cov_pris_param %s are not [36] (or [1, 36]) and [36, 36]"
+                         % (path, mu.shape, cov.shape))
+    return mu.reshape(36), cov
+
+
+def save_niqe_params(path, mu_p, cov_p):
+    """Write (mu_p, cov_p) as the .npz load_niqe_params reads (mu_pris_param as [1, 36])."""
+    import numpy as np
+    np.savez(os.fspath(path), mu_pris_param=np.asarray(mu_p, dtype=np.float64).reshape(1, 36),
+             cov_pris_param=np.asarray(cov_p, dtype=np.float64).reshape(36, 36))
+
+
+def pool_niqe_rows(per_picture, sharp=0.75):
+    """NIQE's own fit from (features [blocks, 36], sharpness [blocks]) pairs, one per pristine picture: per picture the
+    rows whose sharpness exceeds `sharp` times the picture's maximum and that hold no NaN are kept; returns (mu_p, cov_p,
+    rows used) with mu_p the mean and cov_p np.cov of the pooled rows.  Fewer than 37 pooled rows is an error (a 36 x 36
+    covariance of fewer is singular by construction)."""
+    import numpy as np
+    rows = []
+    for feats, sharpness in per_picture:
+        f = feats.detach().cpu().numpy() if torch.is_tensor(feats) else np.asarray(feats)
+        s = sharpness.detach().cpu().numpy() if torch.is_tensor(sharpness) else np.asarray(sharpness)
+        rows.append(f[(s > float(sharp) * s.max()) & ~np.isnan(f).any(axis=1)])
+    rows = np.concatenate(rows) if rows else np.empty((0, 36))
+    if rows.shape[0] < 37:
+        raise ValueError("fit_niqe_params: %d blocks pass the sharpness rule, the 36 x 36 covariance needs at least 37 "
+                         "(more or larger pictures, or a smaller block)" % rows.shape[0])
+    return rows.mean(axis=0), np.cov(rows, rowvar=False), int(rows.shape[0])
+
+
+def fit_niqe_params(pictures, block=96, sharp=0.75, host=False):
+    """Fit NIQE's pristine model from pictures ([C,H,W] float32 or uint8 tensors, C in {1, 3}; moved to the current
+    device unless host=True, which runs the host twin instead): (mu_p, cov_p, rows used), see pool_niqe_rows.  A
+    picture with fewer than two blocks is an error that names its size."""
+    from . import ops
+    per = []
+    for img in pictures:
+        if host:
+            per.append(ops.niqe_features_host(img, 0, block, sharpness=True))
+        else:
+            img = torch.as_tensor(img)
+            per.append(ops.niqe_features(img if img.is_cuda else img.to("cuda"), 0, block, sharpness=True))
+    return pool_niqe_rows(per, sharp)
+
+
+class NIQE(torch.nn.Module):
+    """NIQE (ops.niqe; Mittal et al. 2013, no reference picture, lower is better) as a metric: forward(img) returns the
+    score of one picture [C,H,W] (float32 in [0, 1], read as the 8-bit picture save_img writes, or uint8) as a Python
+    float.  params: a path for load_niqe_params, or (mu_p, cov_p)."""
+
+    def __init__(self, params, shave=0, block=96):
+        super(NIQE, self).__init__()
+        self.params = load_niqe_params(params) if isinstance(params, (str, os.PathLike)) else (params[0], params[1])
+        self.shave, self.block = int(shave), int(block)
+
+    def forward(self, img):
+        from . import ops
+        if not img.is_cuda:
+            img = img.to("cuda")
+        return ops.niqe(img, self.params, self.shave, self.block)
+
+
 class SSIMLoss(torch.nn.Module):
     """1 - SSIM(pred, target) as a training loss (ops.ssim_loss: the prediction unclamped, float domain, loss and gradient
     from one kernel launch); [N,C,H,W] CUDA tensors with planes of at least 11 x 11."""
