@@ -1282,6 +1282,37 @@ int srk_niqe_features(const void* img, int is_u8, const int64_t* strides, int C,
 int srk_niqe_features_host(const void* img, int is_u8, const int64_t* strides, int C, int H, int W, int shave, int block,
                            const double* tables, double* features, double* sharpness);
 
+/* ---- raw video frames (YUV4MPEG2 payloads) to the net and back (csrc/video.hip, csrc/video_common.h) ----------------
+ * (Added without a change of srk_version(): new entry points only, nothing existing changed.)
+ * A frame is planar and 8-bit: Y [H][W], then for SRK_YUV_420 Cb and Cr [H/2][W/2] (H and W even: an odd size is refused),
+ * for SRK_YUV_444 Cb and Cr [H][W], for SRK_YUV_MONO nothing; all dense.  N frames lie frame_stride bytes apart
+ * (>= the frame's bytes) and may start at any address.  Samples are full-range JFIF values; the colour conversions are
+ * those of srk_ycc_to_rgb_u8 / srk_rgb_to_ycc_u8 (Pillow's tables), the quantisation srk_float_to_u8_image's.
+ * srk_yuv_unpack: frames -> out, dense fp32 [N][C][H][W], one launch.
+ *   C = 1: out = Y / 255.0f; the chroma is not read.
+ *   C = 3: R, G, B / 255.0f from Y and full-resolution Cb / Cr: the frame's own planes (444), the constant 128 (mono), or
+ *   chroma_full (420; dense 8-bit [2][N][H][W], all Cb planes then all Cr planes: what srk_img_resize_u8 makes of the
+ *   frames' chroma planes in two calls with plane_stride = frame_stride).  chroma_full is not read otherwise.
+ * srk_yuv_pack: x, fp32 [N][C][OH][OW] through four element strides (image, channel, row, pixel), -> N frames of OW x OH,
+ *   one launch.  Every value is quantised as (uint8)(min(max(v, 0), 1) * 255.0f); NaN gives 0.
+ *   C = 1: Y' = the quantised plane; chroma (dense 8-bit [2][N][ch][cw], ch x cw the frame's chroma size; not read for
+ *   mono) is copied into the frames' Cb and Cr slots.
+ *   C = 3: Y', Cb', Cr' from the quantised R, G, B.  444 writes all three, mono Y' only.  420 writes per 2 x 2 quad
+ *   (a b / c d) of Cb' (and of Cr') the sample (((a + b + 1) >> 1) + ((c + d + 1) >> 1) + 1) >> 1, which is Pillow's
+ *   resize((OW / 2, OH / 2), Image.BOX): it rounds after each pass, so this is not the four-sample mean.
+ * SRK_ERR_BAD_ARG before anything is launched: null pointer, a size <= 0, C not 1 or 3, an unknown sub, an odd 420 size,
+ *   frame_stride below the frame's bytes, negative strides, missing chroma planes.
+ * The _host twins are the same definitions on HOST pointers (they compile the kernels' per-pixel header). */
+enum { SRK_YUV_420 = 0, SRK_YUV_444 = 1, SRK_YUV_MONO = 2 };
+int srk_yuv_unpack(const uint8_t* frames, int64_t frame_stride, int N, int H, int W, int sub, int C,
+                   const uint8_t* chroma_full, float* out, void* stream);
+int srk_yuv_pack(const float* x, const int64_t* strides, int N, int C, int OH, int OW, int sub, const uint8_t* chroma,
+                 uint8_t* frames, int64_t frame_stride, void* stream);
+int srk_yuv_unpack_host(const uint8_t* frames, int64_t frame_stride, int N, int H, int W, int sub, int C,
+                        const uint8_t* chroma_full, float* out);
+int srk_yuv_pack_host(const float* x, const int64_t* strides, int N, int C, int OH, int OW, int sub, const uint8_t* chroma,
+                      uint8_t* frames, int64_t frame_stride);
+
 #ifdef __cplusplus
 }
 #endif

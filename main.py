@@ -55,6 +55,9 @@ image folders only; not with --degrade or --jpeg_quality.
 --niqe_params PATH (an .npz with mu_pris_param and cov_pris_param): test() also reports NIQE (ops.niqe, on the device; no
 ground truth) of the net's 8-bit output -- ' NIQE %.4f' on the --test_only line, a second line after --test_single.
 --niqe_fit DIR --niqe_params OUT fits such a file from the pictures of DIR and exits.
+--test_video IN [--video_out OUT] [--video_batch N] (load the checkpoint, super-resolve the YUV4MPEG2 stream IN -- 8-bit
+4:2:0, 4:4:4 or mono; - = stdin -- in batches of N frames from file bytes to file bytes on the device, write OUT, default
+<save_dir>/test_result/SR_result.y4m, - = stdout; honours --tile and --self_ensemble; no training).
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N main.py ..."""
 import argparse
 import os
@@ -330,6 +333,15 @@ def parse_args(argv=None):
     p.add_argument('--test_single', type=str, default=None, metavar='PATH',
                    help='no training: load the checkpoint, super-resolve this picture file (the Y channel with '
                         '--num_channels 1, colour restored from the bicubic Cb / Cr) and print the name of the PNG written')
+    p.add_argument('--test_video', type=str, default=None, metavar='IN',
+                   help='no training: load the checkpoint and super-resolve this YUV4MPEG2 stream (.y4m: 8-bit 4:2:0, 4:4:4 '
+                        'or mono, progressive; - = stdin, e.g. from ffmpeg -f yuv4mpegpipe) in batches on the device; '
+                        'honours --tile and --self_ensemble')
+    p.add_argument('--video_out', type=str, default=None, metavar='OUT',
+                   help='--test_video: where the super-resolved stream goes (- = stdout); default: '
+                        '<save_dir>/test_result/SR_result.y4m')
+    p.add_argument('--video_batch', type=int, default=8, metavar='N',
+                   help='--test_video: frames per batch (default 8)')
     p.add_argument('--save_test_images', action='store_true',
                    help='test(): write every result image to <save_dir>/test_result/<dataset>/ and report the bicubic PSNR')
     p.add_argument('--tile', type=_tile, default=None, metavar='N|auto',
@@ -474,6 +486,16 @@ def parse_args(argv=None):
                         'each picture\'s sharpest), write it to --niqe_params OUT (which must not exist), print the number '
                         'of blocks used and exit.  Goes with no other mode flag')
     args = p.parse_args(argv)
+    if args.test_video is not None:
+        for flag in ('test_only', 'test_single', 'resume', 'save_test_images', 'niqe_fit'):
+            if getattr(args, flag):
+                p.error('--test_video super-resolves a stream and exits: it does not go with --%s' % flag)
+        if args.test_video != '-' and not os.path.exists(args.test_video):   # a named pipe is a source too
+            p.error('--test_video %s: no such file' % args.test_video)
+        if args.video_batch <= 0:
+            p.error('--video_batch must be positive (got %d)' % args.video_batch)
+    elif args.video_out is not None:
+        p.error('--video_out goes with --test_video IN')
     if args.niqe_fit is not None:
         if not args.niqe_params:
             p.error('--niqe_fit DIR needs --niqe_params OUT, the .npz file to write')
@@ -673,6 +695,16 @@ def main(argv=None):
     args = parse_args(argv)
     if args is None:
         exit()
+    if args.test_video and args.video_out == '-':   # stdout carries the stream and nothing else: messages go to stderr
+        import contextlib
+        import sys
+        sink = sys.stdout.buffer
+        with contextlib.redirect_stdout(sys.stderr):
+            return run(args, sink)
+    return run(args)
+
+
+def run(args, video_sink=None):
     import __graft_entry__
     __graft_entry__.build()
     import pytorch_super_resolution_model_collection_amd as pkg
@@ -685,6 +717,9 @@ def main(argv=None):
         print(net.test_single(args.test_single))
         if args.niqe_params:
             print('NIQE %.4f' % net.test_single_niqe)
+        return net
+    if args.test_video:
+        net.test_video(args.test_video, video_sink if video_sink is not None else args.video_out, args.video_batch)
         return net
     if not args.test_only:
         net.train()                          # main.py:96

@@ -350,6 +350,10 @@ _PROTOTYPES = {
     "srk_niqe_workspace_bytes": (c_size, [c_int] * 3),
     "srk_niqe_features": (c_int, [c_vp, c_int, ctypes.POINTER(ctypes.c_int64)] + [c_int] * 5 + [c_vp] * 5),
     "srk_niqe_features_host": (c_int, [c_vp, c_int, ctypes.POINTER(ctypes.c_int64)] + [c_int] * 5 + [c_vp] * 3),
+    "srk_yuv_unpack": (c_int, [c_vp, ctypes.c_int64] + [c_int] * 5 + [c_vp] * 3),
+    "srk_yuv_pack": (c_int, [c_vp, ctypes.POINTER(ctypes.c_int64)] + [c_int] * 5 + [c_vp, c_vp, ctypes.c_int64, c_vp]),
+    "srk_yuv_unpack_host": (c_int, [c_vp, ctypes.c_int64] + [c_int] * 5 + [c_vp] * 2),
+    "srk_yuv_pack_host": (c_int, [c_vp, ctypes.POINTER(ctypes.c_int64)] + [c_int] * 5 + [c_vp, c_vp, ctypes.c_int64]),
 }
 
 _lib = None

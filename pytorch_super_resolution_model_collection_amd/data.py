@@ -1014,3 +1014,187 @@ class PatchLoader(object):
             else:   # test images differ in size: one item per batch entry, stacked only when they agree
                 items = [ds[i] for i in idx]
                 yield tuple(torch.stack(t) if len(set(x.shape for x in t)) == 1 else list(t) for t in zip(*items)), None
+
+
+# ------------------------------------------------------------------------------------------------
+# YUV4MPEG2 (.y4m): raw planar 8-bit video behind text headers -- the container of test_video.  It needs no codec
+# library, and `ffmpeg -f yuv4mpegpipe` reads and writes it through pipes.
+#   stream:  "YUV4MPEG2 W.. H.. [F..] [I..] [A..] [C..] [X..]*\n", then per frame "FRAME[ params]\n" + the payload
+#   payload: Y [H][W], then Cb and Cr (ops.yuv_layout is the one place that says where)
+# ------------------------------------------------------------------------------------------------
+Y4M_MAGIC = b"YUV4MPEG2"
+Y4M_CHROMA = {"C420jpeg": "420", "C420mpeg2": "420", "C420paldv": "420", "C420": "420", "C444": "444", "Cmono": "mono"}
+Y4M_INTERLACE = ("Ip", "I?")
+_Y4M_LINE_LIMIT = 4096
+
+
+class Y4MHeader(object):
+    """The stream header: W, H and the other tags as they came, in their order.  A missing C tag means C420jpeg.
+    Everything the kernels do not take is a ValueError that names the tag: 4:2:2, any depth above 8 bits, alpha,
+    interlaced material, an unknown tag."""
+
+    def __init__(self, tokens):
+        self.tokens = list(tokens)
+        self.W = self.H = None
+        self.chroma_tag = None
+        for t in self.tokens:
+            if t[:1] == "W" or t[:1] == "H":
+                if not t[1:].isdigit() or int(t[1:]) <= 0:
+                    raise ValueError("Y4M header: bad size tag %r" % t)
+                setattr(self, t[0], int(t[1:]))
+            elif t[:1] == "C":
+                if t not in Y4M_CHROMA:
+                    raise ValueError("Y4M header: chroma tag %r is not supported (8-bit %s only)" % (t, ", ".join(sorted(Y4M_CHROMA))))
+                self.chroma_tag = t
+            elif t[:1] == "I":
+                if t not in Y4M_INTERLACE:
+                    raise ValueError("Y4M header: interlacing tag %r is not supported (progressive %s only)"
+                                     % (t, " / ".join(Y4M_INTERLACE)))
+            elif t[:1] not in ("F", "A", "X"):
+                raise ValueError("Y4M header: unknown tag %r" % t)
+        if self.W is None or self.H is None:
+            raise ValueError("Y4M header: no %s tag" % ("W" if self.W is None else "H"))
+        self.layout = ops.yuv_layout(self.W, self.H, Y4M_CHROMA[self.chroma_tag or "C420jpeg"], self.chroma_tag or "C420jpeg")
+
+    @classmethod
+    def parse(cls, line):
+        if not line.endswith(b"\n"):
+            raise ValueError("Y4M header: no end of line within %d bytes (got %r...)" % (len(line), line[:32]))
+        parts = line[:-1].decode("ascii", "replace").split(" ")
+        if parts[0] != Y4M_MAGIC.decode():
+            raise ValueError("not a YUV4MPEG2 stream: it begins with %r" % line[:16])
+        return cls([p for p in parts[1:] if p])
+
+    def scaled(self, W, H):
+        """The header of the super-resolved stream: W and H replaced, every other tag (F, I, A, C, X) carried through."""
+        return Y4MHeader([("W%d" % W) if t[:1] == "W" else ("H%d" % H) if t[:1] == "H" else t for t in self.tokens])
+
+    def line(self):
+        return " ".join([Y4M_MAGIC.decode()] + self.tokens).encode("ascii") + b"\n"
+
+
+def _y4m_open(target, mode):
+    """(file object, whether we close it): a path, '-' (stdin / stdout, binary) or a binary file object."""
+    if hasattr(target, "read" if mode == "rb" else "write"):
+        return target, False
+    if os.fspath(target) == "-":
+        import sys
+        return (sys.stdin if mode == "rb" else sys.stdout).buffer, False
+    if mode == "wb" and os.path.dirname(os.fspath(target)):
+        os.makedirs(os.path.dirname(os.fspath(target)), exist_ok=True)
+    return open(target, mode), True
+
+
+def _y4m_bytes(buf):
+    """A writable flat byte view of a CPU uint8 tensor (pinned or not), a numpy array or any buffer object."""
+    if torch.is_tensor(buf):
+        if buf.dtype != torch.uint8 or buf.is_cuda or not buf.is_contiguous():
+            raise ValueError("Y4M: a frame buffer must be a dense uint8 tensor on the host")
+        buf = buf.numpy()
+    return memoryview(buf).cast("B")
+
+
+class Y4MReader(object):
+    """Streams a YUV4MPEG2 source (a pipe has no length): read_into(buf, n) copies up to n frame payloads straight into the
+    caller's buffer -- dense, frame k at byte k * layout.frame_bytes, so frames start at any alignment -- and returns how
+    many came (0: the stream has ended).  batches(buffers, n) walks the whole stream through rotating buffers."""
+
+    def __init__(self, src):
+        self.f, self._own = _y4m_open(src, "rb")
+        try:
+            self.header = Y4MHeader.parse(self.f.readline(_Y4M_LINE_LIMIT))
+        except Exception:
+            self.close()
+            raise
+        self.layout = self.header.layout
+        self.frames_read = 0
+
+    def _fill(self, view):
+        got = 0
+        readinto = getattr(self.f, "readinto", None)
+        while got < len(view):
+            if readinto is not None:
+                k = readinto(view[got:])
+            else:
+                chunk = self.f.read(len(view) - got)
+                k = len(chunk)
+                view[got:got + k] = chunk
+            if not k:
+                break
+            got += k
+        return got
+
+    def read_into(self, buf, max_frames=None):
+        view = _y4m_bytes(buf)
+        fb = self.layout.frame_bytes
+        room = len(view) // fb
+        n = room if max_frames is None else min(int(max_frames), room)
+        if n <= 0:
+            raise ValueError("Y4M: a buffer of %d bytes holds no frame of %d bytes" % (len(view), fb))
+        for k in range(n):
+            line = self.f.readline(_Y4M_LINE_LIMIT)
+            if not line:
+                return k
+            if line[:5] != b"FRAME" or line[5:6] not in (b" ", b"\n") or not line.endswith(b"\n"):
+                raise ValueError("Y4M: frame %d does not begin with a FRAME line (got %r)" % (self.frames_read, line[:16]))
+            got = self._fill(view[k * fb:(k + 1) * fb])
+            if got != fb:
+                raise ValueError("Y4M: frame %d ends early: got %d bytes, expected %d" % (self.frames_read, got, fb))
+            self.frames_read += 1
+        return n
+
+    def batches(self, buffers, n):
+        """Yields (buffer, frames) over the whole stream; the buffers rotate, so a yielded one is overwritten len(buffers)
+        batches later."""
+        i = 0
+        while True:
+            k = self.read_into(buffers[i % len(buffers)], n)
+            if k == 0:
+                return
+            yield buffers[i % len(buffers)], k
+            i += 1
+            if k < n:
+                return
+
+    def close(self):
+        if self._own:
+            self.f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class Y4MWriter(object):
+    """Writes `header` (a Y4MHeader; Y4MHeader.scaled makes the output side's), then per frame a bare "FRAME\\n" and the
+    payload.  write(buf, n) takes n dense frames from a buffer as Y4MReader.read_into fills it."""
+
+    def __init__(self, dst, header):
+        self.header, self.layout = header, header.layout
+        self.f, self._own = _y4m_open(dst, "wb")
+        self.f.write(header.line())
+        self.frames_written = 0
+
+    def write(self, buf, n=None):
+        view = _y4m_bytes(buf)
+        fb = self.layout.frame_bytes
+        n = len(view) // fb if n is None else int(n)
+        if n * fb > len(view):
+            raise ValueError("Y4M: %d frames of %d bytes do not fit a buffer of %d bytes" % (n, fb, len(view)))
+        for k in range(n):
+            self.f.write(b"FRAME\n")
+            self.f.write(view[k * fb:(k + 1) * fb])
+        self.frames_written += n
+
+    def close(self):
+        self.f.flush()
+        if self._own:
+            self.f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

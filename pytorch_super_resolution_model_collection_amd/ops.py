@@ -2217,10 +2217,11 @@ def to_u8_image(x):
     return out
 
 
-def resize_u8(planes_u8, oh, ow, interpolation="bicubic", out_float=False):
+def resize_u8(planes_u8, oh, ow, interpolation="bicubic", out_float=False, out=None):
     """Image.resize((ow, oh)) of 8-bit planes [P,H,W] (any strides: an interleaved [H,W,C] image is read in place through
     .permute(2, 0, 1)) on the device: srk_img_resize_u8, bit-exact with Pillow.  Returns uint8 [P,oh,ow], or with
-    out_float the fp32 planes value / 255 (ToTensor); an unchanged size makes that the plain ToTensor of the image."""
+    out_float the fp32 planes value / 255 (ToTensor); an unchanged size makes that the plain ToTensor of the image.
+    out: a dense tensor of that shape and type to write into (a slice of a larger buffer along the first axis is one)."""
     _require_u8("resize_u8", planes_u8)
     if planes_u8.dim() != 3:
         raise RuntimeError("resize_u8 expects [P,H,W] planes, got shape %s" % (tuple(planes_u8.shape),))
@@ -2229,7 +2230,13 @@ def resize_u8(planes_u8, oh, ow, interpolation="bicubic", out_float=False):
     p, h, w = (int(v) for v in planes_u8.shape)
     lib = _lib.load()
     flt = INTERP_BOX if interpolation == "box" else _INTERP[interpolation]
-    y = torch.empty((p, oh, ow), dtype=torch.float32 if out_float else torch.uint8, device=planes_u8.device)
+    y = out
+    if y is None:
+        y = torch.empty((p, oh, ow), dtype=torch.float32 if out_float else torch.uint8, device=planes_u8.device)
+    elif tuple(y.shape) != (p, oh, ow) or y.dtype != (torch.float32 if out_float else torch.uint8) or not y.is_contiguous() \
+            or y.device != planes_u8.device:
+        raise RuntimeError("resize_u8: out must be a dense %s [%d,%d,%d] tensor on %s"
+                           % ("fp32" if out_float else "uint8", p, oh, ow, planes_u8.device))
     nbytes = max(int(lib.srk_img_resize_u8_workspace_bytes(p, h, w, oh, ow, flt)), 256)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=planes_u8.device)
     st = [int(v) for v in planes_u8.stride()]
@@ -3932,3 +3939,173 @@ def niqe(img, params, shave=0, block=96):
     cov_p), what utils.load_niqe_params / utils.fit_niqe_params return.  Syncs (the finish is host arithmetic)."""
     mu_p, cov_p = params
     return niqe_finish(niqe_features(img, shave, block), mu_p, cov_p)
+
+
+# ------------------------------------------------------------------------------------------------
+# Raw video frames (YUV4MPEG2 payloads) to the net and back (csrc/video.hip): the front and the tail of test_video
+# ------------------------------------------------------------------------------------------------
+YUV_SUBSAMPLING = {"420": 0, "444": 1, "mono": 2}   # SRK_YUV_420 / SRK_YUV_444 / SRK_YUV_MONO (include/srk.h)
+
+
+class YuvLayout(object):
+    """Where the planes of one planar 8-bit frame lie: W, H, sub ('420', '444' or 'mono'), the chroma plane's size cw x
+    ch (0 x 0 for mono), the byte offsets y_off / cb_off / cr_off inside the frame and frame_bytes.  Made by yuv_layout
+    alone: the container (data.Y4MReader / Y4MWriter) and the kernels' launchers (yuv_unpack / yuv_pack) read the same
+    object."""
+    __slots__ = ("W", "H", "sub", "cw", "ch", "y_off", "cb_off", "cr_off", "frame_bytes")
+
+    def __init__(self, W, H, sub, cw, ch):
+        self.W, self.H, self.sub, self.cw, self.ch = W, H, sub, cw, ch
+        self.y_off, self.cb_off, self.cr_off = 0, W * H, W * H + cw * ch
+        self.frame_bytes = W * H + 2 * cw * ch
+
+    @property
+    def code(self):
+        return YUV_SUBSAMPLING[self.sub]
+
+    def scaled(self, W, H):
+        """The layout of a W x H frame of the same subsampling (the output side of a stream)."""
+        return yuv_layout(W, H, self.sub)
+
+    def __eq__(self, other):
+        return isinstance(other, YuvLayout) and (self.W, self.H, self.sub) == (other.W, other.H, other.sub)
+
+    def __repr__(self):
+        return "YuvLayout(%d x %d, %s, %d bytes)" % (self.W, self.H, self.sub, self.frame_bytes)
+
+
+def yuv_layout(W, H, sub="420", tag=None):
+    """The one derivation of a frame's layout.  Chroma planes of 4:2:0 are ceil(W/2) x ceil(H/2) by the format's
+    definition; a 4:2:0 frame with an odd W or H is refused by name (`tag`: the stream's own C tag for the message)."""
+    W, H = int(W), int(H)
+    if sub not in YUV_SUBSAMPLING:
+        raise ValueError("yuv_layout: subsampling must be '420', '444' or 'mono' (got %r)" % (sub,))
+    if W <= 0 or H <= 0:
+        raise ValueError("yuv_layout: a frame of %d x %d" % (W, H))
+    if sub == "420" and (W % 2 or H % 2):
+        raise ValueError("%s: a 4:2:0 frame of odd size W%d H%d is refused (its chroma planes would be ceil(W/2) x ceil(H/2) = "
+                         "%d x %d; the 2 x 2 shrink of the output has no definition there)"
+                         % (tag or "C420", W, H, (W + 1) // 2, (H + 1) // 2))
+    cw, ch = {"420": ((W + 1) // 2, (H + 1) // 2), "444": (W, H), "mono": (0, 0)}[sub]
+    return YuvLayout(W, H, sub, cw, ch)
+
+
+def _yuv_frames(what, frames, layout, n=None):
+    """frames: uint8 [N, >= frame_bytes] with dense bytes inside a frame (any frame stride, any first byte)."""
+    if frames.dtype != torch.uint8 or frames.dim() != 2 or frames.shape[0] == 0 or frames.shape[1] < layout.frame_bytes \
+            or frames.stride(1) != 1 or (frames.shape[0] > 1 and frames.stride(0) < layout.frame_bytes) \
+            or (n is not None and frames.shape[0] != n):
+        raise RuntimeError("%s: frames must be uint8 [%s, >= %d] with dense frames, got %s %s strides %s"
+                           % (what, "N" if n is None else n, layout.frame_bytes, frames.dtype, tuple(frames.shape),
+                              tuple(frames.stride())))
+    return int(frames.shape[0]), (int(frames.stride(0)) if frames.shape[0] > 1 else max(int(frames.stride(0)), layout.frame_bytes))
+
+
+def yuv_chroma(frames_u8, layout, oh, ow):
+    """The chroma planes of N packed frames through srk_img_resize_u8 (bicubic, centre-aligned: C420jpeg's siting) to
+    oh x ow: uint8 [2, N, oh, ow], all Cb planes then all Cr planes -- what yuv_unpack takes as chroma_full (oh x ow =
+    H x W) and yuv_pack as chroma (the output frame's chroma size).  The 2 N planes go in two calls: inside a frame Cb
+    and Cr lie cw * ch bytes apart, across frames frame_bytes, and the resizer takes one plane stride."""
+    _require_u8("yuv_chroma", frames_u8)
+    n, fs = _yuv_frames("yuv_chroma", frames_u8, layout)
+    if layout.sub == "mono":
+        raise RuntimeError("yuv_chroma: a mono stream has no chroma planes")
+    out = torch.empty((2, n, int(oh), int(ow)), dtype=torch.uint8, device=frames_u8.device)
+    for k, off in enumerate((layout.cb_off, layout.cr_off)):   # each call writes its half of the one buffer
+        planes = torch.as_strided(frames_u8, (n, layout.ch, layout.cw), (fs, layout.cw, 1), frames_u8.storage_offset() + off)
+        resize_u8(planes, int(oh), int(ow), out=out[k])
+    return out
+
+
+def yuv_unpack(frames_u8, layout, num_channels, chroma_full=None, out=None):
+    """N packed frames (uint8 [N, frame_bytes], any frame stride, any first byte) -> the net's input, fp32 [N,C,H,W], one
+    launch (k_yuv_unpack).  num_channels 1: Y / 255, the chroma is not read.  3: R, G, B / 255 through Pillow's YCbCr ->
+    RGB tables from Y and full-resolution chroma: the frame's own (4:4:4), 128 (mono), or for 4:2:0 chroma_full
+    ([2,N,H,W], None: yuv_chroma makes it here)."""
+    _require_u8("yuv_unpack", frames_u8)
+    n, fs = _yuv_frames("yuv_unpack", frames_u8, layout)
+    c = int(num_channels)
+    if c not in (1, 3):
+        raise RuntimeError("yuv_unpack: num_channels must be 1 or 3 (got %d)" % c)
+    if c == 3 and layout.sub == "420":
+        if chroma_full is None:
+            chroma_full = yuv_chroma(frames_u8, layout, layout.H, layout.W)
+        _require_u8("yuv_unpack", chroma_full)
+        if tuple(chroma_full.shape) != (2, n, layout.H, layout.W) or not chroma_full.is_contiguous():
+            raise RuntimeError("yuv_unpack: chroma_full must be a dense uint8 [2,%d,%d,%d] tensor, got %s"
+                               % (n, layout.H, layout.W, tuple(chroma_full.shape)))
+    else:
+        chroma_full = None
+    out = _f32_out("yuv_unpack", (n, c, layout.H, layout.W), frames_u8.device, out)
+    check(_lib.load().srk_yuv_unpack(ptr(frames_u8), fs, n, layout.H, layout.W, layout.code, c, ptr(chroma_full), ptr(out),
+                                     stream_ptr()), "srk_yuv_unpack")
+    return out
+
+
+def yuv_pack(y, layout, chroma=None, out=None):
+    """The net's output y (fp32 [N,C,OH,OW], any strides: a channels-last output is read in place) -> N packed frames of
+    `layout` (the OUTPUT frame: layout.H x layout.W = OH x OW), uint8 [N, frame_bytes], one launch.  Quantised like
+    to_u8_image.  C = 1: the Y' plane, and `chroma` (uint8 [2,N,ch,cw], yuv_chroma's; not for mono) copied into the Cb and
+    Cr slots.  C = 3: Pillow's RGB -> YCbCr tables; 4:2:0 shrinks the chroma like Image.resize(..., Image.BOX)."""
+    require_cuda(y)
+    y = y.detach()
+    if y.dim() != 4 or y.shape[1] not in (1, 3) or tuple(y.shape[2:]) != (layout.H, layout.W) or y.shape[0] == 0:
+        raise RuntimeError("yuv_pack: expects a [N,C,%d,%d] tensor with C = 1 or 3, got %s" % (layout.H, layout.W, tuple(y.shape)))
+    n, c = int(y.shape[0]), int(y.shape[1])
+    if c == 1 and layout.sub != "mono":
+        if chroma is None:
+            raise RuntimeError("yuv_pack: a one-channel output on a %s stream needs the resized chroma planes" % layout.sub)
+        _require_u8("yuv_pack", chroma)
+        if tuple(chroma.shape) != (2, n, layout.ch, layout.cw) or not chroma.is_contiguous():
+            raise RuntimeError("yuv_pack: chroma must be a dense uint8 [2,%d,%d,%d] tensor, got %s"
+                               % (n, layout.ch, layout.cw, tuple(chroma.shape)))
+    else:
+        chroma = None
+    if out is None:
+        out = torch.empty((n, layout.frame_bytes), dtype=torch.uint8, device=y.device)
+    _require_u8("yuv_pack", out)
+    _, fs = _yuv_frames("yuv_pack: out", out, layout, n)
+    check(_lib.load().srk_yuv_pack(ptr(y), _strides4(y), n, c, layout.H, layout.W, layout.code, ptr(chroma), ptr(out), fs,
+                                   stream_ptr()), "srk_yuv_pack")
+    return out
+
+
+def _np_ptr(a):
+    return None if a is None else ctypes.c_void_p(a.ctypes.data)
+
+
+def yuv_unpack_host(frames_u8, layout, num_channels, chroma_full=None):
+    """yuv_unpack on host memory (srk_yuv_unpack_host: the kernels' per-pixel header in plain C++): numpy uint8
+    [N, frame_bytes] (any frame stride) -> numpy float32 [N,C,H,W].  chroma_full ([2,N,H,W]) is the caller's for 4:2:0
+    with num_channels 3: there is no host resizer."""
+    f = np.asarray(frames_u8)
+    if f.dtype != np.uint8 or f.ndim != 2 or f.shape[1] < layout.frame_bytes or f.strides[1] != 1:
+        raise ValueError("yuv_unpack_host: frames must be uint8 [N, >= %d] with dense frames" % layout.frame_bytes)
+    n, c = int(f.shape[0]), int(num_channels)
+    if chroma_full is not None:
+        chroma_full = np.ascontiguousarray(chroma_full, dtype=np.uint8)
+        if chroma_full.shape != (2, n, layout.H, layout.W):
+            raise ValueError("yuv_unpack_host: chroma_full must be [2,%d,%d,%d]" % (n, layout.H, layout.W))
+    out = np.empty((n, c, layout.H, layout.W), dtype=np.float32)
+    check(_lib.load().srk_yuv_unpack_host(_np_ptr(f), int(f.strides[0]) if n > 1 else max(int(f.strides[0]), layout.frame_bytes),
+                                          n, layout.H, layout.W, layout.code, c, _np_ptr(chroma_full), _np_ptr(out)),
+          "srk_yuv_unpack_host")
+    return out
+
+
+def yuv_pack_host(y, layout, chroma=None):
+    """yuv_pack on host memory (srk_yuv_pack_host): numpy float32 [N,C,OH,OW] of any strides -> numpy uint8
+    [N, frame_bytes]."""
+    y = np.asarray(y)
+    if y.dtype != np.float32 or y.ndim != 4 or y.shape[2:] != (layout.H, layout.W) or any(s % 4 or s < 0 for s in y.strides):
+        raise ValueError("yuv_pack_host: expects a float32 [N,C,%d,%d] array, got %s %s" % (layout.H, layout.W, y.dtype, y.shape))
+    n, c = int(y.shape[0]), int(y.shape[1])
+    if chroma is not None:
+        chroma = np.ascontiguousarray(chroma, dtype=np.uint8)
+        if chroma.shape != (2, n, layout.ch, layout.cw):
+            raise ValueError("yuv_pack_host: chroma must be [2,%d,%d,%d]" % (n, layout.ch, layout.cw))
+    out = np.zeros((n, layout.frame_bytes), dtype=np.uint8)
+    strides = (ctypes.c_int64 * 4)(*[s // 4 for s in y.strides])
+    check(_lib.load().srk_yuv_pack_host(_np_ptr(y), strides, n, c, layout.H, layout.W, layout.code, _np_ptr(chroma), _np_ptr(out),
+                                        layout.frame_bytes), "srk_yuv_pack_host")
+    return out

@@ -841,6 +841,180 @@ class _Trainer(object):
         print('Single test result image is saved.')
         return save_fn
 
+    # -- raw video streams (data.Y4MReader / Y4MWriter, csrc/video.hip) -------------------------------------------------
+    VIDEO_SLOTS = 3   # pinned + device buffers per direction: one being filled, one in flight, one being consumed
+
+    def _video_net(self, frames, lay, per_frame, tile, tile_batch, ens):
+        """Packed frames (device, uint8 [n, frame_bytes]) -> yuv_unpack -> the net's fp32 output [n,C,OH,OW], on the
+        current stream."""
+        n = int(frames.shape[0])
+        x = ops.yuv_unpack(frames, lay, self.num_channels)
+        if per_frame:   # --tile / --self_ensemble: the existing one-picture path in its fp32 form, frame by frame
+            y = torch.cat([self._run(self._net_input(x[k:k + 1]), tile, tile_batch, ens) for k in range(n)])
+        else:
+            y = self._net(self._net_input(x))
+        if y.dim() != 4 or int(y.shape[0]) != n or int(y.shape[1]) != self.num_channels:
+            raise RuntimeError("test_video: the net returned %s for a batch of %d frames of %d channel(s)"
+                               % (tuple(y.shape), n, self.num_channels))
+        return y
+
+    def _video_pack(self, y, frames, lay, out_lay, out):
+        """The net's output y -> the packed output frames `out`, one yuv_pack launch; a Y model's Cb / Cr come from the
+        input frames through the 8-bit bicubic resizer, to the chroma size of what the net actually returned."""
+        chroma = None
+        if self.num_channels == 1 and lay.sub != "mono":
+            chroma = ops.yuv_chroma(frames, lay, out_lay.ch, out_lay.cw)
+        ops.yuv_pack(y, out_lay, chroma, out=out)
+
+    def test_video(self, src, dst=None, batch=None, tile=None, tile_batch=None, self_ensemble=None):
+        """Super-resolve a YUV4MPEG2 stream (8-bit 4:2:0, 4:4:4 or mono, progressive): src / dst are a path, '-' (stdin /
+        stdout) or a binary file object; dst None: <save_dir>/test_result/SR_result.y4m.  Returns the number of frames.
+        Frames go in batches of `batch` (args.video_batch, else 8; the last may be short) from file bytes to file bytes on
+        the device: k_yuv_unpack (num_channels 1: Y / 255; 3: RGB through Pillow's tables, 4:2:0 chroma bicubic to full
+        size first) -> _net_input and the net on the whole batch -> k_yuv_pack (num_channels 1: Y' quantised, Cb / Cr of
+        the input through the 8-bit bicubic resizer to the chroma size of what the net returned; 3: Pillow's RGB -> YCbCr
+        and for 4:2:0 its BOX shrink of the chroma, fused).  Samples are full-range JFIF values; the chroma resampling is
+        centre-aligned whatever the C tag says, and the tag is carried through.
+        A reader thread fills VIDEO_SLOTS pinned buffers, uploads, compute and downloads run on three streams joined by
+        events, a writer thread drains VIDEO_SLOTS pinned buffers; nothing waits for the whole device, and every buffer
+        is made once (the output side after the first batch has shown the net's output size).
+        tile / tile_batch / self_ensemble as test_single: with either, frames go one at a time through _run, with its
+        refusals.  dst '-': everything this call prints goes to stderr.  A caller that sets self.video_trace to a list gets
+        torch.cuda.memory_allocated() appended at the end of every batch."""
+        import contextlib
+        import queue
+        import sys
+        import threading
+        import time
+        from . import data
+        if isinstance(dst, (str, os.PathLike)) and os.fspath(dst) == '-':
+            # stdout carries the stream and nothing else: whatever this call prints (load_model's line, the frame count)
+            # goes to stderr
+            sink = sys.stdout.buffer
+            with contextlib.redirect_stdout(sys.stderr):
+                return self.test_video(src, sink, batch, tile, tile_batch, self_ensemble)
+        if self.model is None:
+            self.model = self.build_model().to(self.device)
+            self.load_model()
+        n_max = int(batch if batch is not None else (getattr(self.args, 'video_batch', None) or 8))
+        if n_max <= 0:
+            raise ValueError("test_video: batch must be positive (got %d)" % n_max)
+        if dst is None:
+            dst = os.path.join(self.save_dir, 'test_result', 'SR_result.y4m')
+        ens = self._self_ensemble(self_ensemble)
+        per_frame = ens or (tile if tile is not None else getattr(self.args, 'tile', None)) is not None
+        slots = self.VIDEO_SLOTS
+        reader = data.Y4MReader(src)
+        lay = reader.layout
+        pin_in = [torch.empty((n_max, lay.frame_bytes), dtype=torch.uint8, pin_memory=True) for _ in range(slots)]
+        dev_in = [torch.empty((n_max, lay.frame_bytes), dtype=torch.uint8, device=self.device) for _ in range(slots)]
+        pin_out = dev_out = out_lay = writer = write_thread = None
+        h2d, comp, d2h = (torch.cuda.Stream(self.device) for _ in range(3))
+        ev_up, ev_in_used, ev_packed, ev_down = ([torch.cuda.Event() for _ in range(slots)] for _ in range(4))
+        free_in, filled, free_out, to_write = (queue.Queue() for _ in range(4))
+        for i in range(slots):
+            free_in.put(i)
+            free_out.put(i)
+
+        def read_loop():
+            try:
+                while True:
+                    i = free_in.get()
+                    if i is None:
+                        return
+                    ev_up[i].synchronize()   # its last upload has left the pinned buffer
+                    k = reader.read_into(pin_in[i], n_max)
+                    filled.put((i, k))
+                    if k < n_max:
+                        return
+            except BaseException as e:   # handed to the caller's thread
+                filled.put(e)
+
+        def write_loop():
+            try:
+                while True:
+                    item = to_write.get()
+                    if item is None:
+                        return
+                    o, k = item
+                    ev_down[o].synchronize()
+                    writer.write(pin_out[o], k)
+                    free_out.put(o)
+            except BaseException as e:
+                free_out.put(e)
+
+        def take(q):
+            item = q.get()
+            if isinstance(item, BaseException):
+                raise item
+            return item
+
+        trace = getattr(self, 'video_trace', None)
+        frames_done = 0
+        t0 = time.perf_counter()
+        cur = torch.cuda.current_stream()
+        for s in (h2d, comp, d2h):
+            s.wait_stream(cur)
+        read_thread = threading.Thread(target=read_loop, name="y4m-reader", daemon=True)
+        read_thread.start()
+        try:
+            while True:
+                i, k = take(filled)
+                if k == 0:
+                    break
+                with torch.cuda.stream(h2d):
+                    h2d.wait_event(ev_in_used[i])
+                    dev_in[i][:k].copy_(pin_in[i][:k], non_blocking=True)
+                    ev_up[i].record(h2d)
+                with torch.cuda.stream(comp):
+                    comp.wait_event(ev_up[i])
+                    y = self._video_net(dev_in[i][:k], lay, per_frame, tile, tile_batch, ens)
+                    if out_lay is None:   # the first batch shows the net's output size: the output side is made now
+                        out_lay = ops.yuv_layout(int(y.shape[-1]), int(y.shape[-2]), lay.sub,
+                                                 "the net's output for a %s stream" % (reader.header.chroma_tag or "C420jpeg"))
+                        writer = data.Y4MWriter(dst, reader.header.scaled(out_lay.W, out_lay.H))
+                        pin_out = [torch.empty((n_max, out_lay.frame_bytes), dtype=torch.uint8, pin_memory=True) for _ in range(slots)]
+                        dev_out = [torch.empty((n_max, out_lay.frame_bytes), dtype=torch.uint8, device=self.device) for _ in range(slots)]
+                        write_thread = threading.Thread(target=write_loop, name="y4m-writer", daemon=True)
+                        write_thread.start()
+                    o = take(free_out)   # the writer has drained it, so its last download is over
+                    self._video_pack(y, dev_in[i][:k], lay, out_lay, dev_out[o][:k])
+                    ev_in_used[i].record(comp)
+                    ev_packed[o].record(comp)
+                    del y
+                    if trace is not None:
+                        trace.append(torch.cuda.memory_allocated(self.device))
+                free_in.put(i)
+                with torch.cuda.stream(d2h):
+                    d2h.wait_event(ev_packed[o])
+                    pin_out[o][:k].copy_(dev_out[o][:k], non_blocking=True)
+                    ev_down[o].record(d2h)
+                to_write.put((o, k))
+                frames_done += k
+                if k < n_max:
+                    break
+            if frames_done == 0:
+                raise ValueError("test_video: the stream holds no frame")
+            to_write.put(None)
+            write_thread.join()
+            for item in list(free_out.queue):   # the drained slots, or the writer's exception
+                if isinstance(item, BaseException):
+                    raise item
+            read_thread.join()   # it has seen the end of the stream
+        finally:   # the end of the call, not its steady state (on an error the reader may sit in a read: it is a daemon)
+            free_in.put(None)
+            to_write.put(None)
+            if write_thread is not None:
+                write_thread.join()
+            for s in (h2d, comp, d2h):
+                s.synchronize()
+            reader.close()
+            if writer is not None:
+                writer.close()
+        dt = time.perf_counter() - t0
+        print('Video: %d frames -> %d x %d (%s), %.1f frames/s' % (frames_done, out_lay.W, out_lay.H, lay.sub, frames_done / dt))
+        return frames_done
+
     def _ckpt_name(self, epoch):
         # srcnn.py:260-269 style for the simple trainers, edsr.py:324-337 style (ch/batch/epoch/lr) for EDSR / SRGAN
         model_dir = os.path.join(self.save_dir, 'model')
