@@ -652,30 +652,11 @@ def check_args(args):   # main.py:39-57
 
 
 def report(net, args):
-    """One line per dataset after test(): PSNR and SSIM, the bicubic pair where --save_test_images produced it, and the
-    --eval_domain / --eval_shave numbers where asked for.  Without any of the three new flags nothing more is printed
-    than before them."""
-    if not (args.test_only or args.save_test_images or getattr(net, 'test_eval', None)):
-        return
-    for name, v in net.test_psnr.items():
-        parts = ['%s PSNR %.4f SSIM %.4f' % (args.model_name, v, net.test_ssim.get(name, float('nan')))]
-        lp = getattr(net, 'test_lpips', None) if getattr(args, 'lpips_vgg', None) else None
-        if lp is not None:
-            parts[0] += ' LPIPS %.4f' % lp.get(name, float('nan'))
-        nq = getattr(net, 'test_niqe', None) if getattr(args, 'niqe_params', None) else None
-        if nq is not None:
-            parts[0] += ' NIQE %.4f' % nq.get(name, float('nan'))
-        if args.save_test_images and name in net.test_bicubic_psnr:
-            parts.insert(0, 'bicubic PSNR %.4f SSIM %.4f' % (net.test_bicubic_psnr[name],
-                                                            net.test_bicubic_ssim.get(name, float('nan'))))
-            if lp is not None:
-                parts[0] += ' LPIPS %.4f' % getattr(net, 'test_bicubic_lpips', {}).get(name, float('nan'))
-            if nq is not None:
-                parts[0] += ' NIQE %.4f' % getattr(net, 'test_bicubic_niqe', {}).get(name, float('nan'))
-        ev = getattr(net, 'test_eval', {}).get(name)
-        if ev:
-            parts.append('%s shave %d: PSNR %.4f SSIM %.4f' % (ev['domain'], ev['shave'], ev['psnr'], ev['ssim']))
-        print('%s: %s' % (name, ', '.join(parts)))
+    """One line per dataset after test(), from the metric table test() fills (evaluation.report_lines): every number it
+    stored.  Without --test_only, --save_test_images or --eval_domain / --eval_shave numbers nothing is printed."""
+    from pytorch_super_resolution_model_collection_amd import evaluation
+    for line in evaluation.report_lines(net, args.model_name, args.save_test_images, args.test_only or args.save_test_images):
+        print(line)
 
 
 def niqe_fit(args):

@@ -20,7 +20,7 @@ import random
 import torch
 
 from . import dp as dpmod
-from . import models, ops, optim, tiling, trainers, utils
+from . import evaluation, models, ops, optim, tiling, trainers, utils
 
 
 def synthetic_loader(kind, args, steps, device, seed=1234):
@@ -102,6 +102,18 @@ def check_perceptual_args(args, kind):
                          % ("perceptual" if perceptual else "vgg_weights"))
 
 
+# trainers.mixed_loss's terms (a new one: here and there): flag -> (what a kind without it lacks, the value that leaves it out)
+TERM_FLAGS = {"ssim_weight": ("SSIM mix", 0.0), "fft_weight": ("frequency-domain term", 0.0), "fft_norm": (None, "backward"),
+              "lpips_weight": ("LPIPS term", 0.0)}
+
+
+def check_term_args(args, kind, name, flags):
+    """SRGAN, DRCN and ESRGAN train on losses of their own: a term weight > 0 is refused, naming the flag."""
+    for flag in flags:
+        if kind in ("srgan", "drcn", "esrgan") and (getattr(args, flag, 0.0) or 0.0) > 0:
+            raise ValueError("%s: %s has no %s (main.py --%s)" % (flag, name, TERM_FLAGS[flag][0], flag))
+
+
 def check_lpips_args(args, kind):
     """--lpips_vgg / --lpips_lin / --lpips_weight of main.py: the two weight files come together, LPIPS reads RGB, and the
     training term belongs to the kinds trainers.mixed_loss serves.  Raises ValueError naming the flag."""
@@ -114,8 +126,7 @@ def check_lpips_args(args, kind):
                          % ("lpips_lin" if vgg else "lpips_vgg"))
     if weight > 0 and not vgg:
         raise ValueError("lpips_weight: needs the weights of the LPIPS net (main.py --lpips_vgg PATH --lpips_lin PATH)")
-    if weight > 0 and kind in ("srgan", "drcn", "esrgan"):
-        raise ValueError("lpips_weight: %s has no LPIPS term (main.py --lpips_weight)" % kind.upper())
+    check_term_args(args, kind, kind.upper(), ("lpips_weight",))
     if vgg and getattr(args, "num_channels", 3) != 3:
         raise ValueError("lpips_vgg: LPIPS reads RGB (main.py --num_channels 3)")
 
@@ -220,6 +231,13 @@ def _ema_name(name):
     return name[:-len('.pkl')] + '_ema.pkl'
 
 
+def _option(args, name, value=None, default=None):
+    """A per-call option: the argument, else args.<name> where the args object has such a field, else `default`."""
+    if value is None:
+        value = getattr(args, name, None)
+    return default if value is None else value
+
+
 class _Trainer(object):
     kind = None
 
@@ -231,12 +249,9 @@ class _Trainer(object):
             setattr(self, k, getattr(args, k, None))
         self.args = args
         self.steps_per_epoch = getattr(args, "steps_per_epoch", 8)
-        if self.kind in ("srgan", "drcn", "esrgan") and (getattr(args, "ssim_weight", 0.0) or 0.0) > 0:
-            raise ValueError("ssim_weight: %s has no SSIM mix (main.py --ssim_weight)" % self.model_name)
-        if self.kind in ("srgan", "drcn", "esrgan") and (getattr(args, "fft_weight", 0.0) or 0.0) > 0:
-            raise ValueError("fft_weight: %s has no frequency-domain term (main.py --fft_weight)" % self.model_name)
+        check_term_args(args, self.kind, self.model_name, ("ssim_weight", "fft_weight"))
         check_perceptual_args(args, self.kind)
-        check_lpips_args(args, self.kind)
+        check_lpips_args(args, self.kind)      # (lpips_weight is refused there, between the checks of its files)
         self.vgg_layers = check_vgg_layers_args(args, self.kind)
         self.disc_args = check_discriminator_args(args, self.kind)
         check_data_flags(args)
@@ -261,11 +276,9 @@ class _Trainer(object):
 
     def build_step(self):
         """(flat parameters, optimizer, DataParallel or None, eager step function) of the freshly built model."""
-        return trainers.build(self.kind, self.model, self.lr, use_dp=self.world > 1,
-                              ssim_weight=getattr(self.args, "ssim_weight", 0.0) or 0.0, ema_decay=self.ema_decay,
-                              fft_weight=getattr(self.args, "fft_weight", 0.0) or 0.0,
-                              fft_norm=getattr(self.args, "fft_norm", None) or "backward",
-                              lpips_weight=getattr(self.args, "lpips_weight", 0.0) or 0.0, lpips_net=self.lpips_net())
+        terms = {flag: getattr(self.args, flag, None) or off for flag, (_, off) in TERM_FLAGS.items()}
+        return trainers.build(self.kind, self.model, self.lr, use_dp=self.world > 1, ema_decay=self.ema_decay,
+                              lpips_net=self.lpips_net(), **terms)
 
     def lpips_net(self):
         """models.LPIPS with the weights of --lpips_vgg / --lpips_lin on this trainer's device, built once; None without
@@ -281,32 +294,10 @@ class _Trainer(object):
             self._niqe = utils.load_niqe_params(self.args.niqe_params)
         return getattr(self, "_niqe", None)
 
-    @staticmethod
-    def _niqe_features(img, shave):
-        """ops.niqe_features of one picture ([1,C,H,W] / [C,H,W] float, or [H,W,3] / [H,W] uint8 as the picture tail
-        writes it) as a device tensor, or None where NIQE does not apply: fewer than two 96 x 96 blocks, or channels
-        other than 1 or 3."""
-        if img.dtype == torch.uint8:
-            img = img.unsqueeze(0) if img.dim() == 2 else img.permute(2, 0, 1)
-        else:
-            img = (img[0] if img.dim() == 4 else img).float()
-        nh, nw = ops.niqe_blocks(img.shape[1], img.shape[2], shave)
-        if img.shape[0] not in (1, 3) or nh * nw < 2:
-            return None
-        return ops.niqe_features(img, shave)
-
-    @staticmethod
-    def _niqe_mean(feats, params):
-        """Mean NIQE over the pictures whose features are given (None entries and pictures with fewer than two NaN-free
-        blocks are left out); None when none is left."""
-        vals = []
-        for f in feats:
-            if f is not None:
-                try:
-                    vals.append(ops.niqe_finish(f, *params))
-                except ValueError:
-                    pass
-        return sum(vals) / len(vals) if vals else None
+    def _ensure_model(self):
+        if self.model is None:
+            self.model = self.build_model().to(self.device)
+            self.load_model()
 
     # -- training state: save at epoch boundaries, continue with --resume --------------------------------------------
     def _state_name(self):
@@ -553,11 +544,9 @@ class _Trainer(object):
 
     # -- tiled inference (tiling.py, csrc/tile.hip) ------------------------------------------------------------------
     def _resolve_tile(self, tile, x, ensemble=False):
-        """The `tile` option for the net input x -> (tile size or None for one pass, the net's geometry or None).
-        tile=None falls back to args.tile (older args objects have no such field); still None: nothing is computed.
-        ensemble: the geometry is the union of the net's cone and its mirror image (tiling.ensemble_geometry)."""
-        if tile is None:
-            tile = getattr(self.args, 'tile', None)
+        """The `tile` option (_option) for the net input x -> (tile size or None for one pass, the net's geometry or None;
+        nothing is computed without the option).  ensemble: the geometry is the union of the net's cone and its mirror image."""
+        tile = _option(self.args, 'tile', tile)
         if tile is None:
             return None, None
         self.model.eval()
@@ -569,7 +558,7 @@ class _Trainer(object):
     # -- x8 geometric self-ensemble (csrc/dihedral.hip) ---------------------------------------------------------------
     def _self_ensemble(self, flag):
         """The `self_ensemble` option: None falls back to args.self_ensemble (older args objects have no such field: off)."""
-        return bool(getattr(self.args, 'self_ensemble', False)) if flag is None else bool(flag)
+        return bool(_option(self.args, 'self_ensemble', flag, False))
 
     def _infer_variants(self, x):
         """The net (last element of a tuple output) on the eight variants T_k, k = 4 m + r, T_k = rot90(flip of the last
@@ -599,9 +588,7 @@ class _Trainer(object):
         variants included, rounded up to whole tiles (tiling.tiles_per_chunk)."""
         plan = tiling.plan(geo, int(x.shape[-2]), int(x.shape[-1]), tile)
         tp = ops.TilePlan(plan, self.device)
-        if tile_batch is None:
-            tile_batch = getattr(self.args, 'tile_batch', None) or tiling.DEFAULT_TILE_BATCH
-        tile_batch = tiling.tiles_per_chunk(tile_batch, plan.ntiles, ensemble)
+        tile_batch = tiling.tiles_per_chunk(_option(self.args, 'tile_batch', tile_batch), plan.ntiles, ensemble)
         cb, cr = self._chroma_at(chroma, plan.OH, plan.OW)
         out = None
         for t0 in range(0, plan.ntiles, tile_batch):
@@ -642,133 +629,46 @@ class _Trainer(object):
         return self._run(self._net_input(x), tile, tile_batch, self._self_ensemble(self_ensemble))
 
     def test(self, loader=None, save_images=False, tile=None, eval_domain=None, eval_shave=None, self_ensemble=None):
-        """Evaluation loop (espcn.py:173-215, edsr.py:196-250): forward + PSNR per image (computed on the device), over
-        `loader`, else over every folder of `test_dataset` that exists under `data_dir` (data.get_test_set), else over
-        seeded synthetic pairs.  Returns the list of PSNRs; `self.test_psnr` holds the per-dataset averages.
-        save_images: as the reference's test() (edsr.py:215-274), every result also goes through utils.save_img into
-        <save_dir>/test_result/<dataset>/SR_result_<n>.png, and `self.test_bicubic_psnr` holds, per dataset, the
-        average PSNR of the loader's bicubic image (the third item, where the loader yields one) against the target
-        (edsr.py:257-261), computed by the same device kernel.
-        tile: None (args.tile, else one pass), a tile size in net-input pixels or 'auto': see test_single.
-        self_ensemble: None (args.self_ensemble, else off) or a bool: every picture through the x8 ensemble, see test_single.
-        Beside every PSNR goes the SSIM of the same two tensors (utils.SSIM, on the device): `self.test_ssim` holds the
-        per-dataset averages, with save_images `self.test_bicubic_ssim` the bicubic image's.  A pair smaller than the
-        11 x 11 window is left out of that average.
-        eval_domain / eval_shave (None: args.eval_domain / args.eval_shave where the args object has them): when either
-        is given, `self.test_eval[name] = {'domain', 'shave', 'psnr', 'ssim'}` holds the averages of ops.ssim's fused
-        outputs in that domain ('float', 'u8': the 8-bit picture, 'y8': its luma) with that border left out -- the
-        protocol of published tables.  The returned list and test_psnr do not depend on either.
-        With the LPIPS weights (args.lpips_vgg / args.lpips_lin) `self.test_lpips` holds the per-dataset averages of
-        ops.lpips of the same two float tensors PSNR sees (unshaved, unclamped; a pair under 16 on a side is left out), and
-        with save_images `self.test_bicubic_lpips` the bicubic image's.
-        With args.niqe_params (a parameter file, utils.load_niqe_params) `self.test_niqe` holds the per-dataset mean of
-        the NIQE of the net's outputs (ops.niqe_features on the 8-bit picture of each output, eval_shave pixels off each
-        side, else 0; no target involved, so a pair of unequal shapes counts too; a picture with fewer than two 96 x 96
-        blocks, or fewer than two blocks without a NaN, is left out), and with save_images `self.test_bicubic_niqe` the
-        bicubic image's.  The features stay on the device inside the loop; the 36 x 36 finish runs after it."""
-        if self.model is None:
-            self.model = self.build_model().to(self.device)
-            self.load_model()
-        if eval_domain is None:
-            eval_domain = getattr(self.args, 'eval_domain', None)
-        if eval_shave is None:
-            eval_shave = getattr(self.args, 'eval_shave', None)
-        want_eval = eval_domain is not None or eval_shave is not None
-        eval_domain = 'float' if eval_domain is None else eval_domain
-        eval_shave = 0 if eval_shave is None else int(eval_shave)
-
-        def fits(t, border=0):   # the window needs 11 x 11 pixels after the crop
-            return min(int(t.shape[-2]), int(t.shape[-1])) - 2 * border >= 11
-        sources = []
-        if loader is not None:
-            sources.append(("loader", loader))
-        else:
-            for name in (self.test_dataset or []):
-                ld = self.load_dataset(name, is_train=False) if isinstance(name, str) and len(name) > 1 else None
-                if ld is not None:
-                    sources.append((name, ld))
-            if not sources:
-                sources.append(("synthetic", synthetic_loader(self.kind, self.args, 2, self.device, 4321)))
-        psnrs, self.test_psnr, self.test_ssim = [], {}, {}
-        lpips_net = self.lpips_net()
-        if lpips_net is not None:
-            self.test_lpips = {}
-
-        def lpips_of(a, b):   # 0-dim device tensor, or None for a pair the five taps do not fit
-            if lpips_net is None or min(int(a.shape[-2]), int(a.shape[-1])) < 16:
-                return None
-            with torch.no_grad():
-                return ops.lpips(a.float(), b.float(), lpips_net, normalize=True, reduce=True)
-        niqe_params = self.niqe_params()
-        if niqe_params is not None:
-            self.test_niqe = {}
-            if save_images:
-                self.test_bicubic_niqe = {}
-        if save_images:
-            self.test_bicubic_psnr, self.test_bicubic_ssim = {}, {}
-            if lpips_net is not None:
-                self.test_bicubic_lpips = {}
-        if want_eval:
-            self.test_eval = {}
-        for name, batches in sources:
-            mine, mine_ssim, mine_eval = [], [], []
-            bicubic, bicubic_ssim, img_num = [], [], 0
-            mine_lpips, bicubic_lpips = [], []
-            mine_niqe, bicubic_niqe = [], []
+        """Evaluation loop (espcn.py:173-215, edsr.py:196-250): the net on every picture of `loader`, else of every folder
+        of `test_dataset` that exists under `data_dir`, else of seeded synthetic pairs, and the rows of evaluation.METRICS
+        of its output against the target, on the device.  Returns the PSNRs, one per picture whose output has the target's
+        shape; `self.test_<key>[dataset]` holds the per-dataset numbers of every row that is on (the table says what a row
+        is, when it is on and which pictures it leaves out; DESIGN.md section 36 which attributes a call creates).
+        save_images: as edsr.py:215-274, every result also goes through utils.save_img into <save_dir>/test_result/
+        <dataset>/SR_result_<n>.png, and the rows of the loader's bicubic picture (the third item, where there is one)
+        against the unshaved target go to `self.test_bicubic_<key>`.  tile / self_ensemble: as test_single takes them.
+        eval_domain / eval_shave: None (the args object's), or the domain and border of the `eval` row; NIQE shaves the same
+        border.  Nothing inside the loop reads a device value back (utils.save_img's copy of the picture apart)."""
+        self._ensure_model()
+        opts = evaluation.Options(self, _option(self.args, 'eval_domain', eval_domain), _option(self.args, 'eval_shave', eval_shave))
+        mine, returned = evaluation.Scores(self, opts), []
+        bicubic = evaluation.Scores(self, opts, bicubic=True) if save_images else None
+        for name, batches in self._test_sources(loader):
+            img_num = 0
             for batch in batches:
                 items = [batch] if torch.is_tensor(batch[0]) else list(zip(*batch))   # ragged test images come as lists
                 for item in items:
                     lr_img, hr_img = self._channels(*[t if t.dim() == 4 else t.unsqueeze(0) for t in item[:2]])
                     out = self._forward(lr_img.to(self.device), tile, self_ensemble=self_ensemble)
-                    tgt = hr_img.to(self.device)
-                    if niqe_params is not None:
-                        mine_niqe.append(self._niqe_features(out, eval_shave))
-                    if self.kind == "srcnn":     # srcnn.py:193-199: border pixels excluded
-                        tgt = utils.shave(tgt, 8)
-                    if out.shape == tgt.shape:
-                        mine.append(utils.PSNR(out, tgt))   # 0-dim device tensors: nothing syncs inside the loop
-                        if fits(out):
-                            mine_ssim.append(utils.SSIM(out, tgt))
-                        mine_lpips.append(lpips_of(out, tgt))
-                        if want_eval and fits(out, eval_shave):
-                            mine_eval.append(torch.stack(ops.ssim(out.float(), tgt.float(), eval_shave, eval_domain)[:2]))
+                    hr = hr_img.to(self.device)
+                    mine.add(out, utils.shave(hr, 8) if self.kind == "srcnn" else hr)   # srcnn.py:193-199: border excluded
                     if save_images:
                         img_num += 1
                         utils.save_img(out[0], img_num, save_dir=os.path.join(self.save_dir, 'test_result', str(name)))
                         if len(item) > 2:
                             bc_img = self._channels(item[2] if item[2].dim() == 4 else item[2].unsqueeze(0))[0]
-                            if niqe_params is not None:
-                                bicubic_niqe.append(self._niqe_features(bc_img.to(self.device), eval_shave))
-                            if bc_img.shape == hr_img.shape:
-                                bicubic.append(utils.PSNR(bc_img.to(self.device), hr_img.to(self.device)))
-                                if fits(bc_img):
-                                    bicubic_ssim.append(utils.SSIM(bc_img.to(self.device), hr_img.to(self.device)))
-                                bicubic_lpips.append(lpips_of(bc_img.to(self.device), hr_img.to(self.device)))
-            vals = [float(v) for v in torch.stack(mine).cpu()] if mine else []
-            if vals:
-                self.test_psnr[name] = sum(vals) / len(vals)
-            psnrs += vals
-            if bicubic:
-                bvals = [float(v) for v in torch.stack(bicubic).cpu()]
-                self.test_bicubic_psnr[name] = sum(bvals) / len(bvals)
-            mine_lpips, bicubic_lpips = ([v for v in vals if v is not None] for vals in (mine_lpips, bicubic_lpips))
-            for vals_dev, into in ((mine_ssim, self.test_ssim), (bicubic_ssim, getattr(self, 'test_bicubic_ssim', None)),
-                                   (mine_lpips, getattr(self, 'test_lpips', None)),
-                                   (bicubic_lpips, getattr(self, 'test_bicubic_lpips', None))):
-                if vals_dev:
-                    svals = [float(v) for v in torch.stack(vals_dev).cpu()]
-                    into[name] = sum(svals) / len(svals)
-            if niqe_params is not None:
-                for feats, into in ((mine_niqe, self.test_niqe), (bicubic_niqe, getattr(self, 'test_bicubic_niqe', None))):
-                    mean = self._niqe_mean(feats, niqe_params)
-                    if mean is not None:
-                        into[name] = mean
-            if mine_eval:
-                ev = torch.stack(mine_eval).double().cpu()
-                self.test_eval[name] = {'domain': eval_domain, 'shave': eval_shave,
-                                        'psnr': sum(float(v) for v in ev[:, 1]) / len(ev),
-                                        'ssim': sum(float(v) for v in ev[:, 0]) / len(ev)}
-        return psnrs
+                            bicubic.add(bc_img.to(self.device), hr)
+            returned += mine.finish(name)[evaluation.RETURNED]
+            if bicubic is not None:
+                bicubic.finish(name)
+        return returned
+
+    def _test_sources(self, loader):
+        """[(dataset name, iterable of batches)] of test(): `loader`, else the test sets on disk, else synthetic pairs."""
+        if loader is not None:
+            return [("loader", loader)]
+        found = [(n, self.load_dataset(n, is_train=False)) for n in (self.test_dataset or []) if isinstance(n, str) and len(n) > 1]
+        return [s for s in found if s[1] is not None] or [("synthetic", synthetic_loader(self.kind, self.args, 2, self.device, 4321))]
 
     def test_single(self, img, tile=None, tile_batch=None, self_ensemble=None):
         """A tensor: super-resolve one [C,H,W] (or [1,C,H,W]) tensor and return the net's output on the host.
@@ -788,9 +688,7 @@ class _Trainer(object):
         (tiling.ensemble_geometry) and `tile_batch` counts net inputs, variants included."""
         if isinstance(img, (str, os.PathLike)):
             return self._test_single_file(img, tile, tile_batch, self_ensemble)
-        if self.model is None:
-            self.model = self.build_model().to(self.device)
-            self.load_model()
+        self._ensure_model()
         x = img if img.dim() == 4 else img.unsqueeze(0)
         return self._forward(x.to(self.device), tile, tile_batch, self_ensemble).cpu()
 
@@ -811,9 +709,7 @@ class _Trainer(object):
         self_ensemble (see test_single): k_dihedral_merge writes the 8-bit picture from the eight outputs (it quantises, and
         merges the resized chroma, on the way); tiled, it writes the fp32 tile outputs the stitch then reads."""
         from . import data
-        if self.model is None:
-            self.model = self.build_model().to(self.device)
-            self.load_model()
+        self._ensure_model()
         rgb = torch.tensor(data.load_img(os.fspath(img_fn)), device=self.device)   # [H,W,3] uint8: the one upload
         h, w = int(rgb.shape[0]), int(rgb.shape[1])
         chroma = None
@@ -824,11 +720,10 @@ class _Trainer(object):
             x = ops.resize_u8(rgb.permute(2, 0, 1), h, w, out_float=True).unsqueeze(0)   # ToTensor: planar, / 255
         ens = self._self_ensemble(self_ensemble)
         img8 = self._run(self._net_input(x), tile, tile_batch, ens, as_u8=True, chroma=chroma)
-        niqe_params = self.niqe_params()
-        if niqe_params is not None:   # of the very bytes the file gets (the colour-restored picture of a Y model)
-            shave = getattr(self.args, 'eval_shave', None) or 0
-            mean = self._niqe_mean([self._niqe_features(img8, int(shave))], niqe_params)
-            self.test_single_niqe = float('nan') if mean is None else mean
+        # NIQE of the very bytes the file gets (the colour-restored picture of a Y model), where --niqe_params asks for it
+        niqe = evaluation.single("niqe", img8, evaluation.Options(self, eval_shave=_option(self.args, 'eval_shave')))
+        if niqe is not None:
+            self.test_single_niqe = niqe
         return self._save_single(img8)
 
     def _save_single(self, img8):
@@ -893,16 +788,14 @@ class _Trainer(object):
             sink = sys.stdout.buffer
             with contextlib.redirect_stdout(sys.stderr):
                 return self.test_video(src, sink, batch, tile, tile_batch, self_ensemble)
-        if self.model is None:
-            self.model = self.build_model().to(self.device)
-            self.load_model()
-        n_max = int(batch if batch is not None else (getattr(self.args, 'video_batch', None) or 8))
+        self._ensure_model()
+        n_max = int(_option(self.args, 'video_batch', batch, 8))
         if n_max <= 0:
             raise ValueError("test_video: batch must be positive (got %d)" % n_max)
         if dst is None:
             dst = os.path.join(self.save_dir, 'test_result', 'SR_result.y4m')
         ens = self._self_ensemble(self_ensemble)
-        per_frame = ens or (tile if tile is not None else getattr(self.args, 'tile', None)) is not None
+        per_frame = ens or _option(self.args, 'tile', tile) is not None
         slots = self.VIDEO_SLOTS
         reader = data.Y4MReader(src)
         lay = reader.layout

@@ -126,30 +126,18 @@ def loss_segments(model, opt, loss_fn, dp=None, clip=None):
 
 
 def mixed_loss(pixel, ssim_weight=0.0, fft_weight=0.0, fft_norm="backward", lpips_weight=0.0, lpips_net=None):
-    """The loss a kind trains on: `pixel` itself (the same function object) for both weights 0, else
-    [(1 - a) * pixel(pred, t) + a * (1 - SSIM(pred, t))] + w * FFT(pred, t): the mix of Zhao et al. (a = ssim_weight) plus
-    the frequency-domain L1 of ops.fft_loss (w = fft_weight >= 0), added by srk_axpby (ops.loss_sum); on one GPU each loss
-    kernel folds its weight into its gradient (ops.weighted_term), so each extra term adds its loss launches, the axpby of
-    two scalars and the axpby of two gradients to a step, and no ATen node to a captured one.  With w == 0 the result is
-    what it was before the argument existed.  lpips_weight v > 0 adds v * ops.lpips(pred, t, lpips_net) (models.LPIPS; the
-    batches of every kind are in [0, 1], so normalize=True) as one more such stage; with v == 0 the result is the object
-    it was before that argument existed."""
+    """The loss a kind trains on: `pixel` itself (the same function object) for all weights 0, else
+    [(1 - a) * pixel(pred, t) + a * (1 - SSIM(pred, t))] + w * FFT(pred, t) + v * LPIPS(pred, t): the mix of Zhao et al.
+    (a = ssim_weight), the frequency-domain L1 of ops.fft_loss (w = fft_weight >= 0) and ops.lpips with lpips_net (v =
+    lpips_weight >= 0; models.LPIPS; every kind's batches are in [0, 1], so normalize=True), added by srk_axpby
+    (ops.loss_sum); on one GPU each loss kernel folds its weight into its gradient (ops.weighted_term), so each extra term
+    adds its loss launches, the axpby of two scalars and the axpby of two gradients to a step, and no ATen node to a
+    captured one.  A term whose weight is 0 leaves the result the object it is without that term."""
     a, w, v = float(ssim_weight), float(fft_weight), float(lpips_weight)
     if not 0.0 <= v < float("inf"):
         raise ValueError("lpips_weight %r is not a non-negative finite number" % (lpips_weight,))
     if v > 0.0 and lpips_net is None:
         raise ValueError("lpips_weight %r needs an lpips_net (models.LPIPS with its weights loaded)" % (lpips_weight,))
-    if v > 0.0:
-        inner = mixed_loss(pixel, ssim_weight, fft_weight, fft_norm)
-
-        def perceptual(pred, target):
-            return ops.lpips(pred, target, lpips_net, normalize=True)
-
-        def with_lpips(pred, target):
-            p1, p2 = ops.fork(pred)
-            # (inner carries weight 1: its terms take their own weights, exactly as without this term)
-            return ops.loss_sum(inner(p1, target), ops.weighted_term(perceptual, v, p2, target), 1.0, v)
-        return with_lpips
     if not 0.0 <= a <= 1.0:
         raise ValueError("ssim_weight %r is not in [0, 1]" % (ssim_weight,))
     if not 0.0 <= w < float("inf"):
@@ -163,38 +151,35 @@ def mixed_loss(pixel, ssim_weight=0.0, fft_weight=0.0, fft_norm="backward", lpip
             p1, p2 = ops.fork(pred)   # the two gradients of pred are added by srk_axpby, not by autograd's ATen add
             return ops.loss_sum(ops.weighted_term(pixel, 1.0 - a, p1, target), ops.weighted_term(ops.ssim_loss, a, p2, target),
                                 1.0 - a, a)
-    if w == 0.0:
-        return base
 
-    def fft(pred, target):
-        return ops.fft_loss(pred, target, fft_norm)
-
-    def loss(pred, target):
-        p1, p2 = ops.fork(pred)
-        # (base carries weight 1: its terms take their own weights, or the general path, exactly as without the third term)
-        return ops.loss_sum(base(p1, target), ops.weighted_term(fft, w, p2, target), 1.0, w)
-    return loss
-
-
-def mse_step(model, opt, dp=None, clip=None, ssim_weight=0.0, fft_weight=0.0, fft_norm="backward", lpips_weight=0.0,
-             lpips_net=None):
-    """srcnn.py:127-131 / fsrcnn.py:153-157 / vdsr.py:143-150 (clip = 0.4)."""
-    return eager_step(loss_segments(model, opt, mixed_loss(ops.mse_loss, ssim_weight, fft_weight, fft_norm, lpips_weight,
-                                                      lpips_net), dp, clip))
+    def stage(inner, fn, weight):
+        def loss(pred, target):
+            p1, p2 = ops.fork(pred)
+            # (inner carries weight 1: its terms take their own weights, or the general path, exactly as without this term)
+            return ops.loss_sum(inner(p1, target), ops.weighted_term(fn, weight, p2, target), 1.0, weight)
+        return loss
+    # the additive terms, innermost first; a new one is one more pair here (and a flag in sr_trainers.TERM_FLAGS)
+    for weight, fn in ((w, lambda pred, t: ops.fft_loss(pred, t, fft_norm)),
+                       (v, lambda pred, t: ops.lpips(pred, t, lpips_net, normalize=True))):
+        if weight > 0.0:
+            base = stage(base, fn, weight)
+    return base
 
 
-def l1_step(model, opt, dp=None, ssim_weight=0.0, fft_weight=0.0, fft_norm="backward", lpips_weight=0.0,
-            lpips_net=None):
-    """edsr.py:151-155"""
-    return eager_step(loss_segments(model, opt, mixed_loss(ops.l1_loss, ssim_weight, fft_weight, fft_norm, lpips_weight,
-                                                      lpips_net), dp))
+def mse_step(model, opt, dp=None, clip=None, **terms):
+    """srcnn.py:127-131 / fsrcnn.py:153-157 / vdsr.py:143-150 (clip = 0.4).  terms: mixed_loss's keywords."""
+    return eager_step(loss_segments(model, opt, mixed_loss(ops.mse_loss, **terms), dp, clip))
 
 
-def lapsrn_step(model, opt, dp=None, ssim_weight=0.0, fft_weight=0.0, fft_norm="backward", lpips_weight=0.0,
-                lpips_net=None):
+def l1_step(model, opt, dp=None, **terms):
+    """edsr.py:151-155.  terms: mixed_loss's keywords."""
+    return eager_step(loss_segments(model, opt, mixed_loss(ops.l1_loss, **terms), dp))
+
+
+def lapsrn_step(model, opt, dp=None, **terms):
     """lapsrn.py:190-199: two Charbonnier losses, two backward calls into the same gradients.  A plain closure without
     segments: it cannot be split at its exchange, so under data parallelism it is never captured."""
-    loss_fn = mixed_loss(ops.charbonnier_loss, ssim_weight, fft_weight, fft_norm, lpips_weight, lpips_net)   # both levels
+    loss_fn = mixed_loss(ops.charbonnier_loss, **terms)   # both levels
 
     def step(inp, target2x, target4x):
         opt.zero_grad()
@@ -636,36 +621,28 @@ class GraphedStep(GraphedSegments):
     seg = property(lambda self: self)   # (the split capture used to be a member of this name: `step.seg.plan` still reads)
 
 
-def build(kind, model, lr, dp_group=None, use_dp=False, ssim_weight=0.0, ema_decay=0.0, fft_weight=0.0, fft_norm="backward",
-          lpips_weight=0.0, lpips_net=None):
+def build(kind, model, lr, dp_group=None, use_dp=False, ema_decay=0.0, **terms):
     """(flat, optimizer, dp, step) for one of 'srcnn' | 'fsrcnn' | 'vdsr' | 'edsr' | 'lapsrn' | 'espcn' | 'rcan' | 'rdn' | 'swinir': the one place that
-    names the loss and the clip a kind trains with.  ssim_weight a in (0, 1]: (1 - a) * that loss + a * (1 - SSIM)
-    (mixed_loss); 0: the step as it is without the argument.  fft_weight w > 0 adds w * ops.fft_loss(pred, target, fft_norm)
-    to that (mixed_loss); 0: the step as it is without the argument.  lpips_weight v > 0 adds v * ops.lpips(pred, target,
-    lpips_net) (mixed_loss; RGB models only, refused for 'srgan' and 'drcn'); 0: the step as it is without the argument.
-    ema_decay d in (0, 1): the optimizer keeps the moving average
-    of the weights (`opt.ema`); it is updated inside opt.step()'s kernel, so eager steps, segments and graphs all carry it
-    without a node of its own, and under data parallelism every rank's shadow is the same (same parameters, same kernel)."""
+    names the loss and the clip a kind trains with.  terms: mixed_loss's keywords (ssim_weight, fft_weight, fft_norm,
+    lpips_weight, lpips_net; RGB models only, refused for 'srgan' and 'drcn'), each of which at 0 leaves the step as it is
+    without the argument.  ema_decay d in (0, 1): the optimizer keeps the moving average of the weights (`opt.ema`); it is
+    updated inside opt.step()'s kernel, so eager steps, segments and graphs all carry it without a node of its own, and
+    under data parallelism every rank's shadow is the same (same parameters, same kernel)."""
     from .dp import DataParallel
-    if float(lpips_weight) > 0.0 and kind in ("srgan", "drcn"):
+    if float(terms.get("lpips_weight", 0.0)) > 0.0 and kind in ("srgan", "drcn"):
         raise ValueError("lpips_weight %r: %s has no LPIPS term (SRGAN trains on an adversarial content term, DRCN through "
-                         "its fused recursive-supervision head)" % (lpips_weight, kind))
+                         "its fused recursive-supervision head)" % (terms["lpips_weight"], kind))
     flat = FlatParams(model)
     opt = make_optimizer(kind, flat, lr, ema_decay=ema_decay)
     dp = DataParallel(flat, dp_group) if use_dp else None
     if dp is not None:
         dp.broadcast_params()
         opt.ema_reset()      # (the shadow starts as a copy of the parameters every rank now has)
-    fft = dict(fft_weight=fft_weight, fft_norm=fft_norm, lpips_weight=lpips_weight, lpips_net=lpips_net)
     if kind in ("edsr", "rcan", "rdn", "swinir"):
-        step = l1_step(model, opt, dp, ssim_weight=ssim_weight, **fft)
-    elif kind == "lapsrn":
-        step = lapsrn_step(model, opt, dp, ssim_weight=ssim_weight, **fft)
-    elif kind == "vdsr":
-        step = mse_step(model, opt, dp, clip=0.4, ssim_weight=ssim_weight, **fft)
-    else:
-        step = mse_step(model, opt, dp, ssim_weight=ssim_weight, **fft)
-    return flat, opt, dp, step
+        return flat, opt, dp, l1_step(model, opt, dp, **terms)
+    if kind == "lapsrn":
+        return flat, opt, dp, lapsrn_step(model, opt, dp, **terms)
+    return flat, opt, dp, mse_step(model, opt, dp, clip=0.4 if kind == "vdsr" else None, **terms)
 
 
 def _repack_touched(flats, seen):

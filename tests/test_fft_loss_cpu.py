@@ -191,6 +191,59 @@ def test_mixed_loss_identities():
     assert pkg.utils.FFTLoss("ortho").norm == "ortho"
 
 
+@pytest.mark.parametrize("a", (0.0, 0.3))
+@pytest.mark.parametrize("w", (0.0, 0.25))
+@pytest.mark.parametrize("v", (0.0, 2.0))
+def test_mixed_loss_is_the_ssim_mix_inside_fft_inside_lpips(monkeypatch, a, w, v):
+    """The call tree of one evaluation of the loss, recorded: pred is forked once per stage, the SSIM mix weighs its two
+    terms (1 - a, a), every additive stage is loss_sum(inner(p1), weighted_term(term, weight, p2), 1.0, weight), FFT around
+    the mix and LPIPS outermost."""
+    import pytorch_super_resolution_model_collection_amd as pkg
+    T, ops = pkg.trainers, pkg.ops
+    forks, net = [], object()
+
+    def fork(x):
+        forks.append(x)
+        return (x, 1), (x, 2)
+    monkeypatch.setattr(ops, "fork", fork)
+    monkeypatch.setattr(ops, "loss_sum", lambda l1, l2, ca=1.0, cb=1.0: ("sum", l1, l2, ca, cb))
+    monkeypatch.setattr(ops, "weighted_term", lambda fn, weight, p, t: ("term", fn(p, t), weight))
+    monkeypatch.setattr(ops, "ssim_loss", lambda p, t: ("ssim", p, t))
+    monkeypatch.setattr(ops, "fft_loss", lambda p, t, norm: ("fft", p, t, norm))
+    monkeypatch.setattr(ops, "lpips", lambda p, t, n, normalize=False: ("lpips", p, t, n, normalize))
+    pixel = lambda p, t: ("pixel", p, t)
+    loss = T.mixed_loss(pixel, a, w, "ortho", v, net)
+    if a == w == v == 0.0:
+        assert loss is pixel
+        return
+
+    def mix(p):
+        if a == 0.0:
+            return ("pixel", p, "t")
+        return ("sum", ("term", ("pixel", (p, 1), "t"), 1.0 - a), ("term", ("ssim", (p, 2), "t"), a), 1.0 - a, a)
+
+    def with_fft(p):
+        if w == 0.0:
+            return mix(p)
+        return ("sum", mix((p, 1)), ("term", ("fft", (p, 2), "t", "ortho"), w), 1.0, w)
+
+    def with_lpips(p):
+        if v == 0.0:
+            return with_fft(p)
+        return ("sum", with_fft((p, 1)), ("term", ("lpips", (p, 2), "t", net, True), v), 1.0, v)
+    assert loss("x", "t") == with_lpips("x")
+    assert len(forks) == (a > 0) + (w > 0) + (v > 0)
+    if a > 0 and w > 0 and v > 0:      # all three, written out
+        assert forks == ["x", ("x", 1), (("x", 1), 1)]
+        assert loss("x", "t") == (
+            "sum",
+            ("sum",
+             ("sum", ("term", ("pixel", ((("x", 1), 1), 1), "t"), 1.0 - 0.3), ("term", ("ssim", ((("x", 1), 1), 2), "t"), 0.3),
+              1.0 - 0.3, 0.3),
+             ("term", ("fft", (("x", 1), 2), "t", "ortho"), 0.25), 1.0, 0.25),
+            ("term", ("lpips", ("x", 2), "t", net, True), 2.0), 1.0, 2.0)
+
+
 def test_trainers_refuse_srgan_and_drcn():
     import argparse
     from pytorch_super_resolution_model_collection_amd import sr_trainers
