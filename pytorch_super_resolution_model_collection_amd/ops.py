@@ -2071,7 +2071,7 @@ def linear(x, weight, bias=None, act=ACT_NONE, slope=0.0):
     return _Linear.apply(x, weight, bias, int(act), float(slope))
 
 
-_INTERP = {"nearest": 0, "bilinear": 2, "bicubic": 3}
+_INTERP = {"nearest": _lib.INTERP_NEAREST, "bilinear": _lib.INTERP_BILINEAR, "bicubic": _lib.INTERP_BICUBIC}
 
 
 def img_interp(imgs, scale_factor, interpolation="bicubic"):
@@ -2343,11 +2343,10 @@ def noise_u8_bytes(x, sigma, seed):
 
 
 # ---- Real-ESRGAN's second-order degradation (data.Degradation2) ------------------------------------
-INTERP_BOX = 4                                                          # SRK_INTERP_BOX
-BLUR_KINDS = {"gauss": 0, "ggauss": 1, "plateau": 2, "sinc": 3}         # SRK_BLUR_*
-NOISE2_OFF, NOISE2_GAUSS, NOISE2_POISSON = 0, 1, 2                      # SRK_NOISE2_*
-POISSON_KT, POISSON_PEAK = 448, 256.0                                   # SRK_POISSON_KT; the chain's fixed peak
-USM_MAX_K = 51                                                          # SRK_USM_MAX_K
+INTERP_BOX, POISSON_KT, USM_MAX_K = _lib.INTERP_BOX, _lib.POISSON_KT, _lib.USM_MAX_K
+NOISE2_OFF, NOISE2_GAUSS, NOISE2_POISSON = _lib.NOISE2_OFF, _lib.NOISE2_GAUSS, _lib.NOISE2_POISSON
+BLUR_KINDS = {"gauss": _lib.BLUR_GAUSS, "ggauss": _lib.BLUR_GGAUSS, "plateau": _lib.BLUR_PLATEAU, "sinc": _lib.BLUR_SINC}
+POISSON_PEAK = 256.0                                                    # the chain's fixed peak (not in the header)
 
 
 def blur_table(kind, K, s1=1.0, s2=1.0, theta=0.0, beta=1.0, cutoff=1.0):
@@ -3620,7 +3619,7 @@ def gan_logit_loss(logits, target_is_real):
 # ------------------------------------------------------------------------------------------------
 # SwinIR's operators: shifted-window attention, LayerNorm, GELU (csrc/wattn.hip, csrc/swin_pointwise.hip)
 # ------------------------------------------------------------------------------------------------
-WATTN_MAX_HEAD_DIM = 32
+WATTN_MAX_HEAD_DIM = _lib.WATTN_MAX_HEAD_DIM
 
 
 def window_attention_check(c, heads, window, shift, h=None, w=None, who="window_attention"):
@@ -3944,7 +3943,7 @@ def niqe(img, params, shave=0, block=96):
 # ------------------------------------------------------------------------------------------------
 # Raw video frames (YUV4MPEG2 payloads) to the net and back (csrc/video.hip): the front and the tail of test_video
 # ------------------------------------------------------------------------------------------------
-YUV_SUBSAMPLING = {"420": 0, "444": 1, "mono": 2}   # SRK_YUV_420 / SRK_YUV_444 / SRK_YUV_MONO (include/srk.h)
+YUV_SUBSAMPLING = {"420": _lib.YUV_420, "444": _lib.YUV_444, "mono": _lib.YUV_MONO}
 
 
 class YuvLayout(object):
