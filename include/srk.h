@@ -267,7 +267,9 @@ int srk_absmax(const float* x, size_t n, float* amax_slots, void* stream);
 /* 1 when srk_conv2d_forward(d, ..., ep) with d->algo = SRK_ALGO_MFMA_F16X3 has a kernel: Conv2d / ConvTranspose2d with
  * Cin >= 8, Cout >= 8, and first layers (Cin <= 4 Conv2d, Cout a multiple of 16, also with x_nchw), every output group
  * on the 16-byte store path.  Those kernels (k_conv_bfd, k_conv_bfw, k_conv_bf3_rows) also fill ep->y_amax -- in every
- * arithmetic they run, not only f16x3. */
+ * arithmetic they run, not only f16x3; so do k_c64, the exact-fp32 MFMA kernels and the 4-wave vector form of k_conv_bf3
+ * (stride-1 and Conv2d gathers) while every output group is on the 16-byte path.  srk_conv_result.wrote_amax is the
+ * authority: where it is 0 the slots are left as they were. */
 int srk_conv2d_f16x3_supported(const srk_conv_desc* d, const srk_epilogue* ep, const float* y);
 
 /* ---- convolution (Conv2d / ConvTranspose2d: base_networks.py:42,77,112-113,156; fsrcnn.py:33) */

@@ -118,8 +118,8 @@ __device__ __forceinline__ void store_tile(const MfmaConvParams& P, float* smem_
   const int row0 = lane / Q4, q4 = lane - row0 * Q4;
   const int oc4 = ocb + q4 * 4;
   // running maximum of what the block stores (ep.y_amax: the next layer's f16x3 scale -- a first layer on this kernel used
-  // to cost the trunk behind it an srk_absmax pass); valid when every channel group takes the 16-byte path, which the
-  // host checks before it reports the maximum as written (conv_mfma_gather)
+  // to cost the trunk behind it an srk_absmax pass); valid when every channel group takes the 16-byte path: the host
+  // hands y_amax over only then (launch_variant), and reports the maximum as written only then
   float amax = 0.f;
   const float peeked = amax_peek(P.ep.y_amax, blockIdx.x + wave);
   if (row0 < RPI && oc4 < P.OC) {
@@ -433,8 +433,11 @@ bool conv_mfma_gather_supported(const GatherConv& g, const Epi& ep) {
 }
 
 template <int NT>
-static void launch_variant(bool tapgroup, const MfmaConvParams& P, dim3 grid, size_t lds, hipStream_t s) {
-  note_amax_written(P.ep.y_amax != nullptr && epi_all_vector(P));   // (store_tile: the vector path keeps the maximum)
+static void launch_variant(bool tapgroup, MfmaConvParams P, dim3 grid, size_t lds, hipStream_t s) {
+  // store_tile keeps the maximum of what the 16-byte path stored; the scalar fallback hands back its unfinished sums, so a
+  // layer with a group on it gets no y_amax at all (srk_conv_result.wrote_amax == 0: the slots stay as they are)
+  if (!epi_all_vector(P)) P.ep.y_amax = nullptr;
+  note_amax_written(P.ep.y_amax != nullptr);
   if (tapgroup) {
     note_kernel("k_conv_mfma_tg<%d>", NT);
     launch_lds<&k_conv_mfma_tg<NT>>(grid, dim3(256), lds, s, P);

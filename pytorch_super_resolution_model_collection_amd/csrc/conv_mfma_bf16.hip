@@ -887,6 +887,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_bf3_rows(Bf3Params B) {
 template <int NT>
 static void bf3_launch_vec(const Bf3Params& B, dim3 grid, size_t lds, hipStream_t s) {
   note_kernel("k_conv_bf3<%d,4,vec>", NT);
+  note_amax_written(B.P.ep.y_amax != nullptr);   // (VEC_ONLY: bf3_epilogue keeps the maximum of what it stores)
   launch_lds<&k_conv_bf3<NT, 4, true>>(grid, dim3(256), lds, s, B);
 }
 
@@ -1020,7 +1021,11 @@ int conv_bf3_gather(const GatherConv& g, const float* in, const float* wp, float
                     const float* mask_y, float mask_slope, hipStream_t s) {
   const size_t elems = (size_t)g.KH * g.KW * g.IC * g.OC;
   const uint4* wq = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(wp) + bf3_prepared_offset(elems));
-  return for_each_phase(g, in, wp, out, ep, mask_y, mask_slope,
+  // the block shape, and with it whether the kernel keeps the running maximum (<NT,4,vec> only), is chosen per phase: a
+  // strided TRANS gather, whose phases can fall either side of that choice, gets no y_amax at all (wrote_amax == 0)
+  Epi e = ep;
+  if (g.trans && g.stride > 1) e.y_amax = nullptr;
+  return for_each_phase(g, in, wp, out, e, mask_y, mask_slope,
                         [&](const MfmaConvParams& P) { return bf3_launch_phase(P, wq, s); });
 }
 

@@ -707,6 +707,7 @@ int conv_tapk_gather(const GatherConv& g, const float* in, const float* wp, floa
     long nb = (units + 15) / 16;  // >= 4 pixel groups per wave
     if (nb > 8 * kNumCU) nb = 8 * kNumCU;
     if (nb < 1) nb = 1;
+    note_kernel("k_conv_tapk<%d>", P.OC / 16 >= 4 ? 4 : P.OC / 16);
     switch (P.OC / 16) {
       case 1: hipLaunchKernelGGL(k_conv_tapk<1>, dim3((unsigned)nb), dim3(256), 0, s, P, gpr, units); break;
       case 2: hipLaunchKernelGGL(k_conv_tapk<2>, dim3((unsigned)nb), dim3(256), 0, s, P, gpr, units); break;
