@@ -58,6 +58,10 @@ ground truth) of the net's 8-bit output -- ' NIQE %.4f' on the --test_only line,
 --test_video IN [--video_out OUT] [--video_batch N] (load the checkpoint, super-resolve the YUV4MPEG2 stream IN -- 8-bit
 4:2:0, 4:4:4 or mono; - = stdin -- in batches of N frames from file bytes to file bytes on the device, write OUT, default
 <save_dir>/test_result/SR_result.y4m, - = stdout; honours --tile and --self_ensemble; no training).
+Which flags go with which model and with each other is said once, by the trainer class (sr_trainers: TRAINERS[model_name].
+check_flags(args), a ValueError naming the flag); parse_args reports it as a usage error and itself holds only the rules
+about the run: the modes --niqe_fit / --test_video / --test_only / --test_single against each other and --resume, files
+that must exist, ESRGAN's --vgg_weights when it trains.
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N main.py ..."""
 import argparse
 import os
@@ -131,17 +135,6 @@ def _unit_interval(text):
     return v
 
 
-def _non_negative(text):
-    """--vgg_loss_weight: a finite number >= 0."""
-    try:
-        v = float(text)
-    except ValueError:
-        v = float('nan')
-    if not 0.0 <= v < float('inf'):
-        raise argparse.ArgumentTypeError("--vgg_loss_weight takes a number >= 0, got %r" % (text,))
-    return v
-
-
 def _fft_weight(text):
     """--fft_weight: a finite number >= 0."""
     try:
@@ -153,28 +146,6 @@ def _fft_weight(text):
     return v
 
 
-def _lpips_weight(text):
-    """--lpips_weight: a finite number >= 0."""
-    try:
-        v = float(text)
-    except ValueError:
-        v = float('nan')
-    if not 0.0 <= v < float('inf'):
-        raise argparse.ArgumentTypeError("--lpips_weight takes a number >= 0, got %r" % (text,))
-    return v
-
-
-def _net_interp(text):
-    """--net_interp: a number in [0, 1] (NaN fails both comparisons)."""
-    try:
-        v = float(text)
-    except ValueError:
-        v = float('nan')
-    if not 0.0 <= v <= 1.0:
-        raise argparse.ArgumentTypeError("--net_interp takes a number in [0, 1], got %r" % (text,))
-    return v
-
-
 def _loss_weight(text):
     """--gan_weight / --pixel_weight: a finite number >= 0."""
     try:
@@ -183,17 +154,6 @@ def _loss_weight(text):
         v = float('nan')
     if not 0.0 <= v < float('inf'):
         raise argparse.ArgumentTypeError("a number >= 0 is expected, got %r" % (text,))
-    return v
-
-
-def _ema_decay(text):
-    """--ema_decay: a number in [0, 1) (NaN fails both comparisons)."""
-    try:
-        v = float(text)
-    except ValueError:
-        v = float('nan')
-    if not 0.0 <= v < 1.0:
-        raise argparse.ArgumentTypeError("--ema_decay takes a number in [0, 1), got %r" % (text,))
     return v
 
 
@@ -298,11 +258,10 @@ def _jpeg_prob(text):
 
 
 def parse_args(argv=None):
+    from pytorch_super_resolution_model_collection_amd.sr_trainers import TRAINERS
     p = argparse.ArgumentParser(description="MI355X-native SR collection (reference-compatible CLI)")
     p.add_argument('--model_name', type=str, default='SRGAN',
-                   choices=['SRCNN', 'VDSR', 'ESPCN', 'FSRCNN', 'SRGAN', 'LapSRN', 'EDSR', 'DRCN', 'RCAN', 'RDN', 'SwinIR',
-                            'ESRGAN'],
-                   help='The type of model')
+                   choices=list(TRAINERS), help='The type of model')
     p.add_argument('--data_dir', type=str, default='../Data')
     p.add_argument('--train_dataset', type=_names, default=['DIV2K'], help='The name(s) of the training dataset, comma-separated')
     p.add_argument('--test_dataset', type=_names, default=['Set5', 'Set14', 'Urban100'], help='The name(s) of the test dataset, comma-separated')
@@ -375,14 +334,14 @@ def parse_args(argv=None):
     p.add_argument('--perceptual', action='store_true',
                    help='SRGAN: the VGG feature term trains the generator (ops.perceptual_loss; the reference detaches it). '
                         'Needs --vgg_weights and --num_channels 3')
-    p.add_argument('--vgg_loss_weight', type=_non_negative, default=None, metavar='W',
+    p.add_argument('--vgg_loss_weight', type=float, default=None, metavar='W',
                    help='SRGAN: weight of the VGG feature term in the G loss (default 6e-3, srgan.py:306); W >= 0.  '
                         'ESRGAN: default 1.0')
     p.add_argument('--resume', type=str, nargs='?', const='auto', default=None, metavar='PATH',
                    help='continue training from a training-state file (weights, optimizer state, learning rates, epoch, '
                         'loss history, random generators): PATH, or without one the file this run writes, '
                         '<save_dir>/model/<model_name>_train_state.pkl.  Runs continue at epoch boundaries only')
-    p.add_argument('--ema_decay', type=_ema_decay, default=0.0, metavar='D',
+    p.add_argument('--ema_decay', type=float, default=0.0, metavar='D',
                    help='keep an exponential moving average of the weights, ema += (1 - D) * (w - ema) after every step, '
                         'inside the optimizer kernel; written beside every checkpoint as ..._ema.pkl.  D in [0, 1), '
                         'default 0: none.  Not for DRCN')
@@ -432,7 +391,7 @@ def parse_args(argv=None):
     p.add_argument('--lpips_lin', type=str, default=None, metavar='PATH',
                    help='the linear layers of LPIPS: the `lpips` package\'s vgg.pth (lin{l}.model.1.weight); goes with '
                         '--lpips_vgg')
-    p.add_argument('--lpips_weight', type=_lpips_weight, default=0.0, metavar='W',
+    p.add_argument('--lpips_weight', type=float, default=0.0, metavar='W',
                    help='add W * LPIPS(prediction, target) to the training loss (LapSRN: both levels); W >= 0, default 0: '
                         'none.  Needs --lpips_vgg and --lpips_lin; HR patches of at least 16 on a side (LapSRN: 32).  Not '
                         'for SRGAN and DRCN')
@@ -458,7 +417,7 @@ def parse_args(argv=None):
                    help='ESRGAN: weight of the relativistic average GAN term in the G loss (default 5e-3)')
     p.add_argument('--pixel_weight', type=_loss_weight, default=1e-2, metavar='W',
                    help='ESRGAN: weight of the L1 pixel term in the G loss of the adversarial phase (default 1e-2)')
-    p.add_argument('--net_interp', type=_net_interp, default=None, metavar='A',
+    p.add_argument('--net_interp', type=float, default=None, metavar='A',
                    help='ESRGAN, with --test_only / --test_single: evaluate (1 - A) * the pre-trained generator + A * the '
                         'adversarially trained one (network interpolation of the ESRGAN paper); A in [0, 1]')
     p.add_argument('--discriminator', type=str, default=None, choices=['vgg', 'unet'],
@@ -468,7 +427,7 @@ def parse_args(argv=None):
     p.add_argument('--gan_type', type=str, default=None, choices=['ragan', 'vanilla'],
                    help='ESRGAN: the GAN loss on the discriminator\'s logits: ragan (relativistic average; default with '
                         '--discriminator vgg) or vanilla (default with, and the only one for, --discriminator unet)')
-    p.add_argument('--unet_feat', type=_positive, default=None, metavar='F',
+    p.add_argument('--unet_feat', type=int, default=None, metavar='F',
                    help='ESRGAN with --discriminator unet: channels of the U-Net\'s first layer (default 64)')
     p.add_argument('--vgg_layers', type=str, default=None, metavar='SPEC',
                    help='ESRGAN: train on Real-ESRGAN\'s multi-layer VGG feature term instead of the single conv5_4 one: '
@@ -508,136 +467,21 @@ def parse_args(argv=None):
             p.error('--niqe_params %s exists: --niqe_fit does not overwrite a parameter file' % args.niqe_params)
     elif args.niqe_params is not None and not os.path.isfile(args.niqe_params):
         p.error('--niqe_params %s: no such file' % args.niqe_params)
-    esrgan = args.model_name == 'ESRGAN'
-    if args.vgg_layers is not None:
-        if not esrgan:
-            p.error('--vgg_layers: only ESRGAN has the multi-layer VGG feature term, not %s' % args.model_name)
-        if not args.vgg_weights:
-            p.error('--vgg_layers needs --vgg_weights PATH (a torchvision vgg19 state_dict file)')
-        from pytorch_super_resolution_model_collection_amd.sr_trainers import parse_vgg_layers
-        try:
-            parse_vgg_layers(args.vgg_layers)
-        except ValueError as e:
-            p.error('--vgg_layers %s: %s' % (args.vgg_layers, e))
-    for flag in ('discriminator', 'gan_type', 'unet_feat'):
-        if getattr(args, flag) is not None and not esrgan:
-            p.error('--%s: only ESRGAN chooses its discriminator and GAN loss, not %s' % (flag, args.model_name))
-    if esrgan:
-        if args.unet_feat is not None and args.discriminator != 'unet':
-            p.error('--unet_feat: only the U-Net discriminator has a feature count to set (pass --discriminator unet)')
-        if args.discriminator == 'unet' and args.gan_type == 'ragan':
-            p.error('--gan_type ragan: the relativistic average loss takes one logit a sample, the U-Net discriminator '
-                    'gives one a pixel (use --gan_type vanilla with --discriminator unet)')
-        if args.discriminator == 'unet' and args.crop_size % 8:
-            p.error('--crop_size %d is not a multiple of 8, which the three stride-2 stages of --discriminator unet need'
-                    % args.crop_size)
-        args.discriminator = args.discriminator or 'vgg'
-        args.gan_type = args.gan_type or ('vanilla' if args.discriminator == 'unet' else 'ragan')
-        if args.discriminator == 'unet' and args.unet_feat is None:
-            args.unet_feat = 64
-    if args.vgg_loss_weight is None:
-        args.vgg_loss_weight = 1.0 if esrgan else 6e-3
-    if esrgan:
-        if args.scale_factor != 4:
-            p.error('--scale_factor %d: RRDBNet upsamples by 4 only' % args.scale_factor)
-        if args.tile is not None:
-            p.error('--tile: the RRDB trunk reaches about 350 LR pixels to each side (23 blocks), a tile would be mostly '
-                    'halo; ESRGAN\'s pictures run in one pass (drop --tile)')
-        if args.rrdb_growth % 16 or args.rrdb_growth > 64:
-            p.error('--rrdb_growth %d: the slice convolutions write 16, 32, 48 or 64 channels' % args.rrdb_growth)
-        if args.num_channels != 3:
-            p.error('--num_channels %d: ESRGAN\'s VGG feature term reads RGB, use --num_channels 3' % args.num_channels)
-        if args.perceptual:
-            p.error('--perceptual: ESRGAN\'s feature term always trains the generator (drop --perceptual)')
-        if not args.vgg_weights and not (args.test_only or args.test_single):
-            p.error('--vgg_weights PATH is required: ESRGAN\'s adversarial phase trains on VGG19 conv5_4 features (a '
-                    'torchvision vgg19 state_dict file)')
-        for flag in ('ssim_weight', 'fft_weight', 'lpips_weight'):
-            if getattr(args, flag) > 0:
-                p.error('--%s %g: ESRGAN\'s adversarial phase has its own three terms (--pixel_weight, --vgg_loss_weight, '
-                        '--gan_weight); use --%s 0' % (flag, getattr(args, flag), flag))
-        if int(os.environ.get('WORLD_SIZE', '1')) > 1:
-            p.error('ESRGAN trains on one GPU (a world size of %s): launch main.py without torch.distributed.run'
-                    % os.environ['WORLD_SIZE'])
-    if args.net_interp is not None and not esrgan:
-        p.error('--net_interp: only ESRGAN has a pre-trained and an adversarial generator to blend, not %s' % args.model_name)
-    if args.net_interp is not None and not (args.test_only or args.test_single):
-        p.error('--net_interp blends two finished checkpoints: it goes with --test_only or --test_single')
-    if args.model_name == 'SwinIR':
-        if args.tile is not None:
-            p.error('--tile: SwinIR\'s WindowAttention partitions the whole image into windows, its pictures run in one '
-                    'pass (drop --tile)')
-        if args.swinir_dim % args.swinir_heads:
-            p.error('--swinir_heads %d does not divide --swinir_dim %d' % (args.swinir_heads, args.swinir_dim))
-        if args.swinir_dim // args.swinir_heads > 32:
-            p.error('--swinir_dim %d / --swinir_heads %d: a head dimension of %d exceeds 32'
-                    % (args.swinir_dim, args.swinir_heads, args.swinir_dim // args.swinir_heads))
-        if not 2 <= args.swinir_window <= 8:
-            p.error('--swinir_window %d is not in 2 .. 8' % args.swinir_window)
-        if args.swinir_upsampler == 'pixelshuffle' and args.scale_factor not in (2, 3, 4, 8):
-            p.error('--scale_factor %d: SwinIR\'s pixelshuffle upsampler works by 2, 3, 4 or 8' % args.scale_factor)
-        if args.crop_size % args.scale_factor or (args.crop_size // args.scale_factor) % args.swinir_window:
-            p.error('--crop_size %d / --scale_factor %d is not a multiple of --swinir_window %d'
-                    % (args.crop_size, args.scale_factor, args.swinir_window))
-    if args.model_name == 'RDN' and (args.rdn_growth % 16 or args.rdn_growth > 64):
-        p.error('--rdn_growth %d: RDN\'s slice convolutions write 16, 32, 48 or 64 channels' % args.rdn_growth)
-    if args.model_name == 'RDN' and args.scale_factor not in (2, 3, 4):
-        p.error('--scale_factor %d: RDN upsamples by 2, 3 or 4' % args.scale_factor)
-    if bool(args.lpips_vgg) != bool(args.lpips_lin):
-        p.error('--lpips_vgg and --lpips_lin come together: LPIPS needs the vgg16 weights and its linear layers')
-    if args.lpips_weight > 0 and not args.lpips_vgg:
-        p.error('--lpips_weight %g needs --lpips_vgg PATH and --lpips_lin PATH' % args.lpips_weight)
-    if args.lpips_vgg and args.num_channels != 3:
-        p.error('--lpips_vgg: LPIPS reads RGB, use --num_channels 3 (got %d; scoring the restored-colour picture of a Y '
-                'model is not supported)' % args.num_channels)
-    if args.lpips_weight > 0 and args.model_name in ('SRGAN', 'DRCN'):
-        p.error('--lpips_weight %g: %s has no LPIPS term (SRGAN trains on an adversarial content term, DRCN through its '
-                'fused recursive-supervision head); use --lpips_weight 0 or another model'
-                % (args.lpips_weight, args.model_name))
-    if args.model_name == 'RCAN' and args.tile is not None:
-        p.error('--tile: RCAN\'s channel attention depends on the whole image, its pictures run in one pass (drop --tile)')
-    if args.model_name == 'RCAN' and 64 % args.rcan_reduction:
-        p.error('--rcan_reduction %d does not divide RCAN\'s 64 channels' % args.rcan_reduction)
-    if args.model_name == 'RCAN' and args.scale_factor not in (2, 4, 8):
-        p.error('--scale_factor %d: RCAN upsamples by 2, 4 or 8' % args.scale_factor)
-    for flag in ('degrade', 'degrade_test', 'jpeg_quality', 'jpeg_test'):
-        if getattr(args, flag) and args.synthetic:
-            p.error('--%s: synthetic patches are not degraded; train and test on image folders (drop --synthetic)' % flag)
-    for flag, on in (('degrade2', args.degrade2 is not None), ('usm', args.usm), ('degrade2_test', args.degrade2_test is not None)):
-        if on and args.synthetic:
-            p.error('--%s: synthetic patches are not degraded; train and test on image folders (drop --synthetic)' % flag)
-    if args.degrade2 is not None and args.degrade:
-        p.error('--degrade2 and --degrade are two degradation models: give one')
-    if args.degrade2 is not None and args.jpeg_quality:
-        p.error('--jpeg_quality belongs to --degrade; --degrade2\'s chain has JPEG stages of its own (jpeg_range, jpeg_range2 '
-                'in its settings file)')
-    if args.degrade2_test is not None and (args.degrade_test or args.jpeg_test):
-        p.error('--degrade2_test brings its own blur, noise and JPEG: give neither --degrade_test nor --jpeg_test with it')
-    if args.jpeg_quality and not args.degrade:
-        p.error('--jpeg_quality is a stage of the training degradation: pass --degrade too (--blur_prob 0 --noise_sigma 0,0 '
-                'leaves JPEG alone)')
-    if args.ema_decay > 0 and args.model_name == 'DRCN':
-        p.error('--ema_decay %g: DRCN keeps no EMA of its weights (its combine weights w train outside the flat '
-                'parameter buffer); use --ema_decay 0 or another model' % args.ema_decay)
     if args.resume and args.test_only:
         p.error('--resume continues a training run; --test_only does not train')
-    if (args.perceptual or args.vgg_weights) and args.model_name not in ('SRGAN', 'ESRGAN'):
-        p.error('%s: only SRGAN has a VGG feature term, not %s'
-                % ('--perceptual' if args.perceptual else '--vgg_weights', args.model_name))
-    if args.perceptual and not args.vgg_weights:
-        p.error('--perceptual needs --vgg_weights PATH (a torchvision vgg19 state_dict file)')
-    if (args.perceptual or args.vgg_weights) and args.num_channels != 3:
-        p.error('%s: the VGG head reads RGB, use --num_channels 3 (got %d)'
-                % ('--perceptual' if args.perceptual else '--vgg_weights', args.num_channels))
-    if args.ssim_weight > 0 and args.model_name in ('SRGAN', 'DRCN'):
-        p.error('--ssim_weight %g: %s has no SSIM mix (SRGAN trains on an adversarial content term, DRCN through its fused '
-                'recursive-supervision head); use --ssim_weight 0 or another model' % (args.ssim_weight, args.model_name))
-    if args.fft_weight > 0 and args.model_name in ('SRGAN', 'DRCN'):
-        p.error('--fft_weight %g: %s has no frequency-domain term (SRGAN trains on an adversarial content term, DRCN through '
-                'its fused recursive-supervision head); use --fft_weight 0 or another model' % (args.fft_weight, args.model_name))
-    if args.fft_weight > 0 and args.crop_size > 256:
-        p.error('--fft_weight %g: the dense DFT takes HR patches of at most 256 on a side, --crop_size is %d'
-                % (args.fft_weight, args.crop_size))
+    if args.net_interp is not None and not (args.test_only or args.test_single):
+        p.error('--net_interp blends two finished checkpoints: it goes with --test_only or --test_single')
+    # which flags go with the model and with each other: the trainer class says (sr_trainers: check_flags)
+    trainer = TRAINERS[args.model_name]
+    try:
+        trainer.check_flags(args)
+    except (ValueError, NotImplementedError) as e:   # (NotImplementedError: a model without data parallelism)
+        p.error(str(e))
+    if args.model_name == 'ESRGAN' and not args.vgg_weights and not (args.test_only or args.test_single):
+        p.error('--vgg_weights PATH is required: ESRGAN\'s adversarial phase trains on VGG19 conv5_4 features (a '
+                'torchvision vgg19 state_dict file)')
+    for flag, value in trainer.flag_defaults(args).items():
+        setattr(args, flag, value)
     return check_args(args)
 
 

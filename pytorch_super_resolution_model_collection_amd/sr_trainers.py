@@ -61,45 +61,48 @@ def apply_lr_decay(kind, epoch, *optimizers):
     return True
 
 
+def _name(args, kind):
+    """What a refusal calls the model: args.model_name, else the kind in capitals."""
+    return getattr(args, "model_name", None) or kind.upper()
+
+
 def check_data_flags(args):
-    """The loader's degradation flags against each other and against --synthetic, as main.py refuses them."""
+    """The loader's degradation flags against each other and against --synthetic."""
     degrade2 = getattr(args, "degrade2", None) is not None      # ({}: --degrade2 with its defaults)
     degrade2_test = getattr(args, "degrade2_test", None) is not None
-    for flag in ("degrade", "degrade_test", "jpeg_quality", "jpeg_test"):
-        if getattr(args, flag, None) and getattr(args, "synthetic", False):
-            raise ValueError("%s: synthetic patches are not degraded, train and test on image folders (main.py "
-                             "--%s without --synthetic)" % (flag, flag))
-    for flag, on in (("degrade2", degrade2), ("usm", bool(getattr(args, "usm", False))), ("degrade2_test", degrade2_test)):
+    flags = [(flag, bool(getattr(args, flag, None))) for flag in ("degrade", "degrade_test", "jpeg_quality", "jpeg_test")]
+    for flag, on in flags + [("degrade2", degrade2), ("usm", bool(getattr(args, "usm", False))), ("degrade2_test", degrade2_test)]:
         if on and getattr(args, "synthetic", False):
-            raise ValueError("%s: synthetic patches are not degraded, train and test on image folders (main.py "
-                             "--%s without --synthetic)" % (flag, flag))
+            raise ValueError("--%s: synthetic patches are not degraded; train and test on image folders (drop --synthetic)"
+                             % flag)
     if degrade2 and getattr(args, "degrade", False):
-        raise ValueError("degrade2 and degrade are two degradation models: give one (main.py --degrade2 or --degrade)")
+        raise ValueError("--degrade2 and --degrade are two degradation models: give one")
     if degrade2 and getattr(args, "jpeg_quality", None):
-        raise ValueError("jpeg_quality belongs to --degrade; degrade2's chain has JPEG stages of its own (jpeg_range, "
-                         "jpeg_range2 in its settings)")
+        raise ValueError("--jpeg_quality belongs to --degrade; --degrade2's chain has JPEG stages of its own (jpeg_range, "
+                         "jpeg_range2 in its settings file)")
     if degrade2_test and (getattr(args, "degrade_test", None) or getattr(args, "jpeg_test", None)):
-        raise ValueError("degrade2_test brings its own blur, noise and JPEG: give neither degrade_test nor jpeg_test with it")
+        raise ValueError("--degrade2_test brings its own blur, noise and JPEG: give neither --degrade_test nor --jpeg_test "
+                         "with it")
     if getattr(args, "jpeg_quality", None) and not getattr(args, "degrade", False):
-        raise ValueError("jpeg_quality is a stage of the training degradation (main.py --jpeg_quality with --degrade)")
+        raise ValueError("--jpeg_quality is a stage of the training degradation: pass --degrade too (--blur_prob 0 "
+                         "--noise_sigma 0,0 leaves JPEG alone)")
 
 
 def check_perceptual_args(args, kind):
-    """--vgg_weights / --perceptual / --vgg_loss_weight of main.py: the VGG feature term belongs to the SRGAN step, reads
-    RGB, and trains only with weights to extract features with.  Raises ValueError naming the flag."""
+    """--vgg_weights / --perceptual / --vgg_loss_weight: the VGG feature term belongs to the SRGAN step, reads RGB, and
+    trains only with weights to extract features with.  Raises ValueError naming the flag."""
     perceptual = bool(getattr(args, "perceptual", False))
     vgg_weights = getattr(args, "vgg_weights", None)
+    flag = "--perceptual" if perceptual else "--vgg_weights"
     weight = getattr(args, "vgg_loss_weight", None)
-    if weight is not None and not float(weight) >= 0.0:
-        raise ValueError("vgg_loss_weight %r must be >= 0 (main.py --vgg_loss_weight)" % (weight,))
+    if weight is not None and not 0.0 <= float(weight) < float("inf"):
+        raise ValueError("--vgg_loss_weight %r must be a finite number >= 0" % (weight,))
     if (perceptual or vgg_weights) and kind not in ("srgan", "esrgan"):
-        raise ValueError("%s: only SRGAN has a VGG feature term (main.py --model_name SRGAN)"
-                         % ("perceptual" if perceptual else "vgg_weights"))
+        raise ValueError("%s: only SRGAN has a VGG feature term, not %s" % (flag, _name(args, kind)))
     if perceptual and not vgg_weights:
-        raise ValueError("perceptual: needs the VGG19 weights to extract features with (main.py --vgg_weights PATH)")
+        raise ValueError("--perceptual needs --vgg_weights PATH (a torchvision vgg19 state_dict file)")
     if (perceptual or vgg_weights) and getattr(args, "num_channels", 3) != 3:
-        raise ValueError("%s: the VGG head reads RGB (main.py --num_channels 3)"
-                         % ("perceptual" if perceptual else "vgg_weights"))
+        raise ValueError("%s: the VGG head reads RGB, use --num_channels 3 (got %r)" % (flag, args.num_channels))
 
 
 # trainers.mixed_loss's terms (a new one: here and there): flag -> (what a kind without it lacks, the value that leaves it out)
@@ -108,33 +111,36 @@ TERM_FLAGS = {"ssim_weight": ("SSIM mix", 0.0), "fft_weight": ("frequency-domain
 
 
 def check_term_args(args, kind, name, flags):
-    """SRGAN, DRCN and ESRGAN train on losses of their own: a term weight > 0 is refused, naming the flag."""
+    """The kinds of trainers.OWN_LOSS_KINDS train on losses of their own: a term weight > 0 is refused, naming the flag."""
     for flag in flags:
-        if kind in ("srgan", "drcn", "esrgan") and (getattr(args, flag, 0.0) or 0.0) > 0:
-            raise ValueError("%s: %s has no %s (main.py --%s)" % (flag, name, TERM_FLAGS[flag][0], flag))
+        weight = getattr(args, flag, 0.0) or 0.0
+        if kind in trainers.OWN_LOSS_KINDS and weight > 0:
+            raise ValueError("--%s %g: %s has no %s (SRGAN and ESRGAN train on adversarial content terms, DRCN through its "
+                             "fused recursive-supervision head); use --%s 0 or another model"
+                             % (flag, weight, name, TERM_FLAGS[flag][0], flag))
 
 
 def check_lpips_args(args, kind):
-    """--lpips_vgg / --lpips_lin / --lpips_weight of main.py: the two weight files come together, LPIPS reads RGB, and the
-    training term belongs to the kinds trainers.mixed_loss serves.  Raises ValueError naming the flag."""
+    """--lpips_vgg / --lpips_lin / --lpips_weight: the two weight files come together, LPIPS reads RGB, and the training
+    term belongs to the kinds trainers.mixed_loss serves.  Raises ValueError naming the flag."""
     vgg, lin = getattr(args, "lpips_vgg", None), getattr(args, "lpips_lin", None)
     weight = getattr(args, "lpips_weight", None) or 0.0
     if not 0.0 <= float(weight) < float("inf"):
-        raise ValueError("lpips_weight %r must be a finite number >= 0 (main.py --lpips_weight)" % (weight,))
+        raise ValueError("--lpips_weight %r must be a finite number >= 0" % (weight,))
     if bool(vgg) != bool(lin):
-        raise ValueError("%s: LPIPS needs both weight files (main.py --lpips_vgg PATH --lpips_lin PATH)"
-                         % ("lpips_lin" if vgg else "lpips_vgg"))
+        raise ValueError("--lpips_vgg and --lpips_lin come together: LPIPS needs the vgg16 weights and its linear layers")
     if weight > 0 and not vgg:
-        raise ValueError("lpips_weight: needs the weights of the LPIPS net (main.py --lpips_vgg PATH --lpips_lin PATH)")
-    check_term_args(args, kind, kind.upper(), ("lpips_weight",))
+        raise ValueError("--lpips_weight %g needs --lpips_vgg PATH and --lpips_lin PATH" % weight)
+    check_term_args(args, kind, _name(args, kind), ("lpips_weight",))
     if vgg and getattr(args, "num_channels", 3) != 3:
-        raise ValueError("lpips_vgg: LPIPS reads RGB (main.py --num_channels 3)")
+        raise ValueError("--lpips_vgg: LPIPS reads RGB, use --num_channels 3 (got %r; scoring the restored-colour picture "
+                         "of a Y model is not supported)" % (args.num_channels,))
 
 
 def parse_vgg_layers(spec):
-    """--vgg_layers of main.py: `name:weight,...` or the word `realesrgan` (Real-ESRGAN's five taps, ops.
-    REALESRGAN_VGG_LAYERS), or a mapping / pair sequence given in code.  -> ops.vgg_layer_plan's [(name, index, weight)],
-    None for no spec.  ValueError naming the culprit."""
+    """--vgg_layers: `name:weight,...` or the word `realesrgan` (Real-ESRGAN's five taps, ops.REALESRGAN_VGG_LAYERS), or a
+    mapping / pair sequence given in code.  -> ops.vgg_layer_plan's [(name, index, weight)], None for no spec.  ValueError
+    naming the culprit."""
     if spec is None:
         return None
     if isinstance(spec, str):
@@ -145,8 +151,7 @@ def parse_vgg_layers(spec):
             for item in spec.split(","):
                 name, sep, weight = item.strip().partition(":")
                 if not sep or not name.strip() or not weight.strip():
-                    raise ValueError("vgg_layers: %r is not name:weight (main.py --vgg_layers conv1_2:0.1,... or "
-                                     "realesrgan)" % (item,))
+                    raise ValueError("vgg_layers: %r is not name:weight (conv1_2:0.1,... or realesrgan)" % (item,))
                 pairs.append((name.strip(), weight.strip()))
     else:
         pairs = spec
@@ -160,43 +165,60 @@ def check_vgg_layers_args(args, kind):
     if spec is None:
         return None
     if kind != "esrgan":
-        raise ValueError("vgg_layers: only ESRGAN has the multi-layer VGG feature term (main.py --model_name ESRGAN)")
+        raise ValueError("--vgg_layers: only ESRGAN has the multi-layer VGG feature term, not %s" % _name(args, kind))
     if not getattr(args, "vgg_weights", None):
-        raise ValueError("vgg_layers: needs the VGG19 weights to extract features with (main.py --vgg_weights PATH)")
-    return parse_vgg_layers(spec)
+        raise ValueError("--vgg_layers needs --vgg_weights PATH (a torchvision vgg19 state_dict file)")
+    try:
+        return parse_vgg_layers(spec)
+    except ValueError as e:
+        raise ValueError("--vgg_layers %s: %s" % (spec, e))
 
 
 DISCRIMINATORS = ("vgg", "unet")
 
 
 def check_discriminator_args(args, kind):
-    """--discriminator / --gan_type / --unet_feat of main.py belong to ESRGAN's adversarial phase; the relativistic loss
-    takes one logit a sample, so it does not go with the U-Net's logit map, whose three stride-2 stages need a crop size
-    that is a multiple of 8.  Raises ValueError naming the flag.  -> (discriminator, gan_type, unet_feat) for ESRGAN."""
+    """--discriminator / --gan_type / --unet_feat belong to ESRGAN's adversarial phase; the relativistic loss takes one
+    logit a sample, so it does not go with the U-Net's logit map, whose three stride-2 stages need a crop size that is a
+    multiple of 8.  Raises ValueError naming the flag.  -> (discriminator, gan_type, unet_feat) for ESRGAN, the defaults
+    of the three filled in (ragan with vgg, vanilla with unet, 64 features)."""
     disc, gan, feat = (getattr(args, n, None) for n in ("discriminator", "gan_type", "unet_feat"))
     if kind != "esrgan":
         for flag, v in (("discriminator", disc), ("gan_type", gan), ("unet_feat", feat)):
             if v is not None:
-                raise ValueError("%s: only ESRGAN chooses its discriminator and GAN loss (main.py --model_name ESRGAN)" % flag)
+                raise ValueError("--%s: only ESRGAN chooses its discriminator and GAN loss, not %s" % (flag, _name(args, kind)))
         return None
     disc = disc or "vgg"
     if disc not in DISCRIMINATORS:
-        raise ValueError("discriminator %r is not one of %s (main.py --discriminator)" % (disc, ", ".join(DISCRIMINATORS)))
+        raise ValueError("--discriminator %r is not one of %s" % (disc, ", ".join(DISCRIMINATORS)))
     gan = gan or ("vanilla" if disc == "unet" else "ragan")
     if gan not in trainers.GAN_TYPES:
-        raise ValueError("gan_type %r is not one of %s (main.py --gan_type)" % (gan, ", ".join(trainers.GAN_TYPES)))
+        raise ValueError("--gan_type %r is not one of %s" % (gan, ", ".join(trainers.GAN_TYPES)))
     if disc == "unet" and gan == "ragan":
-        raise ValueError("gan_type 'ragan': the relativistic average loss takes one logit a sample, the U-Net discriminator "
-                         "gives one a pixel (main.py --gan_type vanilla with --discriminator unet)")
+        raise ValueError("--gan_type ragan: the relativistic average loss takes one logit a sample, the U-Net discriminator "
+                         "gives one a pixel (use --gan_type vanilla with --discriminator unet)")
     if feat is not None and disc != "unet":
-        raise ValueError("unet_feat: only the U-Net discriminator has a feature count to set (main.py --discriminator unet)")
+        raise ValueError("--unet_feat: only the U-Net discriminator has a feature count to set (pass --discriminator unet)")
     if feat is not None and int(feat) < 1:
-        raise ValueError("unet_feat %r must be a whole number >= 1 (main.py --unet_feat)" % (feat,))
+        raise ValueError("--unet_feat %r must be a whole number >= 1" % (feat,))
     crop = getattr(args, "crop_size", None)
     if disc == "unet" and crop is not None and int(crop) % 8:
-        raise ValueError("crop_size %d is not a multiple of 8, which the U-Net discriminator's three stride-2 stages need "
-                         "(main.py --crop_size)" % int(crop))
+        raise ValueError("--crop_size %d is not a multiple of 8, which the three stride-2 stages of --discriminator unet need"
+                         % int(crop))
     return disc, gan, 64 if feat is None else int(feat)
+
+
+def check_one_gpu(name):
+    """ESRGAN and DRCN: no data parallelism (WORLD_SIZE is what torch.distributed.run sets)."""
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise NotImplementedError("%s trains on one GPU (a world size of %s): data parallelism is not implemented for it "
+                                  "(launch main.py without torch.distributed.run)" % (name, os.environ["WORLD_SIZE"]))
+
+
+def check_growth(flag, growth):
+    """--rdn_growth / --rrdb_growth: what the slice convolutions of a dense block can write."""
+    if growth % 16 or growth > 64:
+        raise ValueError("--%s %d: the slice convolutions write 16, 32, 48 or 64 channels" % (flag, growth))
 
 
 def discriminator_kind(state_dict):
@@ -240,8 +262,47 @@ def _option(args, name, value=None, default=None):
 
 class _Trainer(object):
     kind = None
+    decay_kind = property(lambda self: self.kind)   # whose LR_DECAY rule lr_decay applies; a subclass names another kind's
+    pre_upsample = False     # the net takes the bicubic-upsampled picture (SRCNN, VDSR, DRCN)
+    edsr_ckpt_name = False   # checkpoint files named as edsr.py:324-337 (ch / batch / epoch / lr), not as srcnn.py:260-269
+    HYPER = {}               # the model's hyper-parameter flags and their defaults
+    VGG_LOSS_WEIGHT = 6e-3   # --vgg_loss_weight's default (srgan.py:306)
+
+    @classmethod
+    def hyper(cls, args):
+        """{flag: args.<flag>, else its default} for cls.HYPER's flags, for args objects with and without the field."""
+        return {flag: getattr(args, flag, None) or default for flag, default in cls.HYPER.items()}
+
+    @classmethod
+    def check_flags(cls, args):
+        """Every rule about which flags go with this model and with each other, on the host: the one place main.py's
+        usage errors and a trainer built from code take them from.  The rules common to all models are here (the check_*
+        helpers); a subclass puts its own in front and calls this.  Raises ValueError naming the flag as the user types
+        it.  -> (the parsed --vgg_layers plan or None, ESRGAN's (discriminator, gan_type, unet_feat) or None)."""
+        name = _name(args, cls.kind)
+        check_term_args(args, cls.kind, name, ("ssim_weight", "fft_weight"))
+        fft, crop = getattr(args, "fft_weight", None) or 0.0, getattr(args, "crop_size", None)
+        if fft > 0 and crop is not None and crop > 256:
+            raise ValueError("--fft_weight %g: the dense DFT takes HR patches of at most 256 on a side, --crop_size is %d"
+                             % (fft, crop))
+        check_perceptual_args(args, cls.kind)
+        check_lpips_args(args, cls.kind)      # (lpips_weight is refused there, between the checks of its files)
+        vgg_layers = check_vgg_layers_args(args, cls.kind)
+        disc_args = check_discriminator_args(args, cls.kind)
+        if getattr(args, "net_interp", None) is not None and cls.kind != "esrgan":
+            raise ValueError("--net_interp: only ESRGAN has a pre-trained and an adversarial generator to blend, not %s" % name)
+        check_data_flags(args)
+        optim._check_ema_decay(getattr(args, "ema_decay", 0.0))
+        return vgg_layers, disc_args
+
+    @classmethod
+    def flag_defaults(cls, args):
+        """{flag: value} of the flags whose default depends on the model or on another flag, for accepted args."""
+        weight = getattr(args, "vgg_loss_weight", None)
+        return {"vgg_loss_weight": cls.VGG_LOSS_WEIGHT if weight is None else float(weight)}
 
     def __init__(self, args):
+        self.vgg_layers, self.disc_args = type(self).check_flags(args)
         # the reference copies args field by field (edsr.py:49-65)
         for k in ("model_name", "train_dataset", "test_dataset", "crop_size", "num_threads", "num_channels",
                   "scale_factor", "num_epochs", "save_epochs", "batch_size", "test_batch_size", "lr", "data_dir",
@@ -249,15 +310,7 @@ class _Trainer(object):
             setattr(self, k, getattr(args, k, None))
         self.args = args
         self.steps_per_epoch = getattr(args, "steps_per_epoch", 8)
-        check_term_args(args, self.kind, self.model_name, ("ssim_weight", "fft_weight"))
-        check_perceptual_args(args, self.kind)
-        check_lpips_args(args, self.kind)      # (lpips_weight is refused there, between the checks of its files)
-        self.vgg_layers = check_vgg_layers_args(args, self.kind)
-        self.disc_args = check_discriminator_args(args, self.kind)
-        check_data_flags(args)
         self.ema_decay = optim._check_ema_decay(getattr(args, "ema_decay", 0.0))
-        if self.kind == "drcn" and self.ema_decay > 0:
-            raise ValueError("ema_decay: %s keeps no EMA of its weights (main.py --ema_decay)" % self.model_name)
         self.resume = getattr(args, "resume", None)
         self.use_ema = bool(getattr(args, "use_ema", False))
         if not torch.cuda.is_available():
@@ -271,8 +324,8 @@ class _Trainer(object):
     def build_model(self):
         raise NotImplementedError
 
-    def lr_decay(self, epoch, opt):
-        apply_lr_decay(self.kind, epoch, opt)
+    def lr_decay(self, epoch, *optimizers):
+        apply_lr_decay(self.decay_kind, epoch, *optimizers)
 
     def build_step(self):
         """(flat parameters, optimizer, DataParallel or None, eager step function) of the freshly built model."""
@@ -371,22 +424,21 @@ class _Trainer(object):
         return int(state["epochs_done"]), list(state["history"])
 
     def begin_epoch(self, epoch):
-        """Top of every epoch, before its first step: the reference's LR decay (and any per-model schedule)."""
-        self.lr_decay(epoch, self.optimizer)
+        """Top of every epoch, before its first step: the reference's LR decay of every optimizer (and any per-model
+        schedule)."""
+        self.lr_decay(epoch, *self._optimizers().values())
+
+    def _shave(self, target):
+        """The part of a target the net's output covers: all of it, but for SRCNN."""
+        return target
 
     def prepare(self, inp, target):
         """(input, target) of the data loader -> the tensors the train step consumes, on the device:
-          SRCNN   y = img_interp(input, r) (bicubic), x = shave(target, 8)               (srcnn.py:116-125)
-          VDSR    y = img_interp(input, r), x = target                                    (vdsr.py:133-142)
-          LapSRN  y = input, x_coarse = img_interp(target, 1/r*2), x_finer = target       (lapsrn.py:179-188)
+          SRCNN   y = img_interp(input, r) (bicubic), x = shave(target, 8)               (srcnn.py:116-125; its override)
+          VDSR    y = img_interp(input, r), x = target                 (vdsr.py:133-142; drcn.py:183-190 alike)
+          LapSRN  y = input, x_coarse = img_interp(target, 1/r*2), x_finer = target       (lapsrn.py:179-188; its override)
         utils.img_interp is the bit-exact GPU form of the reference's per-image PIL loop."""
-        if self.kind == "srcnn":
-            return utils.img_interp(inp, self.scale_factor), utils.shave(target, 8).contiguous()
-        if self.kind in ("vdsr", "drcn"):    # drcn.py:183-190 as vdsr.py
-            return utils.img_interp(inp, self.scale_factor), target
-        if self.kind == "lapsrn":
-            return inp, utils.img_interp(target, 1 / self.scale_factor * 2), target
-        return inp, target
+        return self._net_input(inp), target
 
     def load_dataset(self, dataset, is_train=True):
         """edsr.py:67-84 / srgan.py:110-129: the image-folder loaders of data.py behind the reference's directory layout
@@ -444,10 +496,17 @@ class _Trainer(object):
                                     rank=self.rank, world=self.world)
         return data.PatchLoader(ds, bs, shuffle=shuffle, num_threads=self.num_threads or 4)
 
-    def _announce_data(self):
+    def open_data(self, loader):
+        """The training batches of train(): `loader`, else the image folders, else None (seeded synthetic patches); says
+        which on rank 0."""
+        self.data_source = "loader"
+        if loader is None:
+            loader = self.load_dataset(self.train_dataset, is_train=True)
+            self.data_source = "folder" if loader is not None else "synthetic"
         if self.rank == 0:
             print("training data: %s%s" % (self.data_source, "" if self.data_source != "folder" else
                                            " %s under %s" % (self.train_dataset, self.data_dir)))
+        return loader
 
     def _channels(self, *tensors):
         """num_channels == 1: only the Y channel is super-resolved (edsr.py:139-142: hr[:, 0].unsqueeze(1))."""
@@ -463,38 +522,50 @@ class _Trainer(object):
         self.model.to(self.device).train()
         utils.print_network(self.model) if self.rank == 0 else None
         self.flat, self.optimizer, self.dp, step = self.build_step()
-        avg_loss = []
-        self.data_source = "loader"
-        if loader is None:
-            loader = self.load_dataset(self.train_dataset, is_train=True)
-            self.data_source = "folder" if loader is not None else "synthetic"
-        self._announce_data()
-        done = 0
-        if state is not None:
-            done, avg_loss = self.load_training_state(state, loader)
+        loader = self.open_data(loader)
+        done, avg_loss = (0, []) if state is None else self.load_training_state(state, loader)
         trainers.quiesce_gc()    # no full cyclic collection (~80 ms) inside a step from here on
-        for epoch in range(done, self.num_epochs):
-            self.begin_epoch(epoch)
-            batches = loader if loader is not None else synthetic_loader(self.kind, self.args, self.steps_per_epoch,
-                                                                         self.device, 1234 + epoch * self.world + self.rank)
-            total, n = torch.zeros((), device=self.device), 0
-            for batch in batches:
+
+        def batches(epoch):
+            for batch in loader if loader is not None else synthetic_loader(self.kind, self.args, self.steps_per_epoch,
+                                                                            self.device, 1234 + epoch * self.world + self.rank):
                 inp, target = self._channels(*[t.to(self.device, non_blocking=True) for t in batch][:2])
-                out = self._step(step, self.prepare(inp, target))
-                loss = sum(out) if isinstance(out, tuple) else out
-                total += loss.detach()   # device-side accumulation: no host sync inside the loop
-                n += 1
-            avg_loss.append(float(total) / max(n, 1))   # one sync per epoch
-            if self.rank == 0:
-                print('Epoch: [%2d] avg loss: %.8f' % (epoch + 1, avg_loss[-1]))
-                if (epoch + 1) % self.save_epochs == 0:
-                    self.save_model(epoch + 1)
-                    self.save_state(epoch + 1, avg_loss, loader)
+                yield self.prepare(inp, target)
+
+        def one_loss(*tensors):
+            out = self._step(step, tensors)
+            return sum(out) if isinstance(out, tuple) else out
+
+        self.run_epochs(done, self.num_epochs, batches, one_loss, 1, avg_loss, 'Epoch: [%2d] avg loss: %.8f', self.begin_epoch,
+                        lambda n: (self.save_model(n), self.save_state(n, avg_loss, loader)))
         self._close_graph()
         if self.rank == 0:
             self.save_model(epoch=None)
             self.save_state(max(done, self.num_epochs), avg_loss, loader)
         return avg_loss
+
+    def run_epochs(self, first, last, batches, step, losses=0, history=None, line=None, begin=None, save=None):
+        """Epochs first .. last - 1 of one training phase: begin(epoch), then step(*tensors) for every item of
+        batches(epoch).  The first `losses` values a step returns are summed on the device (no host sync inside the loop)
+        and read once per epoch: their means go to `history` (a float, or a tuple of several) and on rank 0 into `line`.
+        Every save_epochs epochs rank 0 calls save(epochs done)."""
+        for epoch in range(first, last):
+            if begin is not None:
+                begin(epoch)
+            totals, n = [torch.zeros((), device=self.device) for _ in range(losses)], 0
+            for tensors in batches(epoch):
+                out = step(*tensors)
+                for total, loss in zip(totals, out if isinstance(out, tuple) else (out,)):
+                    total += loss.detach()
+                n += 1
+            if losses:
+                means = tuple(float(total) / max(n, 1) for total in totals)   # one sync per epoch
+                history.append(means if losses > 1 else means[0])
+            if self.rank == 0:
+                if line is not None:
+                    print(line % ((epoch + 1,) + means))
+                if save is not None and (epoch + 1) % self.save_epochs == 0:
+                    save(epoch + 1)
 
     # -- the train step as a hipGraph ------------------------------------------------------------------------------
     # The reference's loop launches ~110 (EDSR) small kernels per iteration; at its default batch sizes the step is a
@@ -504,13 +575,15 @@ class _Trainer(object):
     # the gradient exchange under data parallelism) and replayed from then on.  A batch of another shape (the ragged
     # last one) runs eagerly; a learning-rate decay needs nothing (the rate is a device scalar).  --eager turns it off.
     # A step without segments (LapSRN's two losses, DRCN) cannot be split: it is captured on one GPU only.
+    def auto_graph(self, eager_step, flats, enabled=True):
+        return trainers.AutoGraph(eager_step, lambda ts: trainers.capture_step(eager_step, ts, warmup=0, flats=flats),
+                                  enabled=enabled and not getattr(self.args, "eager", False))
+
     def _step(self, eager_step, tensors):
         auto = getattr(self, "_auto", None)
         if auto is None or auto.eager is not eager_step:
             single = self.dp is None or not self.dp.active
-            auto = self._auto = trainers.AutoGraph(
-                eager_step, lambda ts: trainers.capture_step(eager_step, ts, warmup=0, flats=[self.flat]),
-                enabled=(hasattr(eager_step, "segments") or single) and not getattr(self.args, "eager", False))
+            auto = self._auto = self.auto_graph(eager_step, [self.flat], hasattr(eager_step, "segments") or single)
         return auto(*tensors)
 
     @property
@@ -525,7 +598,7 @@ class _Trainer(object):
 
     def _net_input(self, x):
         """SRCNN / VDSR feed the bicubic-upsampled image to the net (srcnn.py:145, vdsr.py:160)."""
-        return utils.img_interp(x, self.scale_factor) if self.kind in ("srcnn", "vdsr", "drcn") else x
+        return utils.img_interp(x, self.scale_factor) if self.pre_upsample else x
 
     def _infer(self, x):
         self.model.eval()
@@ -651,7 +724,7 @@ class _Trainer(object):
                     lr_img, hr_img = self._channels(*[t if t.dim() == 4 else t.unsqueeze(0) for t in item[:2]])
                     out = self._forward(lr_img.to(self.device), tile, self_ensemble=self_ensemble)
                     hr = hr_img.to(self.device)
-                    mine.add(out, utils.shave(hr, 8) if self.kind == "srcnn" else hr)   # srcnn.py:193-199: border excluded
+                    mine.add(out, self._shave(hr))   # (srcnn.py:193-199: border excluded)
                     if save_images:
                         img_num += 1
                         utils.save_img(out[0], img_num, save_dir=os.path.join(self.save_dir, 'test_result', str(name)))
@@ -912,7 +985,7 @@ class _Trainer(object):
         # srcnn.py:260-269 style for the simple trainers, edsr.py:324-337 style (ch/batch/epoch/lr) for EDSR / SRGAN
         model_dir = os.path.join(self.save_dir, 'model')
         os.makedirs(model_dir, exist_ok=True)
-        if self.kind in ("edsr",):
+        if self.edsr_ckpt_name:
             return model_dir + '/' + self.model_name + '_param_ch%d_batch%d_epoch%d_lr%.g.pkl' % (
                 self.num_channels, self.batch_size, self.num_epochs if epoch is None else epoch, self.lr)
         if epoch is not None:
@@ -947,9 +1020,16 @@ class _Trainer(object):
 
 class SRCNN(_Trainer):
     kind = "srcnn"
+    pre_upsample = True
 
     def build_model(self):
         return models.SRCNNNet(self.num_channels, 64)   # srcnn.py:73
+
+    def _shave(self, target):
+        return utils.shave(target, 8)
+
+    def prepare(self, inp, target):
+        return self._net_input(inp), self._shave(target).contiguous()
 
 
 class ESPCN(_Trainer):
@@ -968,18 +1048,18 @@ class FSRCNN(_Trainer):
 
 class VDSR(_Trainer):
     kind = "vdsr"
+    pre_upsample = True
 
     def build_model(self):
         return models.VDSRNet(self.num_channels, 64, 18)   # vdsr.py:80
 
 
-
 class EDSR(_Trainer):
     kind = "edsr"
+    edsr_ckpt_name = True
 
     def build_model(self):
         return models.EDSRNet(self.num_channels, 64, 16)   # edsr.py:87
-
 
 
 class LapSRN(_Trainer):
@@ -988,13 +1068,14 @@ class LapSRN(_Trainer):
     def build_model(self):
         return models.LapSRNNet(self.num_channels, 64, 10)   # lapsrn.py:129
 
+    def prepare(self, inp, target):
+        return inp, utils.img_interp(target, 1 / self.scale_factor * 2), target
 
 
 class SRGAN(_Trainer):
     """srgan.py:93-528: generator pre-training with MSE, then the adversarial loop."""
     kind = "srgan"
     opt_kinds = ("srgan_g", "srgan_d")
-    decay_kind = "srgan"
 
     def _normalise(self, t):
         """What the loader's batches go through on their way to both phases (srgan.py:193-194,257-258)."""
@@ -1010,11 +1091,10 @@ class SRGAN(_Trainer):
         fe = None
         if getattr(self.args, "vgg_weights", None):
             fe = models.FeatureExtractor().load_vgg19(self.args.vgg_weights).to(self.device)
-        vgg_w = getattr(self.args, "vgg_loss_weight", None)
         return trainers.srgan_step(self.G, self.D, g_opt, d_opt, g_dp, d_dp, feature_extractor=fe, lazy_pack=True,
                                    prune_dead_grads=bool(getattr(self.args, "prune_dead_grads", False)),
                                    perceptual=bool(getattr(self.args, "perceptual", False)),
-                                   vgg_weight=6e-3 if vgg_w is None else float(vgg_w))
+                                   vgg_weight=self.flag_defaults(self.args)["vgg_loss_weight"])
 
     def build_model(self):
         self.G = models.SRGANGenerator(self.num_channels, 64, 16)                 # srgan.py:136
@@ -1047,22 +1127,13 @@ class SRGAN(_Trainer):
                 trainers.sync_batchnorm(self.G)
                 trainers.sync_batchnorm(self.D)
         norm = self._normalise
-
-        self.data_source = "loader"
-        if loader is None:
-            loader = self.load_dataset(self.train_dataset, is_train=True)
-            self.data_source = "folder" if loader is not None else "synthetic"
-        self._announce_data()
+        loader = self.open_data(loader)
         trainers.quiesce_gc()    # no full cyclic collection (~80 ms) inside a step from here on
 
         def batches(seed):   # loaders yield (lr, hr) or the reference's (lr, hr, bicubic) tuples (dataset.py:101)
             for batch in (loader or synthetic_loader("srgan", self.args, self.steps_per_epoch, self.device, seed)):
                 lr_img, hr_img = self._channels(*batch[:2])
                 yield norm(lr_img.to(self.device, non_blocking=True)), norm(hr_img.to(self.device, non_blocking=True))
-
-        def graphed(eager_step, flats):
-            return trainers.AutoGraph(eager_step, lambda ts: trainers.capture_step(eager_step, ts, warmup=0, flats=flats),
-                                      enabled=not bool(getattr(self.args, "eager", False)))
 
         # generator pre-training (srgan.py:179-219): 50 epochs of MSE unless a pre-trained generator checkpoint loads
         self.epoch_pretrain = int(getattr(self.args, "epoch_pretrain", 50)) if pretrain_epochs is None else pretrain_epochs
@@ -1082,12 +1153,9 @@ class SRGAN(_Trainer):
             g_flat.mark_changed()      # parameters changed behind the optimizer's back: re-pack filters
             g_opt.ema_reset()          # ... and the shadow weights start from them
         else:
-            pre_step = graphed(self._pretrain_step(g_opt, g_dp), [g_flat])
-            for epoch in range(pre_done, self.epoch_pretrain):
-                for y_, x_ in batches(77 + epoch):
-                    pre_step(y_, x_)
-                if (epoch + 1) % self.save_epochs == 0 and epoch + 1 < self.epoch_pretrain:
-                    self.save_state(epoch + 1, [], loader, phase="pretrain")
+            pre_step = self.auto_graph(self._pretrain_step(g_opt, g_dp), [g_flat])
+            self.run_epochs(pre_done, self.epoch_pretrain, lambda epoch: batches(77 + epoch), pre_step, save=lambda n:
+                            n < self.epoch_pretrain and self.save_state(n, [], loader, phase="pretrain"))
             pre_step.close()
             if self.rank == 0:
                 self.save_model(is_pretrain=True)
@@ -1095,21 +1163,10 @@ class SRGAN(_Trainer):
             self.phase = "adversarial"
             self.save_state(0, [], loader, phase=self.phase)
         # the adversarial step (two models, two optimizers) as one hipGraph; data parallel: graphs split at the two exchanges
-        step = graphed(self._adversarial_step(g_opt, d_opt, g_dp, d_dp), [g_flat, d_flat])
-        for epoch in range(done, self.num_epochs):
-            apply_lr_decay(self.decay_kind, epoch, g_opt, d_opt)   # srgan.py:239-244: both learning rates /10 every 20 epochs
-            d_tot, g_tot, n = torch.zeros((), device=self.device), torch.zeros((), device=self.device), 0
-            for y_, x_ in batches(1234 + epoch):
-                d_loss, g_loss = step(y_, x_)
-                d_tot += d_loss.detach()
-                g_tot += g_loss.detach()
-                n += 1
-            hist.append((float(d_tot) / max(n, 1), float(g_tot) / max(n, 1)))
-            if self.rank == 0:
-                print('Epoch: [%2d] D_loss: %.8f G_loss: %.8f' % ((epoch + 1,) + hist[-1]))
-                if (epoch + 1) % self.save_epochs == 0:
-                    self.save_model(epoch + 1)
-                    self.save_state(epoch + 1, hist, loader, phase=self.phase)
+        step = self.auto_graph(self._adversarial_step(g_opt, d_opt, g_dp, d_dp), [g_flat, d_flat])
+        self.run_epochs(done, self.num_epochs, lambda epoch: batches(1234 + epoch), step, 2, hist,
+                        'Epoch: [%2d] D_loss: %.8f G_loss: %.8f', self.begin_epoch,   # srgan.py:239-244: both rates decay
+                        lambda n: (self.save_model(n), self.save_state(n, hist, loader, phase=self.phase)))
         step.close()
         if self.rank == 0:
             self.save_model(epoch=None)
@@ -1165,28 +1222,40 @@ class ESRGAN(SRGAN):
     kind = "esrgan"
     opt_kinds = ("esrgan_g", "esrgan_d")
     decay_kind = None
+    HYPER = {"rrdb_blocks": 23, "rrdb_growth": 32}
+    VGG_LOSS_WEIGHT = 1.0
 
-    def __init__(self, args):
-        if getattr(args, "tile", None) is not None:
-            raise ValueError("tile: the RRDB trunk's receptive field (about 350 LR pixels for 23 blocks) leaves a tile mostly "
-                             "halo; ESRGAN's pictures run in one pass (main.py --tile)")
-        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            raise NotImplementedError("ESRGAN trains on one GPU: data parallelism is not implemented for it (launch "
-                                      "main.py without torch.distributed.run)")
+    @classmethod
+    def check_flags(cls, args):
         if getattr(args, "scale_factor", 4) != 4:
-            raise ValueError("scale_factor %r: RRDBNet upsamples by 4 only (main.py --scale_factor 4)" % (args.scale_factor,))
+            raise ValueError("--scale_factor %r: RRDBNet upsamples by 4 only" % (args.scale_factor,))
+        if getattr(args, "tile", None) is not None:
+            raise ValueError("--tile: the RRDB trunk reaches about 350 LR pixels to each side (23 blocks), a tile would be "
+                             "mostly halo; ESRGAN's pictures run in one pass (drop --tile)")
+        check_growth("rrdb_growth", int(cls.hyper(args)["rrdb_growth"]))
+        if getattr(args, "num_channels", 3) != 3:
+            raise ValueError("--num_channels %r: ESRGAN's VGG feature term reads RGB, use --num_channels 3" % (args.num_channels,))
         if getattr(args, "perceptual", False):
-            raise ValueError("perceptual: ESRGAN's feature term always trains the generator (drop main.py --perceptual)")
+            raise ValueError("--perceptual: ESRGAN's feature term always trains the generator (drop --perceptual)")
         interp = getattr(args, "net_interp", None)
         if interp is not None and not 0.0 <= float(interp) <= 1.0:
-            raise ValueError("net_interp %r is not in [0, 1] (main.py --net_interp)" % (interp,))
+            raise ValueError("--net_interp %r is not in [0, 1]" % (interp,))
+        check_one_gpu("ESRGAN")
+        return super(ESRGAN, cls).check_flags(args)
+
+    @classmethod
+    def flag_defaults(cls, args):
+        disc, gan, feat = check_discriminator_args(args, cls.kind)
+        return dict(super(ESRGAN, cls).flag_defaults(args), discriminator=disc, gan_type=gan,
+                    unet_feat=feat if disc == "unet" else None)
+
+    def __init__(self, args):
         super(ESRGAN, self).__init__(args)
-        self.blocks = int(getattr(args, "rrdb_blocks", None) or 23)
-        self.growth = int(getattr(args, "rrdb_growth", None) or 32)
+        self.blocks, self.growth = (int(v) for v in self.hyper(args).values())
         w = lambda name, default: default if getattr(args, name, None) is None else float(getattr(args, name))
         self.gan_weight, self.pixel_weight = w("gan_weight", 5e-3), w("pixel_weight", 1e-2)
-        self.vgg_weight = w("vgg_loss_weight", 1.0)
-        self.net_interp = None if interp is None else float(interp)
+        self.vgg_weight = self.flag_defaults(args)["vgg_loss_weight"]
+        self.net_interp = None if getattr(args, "net_interp", None) is None else float(args.net_interp)
         self.discriminator, self.gan_type, self.unet_feat = self.disc_args
 
     def build_discriminator(self):
@@ -1223,10 +1292,8 @@ class ESRGAN(SRGAN):
 
     def train(self, loader=None, pretrain_epochs=None, log_every=0):
         if not getattr(self.args, "vgg_weights", None):
-            raise ValueError("vgg_weights: ESRGAN's adversarial phase trains on VGG19 conv5_4 features and needs the "
-                             "weights to extract them with (main.py --vgg_weights PATH, a torchvision vgg19 state_dict)")
-        if self.num_channels != 3:
-            raise ValueError("num_channels %r: ESRGAN's feature term reads RGB (main.py --num_channels 3)" % (self.num_channels,))
+            raise ValueError("--vgg_weights PATH is required: ESRGAN's adversarial phase trains on VGG19 conv5_4 features (a "
+                             "torchvision vgg19 state_dict file)")
         return super(ESRGAN, self).train(loader, pretrain_epochs, log_every)
 
     def load_model(self, is_pretrain=False):
@@ -1256,12 +1323,19 @@ class DRCN(_Trainer):
     """drcn.py:62-355: F = 256 and D = 16 hard-coded as in the reference (drcn.py:103-104); Adam over two param groups
     (the model, w) at the same rate; alpha decays from 1 by 1/25 at the top of every epoch, beta = 1e-3."""
     kind = "drcn"
+    pre_upsample = True
     base_filter, num_recursions = 256, 16
 
+    @classmethod
+    def check_flags(cls, args):
+        check_one_gpu("DRCN")
+        checked = super(DRCN, cls).check_flags(args)
+        if float(getattr(args, "ema_decay", None) or 0.0) > 0:
+            raise ValueError("--ema_decay %g: DRCN keeps no EMA of its weights (its combine weights w train outside the flat "
+                             "parameter buffer); use --ema_decay 0 or another model" % args.ema_decay)
+        return checked
+
     def __init__(self, args):
-        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            raise NotImplementedError("DRCN trains on one GPU: data parallelism is not implemented for it (launch "
-                                      "main.py without torch.distributed.run)")
         super(DRCN, self).__init__(args)
         self.loss_alpha = 1.0
         self.loss_alpha_zero_epoch = 25
@@ -1289,10 +1363,7 @@ class DRCN(_Trainer):
                                   self.reg_dev)
         return self.flat, self.optimizer, None, step
 
-    def lr_decay(self, epoch, opt):
-        apply_lr_decay(self.kind, epoch, opt, self.w_optimizer)   # both param groups (drcn.py:164-168)
-
-    def _optimizers(self):
+    def _optimizers(self):   # (both param groups decay: drcn.py:164-168)
         return {"optimizer": self.optimizer, "w_optimizer": self.w_optimizer}
 
     def training_state(self, done, history, loader=None, **extra):
@@ -1339,20 +1410,26 @@ class RCAN(_Trainer):
     learning-rate decay, `--rcan_groups` x `--rcan_blocks` RCABs with `--rcan_reduction`.  Its channel attention reads the
     whole picture, so tiling is refused here (args.tile) and by tiling.net_geometry (test_single(img, tile=...))."""
     kind = "rcan"
+    decay_kind = "edsr"
+    HYPER = {"rcan_groups": 10, "rcan_blocks": 20, "rcan_reduction": 16}
+
+    @classmethod
+    def check_flags(cls, args):
+        if getattr(args, "tile", None) is not None:
+            raise ValueError("--tile: RCAN's channel attention depends on the whole image, its pictures run in one pass "
+                             "(drop --tile)")
+        if 64 % int(cls.hyper(args)["rcan_reduction"]):
+            raise ValueError("--rcan_reduction %d does not divide RCAN's 64 channels" % args.rcan_reduction)
+        if getattr(args, "scale_factor", 4) not in (2, 4, 8):
+            raise ValueError("--scale_factor %r: RCAN upsamples by 2, 4 or 8" % (args.scale_factor,))
+        return super(RCAN, cls).check_flags(args)
 
     def __init__(self, args):
-        if getattr(args, "tile", None) is not None:
-            raise ValueError("tile: RCAN's channel attention depends on the whole image and cannot be tiled (main.py --tile)")
         super(RCAN, self).__init__(args)
-        self.groups = int(getattr(args, "rcan_groups", None) or 10)
-        self.blocks = int(getattr(args, "rcan_blocks", None) or 20)
-        self.reduction = int(getattr(args, "rcan_reduction", None) or 16)
+        self.groups, self.blocks, self.reduction = (int(v) for v in self.hyper(args).values())
 
     def build_model(self):
         return models.RCANNet(self.num_channels, 64, self.groups, self.blocks, self.reduction, self.scale_factor)
-
-    def lr_decay(self, epoch, opt):
-        apply_lr_decay("edsr", epoch, opt)
 
 
 class RDN(_Trainer):
@@ -1360,18 +1437,22 @@ class RDN(_Trainer):
     learning-rate decay, `--rdn_blocks` residual dense blocks of `--rdn_layers` layers with growth `--rdn_growth`, 64
     shallow features.  Purely convolutional: `--tile` works (tiling.net_geometry)."""
     kind = "rdn"
+    decay_kind = "edsr"
+    HYPER = {"rdn_blocks": 16, "rdn_layers": 8, "rdn_growth": 64}
+
+    @classmethod
+    def check_flags(cls, args):
+        check_growth("rdn_growth", int(cls.hyper(args)["rdn_growth"]))
+        if getattr(args, "scale_factor", 4) not in (2, 3, 4):
+            raise ValueError("--scale_factor %r: RDN upsamples by 2, 3 or 4" % (args.scale_factor,))
+        return super(RDN, cls).check_flags(args)
 
     def __init__(self, args):
         super(RDN, self).__init__(args)
-        self.blocks = int(getattr(args, "rdn_blocks", None) or 16)
-        self.layers = int(getattr(args, "rdn_layers", None) or 8)
-        self.growth = int(getattr(args, "rdn_growth", None) or 64)
+        self.blocks, self.layers, self.growth = (int(v) for v in self.hyper(args).values())
 
     def build_model(self):
         return models.RDNNet(self.num_channels, 64, self.blocks, self.layers, self.growth, self.scale_factor)
-
-    def lr_decay(self, epoch, opt):
-        apply_lr_decay("edsr", epoch, opt)
 
 
 class SwinIR(_Trainer):
@@ -1380,26 +1461,39 @@ class SwinIR(_Trainer):
     `--swinir_upsampler`.  The window grid and the border mask of its WindowAttention belong to the whole picture, so
     tiling is refused here (args.tile) and by tiling.net_geometry (test_single(img, tile=...))."""
     kind = "swinir"
+    decay_kind = "edsr"
+    HYPER = {"swinir_dim": 180, "swinir_depths": (6, 6, 6, 6, 6, 6), "swinir_heads": 6, "swinir_window": 8,
+             "swinir_mlp_ratio": 2, "swinir_upsampler": "pixelshuffle"}
+
+    @classmethod
+    def check_flags(cls, args):
+        h = cls.hyper(args)
+        dim, heads, window, upsampler = int(h["swinir_dim"]), int(h["swinir_heads"]), int(h["swinir_window"]), h["swinir_upsampler"]
+        scale, crop = getattr(args, "scale_factor", None), getattr(args, "crop_size", None)
+        if getattr(args, "tile", None) is not None:
+            raise ValueError("--tile: SwinIR's WindowAttention partitions the whole image into windows, its pictures run in "
+                             "one pass (drop --tile)")
+        if dim % heads:
+            raise ValueError("--swinir_heads %d does not divide --swinir_dim %d" % (heads, dim))
+        if dim // heads > 32:
+            raise ValueError("--swinir_dim %d / --swinir_heads %d: a head dimension of %d exceeds 32" % (dim, heads, dim // heads))
+        if not 2 <= window <= 8:
+            raise ValueError("--swinir_window %d is not in 2 .. 8" % window)
+        if upsampler == "pixelshuffle" and scale is not None and scale not in (2, 3, 4, 8):
+            raise ValueError("--scale_factor %d: SwinIR's pixelshuffle upsampler works by 2, 3, 4 or 8" % scale)
+        if scale and crop is not None and (crop % scale or (crop // scale) % window):
+            raise ValueError("--crop_size %d / --scale_factor %d is not a multiple of --swinir_window %d" % (crop, scale, window))
+        return super(SwinIR, cls).check_flags(args)
 
     def __init__(self, args):
-        if getattr(args, "tile", None) is not None:
-            raise ValueError("tile: SwinIR's WindowAttention partitions the whole image into windows and cannot be tiled "
-                             "(main.py --tile)")
         super(SwinIR, self).__init__(args)
-        self.dim = int(getattr(args, "swinir_dim", None) or 180)
-        depths = getattr(args, "swinir_depths", None) or (6, 6, 6, 6, 6, 6)
+        dim, depths, heads, window, mlp_ratio, self.upsampler = self.hyper(args).values()
+        self.dim, self.heads, self.window, self.mlp_ratio = int(dim), int(heads), int(window), float(mlp_ratio)
         self.depths = tuple(int(d) for d in (depths.split(",") if isinstance(depths, str) else depths))
-        self.heads = int(getattr(args, "swinir_heads", None) or 6)
-        self.window = int(getattr(args, "swinir_window", None) or 8)
-        self.mlp_ratio = float(getattr(args, "swinir_mlp_ratio", None) or 2)
-        self.upsampler = getattr(args, "swinir_upsampler", None) or "pixelshuffle"
 
     def build_model(self):
         return models.SwinIRNet(self.num_channels, self.dim, self.depths, self.heads, self.window, self.mlp_ratio,
                                 self.scale_factor, self.upsampler)
-
-    def lr_decay(self, epoch, opt):
-        apply_lr_decay("edsr", epoch, opt)
 
 
 TRAINERS = {"SRCNN": SRCNN, "VDSR": VDSR, "ESPCN": ESPCN, "FSRCNN": FSRCNN, "SRGAN": SRGAN, "LapSRN": LapSRN, "EDSR": EDSR,

@@ -621,17 +621,21 @@ class GraphedStep(GraphedSegments):
     seg = property(lambda self: self)   # (the split capture used to be a member of this name: `step.seg.plan` still reads)
 
 
+# The kinds that train on a loss of their own (SRGAN and ESRGAN on adversarial content terms, DRCN through its fused
+# recursive-supervision head): mixed_loss's terms are refused for them, here and by sr_trainers' flag checks.
+OWN_LOSS_KINDS = ("srgan", "drcn", "esrgan")
+
+
 def build(kind, model, lr, dp_group=None, use_dp=False, ema_decay=0.0, **terms):
     """(flat, optimizer, dp, step) for one of 'srcnn' | 'fsrcnn' | 'vdsr' | 'edsr' | 'lapsrn' | 'espcn' | 'rcan' | 'rdn' | 'swinir': the one place that
     names the loss and the clip a kind trains with.  terms: mixed_loss's keywords (ssim_weight, fft_weight, fft_norm,
-    lpips_weight, lpips_net; RGB models only, refused for 'srgan' and 'drcn'), each of which at 0 leaves the step as it is
+    lpips_weight, lpips_net; RGB models only, refused for OWN_LOSS_KINDS), each of which at 0 leaves the step as it is
     without the argument.  ema_decay d in (0, 1): the optimizer keeps the moving average of the weights (`opt.ema`); it is
     updated inside opt.step()'s kernel, so eager steps, segments and graphs all carry it without a node of its own, and
     under data parallelism every rank's shadow is the same (same parameters, same kernel)."""
     from .dp import DataParallel
-    if float(terms.get("lpips_weight", 0.0)) > 0.0 and kind in ("srgan", "drcn"):
-        raise ValueError("lpips_weight %r: %s has no LPIPS term (SRGAN trains on an adversarial content term, DRCN through "
-                         "its fused recursive-supervision head)" % (terms["lpips_weight"], kind))
+    if float(terms.get("lpips_weight", 0.0)) > 0.0 and kind in OWN_LOSS_KINDS:
+        raise ValueError("lpips_weight %r: %s trains on a loss of its own and has no LPIPS term" % (terms["lpips_weight"], kind))
     flat = FlatParams(model)
     opt = make_optimizer(kind, flat, lr, ema_decay=ema_decay)
     dp = DataParallel(flat, dp_group) if use_dp else None

@@ -125,7 +125,7 @@ def test_cli(tmp_path, capsys):
 def test_trainer_table():
     from pytorch_super_resolution_model_collection_amd import optim, sr_trainers
     assert sr_trainers.TRAINERS["RDN"].kind == "rdn" and sr_trainers.RDN is sr_trainers.TRAINERS["RDN"]
-    assert sr_trainers.LR_DECAY.get("rdn") is None        # EDSR's rule, applied by name in RDN.lr_decay
+    assert sr_trainers.LR_DECAY.get("rdn") is None and sr_trainers.RDN.decay_kind == "edsr"   # EDSR's rule, by name
     with pytest.raises(ValueError):
         optim.make_optimizer("rdn_", None, 1e-3)
 
