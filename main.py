@@ -58,7 +58,15 @@ ground truth) of the net's 8-bit output -- ' NIQE %.4f' on the --test_only line,
 --test_video IN [--video_out OUT] [--video_batch N] (load the checkpoint, super-resolve the YUV4MPEG2 stream IN -- 8-bit
 4:2:0, 4:4:4 or mono; - = stdin -- in batches of N frames from file bytes to file bytes on the device, write OUT, default
 <save_dir>/test_result/SR_result.y4m, - = stdout; honours --tile and --self_ensemble; no training).
-Which flags go with which model and with each other is said once, by the trainer class (sr_trainers: TRAINERS[model_name].
+--model_name VESPCN (not in the reference: ESPCN's video follow-up, models.VESPCNNet): three consecutive LR frames, the two
+neighbours warped onto the centre one by a learned coarse-to-fine flow (fused HIP: ops.motion_fuse), ESPCN's trunk on the
+nine (three for Y) channels; loss MSE + --mc_weight W * motion-compensation MSE + --flow_weight W * flow smoothness
+(defaults 0.01 and 0.001), --vespcn_max_flow PX (default 8).  Training reads clip folders, data_dir/<dataset>/<clip>/<frames>
+(data.ClipDataset), or --synthetic; --crop_size / --scale_factor must be a multiple of 4.  --test_single and test() on
+single pictures use the picture as its own neighbours.  One GPU; no --tile, --self_ensemble, --degrade*, --usm, --jpeg_*,
+--ssim_weight, --fft_weight, --lpips_weight.  --test_video computes frame t from frames t-1, t, t+1 of the stream (the ends
+use themselves; as many frames out as in); test() on a test set of clip folders evaluates every frame with its neighbours.
+Which flags go with which model and with each other is said once, by the trainer class (sr_trainers: trainer_class(model_name).
 check_flags(args), a ValueError naming the flag); parse_args reports it as a usage error and itself holds only the rules
 about the run: the modes --niqe_fit / --test_video / --test_only / --test_single against each other and --resume, files
 that must exist, ESRGAN's --vgg_weights when it trains.
@@ -258,10 +266,10 @@ def _jpeg_prob(text):
 
 
 def parse_args(argv=None):
-    from pytorch_super_resolution_model_collection_amd.sr_trainers import TRAINERS
+    from pytorch_super_resolution_model_collection_amd.sr_trainers import model_names, trainer_class
     p = argparse.ArgumentParser(description="MI355X-native SR collection (reference-compatible CLI)")
     p.add_argument('--model_name', type=str, default='SRGAN',
-                   choices=list(TRAINERS), help='The type of model')
+                   choices=model_names(), help='The type of model')
     p.add_argument('--data_dir', type=str, default='../Data')
     p.add_argument('--train_dataset', type=_names, default=['DIV2K'], help='The name(s) of the training dataset, comma-separated')
     p.add_argument('--test_dataset', type=_names, default=['Set5', 'Set14', 'Urban100'], help='The name(s) of the test dataset, comma-separated')
@@ -434,6 +442,15 @@ def parse_args(argv=None):
                         'name:weight,... over VGG19 conv layers taken before their ReLUs (conv1_1 .. conv5_4), or the word '
                         'realesrgan = conv1_2:0.1,conv2_2:0.1,conv3_4:1,conv4_4:1,conv5_4:1.  Needs --vgg_weights; the whole '
                         'term is weighed by --vgg_loss_weight')
+    p.add_argument('--mc_weight', type=_loss_weight, default=None, metavar='W',
+                   help='VESPCN: weight of the motion-compensation MSE of the warped neighbours (default 0.01: the paper\'s '
+                        'value as remembered, unchecked)')
+    p.add_argument('--flow_weight', type=_loss_weight, default=None, metavar='W',
+                   help='VESPCN: weight of the flow-smoothness (Huber) term (default 0.001: the paper\'s value as '
+                        'remembered, unchecked)')
+    p.add_argument('--vespcn_max_flow', type=float, default=None, metavar='PX',
+                   help='VESPCN: pixels one unit of the coarse flow\'s tanh stands for; the fine stage adds a quarter of it '
+                        '(default 8; the paper gives no scale, this is the project\'s choice)')
     p.add_argument('--niqe_params', type=str, default=None, metavar='PATH',
                    help='NIQE\'s pristine model, an .npz with mu_pris_param [36] and cov_pris_param [36, 36] (BasicSR\'s '
                         'niqe_pris_params.npz, or one written by --niqe_fit): test() also reports NIQE (Mittal et al. 2013; '
@@ -472,7 +489,7 @@ def parse_args(argv=None):
     if args.net_interp is not None and not (args.test_only or args.test_single):
         p.error('--net_interp blends two finished checkpoints: it goes with --test_only or --test_single')
     # which flags go with the model and with each other: the trainer class says (sr_trainers: check_flags)
-    trainer = TRAINERS[args.model_name]
+    trainer = trainer_class(args.model_name)
     try:
         trainer.check_flags(args)
     except (ValueError, NotImplementedError) as e:   # (NotImplementedError: a model without data parallelism)
@@ -535,9 +552,9 @@ def run(args, video_sink=None):
     import pytorch_super_resolution_model_collection_amd as pkg
     if args.niqe_fit is not None:
         return niqe_fit(args)
-    from pytorch_super_resolution_model_collection_amd.sr_trainers import TRAINERS
+    from pytorch_super_resolution_model_collection_amd.sr_trainers import model_names, trainer_class
     pkg.ops.set_precision(args.precision)
-    net = TRAINERS[args.model_name](args)   # main.py:70-89
+    net = trainer_class(args.model_name)(args)   # main.py:70-89
     if args.test_single:                     # main.py:102: net.test_single(img_fn)
         print(net.test_single(args.test_single))
         if args.niqe_params:

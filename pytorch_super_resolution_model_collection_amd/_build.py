@@ -14,8 +14,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsrk.so")
 SOURCES = ["api.hip", "elementwise.hip", "loss_optim.hip", "conv_generic.hip", "conv_mfma.hip", "conv_mfma_bf16.hip", "conv_bfd.hip", "conv_tapn.hip", "conv_rown.hip", "conv_bfw.hip", "conv_bfr.hip", "conv_rowsw.hip", "conv_res2.hip", "conv_c64.hip",
            "conv_wgrad_mfma.hip", "conv_wgrad_bf16.hip", "bn_linear.hip", "resize_pil.hip", "prepost.hip", "drcn.hip", "conv_pair.hip", "color.hip", "tile.hip", "ssim.hip", "ssim_loss.hip", "fft_loss.hip", "dihedral.hip", "degrade.hip", "jpeg.hip", "ca.hip", "lpips.hip", "dense.hip", "wattn.hip", "swin_pointwise.hip", "ragan.hip",
-           "spectral_norm.hip", "bilinear.hip", "gan_logit.hip", "usm.hip", "vgg_tap.hip", "niqe.hip", "video.hip"]
-HEADERS = ["srk_common.h", "conv_problem.h", "conv_tile.h", "conv_wgrad_plan.h", "pack_items.h", "conv_bfw.h", "conv_pair_layout.h", "bf16_frag.h", "color_common.h", "ssim_common.h", "fft_loss_common.h", "degrade_common.h", "jpeg_common.h", "ca_common.h", "lpips_common.h", "dense_common.h", "wattn_common.h", "ragan_common.h", "spectral_norm_common.h", "bilinear_common.h", "usm_common.h", "vgg_tap_common.h", "niqe_common.h", "video_common.h", os.path.join("..", "..", "include", "srk.h")]
+           "spectral_norm.hip", "bilinear.hip", "gan_logit.hip", "usm.hip", "vgg_tap.hip", "niqe.hip", "video.hip", "mc.hip"]
+HEADERS = ["srk_common.h", "conv_problem.h", "conv_tile.h", "conv_wgrad_plan.h", "pack_items.h", "conv_bfw.h", "conv_pair_layout.h", "bf16_frag.h", "color_common.h", "ssim_common.h", "fft_loss_common.h", "degrade_common.h", "jpeg_common.h", "ca_common.h", "lpips_common.h", "dense_common.h", "wattn_common.h", "ragan_common.h", "spectral_norm_common.h", "bilinear_common.h", "usm_common.h", "vgg_tap_common.h", "niqe_common.h", "video_common.h", "mc_common.h", os.path.join("..", "..", "include", "srk.h"), os.path.join("..", "..", "include", "srk_mc.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mcode-object-version=5",
          "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 

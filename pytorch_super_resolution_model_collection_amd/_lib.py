@@ -22,7 +22,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SRK_LIB_PATH") or os.path.join(_HERE, "libsrk.so")  # env override: A/B kernel builds
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "srk.h")
 
+MC_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "srk_mc.h")
+
 _H = _header.read_file(HEADER_PATH)
+_H_MC = _header.read_file(MC_HEADER_PATH)   # the motion-compensation entry points: a header of their own, the same reader
 globals().update({name[len("SRK_"):]: value for name, value in _H.constants.items()})   # ACT_NONE, ALGO_MFMA, VERSION, ...
 SSIM_DOMAINS = {"float": SSIM_FLOAT, "u8": SSIM_U8, "y8": SSIM_Y8}
 ACT_BY_NAME = {None: ACT_NONE, "relu": ACT_RELU, "prelu": ACT_PRELU, "lrelu": ACT_LRELU, "tanh": ACT_TANH,
@@ -86,6 +89,7 @@ class Phase(_Sized, _H.classes["srk_phase"]):
 
 
 _PROTOTYPES = _H.functions   # {name: (restype, [argtypes])}
+_MC_PROTOTYPES = _H_MC.functions   # the same for include/srk_mc.h
 
 _lib = None
 
@@ -93,6 +97,11 @@ _lib = None
 def header_symbols():
     """Every function name declared in include/srk.h."""
     return sorted(_PROTOTYPES)
+
+
+def mc_header_symbols():
+    """Every function name declared in include/srk_mc.h."""
+    return sorted(_MC_PROTOTYPES)
 
 
 def load():
@@ -105,7 +114,7 @@ def load():
             "libsrk.so not found at %s — run `python __graft_entry__.py build` (hipcc --offload-arch=gfx950). "
             "There is no CPU/eager fallback for the hot path." % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in _PROTOTYPES.items():
+    for name, (res, args) in list(_PROTOTYPES.items()) + list(_MC_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -873,6 +873,94 @@ def get_test_set(data_dir, dataset, scale_factor, is_gray=False, device="cuda", 
                                  jpeg=jpeg, jpeg_subsampling=jpeg_subsampling, degrade2=degrade2)
 
 
+class ClipDataset(object):
+    """Training clips for VESPCN: data_dir/<dataset>/<clip>/<frames>, the frames of a clip sorted by name.  An item is
+    three consecutive frames of one clip; ONE draw (crop, rotation, flips; no random rescale) is applied to all three
+    through the per-patch call of TrainDatasetFromFolder, whose Pillow-exact shrink makes the LR frames.  Returns
+    (frames [3,C,lr,lr], the centre HR frame [C,crop,crop]) CUDA tensors.  The draws come from Python's `random`, so
+    --resume reproduces them.  Runs through PatchLoader's per-item path (`decode_ahead = False`: the loader submits no file to its decode pool)."""
+
+    def __init__(self, clip_root_dirs, is_gray=False, crop_size=128, scale_factor=4, device="cuda"):
+        self.items = []          # (frame t-1, frame t, frame t+1) file names
+        self.clips = []          # (clip directory, its frame files)
+        for root in clip_root_dirs:
+            for clip in sorted(listdir(root)):
+                if not os.path.isdir(join(root, clip)):
+                    continue
+                frames = [join(root, clip, x) for x in sorted(listdir(join(root, clip))) if is_image_file(x)]
+                self.clips.append((join(root, clip), frames))
+                self.items.extend(tuple(frames[i:i + 3]) for i in range(len(frames) - 2))
+        self.image_filenames = [it[1] for it in self.items]      # the centre frames (what PatchLoader would decode)
+        self.patcher = TrainDatasetFromFolder([], is_gray=is_gray, random_scale=False, crop_size=crop_size, rotate=True,
+                                              fliplr=True, fliptb=True, scale_factor=scale_factor, device=device)
+
+    dev = property(lambda self: self.patcher.dev)
+    decode_ahead = False      # PatchLoader: an item reads its own three files, there is no one file to decode ahead
+
+    def __len__(self):
+        return len(self.items)
+
+    def __getitem__(self, index):
+        p = self.patcher
+        frames = [load_img(fn) for fn in self.items[index]]
+        h, w = frames[1].shape[0], frames[1].shape[1]
+        for fn, f in zip(self.items[index], frames):
+            if f.shape[:2] != (h, w):
+                raise ValueError("clip frame %s is %d x %d, its neighbour %d x %d" % (fn, f.shape[1], f.shape[0], w, h))
+        params = p.draw(w, h)                                     # one draw for the three frames
+        crop = p.crop_size                                        # (draw made it a multiple of the scale)
+        with p.dev.batch():
+            patches = torch.empty((3, 3, crop, crop), dtype=torch.uint8, device=p.dev.device)
+            for j, f in enumerate(frames):
+                p.patch_u8(f, params, out=patches[j])
+            lr, hr, _ = p.finish(patches)
+        return p.dev.hand_over(lr, hr[1])
+
+
+class ClipTestDataset(object):
+    """Test clips for VESPCN: data_dir/<dataset>/<clip>/<frames>.  Item t of a clip is (the LR frames t-1, t, t+1 of that
+    clip as [3,C,h,w], the ends using themselves; the HR frame t), each frame made by TestDatasetFromFolder's item: every
+    frame is evaluated once, with its real neighbours."""
+    decode_ahead = False
+
+    def __init__(self, root, is_gray=False, scale_factor=4, device="cuda"):
+        self.clips = []
+        for clip in sorted(listdir(root)):
+            if os.path.isdir(join(root, clip)):
+                ds = TestDatasetFromFolder(join(root, clip), is_gray=is_gray, scale_factor=scale_factor, device=device)
+                if len(ds):
+                    self.clips.append(ds)
+        self.index = [(c, t) for c, ds in enumerate(self.clips) for t in range(len(ds))]
+        self.image_filenames = [self.clips[c].image_filenames[t] for c, t in self.index]
+
+    def __len__(self):
+        return len(self.index)
+
+    def neighbours(self, index):
+        """(clip number, (t-1, t, t+1) clamped to the clip) of an item."""
+        c, t = self.index[index]
+        return c, (max(t - 1, 0), t, min(t + 1, len(self.clips[c]) - 1))
+
+    def __getitem__(self, index):
+        c, ts = self.neighbours(index)
+        ds = self.clips[c]
+        made = {t: ds[t] for t in sorted(set(ts))}
+        lr = [made[t][0] for t in ts]
+        if len(set(x.shape for x in lr)) != 1:
+            raise ValueError("clip %s: frames of different sizes around %s" % (os.path.dirname(ds.image_filenames[0]),
+                                                                              ds.image_filenames[ts[1]]))
+        return torch.stack(lr), made[ts[1]][1]
+
+
+def get_clip_test_set(data_dir, dataset, scale_factor, is_gray=False, device="cuda"):
+    return ClipTestDataset(join(data_dir, dataset), is_gray=is_gray, scale_factor=scale_factor, device=device)
+
+
+def get_clip_training_set(data_dir, datasets, crop_size, scale_factor, is_gray=False, device="cuda"):
+    return ClipDataset([join(data_dir, d) for d in datasets], is_gray=is_gray, crop_size=crop_size,
+                       scale_factor=scale_factor, device=device)
+
+
 class PatchLoader(object):
     """DataLoader(dataset=train_set, num_workers=num_threads, batch_size=B, shuffle=True) of the reference
     (edsr.py:75-77), MI355X-first: `num_threads` host threads only DECODE (the next batch is decoded while the current
@@ -929,6 +1017,8 @@ class PatchLoader(object):
             yield idx
 
     def _decode(self, idx):
+        if not getattr(self.ds, "decode_ahead", True):     # (clip datasets: an item reads its own files)
+            return [(i, None) for i in idx]
         res = getattr(self.ds, "resident", None)
         return [(i, None if (res is not None and res(i) is not None) else self.pool.submit(load_img, self.ds.image_filenames[i]))
                 for i in idx]
@@ -993,7 +1083,7 @@ class PatchLoader(object):
             images = []
             for i, f in pending.popleft():
                 if f is None:
-                    images.append(ds.resident(i))
+                    images.append(ds.resident(i) if hasattr(ds, "resident") else None)
                 elif isinstance(ds, TrainDatasetFromFolder):
                     with ds.dev.batch():
                         images.append(ds.keep_resident(i, f.result()))

@@ -64,6 +64,112 @@ class ESPCNNet(nn.Module):
             utils.weights_init_normal(m)
 
 
+class MotionCompensator(nn.Module):
+    """The coarse-to-fine flow estimator of VESPCN (Caballero et al., CVPR 2017, table 1), for one pair of frames:
+      coarse, on [cur | nbr] (2C channels): 5x5 s2 conv -> 24, 3x3 -> 24, 5x5 s2 -> 24, 3x3 -> 24 (ReLU each),
+              3x3 -> 32 with tanh, PixelShuffle(4) -> 2 channels at the input size;
+      fine, on [cur | nbr | coarse | flow_warp(nbr, max_flow * coarse)] (3C + 2): 5x5 s2 -> 24, three 3x3 -> 24 (ReLU
+              each), 3x3 -> 8 with tanh, PixelShuffle(2).
+    The flow in PIXELS is max_flow * coarse + max_flow / 4 * fine (x then y displacement); the paper states no scale,
+    max_flow is this project's choice.  The fine stage sees the coarse flow in its tanh units.  H and W must be multiples
+    of 4.  tanh is pointwise, so conv -> tanh -> shuffle is the PSBlock's conv -> shuffle -> tanh.  Key names: this
+    project's own (coarse.{0..4}.conv, fine.{0..4}.conv); no upstream file exists."""
+
+    def __init__(self, num_channels, max_flow=8.0):
+        super(MotionCompensator, self).__init__()
+        c = num_channels
+        self.max_flow = float(max_flow)
+        self.coarse = nn.Sequential(
+            ConvBlock(2 * c, 24, 5, 2, 2, activation='relu', norm=None),
+            ConvBlock(24, 24, 3, 1, 1, activation='relu', norm=None),
+            ConvBlock(24, 24, 5, 2, 2, activation='relu', norm=None),
+            ConvBlock(24, 24, 3, 1, 1, activation='relu', norm=None),
+            PSBlock(24, 2, 4, 3, 1, 1, activation='tanh', norm=None))
+        self.fine = nn.Sequential(
+            ConvBlock(3 * c + 2, 24, 5, 2, 2, activation='relu', norm=None),
+            ConvBlock(24, 24, 3, 1, 1, activation='relu', norm=None),
+            ConvBlock(24, 24, 3, 1, 1, activation='relu', norm=None),
+            ConvBlock(24, 24, 3, 1, 1, activation='relu', norm=None),
+            PSBlock(24, 2, 2, 3, 1, 1, activation='tanh', norm=None))
+
+    def forward(self, pair):
+        """pair [M, 2C, H, W] = [cur | nbr] -> the flow [M, 2, H, W] in pixels that moves nbr onto cur."""
+        c = pair.shape[1] // 2
+        if pair.shape[2] % 4 or pair.shape[3] % 4:
+            raise ValueError("MotionCompensator: a %d x %d input is not a multiple of 4 (two stride-2 stages)"
+                             % (pair.shape[2], pair.shape[3]))
+        coarse = self.coarse(pair)
+        if _training_graph(self, pair):
+            c_in, rest = ops.fork(coarse)     # three consumers: their gradients are added by srk_axpby
+            c_warp, c_sum = ops.fork(rest)
+        else:
+            c_in = c_warp = c_sum = coarse
+        warped = ops.flow_warp(pair[:, c:], ops.axpby(c_warp, None, self.max_flow))
+        fine = self.fine(torch.cat([pair, c_in, warped], 1))
+        return ops.axpby(c_sum, fine, self.max_flow, self.max_flow / 4.0)
+
+
+class VESPCNNet(nn.Module):
+    """VESPCN (Caballero et al., CVPR 2017), three frames, early fusion: the two neighbours are warped onto the centre
+    frame by the MotionCompensator's flow (both through it as one batch of 2N) and [warp(t-1) | frame t | warp(t+1)] goes
+    through ESPCN's 5-3-3 trunk (valid padding) with 3C input channels and PixelShuffle(r): the output is r (H - 8) on a
+    side, to be held against the centre HR frame shaved by 4 r.
+    x: [N,3,C,H,W] (t-1, t, t+1).  forward(x) -> sr; forward_terms(x) -> (sr, mc, flow): the motion-compensation loss
+    of ops.motion_fuse and the flow [2N,2,H,W] in pixels, for the training loss.  Training refuses sides that are not
+    multiples of 4; eval() replicate-pads the bottom and the right up to one and crops the result."""
+
+    def __init__(self, num_channels, base_filter, scale_factor, max_flow=8.0):
+        super(VESPCNNet, self).__init__()
+        if not float(max_flow) > 0.0:
+            raise ValueError("VESPCNNet: max_flow %r is not positive" % (max_flow,))
+        self.num_channels, self.scale_factor = int(num_channels), int(scale_factor)
+        self.mc = MotionCompensator(num_channels, max_flow)
+        self.layers = nn.Sequential(
+            ConvBlock(3 * num_channels, base_filter, 5, 1, 0, activation='relu', norm=None),
+            ConvBlock(base_filter, base_filter // 2, 3, 1, 0, activation='relu', norm=None),
+            PSBlock(base_filter // 2, num_channels, scale_factor, 3, 1, 0, activation=None, norm=None))
+
+    def weight_init(self):
+        for m in self.modules():
+            utils.weights_init_normal(m)
+
+    def check_image_size(self, x):
+        if x.dim() != 5 or x.shape[1] != 3 or x.shape[2] != self.num_channels:
+            raise ValueError("VESPCNNet: expects [N,3,%d,H,W] (frames t-1, t, t+1), got %s" % (self.num_channels, tuple(x.shape)))
+        h, w = x.shape[3], x.shape[4]
+        if min(h, w) < 9:
+            raise ValueError("VESPCNNet: a %d x %d input leaves nothing after the trunk's 8 border pixels" % (h, w))
+        ph, pw = (-h) % 4, (-w) % 4
+        if not (ph or pw):
+            return x
+        if self.training:
+            raise ValueError("VESPCNNet: a %d x %d input is not a multiple of 4 (training); eval() pads" % (h, w))
+        # (plain torch indexing: not the hot path)
+        rows = torch.cat([torch.arange(h), torch.full((ph,), h - 1, dtype=torch.long)]).to(x.device)
+        cols = torch.cat([torch.arange(w), torch.full((pw,), w - 1, dtype=torch.long)]).to(x.device)
+        return x.index_select(3, rows).index_select(4, cols)
+
+    def forward_terms(self, x):
+        h, w = x.shape[-2], x.shape[-1]
+        x = self.check_image_size(x).contiguous()
+        n, _, c, hp, wp = x.shape
+        pair = torch.cat([x[:, 0:2].flip(1), x[:, 1:3]], 0).reshape(2 * n, 2 * c, hp, wp)   # [cur | t-1] then [cur | t+1]
+        flow = self.mc(pair)
+        if _training_graph(self, x):
+            flow, flow_out = ops.fork(flow)
+        else:
+            flow_out = flow
+        fused, mc = ops.motion_fuse(x, flow)
+        sr = self.layers(fused)
+        r = self.scale_factor
+        if (hp, wp) != (h, w):
+            sr = sr[:, :, :r * (h - 8), :r * (w - 8)]
+        return sr, mc, flow_out
+
+    def forward(self, x):
+        return self.forward_terms(x)[0]
+
+
 class FSRCNNNet(nn.Module):
     """fsrcnn.py:13-55 — note the four 3x3 mapping convs have NO activation between them and are
     followed by one bare PReLU (`mid_part.5`)."""

@@ -1043,6 +1043,30 @@ def add(a, b):
     return _Add.apply(a, b)
 
 
+class _Axpby(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, alpha, beta):
+        require_cuda(a, b)
+        if b is not None and a.shape != b.shape:
+            raise RuntimeError("axpby: shape mismatch %s vs %s" % (tuple(a.shape), tuple(b.shape)))
+        ctx.ab = (alpha, beta)
+        a = _dense(a)
+        return _axpby(a, a if b is None else _dense(b), alpha, beta if b is not None else 0.0)
+
+    @staticmethod
+    def backward(ctx, g):
+        alpha, beta = ctx.ab
+        g = _dense(g)
+        return (_axpby(g, g, alpha, 0.0) if ctx.needs_input_grad[0] else None,
+                _axpby(g, g, beta, 0.0) if ctx.needs_input_grad[1] else None, None, None)
+
+
+def axpby(a, b, alpha, beta=0.0):
+    """alpha * a + beta * b (b None: alpha * a) on srk_axpby, each gradient one srk_axpby launch: VESPCN's flow in
+    pixels, max_flow * coarse + max_flow / 4 * fine."""
+    return _Axpby.apply(a, b, float(alpha), float(beta))
+
+
 class _Fork(torch.autograd.Function):
     """Use a tensor twice (trunk + skip) with the gradient fan-in summed by srk_axpby instead of
     autograd's internal ATen add."""
@@ -3614,6 +3638,209 @@ def gan_logit_loss(logits, target_is_real):
     fp32 device tensor under the seed contract of the losses (_declare_seed).
     include/srk.h: srk_gan_logit_loss_forward_backward."""
     return _GanLogitLoss.apply(logits, bool(target_is_real))
+
+
+# ------------------------------------------------------------------------------------------------
+# Motion compensation: flow warp, early fusion, flow smoothness (csrc/mc.hip, csrc/mc_common.h, DESIGN.md 38)
+# ------------------------------------------------------------------------------------------------
+def _flow_arg(who, flow, rows, h, w):
+    """A flow [rows,2,H,W] as the kernels read it: either dense memory format as it is, anything else copied."""
+    if flow.dim() != 4 or tuple(flow.shape) != (rows, 2, h, w) or flow.dtype != torch.float32:
+        raise ValueError("%s: flow must be fp32 [%d,2,%d,%d] (x then y displacement, in pixels), got %s %s"
+                         % (who, rows, h, w, flow.dtype, tuple(flow.shape)))
+    return flow if (_is_nchw_dense(flow) or _is_nhwc_dense(flow)) else flow.contiguous()
+
+
+def _no_image_grad(who, name, img):
+    if img.requires_grad:
+        raise ValueError("%s: `%s` requires a gradient, but the warped image is a data frame: the gradient goes to the flow "
+                         "only (its adjoint would be a scatter); pass %s.detach()" % (who, name, name))
+
+
+class _FlowWarp(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img, flow):
+        n, c, h, w = img.shape
+        out = _empty_cl(n, c, h, w, img)
+        check(_lib.load().srk_flow_warp_forward(ptr(img), _strides4(img), ptr(flow), _strides4(flow), n, c, h, w, ptr(out),
+                                                stream_ptr()), "srk_flow_warp_forward")
+        ctx.save_for_backward(img, flow)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        img, flow = ctx.saved_tensors
+        n, c, h, w = img.shape
+        dflow = torch.empty_like(flow)
+        check(_lib.load().srk_flow_warp_backward(ptr(img), _strides4(img), ptr(flow), _strides4(flow), ptr(g), _strides4(g),
+                                                 n, c, h, w, ptr(dflow), _strides4(dflow), stream_ptr()),
+              "srk_flow_warp_backward")
+        return None, dflow
+
+
+def flow_warp(img, flow):
+    """img [N,C,H,W] sampled bilinearly at (x + flow[:,0], y + flow[:,1]), in pixels, coordinates clamped to the picture:
+    F.grid_sample(mode='bilinear', padding_mode='border', align_corners=True) on pixel coordinates, one launch, the result
+    channels_last.  The gradient goes to the flow only (one launch; on an integer coordinate the right-hand cell's slope,
+    0 where the unclamped coordinate leaves the picture); an img that requires one is a ValueError.
+    include/srk_mc.h: srk_flow_warp_forward / _backward."""
+    if img.dim() != 4 or img.dtype != torch.float32 or img.numel() == 0:
+        raise ValueError("flow_warp: img must be a non-empty fp32 [N,C,H,W] tensor, got %s %s" % (img.dtype, tuple(img.shape)))
+    _no_image_grad("flow_warp", "img", img)
+    require_cuda(img, flow)
+    n, c, h, w = img.shape
+    flow = _flow_arg("flow_warp", flow, n, h, w)
+    return _FlowWarp.apply(img, flow)    # (img is read through its strides: a channel slice of a batch is not copied)
+
+
+class _MotionFuse(torch.autograd.Function):
+    """srk_motion_fuse_forward / _backward.  The mc loss follows the seed contract of the losses: its own seed (the unit
+    seed, or the one declared by loss_seed) is a host factor of the backward launch, any other upstream gradient a
+    device scalar the same launch reads -- no scale pass either way."""
+
+    @staticmethod
+    def forward(ctx, frames, flow):
+        lib = _lib.load()
+        n, _, c, h, w = frames.shape
+        fused = _empty_cl(n, 3 * c, h, w, frames)
+        loss = torch.empty((), dtype=torch.float32, device=frames.device)
+        ws = torch.empty(int(lib.srk_mc_workspace_bytes()), dtype=torch.uint8, device=frames.device)
+        check(lib.srk_motion_fuse_forward(ptr(frames), ptr(flow), _strides4(flow), n, c, h, w, ptr(fused), ptr(loss), ptr(ws),
+                                          stream_ptr()), "srk_motion_fuse_forward")
+        _declare_seed(ctx)
+        ctx.set_materialize_grads(False)   # an unused output's gradient arrives as None, not as a zeros fill
+        ctx.save_for_backward(frames, flow)
+        return fused, loss
+
+    @staticmethod
+    def backward(ctx, g_fused, g_mc):
+        frames, flow = ctx.saved_tensors
+        n, _, c, h, w = frames.shape
+        if g_mc is None:
+            seed, seed_dev = 0.0, None
+        elif _is_own_seed(ctx, g_mc, frames.device):
+            seed, seed_dev = ctx.seed_value, None
+        else:
+            seed, seed_dev = 1.0, g_mc.reshape(()).to(torch.float32)
+        dflow = torch.empty_like(flow)
+        check(_lib.load().srk_motion_fuse_backward(ptr(frames), ptr(flow), _strides4(flow), ptr(g_fused),
+                                                   None if g_fused is None else _strides4(g_fused), n, c, h, w, seed,
+                                                   ptr(seed_dev), ptr(dflow), _strides4(dflow), stream_ptr()),
+              "srk_motion_fuse_backward")
+        return None, dflow
+
+
+def motion_fuse(frames, flow):
+    """VESPCN's early fusion with its motion-compensation loss, one pass: frames [N,3,C,H,W] (t-1, t, t+1), flow
+    [2N,2,H,W] in pixels (rows 0..N-1 move frame t-1 onto t, rows N..2N-1 frame t+1) ->
+      fused [N,3C,H,W] channels_last = [flow_warp(t-1) | frame t | flow_warp(t+1)],
+      mc = mean over all 2 N C H W elements of (warped - frame t)^2, a 0-dim fp32 tensor under the losses' seed contract.
+    The gradient goes to the flow only, in one launch that recomputes the samples; frames that require one are a
+    ValueError.  include/srk_mc.h: srk_motion_fuse_forward / _backward."""
+    if frames.dim() != 5 or frames.shape[1] != 3 or frames.dtype != torch.float32 or frames.numel() == 0:
+        raise ValueError("motion_fuse: frames must be a non-empty fp32 [N,3,C,H,W] tensor (t-1, t, t+1), got %s %s"
+                         % (frames.dtype, tuple(frames.shape)))
+    _no_image_grad("motion_fuse", "frames", frames)
+    require_cuda(frames, flow)
+    n, _, c, h, w = frames.shape
+    flow = _flow_arg("motion_fuse", flow, 2 * n, h, w)
+    return _MotionFuse.apply(frames.contiguous(), flow)
+
+
+class _FlowHuber(torch.autograd.Function):
+    """srk_flow_huber_forward_backward: loss and gradient from one pass and a finish, under the losses' seed contract."""
+
+    @staticmethod
+    def forward(ctx, flow, eps):
+        lib = _lib.load()
+        m, _, h, w = flow.shape
+        loss = torch.empty((), dtype=torch.float32, device=flow.device)
+        dflow = torch.empty_like(flow) if ctx.needs_input_grad[0] else None   # (preserve_format: stored like the flow)
+        ws = torch.empty(int(lib.srk_mc_workspace_bytes()), dtype=torch.uint8, device=flow.device)
+        check(lib.srk_flow_huber_forward_backward(ptr(flow), _strides4(flow), m, h, w, eps, _declare_seed(ctx), ptr(loss),
+                                                  ptr(dflow), ptr(ws), stream_ptr()), "srk_flow_huber_forward_backward")
+        ctx.grads = (dflow,)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        return _seed_scaled(ctx, g, ctx.grads) + (None,)
+
+
+def flow_huber_loss(flow, eps=0.01):
+    """The flow-smoothness term of VESPCN, per pixel: mean over M H W of sqrt(eps + dx_u^2 + dy_u^2 + dx_v^2 + dy_v^2) with
+    the forward differences of both components of flow [M,2,H,W] (0 at the last column and row).  A 0-dim fp32 device
+    tensor under the seed contract of the losses (_declare_seed).  include/srk_mc.h: srk_flow_huber_forward_backward."""
+    require_cuda(flow)
+    if flow.dim() != 4 or flow.numel() == 0:
+        raise ValueError("flow_huber_loss: flow must be a non-empty [M,2,H,W] tensor, got %s" % (tuple(flow.shape),))
+    if not float(eps) > 0.0:
+        raise ValueError("flow_huber_loss: eps %r is not positive" % (eps,))
+    m, _, h, w = flow.shape
+    return _FlowHuber.apply(_flow_arg("flow_huber_loss", flow, m, h, w), float(eps))
+
+
+def _host_flow(who, flow, rows, h, w):
+    flow = np.asarray(flow)
+    if flow.dtype != np.float32 or flow.shape != (rows, 2, h, w) or any(s % 4 or s < 0 for s in flow.strides):
+        raise ValueError("%s: flow must be a float32 [%d,2,%d,%d] array, got %s %s" % (who, rows, h, w, flow.dtype, flow.shape))
+    return flow, (ctypes.c_int64 * 4)(*[s // 4 for s in flow.strides])
+
+
+def _host_grad(who, g, shape):
+    if g is None:
+        return None
+    g = np.ascontiguousarray(g, dtype=np.float64)
+    if g.shape != shape:
+        raise ValueError("%s: the upstream gradient must be %s, got %s" % (who, shape, g.shape))
+    return g
+
+
+def flow_warp_host(img, flow, g=None):
+    """flow_warp on host memory in double (srk_flow_warp_host: the kernels' per-pixel header in plain C++): numpy float32
+    img [N,C,H,W] and flow [N,2,H,W] of any strides -> (out, dflow), float64 NCHW; dflow is for the upstream gradient g
+    ([N,C,H,W]; None: zeros)."""
+    img = np.asarray(img)
+    if img.dtype != np.float32 or img.ndim != 4 or img.size == 0 or any(s % 4 or s < 0 for s in img.strides):
+        raise ValueError("flow_warp_host: img must be a non-empty float32 [N,C,H,W] array, got %s %s" % (img.dtype, img.shape))
+    n, c, h, w = img.shape
+    flow, fs = _host_flow("flow_warp_host", flow, n, h, w)
+    g = _host_grad("flow_warp_host", g, (n, c, h, w))
+    out, dflow = np.empty((n, c, h, w), dtype=np.float64), np.empty((n, 2, h, w), dtype=np.float64)
+    check(_lib.load().srk_flow_warp_host(_np_ptr(img), (ctypes.c_int64 * 4)(*[s // 4 for s in img.strides]), _np_ptr(flow), fs,
+                                         n, c, h, w, _np_ptr(g), _np_ptr(out), _np_ptr(dflow)), "srk_flow_warp_host")
+    return out, dflow
+
+
+def motion_fuse_host(frames, flow, g_fused=None, seed=1.0):
+    """motion_fuse on host memory in double (srk_motion_fuse_host): numpy float32 frames [N,3,C,H,W] and flow [2N,2,H,W]
+    -> (fused [N,3C,H,W], mc, dflow [2N,2,H,W]), float64; dflow is the gradient of sum(g_fused * fused) + seed * mc."""
+    frames = np.ascontiguousarray(frames)
+    if frames.dtype != np.float32 or frames.ndim != 5 or frames.shape[1] != 3 or frames.size == 0:
+        raise ValueError("motion_fuse_host: frames must be a non-empty float32 [N,3,C,H,W] array, got %s %s"
+                         % (frames.dtype, frames.shape))
+    n, _, c, h, w = frames.shape
+    flow, fs = _host_flow("motion_fuse_host", flow, 2 * n, h, w)
+    g = _host_grad("motion_fuse_host", g_fused, (n, 3 * c, h, w))
+    fused, dflow = np.empty((n, 3 * c, h, w), dtype=np.float64), np.empty((2 * n, 2, h, w), dtype=np.float64)
+    loss = ctypes.c_double()
+    check(_lib.load().srk_motion_fuse_host(_np_ptr(frames), _np_ptr(flow), fs, n, c, h, w, float(seed), _np_ptr(g),
+                                           _np_ptr(fused), ctypes.byref(loss), _np_ptr(dflow)), "srk_motion_fuse_host")
+    return fused, loss.value, dflow
+
+
+def flow_huber_host(flow, eps=0.01, grad_scale=1.0):
+    """flow_huber_loss on host memory in double (srk_flow_huber_host) -> (loss, grad_scale * d loss / d flow)."""
+    flow = np.asarray(flow)
+    if flow.ndim != 4 or flow.size == 0:
+        raise ValueError("flow_huber_host: flow must be a non-empty [M,2,H,W] array, got %s" % (flow.shape,))
+    m, _, h, w = flow.shape
+    flow, fs = _host_flow("flow_huber_host", flow, m, h, w)
+    dflow = np.empty((m, 2, h, w), dtype=np.float64)
+    loss = ctypes.c_double()
+    check(_lib.load().srk_flow_huber_host(_np_ptr(flow), fs, m, h, w, float(eps), float(grad_scale), ctypes.byref(loss),
+                                          _np_ptr(dflow)), "srk_flow_huber_host")
+    return loss.value, dflow
 
 
 # ------------------------------------------------------------------------------------------------

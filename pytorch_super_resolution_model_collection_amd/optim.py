@@ -515,7 +515,7 @@ def make_optimizer(kind, flat, lr, ema_decay=0.0):
         return SGD(flat, lr, momentum=0.9, ema_decay=ema_decay)
     if kind == "vdsr":       # vdsr.py:86-90
         return SGD(flat, lr, momentum=0.9, weight_decay=1e-4, ema_decay=ema_decay)
-    if kind in ("espcn", "lapsrn", "drcn"):   # espcn.py:79, lapsrn.py:135, drcn.py:111 (the model group)
+    if kind in ("espcn", "lapsrn", "drcn", "vespcn"):   # espcn.py:79, lapsrn.py:135, drcn.py:111 (the model group); VESPCN as ESPCN
         return Adam(flat, lr, ema_decay=ema_decay)
     if kind in ("esrgan_g", "esrgan_d"):   # ESRGAN: both nets on Adam at the same rate
         return Adam(flat, lr, betas=(0.9, 0.999), eps=1e-8, ema_decay=ema_decay)

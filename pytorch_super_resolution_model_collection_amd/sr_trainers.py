@@ -34,6 +34,8 @@ def synthetic_loader(kind, args, steps, device, seed=1234):
         # per-model pre-steps (bicubic up/down-sampling, shaving) run on the device in _Trainer.prepare
         if kind == "fsrcnn":            # output r(H-5)+4 = target shaved by 2r (fsrcnn.py:143-150)
             yield torch.rand(b, c, lr, lr, generator=g).to(device), torch.rand(b, c, r * (lr - 5) + 4, r * (lr - 5) + 4, generator=g).to(device)
+        elif kind == "vespcn":          # three LR frames [b,3,c,lr,lr] and the centre HR frame (VESPCN.prepare shaves it by 4r)
+            yield torch.rand(b, 3, c, lr, lr, generator=g).to(device), torch.rand(b, c, hr, hr, generator=g).to(device)
         elif kind == "espcn":           # net output r(H-8) (the reference's own target is inconsistent, App. B-2)
             yield torch.rand(b, c, lr, lr, generator=g).to(device), torch.rand(b, c, r * (lr - 8), r * (lr - 8), generator=g).to(device)
         else:                           # srcnn / vdsr / lapsrn / edsr / srgan: (lr, hr)
@@ -208,6 +210,10 @@ def check_discriminator_args(args, kind):
     return disc, gan, 64 if feat is None else int(feat)
 
 
+# VESPCN's own flags and their defaults (None on the command line: the default; set with another model: refused by name)
+VESPCN_FLAGS = {"mc_weight": 0.01, "flow_weight": 0.001, "vespcn_max_flow": 8.0}
+
+
 def check_one_gpu(name):
     """ESRGAN and DRCN: no data parallelism (WORLD_SIZE is what torch.distributed.run sets)."""
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -291,6 +297,9 @@ class _Trainer(object):
         disc_args = check_discriminator_args(args, cls.kind)
         if getattr(args, "net_interp", None) is not None and cls.kind != "esrgan":
             raise ValueError("--net_interp: only ESRGAN has a pre-trained and an adversarial generator to blend, not %s" % name)
+        for flag in VESPCN_FLAGS:
+            if getattr(args, flag, None) is not None and cls.kind != "vespcn":
+                raise ValueError("--%s: only VESPCN has a motion-compensation stage, not %s" % (flag, name))
         check_data_flags(args)
         optim._check_ema_decay(getattr(args, "ema_decay", 0.0))
         return vgg_layers, disc_args
@@ -511,7 +520,7 @@ class _Trainer(object):
     def _channels(self, *tensors):
         """num_channels == 1: only the Y channel is super-resolved (edsr.py:139-142: hr[:, 0].unsqueeze(1))."""
         if self.num_channels == 1:
-            return tuple(t[:, :1].contiguous() if t.shape[1] != 1 else t for t in tensors)
+            return tuple(t[..., :1, :, :].contiguous() if t.shape[-3] != 1 else t for t in tensors)   # (the channel axis of pictures and clips)
         return tensors
 
     # -- reference surface ------------------------------------------------------------------------
@@ -721,7 +730,7 @@ class _Trainer(object):
             for batch in batches:
                 items = [batch] if torch.is_tensor(batch[0]) else list(zip(*batch))   # ragged test images come as lists
                 for item in items:
-                    lr_img, hr_img = self._channels(*[t if t.dim() == 4 else t.unsqueeze(0) for t in item[:2]])
+                    lr_img, hr_img = self._channels(*[t if t.dim() >= 4 else t.unsqueeze(0) for t in item[:2]])   # (5-D: a batch of clips)
                     out = self._forward(lr_img.to(self.device), tile, self_ensemble=self_ensemble)
                     hr = hr_img.to(self.device)
                     mine.add(out, self._shave(hr))   # (srcnn.py:193-199: border excluded)
@@ -1496,5 +1505,230 @@ class SwinIR(_Trainer):
                                 self.scale_factor, self.upsampler)
 
 
+# -- the three-frame window of VESPCN's test_video --------------------------------------------------------------------------
+# Frame t of the output comes from frames (max(t - 1, 0), t, min(t + 1, T - 1)) of the stream, and the net sees whole
+# batches.  An input slot holds video_batch + 2 frames: [carry, carry, k fresh frames].  The two carries are the last two
+# frames of the previous slot; in the first slot both are replicas of the stream's first frame.  A read that comes back
+# short (k < video_batch, 0 included) has seen the end of the stream and puts a replica of the last frame behind the
+# fresh ones.  So the output lags the input by one frame, and a final empty read flushes the last frame.  Both functions
+# are pure host code (tests/test_vespcn_cpu.py drives them with frame numbers in place of frames).
+def video_window(k, first, last):
+    """One batch of the schedule: k fresh frames read, `first` batch of the stream, `last` (the read came back short).
+    -> (m, lo, n): the slot's first m frames are in use, the windows are slot[j - 1 : j + 2] for the n centres
+    j = lo .. lo + n - 1 (n may be 0: a first batch of one frame that is not the last)."""
+    m = 2 + k + (1 if last else 0)
+    lo = 2 if first else 1
+    return m, lo, max(m - 1 - lo, 0)
+
+
+def video_window_fill(slot, prev, k, kprev, first, last):
+    """Completes a slot whose fresh frames lie at slot[2 : 2 + k]: the carries (from `prev`, the previous slot with its
+    kprev fresh frames; replicas of the first frame in the first batch) and the end's replica.  slot, prev: anything
+    indexable by frame whose rows can be assigned (pinned uint8 tensors, numpy arrays)."""
+    if first:
+        if k == 0:
+            raise ValueError("test_video: the stream holds no frame")
+        slot[0] = slot[2]
+        slot[1] = slot[2]
+    else:
+        slot[0] = prev[kprev]
+        slot[1] = prev[kprev + 1]
+    if last:
+        slot[2 + k] = slot[1 + k]
+
+
+class VESPCN(_Trainer):
+    """VESPCN (models.VESPCNNet; not in the reference collection) behind the common trainer: three LR frames in, the
+    super-resolved centre frame out; MSE + `--mc_weight` * motion-compensation MSE + `--flow_weight` * flow smoothness
+    on Adam, ESPCN's optimizer rule (trainers.build("vespcn")); `--vespcn_max_flow`.  Batches are (frames [B,3,C,h,w],
+    centre HR frame); the target is shaved by 4 r, what the valid trunk leaves.  A single picture (test_single, test() on
+    picture folders) is its own neighbours: the flow net then sees three equal frames.  One GPU."""
+    kind = "vespcn"
+    HYPER = VESPCN_FLAGS
+
+    @classmethod
+    def check_flags(cls, args):
+        if getattr(args, "tile", None) is not None:
+            raise ValueError("--tile: VESPCN's MotionCompensator warps by a learned flow of up to 1.25 --vespcn_max_flow "
+                             "pixels, its pictures run in one pass (drop --tile)")
+        if getattr(args, "self_ensemble", False):
+            raise ValueError("--self_ensemble: a flipped or rotated clip is not run for VESPCN (its flow has a direction); "
+                             "drop --self_ensemble")
+        check_one_gpu("VESPCN")
+        for flag in ("degrade", "degrade_test", "degrade2", "degrade2_test", "usm", "jpeg_quality", "jpeg_test"):
+            v = getattr(args, flag, None)
+            if v is not None and v is not False:
+                raise ValueError("--%s: VESPCN's clips are shrunk by the clean bicubic only; the degradations are per-picture "
+                                 "and not built for three frames" % flag)
+        for flag in ("ssim_weight", "fft_weight", "lpips_weight"):
+            if (getattr(args, flag, 0.0) or 0.0) > 0:
+                raise ValueError("--%s %g: VESPCN trains on MSE + motion compensation + flow smoothness and has no %s; use "
+                                 "--%s 0" % (flag, getattr(args, flag), TERM_FLAGS[flag][0], flag))
+        h = cls.hyper(args)
+        if not float(h["vespcn_max_flow"]) > 0.0:
+            raise ValueError("--vespcn_max_flow %r is not positive" % (args.vespcn_max_flow,))
+        scale, crop = getattr(args, "scale_factor", None) or 4, getattr(args, "crop_size", None)   # (main.py's default scale)
+        if crop is not None and (crop // scale) % 4:
+            raise ValueError("--crop_size %d / --scale_factor %d = %d is not a multiple of 4, which the two stride-2 stages "
+                             "of VESPCN's flow net need" % (crop, scale, crop // scale))
+        return super(VESPCN, cls).check_flags(args)
+
+    @classmethod
+    def hyper(cls, args):
+        return {flag: default if getattr(args, flag, None) is None else getattr(args, flag) for flag, default in cls.HYPER.items()}
+
+    def __init__(self, args):
+        super(VESPCN, self).__init__(args)
+        h = self.hyper(args)
+        self.mc_weight, self.flow_weight, self.max_flow = float(h["mc_weight"]), float(h["flow_weight"]), float(h["vespcn_max_flow"])
+
+    def build_model(self):
+        return models.VESPCNNet(self.num_channels, 64, self.scale_factor, self.max_flow)
+
+    def build_step(self):
+        return trainers.build(self.kind, self.model, self.lr, use_dp=False, ema_decay=self.ema_decay,
+                              mc_weight=self.mc_weight, flow_weight=self.flow_weight)
+
+    def load_dataset(self, dataset, is_train=True):
+        """Clip folders, data_dir/<dataset>/<clip>/<frames>, through data.PatchLoader: data.ClipDataset for training,
+        data.ClipTestDataset for test(); None with --synthetic."""
+        from . import data
+        if not is_train:
+            # a test set of clip folders: every frame with its neighbours (the ends use themselves); a folder of pictures
+            # goes through the picture loader, each picture its own neighbours
+            root = os.path.join(self.data_dir or "", dataset)
+            if bool(getattr(self.args, "synthetic", False)) or not os.path.isdir(root):
+                return None
+            if not any(os.path.isdir(os.path.join(root, d)) for d in os.listdir(root)):
+                return super(VESPCN, self).load_dataset(dataset, is_train)
+            ds = data.get_clip_test_set(self.data_dir, dataset, self.scale_factor, is_gray=self.num_channels == 1,
+                                        device=self.device)
+            return data.PatchLoader(ds, 1, shuffle=False, num_threads=self.num_threads or 4) if len(ds) else None
+        if bool(getattr(self.args, "synthetic", False)):
+            return None
+        try:
+            ds = data.get_clip_training_set(self.data_dir, dataset, self.crop_size, self.scale_factor,
+                                            is_gray=self.num_channels == 1, device=self.device)
+        except (OSError, TypeError) as e:
+            raise FileNotFoundError("training clips %r not found under --data_dir %r (%s: %s); pass --synthetic to train on "
+                                    "seeded random clips instead" % (dataset, self.data_dir, type(e).__name__, e))
+        if len(ds) == 0:
+            raise FileNotFoundError("training set %r under --data_dir %r holds no clip folder of three or more frames; pass "
+                                    "--synthetic to train on seeded random clips instead" % (dataset, self.data_dir))
+        return data.PatchLoader(ds, self.batch_size, shuffle=True, num_threads=self.num_threads or 4, seed=1234)
+
+    def _shave(self, target):
+        return utils.shave(target, 4 * self.scale_factor)
+
+    def prepare(self, inp, target):
+        return self._net_input(inp), self._shave(target).contiguous()
+
+    def _net_input(self, x):
+        """A clip [N,3,C,H,W] as it is; pictures [N,C,H,W] as their own neighbours."""
+        return x if x.dim() == 5 else x.unsqueeze(1).expand(-1, 3, -1, -1, -1).contiguous()
+
+    VIDEO_SLOTS = 2   # input and output buffers: one in flight on the device, one with the host
+
+    def test_video(self, src, dst=None, batch=None, tile=None, tile_batch=None, self_ensemble=None):
+        """_Trainer.test_video for a net that looks at three frames: output frame t is the net on frames (max(t - 1, 0),
+        t, min(t + 1, T - 1)) of the stream, as many frames out as in; a Y model's chroma comes from frame t.  The
+        schedule is video_window / video_window_fill above: slots of video_batch + 2 frames, the last two frames of a
+        slot carried into the next, the first and the last frame of the stream replicated, the output one frame behind
+        the input and a final short (or empty) read flushing the last frame.  Per batch: one upload of the slot,
+        k_yuv_unpack of its frames, the [n,3,C,H,W] windows (one strided copy), the net on the whole batch, k_yuv_pack
+        of the n centre frames, one download; the previous batch's frames are written while this one runs.  Every
+        buffer is made once (the output side when the first batch has shown the net's output size).  tile and
+        self_ensemble are refused, as VESPCN.check_flags refuses them."""
+        import contextlib
+        import sys
+        import time
+        from . import data
+        if isinstance(dst, (str, os.PathLike)) and os.fspath(dst) == '-':
+            with contextlib.redirect_stdout(sys.stderr):
+                return self.test_video(src, sys.stdout.buffer, batch, tile, tile_batch, self_ensemble)
+        if _option(self.args, 'tile', tile) is not None or self._self_ensemble(self_ensemble):
+            raise ValueError("test_video: VESPCN runs its frames in one pass, without --tile and --self_ensemble")
+        self._ensure_model()
+        n_max = int(_option(self.args, 'video_batch', batch, 8))
+        if n_max <= 0:
+            raise ValueError("test_video: batch must be positive (got %d)" % n_max)
+        if dst is None:
+            dst = os.path.join(self.save_dir, 'test_result', 'SR_result.y4m')
+        slots = self.VIDEO_SLOTS
+        reader = data.Y4MReader(src)
+        lay = reader.layout
+        pin_in = [torch.empty((n_max + 2, lay.frame_bytes), dtype=torch.uint8, pin_memory=True) for _ in range(slots)]
+        dev_in = [torch.empty((n_max + 2, lay.frame_bytes), dtype=torch.uint8, device=self.device) for _ in range(slots)]
+        ev_up = [torch.cuda.Event() for _ in range(slots)]
+        ev_down = [torch.cuda.Event() for _ in range(slots)]
+        pin_out = dev_out = out_lay = writer = None
+        trace = getattr(self, 'video_trace', None)
+        pending = None                      # (output slot, frames) downloaded but not written yet
+        frames_done, b, kprev, first = 0, 0, 0, True
+        t0 = time.perf_counter()
+        try:
+            while True:
+                i = b % slots
+                ev_up[i].synchronize()      # its last upload has left the pinned buffer
+                k = reader.read_into(pin_in[i][2:2 + n_max], n_max)
+                last = k < n_max
+                video_window_fill(pin_in[i], pin_in[(b - 1) % slots], k, kprev, first, last)
+                m, lo, n = video_window(k, first, last)
+                if n:
+                    dev_in[i][:m].copy_(pin_in[i][:m], non_blocking=True)
+                    ev_up[i].record()
+                    x = ops.yuv_unpack(dev_in[i][:m], lay, self.num_channels)
+                    win = torch.stack([x[lo - 1:lo - 1 + n], x[lo:lo + n], x[lo + 1:lo + 1 + n]], 1)
+                    y = self._net(win)
+                    if y.dim() != 4 or int(y.shape[0]) != n or int(y.shape[1]) != self.num_channels:
+                        raise RuntimeError("test_video: the net returned %s for %d windows of %d channel(s)"
+                                           % (tuple(y.shape), n, self.num_channels))
+                    if out_lay is None:
+                        out_lay = ops.yuv_layout(int(y.shape[-1]), int(y.shape[-2]), lay.sub,
+                                                 "the net's output for a %s stream" % (reader.header.chroma_tag or "C420jpeg"))
+                        writer = data.Y4MWriter(dst, reader.header.scaled(out_lay.W, out_lay.H))
+                        pin_out = [torch.empty((n_max + 1, out_lay.frame_bytes), dtype=torch.uint8, pin_memory=True) for _ in range(slots)]
+                        dev_out = [torch.empty((n_max + 1, out_lay.frame_bytes), dtype=torch.uint8, device=self.device) for _ in range(slots)]
+                    o = b % slots            # (its last download was written out during the previous batch)
+                    self._video_pack(y, dev_in[i][lo:lo + n], lay, out_lay, dev_out[o][:n])
+                    pin_out[o][:n].copy_(dev_out[o][:n], non_blocking=True)
+                    ev_down[o].record()
+                    del x, win, y
+                if trace is not None:
+                    trace.append(torch.cuda.memory_allocated(self.device))
+                if pending is not None:      # the previous batch's frames go out while this batch runs
+                    ev_down[pending[0]].synchronize()
+                    writer.write(pin_out[pending[0]], pending[1])
+                    frames_done += pending[1]
+                pending = (b % slots, n) if n else None
+                kprev, first, b = k, False, b + 1
+                if last:
+                    break
+            if pending is not None:
+                ev_down[pending[0]].synchronize()
+                writer.write(pin_out[pending[0]], pending[1])
+                frames_done += pending[1]
+        finally:
+            torch.cuda.current_stream().synchronize()
+            reader.close()
+            if writer is not None:
+                writer.close()
+        dt = time.perf_counter() - t0
+        print('Video: %d frames -> %d x %d (%s), %.1f frames/s' % (frames_done, out_lay.W, out_lay.H, lay.sub, frames_done / dt))
+        return frames_done
+
+
 TRAINERS = {"SRCNN": SRCNN, "VDSR": VDSR, "ESPCN": ESPCN, "FSRCNN": FSRCNN, "SRGAN": SRGAN, "LapSRN": LapSRN, "EDSR": EDSR,
             "DRCN": DRCN, "RCAN": RCAN, "RDN": RDN, "SwinIR": SwinIR, "ESRGAN": ESRGAN}
+# The nets that take clips, [N,3,C,H,W], instead of pictures: a table of their own beside the twelve picture models.
+# trainer_class(name) and model_names() are what main.py asks.
+VIDEO_TRAINERS = {"VESPCN": VESPCN}
+
+
+def model_names():
+    return list(TRAINERS) + list(VIDEO_TRAINERS)
+
+
+def trainer_class(name):
+    """The trainer class of --model_name `name`, from either table."""
+    return TRAINERS[name] if name in TRAINERS else VIDEO_TRAINERS[name]

@@ -216,6 +216,9 @@ def _walk(g, m, path):
         if m.mode != "nearest" or r is None or int(r) != r:
             raise ValueError("%s: only integer nearest-neighbour up-sampling has a tiling geometry" % path)
         return _upsample(g, int(r))
+    if isinstance(m, _models().MotionCompensator):
+        raise ValueError("%s: MotionCompensator warps by a learned flow, its reach depends on the picture and cannot be "
+                         "tiled" % path)
     if isinstance(m, _WHOLE_IMAGE):
         raise ValueError("%s: %s depends on the whole image and cannot be tiled" % (path, type(m).__name__))
     if isinstance(m, torch.nn.modules.batchnorm._BatchNorm):
@@ -226,6 +229,11 @@ def _walk(g, m, path):
     if isinstance(m, _POINTWISE):
         return g
     raise ValueError("%s: no tiling geometry for a %s" % (path, type(m).__name__))
+
+
+def _models():
+    from . import models
+    return models
 
 
 def net_geometry(model):
@@ -286,6 +294,8 @@ def net_geometry(model):
             h = _walk(h, model.conv_block, "conv_block")
             out = _union(out, _walk(h, model.reconstruction_layer, "reconstruction_layer"), "reconstruction_layer")
         return out
+    if isinstance(model, M.VESPCNNet):   # raises at the MotionCompensator
+        return _walk(_walk(g, model.mc, "mc"), model.layers, "layers")
     raise ValueError("net_geometry: no composition rule for a %s" % type(model).__name__)
 
 

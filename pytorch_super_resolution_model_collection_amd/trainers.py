@@ -195,6 +195,48 @@ def lapsrn_step(model, opt, dp=None, **terms):
     return step
 
 
+def vespcn_segments(model, opt, mc_weight=0.01, flow_weight=0.001, dp=None):
+    """VESPCN's joint step (Caballero et al. 2017, eq. 7) on frames [B,3,C,H,W] and the shaved centre HR frame:
+      loss = MSE(sr, hr) + mc_weight * mc + flow_weight * flow_huber(total flow),
+    mc the motion-compensation loss of ops.motion_fuse and the flow the MotionCompensator's, in pixels, for both
+    neighbours.  On one GPU each weight in (0, 1) is declared as its term's seed (ops.loss_seed, as ops.weighted_term
+    does), so the two kernels fold it into the gradient they write and no scale pass runs; the sums are srk_axpby
+    (ops.loss_sum).  The same cut as loss_segments: [(zero_grad + forward + loss + backward, dp), (optimizer step, None)]."""
+    mc_weight, flow_weight = float(mc_weight), float(flow_weight)
+    for name, v in (("mc_weight", mc_weight), ("flow_weight", flow_weight)):
+        if not 0.0 <= v < float("inf"):
+            raise ValueError("vespcn step: %s %r is not a non-negative finite number" % (name, v))
+    out = []
+
+    def weighted(weight, device):
+        if ops._LOSS_SEED[0] is None and 0.0 < weight < 1.0:
+            return ops.loss_seed(weight, ops._const_scalar(weight, device))
+        return contextlib.nullcontext()
+
+    def fwd_bwd(frames, target):
+        opt.zero_grad()
+        with _seeded(dp):
+            with weighted(mc_weight, frames.device):      # (the only loss node inside the net is motion_fuse's)
+                sr, mc, flow = model.forward_terms(frames)
+            with weighted(flow_weight, frames.device):
+                smooth = ops.flow_huber_loss(flow)
+            loss = ops.loss_sum(ops.loss_sum(ops.mse_loss(sr, target), mc, 1.0, mc_weight), smooth, 1.0, flow_weight)
+        _backward(loss, dp)
+        out.append(loss)
+        return loss
+
+    def update(*batch):
+        opt.step()
+        return out.pop()
+
+    return [(fwd_bwd, dp), (update, None)]
+
+
+def vespcn_step(model, opt, mc_weight=0.01, flow_weight=0.001, dp=None):
+    """The eager closure of `vespcn_segments` (see there); it carries `segments`, so the common capture takes it."""
+    return eager_step(vespcn_segments(model, opt, mc_weight, flow_weight, dp))
+
+
 def drcn_step(model, opt, w_opt, alpha_dev, beta, reg_dev=None):
     """drcn.py:196-221: zero_grad -> forward -> loss = alpha * mean_d MSE(y_d, t) + (1 - alpha) * MSE(out, t)
     + beta * sum_theta sum theta^2 (R of the parameters BEFORE the update; w excluded) -> backward -> Adam on the model's
@@ -624,6 +666,7 @@ class GraphedStep(GraphedSegments):
 # The kinds that train on a loss of their own (SRGAN and ESRGAN on adversarial content terms, DRCN through its fused
 # recursive-supervision head): mixed_loss's terms are refused for them, here and by sr_trainers' flag checks.
 OWN_LOSS_KINDS = ("srgan", "drcn", "esrgan")
+VESPCN_TERMS = {"mc_weight": 0.01, "flow_weight": 0.001}   # the paper's values as remembered, unchecked
 
 
 def build(kind, model, lr, dp_group=None, use_dp=False, ema_decay=0.0, **terms):
@@ -642,6 +685,12 @@ def build(kind, model, lr, dp_group=None, use_dp=False, ema_decay=0.0, **terms):
     if dp is not None:
         dp.broadcast_params()
         opt.ema_reset()      # (the shadow starts as a copy of the parameters every rank now has)
+    if kind == "vespcn":   # ESPCN's optimizer rule (optim.make_optimizer); its own three-term loss
+        own = {k: terms.pop(k, v) for k, v in VESPCN_TERMS.items()}
+        extra = sorted(k for k, v in terms.items() if k in ("ssim_weight", "fft_weight", "lpips_weight") and v)
+        if extra:
+            raise ValueError("%s: vespcn trains on MSE + mc + flow smoothness and has no such term" % ", ".join(extra))
+        return flat, opt, dp, vespcn_step(model, opt, dp=dp, **own)
     if kind in ("edsr", "rcan", "rdn", "swinir"):
         return flat, opt, dp, l1_step(model, opt, dp, **terms)
     if kind == "lapsrn":
