@@ -20,7 +20,7 @@ import random
 import torch
 
 from . import dp as dpmod
-from . import evaluation, models, ops, optim, tiling, trainers, utils
+from . import evaluation, models, ops, optim, tiling, trainers, utils, video_stream
 
 
 def synthetic_loader(kind, args, steps, device, seed=1234):
@@ -819,29 +819,15 @@ class _Trainer(object):
         return save_fn
 
     # -- raw video streams (data.Y4MReader / Y4MWriter, csrc/video.hip) -------------------------------------------------
-    VIDEO_SLOTS = 3   # pinned + device buffers per direction: one being filled, one in flight, one being consumed
+    VIDEO_RADIUS = 0   # frames on either side of frame t that the net looks at for output frame t (video_stream)
 
-    def _video_net(self, frames, lay, per_frame, tile, tile_batch, ens):
-        """Packed frames (device, uint8 [n, frame_bytes]) -> yuv_unpack -> the net's fp32 output [n,C,OH,OW], on the
-        current stream."""
-        n = int(frames.shape[0])
-        x = ops.yuv_unpack(frames, lay, self.num_channels)
-        if per_frame:   # --tile / --self_ensemble: the existing one-picture path in its fp32 form, frame by frame
-            y = torch.cat([self._run(self._net_input(x[k:k + 1]), tile, tile_batch, ens) for k in range(n)])
-        else:
-            y = self._net(self._net_input(x))
-        if y.dim() != 4 or int(y.shape[0]) != n or int(y.shape[1]) != self.num_channels:
-            raise RuntimeError("test_video: the net returned %s for a batch of %d frames of %d channel(s)"
-                               % (tuple(y.shape), n, self.num_channels))
-        return y
-
-    def _video_pack(self, y, frames, lay, out_lay, out):
-        """The net's output y -> the packed output frames `out`, one yuv_pack launch; a Y model's Cb / Cr come from the
-        input frames through the 8-bit bicubic resizer, to the chroma size of what the net actually returned."""
-        chroma = None
-        if self.num_channels == 1 and lay.sub != "mono":
-            chroma = ops.yuv_chroma(frames, lay, out_lay.ch, out_lay.cw)
-        ops.yuv_pack(y, out_lay, chroma, out=out)
+    def _video_net(self, tile, tile_batch, ens):
+        """The net of test_video, video_stream.run's callable: the unpacked slot x and (lo, n) -> the fp32 output for
+        the frames x[lo : lo + n].  tile (the option, resolved) / ens: frame by frame through the existing one-picture
+        path in its fp32 form, with its refusals."""
+        if ens or tile is not None:
+            return lambda x, lo, n: torch.cat([self._run(self._net_input(x[j:j + 1]), tile, tile_batch, ens) for j in range(lo, lo + n)])
+        return lambda x, lo, n: self._net(self._net_input(x[lo:lo + n]))
 
     def test_video(self, src, dst=None, batch=None, tile=None, tile_batch=None, self_ensemble=None):
         """Super-resolve a YUV4MPEG2 stream (8-bit 4:2:0, 4:4:4 or mono, progressive): src / dst are a path, '-' (stdin /
@@ -852,18 +838,14 @@ class _Trainer(object):
         the input through the 8-bit bicubic resizer to the chroma size of what the net returned; 3: Pillow's RGB -> YCbCr
         and for 4:2:0 its BOX shrink of the chroma, fused).  Samples are full-range JFIF values; the chroma resampling is
         centre-aligned whatever the C tag says, and the tag is carried through.
-        A reader thread fills VIDEO_SLOTS pinned buffers, uploads, compute and downloads run on three streams joined by
-        events, a writer thread drains VIDEO_SLOTS pinned buffers; nothing waits for the whole device, and every buffer
-        is made once (the output side after the first batch has shown the net's output size).
+        The pipeline is video_stream.run, the same for every trainer: reader and writer threads, three streams, every
+        buffer made once.  A trainer gives it VIDEO_RADIUS (output frame t is the net on frames max(t - R, 0) ..
+        min(t + R, T - 1) of the stream, as many frames out as in; a Y model's chroma comes from frame t) and _video_net.
         tile / tile_batch / self_ensemble as test_single: with either, frames go one at a time through _run, with its
         refusals.  dst '-': everything this call prints goes to stderr.  A caller that sets self.video_trace to a list gets
         torch.cuda.memory_allocated() appended at the end of every batch."""
         import contextlib
-        import queue
         import sys
-        import threading
-        import time
-        from . import data
         if isinstance(dst, (str, os.PathLike)) and os.fspath(dst) == '-':
             # stdout carries the stream and nothing else: whatever this call prints (load_model's line, the frame count)
             # goes to stderr
@@ -871,124 +853,16 @@ class _Trainer(object):
             with contextlib.redirect_stdout(sys.stderr):
                 return self.test_video(src, sink, batch, tile, tile_batch, self_ensemble)
         self._ensure_model()
+        net = self._video_net(_option(self.args, 'tile', tile), tile_batch, self._self_ensemble(self_ensemble))
         n_max = int(_option(self.args, 'video_batch', batch, 8))
         if n_max <= 0:
             raise ValueError("test_video: batch must be positive (got %d)" % n_max)
         if dst is None:
             dst = os.path.join(self.save_dir, 'test_result', 'SR_result.y4m')
-        ens = self._self_ensemble(self_ensemble)
-        per_frame = ens or _option(self.args, 'tile', tile) is not None
-        slots = self.VIDEO_SLOTS
-        reader = data.Y4MReader(src)
-        lay = reader.layout
-        pin_in = [torch.empty((n_max, lay.frame_bytes), dtype=torch.uint8, pin_memory=True) for _ in range(slots)]
-        dev_in = [torch.empty((n_max, lay.frame_bytes), dtype=torch.uint8, device=self.device) for _ in range(slots)]
-        pin_out = dev_out = out_lay = writer = write_thread = None
-        h2d, comp, d2h = (torch.cuda.Stream(self.device) for _ in range(3))
-        ev_up, ev_in_used, ev_packed, ev_down = ([torch.cuda.Event() for _ in range(slots)] for _ in range(4))
-        free_in, filled, free_out, to_write = (queue.Queue() for _ in range(4))
-        for i in range(slots):
-            free_in.put(i)
-            free_out.put(i)
-
-        def read_loop():
-            try:
-                while True:
-                    i = free_in.get()
-                    if i is None:
-                        return
-                    ev_up[i].synchronize()   # its last upload has left the pinned buffer
-                    k = reader.read_into(pin_in[i], n_max)
-                    filled.put((i, k))
-                    if k < n_max:
-                        return
-            except BaseException as e:   # handed to the caller's thread
-                filled.put(e)
-
-        def write_loop():
-            try:
-                while True:
-                    item = to_write.get()
-                    if item is None:
-                        return
-                    o, k = item
-                    ev_down[o].synchronize()
-                    writer.write(pin_out[o], k)
-                    free_out.put(o)
-            except BaseException as e:
-                free_out.put(e)
-
-        def take(q):
-            item = q.get()
-            if isinstance(item, BaseException):
-                raise item
-            return item
-
-        trace = getattr(self, 'video_trace', None)
-        frames_done = 0
-        t0 = time.perf_counter()
-        cur = torch.cuda.current_stream()
-        for s in (h2d, comp, d2h):
-            s.wait_stream(cur)
-        read_thread = threading.Thread(target=read_loop, name="y4m-reader", daemon=True)
-        read_thread.start()
-        try:
-            while True:
-                i, k = take(filled)
-                if k == 0:
-                    break
-                with torch.cuda.stream(h2d):
-                    h2d.wait_event(ev_in_used[i])
-                    dev_in[i][:k].copy_(pin_in[i][:k], non_blocking=True)
-                    ev_up[i].record(h2d)
-                with torch.cuda.stream(comp):
-                    comp.wait_event(ev_up[i])
-                    y = self._video_net(dev_in[i][:k], lay, per_frame, tile, tile_batch, ens)
-                    if out_lay is None:   # the first batch shows the net's output size: the output side is made now
-                        out_lay = ops.yuv_layout(int(y.shape[-1]), int(y.shape[-2]), lay.sub,
-                                                 "the net's output for a %s stream" % (reader.header.chroma_tag or "C420jpeg"))
-                        writer = data.Y4MWriter(dst, reader.header.scaled(out_lay.W, out_lay.H))
-                        pin_out = [torch.empty((n_max, out_lay.frame_bytes), dtype=torch.uint8, pin_memory=True) for _ in range(slots)]
-                        dev_out = [torch.empty((n_max, out_lay.frame_bytes), dtype=torch.uint8, device=self.device) for _ in range(slots)]
-                        write_thread = threading.Thread(target=write_loop, name="y4m-writer", daemon=True)
-                        write_thread.start()
-                    o = take(free_out)   # the writer has drained it, so its last download is over
-                    self._video_pack(y, dev_in[i][:k], lay, out_lay, dev_out[o][:k])
-                    ev_in_used[i].record(comp)
-                    ev_packed[o].record(comp)
-                    del y
-                    if trace is not None:
-                        trace.append(torch.cuda.memory_allocated(self.device))
-                free_in.put(i)
-                with torch.cuda.stream(d2h):
-                    d2h.wait_event(ev_packed[o])
-                    pin_out[o][:k].copy_(dev_out[o][:k], non_blocking=True)
-                    ev_down[o].record(d2h)
-                to_write.put((o, k))
-                frames_done += k
-                if k < n_max:
-                    break
-            if frames_done == 0:
-                raise ValueError("test_video: the stream holds no frame")
-            to_write.put(None)
-            write_thread.join()
-            for item in list(free_out.queue):   # the drained slots, or the writer's exception
-                if isinstance(item, BaseException):
-                    raise item
-            read_thread.join()   # it has seen the end of the stream
-        finally:   # the end of the call, not its steady state (on an error the reader may sit in a read: it is a daemon)
-            free_in.put(None)
-            to_write.put(None)
-            if write_thread is not None:
-                write_thread.join()
-            for s in (h2d, comp, d2h):
-                s.synchronize()
-            reader.close()
-            if writer is not None:
-                writer.close()
-        dt = time.perf_counter() - t0
-        print('Video: %d frames -> %d x %d (%s), %.1f frames/s' % (frames_done, out_lay.W, out_lay.H, lay.sub, frames_done / dt))
-        return frames_done
+        frames, lay, out_lay, dt = video_stream.run(src, dst, n_max, self.VIDEO_RADIUS, net, self.num_channels, self.device,
+                                                    getattr(self, 'video_trace', None))
+        print('Video: %d frames -> %d x %d (%s), %.1f frames/s' % (frames, out_lay.W, out_lay.H, lay.sub, frames / dt))
+        return frames
 
     def _ckpt_name(self, epoch):
         # srcnn.py:260-269 style for the simple trainers, edsr.py:324-337 style (ch/batch/epoch/lr) for EDSR / SRGAN
@@ -1505,38 +1379,6 @@ class SwinIR(_Trainer):
                                 self.scale_factor, self.upsampler)
 
 
-# -- the three-frame window of VESPCN's test_video --------------------------------------------------------------------------
-# Frame t of the output comes from frames (max(t - 1, 0), t, min(t + 1, T - 1)) of the stream, and the net sees whole
-# batches.  An input slot holds video_batch + 2 frames: [carry, carry, k fresh frames].  The two carries are the last two
-# frames of the previous slot; in the first slot both are replicas of the stream's first frame.  A read that comes back
-# short (k < video_batch, 0 included) has seen the end of the stream and puts a replica of the last frame behind the
-# fresh ones.  So the output lags the input by one frame, and a final empty read flushes the last frame.  Both functions
-# are pure host code (tests/test_vespcn_cpu.py drives them with frame numbers in place of frames).
-def video_window(k, first, last):
-    """One batch of the schedule: k fresh frames read, `first` batch of the stream, `last` (the read came back short).
-    -> (m, lo, n): the slot's first m frames are in use, the windows are slot[j - 1 : j + 2] for the n centres
-    j = lo .. lo + n - 1 (n may be 0: a first batch of one frame that is not the last)."""
-    m = 2 + k + (1 if last else 0)
-    lo = 2 if first else 1
-    return m, lo, max(m - 1 - lo, 0)
-
-
-def video_window_fill(slot, prev, k, kprev, first, last):
-    """Completes a slot whose fresh frames lie at slot[2 : 2 + k]: the carries (from `prev`, the previous slot with its
-    kprev fresh frames; replicas of the first frame in the first batch) and the end's replica.  slot, prev: anything
-    indexable by frame whose rows can be assigned (pinned uint8 tensors, numpy arrays)."""
-    if first:
-        if k == 0:
-            raise ValueError("test_video: the stream holds no frame")
-        slot[0] = slot[2]
-        slot[1] = slot[2]
-    else:
-        slot[0] = prev[kprev]
-        slot[1] = prev[kprev + 1]
-    if last:
-        slot[2 + k] = slot[1 + k]
-
-
 class VESPCN(_Trainer):
     """VESPCN (models.VESPCNNet; not in the reference collection) behind the common trainer: three LR frames in, the
     super-resolved centre frame out; MSE + `--mc_weight` * motion-compensation MSE + `--flow_weight` * flow smoothness
@@ -1627,95 +1469,14 @@ class VESPCN(_Trainer):
         """A clip [N,3,C,H,W] as it is; pictures [N,C,H,W] as their own neighbours."""
         return x if x.dim() == 5 else x.unsqueeze(1).expand(-1, 3, -1, -1, -1).contiguous()
 
-    VIDEO_SLOTS = 2   # input and output buffers: one in flight on the device, one with the host
+    VIDEO_RADIUS = 1
 
-    def test_video(self, src, dst=None, batch=None, tile=None, tile_batch=None, self_ensemble=None):
-        """_Trainer.test_video for a net that looks at three frames: output frame t is the net on frames (max(t - 1, 0),
-        t, min(t + 1, T - 1)) of the stream, as many frames out as in; a Y model's chroma comes from frame t.  The
-        schedule is video_window / video_window_fill above: slots of video_batch + 2 frames, the last two frames of a
-        slot carried into the next, the first and the last frame of the stream replicated, the output one frame behind
-        the input and a final short (or empty) read flushing the last frame.  Per batch: one upload of the slot,
-        k_yuv_unpack of its frames, the [n,3,C,H,W] windows (one strided copy), the net on the whole batch, k_yuv_pack
-        of the n centre frames, one download; the previous batch's frames are written while this one runs.  Every
-        buffer is made once (the output side when the first batch has shown the net's output size).  tile and
-        self_ensemble are refused, as VESPCN.check_flags refuses them."""
-        import contextlib
-        import sys
-        import time
-        from . import data
-        if isinstance(dst, (str, os.PathLike)) and os.fspath(dst) == '-':
-            with contextlib.redirect_stdout(sys.stderr):
-                return self.test_video(src, sys.stdout.buffer, batch, tile, tile_batch, self_ensemble)
-        if _option(self.args, 'tile', tile) is not None or self._self_ensemble(self_ensemble):
+    def _video_net(self, tile, tile_batch, ens):
+        """The [n,3,C,H,W] windows of the unpacked slot (one strided copy) through the net; tile and self_ensemble are
+        refused, as check_flags refuses them."""
+        if ens or tile is not None:
             raise ValueError("test_video: VESPCN runs its frames in one pass, without --tile and --self_ensemble")
-        self._ensure_model()
-        n_max = int(_option(self.args, 'video_batch', batch, 8))
-        if n_max <= 0:
-            raise ValueError("test_video: batch must be positive (got %d)" % n_max)
-        if dst is None:
-            dst = os.path.join(self.save_dir, 'test_result', 'SR_result.y4m')
-        slots = self.VIDEO_SLOTS
-        reader = data.Y4MReader(src)
-        lay = reader.layout
-        pin_in = [torch.empty((n_max + 2, lay.frame_bytes), dtype=torch.uint8, pin_memory=True) for _ in range(slots)]
-        dev_in = [torch.empty((n_max + 2, lay.frame_bytes), dtype=torch.uint8, device=self.device) for _ in range(slots)]
-        ev_up = [torch.cuda.Event() for _ in range(slots)]
-        ev_down = [torch.cuda.Event() for _ in range(slots)]
-        pin_out = dev_out = out_lay = writer = None
-        trace = getattr(self, 'video_trace', None)
-        pending = None                      # (output slot, frames) downloaded but not written yet
-        frames_done, b, kprev, first = 0, 0, 0, True
-        t0 = time.perf_counter()
-        try:
-            while True:
-                i = b % slots
-                ev_up[i].synchronize()      # its last upload has left the pinned buffer
-                k = reader.read_into(pin_in[i][2:2 + n_max], n_max)
-                last = k < n_max
-                video_window_fill(pin_in[i], pin_in[(b - 1) % slots], k, kprev, first, last)
-                m, lo, n = video_window(k, first, last)
-                if n:
-                    dev_in[i][:m].copy_(pin_in[i][:m], non_blocking=True)
-                    ev_up[i].record()
-                    x = ops.yuv_unpack(dev_in[i][:m], lay, self.num_channels)
-                    win = torch.stack([x[lo - 1:lo - 1 + n], x[lo:lo + n], x[lo + 1:lo + 1 + n]], 1)
-                    y = self._net(win)
-                    if y.dim() != 4 or int(y.shape[0]) != n or int(y.shape[1]) != self.num_channels:
-                        raise RuntimeError("test_video: the net returned %s for %d windows of %d channel(s)"
-                                           % (tuple(y.shape), n, self.num_channels))
-                    if out_lay is None:
-                        out_lay = ops.yuv_layout(int(y.shape[-1]), int(y.shape[-2]), lay.sub,
-                                                 "the net's output for a %s stream" % (reader.header.chroma_tag or "C420jpeg"))
-                        writer = data.Y4MWriter(dst, reader.header.scaled(out_lay.W, out_lay.H))
-                        pin_out = [torch.empty((n_max + 1, out_lay.frame_bytes), dtype=torch.uint8, pin_memory=True) for _ in range(slots)]
-                        dev_out = [torch.empty((n_max + 1, out_lay.frame_bytes), dtype=torch.uint8, device=self.device) for _ in range(slots)]
-                    o = b % slots            # (its last download was written out during the previous batch)
-                    self._video_pack(y, dev_in[i][lo:lo + n], lay, out_lay, dev_out[o][:n])
-                    pin_out[o][:n].copy_(dev_out[o][:n], non_blocking=True)
-                    ev_down[o].record()
-                    del x, win, y
-                if trace is not None:
-                    trace.append(torch.cuda.memory_allocated(self.device))
-                if pending is not None:      # the previous batch's frames go out while this batch runs
-                    ev_down[pending[0]].synchronize()
-                    writer.write(pin_out[pending[0]], pending[1])
-                    frames_done += pending[1]
-                pending = (b % slots, n) if n else None
-                kprev, first, b = k, False, b + 1
-                if last:
-                    break
-            if pending is not None:
-                ev_down[pending[0]].synchronize()
-                writer.write(pin_out[pending[0]], pending[1])
-                frames_done += pending[1]
-        finally:
-            torch.cuda.current_stream().synchronize()
-            reader.close()
-            if writer is not None:
-                writer.close()
-        dt = time.perf_counter() - t0
-        print('Video: %d frames -> %d x %d (%s), %.1f frames/s' % (frames_done, out_lay.W, out_lay.H, lay.sub, frames_done / dt))
-        return frames_done
+        return lambda x, lo, n: self._net(torch.stack([x[lo - 1:lo - 1 + n], x[lo:lo + n], x[lo + 1:lo + 1 + n]], 1))
 
 
 TRAINERS = {"SRCNN": SRCNN, "VDSR": VDSR, "ESPCN": ESPCN, "FSRCNN": FSRCNN, "SRGAN": SRGAN, "LapSRN": LapSRN, "EDSR": EDSR,

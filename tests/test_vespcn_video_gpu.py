@@ -1,7 +1,10 @@
 """VESPCN's test_video on the device: frame t from frames (max(t-1, 0), t, min(t+1, T-1)), as many frames out as in, bytes
 equal to tests/vespcn_ref.py's packing of the net's own fp32 output for the same batches, nothing allocated after the
-first batch; and the picture models still take the existing path."""
+first batch, at batch 3 and at batches where the first read yields nothing, the stream is an exact multiple and one short
+read is all; the carries under a reader thread that waits for a pipe."""
 import io
+import os
+import threading
 
 import numpy as np
 import pytest
@@ -41,20 +44,16 @@ def clip(kind, frames, seed=1):
     return R.stream(tokens, data), tokens, sub, data
 
 
-@pytest.mark.parametrize("channels", [1, 3])
-@pytest.mark.parametrize("kind", ["420", "mono"])
-@pytest.mark.parametrize("frames", [7, 6, 1])      # first, middle and short windows; the empty final read; one frame
-def test_video_equals_the_restatement(gpu, tmp_path_factory, kind, frames, channels):
-    t = trainer(channels, gpu, tmp_path_factory)
+def check_restatement(t, gpu, kind, frames, channels, batch):
     data, tokens, sub, raw = clip(kind, frames)
     out = io.BytesIO()
     t.video_trace = seen = []
     try:
-        assert t.test_video(io.BytesIO(data), out, batch=3) == frames
+        assert t.test_video(io.BytesIO(data), out, batch=batch) == frames
     finally:
         t.video_trace = None
     with torch.no_grad():
-        want, (OW, OH) = V.packed_video(lambda w: t.model(w), raw, 24, 16, sub, channels, 3, gpu)
+        want, (OW, OH) = V.packed_video(lambda w: t.model(w), raw, 24, 16, sub, channels, batch, gpu)
     assert (OW, OH) == (2 * (24 - 8), 2 * (16 - 8))
     out_tokens = " ".join(("W%d" % OW) if k[0] == "W" else ("H%d" % OH) if k[0] == "H" else k for k in tokens.split())
     want = R.stream(out_tokens, want)
@@ -63,7 +62,46 @@ def test_video_equals_the_restatement(gpu, tmp_path_factory, kind, frames, chann
     assert len(R.parse(got)[4]) == frames and len(got) == len(want)       # as many frames as the input's
     diff = np.frombuffer(got, np.uint8) != np.frombuffer(want, np.uint8)
     assert not diff.any(), "%d of %d bytes differ, first at %d" % (diff.sum(), diff.size, int(np.argmax(diff)))
-    assert len(seen) == len(V.output_batches(frames, 3))
+    assert len(seen) == len(V.output_batches(frames, batch))
+
+
+@pytest.mark.parametrize("channels", [1, 3])
+@pytest.mark.parametrize("kind", ["420", "mono"])
+@pytest.mark.parametrize("frames", [7, 6, 1])      # first, middle and short windows; the empty final read; one frame
+def test_video_equals_the_restatement(gpu, tmp_path_factory, kind, frames, channels):
+    check_restatement(trainer(channels, gpu, tmp_path_factory), gpu, kind, frames, channels, 3)
+
+
+@pytest.mark.parametrize("channels", [1, 3])
+@pytest.mark.parametrize("kind", ["420", "mono"])
+@pytest.mark.parametrize("batch,frames", [(1, 3),      # the first batch yields no output; the flushing empty read
+                                          (2, 4),      # an exact multiple
+                                          (8, 4)])     # a single short read
+def test_video_equals_the_restatement_at_other_batches(gpu, tmp_path_factory, kind, batch, frames, channels):
+    check_restatement(trainer(channels, gpu, tmp_path_factory), gpu, kind, frames, channels, batch)
+
+
+def test_video_from_a_slow_pipe_gives_the_same_bytes(gpu, tmp_path_factory):
+    """Seven frames at batch 3 through an os.pipe in 777-byte pieces: the carries under a reader thread that waits for
+    its source."""
+    t = trainer(1, gpu, tmp_path_factory)
+    data = clip("420", 7)[0]
+    want = io.BytesIO()
+    assert t.test_video(io.BytesIO(data), want, batch=3) == 7
+    rd, wr = os.pipe()
+
+    def feed():
+        with os.fdopen(wr, "wb") as f:
+            for i in range(0, len(data), 777):
+                f.write(data[i:i + 777])
+                f.flush()
+    th = threading.Thread(target=feed)
+    th.start()
+    sink = io.BytesIO()
+    with os.fdopen(rd, "rb") as pipe:
+        assert t.test_video(pipe, sink, batch=3) == 7
+    th.join()
+    assert sink.getvalue() == want.getvalue()
 
 
 def test_video_allocates_nothing_after_the_first_batch(gpu, tmp_path_factory):
